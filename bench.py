@@ -5,12 +5,16 @@ One "step" = one pass of the hot path over one batch of synthetic input: G x B c
 detect + 1 s PCM VAD/ASR, when those streams are enabled) + 64-token prompt prefill + 128-token greedy Mistral-7B Q4_K_M decode.
 G x B is stated in config (the weight stream is shared by the cycles decoded together).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 For N > 1 the driver launches one rank per GPU with torch.distributed.run; by default ranks are independent replicas of the cycle
 batch (no data-path collective, weak scaling); --placement model-per-gpu gives the LLM and the perception streams their own GPUs
 (SURVEY.md §8e).  Prints ONE JSON line on rank 0.
 
-What the line carries besides the contract keys (all measured live in this run, rank 0, N = 1):
+A plain run sets up, warms up, times the K steps and prints the headline with what those steps measured (decode / prefill times, the
+whole-step HBM view, perception times).  --dump-outputs DIR also writes what the last timed step computed (CycleBench.outputs: token ids,
+detections, ASR ids, VAD events) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+What --full adds to the line (all measured live in this run, rank 0; everything but the roofline objects at N = 1 only):
   roofline            the W4A8 launch set of one decode step at the headline's rows per pass: WEIGHT bytes / sum of launch times / 8 TB/s
                       (SURVEY.md §8d), HIP events on the session stream; `traffic` = PMC HBM bytes per launch from profiles/ when that
                       file was produced from THIS kernel source (sha stamp), else null
@@ -101,19 +105,22 @@ class CycleBench:
 
     def _vision_pass(self):  # one frame per concurrent cycle, PB frames per detector call
         t = time.time()
-        n = 0
+        dets = []
         for i in range(0, self.G * self.B, self.PB):
-            n += sum(len(r) for r in self.det.detect_batch(self.frames[i:i + self.PB]))
-        self.n_dets = n
+            dets += self.det.detect_batch(self.frames[i:i + self.PB])
+        self.dets = dets
+        self.n_dets = sum(len(r) for r in dets)
         self.perc_ms["vision"].append(1000 * (time.time() - t))
 
     def _audio_pass(self):  # one second of PCM per concurrent cycle
         t = time.time()
+        events = []
         for b in range(self.G * self.B):
             self.vad.reset()
-            self.vad.process_with_events(self.pcm[b])
-        for i in range(0, self.G * self.B, self.PB):
-            self.asr.transcribe_tokens(self.pcm[i:i + self.PB], self.asr_steps, want_aux=False)
+            events.append(self.vad.process_with_events(self.pcm[b]))
+        self.vad_events = events
+        self.asr_tokens = [self.asr.transcribe_tokens(self.pcm[i:i + self.PB], self.asr_steps, want_aux=False)[0]
+                           for i in range(0, self.G * self.B, self.PB)]
         self.perc_ms["audio"].append(1000 * (time.time() - t))
 
     def perception_async(self):
@@ -134,10 +141,10 @@ class CycleBench:
 
         def llm_group(g):
             t_a = time.time()
-            self.sessions[g].prefill(self.prompts[g])
+            first = self.sessions[g].prefill(self.prompts[g])
             t_b = time.time()
             toks, ms_step = self.sessions[g].decode(self.B, self.N)
-            res[g] = (toks, t_b - t_a, time.time() - t_b, ms_step)
+            res[g] = (toks, t_b - t_a, time.time() - t_b, ms_step, first)
 
         lt = [threading.Thread(target=llm_group, args=(g,)) for g in range(1, self.G)]
         for t in lt:
@@ -146,6 +153,7 @@ class CycleBench:
             llm_group(0)
         for t in lt + th:
             t.join()
+        self.llm_out = [(r[4], r[0]) for r in res]
         if not self.G:
             return None, 0.0, 0.0, 0.0
         return res[0][0], float(np.mean([r[1] for r in res])), float(np.mean([r[2] for r in res])), float(np.mean([r[3] for r in res]))
@@ -179,11 +187,41 @@ class CycleBench:
         elapsed = time.time() - t0
         return {"elapsed": elapsed, "prefill_s": pre_s / max(steps, 1), "decode_s": dec_s / max(steps, 1), "decode_ms_per_step": float(np.mean(ms_steps)) if ms_steps else 0.0}
 
+    def outputs(self):
+        """what the last step handed its callers, as float64 arrays: per decode group and sequence the prefill's token and the N greedy
+        tokens after it; with the perception streams, every frame's detections, every clip's forced ASR ids and its VAD events"""
+        out = {"llm_tokens": np.stack([np.concatenate([first[None], toks]).T for first, toks in self.llm_out])}  # [G, B, N + 1]
+        if self.fused:
+            # one row per detection: frame, class id, confidence, box x, y, w, h
+            out["detections"] = np.array([(f, c, conf, *box) for f, r in enumerate(self.dets) for c, _, conf, box in r], np.float64).reshape(-1, 7)
+            out["asr_tokens"] = np.concatenate(self.asr_tokens)  # [G * B, asr_steps]
+            ev = np.full((len(self.vad_events), max(map(len, self.vad_events), default=0)), -1)  # [G * B, most events of a clip], -1 = none
+            for i, e in enumerate(self.vad_events):
+                ev[i, :len(e)] = e
+            out["vad_events"] = ev
+        return {k: np.asarray(v, np.float64) for k, v in out.items()}
+
     def close(self):
         for s in self.sessions:
             s.close()
         if self.fused:
             self.det.close(); self.asr.close(); self.vad.close()
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """<path>/<name>.npy for every array; one larger than its share of DUMP_BYTES is cut into rows along its last
+    axis and keeps a fixed, seeded sample of them"""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            a = a.reshape(-1, a.shape[-1])
+            rows = max(1, share // (a.itemsize * a.shape[1]))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def weight_bytes_per_shape(hp):
@@ -661,8 +699,12 @@ def main():
     ap.add_argument("--prompt", type=int, default=64)
     ap.add_argument("--decode", type=int, default=128)
     ap.add_argument("--layers", type=int, default=32, help="debug only: fewer layers => result marked invalid")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: skip north_star_point, reference_abi_b1 and cpu_baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline objects (isolated launch-set timings) and, on one GPU with 32 layers, the extras "
+                         "(north_star_point, reference_abi_*, prompt_processing, long_context_decode, perception_fast_contraction, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave cpu_baseline out")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: the roofline objects only, no extras")
     ap.add_argument("--sessions", type=int, default=3,
                     help="independent decode groups of --batch cycles run concurrently on their own HIP streams (fills the "
                          "launch/ramp bubbles of one group with another group's kernels); concurrent cycles = sessions * batch")
@@ -692,6 +734,8 @@ def main():
                     help="f16: BASELINE configs[4]'s fp16 checkpoint (14.2 GB of weights per decode step) on the exact fp32 MFMA GEMM; LLM stream only, "
                          "no W4A8 roofline object (other kernels)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.pipeline or args.placement != "replicas" or args.roofline_only or args.steps < 1):
+        ap.error("--dump-outputs needs timed steps of the replicas path")
     if args.fast_perception:
         os.environ["TK_BENCH_FAST_PERCEPTION"] = "1"
 
@@ -750,6 +794,8 @@ def main():
     elapsed = r["elapsed"] if r else 0.0
     if dist is not None and r:
         elapsed = D.max_over_ranks(dist, elapsed, cuda=COLL_CUDA)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cb.outputs())
     if rank != 0:
         cb.close()
         if dist is not None:
@@ -773,8 +819,9 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
-    roofline = gemv_roofline(sess, hp, B, model.weight_bytes)
-    roofline_att = attention_roofline(sess, hp, B, min(P + N // 2, P + N))
+    if args.full or args.roofline_only:  # launch-set timings of their own, after the timed steps
+        roofline = gemv_roofline(sess, hp, B, model.weight_bytes)
+        roofline_att = attention_roofline(sess, hp, B, min(P + N // 2, P + N))
     if args.roofline_only:
         r16 = gemv_roofline(sess, hp, 16, model.weight_bytes) if B != 16 else roofline
         print(json.dumps({"metric": METRIC, "value": None, "unit": "cycles/s", "n_gpus": world, "note": "roofline-only run: no timed steps",
@@ -797,7 +844,7 @@ def main():
         "llm_tok_per_s": round(G * B * world * N / r["decode_s"], 1),
         "decode_ms_per_step": round(dec_ms, 4), "prefill_s_per_cycle_batch": round(r["prefill_s"], 4),
         "model_load_s": round(t_load, 2), "weight_bytes_per_decode_step": int(model.weight_bytes),
-        "roofline": roofline, "roofline_attention": roofline_att,
+        **({"roofline": roofline, "roofline_attention": roofline_att} if args.full else {}),
         # SURVEY.md 8d's whole-step view: (weights + B * 128 KiB * mean context of KV per row) per decode step over 8 TB/s, all groups in flight
         "llm_decode_step_roofline": {"bytes_per_step": int(model.weight_bytes + kv_step), "steps_per_s": round(G * 1000.0 / dec_ms, 1),
                                      "frac": round((model.weight_bytes + kv_step) * (G * 1000.0 / dec_ms) / (HBM_PEAK_GBS * 1e9), 4)},
@@ -812,7 +859,7 @@ def main():
         out["invalid"] = "debug run with fewer layers"
     if not COLL_CUDA:
         out["rehearsal"] = "TK_BENCH_SHARE_GPU=1: all ranks share ONE GPU; not a scaling measurement"
-    extras = not args.no_extras and args.layers == 32 and world == 1
+    extras = args.full and not args.no_extras and args.layers == 32 and world == 1
     roof16 = None
     if extras and not (G == 3 and B == 16):
         # ---- the configuration that meets north_star's two conditions together: 3 groups x 16 rows per pass (every group streams the

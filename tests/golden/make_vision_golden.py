@@ -4,6 +4,9 @@
                            (/root/reference/src/vision/tk_image_preprocessor.c via oracle/_ref) on seeded frames,
                            plus sha256 of its output on the BASELINE-size frames (640x480 -> 640x640, 640x640 -> 640x640,
                            and the reference test's gray-128 frame, tests/tk_cortex_test.cpp:79-84).
+  compiled_reference_answers.json
+                         — answers of the COMPILED reference pre-processor and attribute classifiers (oracle/_ref) on seeded
+                           frames and boxes, with the sha256 of every input (the tests compare against these, no reference tree).
   yolo_tiny.npz          — YOLOv8n raw head maps on a 64x64 input from an INDEPENDENT torch implementation of the
                            published Ultralytics graph, fed with the oracle's synthetic weights.
 """
@@ -370,11 +373,71 @@ def make_attribute_vectors():
         print(name, "->", color, door, "(reference test expects", j[name]["reference_test_expects"], ")")
 
 
+def preprocess_cases():
+    """(frame, target width, target height): odd sizes, the BASELINE 640x480 -> 640x640, an upscale to a non-square target"""
+    rng = np.random.default_rng(9)
+    return [(rng.integers(0, 256, (h, w, 3), dtype=np.uint8), tw, th) for (w, h, tw, th) in ((50, 40, 32, 32), (640, 480, 640, 640), (33, 17, 64, 96))]
+
+
+def attribute_cases():
+    """frames and boxes of the box-attribute comparison: a random frame, saturated primaries, grays, a striped door, a low-saturation frame;
+    per frame whole / corner / quarter / inset boxes and six random small ones.  Returns [(frame, [boxes])]."""
+    rng = np.random.default_rng(2)
+    frames = [rng.integers(0, 256, (48, 64, 3), dtype=np.uint8)]
+    prim = np.zeros((40, 72, 3), np.uint8)
+    for i, c in enumerate([(255, 0, 0), (255, 255, 0), (0, 255, 0), (0, 255, 255), (0, 0, 255), (255, 0, 255), (0, 0, 0), (255, 255, 255), (128, 128, 128)]):
+        prim[:, 8 * i:8 * i + 8] = c
+    frames.append(prim)
+    stripes = np.full((60, 60, 3), 30, np.uint8)
+    stripes[0::4] = 220
+    stripes[1::4] = 220                                   # two bright rows, two dark rows: the rows above and below always differ by 190
+    frames.append(stripes)
+    frames.append((rng.integers(0, 4, (50, 50, 1)) * 60 + rng.integers(0, 20, (50, 50, 3))).astype(np.uint8))  # low saturation
+    out = []
+    for f in frames:
+        H, W = f.shape[:2]
+        boxes = [(0, 0, W, H), (3, 2, 9, 7), (W // 2, H // 2, W // 2, H // 2), (1, 1, W - 2, H - 2)]
+        boxes += [tuple(int(v) for v in (rng.integers(1, W - 8), rng.integers(1, H - 8), rng.integers(3, 8), rng.integers(3, 8))) for _ in range(6)]
+        out.append((f, boxes))
+    return out
+
+
+def outside_box(frame):
+    """a box partly outside the frame: only its colour is compared (the reference's door loop has no bounds check; its colour loop skips)"""
+    H, W = frame.shape[:2]
+    return (W - 6, H - 6, 12, 12)
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def make_reference_answers():
+    """compiled_reference_answers.json: what the COMPILED reference (oracle/_ref) answers on preprocess_cases(), attribute_cases() and
+    attribute_vector_frames(), with the sha256 of every input, so that the tests need no reference tree"""
+    import json
+    assert O.have_ref(), "build oracle/_ref first (make -C oracle ref)"
+    pre = [{"input_sha256": sha(f), "target": [tw, th], "output_sha256": sha(O.ref_preprocess(f, tw, th))} for f, tw, th in preprocess_cases()]
+    attrs = []
+    for f, boxes in attribute_cases():
+        H, W = f.shape[:2]
+        big = np.zeros((H + 16, W, 3), np.uint8)
+        big[:H] = f                  # the reference's door loop reads rows past the box: give it memory to read
+        attrs.append({"frame_sha256": sha(f), "boxes": [list(b) for b in boxes], "answers": [list(O.ref_attributes(f, b)) for b in boxes],
+                      "outside_box": list(outside_box(f)), "outside_color": O.ref_attributes(big[:H], outside_box(f))[0]})
+    vec = {name: {"frame_sha256": sha(f), "bbox": list(b), "answer": list(O.ref_attributes(f, b))} for name, (f, b) in attribute_vector_frames().items()}
+    with open(os.path.join(HERE, "compiled_reference_answers.json"), "w") as fh:
+        json.dump({"_comment": "answers of the reference's pre-processor and attribute classifiers compiled from its own sources (oracle/_ref); "
+                               "regenerate with tests/golden/make_vision_golden.py", "preprocess": pre, "attributes": attrs, "attribute_vectors": vec}, fh, indent=1)
+    print("wrote compiled_reference_answers.json")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "yolo5":
         make_yolo5()
         sys.exit(0)
     make_attribute_vectors()
+    make_reference_answers()
     make_preprocess()
     make_yolo()
     make_yolo_full()

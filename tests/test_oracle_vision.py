@@ -1,16 +1,16 @@
 """CPU: detector-stream oracle against its pins (compiled reference pre-processor, torch YOLOv8n fixture)."""
 import hashlib
+import json
 import os
 import sys
 
 import numpy as np
-import pytest
 
 import oracle_lib as O
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 sys.path.insert(0, GOLD)
-from make_vision_golden import frames  # noqa: E402  (seeded frame generator only; no reference code)
+from make_vision_golden import attribute_vector_frames, frames, preprocess_cases, sha  # noqa: E402  (seeded inputs only; no reference code)
 
 
 def test_preprocess_restatement_matches_compiled_reference_fixture():
@@ -23,12 +23,15 @@ def test_preprocess_restatement_matches_compiled_reference_fixture():
         assert hashlib.sha256(y.tobytes()).digest() == g["sha_" + name].tobytes(), name
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 def test_preprocess_against_live_compiled_reference():
-    rng = np.random.default_rng(9)
-    for (w, h, tw, th) in ((50, 40, 32, 32), (640, 480, 640, 640), (33, 17, 64, 96)):
-        f = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-        assert np.array_equal(O.preprocess(f, tw, th).view(np.uint32), O.ref_preprocess(f, tw, th).view(np.uint32))
+    """bit for bit against the compiled reference on three more frames: its answers were recorded from oracle/_ref with the sha256 of
+    every input (tests/golden/compiled_reference_answers.json, make_vision_golden.py make_reference_answers)"""
+    want = json.load(open(os.path.join(GOLD, "compiled_reference_answers.json")))["preprocess"]
+    cases = preprocess_cases()
+    assert len(cases) == len(want) == 3
+    for (f, tw, th), a in zip(cases, want):
+        assert sha(f) == a["input_sha256"] and [tw, th] == a["target"]
+        assert sha(O.preprocess(f, tw, th)) == a["output_sha256"], (f.shape, tw, th)
 
 
 def test_preprocess_is_not_identity_and_honours_stride():
@@ -78,13 +81,16 @@ def test_yolo_post_matches_independent_torch_detections():
     assert np.abs(boxes - g["torch_boxes"]).max() < 1e-3
 
 
-@pytest.mark.skipif(not O.have_ref() or not os.path.exists(os.path.join(O.ROOT, "oracle", "_ref", "libtkref_attr.so")), reason="compiled reference not built")
 def test_attribute_vectors_fixture_is_what_the_compiled_reference_answers():
-    import json
-    from make_vision_golden import attribute_vector_frames
+    """attribute_vectors.json (hand-written data) against the compiled reference classifiers' answers, recorded from oracle/_ref on exactly
+    these frames (tests/golden/compiled_reference_answers.json: sha256 of each frame)"""
     j = json.load(open(os.path.join(GOLD, "attribute_vectors.json")))
-    for name, (frame, box) in attribute_vector_frames().items():
-        color, door = O.ref_attributes(frame, box)
+    ref = json.load(open(os.path.join(GOLD, "compiled_reference_answers.json")))["attribute_vectors"]
+    fr = attribute_vector_frames()
+    assert set(fr) == set(ref) == {"red_frame", "door_frame"}
+    for name, (frame, box) in fr.items():
+        assert sha(frame) == ref[name]["frame_sha256"] and list(box) == ref[name]["bbox"] == j[name]["bbox"]
+        color, door = ref[name]["answer"]
         assert j[name]["compiled_reference"] == {"color": color, "door": door}
 
 

@@ -149,31 +149,22 @@ def test_detector_full_frame_path_and_batch(gpu):
     assert det.detect(fr[0]) == []                                            # empty result set
 
 
-@pytest.mark.skipif(not O.have_ref() or not os.path.exists(os.path.join(O.ROOT, "oracle", "_ref", "libtkref_attr.so")), reason="compiled reference not built")
 def test_box_attributes_equal_the_compiled_reference(gpu):
     """tk_classify_dominant_color / tk_classify_door_state on the GPU against the reference's own C compiled from its sources:
-    random frames and boxes (also partly outside the frame for the colour histogram), saturated primaries, grays, a striped door"""
-    rng = np.random.default_rng(2)
-    frames = [rng.integers(0, 256, (48, 64, 3), dtype=np.uint8)]
-    prim = np.zeros((40, 72, 3), np.uint8)
-    for i, c in enumerate([(255, 0, 0), (255, 255, 0), (0, 255, 0), (0, 255, 255), (0, 0, 255), (255, 0, 255), (0, 0, 0), (255, 255, 255), (128, 128, 128)]):
-        prim[:, 8 * i:8 * i + 8] = c
-    frames.append(prim)
-    stripes = np.full((60, 60, 3), 30, np.uint8)
-    stripes[0::4] = 220
-    stripes[1::4] = 220                                   # two bright rows, two dark rows: the rows above and below always differ by 190
-    frames.append(stripes)
-    frames.append((rng.integers(0, 4, (50, 50, 1)) * 60 + rng.integers(0, 20, (50, 50, 3))).astype(np.uint8))  # low saturation
-    for f in frames:
-        H, W = f.shape[:2]
-        boxes = [(0, 0, W, H), (3, 2, 9, 7), (W // 2, H // 2, W // 2, H // 2), (1, 1, W - 2, H - 2)]
-        boxes += [tuple(int(v) for v in (rng.integers(1, W - 8), rng.integers(1, H - 8), rng.integers(3, 8), rng.integers(3, 8))) for _ in range(6)]
-        for b in boxes:
-            assert gpu.classify_attributes(f, b) == O.ref_attributes(f, b), (f.shape, b)
-        b = (W - 6, H - 6, 12, 12)   # partly outside: colour only (the reference's door loop has no bounds check; its colour loop skips)
-        big = np.zeros((H + 16, W, 3), np.uint8)
-        big[:H] = f                  # the reference's door loop reads rows past the box: give it memory to read
-        assert gpu.classify_attributes(f, b)[0] == O.ref_attributes(big[:H], b)[0]
+    random frames and boxes (also partly outside the frame for the colour histogram), saturated primaries, grays, a striped door.
+    The compiled reference's answers were recorded from oracle/_ref with the sha256 of every frame (tests/golden/compiled_reference_answers.json)."""
+    import json
+    from make_vision_golden import attribute_cases, outside_box, sha
+    want = json.load(open(os.path.join(GOLD, "compiled_reference_answers.json")))["attributes"]
+    cases = attribute_cases()
+    assert len(cases) == len(want) == 4
+    for (f, boxes), w in zip(cases, want):
+        assert sha(f) == w["frame_sha256"] and [list(b) for b in boxes] == w["boxes"]
+        for b, ans in zip(boxes, w["answers"]):
+            assert list(gpu.classify_attributes(f, b)) == ans, (f.shape, b)
+        assert list(outside_box(f)) == w["outside_box"]
+        assert gpu.classify_attributes(f, outside_box(f))[0] == w["outside_color"]   # partly outside: colour only
+    prim, stripes = cases[1][0], cases[2][0]
     for i, name in enumerate(["red", "yellow", "green", "cyan", "blue", "magenta", "black", "white", "gray"]):
         assert gpu.classify_attributes(prim, (8 * i, 0, 8, 40))[0] == name
     assert gpu.classify_attributes(stripes, (5, 5, 40, 40))[1] == "closed"

@@ -5,7 +5,7 @@
 #      interceptor walks a multi-packet submission linearly and runs off the end of the 16384-packet AQL ring when a hipGraphLaunch
 #      batch straddles it (profiles/r03_rocprofv3_hipgraph_crash_symbolised.txt), so the ring is made large enough never to wrap inside a
 #      profiled run (ROC_AQL_QUEUE_SIZE)
-#   3. the default bench.py line (unprofiled)
+#   3. the bench.py --full line (unprofiled)
 # Everything lands under gpurun_out/; copy what should be judged into profiles/.
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
@@ -51,12 +51,12 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/k
 cp "$(find /tmp/kt_rl -name '*kernel_stats.csv' | head -1)" $O/${R}_roofline_only_kernel_stats.csv
 python3 tools/roofline_check.py "$(find /tmp/kt_rl -name '*kernel_trace.csv' | head -1)" $O/${R}_roofline_only_run.json > $O/${R}_roofline_check.txt 2>&1; tail -12 $O/${R}_roofline_check.txt
 rm -rf /tmp/kt_f
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_f -o f -- python3 bench.py --steps 1 --warmup 1 --no-extras > $O/${R}_fused_3x256_rocprof_run.json 2> $O/${R}_fused_rocprof.err || { echo "fused trace failed"; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_f -o f -- python3 bench.py --steps 1 --warmup 1 --full --no-extras > $O/${R}_fused_3x256_rocprof_run.json 2> $O/${R}_fused_rocprof.err || { echo "fused trace failed"; exit 1; }
 cp "$(find /tmp/kt_f -name '*kernel_stats.csv' | head -1)" $O/${R}_fused_3x256_kernel_stats.csv
 check_budget "$(find /tmp/kt_f -name '*kernel_trace.csv' | head -1)"
 for B in 256 16; do
   rm -rf /tmp/kt_b
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_b -o b -- python3 bench.py --llm-only --batch $B --sessions 1 --steps 1 --warmup 1 --no-extras > $O/${R}_llm_b${B}_solo_run.json 2> $O/${R}_llm_b${B}_solo.err || { echo "solo trace $B failed"; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_b -o b -- python3 bench.py --llm-only --batch $B --sessions 1 --steps 1 --warmup 1 --full --no-extras > $O/${R}_llm_b${B}_solo_run.json 2> $O/${R}_llm_b${B}_solo.err || { echo "solo trace $B failed"; exit 1; }
   cp "$(find /tmp/kt_b -name '*kernel_stats.csv' | head -1)" $O/${R}_llm_b${B}_solo_kernel_stats.csv
 done
 # one runner through the reference entry points (tools/time_b1.py), the norm / SwiGLU producers inside the mat-vec launches (shipped) and as launches of their own
@@ -70,4 +70,4 @@ done
 echo "traces done"
 unset ROC_AQL_QUEUE_SIZE
 for NF in 0 1 0 1; do TK_MI355X_NO_FUSE=$NF python3 tools/time_b1.py >> $O/${R}_b1_runner.txt 2>&1; done; cat $O/${R}_b1_runner.txt
-timeout -k 10 900 python3 bench.py > $O/${R}_bench_default.json 2> $O/${R}_bench_default.err; echo "bench rc=$?"; tail -c 1500 $O/${R}_bench_default.json
+timeout -k 10 900 python3 bench.py --full > $O/${R}_bench_default.json 2> $O/${R}_bench_default.err; echo "bench rc=$?"; tail -c 1500 $O/${R}_bench_default.json
