@@ -4,10 +4,10 @@ rows past slot 0, against the oracle, logits BIT FOR BIT.  Which kernel a pass t
 copy of its rule; on an MI355X (256 CUs):
 
   1, 2, 16 rows   k_attention_narrow                  (one runner; the north-star point's decode passes: <= one workgroup per CU)
-  32 rows         k_attention<2, fused, 128, 64, 2>   (17 .. 63-row passes)
-  64 rows         k_attention<4, fused, 128, 64, 2>
-  256 rows        k_attention<4, fused, 128, 32, 2>   (the headline bench's decode passes)
-  256 rows        k_attention<4, not fused, 128, 32, 2>  (prefill-shaped: several positions of one sequence in a pass, k_qkv_rope_append first)
+  32 rows         k_attention<2, fused, 128, 64>   (17 .. 63-row passes)
+  64 rows         k_attention<4, fused, 128, 64>
+  256 rows        k_attention<4, fused, 128, 32>   (the headline bench's decode passes)
+  256 rows        k_attention<4, not fused, 128, 32>  (prefill-shaped: several positions of one sequence in a pass, k_qkv_rope_append first)
 
 and, with the reference's context window (n_ctx 4096, /root/reference/src/ai_models/tk_runner_lifecycle.c:48; a 2048-token prompt budget,
 /root/reference/src/cortex/tk_cortex_main.c:1334), decode steps and a prefill chunk at 2047 .. 4000 cached positions.

@@ -135,7 +135,7 @@ private:
      * (a prompt's last chunk) */
     hipGraphExec_t graph_prefill[2][TK_MAX_ROWS + 1] = {};
     hipGraphExec_t graph_head_nf[2][TK_MAX_ROWS + 1] = {};
-    /* set by whoever describes a pass, read by enqueue_range: a multi-position pass that reaches position TK_TILED_ATT_MIN_POS or beyond takes
+    /* set by whoever describes a pass, read by enqueue_range: a multi-position pass that reaches position 128 (TK_TILED_ATT_FROM_POS) or beyond takes
      * k_attention_prefill (16 rows of a sequence per workgroup), shorter contexts k_attention's per-row form (3 us per launch quicker below ~128
      * positions, profiles/r05_prefill_attention.txt); the two are bit-identical, so the choice never shows in a result */
     bool tiled_pass = false;

@@ -501,16 +501,14 @@ static bool graphs_enabled() {
  * APIs while this stream records */
 static std::mutex g_capture_mu;
 
-#ifndef TK_TILED_ATT_MIN_POS
-#define TK_TILED_ATT_MIN_POS 128
-#endif
+static constexpr int TK_TILED_ATT_FROM_POS = 128; /* see TkLlmSession::tiled_pass */
 void TkLlmSession::choose_attention(const int32_t* pos, int nrows) {
     int top = 0;
     for (int r = 0; r < nrows; ++r) top = pos[r] > top ? pos[r] : top;
     choose_attention_top(top, nrows);
 }
 void TkLlmSession::choose_attention_top(int top, int nrows) {
-    tiled_pass = top >= TK_TILED_ATT_MIN_POS;
+    tiled_pass = top >= TK_TILED_ATT_FROM_POS;
     long_pass = d_scores != nullptr && nrows <= TK_LONG_ATT_MAX_ROWS && top >= tk_long_att_min_pos(nrows);
 }
 

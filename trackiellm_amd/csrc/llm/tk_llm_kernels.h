@@ -93,7 +93,7 @@ void tk_launch_quant_q8(const float* hbuf, int FF, int nrows, TkActQ8 out, hipSt
 void tk_launch_argmax(const float* logits, int vocab, int nrows, const uint32_t* allow_base, const int32_t* allow_row, TkSampleRow* samp, int32_t* tok,
                       int32_t* pos, int32_t* nsteps, int32_t* hist, int hist_stride, hipStream_t s);
 
-/* the attention launch a pass takes: kernel 0 = k_attention<gq, fused, head_dim, chunk, slots> (chunk = positions per ring slot), kernel 1 =
+/* the attention launch a pass takes: kernel 0 = k_attention<gq, fused, head_dim, chunk> (chunk = positions per ring slot, slots = ring depth 2), kernel 1 =
  * k_attention_narrow (gq 2, chunk = positions resident per chunk, the whole context when it fits) */
 struct TkAttentionPlan { int kernel, gq, chunk, slots; size_t lds_bytes; };
 /* a decode session on `device` came (+1) or went (-1): with more than one alive the plan prefers forms that share a CU with other streams' launches */
@@ -123,7 +123,7 @@ void tk_launch_attention_long(const float* partial, int ks, int n_total, const f
                               float* scores, TkActQ8 out, hipStream_t s);
 size_t tk_gemv_lds_bytes(int K, int ks, int mtiles);
 /* dynamic LDS of one k_attention workgroup; must stay below 160 KiB (the session checks it against its max_ctx) */
-size_t tk_attention_lds_bytes(int gq, int head_dim, int max_ctx, int chunk /* positions per ring slot: 32 or 64 */, int slots = 2 /* ring depth: 2 or 5 */);
+size_t tk_attention_lds_bytes(int gq, int head_dim, int max_ctx, int chunk /* positions per ring slot: 32, 64 or 128 */);
 /* opts every kernel of this file into 160 KiB of dynamic LDS on `device` (which must be the calling thread's current device); idempotent,
  * thread-safe; returns nullptr or an error string.  Sessions call it at creation: launches never change function attributes. */
 const char* tk_llm_prepare_device(int device);

@@ -830,15 +830,14 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
 /* ------------------------------------------------------------------------------------------
  * Batched passes (33..256 rows: prefill chunks, wide decode batches): same work mapping and the same per-row arithmetic as
  * k_gemv_w4a8, but the weight tile is unpacked ONCE and multiplied against MT = 4, 6, 8, 10 or 12 M-tiles (the pass's rows / 16 rounded up to the next
- * instantiation; 14 and 16 exist for the TK_MI355X_G32_FROM=257 A/B against the 32x32x32 kernel), so the dequantisation VALU
- * work and the HBM bytes per row drop by MT.  The K-range's activations no longer fit in LDS, so they stream through a
+ * instantiation), so the dequantisation VALU work and the HBM bytes per row drop by MT.  The K-range's activations no longer fit in LDS, so they stream through a
  * two-slot ring of 256-k blocks (MT x {4 KiB int8 image, 512 B f16 sub-block sums, 64 B scales} each):
  *
- *   every TK_RING_BLOCKS blocks:  s_waitcnt vmcnt(0) -> my DMA pieces of this slot (and my weight tile) have landed
- *                                 barrier            -> everybody's pieces have; everybody is done with the other slot
- *                                 DMA the next TK_RING_BLOCKS blocks into the other slot
- *   every block:                  unpack tile b, request tile b+1 into the same registers, MT x MFMA chains with the LDS operand reads
- *                                 of M-tile m+1 issued before the MFMAs of M-tile m and the fp32 FMAs of m-1 filling the MFMA shadow
+ *   every block:  s_waitcnt vmcnt(0) -> my DMA pieces of this slot (and my weight tile) have landed
+ *                 barrier            -> everybody's pieces have; everybody is done with the other slot
+ *                 DMA the next block into the other slot
+ *                 unpack tile b, request tile b+1 into the same registers, MT x MFMA chains with the LDS operand reads
+ *                 of M-tile m+1 issued before the MFMAs of M-tile m and the fp32 FMAs of m-1 filling the MFMA shadow
  *
  * so a slot's activations have a whole slot time (> 2 us) and the next weight tile a whole block time to arrive.
  * Q6_K tiles are folded like Q4_K ones here: v = scale * (q - 32) (14 bits signed) is split v = 64 vh + vl (vl 0..63,
@@ -910,12 +909,6 @@ __device__ __forceinline__ void lds_tile(ATile& t, const uint8_t* act, const uin
 struct PTile { v4i pl, ph; v4f cm, da; };
 
 #define TK_RING_TILE_BYTES (256 * TK_ROW_SLOTS + 512 + TK_ROW_SLOTS * 4) /* one M-tile of one 256-k block: image + f16 sums + scales */
-#ifndef TK_GEMM_LDS_DEPTH
-#define TK_GEMM_LDS_DEPTH 2
-#endif
-#ifndef TK_RING_BLOCKS
-#define TK_RING_BLOCKS 1 /* 256-k blocks per ring slot (per barrier): 2 slots x 1 block x 16 M-tiles = 138 KiB of the 160 KiB LDS */
-#endif
 
 #define TK_MFMA64 __builtin_amdgcn_mfma_i32_16x16x64_i8
 template <bool Q4>
@@ -937,7 +930,7 @@ template <int MT, int NT, bool Q4>
 __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* chunk, int rot, int lane, float (&acc)[NT][MT][4]) {
     constexpr int OFF_AMN = MT * 4096, OFF_AD = MT * 4096 + MT * 512;
     const v4i zero = {0, 0, 0, 0};
-    constexpr int AD = TK_GEMM_LDS_DEPTH; /* M-tiles of LDS operand reads in flight ahead of the MFMAs */
+    constexpr int AD = 2; /* M-tiles of LDS operand reads in flight ahead of the MFMAs */
     ATile T[AD + 1];
     PTile R[NT];
     /* (m ^ rot) * S = m * S + rot * S for the lower half of the slots, m * S - rot * S for the upper half: two bases, static offsets */
@@ -983,13 +976,15 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
 #undef TK_LDS_TILE
 }
 
-/* NT = weight tiles per wave: 2 (adjacent row tiles, same tensor) when a CU owns enough tiles to keep four such waves busy —
- * the LDS operand stream, the bound of this kernel, is then read once per TWO weight tiles */
-template <int MT, int TYPES, int NT>
-__global__ __launch_bounds__(NT == 2 ? 256 : 512) void k_gemm_w4a8(TkGemvArgs a, int groups, int total_row_tiles) {
+/* One weight tile per wave (two adjacent tiles per wave halve the LDS operand stream but leave one wave per SIMD: 25 % slower on MI355X,
+ * profiles/r01_gemm_batched.txt).  NT and CB are that choice and the ring's one block per slot as constants: the loops over them stay in
+ * the source because folding them by hand changes the compiler's schedule of this kernel (k_gemm_w4a8<12, 3> then spills). */
+template <int MT, int TYPES>
+__global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int total_row_tiles) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    constexpr int NT = 1;                         /* weight tiles per wave */
     constexpr int CH = MT * TK_RING_TILE_BYTES;   /* one block of the ring */
-    constexpr int CB = TK_RING_BLOCKS;            /* blocks per ring slot = per barrier */
+    constexpr int CB = 1;                         /* blocks per ring slot = per barrier */
     constexpr int OFF_AMN = MT * 4096, OFF_AD = MT * 4096 + MT * 512;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1109,7 +1104,7 @@ __global__ __launch_bounds__(NT == 2 ? 256 : 512) void k_gemm_w4a8(TkGemvArgs a,
 
 
 /* ------------------------------------------------------------------------------------------
- * Wide passes (193..256 rows by default, from 129 with TK_MI355X_G32_FROM=129): the same arithmetic on v_mfma_i32_32x32x32_i8.
+ * Wide passes (193..256 rows): the same arithmetic on v_mfma_i32_32x32x32_i8.
  *
  * Why: per (16 rows x 16 weight rows x 256 k) the 16x16x64 formulation above issues 8 int8 MFMAs + 1 f16 MFMA (9 x 8 issue cycles) and four
  * ds_read_b128; the 32x32x32 form does the same multiply-adds with HALF the MFMA issue slots and HALF the LDS operand bytes per MAC (one
@@ -1251,15 +1246,14 @@ __device__ __forceinline__ void load_atile32(ATile32& T, const Ptrs32& p, int t)
 
 /* one 256-k block: this wave's 32 weight rows x its four 32-row M-tiles.  T arrives holding tile 0's operands; the operands of tile
  * t + 1 are requested as soon as the MFMAs of tile t have issued — into the same registers — and land while tile t is finished on the VALU. */
-/* MTW = 32-row M-tiles a workgroup's row range holds: 3 for passes of 129..192 rows (two halves of 96 rows), 4 for 193..256 — a pass of 160
- * rows walks 3 + 3 tiles, not 4 + 4 (round 5: the 129th row cost + 63 %, profiles/r05_width_curve.txt).  A compile-time bound: 48 or 64
- * accumulators and no branch in the loop.  (One tile fewer for the second half of 129..160- and 193..224-row passes as a scalar `break` in the
- * unrolled loop was built too: 108 - 392 bytes of spill per lane at the 256-register budget of two workgroups per CU; not kept.) */
-template <bool Q4, int MTW, typename Hook>
-__device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const Ptrs32& p, float (&acc)[MTW][16], Hook&& after_mfmas) {
+/* The tile count is a compile-time bound: 64 accumulators and no branch in the loop.  (One tile fewer for the second half of 193..224-row
+ * passes as a scalar `break` in the unrolled loop was built: 108 - 392 bytes of spill per lane at the 256-register budget of two workgroups
+ * per CU; not kept.) */
+template <bool Q4, typename Hook>
+__device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const Ptrs32& p, float (&acc)[TK_G32_MTW][16], Hook&& after_mfmas) {
     const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int t = 0; t < MTW; ++t) {
+    for (int t = 0; t < TK_G32_MTW; ++t) {
         /* P = 8 Ph + Pl (64 Ph + Pl for Q6_K) inside ONE accumulator: the high-digit chain first, its result shifted on the VALU, then the
          * low-digit chain on top of it (sixteen live registers fewer than two accumulators, and the finishing below needs no shift-add);
          * the independent min-term MFMA sits where the shift waits for the last high-digit MFMA */
@@ -1285,7 +1279,7 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
 #pragma unroll
         for (int u = 0; u < 8; ++u) pl = TK_MFMA32(A[u], o.bl[u], pl, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        if (t + 1 < MTW) load_atile32<Q4>(T, p, t + 1);
+        if (t + 1 < TK_G32_MTW) load_atile32<Q4>(T, p, t + 1);
         after_mfmas(t); /* a quarter of this wave's ring staging for the next block: LDS-DMA issue costs 60-180 cycles a piece, here they pass while
                          * the tile's MFMAs are still in the matrix pipe */
         __builtin_amdgcn_sched_barrier(0);
@@ -1333,9 +1327,9 @@ __device__ __forceinline__ void g32_unpack(const typename G32Frag<Q4>::type& f0,
 
 
 /* The K loop of one wave: its two weight tiles (32 weight rows) against its four 32-row M-tiles, block by block through the ring. */
-template <bool Q4, int MTW, typename StageSmall, typename StagePart>
+template <bool Q4, typename StageSmall, typename StagePart>
 __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_bytes, ptrdiff_t tile_pitch, int nb, const uint8_t* ring, int slot_bytes, int lane,
-                                           float (&acc)[MTW][16], StageSmall&& stage_small, StagePart&& stage_part) {
+                                           float (&acc)[TK_G32_MTW][16], StageSmall&& stage_small, StagePart&& stage_part) {
     typedef typename G32Frag<Q4>::type F;
     F f0 = g32_load<Q4>(tile, lane), f1 = g32_load<Q4>(tile + tile_pitch, lane);
     stage_small(0, 0);
@@ -1367,19 +1361,13 @@ __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_byte
         f1 = g32_load<Q4>(next + tile_pitch, lane);
         __builtin_amdgcn_sched_barrier(0);
         /* the last block restages itself into the slot nobody reads any more: no branch around the DMA issue */
-        /* the ring's four staging parts ride on the tiles' MFMA phases: one per tile, the rest with the LAST tile when there are fewer than four
-         * (with the first tile the same code needs 148 bytes of spill per lane) */
-        gemm_block32<Q4, MTW>(o, T, bp, acc, [&](int t) {
-            stage_part(more ? b + 1 : b, (b + 1) & 1, t);
-            if (MTW < 4 && t == MTW - 1)
-#pragma unroll
-                for (int q = MTW; q < 4; ++q) stage_part(more ? b + 1 : b, (b + 1) & 1, q);
-        });
+        /* the ring's four staging parts ride on the tiles' MFMA phases: one per tile */
+        gemm_block32<Q4>(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
         __builtin_amdgcn_sched_barrier(0);
     }
 }
 
-/* 193..256 rows (129..192 as MTW = 3 under TK_MI355X_G32_FROM; and one row half alone).  A workgroup = 4 waves, one per SIMD = four pairs of weight tiles (128 weight rows) x ONE half
+/* 193..256 rows.  A workgroup = 4 waves, one per SIMD = four pairs of weight tiles (128 weight rows) x ONE half
  * of the pass's rows (128 rows = four 32-row M-tiles per wave); the two row halves of the same weights are two workgroups that share a CU
  * (73 KiB of ring each) and nothing else.  The SIMD's two resident waves therefore belong to DIFFERENT workgroups: no barrier couples
  * them, so one's weight unpack (190 VALU instructions, no MFMA) drifts under the other's MFMA phases.  With both halves in one 8-wave
@@ -1387,7 +1375,7 @@ __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_byte
  * 8750 cycles per block against 4352 of matrix pipe (profiles/r03_gemm32_segments.txt).
  * blockIdx -> (half, unit): consecutive workgroup ids go round the 8 XCDs, so the two halves of a unit are 8 ids apart: same XCD, same
  * L2 — the second half's weight requests hit the lines the first one brought in. */
-template <int TYPES, int MTW>
+template <int TYPES>
 __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups, int total_row_tiles, int n_halves) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     constexpr int MT = TK_G32_MT;
@@ -1431,20 +1419,18 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     const ptrdiff_t tile_pitch = a.swiglu ? a.seg[1].tiles - a.seg[0].tiles : (ptrdiff_t)((size_t)nblk_total * tile_bytes);
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
-    float acc[MTW][16];
+    float acc[TK_G32_MTW][16];
 #pragma unroll
-    for (int t = 0; t < MTW; ++t)
+    for (int t = 0; t < TK_G32_MTW; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
 
     /* ring staging: of the half's eight 16-row M-tiles, `pair` and `pair + 4` belong to this wave.  The int8 image (4 x 1 KiB pieces per
      * tile, every lane takes part: no exec masking, so the issue can sit between the MFMA phases of the tile loop) in four parts of two
      * pieces; the f16 sub-block sums (32 lanes) and the block scales (4 lanes) separately at the top of a block */
-    /* rows of the pass as 32-row tiles: each half takes MTW of them (rows beyond the pass are computed on whatever the image holds and never stored) */
-    const int t32_0 = half * MTW; /* this half's first 32-row tile */
+    /* rows of the pass as 32-row tiles: each half takes TK_G32_MTW of them (rows beyond the pass are computed on whatever the image holds and never stored) */
+    const int t32_0 = half * TK_G32_MTW; /* this half's first 32-row tile */
     const int m0 = 2 * t32_0;     /* the half's first 16-row M-tile in the pass's activation images */
-    /* the ring is staged whole (eight 16-row M-tiles per block) whatever MTW: the images of all sixteen M-tiles exist (TK_MAX_ROWS), a tile nobody
-     * reads costs L2 -> LDS bytes only, and a branch around the DMA issue inside the tile loop costs registers (148 bytes of spill per lane measured) */
     /* addresses = wave-uniform base (SGPR pair) + this lane's 32-bit offset, formed where they are used: the compiler otherwise hoists five
      * 64-bit per-lane addresses out of the K loop and holds ten registers for them across it (the asm keeps the offset opaque per use) */
     auto stage_part = [&](int c, int slot, int part) {
@@ -1484,8 +1470,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
         }
         return;
     }
-    if (HAS4 && is4) g32_k_loop<true, MTW>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if (HAS6 && !is4) g32_k_loop<false, MTW>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if (HAS4 && is4) g32_k_loop<true>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if (HAS6 && !is4) g32_k_loop<false>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -1499,7 +1485,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
         const int h = lane >> 5, n32 = lane & 31;
         const int n0 = a.col0 + row_base + rt * TK_TILE_ROWS + 4 * (lane & 7);
 #pragma unroll
-        for (int t = 0; t < MTW; ++t) {
+        for (int t = 0; t < TK_G32_MTW; ++t) {
             float* sp = (float*)scr[t & 1];
 #pragma unroll
             for (int r = 0; r < 16; ++r) sp[((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + n32] = acc[t][r];
@@ -1551,15 +1537,30 @@ static int tk_num_cu() {
 template <typename F>
 static hipError_t opt_in_lds(F* fn) { return hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, TK_MAX_DYN_LDS); }
 
-#ifndef TK_G32_MIN_ROWS
-#define TK_G32_MIN_ROWS (8 * TK_ROW_SLOTS + 1)
-#endif
-/* rows per pass from which the 32x32x32 kernel takes over (narrower passes run k_gemm_w4a8 at 4 .. 12 M-tiles); TK_MI355X_G32_FROM=129 .. 257
- * moves it (257 = never), read once */
-static int tk_g32_from() {
-    static const int v = [] { const char* e = getenv("TK_MI355X_G32_FROM"); const int x = e ? atoi(e) : 0; return x >= TK_G32_MIN_ROWS && x <= 257 ? x : 12 * TK_ROW_SLOTS + 1; }();
-    return v;
-}
+/* rows per pass from which the 32x32x32 kernel takes over; narrower passes run k_gemm_w4a8 at 4 .. 12 M-tiles (129..192 rows: its time grows
+ * by ~0.4 ms per 32 rows, 3.3 / 3.7 ms per decode step's launch set against 4.2 of the 32x32x32 kernel at three tiles per half,
+ * profiles/r06_width_curve.txt) */
+static constexpr int TK_GEMM32_FROM_ROWS = 12 * TK_ROW_SLOTS + 1;
+
+/* Every kernel the launchers below can select, and the only instantiations of the mat-vec / GEMM / attention templates:
+ * tk_llm_prepare_device() opts each of them into TK_MAX_DYN_LDS.  nullptr: a combination no launch makes. */
+typedef void (*TkGemvKernel)(TkGemvArgs, int, int);
+typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
+/* [fuse][mt - 1][pf - 1][types - 1]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone */
+static const TkGemvKernel k_gemv_fns[3][2][2][3] = {
+    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>}, {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>}},
+     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>}, {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>}}},
+};
+/* [mt / 2 - 2][types - 1] */
+static const TkGemvKernel k_gemm_fns[5][3] = {
+    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>},    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>},
+    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>},    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>},
+    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>},
+};
+/* [types - 1] */
+static const TkGemm32Kernel k_gemm32_fns[3] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>};
 
 void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
     int row_tiles = 0;
@@ -1571,46 +1572,21 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
     while (waves > 8) { groups *= 2; waves = (row_tiles + groups - 1) / groups; } /* tall matrices: more than one WG per CU */
     int types = 0;
     for (int i = 0; i < a.nseg; ++i) types |= a.seg[i].type == TK_TYPE_Q4_K ? 1 : 2;
-#ifndef TK_G32_MIN_ROWS
-#define TK_G32_MIN_ROWS (8 * TK_ROW_SLOTS + 1)
-#endif
-    /* 129..192 rows: the 16x16x64 kernel at ten / twelve M-tiles (its time grows by ~0.4 ms per 32 rows: 3.3 / 3.7 ms per decode step's launch set
-     * against 4.2 of the 32x32x32 kernel at three tiles per half, profiles/r06_width_curve.txt); TK_MI355X_G32_FROM=129 keeps the round-5 split */
-    if (a.nrows >= tk_g32_from()) {
-        /* tk_g32_from() .. 256 rows: the 32x32x32 kernel, one type per wave (a mixed q / k / v launch needs no split): four (weight-tile pair) slots per
+    if (a.nrows >= TK_GEMM32_FROM_ROWS) {
+        /* 193..256 rows: the 32x32x32 kernel, one type per wave (a mixed q / k / v launch needs no split): four (weight-tile pair) slots per
          * workgroup, one workgroup per row half */
         const int pairs = a.swiglu ? a.seg[0].row_tiles : row_tiles / 2; /* every segment holds a multiple of 4 row tiles: pairs never straddle segments */
         const int g32 = (pairs + 3) / 4;
         const int n_halves = a.nrows > 8 * TK_ROW_SLOTS ? 2 : 1;
-        const int tiles32 = (a.nrows + 31) / 32; /* 5..8 at 129..256 rows: two halves of 3 (<= 192 rows) or 4 tiles */
         const size_t ldsb = (size_t)2 * TK_G32_MT * TK_RING_TILE_BYTES;
-        const dim3 grid(g32 * a.ks * n_halves);
-#define TK_G32_LAUNCH_M(TYV, MTWV) hipLaunchKernelGGL((k_gemm32_w4a8<TYV, MTWV>), grid, dim3(256), ldsb, s, a, g32, row_tiles, n_halves)
-#define TK_G32_LAUNCH(TYV) do { if (n_halves == 1 || tiles32 > 6) TK_G32_LAUNCH_M(TYV, 4); else TK_G32_LAUNCH_M(TYV, 3); } while (0)
-        if (types == 1) TK_G32_LAUNCH(1);
-        else if (types == 2) TK_G32_LAUNCH(2);
-        else TK_G32_LAUNCH(3);
-#undef TK_G32_LAUNCH
-#undef TK_G32_LAUNCH_M
+        hipLaunchKernelGGL(k_gemm32_fns[types - 1], dim3(g32 * a.ks * n_halves), dim3(256), ldsb, s, a, g32, row_tiles, n_halves);
         return;
     }
     if (a.nrows > 2 * TK_ROW_SLOTS) { /* batched passes of 33 rows and more: K-streamed activations, as many M-tiles per weight tile as the pass's rows fill */
         /* 16-row M-tiles a weight tile is multiplied against: 65..96 rows walk six, not eight */
-        const int mtb = a.nrows > 14 * TK_ROW_SLOTS ? 16 : a.nrows > 12 * TK_ROW_SLOTS ? 14 : a.nrows > 10 * TK_ROW_SLOTS ? 12 : a.nrows > 8 * TK_ROW_SLOTS ? 10 : a.nrows > 6 * TK_ROW_SLOTS ? 8 : a.nrows > 4 * TK_ROW_SLOTS ? 6 : 4;
-        const size_t ldsb = (size_t)2 * TK_RING_BLOCKS * mtb * TK_RING_TILE_BYTES;
-        /* one weight tile per wave (two adjacent tiles per wave halve the LDS operand stream but leave one wave per SIMD: 25 % slower on
-         * MI355X, profiles/r01_gemm_batched.txt) */
-#define TK_GEMM_LAUNCH(MTV, TYV) hipLaunchKernelGGL((k_gemm_w4a8<MTV, TYV, 1>), dim3(groups * a.ks), dim3(64 * waves), ldsb, s, a, groups, row_tiles)
-#define TK_GEMM_TY(MTV) do { if (types == 1) TK_GEMM_LAUNCH(MTV, 1); else if (types == 2) TK_GEMM_LAUNCH(MTV, 2); else TK_GEMM_LAUNCH(MTV, 3); } while (0)
-        if (mtb == 4) TK_GEMM_TY(4);
-        else if (mtb == 6) TK_GEMM_TY(6);
-        else if (mtb == 8) TK_GEMM_TY(8);
-        else if (mtb == 10) TK_GEMM_TY(10);
-        else if (mtb == 12) TK_GEMM_TY(12);
-        else if (mtb == 14) TK_GEMM_TY(14);
-        else TK_GEMM_TY(16);
-#undef TK_GEMM_TY
-#undef TK_GEMM_LAUNCH
+        const int mtb = a.nrows > 10 * TK_ROW_SLOTS ? 12 : a.nrows > 8 * TK_ROW_SLOTS ? 10 : a.nrows > 6 * TK_ROW_SLOTS ? 8 : a.nrows > 4 * TK_ROW_SLOTS ? 6 : 4;
+        const size_t ldsb = (size_t)2 * mtb * TK_RING_TILE_BYTES;
+        hipLaunchKernelGGL(k_gemm_fns[mtb / 2 - 2][types - 1], dim3(groups * a.ks), dim3(64 * waves), ldsb, s, a, groups, row_tiles);
         return;
     }
     const int mt = a.nrows > TK_ROW_SLOTS ? 2 : 1;
@@ -1621,15 +1597,10 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
      * depth; the two-type kernel does not. */
     if (mt == 2 && types == 2) types = 3;
     const int pf = nb % 2 == 0 ? 2 : 1;
-#define TK_GEMV_LAUNCH(PFV, MTV, TYV, FUV) hipLaunchKernelGGL((k_gemv_w4a8<PFV, MTV, TYV, FUV>), dim3(groups * a.ks), dim3(64 * waves), lds + fuse_lds, s, a, groups, row_tiles)
-#define TK_GEMV_TY(PFV, MTV, FUV) do { if (types == 1) TK_GEMV_LAUNCH(PFV, MTV, 1, FUV); else if (types == 2) TK_GEMV_LAUNCH(PFV, MTV, 2, FUV); else TK_GEMV_LAUNCH(PFV, MTV, 3, FUV); } while (0)
     const size_t fuse_lds = a.fuse == 1 ? ((size_t)a.K + 4) * sizeof(float) : 0; /* the finished row and the canonical sum's four partials */
-    if (a.fuse && mt == 1 && pf == 2) { /* tk_gemv_fuses_producer() admits only such launches */
-        if (a.fuse == 1) TK_GEMV_TY(2, 1, 1); else TK_GEMV_TY(2, 1, 2);
-    } else if (mt == 1) { if (pf == 2) TK_GEMV_TY(2, 1, 0); else TK_GEMV_TY(1, 1, 0); }
-    else { if (pf == 2) TK_GEMV_TY(2, 2, 0); else TK_GEMV_TY(1, 2, 0); }
-#undef TK_GEMV_TY
-#undef TK_GEMV_LAUNCH
+    /* tk_gemv_fuses_producer() admits only launches of one M-tile and two tiles in flight */
+    const int fuse = a.fuse && mt == 1 && pf == 2 ? (a.fuse == 1 ? 1 : 2) : 0;
+    hipLaunchKernelGGL(k_gemv_fns[fuse][mt - 1][pf - 1][types - 1], dim3(groups * a.ks), dim3(64 * waves), lds + fuse_lds, s, a, groups, row_tiles);
 }
 
 bool tk_gemv_fuses_producer(int nrows, int K, int ks, int fks) {
@@ -1702,7 +1673,7 @@ void tk_launch_qkv_rope_append(const float* partial, int ks, int n_total, int n_
  * ------------------------------------------------------------------------------------------ */
 #define TK_ATT_MAX_GRP 4
 #define TK_ATT_TSPLIT 4 /* canonical: 4 interleaved partial sums over positions (t mod 4), added in order */
-/* ring slots (template parameter SLOTS, 2 everywhere): the next chunk lands while the current one is used.  Wide passes (256 rows x 128
+/* two ring slots: the next chunk lands while the current one is used.  Wide passes (256 rows x 128
  * cached positions, profiles/r02_attention_variants.txt: 2 x 64 rows 53.5 us, 8 x 32 rows 86 us) want a small LDS footprint — workgroups per
  * CU pay, not bytes in flight per workgroup; narrow ones gain nothing from a deeper ring either (profiles/r03_attention_slots.txt) */
 __device__ __forceinline__ float sum_partials_wide(const float* partial, int ks, int n_total, int row, int col) {
@@ -1738,11 +1709,8 @@ __device__ __forceinline__ void att_stage(const uint16_t* run, int row0, int las
     }
 }
 
-template <int GQ, bool FUSED, int HD /* head_dim when it is 64 or 128 (loops unroll, LDS reads batch), 0 = any */, int CH /* positions per ring slot */, int SLOTS = 2>
-#ifndef TK_ATT_WAVES
-#define TK_ATT_WAVES 1
-#endif
-__global__ __launch_bounds__(256, TK_ATT_WAVES) void k_attention(const float* __restrict__ qbuf, const float* __restrict__ partial, int ks, int n_total,
+template <int GQ, bool FUSED, int HD /* head_dim when it is 64 or 128 (loops unroll, LDS reads batch), 0 = any */, int CH /* positions per ring slot */>
+__global__ __launch_bounds__(256, 1) void k_attention(const float* __restrict__ qbuf, const float* __restrict__ partial, int ks, int n_total,
                                                     const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
                                                     uint16_t* __restrict__ kcache, uint16_t* __restrict__ vcache, const int32_t* __restrict__ seq,
                                                     const int32_t* __restrict__ pos, int n_head, int n_kv_head, int head_dim_rt, int layer, int max_seq,
@@ -1761,7 +1729,7 @@ __global__ __launch_bounds__(256, TK_ATT_WAVES) void k_attention(const float* __
     const int slot_bytes = CH * rb;
     /* LDS: the ring (K chunks, then V chunks: one stream), then the float arrays */
     uint8_t* ring = att_lds;
-    float* qs = (float*)(att_lds + SLOTS * slot_bytes); /* [GQ][head_dim] */
+    float* qs = (float*)(att_lds + 2 * slot_bytes);     /* [GQ][head_dim] */
     float* sc = qs + W;                                   /* [GQ][max_ctx] */
     float* red = sc + (size_t)GQ * max_ctx;               /* [4 waves][GQ] */
     uint16_t* own = (uint16_t*)(red + 4 * TK_ATT_MAX_GRP); /* [2][head_dim]: this row's own K and V (FUSED) */
@@ -1776,23 +1744,24 @@ __global__ __launch_bounds__(256, TK_ATT_WAVES) void k_attention(const float* __
     const int nchunk = (T + CH - 1) / CH;
     const int total = 2 * nchunk;              /* the stream: K chunks 0 .. nchunk - 1, then V chunks 0 .. nchunk - 1 */
     const int last_row = max_ctx - 1;
-    const int ppw = slot_bytes / 4096;         /* DMA pieces per wave and chunk */
     const int ppr = rb / 16;
-    auto issue = [&](int j) { /* chunk j of the stream into slot j % SLOTS; always issued (a chunk with nothing cached yet re-reads clamped rows) */
+    auto issue = [&](int j) { /* chunk j of the stream into slot j % 2; always issued (a chunk with nothing cached yet re-reads clamped rows) */
         const bool is_k = j < nchunk;
         const int c = is_k ? j : j - nchunk;
-        att_stage(is_k ? krun : vrun, c * CH, last_row, rb, ring + (j % SLOTS) * slot_bytes, is_k, wave, lane, CH, (SLOTS == 2 && CH > 64) ? T : -1);
+        att_stage(is_k ? krun : vrun, c * CH, last_row, rb, ring + (j % 2) * slot_bytes, is_k, wave, lane, CH, CH > 64 ? T : -1);
     };
-    /* before touching chunk j: all but the chunks issued after it have landed; everybody is done with chunk j - 1, whose slot takes
-     * chunk j + SLOTS - 1 */
+    /* before touching chunk j: it has landed; everybody is done with chunk j - 1, whose slot takes chunk j + 1 */
+    /* (`ahead`, the chunks that may stay in flight, is 0 with two slots; written as the bound at the stream's end, and the first issue as a
+     * loop, because that is the form whose compiled code was measured) */
+    const int ppw = slot_bytes / 4096; /* DMA pieces per wave and chunk */
     auto acquire = [&](int j) {
-        const int ahead = total - 1 - j < SLOTS - 2 ? total - 1 - j : SLOTS - 2;
+        const int ahead = total - 1 - j < 0 ? total - 1 - j : 0;
         wait_vmcnt(ahead * ppw);
         __syncthreads();
-        if (j + SLOTS - 1 < total) issue(j + SLOTS - 1);
+        if (j + 1 < total) issue(j + 1);
     };
 
-    for (int j = 0; j < SLOTS - 1 && j < total; ++j) issue(j); /* in flight under the q / k / v prologue */
+    for (int j = 0; j < 1 && j < total; ++j) issue(j); /* in flight under the q / k / v prologue */
     if (FUSED) {
         const float* cs = rope_cos + (int64_t)p * half;
         const float* sn = rope_sin + (int64_t)p * half;
@@ -1827,7 +1796,7 @@ __global__ __launch_bounds__(256, TK_ATT_WAVES) void k_attention(const float* __
     float mx = -INFINITY;
     for (int c = 0; c < nchunk; ++c) {
         acquire(c); /* the first barrier also publishes qs and own */
-        uint8_t* slot = ring + (c % SLOTS) * slot_bytes;
+        uint8_t* slot = ring + (c % 2) * slot_bytes;
         if (FUSED && c == nchunk - 1) { /* the row's own key (position p, always in the last chunk) comes from LDS, swizzled like the rest */
             const int rr = p - c * CH;
             if (t < ppr) *(uint4*)(slot + rr * rb + ((t ^ (rr & (ppr - 1))) * 16)) = *(const uint4*)((const uint8_t*)own + t * 16);
@@ -1888,7 +1857,7 @@ __global__ __launch_bounds__(256, TK_ATT_WAVES) void k_attention(const float* __
     for (int h = 0; h < GQ; ++h) { l[h] = 0.0f; acc[h][0][0] = acc[h][0][1] = acc[h][1][0] = acc[h][1][1] = 0.0f; }
     for (int c = 0; c < nchunk; ++c) {
         acquire(nchunk + c); /* the first barrier also publishes the probabilities */
-        uint8_t* slot = ring + ((nchunk + c) % SLOTS) * slot_bytes;
+        uint8_t* slot = ring + ((nchunk + c) % 2) * slot_bytes;
         if (FUSED && c == nchunk - 1) {
             const int rr = p - c * CH;
             if (t < ppr) *(uint4*)(slot + rr * rb + t * 16) = *(const uint4*)((const uint8_t*)(own + head_dim) + t * 16);
@@ -2704,56 +2673,70 @@ static int tk_attention_narrow_cap(int nrows, int n_head, int n_kv_head, int hea
     return cap / 32 * 32;
 }
 
-size_t tk_attention_lds_bytes(int gq, int head_dim, int max_ctx, int chunk, int slots) {
+size_t tk_attention_lds_bytes(int gq, int head_dim, int max_ctx, int chunk) {
     const size_t W = (size_t)gq * head_dim;
-    const size_t ring = (size_t)slots * chunk * head_dim * 2;
+    const size_t ring = (size_t)2 * chunk * head_dim * 2;
     const size_t epilogue = ((size_t)TK_ATT_TSPLIT * W + TK_ATT_TSPLIT * TK_ATT_MAX_GRP + W) * sizeof(float); /* aliases the ring */
     return (ring > epilogue ? ring : epilogue) + (W + (size_t)gq * max_ctx + 4 * TK_ATT_MAX_GRP) * sizeof(float) + (size_t)2 * head_dim * 2;
 }
 
-#ifndef TK_ATT_NARROW_CHUNK
-#define TK_ATT_NARROW_CHUNK 128 /* 64: the round-3 form */
-#endif
-#ifndef TK_ATT_WIDE_SLOTS
-#define TK_ATT_WIDE_SLOTS 2 /* ring depth of the many-workgroup (32-position chunk) form */
-#endif
 /* Which attention launch a pass takes on the calling thread's device (the choice depends on its CU count): the one place that decides,
  * used by the launcher and exported (tk_mi355x_attention_plan) so tests assert what they run from the launcher's own answer. */
 TkAttentionPlan tk_attention_plan(int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, bool fused) {
     TkAttentionPlan pl{};
-#ifndef TK_ATT_NO_NARROW
     if (const int cap = tk_attention_narrow_cap(nrows, n_head, n_kv_head, head_dim, max_ctx, fused)) {
         pl.kernel = 1; pl.gq = 2; pl.chunk = cap; pl.slots = 1;
         pl.lds_bytes = tk_attention_narrow_fixed_lds(max_ctx) + (size_t)cap * 512;
         return pl;
     }
-#endif
     int gq = n_head / n_kv_head; /* 1, 2 or 4 (TkLlmModel::init) */
     /* few rows: two workgroups per KV head (two query heads each) — twice the workgroups, half the dependent work in each; K / V are then
      * read twice, which costs nothing while the launch is latency-bound (16 rows: 15.9 -> see profiles/r02_attention_variants.txt) */
     if (gq == 4 && (2 * head_dim) % 256 == 0 && nrows * n_kv_head < 2 * TK_NUM_CU) gq = 2;
-#ifdef TK_ATT_GQ1_ROWS /* diagnostic: one query head per workgroup below this many rows */
-    if (gq == 2 && head_dim % 256 == 0 && nrows <= TK_ATT_GQ1_ROWS) gq = 1;
-#endif
     /* positions per ring slot: 64 while the launch is a latency chain of few workgroups (fewer, longer phases), 32 once several
      * workgroups per CU are resident (16 KiB less LDS each: more of them fit; 256 rows: 47.9 -> 43.3 us, 16 rows would lose 24 %;
      * profiles/r02_attention_variants.txt) */
     /* at most one workgroup per CU and <= 2 query heads per workgroup: 128 positions per slot — the score phase (one fma chain per (head,
      * position): 2 x 64 threads of a 64-position chunk leave two of the four waves idle) runs on all four waves and a context has half as
      * many barrier-separated phases */
-    const bool narrow = TK_ATT_NARROW_CHUNK == 128 && gq * 128 <= 256 && (n_head / gq) * nrows <= TK_NUM_CU && (head_dim == 128 || head_dim == 64) &&
-                        tk_attention_lds_bytes(gq, head_dim, max_ctx, 128, 2) <= (size_t)TK_MAX_DYN_LDS;
+    const bool narrow = gq * 128 <= 256 && (n_head / gq) * nrows <= TK_NUM_CU && (head_dim == 128 || head_dim == 64) &&
+                        tk_attention_lds_bytes(gq, head_dim, max_ctx, 128) <= (size_t)TK_MAX_DYN_LDS;
     const int chunk = narrow ? 128 : (n_head / gq) * nrows > 4 * TK_NUM_CU ? 32 : 64;
     /* ring depth 2 at every pass width: with few workgroups a five-slot ring (every K and V chunk of a 128-position context in flight at
      * once) measured no faster — 16 rows x 128 positions 10.7 us against 11.1, decode step unchanged (profiles/r03_attention_slots.txt): a
      * one-row launch already takes 9.8 us, the launch is a chain of ~10 barrier-separated phases, not of DMA latencies */
-    pl.kernel = 0; pl.gq = gq; pl.chunk = chunk; pl.slots = chunk == 32 ? TK_ATT_WIDE_SLOTS : 2;
-    pl.lds_bytes = tk_attention_lds_bytes(gq, head_dim, max_ctx, chunk, pl.slots);
+    pl.kernel = 0; pl.gq = gq; pl.chunk = chunk; pl.slots = 2;
+    pl.lds_bytes = tk_attention_lds_bytes(gq, head_dim, max_ctx, chunk);
     /* a pass that is not fused holds several positions of a sequence: the session runs k_attention_prefill (kernel 2) where it applies; the
      * other fields keep describing the k_attention form it replaces (TK_MI355X_NO_PREFILL_ATT=1, or a caller of tk_launch_attention itself) */
     if (!fused && tk_attention_prefill_applies(n_head, n_kv_head, head_dim)) pl.kernel = 2;
     return pl;
 }
+
+/* [gq 1, 2, 4][fused][head_dim any, 64, 128][chunk 32, 64, 128]: 128-position chunks only for gq <= 2 and head_dim 64 / 128 (the plan's
+ * `narrow`) */
+typedef void (*TkAttentionKernel)(const float*, const float*, int, int, const float*, const float*, uint16_t*, uint16_t*, const int32_t*,
+                                  const int32_t*, int, int, int, int, int, int, TkActQ8);
+static const TkAttentionKernel k_attention_fns[3][2][3][3] = {
+    {{{k_attention<1, false, 0, 32>, k_attention<1, false, 0, 64>},
+      {k_attention<1, false, 64, 32>, k_attention<1, false, 64, 64>, k_attention<1, false, 64, 128>},
+      {k_attention<1, false, 128, 32>, k_attention<1, false, 128, 64>, k_attention<1, false, 128, 128>}},
+     {{k_attention<1, true, 0, 32>, k_attention<1, true, 0, 64>},
+      {k_attention<1, true, 64, 32>, k_attention<1, true, 64, 64>, k_attention<1, true, 64, 128>},
+      {k_attention<1, true, 128, 32>, k_attention<1, true, 128, 64>, k_attention<1, true, 128, 128>}}},
+    {{{k_attention<2, false, 0, 32>, k_attention<2, false, 0, 64>},
+      {k_attention<2, false, 64, 32>, k_attention<2, false, 64, 64>, k_attention<2, false, 64, 128>},
+      {k_attention<2, false, 128, 32>, k_attention<2, false, 128, 64>, k_attention<2, false, 128, 128>}},
+     {{k_attention<2, true, 0, 32>, k_attention<2, true, 0, 64>},
+      {k_attention<2, true, 64, 32>, k_attention<2, true, 64, 64>, k_attention<2, true, 64, 128>},
+      {k_attention<2, true, 128, 32>, k_attention<2, true, 128, 64>, k_attention<2, true, 128, 128>}}},
+    {{{k_attention<4, false, 0, 32>, k_attention<4, false, 0, 64>},
+      {k_attention<4, false, 64, 32>, k_attention<4, false, 64, 64>},
+      {k_attention<4, false, 128, 32>, k_attention<4, false, 128, 64>}},
+     {{k_attention<4, true, 0, 32>, k_attention<4, true, 0, 64>},
+      {k_attention<4, true, 64, 32>, k_attention<4, true, 64, 64>},
+      {k_attention<4, true, 128, 32>, k_attention<4, true, 128, 64>}}},
+};
 
 void tk_launch_attention(const float* qbuf, const float* partial, int ks, int n_total, const float* rope_cos, const float* rope_sin,
                          uint16_t* kcache, uint16_t* vcache, const int32_t* seq, const int32_t* pos, int nrows, int n_head, int n_kv_head,
@@ -2765,20 +2748,9 @@ void tk_launch_attention(const float* qbuf, const float* partial, int ks, int n_
         return;
     }
     const int gq = pl.gq, chunk = pl.chunk;
-    const size_t lds = pl.lds_bytes;
-#define TK_ATT_LAUNCH_CH(G, F, H, C, S)                                                                                                       \
-    hipLaunchKernelGGL((k_attention<G, F, H, C, S>), dim3(n_head / gq, nrows), dim3(256), lds, s, qbuf, partial, ks, n_total, rope_cos, rope_sin, kcache, \
-                       vcache, seq, pos, n_head, n_kv_head, head_dim, layer, max_seq, max_ctx, out)
-#define TK_ATT_LAUNCH_HD(G, F, H) do { if (chunk == 32) TK_ATT_LAUNCH_CH(G, F, H, 32, TK_ATT_WIDE_SLOTS); else if (chunk == 128 && G <= 2 && H != 0) TK_ATT_LAUNCH_CH((G <= 2 ? G : 2), F, (H ? H : 128), 128, 2); else TK_ATT_LAUNCH_CH(G, F, H, 64, 2); } while (0)
-#define TK_ATT_LAUNCH(G, F) do { if (head_dim == 128) TK_ATT_LAUNCH_HD(G, F, 128); else if (head_dim == 64) TK_ATT_LAUNCH_HD(G, F, 64); else TK_ATT_LAUNCH_HD(G, F, 0); } while (0)
-    if (fused) {
-        if (gq == 4) TK_ATT_LAUNCH(4, true); else if (gq == 2) TK_ATT_LAUNCH(2, true); else TK_ATT_LAUNCH(1, true);
-    } else {
-        if (gq == 4) TK_ATT_LAUNCH(4, false); else if (gq == 2) TK_ATT_LAUNCH(2, false); else TK_ATT_LAUNCH(1, false);
-    }
-#undef TK_ATT_LAUNCH_CH
-#undef TK_ATT_LAUNCH_HD
-#undef TK_ATT_LAUNCH
+    const TkAttentionKernel k = k_attention_fns[gq == 4 ? 2 : gq - 1][fused][head_dim == 128 ? 2 : head_dim == 64 ? 1 : 0][chunk == 128 ? 2 : chunk == 64 ? 1 : 0];
+    hipLaunchKernelGGL(k, dim3(n_head / gq, nrows), dim3(256), pl.lds_bytes, s, qbuf, partial, ks, n_total, rope_cos, rope_sin, kcache, vcache, seq, pos,
+                       n_head, n_kv_head, head_dim, layer, max_seq, max_ctx, out);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -2829,7 +2801,7 @@ void tk_launch_quant_q8(const float* hbuf, int FF, int nrows, TkActQ8 out, hipSt
 }
 
 bool tk_gemv_fuses_swiglu(int nrows, int ks, int type_gate, int type_up) {
-    return nrows >= tk_g32_from() && ks == 1 && type_gate == type_up && (type_gate == TK_TYPE_Q4_K || type_gate == TK_TYPE_Q6_K); /* the 32x32x32 kernel's epilogue */
+    return nrows >= TK_GEMM32_FROM_ROWS && ks == 1 && type_gate == type_up && (type_gate == TK_TYPE_Q4_K || type_gate == TK_TYPE_Q6_K); /* the 32x32x32 kernel's epilogue */
 }
 
 void tk_launch_swiglu_q8(const float* partial, int ks, int FF, int nrows, TkActQ8 out, hipStream_t s) {
@@ -2944,29 +2916,14 @@ const char* tk_llm_prepare_device(int device) {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != device) return "tk_llm_prepare_device: the calling thread's current device must be `device`";
     hipError_t e = hipSuccess;
-#define TK_OPT(fn) do { if (e == hipSuccess) e = opt_in_lds(fn); } while (0)
-#define TK_OPT_GEMM(MTV) do { TK_OPT((k_gemm_w4a8<MTV, 1, 1>)); TK_OPT((k_gemm_w4a8<MTV, 2, 1>)); TK_OPT((k_gemm_w4a8<MTV, 3, 1>)); } while (0)
-    TK_OPT_GEMM(4); TK_OPT_GEMM(6); TK_OPT_GEMM(8); TK_OPT_GEMM(10); TK_OPT_GEMM(12); TK_OPT_GEMM(14); TK_OPT_GEMM(16);
-#define TK_OPT_G32(TYV) do { TK_OPT((k_gemm32_w4a8<TYV, 4>)); TK_OPT((k_gemm32_w4a8<TYV, 3>)); } while (0)
-    TK_OPT_G32(1); TK_OPT_G32(2); TK_OPT_G32(3);
-#undef TK_OPT_G32
-#define TK_OPT_GEMV_F(PFV, MTV, FUV) do { TK_OPT((k_gemv_w4a8<PFV, MTV, 1, FUV>)); TK_OPT((k_gemv_w4a8<PFV, MTV, 2, FUV>)); TK_OPT((k_gemv_w4a8<PFV, MTV, 3, FUV>)); } while (0)
-#define TK_OPT_GEMV(PFV, MTV) TK_OPT_GEMV_F(PFV, MTV, 0)
-    TK_OPT_GEMV(1, 1); TK_OPT_GEMV(2, 1); TK_OPT_GEMV(1, 2); TK_OPT_GEMV(2, 2); TK_OPT_GEMV_F(2, 1, 1); TK_OPT_GEMV_F(2, 1, 2);
-#define TK_OPT_ATT_C(H, C, S) do { TK_OPT((k_attention<1, true, H, C, S>)); TK_OPT((k_attention<2, true, H, C, S>)); TK_OPT((k_attention<4, true, H, C, S>)); \
-                                 TK_OPT((k_attention<1, false, H, C, S>)); TK_OPT((k_attention<2, false, H, C, S>)); TK_OPT((k_attention<4, false, H, C, S>)); } while (0)
-#define TK_OPT_ATT(H) do { TK_OPT_ATT_C(H, 32, TK_ATT_WIDE_SLOTS); TK_OPT_ATT_C(H, 64, 2); } while (0)
-    TK_OPT_ATT(0); TK_OPT_ATT(64); TK_OPT_ATT(128);
-#define TK_OPT_ATT_N(H) do { TK_OPT((k_attention<1, true, H, 128, 2>)); TK_OPT((k_attention<2, true, H, 128, 2>)); TK_OPT((k_attention<1, false, H, 128, 2>)); TK_OPT((k_attention<2, false, H, 128, 2>)); } while (0)
-    TK_OPT_ATT_N(64); TK_OPT_ATT_N(128);
-    TK_OPT(k_attention_narrow);
-    TK_OPT((k_attention_prefill<128>));
-    TK_OPT((k_attention_prefill<64>));
-#undef TK_OPT_ATT_N
-#undef TK_OPT_ATT
-#undef TK_OPT_GEMV
-#undef TK_OPT_GEMM
-#undef TK_OPT
+    auto opt = [&](auto* fn) { if (fn && e == hipSuccess) e = opt_in_lds(fn); }; /* fn: a table entry (nullptr: none) or a single kernel */
+    for (const auto& f3 : k_gemv_fns) for (const auto& f2 : f3) for (const auto& f1 : f2) for (TkGemvKernel fn : f1) opt(fn);
+    for (const auto& f1 : k_gemm_fns) for (TkGemvKernel fn : f1) opt(fn);
+    for (TkGemm32Kernel fn : k_gemm32_fns) opt(fn);
+    for (const auto& f3 : k_attention_fns) for (const auto& f2 : f3) for (const auto& f1 : f2) for (TkAttentionKernel fn : f1) opt(fn);
+    opt(k_attention_narrow);
+    opt(k_attention_prefill<128>);
+    opt(k_attention_prefill<64>);
     if (e != hipSuccess) return hipGetErrorString(e);
     done[device] = true;
     return nullptr;
