@@ -109,6 +109,20 @@ tk_error_code_t tk_mi355x_llm_model_fill_synthetic(tk_mi355x_llm_model_t* m, uin
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, int ks, int nrows, const float* x,
+                                         float* y) {
+    if (!blocks || !x || !y) return TK_ERROR_INVALID_ARGUMENT;
+    std::string err;
+    if (!tk_llm_gemv_probe(device, type, blocks, rows, K, ks, nrows, x, y, err)) return fail(TK_ERROR_INVALID_ARGUMENT, err);
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_model_fill_synthetic_ftype(tk_mi355x_llm_model_t* m, uint64_t seed, int ftype) {
+    if (!m || ftype < 14 || ftype > 17) return TK_ERROR_INVALID_ARGUMENT;
+    if (!m->model.fill_synthetic(seed, false, ftype)) return fail(TK_ERROR_GPU_ROCM_ERROR, m->model.error);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_model_fill_synthetic_f16(tk_mi355x_llm_model_t* m, uint64_t seed) {
     if (!m) return TK_ERROR_INVALID_ARGUMENT;
     if (!m->model.fill_synthetic(seed, true)) return fail(TK_ERROR_GPU_ROCM_ERROR, m->model.error);
@@ -249,7 +263,7 @@ tk_error_code_t tk_mi355x_llm_model_load_gguf_lora(tk_mi355x_llm_model_t** out, 
         const TkGgufTensor* t = f.find(name);
         if (!t && alt) t = f.find(alt);
         if (!t) { tk_error_set_detail("GGUF tensor missing: %s", name.c_str()); return false; }
-        if (!t->data) { tk_error_set_detail("GGUF tensor %s has unsupported type %u (supported: F32, Q4_K, Q6_K)", name.c_str(), t->type); return false; }
+        if (!t->data) { tk_error_set_detail("GGUF tensor %s has unsupported type %u (supported: F32, F16, Q4_K, Q5_K, Q6_K)", name.c_str(), t->type); return false; }
         if (!m->model.set_tensor(layer, which, (int)t->type, t->data, t->nbytes)) { tk_error_set_detail("%s: %s", name.c_str(), m->model.error.c_str()); return false; }
         return true;
     };

@@ -13,6 +13,9 @@
  *         w = d*sc[j]*q - dmin*m[j]
  *   Q6_K: 256 weights / 210 B: 128 B low nibbles, 64 B high 2-bit pairs,
  *         16 int8 scales (groups of 16), f16 d.   w = d*sc[g]*(q-32)
+ *   Q5_K: 256 weights / 176 B: Q4_K's d, dmin and 12 B of (scale, min) pairs,
+ *         32 B of high bits (bit j of qh[l] = weight 32 j + l), 128 B of low
+ *         nibbles laid out as Q4_K's.   w = d*sc[j]*q - dmin*m[j], q in 0..31
  * Host + device code (the quantisers run inside the synthetic-weight kernel
  * and inside the oracle; they are bit-identical by construction).
  */
@@ -27,6 +30,7 @@ enum tk_ggml_type {
     TK_TYPE_F32 = 0,
     TK_TYPE_F16 = 1,
     TK_TYPE_Q4_K = 12,
+    TK_TYPE_Q5_K = 13,
     TK_TYPE_Q6_K = 14,
 };
 
@@ -38,6 +42,14 @@ typedef struct {
 } tk_block_q4_K; /* 144 B */
 
 typedef struct {
+    uint16_t d;
+    uint16_t dmin;
+    uint8_t scales[12];
+    uint8_t qh[32];
+    uint8_t qs[128];
+} tk_block_q5_K; /* 176 B */
+
+typedef struct {
     uint8_t ql[128];
     uint8_t qh[64];
     int8_t scales[16];
@@ -45,10 +57,10 @@ typedef struct {
 } tk_block_q6_K; /* 210 B */
 
 TK_HD size_t tk_type_block_bytes(int type) {
-    return type == TK_TYPE_Q4_K ? 144 : type == TK_TYPE_Q6_K ? 210 : type == TK_TYPE_F16 ? 2 : 4;
+    return type == TK_TYPE_Q4_K ? 144 : type == TK_TYPE_Q5_K ? 176 : type == TK_TYPE_Q6_K ? 210 : type == TK_TYPE_F16 ? 2 : 4;
 }
 TK_HD size_t tk_type_block_elems(int type) {
-    return (type == TK_TYPE_Q4_K || type == TK_TYPE_Q6_K) ? 256 : 1;
+    return (type == TK_TYPE_Q4_K || type == TK_TYPE_Q5_K || type == TK_TYPE_Q6_K) ? 256 : 1;
 }
 
 /* 6-bit (scale, min) pair j of a Q4_K block */
@@ -86,6 +98,23 @@ TK_HD float tk_q4k_dequant(const tk_block_q4_K* b, int i) {
     tk_q4k_get_scale_min(i >> 5, b->scales, &sc, &m);
     float d = tk_f16_to_f32(b->d), dmin = tk_f16_to_f32(b->dmin);
     return (d * (float)sc) * (float)tk_q4k_quant(b, i) - dmin * (float)m;
+}
+
+/* weight i (0..255) of a Q5_K block, q in [0,31]: the Q4_K nibble plus the high bit */
+TK_HD int tk_q5k_quant(const tk_block_q5_K* b, int i) {
+    int c = i >> 6;
+    int r = i & 63;
+    uint8_t byte = b->qs[c * 32 + (r & 31)];
+    int lo = (r < 32) ? (byte & 0x0F) : (byte >> 4);
+    return lo | (((b->qh[i & 31] >> (i >> 5)) & 1) << 4);
+}
+
+/* the expression of tk_q4k_dequant: a block with zero high bits dequantises to the Q4_K block's bits */
+TK_HD float tk_q5k_dequant(const tk_block_q5_K* b, int i) {
+    uint8_t sc, m;
+    tk_q4k_get_scale_min(i >> 5, b->scales, &sc, &m);
+    float d = tk_f16_to_f32(b->d), dmin = tk_f16_to_f32(b->dmin);
+    return (d * (float)sc) * (float)tk_q5k_quant(b, i) - dmin * (float)m;
 }
 
 /* weight i (0..255) of a Q6_K block, q in [0,63] (the stored value, before -32) */
@@ -160,6 +189,54 @@ TK_HD void tk_quantize_q4_K(const float* x, tk_block_q4_K* out) {
             uint8_t* byte = &out->qs[c * 32 + (r & 31)];
             if (r < 32) *byte = (uint8_t)((*byte & 0xF0) | q);
             else *byte = (uint8_t)((*byte & 0x0F) | (q << 4));
+        }
+    }
+}
+
+/* tk_quantize_q4_K with 31 levels per sub-block */
+TK_HD void tk_quantize_q5_K(const float* x, tk_block_q5_K* out) {
+    float scales[8], mins[8];
+    float max_scale = 0.0f, max_min = 0.0f;
+    for (int j = 0; j < 8; ++j) {
+        float mn = x[32 * j], mx = x[32 * j];
+        for (int i = 1; i < 32; ++i) {
+            float v = x[32 * j + i];
+            mn = v < mn ? v : mn;
+            mx = v > mx ? v : mx;
+        }
+        if (mn > 0.0f) mn = 0.0f;
+        scales[j] = tk_divf(mx - mn, 31.0f);
+        if (scales[j] < 0.0f) scales[j] = 0.0f;
+        mins[j] = -mn;
+        max_scale = scales[j] > max_scale ? scales[j] : max_scale;
+        max_min = mins[j] > max_min ? mins[j] : max_min;
+    }
+    float d = tk_divf(max_scale, 63.0f), dmin = tk_divf(max_min, 63.0f);
+    out->d = tk_f32_to_f16(d);
+    out->dmin = tk_f32_to_f16(dmin);
+    float dq = tk_f16_to_f32(out->d), dminq = tk_f16_to_f32(out->dmin);
+    for (int k = 0; k < 12; ++k) out->scales[k] = 0;
+    for (int k = 0; k < 32; ++k) out->qh[k] = 0;
+    for (int k = 0; k < 128; ++k) out->qs[k] = 0;
+    for (int j = 0; j < 8; ++j) {
+        int sc = dq > 0.0f ? (int)tk_rintf(tk_divf(scales[j], dq)) : 0;
+        int m = dminq > 0.0f ? (int)tk_rintf(tk_divf(mins[j], dminq)) : 0;
+        sc = sc > 63 ? 63 : sc;
+        m = m > 63 ? 63 : m;
+        tk_q4k_set_scale_min(j, out->scales, (uint8_t)sc, (uint8_t)m);
+        float dl = dq * (float)sc, ml = dminq * (float)m;
+        for (int i = 0; i < 32; ++i) {
+            int q = 0;
+            if (dl > 0.0f) {
+                q = (int)tk_rintf(tk_divf(x[32 * j + i] + ml, dl));
+                q = q < 0 ? 0 : (q > 31 ? 31 : q);
+            }
+            int idx = 32 * j + i;
+            int c = idx >> 6, r = idx & 63;
+            uint8_t* byte = &out->qs[c * 32 + (r & 31)];
+            if (r < 32) *byte = (uint8_t)((*byte & 0xF0) | (q & 15));
+            else *byte = (uint8_t)((*byte & 0x0F) | ((q & 15) << 4));
+            out->qh[i] = (uint8_t)(out->qh[i] | ((q >> 4) << j));
         }
     }
 }

@@ -54,7 +54,8 @@ public:
     /* returns false and sets `error` on failure */
     bool init(const TkLlmHParams& hp, int device);
     /* f16: the fp16 checkpoint recipe (every matrix and the embedding IEEE f16, norms f32) instead of Q4_K_M */
-    bool fill_synthetic(uint64_t seed, bool f16 = false);
+    /* ftype (k-quant checkpoints): llama.cpp's file type 14 Q4_K_S, 15 Q4_K_M, 16 Q5_K_S, 17 Q5_K_M (recipe_type) */
+    bool fill_synthetic(uint64_t seed, bool f16 = false, int ftype = 15);
     bool has_f16 = false; /* some matrix is f16: sessions also keep f16-rounded f32 activations */
     /* a LoRA adapter to merge into every matrix it names WHILE that matrix is installed (set before set_tensor / fill_synthetic; tk_lora.h);
      * not owned, only read during those calls */
@@ -63,7 +64,7 @@ public:
     /* `host_blocks` is the tensor in GGUF layout (F32 for norms) */
     bool set_tensor(int layer, int which, int type, const void* host_blocks, size_t nbytes);
     bool ready() const;
-    static int recipe_type(const TkLlmHParams& hp, int layer, int which);
+    static int recipe_type(const TkLlmHParams& hp, int layer, int which, int ftype = 15);
     void shape(int layer, int which, int64_t* rows, int64_t* cols) const;
 
 private:
@@ -155,5 +156,10 @@ public:
     double capture_ms = 0.0;
 private:
 };
+
+/* one production mat-vec on raw GGUF blocks (tk_mi355x_llm_gemv_probe): repack, Q8_K-quantise x [nrows][K] on the device, the launcher at
+ * width nrows, the ks slabs summed in ascending order; y [nrows][rows] on the host */
+bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, int ks, int nrows, const float* x, float* y,
+                       std::string& error);
 
 #endif

@@ -33,11 +33,15 @@
 
 static int use_more_bits(int i, int n) { return i < n / 8 || i >= 7 * n / 8 || (i - n / 8) % 3 == 2; }
 
-int TkLlmModel::recipe_type(const TkLlmHParams& hp, int layer, int which) {
-    if (layer < 0) return which == TK_T_OUTPUT ? TK_TYPE_Q6_K : (which == TK_T_TOKEN_EMBD ? TK_TYPE_Q4_K : TK_TYPE_F32);
+/* ftype 15 Q4_K_M / 17 Q5_K_M: the base type, Q6_K for v / down of use_more_bits layers; 16 Q5_K_S: all Q5_K; 14 Q4_K_S: Q4_K, Q5_K for v of
+ * layers < 4 and down of layers < n_layer / 8.  output is Q6_K in all four */
+int TkLlmModel::recipe_type(const TkLlmHParams& hp, int layer, int which, int ftype) {
+    const int base = ftype == 16 || ftype == 17 ? TK_TYPE_Q5_K : TK_TYPE_Q4_K;
+    if (layer < 0) return which == TK_T_OUTPUT ? TK_TYPE_Q6_K : (which == TK_T_TOKEN_EMBD ? base : TK_TYPE_F32);
     if (which == TK_L_ATTN_NORM || which == TK_L_FFN_NORM) return TK_TYPE_F32;
-    if ((which == TK_L_V || which == TK_L_DOWN) && use_more_bits(layer, hp.n_layer)) return TK_TYPE_Q6_K;
-    return TK_TYPE_Q4_K;
+    if (ftype == 14) return (which == TK_L_V && layer < 4) || (which == TK_L_DOWN && layer < hp.n_layer / 8) ? TK_TYPE_Q5_K : TK_TYPE_Q4_K;
+    if (ftype != 16 && (which == TK_L_V || which == TK_L_DOWN) && use_more_bits(layer, hp.n_layer)) return TK_TYPE_Q6_K;
+    return base;
 }
 
 void TkLlmModel::shape(int layer, int which, int64_t* rows, int64_t* cols) const {
@@ -109,7 +113,11 @@ bool TkLlmModel::install(TkDevTensor* t, int type, int64_t rows, int64_t cols, v
         const bool done = hipStreamSynchronize(s) == hipSuccess; /* the factors' host copies and dA / dB live until here */
         (void)hipFree(dA);
         (void)hipFree(dB);
-        if (ok && !taken) { error = "LoRA merge needs a Q4_K, Q6_K or F16 matrix with columns % 256 == 0"; return false; }
+        if (ok && !taken) {
+            error = type == TK_TYPE_Q5_K ? "LoRA merge needs a Q4_K, Q6_K or F16 matrix: merging into a Q5_K matrix is not built"
+                                         : "LoRA merge needs a Q4_K, Q6_K or F16 matrix with columns % 256 == 0";
+            return false;
+        }
         if (!ok || !done) { error = "LoRA merge failed on the device"; return false; }
         lora_merged++;
     }
@@ -132,11 +140,11 @@ bool TkLlmModel::install(TkDevTensor* t, int type, int64_t rows, int64_t cols, v
         }
         return true;
     }
-    if (type != TK_TYPE_Q4_K && type != TK_TYPE_Q6_K) { error = "unsupported tensor type (want F32, F16, Q4_K or Q6_K)"; return false; }
+    if (type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K && type != TK_TYPE_Q6_K) { error = "unsupported tensor type (want F32, F16, Q4_K, Q5_K or Q6_K)"; return false; }
     t->bytes = (size_t)rows * cols / 256 * tk_type_block_bytes(type);
     HIPQ(hipMalloc((void**)&t->data, t->bytes));
     if (!is_matrix) { /* token_embd stays in GGUF layout: one row is gathered per token */
-        if (type != TK_TYPE_Q4_K) { error = "token_embd must be Q4_K or F16"; return false; }
+        if (type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K) { error = "token_embd must be Q4_K, Q5_K or F16"; return false; }
         HIPQ(hipMemcpyAsync(t->data, dev_blocks, t->bytes, hipMemcpyDeviceToDevice, s));
         return true;
     }
@@ -162,10 +170,10 @@ bool TkLlmModel::set_tensor(int layer, int which, int type, const void* host_blo
     return ok;
 }
 
-bool TkLlmModel::fill_synthetic(uint64_t seed, bool f16) {
+bool TkLlmModel::fill_synthetic(uint64_t seed, bool f16, int ftype) {
     HIPQ(hipSetDevice(device));
     auto type_of = [&](int l, int w) {
-        const int t = recipe_type(hp, l, w);
+        const int t = recipe_type(hp, l, w, ftype);
         return (f16 && t != TK_TYPE_F32) ? (int)TK_TYPE_F16 : t; /* fp16 checkpoint: every matrix and the embedding f16, norms f32 */
     };
     /* scratch big enough for the largest tensor in GGUF layout */
@@ -361,6 +369,62 @@ static void set_act(TkGemvArgs& a, const TkActQ8& q) {
 }
 
 static TkGemvSeg seg_of(const TkDevTensor& t) { return TkGemvSeg{t.data, t.type, (int)(t.rows / TK_TILE_ROWS)}; }
+
+bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, int ks, int nrows, const float* x, float* y,
+                       std::string& error) {
+    if (type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K && type != TK_TYPE_Q6_K) { error = "gemv probe: type must be Q4_K, Q5_K or Q6_K"; return false; }
+    if (rows < 64 || rows % 64 || rows > (1 << 20) || ks < 1 || ks > 8 || K < 256 || K % (256 * (int64_t)ks) || K > 65536 || nrows < 1 ||
+        nrows > TK_MAX_ROWS) {
+        error = "gemv probe: needs rows % 64 == 0, ks in [1, 8], K % (256 ks) == 0, nrows in [1, 256]";
+        return false;
+    }
+    if (tk_gemv_lds_bytes((int)K, ks, 2) + (size_t)K * 4 + 16 > 160 * 1024) { error = "gemv probe: K / ks too long for the mat-vec's LDS image"; return false; }
+    HIPQ(hipSetDevice(device));
+    if (const char* e = tk_llm_prepare_device(device)) { error = e; return false; }
+    const size_t nblk = (size_t)rows * (size_t)(K / 256), bb = tk_type_block_bytes(type);
+    const size_t tb = type == TK_TYPE_Q4_K ? TK_Q4K_TILE_BYTES : type == TK_TYPE_Q5_K ? TK_Q5K_TILE_BYTES : TK_Q6K_TILE_BYTES;
+    const size_t nout = (size_t)ks * TK_MAX_ROWS * (size_t)rows;
+    void* db = nullptr;
+    uint8_t* tiles = nullptr;
+    float *dx = nullptr, *out = nullptr;
+    TkActQ8 act{};
+    std::vector<float> part(nout);
+    bool ok = hipMalloc(&db, nblk * bb) == hipSuccess && hipMalloc((void**)&tiles, nblk / TK_TILE_ROWS * tb) == hipSuccess &&
+              hipMalloc((void**)&dx, (size_t)nrows * K * 4) == hipSuccess && hipMalloc((void**)&out, nout * 4) == hipSuccess;
+    if (!ok) error = "gemv probe: out of device memory";
+    ok = ok && alloc_act(&act, (int)K, false, error);
+    if (ok) {
+        hipStream_t s = nullptr;
+        ok = hipMemcpy(db, blocks, nblk * bb, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(dx, x, (size_t)nrows * K * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemset(out, 0, nout * 4) == hipSuccess;
+        if (ok) {
+            tk_launch_repack(type, db, rows, K, tiles, s);
+            tk_launch_quant_q8(dx, (int)K, nrows, act, s);
+            TkGemvArgs a{};
+            a.seg[0] = TkGemvSeg{tiles, type, (int)(rows / TK_TILE_ROWS)};
+            a.nseg = 1; a.K = (int)K; a.ks = ks; a.n_total = (int)rows; a.nrows = nrows;
+            set_act(a, act);
+            a.out = out;
+            tk_launch_gemv(a, s);
+            ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                 hipMemcpy(part.data(), out, nout * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+        if (!ok) error = "gemv probe: device error";
+    }
+    if (ok)
+        for (int r = 0; r < nrows; ++r)
+            for (int64_t n = 0; n < rows; ++n) { /* sum_partials' order */
+                float o = part[(size_t)r * rows + n];
+                for (int sl = 1; sl < ks; ++sl) o = o + part[((size_t)sl * TK_MAX_ROWS + r) * rows + n];
+                y[(size_t)r * rows + n] = o;
+            }
+    free_act(&act);
+    if (db) (void)hipFree(db);
+    if (tiles) (void)hipFree(tiles);
+    if (dx) (void)hipFree(dx);
+    if (out) (void)hipFree(out);
+    return ok;
+}
 
 void TkLlmSession::enqueue_pass(int nrows, bool lm_head, bool fused_attn) { enqueue_range(nrows, 0, model->hp.n_layer, true, false, lm_head, fused_attn); }
 

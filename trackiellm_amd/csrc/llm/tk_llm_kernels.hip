@@ -41,6 +41,10 @@ __global__ void k_synth_blocks(int type, uint64_t seed, uint64_t tid, int64_t nb
         tk_block_q4_K blk;
         tk_quantize_q4_K(x, &blk);
         ((tk_block_q4_K*)out)[b] = blk;
+    } else if (type == TK_TYPE_Q5_K) {
+        tk_block_q5_K blk;
+        tk_quantize_q5_K(x, &blk);
+        ((tk_block_q5_K*)out)[b] = blk;
     } else {
         tk_block_q6_K blk;
         tk_quantize_q6_K(x, &blk);
@@ -168,14 +172,48 @@ __global__ void k_repack_q6k(const tk_block_q6_K* src, int64_t nblk, uint8_t* ti
     }
 }
 
+__global__ void k_repack_q5k(const tk_block_q5_K* src, int64_t nblk, uint8_t* tiles) {
+    const int lane = threadIdx.x;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t rt = blockIdx.y, blk = blockIdx.x;
+    const tk_block_q5_K* b = src + (rt * 16 + n) * nblk + blk;
+    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q5K_TILE_BYTES;
+    uint32_t hb[2] = {0, 0};
+    for (int i = 0; i < 2; ++i) {
+        uint32_t dw[4];
+        for (int s = 0; s < 4; ++s) {
+            int k0 = 32 * (4 * i + s) + 8 * g;
+            uint32_t v = 0;
+            for (int t = 0; t < 4; ++t) {
+                const int qa = tk_q5k_quant(b, k0 + t), qb = tk_q5k_quant(b, k0 + 4 + t);
+                v |= (uint32_t)((qa & 15) | ((qb & 15) << 4)) << (8 * t);
+                hb[i] |= (uint32_t)(qa >> 4) << (8 * t + s);
+                hb[i] |= (uint32_t)(qb >> 4) << (8 * t + 4 + s);
+            }
+            dw[s] = v;
+        }
+        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+    }
+    *(uint2*)(tile + 2048 + lane * 8) = make_uint2(hb[0], hb[1]);
+    if (g == 0) {
+        uint32_t h[4];
+        h[0] = (uint32_t)b->d | ((uint32_t)b->dmin << 16);
+        for (int k = 0; k < 3; ++k)
+            h[1 + k] = (uint32_t)b->scales[4 * k] | ((uint32_t)b->scales[4 * k + 1] << 8) | ((uint32_t)b->scales[4 * k + 2] << 16) |
+                       ((uint32_t)b->scales[4 * k + 3] << 24);
+        *(uint4*)(tile + 2560 + n * 16) = make_uint4(h[0], h[1], h[2], h[3]);
+    }
+}
+
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s) {
     dim3 grid((unsigned)(K / 256), (unsigned)(rows / 16));
     if (type == TK_TYPE_Q4_K) hipLaunchKernelGGL(k_repack_q4k, grid, dim3(64), 0, s, (const tk_block_q4_K*)blocks, K / 256, tiles);
+    else if (type == TK_TYPE_Q5_K) hipLaunchKernelGGL(k_repack_q5k, grid, dim3(64), 0, s, (const tk_block_q5_K*)blocks, K / 256, tiles);
     else hipLaunchKernelGGL(k_repack_q6k, grid, dim3(64), 0, s, (const tk_block_q6_K*)blocks, K / 256, tiles);
 }
 
 /* ------------------------------------------------------------------------------------------
- * token embedding: one Q4_K row (GGUF layout) de-quantised per row slot
+ * token embedding: one Q4_K / Q5_K row (GGUF layout) de-quantised per row slot
  * ------------------------------------------------------------------------------------------ */
 __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, float* x) {
     const int r = blockIdx.y;
@@ -183,6 +221,9 @@ __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, f
     if (i >= D) return;
     if (type == TK_TYPE_F16) {
         x[(int64_t)r * D + i] = tk_f16_to_f32(((const uint16_t*)embd)[(int64_t)tok[r] * D + i]);
+    } else if (type == TK_TYPE_Q5_K) {
+        const tk_block_q5_K* row = (const tk_block_q5_K*)embd + (int64_t)tok[r] * (D / 256);
+        x[(int64_t)r * D + i] = tk_q5k_dequant(row + i / 256, i % 256);
     } else {
         const tk_block_q4_K* row = (const tk_block_q4_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q4k_dequant(row + i / 256, i % 256);
@@ -376,8 +417,10 @@ void tk_launch_rmsnorm_q8(float* x, const float* partial, int ks, int n_total_pa
  * ------------------------------------------------------------------------------------------ */
 struct FragQ4 { uint4 q0, q1, h; };
 struct FragQ6 { uint4 q0, q1, qh, sc; uint32_t d; };
+struct FragQ5 { uint4 q0, q1, h; uint2 qh; };
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef unsigned v2u32 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint4 ldg_nt(const uint8_t* p) {
     const v4u v = __builtin_nontemporal_load((const v4u*)p);
     return make_uint4(v.x, v.y, v.z, v.w);
@@ -388,6 +431,16 @@ __device__ __forceinline__ FragQ4 load_q4(const uint8_t* tile, int lane) {
     f.q0 = ldg_nt(tile + lane * 16);
     f.q1 = ldg_nt(tile + 1024 + lane * 16);
     f.h = ldg_nt(tile + 2048 + (lane & 15) * 16);
+    return f;
+}
+
+__device__ __forceinline__ FragQ5 load_q5(const uint8_t* tile, int lane) {
+    FragQ5 f;
+    f.q0 = ldg_nt(tile + lane * 16);
+    f.q1 = ldg_nt(tile + 1024 + lane * 16);
+    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + lane * 8));
+    f.qh = make_uint2(qh.x, qh.y);
+    f.h = ldg_nt(tile + 2560 + (lane & 15) * 16);
     return f;
 }
 
@@ -474,7 +527,8 @@ __device__ __forceinline__ void unpack_q4(const FragQ4& f, int lane, OpsQ4& o) {
     o.dmin = f16bits_to_f32(f.h.x >> 16);
 }
 
-template <int MT>
+/* SH: P = (Ph << SH) + Pl — 3 for Q4_K's scale digits, 6 for the Q5_K fold (unpack_q5_fold) */
+template <int MT, int SH = 3>
 __device__ __forceinline__ void mma_q4(const OpsQ4& o, const uint8_t* lds_act, const uint8_t* lds_amn, const float* lds_ad, size_t act_ts, int amn_ts,
                                        int ad_ts, int blk, int lane, float (*acc)[4]) {
     const int g = lane >> 4;
@@ -500,7 +554,7 @@ __device__ __forceinline__ void mma_q4(const OpsQ4& o, const uint8_t* lds_act, c
         const v4f da = *(const v4f*)(lds_ad + m * ad_ts + blk * TK_ROW_SLOTS + 4 * g);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int P = (Ph[m][r] << 3) + Pl[m][r];
+            const int P = (Ph[m][r] << SH) + Pl[m][r];
             const int M = (ch[r] << 6) + cl[r];
             acc[m][r] = tk_fmaf(o.dw * da[r], (float)P, acc[m][r]);
             acc[m][r] = tk_fmaf(-(o.dmin * da[r]), (float)M, acc[m][r]);
@@ -526,6 +580,49 @@ __device__ __forceinline__ void unpack_q6(const FragQ6& f, OpsQ6& o) {
     }
     o.sc[0] = f.sc.x; o.sc[1] = f.sc.y; o.sc[2] = f.sc.z; o.sc[3] = f.sc.w;
     o.dw = f16bits_to_f32(f.d);
+}
+
+/*
+ * Q5_K: the scale is folded into the operand as for Q6_K below (v = sc * q, split v = 64 vh + vl), and the min term is Q4_K's.
+ * Exact: v <= 63 * 31 = 1953 < 2^16, so the packed 16-bit products never carry into the next half; vl = v mod 64 <= 63 and
+ * vh = v >> 6 <= 30 are both non-negative int8, and P = sum_k v_k a_k = 64 sum vh a + sum vl a is the oracle's integer.
+ */
+/* four 5-bit quant bytes q_t of one dword times the 6-bit scale s -> the two digit dwords of v_t = s * q_t */
+__device__ __forceinline__ void q5_digits(uint32_t q, unsigned short s, int* vl, int* vh) {
+    const v2u16 S = {s, s};
+    const uint32_t we = __builtin_bit_cast(uint32_t, __builtin_bit_cast(v2u16, q & 0x00FF00FFu) * S);        /* (q_0, q_2) * s */
+    const uint32_t wo = __builtin_bit_cast(uint32_t, __builtin_bit_cast(v2u16, (q >> 8) & 0x00FF00FFu) * S); /* (q_1, q_3) * s */
+    const uint32_t le = we & 0x003F003Fu, lo = wo & 0x003F003Fu;
+    const uint32_t he = (we >> 6) & 0x003F003Fu, ho = (wo >> 6) & 0x003F003Fu; /* bit 5 of each half is 0: v < 2^11 */
+    *vl = (int)__builtin_amdgcn_perm(lo, le, 0x06020400u);
+    *vh = (int)__builtin_amdgcn_perm(ho, he, 0x06020400u);
+}
+
+/* the 5-bit quants of operand dword x (lo: k0 + 0..3, hi: k0 + 4..7) of sub-block 4 i + s, given high-bit dword w = qh[i] (tk_llm_layout.h) */
+__device__ __forceinline__ uint32_t q5_lo(uint32_t x, uint32_t w, int s) { return (x & 0x0F0F0F0Fu) | ((w << (4 - s)) & 0x10101010u); }
+__device__ __forceinline__ uint32_t q5_hi(uint32_t x, uint32_t w, int s) { return ((x >> 4) & 0x0F0F0F0Fu) | ((w >> s) & 0x10101010u); }
+
+__device__ __forceinline__ void unpack_q5_fold(const FragQ5& f, int lane, OpsQ4& o) {
+    const uint32_t qs[8] = {f.q0.x, f.q0.y, f.q0.z, f.q0.w, f.q1.x, f.q1.y, f.q1.z, f.q1.w};
+    uint32_t sc_lo, sc_hi, mn_lo, mn_hi;
+    q4k_scales(f.h, &sc_lo, &sc_hi, &mn_lo, &mn_hi);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t w = j < 4 ? f.qh.x : f.qh.y;
+        const unsigned short sc = (unsigned short)(((j < 4 ? sc_lo : sc_hi) >> (8 * (j & 3))) & 0xFFu);
+        const int e = j & 1;
+        int l0, h0, l1, h1;
+        q5_digits(q5_lo(qs[j], w, j & 3), sc, &l0, &h0);
+        q5_digits(q5_hi(qs[j], w, j & 3), sc, &l1, &h1);
+        o.bl[j >> 1][2 * e] = l0; o.bl[j >> 1][2 * e + 1] = l1;
+        o.bh[j >> 1][2 * e] = h0; o.bh[j >> 1][2 * e + 1] = h1;
+    }
+    o.bm = (lane >> 4) == 0 ? (long)(((unsigned long)mn_hi << 32) | mn_lo) : 0L;
+    const float wsc = (lane >> 4) == 0 ? 2.0f : ((lane >> 4) == 1 ? 1.0f : 0.0f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o.bm16[e] = (_Float16)((float)(((e < 4 ? mn_lo : mn_hi) >> (8 * (e & 3))) & 0xFFu) * wsc);
+    o.dw = f16bits_to_f32(f.h.x & 0xffffu);
+    o.dmin = f16bits_to_f32(f.h.x >> 16);
 }
 
 template <int MT>
@@ -577,7 +674,8 @@ size_t tk_gemv_lds_bytes(int K, int ks, int mtiles) {
  * so (a) every CU streams the same number of 16-row tiles (+-1), (b) the K-range's int8 activations are
  * staged once per CU, (c) all waves of a CU walk disjoint contiguous tile runs.
  */
-/* TYPES: bit 0 = the launch contains Q4_K tiles, bit 1 = Q6_K tiles; single-type launches keep only one fragment ring in registers */
+/* TYPES: bit 0 = the launch contains Q4_K tiles, bit 1 = Q6_K tiles, bit 2 = Q5_K tiles (only alone: tk_launch_gemv splits a mixed launch
+ * with Q5_K per type); single-type launches keep only one fragment ring in registers */
 /* FUSE (TkGemvArgs::fuse, MT = 1 only): 0 = the activation image comes from global memory; 1 / 2 = every workgroup forms it itself —
  * the norm's or SwiGLU's arithmetic, value for value what k_rmsnorm_q8 / k_swiglu_q8 write — under the latency of its first weight tiles */
 template <int PF, int MT, int TYPES, int FUSE>
@@ -604,7 +702,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     }
     const int type = a.seg[seg].type;
     /* compile-time tile pitch in single-type launches: tile addresses become scalar base + immediate */
-    const size_t tile_bytes = TYPES == 1 ? (size_t)TK_Q4K_TILE_BYTES : TYPES == 2 ? (size_t)TK_Q6K_TILE_BYTES
+    const size_t tile_bytes = TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : TYPES == 1 ? (size_t)TK_Q4K_TILE_BYTES : TYPES == 2 ? (size_t)TK_Q6K_TILE_BYTES
                                          : (type == TK_TYPE_Q4_K ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES);
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -628,9 +726,14 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     FragQ4 f4[HAS4 ? PF : 1];
     FragQ6 f6[HAS6 ? PF : 1];
+    FragQ5 f5[TYPES == 4 ? PF : 1];
     if (HAS4 && is4) {
 #pragma unroll
         for (int u = 0; u < PF; ++u) f4[HAS4 ? u : 0] = load_q4(tile + (size_t)u * tile_bytes, lane);
+    }
+    if constexpr (TYPES == 4) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) f5[u] = load_q5(tile + (size_t)u * tile_bytes, lane);
     }
     if (HAS6 && !is4) {
 #pragma unroll
@@ -812,6 +915,29 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q6<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
+    if constexpr (TYPES == 4) {
+        const uint8_t* tp = tile + PF * tile_bytes;
+#pragma unroll 1
+        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                OpsQ4 o;
+                __builtin_amdgcn_sched_barrier(0);
+                unpack_q5_fold(f5[u], lane, o);
+                __builtin_amdgcn_sched_barrier(0);
+                f5[u] = load_q5(tp + u * tile_bytes, lane);
+                __builtin_amdgcn_sched_barrier(0);
+                mma_q4<MT, 6>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, g * PF + u, lane, acc);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            OpsQ4 o;
+            __builtin_amdgcn_sched_barrier(0);
+            unpack_q5_fold(f5[u], lane, o);
+            mma_q4<MT, 6>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
+        }
+    }
 
     const int n = a.col0 + row_base + rt * TK_TILE_ROWS + (lane & 15);
     const int g = lane >> 4;
@@ -911,12 +1037,13 @@ struct PTile { v4i pl, ph; v4f cm, da; };
 #define TK_RING_TILE_BYTES (256 * TK_ROW_SLOTS + 512 + TK_ROW_SLOTS * 4) /* one M-tile of one 256-k block: image + f16 sums + scales */
 
 #define TK_MFMA64 __builtin_amdgcn_mfma_i32_16x16x64_i8
-template <bool Q4>
+/* QT: the tile type.  P = 8 Ph + Pl for Q4_K's scale digits, 64 Ph + Pl for the Q5_K / Q6_K folds; Q4_K and Q5_K have the min term */
+template <int QT>
 __device__ __forceinline__ void finish_tile(const PTile& R, const OpsQ4& o, float* acc) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        acc[r] = tk_fmaf(o.dw * R.da[r], (float)((R.ph[r] << (Q4 ? 3 : 6)) + R.pl[r]), acc[r]);
-        if (Q4) acc[r] = tk_fmaf(-(o.dmin * R.da[r]), R.cm[r], acc[r]); /* cm = sum_j m_j bsum_j, an exact integer below 2^24 */
+        acc[r] = tk_fmaf(o.dw * R.da[r], (float)((R.ph[r] << (QT == TK_TYPE_Q4_K ? 3 : 6)) + R.pl[r]), acc[r]);
+        if (QT != TK_TYPE_Q6_K) acc[r] = tk_fmaf(-(o.dmin * R.da[r]), R.cm[r], acc[r]); /* cm = sum_j m_j bsum_j, an exact integer below 2^24 */
     }
 }
 
@@ -926,7 +1053,7 @@ __device__ __forceinline__ void finish_tile(const PTile& R, const OpsQ4& o, floa
  * SIMD partners of the first half) walk the M-tiles from the middle, so the two waves of a SIMD never want the same LDS rows and the
  * matrix pipe at the same moment (MI355X_MICROARCH.md, "Two waves per SIMD", item 9).  M-tiles are independent accumulators: the order
  * does not enter the result; the epilogue stores slot m to rows of tile m ^ rot. */
-template <int MT, int NT, bool Q4>
+template <int MT, int NT, int QT>
 __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* chunk, int rot, int lane, float (&acc)[NT][MT][4]) {
     constexpr int OFF_AMN = MT * 4096, OFF_AD = MT * 4096 + MT * 512;
     const v4i zero = {0, 0, 0, 0};
@@ -937,7 +1064,7 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
     const uint8_t* act[2] = {chunk + rot * 4096, chunk - rot * 4096};
     const uint8_t* amn[2] = {chunk + OFF_AMN + rot * 512, chunk + OFF_AMN - rot * 512};
     const uint8_t* adp[2] = {chunk + OFF_AD + rot * 64, chunk + OFF_AD - rot * 64};
-#define TK_LDS_TILE(slot, m) lds_tile<Q4>(T[slot], act[(m) >= MT / 2] + (m) * 4096, amn[(m) >= MT / 2] + (m) * 512, adp[(m) >= MT / 2] + (m) * 64, lane)
+#define TK_LDS_TILE(slot, m) lds_tile<QT != TK_TYPE_Q6_K>(T[slot], act[(m) >= MT / 2] + (m) * 4096, amn[(m) >= MT / 2] + (m) * 512, adp[(m) >= MT / 2] + (m) * 64, lane)
 #pragma unroll
     for (int m = 0; m < AD && m < MT; ++m) TK_LDS_TILE(m, m);
 #pragma unroll
@@ -960,19 +1087,19 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
             }
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
-            if (Q4) c[w].cm = __builtin_amdgcn_mfma_f32_16x16x32_f16(t.mn, o[w].bm16, (v4f){0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+            if (QT != TK_TYPE_Q6_K) c[w].cm = __builtin_amdgcn_mfma_f32_16x16x32_f16(t.mn, o[w].bm16, (v4f){0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
             c[w].da = t.da;
         }
         if (m > 0) {
 #pragma unroll
-            for (int w = 0; w < NT; ++w) finish_tile<Q4>(R[w], o[w], acc[w][m - 1]);
+            for (int w = 0; w < NT; ++w) finish_tile<QT>(R[w], o[w], acc[w][m - 1]);
         }
 #pragma unroll
         for (int w = 0; w < NT; ++w) R[w] = c[w];
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
-    for (int w = 0; w < NT; ++w) finish_tile<Q4>(R[w], o[w], acc[w][MT - 1]);
+    for (int w = 0; w < NT; ++w) finish_tile<QT>(R[w], o[w], acc[w][MT - 1]);
 #undef TK_LDS_TILE
 }
 
@@ -1007,7 +1134,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     const int type = a.seg[seg].type;
     constexpr bool HAS4 = (TYPES & 1) != 0, HAS6 = (TYPES & 2) != 0;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
-    const size_t tile_bytes = is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
+    const size_t tile_bytes = TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
     const size_t tile_pitch = (size_t)nblk_total * tile_bytes; /* to the same block of the next row tile */
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -1046,11 +1173,13 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
 
     FragQ4 f4[HAS4 ? NT : 1];
     FragQ6 f6[HAS6 ? NT : 1];
+    FragQ5 f5[TYPES == 4 ? NT : 1];
     if (active) {
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
             if (HAS4 && is4) f4[HAS4 ? w : 0] = load_q4(tile + w * tile_pitch, lane);
             if (HAS6 && !is4) f6[HAS6 ? w : 0] = load_q6(tile + w * tile_pitch, lane);
+            if constexpr (TYPES == 4) f5[w] = load_q5(tile + w * tile_pitch, lane);
         }
     }
     for (int i = 0; i < CB && i < nb; ++i) stage(i, i);
@@ -1073,7 +1202,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
 #pragma unroll
             for (int w = 0; w < NT; ++w) f4[HAS4 ? w : 0] = load_q4(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
-            gemm_block<MT, NT, true>(o, chunk, rot, lane, acc);
+            gemm_block<MT, NT, TK_TYPE_Q4_K>(o, chunk, rot, lane, acc);
         }
         if (HAS6 && !is4) {
 #pragma unroll
@@ -1082,7 +1211,16 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
 #pragma unroll
             for (int w = 0; w < NT; ++w) f6[HAS6 ? w : 0] = load_q6(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
-            gemm_block<MT, NT, false>(o, chunk, rot, lane, acc);
+            gemm_block<MT, NT, TK_TYPE_Q6_K>(o, chunk, rot, lane, acc);
+        }
+        if constexpr (TYPES == 4) {
+#pragma unroll
+            for (int w = 0; w < NT; ++w) unpack_q5_fold(f5[w], lane, o[w]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NT; ++w) f5[w] = load_q5(next + w * tile_pitch, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            gemm_block<MT, NT, TK_TYPE_Q5_K>(o, chunk, rot, lane, acc);
         }
     }
     if (!active) return;
@@ -1126,7 +1264,6 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
  * ------------------------------------------------------------------------------------------ */
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef float v16f __attribute__((ext_vector_type(16)));
-typedef unsigned v2u32 __attribute__((ext_vector_type(2)));
 
 struct Ops32 { v4i bl[8], bh[8]; v8h bm16; float dw, dmin; };
 
@@ -1205,6 +1342,40 @@ __device__ __forceinline__ void unpack_q6_x32(const FragQ6& f0, const FragQ6& f1
     o.dmin = 0.0f;
 }
 
+/* the Q5_K fold of unpack_q5_fold on the 32x32x32 operand map: the high-bit dwords take the same lane swap as the nibble dwords */
+__device__ __forceinline__ void unpack_q5_x32(const FragQ5& f0, const FragQ5& f1, int lane, Ops32& o) {
+    const bool up = (lane & 16) != 0;
+    const uint4 hdr = up ? f1.h : f0.h;
+    const uint32_t q0[8] = {f0.q0.x, f0.q0.y, f0.q0.z, f0.q0.w, f0.q1.x, f0.q1.y, f0.q1.z, f0.q1.w};
+    const uint32_t q1[8] = {f1.q0.x, f1.q0.y, f1.q0.z, f1.q0.w, f1.q1.x, f1.q1.y, f1.q1.z, f1.q1.w};
+    uint32_t sc_lo, sc_hi, mn_lo, mn_hi;
+    q4k_scales(hdr, &sc_lo, &sc_hi, &mn_lo, &mn_hi);
+    uint32_t H[2][2];
+    pair_swap(f0.qh.x, f1.qh.x, &H[0][0], &H[0][1]);
+    pair_swap(f0.qh.y, f1.qh.y, &H[1][0], &H[1][1]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        uint32_t s[2];
+        pair_swap(q0[j], q1[j], &s[0], &s[1]);
+        const unsigned short sc = (unsigned short)(((j < 4 ? sc_lo : sc_hi) >> (8 * (j & 3))) & 0xFFu);
+        const int e = j & 1;
+#pragma unroll
+        for (int gp = 0; gp < 2; ++gp) {
+            int l0, h0, l1, h1;
+            q5_digits(q5_lo(s[gp], H[j >> 2][gp], j & 3), sc, &l0, &h0);
+            q5_digits(q5_hi(s[gp], H[j >> 2][gp], j & 3), sc, &l1, &h1);
+            const int u = 2 * (j >> 1) + gp;
+            o.bl[u][2 * e] = l0; o.bl[u][2 * e + 1] = l1;
+            o.bh[u][2 * e] = h0; o.bh[u][2 * e + 1] = h1;
+        }
+    }
+    const float wsc = (lane >> 5) == 0 ? 2.0f : 1.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o.bm16[e] = (_Float16)((float)(((e < 4 ? mn_lo : mn_hi) >> (8 * (e & 3))) & 0xFFu) * wsc);
+    o.dw = f16bits_to_f32(hdr.x & 0xffffu);
+    o.dmin = f16bits_to_f32(hdr.x >> 16);
+}
+
 /* s_waitcnt vmcnt(n) alone (expcnt / lgkmcnt untouched): until all but this wave's n youngest vector-memory operations are done.  The
  * LDS-DMA pieces of a chunk are invisible to the compiler's own wait insertion, so the ring is guarded by hand. */
 __device__ __forceinline__ void wait_vmcnt(int n) {
@@ -1237,11 +1408,11 @@ __device__ __forceinline__ Ptrs32 block_ptrs32(const uint8_t* blk, int lane) {
     return p;
 }
 
-template <bool Q4>
+template <int QT>
 __device__ __forceinline__ void load_atile32(ATile32& T, const Ptrs32& p, int t) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) T.a[u] = *(const v4i*)(p.ap + t * 8192 + (u >> 1) * 1024 + (u & 1) * 256);
-    if (Q4) T.mn = *(const v8h*)(p.mp + t * 1024);
+    if (QT != TK_TYPE_Q6_K) T.mn = *(const v8h*)(p.mp + t * 1024);
 }
 
 /* one 256-k block: this wave's 32 weight rows x its four 32-row M-tiles.  T arrives holding tile 0's operands; the operands of tile
@@ -1249,14 +1420,15 @@ __device__ __forceinline__ void load_atile32(ATile32& T, const Ptrs32& p, int t)
 /* The tile count is a compile-time bound: 64 accumulators and no branch in the loop.  (One tile fewer for the second half of 193..224-row
  * passes as a scalar `break` in the unrolled loop was built: 108 - 392 bytes of spill per lane at the 256-register budget of two workgroups
  * per CU; not kept.) */
-template <bool Q4, typename Hook>
+template <int QT, typename Hook>
 __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const Ptrs32& p, float (&acc)[TK_G32_MTW][16], Hook&& after_mfmas) {
     const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int t = 0; t < TK_G32_MTW; ++t) {
         /* P = 8 Ph + Pl (64 Ph + Pl for Q6_K) inside ONE accumulator: the high-digit chain first, its result shifted on the VALU, then the
          * low-digit chain on top of it (sixteen live registers fewer than two accumulators, and the finishing below needs no shift-add);
-         * the independent min-term MFMA sits where the shift waits for the last high-digit MFMA */
+         * the independent min-term MFMA sits where the shift waits for the last high-digit MFMA.  Q5_K: 64 Ph + Pl with the min term */
+        constexpr bool MINS = QT != TK_TYPE_Q6_K;
         v4i A[8];
 #pragma unroll
         for (int u = 0; u < 4; ++u) A[u] = T.a[u];
@@ -1270,16 +1442,16 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
         v16i pl;
 #pragma unroll
         for (int u = 0; u < 8; ++u) ph = TK_MFMA32(A[u], o.bh[u], ph, 0, 0, 0);
-        if (Q4) {
+        if (MINS) {
             const v16f fz = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
             cm = __builtin_amdgcn_mfma_f32_32x32x16_f16(T.mn, o.bm16, fz, 0, 0, 0);
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) pl[r] = ph[r] << (Q4 ? 3 : 6);
+        for (int r = 0; r < 16; ++r) pl[r] = ph[r] << (QT == TK_TYPE_Q4_K ? 3 : 6);
 #pragma unroll
         for (int u = 0; u < 8; ++u) pl = TK_MFMA32(A[u], o.bl[u], pl, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        if (t + 1 < TK_G32_MTW) load_atile32<Q4>(T, p, t + 1);
+        if (t + 1 < TK_G32_MTW) load_atile32<QT>(T, p, t + 1);
         after_mfmas(t); /* a quarter of this wave's ring staging for the next block: LDS-DMA issue costs 60-180 cycles a piece, here they pass while
                          * the tile's MFMAs are still in the matrix pipe */
         __builtin_amdgcn_sched_barrier(0);
@@ -1289,21 +1461,30 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
             for (int i = 0; i < 4; ++i) {
                 const int r = 4 * b + i;
                 acc[t][r] = tk_fmaf(o.dw * da[b][i], (float)pl[r], acc[t][r]);
-                if (Q4) acc[t][r] = tk_fmaf(-(o.dmin * da[b][i]), cm[r], acc[t][r]);
+                if (MINS) acc[t][r] = tk_fmaf(-(o.dmin * da[b][i]), cm[r], acc[t][r]);
             }
         __builtin_amdgcn_sched_barrier(0);
     }
 }
 
-template <bool Q4> struct G32Frag { typedef FragQ4 type; };
-template <> struct G32Frag<false> { typedef FragQ6 type; };
+template <int QT> struct G32Frag { typedef FragQ4 type; };
+template <> struct G32Frag<TK_TYPE_Q6_K> { typedef FragQ6 type; };
+template <> struct G32Frag<TK_TYPE_Q5_K> { typedef FragQ5 type; };
 /* `tile` is wave-uniform (an SGPR pair); the per-lane offsets are 32-bit and opaque per call, so the loads take the scalar-base form and no
  * 64-bit per-lane address is hoisted out of the K loop and held across it (load_q4 / load_q6 with a lane pointer cost 12 registers there) */
-template <bool Q4>
-__device__ __forceinline__ typename G32Frag<Q4>::type g32_load(const uint8_t* tile, int lane) {
+template <int QT>
+__device__ __forceinline__ typename G32Frag<QT>::type g32_load(const uint8_t* tile, int lane) {
     unsigned lo = (unsigned)lane * 16u, ho = (unsigned)(lane & 15) * 16u;
     asm volatile("" : "+v"(lo), "+v"(ho));
-    if constexpr (Q4) {
+    if constexpr (QT == TK_TYPE_Q5_K) {
+        FragQ5 f;
+        f.q0 = ldg_nt(tile + lo);
+        f.q1 = ldg_nt(tile + 1024 + lo);
+        const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + (lo >> 1)));
+        f.qh = make_uint2(qh.x, qh.y);
+        f.h = ldg_nt(tile + 2560 + ho);
+        return f;
+    } else if constexpr (QT == TK_TYPE_Q4_K) {
         FragQ4 f;
         f.q0 = ldg_nt(tile + lo);
         f.q1 = ldg_nt(tile + 1024 + lo);
@@ -1319,19 +1500,20 @@ __device__ __forceinline__ typename G32Frag<Q4>::type g32_load(const uint8_t* ti
         return f;
     }
 }
-template <bool Q4>
-__device__ __forceinline__ void g32_unpack(const typename G32Frag<Q4>::type& f0, const typename G32Frag<Q4>::type& f1, int lane, Ops32& o) {
-    if constexpr (Q4) unpack_q4_x32(f0, f1, lane, o);
+template <int QT>
+__device__ __forceinline__ void g32_unpack(const typename G32Frag<QT>::type& f0, const typename G32Frag<QT>::type& f1, int lane, Ops32& o) {
+    if constexpr (QT == TK_TYPE_Q4_K) unpack_q4_x32(f0, f1, lane, o);
+    else if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_x32(f0, f1, lane, o);
     else unpack_q6_x32(f0, f1, lane, o);
 }
 
 
 /* The K loop of one wave: its two weight tiles (32 weight rows) against its four 32-row M-tiles, block by block through the ring. */
-template <bool Q4, typename StageSmall, typename StagePart>
+template <int QT, typename StageSmall, typename StagePart>
 __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_bytes, ptrdiff_t tile_pitch, int nb, const uint8_t* ring, int slot_bytes, int lane,
                                            float (&acc)[TK_G32_MTW][16], StageSmall&& stage_small, StagePart&& stage_part) {
-    typedef typename G32Frag<Q4>::type F;
-    F f0 = g32_load<Q4>(tile, lane), f1 = g32_load<Q4>(tile + tile_pitch, lane);
+    typedef typename G32Frag<QT>::type F;
+    F f0 = g32_load<QT>(tile, lane), f1 = g32_load<QT>(tile + tile_pitch, lane);
     stage_small(0, 0);
     for (int part = 0; part < 4; ++part) stage_part(0, 0, part);
 #pragma unroll 1
@@ -1352,17 +1534,17 @@ __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_byte
         const uint8_t* next = tile + (size_t)(more ? b + 1 : b) * tile_bytes; /* the last step re-requests its own tile: no branch around a load */
         const Ptrs32 bp = block_ptrs32(ring + (b & 1) * slot_bytes, lane);
         ATile32 T;
-        load_atile32<Q4>(T, bp, 0); /* tile 0's operands: their LDS latency hides under the unpack */
+        load_atile32<QT>(T, bp, 0); /* tile 0's operands: their LDS latency hides under the unpack */
         __builtin_amdgcn_sched_barrier(0);
         Ops32 o;
-        g32_unpack<Q4>(f0, f1, lane, o);
+        g32_unpack<QT>(f0, f1, lane, o);
         __builtin_amdgcn_sched_barrier(0);
-        f0 = g32_load<Q4>(next, lane);
-        f1 = g32_load<Q4>(next + tile_pitch, lane);
+        f0 = g32_load<QT>(next, lane);
+        f1 = g32_load<QT>(next + tile_pitch, lane);
         __builtin_amdgcn_sched_barrier(0);
         /* the last block restages itself into the slot nobody reads any more: no branch around the DMA issue */
         /* the ring's four staging parts ride on the tiles' MFMA phases: one per tile */
-        gemm_block32<Q4>(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
+        gemm_block32<QT>(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -1415,7 +1597,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     const int type = a.seg[seg].type;
     constexpr bool HAS4 = (TYPES & 1) != 0, HAS6 = (TYPES & 2) != 0;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
-    const size_t tile_bytes = is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
+    const size_t tile_bytes = TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
     const ptrdiff_t tile_pitch = a.swiglu ? a.seg[1].tiles - a.seg[0].tiles : (ptrdiff_t)((size_t)nblk_total * tile_bytes);
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -1470,8 +1652,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
         }
         return;
     }
-    if (HAS4 && is4) g32_k_loop<true>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if (HAS6 && !is4) g32_k_loop<false>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if (HAS4 && is4) g32_k_loop<TK_TYPE_Q4_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if (HAS6 && !is4) g32_k_loop<TK_TYPE_Q6_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (TYPES == 4) g32_k_loop<TK_TYPE_Q5_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -1546,23 +1729,47 @@ static constexpr int TK_GEMM32_FROM_ROWS = 12 * TK_ROW_SLOTS + 1;
  * tk_llm_prepare_device() opts each of them into TK_MAX_DYN_LDS.  nullptr: a combination no launch makes. */
 typedef void (*TkGemvKernel)(TkGemvArgs, int, int);
 typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
-/* [fuse][mt - 1][pf - 1][types - 1]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone */
-static const TkGemvKernel k_gemv_fns[3][2][2][3] = {
-    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>}, {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>}},
-     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>}, {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>}}},
+/* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone.  Type index =
+ * types - 1 for Q4_K / Q6_K / both, 3 for Q5_K alone (tk_launch_gemv) */
+static const TkGemvKernel k_gemv_fns[3][2][2][4] = {
+    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>},
+      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>}},
+     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>},
+      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>}}},
 };
-/* [mt / 2 - 2][types - 1] */
-static const TkGemvKernel k_gemm_fns[5][3] = {
-    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>},    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>},
-    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>},    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>},
-    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>},
+/* [mt / 2 - 2][type index] */
+static const TkGemvKernel k_gemm_fns[5][4] = {
+    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>},     {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>},
+    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>},     {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>},
+    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>},
 };
-/* [types - 1] */
-static const TkGemm32Kernel k_gemm32_fns[3] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>};
+/* [type index] */
+static const TkGemm32Kernel k_gemm32_fns[4] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>};
 
 void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
+    int types = 0;
+    for (int i = 0; i < a.nseg; ++i) types |= a.seg[i].type == TK_TYPE_Q4_K ? 1 : a.seg[i].type == TK_TYPE_Q5_K ? 4 : 2;
+    if ((types & 4) && types != 4) {
+        /* Q5_K beside another type (Q4_K_S, Q5_K_M layers): one launch per run of same-type segments, each writing its own columns of
+         * the same slabs; a fused producer then runs once per launch and writes the same values.  (swiglu launches are single-type:
+         * tk_gemv_fuses_swiglu) */
+        int i0 = 0, col = a.col0;
+        while (i0 < a.nseg) {
+            int i1 = i0 + 1;
+            while (i1 < a.nseg && a.seg[i1].type == a.seg[i0].type) ++i1;
+            TkGemvArgs p = a;
+            p.nseg = i1 - i0;
+            for (int i = 0; i < p.nseg; ++i) p.seg[i] = a.seg[i0 + i];
+            p.col0 = col;
+            tk_launch_gemv(p, s);
+            for (int i = i0; i < i1; ++i) col += a.seg[i].row_tiles * TK_TILE_ROWS;
+            i0 = i1;
+        }
+        return;
+    }
+    const int ti = types == 4 ? 3 : types - 1; /* index into the kernel tables */
     int row_tiles = 0;
     for (int i = 0; i < a.nseg; ++i) row_tiles += a.seg[i].row_tiles;
     int groups = TK_NUM_CU / a.ks;            /* workgroups per K-range */
@@ -1570,8 +1777,6 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
     if (groups > row_tiles) groups = row_tiles;
     int waves = (row_tiles + groups - 1) / groups;
     while (waves > 8) { groups *= 2; waves = (row_tiles + groups - 1) / groups; } /* tall matrices: more than one WG per CU */
-    int types = 0;
-    for (int i = 0; i < a.nseg; ++i) types |= a.seg[i].type == TK_TYPE_Q4_K ? 1 : 2;
     if (a.nrows >= TK_GEMM32_FROM_ROWS) {
         /* 193..256 rows: the 32x32x32 kernel, one type per wave (a mixed q / k / v launch needs no split): four (weight-tile pair) slots per
          * workgroup, one workgroup per row half */
@@ -1579,14 +1784,14 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
         const int g32 = (pairs + 3) / 4;
         const int n_halves = a.nrows > 8 * TK_ROW_SLOTS ? 2 : 1;
         const size_t ldsb = (size_t)2 * TK_G32_MT * TK_RING_TILE_BYTES;
-        hipLaunchKernelGGL(k_gemm32_fns[types - 1], dim3(g32 * a.ks * n_halves), dim3(256), ldsb, s, a, g32, row_tiles, n_halves);
+        hipLaunchKernelGGL(k_gemm32_fns[ti], dim3(g32 * a.ks * n_halves), dim3(256), ldsb, s, a, g32, row_tiles, n_halves);
         return;
     }
     if (a.nrows > 2 * TK_ROW_SLOTS) { /* batched passes of 33 rows and more: K-streamed activations, as many M-tiles per weight tile as the pass's rows fill */
         /* 16-row M-tiles a weight tile is multiplied against: 65..96 rows walk six, not eight */
         const int mtb = a.nrows > 10 * TK_ROW_SLOTS ? 12 : a.nrows > 8 * TK_ROW_SLOTS ? 10 : a.nrows > 6 * TK_ROW_SLOTS ? 8 : a.nrows > 4 * TK_ROW_SLOTS ? 6 : 4;
         const size_t ldsb = (size_t)2 * mtb * TK_RING_TILE_BYTES;
-        hipLaunchKernelGGL(k_gemm_fns[mtb / 2 - 2][types - 1], dim3(groups * a.ks), dim3(64 * waves), ldsb, s, a, groups, row_tiles);
+        hipLaunchKernelGGL(k_gemm_fns[mtb / 2 - 2][ti], dim3(groups * a.ks), dim3(64 * waves), ldsb, s, a, groups, row_tiles);
         return;
     }
     const int mt = a.nrows > TK_ROW_SLOTS ? 2 : 1;
@@ -1595,12 +1800,12 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
     /* weight tiles in flight per wave: 2, the largest depth every (M-tiles, tile types) variant holds without spilling (compiler resource
      * report + timings on MI355X, profiles/r01_gemv_variants.txt).  A Q6-only launch with two M-tiles spills as a single-type kernel at that
      * depth; the two-type kernel does not. */
-    if (mt == 2 && types == 2) types = 3;
+    const int gti = mt == 2 && types == 2 ? 2 : ti;
     const int pf = nb % 2 == 0 ? 2 : 1;
     const size_t fuse_lds = a.fuse == 1 ? ((size_t)a.K + 4) * sizeof(float) : 0; /* the finished row and the canonical sum's four partials */
     /* tk_gemv_fuses_producer() admits only launches of one M-tile and two tiles in flight */
     const int fuse = a.fuse && mt == 1 && pf == 2 ? (a.fuse == 1 ? 1 : 2) : 0;
-    hipLaunchKernelGGL(k_gemv_fns[fuse][mt - 1][pf - 1][types - 1], dim3(groups * a.ks), dim3(64 * waves), lds + fuse_lds, s, a, groups, row_tiles);
+    hipLaunchKernelGGL(k_gemv_fns[fuse][mt - 1][pf - 1][gti], dim3(groups * a.ks), dim3(64 * waves), lds + fuse_lds, s, a, groups, row_tiles);
 }
 
 bool tk_gemv_fuses_producer(int nrows, int K, int ks, int fks) {
@@ -2801,7 +3006,8 @@ void tk_launch_quant_q8(const float* hbuf, int FF, int nrows, TkActQ8 out, hipSt
 }
 
 bool tk_gemv_fuses_swiglu(int nrows, int ks, int type_gate, int type_up) {
-    return nrows >= TK_GEMM32_FROM_ROWS && ks == 1 && type_gate == type_up && (type_gate == TK_TYPE_Q4_K || type_gate == TK_TYPE_Q6_K); /* the 32x32x32 kernel's epilogue */
+    return nrows >= TK_GEMM32_FROM_ROWS && ks == 1 && type_gate == type_up &&
+           (type_gate == TK_TYPE_Q4_K || type_gate == TK_TYPE_Q5_K || type_gate == TK_TYPE_Q6_K); /* the 32x32x32 kernel's epilogue */
 }
 
 void tk_launch_swiglu_q8(const float* partial, int ks, int FF, int nrows, TkActQ8 out, hipStream_t s) {

@@ -14,6 +14,12 @@
  *      [1024 ,2048)  load 1: lane l -> 4 dwords, dword s = sub-block 4 + s
  *                    dword byte t = q[k0 + t] | q[k0 + 4 + t] << 4   (k0 = 32 j + 8 g)
  *      [2048 ,2304)  16 rows x {f16 d, f16 dmin, 12 B packed 6-bit scales/mins} verbatim
+ *  Q5_K tile (2816 B = 16 x 176):
+ *      [0    ,2048)  the low nibbles as the two loads of the Q4_K tile
+ *      [2048 ,2560)  lane l -> 2 dwords: the high bits of the 64 weights whose nibbles lane l holds; dword i covers sub-blocks
+ *                    4 i + s (s = 0..3): the high bit of the weight in byte y of operand dword lo / hi (k0 + y / k0 + 4 + y) of
+ *                    sub-block 4 i + s sits at bit 8y + s / 8y + 4 + s, so one shift and one mask put it at bit 4 of its byte
+ *      [2560 ,2816)  16 rows x {f16 d, f16 dmin, 12 B packed 6-bit scales/mins} verbatim
  *  Q6_K tile (3360 B = 16 x 210): weights stored as 6-bit two's complement q' = (q - 32) & 63
  *      [0    ,2048)  two loads as above holding the LOW nibbles of q'
  *      [2048 ,3072)  lane l -> 4 dwords; dword u covers sub-blocks 2u, 2u+1: the 2 high bits of
@@ -47,6 +53,7 @@
 
 #define TK_TILE_ROWS 16
 #define TK_Q4K_TILE_BYTES 2304
+#define TK_Q5K_TILE_BYTES 2816
 #define TK_Q6K_TILE_BYTES 3360
 #define TK_ROW_SLOTS 16  /* rows of one MFMA M-tile */
 #define TK_MAX_TILES 16   /* M-tiles per pass: a weight tile is unpacked once and multiplied against all of them */

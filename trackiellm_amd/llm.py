@@ -6,6 +6,11 @@ import numpy as np
 from ._lib import check, lib
 
 
+# GGUF tensor types the LLM path loads, and llama.cpp's k-quant file types (fill_synthetic(ftype=...))
+TYPE_F32, TYPE_F16, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 0, 1, 12, 13, 14
+FTYPE_Q4_K_S, FTYPE_Q4_K_M, FTYPE_Q5_K_S, FTYPE_Q5_K_M = 14, 15, 16, 17
+
+
 class LlmHParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_layer", "d_model", "n_head", "n_kv_head", "head_dim", "d_ff", "vocab")] + \
                [("rms_eps", C.c_float), ("rope_theta", C.c_float)] + \
@@ -20,6 +25,17 @@ def lora_probe(path):
     r, a, n = C.c_int32(0), C.c_float(0), C.c_int32(0)
     check(lib().tk_mi355x_lora_probe(path.encode(), C.byref(r), C.byref(a), C.byref(n)))
     return r.value, a.value, n.value
+
+
+def gemv_probe(ttype, blocks, rows, K, ks, x, device=0):
+    """one production mat-vec (tk_mi355x_llm_gemv_probe): raw GGUF blocks [rows][K / 256] of `ttype` against x [nrows][K] with K split ks
+    ways; returns y [nrows][rows] float32"""
+    blocks = np.ascontiguousarray(blocks).view(np.uint8).reshape(-1)
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, K)
+    y = np.empty((x.shape[0], rows), np.float32)
+    lib().tk_mi355x_llm_gemv_probe.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    check(lib().tk_mi355x_llm_gemv_probe(device, ttype, _p(blocks), rows, K, ks, x.shape[0], _p(x), _p(y)))
+    return y
 
 
 def attention_plan(nrows, n_head, n_kv_head, head_dim, max_ctx, fused=True, device=0, top_position=None):
@@ -70,7 +86,13 @@ class LlmModel:
         lib().tk_mi355x_llm_model_weight_bytes.restype = C.c_uint64
         return lib().tk_mi355x_llm_model_weight_bytes(self.h)
 
-    def fill_synthetic(self, seed, f16=False):
+    def fill_synthetic(self, seed, f16=False, ftype=None):
+        """ftype (one of the FTYPE_* k-quant mixes) selects the recipe; None = Q4_K_M"""
+        if ftype is not None:
+            if f16:
+                raise ValueError("fill_synthetic: f16 and ftype select different recipes; give one")
+            check(lib().tk_mi355x_llm_model_fill_synthetic_ftype(self.h, C.c_uint64(seed), int(ftype)))
+            return self
         fn = lib().tk_mi355x_llm_model_fill_synthetic_f16 if f16 else lib().tk_mi355x_llm_model_fill_synthetic
         check(fn(self.h, C.c_uint64(seed)))
         return self
