@@ -1893,6 +1893,25 @@ __device__ __forceinline__ float sum_partials_wide(const float* partial, int ks,
     return o;
 }
 
+/* the same sums for the adjacent columns (col, col + 1), col even: ONE 8-byte load per slab, addressed as a wave-uniform slab base plus
+ * one 32-bit lane offset (an address pair per column and slab is what cost k_attention's fused form 17 registers).  Each column's slabs
+ * are added in ascending order, as above. */
+__device__ __forceinline__ v2f sum_partials_pair(const float* partial, int ks, int n_total, int row, int col) {
+    const int64_t slab = (int64_t)TK_MAX_ROWS * n_total; /* floats per slab */
+    const float* base = partial + (int64_t)row * n_total; /* wave-uniform */
+    v2f o = *(const v2f*)(base + (uint32_t)col);
+    for (int s0 = 1; s0 < ks; s0 += 3) { /* three slabs requested together (ks = 4: all of them at once), added in ascending order */
+        v2f q[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+            if (s0 + u < ks) q[u] = *(const v2f*)(base + (s0 + u) * slab + (uint32_t)col);
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+            if (s0 + u < ks) o = o + q[u];
+    }
+    return o;
+}
+
 /* stage rows [row0, row0 + 32) of one (sequence, kv head) cache run into an LDS slot; rows past `last_row` are clamped (their
  * content is never used).  swz: XOR-swizzle the 16-byte pieces of a row by the row number (K); plain copy otherwise (V).
  * Every wave issues exactly chunk_bytes / 4096 one-KiB pieces: the counted waits rely on it. */
@@ -1915,7 +1934,7 @@ __device__ __forceinline__ void att_stage(const uint16_t* run, int row0, int las
 }
 
 template <int GQ, bool FUSED, int HD /* head_dim when it is 64 or 128 (loops unroll, LDS reads batch), 0 = any */, int CH /* positions per ring slot */>
-__global__ __launch_bounds__(256, 1) void k_attention(const float* __restrict__ qbuf, const float* __restrict__ partial, int ks, int n_total,
+__global__ __launch_bounds__(256, CH == 32 ? 8 : 4) void k_attention(const float* __restrict__ qbuf, const float* __restrict__ partial, int ks, int n_total,
                                                     const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
                                                     uint16_t* __restrict__ kcache, uint16_t* __restrict__ vcache, const int32_t* __restrict__ seq,
                                                     const int32_t* __restrict__ pos, int n_head, int n_kv_head, int head_dim_rt, int layer, int max_seq,
@@ -1932,14 +1951,25 @@ __global__ __launch_bounds__(256, 1) void k_attention(const float* __restrict__ 
     const int rb = head_dim * 2;               /* bytes of one cache row */
     const int half = head_dim / 2, QD = n_head * head_dim, KVD = n_kv_head * head_dim;
     const int slot_bytes = CH * rb;
-    /* LDS: the ring (K chunks, then V chunks: one stream), then the float arrays */
+    /* LDS: the ring (K chunks, then V chunks: one stream), then the float arrays (tk_attention_lds_bytes mirrors this).
+     * The scores lie position-major, sc[position][head]: the PV phase reads a position's GQ probabilities as one LDS word group.
+     * With head_dim known the staged q has no bytes of its own: it lies over the score slots of the first head_dim positions — the
+     * context's first NH chunks.  The key chunks are walked from the LAST to the first (a score does not
+     * depend on the order its chunk is visited in, nor does the maximum), so those slots are the last to be produced; a thread keeps its
+     * scores of those NH chunks in registers until every wave is done reading q, then stores them.  2 KiB less per workgroup at 4 heads x
+     * 128 dims: with the registers at 64 that is what lets eight workgroups share a CU at a 200-position session. */
+    constexpr int NH = HD ? (HD + CH - 1) / CH : 0;
+    const int scp = HD && max_ctx < HD + HD / 2 ? HD + HD / 2 : max_ctx; /* positions the score array has room for */
     uint8_t* ring = att_lds;
-    float* qs = (float*)(att_lds + 2 * slot_bytes);     /* [GQ][head_dim] */
-    float* sc = qs + W;                                   /* [GQ][max_ctx] */
-    float* red = sc + (size_t)GQ * max_ctx;               /* [4 waves][GQ] */
-    uint16_t* own = (uint16_t*)(red + 4 * TK_ATT_MAX_GRP); /* [2][head_dim]: this row's own K and V (FUSED) */
+    float* sc = (float*)(att_lds + 2 * slot_bytes);       /* [scp][GQ] */
+    float* qs = HD ? sc : sc + (size_t)GQ * scp;          /* [GQ][head_dim] */
+    float* red = HD ? sc + (size_t)GQ * scp : qs + W;     /* [4 waves][GQ]: only where a head's threads span several waves (CH > 64) */
+    /* this row's own K (FUSED), f16 [head_dim]: patched into the first key chunk visited, before the first score is stored — with head_dim
+     * known it sits behind q inside the score array (HD / 2 floats: the array has room for HD + HD / 2 positions at least).  The row's own
+     * V stays in the registers of the threads that formed it until the last value chunk. */
+    uint16_t* own = HD ? (uint16_t*)(sc + W) : (uint16_t*)(red + (CH > 64 ? 4 * TK_ATT_MAX_GRP : 0));
     /* the epilogue's arrays live in the ring, which is idle once the last V chunk is consumed (a barrier separates the two uses): 10 KiB
-     * less LDS per workgroup = four workgroups per CU instead of three at the bench's context length */
+     * less LDS per workgroup */
     float* part = (float*)ring;                           /* [TSPLIT][W] partial outputs */
     float* lpart = part + TK_ATT_TSPLIT * W;              /* [TSPLIT][GQ] partial denominators */
     float* obuf = lpart + TK_ATT_TSPLIT * TK_ATT_MAX_GRP; /* [W] */
@@ -1947,49 +1977,45 @@ __global__ __launch_bounds__(256, 1) void k_attention(const float* __restrict__ 
     const uint16_t* krun = kcache + run0;
     const uint16_t* vrun = vcache + run0;
     const int nchunk = (T + CH - 1) / CH;
-    const int total = 2 * nchunk;              /* the stream: K chunks 0 .. nchunk - 1, then V chunks 0 .. nchunk - 1 */
+    const int total = 2 * nchunk;              /* the stream: K chunks nchunk - 1 .. 0, then V chunks 0 .. nchunk - 1 */
     const int last_row = max_ctx - 1;
     const int ppr = rb / 16;
     auto issue = [&](int j) { /* chunk j of the stream into slot j % 2; always issued (a chunk with nothing cached yet re-reads clamped rows) */
         const bool is_k = j < nchunk;
-        const int c = is_k ? j : j - nchunk;
+        const int c = is_k ? nchunk - 1 - j : j - nchunk;
         att_stage(is_k ? krun : vrun, c * CH, last_row, rb, ring + (j % 2) * slot_bytes, is_k, wave, lane, CH, CH > 64 ? T : -1);
     };
     /* before touching chunk j: it has landed; everybody is done with chunk j - 1, whose slot takes chunk j + 1 */
-    /* (`ahead`, the chunks that may stay in flight, is 0 with two slots; written as the bound at the stream's end, and the first issue as a
-     * loop, because that is the form whose compiled code was measured) */
-    const int ppw = slot_bytes / 4096; /* DMA pieces per wave and chunk */
     auto acquire = [&](int j) {
-        const int ahead = total - 1 - j < 0 ? total - 1 - j : 0;
-        wait_vmcnt(ahead * ppw);
+        wait_vmcnt(0);
         __syncthreads();
         if (j + 1 < total) issue(j + 1);
     };
 
-    for (int j = 0; j < 1 && j < total; ++j) issue(j); /* in flight under the q / k / v prologue */
+    issue(0); /* in flight under the q / k / v prologue */
+    uint32_t own_v = 0; /* dims (2 i, 2 i + 1) of the row's own V, i = own_vi: half <= 256 threads hold one pair each */
+    const int own_vi = (t + 256 * (((GQ + 1) * half - t + 255) / 256)) - (GQ + 1) * half; /* the prologue's idx of this thread inside the V range */
     if (FUSED) {
         const float* cs = rope_cos + (int64_t)p * half;
         const float* sn = rope_sin + (int64_t)p * half;
         for (int idx = t; idx < (GQ + 2) * half; idx += 256) {
             const int hsel = idx / half, i = idx % half;
+            /* columns (2 i, 2 i + 1) of a query head, of this KV head's key, or of its value: one slab walk for the three */
+            const int col = (hsel < GQ ? (hb * GQ + hsel) * head_dim : hsel == GQ ? QD + kvh * head_dim : QD + KVD + kvh * head_dim) + 2 * i;
+            const v2f ab = sum_partials_pair(partial, ks, n_total, r, col);
+            const float a = ab[0], b = ab[1];
             if (hsel < GQ) {
-                const int col = (hb * GQ + hsel) * head_dim + 2 * i;
-                const float a = sum_partials_wide(partial, ks, n_total, r, col), b = sum_partials_wide(partial, ks, n_total, r, col + 1);
                 qs[hsel * head_dim + 2 * i] = tk_fmaf(-b, sn[i], a * cs[i]);
                 qs[hsel * head_dim + 2 * i + 1] = tk_fmaf(a, sn[i], b * cs[i]);
             } else if (hsel == GQ) {
-                const int col = QD + kvh * head_dim + 2 * i;
-                const float a = sum_partials_wide(partial, ks, n_total, r, col), b = sum_partials_wide(partial, ks, n_total, r, col + 1);
                 const uint16_t k0 = tk_f32_to_f16(tk_fmaf(-b, sn[i], a * cs[i])), k1 = tk_f32_to_f16(tk_fmaf(a, sn[i], b * cs[i]));
                 const uint32_t kk = (uint32_t)k0 | ((uint32_t)k1 << 16);
                 *(uint32_t*)(kcache + run0 + (int64_t)p * head_dim + 2 * i) = kk;
                 *(uint32_t*)(own + 2 * i) = kk;
             } else {
-                const int col = QD + KVD + kvh * head_dim + 2 * i;
-                const uint16_t v0 = tk_f32_to_f16(sum_partials_wide(partial, ks, n_total, r, col)), v1 = tk_f32_to_f16(sum_partials_wide(partial, ks, n_total, r, col + 1));
-                const uint32_t vv = (uint32_t)v0 | ((uint32_t)v1 << 16);
+                const uint32_t vv = (uint32_t)tk_f32_to_f16(a) | ((uint32_t)tk_f32_to_f16(b) << 16);
                 *(uint32_t*)(vcache + run0 + (int64_t)p * head_dim + 2 * i) = vv;
-                *(uint32_t*)(own + head_dim + 2 * i) = vv;
+                own_v = vv;
             }
         }
     } else {
@@ -1997,75 +2023,94 @@ __global__ __launch_bounds__(256, 1) void k_attention(const float* __restrict__ 
     }
     const float att_scale = tk_divf(1.0f, tk_sqrtf((float)head_dim));
 
-    /* ---- scores: thread = (head, position of the chunk); GQ * CHUNK threads work, one fma chain over head_dim each ---- */
+    /* ---- scores: thread = (head, position of the chunk); GQ * CHUNK <= 256 threads work, one fma chain over head_dim each ---- */
+    const bool scorer = t < GQ * CH;
+    const int sh = t / CH, srr = t % CH; /* this thread's head and row of every chunk */
     float mx = -INFINITY;
-    for (int c = 0; c < nchunk; ++c) {
-        acquire(c); /* the first barrier also publishes qs and own */
-        uint8_t* slot = ring + (c % 2) * slot_bytes;
-        if (FUSED && c == nchunk - 1) { /* the row's own key (position p, always in the last chunk) comes from LDS, swizzled like the rest */
+    float held[NH ? NH : 1]; /* its scores of chunks 0 .. NH - 1 */
+#pragma unroll
+    for (int u = 0; u < (NH ? NH : 1); ++u) held[u] = 0.0f;
+    for (int j = 0; j < nchunk; ++j) {
+        const int c = nchunk - 1 - j;
+        acquire(j); /* the first barrier also publishes qs and own */
+        uint8_t* slot = ring + (j % 2) * slot_bytes;
+        if (FUSED && j == 0) { /* the row's own key (position p, always in the last chunk) comes from LDS, swizzled like the rest */
             const int rr = p - c * CH;
             if (t < ppr) *(uint4*)(slot + rr * rb + ((t ^ (rr & (ppr - 1))) * 16)) = *(const uint4*)((const uint8_t*)own + t * 16);
             __syncthreads();
         }
-        for (int idx = t; idx < GQ * CH; idx += 256) {
-            const int h = idx / CH, rr = idx % CH, tt = c * CH + rr;
-            if (tt < T) {
-                const uint8_t* kr = slot + rr * rb;
-                const float* qh = qs + h * head_dim;
-                float a = 0.0f;
-                constexpr int KB = HD ? HD / 8 : 1; /* key pieces read per batch: the whole row when head_dim is known */
-                for (int i0 = 0; i0 < ppr; i0 += KB) {
-                    uint4 kv[KB];
+        const int tt = c * CH + srr;
+        if (scorer && tt < T) {
+            const uint8_t* kr = slot + srr * rb;
+            const float* qh = qs + sh * head_dim;
+            float a = 0.0f;
+            constexpr int KB = HD ? HD / 8 : 1; /* key pieces read per batch: the whole row when head_dim is known */
+            for (int i0 = 0; i0 < ppr; i0 += KB) {
+                uint4 kv[KB];
 #pragma unroll
-                    for (int u = 0; u < KB; ++u) kv[u] = *(const uint4*)(kr + (((i0 + u) ^ (rr & (ppr - 1))) * 16));
+                for (int u = 0; u < KB; ++u) kv[u] = *(const uint4*)(kr + (((i0 + u) ^ (srr & (ppr - 1))) * 16));
 #pragma unroll
-                    for (int u = 0; u < KB; ++u) {
-                        const v4f q0 = *(const v4f*)(qh + 8 * (i0 + u)), q1 = *(const v4f*)(qh + 8 * (i0 + u) + 4);
-                        const uint32_t kw[4] = {kv[u].x, kv[u].y, kv[u].z, kv[u].w};
+                for (int u = 0; u < KB; ++u) {
+                    const v4f q0 = *(const v4f*)(qh + 8 * (i0 + u)), q1 = *(const v4f*)(qh + 8 * (i0 + u) + 4);
+                    const uint32_t kw[4] = {kv[u].x, kv[u].y, kv[u].z, kv[u].w};
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float kf = f16bits_to_f32((kw[e >> 1] >> (16 * (e & 1))) & 0xffffu);
-                            a = tk_fmaf(e < 4 ? q0[e] : q1[e - 4], kf, a);
-                        }
+                    for (int e = 0; e < 8; ++e) {
+                        const float kf = f16bits_to_f32((kw[e >> 1] >> (16 * (e & 1))) & 0xffffu);
+                        a = tk_fmaf(e < 4 ? q0[e] : q1[e - 4], kf, a);
                     }
                 }
-                const float s = a * att_scale;
-                sc[(size_t)h * max_ctx + tt] = s;
-                mx = tk_fmaxf(mx, s);
             }
+            const float s = a * att_scale;
+            mx = tk_fmaxf(mx, s);
+            if (c >= NH) sc[(size_t)tt * GQ + sh] = s;
+#pragma unroll
+            for (int u = 0; u < NH; ++u) held[u] = c == u ? s : held[u];
         }
     }
-    /* row maximum per head: thread idx = h * CHUNK + rr served head h in every chunk (GQ * CHUNK <= 256 threads: one idx per thread) */
+    /* row maximum per head: thread (sh, srr) served head sh in every chunk */
+    float m = mx;
     if (CH <= 64) {
-        float m = mx;
-        for (int s = CH / 2; s >= 1; s >>= 1) m = tk_fmaxf(m, wave_xor_f(m, s)); /* over the CHUNK lanes of one head */
-        if ((lane & (CH - 1)) == 0 && t < GQ * CH) red[t / CH] = m;
+        for (int s = CH / 2; s >= 1; s >>= 1) m = tk_fmaxf(m, wave_xor_f(m, s)); /* over the CHUNK lanes of one head: every one of them ends with it */
     } else { /* a head's CHUNK threads span CH / 64 whole waves: per-wave maxima, joined below (a maximum does not depend on the order) */
-        float m = mx;
         for (int s = 32; s >= 1; s >>= 1) m = tk_fmaxf(m, wave_xor_f(m, s));
-        if (lane == 0) red[TK_ATT_MAX_GRP + wave] = m; /* the second row of red[4][GQ <= 4]: free until the epilogue's lpart, which lives in the ring */
+        if (lane == 0) red[TK_ATT_MAX_GRP + wave] = m; /* the second row of red[4][GQ <= 4] */
+        __syncthreads();
+        if (t < GQ) {
+            float mm = red[TK_ATT_MAX_GRP + t * (CH / 64)];
+            for (int w = 1; w < CH / 64; ++w) mm = tk_fmaxf(mm, red[TK_ATT_MAX_GRP + t * (CH / 64) + w]);
+            red[t] = mm;
+        }
+        __syncthreads();
+        m = red[scorer ? sh : 0];
     }
-    __syncthreads(); /* every score is written */
-    if (CH > 64 && t < GQ) {
-        float m = red[TK_ATT_MAX_GRP + t * (CH / 64)];
-        for (int w = 1; w < CH / 64; ++w) m = tk_fmaxf(m, red[TK_ATT_MAX_GRP + t * (CH / 64) + w]);
-        red[t] = m;
-    }
-    if (CH > 64) __syncthreads();
-    for (int h = 0; h < GQ; ++h) {
-        const float m = red[h];
-        for (int tt = t; tt < T; tt += 256) sc[(size_t)h * max_ctx + tt] = tk_expf(sc[(size_t)h * max_ctx + tt] - m);
+    /* e = exp(s - max): every thread for the scores it produced itself (no barrier between: its own stores, or its registers) */
+    if (scorer) {
+        for (int c = NH; c < nchunk; ++c) {
+            const int tt = c * CH + srr;
+            if (tt < T) sc[(size_t)tt * GQ + sh] = tk_expf(sc[(size_t)tt * GQ + sh] - m);
+        }
+#pragma unroll
+        for (int u = 0; u < NH; ++u)
+            if (u * CH + srr < T) held[u] = tk_expf(held[u] - m);
     }
     /* ---- PV: wave j takes positions t = j (mod 4); lane owns dims (2 lane, 2 lane + 1) [+ 128 k] of every head ---- */
     float acc[GQ][2][2], l[GQ]; /* [head][dim block of 128][pair] */
 #pragma unroll
     for (int h = 0; h < GQ; ++h) { l[h] = 0.0f; acc[h][0][0] = acc[h][0][1] = acc[h][1][0] = acc[h][1][1] = 0.0f; }
     for (int c = 0; c < nchunk; ++c) {
-        acquire(nchunk + c); /* the first barrier also publishes the probabilities */
+        acquire(nchunk + c);
         uint8_t* slot = ring + ((nchunk + c) % 2) * slot_bytes;
+        if (c == 0 && NH) { /* every wave is past its last read of q (the barrier above): the kept probabilities take its place */
+            if (scorer) {
+#pragma unroll
+                for (int u = 0; u < NH; ++u)
+                    if (u * CH + srr < T) sc[(size_t)(u * CH + srr) * GQ + sh] = held[u];
+            }
+            if (!(FUSED && c == nchunk - 1)) __syncthreads(); /* publishes them (and every other probability); the patch's barrier does where it follows */
+        }
         if (FUSED && c == nchunk - 1) {
             const int rr = p - c * CH;
-            if (t < ppr) *(uint4*)(slot + rr * rb + t * 16) = *(const uint4*)((const uint8_t*)(own + head_dim) + t * 16);
+            if (own_vi < half) *(uint32_t*)(slot + rr * rb + own_vi * 4) = own_v;
             __syncthreads();
         }
         const int t_end = T - c * CH < CH ? T - c * CH : CH;
@@ -2080,8 +2125,12 @@ __global__ __launch_bounds__(256, 1) void k_attention(const float* __restrict__ 
                 const int rr = rr0 + u * TK_ATT_TSPLIT;
                 const bool live = rr < t_end;
                 const int rc = live ? rr : t_end - 1;
+                const float* pp = sc + (size_t)(c * CH + rc) * GQ; /* GQ = 1, 2 or 4 floats, aligned as a group */
+                if (GQ == 4) { const v4f x = *(const v4f*)pp; pr[u][0] = x[0]; pr[u][1 % GQ] = x[1]; pr[u][2 % GQ] = x[2]; pr[u][3 % GQ] = x[3]; }
+                else if (GQ == 2) { const v2f x = *(const v2f*)pp; pr[u][0] = x[0]; pr[u][1 % GQ] = x[1]; }
+                else pr[u][0] = pp[0];
 #pragma unroll
-                for (int h = 0; h < GQ; ++h) pr[u][h] = live ? sc[(size_t)h * max_ctx + c * CH + rc] : 0.0f;
+                for (int h = 0; h < GQ; ++h) pr[u][h] = live ? pr[u][h] : 0.0f;
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
                     const int d0 = 2 * lane + 128 * db;
@@ -2882,7 +2931,14 @@ size_t tk_attention_lds_bytes(int gq, int head_dim, int max_ctx, int chunk) {
     const size_t W = (size_t)gq * head_dim;
     const size_t ring = (size_t)2 * chunk * head_dim * 2;
     const size_t epilogue = ((size_t)TK_ATT_TSPLIT * W + TK_ATT_TSPLIT * TK_ATT_MAX_GRP + W) * sizeof(float); /* aliases the ring */
-    return (ring > epilogue ? ring : epilogue) + (W + (size_t)gq * max_ctx + 4 * TK_ATT_MAX_GRP) * sizeof(float) + (size_t)2 * head_dim * 2;
+    const size_t red = chunk > 64 ? 4 * TK_ATT_MAX_GRP * sizeof(float) : 0;
+    /* the instantiations that know head_dim keep q and the row's own key inside the score array (room for head_dim * 3 / 2 positions at
+     * least), the others beside it: 4 heads x 128 dims, 32-position slots = 16 KiB + 16 B per position of capacity */
+    if (head_dim == 128 || head_dim == 64) {
+        const size_t scp = max_ctx > head_dim + head_dim / 2 ? max_ctx : head_dim + head_dim / 2;
+        return (ring > epilogue ? ring : epilogue) + (size_t)gq * scp * sizeof(float) + red;
+    }
+    return (ring > epilogue ? ring : epilogue) + ((size_t)gq * max_ctx + W) * sizeof(float) + red + (size_t)head_dim * 2;
 }
 
 /* Which attention launch a pass takes on the calling thread's device (the choice depends on its CU count): the one place that decides,
