@@ -92,6 +92,28 @@ TK_API void tk_mi355x_llm_model_batch_stats(void* model_handle, uint64_t* passes
  * of its owner's next tk_llm_runner_generate_next_token; a runner that stops or changes course costs one such row.  `rows` above counts
  * only rows an owner asked for. */
 TK_API uint64_t tk_mi355x_llm_model_run_ahead_wasted(void* model_handle);
+/* ---- prompt prefix cache (csrc/llm/tk_llm_batcher.h; opt-in; include/tk/ABI_NOTES.md).  A cache row at position p depends only on tokens 0 .. p
+ * and its bits do not depend on the pass that computes it, so a row already in the shared KV cache for the same leading tokens is the row a
+ * recomputation would write. ---- */
+/* on = 0 (default): prepare_generation recomputes every row, as the reference does.  on = 1: rows whose tokens equal what the runner's slot
+ * already holds are kept, rows another slot of the model holds are copied.  May be changed at any time; takes effect for the next prompt.
+ * Tokens are the same either way.  TK_ERROR_NOT_IMPLEMENTED on a model whose head_dim is not a multiple of 8. */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_set_prefix_cache(void* model_handle, int on);
+/* totals over the model's schedulers since load: prompt rows asked for by prepare_generation, of them kept in place, of them copied from
+ * another slot, copy launches.  tk_mi355x_llm_model_batch_stats' `rows` keeps its meaning (rows COMPUTED for an owner): with the cache on it
+ * falls by kept + copied. */
+TK_API void tk_mi355x_llm_model_prefix_cache_stats(void* model_handle, uint64_t* prompt_rows, uint64_t* kept, uint64_t* copied,
+                                                   uint64_t* copy_launches);
+/* the same three row counts for this runner's last prepare_generation */
+struct tk_llm_runner_s;
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_last_prompt_rows(struct tk_llm_runner_s* runner, int32_t* prompt_rows, int32_t* kept,
+                                                                          int32_t* copied);
+/* the cache's matching rules on hand-written records, no device involved (tests): records[s * stride ..] holds the record_len[s] token ids whose
+ * rows slot s holds.  out[0] = rows of toks[0 .. n) that self_slot's own record covers (at most n - 1; 0 when self_slot = -1); out[1] = the slot
+ * that rows [cursor, out[2]) would be copied from (cursor = -1: out[0]), -1 = none: the longest match of at least 16 positions beyond the
+ * cursor, the lowest slot among equals.  Returns 0, or -1 on bad arguments. */
+TK_API int tk_mi355x_prefix_match(const int32_t* toks, int n, const int32_t* records, const int32_t* record_len, int n_slots, int stride, int self_slot,
+                                  int cursor, int32_t out[3]);
 
 /* sessions --------------------------------------------------------------------------------- */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_create(tk_mi355x_llm_session_t** out, tk_mi355x_llm_model_t* m, int max_seq,
@@ -137,6 +159,14 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_kv_write(tk_mi355x_llm
                                                                    const uint16_t* k, const uint16_t* v);
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_kv_read(tk_mi355x_llm_session_t* s, int layer, int seq, int pos0, int n_pos,
                                                                   uint16_t* k, uint16_t* v);
+/* rows [pos0, pos0 + n_pos) of sequence src_seq copied onto the same rows of dst_seq (src_seq != dst_seq) in every layer, on the device: one
+ * launch of the prefix cache's copy kernel.  Synchronous. */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_kv_copy(tk_mi355x_llm_session_t* s, int src_seq, int dst_seq, int pos0, int n_pos);
+/* stand-alone timing of that copy (tools/time_kv_copy.py): rows [0, n_pos) of sequence 0 onto sequences 1 .. n_dst as ONE kernel launch and as the
+ * form it replaces, a hipMemcpy2DAsync per (destination, layer, K | V), alternating on the session's stream, device events around each; average ms
+ * of `iters` rounds after a warm-up; bytes = read + written by one round of either form */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_time_kv_copy(tk_mi355x_llm_session_t* s, int n_pos, int n_dst, int iters, float* kernel_ms,
+                                                               float* memcpy_ms, double* bytes);
 /* equal-length prompts for sequences 0..nseq-1; first_tokens[nseq] optional */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_prefill(tk_mi355x_llm_session_t* s, int nseq, int n_prompt, const int32_t* tokens,
                                                           int32_t* first_tokens);

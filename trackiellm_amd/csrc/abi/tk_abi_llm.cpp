@@ -27,6 +27,7 @@
 #include "../llm/tk_llm_batcher.h"
 #include "../llm/tk_llm_engine.h"
 #include "../llm/tk_lora.h"
+#include "../llm/tk_prefix_match.h"
 #include "../llm/tk_llm_pipe.h"
 #include "../llm/tk_tokenizer.h"
 #include "../common/tk_ggml_blocks.h"
@@ -45,6 +46,7 @@ struct tk_mi355x_llm_model_s {
     std::mutex batch_mu;
     std::vector<std::unique_ptr<TkLlmBatcher>> batchers;
     int runner_slots = 0; /* sequences per shared session; 0 = $TK_MI355X_RUNNER_SLOTS or 16 */
+    bool prefix_cache = false; /* tk_mi355x_llm_model_set_prefix_cache: handed to every scheduler of the model, present and future */
 };
 
 struct tk_mi355x_llm_session_s {
@@ -336,6 +338,16 @@ tk_error_code_t tk_mi355x_llm_session_kv_read(tk_mi355x_llm_session_t* s, int la
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_llm_session_kv_copy(tk_mi355x_llm_session_t* s, int src_seq, int dst_seq, int pos0, int n_pos) {
+    if (!s) return TK_ERROR_INVALID_ARGUMENT;
+    if (!s->session.kv_copy_applies()) return fail(TK_ERROR_NOT_IMPLEMENTED, "kv_copy needs head_dim to be a multiple of 8");
+    if (src_seq < 0 || src_seq >= s->session.max_seq || dst_seq < 0 || dst_seq >= s->session.max_seq || src_seq == dst_seq || pos0 < 0 || n_pos <= 0 ||
+        n_pos > s->session.max_ctx - pos0)
+        return fail(TK_ERROR_INVALID_ARGUMENT, "kv_copy: (source, destination, positions) outside the cache, or source = destination");
+    if (!s->session.kv_copy(src_seq, dst_seq, pos0, n_pos)) return fail(TK_ERROR_GPU_ROCM_ERROR, s->session.error);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_prefill(tk_mi355x_llm_session_t* s, int nseq, int n_prompt, const int32_t* tokens, int32_t* first_tokens) {
     if (!s || !tokens) return TK_ERROR_INVALID_ARGUMENT;
     if (!s->session.prefill(nseq, n_prompt, tokens, first_tokens)) return fail(TK_ERROR_INFERENCE_FAILED, s->session.error);
@@ -462,6 +474,12 @@ tk_error_code_t tk_mi355x_llm_time_attention(tk_mi355x_llm_session_t* s, int nro
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_llm_time_kv_copy(tk_mi355x_llm_session_t* s, int n_pos, int n_dst, int iters, float* kernel_ms, float* memcpy_ms, double* bytes) {
+    if (!s || !kernel_ms || !memcpy_ms || !bytes) return TK_ERROR_INVALID_ARGUMENT;
+    if (!s->session.time_kv_copy(n_pos, n_dst, iters, kernel_ms, memcpy_ms, bytes)) return fail(TK_ERROR_GPU_ROCM_ERROR, s->session.error);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_model_set_runner_slots(void* model_handle, int slots) {
     if (!model_handle || slots < 1 || slots > TK_MAX_ROWS) return TK_ERROR_INVALID_ARGUMENT;
     tk_mi355x_llm_model_t* m = (tk_mi355x_llm_model_t*)model_handle;
@@ -486,6 +504,51 @@ void tk_mi355x_llm_model_batch_stats(void* model_handle, uint64_t* passes, uint6
     if (passes) *passes = p;
     if (rows) *rows = r;
     if (max_rows_in_a_pass) *max_rows_in_a_pass = mx;
+}
+
+tk_error_code_t tk_mi355x_llm_model_set_prefix_cache(void* model_handle, int on) {
+    if (!model_handle || (on != 0 && on != 1)) return TK_ERROR_INVALID_ARGUMENT;
+    tk_mi355x_llm_model_t* m = (tk_mi355x_llm_model_t*)model_handle;
+    if (on && m->model.hp.head_dim % 8 != 0) return fail(TK_ERROR_NOT_IMPLEMENTED, "the prefix cache copies rows in 16-byte words: head_dim must be a multiple of 8");
+    std::lock_guard<std::mutex> lk(m->batch_mu);
+    m->prefix_cache = on != 0;
+    for (auto& b : m->batchers) (void)b->set_prefix_cache(on != 0);
+    return TK_SUCCESS;
+}
+
+void tk_mi355x_llm_model_prefix_cache_stats(void* model_handle, uint64_t* prompt_rows, uint64_t* kept, uint64_t* copied, uint64_t* copy_launches) {
+    uint64_t t[4] = {0, 0, 0, 0};
+    if (model_handle) {
+        tk_mi355x_llm_model_t* m = (tk_mi355x_llm_model_t*)model_handle;
+        std::lock_guard<std::mutex> lk(m->batch_mu);
+        for (auto& b : m->batchers) {
+            uint64_t v[4] = {0, 0, 0, 0};
+            b->prefix_stats(&v[0], &v[1], &v[2], &v[3]);
+            for (int i = 0; i < 4; ++i) t[i] += v[i];
+        }
+    }
+    if (prompt_rows) *prompt_rows = t[0];
+    if (kept) *kept = t[1];
+    if (copied) *copied = t[2];
+    if (copy_launches) *copy_launches = t[3];
+}
+
+int tk_mi355x_prefix_match(const int32_t* toks, int n, const int32_t* records, const int32_t* record_len, int n_slots, int stride, int self_slot, int cursor,
+                           int32_t out[3]) {
+    if (!toks || n < 1 || !records || !record_len || n_slots < 1 || n_slots > TK_MAX_ROWS || stride < 0 || self_slot < -1 || self_slot >= n_slots || cursor < -1 || !out) return -1;
+    const int32_t* recs[TK_MAX_ROWS];
+    int lens[TK_MAX_ROWS];
+    for (int s = 0; s < n_slots; ++s) {
+        if (record_len[s] < 0 || record_len[s] > stride) return -1;
+        recs[s] = records + (size_t)s * stride;
+        lens[s] = record_len[s];
+    }
+    out[0] = self_slot >= 0 ? tk_prefix_common(toks, n, recs[self_slot], lens[self_slot]) : 0;
+    if (cursor < 0) cursor = out[0];
+    int match = cursor;
+    out[1] = tk_prefix_best_donor(toks, n, recs, lens, n_slots, self_slot, cursor, nullptr, &match);
+    out[2] = match;
+    return 0;
 }
 
 uint64_t tk_mi355x_llm_model_run_ahead_wasted(void* model_handle) {
@@ -655,6 +718,7 @@ struct tk_llm_runner_s {
     int n_ctx = 0;
     int n_past = 0;
     int32_t pending = -1; /* token sampled from the last logits, not yet decoded */
+    TkLlmBatcher::PrefixRows last_prompt; /* what became of the rows of the last prepare_generation (tk_mi355x_llm_runner_last_prompt_rows) */
     /* sampling: greedy unless tk_mi355x_llm_runner_set_sampling gave a temperature; the generator is keyed by (config.random_seed, number of
      * tokens this runner has sampled since its creation), so a runner's ids do not depend on which other runners share its passes */
     TkSampleRow samp{};
@@ -703,6 +767,14 @@ static std::string load_tool_grammar_text() {
     return TK_DEFAULT_TOOL_CALL_GBNF;
 }
 
+tk_error_code_t tk_mi355x_llm_runner_last_prompt_rows(tk_llm_runner_t* runner, int32_t* prompt_rows, int32_t* kept, int32_t* copied) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    if (prompt_rows) *prompt_rows = runner->last_prompt.prompt_rows;
+    if (kept) *kept = runner->last_prompt.kept;
+    if (copied) *copied = runner->last_prompt.copied;
+    return TK_SUCCESS;
+}
+
 const char* tk_mi355x_llm_runner_tool_call_text(tk_llm_runner_t* runner) { return runner ? runner->tool_call_text.c_str() : NULL; }
 
 tk_error_code_t tk_mi355x_llm_runner_set_sampling(tk_llm_runner_t* runner, float temperature, int32_t top_k, float top_p, float min_p) {
@@ -733,6 +805,7 @@ tk_error_code_t tk_llm_runner_create(tk_llm_runner_t** out_runner, void* model_h
             std::unique_ptr<TkLlmBatcher> b(new TkLlmBatcher());
             std::string err;
             if (!b->init(&r->model->model, slots, r->n_ctx, r->model->tok.eos, &err)) return fail(TK_ERROR_GPU_MEMORY, err);
+            if (r->model->prefix_cache) (void)b->set_prefix_cache(true);
             r->slot = b->acquire_slot();
             r->batcher = b.get();
             r->model->batchers.push_back(std::move(b));
@@ -761,12 +834,14 @@ void tk_llm_runner_destroy(tk_llm_runner_t** runner) {
 }
 
 /* feed `toks` at positions n_past.. ; the last one is sampled.  The rows join whatever passes the model's scheduler is forming. */
-static tk_error_code_t feed(tk_llm_runner_s* r, const std::vector<int32_t>& toks) {
+static tk_error_code_t feed(tk_llm_runner_s* r, const std::vector<int32_t>& toks, bool whole_context = false) {
     if (toks.empty()) return TK_SUCCESS;
     if (r->n_past + (int)toks.size() >= r->n_ctx) return fail(TK_ERROR_INFERENCE_FAILED, "prompt exceeds the context window");
     int32_t am = -1;
     std::string err;
-    if (!r->batcher->submit(r->slot, r->n_past, toks.data(), (int)toks.size(), r->next_mask(), &am, &err, r->next_samp())) return fail(TK_ERROR_INFERENCE_FAILED, err);
+    /* whole_context (prepare_generation): the tokens start at position 0, so the scheduler may keep or copy rows the cache already holds for them */
+    if (!r->batcher->submit(r->slot, r->n_past, toks.data(), (int)toks.size(), r->next_mask(), &am, &err, r->next_samp(), whole_context ? &r->last_prompt : nullptr))
+        return fail(TK_ERROR_INFERENCE_FAILED, err);
     if (r->samp.temp > 0.0f) r->samp.counter++;
     r->n_past += (int)toks.size();
     r->pending = am;
@@ -783,7 +858,8 @@ tk_error_code_t tk_llm_runner_prepare_generation(tk_llm_runner_t* runner, const 
     std::vector<int32_t> toks = runner->model->tok.encode(prompt, true);
     runner->n_past = 0; /* llama_kv_cache_clear: positions restart, stale cache rows are never attended */
     runner->pending = -1;
-    tk_error_code_t rc = feed(runner, toks);
+    runner->last_prompt = TkLlmBatcher::PrefixRows{(int32_t)toks.size(), 0, 0};
+    tk_error_code_t rc = feed(runner, toks, true);
     if (rc != TK_SUCCESS) return rc;
     runner->is_processing = true;
     return TK_SUCCESS;

@@ -1,4 +1,5 @@
 #include "tk_llm_batcher.h"
+#include "tk_prefix_match.h"
 
 #include <algorithm>
 #include <chrono>
@@ -29,6 +30,8 @@ bool TkLlmBatcher::init(TkLlmModel* model, int slots, int n_ctx, int32_t eos, st
     n_ctx_ = n_ctx;
     slot_used_.assign((size_t)slots, 0);
     ahead_.assign((size_t)slots, Ahead());
+    rec_.assign((size_t)slots, std::vector<int32_t>());
+    for (auto& r : rec_) r.reserve((size_t)n_ctx);
     eos_ = eos;
     if (const char* e = getenv("TK_MI355X_BATCHER_DECODE_FIRST")) decode_first_ = e[0] == '1';
     if (const char* e = getenv("TK_MI355X_BATCHER_TRACE")) { trace_path_ = e; trace_.reserve(4096); }
@@ -56,6 +59,30 @@ void TkLlmBatcher::stats(uint64_t* passes, uint64_t* rows, int* max_rows, uint64
     if (wasted) *wasted = wasted_;
 }
 
+bool TkLlmBatcher::set_prefix_cache(bool on) {
+    if (on && !session_.kv_copy_applies()) return false;
+    std::lock_guard<std::mutex> lk(mu_);
+    prefix_cache_ = on;
+    return true;
+}
+
+void TkLlmBatcher::prefix_stats(uint64_t* prompt_rows, uint64_t* kept, uint64_t* copied, uint64_t* copy_launches) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (prompt_rows) *prompt_rows = prompt_rows_;
+    if (kept) *kept = kept_;
+    if (copied) *copied = copied_;
+    if (copy_launches) *copy_launches = copy_launches_;
+}
+
+/* a completed pass wrote the row of `tok` at `pos` of `slot`: it attended to rows 0 .. pos - 1, which are what the record lists as long as the
+ * record reaches pos (rows are fed in order, so it does; a row beyond the record's end is simply not recorded) */
+void TkLlmBatcher::record_row(int slot, int pos, int32_t tok) {
+    std::vector<int32_t>& r = rec_[(size_t)slot];
+    if ((size_t)pos > r.size()) return;
+    r.resize((size_t)pos);
+    r.push_back(tok);
+}
+
 /* the owner of `slot` has just been handed `sampled` for position pos_done: feed it at pos_done + 1 in the next pass */
 void TkLlmBatcher::plan_ahead(int slot, int pos_done, int32_t sampled, bool masked) {
     Ahead& a = ahead_[(size_t)slot];
@@ -74,12 +101,15 @@ void TkLlmBatcher::drop_ahead(int slot) {
     a = Ahead();
 }
 
-bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp) {
+bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp,
+                          PrefixRows* prefix) {
     if (n <= 0) { *err = "nothing to feed"; return false; }
     if (slot < 0 || slot >= (int)slot_used_.size() || pos0 < 0 || pos0 + n > n_ctx_) { *err = "rows do not fit the context window"; return false; }
     Request r;
     r.slot = slot; r.pos0 = pos0; r.n = n; r.toks = toks; r.mask = mask;
     if (samp) r.samp = *samp;
+    r.whole = prefix != nullptr && pos0 == 0;
+    if (prefix) *prefix = PrefixRows{n, 0, 0};
     const bool stochastic = r.samp.temp > 0.0f;
     std::unique_lock<std::mutex> lk(mu_);
     if (stop_) { *err = "scheduler stopped"; return false; }
@@ -109,6 +139,7 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
     queue_.push_back(&r);
     cv_.notify_all();
     r.cv.wait(lk, [&] { return r.finished; });
+    if (prefix) { prefix->kept = r.kept; prefix->copied = r.copied; }
     if (!r.ok) { *err = r.error; return false; }
     *sampled = r.sampled;
     return true;
@@ -123,6 +154,14 @@ void TkLlmBatcher::loop() {
     std::vector<Taken> in_pass;
     std::vector<Request*> completing;
     std::vector<AheadRow> ahead_rows;
+    /* prefix cache: the copies of the pass being formed (at most one per request of the pass), the request each serves, and the slots that are
+     * a source / a destination of this launch */
+    std::vector<TkKvCopyDesc> copies;
+    std::vector<Request*> copy_for;
+    std::vector<const int32_t*> rec_ptr(rec_.size());
+    std::vector<int> rec_len(rec_.size());
+    std::vector<char> is_src(rec_.size()), is_dst(rec_.size());
+    copies.reserve(TK_MAX_ROWS); copy_for.reserve(TK_MAX_ROWS);
     auto any_planned = [&] {
         for (const Ahead& a : ahead_) if (a.st == Ahead::PLANNED) return true;
         return false;
@@ -131,7 +170,7 @@ void TkLlmBatcher::loop() {
     auto now_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_origin).count(); };
     for (;;) {
         double t_woke = 0.0;
-        in_pass.clear(); completing.clear(); ahead_rows.clear();
+        in_pass.clear(); completing.clear(); ahead_rows.clear(); copies.clear(); copy_for.clear();
         sq.clear(); ps.clear(); tk.clear(); masks.clear(); samps.clear();
         bool any_mask = false, any_samp = false;
         {
@@ -178,10 +217,39 @@ void TkLlmBatcher::loop() {
                     any_samp = any_samp || r->samp.temp > 0.0f;
                 }
             };
+            /* prefix cache (tk_llm_batcher.h): a whole-context request that is about to enter the pass first moves its cursor over the rows its
+             * own slot holds (once), then over rows another slot holds (each pass, at the cursor where it stands) */
+            std::fill(is_src.begin(), is_src.end(), 0);
+            std::fill(is_dst.begin(), is_dst.end(), 0);
+            for (size_t s = 0; s < rec_.size(); ++s) { rec_ptr[s] = rec_[s].data(); rec_len[s] = (int)rec_[s].size(); }
+            auto use_cache = [&](Request* r) {
+                if (!r->whole) return;
+                if (!r->taken) {
+                    r->taken = true;
+                    prompt_rows_ += (uint64_t)r->n;
+                    r->cached = prefix_cache_;
+                    if (!r->cached) return;
+                    r->kept = tk_prefix_common(r->toks, r->n, rec_ptr[(size_t)r->slot], rec_len[(size_t)r->slot]);
+                    r->done_rows = r->kept;
+                    kept_ += (uint64_t)r->kept;
+                }
+                if (!r->cached || is_src[(size_t)r->slot] || is_dst[(size_t)r->slot] || (int)copies.size() >= TK_MAX_ROWS) return;
+                int match = 0;
+                const int donor = tk_prefix_best_donor(r->toks, r->n, rec_ptr.data(), rec_len.data(), (int)rec_.size(), r->slot, r->done_rows, is_dst.data(), &match);
+                if (donor < 0) return;
+                copies.push_back(TkKvCopyDesc{donor, r->slot, r->done_rows, match - r->done_rows});
+                copy_for.push_back(r);
+                is_src[(size_t)donor] = 1;
+                is_dst[(size_t)r->slot] = 1;
+                r->copied += match - r->done_rows;
+                copied_ += (uint64_t)(match - r->done_rows);
+                r->done_rows = match;
+            };
             const bool decode_first = decode_first_;
             if (decode_first)
                 for (Request* r : queue_) {
                     if ((int)sq.size() >= TK_MAX_ROWS) break;
+                    use_cache(r);
                     if (r->n - r->done_rows == 1) add_rows(r, 1);
                 }
             auto add_ahead = [&] {
@@ -200,6 +268,7 @@ void TkLlmBatcher::loop() {
             if (decode_first) add_ahead(); /* one per sequence whose owner holds the id they feed */
             for (Request* r : queue_) {
                 if ((int)sq.size() >= TK_MAX_ROWS) break;
+                use_cache(r);
                 if (decode_first && r->n - r->done_rows == 1) continue; /* taken above */
                 add_rows(r, std::min(r->n - r->done_rows, TK_MAX_ROWS - (int)sq.size()));
             }
@@ -210,13 +279,26 @@ void TkLlmBatcher::loop() {
         am.assign((size_t)nrows, -1);
         const double t_formed = trace_path_.empty() ? 0.0 : now_ms();
         const bool head = !completing.empty() || !ahead_rows.empty();
-        const bool ok = session_.forward(nrows, sq.data(), ps.data(), tk.data(), nullptr, head ? am.data() : nullptr, head, head && any_mask ? masks.data() : nullptr,
+        /* the copies go first on the session's stream: forward() then reads the copied rows, and a source row it overwrites was read before */
+        bool copied_ok = true;
+        if (!copies.empty()) copied_ok = session_.enqueue_kv_copy(copies.data(), (int)copies.size());
+        const bool ok = copied_ok && session_.forward(nrows, sq.data(), ps.data(), tk.data(), nullptr, head ? am.data() : nullptr, head, head && any_mask ? masks.data() : nullptr,
                                         head && any_samp ? samps.data() : nullptr);
         {
             std::lock_guard<std::mutex> lk(mu_);
             passes_++;
             if (nrows > max_rows_) max_rows_ = nrows;
             if (!ok) last_error_ = session_.error;
+            if (!copies.empty()) copy_launches_++;
+            /* records: what the cache holds now that the pass is complete — copied rows, then the pass's rows in feeding order */
+            if (ok) {
+                for (size_t c = 0; c < copies.size(); ++c)
+                    for (int i = 0; i < copies[c].n; ++i) record_row(copies[c].dst_seq, copies[c].p0 + i, copy_for[c]->toks[copies[c].p0 + i]);
+                for (int i = 0; i < nrows; ++i) record_row(sq[(size_t)i], ps[(size_t)i], tk[(size_t)i]);
+            } else {
+                for (const TkKvCopyDesc& c : copies) rec_[(size_t)c.dst_seq].clear();
+                for (int i = 0; i < nrows; ++i) rec_[(size_t)sq[(size_t)i]].clear();
+            }
             size_t held = 0; /* completing requests that got no run-ahead row: their owners are waited for */
             for (const Taken& t : in_pass) {
                 Request* r = t.r;

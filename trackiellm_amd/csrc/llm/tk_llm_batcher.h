@@ -17,6 +17,29 @@
  * the accepted token), not after EOS, not at the end of the context.  An owner that comes back with something else (a tool response, a
  * new prompt) or not at all costs one wasted row: the cache row it wrote is overwritten before anything attends to it, because positions
  * are fed in order.  Tokens are unchanged — a row's result does not depend on when or with whom it runs.
+ *
+ * Prompt prefix cache (set_prefix_cache, OFF by default: with it off every prompt is fed from position 0, as the reference does after its
+ * llama_kv_cache_clear, src/ai_models/tk_runner_streaming.c:31).  A cache row at position p depends only on tokens 0 .. p, and a row's bits do
+ * not depend on its pass, so a row that is already in the cache for the same leading tokens is the row a recomputation would write.
+ *   Records.  Per slot, the token id whose K/V row sits at each position (rec_).  Only the scheduler thread writes them, and only after a pass
+ *     has completed: every row (slot, pos, tok) of the pass — request rows and run-ahead rows alike — truncates the slot's record to pos and
+ *     appends tok; a failed pass clears the records of the slots it touched.  Records describe cache CONTENTS, not ownership: they survive
+ *     reset_context, a new prompt and release_slot / acquire_slot, because nothing but this scheduler's passes and copies writes the cache.
+ *   Keep.  When the scheduler first takes a request whose tokens are the whole context from position 0 (submit's `prefix` argument, set by
+ *     prepare_generation only), the request's cursor (done_rows) skips the longest common prefix of its tokens and its slot's record, at most
+ *     n - 1 rows: the last prompt token is always computed.
+ *   Copy.  Each time a pass is formed, a request that enters it looks for another slot whose record matches its tokens at least
+ *     TK_PREFIX_COPY_MIN positions beyond the cursor (tk_prefix_match.h: longest match, lowest slot on ties); rows [cursor, match) are copied
+ *     from that slot by ONE k_kv_copy_rows launch per pass for all such requests, and the cursor moves to match.  Matching reads records as
+ *     of the last completed pass; rows the pass being formed will compute are not a source, so requests that share a pass both compute.
+ *   Ordering rule.  The copy launch goes on the session stream BEFORE the pass's forward, outside any graph capture: a source slot whose owner
+ *     overwrites it in this very pass is read first.  Within a launch no slot is both a source and a destination (a request whose slot already
+ *     serves as a source in this launch, or whose best donor is a destination of it, computes this pass and looks again in the next).
+ *   Stale rows.  Positions are still fed in ascending order from the cursor, so a row beyond the cursor is overwritten before anything attends
+ *     to it, exactly as for a restart at position 0.  drop_ahead needs nothing new for a cursor > 0: a PLANNED run-ahead row never ran; a DONE
+ *     one is in the record already; an INFLIGHT one belongs to a pass that completes — and enters the record, at its position, for its token —
+ *     before the scheduler forms the next pass, which is the first moment the new prompt is matched.  The record says the truth either way: if
+ *     the new prompt continues with that very token the row is kept, otherwise the match ends before it.
  */
 #ifndef TK_LLM_BATCHER_H
 #define TK_LLM_BATCHER_H
@@ -43,7 +66,16 @@ public:
      * tokens `mask` allows, when given: (vocab + 31) / 32 words, bit t = token t).  Thread-safe; one outstanding call per slot. */
     /* samp (optional): sampling state of the sampled row — temp > 0 draws from the reference's default stochastic chain with the given
      * (seed, counter) instead of the arg max; such rows never run ahead (the next counter is the owner's) */
-    bool submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp = nullptr);
+    /* prefix (optional; prepare_generation only): the tokens are the WHOLE context from position 0 (pos0 == 0), so rows the cache already holds
+     * for them may be kept or copied when the prefix cache is on; receives what became of the n rows */
+    struct PrefixRows { int32_t prompt_rows = 0, kept = 0, copied = 0; };
+    bool submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp = nullptr,
+                PrefixRows* prefix = nullptr);
+    /* the prompt prefix cache, off by default; may change at any time, read when the scheduler first takes a prompt.  false: the model's rows are
+     * not whole 16-byte words (head_dim % 8 != 0) */
+    bool set_prefix_cache(bool on);
+    /* totals since init: prompt rows asked for through `prefix`, of them kept in place, of them copied from another slot, copy launches */
+    void prefix_stats(uint64_t* prompt_rows, uint64_t* kept, uint64_t* copied, uint64_t* copy_launches);
     /* counters for tests and bench: passes run, rows processed FOR AN OWNER (a run-ahead row counts when its owner takes it; wasted ones
      * are in *wasted), the widest pass so far */
     void stats(uint64_t* passes, uint64_t* rows, int* max_rows, uint64_t* wasted = nullptr);
@@ -51,6 +83,8 @@ public:
 private:
     struct Request {
         int slot, pos0, n, done_rows = 0;
+        bool whole = false, taken = false, cached = false; /* whole context from position 0; seen by the scheduler; the cache was on at that moment */
+        int kept = 0, copied = 0;
         const int32_t* toks;
         const uint32_t* mask;
         TkSampleRow samp{};
@@ -84,6 +118,11 @@ private:
     bool decode_first_ = false; /* TK_MI355X_BATCHER_DECODE_FIRST=1: sampled rows before prompt rows when a pass is formed (A/B; tk_llm_batcher.cpp) */
     size_t expect_ = 0; /* requests finished by the last pass: their owners are about to submit the next token */
     uint64_t passes_ = 0, rows_ = 0;
+    /* prompt prefix cache (header comment) */
+    bool prefix_cache_ = false;
+    std::vector<std::vector<int32_t>> rec_; /* [slot]: token id of the row at each position, capacity n_ctx */
+    void record_row(int slot, int pos, int32_t tok); /* scheduler thread, mu_ held, after a completed pass */
+    uint64_t prompt_rows_ = 0, kept_ = 0, copied_ = 0, copy_launches_ = 0;
     int max_rows_ = 0;
     /* TK_MI355X_BATCHER_TRACE=<file>: one line per pass (times in ms since the scheduler started: woken, pass formed, pass done; rows, of them
      * run-ahead rows, requests completed, requests still queued, graph captures so far and their host time), written when the batcher dies */

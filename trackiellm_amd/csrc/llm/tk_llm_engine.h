@@ -107,12 +107,25 @@ public:
      * parity tests use it to put an attention launch at any context length in one decode step. */
     bool kv_write(int layer, int seq, int pos0, int n_pos, const uint16_t* k, const uint16_t* v);
     bool kv_read(int layer, int seq, int pos0, int n_pos, uint16_t* k, uint16_t* v);
+    /* rows [pos0, pos0 + n_pos) of sequence src_seq copied onto the same rows of dst_seq (src_seq != dst_seq) in every layer: one launch of
+     * k_kv_copy_rows, synchronous.  A cache row at position p depends only on tokens 0 .. p, so a sequence that is to hold the same leading
+     * tokens as another can take its rows instead of recomputing them (the prompt prefix cache, tk_llm_batcher.h). */
+    bool kv_copy(int src_seq, int dst_seq, int pos0, int n_pos);
+    /* the scheduler's form: up to TK_MAX_ROWS copies in one launch on `stream`, not waited for — a forward() that follows on the stream sees the
+     * copied rows, and a source row that forward() overwrites is read first.  Descriptors are checked like kv_copy's arguments; no two share a
+     * destination and no destination is another one's source (the caller's rule: the kernel copies them in no particular order). */
+    bool enqueue_kv_copy(const TkKvCopyDesc* descs, int n);
+    bool kv_copy_applies() const { return model && model->hp.head_dim % 8 == 0; } /* 16-byte accesses need rows of whole 16-byte words */
     /* per-launch timing of the last decode(): average ms of one step measured with HIP events */
     float last_step_ms = 0.0f;
     /* stand-alone timing of the dominant GEMV (gate/up of layer 0) for bench.py's roofline leg */
     bool time_gemv(int layer, int which, int nrows, int iters, float* avg_ms, double* algo_bytes);
     /* stand-alone timing of the decode attention launch at nrows rows x ctx cached positions, for bench.py's second roofline object */
     bool time_attention(int nrows, int ctx, int iters, float* avg_ms, double* kv_bytes);
+    /* stand-alone timing of the prefix cache's copy: rows [0, n_pos) of sequence 0 onto sequences 1 .. n_dst, as ONE k_kv_copy_rows launch and as the
+     * form it replaces — a hipMemcpy2DAsync per (destination, layer, K | V) on the same stream — alternating, `iters` times after one untimed round
+     * of each, device events around each form; bytes = read + written by one round of either */
+    bool time_kv_copy(int n_pos, int n_dst, int iters, float* kernel_ms, float* memcpy_ms, double* bytes);
 
 private:
     friend class TkLlmPipe; /* tk_llm_pipe.h: a pipeline stage enqueues layer ranges of this session between its hand-off kernels */
@@ -129,6 +142,7 @@ private:
     bool mask_rows_dirty = true;    /* d_mask_row holds something other than all -1 */
     TkSampleRow* d_samp = nullptr;  /* [TK_MAX_ROWS] sampling state of the rows of the current pass (temp 0 = greedy); decode() continues from it */
     bool samp_dirty = false;        /* d_samp holds a stochastic row */
+    TkKvCopyDesc *d_kvcopy = nullptr, *h_kvcopy = nullptr; /* [TK_MAX_ROWS] descriptors of one k_kv_copy_rows launch: device array, pinned staging */
     std::string launch_error; /* set by enqueue_* when a launcher refuses its arguments (no HIP error is raised for that) */
     int hist_cap = 0;
     hipGraphExec_t graph_exec[2][TK_MAX_ROWS + 1] = {}; /* [long_pass][row count]: decode pass (head + sampling, every sequence once) */

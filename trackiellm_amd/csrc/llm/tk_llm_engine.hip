@@ -296,6 +296,9 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     HIPQ(hipMalloc((void**)&d_samp, TK_MAX_ROWS * sizeof(TkSampleRow)));
     HIPQ(hipMemset(d_samp, 0, TK_MAX_ROWS * sizeof(TkSampleRow))); /* temp 0: every row samples greedily */
     samp_dirty = false;
+    HIPQ(hipMalloc((void**)&d_kvcopy, TK_MAX_ROWS * sizeof(TkKvCopyDesc)));
+    HIPQ(hipMemset(d_kvcopy, 0, TK_MAX_ROWS * sizeof(TkKvCopyDesc)));
+    HIPQ(hipHostMalloc((void**)&h_kvcopy, TK_MAX_ROWS * sizeof(TkKvCopyDesc), hipHostMallocDefault));
     /* RoPE table, double precision on the host (same formula as the oracle) */
     std::vector<float> cs((size_t)mctx * half), sn((size_t)mctx * half);
     for (int p = 0; p < mctx; ++p)
@@ -312,6 +315,9 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     /* kernels that want more than the default 64 KiB of dynamic LDS: a per-device opt-in */
     if (const char* e = tk_llm_prepare_device(m->device)) { error = std::string("LDS opt-in failed: ") + e; return false; }
     if (m->has_f16 && !tk_gemm_tiled_prepare_device()) { error = "LDS opt-in of the tiled GEMM failed"; return false; }
+    /* the prefix cache's copy kernel runs between passes, outside any capture: launched once here, with nothing to copy, so that its code object
+     * is loaded before the first pass is recorded into a graph */
+    if (kv_copy_applies() && !enqueue_kv_copy(nullptr, 0)) return false;
     HIPQ(hipDeviceSynchronize());
     return true;
 }
@@ -325,6 +331,8 @@ TkLlmSession::~TkLlmSession() {
     for (auto& v : graph_head_nf) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     void* ptrs[] = {kcache, vcache, x, x2, qbuf, partial, partial2, logits, rope_cos, rope_sin, d_seq, d_pos, d_tok, d_nsteps, d_hist, d_mask, d_mask_row, d_samp, d_tab, d_tiles, d_scores};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (d_kvcopy) (void)hipFree(d_kvcopy);
+    if (h_kvcopy) (void)hipHostFree(h_kvcopy);
     free_act(&act_d); free_act(&act_qd); free_act(&act_ff);
     if (stream) (void)hipStreamDestroy(stream);
 }
@@ -360,6 +368,35 @@ bool TkLlmSession::kv_read(int layer, int seq, int pos0, int n_pos, uint16_t* k,
         HIPQ(hipMemcpy2DAsync(k + (size_t)kvh * h.head_dim, hd * h.n_kv_head, kcache + src, hd, hd, (size_t)n_pos, hipMemcpyDeviceToHost, stream));
         HIPQ(hipMemcpy2DAsync(v + (size_t)kvh * h.head_dim, hd * h.n_kv_head, vcache + src, hd, hd, (size_t)n_pos, hipMemcpyDeviceToHost, stream));
     }
+    HIPQ(hipStreamSynchronize(stream));
+    return true;
+}
+
+bool TkLlmSession::enqueue_kv_copy(const TkKvCopyDesc* descs, int n) {
+    const TkLlmHParams& h = model->hp;
+    if (!kv_copy_applies()) { error = "kv_copy: head_dim must be a multiple of 8"; return false; }
+    if (n < 0 || n > TK_MAX_ROWS || (n > 0 && !descs)) { error = "kv_copy: between 0 and TK_MAX_ROWS descriptors"; return false; }
+    int max_n = 0;
+    for (int i = 0; i < n; ++i) {
+        const TkKvCopyDesc& d = descs[i];
+        if (d.src_seq < 0 || d.src_seq >= max_seq || d.dst_seq < 0 || d.dst_seq >= max_seq || d.src_seq == d.dst_seq || d.p0 < 0 || d.n <= 0 || d.n > max_ctx - d.p0) {
+            error = "kv_copy: (source, destination, positions) outside the cache, or source = destination";
+            return false;
+        }
+        max_n = std::max(max_n, d.n);
+    }
+    HIPQ(hipSetDevice(model->device));
+    if (n > 0) { /* h_kvcopy is free again: whoever enqueued the previous copy has waited for the stream since (forward() and kv_copy() end with a sync) */
+        memcpy(h_kvcopy, descs, (size_t)n * sizeof(TkKvCopyDesc));
+        HIPQ(hipMemcpyAsync(d_kvcopy, h_kvcopy, (size_t)n * sizeof(TkKvCopyDesc), hipMemcpyHostToDevice, stream));
+    }
+    if (!tk_launch_kv_copy_rows(d_kvcopy, n, max_n, kcache, vcache, h.n_layer, h.n_kv_head, h.head_dim, max_seq, max_ctx, stream)) { error = "kv_copy: launch failed"; return false; }
+    return true;
+}
+
+bool TkLlmSession::kv_copy(int src_seq, int dst_seq, int pos0, int n_pos) {
+    const TkKvCopyDesc d{src_seq, dst_seq, pos0, n_pos};
+    if (!enqueue_kv_copy(&d, 1)) return false;
     HIPQ(hipStreamSynchronize(stream));
     return true;
 }
@@ -876,6 +913,46 @@ bool TkLlmSession::time_gemv(int layer, int which, int nrows, int iters, float* 
 /* stand-alone timing of the decode attention launch (k_attention, fused rope/append form) at `nrows` rows whose sequences all sit at
  * position ctx - 1: `iters` launches cycling through the layers (each layer's cache region is its own HBM range), launched as hipGraph
  * nodes like decode().  kv_bytes = the K and V rows one launch must read once: nrows * ctx * n_kv_head * head_dim * 2 B * 2. */
+bool TkLlmSession::time_kv_copy(int n_pos, int n_dst, int iters, float* kernel_ms, float* memcpy_ms, double* bytes) {
+    const TkLlmHParams& h = model->hp;
+    if (n_pos < 1 || n_pos > max_ctx || n_dst < 1 || n_dst >= max_seq || n_dst > TK_MAX_ROWS || iters < 1) { error = "bad n_pos / n_dst / iters"; return false; }
+    HIPQ(hipSetDevice(model->device));
+    std::vector<TkKvCopyDesc> ds((size_t)n_dst);
+    for (int d = 0; d < n_dst; ++d) ds[(size_t)d] = TkKvCopyDesc{0, d + 1, 0, n_pos};
+    const size_t width = (size_t)n_pos * h.head_dim * 2, pitch = (size_t)max_ctx * h.head_dim * 2; /* one KV head's run; the next head's starts a pitch on */
+    auto memcpy_form = [&]() -> bool {
+        for (int d = 0; d < n_dst; ++d)
+            for (int l = 0; l < h.n_layer; ++l) {
+                const size_t so = (((size_t)l * max_seq + 0) * h.n_kv_head) * max_ctx * h.head_dim, dof = (((size_t)l * max_seq + d + 1) * h.n_kv_head) * max_ctx * h.head_dim;
+                HIPQ(hipMemcpy2DAsync(kcache + dof, pitch, kcache + so, pitch, width, (size_t)h.n_kv_head, hipMemcpyDeviceToDevice, stream));
+                HIPQ(hipMemcpy2DAsync(vcache + dof, pitch, vcache + so, pitch, width, (size_t)h.n_kv_head, hipMemcpyDeviceToDevice, stream));
+            }
+        return true;
+    };
+    hipEvent_t e0, e1, e2;
+    HIPQ(hipEventCreate(&e0));
+    HIPQ(hipEventCreate(&e1));
+    HIPQ(hipEventCreate(&e2));
+    double k_sum = 0.0, m_sum = 0.0;
+    for (int i = -1; i < iters; ++i) { /* round -1 is the warm-up */
+        HIPQ(hipEventRecord(e0, stream));
+        if (!enqueue_kv_copy(ds.data(), n_dst)) return false;
+        HIPQ(hipEventRecord(e1, stream));
+        if (!memcpy_form()) return false;
+        HIPQ(hipEventRecord(e2, stream));
+        HIPQ(hipStreamSynchronize(stream));
+        float k = 0.0f, m = 0.0f;
+        HIPQ(hipEventElapsedTime(&k, e0, e1));
+        HIPQ(hipEventElapsedTime(&m, e1, e2));
+        if (i >= 0) { k_sum += k; m_sum += m; }
+    }
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
+    *kernel_ms = (float)(k_sum / iters);
+    *memcpy_ms = (float)(m_sum / iters);
+    *bytes = 2.0 * (double)n_dst * n_pos * h.n_layer * h.n_kv_head * h.head_dim * 2.0 * 2.0; /* read + write, K + V, f16 */
+    return true;
+}
+
 bool TkLlmSession::time_attention(int nrows, int ctx, int iters, float* avg_ms, double* kv_bytes) {
     const TkLlmHParams& h = model->hp;
     if (nrows < 1 || nrows > TK_MAX_ROWS || nrows > max_seq || ctx < 1 || ctx > max_ctx || iters < 1) { error = "bad nrows / ctx / iters"; return false; }

@@ -121,6 +121,13 @@ size_t tk_attention_long_scratch_floats(int n_head, int head_dim, int max_ctx); 
 void tk_launch_attention_long(const float* partial, int ks, int n_total, const float* rope_cos, const float* rope_sin, uint16_t* kcache, uint16_t* vcache,
                               const int32_t* seq, const int32_t* pos, int nrows, int n_head, int n_kv_head, int head_dim, int layer, int max_seq, int max_ctx,
                               float* scores, TkActQ8 out, hipStream_t s);
+/* prompt prefix cache (tk_llm_batcher.h): rows [p0, p0 + n) of sequence src_seq copied onto the same rows of dst_seq in every layer, KV head and
+ * both caches, all `ndesc` <= TK_MAX_ROWS descriptors (a device array) in one launch.  src_seq != dst_seq; no two descriptors of a launch share a
+ * destination, and no destination of a launch is another descriptor's source.  max_n = the largest n among them (sizes the grid together with the
+ * device's CU count).  ndesc = 0 launches one idle workgroup.  false: arguments the kernel does not take (head_dim % 8 != 0) or a failed launch */
+struct TkKvCopyDesc { int32_t src_seq, dst_seq, p0, n; };
+bool tk_launch_kv_copy_rows(const TkKvCopyDesc* desc, int ndesc, int max_n, uint16_t* kcache, uint16_t* vcache, int n_layer, int n_kv_head, int head_dim, int max_seq,
+                            int max_ctx, hipStream_t s);
 size_t tk_gemv_lds_bytes(int K, int ks, int mtiles);
 /* dynamic LDS of one k_attention workgroup; must stay below 160 KiB (the session checks it against its max_ctx) */
 size_t tk_attention_lds_bytes(int gq, int head_dim, int max_ctx, int chunk /* positions per ring slot: 32, 64 or 128 */);

@@ -2883,6 +2883,59 @@ void tk_launch_att_tiles(const int32_t* seq, int nrows, int32_t* tiles, hipStrea
     hipLaunchKernelGGL(k_att_tiles, dim3(1), dim3(TK_MAX_ROWS), 0, s, seq, nrows, tiles);
 }
 
+/* Prompt prefix cache (tk_llm_batcher.h): cache rows [p0, p0 + n) of sequence src_seq become the same rows of dst_seq, in every layer, KV head
+ * and both caches — a bit copy.  The cache is [layer][seq][kv_head][max_ctx][head_dim] f16, so for one (descriptor, K | V, layer, kv_head) the
+ * rows are ONE contiguous run of n * head_dim * 2 bytes, 16-byte aligned because head_dim % 8 == 0.  blockIdx.x names the run, the gridDim.y
+ * workgroups of a run stride over its 16-byte words: consecutive lanes on consecutive words, four independent loads in flight per lane. */
+#define TK_KV_COPY_THREADS 256
+#define TK_KV_COPY_UNROLL 4
+__global__ __launch_bounds__(TK_KV_COPY_THREADS) void k_kv_copy_rows(const TkKvCopyDesc* __restrict__ desc, int ndesc, uint16_t* kcache, uint16_t* vcache, int n_layer,
+                                                                     int n_kv_head, int max_seq, int max_ctx, int head_dim) {
+    int run = (int)blockIdx.x;
+    const int kvh = run % n_kv_head; run /= n_kv_head;
+    const int layer = run % n_layer; run /= n_layer;
+    const int d = run >> 1;
+    if (d >= ndesc) return;
+    const TkKvCopyDesc ds = desc[d];
+    /* the host checks every descriptor before it is sent; a bad one copies nothing rather than touching memory outside the cache */
+    if (ds.src_seq < 0 || ds.src_seq >= max_seq || ds.dst_seq < 0 || ds.dst_seq >= max_seq || ds.src_seq == ds.dst_seq || ds.p0 < 0 || ds.n <= 0 ||
+        ds.n > max_ctx - ds.p0)
+        return;
+    uint16_t* base = (run & 1) ? vcache : kcache;
+    const size_t src = ((((size_t)layer * max_seq + ds.src_seq) * n_kv_head + kvh) * max_ctx + ds.p0) * head_dim;
+    const size_t dst = ((((size_t)layer * max_seq + ds.dst_seq) * n_kv_head + kvh) * max_ctx + ds.p0) * head_dim;
+    const v4i* __restrict__ sp = (const v4i*)(base + src);
+    v4i* __restrict__ dp = (v4i*)(base + dst);
+    const int words = ds.n * (head_dim / 8);
+    const int stride = (int)gridDim.y * TK_KV_COPY_THREADS;
+    int w = (int)blockIdx.y * TK_KV_COPY_THREADS + (int)threadIdx.x;
+    for (; w + (TK_KV_COPY_UNROLL - 1) * stride < words; w += TK_KV_COPY_UNROLL * stride) {
+        v4i t[TK_KV_COPY_UNROLL];
+#pragma unroll
+        for (int u = 0; u < TK_KV_COPY_UNROLL; ++u) t[u] = sp[w + u * stride];
+#pragma unroll
+        for (int u = 0; u < TK_KV_COPY_UNROLL; ++u) dp[w + u * stride] = t[u];
+    }
+    for (; w < words; w += stride) dp[w] = sp[w];
+}
+
+bool tk_launch_kv_copy_rows(const TkKvCopyDesc* desc, int ndesc, int max_n, uint16_t* kcache, uint16_t* vcache, int n_layer, int n_kv_head, int head_dim, int max_seq,
+                            int max_ctx, hipStream_t s) {
+    if (ndesc < 0 || ndesc > TK_MAX_ROWS || max_n < 0 || max_n > max_ctx || head_dim % 8 != 0 || n_layer < 1 || n_kv_head < 1) return false;
+    /* zero descriptors: one workgroup that returns at once (sessions launch it at creation so that the code object is resident before any
+     * stream capture begins) */
+    const long runs = ndesc > 0 ? 2L * ndesc * n_layer * n_kv_head : 1;
+    /* workgroups per run: enough in flight over the whole launch to stream (8 four-wave workgroups per CU), never more than one sweep of the
+     * longest run needs (256 lanes x 4 words x 16 bytes = 16 KiB per workgroup and sweep) */
+    const long sweep = (long)TK_KV_COPY_THREADS * TK_KV_COPY_UNROLL;
+    const long need = std::max(1L, ((long)max_n * (head_dim / 8) + sweep - 1) / sweep);
+    const long want = (8L * TK_NUM_CU + runs - 1) / runs;
+    const long gy = std::min(std::min(need, want), 65535L);
+    hipLaunchKernelGGL(k_kv_copy_rows, dim3((unsigned)runs, (unsigned)std::max(1L, gy)), dim3(TK_KV_COPY_THREADS), 0, s, desc, ndesc, kcache, vcache, n_layer, n_kv_head,
+                       max_seq, max_ctx, head_dim);
+    return hipGetLastError() == hipSuccess;
+}
+
 void tk_launch_attention_prefill(const float* qbuf, const uint16_t* kcache, const uint16_t* vcache, const int32_t* seq, const int32_t* pos,
                                  const int32_t* tiles, int nrows, int n_head, int n_kv_head, int head_dim, int layer, int max_seq, int max_ctx, TkActQ8 out,
                                  hipStream_t s) {

@@ -11,6 +11,22 @@ TYPE_F32, TYPE_F16, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 0, 1, 12, 13, 14
 FTYPE_Q4_K_S, FTYPE_Q4_K_M, FTYPE_Q5_K_S, FTYPE_Q5_K_M = 14, 15, 16, 17
 
 
+def prefix_match(toks, records, self_slot=-1, cursor=-1):
+    """the prefix cache's matching rules on hand-written records (lists of token ids, one per slot), no GPU involved: (rows of `toks` kept from
+    self_slot's own record, donor slot or -1, position the donor's match ends at); cursor -1 = the kept count (tk_mi355x_prefix_match)"""
+    toks = np.ascontiguousarray(toks, dtype=np.int32)
+    stride = max([len(r) for r in records] + [1])
+    tab = np.zeros((len(records), stride), np.int32)
+    lens = np.zeros(len(records), np.int32)
+    for s, r in enumerate(records):
+        tab[s, :len(r)] = r
+        lens[s] = len(r)
+    out = (C.c_int32 * 3)()
+    if lib().tk_mi355x_prefix_match(_p(toks), len(toks), _p(tab), _p(lens), len(records), stride, int(self_slot), int(cursor), out) != 0:
+        raise ValueError("prefix_match: bad arguments")
+    return out[0], out[1], out[2]
+
+
 class LlmHParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_layer", "d_model", "n_head", "n_kv_head", "head_dim", "d_ff", "vocab")] + \
                [("rms_eps", C.c_float), ("rope_theta", C.c_float)] + \
@@ -182,6 +198,10 @@ class LlmSession:
         check(lib().tk_mi355x_llm_session_kv_read(self.h, layer, seq, pos0, n_pos, _p(k), _p(v)))
         return k, v
 
+    def kv_copy(self, src_seq, dst_seq, pos0, n_pos):
+        """rows [pos0, pos0 + n_pos) of src_seq onto the same rows of dst_seq, every layer, on the device (tk_mi355x_llm_session_kv_copy)"""
+        check(lib().tk_mi355x_llm_session_kv_copy(self.h, int(src_seq), int(dst_seq), int(pos0), int(n_pos)))
+
     def prefill(self, tokens):
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
         nseq, n_prompt = tokens.shape
@@ -206,6 +226,12 @@ class LlmSession:
         nbytes = C.c_double(0)
         check(lib().tk_mi355x_llm_time_attention(self.h, nrows, ctx, iters, C.byref(ms), C.byref(nbytes)))
         return ms.value, nbytes.value
+
+    def time_kv_copy(self, n_pos, n_dst, iters):
+        """(kernel ms, memcpy-form ms, bytes read + written) of copying rows [0, n_pos) of sequence 0 onto sequences 1 .. n_dst"""
+        k, m, nbytes = C.c_float(0), C.c_float(0), C.c_double(0)
+        check(lib().tk_mi355x_llm_time_kv_copy(self.h, n_pos, n_dst, iters, C.byref(k), C.byref(m), C.byref(nbytes)))
+        return k.value, m.value, nbytes.value
 
     def close(self):
         if self.h:
@@ -345,6 +371,21 @@ class ModelLoader:
         f.argtypes = [C.c_void_p]
         return int(f(handle))
 
+    @staticmethod
+    def set_prefix_cache(handle, on):
+        """prompt prefix cache of the runners of this model handle (off by default): prepare keeps the rows its slot already holds for the same
+        leading tokens and copies rows another slot holds; same tokens either way"""
+        check(lib().tk_mi355x_llm_model_set_prefix_cache(handle, 1 if on else 0))
+
+    @staticmethod
+    def prefix_cache_stats(handle):
+        """(prompt rows asked for by prepare, of them kept, of them copied, copy launches) over this model's schedulers"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        f = lib().tk_mi355x_llm_model_prefix_cache_stats
+        f.restype = None
+        f(handle, *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
     def close(self):
         if self.h:
             lib().tk_model_loader_destroy(C.byref(self.h))
@@ -366,6 +407,12 @@ class LlmRunner:
     def set_sampling(self, temperature, top_k=40, top_p=0.95, min_p=0.05):
         """the reference's default stochastic chain (llama_sampling_default_params) instead of greedy; temperature 0 = greedy again"""
         check(lib().tk_mi355x_llm_runner_set_sampling(self.h, C.c_float(temperature), top_k, C.c_float(top_p), C.c_float(min_p)))
+
+    def last_prompt_rows(self):
+        """(rows, of them kept in place, of them copied from another runner's slot) of the last prepare()"""
+        n, k, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        check(lib().tk_mi355x_llm_runner_last_prompt_rows(self.h, C.byref(n), C.byref(k), C.byref(c)))
+        return n.value, k.value, c.value
 
     def next_token(self):
         p = lib().tk_llm_runner_generate_next_token(self.h)
