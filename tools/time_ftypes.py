@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Q5_K against Q4_K on the MI355X (developer tool, needs the GPU): full synthetic Mistral-7B in the Q4_K_M and Q5_K_M recipes.
-Per recipe: the decode-step time at 16, 64, 128 and 256 rows (a 32-token prompt per sequence, then greedy steps through the captured
+"""The k-quant recipes against Q4_K_M on the MI355X (developer tool, needs the GPU): full synthetic Mistral-7B in the Q4_K_M, Q5_K_M,
+Q3_K_S and Q3_K_M recipes, one after the other in one process.
+Per recipe: the weight bytes a decode step streams, the decode-step time at 16, 64, 128 and 256 rows (a 32-token prompt per sequence, then greedy steps through the captured
 pass, HIP events around the loop), and the stand-alone gate | up mat-vec of layer 0 at 16 rows (tk_mi355x_llm_time_gemv: weight bytes
-plus activation and slab bytes over kernel time), so the Q5_K mat-vec's rate stands beside the Q4_K one.
+plus activation and slab bytes over kernel time), so each type's mat-vec rate stands beside the Q4_K one.
     python tools/time_ftypes.py [steps]"""
 import ctypes as C
 import os
@@ -17,10 +18,12 @@ steps = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 wb = tk.lib().tk_mi355x_llm_model_weight_bytes
 wb.restype = C.c_uint64
 base = {}
-for name, ftype in (("Q4_K_M", tk.FTYPE_Q4_K_M), ("Q5_K_M", tk.FTYPE_Q5_K_M)):
+base_bytes = 0
+for name, ftype in (("Q4_K_M", tk.FTYPE_Q4_K_M), ("Q5_K_M", tk.FTYPE_Q5_K_M), ("Q3_K_S", tk.FTYPE_Q3_K_S), ("Q3_K_M", tk.FTYPE_Q3_K_M)):
     model = tk.LlmModel(tk.MISTRAL_7B(), device=0).fill_synthetic(4, ftype=ftype)
     nbytes = wb(model.h)
-    print(f"{name}: {nbytes / 1e9:.3f} GB of weights", flush=True)
+    base_bytes = base_bytes if name != "Q4_K_M" else nbytes
+    print(f"{name}: {nbytes / 1e9:.3f} GB of weights streamed per decode step, x{nbytes / base_bytes:.3f} of Q4_K_M", flush=True)
     for rows in (16, 64, 128, 256):
         sess = tk.LlmSession(model, rows, 32 + steps + 16)
         prompts = np.random.default_rng(1).integers(3, model.hparams.vocab, (rows, 32)).astype(np.int32)

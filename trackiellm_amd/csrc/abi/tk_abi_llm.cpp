@@ -119,8 +119,21 @@ tk_error_code_t tk_mi355x_llm_gemv_probe(int device, int type, const void* block
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_quantize_blocks(int type, const float* x, int64_t n_blocks, void* out) {
+    if (!x || !out || n_blocks < 0 || (type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K && type != TK_TYPE_Q6_K))
+        return TK_ERROR_INVALID_ARGUMENT;
+    for (int64_t b = 0; b < n_blocks; ++b) {
+        const float* xb = x + 256 * b;
+        if (type == TK_TYPE_Q3_K) tk_quantize_q3_K(xb, (tk_block_q3_K*)out + b);
+        else if (type == TK_TYPE_Q4_K) tk_quantize_q4_K(xb, (tk_block_q4_K*)out + b);
+        else if (type == TK_TYPE_Q5_K) tk_quantize_q5_K(xb, (tk_block_q5_K*)out + b);
+        else tk_quantize_q6_K(xb, (tk_block_q6_K*)out + b);
+    }
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_model_fill_synthetic_ftype(tk_mi355x_llm_model_t* m, uint64_t seed, int ftype) {
-    if (!m || ftype < 14 || ftype > 17) return TK_ERROR_INVALID_ARGUMENT;
+    if (!m || !(ftype == 11 || ftype == 12 || (ftype >= 14 && ftype <= 17))) return TK_ERROR_INVALID_ARGUMENT;
     if (!m->model.fill_synthetic(seed, false, ftype)) return fail(TK_ERROR_GPU_ROCM_ERROR, m->model.error);
     return TK_SUCCESS;
 }
@@ -265,7 +278,7 @@ tk_error_code_t tk_mi355x_llm_model_load_gguf_lora(tk_mi355x_llm_model_t** out, 
         const TkGgufTensor* t = f.find(name);
         if (!t && alt) t = f.find(alt);
         if (!t) { tk_error_set_detail("GGUF tensor missing: %s", name.c_str()); return false; }
-        if (!t->data) { tk_error_set_detail("GGUF tensor %s has unsupported type %u (supported: F32, F16, Q4_K, Q5_K, Q6_K)", name.c_str(), t->type); return false; }
+        if (!t->data) { tk_error_set_detail("GGUF tensor %s has unsupported type %u (supported: F32, F16, Q3_K, Q4_K, Q5_K, Q6_K)", name.c_str(), t->type); return false; }
         if (!m->model.set_tensor(layer, which, (int)t->type, t->data, t->nbytes)) { tk_error_set_detail("%s: %s", name.c_str(), m->model.error.c_str()); return false; }
         return true;
     };

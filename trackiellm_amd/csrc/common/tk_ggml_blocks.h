@@ -16,6 +16,9 @@
  *   Q5_K: 256 weights / 176 B: Q4_K's d, dmin and 12 B of (scale, min) pairs,
  *         32 B of high bits (bit j of qh[l] = weight 32 j + l), 128 B of low
  *         nibbles laid out as Q4_K's.   w = d*sc[j]*q - dmin*m[j], q in 0..31
+ *   Q3_K: 256 weights / 110 B: 32 B of high bits (bit 4 n + j of hmask[l] =
+ *         weight 128 n + 32 j + l), 64 B of low 2-bit pairs, 12 B of packed
+ *         6-bit scales (groups of 16), f16 d.   w = d*(sc[g]-32)*q, q in -4..3
  * Host + device code (the quantisers run inside the synthetic-weight kernel
  * and inside the oracle; they are bit-identical by construction).
  */
@@ -29,6 +32,7 @@
 enum tk_ggml_type {
     TK_TYPE_F32 = 0,
     TK_TYPE_F16 = 1,
+    TK_TYPE_Q3_K = 11,
     TK_TYPE_Q4_K = 12,
     TK_TYPE_Q5_K = 13,
     TK_TYPE_Q6_K = 14,
@@ -56,11 +60,18 @@ typedef struct {
     uint16_t d;
 } tk_block_q6_K; /* 210 B */
 
+typedef struct {
+    uint8_t hmask[32];
+    uint8_t qs[64];
+    uint8_t scales[12];
+    uint16_t d;
+} tk_block_q3_K; /* 110 B */
+
 TK_HD size_t tk_type_block_bytes(int type) {
-    return type == TK_TYPE_Q4_K ? 144 : type == TK_TYPE_Q5_K ? 176 : type == TK_TYPE_Q6_K ? 210 : type == TK_TYPE_F16 ? 2 : 4;
+    return type == TK_TYPE_Q3_K ? 110 : type == TK_TYPE_Q4_K ? 144 : type == TK_TYPE_Q5_K ? 176 : type == TK_TYPE_Q6_K ? 210 : type == TK_TYPE_F16 ? 2 : 4;
 }
 TK_HD size_t tk_type_block_elems(int type) {
-    return (type == TK_TYPE_Q4_K || type == TK_TYPE_Q5_K || type == TK_TYPE_Q6_K) ? 256 : 1;
+    return (type == TK_TYPE_Q3_K || type == TK_TYPE_Q4_K || type == TK_TYPE_Q5_K || type == TK_TYPE_Q6_K) ? 256 : 1;
 }
 
 /* 6-bit (scale, min) pair j of a Q4_K block */
@@ -141,6 +152,43 @@ TK_HD void tk_q6k_set_quant(tk_block_q6_K* b, int i, int q) {
     else *qlb = (uint8_t)((*qlb & 0x0F) | ((q & 0x0F) << 4));
     uint8_t* qhb = &b->qh[n * 32 + l];
     *qhb = (uint8_t)((*qhb & ~(3 << (2 * quarter))) | ((q >> 4) << (2 * quarter)));
+}
+
+/* weight i (0..255) of a Q3_K block, q in [-4,3]: the 2-bit pair plus 4 * the mask bit, minus 4 */
+TK_HD int tk_q3k_quant(const tk_block_q3_K* b, int i) {
+    int n = i >> 7, j = (i & 127) >> 5, l = i & 31;
+    int lo = (b->qs[32 * n + l] >> (2 * j)) & 3;
+    int hi = (b->hmask[l] >> (4 * n + j)) & 1;
+    return lo + 4 * hi - 4;
+}
+
+/* scale of group g (0..15) of a Q3_K block: the stored 6 bits minus 32, in [-32,31] */
+TK_HD int tk_q3k_scale(const tk_block_q3_K* b, int g) {
+    int lo = g < 8 ? (b->scales[g] & 15) : (b->scales[g - 8] >> 4);
+    int hi = (b->scales[8 + (g & 3)] >> (2 * (g >> 2))) & 3;
+    return (lo | (hi << 4)) - 32;
+}
+
+TK_HD void tk_q3k_set_scale(tk_block_q3_K* b, int g, int s) {
+    int v = s + 32;
+    if (g < 8) b->scales[g] = (uint8_t)((b->scales[g] & 0xF0) | (v & 15));
+    else b->scales[g - 8] = (uint8_t)((b->scales[g - 8] & 0x0F) | ((v & 15) << 4));
+    uint8_t* h = &b->scales[8 + (g & 3)];
+    *h = (uint8_t)((*h & ~(3 << (2 * (g >> 2)))) | ((v >> 4) << (2 * (g >> 2))));
+}
+
+/* the expression of tk_q6k_dequant: the Q6_K block with the same d, scales[g] = this scale and q6 = q + 32 dequantises to the same bits */
+TK_HD float tk_q3k_dequant(const tk_block_q3_K* b, int i) {
+    float d = tk_f16_to_f32(b->d);
+    return (d * (float)tk_q3k_scale(b, i >> 4)) * (float)tk_q3k_quant(b, i);
+}
+
+TK_HD void tk_q3k_set_quant(tk_block_q3_K* b, int i, int q) {
+    int n = i >> 7, j = (i & 127) >> 5, l = i & 31, u = q + 4;
+    uint8_t* lo = &b->qs[32 * n + l];
+    *lo = (uint8_t)((*lo & ~(3 << (2 * j))) | ((u & 3) << (2 * j)));
+    uint8_t* hi = &b->hmask[l];
+    *hi = (uint8_t)((*hi & ~(1 << (4 * n + j))) | ((u >> 2) << (4 * n + j)));
 }
 
 /*
@@ -270,6 +318,43 @@ TK_HD void tk_quantize_q6_K(const float* x, tk_block_q6_K* out) {
                 q = q < 0 ? 0 : (q > 63 ? 63 : q);
             }
             tk_q6k_set_quant(out, 16 * g + i, q);
+        }
+    }
+}
+
+/* Q3_K: eight levels -4..3 per group of 16 and a signed 6-bit group scale.  The sign of the group scale is chosen so that the
+ * largest-magnitude weight of the group lands on -4 (the long side of the asymmetric range); d spreads the group scales over +-31 */
+TK_HD void tk_quantize_q3_K(const float* x, tk_block_q3_K* out) {
+    float gscale[16];
+    float max_abs_scale = 0.0f;
+    for (int g = 0; g < 16; ++g) {
+        float amax = 0.0f, vmax = 0.0f;
+        for (int i = 0; i < 16; ++i) {
+            float a = tk_fabsf(x[16 * g + i]);
+            if (a > amax) { amax = a; vmax = x[16 * g + i]; }
+        }
+        gscale[g] = tk_divf(-vmax, 4.0f);
+        float as = tk_fabsf(gscale[g]);
+        max_abs_scale = as > max_abs_scale ? as : max_abs_scale;
+    }
+    float d = tk_divf(max_abs_scale, 31.0f);
+    out->d = tk_f32_to_f16(d);
+    float dq = tk_f16_to_f32(out->d);
+    for (int k = 0; k < 32; ++k) out->hmask[k] = 0;
+    for (int k = 0; k < 64; ++k) out->qs[k] = 0;
+    for (int k = 0; k < 12; ++k) out->scales[k] = 0;
+    for (int g = 0; g < 16; ++g) {
+        int sc = dq > 0.0f ? (int)tk_rintf(tk_divf(gscale[g], dq)) : 0;
+        sc = sc < -32 ? -32 : (sc > 31 ? 31 : sc);
+        tk_q3k_set_scale(out, g, sc);
+        float dl = dq * (float)sc;
+        for (int i = 0; i < 16; ++i) {
+            int q = 0;
+            if (dl != 0.0f) {
+                q = (int)tk_rintf(tk_divf(x[16 * g + i], dl));
+                q = q < -4 ? -4 : (q > 3 ? 3 : q);
+            }
+            tk_q3k_set_quant(out, 16 * g + i, q);
         }
     }
 }

@@ -45,6 +45,10 @@ __global__ void k_synth_blocks(int type, uint64_t seed, uint64_t tid, int64_t nb
         tk_block_q5_K blk;
         tk_quantize_q5_K(x, &blk);
         ((tk_block_q5_K*)out)[b] = blk;
+    } else if (type == TK_TYPE_Q3_K) {
+        tk_block_q3_K blk;
+        tk_quantize_q3_K(x, &blk);
+        ((tk_block_q3_K*)out)[b] = blk;
     } else {
         tk_block_q6_K blk;
         tk_quantize_q6_K(x, &blk);
@@ -205,15 +209,44 @@ __global__ void k_repack_q5k(const tk_block_q5_K* src, int64_t nblk, uint8_t* ti
     }
 }
 
+/* Q3_K tile (tk_llm_layout.h): operand dword o = 2 j + hh (sub-block j, k0 + 4 hh .. + 3) keeps its four 3-bit quants u = q + 4 as
+ * 2-bit slot o & 3 of the bytes of low dword o >> 2 and bit o & 7 of the bytes of high dword o >> 3 */
+__global__ void k_repack_q3k(const tk_block_q3_K* src, int64_t nblk, uint8_t* tiles) {
+    const int lane = threadIdx.x;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t rt = blockIdx.y, blk = blockIdx.x;
+    const tk_block_q3_K* b = src + (rt * 16 + n) * nblk + blk;
+    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q3K_TILE_BYTES;
+    uint32_t lo[4] = {0, 0, 0, 0}, hi[2] = {0, 0};
+    for (int o = 0; o < 16; ++o) {
+        const int k0 = 32 * (o >> 1) + 8 * g + 4 * (o & 1);
+        for (int t = 0; t < 4; ++t) {
+            const int u = tk_q3k_quant(b, k0 + t) + 4;
+            lo[o >> 2] |= (uint32_t)(u & 3) << (8 * t + 2 * (o & 3));
+            hi[o >> 3] |= (uint32_t)(u >> 2) << (8 * t + (o & 7));
+        }
+    }
+    *(uint4*)(tile + lane * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    *(uint2*)(tile + 1024 + lane * 8) = make_uint2(hi[0], hi[1]);
+    if (g == 0) {
+        uint32_t sc[4] = {0, 0, 0, 0}; /* byte 8 h + j = the scale of group 2 j + h: the eight scales of one k half are one 8-byte read */
+        for (int h = 0; h < 2; ++h)
+            for (int j = 0; j < 8; ++j) sc[2 * h + (j >> 2)] |= (uint32_t)(uint8_t)tk_q3k_scale(b, 2 * j + h) << (8 * (j & 3));
+        *(uint4*)(tile + 1536 + n * 16) = make_uint4(sc[0], sc[1], sc[2], sc[3]);
+        *(uint16_t*)(tile + 1792 + n * 2) = b->d;
+    }
+}
+
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s) {
     dim3 grid((unsigned)(K / 256), (unsigned)(rows / 16));
+    if (type == TK_TYPE_Q3_K) { hipLaunchKernelGGL(k_repack_q3k, grid, dim3(64), 0, s, (const tk_block_q3_K*)blocks, K / 256, tiles); return; }
     if (type == TK_TYPE_Q4_K) hipLaunchKernelGGL(k_repack_q4k, grid, dim3(64), 0, s, (const tk_block_q4_K*)blocks, K / 256, tiles);
     else if (type == TK_TYPE_Q5_K) hipLaunchKernelGGL(k_repack_q5k, grid, dim3(64), 0, s, (const tk_block_q5_K*)blocks, K / 256, tiles);
     else hipLaunchKernelGGL(k_repack_q6k, grid, dim3(64), 0, s, (const tk_block_q6_K*)blocks, K / 256, tiles);
 }
 
 /* ------------------------------------------------------------------------------------------
- * token embedding: one Q4_K / Q5_K row (GGUF layout) de-quantised per row slot
+ * token embedding: one Q3_K / Q4_K / Q5_K row (GGUF layout) de-quantised per row slot
  * ------------------------------------------------------------------------------------------ */
 __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, float* x) {
     const int r = blockIdx.y;
@@ -224,6 +257,9 @@ __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, f
     } else if (type == TK_TYPE_Q5_K) {
         const tk_block_q5_K* row = (const tk_block_q5_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q5k_dequant(row + i / 256, i % 256);
+    } else if (type == TK_TYPE_Q3_K) {
+        const tk_block_q3_K* row = (const tk_block_q3_K*)embd + (int64_t)tok[r] * (D / 256);
+        x[(int64_t)r * D + i] = tk_q3k_dequant(row + i / 256, i % 256);
     } else {
         const tk_block_q4_K* row = (const tk_block_q4_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q4k_dequant(row + i / 256, i % 256);
@@ -418,6 +454,7 @@ void tk_launch_rmsnorm_q8(float* x, const float* partial, int ks, int n_total_pa
 struct FragQ4 { uint4 q0, q1, h; };
 struct FragQ6 { uint4 q0, q1, qh, sc; uint32_t d; };
 struct FragQ5 { uint4 q0, q1, h; uint2 qh; };
+struct FragQ3 { uint4 q; uint2 qh, sc; uint32_t d; };
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef unsigned v2u32 __attribute__((ext_vector_type(2)));
@@ -441,6 +478,18 @@ __device__ __forceinline__ FragQ5 load_q5(const uint8_t* tile, int lane) {
     const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + lane * 8));
     f.qh = make_uint2(qh.x, qh.y);
     f.h = ldg_nt(tile + 2560 + (lane & 15) * 16);
+    return f;
+}
+
+/* sc: the eight group scales of this lane's k half (lane groups 2, 3 hold k 16..31 of every sub-block) */
+__device__ __forceinline__ FragQ3 load_q3(const uint8_t* tile, int lane) {
+    FragQ3 f;
+    f.q = ldg_nt(tile + lane * 16);
+    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + lane * 8));
+    f.qh = make_uint2(qh.x, qh.y);
+    const v2u32 sc = __builtin_nontemporal_load((const v2u32*)(tile + 1536 + (lane & 15) * 16 + (lane >> 5) * 8));
+    f.sc = make_uint2(sc.x, sc.y);
+    f.d = *(const uint16_t*)(tile + 1792 + (lane & 15) * 2);
     return f;
 }
 
@@ -663,6 +712,75 @@ __device__ __forceinline__ void mma_q6(const OpsQ6& o, const uint8_t* lds_act, c
     }
 }
 
+/*
+ * Q3_K: w = d * s * q with s in -32..31 and q in -4..3, no min term.  s * q lies in -124..128, so its NEGATIVE fits one int8 and the
+ * scale folds into the B operand whole: one MFMA chain per M-tile gives -P = sum_k -(s q)_k a_k, |P| <= 256 * 128 * 127 < 2^23, and
+ * fmaf(d * d8, (float)P, acc) is the Q6_K contract of the block's Q6_K twin (scales[g] = s, q6 = q + 32) value for value.
+ * The operand bytes come from a table: per sub-block the eight bytes -(s (u - 4)), u = 0..7, and v_perm_b32 picks four of them with
+ * the four 3-bit quants of an operand dword as its selector.
+ */
+/* the table of scale s as (bytes u = 0..3, bytes u = 4..7) = (4s, 3s, 2s, s), (0, -s, -2s, -3s) mod 256 */
+__device__ __forceinline__ void q3_table(int s, uint32_t* t0, uint32_t* t1) {
+    typedef short v2s __attribute__((ext_vector_type(2)));
+    const v2s S = {(short)s, (short)s}, N = {(short)-s, (short)-s};
+    const uint32_t a = __builtin_bit_cast(uint32_t, (v2s){4, 3} * S), b = __builtin_bit_cast(uint32_t, (v2s){2, 1} * S);
+    const uint32_t na = __builtin_bit_cast(uint32_t, (v2s){4, 3} * N), nb = __builtin_bit_cast(uint32_t, (v2s){2, 1} * N);
+    *t0 = __builtin_amdgcn_perm(b, a, 0x06040200u);   /* a.0, a.2, b.0, b.2: v_perm_b32 source bytes 0..3 = second operand, 4..7 = first */
+    *t1 = __builtin_amdgcn_perm(nb, na, 0x0204060cu); /* 0, nb.2, nb.0, na.2 */
+}
+
+/* selector dword of operand dword o (tk_llm_layout.h): byte t = u of weight k0 + t */
+__device__ __forceinline__ uint32_t q3_sel(const uint32_t (&X)[4], const uint32_t (&H)[2], int o) {
+    const uint32_t lo = (X[o >> 2] >> (2 * (o & 3))) & 0x03030303u;
+    const uint32_t h = H[o >> 3];
+    return lo | (((o & 7) <= 2 ? h << (2 - (o & 7)) : h >> ((o & 7) - 2)) & 0x04040404u);
+}
+
+/* the sixteen operand dwords of one lane's k slice into b[ST * (o >> 2) + OFF][o & 3]: ST = 1 for the 16x16x64 map, 2 for the 32x32x32 one */
+template <int ST, int OFF>
+__device__ __forceinline__ void q3_operands(const uint32_t (&X)[4], const uint32_t (&H)[2], const uint32_t (&T0)[8], const uint32_t (&T1)[8], v4i* b) {
+#pragma unroll
+    for (int o = 0; o < 16; ++o) b[ST * (o >> 2) + OFF][o & 3] = (int)__builtin_amdgcn_perm(T1[o >> 1], T0[o >> 1], q3_sel(X, H, o));
+}
+
+__device__ __forceinline__ void q3_tables(uint2 sc, uint32_t (&T0)[8], uint32_t (&T1)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) q3_table((int)(int8_t)((j < 4 ? sc.x : sc.y) >> (8 * (j & 3))), &T0[j], &T1[j]);
+}
+
+__device__ __forceinline__ void unpack_q3(const FragQ3& f, OpsQ4& o) { /* bl = the operand, dw = d; bh, bm, dmin stay unused */
+    const uint32_t X[4] = {f.q.x, f.q.y, f.q.z, f.q.w}, H[2] = {f.qh.x, f.qh.y};
+    uint32_t T0[8], T1[8];
+    q3_tables(f.sc, T0, T1);
+    q3_operands<1, 0>(X, H, T0, T1, o.bl);
+    o.dw = f16bits_to_f32(f.d);
+}
+
+template <int MT>
+__device__ __forceinline__ void mma_q3(const OpsQ4& o, const uint8_t* lds_act, const float* lds_ad, size_t act_ts, int ad_ts, int blk, int lane,
+                                       float (*acc)[4]) {
+    const int g = lane >> 4;
+    const v4i zero = {0, 0, 0, 0};
+    v4i N[MT]; /* -P */
+#pragma unroll
+    for (int m = 0; m < MT; ++m) N[m] = zero;
+    const uint8_t* ap = lds_act + (size_t)blk * 4096 + lane * 16;
+#pragma unroll
+    for (int j2 = 0; j2 < 4; ++j2) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const v4i a = *(const v4i*)(ap + m * act_ts + j2 * 1024);
+            N[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, o.bl[j2], N[m], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const v4f da = *(const v4f*)(lds_ad + m * ad_ts + blk * TK_ROW_SLOTS + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[m][r] = tk_fmaf(o.dw * da[r], (float)(-N[m][r]), acc[m][r]);
+    }
+}
+
 size_t tk_gemv_lds_bytes(int K, int ks, int mtiles) {
     size_t Kr = (size_t)K / ks;
     return (size_t)mtiles * (Kr * TK_ROW_SLOTS + (Kr / 256) * TK_ROW_SLOTS * 4 + (Kr / 256) * 256);
@@ -674,8 +792,8 @@ size_t tk_gemv_lds_bytes(int K, int ks, int mtiles) {
  * so (a) every CU streams the same number of 16-row tiles (+-1), (b) the K-range's int8 activations are
  * staged once per CU, (c) all waves of a CU walk disjoint contiguous tile runs.
  */
-/* TYPES: bit 0 = the launch contains Q4_K tiles, bit 1 = Q6_K tiles, bit 2 = Q5_K tiles (only alone: tk_launch_gemv splits a mixed launch
- * with Q5_K per type); single-type launches keep only one fragment ring in registers */
+/* TYPES: bit 0 = the launch contains Q4_K tiles, bit 1 = Q6_K tiles, bit 2 = Q5_K tiles, bit 3 = Q3_K tiles (the last two only alone:
+ * tk_launch_gemv splits a mixed launch with Q5_K or Q3_K per type); single-type launches keep only one fragment ring in registers */
 /* FUSE (TkGemvArgs::fuse, MT = 1 only): 0 = the activation image comes from global memory; 1 / 2 = every workgroup forms it itself —
  * the norm's or SwiGLU's arithmetic, value for value what k_rmsnorm_q8 / k_swiglu_q8 write — under the latency of its first weight tiles */
 template <int PF, int MT, int TYPES, int FUSE>
@@ -702,7 +820,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     }
     const int type = a.seg[seg].type;
     /* compile-time tile pitch in single-type launches: tile addresses become scalar base + immediate */
-    const size_t tile_bytes = TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : TYPES == 1 ? (size_t)TK_Q4K_TILE_BYTES : TYPES == 2 ? (size_t)TK_Q6K_TILE_BYTES
+    const size_t tile_bytes = TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : TYPES == 1 ? (size_t)TK_Q4K_TILE_BYTES : TYPES == 2 ? (size_t)TK_Q6K_TILE_BYTES
                                          : (type == TK_TYPE_Q4_K ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES);
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -727,6 +845,11 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     FragQ4 f4[HAS4 ? PF : 1];
     FragQ6 f6[HAS6 ? PF : 1];
     FragQ5 f5[TYPES == 4 ? PF : 1];
+    FragQ3 f3[TYPES == 8 ? PF : 1];
+    if constexpr (TYPES == 8) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) f3[u] = load_q3(tile + (size_t)u * tile_bytes, lane);
+    }
     if (HAS4 && is4) {
 #pragma unroll
         for (int u = 0; u < PF; ++u) f4[HAS4 ? u : 0] = load_q4(tile + (size_t)u * tile_bytes, lane);
@@ -938,6 +1061,29 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q4<MT, 6>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
+    if constexpr (TYPES == 8) {
+        const uint8_t* tp = tile + PF * tile_bytes;
+#pragma unroll 1
+        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                OpsQ4 o;
+                __builtin_amdgcn_sched_barrier(0);
+                unpack_q3(f3[u], o);
+                __builtin_amdgcn_sched_barrier(0);
+                f3[u] = load_q3(tp + u * tile_bytes, lane);
+                __builtin_amdgcn_sched_barrier(0);
+                mma_q3<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            OpsQ4 o;
+            __builtin_amdgcn_sched_barrier(0);
+            unpack_q3(f3[u], o);
+            mma_q3<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
+        }
+    }
 
     const int n = a.col0 + row_base + rt * TK_TILE_ROWS + (lane & 15);
     const int g = lane >> 4;
@@ -1037,9 +1183,16 @@ struct PTile { v4i pl, ph; v4f cm, da; };
 #define TK_RING_TILE_BYTES (256 * TK_ROW_SLOTS + 512 + TK_ROW_SLOTS * 4) /* one M-tile of one 256-k block: image + f16 sums + scales */
 
 #define TK_MFMA64 __builtin_amdgcn_mfma_i32_16x16x64_i8
-/* QT: the tile type.  P = 8 Ph + Pl for Q4_K's scale digits, 64 Ph + Pl for the Q5_K / Q6_K folds; Q4_K and Q5_K have the min term */
+/* QT: the tile type.  P = 8 Ph + Pl for Q4_K's scale digits, 64 Ph + Pl for the Q5_K / Q6_K folds, -Pl for Q3_K's one chain (mma_q3);
+ * Q4_K and Q5_K have the min term */
+constexpr bool tk_has_mins(int qt) { return qt != TK_TYPE_Q6_K && qt != TK_TYPE_Q3_K; }
 template <int QT>
 __device__ __forceinline__ void finish_tile(const PTile& R, const OpsQ4& o, float* acc) {
+    if constexpr (QT == TK_TYPE_Q3_K) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = tk_fmaf(o.dw * R.da[r], (float)(-R.pl[r]), acc[r]);
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         acc[r] = tk_fmaf(o.dw * R.da[r], (float)((R.ph[r] << (QT == TK_TYPE_Q4_K ? 3 : 6)) + R.pl[r]), acc[r]);
@@ -1064,7 +1217,7 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
     const uint8_t* act[2] = {chunk + rot * 4096, chunk - rot * 4096};
     const uint8_t* amn[2] = {chunk + OFF_AMN + rot * 512, chunk + OFF_AMN - rot * 512};
     const uint8_t* adp[2] = {chunk + OFF_AD + rot * 64, chunk + OFF_AD - rot * 64};
-#define TK_LDS_TILE(slot, m) lds_tile<QT != TK_TYPE_Q6_K>(T[slot], act[(m) >= MT / 2] + (m) * 4096, amn[(m) >= MT / 2] + (m) * 512, adp[(m) >= MT / 2] + (m) * 64, lane)
+#define TK_LDS_TILE(slot, m) lds_tile<tk_has_mins(QT)>(T[slot], act[(m) >= MT / 2] + (m) * 4096, amn[(m) >= MT / 2] + (m) * 512, adp[(m) >= MT / 2] + (m) * 64, lane)
 #pragma unroll
     for (int m = 0; m < AD && m < MT; ++m) TK_LDS_TILE(m, m);
 #pragma unroll
@@ -1076,18 +1229,19 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
             c[w].pl = TK_MFMA64(t.a[0], o[w].bl[0], zero, 0, 0, 0);
-            c[w].ph = TK_MFMA64(t.a[0], o[w].bh[0], zero, 0, 0, 0);
+            if constexpr (QT != TK_TYPE_Q3_K) c[w].ph = TK_MFMA64(t.a[0], o[w].bh[0], zero, 0, 0, 0);
+            else c[w].ph = zero;
         }
 #pragma unroll
         for (int j2 = 1; j2 < 4; ++j2)
 #pragma unroll
             for (int w = 0; w < NT; ++w) {
                 c[w].pl = TK_MFMA64(t.a[j2], o[w].bl[j2], c[w].pl, 0, 0, 0);
-                c[w].ph = TK_MFMA64(t.a[j2], o[w].bh[j2], c[w].ph, 0, 0, 0);
+                if constexpr (QT != TK_TYPE_Q3_K) c[w].ph = TK_MFMA64(t.a[j2], o[w].bh[j2], c[w].ph, 0, 0, 0);
             }
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
-            if (QT != TK_TYPE_Q6_K) c[w].cm = __builtin_amdgcn_mfma_f32_16x16x32_f16(t.mn, o[w].bm16, (v4f){0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+            if (tk_has_mins(QT)) c[w].cm = __builtin_amdgcn_mfma_f32_16x16x32_f16(t.mn, o[w].bm16, (v4f){0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
             c[w].da = t.da;
         }
         if (m > 0) {
@@ -1134,7 +1288,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     const int type = a.seg[seg].type;
     constexpr bool HAS4 = (TYPES & 1) != 0, HAS6 = (TYPES & 2) != 0;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
-    const size_t tile_bytes = TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
+    const size_t tile_bytes = TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
     const size_t tile_pitch = (size_t)nblk_total * tile_bytes; /* to the same block of the next row tile */
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -1174,12 +1328,14 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     FragQ4 f4[HAS4 ? NT : 1];
     FragQ6 f6[HAS6 ? NT : 1];
     FragQ5 f5[TYPES == 4 ? NT : 1];
+    FragQ3 f3[TYPES == 8 ? NT : 1];
     if (active) {
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
             if (HAS4 && is4) f4[HAS4 ? w : 0] = load_q4(tile + w * tile_pitch, lane);
             if (HAS6 && !is4) f6[HAS6 ? w : 0] = load_q6(tile + w * tile_pitch, lane);
             if constexpr (TYPES == 4) f5[w] = load_q5(tile + w * tile_pitch, lane);
+            if constexpr (TYPES == 8) f3[w] = load_q3(tile + w * tile_pitch, lane);
         }
     }
     for (int i = 0; i < CB && i < nb; ++i) stage(i, i);
@@ -1221,6 +1377,15 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             for (int w = 0; w < NT; ++w) f5[w] = load_q5(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
             gemm_block<MT, NT, TK_TYPE_Q5_K>(o, chunk, rot, lane, acc);
+        }
+        if constexpr (TYPES == 8) {
+#pragma unroll
+            for (int w = 0; w < NT; ++w) unpack_q3(f3[w], o[w]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NT; ++w) f3[w] = load_q3(next + w * tile_pitch, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            gemm_block<MT, NT, TK_TYPE_Q3_K>(o, chunk, rot, lane, acc);
         }
     }
     if (!active) return;
@@ -1376,6 +1541,24 @@ __device__ __forceinline__ void unpack_q5_x32(const FragQ5& f0, const FragQ5& f1
     o.dmin = f16bits_to_f32(hdr.x >> 16);
 }
 
+/* the Q3_K operand (unpack_q3) on the 32x32x32 map: the six packed dwords take the lane swap, the table is that of the lane's own row and
+ * k half (lane half h holds k 16 h .. 16 h + 15 of every sub-block: the scales its own load fetched) */
+__device__ __forceinline__ void unpack_q3_x32(const FragQ3& f0, const FragQ3& f1, int lane, Ops32& o) {
+    const bool up = (lane & 16) != 0;
+    const uint32_t x0[4] = {f0.q.x, f0.q.y, f0.q.z, f0.q.w}, x1[4] = {f1.q.x, f1.q.y, f1.q.z, f1.q.w};
+    uint32_t Xa[4], Xb[4], Ha[2], Hb[2];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) pair_swap(x0[c], x1[c], &Xa[c], &Xb[c]);
+    pair_swap(f0.qh.x, f1.qh.x, &Ha[0], &Hb[0]);
+    pair_swap(f0.qh.y, f1.qh.y, &Ha[1], &Hb[1]);
+    uint32_t T0[8], T1[8];
+    q3_tables(make_uint2(up ? f1.sc.x : f0.sc.x, up ? f1.sc.y : f0.sc.y), T0, T1);
+    q3_operands<2, 0>(Xa, Ha, T0, T1, o.bl);
+    q3_operands<2, 1>(Xb, Hb, T0, T1, o.bl);
+    o.dw = f16bits_to_f32(up ? f1.d : f0.d);
+    o.dmin = 0.0f;
+}
+
 /* s_waitcnt vmcnt(n) alone (expcnt / lgkmcnt untouched): until all but this wave's n youngest vector-memory operations are done.  The
  * LDS-DMA pieces of a chunk are invisible to the compiler's own wait insertion, so the ring is guarded by hand. */
 __device__ __forceinline__ void wait_vmcnt(int n) {
@@ -1412,7 +1595,7 @@ template <int QT>
 __device__ __forceinline__ void load_atile32(ATile32& T, const Ptrs32& p, int t) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) T.a[u] = *(const v4i*)(p.ap + t * 8192 + (u >> 1) * 1024 + (u & 1) * 256);
-    if (QT != TK_TYPE_Q6_K) T.mn = *(const v8h*)(p.mp + t * 1024);
+    if (tk_has_mins(QT)) T.mn = *(const v8h*)(p.mp + t * 1024);
 }
 
 /* one 256-k block: this wave's 32 weight rows x its four 32-row M-tiles.  T arrives holding tile 0's operands; the operands of tile
@@ -1428,7 +1611,7 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
         /* P = 8 Ph + Pl (64 Ph + Pl for Q6_K) inside ONE accumulator: the high-digit chain first, its result shifted on the VALU, then the
          * low-digit chain on top of it (sixteen live registers fewer than two accumulators, and the finishing below needs no shift-add);
          * the independent min-term MFMA sits where the shift waits for the last high-digit MFMA.  Q5_K: 64 Ph + Pl with the min term */
-        constexpr bool MINS = QT != TK_TYPE_Q6_K;
+        constexpr bool MINS = tk_has_mins(QT); /* Q3_K: the low chain alone, from zero, holding -P */
         v4i A[8];
 #pragma unroll
         for (int u = 0; u < 4; ++u) A[u] = T.a[u];
@@ -1440,8 +1623,10 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
         v16i ph = zero;
         v16f cm;
         v16i pl;
+        if constexpr (QT != TK_TYPE_Q3_K) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) ph = TK_MFMA32(A[u], o.bh[u], ph, 0, 0, 0);
+            for (int u = 0; u < 8; ++u) ph = TK_MFMA32(A[u], o.bh[u], ph, 0, 0, 0);
+        }
         if (MINS) {
             const v16f fz = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
             cm = __builtin_amdgcn_mfma_f32_32x32x16_f16(T.mn, o.bm16, fz, 0, 0, 0);
@@ -1460,7 +1645,7 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int r = 4 * b + i;
-                acc[t][r] = tk_fmaf(o.dw * da[b][i], (float)pl[r], acc[t][r]);
+                acc[t][r] = tk_fmaf(o.dw * da[b][i], (float)(QT == TK_TYPE_Q3_K ? -pl[r] : pl[r]), acc[t][r]);
                 if (MINS) acc[t][r] = tk_fmaf(-(o.dmin * da[b][i]), cm[r], acc[t][r]);
             }
         __builtin_amdgcn_sched_barrier(0);
@@ -1470,13 +1655,23 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
 template <int QT> struct G32Frag { typedef FragQ4 type; };
 template <> struct G32Frag<TK_TYPE_Q6_K> { typedef FragQ6 type; };
 template <> struct G32Frag<TK_TYPE_Q5_K> { typedef FragQ5 type; };
+template <> struct G32Frag<TK_TYPE_Q3_K> { typedef FragQ3 type; };
 /* `tile` is wave-uniform (an SGPR pair); the per-lane offsets are 32-bit and opaque per call, so the loads take the scalar-base form and no
  * 64-bit per-lane address is hoisted out of the K loop and held across it (load_q4 / load_q6 with a lane pointer cost 12 registers there) */
 template <int QT>
 __device__ __forceinline__ typename G32Frag<QT>::type g32_load(const uint8_t* tile, int lane) {
     unsigned lo = (unsigned)lane * 16u, ho = (unsigned)(lane & 15) * 16u;
     asm volatile("" : "+v"(lo), "+v"(ho));
-    if constexpr (QT == TK_TYPE_Q5_K) {
+    if constexpr (QT == TK_TYPE_Q3_K) {
+        FragQ3 f;
+        f.q = ldg_nt(tile + lo);
+        const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + (lo >> 1)));
+        f.qh = make_uint2(qh.x, qh.y);
+        const v2u32 sc = __builtin_nontemporal_load((const v2u32*)(tile + 1536 + ho + ((lo >> 6) & 8u)));
+        f.sc = make_uint2(sc.x, sc.y);
+        f.d = *(const uint16_t*)(tile + 1792 + (ho >> 3));
+        return f;
+    } else if constexpr (QT == TK_TYPE_Q5_K) {
         FragQ5 f;
         f.q0 = ldg_nt(tile + lo);
         f.q1 = ldg_nt(tile + 1024 + lo);
@@ -1504,6 +1699,7 @@ template <int QT>
 __device__ __forceinline__ void g32_unpack(const typename G32Frag<QT>::type& f0, const typename G32Frag<QT>::type& f1, int lane, Ops32& o) {
     if constexpr (QT == TK_TYPE_Q4_K) unpack_q4_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_x32(f0, f1, lane, o);
+    else if constexpr (QT == TK_TYPE_Q3_K) unpack_q3_x32(f0, f1, lane, o);
     else unpack_q6_x32(f0, f1, lane, o);
 }
 
@@ -1597,7 +1793,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     const int type = a.seg[seg].type;
     constexpr bool HAS4 = (TYPES & 1) != 0, HAS6 = (TYPES & 2) != 0;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
-    const size_t tile_bytes = TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
+    const size_t tile_bytes = TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
     const ptrdiff_t tile_pitch = a.swiglu ? a.seg[1].tiles - a.seg[0].tiles : (ptrdiff_t)((size_t)nblk_total * tile_bytes);
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -1655,6 +1851,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     if (HAS4 && is4) g32_k_loop<TK_TYPE_Q4_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if (HAS6 && !is4) g32_k_loop<TK_TYPE_Q6_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (TYPES == 4) g32_k_loop<TK_TYPE_Q5_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (TYPES == 8) g32_k_loop<TK_TYPE_Q3_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -1730,29 +1927,31 @@ static constexpr int TK_GEMM32_FROM_ROWS = 12 * TK_ROW_SLOTS + 1;
 typedef void (*TkGemvKernel)(TkGemvArgs, int, int);
 typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
 /* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone.  Type index =
- * types - 1 for Q4_K / Q6_K / both, 3 for Q5_K alone (tk_launch_gemv) */
-static const TkGemvKernel k_gemv_fns[3][2][2][4] = {
-    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>},
-      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>}},
-     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>},
-      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>}}},
+ * types - 1 for Q4_K / Q6_K / both, 3 for Q5_K alone, 4 for Q3_K alone (tk_launch_gemv) */
+static const TkGemvKernel k_gemv_fns[3][2][2][5] = {
+    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>},
+      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>}},
+     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>},
+      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>}}},
 };
 /* [mt / 2 - 2][type index] */
-static const TkGemvKernel k_gemm_fns[5][4] = {
-    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>},     {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>},
-    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>},     {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>},
-    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>},
+static const TkGemvKernel k_gemm_fns[5][5] = {
+    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>},
+    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>},
+    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>},
+    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>},
+    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>},
 };
 /* [type index] */
-static const TkGemm32Kernel k_gemm32_fns[4] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>};
+static const TkGemm32Kernel k_gemm32_fns[5] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>};
 
 void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
     int types = 0;
-    for (int i = 0; i < a.nseg; ++i) types |= a.seg[i].type == TK_TYPE_Q4_K ? 1 : a.seg[i].type == TK_TYPE_Q5_K ? 4 : 2;
-    if ((types & 4) && types != 4) {
-        /* Q5_K beside another type (Q4_K_S, Q5_K_M layers): one launch per run of same-type segments, each writing its own columns of
+    for (int i = 0; i < a.nseg; ++i) types |= a.seg[i].type == TK_TYPE_Q4_K ? 1 : a.seg[i].type == TK_TYPE_Q5_K ? 4 : a.seg[i].type == TK_TYPE_Q3_K ? 8 : 2;
+    if ((types & 12) && types != 4 && types != 8) {
+        /* Q5_K or Q3_K beside another type (Q4_K_S, Q5_K_M, Q3_K_M, Q3_K_L layers): one launch per run of same-type segments, each writing its own columns of
          * the same slabs; a fused producer then runs once per launch and writes the same values.  (swiglu launches are single-type:
          * tk_gemv_fuses_swiglu) */
         int i0 = 0, col = a.col0;
@@ -1769,7 +1968,7 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
         }
         return;
     }
-    const int ti = types == 4 ? 3 : types - 1; /* index into the kernel tables */
+    const int ti = types == 8 ? 4 : types == 4 ? 3 : types - 1; /* index into the kernel tables */
     int row_tiles = 0;
     for (int i = 0; i < a.nseg; ++i) row_tiles += a.seg[i].row_tiles;
     int groups = TK_NUM_CU / a.ks;            /* workgroups per K-range */
@@ -3116,7 +3315,7 @@ void tk_launch_quant_q8(const float* hbuf, int FF, int nrows, TkActQ8 out, hipSt
 
 bool tk_gemv_fuses_swiglu(int nrows, int ks, int type_gate, int type_up) {
     return nrows >= TK_GEMM32_FROM_ROWS && ks == 1 && type_gate == type_up &&
-           (type_gate == TK_TYPE_Q4_K || type_gate == TK_TYPE_Q5_K || type_gate == TK_TYPE_Q6_K); /* the 32x32x32 kernel's epilogue */
+           (type_gate == TK_TYPE_Q3_K || type_gate == TK_TYPE_Q4_K || type_gate == TK_TYPE_Q5_K || type_gate == TK_TYPE_Q6_K); /* the 32x32x32 kernel's epilogue */
 }
 
 void tk_launch_swiglu_q8(const float* partial, int ks, int FF, int nrows, TkActQ8 out, hipStream_t s) {

@@ -20,6 +20,13 @@
  *                    4 i + s (s = 0..3): the high bit of the weight in byte y of operand dword lo / hi (k0 + y / k0 + 4 + y) of
  *                    sub-block 4 i + s sits at bit 8y + s / 8y + 4 + s, so one shift and one mask put it at bit 4 of its byte
  *      [2560 ,2816)  16 rows x {f16 d, f16 dmin, 12 B packed 6-bit scales/mins} verbatim
+ *  Q3_K tile (1824 B = 16 x 114): weights stored as u = q + 4 (0..7).  Operand dword o = 2 j + hh (o = 0..15) of lane l holds the four
+ *  weights k0 + 4 hh + t (t = 0..3, k0 = 32 j + 8 g) of sub-block j, as in the tiles above
+ *      [0    ,1024)  one load: lane l -> 4 dwords; bits 8 t + 2 (o & 3) .. + 1 of dword o >> 2 = u & 3 of weight t of operand dword o
+ *      [1024 ,1536)  lane l -> 2 dwords; bit 8 t + (o & 7) of dword o >> 3 = u >> 2 of weight t of operand dword o
+ *                    (one shift and one mask per part put the four 3-bit u of an operand dword at bits 0..2 of its bytes)
+ *      [1536 ,1792)  16 rows x 16 int8 group scales s = sc6 - 32, byte 8 h + j = group 2 j + h: a lane reads the 8 bytes of its k half
+ *      [1792 ,1824)  16 x f16 d
  *  Q6_K tile (3360 B = 16 x 210): weights stored as 6-bit two's complement q' = (q - 32) & 63
  *      [0    ,2048)  two loads as above holding the LOW nibbles of q'
  *      [2048 ,3072)  lane l -> 4 dwords; dword u covers sub-blocks 2u, 2u+1: the 2 high bits of
@@ -52,6 +59,7 @@
 #include <stdint.h>
 
 #define TK_TILE_ROWS 16
+#define TK_Q3K_TILE_BYTES 1824
 #define TK_Q4K_TILE_BYTES 2304
 #define TK_Q5K_TILE_BYTES 2816
 #define TK_Q6K_TILE_BYTES 3360

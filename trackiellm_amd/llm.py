@@ -7,8 +7,9 @@ from ._lib import check, lib
 
 
 # GGUF tensor types the LLM path loads, and llama.cpp's k-quant file types (fill_synthetic(ftype=...))
-TYPE_F32, TYPE_F16, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 0, 1, 12, 13, 14
-FTYPE_Q4_K_S, FTYPE_Q4_K_M, FTYPE_Q5_K_S, FTYPE_Q5_K_M = 14, 15, 16, 17
+TYPE_F32, TYPE_F16, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 0, 1, 11, 12, 13, 14
+FTYPE_Q3_K_S, FTYPE_Q3_K_M, FTYPE_Q4_K_S, FTYPE_Q4_K_M, FTYPE_Q5_K_S, FTYPE_Q5_K_M = 11, 12, 14, 15, 16, 17
+BLOCK_BYTES = {TYPE_Q3_K: 110, TYPE_Q4_K: 144, TYPE_Q5_K: 176, TYPE_Q6_K: 210}
 
 
 def prefix_match(toks, records, self_slot=-1, cursor=-1):
@@ -41,6 +42,16 @@ def lora_probe(path):
     r, a, n = C.c_int32(0), C.c_float(0), C.c_int32(0)
     check(lib().tk_mi355x_lora_probe(path.encode(), C.byref(r), C.byref(a), C.byref(n)))
     return r.value, a.value, n.value
+
+
+def quantize_blocks(ttype, x):
+    """the build's own block quantiser on the host, no GPU (tk_mi355x_quantize_blocks): x [..., 256 n] float32 -> uint8 [n_blocks][block bytes]
+    of k-quant `ttype`"""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 256)
+    out = np.empty((x.shape[0], BLOCK_BYTES[ttype]), np.uint8)
+    lib().tk_mi355x_quantize_blocks.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    check(lib().tk_mi355x_quantize_blocks(ttype, _p(x), x.shape[0], _p(out)))
+    return out
 
 
 def gemv_probe(ttype, blocks, rows, K, ks, x, device=0):
