@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""The k-quant recipes against Q4_K_M on the MI355X (developer tool, needs the GPU): full synthetic Mistral-7B in the Q4_K_M, Q5_K_M,
-Q3_K_S and Q3_K_M recipes, one after the other in one process.
-Per recipe: the weight bytes a decode step streams, the decode-step time at 16, 64, 128 and 256 rows (a 32-token prompt per sequence, then greedy steps through the captured
-pass, HIP events around the loop), and the stand-alone gate | up mat-vec of layer 0 at 16 rows (tk_mi355x_llm_time_gemv: weight bytes
-plus activation and slab bytes over kernel time), so each type's mat-vec rate stands beside the Q4_K one.
-    python tools/time_ftypes.py [steps]"""
+"""The k-quant recipes against Q4_K_M on the MI355X (developer tool, needs the GPU): full synthetic Mistral-7B models in the named
+recipes, all resident in one process and timed INTERLEAVED: every repeat walks the widths 16, 64, 128 and 256 rows and, per width, every
+recipe in turn, so a drift of the machine lands on all recipes alike.
+Per recipe: the weight bytes a decode step streams and the stand-alone gate | up mat-vec of layer 0 at 16 rows (tk_mi355x_llm_time_gemv:
+weight bytes plus activation and slab bytes over kernel time).  Per width and recipe: the median decode-step time over the repeats (a
+32-token prompt per sequence, 4 warm-up steps, then greedy steps through the captured pass, HIP events around the loop) and its ratio to
+Q4_K_M's median; for Q4_K_M also the spread of its repeats, the yardstick for every ratio beside it.
+    python tools/time_ftypes.py [steps [repeats [recipe ...]]]      recipes: Q2_K Q2_K_S Q3_K_S Q3_K_M Q4_K_S Q5_K_S Q5_K_M"""
 import ctypes as C
 import os
 import sys
@@ -14,29 +16,49 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import trackiellm_amd as tk  # noqa: E402
 
+FTYPES = {"Q2_K": tk.FTYPE_Q2_K, "Q2_K_S": tk.FTYPE_Q2_K_S, "Q3_K_S": tk.FTYPE_Q3_K_S, "Q3_K_M": tk.FTYPE_Q3_K_M, "Q4_K_S": tk.FTYPE_Q4_K_S,
+          "Q4_K_M": tk.FTYPE_Q4_K_M, "Q5_K_S": tk.FTYPE_Q5_K_S, "Q5_K_M": tk.FTYPE_Q5_K_M}
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+names = ["Q4_K_M"] + [n for n in (sys.argv[3:] or ["Q5_K_M", "Q3_K_S", "Q3_K_M", "Q2_K", "Q2_K_S"]) if n != "Q4_K_M"]
+for n in names:
+    if n not in FTYPES:
+        sys.exit(f"unknown recipe {n}; known: {' '.join(FTYPES)}")
 wb = tk.lib().tk_mi355x_llm_model_weight_bytes
 wb.restype = C.c_uint64
-base = {}
-base_bytes = 0
-for name, ftype in (("Q4_K_M", tk.FTYPE_Q4_K_M), ("Q5_K_M", tk.FTYPE_Q5_K_M), ("Q3_K_S", tk.FTYPE_Q3_K_S), ("Q3_K_M", tk.FTYPE_Q3_K_M)):
-    model = tk.LlmModel(tk.MISTRAL_7B(), device=0).fill_synthetic(4, ftype=ftype)
-    nbytes = wb(model.h)
-    base_bytes = base_bytes if name != "Q4_K_M" else nbytes
-    print(f"{name}: {nbytes / 1e9:.3f} GB of weights streamed per decode step, x{nbytes / base_bytes:.3f} of Q4_K_M", flush=True)
-    for rows in (16, 64, 128, 256):
-        sess = tk.LlmSession(model, rows, 32 + steps + 16)
-        prompts = np.random.default_rng(1).integers(3, model.hparams.vocab, (rows, 32)).astype(np.int32)
-        prompts[:, 0] = 1
-        sess.prefill(prompts)
-        sess.decode(rows, 4)
-        _, ms = sess.decode(rows, steps)
-        rel = f", x{ms / base[rows]:.3f} of Q4_K_M" if rows in base and name != "Q4_K_M" else ""
-        base.setdefault(rows, ms)
-        print(f"{name} {rows:3d} rows: {ms:.3f} ms per decode step, weights at {nbytes / ms / 1e9:.2f} TB/s{rel}", flush=True)
-        if rows == 16:
-            gms, gbytes = sess.time_gemv(0, 0, 16, 50)
-            print(f"{name} ffn_gate|up mat-vec, layer 0, 16 rows: {gms * 1e3:.1f} us, {gbytes / gms / 1e9:.2f} TB/s = {gbytes / gms / 1e9 / 8:.3f} of 8 TB/s",
-                  flush=True)
-        sess.close()
-    model.close()
+WIDTHS = (16, 64, 128, 256)
+
+models, nbytes = {}, {}
+for name in names:
+    models[name] = tk.LlmModel(tk.MISTRAL_7B(), device=0).fill_synthetic(4, ftype=FTYPES[name])
+    nbytes[name] = wb(models[name].h)
+    print(f"{name}: {nbytes[name] / 1e9:.3f} GB of weights streamed per decode step, x{nbytes[name] / nbytes['Q4_K_M']:.3f} of Q4_K_M", flush=True)
+
+ms = {(n, r): [] for n in names for r in WIDTHS}
+for rep in range(repeats):
+    for rows in WIDTHS:
+        for name in names:
+            model = models[name]
+            sess = tk.LlmSession(model, rows, 32 + steps + 16)
+            prompts = np.random.default_rng(1).integers(3, model.hparams.vocab, (rows, 32)).astype(np.int32)
+            prompts[:, 0] = 1
+            sess.prefill(prompts)
+            sess.decode(rows, 4)
+            _, t = sess.decode(rows, steps)
+            ms[(name, rows)].append(t)
+            if rows == 16 and rep == 0:
+                gms, gbytes = sess.time_gemv(0, 0, 16, 50)
+                print(f"{name} ffn_gate|up mat-vec, layer 0, 16 rows: {gms * 1e3:.1f} us, {gbytes / gms / 1e9:.2f} TB/s = {gbytes / gms / 1e9 / 8:.3f} of 8 TB/s",
+                      flush=True)
+            sess.close()
+
+for rows in WIDTHS:
+    base = float(np.median(ms[("Q4_K_M", rows)]))
+    for name in names:
+        v = ms[(name, rows)]
+        med = float(np.median(v))
+        tail = (f", repeats {min(v):.3f} .. {max(v):.3f} ms: spread {100 * (max(v) - min(v)) / med:.1f} % of the median" if name == "Q4_K_M"
+                else f", x{med / base:.3f} of Q4_K_M (repeats x{min(v) / base:.3f} .. x{max(v) / base:.3f})")
+        print(f"{name} {rows:3d} rows: {med:.3f} ms per decode step (median of {repeats}), weights at {nbytes[name] / med / 1e9:.2f} TB/s{tail}", flush=True)
+for m in models.values():
+    m.close()

@@ -132,8 +132,14 @@ tk_error_code_t tk_mi355x_quantize_blocks(int type, const float* x, int64_t n_bl
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_quantize_blocks_q2k(const float* x, int64_t n_blocks, void* out) {
+    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
+    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_q2_K(x + 256 * b, (tk_block_q2_K*)out + b);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_model_fill_synthetic_ftype(tk_mi355x_llm_model_t* m, uint64_t seed, int ftype) {
-    if (!m || !(ftype == 11 || ftype == 12 || (ftype >= 14 && ftype <= 17))) return TK_ERROR_INVALID_ARGUMENT;
+    if (!m || !(ftype == 10 || ftype == 11 || ftype == 12 || (ftype >= 14 && ftype <= 17) || ftype == 21)) return TK_ERROR_INVALID_ARGUMENT;
     if (!m->model.fill_synthetic(seed, false, ftype)) return fail(TK_ERROR_GPU_ROCM_ERROR, m->model.error);
     return TK_SUCCESS;
 }
@@ -278,7 +284,7 @@ tk_error_code_t tk_mi355x_llm_model_load_gguf_lora(tk_mi355x_llm_model_t** out, 
         const TkGgufTensor* t = f.find(name);
         if (!t && alt) t = f.find(alt);
         if (!t) { tk_error_set_detail("GGUF tensor missing: %s", name.c_str()); return false; }
-        if (!t->data) { tk_error_set_detail("GGUF tensor %s has unsupported type %u (supported: F32, F16, Q3_K, Q4_K, Q5_K, Q6_K)", name.c_str(), t->type); return false; }
+        if (!t->data) { tk_error_set_detail("GGUF tensor %s has unsupported type %u (supported: F32, F16, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K)", name.c_str(), t->type); return false; }
         if (!m->model.set_tensor(layer, which, (int)t->type, t->data, t->nbytes)) { tk_error_set_detail("%s: %s", name.c_str(), m->model.error.c_str()); return false; }
         return true;
     };
@@ -690,12 +696,17 @@ tk_error_code_t tk_model_loader_load_model(tk_model_loader_t* loader, const tk_m
         tk_mi355x_llm_hparams_t h{};
         const bool f16 = name.size() > 4 && name.compare(name.size() - 4, 4, "-f16") == 0; /* the fp16 checkpoint recipe (BASELINE configs[4]) */
         if (f16) name.resize(name.size() - 4);
+        int ftype = 0; /* the Q2_K recipes of fill_synthetic_ftype: synthetic://mistral-7b-q2k, synthetic://tiny-q2ks */
+        if (name.size() > 5 && name.compare(name.size() - 5, 5, "-q2ks") == 0) { ftype = 21; name.resize(name.size() - 5); }
+        else if (name.size() > 4 && name.compare(name.size() - 4, 4, "-q2k") == 0) { ftype = 10; name.resize(name.size() - 4); }
         if (name == "mistral-7b") h = tk_mi355x_llm_hparams_t{32, 4096, 32, 8, 128, 14336, 32000, 1e-5f, 10000.0f, 0, 0, 0, 0, 1};
         else if (name == "tiny") h = tk_mi355x_llm_hparams_t{2, 256, 8, 2, 64, 512, 512, 1e-5f, 10000.0f, 0, 0, 0, 0, 1};
         else return fail(TK_ERROR_FILE_NOT_FOUND, "unknown synthetic model: " + name);
         rc = tk_mi355x_llm_model_create(&m, &h, device);
         if (rc == TK_SUCCESS && !lora.empty()) rc = tk_mi355x_llm_model_set_lora(m, lora.c_str());
-        if (rc == TK_SUCCESS) rc = f16 ? tk_mi355x_llm_model_fill_synthetic_f16(m, seed) : tk_mi355x_llm_model_fill_synthetic(m, seed);
+        if (rc == TK_SUCCESS)
+            rc = f16 ? tk_mi355x_llm_model_fill_synthetic_f16(m, seed)
+                     : ftype ? tk_mi355x_llm_model_fill_synthetic_ftype(m, seed, ftype) : tk_mi355x_llm_model_fill_synthetic(m, seed);
         if (rc != TK_SUCCESS) { if (m) release_model(m); return rc; } /* g_models_mu is held here */
         if (m->lora) { m->model.lora = nullptr; m->lora->drop_factors(); }
         m->path = path;

@@ -19,6 +19,10 @@
  *   Q3_K: 256 weights / 110 B: 32 B of high bits (bit 4 n + j of hmask[l] =
  *         weight 128 n + 32 j + l), 64 B of low 2-bit pairs, 12 B of packed
  *         6-bit scales (groups of 16), f16 d.   w = d*(sc[g]-32)*q, q in -4..3
+ *   Q2_K: 256 weights / 84 B: 16 B of (scale, min) nibble pairs (groups of
+ *         16: low nibble the scale, high nibble the min), 64 B of 2-bit quants
+ *         (weight 128 n + 32 j + l = (qs[32 n + l] >> 2 j) & 3), f16 d, f16
+ *         dmin.   w = d*sc[g]*q - dmin*m[g], q in 0..3
  * Host + device code (the quantisers run inside the synthetic-weight kernel
  * and inside the oracle; they are bit-identical by construction).
  */
@@ -32,6 +36,7 @@
 enum tk_ggml_type {
     TK_TYPE_F32 = 0,
     TK_TYPE_F16 = 1,
+    TK_TYPE_Q2_K = 10,
     TK_TYPE_Q3_K = 11,
     TK_TYPE_Q4_K = 12,
     TK_TYPE_Q5_K = 13,
@@ -67,11 +72,19 @@ typedef struct {
     uint16_t d;
 } tk_block_q3_K; /* 110 B */
 
+typedef struct {
+    uint8_t scales[16];
+    uint8_t qs[64];
+    uint16_t d;
+    uint16_t dmin;
+} tk_block_q2_K; /* 84 B */
+
 TK_HD size_t tk_type_block_bytes(int type) {
+    if (type == TK_TYPE_Q2_K) return 84;
     return type == TK_TYPE_Q3_K ? 110 : type == TK_TYPE_Q4_K ? 144 : type == TK_TYPE_Q5_K ? 176 : type == TK_TYPE_Q6_K ? 210 : type == TK_TYPE_F16 ? 2 : 4;
 }
 TK_HD size_t tk_type_block_elems(int type) {
-    return (type == TK_TYPE_Q3_K || type == TK_TYPE_Q4_K || type == TK_TYPE_Q5_K || type == TK_TYPE_Q6_K) ? 256 : 1;
+    return (type == TK_TYPE_Q2_K || type == TK_TYPE_Q3_K || type == TK_TYPE_Q4_K || type == TK_TYPE_Q5_K || type == TK_TYPE_Q6_K) ? 256 : 1;
 }
 
 /* 6-bit (scale, min) pair j of a Q4_K block */
@@ -189,6 +202,31 @@ TK_HD void tk_q3k_set_quant(tk_block_q3_K* b, int i, int q) {
     *lo = (uint8_t)((*lo & ~(3 << (2 * j))) | ((u & 3) << (2 * j)));
     uint8_t* hi = &b->hmask[l];
     *hi = (uint8_t)((*hi & ~(1 << (4 * n + j))) | ((u >> 2) << (4 * n + j)));
+}
+
+/* weight i (0..255) of a Q2_K block, q in [0,3] */
+TK_HD int tk_q2k_quant(const tk_block_q2_K* b, int i) {
+    int n = i >> 7, j = (i & 127) >> 5, l = i & 31;
+    return (b->qs[32 * n + l] >> (2 * j)) & 3;
+}
+
+/* scale and min of group g (0..15) of a Q2_K block, both in [0,15] */
+TK_HD int tk_q2k_scale(const tk_block_q2_K* b, int g) { return b->scales[g] & 15; }
+TK_HD int tk_q2k_min(const tk_block_q2_K* b, int g) { return b->scales[g] >> 4; }
+
+TK_HD void tk_q2k_set_scale(tk_block_q2_K* b, int g, int s) { b->scales[g] = (uint8_t)((b->scales[g] & 0xF0) | (s & 15)); }
+TK_HD void tk_q2k_set_min(tk_block_q2_K* b, int g, int m) { b->scales[g] = (uint8_t)((b->scales[g] & 0x0F) | ((m & 15) << 4)); }
+
+/* the expression of tk_q4k_dequant: the Q4_K block with the same d, dmin, (scale, min) and quants dequantises to the same bits */
+TK_HD float tk_q2k_dequant(const tk_block_q2_K* b, int i) {
+    float d = tk_f16_to_f32(b->d), dmin = tk_f16_to_f32(b->dmin);
+    return (d * (float)tk_q2k_scale(b, i >> 4)) * (float)tk_q2k_quant(b, i) - dmin * (float)tk_q2k_min(b, i >> 4);
+}
+
+TK_HD void tk_q2k_set_quant(tk_block_q2_K* b, int i, int q) {
+    int n = i >> 7, j = (i & 127) >> 5, l = i & 31;
+    uint8_t* p = &b->qs[32 * n + l];
+    *p = (uint8_t)((*p & ~(3 << (2 * j))) | ((q & 3) << (2 * j)));
 }
 
 /*
@@ -355,6 +393,49 @@ TK_HD void tk_quantize_q3_K(const float* x, tk_block_q3_K* out) {
                 q = q < -4 ? -4 : (q > 3 ? 3 : q);
             }
             tk_q3k_set_quant(out, 16 * g + i, q);
+        }
+    }
+}
+
+/* Q2_K: tk_quantize_q4_K with four levels per group of 16 and 4-bit fractions of d and dmin */
+TK_HD void tk_quantize_q2_K(const float* x, tk_block_q2_K* out) {
+    float scales[16], mins[16];
+    float max_scale = 0.0f, max_min = 0.0f;
+    for (int g = 0; g < 16; ++g) {
+        float mn = x[16 * g], mx = x[16 * g];
+        for (int i = 1; i < 16; ++i) {
+            float v = x[16 * g + i];
+            mn = v < mn ? v : mn;
+            mx = v > mx ? v : mx;
+        }
+        if (mn > 0.0f) mn = 0.0f;
+        scales[g] = tk_divf(mx - mn, 3.0f);
+        if (scales[g] < 0.0f) scales[g] = 0.0f;
+        mins[g] = -mn;
+        max_scale = scales[g] > max_scale ? scales[g] : max_scale;
+        max_min = mins[g] > max_min ? mins[g] : max_min;
+    }
+    float d = tk_divf(max_scale, 15.0f), dmin = tk_divf(max_min, 15.0f);
+    out->d = tk_f32_to_f16(d);
+    out->dmin = tk_f32_to_f16(dmin);
+    float dq = tk_f16_to_f32(out->d), dminq = tk_f16_to_f32(out->dmin);
+    for (int k = 0; k < 16; ++k) out->scales[k] = 0;
+    for (int k = 0; k < 64; ++k) out->qs[k] = 0;
+    for (int g = 0; g < 16; ++g) {
+        int sc = dq > 0.0f ? (int)tk_rintf(tk_divf(scales[g], dq)) : 0;
+        int m = dminq > 0.0f ? (int)tk_rintf(tk_divf(mins[g], dminq)) : 0;
+        sc = sc > 15 ? 15 : sc;
+        m = m > 15 ? 15 : m;
+        tk_q2k_set_scale(out, g, sc);
+        tk_q2k_set_min(out, g, m);
+        float dl = dq * (float)sc, ml = dminq * (float)m;
+        for (int i = 0; i < 16; ++i) {
+            int q = 0;
+            if (dl > 0.0f) {
+                q = (int)tk_rintf(tk_divf(x[16 * g + i] + ml, dl));
+                q = q < 0 ? 0 : (q > 3 ? 3 : q);
+            }
+            tk_q2k_set_quant(out, 16 * g + i, q);
         }
     }
 }

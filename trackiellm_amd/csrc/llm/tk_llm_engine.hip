@@ -35,12 +35,19 @@ static int use_more_bits(int i, int n) { return i < n / 8 || i >= 7 * n / 8 || (
 
 /* ftype 15 Q4_K_M / 17 Q5_K_M: the base type, Q6_K for v / down of use_more_bits layers; 16 Q5_K_S: all Q5_K; 14 Q4_K_S: Q4_K, Q5_K for v of
  * layers < 4 and down of layers < n_layer / 8; 11 Q3_K_S: all Q3_K; 12 Q3_K_M: Q3_K, v Q5_K for layers < 2 else Q4_K, o Q4_K, down Q5_K
- * for layers < n_layer / 16 else Q4_K.  output is Q6_K in all six */
+ * for layers < n_layer / 16 else Q4_K; 10 Q2_K: Q2_K, v Q4_K when n_head / n_kv_head >= 4 else Q3_K, o and down Q3_K; 21 Q2_K_S: Q2_K,
+ * v Q4_K when n_head / n_kv_head >= 4, down Q4_K for layers < n_layer / 8.  output is Q6_K in all eight */
 int TkLlmModel::recipe_type(const TkLlmHParams& hp, int layer, int which, int ftype) {
-    const int base = ftype == 11 || ftype == 12 ? TK_TYPE_Q3_K : ftype == 16 || ftype == 17 ? TK_TYPE_Q5_K : TK_TYPE_Q4_K;
+    const int base = ftype == 10 || ftype == 21 ? TK_TYPE_Q2_K : ftype == 11 || ftype == 12 ? TK_TYPE_Q3_K : ftype == 16 || ftype == 17 ? TK_TYPE_Q5_K : TK_TYPE_Q4_K;
     if (layer < 0) return which == TK_T_OUTPUT ? TK_TYPE_Q6_K : (which == TK_T_TOKEN_EMBD ? base : TK_TYPE_F32);
     if (which == TK_L_ATTN_NORM || which == TK_L_FFN_NORM) return TK_TYPE_F32;
     if (ftype == 11) return base;
+    if (ftype == 10 || ftype == 21) {
+        const bool gqa4 = hp.n_kv_head > 0 && hp.n_head / hp.n_kv_head >= 4;
+        if (which == TK_L_V) return gqa4 ? TK_TYPE_Q4_K : ftype == 10 ? TK_TYPE_Q3_K : base;
+        if (ftype == 10) return which == TK_L_O || which == TK_L_DOWN ? TK_TYPE_Q3_K : base;
+        return which == TK_L_DOWN && layer < hp.n_layer / 8 ? TK_TYPE_Q4_K : base;
+    }
     if (ftype == 12) {
         if (which == TK_L_V) return layer < 2 ? TK_TYPE_Q5_K : TK_TYPE_Q4_K;
         if (which == TK_L_O) return TK_TYPE_Q4_K;
@@ -124,6 +131,7 @@ bool TkLlmModel::install(TkDevTensor* t, int type, int64_t rows, int64_t cols, v
         if (ok && !taken) {
             error = type == TK_TYPE_Q5_K ? "LoRA merge needs a Q4_K, Q6_K or F16 matrix: merging into a Q5_K matrix is not built"
                     : type == TK_TYPE_Q3_K ? "LoRA merge needs a Q4_K, Q6_K or F16 matrix: merging into a Q3_K matrix is not built"
+                    : type == TK_TYPE_Q2_K ? "LoRA merge needs a Q4_K, Q6_K or F16 matrix: merging into a Q2_K matrix is not built"
                                          : "LoRA merge needs a Q4_K, Q6_K or F16 matrix with columns % 256 == 0";
             return false;
         }
@@ -149,15 +157,16 @@ bool TkLlmModel::install(TkDevTensor* t, int type, int64_t rows, int64_t cols, v
         }
         return true;
     }
-    if (type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K && type != TK_TYPE_Q6_K) {
-        error = "unsupported tensor type (want F32, F16, Q3_K, Q4_K, Q5_K or Q6_K)";
+    if (type != TK_TYPE_Q2_K && type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K && type != TK_TYPE_Q6_K) {
+        error = "unsupported tensor type (want F32, F16, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K)";
         return false;
     }
     t->bytes = (size_t)rows * cols / 256 * tk_type_block_bytes(type);
     if (type == TK_TYPE_Q3_K && is_matrix) t->bytes = (size_t)(rows / TK_TILE_ROWS) * (cols / 256) * TK_Q3K_TILE_BYTES; /* int8 scales: 114 B per block */
+    if (type == TK_TYPE_Q2_K && is_matrix) t->bytes = (size_t)(rows / TK_TILE_ROWS) * (cols / 256) * TK_Q2K_TILE_BYTES;
     HIPQ(hipMalloc((void**)&t->data, t->bytes));
     if (!is_matrix) { /* token_embd stays in GGUF layout: one row is gathered per token */
-        if (type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K) { error = "token_embd must be Q3_K, Q4_K, Q5_K or F16"; return false; }
+        if (type != TK_TYPE_Q2_K && type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K) { error = "token_embd must be Q2_K, Q3_K, Q4_K, Q5_K or F16"; return false; }
         HIPQ(hipMemcpyAsync(t->data, dev_blocks, t->bytes, hipMemcpyDeviceToDevice, s));
         return true;
     }
@@ -422,8 +431,8 @@ static TkGemvSeg seg_of(const TkDevTensor& t) { return TkGemvSeg{t.data, t.type,
 
 bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, int ks, int nrows, const float* x, float* y,
                        std::string& error) {
-    if (type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K && type != TK_TYPE_Q6_K) {
-        error = "gemv probe: type must be Q3_K, Q4_K, Q5_K or Q6_K";
+    if (type != TK_TYPE_Q2_K && type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K && type != TK_TYPE_Q6_K) {
+        error = "gemv probe: type must be Q2_K, Q3_K, Q4_K, Q5_K or Q6_K";
         return false;
     }
     if (rows < 64 || rows % 64 || rows > (1 << 20) || ks < 1 || ks > 8 || K < 256 || K % (256 * (int64_t)ks) || K > 65536 || nrows < 1 ||
@@ -431,11 +440,10 @@ bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, i
         error = "gemv probe: needs rows % 64 == 0, ks in [1, 8], K % (256 ks) == 0, nrows in [1, 256]";
         return false;
     }
-    if (tk_gemv_lds_bytes((int)K, ks, 2) + (size_t)K * 4 + 16 > 160 * 1024) { error = "gemv probe: K / ks too long for the mat-vec's LDS image"; return false; }
     HIPQ(hipSetDevice(device));
     if (const char* e = tk_llm_prepare_device(device)) { error = e; return false; }
     const size_t nblk = (size_t)rows * (size_t)(K / 256), bb = tk_type_block_bytes(type);
-    const size_t tb = type == TK_TYPE_Q3_K ? TK_Q3K_TILE_BYTES : type == TK_TYPE_Q4_K ? TK_Q4K_TILE_BYTES : type == TK_TYPE_Q5_K ? TK_Q5K_TILE_BYTES : TK_Q6K_TILE_BYTES;
+    const size_t tb = type == TK_TYPE_Q2_K ? TK_Q2K_TILE_BYTES : type == TK_TYPE_Q3_K ? TK_Q3K_TILE_BYTES : type == TK_TYPE_Q4_K ? TK_Q4K_TILE_BYTES : type == TK_TYPE_Q5_K ? TK_Q5K_TILE_BYTES : TK_Q6K_TILE_BYTES;
     const size_t nout = (size_t)ks * TK_MAX_ROWS * (size_t)rows;
     void* db = nullptr;
     uint8_t* tiles = nullptr;

@@ -49,6 +49,10 @@ __global__ void k_synth_blocks(int type, uint64_t seed, uint64_t tid, int64_t nb
         tk_block_q3_K blk;
         tk_quantize_q3_K(x, &blk);
         ((tk_block_q3_K*)out)[b] = blk;
+    } else if (type == TK_TYPE_Q2_K) {
+        tk_block_q2_K blk;
+        tk_quantize_q2_K(x, &blk);
+        ((tk_block_q2_K*)out)[b] = blk;
     } else {
         tk_block_q6_K blk;
         tk_quantize_q6_K(x, &blk);
@@ -237,8 +241,31 @@ __global__ void k_repack_q3k(const tk_block_q3_K* src, int64_t nblk, uint8_t* ti
     }
 }
 
+/* Q2_K tile (tk_llm_layout.h): the Q3_K tile's low part alone, the (scale, min) bytes ordered by k half, then (d, dmin) */
+__global__ void k_repack_q2k(const tk_block_q2_K* src, int64_t nblk, uint8_t* tiles) {
+    const int lane = threadIdx.x;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t rt = blockIdx.y, blk = blockIdx.x;
+    const tk_block_q2_K* b = src + (rt * 16 + n) * nblk + blk;
+    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q2K_TILE_BYTES;
+    uint32_t q[4] = {0, 0, 0, 0};
+    for (int o = 0; o < 16; ++o) {
+        const int k0 = 32 * (o >> 1) + 8 * g + 4 * (o & 1);
+        for (int t = 0; t < 4; ++t) q[o >> 2] |= (uint32_t)tk_q2k_quant(b, k0 + t) << (8 * t + 2 * (o & 3));
+    }
+    *(uint4*)(tile + lane * 16) = make_uint4(q[0], q[1], q[2], q[3]);
+    if (g == 0) {
+        uint32_t sm[4] = {0, 0, 0, 0};
+        for (int h = 0; h < 2; ++h)
+            for (int j = 0; j < 8; ++j) sm[2 * h + (j >> 2)] |= (uint32_t)b->scales[2 * j + h] << (8 * (j & 3));
+        *(uint4*)(tile + 1024 + n * 16) = make_uint4(sm[0], sm[1], sm[2], sm[3]);
+        *(uint32_t*)(tile + 1280 + n * 4) = (uint32_t)b->d | ((uint32_t)b->dmin << 16);
+    }
+}
+
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s) {
     dim3 grid((unsigned)(K / 256), (unsigned)(rows / 16));
+    if (type == TK_TYPE_Q2_K) { hipLaunchKernelGGL(k_repack_q2k, grid, dim3(64), 0, s, (const tk_block_q2_K*)blocks, K / 256, tiles); return; }
     if (type == TK_TYPE_Q3_K) { hipLaunchKernelGGL(k_repack_q3k, grid, dim3(64), 0, s, (const tk_block_q3_K*)blocks, K / 256, tiles); return; }
     if (type == TK_TYPE_Q4_K) hipLaunchKernelGGL(k_repack_q4k, grid, dim3(64), 0, s, (const tk_block_q4_K*)blocks, K / 256, tiles);
     else if (type == TK_TYPE_Q5_K) hipLaunchKernelGGL(k_repack_q5k, grid, dim3(64), 0, s, (const tk_block_q5_K*)blocks, K / 256, tiles);
@@ -246,7 +273,7 @@ void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uin
 }
 
 /* ------------------------------------------------------------------------------------------
- * token embedding: one Q3_K / Q4_K / Q5_K row (GGUF layout) de-quantised per row slot
+ * token embedding: one Q2_K / Q3_K / Q4_K / Q5_K row (GGUF layout) de-quantised per row slot
  * ------------------------------------------------------------------------------------------ */
 __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, float* x) {
     const int r = blockIdx.y;
@@ -260,6 +287,9 @@ __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, f
     } else if (type == TK_TYPE_Q3_K) {
         const tk_block_q3_K* row = (const tk_block_q3_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q3k_dequant(row + i / 256, i % 256);
+    } else if (type == TK_TYPE_Q2_K) {
+        const tk_block_q2_K* row = (const tk_block_q2_K*)embd + (int64_t)tok[r] * (D / 256);
+        x[(int64_t)r * D + i] = tk_q2k_dequant(row + i / 256, i % 256);
     } else {
         const tk_block_q4_K* row = (const tk_block_q4_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q4k_dequant(row + i / 256, i % 256);
@@ -455,6 +485,7 @@ struct FragQ4 { uint4 q0, q1, h; };
 struct FragQ6 { uint4 q0, q1, qh, sc; uint32_t d; };
 struct FragQ5 { uint4 q0, q1, h; uint2 qh; };
 struct FragQ3 { uint4 q; uint2 qh, sc; uint32_t d; };
+struct FragQ2 { uint4 q; uint2 sm; uint32_t dd; };
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef unsigned v2u32 __attribute__((ext_vector_type(2)));
@@ -490,6 +521,16 @@ __device__ __forceinline__ FragQ3 load_q3(const uint8_t* tile, int lane) {
     const v2u32 sc = __builtin_nontemporal_load((const v2u32*)(tile + 1536 + (lane & 15) * 16 + (lane >> 5) * 8));
     f.sc = make_uint2(sc.x, sc.y);
     f.d = *(const uint16_t*)(tile + 1792 + (lane & 15) * 2);
+    return f;
+}
+
+/* sm: the eight (scale, min) bytes of this lane's k half; dd = d | dmin << 16 */
+__device__ __forceinline__ FragQ2 load_q2(const uint8_t* tile, int lane) {
+    FragQ2 f;
+    f.q = ldg_nt(tile + lane * 16);
+    const v2u32 sm = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + (lane & 15) * 16 + (lane >> 5) * 8));
+    f.sm = make_uint2(sm.x, sm.y);
+    f.dd = *(const uint32_t*)(tile + 1280 + (lane & 15) * 4);
     return f;
 }
 
@@ -781,6 +822,73 @@ __device__ __forceinline__ void mma_q3(const OpsQ4& o, const uint8_t* lds_act, c
     }
 }
 
+/*
+ * Q2_K: w = d * s * q - dmin * m per group of 16, s and m in 0..15, q in 0..3.  s * q <= 45 fits an int8, so the scale folds into the B
+ * operand whole: the four possible bytes {0, s, 2s, 3s} of a group are one dword and v_perm_b32 picks four of them with the four 2-bit
+ * quants of an operand dword as its selector.  One MFMA chain per M-tile gives P = sum_k (s q)_k a_k.  The min term is a second chain over
+ * the SAME int8 activation image whose B bytes are the group's m: M = sum_k m_g(k) a_k = sum_g m_g sum_{k in g} a_k, so no 16-wide sum
+ * image is needed and the activation quantisers are untouched.  |P| <= 256 * 45 * 127 and |M| <= 256 * 15 * 127, both below 2^23: the two
+ * fp32 FMAs per block are those of the block's Q4_K twin (paired groups) and, with dmin = 0, of its Q6_K twin.
+ */
+/* per sub-block j of this lane's k half: T[j] = the bytes {0, s, 2s, 3s}, R[j] = the min in all four bytes */
+__device__ __forceinline__ void q2_tables(uint2 sm, uint32_t (&T)[8], uint32_t (&R)[8]) {
+    const uint32_t sc[2] = {sm.x & 0x0F0F0F0Fu, sm.y & 0x0F0F0F0Fu}, mn[2] = {(sm.x >> 4) & 0x0F0F0F0Fu, (sm.y >> 4) & 0x0F0F0F0Fu};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const unsigned short s = (unsigned short)((sc[j >> 2] >> (8 * (j & 3))) & 0xFFu);
+        T[j] = __builtin_bit_cast(uint32_t, (v2u16){0x0100, 0x0302} * (v2u16){s, s}); /* 3 s <= 45: no carry between the bytes */
+        R[j] = __builtin_amdgcn_perm(0u, mn[j >> 2], 0x01010101u * (uint32_t)(j & 3));
+    }
+}
+
+/* the sixteen operand dwords of one lane's k slice and their min-chain twins into bl / bh[ST * (o >> 2) + OFF][o & 3] (q3_operands) */
+template <int ST, int OFF>
+__device__ __forceinline__ void q2_operands(const uint32_t (&X)[4], const uint32_t (&T)[8], const uint32_t (&R)[8], v4i* bl, v4i* bh) {
+#pragma unroll
+    for (int o = 0; o < 16; ++o) {
+        bl[ST * (o >> 2) + OFF][o & 3] = (int)__builtin_amdgcn_perm(0u, T[o >> 1], (X[o >> 2] >> (2 * (o & 3))) & 0x03030303u);
+        bh[ST * (o >> 2) + OFF][o & 3] = (int)R[o >> 1];
+    }
+}
+
+__device__ __forceinline__ void unpack_q2(const FragQ2& f, OpsQ4& o) { /* bl = the scaled operand, bh = the mins; bm, bm16 stay unused */
+    const uint32_t X[4] = {f.q.x, f.q.y, f.q.z, f.q.w};
+    uint32_t T[8], R[8];
+    q2_tables(f.sm, T, R);
+    q2_operands<1, 0>(X, T, R, o.bl, o.bh);
+    o.dw = f16bits_to_f32(f.dd & 0xffffu);
+    o.dmin = f16bits_to_f32(f.dd >> 16);
+}
+
+template <int MT>
+__device__ __forceinline__ void mma_q2(const OpsQ4& o, const uint8_t* lds_act, const float* lds_ad, size_t act_ts, int ad_ts, int blk, int lane,
+                                       float (*acc)[4]) {
+    const int g = lane >> 4;
+    const v4i zero = {0, 0, 0, 0};
+    v4i P[MT], M[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) P[m] = M[m] = zero;
+    const uint8_t* ap = lds_act + (size_t)blk * 4096 + lane * 16;
+#pragma unroll
+    for (int j2 = 0; j2 < 4; ++j2) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const v4i a = *(const v4i*)(ap + m * act_ts + j2 * 1024);
+            P[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, o.bl[j2], P[m], 0, 0, 0);
+            M[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, o.bh[j2], M[m], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const v4f da = *(const v4f*)(lds_ad + m * ad_ts + blk * TK_ROW_SLOTS + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            acc[m][r] = tk_fmaf(o.dw * da[r], (float)P[m][r], acc[m][r]);
+            acc[m][r] = tk_fmaf(-(o.dmin * da[r]), (float)M[m][r], acc[m][r]);
+        }
+    }
+}
+
 size_t tk_gemv_lds_bytes(int K, int ks, int mtiles) {
     size_t Kr = (size_t)K / ks;
     return (size_t)mtiles * (Kr * TK_ROW_SLOTS + (Kr / 256) * TK_ROW_SLOTS * 4 + (Kr / 256) * 256);
@@ -792,8 +900,9 @@ size_t tk_gemv_lds_bytes(int K, int ks, int mtiles) {
  * so (a) every CU streams the same number of 16-row tiles (+-1), (b) the K-range's int8 activations are
  * staged once per CU, (c) all waves of a CU walk disjoint contiguous tile runs.
  */
-/* TYPES: bit 0 = the launch contains Q4_K tiles, bit 1 = Q6_K tiles, bit 2 = Q5_K tiles, bit 3 = Q3_K tiles (the last two only alone:
- * tk_launch_gemv splits a mixed launch with Q5_K or Q3_K per type); single-type launches keep only one fragment ring in registers */
+/* TYPES: bit 0 = the launch contains Q4_K tiles, bit 1 = Q6_K tiles, bit 2 = Q5_K tiles, bit 3 = Q3_K tiles, bit 4 = Q2_K tiles (the last
+ * three only alone: tk_launch_gemv splits a mixed launch with Q5_K, Q3_K or Q2_K per type); single-type launches keep only one fragment
+ * ring in registers */
 /* FUSE (TkGemvArgs::fuse, MT = 1 only): 0 = the activation image comes from global memory; 1 / 2 = every workgroup forms it itself —
  * the norm's or SwiGLU's arithmetic, value for value what k_rmsnorm_q8 / k_swiglu_q8 write — under the latency of its first weight tiles */
 template <int PF, int MT, int TYPES, int FUSE>
@@ -820,7 +929,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     }
     const int type = a.seg[seg].type;
     /* compile-time tile pitch in single-type launches: tile addresses become scalar base + immediate */
-    const size_t tile_bytes = TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : TYPES == 1 ? (size_t)TK_Q4K_TILE_BYTES : TYPES == 2 ? (size_t)TK_Q6K_TILE_BYTES
+    const size_t tile_bytes = TYPES == 16 ? (size_t)TK_Q2K_TILE_BYTES : TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : TYPES == 1 ? (size_t)TK_Q4K_TILE_BYTES : TYPES == 2 ? (size_t)TK_Q6K_TILE_BYTES
                                          : (type == TK_TYPE_Q4_K ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES);
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -846,9 +955,14 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     FragQ6 f6[HAS6 ? PF : 1];
     FragQ5 f5[TYPES == 4 ? PF : 1];
     FragQ3 f3[TYPES == 8 ? PF : 1];
+    FragQ2 f2[TYPES == 16 ? PF : 1];
     if constexpr (TYPES == 8) {
 #pragma unroll
         for (int u = 0; u < PF; ++u) f3[u] = load_q3(tile + (size_t)u * tile_bytes, lane);
+    }
+    if constexpr (TYPES == 16) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) f2[u] = load_q2(tile + (size_t)u * tile_bytes, lane);
     }
     if (HAS4 && is4) {
 #pragma unroll
@@ -1084,6 +1198,29 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q3<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
+    if constexpr (TYPES == 16) {
+        const uint8_t* tp = tile + PF * tile_bytes;
+#pragma unroll 1
+        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                OpsQ4 o;
+                __builtin_amdgcn_sched_barrier(0);
+                unpack_q2(f2[u], o);
+                __builtin_amdgcn_sched_barrier(0);
+                f2[u] = load_q2(tp + u * tile_bytes, lane);
+                __builtin_amdgcn_sched_barrier(0);
+                mma_q2<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            OpsQ4 o;
+            __builtin_amdgcn_sched_barrier(0);
+            unpack_q2(f2[u], o);
+            mma_q2<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
+        }
+    }
 
     const int n = a.col0 + row_base + rt * TK_TILE_ROWS + (lane & 15);
     const int g = lane >> 4;
@@ -1184,13 +1321,21 @@ struct PTile { v4i pl, ph; v4f cm, da; };
 
 #define TK_MFMA64 __builtin_amdgcn_mfma_i32_16x16x64_i8
 /* QT: the tile type.  P = 8 Ph + Pl for Q4_K's scale digits, 64 Ph + Pl for the Q5_K / Q6_K folds, -Pl for Q3_K's one chain (mma_q3);
- * Q4_K and Q5_K have the min term */
-constexpr bool tk_has_mins(int qt) { return qt != TK_TYPE_Q6_K && qt != TK_TYPE_Q3_K; }
+ * Q4_K and Q5_K have the min term on the sub-block sums.  Q2_K: P = Pl and its min term M = Ph, the second int8 chain (mma_q2) */
+constexpr bool tk_has_mins(int qt) { return qt != TK_TYPE_Q6_K && qt != TK_TYPE_Q3_K && qt != TK_TYPE_Q2_K; }
 template <int QT>
 __device__ __forceinline__ void finish_tile(const PTile& R, const OpsQ4& o, float* acc) {
     if constexpr (QT == TK_TYPE_Q3_K) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[r] = tk_fmaf(o.dw * R.da[r], (float)(-R.pl[r]), acc[r]);
+        return;
+    }
+    if constexpr (QT == TK_TYPE_Q2_K) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            acc[r] = tk_fmaf(o.dw * R.da[r], (float)R.pl[r], acc[r]);
+            acc[r] = tk_fmaf(-(o.dmin * R.da[r]), (float)R.ph[r], acc[r]);
+        }
         return;
     }
 #pragma unroll
@@ -1288,7 +1433,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     const int type = a.seg[seg].type;
     constexpr bool HAS4 = (TYPES & 1) != 0, HAS6 = (TYPES & 2) != 0;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
-    const size_t tile_bytes = TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
+    const size_t tile_bytes = TYPES == 16 ? (size_t)TK_Q2K_TILE_BYTES : TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
     const size_t tile_pitch = (size_t)nblk_total * tile_bytes; /* to the same block of the next row tile */
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -1329,6 +1474,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     FragQ6 f6[HAS6 ? NT : 1];
     FragQ5 f5[TYPES == 4 ? NT : 1];
     FragQ3 f3[TYPES == 8 ? NT : 1];
+    FragQ2 f2[TYPES == 16 ? NT : 1];
     if (active) {
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
@@ -1336,6 +1482,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             if (HAS6 && !is4) f6[HAS6 ? w : 0] = load_q6(tile + w * tile_pitch, lane);
             if constexpr (TYPES == 4) f5[w] = load_q5(tile + w * tile_pitch, lane);
             if constexpr (TYPES == 8) f3[w] = load_q3(tile + w * tile_pitch, lane);
+            if constexpr (TYPES == 16) f2[w] = load_q2(tile + w * tile_pitch, lane);
         }
     }
     for (int i = 0; i < CB && i < nb; ++i) stage(i, i);
@@ -1386,6 +1533,15 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             for (int w = 0; w < NT; ++w) f3[w] = load_q3(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
             gemm_block<MT, NT, TK_TYPE_Q3_K>(o, chunk, rot, lane, acc);
+        }
+        if constexpr (TYPES == 16) {
+#pragma unroll
+            for (int w = 0; w < NT; ++w) unpack_q2(f2[w], o[w]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NT; ++w) f2[w] = load_q2(next + w * tile_pitch, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            gemm_block<MT, NT, TK_TYPE_Q2_K>(o, chunk, rot, lane, acc);
         }
     }
     if (!active) return;
@@ -1559,6 +1715,23 @@ __device__ __forceinline__ void unpack_q3_x32(const FragQ3& f0, const FragQ3& f1
     o.dmin = 0.0f;
 }
 
+/* the Q2_K operands (unpack_q2) on the 32x32x32 map: the four packed dwords take the lane swap, the tables are those of the lane's own row
+ * and k half, as for Q3_K */
+__device__ __forceinline__ void unpack_q2_x32(const FragQ2& f0, const FragQ2& f1, int lane, Ops32& o) {
+    const bool up = (lane & 16) != 0;
+    const uint32_t x0[4] = {f0.q.x, f0.q.y, f0.q.z, f0.q.w}, x1[4] = {f1.q.x, f1.q.y, f1.q.z, f1.q.w};
+    uint32_t Xa[4], Xb[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) pair_swap(x0[c], x1[c], &Xa[c], &Xb[c]);
+    uint32_t T[8], R[8];
+    q2_tables(make_uint2(up ? f1.sm.x : f0.sm.x, up ? f1.sm.y : f0.sm.y), T, R);
+    q2_operands<2, 0>(Xa, T, R, o.bl, o.bh);
+    q2_operands<2, 1>(Xb, T, R, o.bl, o.bh);
+    const uint32_t dd = up ? f1.dd : f0.dd;
+    o.dw = f16bits_to_f32(dd & 0xffffu);
+    o.dmin = f16bits_to_f32(dd >> 16);
+}
+
 /* s_waitcnt vmcnt(n) alone (expcnt / lgkmcnt untouched): until all but this wave's n youngest vector-memory operations are done.  The
  * LDS-DMA pieces of a chunk are invisible to the compiler's own wait insertion, so the ring is guarded by hand. */
 __device__ __forceinline__ void wait_vmcnt(int n) {
@@ -1611,7 +1784,8 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
         /* P = 8 Ph + Pl (64 Ph + Pl for Q6_K) inside ONE accumulator: the high-digit chain first, its result shifted on the VALU, then the
          * low-digit chain on top of it (sixteen live registers fewer than two accumulators, and the finishing below needs no shift-add);
          * the independent min-term MFMA sits where the shift waits for the last high-digit MFMA.  Q5_K: 64 Ph + Pl with the min term */
-        constexpr bool MINS = tk_has_mins(QT); /* Q3_K: the low chain alone, from zero, holding -P */
+        constexpr bool MINS = tk_has_mins(QT); /* Q3_K: the low chain alone, from zero, holding -P.  Q2_K: ph is the min chain M and stays
+                                                * beside pl = P, which starts from zero (the registers cm has for the other min types) */
         v4i A[8];
 #pragma unroll
         for (int u = 0; u < 4; ++u) A[u] = T.a[u];
@@ -1632,7 +1806,7 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
             cm = __builtin_amdgcn_mfma_f32_32x32x16_f16(T.mn, o.bm16, fz, 0, 0, 0);
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) pl[r] = ph[r] << (QT == TK_TYPE_Q4_K ? 3 : 6);
+        for (int r = 0; r < 16; ++r) pl[r] = QT == TK_TYPE_Q2_K ? 0 : ph[r] << (QT == TK_TYPE_Q4_K ? 3 : 6);
 #pragma unroll
         for (int u = 0; u < 8; ++u) pl = TK_MFMA32(A[u], o.bl[u], pl, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -1647,6 +1821,7 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
                 const int r = 4 * b + i;
                 acc[t][r] = tk_fmaf(o.dw * da[b][i], (float)(QT == TK_TYPE_Q3_K ? -pl[r] : pl[r]), acc[t][r]);
                 if (MINS) acc[t][r] = tk_fmaf(-(o.dmin * da[b][i]), cm[r], acc[t][r]);
+                if constexpr (QT == TK_TYPE_Q2_K) acc[t][r] = tk_fmaf(-(o.dmin * da[b][i]), (float)ph[r], acc[t][r]);
             }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -1656,13 +1831,21 @@ template <int QT> struct G32Frag { typedef FragQ4 type; };
 template <> struct G32Frag<TK_TYPE_Q6_K> { typedef FragQ6 type; };
 template <> struct G32Frag<TK_TYPE_Q5_K> { typedef FragQ5 type; };
 template <> struct G32Frag<TK_TYPE_Q3_K> { typedef FragQ3 type; };
+template <> struct G32Frag<TK_TYPE_Q2_K> { typedef FragQ2 type; };
 /* `tile` is wave-uniform (an SGPR pair); the per-lane offsets are 32-bit and opaque per call, so the loads take the scalar-base form and no
  * 64-bit per-lane address is hoisted out of the K loop and held across it (load_q4 / load_q6 with a lane pointer cost 12 registers there) */
 template <int QT>
 __device__ __forceinline__ typename G32Frag<QT>::type g32_load(const uint8_t* tile, int lane) {
     unsigned lo = (unsigned)lane * 16u, ho = (unsigned)(lane & 15) * 16u;
     asm volatile("" : "+v"(lo), "+v"(ho));
-    if constexpr (QT == TK_TYPE_Q3_K) {
+    if constexpr (QT == TK_TYPE_Q2_K) {
+        FragQ2 f;
+        f.q = ldg_nt(tile + lo);
+        const v2u32 sm = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + ho + ((lo >> 6) & 8u)));
+        f.sm = make_uint2(sm.x, sm.y);
+        f.dd = *(const uint32_t*)(tile + 1280 + (ho >> 2));
+        return f;
+    } else if constexpr (QT == TK_TYPE_Q3_K) {
         FragQ3 f;
         f.q = ldg_nt(tile + lo);
         const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + (lo >> 1)));
@@ -1700,6 +1883,7 @@ __device__ __forceinline__ void g32_unpack(const typename G32Frag<QT>::type& f0,
     if constexpr (QT == TK_TYPE_Q4_K) unpack_q4_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q3_K) unpack_q3_x32(f0, f1, lane, o);
+    else if constexpr (QT == TK_TYPE_Q2_K) unpack_q2_x32(f0, f1, lane, o);
     else unpack_q6_x32(f0, f1, lane, o);
 }
 
@@ -1793,7 +1977,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     const int type = a.seg[seg].type;
     constexpr bool HAS4 = (TYPES & 1) != 0, HAS6 = (TYPES & 2) != 0;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
-    const size_t tile_bytes = TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
+    const size_t tile_bytes = TYPES == 16 ? (size_t)TK_Q2K_TILE_BYTES : TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
     const ptrdiff_t tile_pitch = a.swiglu ? a.seg[1].tiles - a.seg[0].tiles : (ptrdiff_t)((size_t)nblk_total * tile_bytes);
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -1852,6 +2036,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     if (HAS6 && !is4) g32_k_loop<TK_TYPE_Q6_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (TYPES == 4) g32_k_loop<TK_TYPE_Q5_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (TYPES == 8) g32_k_loop<TK_TYPE_Q3_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (TYPES == 16) g32_k_loop<TK_TYPE_Q2_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -1927,31 +2112,31 @@ static constexpr int TK_GEMM32_FROM_ROWS = 12 * TK_ROW_SLOTS + 1;
 typedef void (*TkGemvKernel)(TkGemvArgs, int, int);
 typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
 /* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone.  Type index =
- * types - 1 for Q4_K / Q6_K / both, 3 for Q5_K alone, 4 for Q3_K alone (tk_launch_gemv) */
-static const TkGemvKernel k_gemv_fns[3][2][2][5] = {
-    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>},
-      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>}},
-     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>},
-      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>}}},
+ * types - 1 for Q4_K / Q6_K / both, 3 for Q5_K alone, 4 for Q3_K alone, 5 for Q2_K alone (tk_launch_gemv) */
+static const TkGemvKernel k_gemv_fns[3][2][2][6] = {
+    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>},
+      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>}},
+     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>},
+      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>}}},
 };
 /* [mt / 2 - 2][type index] */
-static const TkGemvKernel k_gemm_fns[5][5] = {
-    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>},
-    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>},
-    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>},
-    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>},
-    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>},
+static const TkGemvKernel k_gemm_fns[5][6] = {
+    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>},
+    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>},
+    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>},
+    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>},
+    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>},
 };
 /* [type index] */
-static const TkGemm32Kernel k_gemm32_fns[5] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>};
+static const TkGemm32Kernel k_gemm32_fns[6] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>};
 
 void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
     int types = 0;
-    for (int i = 0; i < a.nseg; ++i) types |= a.seg[i].type == TK_TYPE_Q4_K ? 1 : a.seg[i].type == TK_TYPE_Q5_K ? 4 : a.seg[i].type == TK_TYPE_Q3_K ? 8 : 2;
-    if ((types & 12) && types != 4 && types != 8) {
-        /* Q5_K or Q3_K beside another type (Q4_K_S, Q5_K_M, Q3_K_M, Q3_K_L layers): one launch per run of same-type segments, each writing its own columns of
+    for (int i = 0; i < a.nseg; ++i) types |= a.seg[i].type == TK_TYPE_Q4_K ? 1 : a.seg[i].type == TK_TYPE_Q5_K ? 4 : a.seg[i].type == TK_TYPE_Q3_K ? 8 : a.seg[i].type == TK_TYPE_Q2_K ? 16 : 2;
+    if ((types & 28) && types != 4 && types != 8 && types != 16) {
+        /* Q5_K, Q3_K or Q2_K beside another type (Q4_K_S, Q5_K_M, Q3_K_M, Q3_K_L, Q2_K layers): one launch per run of same-type segments, each writing its own columns of
          * the same slabs; a fused producer then runs once per launch and writes the same values.  (swiglu launches are single-type:
          * tk_gemv_fuses_swiglu) */
         int i0 = 0, col = a.col0;
@@ -1968,7 +2153,7 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
         }
         return;
     }
-    const int ti = types == 8 ? 4 : types == 4 ? 3 : types - 1; /* index into the kernel tables */
+    const int ti = types == 16 ? 5 : types == 8 ? 4 : types == 4 ? 3 : types - 1; /* index into the kernel tables */
     int row_tiles = 0;
     for (int i = 0; i < a.nseg; ++i) row_tiles += a.seg[i].row_tiles;
     int groups = TK_NUM_CU / a.ks;            /* workgroups per K-range */
@@ -1986,7 +2171,12 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(k_gemm32_fns[ti], dim3(g32 * a.ks * n_halves), dim3(256), ldsb, s, a, g32, row_tiles, n_halves);
         return;
     }
-    if (a.nrows > 2 * TK_ROW_SLOTS) { /* batched passes of 33 rows and more: K-streamed activations, as many M-tiles per weight tile as the pass's rows fill */
+    /* a narrow pass whose K-range is longer than 16 blocks (no model geometry here has one, the probe does) takes the K-streamed kernel at
+     * its four M-tiles: the mat-vec stages the scales and sums of a K-range in one pass of a workgroup that may be a single wave, which
+     * covers 16 blocks, and two M-tiles of a longer range do not fit its LDS image.  The same contract, so the same bits.  A fused producer
+     * lives in the mat-vec only: such a launch stays there (tk_gemv_fuses_producer) */
+    const bool image_fits = a.fuse != 0 || a.K / a.ks <= 16 * 256;
+    if (a.nrows > 2 * TK_ROW_SLOTS || !image_fits) { /* batched passes of 33 rows and more: K-streamed activations, as many M-tiles per weight tile as the pass's rows fill */
         /* 16-row M-tiles a weight tile is multiplied against: 65..96 rows walk six, not eight */
         const int mtb = a.nrows > 10 * TK_ROW_SLOTS ? 12 : a.nrows > 8 * TK_ROW_SLOTS ? 10 : a.nrows > 6 * TK_ROW_SLOTS ? 8 : a.nrows > 4 * TK_ROW_SLOTS ? 6 : 4;
         const size_t ldsb = (size_t)2 * mtb * TK_RING_TILE_BYTES;
@@ -3315,7 +3505,7 @@ void tk_launch_quant_q8(const float* hbuf, int FF, int nrows, TkActQ8 out, hipSt
 
 bool tk_gemv_fuses_swiglu(int nrows, int ks, int type_gate, int type_up) {
     return nrows >= TK_GEMM32_FROM_ROWS && ks == 1 && type_gate == type_up &&
-           (type_gate == TK_TYPE_Q3_K || type_gate == TK_TYPE_Q4_K || type_gate == TK_TYPE_Q5_K || type_gate == TK_TYPE_Q6_K); /* the 32x32x32 kernel's epilogue */
+           (type_gate == TK_TYPE_Q2_K || type_gate == TK_TYPE_Q3_K || type_gate == TK_TYPE_Q4_K || type_gate == TK_TYPE_Q5_K || type_gate == TK_TYPE_Q6_K); /* the 32x32x32 kernel's epilogue */
 }
 
 void tk_launch_swiglu_q8(const float* partial, int ks, int FF, int nrows, TkActQ8 out, hipStream_t s) {

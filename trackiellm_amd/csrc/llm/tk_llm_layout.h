@@ -20,6 +20,12 @@
  *                    4 i + s (s = 0..3): the high bit of the weight in byte y of operand dword lo / hi (k0 + y / k0 + 4 + y) of
  *                    sub-block 4 i + s sits at bit 8y + s / 8y + 4 + s, so one shift and one mask put it at bit 4 of its byte
  *      [2560 ,2816)  16 rows x {f16 d, f16 dmin, 12 B packed 6-bit scales/mins} verbatim
+ *  Q2_K tile (1344 B = 16 x 84): operand dword o = 2 j + hh of lane l as in the Q3_K tile below
+ *      [0    ,1024)  one load: lane l -> 4 dwords; bits 8 t + 2 (o & 3) .. + 1 of dword o >> 2 = q of weight t of operand dword o
+ *                    (one shift and one mask give the four byte selectors 0..3 of an operand dword)
+ *      [1024 ,1280)  16 rows x 16 (scale, min) bytes as the block holds them (low nibble scale, high nibble min), byte 8 h + j = group
+ *                    2 j + h: a lane reads the 8 bytes of its k half
+ *      [1280 ,1344)  16 x {f16 d, f16 dmin}
  *  Q3_K tile (1824 B = 16 x 114): weights stored as u = q + 4 (0..7).  Operand dword o = 2 j + hh (o = 0..15) of lane l holds the four
  *  weights k0 + 4 hh + t (t = 0..3, k0 = 32 j + 8 g) of sub-block j, as in the tiles above
  *      [0    ,1024)  one load: lane l -> 4 dwords; bits 8 t + 2 (o & 3) .. + 1 of dword o >> 2 = u & 3 of weight t of operand dword o
@@ -59,6 +65,7 @@
 #include <stdint.h>
 
 #define TK_TILE_ROWS 16
+#define TK_Q2K_TILE_BYTES 1344
 #define TK_Q3K_TILE_BYTES 1824
 #define TK_Q4K_TILE_BYTES 2304
 #define TK_Q5K_TILE_BYTES 2816

@@ -7,9 +7,10 @@ from ._lib import check, lib
 
 
 # GGUF tensor types the LLM path loads, and llama.cpp's k-quant file types (fill_synthetic(ftype=...))
-TYPE_F32, TYPE_F16, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 0, 1, 11, 12, 13, 14
+TYPE_F32, TYPE_F16, TYPE_Q2_K, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 0, 1, 10, 11, 12, 13, 14
+FTYPE_Q2_K, FTYPE_Q2_K_S = 10, 21
 FTYPE_Q3_K_S, FTYPE_Q3_K_M, FTYPE_Q4_K_S, FTYPE_Q4_K_M, FTYPE_Q5_K_S, FTYPE_Q5_K_M = 11, 12, 14, 15, 16, 17
-BLOCK_BYTES = {TYPE_Q3_K: 110, TYPE_Q4_K: 144, TYPE_Q5_K: 176, TYPE_Q6_K: 210}
+BLOCK_BYTES = {TYPE_Q2_K: 84, TYPE_Q3_K: 110, TYPE_Q4_K: 144, TYPE_Q5_K: 176, TYPE_Q6_K: 210}
 
 
 def prefix_match(toks, records, self_slot=-1, cursor=-1):
@@ -45,10 +46,14 @@ def lora_probe(path):
 
 
 def quantize_blocks(ttype, x):
-    """the build's own block quantiser on the host, no GPU (tk_mi355x_quantize_blocks): x [..., 256 n] float32 -> uint8 [n_blocks][block bytes]
-    of k-quant `ttype`"""
+    """the build's own block quantiser on the host, no GPU (tk_mi355x_quantize_blocks; tk_mi355x_quantize_blocks_q2k for TYPE_Q2_K):
+    x [..., 256 n] float32 -> uint8 [n_blocks][block bytes] of k-quant `ttype`"""
     x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 256)
     out = np.empty((x.shape[0], BLOCK_BYTES[ttype]), np.uint8)
+    if ttype == TYPE_Q2_K:
+        lib().tk_mi355x_quantize_blocks_q2k.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        check(lib().tk_mi355x_quantize_blocks_q2k(_p(x), x.shape[0], _p(out)))
+        return out
     lib().tk_mi355x_quantize_blocks.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     check(lib().tk_mi355x_quantize_blocks(ttype, _p(x), x.shape[0], _p(out)))
     return out
