@@ -9,14 +9,9 @@ import pytest
 import gguf_util
 import oracle_lib as O
 import q5k_ref as R
+from kquant_gpu_util import install, logits_in_passes, oracle_cfg_from, WIDTHS
 
 pytestmark = pytest.mark.gpu
-
-
-def oracle_cfg_from(hp, max_ctx, max_seq):
-    return O.LlmConfig(n_layer=hp.n_layer, d_model=hp.d_model, n_head=hp.n_head, n_kv_head=hp.n_kv_head, head_dim=hp.head_dim,
-                       d_ff=hp.d_ff, vocab=hp.vocab, max_ctx=max_ctx, max_seq=max_seq, rms_eps=hp.rms_eps, rope_theta=hp.rope_theta,
-                       ks_qkv=hp.ks_qkv, ks_o=hp.ks_o, ks_gateup=hp.ks_gateup, ks_down=hp.ks_down, ks_out=hp.ks_out)
 
 
 class Reencoded:
@@ -34,17 +29,6 @@ class Reencoded:
 
 Q5_K_M = lambda layer, which: True                                 # every Q4_K tensor, token_embd included
 Q4_K_S = lambda layer, which: (which == 3 and layer == 0) or (which == 8 and layer == 1)   # attn_v / ffn_down of chosen layers
-
-
-def install(model, src, n_layer):
-    for which in (O.T_TOKEN_EMBD, O.T_OUT_NORM, O.T_OUTPUT):
-        model.set_tensor(-1, which, *src.get_tensor(-1, which))
-    for l in range(n_layer):
-        for which in range(9):
-            model.set_tensor(l, which, *src.get_tensor(l, which))
-
-
-WIDTHS = [1, 2, 16, 24, 40, 128, 200, 256]
 
 
 @pytest.mark.parametrize("mix", ["q5_k_m", "q4_k_s"])
@@ -219,21 +203,6 @@ def test_q5k_mistral_shape_layer_bit_exact(gpu, nrows):
     got, gam = sess.forward(seq, np.zeros(nrows, np.int32), tok)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), np.abs(got - want).max()
     assert np.array_equal(gam, wam)
-
-
-def logits_in_passes(gpu, model, hp, width, toks):
-    """256 sequences, two positions, in passes of `width` rows (each pass its own slice of the sequences)"""
-    sess = gpu.LlmSession(model, 256, 4)
-    out = []
-    for p in range(2):
-        rows = []
-        for r0 in range(0, 256, width):
-            seq = np.arange(r0, r0 + width, dtype=np.int32)
-            got, _ = sess.forward(seq, np.full(width, p, np.int32), toks[p][r0:r0 + width])
-            rows.append(got.copy())
-        out.append(np.concatenate(rows))
-    sess.close()
-    return out
 
 
 @pytest.mark.parametrize("ftype", [17, 14])

@@ -120,14 +120,15 @@ tk_error_code_t tk_mi355x_llm_gemv_probe(int device, int type, const void* block
 }
 
 tk_error_code_t tk_mi355x_quantize_blocks(int type, const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0 || (type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K && type != TK_TYPE_Q6_K))
-        return TK_ERROR_INVALID_ARGUMENT;
+    if (!x || !out || n_blocks < 0 || !tk_type_desc_of(type).host_quantize) return TK_ERROR_INVALID_ARGUMENT;
     for (int64_t b = 0; b < n_blocks; ++b) {
         const float* xb = x + 256 * b;
-        if (type == TK_TYPE_Q3_K) tk_quantize_q3_K(xb, (tk_block_q3_K*)out + b);
-        else if (type == TK_TYPE_Q4_K) tk_quantize_q4_K(xb, (tk_block_q4_K*)out + b);
-        else if (type == TK_TYPE_Q5_K) tk_quantize_q5_K(xb, (tk_block_q5_K*)out + b);
-        else tk_quantize_q6_K(xb, (tk_block_q6_K*)out + b);
+        switch (type) {
+            case TK_TYPE_Q3_K: tk_quantize_q3_K(xb, (tk_block_q3_K*)out + b); break;
+            case TK_TYPE_Q4_K: tk_quantize_q4_K(xb, (tk_block_q4_K*)out + b); break;
+            case TK_TYPE_Q5_K: tk_quantize_q5_K(xb, (tk_block_q5_K*)out + b); break;
+            default: tk_quantize_q6_K(xb, (tk_block_q6_K*)out + b); break;
+        }
     }
     return TK_SUCCESS;
 }
@@ -284,7 +285,7 @@ tk_error_code_t tk_mi355x_llm_model_load_gguf_lora(tk_mi355x_llm_model_t** out, 
         const TkGgufTensor* t = f.find(name);
         if (!t && alt) t = f.find(alt);
         if (!t) { tk_error_set_detail("GGUF tensor missing: %s", name.c_str()); return false; }
-        if (!t->data) { tk_error_set_detail("GGUF tensor %s has unsupported type %u (supported: F32, F16, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K)", name.c_str(), t->type); return false; }
+        if (!t->data) { tk_error_set_detail("GGUF tensor %s has unsupported type %u (supported: " TK_TYPE_NAMES ")", name.c_str(), t->type); return false; }
         if (!m->model.set_tensor(layer, which, (int)t->type, t->data, t->nbytes)) { tk_error_set_detail("%s: %s", name.c_str(), m->model.error.c_str()); return false; }
         return true;
     };

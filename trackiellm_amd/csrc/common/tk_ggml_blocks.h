@@ -29,7 +29,10 @@
 #ifndef TK_GGML_BLOCKS_H
 #define TK_GGML_BLOCKS_H
 
+#include <stddef.h>
+
 #include "tk_exact_math.h"
+#include "../llm/tk_llm_layout.h" /* TK_Q*K_TILE_BYTES feed the table's tile_bytes */
 
 #define TK_QK_K 256
 
@@ -79,13 +82,80 @@ typedef struct {
     uint16_t dmin;
 } tk_block_q2_K; /* 84 B */
 
-TK_HD size_t tk_type_block_bytes(int type) {
-    if (type == TK_TYPE_Q2_K) return 84;
-    return type == TK_TYPE_Q3_K ? 110 : type == TK_TYPE_Q4_K ? 144 : type == TK_TYPE_Q5_K ? 176 : type == TK_TYPE_Q6_K ? 210 : type == TK_TYPE_F16 ? 2 : 4;
+/* The tensor types, described once: what the loaders, the launchers and the W4A8 kernels ask about a type is a column of this table, and
+ * a new type is one more row ("Adding a tensor type") */
+struct tk_type_desc {
+    const char* name;              /* null: no type of this build; it is sized like F32, as it always was, and refused by tk_type_known() */
+    int block_elems, block_bytes;
+    int tile_bytes;                /* the W4A8 weight tile of 16 rows x 256 k (tk_llm_layout.h); 0 = not a k-quant */
+    int mask, kernel_index;        /* its bit in the kernels' TYPES argument; its column in k_gemv_fns / k_gemm_fns / k_gemm32_fns */
+    bool shares_launch;            /* may ride in one launch beside another such type (the Q4_K | Q6_K kernels); tk_launch_gemv splits any other mix */
+    bool token_embd, lora_merge;   /* k_embed decodes it; k_lora_merge re-quantises it */
+    bool host_quantize;            /* tk_mi355x_quantize_blocks takes it (a pinned set: Q2_K has an entry point of its own) */
+};
+TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
+    switch (type) {
+        /*                         name    elems bytes tile               mask idx shares embd   lora   host_q */
+        case TK_TYPE_F32:  return {"F32",  1,    4,    0,                 0,   -1, false, false, false, false};
+        case TK_TYPE_F16:  return {"F16",  1,    2,    0,                 0,   -1, false, true,  true,  false};
+        case TK_TYPE_Q2_K: return {"Q2_K", 256,  84,   TK_Q2K_TILE_BYTES, 16,  5,  false, true,  false, false};
+        case TK_TYPE_Q3_K: return {"Q3_K", 256,  110,  TK_Q3K_TILE_BYTES, 8,   4,  false, true,  false, true};
+        case TK_TYPE_Q4_K: return {"Q4_K", 256,  144,  TK_Q4K_TILE_BYTES, 1,   0,  true,  true,  true,  true};
+        case TK_TYPE_Q5_K: return {"Q5_K", 256,  176,  TK_Q5K_TILE_BYTES, 4,   3,  false, true,  false, true};
+        case TK_TYPE_Q6_K: return {"Q6_K", 256,  210,  TK_Q6K_TILE_BYTES, 2,   1,  true,  false, true,  true};
+        default:           return {nullptr, 1,   4,    0,                 0,   -1, false, false, false, false};
+    }
 }
-TK_HD size_t tk_type_block_elems(int type) {
-    return (type == TK_TYPE_Q2_K || type == TK_TYPE_Q3_K || type == TK_TYPE_Q4_K || type == TK_TYPE_Q5_K || type == TK_TYPE_Q6_K) ? 256 : 1;
+/* the lists the messages print: kept beside the table, edited with it */
+#define TK_TYPE_NAMES "F32, F16, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K"
+#define TK_TYPE_NAMES_OR "F32, F16, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
+#define TK_KQUANT_NAMES_OR "Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
+#define TK_TOKEN_EMBD_NAMES_OR "Q2_K, Q3_K, Q4_K, Q5_K or F16"
+#define TK_LORA_MERGE_NAMES_OR "Q4_K, Q6_K or F16"
+
+TK_HD constexpr bool tk_type_known(int type) { return tk_type_desc_of(type).name != nullptr; }
+TK_HD constexpr bool tk_type_is_kquant(int type) { return tk_type_desc_of(type).tile_bytes != 0; }
+TK_HD constexpr size_t tk_type_block_bytes(int type) { return (size_t)tk_type_desc_of(type).block_bytes; }
+TK_HD constexpr size_t tk_type_block_elems(int type) { return (size_t)tk_type_desc_of(type).block_elems; }
+
+/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make six values: the five k-quants alone and
+ * the one mix of the two shares_launch types, whose kernels pick the tile type per segment at run time. */
+#define TK_KQUANT_FIRST TK_TYPE_Q2_K /* the k-quants are the contiguous enum range [TK_KQUANT_FIRST, TK_KQUANT_LAST] */
+#define TK_KQUANT_LAST TK_TYPE_Q6_K
+#define TK_TYPES_Q4K_Q6K (tk_type_desc_of(TK_TYPE_Q4_K).mask | tk_type_desc_of(TK_TYPE_Q6_K).mask)
+#define TK_KERNEL_INDEX_Q4K_Q6K 2
+#define TK_KERNEL_VARIANTS 6
+TK_HD constexpr bool tk_types_has(int types, int type) { return (types & tk_type_desc_of(type).mask) != 0; }
+TK_HD constexpr bool tk_types_is(int types, int type) { return types == tk_type_desc_of(type).mask; }
+/* tile bytes of a single-type launch: a compile-time pitch (tile addresses become scalar base + immediate); 0 for the mix */
+TK_HD constexpr size_t tk_types_tile_bytes(int types) {
+    for (int t = TK_KQUANT_FIRST; t <= TK_KQUANT_LAST; ++t)
+        if (tk_types_is(types, t)) return (size_t)tk_type_desc_of(t).tile_bytes;
+    return 0;
 }
+
+#define TK_TYPE_ROW_CHECK(T, block, tile_per_block)                                                                                   \
+    static_assert(sizeof(block) == tk_type_desc_of(T).block_bytes, #T ": block_bytes is not the size of its block struct");         \
+    static_assert(tk_type_desc_of(T).tile_bytes == TK_TILE_ROWS * (tile_per_block), #T ": tile_bytes is not 16 x the tile's bytes per block (tk_llm_layout.h)")
+TK_TYPE_ROW_CHECK(TK_TYPE_Q2_K, tk_block_q2_K, 84);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q3_K, tk_block_q3_K, 114); /* the tile holds the sixteen group scales as int8: 4 B more than the block's packed 6-bit ones */
+TK_TYPE_ROW_CHECK(TK_TYPE_Q4_K, tk_block_q4_K, 144);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q5_K, tk_block_q5_K, 176);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q6_K, tk_block_q6_K, 210);
+#undef TK_TYPE_ROW_CHECK
+/* every mask is one bit of its own, and the kernel indices of the six TYPES values are 0 .. 5, each once */
+TK_HD constexpr bool tk_type_table_consistent() {
+    int masks = 0, indices = 1 << TK_KERNEL_INDEX_Q4K_Q6K;
+    for (int t = TK_KQUANT_FIRST; t <= TK_KQUANT_LAST; ++t) {
+        const tk_type_desc d = tk_type_desc_of(t);
+        if (d.mask == 0 || (d.mask & (d.mask - 1)) != 0 || (masks & d.mask) != 0) return false;
+        if (d.kernel_index < 0 || d.kernel_index >= TK_KERNEL_VARIANTS || ((indices >> d.kernel_index) & 1) != 0) return false;
+        masks |= d.mask;
+        indices |= 1 << d.kernel_index;
+    }
+    return indices == (1 << TK_KERNEL_VARIANTS) - 1;
+}
+static_assert(tk_type_table_consistent(), "tk_type_desc_of: masks must be distinct bits and kernel indices 0 .. 5, each once");
 
 /* 6-bit (scale, min) pair j of a Q4_K block */
 TK_HD void tk_q4k_get_scale_min(int j, const uint8_t* q, uint8_t* sc, uint8_t* m) {

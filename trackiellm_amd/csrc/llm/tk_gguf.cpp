@@ -166,8 +166,7 @@ bool TkGgufFile::open_checked(const char* path) {
         }
         if (overflow) { error = "tensor element count overflows: " + t.name; return false; }
         size_t be = tk_type_block_elems((int)t.type), bb = tk_type_block_bytes((int)t.type);
-        if (t.type != TK_TYPE_F32 && t.type != TK_TYPE_F16 && t.type != TK_TYPE_Q2_K && t.type != TK_TYPE_Q3_K && t.type != TK_TYPE_Q4_K && t.type != TK_TYPE_Q5_K &&
-            t.type != TK_TYPE_Q6_K) {
+        if (!tk_type_known((int)t.type)) {
             t.nbytes = 0; /* unsupported type: reported when a consumer asks for this tensor */
             t.data = nullptr;
             continue;

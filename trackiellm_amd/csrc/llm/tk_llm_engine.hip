@@ -129,10 +129,10 @@ bool TkLlmModel::install(TkDevTensor* t, int type, int64_t rows, int64_t cols, v
         (void)hipFree(dA);
         (void)hipFree(dB);
         if (ok && !taken) {
-            error = type == TK_TYPE_Q5_K ? "LoRA merge needs a Q4_K, Q6_K or F16 matrix: merging into a Q5_K matrix is not built"
-                    : type == TK_TYPE_Q3_K ? "LoRA merge needs a Q4_K, Q6_K or F16 matrix: merging into a Q3_K matrix is not built"
-                    : type == TK_TYPE_Q2_K ? "LoRA merge needs a Q4_K, Q6_K or F16 matrix: merging into a Q2_K matrix is not built"
-                                         : "LoRA merge needs a Q4_K, Q6_K or F16 matrix with columns % 256 == 0";
+            const tk_type_desc d = tk_type_desc_of(type);
+            error = "LoRA merge needs a " TK_LORA_MERGE_NAMES_OR " matrix";
+            if (d.tile_bytes != 0 && !d.lora_merge) error += std::string(": merging into a ") + d.name + " matrix is not built";
+            else error += " with columns % 256 == 0";
             return false;
         }
         if (!ok || !done) { error = "LoRA merge failed on the device"; return false; }
@@ -157,16 +157,16 @@ bool TkLlmModel::install(TkDevTensor* t, int type, int64_t rows, int64_t cols, v
         }
         return true;
     }
-    if (type != TK_TYPE_Q2_K && type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K && type != TK_TYPE_Q6_K) {
-        error = "unsupported tensor type (want F32, F16, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K)";
+    const tk_type_desc d = tk_type_desc_of(type);
+    if (d.tile_bytes == 0) {
+        error = "unsupported tensor type (want " TK_TYPE_NAMES_OR ")";
         return false;
     }
-    t->bytes = (size_t)rows * cols / 256 * tk_type_block_bytes(type);
-    if (type == TK_TYPE_Q3_K && is_matrix) t->bytes = (size_t)(rows / TK_TILE_ROWS) * (cols / 256) * TK_Q3K_TILE_BYTES; /* int8 scales: 114 B per block */
-    if (type == TK_TYPE_Q2_K && is_matrix) t->bytes = (size_t)(rows / TK_TILE_ROWS) * (cols / 256) * TK_Q2K_TILE_BYTES;
+    /* a matrix is held as tiles (a Q3_K tile is larger than its sixteen blocks: tk_llm_layout.h), anything else as the file's blocks */
+    t->bytes = is_matrix ? (size_t)(rows / TK_TILE_ROWS) * (cols / 256) * d.tile_bytes : (size_t)rows * cols / 256 * d.block_bytes;
     HIPQ(hipMalloc((void**)&t->data, t->bytes));
     if (!is_matrix) { /* token_embd stays in GGUF layout: one row is gathered per token */
-        if (type != TK_TYPE_Q2_K && type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K) { error = "token_embd must be Q2_K, Q3_K, Q4_K, Q5_K or F16"; return false; }
+        if (!d.token_embd) { error = "token_embd must be " TK_TOKEN_EMBD_NAMES_OR; return false; }
         HIPQ(hipMemcpyAsync(t->data, dev_blocks, t->bytes, hipMemcpyDeviceToDevice, s));
         return true;
     }
@@ -431,8 +431,8 @@ static TkGemvSeg seg_of(const TkDevTensor& t) { return TkGemvSeg{t.data, t.type,
 
 bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, int ks, int nrows, const float* x, float* y,
                        std::string& error) {
-    if (type != TK_TYPE_Q2_K && type != TK_TYPE_Q3_K && type != TK_TYPE_Q4_K && type != TK_TYPE_Q5_K && type != TK_TYPE_Q6_K) {
-        error = "gemv probe: type must be Q2_K, Q3_K, Q4_K, Q5_K or Q6_K";
+    if (!tk_type_is_kquant(type)) {
+        error = "gemv probe: type must be " TK_KQUANT_NAMES_OR;
         return false;
     }
     if (rows < 64 || rows % 64 || rows > (1 << 20) || ks < 1 || ks > 8 || K < 256 || K % (256 * (int64_t)ks) || K > 65536 || nrows < 1 ||
@@ -443,7 +443,7 @@ bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, i
     HIPQ(hipSetDevice(device));
     if (const char* e = tk_llm_prepare_device(device)) { error = e; return false; }
     const size_t nblk = (size_t)rows * (size_t)(K / 256), bb = tk_type_block_bytes(type);
-    const size_t tb = type == TK_TYPE_Q2_K ? TK_Q2K_TILE_BYTES : type == TK_TYPE_Q3_K ? TK_Q3K_TILE_BYTES : type == TK_TYPE_Q4_K ? TK_Q4K_TILE_BYTES : type == TK_TYPE_Q5_K ? TK_Q5K_TILE_BYTES : TK_Q6K_TILE_BYTES;
+    const size_t tb = (size_t)tk_type_desc_of(type).tile_bytes;
     const size_t nout = (size_t)ks * TK_MAX_ROWS * (size_t)rows;
     void* db = nullptr;
     uint8_t* tiles = nullptr;

@@ -13,7 +13,7 @@
 
 struct TkGemvSeg {
     const uint8_t* tiles; /* device tiles [row_tile][K/256][tile bytes] */
-    int type;             /* TK_TYPE_Q2_K / TK_TYPE_Q3_K / TK_TYPE_Q4_K / TK_TYPE_Q5_K / TK_TYPE_Q6_K */
+    int type;             /* a k-quant of tk_type_desc_of (common/tk_ggml_blocks.h) */
     int row_tiles;        /* rows / 16; must be a multiple of 4 */
 };
 
@@ -63,13 +63,13 @@ struct TkActQ8 { /* quantised-activation buffers for one K */
 /* weights */
 void tk_launch_synth_blocks(int type, uint64_t seed, uint64_t tensor_id, int64_t nblocks, float scale, void* out, hipStream_t s);
 void tk_launch_synth_f32(uint64_t seed, uint64_t tensor_id, int64_t n, float* out, hipStream_t s);
-/* W += scale (B A) on a matrix in GGUF layout (Q4_K / Q6_K blocks or f16), quantised back to its own type; A [r][K], B [rows][r] on the device.
+/* W += scale (B A) on a matrix in GGUF layout (a lora_merge type of tk_type_desc_of), quantised back to its own type; A [r][K], B [rows][r] on the device.
  * false: arguments the kernel does not take (type, K % 256, more than 2^31 blocks) */
 bool tk_launch_lora_merge(int type, void* blocks, int64_t rows, int64_t K, const float* A, const float* B, int r, float scale, hipStream_t s);
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s);
 
 /* step kernels */
-void tk_launch_embed(const void* embd, int type /* TK_TYPE_Q2_K, TK_TYPE_Q3_K, TK_TYPE_Q4_K, TK_TYPE_Q5_K or TK_TYPE_F16 */, int D, const int32_t* tok, int nrows, float* x, hipStream_t s);
+void tk_launch_embed(const void* embd, int type /* a token_embd type of tk_type_desc_of */, int D, const int32_t* tok, int nrows, float* x, hipStream_t s);
 void tk_launch_synth_f16(uint64_t seed, uint64_t tensor_id, int64_t n, float scale, uint16_t* out, hipStream_t s);
 void tk_launch_rmsnorm_q8(float* x, const float* partial, int ks, int n_total_partial, const float* w, float eps, int D, int nrows,
                           TkActQ8 out, hipStream_t s);

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(64) void k_lora_merge(int type, void* blocks, int64
     }
 }
 bool tk_launch_lora_merge(int type, void* blocks, int64_t rows, int64_t K, const float* A, const float* B, int r, float scale, hipStream_t s) {
-    if ((type != TK_TYPE_Q4_K && type != TK_TYPE_Q6_K && type != TK_TYPE_F16) || K % 256 || rows < 1 || r < 1 || rows * (K / 256) > 0x7fffffffLL) return false;
+    if (!tk_type_desc_of(type).lora_merge || K % 256 || rows < 1 || r < 1 || rows * (K / 256) > 0x7fffffffLL) return false;
     hipLaunchKernelGGL(k_lora_merge, dim3((unsigned)(rows * (K / 256))), dim3(64), 0, s, type, blocks, K, A, B, r, scale);
     return true;
 }
@@ -265,15 +265,17 @@ __global__ void k_repack_q2k(const tk_block_q2_K* src, int64_t nblk, uint8_t* ti
 
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s) {
     dim3 grid((unsigned)(K / 256), (unsigned)(rows / 16));
-    if (type == TK_TYPE_Q2_K) { hipLaunchKernelGGL(k_repack_q2k, grid, dim3(64), 0, s, (const tk_block_q2_K*)blocks, K / 256, tiles); return; }
-    if (type == TK_TYPE_Q3_K) { hipLaunchKernelGGL(k_repack_q3k, grid, dim3(64), 0, s, (const tk_block_q3_K*)blocks, K / 256, tiles); return; }
-    if (type == TK_TYPE_Q4_K) hipLaunchKernelGGL(k_repack_q4k, grid, dim3(64), 0, s, (const tk_block_q4_K*)blocks, K / 256, tiles);
-    else if (type == TK_TYPE_Q5_K) hipLaunchKernelGGL(k_repack_q5k, grid, dim3(64), 0, s, (const tk_block_q5_K*)blocks, K / 256, tiles);
-    else hipLaunchKernelGGL(k_repack_q6k, grid, dim3(64), 0, s, (const tk_block_q6_K*)blocks, K / 256, tiles);
+    switch (type) {
+        case TK_TYPE_Q2_K: hipLaunchKernelGGL(k_repack_q2k, grid, dim3(64), 0, s, (const tk_block_q2_K*)blocks, K / 256, tiles); break;
+        case TK_TYPE_Q3_K: hipLaunchKernelGGL(k_repack_q3k, grid, dim3(64), 0, s, (const tk_block_q3_K*)blocks, K / 256, tiles); break;
+        case TK_TYPE_Q4_K: hipLaunchKernelGGL(k_repack_q4k, grid, dim3(64), 0, s, (const tk_block_q4_K*)blocks, K / 256, tiles); break;
+        case TK_TYPE_Q5_K: hipLaunchKernelGGL(k_repack_q5k, grid, dim3(64), 0, s, (const tk_block_q5_K*)blocks, K / 256, tiles); break;
+        default: hipLaunchKernelGGL(k_repack_q6k, grid, dim3(64), 0, s, (const tk_block_q6_K*)blocks, K / 256, tiles); break;
+    }
 }
 
 /* ------------------------------------------------------------------------------------------
- * token embedding: one Q2_K / Q3_K / Q4_K / Q5_K row (GGUF layout) de-quantised per row slot
+ * token embedding: one row of a token_embd type (tk_type_desc_of) in GGUF layout, de-quantised per row slot
  * ------------------------------------------------------------------------------------------ */
 __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, float* x) {
     const int r = blockIdx.y;
@@ -542,6 +544,30 @@ __device__ __forceinline__ FragQ6 load_q6(const uint8_t* tile, int lane) {
     f.sc = ldg_nt(tile + 3072 + (lane & 15) * 16);
     f.d = *(const uint16_t*)(tile + 3328 + (lane & 15) * 2);
     return f;
+}
+
+/* The weight tile of a type as the three W4A8 families see it: one lane's packed fragment, the tile's bytes and the lane-pointer load
+ * (k_gemm32_w4a8 issues the same loads in scalar-base form: g32_load) */
+template <int QT> struct TkTile;
+#define TK_TILE(NAME, QT, F, LOAD)                                                                            \
+    template <> struct TkTile<QT> {                                                                           \
+        typedef F Frag;                                                                                       \
+        static constexpr size_t bytes = tk_type_desc_of(QT).tile_bytes;                                       \
+        static __device__ __forceinline__ F load(const uint8_t* tile, int lane) { return LOAD(tile, lane); }  \
+    };                                                                                                        \
+    typedef TkTile<QT> NAME
+TK_TILE(TileQ2, TK_TYPE_Q2_K, FragQ2, load_q2);
+TK_TILE(TileQ3, TK_TYPE_Q3_K, FragQ3, load_q3);
+TK_TILE(TileQ4, TK_TYPE_Q4_K, FragQ4, load_q4);
+TK_TILE(TileQ5, TK_TYPE_Q5_K, FragQ5, load_q5);
+TK_TILE(TileQ6, TK_TYPE_Q6_K, FragQ6, load_q6);
+#undef TK_TILE
+/* the tile pitch of a launch: a compile-time constant in single-type launches (tile addresses become scalar base + immediate); the
+ * Q4_K | Q6_K kernels take it from the segment's type */
+template <int TYPES>
+__device__ __forceinline__ size_t types_tile_bytes(bool is4) {
+    constexpr size_t fixed = tk_types_tile_bytes(TYPES);
+    return fixed != 0 ? fixed : is4 ? (size_t)TileQ4::bytes : (size_t)TileQ6::bytes;
 }
 
 __device__ __forceinline__ float f16bits_to_f32(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }
@@ -900,9 +926,8 @@ size_t tk_gemv_lds_bytes(int K, int ks, int mtiles) {
  * so (a) every CU streams the same number of 16-row tiles (+-1), (b) the K-range's int8 activations are
  * staged once per CU, (c) all waves of a CU walk disjoint contiguous tile runs.
  */
-/* TYPES: bit 0 = the launch contains Q4_K tiles, bit 1 = Q6_K tiles, bit 2 = Q5_K tiles, bit 3 = Q3_K tiles, bit 4 = Q2_K tiles (the last
- * three only alone: tk_launch_gemv splits a mixed launch with Q5_K, Q3_K or Q2_K per type); single-type launches keep only one fragment
- * ring in registers */
+/* TYPES: the masks (tk_type_desc_of) of the tile types the launch contains: one type, or the two shares_launch types together
+ * (tk_launch_gemv splits any other mix per type); single-type launches keep only one fragment ring in registers */
 /* FUSE (TkGemvArgs::fuse, MT = 1 only): 0 = the activation image comes from global memory; 1 / 2 = every workgroup forms it itself —
  * the norm's or SwiGLU's arithmetic, value for value what k_rmsnorm_q8 / k_swiglu_q8 write — under the latency of its first weight tiles */
 template <int PF, int MT, int TYPES, int FUSE>
@@ -928,9 +953,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
         ++seg;
     }
     const int type = a.seg[seg].type;
-    /* compile-time tile pitch in single-type launches: tile addresses become scalar base + immediate */
-    const size_t tile_bytes = TYPES == 16 ? (size_t)TK_Q2K_TILE_BYTES : TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : TYPES == 1 ? (size_t)TK_Q4K_TILE_BYTES : TYPES == 2 ? (size_t)TK_Q6K_TILE_BYTES
-                                         : (type == TK_TYPE_Q4_K ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES);
+    const size_t tile_bytes = types_tile_bytes<TYPES>(type == TK_TYPE_Q4_K);
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
     /* LDS: [MT] activation images, then [MT] block scales, then [MT] sub-block sums */
@@ -949,32 +972,33 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     /* The first PF weight tiles are requested before the activations are staged so HBM latency overlaps the LDS
      * fill.  Loop bodies below contain NO conditional loads: hipcc then keeps counted vmcnt waits and the next
      * group's tiles stay in flight under the current group's MFMAs (a branch around a load costs a vmcnt(0)). */
-    constexpr bool HAS4 = (TYPES & 1) != 0, HAS6 = (TYPES & 2) != 0;
+    constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
+    constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
-    FragQ4 f4[HAS4 ? PF : 1];
-    FragQ6 f6[HAS6 ? PF : 1];
-    FragQ5 f5[TYPES == 4 ? PF : 1];
-    FragQ3 f3[TYPES == 8 ? PF : 1];
-    FragQ2 f2[TYPES == 16 ? PF : 1];
-    if constexpr (TYPES == 8) {
+    TileQ4::Frag f4[HAS4 ? PF : 1];
+    TileQ6::Frag f6[HAS6 ? PF : 1];
+    TileQ5::Frag f5[ONLY5 ? PF : 1];
+    TileQ3::Frag f3[ONLY3 ? PF : 1];
+    TileQ2::Frag f2[ONLY2 ? PF : 1];
+    if constexpr (ONLY3) {
 #pragma unroll
-        for (int u = 0; u < PF; ++u) f3[u] = load_q3(tile + (size_t)u * tile_bytes, lane);
+        for (int u = 0; u < PF; ++u) f3[u] = TileQ3::load(tile + (size_t)u * tile_bytes, lane);
     }
-    if constexpr (TYPES == 16) {
+    if constexpr (ONLY2) {
 #pragma unroll
-        for (int u = 0; u < PF; ++u) f2[u] = load_q2(tile + (size_t)u * tile_bytes, lane);
+        for (int u = 0; u < PF; ++u) f2[u] = TileQ2::load(tile + (size_t)u * tile_bytes, lane);
     }
     if (HAS4 && is4) {
 #pragma unroll
-        for (int u = 0; u < PF; ++u) f4[HAS4 ? u : 0] = load_q4(tile + (size_t)u * tile_bytes, lane);
+        for (int u = 0; u < PF; ++u) f4[HAS4 ? u : 0] = TileQ4::load(tile + (size_t)u * tile_bytes, lane);
     }
-    if constexpr (TYPES == 4) {
+    if constexpr (ONLY5) {
 #pragma unroll
-        for (int u = 0; u < PF; ++u) f5[u] = load_q5(tile + (size_t)u * tile_bytes, lane);
+        for (int u = 0; u < PF; ++u) f5[u] = TileQ5::load(tile + (size_t)u * tile_bytes, lane);
     }
     if (HAS6 && !is4) {
 #pragma unroll
-        for (int u = 0; u < PF; ++u) f6[HAS6 ? u : 0] = load_q6(tile + (size_t)u * tile_bytes, lane);
+        for (int u = 0; u < PF; ++u) f6[HAS6 ? u : 0] = TileQ6::load(tile + (size_t)u * tile_bytes, lane);
     }
     if (FUSE != 0) {
         const int nw = nthr >> 6, hw = tid >> 5, nhw = nthr >> 5;
@@ -1106,6 +1130,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
 
     /* steady state per tile: unpack (frees the packed fragment) -> request the tile PF blocks ahead into the same registers ->
      * MFMAs; so a tile has PF - 1 blocks of MFMA time plus its own to arrive */
+    /* One copy of the loop per type on purpose: behind a function template or a lambda the compiler schedules every instantiation differently. */
     if (HAS4 && is4) {
         const uint8_t* tp = tile + PF * tile_bytes; /* one moving wave-uniform pointer: no per-load 64-bit VGPR address chains */
 #pragma unroll 1
@@ -1116,7 +1141,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
                 __builtin_amdgcn_sched_barrier(0);
                 unpack_q4(f4[HAS4 ? u : 0], lane, o);
                 __builtin_amdgcn_sched_barrier(0);
-                f4[HAS4 ? u : 0] = load_q4(tp + u * tile_bytes, lane);
+                f4[HAS4 ? u : 0] = TileQ4::load(tp + u * tile_bytes, lane);
                 __builtin_amdgcn_sched_barrier(0);
                 mma_q4<MT>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, g * PF + u, lane, acc);
             }
@@ -1139,7 +1164,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
                 __builtin_amdgcn_sched_barrier(0);
                 unpack_q6(f6[HAS6 ? u : 0], o);
                 __builtin_amdgcn_sched_barrier(0);
-                f6[HAS6 ? u : 0] = load_q6(tp + u * tile_bytes, lane);
+                f6[HAS6 ? u : 0] = TileQ6::load(tp + u * tile_bytes, lane);
                 __builtin_amdgcn_sched_barrier(0);
                 mma_q6<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
             }
@@ -1152,7 +1177,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q6<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
-    if constexpr (TYPES == 4) {
+    if constexpr (ONLY5) {
         const uint8_t* tp = tile + PF * tile_bytes;
 #pragma unroll 1
         for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
@@ -1162,7 +1187,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
                 __builtin_amdgcn_sched_barrier(0);
                 unpack_q5_fold(f5[u], lane, o);
                 __builtin_amdgcn_sched_barrier(0);
-                f5[u] = load_q5(tp + u * tile_bytes, lane);
+                f5[u] = TileQ5::load(tp + u * tile_bytes, lane);
                 __builtin_amdgcn_sched_barrier(0);
                 mma_q4<MT, 6>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, g * PF + u, lane, acc);
             }
@@ -1175,7 +1200,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q4<MT, 6>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
-    if constexpr (TYPES == 8) {
+    if constexpr (ONLY3) {
         const uint8_t* tp = tile + PF * tile_bytes;
 #pragma unroll 1
         for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
@@ -1185,7 +1210,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
                 __builtin_amdgcn_sched_barrier(0);
                 unpack_q3(f3[u], o);
                 __builtin_amdgcn_sched_barrier(0);
-                f3[u] = load_q3(tp + u * tile_bytes, lane);
+                f3[u] = TileQ3::load(tp + u * tile_bytes, lane);
                 __builtin_amdgcn_sched_barrier(0);
                 mma_q3<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
             }
@@ -1198,7 +1223,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q3<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
-    if constexpr (TYPES == 16) {
+    if constexpr (ONLY2) {
         const uint8_t* tp = tile + PF * tile_bytes;
 #pragma unroll 1
         for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
@@ -1208,7 +1233,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
                 __builtin_amdgcn_sched_barrier(0);
                 unpack_q2(f2[u], o);
                 __builtin_amdgcn_sched_barrier(0);
-                f2[u] = load_q2(tp + u * tile_bytes, lane);
+                f2[u] = TileQ2::load(tp + u * tile_bytes, lane);
                 __builtin_amdgcn_sched_barrier(0);
                 mma_q2<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
             }
@@ -1431,9 +1456,10 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
         ++seg;
     }
     const int type = a.seg[seg].type;
-    constexpr bool HAS4 = (TYPES & 1) != 0, HAS6 = (TYPES & 2) != 0;
+    constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
+    constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
-    const size_t tile_bytes = TYPES == 16 ? (size_t)TK_Q2K_TILE_BYTES : TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
+    const size_t tile_bytes = types_tile_bytes<TYPES>(is4);
     const size_t tile_pitch = (size_t)nblk_total * tile_bytes; /* to the same block of the next row tile */
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -1470,19 +1496,19 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
         }
     };
 
-    FragQ4 f4[HAS4 ? NT : 1];
-    FragQ6 f6[HAS6 ? NT : 1];
-    FragQ5 f5[TYPES == 4 ? NT : 1];
-    FragQ3 f3[TYPES == 8 ? NT : 1];
-    FragQ2 f2[TYPES == 16 ? NT : 1];
+    TileQ4::Frag f4[HAS4 ? NT : 1];
+    TileQ6::Frag f6[HAS6 ? NT : 1];
+    TileQ5::Frag f5[ONLY5 ? NT : 1];
+    TileQ3::Frag f3[ONLY3 ? NT : 1];
+    TileQ2::Frag f2[ONLY2 ? NT : 1];
     if (active) {
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
-            if (HAS4 && is4) f4[HAS4 ? w : 0] = load_q4(tile + w * tile_pitch, lane);
-            if (HAS6 && !is4) f6[HAS6 ? w : 0] = load_q6(tile + w * tile_pitch, lane);
-            if constexpr (TYPES == 4) f5[w] = load_q5(tile + w * tile_pitch, lane);
-            if constexpr (TYPES == 8) f3[w] = load_q3(tile + w * tile_pitch, lane);
-            if constexpr (TYPES == 16) f2[w] = load_q2(tile + w * tile_pitch, lane);
+            if (HAS4 && is4) f4[HAS4 ? w : 0] = TileQ4::load(tile + w * tile_pitch, lane);
+            if (HAS6 && !is4) f6[HAS6 ? w : 0] = TileQ6::load(tile + w * tile_pitch, lane);
+            if constexpr (ONLY5) f5[w] = TileQ5::load(tile + w * tile_pitch, lane);
+            if constexpr (ONLY3) f3[w] = TileQ3::load(tile + w * tile_pitch, lane);
+            if constexpr (ONLY2) f2[w] = TileQ2::load(tile + w * tile_pitch, lane);
         }
     }
     for (int i = 0; i < CB && i < nb; ++i) stage(i, i);
@@ -1498,12 +1524,13 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
         const uint8_t* chunk = lds + (((b / CB) & 1) * CB + b % CB) * CH;
         const uint8_t* next = tile + (size_t)(b + 1 < nb ? b + 1 : b) * tile_bytes; /* the last step re-requests its own tile: no branch around a load */
         OpsQ4 o[NT];
+        /* One copy of the step per type on purpose: behind a function template the compiler schedules every instantiation differently. */
         if (HAS4 && is4) {
 #pragma unroll
             for (int w = 0; w < NT; ++w) unpack_q4(f4[HAS4 ? w : 0], lane, o[w]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int w = 0; w < NT; ++w) f4[HAS4 ? w : 0] = load_q4(next + w * tile_pitch, lane);
+            for (int w = 0; w < NT; ++w) f4[HAS4 ? w : 0] = TileQ4::load(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
             gemm_block<MT, NT, TK_TYPE_Q4_K>(o, chunk, rot, lane, acc);
         }
@@ -1512,34 +1539,34 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             for (int w = 0; w < NT; ++w) unpack_q6_fold(f6[HAS6 ? w : 0], lane, o[w]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int w = 0; w < NT; ++w) f6[HAS6 ? w : 0] = load_q6(next + w * tile_pitch, lane);
+            for (int w = 0; w < NT; ++w) f6[HAS6 ? w : 0] = TileQ6::load(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
             gemm_block<MT, NT, TK_TYPE_Q6_K>(o, chunk, rot, lane, acc);
         }
-        if constexpr (TYPES == 4) {
+        if constexpr (ONLY5) {
 #pragma unroll
             for (int w = 0; w < NT; ++w) unpack_q5_fold(f5[w], lane, o[w]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int w = 0; w < NT; ++w) f5[w] = load_q5(next + w * tile_pitch, lane);
+            for (int w = 0; w < NT; ++w) f5[w] = TileQ5::load(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
             gemm_block<MT, NT, TK_TYPE_Q5_K>(o, chunk, rot, lane, acc);
         }
-        if constexpr (TYPES == 8) {
+        if constexpr (ONLY3) {
 #pragma unroll
             for (int w = 0; w < NT; ++w) unpack_q3(f3[w], o[w]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int w = 0; w < NT; ++w) f3[w] = load_q3(next + w * tile_pitch, lane);
+            for (int w = 0; w < NT; ++w) f3[w] = TileQ3::load(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
             gemm_block<MT, NT, TK_TYPE_Q3_K>(o, chunk, rot, lane, acc);
         }
-        if constexpr (TYPES == 16) {
+        if constexpr (ONLY2) {
 #pragma unroll
             for (int w = 0; w < NT; ++w) unpack_q2(f2[w], o[w]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int w = 0; w < NT; ++w) f2[w] = load_q2(next + w * tile_pitch, lane);
+            for (int w = 0; w < NT; ++w) f2[w] = TileQ2::load(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
             gemm_block<MT, NT, TK_TYPE_Q2_K>(o, chunk, rot, lane, acc);
         }
@@ -1827,15 +1854,10 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
     }
 }
 
-template <int QT> struct G32Frag { typedef FragQ4 type; };
-template <> struct G32Frag<TK_TYPE_Q6_K> { typedef FragQ6 type; };
-template <> struct G32Frag<TK_TYPE_Q5_K> { typedef FragQ5 type; };
-template <> struct G32Frag<TK_TYPE_Q3_K> { typedef FragQ3 type; };
-template <> struct G32Frag<TK_TYPE_Q2_K> { typedef FragQ2 type; };
 /* `tile` is wave-uniform (an SGPR pair); the per-lane offsets are 32-bit and opaque per call, so the loads take the scalar-base form and no
  * 64-bit per-lane address is hoisted out of the K loop and held across it (load_q4 / load_q6 with a lane pointer cost 12 registers there) */
 template <int QT>
-__device__ __forceinline__ typename G32Frag<QT>::type g32_load(const uint8_t* tile, int lane) {
+__device__ __forceinline__ typename TkTile<QT>::Frag g32_load(const uint8_t* tile, int lane) {
     unsigned lo = (unsigned)lane * 16u, ho = (unsigned)(lane & 15) * 16u;
     asm volatile("" : "+v"(lo), "+v"(ho));
     if constexpr (QT == TK_TYPE_Q2_K) {
@@ -1879,7 +1901,7 @@ __device__ __forceinline__ typename G32Frag<QT>::type g32_load(const uint8_t* ti
     }
 }
 template <int QT>
-__device__ __forceinline__ void g32_unpack(const typename G32Frag<QT>::type& f0, const typename G32Frag<QT>::type& f1, int lane, Ops32& o) {
+__device__ __forceinline__ void g32_unpack(const typename TkTile<QT>::Frag& f0, const typename TkTile<QT>::Frag& f1, int lane, Ops32& o) {
     if constexpr (QT == TK_TYPE_Q4_K) unpack_q4_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q3_K) unpack_q3_x32(f0, f1, lane, o);
@@ -1892,7 +1914,7 @@ __device__ __forceinline__ void g32_unpack(const typename G32Frag<QT>::type& f0,
 template <int QT, typename StageSmall, typename StagePart>
 __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_bytes, ptrdiff_t tile_pitch, int nb, const uint8_t* ring, int slot_bytes, int lane,
                                            float (&acc)[TK_G32_MTW][16], StageSmall&& stage_small, StagePart&& stage_part) {
-    typedef typename G32Frag<QT>::type F;
+    typedef typename TkTile<QT>::Frag F;
     F f0 = g32_load<QT>(tile, lane), f1 = g32_load<QT>(tile + tile_pitch, lane);
     stage_small(0, 0);
     for (int part = 0; part < 4; ++part) stage_part(0, 0, part);
@@ -1975,9 +1997,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
         ++seg;
     }
     const int type = a.seg[seg].type;
-    constexpr bool HAS4 = (TYPES & 1) != 0, HAS6 = (TYPES & 2) != 0;
+    constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
+    constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
-    const size_t tile_bytes = TYPES == 16 ? (size_t)TK_Q2K_TILE_BYTES : TYPES == 8 ? (size_t)TK_Q3K_TILE_BYTES : TYPES == 4 ? (size_t)TK_Q5K_TILE_BYTES : is4 ? (size_t)TK_Q4K_TILE_BYTES : (size_t)TK_Q6K_TILE_BYTES;
+    const size_t tile_bytes = types_tile_bytes<TYPES>(is4);
     const ptrdiff_t tile_pitch = a.swiglu ? a.seg[1].tiles - a.seg[0].tiles : (ptrdiff_t)((size_t)nblk_total * tile_bytes);
     const uint8_t* tile = a.seg[seg].tiles + ((size_t)rt * nblk_total + blk0) * tile_bytes;
 
@@ -2034,9 +2057,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     }
     if (HAS4 && is4) g32_k_loop<TK_TYPE_Q4_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if (HAS6 && !is4) g32_k_loop<TK_TYPE_Q6_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (TYPES == 4) g32_k_loop<TK_TYPE_Q5_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (TYPES == 8) g32_k_loop<TK_TYPE_Q3_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (TYPES == 16) g32_k_loop<TK_TYPE_Q2_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (ONLY5) g32_k_loop<TK_TYPE_Q5_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (ONLY3) g32_k_loop<TK_TYPE_Q3_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (ONLY2) g32_k_loop<TK_TYPE_Q2_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -2112,8 +2135,8 @@ static constexpr int TK_GEMM32_FROM_ROWS = 12 * TK_ROW_SLOTS + 1;
 typedef void (*TkGemvKernel)(TkGemvArgs, int, int);
 typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
 /* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone.  Type index =
- * types - 1 for Q4_K / Q6_K / both, 3 for Q5_K alone, 4 for Q3_K alone, 5 for Q2_K alone (tk_launch_gemv) */
-static const TkGemvKernel k_gemv_fns[3][2][2][6] = {
+ * the type's kernel_index (tk_type_desc_of), TK_KERNEL_INDEX_Q4K_Q6K for the mix; the static_asserts below hold every column to it */
+static const TkGemvKernel k_gemv_fns[3][2][2][TK_KERNEL_VARIANTS] = {
     {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>},
       {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>}},
      {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>},
@@ -2122,7 +2145,7 @@ static const TkGemvKernel k_gemv_fns[3][2][2][6] = {
     {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>}}},
 };
 /* [mt / 2 - 2][type index] */
-static const TkGemvKernel k_gemm_fns[5][6] = {
+static const TkGemvKernel k_gemm_fns[5][TK_KERNEL_VARIANTS] = {
     {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>},
     {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>},
     {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>},
@@ -2130,13 +2153,29 @@ static const TkGemvKernel k_gemm_fns[5][6] = {
     {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>},
 };
 /* [type index] */
-static const TkGemm32Kernel k_gemm32_fns[6] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>};
+static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>};
+
+/* column c of the three tables holds the kernels of TYPES = tk_column_types[c]: every type's mask at its kernel_index */
+constexpr bool tk_columns_match_the_type_table() {
+    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16};
+    for (int t = TK_KQUANT_FIRST; t <= TK_KQUANT_LAST; ++t)
+        if (tk_column_types[tk_type_desc_of(t).kernel_index] != tk_type_desc_of(t).mask) return false;
+    return tk_column_types[TK_KERNEL_INDEX_Q4K_Q6K] == TK_TYPES_Q4K_Q6K;
+}
+static_assert(tk_columns_match_the_type_table(), "k_gemv_fns / k_gemm_fns / k_gemm32_fns: column order against tk_type_desc_of");
 
 void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
     int types = 0;
-    for (int i = 0; i < a.nseg; ++i) types |= a.seg[i].type == TK_TYPE_Q4_K ? 1 : a.seg[i].type == TK_TYPE_Q5_K ? 4 : a.seg[i].type == TK_TYPE_Q3_K ? 8 : a.seg[i].type == TK_TYPE_Q2_K ? 16 : 2;
-    if ((types & 28) && types != 4 && types != 8 && types != 16) {
-        /* Q5_K, Q3_K or Q2_K beside another type (Q4_K_S, Q5_K_M, Q3_K_M, Q3_K_L, Q2_K layers): one launch per run of same-type segments, each writing its own columns of
+    bool all_share = true;
+    for (int i = 0; i < a.nseg; ++i) {
+        const tk_type_desc d = tk_type_desc_of(a.seg[i].type);
+        types |= d.mask;
+        all_share = all_share && d.shares_launch;
+    }
+    const tk_type_desc first = tk_type_desc_of(a.seg[0].type);
+    const bool one_type = types == first.mask;
+    if (!one_type && !all_share) {
+        /* a type that shares no launch beside another type (Q4_K_S, Q5_K_M, Q3_K_M, Q3_K_L, Q2_K layers): one launch per run of same-type segments, each writing its own columns of
          * the same slabs; a fused producer then runs once per launch and writes the same values.  (swiglu launches are single-type:
          * tk_gemv_fuses_swiglu) */
         int i0 = 0, col = a.col0;
@@ -2153,7 +2192,7 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
         }
         return;
     }
-    const int ti = types == 16 ? 5 : types == 8 ? 4 : types == 4 ? 3 : types - 1; /* index into the kernel tables */
+    const int ti = one_type ? first.kernel_index : TK_KERNEL_INDEX_Q4K_Q6K; /* index into the kernel tables */
     int row_tiles = 0;
     for (int i = 0; i < a.nseg; ++i) row_tiles += a.seg[i].row_tiles;
     int groups = TK_NUM_CU / a.ks;            /* workgroups per K-range */
@@ -2189,7 +2228,7 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
     /* weight tiles in flight per wave: 2, the largest depth every (M-tiles, tile types) variant holds without spilling (compiler resource
      * report + timings on MI355X, profiles/r01_gemv_variants.txt).  A Q6-only launch with two M-tiles spills as a single-type kernel at that
      * depth; the two-type kernel does not. */
-    const int gti = mt == 2 && types == 2 ? 2 : ti;
+    const int gti = mt == 2 && tk_types_is(types, TK_TYPE_Q6_K) ? TK_KERNEL_INDEX_Q4K_Q6K : ti;
     const int pf = nb % 2 == 0 ? 2 : 1;
     const size_t fuse_lds = a.fuse == 1 ? ((size_t)a.K + 4) * sizeof(float) : 0; /* the finished row and the canonical sum's four partials */
     /* tk_gemv_fuses_producer() admits only launches of one M-tile and two tiles in flight */
@@ -3505,7 +3544,7 @@ void tk_launch_quant_q8(const float* hbuf, int FF, int nrows, TkActQ8 out, hipSt
 
 bool tk_gemv_fuses_swiglu(int nrows, int ks, int type_gate, int type_up) {
     return nrows >= TK_GEMM32_FROM_ROWS && ks == 1 && type_gate == type_up &&
-           (type_gate == TK_TYPE_Q2_K || type_gate == TK_TYPE_Q3_K || type_gate == TK_TYPE_Q4_K || type_gate == TK_TYPE_Q5_K || type_gate == TK_TYPE_Q6_K); /* the 32x32x32 kernel's epilogue */
+           tk_type_is_kquant(type_gate); /* the 32x32x32 kernel's epilogue */
 }
 
 void tk_launch_swiglu_q8(const float* partial, int ks, int FF, int nrows, TkActQ8 out, hipStream_t s) {

@@ -1,8 +1,8 @@
 /*
  * tk_llm_layout.h — HBM layouts of the MI355X LLM path.
  *
- * GGUF k-quant blocks are kept bit-for-bit (same 144 B / 210 B per 256 weights, same
- * quantised values) but re-tiled at load time so that one wavefront's 16-byte-per-lane
+ * GGUF k-quant blocks are kept bit-for-bit (the same quantised values, and the file's bytes per 256 weights
+ * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked) but re-tiled at load time so that one wavefront's 16-byte-per-lane
  * load is a contiguous 1 KiB run that already IS an MFMA operand:
  *
  *  Weight tile = 16 weight rows x 256 k (one super-block column).  Lane l = (n = l & 15, g = l >> 4)
@@ -65,6 +65,7 @@
 #include <stdint.h>
 
 #define TK_TILE_ROWS 16
+/* the tile sizes documented above; tk_type_desc_of (common/tk_ggml_blocks.h) takes them as each type's tile_bytes and checks them */
 #define TK_Q2K_TILE_BYTES 1344
 #define TK_Q3K_TILE_BYTES 1824
 #define TK_Q4K_TILE_BYTES 2304

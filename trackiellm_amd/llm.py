@@ -6,7 +6,7 @@ import numpy as np
 from ._lib import check, lib
 
 
-# GGUF tensor types the LLM path loads, and llama.cpp's k-quant file types (fill_synthetic(ftype=...))
+# GGUF tensor types the LLM path loads (the rows of tk_type_desc_of in csrc/common/tk_ggml_blocks.h), and llama.cpp's k-quant file types (fill_synthetic(ftype=...))
 TYPE_F32, TYPE_F16, TYPE_Q2_K, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 0, 1, 10, 11, 12, 13, 14
 FTYPE_Q2_K, FTYPE_Q2_K_S = 10, 21
 FTYPE_Q3_K_S, FTYPE_Q3_K_M, FTYPE_Q4_K_S, FTYPE_Q4_K_M, FTYPE_Q5_K_S, FTYPE_Q5_K_M = 11, 12, 14, 15, 16, 17
