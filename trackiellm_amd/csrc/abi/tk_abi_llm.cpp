@@ -122,8 +122,9 @@ tk_error_code_t tk_mi355x_llm_gemv_probe(int device, int type, const void* block
 tk_error_code_t tk_mi355x_quantize_blocks(int type, const float* x, int64_t n_blocks, void* out) {
     if (!x || !out || n_blocks < 0 || !tk_type_desc_of(type).host_quantize) return TK_ERROR_INVALID_ARGUMENT;
     for (int64_t b = 0; b < n_blocks; ++b) {
-        const float* xb = x + 256 * b;
+        const float* xb = x + tk_type_block_elems(type) * b; /* n_blocks counts the type's own blocks: 32 weights for Q8_0, 256 for the k-quants */
         switch (type) {
+            case TK_TYPE_Q8_0: tk_quantize_q8_0(xb, (tk_block_q8_0*)out + b); break;
             case TK_TYPE_Q3_K: tk_quantize_q3_K(xb, (tk_block_q3_K*)out + b); break;
             case TK_TYPE_Q4_K: tk_quantize_q4_K(xb, (tk_block_q4_K*)out + b); break;
             case TK_TYPE_Q5_K: tk_quantize_q5_K(xb, (tk_block_q5_K*)out + b); break;
@@ -140,7 +141,7 @@ tk_error_code_t tk_mi355x_quantize_blocks_q2k(const float* x, int64_t n_blocks, 
 }
 
 tk_error_code_t tk_mi355x_llm_model_fill_synthetic_ftype(tk_mi355x_llm_model_t* m, uint64_t seed, int ftype) {
-    if (!m || !(ftype == 10 || ftype == 11 || ftype == 12 || (ftype >= 14 && ftype <= 17) || ftype == 21)) return TK_ERROR_INVALID_ARGUMENT;
+    if (!m || !(ftype == 7 || ftype == 10 || ftype == 11 || ftype == 12 || (ftype >= 14 && ftype <= 17) || ftype == 21)) return TK_ERROR_INVALID_ARGUMENT;
     if (!m->model.fill_synthetic(seed, false, ftype)) return fail(TK_ERROR_GPU_ROCM_ERROR, m->model.error);
     return TK_SUCCESS;
 }
@@ -697,8 +698,9 @@ tk_error_code_t tk_model_loader_load_model(tk_model_loader_t* loader, const tk_m
         tk_mi355x_llm_hparams_t h{};
         const bool f16 = name.size() > 4 && name.compare(name.size() - 4, 4, "-f16") == 0; /* the fp16 checkpoint recipe (BASELINE configs[4]) */
         if (f16) name.resize(name.size() - 4);
-        int ftype = 0; /* the Q2_K recipes of fill_synthetic_ftype: synthetic://mistral-7b-q2k, synthetic://tiny-q2ks */
-        if (name.size() > 5 && name.compare(name.size() - 5, 5, "-q2ks") == 0) { ftype = 21; name.resize(name.size() - 5); }
+        int ftype = 0; /* the Q8_0 and Q2_K recipes of fill_synthetic_ftype: synthetic://mistral-7b-q80, synthetic://mistral-7b-q2k, synthetic://tiny-q2ks */
+        if (name.size() > 4 && name.compare(name.size() - 4, 4, "-q80") == 0) { ftype = 7; name.resize(name.size() - 4); }
+        else if (name.size() > 5 && name.compare(name.size() - 5, 5, "-q2ks") == 0) { ftype = 21; name.resize(name.size() - 5); }
         else if (name.size() > 4 && name.compare(name.size() - 4, 4, "-q2k") == 0) { ftype = 10; name.resize(name.size() - 4); }
         if (name == "mistral-7b") h = tk_mi355x_llm_hparams_t{32, 4096, 32, 8, 128, 14336, 32000, 1e-5f, 10000.0f, 0, 0, 0, 0, 1};
         else if (name == "tiny") h = tk_mi355x_llm_hparams_t{2, 256, 8, 2, 64, 512, 512, 1e-5f, 10000.0f, 0, 0, 0, 0, 1};

@@ -23,6 +23,7 @@
  *         16: low nibble the scale, high nibble the min), 64 B of 2-bit quants
  *         (weight 128 n + 32 j + l = (qs[32 n + l] >> 2 j) & 3), f16 d, f16
  *         dmin.   w = d*sc[g]*q - dmin*m[g], q in 0..3
+ *   Q8_0: 32 weights / 34 B: f16 d, 32 int8 quants.   w = d*q (exact in fp32), every int8 value legal, -128 included
  * Host + device code (the quantisers run inside the synthetic-weight kernel
  * and inside the oracle; they are bit-identical by construction).
  */
@@ -39,6 +40,7 @@
 enum tk_ggml_type {
     TK_TYPE_F32 = 0,
     TK_TYPE_F16 = 1,
+    TK_TYPE_Q8_0 = 8,
     TK_TYPE_Q2_K = 10,
     TK_TYPE_Q3_K = 11,
     TK_TYPE_Q4_K = 12,
@@ -82,6 +84,12 @@ typedef struct {
     uint16_t dmin;
 } tk_block_q2_K; /* 84 B */
 
+typedef struct {
+    uint16_t d;
+    int8_t qs[32];
+} tk_block_q8_0; /* 34 B, 32 weights */
+#define TK_Q8_0_PER_RUN (TK_QK_K / 32) /* Q8_0 blocks of one 256-k run = one W4A8 tile column */
+
 /* The tensor types, described once: what the loaders, the launchers and the W4A8 kernels ask about a type is a column of this table, and
  * a new type is one more row ("Adding a tensor type") */
 struct tk_type_desc {
@@ -98,19 +106,20 @@ TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
         /*                         name    elems bytes tile               mask idx shares embd   lora   host_q */
         case TK_TYPE_F32:  return {"F32",  1,    4,    0,                 0,   -1, false, false, false, false};
         case TK_TYPE_F16:  return {"F16",  1,    2,    0,                 0,   -1, false, true,  true,  false};
+        case TK_TYPE_Q8_0: return {"Q8_0", 32,   34,   TK_Q8_0_TILE_BYTES, 32, 6,  false, true,  false, true};
         case TK_TYPE_Q2_K: return {"Q2_K", 256,  84,   TK_Q2K_TILE_BYTES, 16,  5,  false, true,  false, false};
         case TK_TYPE_Q3_K: return {"Q3_K", 256,  110,  TK_Q3K_TILE_BYTES, 8,   4,  false, true,  false, true};
         case TK_TYPE_Q4_K: return {"Q4_K", 256,  144,  TK_Q4K_TILE_BYTES, 1,   0,  true,  true,  true,  true};
         case TK_TYPE_Q5_K: return {"Q5_K", 256,  176,  TK_Q5K_TILE_BYTES, 4,   3,  false, true,  false, true};
-        case TK_TYPE_Q6_K: return {"Q6_K", 256,  210,  TK_Q6K_TILE_BYTES, 2,   1,  true,  false, true,  true};
+        case TK_TYPE_Q6_K: return {"Q6_K", 256,  210,  TK_Q6K_TILE_BYTES, 2,   1,  true,  true,  true,  true};
         default:           return {nullptr, 1,   4,    0,                 0,   -1, false, false, false, false};
     }
 }
 /* the lists the messages print: kept beside the table, edited with it */
-#define TK_TYPE_NAMES "F32, F16, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K"
-#define TK_TYPE_NAMES_OR "F32, F16, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
-#define TK_KQUANT_NAMES_OR "Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
-#define TK_TOKEN_EMBD_NAMES_OR "Q2_K, Q3_K, Q4_K, Q5_K or F16"
+#define TK_TYPE_NAMES "F32, F16, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K"
+#define TK_TYPE_NAMES_OR "F32, F16, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
+#define TK_KQUANT_NAMES_OR "Q8_0, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
+#define TK_TOKEN_EMBD_NAMES_OR "Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K or F16"
 #define TK_LORA_MERGE_NAMES_OR "Q4_K, Q6_K or F16"
 
 TK_HD constexpr bool tk_type_known(int type) { return tk_type_desc_of(type).name != nullptr; }
@@ -118,36 +127,48 @@ TK_HD constexpr bool tk_type_is_kquant(int type) { return tk_type_desc_of(type).
 TK_HD constexpr size_t tk_type_block_bytes(int type) { return (size_t)tk_type_desc_of(type).block_bytes; }
 TK_HD constexpr size_t tk_type_block_elems(int type) { return (size_t)tk_type_desc_of(type).block_elems; }
 
-/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make six values: the five k-quants alone and
- * the one mix of the two shares_launch types, whose kernels pick the tile type per segment at run time. */
-#define TK_KQUANT_FIRST TK_TYPE_Q2_K /* the k-quants are the contiguous enum range [TK_KQUANT_FIRST, TK_KQUANT_LAST] */
-#define TK_KQUANT_LAST TK_TYPE_Q6_K
+/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make seven values: the six tiled types alone
+ * and the one mix of the two shares_launch types, whose kernels pick the tile type per segment at run time. */
+/* the tiled types (tile_bytes != 0), listed: their enum values are not one range (Q8_0 = 8, the k-quants 10 .. 14), and a loop over
+ * [first, last] would lean on type 9 having no row */
+#define TK_TILED_TYPES 6
+TK_HD constexpr int tk_tiled_type(int i) {
+    constexpr int types[TK_TILED_TYPES] = {TK_TYPE_Q8_0, TK_TYPE_Q2_K, TK_TYPE_Q3_K, TK_TYPE_Q4_K, TK_TYPE_Q5_K, TK_TYPE_Q6_K};
+    return types[i];
+}
 #define TK_TYPES_Q4K_Q6K (tk_type_desc_of(TK_TYPE_Q4_K).mask | tk_type_desc_of(TK_TYPE_Q6_K).mask)
 #define TK_KERNEL_INDEX_Q4K_Q6K 2
-#define TK_KERNEL_VARIANTS 6
+#define TK_KERNEL_VARIANTS 7
 TK_HD constexpr bool tk_types_has(int types, int type) { return (types & tk_type_desc_of(type).mask) != 0; }
 TK_HD constexpr bool tk_types_is(int types, int type) { return types == tk_type_desc_of(type).mask; }
 /* tile bytes of a single-type launch: a compile-time pitch (tile addresses become scalar base + immediate); 0 for the mix */
 TK_HD constexpr size_t tk_types_tile_bytes(int types) {
-    for (int t = TK_KQUANT_FIRST; t <= TK_KQUANT_LAST; ++t)
-        if (tk_types_is(types, t)) return (size_t)tk_type_desc_of(t).tile_bytes;
+    for (int i = 0; i < TK_TILED_TYPES; ++i)
+        if (tk_types_is(types, tk_tiled_type(i))) return (size_t)tk_type_desc_of(tk_tiled_type(i)).tile_bytes;
     return 0;
 }
 
 #define TK_TYPE_ROW_CHECK(T, block, tile_per_block)                                                                                   \
     static_assert(sizeof(block) == tk_type_desc_of(T).block_bytes, #T ": block_bytes is not the size of its block struct");         \
     static_assert(tk_type_desc_of(T).tile_bytes == TK_TILE_ROWS * (tile_per_block), #T ": tile_bytes is not 16 x the tile's bytes per block (tk_llm_layout.h)")
+TK_TYPE_ROW_CHECK(TK_TYPE_Q8_0, tk_block_q8_0, TK_Q8_0_PER_RUN * 34); /* a tile column is one 256-k run: eight blocks per row */
+static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_Q8_0).block_elems == 0, "Q8_0: a 256-k run must be whole blocks");
 TK_TYPE_ROW_CHECK(TK_TYPE_Q2_K, tk_block_q2_K, 84);
 TK_TYPE_ROW_CHECK(TK_TYPE_Q3_K, tk_block_q3_K, 114); /* the tile holds the sixteen group scales as int8: 4 B more than the block's packed 6-bit ones */
 TK_TYPE_ROW_CHECK(TK_TYPE_Q4_K, tk_block_q4_K, 144);
 TK_TYPE_ROW_CHECK(TK_TYPE_Q5_K, tk_block_q5_K, 176);
 TK_TYPE_ROW_CHECK(TK_TYPE_Q6_K, tk_block_q6_K, 210);
 #undef TK_TYPE_ROW_CHECK
-/* every mask is one bit of its own, and the kernel indices of the six TYPES values are 0 .. 5, each once */
+/* every tiled type is listed once and nothing else has a tile; every mask is one bit of its own, and the kernel indices of the seven
+ * TYPES values are 0 .. 6, each once */
 TK_HD constexpr bool tk_type_table_consistent() {
     int masks = 0, indices = 1 << TK_KERNEL_INDEX_Q4K_Q6K;
-    for (int t = TK_KQUANT_FIRST; t <= TK_KQUANT_LAST; ++t) {
-        const tk_type_desc d = tk_type_desc_of(t);
+    int listed = 0;
+    for (int t = 0; t < 64; ++t) listed += tk_type_is_kquant(t) ? 1 : 0;
+    if (listed != TK_TILED_TYPES) return false;
+    for (int i = 0; i < TK_TILED_TYPES; ++i) {
+        const tk_type_desc d = tk_type_desc_of(tk_tiled_type(i));
+        if (d.tile_bytes == 0) return false;
         if (d.mask == 0 || (d.mask & (d.mask - 1)) != 0 || (masks & d.mask) != 0) return false;
         if (d.kernel_index < 0 || d.kernel_index >= TK_KERNEL_VARIANTS || ((indices >> d.kernel_index) & 1) != 0) return false;
         masks |= d.mask;
@@ -155,7 +176,7 @@ TK_HD constexpr bool tk_type_table_consistent() {
     }
     return indices == (1 << TK_KERNEL_VARIANTS) - 1;
 }
-static_assert(tk_type_table_consistent(), "tk_type_desc_of: masks must be distinct bits and kernel indices 0 .. 5, each once");
+static_assert(tk_type_table_consistent(), "tk_type_desc_of: tk_tiled_type must list the rows with a tile, masks must be distinct bits and kernel indices 0 .. 6, each once");
 
 /* 6-bit (scale, min) pair j of a Q4_K block */
 TK_HD void tk_q4k_get_scale_min(int j, const uint8_t* q, uint8_t* sc, uint8_t* m) {
@@ -298,6 +319,9 @@ TK_HD void tk_q2k_set_quant(tk_block_q2_K* b, int i, int q) {
     uint8_t* p = &b->qs[32 * n + l];
     *p = (uint8_t)((*p & ~(3 << (2 * j))) | ((q & 3) << (2 * j)));
 }
+
+/* weight i (0..31) of a Q8_0 block: d * q, exact in fp32 (11 significant bits times 8) */
+TK_HD float tk_q8_0_dequant(const tk_block_q8_0* b, int i) { return tk_f16_to_f32(b->d) * (float)b->qs[i]; }
 
 /*
  * Deterministic min/max quantisers ("the build's own Q4_K_M recipe").
@@ -507,6 +531,24 @@ TK_HD void tk_quantize_q2_K(const float* x, tk_block_q2_K* out) {
             }
             tk_q2k_set_quant(out, 16 * g + i, q);
         }
+    }
+}
+
+/* Q8_0: ggml's published quantize_row_q8_0_ref, value for value: d = amax / 127, id = d ? 1 / d : 0, q = roundf(x * id) (half away
+ * from zero), d stored as f16 */
+TK_HD void tk_quantize_q8_0(const float* x, tk_block_q8_0* out) {
+    float amax = 0.0f;
+    for (int i = 0; i < 32; ++i) {
+        float a = tk_fabsf(x[i]);
+        amax = a > amax ? a : amax;
+    }
+    const float d = tk_divf(amax, 127.0f);
+    const float id = d != 0.0f ? tk_divf(1.0f, d) : 0.0f;
+    out->d = tk_f32_to_f16(d);
+    for (int i = 0; i < 32; ++i) {
+        const float v = x[i] * id, t = (float)(int)v; /* |v| <= 127 up to rounding: the truncation is exact */
+        const float r = v - t;
+        out->qs[i] = (int8_t)((int)t + (r >= 0.5f ? 1 : r <= -0.5f ? -1 : 0));
     }
 }
 

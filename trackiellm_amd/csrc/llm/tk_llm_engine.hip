@@ -36,8 +36,10 @@ static int use_more_bits(int i, int n) { return i < n / 8 || i >= 7 * n / 8 || (
 /* ftype 15 Q4_K_M / 17 Q5_K_M: the base type, Q6_K for v / down of use_more_bits layers; 16 Q5_K_S: all Q5_K; 14 Q4_K_S: Q4_K, Q5_K for v of
  * layers < 4 and down of layers < n_layer / 8; 11 Q3_K_S: all Q3_K; 12 Q3_K_M: Q3_K, v Q5_K for layers < 2 else Q4_K, o Q4_K, down Q5_K
  * for layers < n_layer / 16 else Q4_K; 10 Q2_K: Q2_K, v Q4_K when n_head / n_kv_head >= 4 else Q3_K, o and down Q3_K; 21 Q2_K_S: Q2_K,
- * v Q4_K when n_head / n_kv_head >= 4, down Q4_K for layers < n_layer / 8.  output is Q6_K in all eight */
+ * v Q4_K when n_head / n_kv_head >= 4, down Q4_K for layers < n_layer / 8.  output is Q6_K in all eight.  7 Q8_0: every matrix, token_embd
+ * and output Q8_0 */
 int TkLlmModel::recipe_type(const TkLlmHParams& hp, int layer, int which, int ftype) {
+    if (ftype == 7) return (layer < 0 ? which == TK_T_OUT_NORM : which == TK_L_ATTN_NORM || which == TK_L_FFN_NORM) ? TK_TYPE_F32 : TK_TYPE_Q8_0;
     const int base = ftype == 10 || ftype == 21 ? TK_TYPE_Q2_K : ftype == 11 || ftype == 12 ? TK_TYPE_Q3_K : ftype == 16 || ftype == 17 ? TK_TYPE_Q5_K : TK_TYPE_Q4_K;
     if (layer < 0) return which == TK_T_OUTPUT ? TK_TYPE_Q6_K : (which == TK_T_TOKEN_EMBD ? base : TK_TYPE_F32);
     if (which == TK_L_ATTN_NORM || which == TK_L_FFN_NORM) return TK_TYPE_F32;
@@ -163,7 +165,8 @@ bool TkLlmModel::install(TkDevTensor* t, int type, int64_t rows, int64_t cols, v
         return false;
     }
     /* a matrix is held as tiles (a Q3_K tile is larger than its sixteen blocks: tk_llm_layout.h), anything else as the file's blocks */
-    t->bytes = is_matrix ? (size_t)(rows / TK_TILE_ROWS) * (cols / 256) * d.tile_bytes : (size_t)rows * cols / 256 * d.block_bytes;
+    if (cols % 256) { error = std::string("a ") + d.name + " tensor needs columns % 256 == 0 (the W4A8 tile and the Q8_K activation run are 256 k wide)"; return false; }
+    t->bytes = is_matrix ? (size_t)(rows / TK_TILE_ROWS) * (cols / 256) * d.tile_bytes : (size_t)rows * cols / d.block_elems * d.block_bytes;
     HIPQ(hipMalloc((void**)&t->data, t->bytes));
     if (!is_matrix) { /* token_embd stays in GGUF layout: one row is gathered per token */
         if (!d.token_embd) { error = "token_embd must be " TK_TOKEN_EMBD_NAMES_OR; return false; }
@@ -442,7 +445,8 @@ bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, i
     }
     HIPQ(hipSetDevice(device));
     if (const char* e = tk_llm_prepare_device(device)) { error = e; return false; }
-    const size_t nblk = (size_t)rows * (size_t)(K / 256), bb = tk_type_block_bytes(type);
+    const size_t nblk = (size_t)rows * (size_t)(K / 256); /* 256-k runs = tile columns; a run is 256 / block_elems blocks of the file */
+    const size_t bb = 256 / tk_type_block_elems(type) * tk_type_block_bytes(type);
     const size_t tb = (size_t)tk_type_desc_of(type).tile_bytes;
     const size_t nout = (size_t)ks * TK_MAX_ROWS * (size_t)rows;
     void* db = nullptr;

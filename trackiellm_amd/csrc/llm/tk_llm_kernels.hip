@@ -53,6 +53,12 @@ __global__ void k_synth_blocks(int type, uint64_t seed, uint64_t tid, int64_t nb
         tk_block_q2_K blk;
         tk_quantize_q2_K(x, &blk);
         ((tk_block_q2_K*)out)[b] = blk;
+    } else if (type == TK_TYPE_Q8_0) { /* b counts 256-weight runs here too: the run's eight 32-weight blocks */
+        for (int j = 0; j < TK_Q8_0_PER_RUN; ++j) {
+            tk_block_q8_0 blk;
+            tk_quantize_q8_0(x + 32 * j, &blk);
+            ((tk_block_q8_0*)out)[TK_Q8_0_PER_RUN * b + j] = blk;
+        }
     } else {
         tk_block_q6_K blk;
         tk_quantize_q6_K(x, &blk);
@@ -263,9 +269,32 @@ __global__ void k_repack_q2k(const tk_block_q2_K* src, int64_t nblk, uint8_t* ti
     }
 }
 
+/* Q8_0 tile (tk_llm_layout.h): a 256-k run of 16 rows = eight blocks per row.  nblk counts 256-k runs, as for the other tiles */
+__global__ void k_repack_q8_0(const tk_block_q8_0* src, int64_t nblk, uint8_t* tiles) {
+    const int lane = threadIdx.x;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t rt = blockIdx.y, blk = blockIdx.x;
+    const tk_block_q8_0* b = src + ((rt * 16 + n) * nblk + blk) * TK_Q8_0_PER_RUN;
+    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q8_0_TILE_BYTES;
+    for (int i = 0; i < 4; ++i) {
+        uint32_t dw[4];
+        for (int c = 0; c < 4; ++c) { /* dword 2 e + hh: weights 8 g + 4 hh .. + 3 of block 2 i + e */
+            const int8_t* q = b[2 * i + (c >> 1)].qs + 8 * g + 4 * (c & 1);
+            dw[c] = (uint32_t)(uint8_t)q[0] | ((uint32_t)(uint8_t)q[1] << 8) | ((uint32_t)(uint8_t)q[2] << 16) | ((uint32_t)(uint8_t)q[3] << 24);
+        }
+        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+    }
+    if (g == 0) {
+        uint32_t d[4];
+        for (int k = 0; k < 4; ++k) d[k] = (uint32_t)b[2 * k].d | ((uint32_t)b[2 * k + 1].d << 16);
+        *(uint4*)(tile + 4096 + n * 16) = make_uint4(d[0], d[1], d[2], d[3]);
+    }
+}
+
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s) {
     dim3 grid((unsigned)(K / 256), (unsigned)(rows / 16));
     switch (type) {
+        case TK_TYPE_Q8_0: hipLaunchKernelGGL(k_repack_q8_0, grid, dim3(64), 0, s, (const tk_block_q8_0*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q2_K: hipLaunchKernelGGL(k_repack_q2k, grid, dim3(64), 0, s, (const tk_block_q2_K*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q3_K: hipLaunchKernelGGL(k_repack_q3k, grid, dim3(64), 0, s, (const tk_block_q3_K*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q4_K: hipLaunchKernelGGL(k_repack_q4k, grid, dim3(64), 0, s, (const tk_block_q4_K*)blocks, K / 256, tiles); break;
@@ -292,6 +321,12 @@ __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, f
     } else if (type == TK_TYPE_Q2_K) {
         const tk_block_q2_K* row = (const tk_block_q2_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q2k_dequant(row + i / 256, i % 256);
+    } else if (type == TK_TYPE_Q8_0) {
+        const tk_block_q8_0* row = (const tk_block_q8_0*)embd + (int64_t)tok[r] * (D / 32);
+        x[(int64_t)r * D + i] = tk_q8_0_dequant(row + i / 32, i % 32);
+    } else if (type == TK_TYPE_Q6_K) {
+        const tk_block_q6_K* row = (const tk_block_q6_K*)embd + (int64_t)tok[r] * (D / 256);
+        x[(int64_t)r * D + i] = tk_q6k_dequant(row + i / 256, i % 256);
     } else {
         const tk_block_q4_K* row = (const tk_block_q4_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q4k_dequant(row + i / 256, i % 256);
@@ -488,6 +523,7 @@ struct FragQ6 { uint4 q0, q1, qh, sc; uint32_t d; };
 struct FragQ5 { uint4 q0, q1, h; uint2 qh; };
 struct FragQ3 { uint4 q; uint2 qh, sc; uint32_t d; };
 struct FragQ2 { uint4 q; uint2 sm; uint32_t dd; };
+struct FragQ8 { uint4 q[4], d; };
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef unsigned v2u32 __attribute__((ext_vector_type(2)));
@@ -536,6 +572,15 @@ __device__ __forceinline__ FragQ2 load_q2(const uint8_t* tile, int lane) {
     return f;
 }
 
+/* q[i]: the lane's eight weights of blocks 2 i and 2 i + 1, operand bytes as they stand; d: the eight f16 block scales of the lane's row */
+__device__ __forceinline__ FragQ8 load_q8(const uint8_t* tile, int lane) {
+    FragQ8 f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f.q[i] = ldg_nt(tile + 1024 * i + lane * 16);
+    f.d = ldg_nt(tile + 4096 + (lane & 15) * 16);
+    return f;
+}
+
 __device__ __forceinline__ FragQ6 load_q6(const uint8_t* tile, int lane) {
     FragQ6 f;
     f.q0 = ldg_nt(tile + lane * 16);
@@ -561,6 +606,7 @@ TK_TILE(TileQ3, TK_TYPE_Q3_K, FragQ3, load_q3);
 TK_TILE(TileQ4, TK_TYPE_Q4_K, FragQ4, load_q4);
 TK_TILE(TileQ5, TK_TYPE_Q5_K, FragQ5, load_q5);
 TK_TILE(TileQ6, TK_TYPE_Q6_K, FragQ6, load_q6);
+TK_TILE(TileQ8, TK_TYPE_Q8_0, FragQ8, load_q8);
 #undef TK_TILE
 /* the tile pitch of a launch: a compile-time constant in single-type launches (tile addresses become scalar base + immediate); the
  * Q4_K | Q6_K kernels take it from the segment's type */
@@ -915,6 +961,51 @@ __device__ __forceinline__ void mma_q2(const OpsQ4& o, const uint8_t* lds_act, c
     }
 }
 
+/*
+ * Q8_0: w = d * q per block of 32, d an f16 and q any int8, so a 256-k run carries eight scales per weight row and nothing folds into
+ * the operand: the tile's bytes ARE the B operand.  Per 32-block j one K = 32 MFMA from a zero accumulator gives the exact integer
+ * P_j = sum_k q_k a_k (|P_j| <= 32 * 128 * 127 < 2^23) over the existing Q8_K activation image — its [2 sub-blocks][8] lane layout holds the
+ * A operand of a 32-block as one 8-byte half of the 16-byte read — and the contract's step is acc = fmaf(d_j * d8, (float)P_j, acc), blocks
+ * ascending: one convert, one multiply and one fma per output and block.  With seven d of a run +0 and the live block's q in -32..31
+ * this is the Q6_K contract of the run's Q6_K twin (fmaf(+-0, P, acc) = acc).
+ */
+struct OpsQ8 { v4i b[4]; float d[8]; };
+
+__device__ __forceinline__ void unpack_q8(const FragQ8& f, OpsQ8& o) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o.b[i] = (v4i){(int)f.q[i].x, (int)f.q[i].y, (int)f.q[i].z, (int)f.q[i].w};
+    const uint32_t dd[4] = {f.d.x, f.d.y, f.d.z, f.d.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o.d[j] = f16bits_to_f32((dd[j >> 1] >> (16 * (j & 1))) & 0xffffu);
+}
+
+/* the 8-byte half e of a 16-byte operand register set: the A or B operand of one 32-block */
+__device__ __forceinline__ long half_of(const v4i& v, int e) { return (long)(((unsigned long)(uint32_t)v[2 * e + 1] << 32) | (uint32_t)v[2 * e]); }
+
+template <int MT>
+__device__ __forceinline__ void mma_q8(const OpsQ8& o, const uint8_t* lds_act, const float* lds_ad, size_t act_ts, int ad_ts, int blk, int lane,
+                                       float (*acc)[4]) {
+    const int g = lane >> 4;
+    const v4i zero = {0, 0, 0, 0};
+    const uint8_t* ap = lds_act + (size_t)blk * 4096 + lane * 16;
+    v4f da[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) da[m] = *(const v4f*)(lds_ad + m * ad_ts + blk * TK_ROW_SLOTS + 4 * g);
+#pragma unroll
+    for (int j2 = 0; j2 < 4; ++j2) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const v4i a = *(const v4i*)(ap + m * act_ts + j2 * 1024);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const v4i P = __builtin_amdgcn_mfma_i32_16x16x32_i8(half_of(a, e), half_of(o.b[j2], e), zero, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[m][r] = tk_fmaf(o.d[2 * j2 + e] * da[m][r], (float)P[r], acc[m][r]);
+            }
+        }
+    }
+}
+
 size_t tk_gemv_lds_bytes(int K, int ks, int mtiles) {
     size_t Kr = (size_t)K / ks;
     return (size_t)mtiles * (Kr * TK_ROW_SLOTS + (Kr / 256) * TK_ROW_SLOTS * 4 + (Kr / 256) * 256);
@@ -974,12 +1065,18 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
      * group's tiles stay in flight under the current group's MFMAs (a branch around a load costs a vmcnt(0)). */
     constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
     constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
+    constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     TileQ4::Frag f4[HAS4 ? PF : 1];
     TileQ6::Frag f6[HAS6 ? PF : 1];
     TileQ5::Frag f5[ONLY5 ? PF : 1];
     TileQ3::Frag f3[ONLY3 ? PF : 1];
     TileQ2::Frag f2[ONLY2 ? PF : 1];
+    TileQ8::Frag f8[ONLY8 ? PF : 1];
+    if constexpr (ONLY8) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) f8[u] = TileQ8::load(tile + (size_t)u * tile_bytes, lane);
+    }
     if constexpr (ONLY3) {
 #pragma unroll
         for (int u = 0; u < PF; ++u) f3[u] = TileQ3::load(tile + (size_t)u * tile_bytes, lane);
@@ -1246,6 +1343,29 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q2<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
+    if constexpr (ONLY8) {
+        const uint8_t* tp = tile + PF * tile_bytes;
+#pragma unroll 1
+        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                OpsQ8 o;
+                __builtin_amdgcn_sched_barrier(0);
+                unpack_q8(f8[u], o);
+                __builtin_amdgcn_sched_barrier(0);
+                f8[u] = TileQ8::load(tp + u * tile_bytes, lane);
+                __builtin_amdgcn_sched_barrier(0);
+                mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            OpsQ8 o;
+            __builtin_amdgcn_sched_barrier(0);
+            unpack_q8(f8[u], o);
+            mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
+        }
+    }
 
     const int n = a.col0 + row_base + rt * TK_TILE_ROWS + (lane & 15);
     const int g = lane >> 4;
@@ -1427,6 +1547,44 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
 #undef TK_LDS_TILE
 }
 
+/* gemm_block for a Q8_0 tile: per M-tile eight K = 32 MFMAs from zero, one per 32-block, finished — block by block, ascending — while the
+ * next M-tile's MFMAs run.  Same ring, same look-ahead, same rot */
+struct PTile8 { v4i p[8]; v4f da; };
+__device__ __forceinline__ void finish_tile_q8(const PTile8& R, const OpsQ8& o, float* acc) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = tk_fmaf(o.d[j] * R.da[r], (float)R.p[j][r], acc[r]);
+}
+template <int MT>
+__device__ __forceinline__ void gemm_block_q8(const OpsQ8& o, const uint8_t* chunk, int rot, int lane, float (&acc)[MT][4]) {
+    constexpr int OFF_AMN = MT * 4096, OFF_AD = MT * 4096 + MT * 512;
+    const v4i zero = {0, 0, 0, 0};
+    constexpr int AD = 2;
+    ATile T[AD + 1];
+    PTile8 R;
+    const uint8_t* act[2] = {chunk + rot * 4096, chunk - rot * 4096};
+    const uint8_t* adp[2] = {chunk + OFF_AD + rot * 64, chunk + OFF_AD - rot * 64};
+#define TK_LDS_TILE(slot, m) lds_tile<false>(T[slot], act[(m) >= MT / 2] + (m) * 4096, chunk + OFF_AMN, adp[(m) >= MT / 2] + (m) * 64, lane)
+#pragma unroll
+    for (int m = 0; m < AD && m < MT; ++m) TK_LDS_TILE(m, m);
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        if (m + AD < MT) TK_LDS_TILE((m + AD) % (AD + 1), m + AD);
+        __builtin_amdgcn_sched_barrier(0);
+        const ATile& t = T[m % (AD + 1)];
+        PTile8 c;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) c.p[j] = __builtin_amdgcn_mfma_i32_16x16x32_i8(half_of(t.a[j >> 1], j & 1), half_of(o.b[j >> 1], j & 1), zero, 0, 0, 0);
+        c.da = t.da;
+        if (m > 0) finish_tile_q8(R, o, acc[m - 1]);
+        R = c;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    finish_tile_q8(R, o, acc[MT - 1]);
+#undef TK_LDS_TILE
+}
+
 /* One weight tile per wave (two adjacent tiles per wave halve the LDS operand stream but leave one wave per SIMD: 25 % slower on MI355X,
  * profiles/r01_gemm_batched.txt).  NT and CB are that choice and the ring's one block per slot as constants: the loops over them stay in
  * the source because folding them by hand changes the compiler's schedule of this kernel (k_gemm_w4a8<12, 3> then spills). */
@@ -1458,6 +1616,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     const int type = a.seg[seg].type;
     constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
     constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
+    constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     const size_t tile_bytes = types_tile_bytes<TYPES>(is4);
     const size_t tile_pitch = (size_t)nblk_total * tile_bytes; /* to the same block of the next row tile */
@@ -1501,6 +1660,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     TileQ5::Frag f5[ONLY5 ? NT : 1];
     TileQ3::Frag f3[ONLY3 ? NT : 1];
     TileQ2::Frag f2[ONLY2 ? NT : 1];
+    TileQ8::Frag f8[ONLY8 ? NT : 1];
     if (active) {
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
@@ -1509,6 +1669,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             if constexpr (ONLY5) f5[w] = TileQ5::load(tile + w * tile_pitch, lane);
             if constexpr (ONLY3) f3[w] = TileQ3::load(tile + w * tile_pitch, lane);
             if constexpr (ONLY2) f2[w] = TileQ2::load(tile + w * tile_pitch, lane);
+            if constexpr (ONLY8) f8[w] = TileQ8::load(tile + w * tile_pitch, lane);
         }
     }
     for (int i = 0; i < CB && i < nb; ++i) stage(i, i);
@@ -1569,6 +1730,17 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             for (int w = 0; w < NT; ++w) f2[w] = TileQ2::load(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
             gemm_block<MT, NT, TK_TYPE_Q2_K>(o, chunk, rot, lane, acc);
+        }
+        if constexpr (ONLY8) {
+            OpsQ8 o8[NT];
+#pragma unroll
+            for (int w = 0; w < NT; ++w) unpack_q8(f8[w], o8[w]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NT; ++w) f8[w] = TileQ8::load(next + w * tile_pitch, lane);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NT; ++w) gemm_block_q8<MT>(o8[w], chunk, rot, lane, acc[w]);
         }
     }
     if (!active) return;
@@ -1759,6 +1931,28 @@ __device__ __forceinline__ void unpack_q2_x32(const FragQ2& f0, const FragQ2& f1
     o.dmin = f16bits_to_f32(dd >> 16);
 }
 
+/* Q8_0 on the 32x32x32 map: one v_mfma_i32_32x32x32_i8 is exactly one 32-block of the wave's 32 weight rows.  After the lane swap dword
+ * pair (2 e, 2 e + 1) of load i holds k-slices 2 h and 2 h + 1 of block 2 i + e: b[j] = the lane's sixteen weights of block j.  d: the
+ * eight scales of the lane's own weight row (lanes 16..31 of a half: tile 1's) */
+struct Ops32Q8 { v4i b[8]; float d[8]; };
+__device__ __forceinline__ void unpack_q8_x32(const FragQ8& f0, const FragQ8& f1, int lane, Ops32Q8& o) {
+    const bool up = (lane & 16) != 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t x0[4] = {f0.q[i].x, f0.q[i].y, f0.q[i].z, f0.q[i].w}, x1[4] = {f1.q[i].x, f1.q[i].y, f1.q[i].z, f1.q[i].w};
+        uint32_t sa[4], sb[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) pair_swap(x0[c], x1[c], &sa[c], &sb[c]);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) o.b[2 * i + e] = (v4i){(int)sa[2 * e], (int)sa[2 * e + 1], (int)sb[2 * e], (int)sb[2 * e + 1]};
+    }
+    const uint32_t dd[4] = {up ? f1.d.x : f0.d.x, up ? f1.d.y : f0.d.y, up ? f1.d.z : f0.d.z, up ? f1.d.w : f0.d.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o.d[j] = f16bits_to_f32((dd[j >> 1] >> (16 * (j & 1))) & 0xffffu);
+}
+template <int QT> struct G32Ops { typedef struct Ops32 type; };
+template <> struct G32Ops<TK_TYPE_Q8_0> { typedef Ops32Q8 type; };
+
 /* s_waitcnt vmcnt(n) alone (expcnt / lgkmcnt untouched): until all but this wave's n youngest vector-memory operations are done.  The
  * LDS-DMA pieces of a chunk are invisible to the compiler's own wait insertion, so the ring is guarded by hand. */
 __device__ __forceinline__ void wait_vmcnt(int n) {
@@ -1791,8 +1985,21 @@ __device__ __forceinline__ Ptrs32 block_ptrs32(const uint8_t* blk, int lane) {
     return p;
 }
 
+/* the A operand of 32-block j of a Q8_0 tile: the 8-byte halves e = j & 1 of the two 16-byte groups (k-slices 2 h and 2 h + 1) the other
+ * types read whole */
+__device__ __forceinline__ v4i q8_a32(const Ptrs32& p, int t, int j) {
+    const uint8_t* q = p.ap + t * 8192 + (j >> 1) * 1024 + (j & 1) * 8;
+    const v2i x = *(const v2i*)q, y = *(const v2i*)(q + 256);
+    return (v4i){x.x, x.y, y.x, y.y};
+}
+
 template <int QT>
 __device__ __forceinline__ void load_atile32(ATile32& T, const Ptrs32& p, int t) {
+    if constexpr (QT == TK_TYPE_Q8_0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) T.a[j] = q8_a32(p, t, j);
+        return;
+    }
 #pragma unroll
     for (int u = 0; u < 4; ++u) T.a[u] = *(const v4i*)(p.ap + t * 8192 + (u >> 1) * 1024 + (u & 1) * 256);
     if (tk_has_mins(QT)) T.mn = *(const v8h*)(p.mp + t * 1024);
@@ -1854,13 +2061,54 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
     }
 }
 
+/* gemm_block32 for a Q8_0 tile pair: per M-tile eight MFMAs from zero, one per 32-block; block j is finished (convert, scale product, fma
+ * per output) while block j + 1 is in the matrix pipe, so two result sets are live, not eight */
+template <typename Hook>
+__device__ __forceinline__ void gemm_block32_q8(const Ops32Q8& o, ATile32& T, const Ptrs32& p, float (&acc)[TK_G32_MTW][16], Hook&& after_mfmas) {
+    const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < TK_G32_MTW; ++t) {
+        v4i A[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) A[j] = T.a[j];
+        v4f da[4];
+#pragma unroll
+        for (int j = 4; j < 8; ++j) A[j] = q8_a32(p, t, j);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) da[b] = *(const v4f*)(p.dp + t * 128 + b * 32);
+        v16i P = TK_MFMA32(A[0], o.b[0], zero, 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const v16i Q = P;
+            if (j + 1 < 8) P = TK_MFMA32(A[j + 1], o.b[j + 1], zero, 0, 0, 0);
+            if (j == 6) { /* every operand of the tile has been consumed or issued: the next tile's first reads, and a quarter of the ring staging */
+                __builtin_amdgcn_sched_barrier(0);
+                if (t + 1 < TK_G32_MTW) load_atile32<TK_TYPE_Q8_0>(T, p, t + 1);
+                after_mfmas(t);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[t][4 * b + i] = tk_fmaf(o.d[j] * da[b][i], (float)Q[4 * b + i], acc[t][4 * b + i]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 /* `tile` is wave-uniform (an SGPR pair); the per-lane offsets are 32-bit and opaque per call, so the loads take the scalar-base form and no
  * 64-bit per-lane address is hoisted out of the K loop and held across it (load_q4 / load_q6 with a lane pointer cost 12 registers there) */
 template <int QT>
 __device__ __forceinline__ typename TkTile<QT>::Frag g32_load(const uint8_t* tile, int lane) {
     unsigned lo = (unsigned)lane * 16u, ho = (unsigned)(lane & 15) * 16u;
     asm volatile("" : "+v"(lo), "+v"(ho));
-    if constexpr (QT == TK_TYPE_Q2_K) {
+    if constexpr (QT == TK_TYPE_Q8_0) {
+        FragQ8 f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f.q[i] = ldg_nt(tile + 1024 * i + lo);
+        f.d = ldg_nt(tile + 4096 + ho);
+        return f;
+    } else if constexpr (QT == TK_TYPE_Q2_K) {
         FragQ2 f;
         f.q = ldg_nt(tile + lo);
         const v2u32 sm = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + ho + ((lo >> 6) & 8u)));
@@ -1901,8 +2149,9 @@ __device__ __forceinline__ typename TkTile<QT>::Frag g32_load(const uint8_t* til
     }
 }
 template <int QT>
-__device__ __forceinline__ void g32_unpack(const typename TkTile<QT>::Frag& f0, const typename TkTile<QT>::Frag& f1, int lane, Ops32& o) {
-    if constexpr (QT == TK_TYPE_Q4_K) unpack_q4_x32(f0, f1, lane, o);
+__device__ __forceinline__ void g32_unpack(const typename TkTile<QT>::Frag& f0, const typename TkTile<QT>::Frag& f1, int lane, typename G32Ops<QT>::type& o) {
+    if constexpr (QT == TK_TYPE_Q8_0) unpack_q8_x32(f0, f1, lane, o);
+    else if constexpr (QT == TK_TYPE_Q4_K) unpack_q4_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q3_K) unpack_q3_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q2_K) unpack_q2_x32(f0, f1, lane, o);
@@ -1938,7 +2187,7 @@ __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_byte
         ATile32 T;
         load_atile32<QT>(T, bp, 0); /* tile 0's operands: their LDS latency hides under the unpack */
         __builtin_amdgcn_sched_barrier(0);
-        Ops32 o;
+        typename G32Ops<QT>::type o;
         g32_unpack<QT>(f0, f1, lane, o);
         __builtin_amdgcn_sched_barrier(0);
         f0 = g32_load<QT>(next, lane);
@@ -1946,7 +2195,8 @@ __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_byte
         __builtin_amdgcn_sched_barrier(0);
         /* the last block restages itself into the slot nobody reads any more: no branch around the DMA issue */
         /* the ring's four staging parts ride on the tiles' MFMA phases: one per tile */
-        gemm_block32<QT>(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
+        if constexpr (QT == TK_TYPE_Q8_0) gemm_block32_q8(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
+        else gemm_block32<QT>(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -1999,6 +2249,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     const int type = a.seg[seg].type;
     constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
     constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
+    constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     const size_t tile_bytes = types_tile_bytes<TYPES>(is4);
     const ptrdiff_t tile_pitch = a.swiglu ? a.seg[1].tiles - a.seg[0].tiles : (ptrdiff_t)((size_t)nblk_total * tile_bytes);
@@ -2060,6 +2311,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     if constexpr (ONLY5) g32_k_loop<TK_TYPE_Q5_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (ONLY3) g32_k_loop<TK_TYPE_Q3_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (ONLY2) g32_k_loop<TK_TYPE_Q2_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (ONLY8) g32_k_loop<TK_TYPE_Q8_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -2137,29 +2389,29 @@ typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
 /* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone.  Type index =
  * the type's kernel_index (tk_type_desc_of), TK_KERNEL_INDEX_Q4K_Q6K for the mix; the static_asserts below hold every column to it */
 static const TkGemvKernel k_gemv_fns[3][2][2][TK_KERNEL_VARIANTS] = {
-    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>},
-      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>}},
-     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>},
-      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>}}},
+    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>, k_gemv_w4a8<1, 1, 32, 0>},
+      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>, k_gemv_w4a8<2, 1, 32, 0>}},
+     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>, k_gemv_w4a8<1, 2, 32, 0>},
+      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>, k_gemv_w4a8<2, 2, 32, 0>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>, k_gemv_w4a8<2, 1, 32, 1>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>, k_gemv_w4a8<2, 1, 32, 2>}}},
 };
 /* [mt / 2 - 2][type index] */
 static const TkGemvKernel k_gemm_fns[5][TK_KERNEL_VARIANTS] = {
-    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>},
-    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>},
-    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>},
-    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>},
-    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>},
+    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>, k_gemm_w4a8<4, 32>},
+    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>, k_gemm_w4a8<6, 32>},
+    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>, k_gemm_w4a8<8, 32>},
+    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>, k_gemm_w4a8<10, 32>},
+    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>, k_gemm_w4a8<12, 32>},
 };
 /* [type index] */
-static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>};
+static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>, k_gemm32_w4a8<32>};
 
 /* column c of the three tables holds the kernels of TYPES = tk_column_types[c]: every type's mask at its kernel_index */
 constexpr bool tk_columns_match_the_type_table() {
-    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16};
-    for (int t = TK_KQUANT_FIRST; t <= TK_KQUANT_LAST; ++t)
-        if (tk_column_types[tk_type_desc_of(t).kernel_index] != tk_type_desc_of(t).mask) return false;
+    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16, 32};
+    for (int i = 0; i < TK_TILED_TYPES; ++i)
+        if (tk_column_types[tk_type_desc_of(tk_tiled_type(i)).kernel_index] != tk_type_desc_of(tk_tiled_type(i)).mask) return false;
     return tk_column_types[TK_KERNEL_INDEX_Q4K_Q6K] == TK_TYPES_Q4K_Q6K;
 }
 static_assert(tk_columns_match_the_type_table(), "k_gemv_fns / k_gemm_fns / k_gemm32_fns: column order against tk_type_desc_of");

@@ -2,7 +2,7 @@
  * tk_llm_layout.h — HBM layouts of the MI355X LLM path.
  *
  * GGUF k-quant blocks are kept bit-for-bit (the same quantised values, and the file's bytes per 256 weights
- * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked) but re-tiled at load time so that one wavefront's 16-byte-per-lane
+ * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked; Q8_0: eight 34-byte blocks per 256 weights) but re-tiled at load time so that one wavefront's 16-byte-per-lane
  * load is a contiguous 1 KiB run that already IS an MFMA operand:
  *
  *  Weight tile = 16 weight rows x 256 k (one super-block column).  Lane l = (n = l & 15, g = l >> 4)
@@ -26,6 +26,11 @@
  *      [1024 ,1280)  16 rows x 16 (scale, min) bytes as the block holds them (low nibble scale, high nibble min), byte 8 h + j = group
  *                    2 j + h: a lane reads the 8 bytes of its k half
  *      [1280 ,1344)  16 x {f16 d, f16 dmin}
+ *  Q8_0 tile (4352 B = 16 x 272 = 16 rows x eight 34-byte blocks): a 256-k run of 16 rows, the int8 quants as the file holds them
+ *      [0    ,4096)  four loads: load i, lane l -> 4 dwords, dword 2 e + hh = the weights k0 + 4 hh .. + 3 (k0 = 32 (2 i + e) + 8 g) of
+ *                    32-block 2 i + e: the lane's eight weights of each block, already the B operand bytes (dwords 2 e, 2 e + 1 of
+ *                    load i are one v_mfma_i32_16x16x32_i8 operand; the whole load is the 16x16x64 operand of the other tiles)
+ *      [4096 ,4352)  16 rows x 8 f16 d, row n's eight block scales in block order: one 16-byte read per lane
  *  Q3_K tile (1824 B = 16 x 114): weights stored as u = q + 4 (0..7).  Operand dword o = 2 j + hh (o = 0..15) of lane l holds the four
  *  weights k0 + 4 hh + t (t = 0..3, k0 = 32 j + 8 g) of sub-block j, as in the tiles above
  *      [0    ,1024)  one load: lane l -> 4 dwords; bits 8 t + 2 (o & 3) .. + 1 of dword o >> 2 = u & 3 of weight t of operand dword o
@@ -71,6 +76,7 @@
 #define TK_Q4K_TILE_BYTES 2304
 #define TK_Q5K_TILE_BYTES 2816
 #define TK_Q6K_TILE_BYTES 3360
+#define TK_Q8_0_TILE_BYTES 4352
 #define TK_ROW_SLOTS 16  /* rows of one MFMA M-tile */
 #define TK_MAX_TILES 16   /* M-tiles per pass: a weight tile is unpacked once and multiplied against all of them */
 #define TK_MAX_ROWS (TK_ROW_SLOTS * TK_MAX_TILES)
