@@ -273,6 +273,20 @@ TK_API const char* tk_mi355x_llm_runner_tool_call_text(struct tk_llm_runner_s* r
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_gemm_pair(int device, int M, int N, int K, const float* a, const float* w, const float* bias,
                                                         const float* residual, int act, int f16, float* c_staged, float* c_tiled);
 
+/* test hook for the node-by-node ONNX executor (csrc/nn/tk_onnx_exec): loads `path`, binds the n_feeds float tensors (name, data on the
+ * host, rank and dims), runs the graph once and keeps host copies of the n_outputs named float values WITH THE SHAPES THE EXECUTOR
+ * PRODUCED.  A refusal (unsupported op / attribute, bad shapes) comes back as an error code with the executor's text as the error
+ * detail.  Integer tensors enter a graph only as initialisers; an integer-valued output is an error.  The result is read with the
+ * accessors below (i = index into output_names) and released with tk_mi355x_onnx_result_free. */
+typedef struct tk_mi355x_onnx_result_s tk_mi355x_onnx_result_t;
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_onnx_run(int device, const char* path, int32_t n_feeds, const char* const* feed_names,
+                                                       const float* const* feed_data, const int32_t* feed_ranks, const int64_t* const* feed_dims,
+                                                       int32_t n_outputs, const char* const* output_names, tk_mi355x_onnx_result_t** out_result);
+TK_API int32_t tk_mi355x_onnx_result_rank(const tk_mi355x_onnx_result_t* r, int32_t i);
+TK_API const int64_t* tk_mi355x_onnx_result_dims(const tk_mi355x_onnx_result_t* r, int32_t i);
+TK_API const float* tk_mi355x_onnx_result_data(const tk_mi355x_onnx_result_t* r, int32_t i);
+TK_API void tk_mi355x_onnx_result_free(tk_mi355x_onnx_result_t** r);
+
 #ifdef __cplusplus
 }
 #endif

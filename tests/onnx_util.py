@@ -100,6 +100,10 @@ def attr_float(name, v):
     return _ld(1, name.encode()) + _varint((2 << 3) | 5) + struct.pack("<f", v) + _vi(20, 1)
 
 
+def attr_floats(name, vals):
+    return _ld(1, name.encode()) + b"".join(_varint((7 << 3) | 5) + struct.pack("<f", v) for v in vals) + _vi(20, 6)
+
+
 def attr_graph(name, graph_bytes):
     """a sub-graph attribute (AttributeProto.g = 6, type GRAPH = 5): the then_branch / else_branch of If"""
     return _ld(1, name.encode()) + _ld(6, graph_bytes) + _vi(20, 5)
@@ -127,10 +131,11 @@ def value_info(name, elem_type, dims):
     return _ld(1, name.encode()) + _ld(2, _ld(1, tensor_type))
 
 
-def model(nodes, initialisers, inputs, outputs):
+def model(nodes, initialisers, inputs, outputs, opset=17):
+    """opset: the version of the default operator set the file imports (the definition of Softmax changed at 13)"""
     graph = b"".join(_ld(1, n) for n in nodes) + _ld(2, b"g") + b"".join(_ld(5, t) for t in initialisers)
     graph += b"".join(_ld(11, i) for i in inputs) + b"".join(_ld(12, o) for o in outputs)
-    return _vi(1, 8) + _ld(2, b"test") + _ld(7, graph) + _ld(8, _ld(1, b"") + _vi(2, 17))
+    return _vi(1, 8) + _ld(2, b"test") + _ld(7, graph) + _ld(8, _ld(1, b"") + _vi(2, opset))
 
 
 def vad_weights(seed, n_bins=33, n_fft=64, hidden=32):
@@ -517,6 +522,8 @@ def spec_nodes(spec):
                 attrs.append(attr_float(k, v))
             elif isinstance(v, int):
                 attrs.append(attr_int(k, v))
+            elif len(v) and isinstance(v[0], float):
+                attrs.append(attr_floats(k, v))
             else:
                 attrs.append(attr_ints(k, v))
         nodes.append(node(nd["op"], nd["in"], nd["out"], attrs, name=next(o for o in nd["out"] if o) + "_node"))

@@ -12,5 +12,6 @@ from .llm import LlmHParams, LlmModel, LlmSession, LlmPipe, PipeHandle, ModelLoa
 from .llm import TYPE_F32, TYPE_F16, TYPE_Q8_0, TYPE_Q2_K, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K, FTYPE_Q8_0, FTYPE_Q2_K, FTYPE_Q2_K_S, FTYPE_Q3_K_S, FTYPE_Q3_K_M, FTYPE_Q4_K_S, FTYPE_Q4_K_M, FTYPE_Q5_K_S, FTYPE_Q5_K_M  # noqa: F401
 from .vision import ObjectDetector, VisionPipeline, classify_attributes, preprocess, COCO80  # noqa: F401,E402
 from .vision import DepthEstimator, depth_onnx_probe, fuse_data, fusion_reset, fusion_raw_distance  # noqa: F401,E402
+from .vision import onnx_run  # noqa: F401,E402
 from .audio import Asr, Vad, WhisperHP, WHISPER_TINY_EN, AudioPipeline  # noqa: F401,E402
 from .cortex import Cortex, RocmDispatcher, PreprocessParams, DepthPostParams, DepthToPointsParams, Float3  # noqa: F401,E402

@@ -20,9 +20,15 @@
  *   along axis 0, forward or reversed; scan outputs along axis 0) run their body graph in the same value map, one fresh set of arena tensors
  *   per iteration — what exporters emit for recurrences written as Python loops.  A condition computed from activations (Equal / Less / Greater
  *   on float tensors of up to 64 elements) is evaluated on the host after a stream synchronisation.
- * Anything else fails at load time with the op's name.
+ * Anything else fails at load time with the op's name.  An attribute this path cannot honour is refused when its node runs, with the op's
+ * and the attribute's name in the text — a pads / strides / dilations list of another length than the input's spatial rank, Gemm's alpha /
+ * beta / transA and a C that is not a row bias, a ConvTranspose output_shape that contradicts strides and pads — never dropped silently.
  * Arithmetic: fp32; every contraction is one k-ascending fma chain per output element (input channel outer, kernel row, kernel column
- * inner; the bias enters last), the exact-math exp / tanh / sigmoid / sqrt of common/tk_exact_math.h.
+ * inner; the bias enters last), the exact-math exp / tanh / sigmoid / sqrt of common/tk_exact_math.h.  Those routines are defined on the
+ * normal range; Sqrt, Log, Exp and Pow complete them here to IEEE results (NaN outside the domain, infinities, zeros, subnormals; Pow with
+ * the sign of an odd integer exponent on a negative base), bit for bit the shared routine wherever that is defined.  Softmax follows the
+ * file's opset: one axis from opset 13 on, the 2-D coercion at `axis` (default 1) before.  Every op is tested alone against a float64
+ * reference (tests/test_onnx_ops_gpu.py).
  */
 #ifndef TK_ONNX_EXEC_H
 #define TK_ONNX_EXEC_H

@@ -21,6 +21,54 @@
 enum { U_RELU, U_SIGMOID, U_TANH, U_SQRT, U_ABS, U_NEG, U_EXP, U_LOG };
 enum { B_ADD, B_SUB, B_MUL, B_DIV, B_POW };
 
+/* The shared routines of common/tk_exact_math.h are defined on the normal range only (sqrt and log of positive normal numbers, exp on
+ * [-87, 88]).  A graph from a file may feed anything, so the executor completes them here to IEEE results — NaN outside the domain,
+ * infinities, zeros and subnormals by exact power-of-two scaling — and leaves every in-range result bit for bit what the shared routine gives. */
+__device__ __forceinline__ float vg_sqrtf(float v) {
+    if (v != v || v < 0.0f) return NAN;
+    if (v == 0.0f || v == INFINITY) return v;
+    if (v < 1.17549435e-38f) return tk_sqrtf(v * 281474976710656.0f) * 5.9604644775390625e-8f; /* subnormal: sqrt(v 2^48) 2^-24, both scalings exact */
+    return tk_sqrtf(v);
+}
+__device__ __forceinline__ float vg_logf(float v) {
+    if (v != v || v < 0.0f) return NAN;
+    if (v == 0.0f) return -INFINITY;
+    if (v == INFINITY) return v;
+    if (v < 1.17549435e-38f) /* subnormal: log(v 2^64) - 64 ln 2, with the routine's own two-part ln 2 (64 ln2_hi is exact) */
+        return tk_fmaf(-64.0f, 0.693145751953125f, tk_fmaf(-64.0f, 1.42860682030941723e-6f, tk_logf(v * 18446744073709551616.0f)));
+    return tk_logf(v);
+}
+__device__ __forceinline__ float vg_expf(float v) {
+    if (v != v) return v;
+    if (v > 88.7228394f) return INFINITY; /* above log(FLT_MAX) */
+    if (v > 88.0f || v < -87.0f) { /* the tails the routine clamps: exp(v / 2) squared (v / 2 is exact); underflows gradually to 0 */
+        if (v < -104.0f) return 0.0f;
+        const float h = tk_expf(0.5f * v);
+        return h * h;
+    }
+    return tk_expf(v);
+}
+/* Pow: exponents 2 and 1 are exact, 0.5 is the root; everything else is exp(z log |x|) with the sign of an odd integer exponent restored,
+ * NaN for a negative base under a non-integer exponent, and C's pow() results at zero and infinite bases */
+__device__ __forceinline__ float vg_powf(float x, float z) {
+    if (z == 2.0f) return x * x;
+    if (z == 1.0f) return x;
+    if (z == 0.0f) return 1.0f;
+    if (x != x || z != z) return NAN;
+    if (z == 0.5f && x >= 0.0f) return vg_sqrtf(x);
+    const float ax = tk_fabsf(x);
+    const bool z_int = truncf(z) == z;
+    const bool z_odd = z_int && tk_fabsf(z) < 16777216.0f && ((int32_t)z & 1) != 0;
+    const bool neg = x < 0.0f || (x == 0.0f && tk_f32_bits(x) != 0u);
+    if (x < 0.0f && !z_int) return NAN;
+    float mag;
+    if (ax == 1.0f) mag = 1.0f;
+    else if (ax == 0.0f) mag = z > 0.0f ? 0.0f : INFINITY;
+    else if (ax == INFINITY) mag = z > 0.0f ? INFINITY : 0.0f;
+    else mag = vg_expf(z * vg_logf(ax));
+    return neg && z_odd ? -mag : mag;
+}
+
 __global__ void k_vg_unary(int op, const float* x, float* y, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -30,11 +78,11 @@ __global__ void k_vg_unary(int op, const float* x, float* y, int64_t n) {
         case U_RELU: r = tk_fmaxf(v, 0.0f); break;
         case U_SIGMOID: r = tk_sigmoidf(v); break;
         case U_TANH: r = tk_tanhf(v); break;
-        case U_SQRT: r = tk_sqrtf(v); break;
+        case U_SQRT: r = vg_sqrtf(v); break;
         case U_ABS: r = tk_fabsf(v); break;
         case U_NEG: r = -v; break;
-        case U_EXP: r = tk_expf(v); break;
-        default: r = tk_logf(v); break;
+        case U_EXP: r = vg_expf(v); break;
+        default: r = vg_logf(v); break;
     }
     y[i] = r;
 }
@@ -59,9 +107,7 @@ __global__ void k_vg_binary(int op, const float* a, const float* b, float* y, Vg
         case B_SUB: v = x - z; break;
         case B_MUL: v = x * z; break;
         case B_DIV: v = tk_divf(x, z); break;
-        default: /* Pow: the exponents these graphs use (magnitude: 2; root: 0.5) */
-            v = z == 2.0f ? x * x : z == 0.5f ? tk_sqrtf(x) : z == 1.0f ? x : tk_expf(z * tk_logf(x));
-            break;
+        default: v = vg_powf(x, z); break;
     }
     y[i] = v;
 }
@@ -272,7 +318,7 @@ __global__ void k_oe_resize(const float* x, float* y, int64_t NC, int H, int W, 
 }
 
 __global__ void k_oe_pool(const float* x, float* y, int64_t NC, int H, int W, int kh, int kw, int sh, int sw, int pt, int pl, int Ho, int Wo, int is_max,
-                          int include_pad) {
+                          int include_pad, int Hp, int Wp) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= NC * Ho * Wo) return;
     const int wo = (int)(i % Wo), ho = (int)((i / Wo) % Ho);
@@ -288,7 +334,7 @@ __global__ void k_oe_pool(const float* x, float* y, int64_t NC, int H, int W, in
                 const float v = xp[(int64_t)h * W + w];
                 acc = is_max ? tk_fmaxf(acc, v) : acc + v;
             }
-            if (in || include_pad) ++cnt;
+            if (in || (include_pad && h < Hp && w < Wp)) ++cnt; /* pad cells count, cells past the padded extent [.., H + pad_end) (ceil_mode) never do */
         }
     }
     y[i] = is_max ? acc : tk_divf(acc, (float)(cnt > 0 ? cnt : 1));
@@ -731,7 +777,7 @@ bool TkOnnxExec::exec(const TkOnnxNode& nd, std::map<std::string, Val>& v) {
             std::vector<int64_t> os(r);
             for (size_t i = 0; i < r; ++i) {
                 const size_t d = 4 - r + i;
-                if (pads[i] < 0 || pads[r + i] < 0 || (mode == "reflect" && (pads[i] >= xc.shape[i] || pads[r + i] >= xc.shape[i]))) { error = "bad pad amounts"; return false; }
+                if (pads[i] < 0 || pads[r + i] < 0 || (mode == "reflect" && (pads[i] >= xc.shape[i] || pads[r + i] >= xc.shape[i]))) { error = "Pad: 'pads' must be non-negative, and smaller than the dimension in reflect mode"; return false; }
                 pp.in[d] = xc.shape[i];
                 pp.before[d] = pads[i];
                 pp.out[d] = os[i] = xc.shape[i] + pads[i] + pads[r + i];
@@ -742,7 +788,7 @@ bool TkOnnxExec::exec(const TkOnnxNode& nd, std::map<std::string, Val>& v) {
             return true;
         }
         const int64_t L = xc.shape[r - 1], pb = pads[r - 1], pe = pads[2 * r - 1], Lo = L + pb + pe;
-        if (pb < 0 || pe < 0 || (mode == "reflect" && (pb >= L || pe >= L))) { error = "bad pad amounts"; return false; }
+        if (pb < 0 || pe < 0 || (mode == "reflect" && (pb >= L || pe >= L))) { error = "Pad: 'pads' must be non-negative, and smaller than the dimension in reflect mode"; return false; }
         std::vector<int64_t> os = xc.shape;
         os[r - 1] = Lo;
         Val* y = out_f(0, os);
@@ -763,9 +809,14 @@ bool TkOnnxExec::exec(const TkOnnxNode& nd, std::map<std::string, Val>& v) {
         const int64_t L = xc.shape[2];
         if (wc.shape[1] != C) { error = "channel counts differ"; return false; }
         int stride = 1, dil = 1, pb = 0, pe = 0;
-        if (const auto* s = nd.aints("strides")) if (!s->empty()) stride = (int)(*s)[0];
-        if (const auto* d = nd.aints("dilations")) if (!d->empty()) dil = (int)(*d)[0];
-        if (const auto* p = nd.aints("pads")) if (p->size() == 2) { pb = (int)(*p)[0]; pe = (int)(*p)[1]; }
+        for (const char* k : {"strides", "dilations", "pads"})
+            if (const auto* a = nd.aints(k)) {
+                const size_t want = k[0] == 'p' ? 2 : 1;
+                if (a->size() != want) { error = std::string("Conv: attribute '") + k + "' must hold " + std::to_string(want) + " value(s) for a 1-D input (it holds " + std::to_string(a->size()) + ")"; return false; }
+            }
+        if (const auto* s = nd.aints("strides")) stride = (int)(*s)[0];
+        if (const auto* d = nd.aints("dilations")) dil = (int)(*d)[0];
+        if (const auto* p = nd.aints("pads")) { pb = (int)(*p)[0]; pe = (int)(*p)[1]; }
         const std::string ap = nd.as("auto_pad", "NOTSET");
         if (ap != "NOTSET" && ap != "VALID") { error = "auto_pad '" + ap + "' is not supported"; return false; }
         const int64_t Lo = (L + pb + pe - (int64_t)dil * (K - 1) - 1) / stride + 1;
@@ -782,11 +833,15 @@ bool TkOnnxExec::exec(const TkOnnxNode& nd, std::map<std::string, Val>& v) {
         if (!x) return false;
         const Val xc = *x;
         std::vector<int64_t> axes;
-        if (!ints_arg("axes", 1, &axes)) for (size_t i = 0; i < xc.shape.size(); ++i) axes.push_back((int64_t)i);
+        (void)ints_arg("axes", 1, &axes);
+        if (axes.empty()) { /* no axes, or an empty axes input: every axis — or the identity under noop_with_empty_axes */
+            if (nd.ai("noop_with_empty_axes", 0)) { v[nd.out[0]] = xc; return true; }
+            for (size_t i = 0; i < xc.shape.size(); ++i) axes.push_back((int64_t)i);
+        }
         for (auto& a : axes) if (a < 0) a += (int64_t)xc.shape.size();
         std::sort(axes.begin(), axes.end());
         for (size_t i = 1; i < axes.size(); ++i) if (axes[i] != axes[i - 1] + 1) { error = "reduced axes must be adjacent"; return false; }
-        if (axes.empty() || axes.back() >= (int64_t)xc.shape.size()) { error = "bad axes"; return false; }
+        if (axes.empty() || axes.front() < 0 || axes.back() >= (int64_t)xc.shape.size()) { error = "ReduceMean: 'axes' outside the rank of the input"; return false; }
         int64_t outer = 1, mid = 1, inner = 1;
         std::vector<int64_t> os;
         const bool keep = nd.ai("keepdims", 1) != 0;
@@ -859,9 +914,21 @@ bool TkOnnxExec::exec_image_op(const TkOnnxNode& nd, std::map<std::string, Val>&
         v[nd.out[i]] = o;
         return &v[nd.out[i]];
     };
+    /* a per-axis attribute of a 2-D op: absent = the default; any other length than one value per spatial axis is refused, never ignored */
     auto pair_attr = [&](const char* k, int dflt, int* a, int* b) {
         *a = *b = dflt;
-        if (const auto* p = nd.aints(k)) if (p->size() == 2) { *a = (int)(*p)[0]; *b = (int)(*p)[1]; }
+        const auto* p = nd.aints(k);
+        if (!p) return true;
+        if (p->size() != 2) { error = nd.op + ": attribute '" + k + "' must hold 2 values for a 2-D input (it holds " + std::to_string(p->size()) + ")"; return false; }
+        *a = (int)(*p)[0]; *b = (int)(*p)[1];
+        return true;
+    };
+    auto pads_attr = [&](int* t, int* l, int* b, int* r) {
+        const auto* p = nd.aints("pads");
+        if (!p) return true;
+        if (p->size() != 4) { error = nd.op + ": attribute 'pads' must hold 4 values for a 2-D input (it holds " + std::to_string(p->size()) + ")"; return false; }
+        *t = (int)(*p)[0]; *l = (int)(*p)[1]; *b = (int)(*p)[2]; *r = (int)(*p)[3];
+        return true;
     };
     const std::string& op = nd.op;
     *handled = true;
@@ -906,10 +973,9 @@ bool TkOnnxExec::exec_image_op(const TkOnnxNode& nd, std::map<std::string, Val>&
         p.C = (int)xc.shape[1]; p.H = (int)xc.shape[2]; p.W = (int)xc.shape[3];
         p.M = (int)wc.shape[0]; p.kh = (int)wc.shape[2]; p.kw = (int)wc.shape[3];
         if (p.groups < 1 || p.C % p.groups || p.M % p.groups || wc.shape[1] != p.C / p.groups) { error = "channel counts and group do not fit"; return false; }
-        pair_attr("strides", 1, &p.sh, &p.sw);
-        pair_attr("dilations", 1, &p.dh, &p.dw);
         int pb = 0, pr = 0;
-        if (const auto* pd = nd.aints("pads")) if (pd->size() == 4) { p.pt = (int)(*pd)[0]; p.pl = (int)(*pd)[1]; pb = (int)(*pd)[2]; pr = (int)(*pd)[3]; }
+        if (!pair_attr("strides", 1, &p.sh, &p.sw) || !pair_attr("dilations", 1, &p.dh, &p.dw) || !pads_attr(&p.pt, &p.pl, &pb, &pr)) return false;
+        if (const auto* ks = nd.aints("kernel_shape")) if (ks->size() != 2 || (*ks)[0] != p.kh || (*ks)[1] != p.kw) { error = "Conv: attribute 'kernel_shape' differs from the weights' shape"; return false; }
         const std::string ap = nd.as("auto_pad", "NOTSET");
         if (ap == "SAME_UPPER" || ap == "SAME_LOWER") {
             const int oh = (p.H + p.sh - 1) / p.sh, ow = (p.W + p.sw - 1) / p.sw;
@@ -1012,8 +1078,7 @@ bool TkOnnxExec::exec_image_op(const TkOnnxNode& nd, std::map<std::string, Val>&
             const auto* ks = nd.aints("kernel_shape");
             if (!ks || ks->size() != 2) { error = "needs a 2-D kernel_shape"; return false; }
             kh = (int)(*ks)[0]; kw = (int)(*ks)[1];
-            pair_attr("strides", 1, &sh, &sw);
-            if (const auto* pd = nd.aints("pads")) if (pd->size() == 4) { pt = (int)(*pd)[0]; pl = (int)(*pd)[1]; pb = (int)(*pd)[2]; pr = (int)(*pd)[3]; }
+            if (!pair_attr("strides", 1, &sh, &sw) || !pads_attr(&pt, &pl, &pb, &pr)) return false;
             if (nd.as("auto_pad", "NOTSET") != "NOTSET") { error = "auto_pad is not supported"; return false; }
             if (const auto* dl = nd.aints("dilations")) for (int64_t d : *dl) if (d != 1) { error = "dilated pooling is not supported"; return false; }
         }
@@ -1033,7 +1098,7 @@ bool TkOnnxExec::exec_image_op(const TkOnnxNode& nd, std::map<std::string, Val>&
             return true;
         }
         hipLaunchKernelGGL(k_oe_pool, grid_for(y->count()), dim3(128), 0, stream_, xc.d, y->d, xc.shape[0] * xc.shape[1], H, W, kh, kw, sh, sw, pt, pl, Ho, Wo,
-                           op == "MaxPool" ? 1 : 0, (int)nd.ai("count_include_pad", 0));
+                           op == "MaxPool" ? 1 : 0, (int)nd.ai("count_include_pad", 0), H + pb, W + pr);
         return true;
     }
     if (op == "BatchNormalization") {
@@ -1059,13 +1124,19 @@ bool TkOnnxExec::exec_image_op(const TkOnnxNode& nd, std::map<std::string, Val>&
         const Val ac = *a, bc = *b;
         const bool gemm = op == "Gemm";
         const bool tb = gemm && nd.ai("transB", 0) != 0;
-        if (gemm && (nd.ai("transA", 0) != 0 || nd.af("alpha", 1.0f) != 1.0f || nd.af("beta", 1.0f) != 1.0f)) { error = "only alpha = beta = 1, transA = 0"; return false; }
+        if (gemm && (nd.ai("transA", 0) != 0 || nd.af("alpha", 1.0f) != 1.0f || nd.af("beta", 1.0f) != 1.0f)) { error = "Gemm: only alpha = 1, beta = 1 and transA = 0 are supported"; return false; }
         if (ac.shape.size() < 2 || bc.shape.size() != 2 || (gemm && ac.shape.size() != 2)) { error = "expects A [..., M, K] and a 2-D B"; return false; }
         const int K = (int)ac.shape.back(), N = (int)(tb ? bc.shape[0] : bc.shape[1]);
         if ((tb ? bc.shape[1] : bc.shape[0]) != K) { error = "inner dimensions differ"; return false; }
         const int64_t M = ac.count() / K;
         const float* bias = nullptr;
-        if (gemm) if (Val* c = in(2)) { if (c->is_int || c->count() != N) { error = "C must hold N values"; return false; } bias = c->d; }
+        if (gemm) if (Val* c = in(2)) {
+            /* C is added as one row bias: [N] or [1, N] (leading 1s).  [M, 1] holds N values too when M == N, but broadcasts down the columns */
+            size_t lead = 0;
+            while (lead + 1 < c->shape.size() && c->shape[lead] == 1) ++lead;
+            if (c->is_int || c->shape.size() - lead != 1 || c->shape[lead] != N) { error = "Gemm: input C must be a row bias of shape [N] or [1, N]; other broadcasts of C are not supported"; return false; }
+            bias = c->d;
+        }
         std::vector<int64_t> os = ac.shape;
         os.back() = N;
         Val* y = out_f(0, os);
@@ -1082,9 +1153,22 @@ bool TkOnnxExec::exec_image_op(const TkOnnxNode& nd, std::map<std::string, Val>&
         if (!x) return false;
         const Val xc = *x;
         const int64_t r = (int64_t)xc.shape.size();
-        int64_t ax = nd.ai("axis", -1);
+        /* opset 13 on: one axis, default -1.  Before: the input is coerced to 2-D [prod(shape[:axis]), prod(shape[axis:])] (default axis 1)
+         * and every row of that matrix is normalised */
+        const bool coerced = g_.opset > 0 && g_.opset < 13;
+        int64_t ax = nd.ai("axis", coerced ? 1 : -1);
         if (ax < 0) ax += r;
         if (r < 1 || ax < 0 || ax >= r) { error = "Softmax axis outside the rank of its input"; return false; }
+        if (coerced) {
+            int64_t cols = 1;
+            for (int64_t i = ax; i < r; ++i) cols *= xc.shape[(size_t)i];
+            Val* y = out_f(0, xc.shape);
+            if (!y) return false;
+            if (xc.count() == 0) return true;
+            hipLaunchKernelGGL(k_oe_copy, grid_for(xc.count()), dim3(128), 0, stream_, xc.d, y->d, xc.count());
+            tk_launch_softmax_rows(y->d, (int)(xc.count() / cols), (int)cols, (int)cols, stream_);
+            return true;
+        }
         if (ax != r - 1) { /* an inner axis (the DFL of a YOLO head: [1, 16, 4, anchors] over axis 1): one thread per (outer, inner) pair walks the axis in index order */
             Val* y = out_f(0, xc.shape);
             if (!y) return false;

@@ -647,14 +647,19 @@ bool TkOnnxExec::exec_seq_op(const TkOnnxNode& nd, std::map<std::string, Val>& v
         p.Co = (int)wc.shape[1]; p.kh = (int)wc.shape[2]; p.kw = (int)wc.shape[3];
         if (wc.shape[0] != p.Ci) { error = "weight channels differ from the input's"; return false; }
         p.sh = p.sw = 1;
-        if (const auto* s = nd.aints("strides")) if (s->size() == 2) { p.sh = (int)(*s)[0]; p.sw = (int)(*s)[1]; }
+        for (const char* k : {"strides", "pads", "output_padding", "output_shape", "kernel_shape"}) /* one value per spatial axis (pads: two), or absent: never ignored */
+            if (const auto* a = nd.aints(k)) {
+                const size_t want = k[0] == 'p' ? 4 : 2;
+                if (a->size() != want) { error = std::string("ConvTranspose: attribute '") + k + "' must hold " + std::to_string(want) + " values for a 2-D input (it holds " + std::to_string(a->size()) + ")"; return false; }
+            }
+        if (const auto* s = nd.aints("strides")) { p.sh = (int)(*s)[0]; p.sw = (int)(*s)[1]; }
         int pb = 0, pr = 0, oph = 0, opw = 0;
-        if (const auto* pd = nd.aints("pads")) if (pd->size() == 4) { p.pt = (int)(*pd)[0]; p.pl = (int)(*pd)[1]; pb = (int)(*pd)[2]; pr = (int)(*pd)[3]; }
-        if (const auto* op2 = nd.aints("output_padding")) if (op2->size() == 2) { oph = (int)(*op2)[0]; opw = (int)(*op2)[1]; }
+        if (const auto* pd = nd.aints("pads")) { p.pt = (int)(*pd)[0]; p.pl = (int)(*pd)[1]; pb = (int)(*pd)[2]; pr = (int)(*pd)[3]; }
+        if (const auto* op2 = nd.aints("output_padding")) { oph = (int)(*op2)[0]; opw = (int)(*op2)[1]; }
         if (p.sh < 1 || p.sw < 1 || p.kh < 1 || p.kw < 1 || p.pt < 0 || p.pl < 0 || pb < 0 || pr < 0) { error = "bad strides / pads"; return false; }
         p.Ho = (p.H - 1) * p.sh + p.kh - p.pt - pb + oph;
         p.Wo = (p.W - 1) * p.sw + p.kw - p.pl - pr + opw;
-        if (const auto* osz = nd.aints("output_shape")) if (osz->size() == 2 && ((int)(*osz)[0] != p.Ho || (int)(*osz)[1] != p.Wo)) { error = "output_shape differs from what strides and pads give"; return false; }
+        if (const auto* osz = nd.aints("output_shape")) if ((int)(*osz)[0] != p.Ho || (int)(*osz)[1] != p.Wo) { error = "ConvTranspose: attribute 'output_shape' differs from what strides, pads and output_padding give"; return false; }
         if (p.Ho < 1 || p.Wo < 1) { error = "empty output"; return false; }
         const float* bias = nullptr;
         if (Val* b = in(2)) { if (b->is_int || b->count() != p.Co) { error = "B must hold one value per output channel"; return false; } bias = b->d; }

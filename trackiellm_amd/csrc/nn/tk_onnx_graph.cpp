@@ -204,7 +204,7 @@ bool parse_graph(Span g, TkOnnxGraph* out, int depth, std::string* err) {
 
 bool TkOnnxGraph::load(const char* path) {
     try {
-        nodes.clear(); init.clear(); inputs.clear(); outputs.clear();
+        nodes.clear(); init.clear(); inputs.clear(); outputs.clear(); opset = 0;
         FILE* f = fopen(path, "rb");
         if (!f) { error = std::string("cannot open ") + path; return false; }
         fseek(f, 0, SEEK_END);
@@ -222,6 +222,18 @@ bool TkOnnxGraph::load(const char* path) {
         while (m.p < m.e) {
             if (!field(m, &num, &wt, &sub, &v)) { error = "corrupt ModelProto"; return false; }
             if (num == 7 && wt == 2) graph = sub;
+            else if (num == 8 && wt == 2) { /* opset_import: the default domain's version decides op definitions that changed (Softmax) */
+                Span os = sub, f2;
+                uint32_t fn, fw;
+                uint64_t fv, ver = 0;
+                std::string domain;
+                while (os.p < os.e) {
+                    if (!field(os, &fn, &fw, &f2, &fv)) { error = "corrupt OperatorSetIdProto"; return false; }
+                    if (fn == 1 && fw == 2) domain = str(f2);
+                    else if (fn == 2 && fw == 0) ver = fv;
+                }
+                if (domain.empty() || domain == "ai.onnx") opset = (int64_t)ver;
+            }
         }
         if (!graph.p) { error = "no graph in the ONNX file"; return false; }
         if (!parse_graph(graph, this, 0, &error)) return false;

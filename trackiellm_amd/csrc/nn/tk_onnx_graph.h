@@ -1,7 +1,7 @@
 /*
  * tk_onnx_graph.h — an ONNX file as a graph: nodes with attributes, initialisers, declared inputs / outputs.  Wire-format reader only
  * (onnx.proto3 field numbers), no ONNX Runtime:
- *   ModelProto.graph = 7
+ *   ModelProto.graph = 7, .opset_import = 8 -> OperatorSetIdProto {domain = 1, version = 2}
  *   GraphProto.node = 1, .initializer = 5, .input = 11, .output = 12
  *   NodeProto.input = 1, .output = 2, .name = 3, .op_type = 4, .attribute = 5
  *   AttributeProto.name = 1, .f = 2, .i = 3, .s = 4, .t = 5, .g = 6 (a sub-graph: the branches of If), .floats = 7, .ints = 8, .type = 20
@@ -64,6 +64,7 @@ struct TkOnnxGraph {
     std::vector<TkOnnxNode> nodes; /* file order = a valid execution order (ONNX requires topological order) */
     std::map<std::string, TkOnnxTensor> init;
     std::vector<TkOnnxValueInfo> inputs, outputs; /* inputs exclude initialisers */
+    int64_t opset = 0; /* version of the default operator set ("" / "ai.onnx") the file imports; 0 when it names none */
     std::string error;
     bool load(const char* path);
     /* every node of the graph and of its sub-graphs, outer ones first (op checks, Constant collection) */

@@ -351,3 +351,39 @@ def fusion_raw_distance(box, depth, frame_w, frame_h):
     lib().tk_mi355x_fusion_raw_distance.restype = C.c_float
     r = Rect(*[int(t) for t in box])
     return np.float32(lib().tk_mi355x_fusion_raw_distance(C.byref(r), C.byref(dm), C.c_uint32(frame_w), C.c_uint32(frame_h)))
+
+
+def onnx_run(path, feeds, outputs, device=0):
+    """Test hook (tk_mi355x_onnx_run): one run of the ONNX file at `path` on the node-by-node graph executor.  feeds: name -> float32
+    array, bound with its shape; outputs: names of float values of the graph.  Returns name -> float32 array with the shape the executor
+    produced.  A refusal by the executor raises TkError with its text."""
+    L = lib()
+    names = list(feeds)
+    arrs = [np.require(feeds[k], np.float32, "C") for k in names]  # keeps rank 0, which ascontiguousarray would not
+    n = len(names)
+    c_names = (C.c_char_p * max(n, 1))(*[k.encode() for k in names])
+    c_data = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+    c_ranks = (C.c_int32 * max(n, 1))(*[a.ndim for a in arrs])
+    dims = [(C.c_int64 * max(a.ndim, 1))(*a.shape) for a in arrs]
+    c_dims = (C.c_void_p * max(n, 1))(*[C.addressof(d) for d in dims])
+    outputs = list(outputs)
+    c_outs = (C.c_char_p * len(outputs))(*[k.encode() for k in outputs])
+    res = C.c_void_p()
+    check(L.tk_mi355x_onnx_run(device, str(path).encode(), n, c_names, c_data, c_ranks, c_dims, len(outputs), c_outs, C.byref(res)))
+    L.tk_mi355x_onnx_result_rank.argtypes = [C.c_void_p, C.c_int32]
+    L.tk_mi355x_onnx_result_dims.argtypes = [C.c_void_p, C.c_int32]
+    L.tk_mi355x_onnx_result_dims.restype = C.POINTER(C.c_int64)
+    L.tk_mi355x_onnx_result_data.argtypes = [C.c_void_p, C.c_int32]
+    L.tk_mi355x_onnx_result_data.restype = C.POINTER(C.c_float)
+    try:
+        got = {}
+        for i, k in enumerate(outputs):
+            r = L.tk_mi355x_onnx_result_rank(res, i)
+            d = L.tk_mi355x_onnx_result_dims(res, i)
+            shape = tuple(int(d[j]) for j in range(r))
+            cnt = int(np.prod(shape, dtype=np.int64))
+            p = L.tk_mi355x_onnx_result_data(res, i)
+            got[k] = np.ctypeslib.as_array(p, shape=(cnt,)).copy().reshape(shape) if cnt else np.zeros(shape, np.float32)
+        return got
+    finally:
+        L.tk_mi355x_onnx_result_free(C.byref(res))
