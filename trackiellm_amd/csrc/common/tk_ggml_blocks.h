@@ -24,6 +24,10 @@
  *         (weight 128 n + 32 j + l = (qs[32 n + l] >> 2 j) & 3), f16 d, f16
  *         dmin.   w = d*sc[g]*q - dmin*m[g], q in 0..3
  *   Q8_0: 32 weights / 34 B: f16 d, 32 int8 quants.   w = d*q (exact in fp32), every int8 value legal, -128 included
+ *   Q4_0: 32 weights / 18 B: f16 d, 16 B of nibbles (weight j = qs[j] & 15, weight j + 16 = qs[j] >> 4, j = 0..15).
+ *         w = d*(q-8), q in 0..15 (exact in fp32): the Q8_0 block with the same d and q8 = q - 8
+ *   Q5_0: 32 weights / 22 B: f16 d, 4 B of high bits (one little-endian u32: bit i = bit 4 of weight i), 16 B of nibbles laid out
+ *         as Q4_0's.   w = d*(q-16), q in 0..31 (exact in fp32): the Q8_0 block with the same d and q8 = q - 16
  * Host + device code (the quantisers run inside the synthetic-weight kernel
  * and inside the oracle; they are bit-identical by construction).
  */
@@ -40,6 +44,8 @@
 enum tk_ggml_type {
     TK_TYPE_F32 = 0,
     TK_TYPE_F16 = 1,
+    TK_TYPE_Q4_0 = 2,
+    TK_TYPE_Q5_0 = 6,
     TK_TYPE_Q8_0 = 8,
     TK_TYPE_Q2_K = 10,
     TK_TYPE_Q3_K = 11,
@@ -90,6 +96,18 @@ typedef struct {
 } tk_block_q8_0; /* 34 B, 32 weights */
 #define TK_Q8_0_PER_RUN (TK_QK_K / 32) /* Q8_0 blocks of one 256-k run = one W4A8 tile column */
 
+typedef struct {
+    uint16_t d;
+    uint8_t qs[16];
+} tk_block_q4_0; /* 18 B, 32 weights */
+
+typedef struct {
+    uint16_t d;
+    uint8_t qh[4]; /* one little-endian u32 */
+    uint8_t qs[16];
+} tk_block_q5_0; /* 22 B, 32 weights */
+#define TK_Q32_PER_RUN (TK_QK_K / 32) /* 32-weight blocks (Q4_0, Q5_0, Q8_0) of one 256-k run */
+
 /* The tensor types, described once: what the loaders, the launchers and the W4A8 kernels ask about a type is a column of this table, and
  * a new type is one more row ("Adding a tensor type") */
 struct tk_type_desc {
@@ -99,13 +117,15 @@ struct tk_type_desc {
     int mask, kernel_index;        /* its bit in the kernels' TYPES argument; its column in k_gemv_fns / k_gemm_fns / k_gemm32_fns */
     bool shares_launch;            /* may ride in one launch beside another such type (the Q4_K | Q6_K kernels); tk_launch_gemv splits any other mix */
     bool token_embd, lora_merge;   /* k_embed decodes it; k_lora_merge re-quantises it */
-    bool host_quantize;            /* tk_mi355x_quantize_blocks takes it (a pinned set: Q2_K has an entry point of its own) */
+    bool host_quantize;            /* tk_mi355x_quantize_blocks takes it (a pinned set: Q2_K, Q4_0 and Q5_0 have entry points of their own) */
 };
 TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
     switch (type) {
         /*                         name    elems bytes tile               mask idx shares embd   lora   host_q */
         case TK_TYPE_F32:  return {"F32",  1,    4,    0,                 0,   -1, false, false, false, false};
         case TK_TYPE_F16:  return {"F16",  1,    2,    0,                 0,   -1, false, true,  true,  false};
+        case TK_TYPE_Q4_0: return {"Q4_0", 32,   18,   TK_Q4_0_TILE_BYTES, 64, 7,  false, true,  false, false};
+        case TK_TYPE_Q5_0: return {"Q5_0", 32,   22,   TK_Q5_0_TILE_BYTES, 128, 8, false, true,  false, false};
         case TK_TYPE_Q8_0: return {"Q8_0", 32,   34,   TK_Q8_0_TILE_BYTES, 32, 6,  false, true,  false, true};
         case TK_TYPE_Q2_K: return {"Q2_K", 256,  84,   TK_Q2K_TILE_BYTES, 16,  5,  false, true,  false, false};
         case TK_TYPE_Q3_K: return {"Q3_K", 256,  110,  TK_Q3K_TILE_BYTES, 8,   4,  false, true,  false, true};
@@ -116,10 +136,10 @@ TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
     }
 }
 /* the lists the messages print: kept beside the table, edited with it */
-#define TK_TYPE_NAMES "F32, F16, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K"
-#define TK_TYPE_NAMES_OR "F32, F16, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
-#define TK_KQUANT_NAMES_OR "Q8_0, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
-#define TK_TOKEN_EMBD_NAMES_OR "Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K or F16"
+#define TK_TYPE_NAMES "F32, F16, Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K"
+#define TK_TYPE_NAMES_OR "F32, F16, Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
+#define TK_KQUANT_NAMES_OR "Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
+#define TK_TOKEN_EMBD_NAMES_OR "Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K or F16"
 #define TK_LORA_MERGE_NAMES_OR "Q4_K, Q6_K or F16"
 
 TK_HD constexpr bool tk_type_known(int type) { return tk_type_desc_of(type).name != nullptr; }
@@ -127,18 +147,18 @@ TK_HD constexpr bool tk_type_is_kquant(int type) { return tk_type_desc_of(type).
 TK_HD constexpr size_t tk_type_block_bytes(int type) { return (size_t)tk_type_desc_of(type).block_bytes; }
 TK_HD constexpr size_t tk_type_block_elems(int type) { return (size_t)tk_type_desc_of(type).block_elems; }
 
-/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make seven values: the six tiled types alone
+/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make nine values: the eight tiled types alone
  * and the one mix of the two shares_launch types, whose kernels pick the tile type per segment at run time. */
-/* the tiled types (tile_bytes != 0), listed: their enum values are not one range (Q8_0 = 8, the k-quants 10 .. 14), and a loop over
- * [first, last] would lean on type 9 having no row */
-#define TK_TILED_TYPES 6
+/* the tiled types (tile_bytes != 0), listed: their enum values are not one range (Q4_0 = 2, Q5_0 = 6, Q8_0 = 8, the k-quants 10 .. 14), and a
+ * loop over [first, last] would lean on the types between having no row */
+#define TK_TILED_TYPES 8
 TK_HD constexpr int tk_tiled_type(int i) {
-    constexpr int types[TK_TILED_TYPES] = {TK_TYPE_Q8_0, TK_TYPE_Q2_K, TK_TYPE_Q3_K, TK_TYPE_Q4_K, TK_TYPE_Q5_K, TK_TYPE_Q6_K};
+    constexpr int types[TK_TILED_TYPES] = {TK_TYPE_Q4_0, TK_TYPE_Q5_0, TK_TYPE_Q8_0, TK_TYPE_Q2_K, TK_TYPE_Q3_K, TK_TYPE_Q4_K, TK_TYPE_Q5_K, TK_TYPE_Q6_K};
     return types[i];
 }
 #define TK_TYPES_Q4K_Q6K (tk_type_desc_of(TK_TYPE_Q4_K).mask | tk_type_desc_of(TK_TYPE_Q6_K).mask)
 #define TK_KERNEL_INDEX_Q4K_Q6K 2
-#define TK_KERNEL_VARIANTS 7
+#define TK_KERNEL_VARIANTS 9
 TK_HD constexpr bool tk_types_has(int types, int type) { return (types & tk_type_desc_of(type).mask) != 0; }
 TK_HD constexpr bool tk_types_is(int types, int type) { return types == tk_type_desc_of(type).mask; }
 /* tile bytes of a single-type launch: a compile-time pitch (tile addresses become scalar base + immediate); 0 for the mix */
@@ -152,6 +172,9 @@ TK_HD constexpr size_t tk_types_tile_bytes(int types) {
     static_assert(sizeof(block) == tk_type_desc_of(T).block_bytes, #T ": block_bytes is not the size of its block struct");         \
     static_assert(tk_type_desc_of(T).tile_bytes == TK_TILE_ROWS * (tile_per_block), #T ": tile_bytes is not 16 x the tile's bytes per block (tk_llm_layout.h)")
 TK_TYPE_ROW_CHECK(TK_TYPE_Q8_0, tk_block_q8_0, TK_Q8_0_PER_RUN * 34); /* a tile column is one 256-k run: eight blocks per row */
+TK_TYPE_ROW_CHECK(TK_TYPE_Q4_0, tk_block_q4_0, TK_Q32_PER_RUN * 18);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q5_0, tk_block_q5_0, TK_Q32_PER_RUN * 22);
+static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_Q4_0).block_elems == 0 && TK_QK_K % tk_type_desc_of(TK_TYPE_Q5_0).block_elems == 0, "Q4_0 / Q5_0: a 256-k run must be whole blocks");
 static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_Q8_0).block_elems == 0, "Q8_0: a 256-k run must be whole blocks");
 TK_TYPE_ROW_CHECK(TK_TYPE_Q2_K, tk_block_q2_K, 84);
 TK_TYPE_ROW_CHECK(TK_TYPE_Q3_K, tk_block_q3_K, 114); /* the tile holds the sixteen group scales as int8: 4 B more than the block's packed 6-bit ones */
@@ -159,8 +182,8 @@ TK_TYPE_ROW_CHECK(TK_TYPE_Q4_K, tk_block_q4_K, 144);
 TK_TYPE_ROW_CHECK(TK_TYPE_Q5_K, tk_block_q5_K, 176);
 TK_TYPE_ROW_CHECK(TK_TYPE_Q6_K, tk_block_q6_K, 210);
 #undef TK_TYPE_ROW_CHECK
-/* every tiled type is listed once and nothing else has a tile; every mask is one bit of its own, and the kernel indices of the seven
- * TYPES values are 0 .. 6, each once */
+/* every tiled type is listed once and nothing else has a tile; every mask is one bit of its own, and the kernel indices of the nine
+ * TYPES values are 0 .. 8, each once */
 TK_HD constexpr bool tk_type_table_consistent() {
     int masks = 0, indices = 1 << TK_KERNEL_INDEX_Q4K_Q6K;
     int listed = 0;
@@ -176,7 +199,7 @@ TK_HD constexpr bool tk_type_table_consistent() {
     }
     return indices == (1 << TK_KERNEL_VARIANTS) - 1;
 }
-static_assert(tk_type_table_consistent(), "tk_type_desc_of: tk_tiled_type must list the rows with a tile, masks must be distinct bits and kernel indices 0 .. 6, each once");
+static_assert(tk_type_table_consistent(), "tk_type_desc_of: tk_tiled_type must list the rows with a tile, masks must be distinct bits and kernel indices 0 .. 8, each once");
 
 /* 6-bit (scale, min) pair j of a Q4_K block */
 TK_HD void tk_q4k_get_scale_min(int j, const uint8_t* q, uint8_t* sc, uint8_t* m) {
@@ -322,6 +345,18 @@ TK_HD void tk_q2k_set_quant(tk_block_q2_K* b, int i, int q) {
 
 /* weight i (0..31) of a Q8_0 block: d * q, exact in fp32 (11 significant bits times 8) */
 TK_HD float tk_q8_0_dequant(const tk_block_q8_0* b, int i) { return tk_f16_to_f32(b->d) * (float)b->qs[i]; }
+
+/* weight i (0..31) of a Q4_0 block, q in [0,15] (the stored value, before -8): weights 0..15 are the low nibbles, 16..31 the high ones */
+TK_HD int tk_q4_0_quant(const tk_block_q4_0* b, int i) { return i < 16 ? (b->qs[i] & 15) : (b->qs[i - 16] >> 4); }
+/* d * (q - 8), exact in fp32: the Q8_0 block with the same d and q8 = q - 8 dequantises to the same bits */
+TK_HD float tk_q4_0_dequant(const tk_block_q4_0* b, int i) { return tk_f16_to_f32(b->d) * (float)(tk_q4_0_quant(b, i) - 8); }
+
+/* weight i (0..31) of a Q5_0 block, q in [0,31] (before -16): the Q4_0 nibble plus bit i of the little-endian u32 qh */
+TK_HD int tk_q5_0_quant(const tk_block_q5_0* b, int i) {
+    const int lo = i < 16 ? (b->qs[i] & 15) : (b->qs[i - 16] >> 4);
+    return lo | (((b->qh[i >> 3] >> (i & 7)) & 1) << 4);
+}
+TK_HD float tk_q5_0_dequant(const tk_block_q5_0* b, int i) { return tk_f16_to_f32(b->d) * (float)(tk_q5_0_quant(b, i) - 16); }
 
 /*
  * Deterministic min/max quantisers ("the build's own Q4_K_M recipe").
@@ -550,6 +585,50 @@ TK_HD void tk_quantize_q8_0(const float* x, tk_block_q8_0* out) {
         const float r = v - t;
         out->qs[i] = (int8_t)((int)t + (r >= 0.5f ? 1 : r <= -0.5f ? -1 : 0));
     }
+}
+
+/* Q4_0 / Q5_0: ggml's published quantize_row_q4_0_ref / quantize_row_q5_0_ref, value for value, all in binary32: max = the element of
+ * largest magnitude with its sign (the first one on ties), d = max / -8 (-16), id = d ? 1 / d : 0 from the unrounded d, d stored as f16,
+ * q = min(15 (31), (int8_t)(x * id + 8.5f (16.5f))): one multiply, one add, truncation.  x * id lies in [-8, 8] ([-16, 16]) up to
+ * rounding, so the sum is in [0.49, 16.5] ([0.49, 32.5]) and the int8 conversion never wraps */
+TK_HD void tk_quantize_q4_0(const float* x, tk_block_q4_0* out) {
+    float amax = 0.0f, max = 0.0f;
+    for (int i = 0; i < 32; ++i) {
+        const float v = x[i];
+        if (amax < tk_fabsf(v)) { amax = tk_fabsf(v); max = v; }
+    }
+    const float d = tk_divf(max, -8.0f);
+    const float id = d != 0.0f ? tk_divf(1.0f, d) : 0.0f;
+    out->d = tk_f32_to_f16(d);
+    for (int j = 0; j < 16; ++j) {
+        const float x0 = x[j] * id, x1 = x[16 + j] * id;
+        int q0 = (int)(int8_t)(int)(x0 + 8.5f), q1 = (int)(int8_t)(int)(x1 + 8.5f);
+        q0 = q0 > 15 ? 15 : q0;
+        q1 = q1 > 15 ? 15 : q1;
+        out->qs[j] = (uint8_t)((uint8_t)q0 | ((uint8_t)q1 << 4));
+    }
+}
+
+TK_HD void tk_quantize_q5_0(const float* x, tk_block_q5_0* out) {
+    float amax = 0.0f, max = 0.0f;
+    for (int i = 0; i < 32; ++i) {
+        const float v = x[i];
+        if (amax < tk_fabsf(v)) { amax = tk_fabsf(v); max = v; }
+    }
+    const float d = tk_divf(max, -16.0f);
+    const float id = d != 0.0f ? tk_divf(1.0f, d) : 0.0f;
+    out->d = tk_f32_to_f16(d);
+    uint32_t qh = 0;
+    for (int j = 0; j < 16; ++j) {
+        const float x0 = x[j] * id, x1 = x[16 + j] * id;
+        int q0 = (int)(int8_t)(int)(x0 + 16.5f), q1 = (int)(int8_t)(int)(x1 + 16.5f);
+        q0 = q0 > 31 ? 31 : q0;
+        q1 = q1 > 31 ? 31 : q1;
+        out->qs[j] = (uint8_t)((q0 & 15) | ((q1 & 15) << 4));
+        qh |= (uint32_t)((q0 & 16) >> 4) << j;
+        qh |= (uint32_t)((q1 & 16) >> 4) << (j + 16);
+    }
+    for (int k = 0; k < 4; ++k) out->qh[k] = (uint8_t)(qh >> (8 * k));
 }
 
 /* ---- seeded synthetic tensors (splitmix64, seed stated per item) ---- */

@@ -59,6 +59,18 @@ __global__ void k_synth_blocks(int type, uint64_t seed, uint64_t tid, int64_t nb
             tk_quantize_q8_0(x + 32 * j, &blk);
             ((tk_block_q8_0*)out)[TK_Q8_0_PER_RUN * b + j] = blk;
         }
+    } else if (type == TK_TYPE_Q4_0) {
+        for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
+            tk_block_q4_0 blk;
+            tk_quantize_q4_0(x + 32 * j, &blk);
+            ((tk_block_q4_0*)out)[TK_Q32_PER_RUN * b + j] = blk;
+        }
+    } else if (type == TK_TYPE_Q5_0) {
+        for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
+            tk_block_q5_0 blk;
+            tk_quantize_q5_0(x + 32 * j, &blk);
+            ((tk_block_q5_0*)out)[TK_Q32_PER_RUN * b + j] = blk;
+        }
     } else {
         tk_block_q6_K blk;
         tk_quantize_q6_K(x, &blk);
@@ -291,9 +303,68 @@ __global__ void k_repack_q8_0(const tk_block_q8_0* src, int64_t nblk, uint8_t* t
     }
 }
 
+/* Q4_0 tile (tk_llm_layout.h): the Q4_K tile's two nibble loads with the run's 32-blocks in place of sub-blocks, then the eight d per row */
+__global__ void k_repack_q4_0(const tk_block_q4_0* src, int64_t nblk, uint8_t* tiles) {
+    const int lane = threadIdx.x;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t rt = blockIdx.y, blk = blockIdx.x;
+    const tk_block_q4_0* b = src + ((rt * 16 + n) * nblk + blk) * TK_Q32_PER_RUN;
+    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q4_0_TILE_BYTES;
+    for (int i = 0; i < 2; ++i) {
+        uint32_t dw[4];
+        for (int s = 0; s < 4; ++s) {
+            const tk_block_q4_0* bj = b + 4 * i + s;
+            const int k0 = 8 * g;
+            uint32_t v = 0;
+            for (int t = 0; t < 4; ++t) v |= (uint32_t)(tk_q4_0_quant(bj, k0 + t) | (tk_q4_0_quant(bj, k0 + 4 + t) << 4)) << (8 * t);
+            dw[s] = v;
+        }
+        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+    }
+    if (g == 0) {
+        uint32_t d[4];
+        for (int k = 0; k < 4; ++k) d[k] = (uint32_t)b[2 * k].d | ((uint32_t)b[2 * k + 1].d << 16);
+        *(uint4*)(tile + 2048 + n * 16) = make_uint4(d[0], d[1], d[2], d[3]);
+    }
+}
+
+/* Q5_0 tile: the Q4_0 tile's nibble loads, the high bits where the Q5_K tile keeps them, then the eight d per row */
+__global__ void k_repack_q5_0(const tk_block_q5_0* src, int64_t nblk, uint8_t* tiles) {
+    const int lane = threadIdx.x;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t rt = blockIdx.y, blk = blockIdx.x;
+    const tk_block_q5_0* b = src + ((rt * 16 + n) * nblk + blk) * TK_Q32_PER_RUN;
+    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q5_0_TILE_BYTES;
+    uint32_t hb[2] = {0, 0};
+    for (int i = 0; i < 2; ++i) {
+        uint32_t dw[4];
+        for (int s = 0; s < 4; ++s) {
+            const tk_block_q5_0* bj = b + 4 * i + s;
+            const int k0 = 8 * g;
+            uint32_t v = 0;
+            for (int t = 0; t < 4; ++t) {
+                const int qa = tk_q5_0_quant(bj, k0 + t), qb = tk_q5_0_quant(bj, k0 + 4 + t);
+                v |= (uint32_t)((qa & 15) | ((qb & 15) << 4)) << (8 * t);
+                hb[i] |= (uint32_t)(qa >> 4) << (8 * t + s);
+                hb[i] |= (uint32_t)(qb >> 4) << (8 * t + 4 + s);
+            }
+            dw[s] = v;
+        }
+        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+    }
+    *(uint2*)(tile + 2048 + lane * 8) = make_uint2(hb[0], hb[1]);
+    if (g == 0) {
+        uint32_t d[4];
+        for (int k = 0; k < 4; ++k) d[k] = (uint32_t)b[2 * k].d | ((uint32_t)b[2 * k + 1].d << 16);
+        *(uint4*)(tile + 2560 + n * 16) = make_uint4(d[0], d[1], d[2], d[3]);
+    }
+}
+
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s) {
     dim3 grid((unsigned)(K / 256), (unsigned)(rows / 16));
     switch (type) {
+        case TK_TYPE_Q4_0: hipLaunchKernelGGL(k_repack_q4_0, grid, dim3(64), 0, s, (const tk_block_q4_0*)blocks, K / 256, tiles); break;
+        case TK_TYPE_Q5_0: hipLaunchKernelGGL(k_repack_q5_0, grid, dim3(64), 0, s, (const tk_block_q5_0*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q8_0: hipLaunchKernelGGL(k_repack_q8_0, grid, dim3(64), 0, s, (const tk_block_q8_0*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q2_K: hipLaunchKernelGGL(k_repack_q2k, grid, dim3(64), 0, s, (const tk_block_q2_K*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q3_K: hipLaunchKernelGGL(k_repack_q3k, grid, dim3(64), 0, s, (const tk_block_q3_K*)blocks, K / 256, tiles); break;
@@ -324,6 +395,12 @@ __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, f
     } else if (type == TK_TYPE_Q8_0) {
         const tk_block_q8_0* row = (const tk_block_q8_0*)embd + (int64_t)tok[r] * (D / 32);
         x[(int64_t)r * D + i] = tk_q8_0_dequant(row + i / 32, i % 32);
+    } else if (type == TK_TYPE_Q4_0) {
+        const tk_block_q4_0* row = (const tk_block_q4_0*)embd + (int64_t)tok[r] * (D / 32);
+        x[(int64_t)r * D + i] = tk_q4_0_dequant(row + i / 32, i % 32);
+    } else if (type == TK_TYPE_Q5_0) {
+        const tk_block_q5_0* row = (const tk_block_q5_0*)embd + (int64_t)tok[r] * (D / 32);
+        x[(int64_t)r * D + i] = tk_q5_0_dequant(row + i / 32, i % 32);
     } else if (type == TK_TYPE_Q6_K) {
         const tk_block_q6_K* row = (const tk_block_q6_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q6k_dequant(row + i / 256, i % 256);
@@ -524,6 +601,8 @@ struct FragQ5 { uint4 q0, q1, h; uint2 qh; };
 struct FragQ3 { uint4 q; uint2 qh, sc; uint32_t d; };
 struct FragQ2 { uint4 q; uint2 sm; uint32_t dd; };
 struct FragQ8 { uint4 q[4], d; };
+struct FragQ40 { uint4 q0, q1, d; };
+struct FragQ50 { uint4 q0, q1, d; uint2 qh; };
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef unsigned v2u32 __attribute__((ext_vector_type(2)));
@@ -581,6 +660,25 @@ __device__ __forceinline__ FragQ8 load_q8(const uint8_t* tile, int lane) {
     return f;
 }
 
+/* q0, q1: the Q4_K tile's nibble loads (dword s of load L = block 4 L + s); d: the eight f16 block scales of the lane's row */
+__device__ __forceinline__ FragQ40 load_q4_0(const uint8_t* tile, int lane) {
+    FragQ40 f;
+    f.q0 = ldg_nt(tile + lane * 16);
+    f.q1 = ldg_nt(tile + 1024 + lane * 16);
+    f.d = ldg_nt(tile + 2048 + (lane & 15) * 16);
+    return f;
+}
+
+__device__ __forceinline__ FragQ50 load_q5_0(const uint8_t* tile, int lane) {
+    FragQ50 f;
+    f.q0 = ldg_nt(tile + lane * 16);
+    f.q1 = ldg_nt(tile + 1024 + lane * 16);
+    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + lane * 8));
+    f.qh = make_uint2(qh.x, qh.y);
+    f.d = ldg_nt(tile + 2560 + (lane & 15) * 16);
+    return f;
+}
+
 __device__ __forceinline__ FragQ6 load_q6(const uint8_t* tile, int lane) {
     FragQ6 f;
     f.q0 = ldg_nt(tile + lane * 16);
@@ -607,6 +705,8 @@ TK_TILE(TileQ4, TK_TYPE_Q4_K, FragQ4, load_q4);
 TK_TILE(TileQ5, TK_TYPE_Q5_K, FragQ5, load_q5);
 TK_TILE(TileQ6, TK_TYPE_Q6_K, FragQ6, load_q6);
 TK_TILE(TileQ8, TK_TYPE_Q8_0, FragQ8, load_q8);
+TK_TILE(TileQ40, TK_TYPE_Q4_0, FragQ40, load_q4_0);
+TK_TILE(TileQ50, TK_TYPE_Q5_0, FragQ50, load_q5_0);
 #undef TK_TILE
 /* the tile pitch of a launch: a compile-time constant in single-type launches (tile addresses become scalar base + immediate); the
  * Q4_K | Q6_K kernels take it from the segment's type */
@@ -979,6 +1079,44 @@ __device__ __forceinline__ void unpack_q8(const FragQ8& f, OpsQ8& o) {
     for (int j = 0; j < 8; ++j) o.d[j] = f16bits_to_f32((dd[j >> 1] >> (16 * (j & 1))) & 0xffffu);
 }
 
+/*
+ * Q4_0 / Q5_0: w = d * (q - z), z = 8 / 16: the Q8_0 block with the same d and q8 = q - z, so the tile is unpacked into the Q8_0 operand
+ * form and runs the Q8_0 chains (mma_q8, gemm_block_q8, gemm_block32_q8) unchanged: same integer P_j, same acc = fmaf(d_j * d8, P_j, acc).
+ * Four bytes holding q become q - z in two operations and no byte carries: 0x78 + q <= 0x87 and 0x70 + q <= 0x8F, and the xor flips
+ * bit 7, which is subtracting 0x80 modulo 256.  Nothing is folded into d.
+ */
+__device__ __forceinline__ int q4_0_s8(uint32_t q) { return (int)((q + 0x78787878u) ^ 0x80808080u); }
+__device__ __forceinline__ int q5_0_s8(uint32_t q) { return (int)((q + 0x70707070u) ^ 0x80808080u); }
+__device__ __forceinline__ void q32_scales(const uint4& d, float (&out)[8]) {
+    const uint32_t dd[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[j] = f16bits_to_f32((dd[j >> 1] >> (16 * (j & 1))) & 0xffffu);
+}
+
+__device__ __forceinline__ void unpack_q32(const FragQ40& f, OpsQ8& o) {
+    const uint32_t qs[8] = {f.q0.x, f.q0.y, f.q0.z, f.q0.w, f.q1.x, f.q1.y, f.q1.z, f.q1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        o.b[j >> 1][2 * (j & 1)] = q4_0_s8(qs[j] & 0x0F0F0F0Fu);
+        o.b[j >> 1][2 * (j & 1) + 1] = q4_0_s8((qs[j] >> 4) & 0x0F0F0F0Fu);
+    }
+    q32_scales(f.d, o.d);
+}
+
+__device__ __forceinline__ void unpack_q32(const FragQ50& f, OpsQ8& o) {
+    const uint32_t qs[8] = {f.q0.x, f.q0.y, f.q0.z, f.q0.w, f.q1.x, f.q1.y, f.q1.z, f.q1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t w = j < 4 ? f.qh.x : f.qh.y;
+        o.b[j >> 1][2 * (j & 1)] = q5_0_s8(q5_lo(qs[j], w, j & 3));
+        o.b[j >> 1][2 * (j & 1) + 1] = q5_0_s8(q5_hi(qs[j], w, j & 3));
+    }
+    q32_scales(f.d, o.d);
+}
+/* the tile of a launch whose TYPES is Q4_0's or Q5_0's mask alone (any other TYPES: Q4_0's, unused) */
+template <int TYPES> struct TileQ32Of { typedef TileQ40 type; };
+template <> struct TileQ32Of<tk_type_desc_of(TK_TYPE_Q5_0).mask> { typedef TileQ50 type; };
+
 /* the 8-byte half e of a 16-byte operand register set: the A or B operand of one 32-block */
 __device__ __forceinline__ long half_of(const v4i& v, int e) { return (long)(((unsigned long)(uint32_t)v[2 * e + 1] << 32) | (uint32_t)v[2 * e]); }
 
@@ -1066,6 +1204,8 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
     constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
     constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
+    constexpr bool ONLY32 = tk_types_is(TYPES, TK_TYPE_Q4_0) || tk_types_is(TYPES, TK_TYPE_Q5_0);
+    typedef typename TileQ32Of<TYPES>::type TileQ32;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     TileQ4::Frag f4[HAS4 ? PF : 1];
     TileQ6::Frag f6[HAS6 ? PF : 1];
@@ -1073,9 +1213,14 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     TileQ3::Frag f3[ONLY3 ? PF : 1];
     TileQ2::Frag f2[ONLY2 ? PF : 1];
     TileQ8::Frag f8[ONLY8 ? PF : 1];
+    typename TileQ32::Frag f32[ONLY32 ? PF : 1];
     if constexpr (ONLY8) {
 #pragma unroll
         for (int u = 0; u < PF; ++u) f8[u] = TileQ8::load(tile + (size_t)u * tile_bytes, lane);
+    }
+    if constexpr (ONLY32) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) f32[u] = TileQ32::load(tile + (size_t)u * tile_bytes, lane);
     }
     if constexpr (ONLY3) {
 #pragma unroll
@@ -1366,6 +1511,29 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
+    if constexpr (ONLY32) { /* Q4_0 / Q5_0: the Q8_0 loop with the type's unpack in front of the Q8_0 chain */
+        const uint8_t* tp = tile + PF * tile_bytes;
+#pragma unroll 1
+        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                OpsQ8 o;
+                __builtin_amdgcn_sched_barrier(0);
+                unpack_q32(f32[u], o);
+                __builtin_amdgcn_sched_barrier(0);
+                f32[u] = TileQ32::load(tp + u * tile_bytes, lane);
+                __builtin_amdgcn_sched_barrier(0);
+                mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            OpsQ8 o;
+            __builtin_amdgcn_sched_barrier(0);
+            unpack_q32(f32[u], o);
+            mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
+        }
+    }
 
     const int n = a.col0 + row_base + rt * TK_TILE_ROWS + (lane & 15);
     const int g = lane >> 4;
@@ -1617,6 +1785,8 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
     constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
     constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
+    constexpr bool ONLY32 = tk_types_is(TYPES, TK_TYPE_Q4_0) || tk_types_is(TYPES, TK_TYPE_Q5_0);
+    typedef typename TileQ32Of<TYPES>::type TileQ32;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     const size_t tile_bytes = types_tile_bytes<TYPES>(is4);
     const size_t tile_pitch = (size_t)nblk_total * tile_bytes; /* to the same block of the next row tile */
@@ -1661,6 +1831,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     TileQ3::Frag f3[ONLY3 ? NT : 1];
     TileQ2::Frag f2[ONLY2 ? NT : 1];
     TileQ8::Frag f8[ONLY8 ? NT : 1];
+    typename TileQ32::Frag f32[ONLY32 ? NT : 1];
     if (active) {
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
@@ -1670,6 +1841,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             if constexpr (ONLY3) f3[w] = TileQ3::load(tile + w * tile_pitch, lane);
             if constexpr (ONLY2) f2[w] = TileQ2::load(tile + w * tile_pitch, lane);
             if constexpr (ONLY8) f8[w] = TileQ8::load(tile + w * tile_pitch, lane);
+            if constexpr (ONLY32) f32[w] = TileQ32::load(tile + w * tile_pitch, lane);
         }
     }
     for (int i = 0; i < CB && i < nb; ++i) stage(i, i);
@@ -1738,6 +1910,17 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int w = 0; w < NT; ++w) f8[w] = TileQ8::load(next + w * tile_pitch, lane);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NT; ++w) gemm_block_q8<MT>(o8[w], chunk, rot, lane, acc[w]);
+        }
+        if constexpr (ONLY32) {
+            OpsQ8 o8[NT];
+#pragma unroll
+            for (int w = 0; w < NT; ++w) unpack_q32(f32[w], o8[w]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NT; ++w) f32[w] = TileQ32::load(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int w = 0; w < NT; ++w) gemm_block_q8<MT>(o8[w], chunk, rot, lane, acc[w]);
@@ -1950,8 +2133,42 @@ __device__ __forceinline__ void unpack_q8_x32(const FragQ8& f0, const FragQ8& f1
 #pragma unroll
     for (int j = 0; j < 8; ++j) o.d[j] = f16bits_to_f32((dd[j >> 1] >> (16 * (j & 1))) & 0xffffu);
 }
+/* Q4_0 / Q5_0 on the 32x32x32 map: the nibble dword of block j (and Q5_0's two high-bit dwords) takes the lane swap as in unpack_q4_x32 /
+ * unpack_q5_x32; the swapped pair is k-slices 2 h and 2 h + 1 of the block, each unpacked to its lo / hi operand dwords as q - z */
+__device__ __forceinline__ void unpack_q32_x32(const FragQ40& f0, const FragQ40& f1, int lane, Ops32Q8& o) {
+    const bool up = (lane & 16) != 0;
+    const uint32_t q0[8] = {f0.q0.x, f0.q0.y, f0.q0.z, f0.q0.w, f0.q1.x, f0.q1.y, f0.q1.z, f0.q1.w};
+    const uint32_t q1[8] = {f1.q0.x, f1.q0.y, f1.q0.z, f1.q0.w, f1.q1.x, f1.q1.y, f1.q1.z, f1.q1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        uint32_t s[2];
+        pair_swap(q0[j], q1[j], &s[0], &s[1]);
+        o.b[j] = (v4i){q4_0_s8(s[0] & 0x0F0F0F0Fu), q4_0_s8((s[0] >> 4) & 0x0F0F0F0Fu), q4_0_s8(s[1] & 0x0F0F0F0Fu), q4_0_s8((s[1] >> 4) & 0x0F0F0F0Fu)};
+    }
+    q32_scales(up ? f1.d : f0.d, o.d);
+}
+__device__ __forceinline__ void unpack_q32_x32(const FragQ50& f0, const FragQ50& f1, int lane, Ops32Q8& o) {
+    const bool up = (lane & 16) != 0;
+    const uint32_t q0[8] = {f0.q0.x, f0.q0.y, f0.q0.z, f0.q0.w, f0.q1.x, f0.q1.y, f0.q1.z, f0.q1.w};
+    const uint32_t q1[8] = {f1.q0.x, f1.q0.y, f1.q0.z, f1.q0.w, f1.q1.x, f1.q1.y, f1.q1.z, f1.q1.w};
+    uint32_t H[2][2];
+    pair_swap(f0.qh.x, f1.qh.x, &H[0][0], &H[0][1]);
+    pair_swap(f0.qh.y, f1.qh.y, &H[1][0], &H[1][1]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        uint32_t s[2];
+        pair_swap(q0[j], q1[j], &s[0], &s[1]);
+        o.b[j] = (v4i){q5_0_s8(q5_lo(s[0], H[j >> 2][0], j & 3)), q5_0_s8(q5_hi(s[0], H[j >> 2][0], j & 3)),
+                       q5_0_s8(q5_lo(s[1], H[j >> 2][1], j & 3)), q5_0_s8(q5_hi(s[1], H[j >> 2][1], j & 3))};
+    }
+    q32_scales(up ? f1.d : f0.d, o.d);
+}
+/* the types that run the Q8_0 chains: one K = 32 MFMA and one scale per 32-block */
+constexpr bool tk_is_q32(int qt) { return qt == TK_TYPE_Q8_0 || qt == TK_TYPE_Q4_0 || qt == TK_TYPE_Q5_0; }
 template <int QT> struct G32Ops { typedef struct Ops32 type; };
 template <> struct G32Ops<TK_TYPE_Q8_0> { typedef Ops32Q8 type; };
+template <> struct G32Ops<TK_TYPE_Q4_0> { typedef Ops32Q8 type; };
+template <> struct G32Ops<TK_TYPE_Q5_0> { typedef Ops32Q8 type; };
 
 /* s_waitcnt vmcnt(n) alone (expcnt / lgkmcnt untouched): until all but this wave's n youngest vector-memory operations are done.  The
  * LDS-DMA pieces of a chunk are invisible to the compiler's own wait insertion, so the ring is guarded by hand. */
@@ -1995,7 +2212,7 @@ __device__ __forceinline__ v4i q8_a32(const Ptrs32& p, int t, int j) {
 
 template <int QT>
 __device__ __forceinline__ void load_atile32(ATile32& T, const Ptrs32& p, int t) {
-    if constexpr (QT == TK_TYPE_Q8_0) {
+    if constexpr (tk_is_q32(QT)) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) T.a[j] = q8_a32(p, t, j);
         return;
@@ -2108,6 +2325,20 @@ __device__ __forceinline__ typename TkTile<QT>::Frag g32_load(const uint8_t* til
         for (int i = 0; i < 4; ++i) f.q[i] = ldg_nt(tile + 1024 * i + lo);
         f.d = ldg_nt(tile + 4096 + ho);
         return f;
+    } else if constexpr (QT == TK_TYPE_Q4_0) {
+        FragQ40 f;
+        f.q0 = ldg_nt(tile + lo);
+        f.q1 = ldg_nt(tile + 1024 + lo);
+        f.d = ldg_nt(tile + 2048 + ho);
+        return f;
+    } else if constexpr (QT == TK_TYPE_Q5_0) {
+        FragQ50 f;
+        f.q0 = ldg_nt(tile + lo);
+        f.q1 = ldg_nt(tile + 1024 + lo);
+        const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + (lo >> 1)));
+        f.qh = make_uint2(qh.x, qh.y);
+        f.d = ldg_nt(tile + 2560 + ho);
+        return f;
     } else if constexpr (QT == TK_TYPE_Q2_K) {
         FragQ2 f;
         f.q = ldg_nt(tile + lo);
@@ -2151,6 +2382,7 @@ __device__ __forceinline__ typename TkTile<QT>::Frag g32_load(const uint8_t* til
 template <int QT>
 __device__ __forceinline__ void g32_unpack(const typename TkTile<QT>::Frag& f0, const typename TkTile<QT>::Frag& f1, int lane, typename G32Ops<QT>::type& o) {
     if constexpr (QT == TK_TYPE_Q8_0) unpack_q8_x32(f0, f1, lane, o);
+    else if constexpr (QT == TK_TYPE_Q4_0 || QT == TK_TYPE_Q5_0) unpack_q32_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q4_K) unpack_q4_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q3_K) unpack_q3_x32(f0, f1, lane, o);
@@ -2195,7 +2427,7 @@ __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_byte
         __builtin_amdgcn_sched_barrier(0);
         /* the last block restages itself into the slot nobody reads any more: no branch around the DMA issue */
         /* the ring's four staging parts ride on the tiles' MFMA phases: one per tile */
-        if constexpr (QT == TK_TYPE_Q8_0) gemm_block32_q8(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
+        if constexpr (tk_is_q32(QT)) gemm_block32_q8(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
         else gemm_block32<QT>(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -2312,6 +2544,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     if constexpr (ONLY3) g32_k_loop<TK_TYPE_Q3_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (ONLY2) g32_k_loop<TK_TYPE_Q2_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (ONLY8) g32_k_loop<TK_TYPE_Q8_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (tk_types_is(TYPES, TK_TYPE_Q4_0)) g32_k_loop<TK_TYPE_Q4_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (tk_types_is(TYPES, TK_TYPE_Q5_0)) g32_k_loop<TK_TYPE_Q5_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -2389,27 +2623,27 @@ typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
 /* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone.  Type index =
  * the type's kernel_index (tk_type_desc_of), TK_KERNEL_INDEX_Q4K_Q6K for the mix; the static_asserts below hold every column to it */
 static const TkGemvKernel k_gemv_fns[3][2][2][TK_KERNEL_VARIANTS] = {
-    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>, k_gemv_w4a8<1, 1, 32, 0>},
-      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>, k_gemv_w4a8<2, 1, 32, 0>}},
-     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>, k_gemv_w4a8<1, 2, 32, 0>},
-      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>, k_gemv_w4a8<2, 2, 32, 0>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>, k_gemv_w4a8<2, 1, 32, 1>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>, k_gemv_w4a8<2, 1, 32, 2>}}},
+    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>, k_gemv_w4a8<1, 1, 32, 0>, k_gemv_w4a8<1, 1, 64, 0>, k_gemv_w4a8<1, 1, 128, 0>},
+      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>, k_gemv_w4a8<2, 1, 32, 0>, k_gemv_w4a8<2, 1, 64, 0>, k_gemv_w4a8<2, 1, 128, 0>}},
+     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>, k_gemv_w4a8<1, 2, 32, 0>, k_gemv_w4a8<1, 2, 64, 0>, k_gemv_w4a8<1, 2, 128, 0>},
+      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>, k_gemv_w4a8<2, 2, 32, 0>, k_gemv_w4a8<2, 2, 64, 0>, k_gemv_w4a8<2, 2, 128, 0>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>, k_gemv_w4a8<2, 1, 32, 1>, k_gemv_w4a8<2, 1, 64, 1>, k_gemv_w4a8<2, 1, 128, 1>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>, k_gemv_w4a8<2, 1, 32, 2>, k_gemv_w4a8<2, 1, 64, 2>, k_gemv_w4a8<2, 1, 128, 2>}}},
 };
 /* [mt / 2 - 2][type index] */
 static const TkGemvKernel k_gemm_fns[5][TK_KERNEL_VARIANTS] = {
-    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>, k_gemm_w4a8<4, 32>},
-    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>, k_gemm_w4a8<6, 32>},
-    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>, k_gemm_w4a8<8, 32>},
-    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>, k_gemm_w4a8<10, 32>},
-    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>, k_gemm_w4a8<12, 32>},
+    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>, k_gemm_w4a8<4, 32>, k_gemm_w4a8<4, 64>, k_gemm_w4a8<4, 128>},
+    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>, k_gemm_w4a8<6, 32>, k_gemm_w4a8<6, 64>, k_gemm_w4a8<6, 128>},
+    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>, k_gemm_w4a8<8, 32>, k_gemm_w4a8<8, 64>, k_gemm_w4a8<8, 128>},
+    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>, k_gemm_w4a8<10, 32>, k_gemm_w4a8<10, 64>, k_gemm_w4a8<10, 128>},
+    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>, k_gemm_w4a8<12, 32>, k_gemm_w4a8<12, 64>, k_gemm_w4a8<12, 128>},
 };
 /* [type index] */
-static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>, k_gemm32_w4a8<32>};
+static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>, k_gemm32_w4a8<32>, k_gemm32_w4a8<64>, k_gemm32_w4a8<128>};
 
 /* column c of the three tables holds the kernels of TYPES = tk_column_types[c]: every type's mask at its kernel_index */
 constexpr bool tk_columns_match_the_type_table() {
-    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16, 32};
+    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16, 32, 64, 128};
     for (int i = 0; i < TK_TILED_TYPES; ++i)
         if (tk_column_types[tk_type_desc_of(tk_tiled_type(i)).kernel_index] != tk_type_desc_of(tk_tiled_type(i)).mask) return false;
     return tk_column_types[TK_KERNEL_INDEX_Q4K_Q6K] == TK_TYPES_Q4K_Q6K;

@@ -2,7 +2,7 @@
  * tk_llm_layout.h — HBM layouts of the MI355X LLM path.
  *
  * GGUF k-quant blocks are kept bit-for-bit (the same quantised values, and the file's bytes per 256 weights
- * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked; Q8_0: eight 34-byte blocks per 256 weights) but re-tiled at load time so that one wavefront's 16-byte-per-lane
+ * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked; Q8_0 / Q4_0 / Q5_0: eight 34- / 18- / 22-byte blocks per 256 weights) but re-tiled at load time so that one wavefront's 16-byte-per-lane
  * load is a contiguous 1 KiB run that already IS an MFMA operand:
  *
  *  Weight tile = 16 weight rows x 256 k (one super-block column).  Lane l = (n = l & 15, g = l >> 4)
@@ -31,6 +31,18 @@
  *                    32-block 2 i + e: the lane's eight weights of each block, already the B operand bytes (dwords 2 e, 2 e + 1 of
  *                    load i are one v_mfma_i32_16x16x32_i8 operand; the whole load is the 16x16x64 operand of the other tiles)
  *      [4096 ,4352)  16 rows x 8 f16 d, row n's eight block scales in block order: one 16-byte read per lane
+ *  Q4_0 tile (2304 B = 16 x 144 = 16 rows x eight 18-byte blocks): a 256-k run of 16 rows, the stored nibbles q (0..15, w = d (q - 8))
+ *      [0    ,2048)  the two loads of the Q4_K tile with 32-block 4 L + s in place of sub-block 4 L + s: dword s of load L, byte t =
+ *                    q[k0 + t] | q[k0 + 4 + t] << 4 (k0 = 8 g, weights counted inside the block)
+ *      [2048 ,2304)  16 rows x 8 f16 d in block order, as the Q8_0 tile's tail
+ *  Q5_0 tile (2816 B = 16 x 176 = 16 rows x eight 22-byte blocks): the stored q (0..31, w = d (q - 16))
+ *      [0    ,2048)  the low nibbles as the two loads of the Q4_0 tile
+ *      [2048 ,2560)  lane l -> 2 dwords, the high bits as the Q5_K tile arranges them: dword L covers blocks 4 L + s, the bit of the
+ *                    weight in byte y of operand dword lo / hi (k0 + y / k0 + 4 + y) of block 4 L + s at bit 8y + s / 8y + 4 + s
+ *      [2560 ,2816)  16 rows x 8 f16 d in block order
+ *  The kernels turn a masked nibble dword (plus the high bits at bit 4) into int8 q - 8 / q - 16 with one add and one xor,
+ *  (x + 0x78787878) ^ 0x80808080 / (x + 0x70707070) ^ 0x80808080: no byte carries (0x78 + 15 and 0x70 + 31 stay below 0x100), and the
+ *  result is the B operand the Q8_0 chains take.
  *  Q3_K tile (1824 B = 16 x 114): weights stored as u = q + 4 (0..7).  Operand dword o = 2 j + hh (o = 0..15) of lane l holds the four
  *  weights k0 + 4 hh + t (t = 0..3, k0 = 32 j + 8 g) of sub-block j, as in the tiles above
  *      [0    ,1024)  one load: lane l -> 4 dwords; bits 8 t + 2 (o & 3) .. + 1 of dword o >> 2 = u & 3 of weight t of operand dword o
@@ -77,6 +89,8 @@
 #define TK_Q5K_TILE_BYTES 2816
 #define TK_Q6K_TILE_BYTES 3360
 #define TK_Q8_0_TILE_BYTES 4352
+#define TK_Q4_0_TILE_BYTES 2304
+#define TK_Q5_0_TILE_BYTES 2816
 #define TK_ROW_SLOTS 16  /* rows of one MFMA M-tile */
 #define TK_MAX_TILES 16   /* M-tiles per pass: a weight tile is unpacked once and multiplied against all of them */
 #define TK_MAX_ROWS (TK_ROW_SLOTS * TK_MAX_TILES)
