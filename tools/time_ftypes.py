@@ -6,7 +6,7 @@ Per recipe: the weight bytes a decode step streams and the stand-alone gate | up
 weight bytes plus activation and slab bytes over kernel time).  Per width and recipe: the median decode-step time over the repeats (a
 32-token prompt per sequence, 4 warm-up steps, then greedy steps through the captured pass, HIP events around the loop) and its ratio to
 Q4_K_M's median; for Q4_K_M also the spread of its repeats, the yardstick for every ratio beside it.
-    python tools/time_ftypes.py [steps [repeats [recipe ...]]]      recipes: Q4_0 Q5_0 Q8_0 Q2_K Q2_K_S Q3_K_S Q3_K_M Q4_K_S Q5_K_S Q5_K_M"""
+    python tools/time_ftypes.py [steps [repeats [recipe ...]]]      recipes: IQ4_NL IQ4_XS Q4_0 Q5_0 Q8_0 Q2_K Q2_K_S Q3_K_S Q3_K_M Q4_K_S Q5_K_S Q5_K_M"""
 import ctypes as C
 import os
 import sys
@@ -16,7 +16,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import trackiellm_amd as tk  # noqa: E402
 
-FTYPES = {"Q4_0": tk.FTYPE_Q4_0, "Q5_0": tk.FTYPE_Q5_0, "Q8_0": tk.FTYPE_Q8_0, "Q2_K": tk.FTYPE_Q2_K, "Q2_K_S": tk.FTYPE_Q2_K_S, "Q3_K_S": tk.FTYPE_Q3_K_S, "Q3_K_M": tk.FTYPE_Q3_K_M, "Q4_K_S": tk.FTYPE_Q4_K_S,
+FTYPES = {"IQ4_NL": tk.FTYPE_IQ4_NL, "IQ4_XS": tk.FTYPE_IQ4_XS, "Q4_0": tk.FTYPE_Q4_0, "Q5_0": tk.FTYPE_Q5_0, "Q8_0": tk.FTYPE_Q8_0, "Q2_K": tk.FTYPE_Q2_K, "Q2_K_S": tk.FTYPE_Q2_K_S, "Q3_K_S": tk.FTYPE_Q3_K_S, "Q3_K_M": tk.FTYPE_Q3_K_M, "Q4_K_S": tk.FTYPE_Q4_K_S,
           "Q4_K_M": tk.FTYPE_Q4_K_M, "Q5_K_S": tk.FTYPE_Q5_K_S, "Q5_K_M": tk.FTYPE_Q5_K_M}
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 3

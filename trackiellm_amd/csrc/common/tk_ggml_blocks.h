@@ -28,6 +28,11 @@
  *         w = d*(q-8), q in 0..15 (exact in fp32): the Q8_0 block with the same d and q8 = q - 8
  *   Q5_0: 32 weights / 22 B: f16 d, 4 B of high bits (one little-endian u32: bit i = bit 4 of weight i), 16 B of nibbles laid out
  *         as Q4_0's.   w = d*(q-16), q in 0..31 (exact in fp32): the Q8_0 block with the same d and q8 = q - 16
+ *   IQ4_NL: 32 weights / 18 B: the Q4_0 block's bytes, the nibble an index into the 16-entry code book tk_iq4_kv.
+ *         w = d*kv[q] (exact in fp32): the Q8_0 block with the same d and q8 = kv[q]
+ *   IQ4_XS: 256 weights / 136 B: f16 d, u16 scales_h (little endian), scales_l[4], 128 B of nibbles (sub-block j of 32 weights =
+ *         qs[16 j .. 16 j + 15], ordered as an IQ4_NL block).  ls_j = ((scales_l[j / 2] >> 4 (j % 2)) & 15) | ((scales_h >> 2 j) & 3) << 4,
+ *         s_j = ls_j - 32 in -32..31, w = (d*s_j)*kv[q], both products exact in fp32 (11 bits times 6, then 17 times 7)
  * Host + device code (the quantisers run inside the synthetic-weight kernel
  * and inside the oracle; they are bit-identical by construction).
  */
@@ -52,6 +57,8 @@ enum tk_ggml_type {
     TK_TYPE_Q4_K = 12,
     TK_TYPE_Q5_K = 13,
     TK_TYPE_Q6_K = 14,
+    TK_TYPE_IQ4_NL = 20,
+    TK_TYPE_IQ4_XS = 23,
 };
 
 typedef struct {
@@ -106,7 +113,29 @@ typedef struct {
     uint8_t qh[4]; /* one little-endian u32 */
     uint8_t qs[16];
 } tk_block_q5_0; /* 22 B, 32 weights */
-#define TK_Q32_PER_RUN (TK_QK_K / 32) /* 32-weight blocks (Q4_0, Q5_0, Q8_0) of one 256-k run */
+#define TK_Q32_PER_RUN (TK_QK_K / 32) /* 32-weight blocks (Q4_0, Q5_0, Q8_0, IQ4_NL) of one 256-k run */
+
+typedef struct {
+    uint16_t d;
+    uint8_t qs[16];
+} tk_block_iq4_nl; /* 18 B, 32 weights: the Q4_0 block's layout */
+
+typedef struct {
+    uint16_t d;
+    uint16_t scales_h; /* little endian: bits 2 j, 2 j + 1 = the high two bits of sub-block j's 6-bit scale */
+    uint8_t scales_l[4];
+    uint8_t qs[128];
+} tk_block_iq4_xs; /* 136 B, 256 weights */
+
+/* the non-linear code book of IQ4_NL / IQ4_XS (ggml's published kvalues_iq4nl), indexed by the stored nibble */
+/* -127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113 as the bytes of two constants: a shift and a sign extension on
+ * host and device, no table in memory */
+TK_HD constexpr int tk_iq4_kv(int q) {
+    return (int)(int8_t)(uint8_t)((q < 8 ? 0xF6EADDCFBFAD9881ull : 0x7159453526190D01ull) >> (8 * (q & 7)));
+}
+static_assert(tk_iq4_kv(0) == -127 && tk_iq4_kv(1) == -104 && tk_iq4_kv(2) == -83 && tk_iq4_kv(3) == -65 && tk_iq4_kv(4) == -49 && tk_iq4_kv(5) == -35 &&
+              tk_iq4_kv(6) == -22 && tk_iq4_kv(7) == -10 && tk_iq4_kv(8) == 1 && tk_iq4_kv(9) == 13 && tk_iq4_kv(10) == 25 && tk_iq4_kv(11) == 38 &&
+              tk_iq4_kv(12) == 53 && tk_iq4_kv(13) == 69 && tk_iq4_kv(14) == 89 && tk_iq4_kv(15) == 113, "tk_iq4_kv: ggml's kvalues_iq4nl");
 
 /* The tensor types, described once: what the loaders, the launchers and the W4A8 kernels ask about a type is a column of this table, and
  * a new type is one more row ("Adding a tensor type") */
@@ -117,7 +146,7 @@ struct tk_type_desc {
     int mask, kernel_index;        /* its bit in the kernels' TYPES argument; its column in k_gemv_fns / k_gemm_fns / k_gemm32_fns */
     bool shares_launch;            /* may ride in one launch beside another such type (the Q4_K | Q6_K kernels); tk_launch_gemv splits any other mix */
     bool token_embd, lora_merge;   /* k_embed decodes it; k_lora_merge re-quantises it */
-    bool host_quantize;            /* tk_mi355x_quantize_blocks takes it (a pinned set: Q2_K, Q4_0 and Q5_0 have entry points of their own) */
+    bool host_quantize;            /* tk_mi355x_quantize_blocks takes it (a pinned set: Q2_K, Q4_0, Q5_0, IQ4_NL and IQ4_XS have entry points of their own) */
 };
 TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
     switch (type) {
@@ -132,14 +161,16 @@ TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
         case TK_TYPE_Q4_K: return {"Q4_K", 256,  144,  TK_Q4K_TILE_BYTES, 1,   0,  true,  true,  true,  true};
         case TK_TYPE_Q5_K: return {"Q5_K", 256,  176,  TK_Q5K_TILE_BYTES, 4,   3,  false, true,  false, true};
         case TK_TYPE_Q6_K: return {"Q6_K", 256,  210,  TK_Q6K_TILE_BYTES, 2,   1,  true,  true,  true,  true};
+        case TK_TYPE_IQ4_NL: return {"IQ4_NL", 32, 18, TK_IQ4_NL_TILE_BYTES, 256, 9, false, true, false, false};
+        case TK_TYPE_IQ4_XS: return {"IQ4_XS", 256, 136, TK_IQ4_XS_TILE_BYTES, 512, 10, false, true, false, false};
         default:           return {nullptr, 1,   4,    0,                 0,   -1, false, false, false, false};
     }
 }
 /* the lists the messages print: kept beside the table, edited with it */
-#define TK_TYPE_NAMES "F32, F16, Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K"
-#define TK_TYPE_NAMES_OR "F32, F16, Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
-#define TK_KQUANT_NAMES_OR "Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K"
-#define TK_TOKEN_EMBD_NAMES_OR "Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K or F16"
+#define TK_TYPE_NAMES "F32, F16, Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS"
+#define TK_TYPE_NAMES_OR "F32, F16, Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
+#define TK_KQUANT_NAMES_OR "Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
+#define TK_TOKEN_EMBD_NAMES_OR "Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS or F16"
 #define TK_LORA_MERGE_NAMES_OR "Q4_K, Q6_K or F16"
 
 TK_HD constexpr bool tk_type_known(int type) { return tk_type_desc_of(type).name != nullptr; }
@@ -147,18 +178,19 @@ TK_HD constexpr bool tk_type_is_kquant(int type) { return tk_type_desc_of(type).
 TK_HD constexpr size_t tk_type_block_bytes(int type) { return (size_t)tk_type_desc_of(type).block_bytes; }
 TK_HD constexpr size_t tk_type_block_elems(int type) { return (size_t)tk_type_desc_of(type).block_elems; }
 
-/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make nine values: the eight tiled types alone
+/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make eleven values: the ten tiled types alone
  * and the one mix of the two shares_launch types, whose kernels pick the tile type per segment at run time. */
-/* the tiled types (tile_bytes != 0), listed: their enum values are not one range (Q4_0 = 2, Q5_0 = 6, Q8_0 = 8, the k-quants 10 .. 14), and a
+/* the tiled types (tile_bytes != 0), listed: their enum values are not one range (Q4_0 = 2, Q5_0 = 6, Q8_0 = 8, the k-quants 10 .. 14, IQ4_NL = 20, IQ4_XS = 23), and a
  * loop over [first, last] would lean on the types between having no row */
-#define TK_TILED_TYPES 8
+#define TK_TILED_TYPES 10
 TK_HD constexpr int tk_tiled_type(int i) {
-    constexpr int types[TK_TILED_TYPES] = {TK_TYPE_Q4_0, TK_TYPE_Q5_0, TK_TYPE_Q8_0, TK_TYPE_Q2_K, TK_TYPE_Q3_K, TK_TYPE_Q4_K, TK_TYPE_Q5_K, TK_TYPE_Q6_K};
+    constexpr int types[TK_TILED_TYPES] = {TK_TYPE_Q4_0, TK_TYPE_Q5_0, TK_TYPE_Q8_0, TK_TYPE_Q2_K, TK_TYPE_Q3_K, TK_TYPE_Q4_K, TK_TYPE_Q5_K, TK_TYPE_Q6_K,
+                                             TK_TYPE_IQ4_NL, TK_TYPE_IQ4_XS};
     return types[i];
 }
 #define TK_TYPES_Q4K_Q6K (tk_type_desc_of(TK_TYPE_Q4_K).mask | tk_type_desc_of(TK_TYPE_Q6_K).mask)
 #define TK_KERNEL_INDEX_Q4K_Q6K 2
-#define TK_KERNEL_VARIANTS 9
+#define TK_KERNEL_VARIANTS 11
 TK_HD constexpr bool tk_types_has(int types, int type) { return (types & tk_type_desc_of(type).mask) != 0; }
 TK_HD constexpr bool tk_types_is(int types, int type) { return types == tk_type_desc_of(type).mask; }
 /* tile bytes of a single-type launch: a compile-time pitch (tile addresses become scalar base + immediate); 0 for the mix */
@@ -181,9 +213,13 @@ TK_TYPE_ROW_CHECK(TK_TYPE_Q3_K, tk_block_q3_K, 114); /* the tile holds the sixte
 TK_TYPE_ROW_CHECK(TK_TYPE_Q4_K, tk_block_q4_K, 144);
 TK_TYPE_ROW_CHECK(TK_TYPE_Q5_K, tk_block_q5_K, 176);
 TK_TYPE_ROW_CHECK(TK_TYPE_Q6_K, tk_block_q6_K, 210);
+TK_TYPE_ROW_CHECK(TK_TYPE_IQ4_NL, tk_block_iq4_nl, TK_Q32_PER_RUN * 18);
+TK_TYPE_ROW_CHECK(TK_TYPE_IQ4_XS, tk_block_iq4_xs, 144); /* the tile holds the eight sub-block scales as int8 in a 16-byte row tail: 8 B more than the block */
+static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_IQ4_NL).block_elems == 0, "IQ4_NL: a 256-k run must be whole blocks");
+static_assert(sizeof(tk_block_iq4_nl) == sizeof(tk_block_q4_0) && TK_IQ4_NL_TILE_BYTES == TK_Q4_0_TILE_BYTES, "IQ4_NL rides on the Q4_0 repack, fragment and load");
 #undef TK_TYPE_ROW_CHECK
-/* every tiled type is listed once and nothing else has a tile; every mask is one bit of its own, and the kernel indices of the nine
- * TYPES values are 0 .. 8, each once */
+/* every tiled type is listed once and nothing else has a tile; every mask is one bit of its own, and the kernel indices of the eleven
+ * TYPES values are 0 .. 10, each once */
 TK_HD constexpr bool tk_type_table_consistent() {
     int masks = 0, indices = 1 << TK_KERNEL_INDEX_Q4K_Q6K;
     int listed = 0;
@@ -199,7 +235,7 @@ TK_HD constexpr bool tk_type_table_consistent() {
     }
     return indices == (1 << TK_KERNEL_VARIANTS) - 1;
 }
-static_assert(tk_type_table_consistent(), "tk_type_desc_of: tk_tiled_type must list the rows with a tile, masks must be distinct bits and kernel indices 0 .. 8, each once");
+static_assert(tk_type_table_consistent(), "tk_type_desc_of: tk_tiled_type must list the rows with a tile, masks must be distinct bits and kernel indices 0 .. 10, each once");
 
 /* 6-bit (scale, min) pair j of a Q4_K block */
 TK_HD void tk_q4k_get_scale_min(int j, const uint8_t* q, uint8_t* sc, uint8_t* m) {
@@ -357,6 +393,27 @@ TK_HD int tk_q5_0_quant(const tk_block_q5_0* b, int i) {
     return lo | (((b->qh[i >> 3] >> (i & 7)) & 1) << 4);
 }
 TK_HD float tk_q5_0_dequant(const tk_block_q5_0* b, int i) { return tk_f16_to_f32(b->d) * (float)(tk_q5_0_quant(b, i) - 16); }
+
+/* stored nibble (the code-book index, 0..15) of weight i (0..31) of an IQ4_NL block or of one IQ4_XS sub-block, whose sixteen bytes qs
+ * are laid out as Q4_0's */
+TK_HD int tk_iq4_quant(const uint8_t* qs, int i) { return i < 16 ? (qs[i] & 15) : (qs[i - 16] >> 4); }
+/* d * kv[q], exact in fp32: the Q8_0 block with the same d and q8 = kv[q] dequantises to the same bits */
+TK_HD float tk_iq4nl_dequant(const tk_block_iq4_nl* b, int i) { return tk_f16_to_f32(b->d) * (float)tk_iq4_kv(tk_iq4_quant(b->qs, i)); }
+
+/* scale of sub-block j (0..7) of an IQ4_XS block: the stored 6 bits minus 32, in [-32,31] */
+TK_HD int tk_iq4xs_scale(const tk_block_iq4_xs* b, int j) {
+    return (((b->scales_l[j >> 1] >> (4 * (j & 1))) & 15) | (((b->scales_h >> (2 * j)) & 3) << 4)) - 32;
+}
+TK_HD void tk_iq4xs_set_scale(tk_block_iq4_xs* b, int j, int s) {
+    const int v = s + 32;
+    uint8_t* l = &b->scales_l[j >> 1];
+    *l = (uint8_t)((*l & ~(15 << (4 * (j & 1)))) | ((v & 15) << (4 * (j & 1))));
+    b->scales_h = (uint16_t)((b->scales_h & ~(3 << (2 * j))) | ((v >> 4) << (2 * j)));
+}
+/* weight i (0..255): (d * s_j) * kv[q], one (exact) rounding per operation */
+TK_HD float tk_iq4xs_dequant(const tk_block_iq4_xs* b, int i) {
+    return (tk_f16_to_f32(b->d) * (float)tk_iq4xs_scale(b, i >> 5)) * (float)tk_iq4_kv(tk_iq4_quant(b->qs + 16 * (i >> 5), i & 31));
+}
 
 /*
  * Deterministic min/max quantisers ("the build's own Q4_K_M recipe").
@@ -629,6 +686,71 @@ TK_HD void tk_quantize_q5_0(const float* x, tk_block_q5_0* out) {
         qh |= (uint32_t)((q1 & 16) >> 4) << (j + 16);
     }
     for (int k = 0; k < 4; ++k) out->qh[k] = (uint8_t)(qh >> (8 * k));
+}
+
+/* IQ4_NL / IQ4_XS: the build's own one-pass quantisers (IEEE operations only, so host and device make identical blocks), as Q3_K's and
+ * Q2_K's are; ggml's IQ4 quantiser is an iterative search and is not restated.  The code-book index of a scaled value v = x * id is the
+ * number of midpoints (kv[k] + kv[k + 1]) / 2 below it: the nearest code-book value, ties to the lower index */
+/* the loops of these quantisers stay rolled in device code: unrolled and inlined, the 8 x 32 x 15 compares of one IQ4_XS block took the
+ * device compiler a quarter of an hour.  The operations and their order are the same either way, so host and device blocks stay identical */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TK_ROLLED _Pragma("unroll 1")
+#else
+#define TK_ROLLED
+#endif
+TK_HD int tk_iq4_index(float v) {
+    int q = 0;
+    TK_ROLLED
+    for (int k = 0; k < 15; ++k) q += v > (float)(tk_iq4_kv(k) + tk_iq4_kv(k + 1)) * 0.5f ? 1 : 0;
+    return q;
+}
+/* the element of largest magnitude with its sign, the first one on ties */
+TK_HD float tk_iq4_signed_max(const float* x) {
+    float amax = 0.0f, max = 0.0f;
+    TK_ROLLED
+    for (int i = 0; i < 32; ++i) {
+        const float v = x[i];
+        if (amax < tk_fabsf(v)) { amax = tk_fabsf(v); max = v; }
+    }
+    return max;
+}
+TK_HD void tk_iq4_pack(const float* x, float id, uint8_t* qs) {
+    TK_ROLLED
+    for (int j = 0; j < 16; ++j) qs[j] = (uint8_t)(tk_iq4_index(x[j] * id) | (tk_iq4_index(x[16 + j] * id) << 4));
+}
+
+/* d = max / -127 (the extreme lands on kv[0] = -127), id = d ? 1 / d : 0 from the unrounded d, d stored as f16 */
+TK_HD void tk_quantize_iq4_nl(const float* x, tk_block_iq4_nl* out) {
+    const float d = tk_divf(tk_iq4_signed_max(x), -127.0f);
+    const float id = d != 0.0f ? tk_divf(1.0f, d) : 0.0f;
+    out->d = tk_f32_to_f16(d);
+    tk_iq4_pack(x, id, out->qs);
+}
+
+/* per sub-block the real scale r_j = max_j / -127; d = max |r_j| / 31 stored as f16, s_j = clamp(rint(r_j / dq), -32, 31) with dq the
+ * stored d (0 when dq == 0), and the indices against dl = dq * s_j */
+TK_HD void tk_quantize_iq4_xs(const float* x, tk_block_iq4_xs* out) {
+    float r[8];
+    float max_abs = 0.0f;
+    TK_ROLLED
+    for (int j = 0; j < 8; ++j) {
+        r[j] = tk_divf(tk_iq4_signed_max(x + 32 * j), -127.0f);
+        const float a = tk_fabsf(r[j]);
+        max_abs = a > max_abs ? a : max_abs;
+    }
+    out->d = tk_f32_to_f16(tk_divf(max_abs, 31.0f));
+    const float dq = tk_f16_to_f32(out->d);
+    out->scales_h = 0;
+    for (int k = 0; k < 4; ++k) out->scales_l[k] = 0;
+    TK_ROLLED
+    for (int j = 0; j < 8; ++j) {
+        int s = dq != 0.0f ? (int)tk_rintf(tk_divf(r[j], dq)) : 0;
+        s = s < -32 ? -32 : (s > 31 ? 31 : s);
+        tk_iq4xs_set_scale(out, j, s);
+        const float dl = dq * (float)s;
+        const float idl = dl != 0.0f ? tk_divf(1.0f, dl) : 0.0f;
+        tk_iq4_pack(x + 32 * j, idl, out->qs + 16 * j);
+    }
 }
 
 /* ---- seeded synthetic tensors (splitmix64, seed stated per item) ---- */

@@ -71,6 +71,16 @@ __global__ void k_synth_blocks(int type, uint64_t seed, uint64_t tid, int64_t nb
             tk_quantize_q5_0(x + 32 * j, &blk);
             ((tk_block_q5_0*)out)[TK_Q32_PER_RUN * b + j] = blk;
         }
+    } else if (type == TK_TYPE_IQ4_NL) {
+        for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
+            tk_block_iq4_nl blk;
+            tk_quantize_iq4_nl(x + 32 * j, &blk);
+            ((tk_block_iq4_nl*)out)[TK_Q32_PER_RUN * b + j] = blk;
+        }
+    } else if (type == TK_TYPE_IQ4_XS) {
+        tk_block_iq4_xs blk;
+        tk_quantize_iq4_xs(x, &blk);
+        ((tk_block_iq4_xs*)out)[b] = blk;
     } else {
         tk_block_q6_K blk;
         tk_quantize_q6_K(x, &blk);
@@ -360,9 +370,38 @@ __global__ void k_repack_q5_0(const tk_block_q5_0* src, int64_t nblk, uint8_t* t
     }
 }
 
+/* IQ4_XS tile (tk_llm_layout.h): the Q4_0 tile's two nibble loads with the block's sub-blocks in place of 32-blocks, then per row the
+ * eight scales s_j as int8, the f16 d and six zero bytes */
+__global__ void k_repack_iq4_xs(const tk_block_iq4_xs* src, int64_t nblk, uint8_t* tiles) {
+    const int lane = threadIdx.x;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t rt = blockIdx.y, blk = blockIdx.x;
+    const tk_block_iq4_xs* b = src + (rt * 16 + n) * nblk + blk;
+    uint8_t* tile = tiles + (rt * nblk + blk) * TK_IQ4_XS_TILE_BYTES;
+    for (int i = 0; i < 2; ++i) {
+        uint32_t dw[4];
+        for (int s = 0; s < 4; ++s) {
+            const uint8_t* qs = b->qs + 16 * (4 * i + s);
+            const int k0 = 8 * g;
+            uint32_t v = 0;
+            for (int t = 0; t < 4; ++t) v |= (uint32_t)(tk_iq4_quant(qs, k0 + t) | (tk_iq4_quant(qs, k0 + 4 + t) << 4)) << (8 * t);
+            dw[s] = v;
+        }
+        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+    }
+    if (g == 0) {
+        uint32_t sc[2] = {0, 0};
+        for (int j = 0; j < 8; ++j) sc[j >> 2] |= (uint32_t)(uint8_t)(int8_t)tk_iq4xs_scale(b, j) << (8 * (j & 3));
+        *(uint4*)(tile + 2048 + n * 16) = make_uint4(sc[0], sc[1], (uint32_t)b->d, 0u);
+    }
+}
+
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s) {
     dim3 grid((unsigned)(K / 256), (unsigned)(rows / 16));
     switch (type) {
+        /* an IQ4_NL block has the Q4_0 block's bytes and its tile is the Q4_0 tile: the same kernel */
+        case TK_TYPE_IQ4_NL: hipLaunchKernelGGL(k_repack_q4_0, grid, dim3(64), 0, s, (const tk_block_q4_0*)blocks, K / 256, tiles); break;
+        case TK_TYPE_IQ4_XS: hipLaunchKernelGGL(k_repack_iq4_xs, grid, dim3(64), 0, s, (const tk_block_iq4_xs*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q4_0: hipLaunchKernelGGL(k_repack_q4_0, grid, dim3(64), 0, s, (const tk_block_q4_0*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q5_0: hipLaunchKernelGGL(k_repack_q5_0, grid, dim3(64), 0, s, (const tk_block_q5_0*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q8_0: hipLaunchKernelGGL(k_repack_q8_0, grid, dim3(64), 0, s, (const tk_block_q8_0*)blocks, K / 256, tiles); break;
@@ -401,6 +440,12 @@ __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, f
     } else if (type == TK_TYPE_Q5_0) {
         const tk_block_q5_0* row = (const tk_block_q5_0*)embd + (int64_t)tok[r] * (D / 32);
         x[(int64_t)r * D + i] = tk_q5_0_dequant(row + i / 32, i % 32);
+    } else if (type == TK_TYPE_IQ4_NL) {
+        const tk_block_iq4_nl* row = (const tk_block_iq4_nl*)embd + (int64_t)tok[r] * (D / 32);
+        x[(int64_t)r * D + i] = tk_iq4nl_dequant(row + i / 32, i % 32);
+    } else if (type == TK_TYPE_IQ4_XS) {
+        const tk_block_iq4_xs* row = (const tk_block_iq4_xs*)embd + (int64_t)tok[r] * (D / 256);
+        x[(int64_t)r * D + i] = tk_iq4xs_dequant(row + i / 256, i % 256);
     } else if (type == TK_TYPE_Q6_K) {
         const tk_block_q6_K* row = (const tk_block_q6_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q6k_dequant(row + i / 256, i % 256);
@@ -601,7 +646,12 @@ struct FragQ5 { uint4 q0, q1, h; uint2 qh; };
 struct FragQ3 { uint4 q; uint2 qh, sc; uint32_t d; };
 struct FragQ2 { uint4 q; uint2 sm; uint32_t dd; };
 struct FragQ8 { uint4 q[4], d; };
-struct FragQ40 { uint4 q0, q1, d; };
+/* the Q4_0 tile's fragment; IQ4_NL and IQ4_XS load the same three reads, and the type id in the name picks their unpack_q32 overload.
+ * IQ4_XS: d = the row's 16-byte tile tail, s_0 .. s_7 as int8 in d.x, d.y and the f16 d in the low half of d.z */
+template <int QT> struct FragQ4x { uint4 q0, q1, d; };
+typedef FragQ4x<TK_TYPE_Q4_0> FragQ40;
+typedef FragQ4x<TK_TYPE_IQ4_NL> FragIQ4NL;
+typedef FragQ4x<TK_TYPE_IQ4_XS> FragIQ4XS;
 struct FragQ50 { uint4 q0, q1, d; uint2 qh; };
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
@@ -661,8 +711,9 @@ __device__ __forceinline__ FragQ8 load_q8(const uint8_t* tile, int lane) {
 }
 
 /* q0, q1: the Q4_K tile's nibble loads (dword s of load L = block 4 L + s); d: the eight f16 block scales of the lane's row */
-__device__ __forceinline__ FragQ40 load_q4_0(const uint8_t* tile, int lane) {
-    FragQ40 f;
+template <int QT>
+__device__ __forceinline__ FragQ4x<QT> load_q4_0(const uint8_t* tile, int lane) {
+    FragQ4x<QT> f;
     f.q0 = ldg_nt(tile + lane * 16);
     f.q1 = ldg_nt(tile + 1024 + lane * 16);
     f.d = ldg_nt(tile + 2048 + (lane & 15) * 16);
@@ -705,8 +756,10 @@ TK_TILE(TileQ4, TK_TYPE_Q4_K, FragQ4, load_q4);
 TK_TILE(TileQ5, TK_TYPE_Q5_K, FragQ5, load_q5);
 TK_TILE(TileQ6, TK_TYPE_Q6_K, FragQ6, load_q6);
 TK_TILE(TileQ8, TK_TYPE_Q8_0, FragQ8, load_q8);
-TK_TILE(TileQ40, TK_TYPE_Q4_0, FragQ40, load_q4_0);
+TK_TILE(TileQ40, TK_TYPE_Q4_0, FragQ40, load_q4_0<TK_TYPE_Q4_0>);
 TK_TILE(TileQ50, TK_TYPE_Q5_0, FragQ50, load_q5_0);
+TK_TILE(TileIQ4NL, TK_TYPE_IQ4_NL, FragIQ4NL, load_q4_0<TK_TYPE_IQ4_NL>);
+TK_TILE(TileIQ4XS, TK_TYPE_IQ4_XS, FragIQ4XS, load_q4_0<TK_TYPE_IQ4_XS>);
 #undef TK_TILE
 /* the tile pitch of a launch: a compile-time constant in single-type launches (tile addresses become scalar base + immediate); the
  * Q4_K | Q6_K kernels take it from the segment's type */
@@ -1113,9 +1166,58 @@ __device__ __forceinline__ void unpack_q32(const FragQ50& f, OpsQ8& o) {
     }
     q32_scales(f.d, o.d);
 }
-/* the tile of a launch whose TYPES is Q4_0's or Q5_0's mask alone (any other TYPES: Q4_0's, unused) */
+/*
+ * IQ4_NL / IQ4_XS: w = D * kv[q] with kv the 16-entry int8 code book and D = d (IQ4_NL) or d * (float)s_j (IQ4_XS, exact in fp32): the
+ * Q8_0 block with scale D and q8 = kv[q], so these too are unpacked into the Q8_0 operand form and run the Q8_0 chains unchanged.
+ * The look-up of the four nibbles at bits SH .. SH + 3 of the bytes of qs: the code book is four constant dwords, v_perm_b32 with the
+ * selector q & 7 reads kv[0..7] and kv[8..15] for all four bytes, and a third v_perm_b32 picks byte t of the one or the other by bit 3
+ * of nibble t (selector byte t | bit 3 << 2: 0..3 = the second operand's bytes, 4..7 = the first's).
+ */
+template <int SH>
+__device__ __forceinline__ int iq4_s8(uint32_t qs) {
+    constexpr uint32_t KV0 = 0xBFAD9881u, KV1 = 0xF6EADDCFu, KV2 = 0x26190D01u, KV3 = 0x71594535u;
+    const uint32_t sel = (qs >> SH) & 0x07070707u;
+    const uint32_t lo = __builtin_amdgcn_perm(KV1, KV0, sel), hi = __builtin_amdgcn_perm(KV3, KV2, sel);
+    return (int)__builtin_amdgcn_perm(hi, lo, ((qs >> (SH + 1)) & 0x04040404u) | 0x03020100u);
+}
+constexpr uint32_t tk_iq4_kv_dword(int i) {
+    return (uint32_t)(uint8_t)tk_iq4_kv(4 * i) | (uint32_t)(uint8_t)tk_iq4_kv(4 * i + 1) << 8 | (uint32_t)(uint8_t)tk_iq4_kv(4 * i + 2) << 16 |
+           (uint32_t)(uint8_t)tk_iq4_kv(4 * i + 3) << 24;
+}
+static_assert(tk_iq4_kv_dword(0) == 0xBFAD9881u && tk_iq4_kv_dword(1) == 0xF6EADDCFu && tk_iq4_kv_dword(2) == 0x26190D01u && tk_iq4_kv_dword(3) == 0x71594535u,
+              "iq4_s8: the four dwords are tk_iq4_kv, little endian");
+/* the eight block scales of an IQ4_XS row: d * (float)s_j, computed in fp32 */
+__device__ __forceinline__ void iq4xs_scales(const uint4& t, float (&out)[8]) {
+    const float d = f16bits_to_f32(t.z & 0xffffu);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[j] = d * (float)(int)(int8_t)((j < 4 ? t.x : t.y) >> (8 * (j & 3)));
+}
+template <int QT>
+__device__ __forceinline__ void iq4_operands(const FragQ4x<QT>& f, OpsQ8& o) {
+    const uint32_t qs[8] = {f.q0.x, f.q0.y, f.q0.z, f.q0.w, f.q1.x, f.q1.y, f.q1.z, f.q1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        o.b[j >> 1][2 * (j & 1)] = iq4_s8<0>(qs[j]);
+        o.b[j >> 1][2 * (j & 1) + 1] = iq4_s8<4>(qs[j]);
+    }
+}
+__device__ __forceinline__ void unpack_q32(const FragIQ4NL& f, OpsQ8& o) {
+    iq4_operands(f, o);
+    q32_scales(f.d, o.d);
+}
+__device__ __forceinline__ void unpack_q32(const FragIQ4XS& f, OpsQ8& o) {
+    iq4_operands(f, o);
+    iq4xs_scales(f.d, o.d);
+}
+/* the tile of a launch whose TYPES is the mask of Q4_0, Q5_0, IQ4_NL or IQ4_XS alone (any other TYPES: Q4_0's, unused) */
 template <int TYPES> struct TileQ32Of { typedef TileQ40 type; };
 template <> struct TileQ32Of<tk_type_desc_of(TK_TYPE_Q5_0).mask> { typedef TileQ50 type; };
+template <> struct TileQ32Of<tk_type_desc_of(TK_TYPE_IQ4_NL).mask> { typedef TileIQ4NL type; };
+template <> struct TileQ32Of<tk_type_desc_of(TK_TYPE_IQ4_XS).mask> { typedef TileIQ4XS type; };
+/* the launches that run the Q8_0 chains behind an unpack of their own */
+constexpr bool tk_types_only32(int types) {
+    return tk_types_is(types, TK_TYPE_Q4_0) || tk_types_is(types, TK_TYPE_Q5_0) || tk_types_is(types, TK_TYPE_IQ4_NL) || tk_types_is(types, TK_TYPE_IQ4_XS);
+}
 
 /* the 8-byte half e of a 16-byte operand register set: the A or B operand of one 32-block */
 __device__ __forceinline__ long half_of(const v4i& v, int e) { return (long)(((unsigned long)(uint32_t)v[2 * e + 1] << 32) | (uint32_t)v[2 * e]); }
@@ -1204,7 +1306,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
     constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
     constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
-    constexpr bool ONLY32 = tk_types_is(TYPES, TK_TYPE_Q4_0) || tk_types_is(TYPES, TK_TYPE_Q5_0);
+    constexpr bool ONLY32 = tk_types_only32(TYPES);
     typedef typename TileQ32Of<TYPES>::type TileQ32;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     TileQ4::Frag f4[HAS4 ? PF : 1];
@@ -1511,7 +1613,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
-    if constexpr (ONLY32) { /* Q4_0 / Q5_0: the Q8_0 loop with the type's unpack in front of the Q8_0 chain */
+    if constexpr (ONLY32) { /* Q4_0 / Q5_0 / IQ4_NL / IQ4_XS: the Q8_0 loop with the type's unpack in front of the Q8_0 chain */
         const uint8_t* tp = tile + PF * tile_bytes;
 #pragma unroll 1
         for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
@@ -1785,7 +1887,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
     constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
     constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
-    constexpr bool ONLY32 = tk_types_is(TYPES, TK_TYPE_Q4_0) || tk_types_is(TYPES, TK_TYPE_Q5_0);
+    constexpr bool ONLY32 = tk_types_only32(TYPES);
     typedef typename TileQ32Of<TYPES>::type TileQ32;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     const size_t tile_bytes = types_tile_bytes<TYPES>(is4);
@@ -2163,12 +2265,36 @@ __device__ __forceinline__ void unpack_q32_x32(const FragQ50& f0, const FragQ50&
     }
     q32_scales(up ? f1.d : f0.d, o.d);
 }
+/* IQ4_NL / IQ4_XS on the 32x32x32 map: the lane swap of the Q4_0 form, the look-up in place of its add and xor */
+template <int QT>
+__device__ __forceinline__ void iq4_operands_x32(const FragQ4x<QT>& f0, const FragQ4x<QT>& f1, Ops32Q8& o) {
+    const uint32_t q0[8] = {f0.q0.x, f0.q0.y, f0.q0.z, f0.q0.w, f0.q1.x, f0.q1.y, f0.q1.z, f0.q1.w};
+    const uint32_t q1[8] = {f1.q0.x, f1.q0.y, f1.q0.z, f1.q0.w, f1.q1.x, f1.q1.y, f1.q1.z, f1.q1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        uint32_t s[2];
+        pair_swap(q0[j], q1[j], &s[0], &s[1]);
+        o.b[j] = (v4i){iq4_s8<0>(s[0]), iq4_s8<4>(s[0]), iq4_s8<0>(s[1]), iq4_s8<4>(s[1])};
+    }
+}
+__device__ __forceinline__ void unpack_q32_x32(const FragIQ4NL& f0, const FragIQ4NL& f1, int lane, Ops32Q8& o) {
+    const bool up = (lane & 16) != 0;
+    iq4_operands_x32(f0, f1, o);
+    q32_scales(up ? f1.d : f0.d, o.d);
+}
+__device__ __forceinline__ void unpack_q32_x32(const FragIQ4XS& f0, const FragIQ4XS& f1, int lane, Ops32Q8& o) {
+    const bool up = (lane & 16) != 0;
+    iq4_operands_x32(f0, f1, o);
+    iq4xs_scales(up ? f1.d : f0.d, o.d);
+}
 /* the types that run the Q8_0 chains: one K = 32 MFMA and one scale per 32-block */
-constexpr bool tk_is_q32(int qt) { return qt == TK_TYPE_Q8_0 || qt == TK_TYPE_Q4_0 || qt == TK_TYPE_Q5_0; }
+constexpr bool tk_is_q32(int qt) { return qt == TK_TYPE_Q8_0 || qt == TK_TYPE_Q4_0 || qt == TK_TYPE_Q5_0 || qt == TK_TYPE_IQ4_NL || qt == TK_TYPE_IQ4_XS; }
 template <int QT> struct G32Ops { typedef struct Ops32 type; };
 template <> struct G32Ops<TK_TYPE_Q8_0> { typedef Ops32Q8 type; };
 template <> struct G32Ops<TK_TYPE_Q4_0> { typedef Ops32Q8 type; };
 template <> struct G32Ops<TK_TYPE_Q5_0> { typedef Ops32Q8 type; };
+template <> struct G32Ops<TK_TYPE_IQ4_NL> { typedef Ops32Q8 type; };
+template <> struct G32Ops<TK_TYPE_IQ4_XS> { typedef Ops32Q8 type; };
 
 /* s_waitcnt vmcnt(n) alone (expcnt / lgkmcnt untouched): until all but this wave's n youngest vector-memory operations are done.  The
  * LDS-DMA pieces of a chunk are invisible to the compiler's own wait insertion, so the ring is guarded by hand. */
@@ -2325,8 +2451,8 @@ __device__ __forceinline__ typename TkTile<QT>::Frag g32_load(const uint8_t* til
         for (int i = 0; i < 4; ++i) f.q[i] = ldg_nt(tile + 1024 * i + lo);
         f.d = ldg_nt(tile + 4096 + ho);
         return f;
-    } else if constexpr (QT == TK_TYPE_Q4_0) {
-        FragQ40 f;
+    } else if constexpr (QT == TK_TYPE_Q4_0 || QT == TK_TYPE_IQ4_NL || QT == TK_TYPE_IQ4_XS) { /* one tile layout, one set of loads */
+        FragQ4x<QT> f;
         f.q0 = ldg_nt(tile + lo);
         f.q1 = ldg_nt(tile + 1024 + lo);
         f.d = ldg_nt(tile + 2048 + ho);
@@ -2382,7 +2508,7 @@ __device__ __forceinline__ typename TkTile<QT>::Frag g32_load(const uint8_t* til
 template <int QT>
 __device__ __forceinline__ void g32_unpack(const typename TkTile<QT>::Frag& f0, const typename TkTile<QT>::Frag& f1, int lane, typename G32Ops<QT>::type& o) {
     if constexpr (QT == TK_TYPE_Q8_0) unpack_q8_x32(f0, f1, lane, o);
-    else if constexpr (QT == TK_TYPE_Q4_0 || QT == TK_TYPE_Q5_0) unpack_q32_x32(f0, f1, lane, o);
+    else if constexpr (QT == TK_TYPE_Q4_0 || QT == TK_TYPE_Q5_0 || QT == TK_TYPE_IQ4_NL || QT == TK_TYPE_IQ4_XS) unpack_q32_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q4_K) unpack_q4_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q3_K) unpack_q3_x32(f0, f1, lane, o);
@@ -2546,6 +2672,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     if constexpr (ONLY8) g32_k_loop<TK_TYPE_Q8_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (tk_types_is(TYPES, TK_TYPE_Q4_0)) g32_k_loop<TK_TYPE_Q4_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (tk_types_is(TYPES, TK_TYPE_Q5_0)) g32_k_loop<TK_TYPE_Q5_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (tk_types_is(TYPES, TK_TYPE_IQ4_NL)) g32_k_loop<TK_TYPE_IQ4_NL>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (tk_types_is(TYPES, TK_TYPE_IQ4_XS)) g32_k_loop<TK_TYPE_IQ4_XS>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -2623,27 +2751,27 @@ typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
 /* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone.  Type index =
  * the type's kernel_index (tk_type_desc_of), TK_KERNEL_INDEX_Q4K_Q6K for the mix; the static_asserts below hold every column to it */
 static const TkGemvKernel k_gemv_fns[3][2][2][TK_KERNEL_VARIANTS] = {
-    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>, k_gemv_w4a8<1, 1, 32, 0>, k_gemv_w4a8<1, 1, 64, 0>, k_gemv_w4a8<1, 1, 128, 0>},
-      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>, k_gemv_w4a8<2, 1, 32, 0>, k_gemv_w4a8<2, 1, 64, 0>, k_gemv_w4a8<2, 1, 128, 0>}},
-     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>, k_gemv_w4a8<1, 2, 32, 0>, k_gemv_w4a8<1, 2, 64, 0>, k_gemv_w4a8<1, 2, 128, 0>},
-      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>, k_gemv_w4a8<2, 2, 32, 0>, k_gemv_w4a8<2, 2, 64, 0>, k_gemv_w4a8<2, 2, 128, 0>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>, k_gemv_w4a8<2, 1, 32, 1>, k_gemv_w4a8<2, 1, 64, 1>, k_gemv_w4a8<2, 1, 128, 1>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>, k_gemv_w4a8<2, 1, 32, 2>, k_gemv_w4a8<2, 1, 64, 2>, k_gemv_w4a8<2, 1, 128, 2>}}},
+    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>, k_gemv_w4a8<1, 1, 32, 0>, k_gemv_w4a8<1, 1, 64, 0>, k_gemv_w4a8<1, 1, 128, 0>, k_gemv_w4a8<1, 1, 256, 0>, k_gemv_w4a8<1, 1, 512, 0>},
+      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>, k_gemv_w4a8<2, 1, 32, 0>, k_gemv_w4a8<2, 1, 64, 0>, k_gemv_w4a8<2, 1, 128, 0>, k_gemv_w4a8<2, 1, 256, 0>, k_gemv_w4a8<2, 1, 512, 0>}},
+     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>, k_gemv_w4a8<1, 2, 32, 0>, k_gemv_w4a8<1, 2, 64, 0>, k_gemv_w4a8<1, 2, 128, 0>, k_gemv_w4a8<1, 2, 256, 0>, k_gemv_w4a8<1, 2, 512, 0>},
+      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>, k_gemv_w4a8<2, 2, 32, 0>, k_gemv_w4a8<2, 2, 64, 0>, k_gemv_w4a8<2, 2, 128, 0>, k_gemv_w4a8<2, 2, 256, 0>, k_gemv_w4a8<2, 2, 512, 0>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>, k_gemv_w4a8<2, 1, 32, 1>, k_gemv_w4a8<2, 1, 64, 1>, k_gemv_w4a8<2, 1, 128, 1>, k_gemv_w4a8<2, 1, 256, 1>, k_gemv_w4a8<2, 1, 512, 1>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>, k_gemv_w4a8<2, 1, 32, 2>, k_gemv_w4a8<2, 1, 64, 2>, k_gemv_w4a8<2, 1, 128, 2>, k_gemv_w4a8<2, 1, 256, 2>, k_gemv_w4a8<2, 1, 512, 2>}}},
 };
 /* [mt / 2 - 2][type index] */
 static const TkGemvKernel k_gemm_fns[5][TK_KERNEL_VARIANTS] = {
-    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>, k_gemm_w4a8<4, 32>, k_gemm_w4a8<4, 64>, k_gemm_w4a8<4, 128>},
-    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>, k_gemm_w4a8<6, 32>, k_gemm_w4a8<6, 64>, k_gemm_w4a8<6, 128>},
-    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>, k_gemm_w4a8<8, 32>, k_gemm_w4a8<8, 64>, k_gemm_w4a8<8, 128>},
-    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>, k_gemm_w4a8<10, 32>, k_gemm_w4a8<10, 64>, k_gemm_w4a8<10, 128>},
-    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>, k_gemm_w4a8<12, 32>, k_gemm_w4a8<12, 64>, k_gemm_w4a8<12, 128>},
+    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>, k_gemm_w4a8<4, 32>, k_gemm_w4a8<4, 64>, k_gemm_w4a8<4, 128>, k_gemm_w4a8<4, 256>, k_gemm_w4a8<4, 512>},
+    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>, k_gemm_w4a8<6, 32>, k_gemm_w4a8<6, 64>, k_gemm_w4a8<6, 128>, k_gemm_w4a8<6, 256>, k_gemm_w4a8<6, 512>},
+    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>, k_gemm_w4a8<8, 32>, k_gemm_w4a8<8, 64>, k_gemm_w4a8<8, 128>, k_gemm_w4a8<8, 256>, k_gemm_w4a8<8, 512>},
+    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>, k_gemm_w4a8<10, 32>, k_gemm_w4a8<10, 64>, k_gemm_w4a8<10, 128>, k_gemm_w4a8<10, 256>, k_gemm_w4a8<10, 512>},
+    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>, k_gemm_w4a8<12, 32>, k_gemm_w4a8<12, 64>, k_gemm_w4a8<12, 128>, k_gemm_w4a8<12, 256>, k_gemm_w4a8<12, 512>},
 };
 /* [type index] */
-static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>, k_gemm32_w4a8<32>, k_gemm32_w4a8<64>, k_gemm32_w4a8<128>};
+static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>, k_gemm32_w4a8<32>, k_gemm32_w4a8<64>, k_gemm32_w4a8<128>, k_gemm32_w4a8<256>, k_gemm32_w4a8<512>};
 
 /* column c of the three tables holds the kernels of TYPES = tk_column_types[c]: every type's mask at its kernel_index */
 constexpr bool tk_columns_match_the_type_table() {
-    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16, 32, 64, 128};
+    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16, 32, 64, 128, 256, 512};
     for (int i = 0; i < TK_TILED_TYPES; ++i)
         if (tk_column_types[tk_type_desc_of(tk_tiled_type(i)).kernel_index] != tk_type_desc_of(tk_tiled_type(i)).mask) return false;
     return tk_column_types[TK_KERNEL_INDEX_Q4K_Q6K] == TK_TYPES_Q4K_Q6K;

@@ -2,7 +2,7 @@
  * tk_llm_layout.h — HBM layouts of the MI355X LLM path.
  *
  * GGUF k-quant blocks are kept bit-for-bit (the same quantised values, and the file's bytes per 256 weights
- * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked; Q8_0 / Q4_0 / Q5_0: eight 34- / 18- / 22-byte blocks per 256 weights) but re-tiled at load time so that one wavefront's 16-byte-per-lane
+ * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked; Q8_0 / Q4_0 / Q5_0 / IQ4_NL: eight 34- / 18- / 22- / 18-byte blocks per 256 weights; IQ4_XS: its scales unpacked too) but re-tiled at load time so that one wavefront's 16-byte-per-lane
  * load is a contiguous 1 KiB run that already IS an MFMA operand:
  *
  *  Weight tile = 16 weight rows x 256 k (one super-block column).  Lane l = (n = l & 15, g = l >> 4)
@@ -43,6 +43,16 @@
  *  The kernels turn a masked nibble dword (plus the high bits at bit 4) into int8 q - 8 / q - 16 with one add and one xor,
  *  (x + 0x78787878) ^ 0x80808080 / (x + 0x70707070) ^ 0x80808080: no byte carries (0x78 + 15 and 0x70 + 31 stay below 0x100), and the
  *  result is the B operand the Q8_0 chains take.
+ *  IQ4_NL tile (2304 B): the Q4_0 tile byte for byte (same repack kernel, fragment and load); the nibble is a code-book index
+ *  IQ4_XS tile (2304 B = 16 x 144; the block has 136 B): a 256-weight block of 16 rows
+ *      [0    ,2048)  the two nibble loads of the Q4_0 tile with sub-block j in place of 32-block j
+ *      [2048 ,2304)  16 rows x 16 B: the eight sub-block scales s_j = ls_j - 32 as int8 (bytes 0..7), the f16 d (bytes 8, 9), six zero
+ *                    bytes: one 16-byte read per lane where the Q4_0 tile has its eight d, so the fragment and load are the Q4_0 tile's
+ *                    too.  A tighter tail (the block's own 8 bytes: d, scales_h, scales_l = 2176 B) was not taken: it would need a load
+ *                    and a 6-bit unpack of its own in all three families for 5.6 % of the tile's bytes
+ *  The kernels turn four nibbles of a dword into int8 kv[q] with three v_perm_b32: the code book is four constant dwords, two permutes
+ *  on q & 7 look up both halves and a third picks per byte by bit 3.  The result is the B operand the Q8_0 chains take; the block scale
+ *  is d (IQ4_NL) or d * (float)s_j in fp32 (IQ4_XS, exact).
  *  Q3_K tile (1824 B = 16 x 114): weights stored as u = q + 4 (0..7).  Operand dword o = 2 j + hh (o = 0..15) of lane l holds the four
  *  weights k0 + 4 hh + t (t = 0..3, k0 = 32 j + 8 g) of sub-block j, as in the tiles above
  *      [0    ,1024)  one load: lane l -> 4 dwords; bits 8 t + 2 (o & 3) .. + 1 of dword o >> 2 = u & 3 of weight t of operand dword o
@@ -91,6 +101,8 @@
 #define TK_Q8_0_TILE_BYTES 4352
 #define TK_Q4_0_TILE_BYTES 2304
 #define TK_Q5_0_TILE_BYTES 2816
+#define TK_IQ4_NL_TILE_BYTES TK_Q4_0_TILE_BYTES
+#define TK_IQ4_XS_TILE_BYTES 2304
 #define TK_ROW_SLOTS 16  /* rows of one MFMA M-tile */
 #define TK_MAX_TILES 16   /* M-tiles per pass: a weight tile is unpacked once and multiplied against all of them */
 #define TK_MAX_ROWS (TK_ROW_SLOTS * TK_MAX_TILES)
