@@ -45,14 +45,18 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_fill_synthetic_f16(tk_mi
  * attn_v of layers < 4 and ffn_down of layers < n_layer / 8), 15 Q4_K_M (= fill_synthetic), 16 Q5_K_S (every matrix and token_embd Q5_K),
  * 17 Q5_K_M (Q4_K_M with Q5_K in place of Q4_K); output is Q6_K in all eight; 7 Q8_0 (every matrix, token_embd and output Q8_0); 2 Q4_0, 8 Q5_0, 25 IQ4_NL and 30 IQ4_XS (every layer matrix and token_embd in the base type, output Q6_K).  Other values: TK_ERROR_INVALID_ARGUMENT — among them 13 Q3_K_L
  * (Q3_K with Q5_K attn_v, attn_output and ffn_down), which has no synthetic recipe; Q3_K_L FILES load all the same, since loading goes by
- * each tensor's own type and any mix of Q4_0 / Q5_0 / Q8_0 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_NL / IQ4_XS / F16 tensors is accepted
+ * each tensor's own type and any mix of Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_NL / IQ4_XS / F16 tensors is accepted
  * (file type 18, all Q6_K with a Q6_K token_embd, among them; it has no synthetic recipe either).
  * Loader names of the Q2_K recipes: synthetic://mistral-7b-q2k, synthetic://mistral-7b-q2ks, synthetic://tiny-q2k, synthetic://tiny-q2ks; of
  * the Q8_0 recipe: synthetic://mistral-7b-q80, synthetic://tiny-q80; of the Q4_0 / Q5_0 recipes: synthetic://mistral-7b-q40, synthetic://tiny-q40,
  * synthetic://mistral-7b-q50, synthetic://tiny-q50; of the IQ4_NL / IQ4_XS recipes: synthetic://mistral-7b-iq4nl, synthetic://tiny-iq4nl,
- * synthetic://mistral-7b-iq4xs, synthetic://tiny-iq4xs */
+ * synthetic://mistral-7b-iq4xs, synthetic://tiny-iq4xs.  File types 3 (Q4_1) and 9 (Q5_1) have no recipe here: tk_mi355x_llm_model_fill_synthetic_type */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_fill_synthetic_ftype(tk_mi355x_llm_model_t* m, uint64_t seed, int ftype);
-/* test / measurement entry: one production mat-vec of `rows` x K raw GGUF blocks of `type` (2 Q4_0, 6 Q5_0, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS; rows % 64 == 0,
+/* seeded weights by TENSOR type: every layer matrix and token_embd of GGML type `ggml_type`, output Q6_K, norms F32.  Takes 3 (Q4_1) and
+ * 7 (Q5_1), the types whose file types fill_synthetic_ftype refuses; any other value: TK_ERROR_INVALID_ARGUMENT.
+ * Loader names: synthetic://mistral-7b-q41, synthetic://tiny-q41, synthetic://mistral-7b-q51, synthetic://tiny-q51 */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_fill_synthetic_type(tk_mi355x_llm_model_t* m, uint64_t seed, int ggml_type);
+/* test / measurement entry: one production mat-vec of `rows` x K raw GGUF blocks of `type` (2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS; rows % 64 == 0,
  * K % (256 ks) == 0, ks <= 8) against x [nrows][K] (nrows <= 256): the blocks are repacked, x is quantised by the production Q8_K kernel,
  * the production launcher runs at width nrows with K split ks ways, and the ks partial sums are added in ascending order into y [nrows][rows] */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, int ks, int nrows,
@@ -65,6 +69,11 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks(int type, const fl
  * blocks.  Entries of their own for the reason given below for Q2_K: types 2 and 6 stay TK_ERROR_INVALID_ARGUMENT in tk_mi355x_quantize_blocks */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_q4_0(const float* x, int64_t n_blocks, void* out);
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_q5_0(const float* x, int64_t n_blocks, void* out);
+/* ggml's quantize_row_q4_1_ref / quantize_row_q5_1_ref value for value (GGML types 3 and 7): x [n_blocks][32] floats -> n_blocks 20- / 24-byte
+ * blocks (f16 d, f16 m = the block's minimum, then Q4_0's / Q5_0's quant bytes; w = d q + m).  Types 3 and 7 stay TK_ERROR_INVALID_ARGUMENT in
+ * tk_mi355x_quantize_blocks */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_q4_1(const float* x, int64_t n_blocks, void* out);
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_q5_1(const float* x, int64_t n_blocks, void* out);
 /* IQ4_NL / IQ4_XS (GGML types 20 and 23): x [n_blocks][32] / [n_blocks][256] floats -> n_blocks 18- / 136-byte blocks, by this build's own
  * one-pass quantisers (the nearest code-book value against a scale that puts the block's signed extreme on -127; ggml's iterative search
  * is not restated).  Entries of their own for the same reason: types 20 and 23 stay TK_ERROR_INVALID_ARGUMENT in tk_mi355x_quantize_blocks */
@@ -74,8 +83,8 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_iq4_xs(const float
  * tk_mi355x_quantize_blocks takes is fixed — callers rely on type 10 being TK_ERROR_INVALID_ARGUMENT there */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_q2k(const float* x, int64_t n_blocks, void* out);
 /* tensor in GGUF block layout; layer = -1 for {0 token_embd, 1 output_norm, 2 output}, else
- * {0 attn_norm,1 q,2 k,3 v,4 o,5 ffn_norm,6 gate,7 up,8 down}; type = ggml type id (0 F32, 1 F16, 2 Q4_0, 6 Q5_0, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS).
- * token_embd takes every one of them but F32; a Q4_0, Q5_0, Q8_0, IQ4_NL, IQ4_XS or k-quant tensor needs columns % 256 == 0 */
+ * {0 attn_norm,1 q,2 k,3 v,4 o,5 ffn_norm,6 gate,7 up,8 down}; type = ggml type id (0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS).
+ * token_embd takes every one of them but F32; a Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, IQ4_NL, IQ4_XS or k-quant tensor needs columns % 256 == 0 */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_set_tensor(tk_mi355x_llm_model_t* m, int layer, int which, int type, const void* data,
                                                                    size_t nbytes);
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_load_gguf(tk_mi355x_llm_model_t** out, const char* path, int device);

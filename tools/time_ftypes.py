@@ -6,7 +6,7 @@ Per recipe: the weight bytes a decode step streams and the stand-alone gate | up
 weight bytes plus activation and slab bytes over kernel time).  Per width and recipe: the median decode-step time over the repeats (a
 32-token prompt per sequence, 4 warm-up steps, then greedy steps through the captured pass, HIP events around the loop) and its ratio to
 Q4_K_M's median; for Q4_K_M also the spread of its repeats, the yardstick for every ratio beside it.
-    python tools/time_ftypes.py [steps [repeats [recipe ...]]]      recipes: IQ4_NL IQ4_XS Q4_0 Q5_0 Q8_0 Q2_K Q2_K_S Q3_K_S Q3_K_M Q4_K_S Q5_K_S Q5_K_M"""
+    python tools/time_ftypes.py [steps [repeats [recipe ...]]]      recipes: IQ4_NL IQ4_XS Q4_0 Q4_1 Q5_0 Q5_1 Q8_0 Q2_K Q2_K_S Q3_K_S Q3_K_M Q4_K_S Q5_K_S Q5_K_M"""
 import ctypes as C
 import os
 import sys
@@ -18,19 +18,21 @@ import trackiellm_amd as tk  # noqa: E402
 
 FTYPES = {"IQ4_NL": tk.FTYPE_IQ4_NL, "IQ4_XS": tk.FTYPE_IQ4_XS, "Q4_0": tk.FTYPE_Q4_0, "Q5_0": tk.FTYPE_Q5_0, "Q8_0": tk.FTYPE_Q8_0, "Q2_K": tk.FTYPE_Q2_K, "Q2_K_S": tk.FTYPE_Q2_K_S, "Q3_K_S": tk.FTYPE_Q3_K_S, "Q3_K_M": tk.FTYPE_Q3_K_M, "Q4_K_S": tk.FTYPE_Q4_K_S,
           "Q4_K_M": tk.FTYPE_Q4_K_M, "Q5_K_S": tk.FTYPE_Q5_K_S, "Q5_K_M": tk.FTYPE_Q5_K_M}
+TTYPES = {"Q4_1": tk.TYPE_Q4_1, "Q5_1": tk.TYPE_Q5_1}  # recipes by tensor type (fill_synthetic_type): no file type of fill_synthetic makes them
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 names = ["Q4_K_M"] + [n for n in (sys.argv[3:] or ["Q5_K_M", "Q3_K_S", "Q3_K_M", "Q2_K", "Q2_K_S"]) if n != "Q4_K_M"]
 for n in names:
-    if n not in FTYPES:
-        sys.exit(f"unknown recipe {n}; known: {' '.join(FTYPES)}")
+    if n not in FTYPES and n not in TTYPES:
+        sys.exit(f"unknown recipe {n}; known: {' '.join(list(FTYPES) + list(TTYPES))}")
 wb = tk.lib().tk_mi355x_llm_model_weight_bytes
 wb.restype = C.c_uint64
 WIDTHS = (16, 64, 128, 256)
 
 models, nbytes = {}, {}
 for name in names:
-    models[name] = tk.LlmModel(tk.MISTRAL_7B(), device=0).fill_synthetic(4, ftype=FTYPES[name])
+    model = tk.LlmModel(tk.MISTRAL_7B(), device=0)
+    models[name] = model.fill_synthetic_type(4, TTYPES[name]) if name in TTYPES else model.fill_synthetic(4, ftype=FTYPES[name])
     nbytes[name] = wb(models[name].h)
     print(f"{name}: {nbytes[name] / 1e9:.3f} GB of weights streamed per decode step, x{nbytes[name] / nbytes['Q4_K_M']:.3f} of Q4_K_M", flush=True)
 

@@ -152,6 +152,18 @@ tk_error_code_t tk_mi355x_quantize_blocks_q5_0(const float* x, int64_t n_blocks,
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_quantize_blocks_q4_1(const float* x, int64_t n_blocks, void* out) {
+    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
+    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_q4_1(x + 32 * b, (tk_block_q4_1*)out + b);
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_quantize_blocks_q5_1(const float* x, int64_t n_blocks, void* out) {
+    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
+    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_q5_1(x + 32 * b, (tk_block_q5_1*)out + b);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_quantize_blocks_iq4_nl(const float* x, int64_t n_blocks, void* out) {
     if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
     for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_iq4_nl(x + 32 * b, (tk_block_iq4_nl*)out + b);
@@ -167,6 +179,12 @@ tk_error_code_t tk_mi355x_quantize_blocks_iq4_xs(const float* x, int64_t n_block
 tk_error_code_t tk_mi355x_llm_model_fill_synthetic_ftype(tk_mi355x_llm_model_t* m, uint64_t seed, int ftype) {
     if (!m || !(ftype == 2 || ftype == 8 || ftype == 7 || ftype == 10 || ftype == 11 || ftype == 12 || (ftype >= 14 && ftype <= 17) || ftype == 21 || ftype == 25 || ftype == 30)) return TK_ERROR_INVALID_ARGUMENT;
     if (!m->model.fill_synthetic(seed, false, ftype)) return fail(TK_ERROR_GPU_ROCM_ERROR, m->model.error);
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_model_fill_synthetic_type(tk_mi355x_llm_model_t* m, uint64_t seed, int ggml_type) {
+    if (!m || !(ggml_type == TK_TYPE_Q4_1 || ggml_type == TK_TYPE_Q5_1)) return TK_ERROR_INVALID_ARGUMENT;
+    if (!m->model.fill_synthetic_type(seed, ggml_type)) return fail(TK_ERROR_GPU_ROCM_ERROR, m->model.error);
     return TK_SUCCESS;
 }
 
@@ -723,9 +741,12 @@ tk_error_code_t tk_model_loader_load_model(tk_model_loader_t* loader, const tk_m
         const bool f16 = name.size() > 4 && name.compare(name.size() - 4, 4, "-f16") == 0; /* the fp16 checkpoint recipe (BASELINE configs[4]) */
         if (f16) name.resize(name.size() - 4);
         int ftype = 0; /* the Q8_0, Q4_0, Q5_0, IQ4_NL, IQ4_XS and Q2_K recipes of fill_synthetic_ftype: synthetic://mistral-7b-q80, synthetic://mistral-7b-q40, synthetic://tiny-q50, synthetic://mistral-7b-iq4nl, synthetic://tiny-iq4xs, synthetic://mistral-7b-q2k, synthetic://tiny-q2ks */
+        int gtype = 0; /* the recipes of fill_synthetic_type, by tensor type: synthetic://mistral-7b-q41, synthetic://tiny-q51 */
         if (name.size() > 4 && name.compare(name.size() - 4, 4, "-q80") == 0) { ftype = 7; name.resize(name.size() - 4); }
         else if (name.size() > 4 && name.compare(name.size() - 4, 4, "-q40") == 0) { ftype = 2; name.resize(name.size() - 4); }
         else if (name.size() > 4 && name.compare(name.size() - 4, 4, "-q50") == 0) { ftype = 8; name.resize(name.size() - 4); }
+        else if (name.size() > 4 && name.compare(name.size() - 4, 4, "-q41") == 0) { gtype = TK_TYPE_Q4_1; name.resize(name.size() - 4); }
+        else if (name.size() > 4 && name.compare(name.size() - 4, 4, "-q51") == 0) { gtype = TK_TYPE_Q5_1; name.resize(name.size() - 4); }
         else if (name.size() > 6 && name.compare(name.size() - 6, 6, "-iq4nl") == 0) { ftype = 25; name.resize(name.size() - 6); }
         else if (name.size() > 6 && name.compare(name.size() - 6, 6, "-iq4xs") == 0) { ftype = 30; name.resize(name.size() - 6); }
         else if (name.size() > 5 && name.compare(name.size() - 5, 5, "-q2ks") == 0) { ftype = 21; name.resize(name.size() - 5); }
@@ -737,6 +758,7 @@ tk_error_code_t tk_model_loader_load_model(tk_model_loader_t* loader, const tk_m
         if (rc == TK_SUCCESS && !lora.empty()) rc = tk_mi355x_llm_model_set_lora(m, lora.c_str());
         if (rc == TK_SUCCESS)
             rc = f16 ? tk_mi355x_llm_model_fill_synthetic_f16(m, seed)
+                     : gtype ? tk_mi355x_llm_model_fill_synthetic_type(m, seed, gtype)
                      : ftype ? tk_mi355x_llm_model_fill_synthetic_ftype(m, seed, ftype) : tk_mi355x_llm_model_fill_synthetic(m, seed);
         if (rc != TK_SUCCESS) { if (m) release_model(m); return rc; } /* g_models_mu is held here */
         if (m->lora) { m->model.lora = nullptr; m->lora->drop_factors(); }

@@ -28,6 +28,9 @@
  *         w = d*(q-8), q in 0..15 (exact in fp32): the Q8_0 block with the same d and q8 = q - 8
  *   Q5_0: 32 weights / 22 B: f16 d, 4 B of high bits (one little-endian u32: bit i = bit 4 of weight i), 16 B of nibbles laid out
  *         as Q4_0's.   w = d*(q-16), q in 0..31 (exact in fp32): the Q8_0 block with the same d and q8 = q - 16
+ *   Q4_1: 32 weights / 20 B: f16 d, f16 m, 16 B of nibbles laid out as Q4_0's.   w = d*q + m, q in 0..15: d*q is exact in fp32, the add
+ *         rounds once, so the decode is fmaf(d, q, m)
+ *   Q5_1: 32 weights / 24 B: f16 d, f16 m, 4 B of high bits and 16 B of nibbles as Q5_0's.   w = d*q + m = fmaf(d, q, m), q in 0..31
  *   IQ4_NL: 32 weights / 18 B: the Q4_0 block's bytes, the nibble an index into the 16-entry code book tk_iq4_kv.
  *         w = d*kv[q] (exact in fp32): the Q8_0 block with the same d and q8 = kv[q]
  *   IQ4_XS: 256 weights / 136 B: f16 d, u16 scales_h (little endian), scales_l[4], 128 B of nibbles (sub-block j of 32 weights =
@@ -50,7 +53,9 @@ enum tk_ggml_type {
     TK_TYPE_F32 = 0,
     TK_TYPE_F16 = 1,
     TK_TYPE_Q4_0 = 2,
+    TK_TYPE_Q4_1 = 3,
     TK_TYPE_Q5_0 = 6,
+    TK_TYPE_Q5_1 = 7,
     TK_TYPE_Q8_0 = 8,
     TK_TYPE_Q2_K = 10,
     TK_TYPE_Q3_K = 11,
@@ -113,7 +118,20 @@ typedef struct {
     uint8_t qh[4]; /* one little-endian u32 */
     uint8_t qs[16];
 } tk_block_q5_0; /* 22 B, 32 weights */
-#define TK_Q32_PER_RUN (TK_QK_K / 32) /* 32-weight blocks (Q4_0, Q5_0, Q8_0, IQ4_NL) of one 256-k run */
+#define TK_Q32_PER_RUN (TK_QK_K / 32) /* 32-weight blocks (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, IQ4_NL) of one 256-k run */
+
+typedef struct {
+    uint16_t d;
+    uint16_t m;
+    uint8_t qs[16];
+} tk_block_q4_1; /* 20 B, 32 weights */
+
+typedef struct {
+    uint16_t d;
+    uint16_t m;
+    uint8_t qh[4]; /* one little-endian u32 */
+    uint8_t qs[16];
+} tk_block_q5_1; /* 24 B, 32 weights */
 
 typedef struct {
     uint16_t d;
@@ -146,7 +164,7 @@ struct tk_type_desc {
     int mask, kernel_index;        /* its bit in the kernels' TYPES argument; its column in k_gemv_fns / k_gemm_fns / k_gemm32_fns */
     bool shares_launch;            /* may ride in one launch beside another such type (the Q4_K | Q6_K kernels); tk_launch_gemv splits any other mix */
     bool token_embd, lora_merge;   /* k_embed decodes it; k_lora_merge re-quantises it */
-    bool host_quantize;            /* tk_mi355x_quantize_blocks takes it (a pinned set: Q2_K, Q4_0, Q5_0, IQ4_NL and IQ4_XS have entry points of their own) */
+    bool host_quantize;            /* tk_mi355x_quantize_blocks takes it (a pinned set: Q2_K, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL and IQ4_XS have entry points of their own) */
 };
 TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
     switch (type) {
@@ -155,6 +173,8 @@ TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
         case TK_TYPE_F16:  return {"F16",  1,    2,    0,                 0,   -1, false, true,  true,  false};
         case TK_TYPE_Q4_0: return {"Q4_0", 32,   18,   TK_Q4_0_TILE_BYTES, 64, 7,  false, true,  false, false};
         case TK_TYPE_Q5_0: return {"Q5_0", 32,   22,   TK_Q5_0_TILE_BYTES, 128, 8, false, true,  false, false};
+        case TK_TYPE_Q4_1: return {"Q4_1", 32,   20,   TK_Q4_1_TILE_BYTES, 1024, 11, false, true, false, false};
+        case TK_TYPE_Q5_1: return {"Q5_1", 32,   24,   TK_Q5_1_TILE_BYTES, 2048, 12, false, true, false, false};
         case TK_TYPE_Q8_0: return {"Q8_0", 32,   34,   TK_Q8_0_TILE_BYTES, 32, 6,  false, true,  false, true};
         case TK_TYPE_Q2_K: return {"Q2_K", 256,  84,   TK_Q2K_TILE_BYTES, 16,  5,  false, true,  false, false};
         case TK_TYPE_Q3_K: return {"Q3_K", 256,  110,  TK_Q3K_TILE_BYTES, 8,   4,  false, true,  false, true};
@@ -167,10 +187,10 @@ TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
     }
 }
 /* the lists the messages print: kept beside the table, edited with it */
-#define TK_TYPE_NAMES "F32, F16, Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS"
-#define TK_TYPE_NAMES_OR "F32, F16, Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
-#define TK_KQUANT_NAMES_OR "Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
-#define TK_TOKEN_EMBD_NAMES_OR "Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS or F16"
+#define TK_TYPE_NAMES "F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS"
+#define TK_TYPE_NAMES_OR "F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
+#define TK_KQUANT_NAMES_OR "Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
+#define TK_TOKEN_EMBD_NAMES_OR "Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS or F16"
 #define TK_LORA_MERGE_NAMES_OR "Q4_K, Q6_K or F16"
 
 TK_HD constexpr bool tk_type_known(int type) { return tk_type_desc_of(type).name != nullptr; }
@@ -178,19 +198,19 @@ TK_HD constexpr bool tk_type_is_kquant(int type) { return tk_type_desc_of(type).
 TK_HD constexpr size_t tk_type_block_bytes(int type) { return (size_t)tk_type_desc_of(type).block_bytes; }
 TK_HD constexpr size_t tk_type_block_elems(int type) { return (size_t)tk_type_desc_of(type).block_elems; }
 
-/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make eleven values: the ten tiled types alone
+/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make thirteen values: the twelve tiled types alone
  * and the one mix of the two shares_launch types, whose kernels pick the tile type per segment at run time. */
-/* the tiled types (tile_bytes != 0), listed: their enum values are not one range (Q4_0 = 2, Q5_0 = 6, Q8_0 = 8, the k-quants 10 .. 14, IQ4_NL = 20, IQ4_XS = 23), and a
+/* the tiled types (tile_bytes != 0), listed: their enum values are not one range (Q4_0 = 2, Q4_1 = 3, Q5_0 = 6, Q5_1 = 7, Q8_0 = 8, the k-quants 10 .. 14, IQ4_NL = 20, IQ4_XS = 23), and a
  * loop over [first, last] would lean on the types between having no row */
-#define TK_TILED_TYPES 10
+#define TK_TILED_TYPES 12
 TK_HD constexpr int tk_tiled_type(int i) {
     constexpr int types[TK_TILED_TYPES] = {TK_TYPE_Q4_0, TK_TYPE_Q5_0, TK_TYPE_Q8_0, TK_TYPE_Q2_K, TK_TYPE_Q3_K, TK_TYPE_Q4_K, TK_TYPE_Q5_K, TK_TYPE_Q6_K,
-                                             TK_TYPE_IQ4_NL, TK_TYPE_IQ4_XS};
+                                             TK_TYPE_IQ4_NL, TK_TYPE_IQ4_XS, TK_TYPE_Q4_1, TK_TYPE_Q5_1};
     return types[i];
 }
 #define TK_TYPES_Q4K_Q6K (tk_type_desc_of(TK_TYPE_Q4_K).mask | tk_type_desc_of(TK_TYPE_Q6_K).mask)
 #define TK_KERNEL_INDEX_Q4K_Q6K 2
-#define TK_KERNEL_VARIANTS 11
+#define TK_KERNEL_VARIANTS 13
 TK_HD constexpr bool tk_types_has(int types, int type) { return (types & tk_type_desc_of(type).mask) != 0; }
 TK_HD constexpr bool tk_types_is(int types, int type) { return types == tk_type_desc_of(type).mask; }
 /* tile bytes of a single-type launch: a compile-time pitch (tile addresses become scalar base + immediate); 0 for the mix */
@@ -206,6 +226,9 @@ TK_HD constexpr size_t tk_types_tile_bytes(int types) {
 TK_TYPE_ROW_CHECK(TK_TYPE_Q8_0, tk_block_q8_0, TK_Q8_0_PER_RUN * 34); /* a tile column is one 256-k run: eight blocks per row */
 TK_TYPE_ROW_CHECK(TK_TYPE_Q4_0, tk_block_q4_0, TK_Q32_PER_RUN * 18);
 TK_TYPE_ROW_CHECK(TK_TYPE_Q5_0, tk_block_q5_0, TK_Q32_PER_RUN * 22);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q4_1, tk_block_q4_1, TK_Q32_PER_RUN * 20);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q5_1, tk_block_q5_1, TK_Q32_PER_RUN * 24);
+static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_Q4_1).block_elems == 0 && TK_QK_K % tk_type_desc_of(TK_TYPE_Q5_1).block_elems == 0, "Q4_1 / Q5_1: a 256-k run must be whole blocks");
 static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_Q4_0).block_elems == 0 && TK_QK_K % tk_type_desc_of(TK_TYPE_Q5_0).block_elems == 0, "Q4_0 / Q5_0: a 256-k run must be whole blocks");
 static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_Q8_0).block_elems == 0, "Q8_0: a 256-k run must be whole blocks");
 TK_TYPE_ROW_CHECK(TK_TYPE_Q2_K, tk_block_q2_K, 84);
@@ -218,8 +241,8 @@ TK_TYPE_ROW_CHECK(TK_TYPE_IQ4_XS, tk_block_iq4_xs, 144); /* the tile holds the e
 static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_IQ4_NL).block_elems == 0, "IQ4_NL: a 256-k run must be whole blocks");
 static_assert(sizeof(tk_block_iq4_nl) == sizeof(tk_block_q4_0) && TK_IQ4_NL_TILE_BYTES == TK_Q4_0_TILE_BYTES, "IQ4_NL rides on the Q4_0 repack, fragment and load");
 #undef TK_TYPE_ROW_CHECK
-/* every tiled type is listed once and nothing else has a tile; every mask is one bit of its own, and the kernel indices of the eleven
- * TYPES values are 0 .. 10, each once */
+/* every tiled type is listed once and nothing else has a tile; every mask is one bit of its own, and the kernel indices of the thirteen
+ * TYPES values are 0 .. 12, each once */
 TK_HD constexpr bool tk_type_table_consistent() {
     int masks = 0, indices = 1 << TK_KERNEL_INDEX_Q4K_Q6K;
     int listed = 0;
@@ -235,7 +258,7 @@ TK_HD constexpr bool tk_type_table_consistent() {
     }
     return indices == (1 << TK_KERNEL_VARIANTS) - 1;
 }
-static_assert(tk_type_table_consistent(), "tk_type_desc_of: tk_tiled_type must list the rows with a tile, masks must be distinct bits and kernel indices 0 .. 10, each once");
+static_assert(tk_type_table_consistent(), "tk_type_desc_of: tk_tiled_type must list the rows with a tile, masks must be distinct bits and kernel indices 0 .. 12, each once");
 
 /* 6-bit (scale, min) pair j of a Q4_K block */
 TK_HD void tk_q4k_get_scale_min(int j, const uint8_t* q, uint8_t* sc, uint8_t* m) {
@@ -393,6 +416,18 @@ TK_HD int tk_q5_0_quant(const tk_block_q5_0* b, int i) {
     return lo | (((b->qh[i >> 3] >> (i & 7)) & 1) << 4);
 }
 TK_HD float tk_q5_0_dequant(const tk_block_q5_0* b, int i) { return tk_f16_to_f32(b->d) * (float)(tk_q5_0_quant(b, i) - 16); }
+
+/* weight i (0..31) of a Q4_1 block, q in [0,15]: the Q4_0 nibble order.  w = d * q + m: the product is exact in fp32 (11 bits times 4), the
+ * add rounds once, which is what one fma computes */
+TK_HD int tk_q4_1_quant(const tk_block_q4_1* b, int i) { return i < 16 ? (b->qs[i] & 15) : (b->qs[i - 16] >> 4); }
+TK_HD float tk_q4_1_dequant(const tk_block_q4_1* b, int i) { return tk_fmaf(tk_f16_to_f32(b->d), (float)tk_q4_1_quant(b, i), tk_f16_to_f32(b->m)); }
+
+/* weight i (0..31) of a Q5_1 block, q in [0,31]: the Q5_0 nibble and high-bit order.  w = fmaf(d, q, m) (11 bits times 5) */
+TK_HD int tk_q5_1_quant(const tk_block_q5_1* b, int i) {
+    const int lo = i < 16 ? (b->qs[i] & 15) : (b->qs[i - 16] >> 4);
+    return lo | (((b->qh[i >> 3] >> (i & 7)) & 1) << 4);
+}
+TK_HD float tk_q5_1_dequant(const tk_block_q5_1* b, int i) { return tk_fmaf(tk_f16_to_f32(b->d), (float)tk_q5_1_quant(b, i), tk_f16_to_f32(b->m)); }
 
 /* stored nibble (the code-book index, 0..15) of weight i (0..31) of an IQ4_NL block or of one IQ4_XS sub-block, whose sixteen bytes qs
  * are laid out as Q4_0's */
@@ -681,6 +716,52 @@ TK_HD void tk_quantize_q5_0(const float* x, tk_block_q5_0* out) {
         int q0 = (int)(int8_t)(int)(x0 + 16.5f), q1 = (int)(int8_t)(int)(x1 + 16.5f);
         q0 = q0 > 31 ? 31 : q0;
         q1 = q1 > 31 ? 31 : q1;
+        out->qs[j] = (uint8_t)((q0 & 15) | ((q1 & 15) << 4));
+        qh |= (uint32_t)((q0 & 16) >> 4) << j;
+        qh |= (uint32_t)((q1 & 16) >> 4) << (j + 16);
+    }
+    for (int k = 0; k < 4; ++k) out->qh[k] = (uint8_t)(qh >> (8 * k));
+}
+
+/* Q4_1 / Q5_1: ggml's published quantize_row_q4_1_ref / quantize_row_q5_1_ref, value for value, all in binary32: min and max the block's
+ * smallest and largest element, d = (max - min) / 15 (31), id = d ? 1 / d : 0 from the unrounded d, d and m = min stored as f16,
+ * q = min(15, (int8_t)((x - min) * id + 0.5f)) for Q4_1 and (uint8_t)((x - min) * id + 0.5f) for Q5_1, which takes no clamp:
+ * (x - min) * id <= 31 (1 + a few 2^-24), so the sum stays below 32.  A constant block gives d = +0, q = 0, m = x */
+TK_HD void tk_quantize_q4_1(const float* x, tk_block_q4_1* out) {
+    float min = x[0], max = x[0];
+    for (int i = 1; i < 32; ++i) {
+        const float v = x[i];
+        if (v < min) min = v;
+        if (v > max) max = v;
+    }
+    const float d = tk_divf(max - min, 15.0f);
+    const float id = d != 0.0f ? tk_divf(1.0f, d) : 0.0f;
+    out->d = tk_f32_to_f16(d);
+    out->m = tk_f32_to_f16(min);
+    for (int j = 0; j < 16; ++j) {
+        const float x0 = (x[j] - min) * id, x1 = (x[16 + j] - min) * id;
+        int q0 = (int)(int8_t)(int)(x0 + 0.5f), q1 = (int)(int8_t)(int)(x1 + 0.5f);
+        q0 = q0 > 15 ? 15 : q0;
+        q1 = q1 > 15 ? 15 : q1;
+        out->qs[j] = (uint8_t)((uint8_t)q0 | ((uint8_t)q1 << 4));
+    }
+}
+
+TK_HD void tk_quantize_q5_1(const float* x, tk_block_q5_1* out) {
+    float min = x[0], max = x[0];
+    for (int i = 1; i < 32; ++i) {
+        const float v = x[i];
+        if (v < min) min = v;
+        if (v > max) max = v;
+    }
+    const float d = tk_divf(max - min, 31.0f);
+    const float id = d != 0.0f ? tk_divf(1.0f, d) : 0.0f;
+    out->d = tk_f32_to_f16(d);
+    out->m = tk_f32_to_f16(min);
+    uint32_t qh = 0;
+    for (int j = 0; j < 16; ++j) {
+        const float x0 = (x[j] - min) * id, x1 = (x[16 + j] - min) * id;
+        const int q0 = (int)(uint8_t)(int)(x0 + 0.5f), q1 = (int)(uint8_t)(int)(x1 + 0.5f);
         out->qs[j] = (uint8_t)((q0 & 15) | ((q1 & 15) << 4));
         qh |= (uint32_t)((q0 & 16) >> 4) << j;
         qh |= (uint32_t)((q1 & 16) >> 4) << (j + 16);

@@ -71,6 +71,18 @@ __global__ void k_synth_blocks(int type, uint64_t seed, uint64_t tid, int64_t nb
             tk_quantize_q5_0(x + 32 * j, &blk);
             ((tk_block_q5_0*)out)[TK_Q32_PER_RUN * b + j] = blk;
         }
+    } else if (type == TK_TYPE_Q4_1) {
+        for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
+            tk_block_q4_1 blk;
+            tk_quantize_q4_1(x + 32 * j, &blk);
+            ((tk_block_q4_1*)out)[TK_Q32_PER_RUN * b + j] = blk;
+        }
+    } else if (type == TK_TYPE_Q5_1) {
+        for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
+            tk_block_q5_1 blk;
+            tk_quantize_q5_1(x + 32 * j, &blk);
+            ((tk_block_q5_1*)out)[TK_Q32_PER_RUN * b + j] = blk;
+        }
     } else if (type == TK_TYPE_IQ4_NL) {
         for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
             tk_block_iq4_nl blk;
@@ -370,6 +382,63 @@ __global__ void k_repack_q5_0(const tk_block_q5_0* src, int64_t nblk, uint8_t* t
     }
 }
 
+/* Q4_1 tile (tk_llm_layout.h): the Q4_0 tile's two nibble loads, then per row the eight d and the eight m */
+__global__ void k_repack_q4_1(const tk_block_q4_1* src, int64_t nblk, uint8_t* tiles) {
+    const int lane = threadIdx.x;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t rt = blockIdx.y, blk = blockIdx.x;
+    const tk_block_q4_1* b = src + ((rt * 16 + n) * nblk + blk) * TK_Q32_PER_RUN;
+    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q4_1_TILE_BYTES;
+    for (int i = 0; i < 2; ++i) {
+        uint32_t dw[4];
+        for (int s = 0; s < 4; ++s) {
+            const tk_block_q4_1* bj = b + 4 * i + s;
+            const int k0 = 8 * g;
+            uint32_t v = 0;
+            for (int t = 0; t < 4; ++t) v |= (uint32_t)(tk_q4_1_quant(bj, k0 + t) | (tk_q4_1_quant(bj, k0 + 4 + t) << 4)) << (8 * t);
+            dw[s] = v;
+        }
+        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+    }
+    if (g < 2) { /* lane group 0 writes the row's d, group 1 its m */
+        uint32_t d[4];
+        for (int k = 0; k < 4; ++k) d[k] = g == 0 ? (uint32_t)b[2 * k].d | ((uint32_t)b[2 * k + 1].d << 16) : (uint32_t)b[2 * k].m | ((uint32_t)b[2 * k + 1].m << 16);
+        *(uint4*)(tile + 2048 + n * 32 + g * 16) = make_uint4(d[0], d[1], d[2], d[3]);
+    }
+}
+
+/* Q5_1 tile: the Q5_0 tile's nibble loads and high bits, then the Q4_1 tile's (d, m) tail */
+__global__ void k_repack_q5_1(const tk_block_q5_1* src, int64_t nblk, uint8_t* tiles) {
+    const int lane = threadIdx.x;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t rt = blockIdx.y, blk = blockIdx.x;
+    const tk_block_q5_1* b = src + ((rt * 16 + n) * nblk + blk) * TK_Q32_PER_RUN;
+    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q5_1_TILE_BYTES;
+    uint32_t hb[2] = {0, 0};
+    for (int i = 0; i < 2; ++i) {
+        uint32_t dw[4];
+        for (int s = 0; s < 4; ++s) {
+            const tk_block_q5_1* bj = b + 4 * i + s;
+            const int k0 = 8 * g;
+            uint32_t v = 0;
+            for (int t = 0; t < 4; ++t) {
+                const int qa = tk_q5_1_quant(bj, k0 + t), qb = tk_q5_1_quant(bj, k0 + 4 + t);
+                v |= (uint32_t)((qa & 15) | ((qb & 15) << 4)) << (8 * t);
+                hb[i] |= (uint32_t)(qa >> 4) << (8 * t + s);
+                hb[i] |= (uint32_t)(qb >> 4) << (8 * t + 4 + s);
+            }
+            dw[s] = v;
+        }
+        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+    }
+    *(uint2*)(tile + 2048 + lane * 8) = make_uint2(hb[0], hb[1]);
+    if (g < 2) {
+        uint32_t d[4];
+        for (int k = 0; k < 4; ++k) d[k] = g == 0 ? (uint32_t)b[2 * k].d | ((uint32_t)b[2 * k + 1].d << 16) : (uint32_t)b[2 * k].m | ((uint32_t)b[2 * k + 1].m << 16);
+        *(uint4*)(tile + 2560 + n * 32 + g * 16) = make_uint4(d[0], d[1], d[2], d[3]);
+    }
+}
+
 /* IQ4_XS tile (tk_llm_layout.h): the Q4_0 tile's two nibble loads with the block's sub-blocks in place of 32-blocks, then per row the
  * eight scales s_j as int8, the f16 d and six zero bytes */
 __global__ void k_repack_iq4_xs(const tk_block_iq4_xs* src, int64_t nblk, uint8_t* tiles) {
@@ -404,6 +473,8 @@ void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uin
         case TK_TYPE_IQ4_XS: hipLaunchKernelGGL(k_repack_iq4_xs, grid, dim3(64), 0, s, (const tk_block_iq4_xs*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q4_0: hipLaunchKernelGGL(k_repack_q4_0, grid, dim3(64), 0, s, (const tk_block_q4_0*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q5_0: hipLaunchKernelGGL(k_repack_q5_0, grid, dim3(64), 0, s, (const tk_block_q5_0*)blocks, K / 256, tiles); break;
+        case TK_TYPE_Q4_1: hipLaunchKernelGGL(k_repack_q4_1, grid, dim3(64), 0, s, (const tk_block_q4_1*)blocks, K / 256, tiles); break;
+        case TK_TYPE_Q5_1: hipLaunchKernelGGL(k_repack_q5_1, grid, dim3(64), 0, s, (const tk_block_q5_1*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q8_0: hipLaunchKernelGGL(k_repack_q8_0, grid, dim3(64), 0, s, (const tk_block_q8_0*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q2_K: hipLaunchKernelGGL(k_repack_q2k, grid, dim3(64), 0, s, (const tk_block_q2_K*)blocks, K / 256, tiles); break;
         case TK_TYPE_Q3_K: hipLaunchKernelGGL(k_repack_q3k, grid, dim3(64), 0, s, (const tk_block_q3_K*)blocks, K / 256, tiles); break;
@@ -440,6 +511,12 @@ __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, f
     } else if (type == TK_TYPE_Q5_0) {
         const tk_block_q5_0* row = (const tk_block_q5_0*)embd + (int64_t)tok[r] * (D / 32);
         x[(int64_t)r * D + i] = tk_q5_0_dequant(row + i / 32, i % 32);
+    } else if (type == TK_TYPE_Q4_1) {
+        const tk_block_q4_1* row = (const tk_block_q4_1*)embd + (int64_t)tok[r] * (D / 32);
+        x[(int64_t)r * D + i] = tk_q4_1_dequant(row + i / 32, i % 32);
+    } else if (type == TK_TYPE_Q5_1) {
+        const tk_block_q5_1* row = (const tk_block_q5_1*)embd + (int64_t)tok[r] * (D / 32);
+        x[(int64_t)r * D + i] = tk_q5_1_dequant(row + i / 32, i % 32);
     } else if (type == TK_TYPE_IQ4_NL) {
         const tk_block_iq4_nl* row = (const tk_block_iq4_nl*)embd + (int64_t)tok[r] * (D / 32);
         x[(int64_t)r * D + i] = tk_iq4nl_dequant(row + i / 32, i % 32);
@@ -653,6 +730,9 @@ typedef FragQ4x<TK_TYPE_Q4_0> FragQ40;
 typedef FragQ4x<TK_TYPE_IQ4_NL> FragIQ4NL;
 typedef FragQ4x<TK_TYPE_IQ4_XS> FragIQ4XS;
 struct FragQ50 { uint4 q0, q1, d; uint2 qh; };
+/* Q4_1 / Q5_1: the Q4_0 / Q5_0 fragment plus the row's eight f16 m */
+struct FragQ41 { uint4 q0, q1, d, m; };
+struct FragQ51 { uint4 q0, q1, d, m; uint2 qh; };
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef unsigned v2u32 __attribute__((ext_vector_type(2)));
@@ -730,6 +810,27 @@ __device__ __forceinline__ FragQ50 load_q5_0(const uint8_t* tile, int lane) {
     return f;
 }
 
+/* d, m: the two 16-byte halves of the row's 32-byte tile tail */
+__device__ __forceinline__ FragQ41 load_q4_1(const uint8_t* tile, int lane) {
+    FragQ41 f;
+    f.q0 = ldg_nt(tile + lane * 16);
+    f.q1 = ldg_nt(tile + 1024 + lane * 16);
+    f.d = ldg_nt(tile + 2048 + (lane & 15) * 32);
+    f.m = ldg_nt(tile + 2064 + (lane & 15) * 32);
+    return f;
+}
+
+__device__ __forceinline__ FragQ51 load_q5_1(const uint8_t* tile, int lane) {
+    FragQ51 f;
+    f.q0 = ldg_nt(tile + lane * 16);
+    f.q1 = ldg_nt(tile + 1024 + lane * 16);
+    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + lane * 8));
+    f.qh = make_uint2(qh.x, qh.y);
+    f.d = ldg_nt(tile + 2560 + (lane & 15) * 32);
+    f.m = ldg_nt(tile + 2576 + (lane & 15) * 32);
+    return f;
+}
+
 __device__ __forceinline__ FragQ6 load_q6(const uint8_t* tile, int lane) {
     FragQ6 f;
     f.q0 = ldg_nt(tile + lane * 16);
@@ -760,6 +861,8 @@ TK_TILE(TileQ40, TK_TYPE_Q4_0, FragQ40, load_q4_0<TK_TYPE_Q4_0>);
 TK_TILE(TileQ50, TK_TYPE_Q5_0, FragQ50, load_q5_0);
 TK_TILE(TileIQ4NL, TK_TYPE_IQ4_NL, FragIQ4NL, load_q4_0<TK_TYPE_IQ4_NL>);
 TK_TILE(TileIQ4XS, TK_TYPE_IQ4_XS, FragIQ4XS, load_q4_0<TK_TYPE_IQ4_XS>);
+TK_TILE(TileQ41, TK_TYPE_Q4_1, FragQ41, load_q4_1);
+TK_TILE(TileQ51, TK_TYPE_Q5_1, FragQ51, load_q5_1);
 #undef TK_TILE
 /* the tile pitch of a launch: a compile-time constant in single-type launches (tile addresses become scalar base + immediate); the
  * Q4_K | Q6_K kernels take it from the segment's type */
@@ -1246,6 +1349,97 @@ __device__ __forceinline__ void mma_q8(const OpsQ8& o, const uint8_t* lds_act, c
     }
 }
 
+/*
+ * Q4_1 / Q5_1: w = d * q + m per block of 32, q unsigned (0..15 / 0..31), d and m f16.  The masked nibble dword (plus Q5_1's high bits at
+ * bit 4) IS the int8 B operand: no offset, nothing folded into a scale.  Per 32-block j and output the contract is Q4_K's pair of FMAs,
+ *     acc = fmaf(d_j * d8, (float)P_j, acc);  acc = fmaf(m_j * d8, (float)S_j, acc);      P_j = sum_k q_k a_k,  S_j = sum_k a_k
+ * blocks ascending, both integers exact (|P_j| <= 32 * 31 * 127, |S_j| <= 32 * 127).  S_j comes from the matrix pipe: the block's A operand
+ * against an all-ones B operand lands in P_j's accumulator layout, with no LDS read, no lane movement and no unpacking on the VALU,
+ * which bounds the Q8_0 chains at wide passes.  A run with one live block is the run's Q4_K twin with
+ * dmin = -m and sc = mn = 1 on that sub-block (Q5_1 with high bits: its Q5_K twin); a block with m = +-0 is its Q8_0 twin.
+ */
+struct OpsQ81 { v4i b[4]; float d[8], m[8]; };
+#define TK_ONES8 0x0101010101010101L /* the B operand of S_j, one 32-block: eight int8 ones per lane */
+
+__device__ __forceinline__ void unpack_q41(const FragQ41& f, OpsQ81& o) {
+    const uint32_t qs[8] = {f.q0.x, f.q0.y, f.q0.z, f.q0.w, f.q1.x, f.q1.y, f.q1.z, f.q1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        o.b[j >> 1][2 * (j & 1)] = (int)(qs[j] & 0x0F0F0F0Fu);
+        o.b[j >> 1][2 * (j & 1) + 1] = (int)((qs[j] >> 4) & 0x0F0F0F0Fu);
+    }
+    q32_scales(f.d, o.d);
+    q32_scales(f.m, o.m);
+}
+
+__device__ __forceinline__ void unpack_q41(const FragQ51& f, OpsQ81& o) {
+    const uint32_t qs[8] = {f.q0.x, f.q0.y, f.q0.z, f.q0.w, f.q1.x, f.q1.y, f.q1.z, f.q1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t w = j < 4 ? f.qh.x : f.qh.y;
+        o.b[j >> 1][2 * (j & 1)] = (int)q5_lo(qs[j], w, j & 3);
+        o.b[j >> 1][2 * (j & 1) + 1] = (int)q5_hi(qs[j], w, j & 3);
+    }
+    q32_scales(f.d, o.d);
+    q32_scales(f.m, o.m);
+}
+/* the tile of a launch whose TYPES is the mask of Q4_1 or Q5_1 alone (any other TYPES: Q4_1's, unused) */
+template <int TYPES> struct TileQ41Of { typedef TileQ41 type; };
+template <> struct TileQ41Of<tk_type_desc_of(TK_TYPE_Q5_1).mask> { typedef TileQ51 type; };
+constexpr bool tk_types_only41(int types) { return tk_types_is(types, TK_TYPE_Q4_1) || tk_types_is(types, TK_TYPE_Q5_1); }
+
+/* mma_q8 with the min term: per 32-block the product MFMA and, on the same A operand, the sum MFMA against all ones.  Two blocks (one
+ * 16-byte A read per M-tile) form a group; the MFMAs of group j2 + 1 are issued before group j2 is finished on the VALU and no further
+ * ahead, so two groups of results are live — the register set of mma_q8, which lets all eight products of a tile run ahead */
+template <int MT>
+__device__ __forceinline__ void mma_q81(const OpsQ81& o, const uint8_t* lds_act, const float* lds_ad, size_t act_ts, int ad_ts, int blk, int lane,
+                                        float (*acc)[4]) {
+    const int g = lane >> 4;
+    const v4i zero = {0, 0, 0, 0};
+    const uint8_t* ap = lds_act + (size_t)blk * 4096 + lane * 16;
+    v4f da[MT];
+    v4i a[4][MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) da[m] = *(const v4f*)(lds_ad + m * ad_ts + blk * TK_ROW_SLOTS + 4 * g);
+#pragma unroll
+    for (int j2 = 0; j2 < 4; ++j2)
+#pragma unroll
+        for (int m = 0; m < MT; ++m) a[j2][m] = *(const v4i*)(ap + m * act_ts + j2 * 1024);
+    v4i P[MT][2], S[MT][2];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            P[m][e] = __builtin_amdgcn_mfma_i32_16x16x32_i8(half_of(a[0][m], e), half_of(o.b[0], e), zero, 0, 0, 0);
+            S[m][e] = __builtin_amdgcn_mfma_i32_16x16x32_i8(half_of(a[0][m], e), TK_ONES8, zero, 0, 0, 0);
+        }
+#pragma unroll
+    for (int j2 = 0; j2 < 4; ++j2) {
+        v4i Q[MT][2], QS[MT][2];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                Q[m][e] = P[m][e];
+                QS[m][e] = S[m][e];
+                if (j2 + 1 < 4) {
+                    P[m][e] = __builtin_amdgcn_mfma_i32_16x16x32_i8(half_of(a[j2 + 1][m], e), half_of(o.b[j2 + 1], e), zero, 0, 0, 0);
+                    S[m][e] = __builtin_amdgcn_mfma_i32_16x16x32_i8(half_of(a[j2 + 1][m], e), TK_ONES8, zero, 0, 0, 0);
+                }
+            }
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    acc[m][r] = tk_fmaf(o.d[2 * j2 + e] * da[m][r], (float)Q[m][e][r], acc[m][r]);
+                    acc[m][r] = tk_fmaf(o.m[2 * j2 + e] * da[m][r], (float)QS[m][e][r], acc[m][r]);
+                }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 size_t tk_gemv_lds_bytes(int K, int ks, int mtiles) {
     size_t Kr = (size_t)K / ks;
     return (size_t)mtiles * (Kr * TK_ROW_SLOTS + (Kr / 256) * TK_ROW_SLOTS * 4 + (Kr / 256) * 256);
@@ -1308,6 +1502,8 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
     constexpr bool ONLY32 = tk_types_only32(TYPES);
     typedef typename TileQ32Of<TYPES>::type TileQ32;
+    constexpr bool ONLY41 = tk_types_only41(TYPES);
+    typedef typename TileQ41Of<TYPES>::type TileQ41x;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     TileQ4::Frag f4[HAS4 ? PF : 1];
     TileQ6::Frag f6[HAS6 ? PF : 1];
@@ -1316,6 +1512,7 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     TileQ2::Frag f2[ONLY2 ? PF : 1];
     TileQ8::Frag f8[ONLY8 ? PF : 1];
     typename TileQ32::Frag f32[ONLY32 ? PF : 1];
+    typename TileQ41x::Frag f41[ONLY41 ? PF : 1];
     if constexpr (ONLY8) {
 #pragma unroll
         for (int u = 0; u < PF; ++u) f8[u] = TileQ8::load(tile + (size_t)u * tile_bytes, lane);
@@ -1323,6 +1520,10 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     if constexpr (ONLY32) {
 #pragma unroll
         for (int u = 0; u < PF; ++u) f32[u] = TileQ32::load(tile + (size_t)u * tile_bytes, lane);
+    }
+    if constexpr (ONLY41) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) f41[u] = TileQ41x::load(tile + (size_t)u * tile_bytes, lane);
     }
     if constexpr (ONLY3) {
 #pragma unroll
@@ -1636,6 +1837,35 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
+    if constexpr (ONLY41) { /* Q4_1 / Q5_1: the same loop in front of the chain with the min term */
+        const uint8_t* tp = tile + PF * tile_bytes;
+#pragma unroll 1
+        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                OpsQ81 o;
+                __builtin_amdgcn_sched_barrier(0);
+                unpack_q41(f41[u], o);
+                __builtin_amdgcn_sched_barrier(0);
+                f41[u] = TileQ41x::load(tp + u * tile_bytes, lane);
+                __builtin_amdgcn_sched_barrier(0);
+                mma_q81<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            OpsQ81 o;
+            __builtin_amdgcn_sched_barrier(0);
+            unpack_q41(f41[u], o);
+            mma_q81<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
+        }
+        /* the results are read under `row < nrows` only, and the compiler sinks the last tiles' finishing into that branch, behind all of
+         * their MFMAs: with twice the results of a Q8_0 tile alive that spills at PF = MT = 2.  An opaque use keeps it where it is written */
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(acc[m][r]));
+    }
 
     const int n = a.col0 + row_base + rt * TK_TILE_ROWS + (lane & 15);
     const int g = lane >> 4;
@@ -1855,6 +2085,56 @@ __device__ __forceinline__ void gemm_block_q8(const OpsQ8& o, const uint8_t* chu
 #undef TK_LDS_TILE
 }
 
+/* gemm_block_q8 with the min term: per 32-block the product MFMA and, on the same A operand, the sum MFMA against all ones.  The unit of
+ * the pipeline is half an M-tile — four blocks, eight MFMAs, the result registers of gemm_block_q8's whole tile —: the finished half's two
+ * FMAs per block and output run while the next half's MFMAs are in the pipe.  Same ring, same look-ahead of the LDS reads, same rot */
+struct PTile81 { v4i p[4], s[4]; v4f da; };
+__device__ __forceinline__ void finish_half_q81(const PTile81& R, const OpsQ81& o, int h, float* acc) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            acc[r] = tk_fmaf(o.d[4 * h + j] * R.da[r], (float)R.p[j][r], acc[r]);
+            acc[r] = tk_fmaf(o.m[4 * h + j] * R.da[r], (float)R.s[j][r], acc[r]);
+        }
+}
+template <int MT>
+__device__ __forceinline__ void gemm_block_q81(const OpsQ81& o, const uint8_t* chunk, int rot, int lane, float (&acc)[MT][4]) {
+    constexpr int OFF_AMN = MT * 4096, OFF_AD = MT * 4096 + MT * 512;
+    const v4i zero = {0, 0, 0, 0};
+    constexpr int AD = 2;
+    ATile T[AD + 1];
+    PTile81 R;
+    const uint8_t* act[2] = {chunk + rot * 4096, chunk - rot * 4096};
+    const uint8_t* adp[2] = {chunk + OFF_AD + rot * 64, chunk + OFF_AD - rot * 64};
+#define TK_LDS_TILE(slot, m) lds_tile<false>(T[slot], act[(m) >= MT / 2] + (m) * 4096, chunk + OFF_AMN, adp[(m) >= MT / 2] + (m) * 64, lane)
+#pragma unroll
+    for (int m = 0; m < AD && m < MT; ++m) TK_LDS_TILE(m, m);
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        if (m + AD < MT) TK_LDS_TILE((m + AD) % (AD + 1), m + AD);
+        __builtin_amdgcn_sched_barrier(0);
+        const ATile& t = T[m % (AD + 1)];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            PTile81 c;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int jj = 4 * h + j;
+                c.p[j] = __builtin_amdgcn_mfma_i32_16x16x32_i8(half_of(t.a[jj >> 1], jj & 1), half_of(o.b[jj >> 1], jj & 1), zero, 0, 0, 0);
+                c.s[j] = __builtin_amdgcn_mfma_i32_16x16x32_i8(half_of(t.a[jj >> 1], jj & 1), TK_ONES8, zero, 0, 0, 0);
+            }
+            c.da = t.da;
+            if (h == 1) finish_half_q81(R, o, 0, acc[m]);
+            else if (m > 0) finish_half_q81(R, o, 1, acc[m - 1]);
+            R = c;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    finish_half_q81(R, o, 1, acc[MT - 1]);
+#undef TK_LDS_TILE
+}
+
 /* One weight tile per wave (two adjacent tiles per wave halve the LDS operand stream but leave one wave per SIMD: 25 % slower on MI355X,
  * profiles/r01_gemm_batched.txt).  NT and CB are that choice and the ring's one block per slot as constants: the loops over them stay in
  * the source because folding them by hand changes the compiler's schedule of this kernel (k_gemm_w4a8<12, 3> then spills). */
@@ -1889,6 +2169,8 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
     constexpr bool ONLY32 = tk_types_only32(TYPES);
     typedef typename TileQ32Of<TYPES>::type TileQ32;
+    constexpr bool ONLY41 = tk_types_only41(TYPES);
+    typedef typename TileQ41Of<TYPES>::type TileQ41x;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     const size_t tile_bytes = types_tile_bytes<TYPES>(is4);
     const size_t tile_pitch = (size_t)nblk_total * tile_bytes; /* to the same block of the next row tile */
@@ -1934,6 +2216,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     TileQ2::Frag f2[ONLY2 ? NT : 1];
     TileQ8::Frag f8[ONLY8 ? NT : 1];
     typename TileQ32::Frag f32[ONLY32 ? NT : 1];
+    typename TileQ41x::Frag f41[ONLY41 ? NT : 1];
     if (active) {
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
@@ -1944,6 +2227,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             if constexpr (ONLY2) f2[w] = TileQ2::load(tile + w * tile_pitch, lane);
             if constexpr (ONLY8) f8[w] = TileQ8::load(tile + w * tile_pitch, lane);
             if constexpr (ONLY32) f32[w] = TileQ32::load(tile + w * tile_pitch, lane);
+            if constexpr (ONLY41) f41[w] = TileQ41x::load(tile + w * tile_pitch, lane);
         }
     }
     for (int i = 0; i < CB && i < nb; ++i) stage(i, i);
@@ -2026,6 +2310,17 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int w = 0; w < NT; ++w) gemm_block_q8<MT>(o8[w], chunk, rot, lane, acc[w]);
+        }
+        if constexpr (ONLY41) {
+            OpsQ81 o8[NT];
+#pragma unroll
+            for (int w = 0; w < NT; ++w) unpack_q41(f41[w], o8[w]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NT; ++w) f41[w] = TileQ41x::load(next + w * tile_pitch, lane);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NT; ++w) gemm_block_q81<MT>(o8[w], chunk, rot, lane, acc[w]);
         }
     }
     if (!active) return;
@@ -2287,6 +2582,40 @@ __device__ __forceinline__ void unpack_q32_x32(const FragIQ4XS& f0, const FragIQ
     iq4_operands_x32(f0, f1, o);
     iq4xs_scales(up ? f1.d : f0.d, o.d);
 }
+/* Q4_1 / Q5_1 on the 32x32x32 map: the lane swap of the Q4_0 / Q5_0 form; the unsigned q is the operand byte as it stands */
+struct Ops32Q81 { v4i b[8]; float d[8], m[8]; };
+__device__ __forceinline__ void unpack_q41_x32(const FragQ41& f0, const FragQ41& f1, int lane, Ops32Q81& o) {
+    const bool up = (lane & 16) != 0;
+    const uint32_t q0[8] = {f0.q0.x, f0.q0.y, f0.q0.z, f0.q0.w, f0.q1.x, f0.q1.y, f0.q1.z, f0.q1.w};
+    const uint32_t q1[8] = {f1.q0.x, f1.q0.y, f1.q0.z, f1.q0.w, f1.q1.x, f1.q1.y, f1.q1.z, f1.q1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        uint32_t s[2];
+        pair_swap(q0[j], q1[j], &s[0], &s[1]);
+        o.b[j] = (v4i){(int)(s[0] & 0x0F0F0F0Fu), (int)((s[0] >> 4) & 0x0F0F0F0Fu), (int)(s[1] & 0x0F0F0F0Fu), (int)((s[1] >> 4) & 0x0F0F0F0Fu)};
+    }
+    q32_scales(up ? f1.d : f0.d, o.d);
+    q32_scales(up ? f1.m : f0.m, o.m);
+}
+__device__ __forceinline__ void unpack_q41_x32(const FragQ51& f0, const FragQ51& f1, int lane, Ops32Q81& o) {
+    const bool up = (lane & 16) != 0;
+    const uint32_t q0[8] = {f0.q0.x, f0.q0.y, f0.q0.z, f0.q0.w, f0.q1.x, f0.q1.y, f0.q1.z, f0.q1.w};
+    const uint32_t q1[8] = {f1.q0.x, f1.q0.y, f1.q0.z, f1.q0.w, f1.q1.x, f1.q1.y, f1.q1.z, f1.q1.w};
+    uint32_t H[2][2];
+    pair_swap(f0.qh.x, f1.qh.x, &H[0][0], &H[0][1]);
+    pair_swap(f0.qh.y, f1.qh.y, &H[1][0], &H[1][1]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        uint32_t s[2];
+        pair_swap(q0[j], q1[j], &s[0], &s[1]);
+        o.b[j] = (v4i){(int)q5_lo(s[0], H[j >> 2][0], j & 3), (int)q5_hi(s[0], H[j >> 2][0], j & 3),
+                       (int)q5_lo(s[1], H[j >> 2][1], j & 3), (int)q5_hi(s[1], H[j >> 2][1], j & 3)};
+    }
+    q32_scales(up ? f1.d : f0.d, o.d);
+    q32_scales(up ? f1.m : f0.m, o.m);
+}
+/* the types that run the chains with the min term (gemm_block32_q81); they read the A operand as the Q8_0 chains do */
+constexpr bool tk_is_q41(int qt) { return qt == TK_TYPE_Q4_1 || qt == TK_TYPE_Q5_1; }
 /* the types that run the Q8_0 chains: one K = 32 MFMA and one scale per 32-block */
 constexpr bool tk_is_q32(int qt) { return qt == TK_TYPE_Q8_0 || qt == TK_TYPE_Q4_0 || qt == TK_TYPE_Q5_0 || qt == TK_TYPE_IQ4_NL || qt == TK_TYPE_IQ4_XS; }
 template <int QT> struct G32Ops { typedef struct Ops32 type; };
@@ -2295,6 +2624,8 @@ template <> struct G32Ops<TK_TYPE_Q4_0> { typedef Ops32Q8 type; };
 template <> struct G32Ops<TK_TYPE_Q5_0> { typedef Ops32Q8 type; };
 template <> struct G32Ops<TK_TYPE_IQ4_NL> { typedef Ops32Q8 type; };
 template <> struct G32Ops<TK_TYPE_IQ4_XS> { typedef Ops32Q8 type; };
+template <> struct G32Ops<TK_TYPE_Q4_1> { typedef Ops32Q81 type; };
+template <> struct G32Ops<TK_TYPE_Q5_1> { typedef Ops32Q81 type; };
 
 /* s_waitcnt vmcnt(n) alone (expcnt / lgkmcnt untouched): until all but this wave's n youngest vector-memory operations are done.  The
  * LDS-DMA pieces of a chunk are invisible to the compiler's own wait insertion, so the ring is guarded by hand. */
@@ -2338,7 +2669,7 @@ __device__ __forceinline__ v4i q8_a32(const Ptrs32& p, int t, int j) {
 
 template <int QT>
 __device__ __forceinline__ void load_atile32(ATile32& T, const Ptrs32& p, int t) {
-    if constexpr (tk_is_q32(QT)) {
+    if constexpr (tk_is_q32(QT) || tk_is_q41(QT)) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) T.a[j] = q8_a32(p, t, j);
         return;
@@ -2439,6 +2770,49 @@ __device__ __forceinline__ void gemm_block32_q8(const Ops32Q8& o, ATile32& T, co
     }
 }
 
+/* gemm_block32_q8 with the min term.  The product and the sum MFMA of the blocks alternate in the pipe — P_0, S_0, P_1, S_1, ... — and each
+ * result is finished while the next one runs: block j's fma on P_j under S_j, its fma on S_j under P_(j+1).  Two result sets live, as in
+ * gemm_block32_q8, and per output the contract's order: P_j, then S_j, blocks ascending */
+template <typename Hook>
+__device__ __forceinline__ void gemm_block32_q81(const Ops32Q81& o, ATile32& T, const Ptrs32& p, float (&acc)[TK_G32_MTW][16], Hook&& after_mfmas) {
+    const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
+#pragma unroll
+    for (int t = 0; t < TK_G32_MTW; ++t) {
+        v4i A[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) A[j] = T.a[j];
+        v4f da[4];
+#pragma unroll
+        for (int j = 4; j < 8; ++j) A[j] = q8_a32(p, t, j);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) da[b] = *(const v4f*)(p.dp + t * 128 + b * 32);
+        v16i X = TK_MFMA32(A[0], o.b[0], zero, 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const v16i Q = X;
+            X = TK_MFMA32(A[j], ones, zero, 0, 0, 0);
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[t][4 * b + i] = tk_fmaf(o.d[j] * da[b][i], (float)Q[4 * b + i], acc[t][4 * b + i]);
+            const v16i QS = X;
+            if (j + 1 < 8) X = TK_MFMA32(A[j + 1], o.b[j + 1], zero, 0, 0, 0);
+            if (j == 6) { /* every MFMA of the tile but the last sum has issued: the next tile's first reads, and a quarter of the ring staging */
+                __builtin_amdgcn_sched_barrier(0);
+                if (t + 1 < TK_G32_MTW) load_atile32<TK_TYPE_Q4_1>(T, p, t + 1);
+                after_mfmas(t);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[t][4 * b + i] = tk_fmaf(o.m[j] * da[b][i], (float)QS[4 * b + i], acc[t][4 * b + i]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 /* `tile` is wave-uniform (an SGPR pair); the per-lane offsets are 32-bit and opaque per call, so the loads take the scalar-base form and no
  * 64-bit per-lane address is hoisted out of the K loop and held across it (load_q4 / load_q6 with a lane pointer cost 12 registers there) */
 template <int QT>
@@ -2456,6 +2830,22 @@ __device__ __forceinline__ typename TkTile<QT>::Frag g32_load(const uint8_t* til
         f.q0 = ldg_nt(tile + lo);
         f.q1 = ldg_nt(tile + 1024 + lo);
         f.d = ldg_nt(tile + 2048 + ho);
+        return f;
+    } else if constexpr (QT == TK_TYPE_Q4_1) {
+        FragQ41 f;
+        f.q0 = ldg_nt(tile + lo);
+        f.q1 = ldg_nt(tile + 1024 + lo);
+        f.d = ldg_nt(tile + 2048 + 2 * ho);
+        f.m = ldg_nt(tile + 2064 + 2 * ho);
+        return f;
+    } else if constexpr (QT == TK_TYPE_Q5_1) {
+        FragQ51 f;
+        f.q0 = ldg_nt(tile + lo);
+        f.q1 = ldg_nt(tile + 1024 + lo);
+        const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + (lo >> 1)));
+        f.qh = make_uint2(qh.x, qh.y);
+        f.d = ldg_nt(tile + 2560 + 2 * ho);
+        f.m = ldg_nt(tile + 2576 + 2 * ho);
         return f;
     } else if constexpr (QT == TK_TYPE_Q5_0) {
         FragQ50 f;
@@ -2509,6 +2899,7 @@ template <int QT>
 __device__ __forceinline__ void g32_unpack(const typename TkTile<QT>::Frag& f0, const typename TkTile<QT>::Frag& f1, int lane, typename G32Ops<QT>::type& o) {
     if constexpr (QT == TK_TYPE_Q8_0) unpack_q8_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q4_0 || QT == TK_TYPE_Q5_0 || QT == TK_TYPE_IQ4_NL || QT == TK_TYPE_IQ4_XS) unpack_q32_x32(f0, f1, lane, o);
+    else if constexpr (tk_is_q41(QT)) unpack_q41_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q4_K) unpack_q4_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q3_K) unpack_q3_x32(f0, f1, lane, o);
@@ -2554,6 +2945,7 @@ __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_byte
         /* the last block restages itself into the slot nobody reads any more: no branch around the DMA issue */
         /* the ring's four staging parts ride on the tiles' MFMA phases: one per tile */
         if constexpr (tk_is_q32(QT)) gemm_block32_q8(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
+        else if constexpr (tk_is_q41(QT)) gemm_block32_q81(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
         else gemm_block32<QT>(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -2674,6 +3066,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     if constexpr (tk_types_is(TYPES, TK_TYPE_Q5_0)) g32_k_loop<TK_TYPE_Q5_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (tk_types_is(TYPES, TK_TYPE_IQ4_NL)) g32_k_loop<TK_TYPE_IQ4_NL>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (tk_types_is(TYPES, TK_TYPE_IQ4_XS)) g32_k_loop<TK_TYPE_IQ4_XS>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (tk_types_is(TYPES, TK_TYPE_Q4_1)) g32_k_loop<TK_TYPE_Q4_1>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (tk_types_is(TYPES, TK_TYPE_Q5_1)) g32_k_loop<TK_TYPE_Q5_1>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -2751,27 +3145,27 @@ typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
 /* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone.  Type index =
  * the type's kernel_index (tk_type_desc_of), TK_KERNEL_INDEX_Q4K_Q6K for the mix; the static_asserts below hold every column to it */
 static const TkGemvKernel k_gemv_fns[3][2][2][TK_KERNEL_VARIANTS] = {
-    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>, k_gemv_w4a8<1, 1, 32, 0>, k_gemv_w4a8<1, 1, 64, 0>, k_gemv_w4a8<1, 1, 128, 0>, k_gemv_w4a8<1, 1, 256, 0>, k_gemv_w4a8<1, 1, 512, 0>},
-      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>, k_gemv_w4a8<2, 1, 32, 0>, k_gemv_w4a8<2, 1, 64, 0>, k_gemv_w4a8<2, 1, 128, 0>, k_gemv_w4a8<2, 1, 256, 0>, k_gemv_w4a8<2, 1, 512, 0>}},
-     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>, k_gemv_w4a8<1, 2, 32, 0>, k_gemv_w4a8<1, 2, 64, 0>, k_gemv_w4a8<1, 2, 128, 0>, k_gemv_w4a8<1, 2, 256, 0>, k_gemv_w4a8<1, 2, 512, 0>},
-      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>, k_gemv_w4a8<2, 2, 32, 0>, k_gemv_w4a8<2, 2, 64, 0>, k_gemv_w4a8<2, 2, 128, 0>, k_gemv_w4a8<2, 2, 256, 0>, k_gemv_w4a8<2, 2, 512, 0>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>, k_gemv_w4a8<2, 1, 32, 1>, k_gemv_w4a8<2, 1, 64, 1>, k_gemv_w4a8<2, 1, 128, 1>, k_gemv_w4a8<2, 1, 256, 1>, k_gemv_w4a8<2, 1, 512, 1>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>, k_gemv_w4a8<2, 1, 32, 2>, k_gemv_w4a8<2, 1, 64, 2>, k_gemv_w4a8<2, 1, 128, 2>, k_gemv_w4a8<2, 1, 256, 2>, k_gemv_w4a8<2, 1, 512, 2>}}},
+    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>, k_gemv_w4a8<1, 1, 32, 0>, k_gemv_w4a8<1, 1, 64, 0>, k_gemv_w4a8<1, 1, 128, 0>, k_gemv_w4a8<1, 1, 256, 0>, k_gemv_w4a8<1, 1, 512, 0>, k_gemv_w4a8<1, 1, 1024, 0>, k_gemv_w4a8<1, 1, 2048, 0>},
+      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>, k_gemv_w4a8<2, 1, 32, 0>, k_gemv_w4a8<2, 1, 64, 0>, k_gemv_w4a8<2, 1, 128, 0>, k_gemv_w4a8<2, 1, 256, 0>, k_gemv_w4a8<2, 1, 512, 0>, k_gemv_w4a8<2, 1, 1024, 0>, k_gemv_w4a8<2, 1, 2048, 0>}},
+     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>, k_gemv_w4a8<1, 2, 32, 0>, k_gemv_w4a8<1, 2, 64, 0>, k_gemv_w4a8<1, 2, 128, 0>, k_gemv_w4a8<1, 2, 256, 0>, k_gemv_w4a8<1, 2, 512, 0>, k_gemv_w4a8<1, 2, 1024, 0>, k_gemv_w4a8<1, 2, 2048, 0>},
+      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>, k_gemv_w4a8<2, 2, 32, 0>, k_gemv_w4a8<2, 2, 64, 0>, k_gemv_w4a8<2, 2, 128, 0>, k_gemv_w4a8<2, 2, 256, 0>, k_gemv_w4a8<2, 2, 512, 0>, k_gemv_w4a8<2, 2, 1024, 0>, k_gemv_w4a8<2, 2, 2048, 0>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>, k_gemv_w4a8<2, 1, 32, 1>, k_gemv_w4a8<2, 1, 64, 1>, k_gemv_w4a8<2, 1, 128, 1>, k_gemv_w4a8<2, 1, 256, 1>, k_gemv_w4a8<2, 1, 512, 1>, k_gemv_w4a8<2, 1, 1024, 1>, k_gemv_w4a8<2, 1, 2048, 1>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>, k_gemv_w4a8<2, 1, 32, 2>, k_gemv_w4a8<2, 1, 64, 2>, k_gemv_w4a8<2, 1, 128, 2>, k_gemv_w4a8<2, 1, 256, 2>, k_gemv_w4a8<2, 1, 512, 2>, k_gemv_w4a8<2, 1, 1024, 2>, k_gemv_w4a8<2, 1, 2048, 2>}}},
 };
 /* [mt / 2 - 2][type index] */
 static const TkGemvKernel k_gemm_fns[5][TK_KERNEL_VARIANTS] = {
-    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>, k_gemm_w4a8<4, 32>, k_gemm_w4a8<4, 64>, k_gemm_w4a8<4, 128>, k_gemm_w4a8<4, 256>, k_gemm_w4a8<4, 512>},
-    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>, k_gemm_w4a8<6, 32>, k_gemm_w4a8<6, 64>, k_gemm_w4a8<6, 128>, k_gemm_w4a8<6, 256>, k_gemm_w4a8<6, 512>},
-    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>, k_gemm_w4a8<8, 32>, k_gemm_w4a8<8, 64>, k_gemm_w4a8<8, 128>, k_gemm_w4a8<8, 256>, k_gemm_w4a8<8, 512>},
-    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>, k_gemm_w4a8<10, 32>, k_gemm_w4a8<10, 64>, k_gemm_w4a8<10, 128>, k_gemm_w4a8<10, 256>, k_gemm_w4a8<10, 512>},
-    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>, k_gemm_w4a8<12, 32>, k_gemm_w4a8<12, 64>, k_gemm_w4a8<12, 128>, k_gemm_w4a8<12, 256>, k_gemm_w4a8<12, 512>},
+    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>, k_gemm_w4a8<4, 32>, k_gemm_w4a8<4, 64>, k_gemm_w4a8<4, 128>, k_gemm_w4a8<4, 256>, k_gemm_w4a8<4, 512>, k_gemm_w4a8<4, 1024>, k_gemm_w4a8<4, 2048>},
+    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>, k_gemm_w4a8<6, 32>, k_gemm_w4a8<6, 64>, k_gemm_w4a8<6, 128>, k_gemm_w4a8<6, 256>, k_gemm_w4a8<6, 512>, k_gemm_w4a8<6, 1024>, k_gemm_w4a8<6, 2048>},
+    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>, k_gemm_w4a8<8, 32>, k_gemm_w4a8<8, 64>, k_gemm_w4a8<8, 128>, k_gemm_w4a8<8, 256>, k_gemm_w4a8<8, 512>, k_gemm_w4a8<8, 1024>, k_gemm_w4a8<8, 2048>},
+    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>, k_gemm_w4a8<10, 32>, k_gemm_w4a8<10, 64>, k_gemm_w4a8<10, 128>, k_gemm_w4a8<10, 256>, k_gemm_w4a8<10, 512>, k_gemm_w4a8<10, 1024>, k_gemm_w4a8<10, 2048>},
+    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>, k_gemm_w4a8<12, 32>, k_gemm_w4a8<12, 64>, k_gemm_w4a8<12, 128>, k_gemm_w4a8<12, 256>, k_gemm_w4a8<12, 512>, k_gemm_w4a8<12, 1024>, k_gemm_w4a8<12, 2048>},
 };
 /* [type index] */
-static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>, k_gemm32_w4a8<32>, k_gemm32_w4a8<64>, k_gemm32_w4a8<128>, k_gemm32_w4a8<256>, k_gemm32_w4a8<512>};
+static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>, k_gemm32_w4a8<32>, k_gemm32_w4a8<64>, k_gemm32_w4a8<128>, k_gemm32_w4a8<256>, k_gemm32_w4a8<512>, k_gemm32_w4a8<1024>, k_gemm32_w4a8<2048>};
 
 /* column c of the three tables holds the kernels of TYPES = tk_column_types[c]: every type's mask at its kernel_index */
 constexpr bool tk_columns_match_the_type_table() {
-    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16, 32, 64, 128, 256, 512};
+    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048};
     for (int i = 0; i < TK_TILED_TYPES; ++i)
         if (tk_column_types[tk_type_desc_of(tk_tiled_type(i)).kernel_index] != tk_type_desc_of(tk_tiled_type(i)).mask) return false;
     return tk_column_types[TK_KERNEL_INDEX_Q4K_Q6K] == TK_TYPES_Q4K_Q6K;

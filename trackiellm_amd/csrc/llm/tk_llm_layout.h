@@ -2,7 +2,7 @@
  * tk_llm_layout.h — HBM layouts of the MI355X LLM path.
  *
  * GGUF k-quant blocks are kept bit-for-bit (the same quantised values, and the file's bytes per 256 weights
- * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked; Q8_0 / Q4_0 / Q5_0 / IQ4_NL: eight 34- / 18- / 22- / 18-byte blocks per 256 weights; IQ4_XS: its scales unpacked too) but re-tiled at load time so that one wavefront's 16-byte-per-lane
+ * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked; Q8_0 / Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1: eight 34- / 18- / 22- / 18- / 20- / 24-byte blocks per 256 weights; IQ4_XS: its scales unpacked too) but re-tiled at load time so that one wavefront's 16-byte-per-lane
  * load is a contiguous 1 KiB run that already IS an MFMA operand:
  *
  *  Weight tile = 16 weight rows x 256 k (one super-block column).  Lane l = (n = l & 15, g = l >> 4)
@@ -43,6 +43,14 @@
  *  The kernels turn a masked nibble dword (plus the high bits at bit 4) into int8 q - 8 / q - 16 with one add and one xor,
  *  (x + 0x78787878) ^ 0x80808080 / (x + 0x70707070) ^ 0x80808080: no byte carries (0x78 + 15 and 0x70 + 31 stay below 0x100), and the
  *  result is the B operand the Q8_0 chains take.
+ *  Q4_1 tile (2560 B = 16 x 160 = 16 rows x eight 20-byte blocks): the stored q (0..15, w = d q + m), unsigned as it goes into the int8 operand
+ *      [0    ,2048)  the two nibble loads of the Q4_0 tile
+ *      [2048 ,2560)  16 rows x 32 B: row n's eight f16 d in block order, then its eight f16 m: two 16-byte reads per lane
+ *  Q5_1 tile (3072 B = 16 x 192 = 16 rows x eight 24-byte blocks): the stored q (0..31, w = d q + m)
+ *      [0    ,2560)  the nibble loads and the high bits of the Q5_0 tile
+ *      [2560 ,3072)  16 rows x 32 B: eight d, then eight m, as the Q4_1 tile's tail
+ *  Neither needs an offset: the nibble dword (plus the high bits at bit 4) IS the B operand.  The min term m_j * sum_k a_k takes the
+ *  block's activation sum from the matrix pipe (the A operand against an all-ones B), in the accumulator layout of P_j.
  *  IQ4_NL tile (2304 B): the Q4_0 tile byte for byte (same repack kernel, fragment and load); the nibble is a code-book index
  *  IQ4_XS tile (2304 B = 16 x 144; the block has 136 B): a 256-weight block of 16 rows
  *      [0    ,2048)  the two nibble loads of the Q4_0 tile with sub-block j in place of 32-block j
@@ -103,6 +111,8 @@
 #define TK_Q5_0_TILE_BYTES 2816
 #define TK_IQ4_NL_TILE_BYTES TK_Q4_0_TILE_BYTES
 #define TK_IQ4_XS_TILE_BYTES 2304
+#define TK_Q4_1_TILE_BYTES 2560
+#define TK_Q5_1_TILE_BYTES 3072
 #define TK_ROW_SLOTS 16  /* rows of one MFMA M-tile */
 #define TK_MAX_TILES 16   /* M-tiles per pass: a weight tile is unpacked once and multiplied against all of them */
 #define TK_MAX_ROWS (TK_ROW_SLOTS * TK_MAX_TILES)
