@@ -38,6 +38,25 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_fill_synthetic(tk_mi355x
  * on the exact fp32 MFMA GEMM over f16-rounded activations (one k-ordered chain per output, no K-split): results stay bit-identical to
  * the oracle.  Loader name: synthetic://mistral-7b-f16, synthetic://tiny-f16; GGUF files with F16 tensors load the same way. */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_fill_synthetic_f16(tk_mi355x_llm_model_t* m, uint64_t seed);
+/* the same recipe in the other two float types: ggml_type 30 (BF16: every matrix and the token embedding bfloat16, the seeded values stored through
+ * tk_mi355x_convert_bf16's rounding) or 0 (F32: stored unconverted); norms f32.  Any other value: TK_ERROR_INVALID_ARGUMENT.  The matrices run on the
+ * same exact fp32 MFMA GEMM: a BF16 weight is its bits << 16 and the activations are rounded to bf16 (ggml's vec_dot_type for BF16), an F32 weight
+ * is used as stored against unrounded activations; per K-split slab one fmaf chain over k ascending from +0, the slabs added in ascending order.
+ * Loader names: synthetic://mistral-7b-bf16, synthetic://tiny-bf16, synthetic://mistral-7b-f32, synthetic://tiny-f32; GGUF files with BF16 / F32
+ * matrices (convert_hf_to_gguf.py --outtype bf16 | f32) load the same way.  Among a model's matrices (layer matrices and output) at most ONE of F16 /
+ * BF16 / F32 may occur, beside any mix of quantised types: a second float type fails the load (set_tensor, load_gguf, session_create) with a message
+ * naming both.  token_embd is free of that rule. */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_fill_synthetic_float(tk_mi355x_llm_model_t* m, uint64_t seed, int ggml_type);
+/* no GPU: the build's float -> bfloat16 rounding (ggml_compute_fp32_to_bf16: nearest even on the bits, subnormals kept, 0x7f7f8000 -> +inf, a NaN
+ * becomes (bits >> 16) | 64), the one function host and kernels share; x [n] -> out [n] */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_convert_bf16(const float* x, int64_t n, uint16_t* out);
+/* test / measurement entry: one production float matmul.  w [rows][K]: row-major values of `type` (1 F16, 30 BF16: uint16 bits; 0 F32), rows = the sum
+ * of nseg (1 .. 3) segments of seg_rows[i] rows (each % 16 == 0), every segment tiled as a matrix of its own, as a model's q | k | v are; x [nrows][K]
+ * (nrows <= 256; K % (256 ks) == 0, ks <= 8, rows <= 65536, rows x K <= 2^26) goes through the production operand-image producer with the type's rounding; ONE production launch with the
+ * segments side by side and K split ks ways; the ks slabs added in ascending order into y [nrows][rows].  Other types: TK_ERROR_INVALID_ARGUMENT
+ * (tk_mi355x_llm_gemv_probe keeps its own set) */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_matmul_float_probe(int device, int type, const void* w, int64_t rows, int64_t K, int ks, int nseg,
+                                                                     const int32_t seg_rows[3], int nrows, const float* x, float* y);
 /* the seeded weights of fill_synthetic under llama.cpp's k-quant mix `ftype`: 10 Q2_K (every matrix and token_embd Q2_K; attn_v Q4_K when
  * n_head / n_kv_head >= 4, else Q3_K; attn_output and ffn_down Q3_K), 21 Q2_K_S (Q2_K; attn_v Q4_K when n_head / n_kv_head >= 4; ffn_down Q4_K
  * for layers < n_layer / 8) — this build's definition of the two, files load by each tensor's own type regardless —, 11 Q3_K_S (every matrix and token_embd Q3_K), 12 Q3_K_M (Q3_K;
@@ -45,7 +64,7 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_fill_synthetic_f16(tk_mi
  * attn_v of layers < 4 and ffn_down of layers < n_layer / 8), 15 Q4_K_M (= fill_synthetic), 16 Q5_K_S (every matrix and token_embd Q5_K),
  * 17 Q5_K_M (Q4_K_M with Q5_K in place of Q4_K); output is Q6_K in all eight; 7 Q8_0 (every matrix, token_embd and output Q8_0); 2 Q4_0, 8 Q5_0, 25 IQ4_NL and 30 IQ4_XS (every layer matrix and token_embd in the base type, output Q6_K).  Other values: TK_ERROR_INVALID_ARGUMENT — among them 13 Q3_K_L
  * (Q3_K with Q5_K attn_v, attn_output and ffn_down), which has no synthetic recipe; Q3_K_L FILES load all the same, since loading goes by
- * each tensor's own type and any mix of Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_NL / IQ4_XS / F16 tensors is accepted
+ * each tensor's own type and any mix of Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_NL / IQ4_XS tensors beside one of F16 / BF16 / F32 is accepted
  * (file type 18, all Q6_K with a Q6_K token_embd, among them; it has no synthetic recipe either).
  * Loader names of the Q2_K recipes: synthetic://mistral-7b-q2k, synthetic://mistral-7b-q2ks, synthetic://tiny-q2k, synthetic://tiny-q2ks; of
  * the Q8_0 recipe: synthetic://mistral-7b-q80, synthetic://tiny-q80; of the Q4_0 / Q5_0 recipes: synthetic://mistral-7b-q40, synthetic://tiny-q40,
@@ -83,8 +102,9 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_iq4_xs(const float
  * tk_mi355x_quantize_blocks takes is fixed — callers rely on type 10 being TK_ERROR_INVALID_ARGUMENT there */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_q2k(const float* x, int64_t n_blocks, void* out);
 /* tensor in GGUF block layout; layer = -1 for {0 token_embd, 1 output_norm, 2 output}, else
- * {0 attn_norm,1 q,2 k,3 v,4 o,5 ffn_norm,6 gate,7 up,8 down}; type = ggml type id (0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS).
- * token_embd takes every one of them but F32; a Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, IQ4_NL, IQ4_XS or k-quant tensor needs columns % 256 == 0 */
+ * {0 attn_norm,1 q,2 k,3 v,4 o,5 ffn_norm,6 gate,7 up,8 down}; type = ggml type id (0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS, 30 BF16).
+ * token_embd takes every one of them; a matrix of F32 / F16 / BF16 needs rows % 16 == 0 and columns % 32 == 0, and a model's matrices hold at most
+ * one of the three (tk_mi355x_llm_model_fill_synthetic_float); a Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, IQ4_NL, IQ4_XS or k-quant tensor needs columns % 256 == 0 */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_set_tensor(tk_mi355x_llm_model_t* m, int layer, int which, int type, const void* data,
                                                                    size_t nbytes);
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_load_gguf(tk_mi355x_llm_model_t** out, const char* path, int device);

@@ -10,7 +10,7 @@
  * tk_runner_helpers.c:78-138; sampling is argmax.
  *
  * model_path forms accepted by tk_model_loader_load_model:
- *   "/path/model.gguf"                         GGUF v3, llama arch, F32/F16/Q4_0/Q4_1/Q5_0/Q5_1/Q8_0/Q2_K/Q3_K/Q4_K/Q5_K/Q6_K/IQ4_NL/IQ4_XS tensors
+ *   "/path/model.gguf"                         GGUF v3, llama arch, F32/F16/BF16/Q4_0/Q4_1/Q5_0/Q5_1/Q8_0/Q2_K/Q3_K/Q4_K/Q5_K/Q6_K/IQ4_NL/IQ4_XS tensors
  *   "synthetic://mistral-7b?seed=4"            Mistral-7B-v0.1-shaped, Q4_K_M recipe, seeded weights
  *   "synthetic://tiny?seed=4"                  2-layer test geometry
  *   "synthetic://mistral-7b-q2k", "...-q2ks"   the same shapes in the Q2_K / Q2_K_S recipes (also tiny-q2k, tiny-q2ks)

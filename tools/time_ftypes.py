@@ -6,7 +6,9 @@ Per recipe: the weight bytes a decode step streams and the stand-alone gate | up
 weight bytes plus activation and slab bytes over kernel time).  Per width and recipe: the median decode-step time over the repeats (a
 32-token prompt per sequence, 4 warm-up steps, then greedy steps through the captured pass, HIP events around the loop) and its ratio to
 Q4_K_M's median; for Q4_K_M also the spread of its repeats, the yardstick for every ratio beside it.
-    python tools/time_ftypes.py [steps [repeats [recipe ...]]]      recipes: IQ4_NL IQ4_XS Q4_0 Q4_1 Q5_0 Q5_1 Q8_0 Q2_K Q2_K_S Q3_K_S Q3_K_M Q4_K_S Q5_K_S Q5_K_M"""
+The float recipes (F16, BF16, F32: every matrix and token_embd in the type, on the exact fp32 MFMA GEMM) have no W4A8 mat-vec to time alone; with
+F16 among the recipes, BF16 and F32 are also printed as ratios to F16's median.
+    python tools/time_ftypes.py [steps [repeats [recipe ...]]]      recipes: IQ4_NL IQ4_XS Q4_0 Q4_1 Q5_0 Q5_1 Q8_0 Q2_K Q2_K_S Q3_K_S Q3_K_M Q4_K_S Q5_K_S Q5_K_M F16 BF16 F32"""
 import ctypes as C
 import os
 import sys
@@ -19,12 +21,13 @@ import trackiellm_amd as tk  # noqa: E402
 FTYPES = {"IQ4_NL": tk.FTYPE_IQ4_NL, "IQ4_XS": tk.FTYPE_IQ4_XS, "Q4_0": tk.FTYPE_Q4_0, "Q5_0": tk.FTYPE_Q5_0, "Q8_0": tk.FTYPE_Q8_0, "Q2_K": tk.FTYPE_Q2_K, "Q2_K_S": tk.FTYPE_Q2_K_S, "Q3_K_S": tk.FTYPE_Q3_K_S, "Q3_K_M": tk.FTYPE_Q3_K_M, "Q4_K_S": tk.FTYPE_Q4_K_S,
           "Q4_K_M": tk.FTYPE_Q4_K_M, "Q5_K_S": tk.FTYPE_Q5_K_S, "Q5_K_M": tk.FTYPE_Q5_K_M}
 TTYPES = {"Q4_1": tk.TYPE_Q4_1, "Q5_1": tk.TYPE_Q5_1}  # recipes by tensor type (fill_synthetic_type): no file type of fill_synthetic makes them
+FLOATS = {"F16": tk.TYPE_F16, "BF16": tk.TYPE_BF16, "F32": tk.TYPE_F32}  # the float checkpoint recipes (fill_synthetic(f16=True), fill_synthetic_float)
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 names = ["Q4_K_M"] + [n for n in (sys.argv[3:] or ["Q5_K_M", "Q3_K_S", "Q3_K_M", "Q2_K", "Q2_K_S"]) if n != "Q4_K_M"]
 for n in names:
-    if n not in FTYPES and n not in TTYPES:
-        sys.exit(f"unknown recipe {n}; known: {' '.join(list(FTYPES) + list(TTYPES))}")
+    if n not in FTYPES and n not in TTYPES and n not in FLOATS:
+        sys.exit(f"unknown recipe {n}; known: {' '.join(list(FTYPES) + list(TTYPES) + list(FLOATS))}")
 wb = tk.lib().tk_mi355x_llm_model_weight_bytes
 wb.restype = C.c_uint64
 WIDTHS = (16, 64, 128, 256)
@@ -32,7 +35,10 @@ WIDTHS = (16, 64, 128, 256)
 models, nbytes = {}, {}
 for name in names:
     model = tk.LlmModel(tk.MISTRAL_7B(), device=0)
-    models[name] = model.fill_synthetic_type(4, TTYPES[name]) if name in TTYPES else model.fill_synthetic(4, ftype=FTYPES[name])
+    if name in FLOATS:
+        models[name] = model.fill_synthetic(4, f16=True) if name == "F16" else model.fill_synthetic_float(4, FLOATS[name])
+    else:
+        models[name] = model.fill_synthetic_type(4, TTYPES[name]) if name in TTYPES else model.fill_synthetic(4, ftype=FTYPES[name])
     nbytes[name] = wb(models[name].h)
     print(f"{name}: {nbytes[name] / 1e9:.3f} GB of weights streamed per decode step, x{nbytes[name] / nbytes['Q4_K_M']:.3f} of Q4_K_M", flush=True)
 
@@ -48,7 +54,7 @@ for rep in range(repeats):
             sess.decode(rows, 4)
             _, t = sess.decode(rows, steps)
             ms[(name, rows)].append(t)
-            if rows == 16 and rep == 0:
+            if rows == 16 and rep == 0 and name not in FLOATS:
                 gms, gbytes = sess.time_gemv(0, 0, 16, 50)
                 print(f"{name} ffn_gate|up mat-vec, layer 0, 16 rows: {gms * 1e3:.1f} us, {gbytes / gms / 1e9:.2f} TB/s = {gbytes / gms / 1e9 / 8:.3f} of 8 TB/s",
                       flush=True)
@@ -61,6 +67,10 @@ for rows in WIDTHS:
         med = float(np.median(v))
         tail = (f", repeats {min(v):.3f} .. {max(v):.3f} ms: spread {100 * (max(v) - min(v)) / med:.1f} % of the median" if name == "Q4_K_M"
                 else f", x{med / base:.3f} of Q4_K_M (repeats x{min(v) / base:.3f} .. x{max(v) / base:.3f})")
+        if name in ("BF16", "F32") and "F16" in names:
+            f16 = ms[("F16", rows)]
+            fm = float(np.median(f16))
+            tail += f"; x{med / fm:.3f} of F16 (F16's repeats span {100 * (max(f16) - min(f16)) / fm:.1f} % of its median)"
         print(f"{name} {rows:3d} rows: {med:.3f} ms per decode step (median of {repeats}), weights at {nbytes[name] / med / 1e9:.2f} TB/s{tail}", flush=True)
 for m in models.values():
     m.close()

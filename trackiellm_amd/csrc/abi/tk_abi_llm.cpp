@@ -194,6 +194,27 @@ tk_error_code_t tk_mi355x_llm_model_fill_synthetic_f16(tk_mi355x_llm_model_t* m,
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_llm_model_fill_synthetic_float(tk_mi355x_llm_model_t* m, uint64_t seed, int ggml_type) {
+    if (!m || !(ggml_type == TK_TYPE_BF16 || ggml_type == TK_TYPE_F32)) return TK_ERROR_INVALID_ARGUMENT;
+    if (!m->model.fill_synthetic_float(seed, ggml_type)) return fail(TK_ERROR_GPU_ROCM_ERROR, m->model.error);
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_convert_bf16(const float* x, int64_t n, uint16_t* out) {
+    if (!x || !out || n < 0) return TK_ERROR_INVALID_ARGUMENT;
+    for (int64_t i = 0; i < n; ++i) out[i] = tk_f32_to_bf16(x[i]);
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_matmul_float_probe(int device, int type, const void* w, int64_t rows, int64_t K, int ks, int nseg, const int32_t seg_rows[3],
+                                                 int nrows, const float* x, float* y) {
+    if (!w || !seg_rows || !x || !y || !(type == TK_TYPE_F16 || type == TK_TYPE_BF16 || type == TK_TYPE_F32)) return TK_ERROR_INVALID_ARGUMENT;
+    std::string err;
+    if (!tk_llm_matmul_float_probe(device, type, w, rows, K, ks, nseg, seg_rows, nrows, x, y, err))
+        return fail(err.find("needs") != std::string::npos ? TK_ERROR_INVALID_ARGUMENT : TK_ERROR_GPU_ROCM_ERROR, err);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_model_set_lora(tk_mi355x_llm_model_t* m, const char* adapter_path) {
     if (!m) return TK_ERROR_INVALID_ARGUMENT;
     if (!adapter_path || !*adapter_path) { m->model.lora = nullptr; m->lora.reset(); return TK_SUCCESS; }
@@ -738,7 +759,11 @@ tk_error_code_t tk_model_loader_load_model(tk_model_loader_t* loader, const tk_m
     tk_error_code_t rc;
     if (parse_synthetic(file, &name, &seed)) {
         tk_mi355x_llm_hparams_t h{};
-        const bool f16 = name.size() > 4 && name.compare(name.size() - 4, 4, "-f16") == 0; /* the fp16 checkpoint recipe (BASELINE configs[4]) */
+        /* the float recipes of fill_synthetic_float, parsed before -f16 (which "-bf16" also ends in): synthetic://mistral-7b-bf16, synthetic://tiny-f32 */
+        int flt = -1;
+        if (name.size() > 5 && name.compare(name.size() - 5, 5, "-bf16") == 0) { flt = TK_TYPE_BF16; name.resize(name.size() - 5); }
+        else if (name.size() > 4 && name.compare(name.size() - 4, 4, "-f32") == 0) { flt = TK_TYPE_F32; name.resize(name.size() - 4); }
+        const bool f16 = flt < 0 && name.size() > 4 && name.compare(name.size() - 4, 4, "-f16") == 0; /* the fp16 checkpoint recipe (BASELINE configs[4]) */
         if (f16) name.resize(name.size() - 4);
         int ftype = 0; /* the Q8_0, Q4_0, Q5_0, IQ4_NL, IQ4_XS and Q2_K recipes of fill_synthetic_ftype: synthetic://mistral-7b-q80, synthetic://mistral-7b-q40, synthetic://tiny-q50, synthetic://mistral-7b-iq4nl, synthetic://tiny-iq4xs, synthetic://mistral-7b-q2k, synthetic://tiny-q2ks */
         int gtype = 0; /* the recipes of fill_synthetic_type, by tensor type: synthetic://mistral-7b-q41, synthetic://tiny-q51 */
@@ -757,7 +782,8 @@ tk_error_code_t tk_model_loader_load_model(tk_model_loader_t* loader, const tk_m
         rc = tk_mi355x_llm_model_create(&m, &h, device);
         if (rc == TK_SUCCESS && !lora.empty()) rc = tk_mi355x_llm_model_set_lora(m, lora.c_str());
         if (rc == TK_SUCCESS)
-            rc = f16 ? tk_mi355x_llm_model_fill_synthetic_f16(m, seed)
+            rc = flt >= 0 ? tk_mi355x_llm_model_fill_synthetic_float(m, seed, flt)
+                     : f16 ? tk_mi355x_llm_model_fill_synthetic_f16(m, seed)
                      : gtype ? tk_mi355x_llm_model_fill_synthetic_type(m, seed, gtype)
                      : ftype ? tk_mi355x_llm_model_fill_synthetic_ftype(m, seed, ftype) : tk_mi355x_llm_model_fill_synthetic(m, seed);
         if (rc != TK_SUCCESS) { if (m) release_model(m); return rc; } /* g_models_mu is held here */

@@ -178,4 +178,21 @@ TK_HD uint16_t tk_f32_to_f16(float f) {
     return (uint16_t)(sign | out);
 }
 
+/* bfloat16 <-> binary32: ggml's ggml_compute_fp32_to_bf16 / ggml_compute_bf16_to_fp32.  Widening is exact (the bits, shifted); narrowing
+ * rounds to nearest even on the integer image, keeps subnormals, lets 0x7f7f8000 and above round to infinity and quiets a NaN by setting
+ * bit 6 of the kept half (the payload's upper seven bits survive).  Not a hardware convert: its NaN and subnormal handling is not this. */
+TK_HD float tk_bf16_to_f32(uint16_t h) { return tk_bits_f32((uint32_t)h << 16); }
+
+TK_HD uint16_t tk_f32_to_bf16(float f) {
+    const uint32_t u = tk_f32_bits(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 64u);
+    return (uint16_t)((u + (0x7fffu + ((u >> 16) & 1u))) >> 16);
+}
+
+/* what a float matrix's activation operand is rounded through: ggml's vec_dot_type of the weight type (F32: as it is, F16, BF16) */
+enum TkRound { TK_ROUND_NONE = 0, TK_ROUND_F16 = 1, TK_ROUND_BF16 = 2 };
+TK_HD float tk_round_through(float v, int mode) {
+    return mode == TK_ROUND_F16 ? tk_f16_to_f32(tk_f32_to_f16(v)) : mode == TK_ROUND_BF16 ? tk_bf16_to_f32(tk_f32_to_bf16(v)) : v;
+}
+
 #endif /* TK_EXACT_MATH_H */

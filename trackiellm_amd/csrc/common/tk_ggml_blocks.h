@@ -64,6 +64,7 @@ enum tk_ggml_type {
     TK_TYPE_Q6_K = 14,
     TK_TYPE_IQ4_NL = 20,
     TK_TYPE_IQ4_XS = 23,
+    TK_TYPE_BF16 = 30,
 };
 
 typedef struct {
@@ -169,7 +170,8 @@ struct tk_type_desc {
 TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
     switch (type) {
         /*                         name    elems bytes tile               mask idx shares embd   lora   host_q */
-        case TK_TYPE_F32:  return {"F32",  1,    4,    0,                 0,   -1, false, false, false, false};
+        case TK_TYPE_F32:  return {"F32",  1,    4,    0,                 0,   -1, false, true,  true,  false};
+        case TK_TYPE_BF16: return {"BF16", 1,    2,    0,                 0,   -1, false, true,  true,  false};
         case TK_TYPE_F16:  return {"F16",  1,    2,    0,                 0,   -1, false, true,  true,  false};
         case TK_TYPE_Q4_0: return {"Q4_0", 32,   18,   TK_Q4_0_TILE_BYTES, 64, 7,  false, true,  false, false};
         case TK_TYPE_Q5_0: return {"Q5_0", 32,   22,   TK_Q5_0_TILE_BYTES, 128, 8, false, true,  false, false};
@@ -187,11 +189,15 @@ TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
     }
 }
 /* the lists the messages print: kept beside the table, edited with it */
-#define TK_TYPE_NAMES "F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS"
-#define TK_TYPE_NAMES_OR "F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
+#define TK_TYPE_NAMES "F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS"
+#define TK_TYPE_NAMES_OR "F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
 #define TK_KQUANT_NAMES_OR "Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
-#define TK_TOKEN_EMBD_NAMES_OR "Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS or F16"
-#define TK_LORA_MERGE_NAMES_OR "Q4_K, Q6_K or F16"
+#define TK_TOKEN_EMBD_NAMES_OR "Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS, F16, BF16 or F32"
+#define TK_LORA_MERGE_NAMES_OR "Q4_K, Q6_K, F16, BF16 or F32"
+/* the float matrix types: tiles of the exact fp32 GEMM (nn/tk_gemm_tiled.h), 2 or 4 bytes a weight.  A model holds at most one of them among
+ * its matrices: the sessions' operand image carries one rounding (tk_type_float_round) */
+TK_HD constexpr bool tk_type_is_float(int type) { return type == TK_TYPE_F32 || type == TK_TYPE_F16 || type == TK_TYPE_BF16; }
+TK_HD constexpr int tk_type_float_round(int type) { return type == TK_TYPE_F16 ? TK_ROUND_F16 : type == TK_TYPE_BF16 ? TK_ROUND_BF16 : TK_ROUND_NONE; }
 
 TK_HD constexpr bool tk_type_known(int type) { return tk_type_desc_of(type).name != nullptr; }
 TK_HD constexpr bool tk_type_is_kquant(int type) { return tk_type_desc_of(type).tile_bytes != 0; }

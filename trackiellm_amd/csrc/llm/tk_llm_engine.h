@@ -58,7 +58,14 @@ public:
     bool fill_synthetic(uint64_t seed, bool f16 = false, int ftype = 15);
     /* by tensor type, for the types no file type of fill_synthetic names (Q4_1, Q5_1): every layer matrix and token_embd `type`, output Q6_K, norms F32 */
     bool fill_synthetic_type(uint64_t seed, int type);
-    bool has_f16 = false; /* some matrix is f16: sessions also keep f16-rounded f32 activations */
+    /* by float tensor type (30 BF16 or 0 F32; F16 is fill_synthetic's f16): every matrix and token_embd of that type, the values 0.02 * tk_synth_normal
+     * stored through tk_f32_to_bf16 / unconverted; norms F32 */
+    bool fill_synthetic_float(uint64_t seed, int type);
+    /* the model's float kind: the one float type (F16 / BF16 / F32) among its matrices — layer matrices and output; token_embd is free —, or -1
+     * when every matrix is a tiled quantised type.  Sessions of a float model also keep their activations as f32 values rounded through that type
+     * (TkActQ8::af).  Two float types among the matrices: install refuses the second, ready() is false; *other (optional) = that second type.
+     * except (optional): a tensor left out of the count */
+    int float_type(int* other = nullptr, const TkDevTensor* except = nullptr) const;
     /* a LoRA adapter to merge into every matrix it names WHILE that matrix is installed (set before set_tensor / fill_synthetic; tk_lora.h);
      * not owned, only read during those calls */
     const struct TkLoraAdapter* lora = nullptr;
@@ -72,6 +79,7 @@ public:
 private:
     TkDevTensor* slot(int layer, int which);
     bool install(TkDevTensor* t, int type, int64_t rows, int64_t cols, void* dev_blocks, hipStream_t s, int layer, int which);
+    bool fill_synthetic_as(uint64_t seed, int float_type, int ftype);
 };
 
 class TkLlmPipe;
@@ -172,6 +180,13 @@ public:
     double capture_ms = 0.0;
 private:
 };
+
+/* one production float matmul (tk_mi355x_llm_matmul_float_probe): w [rows][K] row-major values of `type` (1 F16, 30 BF16, 0 F32), rows = the sum of
+ * the nseg <= 3 segments' seg_rows (each a multiple of 16), tiled per segment as install() does; x [nrows][K] through the production image
+ * producer (k_quant_q8 with the type's rounding); one tk_launch_gemm_tiled with the segments side by side and K split ks ways; the slabs added
+ * in ascending order; y [nrows][rows] on the host */
+bool tk_llm_matmul_float_probe(int device, int type, const void* w, int64_t rows, int64_t K, int ks, int nseg, const int32_t* seg_rows, int nrows,
+                               const float* x, float* y, std::string& error);
 
 /* one production mat-vec on raw GGUF blocks (tk_mi355x_llm_gemv_probe): repack, Q8_K-quantise x [nrows][K] on the device, the launcher at
  * width nrows, the ks slabs summed in ascending order; y [nrows][rows] on the host */

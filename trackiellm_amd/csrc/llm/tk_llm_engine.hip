@@ -10,6 +10,7 @@
 #include <math.h>
 #include <algorithm>
 #include <mutex>
+#include <new>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -121,9 +122,16 @@ TkLlmModel::~TkLlmModel() {
 
 /* dev_blocks: tensor in GGUF layout already in device memory */
 bool TkLlmModel::install(TkDevTensor* t, int type, int64_t rows, int64_t cols, void* dev_blocks, hipStream_t s, int layer, int which) {
+    const bool is_matrix = rows > 1 && t != &token_embd;
+    if (is_matrix && tk_type_is_float(type)) { /* one float type per model: the sessions' operand image carries one rounding */
+        const int have = float_type(nullptr, t); /* the tensor being replaced does not count */
+        if (have >= 0 && have != type) {
+            error = std::string("a model's matrices hold at most one float type: this one is ") + tk_type_desc_of(type).name + ", another is " + tk_type_desc_of(have).name;
+            return false;
+        }
+    }
     if (t->data) { (void)hipFree(t->data); t->data = nullptr; }
     t->type = type; t->rows = rows; t->cols = cols;
-    const bool is_matrix = rows > 1 && t != &token_embd;
     if (const TkLoraTensor* lt = (lora && is_matrix) ? lora->find(layer, which) : nullptr) {
         /* the reference's llama_model_apply_lora_from_file (tk_model_loader.c:259-270): W += (alpha / r) B A on the blocks as the file holds them */
         if (lt->n_out != rows || lt->k_in != cols) { error = "LoRA adapter does not fit this model (factor shapes against the base matrix)"; return false; }
@@ -146,20 +154,21 @@ bool TkLlmModel::install(TkDevTensor* t, int type, int64_t rows, int64_t cols, v
         if (!ok || !done) { error = "LoRA merge failed on the device"; return false; }
         lora_merged++;
     }
-    if (type == TK_TYPE_F32) {
-        t->bytes = (size_t)rows * cols * 4;
-        HIPQ(hipMalloc((void**)&t->data, t->bytes));
-        HIPQ(hipMemcpyAsync(t->data, dev_blocks, t->bytes, hipMemcpyDeviceToDevice, s));
-        return true;
-    }
-    if (type == TK_TYPE_F16) { /* fp16 checkpoints: matrices become the tiled GEMM's weight tiles (csrc/nn/tk_gemm_tiled.h), the embedding stays row-major */
-        if (cols % 32 || (is_matrix && rows % 16)) { error = "f16 matrices need rows % 16 == 0 and columns % 32 == 0"; return false; }
-        t->bytes = (size_t)rows * cols * 2;
+    if (tk_type_is_float(type)) {
+        /* float checkpoints: matrices become the tiled GEMM's weight tiles (csrc/nn/tk_gemm_tiled.h: 2 bytes a value for F16 / BF16, 4 for F32), the
+         * embedding and the norm rows stay row-major */
+        const int wb = type == TK_TYPE_F32 ? 4 : 2;
+        /* a matrix is tiled 16 rows x 32 k.  A row-major tensor has no such need; an F16 token_embd has all the same been held to columns % 32
+         * since F16 loads, and that refusal stays as it is (BF16 / F32 embeddings and the norm rows are not held to it) */
+        if ((is_matrix && (rows % 16 || cols % 32)) || (type == TK_TYPE_F16 && cols % 32)) {
+            error = std::string(type == TK_TYPE_F16 ? "f16" : tk_type_desc_of(type).name) + " matrices need rows % 16 == 0 and columns % 32 == 0";
+            return false;
+        }
+        t->bytes = (size_t)rows * cols * wb;
         HIPQ(hipMalloc((void**)&t->data, t->bytes));
         if (is_matrix) {
-            tk_launch_tile_weights(dev_blocks, 2, rows, cols, t->data, s);
+            tk_launch_tile_weights(dev_blocks, wb, rows, cols, t->data, s);
             HIPQ(hipGetLastError());
-            has_f16 = true;
         } else {
             HIPQ(hipMemcpyAsync(t->data, dev_blocks, t->bytes, hipMemcpyDeviceToDevice, s));
         }
@@ -201,12 +210,39 @@ bool TkLlmModel::set_tensor(int layer, int which, int type, const void* host_blo
     return ok;
 }
 
-bool TkLlmModel::fill_synthetic(uint64_t seed, bool f16, int ftype) {
+int TkLlmModel::float_type(int* other, const TkDevTensor* except) const {
+    int found = -1;
+    if (other) *other = -1;
+    auto see = [&](const TkDevTensor& t) {
+        if (&t == except || !t.data || !tk_type_is_float(t.type)) return;
+        if (found < 0) found = t.type;
+        else if (t.type != found && other) *other = t.type;
+    };
+    see(output);
+    for (const auto& L : layers) { see(L.q); see(L.k); see(L.v); see(L.o); see(L.gate); see(L.up); see(L.down); }
+    return found;
+}
+
+bool TkLlmModel::fill_synthetic(uint64_t seed, bool f16, int ftype) { return fill_synthetic_as(seed, f16 ? (int)TK_TYPE_F16 : -1, ftype); }
+
+bool TkLlmModel::fill_synthetic_float(uint64_t seed, int type) {
+    if (type != TK_TYPE_BF16 && type != TK_TYPE_F32) { error = "fill_synthetic_float: type must be BF16 or F32"; return false; }
+    return fill_synthetic_as(seed, type, 15);
+}
+
+bool TkLlmModel::fill_synthetic_as(uint64_t seed, int float_type, int ftype) {
     HIPQ(hipSetDevice(device));
     auto type_of = [&](int l, int w) {
         const int t = recipe_type(hp, l, w, ftype);
-        return (f16 && t != TK_TYPE_F32) ? (int)TK_TYPE_F16 : t; /* fp16 checkpoint: every matrix and the embedding f16, norms f32 */
+        return (float_type >= 0 && t != TK_TYPE_F32) ? float_type : t; /* float checkpoint: every matrix and the embedding in the float type, norms f32 */
     };
+    /* a fill replaces every tensor: what an earlier fill or set_tensor left goes first, so that a handle may be refilled in another float type
+     * (install() would refuse the first matrix of the new type beside the old ones) */
+    for (int l = -1; l < hp.n_layer; ++l)
+        for (int w = 0; w < (l < 0 ? 3 : (int)TK_L_COUNT); ++w) {
+            TkDevTensor* t = slot(l, w);
+            if (t->data) { (void)hipFree(t->data); t->data = nullptr; }
+        }
     /* scratch big enough for the largest tensor in GGUF layout */
     size_t maxb = 0;
     for (int l = -1; l < hp.n_layer; ++l)
@@ -226,7 +262,8 @@ bool TkLlmModel::fill_synthetic(uint64_t seed, bool f16, int ftype) {
             shape(l, w, &r, &c);
             int type = type_of(l, w);
             uint64_t tid = l < 0 ? (uint64_t)w : (uint64_t)(16 + l * 16 + w);
-            if (type == TK_TYPE_F32) tk_launch_synth_f32(seed, tid, r * c, (float*)tmp, nullptr);
+            if (r == 1) tk_launch_synth_f32(seed, tid, r * c, (float*)tmp, nullptr); /* the norm rows, F32 in every recipe */
+            else if (type == TK_TYPE_BF16 || type == TK_TYPE_F32) tk_launch_synth_float(type, seed, tid, r * c, 0.02f, tmp, nullptr);
             else if (type == TK_TYPE_F16) tk_launch_synth_f16(seed, tid, r * c, 0.02f, (uint16_t*)tmp, nullptr);
             else tk_launch_synth_blocks(type, seed, tid, r * c / 256, 0.02f, tmp, nullptr);
             ok = install(slot(l, w), type, r, c, tmp, nullptr, l, w);
@@ -246,19 +283,23 @@ bool TkLlmModel::ready() const {
     for (const auto& L : layers) {
         if (!L.attn_norm.data || !L.ffn_norm.data || !L.q.data || !L.k.data || !L.v.data || !L.o.data || !L.gate.data || !L.up.data || !L.down.data)
             return false;
-        /* the tensors of one fused launch (q|k|v, gate|up) are all k-quants or all f16 */
-        const bool f_qkv = L.q.type == TK_TYPE_F16, f_gu = L.gate.type == TK_TYPE_F16;
-        if ((L.k.type == TK_TYPE_F16) != f_qkv || (L.v.type == TK_TYPE_F16) != f_qkv || (L.up.type == TK_TYPE_F16) != f_gu) return false;
+        /* the tensors of one fused launch (q|k|v, gate|up) are all tiled quantised types or all float */
+        const bool f_qkv = tk_type_is_float(L.q.type), f_gu = tk_type_is_float(L.gate.type);
+        if (tk_type_is_float(L.k.type) != f_qkv || tk_type_is_float(L.v.type) != f_qkv || tk_type_is_float(L.up.type) != f_gu) return false;
     }
-    return true;
+    int other = -1;
+    (void)float_type(&other);
+    return other < 0; /* at most one float type among the matrices */
 }
 
 /* ------------------------------------------------------------------ session ---------------- */
 
-static bool alloc_act(TkActQ8* a, int K, bool want_f16, std::string& error) {
+/* float_type: the model's float kind (TkLlmModel::float_type), -1 = none: no operand image */
+static bool alloc_act(TkActQ8* a, int K, int float_type, std::string& error) {
     a->aq_ts = TK_AQ_BYTES(K); a->ad_ts = TK_AD_FLOATS(K); a->abs_ts = TK_ABS_BYTES(K);
-    a->af = nullptr; a->af_ts = (size_t)K * TK_ROW_SLOTS;
-    if (want_f16 && hipMalloc((void**)&a->af, (size_t)TK_MAX_ROWS * K * 4) != hipSuccess) { error = "out of device memory (f16 activation buffers)"; return false; }
+    a->af = nullptr; a->af_ts = (uint32_t)((size_t)K * TK_ROW_SLOTS);
+    a->af_round = float_type >= 0 ? tk_type_float_round(float_type) : (int)TK_ROUND_NONE;
+    if (float_type >= 0 && hipMalloc((void**)&a->af, (size_t)TK_MAX_ROWS * K * 4) != hipSuccess) { error = "out of device memory (float activation buffers)"; return false; }
     if (a->af) (void)hipMemset(a->af, 0, (size_t)TK_MAX_ROWS * K * 4);
     if (hipMalloc((void**)&a->aq, TK_MAX_TILES * a->aq_ts) != hipSuccess || hipMalloc((void**)&a->ad, TK_MAX_TILES * a->ad_ts * 4) != hipSuccess ||
         hipMalloc((void**)&a->abs, TK_MAX_TILES * a->abs_ts) != hipSuccess || hipMalloc((void**)&a->abs16, TK_MAX_TILES * a->abs_ts * 2) != hipSuccess) {
@@ -284,6 +325,11 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     model = m;
     max_seq = mseq;
     max_ctx = mctx;
+    if (m && !m->ready()) {
+        int other = -1;
+        const int ft = m->float_type(&other);
+        if (other >= 0) { error = std::string("a model's matrices hold at most one float type: this model has ") + tk_type_desc_of(ft).name + " and " + tk_type_desc_of(other).name; return false; }
+    }
     if (!m || !m->ready()) { error = "model has missing tensors"; return false; }
     if (mseq <= 0 || mctx <= 0) { error = "max_seq and max_ctx must be positive"; return false; }
     const TkLlmHParams& h = m->hp;
@@ -313,7 +359,8 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     HIPQ(hipMalloc((void**)&x2, (size_t)TK_MAX_ROWS * h.d_model * 4));
     HIPQ(hipMalloc((void**)&partial2, pmax * TK_MAX_ROWS * 4));
     HIPQ(hipMalloc((void**)&logits, (size_t)TK_MAX_ROWS * h.vocab * 4));
-    if (!alloc_act(&act_d, h.d_model, m->has_f16, error) || !alloc_act(&act_qd, QD, m->has_f16, error) || !alloc_act(&act_ff, h.d_ff, m->has_f16, error)) return false;
+    const int ft = m->float_type();
+    if (!alloc_act(&act_d, h.d_model, ft, error) || !alloc_act(&act_qd, QD, ft, error) || !alloc_act(&act_ff, h.d_ff, ft, error)) return false;
     HIPQ(hipMalloc((void**)&d_seq, TK_MAX_ROWS * 4));
     HIPQ(hipMalloc((void**)&d_pos, TK_MAX_ROWS * 4));
     HIPQ(hipMalloc((void**)&d_tok, TK_MAX_ROWS * 4));
@@ -350,7 +397,7 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     HIPQ(hipMemcpy(rope_sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
     /* kernels that want more than the default 64 KiB of dynamic LDS: a per-device opt-in */
     if (const char* e = tk_llm_prepare_device(m->device)) { error = std::string("LDS opt-in failed: ") + e; return false; }
-    if (m->has_f16 && !tk_gemm_tiled_prepare_device()) { error = "LDS opt-in of the tiled GEMM failed"; return false; }
+    if (ft >= 0 && !tk_gemm_tiled_prepare_device()) { error = "LDS opt-in of the tiled GEMM failed"; return false; }
     /* the prefix cache's copy kernel runs between passes, outside any capture: launched once here, with nothing to copy, so that its code object
      * is loaded before the first pass is recorded into a graph */
     if (kv_copy_applies() && !enqueue_kv_copy(nullptr, 0)) return false;
@@ -464,11 +511,12 @@ bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, i
     uint8_t* tiles = nullptr;
     float *dx = nullptr, *out = nullptr;
     TkActQ8 act{};
-    std::vector<float> part(nout);
+    std::vector<float> part;
+    try { part.resize(nout); } catch (const std::bad_alloc&) { error = "gemv probe: out of host memory"; return false; } /* nothing may be thrown across the C ABI */
     bool ok = hipMalloc(&db, nblk * bb) == hipSuccess && hipMalloc((void**)&tiles, nblk / TK_TILE_ROWS * tb) == hipSuccess &&
               hipMalloc((void**)&dx, (size_t)nrows * K * 4) == hipSuccess && hipMalloc((void**)&out, nout * 4) == hipSuccess;
     if (!ok) error = "gemv probe: out of device memory";
-    ok = ok && alloc_act(&act, (int)K, false, error);
+    ok = ok && alloc_act(&act, (int)K, -1, error);
     if (ok) {
         hipStream_t s = nullptr;
         ok = hipMemcpy(db, blocks, nblk * bb, hipMemcpyHostToDevice) == hipSuccess &&
@@ -502,24 +550,90 @@ bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, i
     return ok;
 }
 
+bool tk_llm_matmul_float_probe(int device, int type, const void* w, int64_t rows, int64_t K, int ks, int nseg, const int32_t* seg_rows, int nrows,
+                               const float* x, float* y, std::string& error) {
+    if (type != TK_TYPE_F16 && type != TK_TYPE_BF16 && type != TK_TYPE_F32) { error = "float matmul probe: type must be F16, BF16 or F32"; return false; }
+    int64_t sum = 0;
+    bool segs_ok = nseg >= 1 && nseg <= 3;
+    for (int i = 0; segs_ok && i < nseg; ++i) { segs_ok = seg_rows[i] >= 16 && seg_rows[i] % 16 == 0; sum += seg_rows[i]; }
+    /* a test entry: rows x K up to 2^26 values (a 256 MiB F32 matrix; Mistral's largest is 14336 x 4096 = 2^25.8), so the host's slab copy
+     * (ks x 256 x rows floats) stays below 512 MiB */
+    if (!segs_ok || sum != rows || rows > 65536 || ks < 1 || ks > 8 || K < 256 || K % (256 * (int64_t)ks) || K > 65536 || rows * K > (1 << 26) || nrows < 1 ||
+        nrows > TK_MAX_ROWS) {
+        error = "float matmul probe: needs 1 .. 3 segments of rows % 16 == 0 that add up to rows <= 65536, ks in [1, 8], K % (256 ks) == 0, rows x K <= 2^26, nrows in [1, 256]";
+        return false;
+    }
+    HIPQ(hipSetDevice(device));
+    if (const char* e = tk_llm_prepare_device(device)) { error = e; return false; }
+    if (!tk_gemm_tiled_prepare_device()) { error = "LDS opt-in of the tiled GEMM failed"; return false; }
+    const int wb = type == TK_TYPE_F32 ? 4 : 2;
+    const size_t wbytes = (size_t)rows * (size_t)K * wb, nout = (size_t)ks * TK_MAX_ROWS * (size_t)rows;
+    uint8_t *dw = nullptr, *tiles = nullptr;
+    float *dx = nullptr, *out = nullptr;
+    TkActQ8 act{};
+    std::vector<float> part;
+    try { part.resize(nout); } catch (const std::bad_alloc&) { error = "float matmul probe: out of host memory"; return false; } /* nothing may be thrown across the C ABI */
+    bool ok = hipMalloc((void**)&dw, wbytes) == hipSuccess && hipMalloc((void**)&tiles, wbytes) == hipSuccess &&
+              hipMalloc((void**)&dx, (size_t)nrows * K * 4) == hipSuccess && hipMalloc((void**)&out, nout * 4) == hipSuccess;
+    if (!ok) error = "float matmul probe: out of device memory";
+    ok = ok && alloc_act(&act, (int)K, type, error);
+    if (ok) {
+        hipStream_t s = nullptr;
+        ok = hipMemcpy(dw, w, wbytes, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dx, x, (size_t)nrows * K * 4, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemset(out, 0, nout * 4) == hipSuccess;
+        if (ok) {
+            TkTiledGemm f{};
+            size_t at = 0;
+            for (int i = 0; i < nseg; ++i) { /* every segment a matrix of its own, tiled as install() tiles it */
+                tk_launch_tile_weights(dw + at, wb, seg_rows[i], K, tiles + at, s);
+                f.tiles[i] = tiles + at; f.row_tiles[i] = seg_rows[i] / TK_TILE_ROWS;
+                at += (size_t)seg_rows[i] * (size_t)K * wb;
+            }
+            tk_launch_quant_q8(dx, (int)K, nrows, act, s);
+            f.nseg = nseg; f.wbytes = wb; f.bf16 = type == TK_TYPE_BF16 ? 1 : 0; f.K = (int)K; f.ks = ks; f.ldc = (int)rows; f.n_valid = (int)rows; f.nrows = nrows;
+            f.slab_rows = TK_MAX_ROWS; f.a_img = act.af; f.a_ts = act.af_ts; f.out = out;
+            ok = tk_launch_gemm_tiled(f, s);
+            if (!ok) error = "float matmul probe: the tiled GEMM refused the launch";
+            else {
+                ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                     hipMemcpy(part.data(), out, nout * 4, hipMemcpyDeviceToHost) == hipSuccess;
+                if (!ok) error = "float matmul probe: device error";
+            }
+        } else error = "float matmul probe: device error";
+    }
+    if (ok)
+        for (int r = 0; r < nrows; ++r)
+            for (int64_t n = 0; n < rows; ++n) { /* sum_partials' order */
+                float o = part[(size_t)r * rows + n];
+                for (int sl = 1; sl < ks; ++sl) o = o + part[((size_t)sl * TK_MAX_ROWS + r) * rows + n];
+                y[(size_t)r * rows + n] = o;
+            }
+    free_act(&act);
+    if (dw) (void)hipFree(dw);
+    if (tiles) (void)hipFree(tiles);
+    if (dx) (void)hipFree(dx);
+    if (out) (void)hipFree(out);
+    return ok;
+}
+
 void TkLlmSession::enqueue_pass(int nrows, bool lm_head, bool fused_attn) { enqueue_range(nrows, 0, model->hp.n_layer, true, false, lm_head, fused_attn); }
 
 /* layers [l0, l1) of one pass.  embed: the residual stream starts from the token embeddings (first pipeline stage), otherwise x
  * already holds it.  fold_out: finish the last layer's residual update so x is the complete stream (it leaves this GPU).
  * head: final norm + lm_head + arg max (last stage). */
-/* one matmul group of a pass: the K-quant tensors of a launch go to the W4A8 kernels (K-split partial slabs, canonical plan `ks`); an f16
- * group goes, tensor by tensor, through the exact fp32 GEMM on the f16-rounded activations (one chain over K: a single slab).  Returns
+/* one matmul group of a pass: the K-quant tensors of a launch go to the W4A8 kernels (K-split partial slabs, canonical plan `ks`); a float
+ * group (F16 / BF16 / F32) goes through the exact fp32 GEMM on the activations rounded through that type (per slab one chain over its k).  Returns
  * the number of partial slabs the consumers must add. */
 int TkLlmSession::enqueue_matmul(const TkDevTensor* const* t, int nseg, int K, int ks, int n_total, const TkActQ8& act, float* out, int nrows) {
     hipStream_t s = stream;
-    if (t[0]->type == TK_TYPE_F16) {
+    if (tk_type_is_float(t[0]->type)) {
         TkTiledGemm f{};
         for (int i = 0; i < nseg; ++i) { f.tiles[i] = t[i]->data; f.row_tiles[i] = (int)(t[i]->rows / TK_TILE_ROWS); }
-        f.nseg = nseg; f.wbytes = 2; f.K = K; f.ks = ks; f.ldc = n_total; f.n_valid = n_total; f.nrows = nrows; f.slab_rows = TK_MAX_ROWS;
+        f.nseg = nseg; f.wbytes = t[0]->type == TK_TYPE_F32 ? 4 : 2; f.bf16 = t[0]->type == TK_TYPE_BF16 ? 1 : 0; f.K = K; f.ks = ks; f.ldc = n_total; f.n_valid = n_total; f.nrows = nrows; f.slab_rows = TK_MAX_ROWS;
         f.a_img = act.af; f.a_ts = act.af_ts; f.out = out;
         /* shapes were validated when the model was installed (K a multiple of 256 ks); a refusal here would leave the slab unwritten, so it is
          * recorded and fails the pass (forward / decode / capture_pass check launch_error) instead of producing garbage silently */
-        if (!tk_launch_gemm_tiled(f, s) && launch_error.empty()) launch_error = "tiled GEMM launch refused (shape outside what the f16 path supports)";
+        if (!tk_launch_gemm_tiled(f, s) && launch_error.empty()) launch_error = "tiled GEMM launch refused (shape outside what the float path supports)";
         return ks;
     }
     TkGemvArgs a{};
@@ -548,11 +662,11 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
      * (x, slabs) of one buffer pair while workgroup 0 writes the updated stream into the other and all write their slabs there:
      *   q|k|v: x, partial -> x2, partial2;  attention reads partial2;  o -> partial;  gate|up: x2, partial -> x, partial2;
      *   down: partial2 -> partial — at every layer boundary x and `partial` hold what the unfused path leaves there. */
-    bool kq = model->output.type != TK_TYPE_F16;
+    bool kq = !tk_type_is_float(model->output.type);
     for (int l = l0; l < l1 && kq; ++l) {
         const TkLlmLayer& L = model->layers[l];
-        kq = L.q.type != TK_TYPE_F16 && L.k.type != TK_TYPE_F16 && L.v.type != TK_TYPE_F16 && L.o.type != TK_TYPE_F16 && L.gate.type != TK_TYPE_F16 &&
-             L.up.type != TK_TYPE_F16 && L.down.type != TK_TYPE_F16;
+        kq = !tk_type_is_float(L.q.type) && !tk_type_is_float(L.k.type) && !tk_type_is_float(L.v.type) && !tk_type_is_float(L.o.type) &&
+             !tk_type_is_float(L.gate.type) && !tk_type_is_float(L.up.type) && !tk_type_is_float(L.down.type);
     }
     const bool fuse = kq && producer_fusion_enabled() && tk_gemv_fuses_producer(nrows, D, h.ks_qkv, h.ks_down) &&
                       tk_gemv_fuses_producer(nrows, D, h.ks_gateup, h.ks_o) && tk_gemv_fuses_producer(nrows, FF, h.ks_down, h.ks_gateup) &&

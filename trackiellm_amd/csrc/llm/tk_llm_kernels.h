@@ -53,10 +53,12 @@ struct TkActQ8 { /* quantised-activation buffers for one K */
     int8_t* abs; /* (l, h) images of the sub-block sums, 256 B per 256-block */
     uint16_t* abs16; /* (hh, ll) f16 images of the same sums, 512 B per 256-block: the batched kernel's one-MFMA min term */
     size_t aq_ts, ad_ts, abs_ts; /* M-tile strides */
-    /* f16-weight matrices (fp16 checkpoints) consume the activations as f32 values rounded through f16 — what a CPU engine's f16 matmul
-     * does to its f32 input; null when the model has no such matrix */
+    /* float-weight matrices (F16 / BF16 / F32 checkpoints) consume the activations as f32 values rounded through the weight type — what a CPU
+     * engine's matmul does to its f32 input (ggml's vec_dot_type: F16 for F16, BF16 for BF16, none for F32); null when the model has no such
+     * matrix */
     float* af;    /* the tiled GEMM's operand image (csrc/nn/tk_gemm_tiled.h): [M-tile][K / 16][4 g][16 rows][4 t] floats, k = 16 j + 4 t + g */
-    size_t af_ts; /* floats between M-tiles = 16 K */
+    uint32_t af_ts;   /* floats between M-tiles = 16 K */
+    int32_t af_round; /* TkRound (common/tk_exact_math.h): the image's rounding; one per model.  (The two share the eight bytes af_ts had alone) */
 };
 
 
@@ -65,12 +67,15 @@ void tk_launch_synth_blocks(int type, uint64_t seed, uint64_t tensor_id, int64_t
 void tk_launch_synth_f32(uint64_t seed, uint64_t tensor_id, int64_t n, float* out, hipStream_t s);
 /* W += scale (B A) on a matrix in GGUF layout (a lora_merge type of tk_type_desc_of), quantised back to its own type; A [r][K], B [rows][r] on the device.
  * false: arguments the kernel does not take (type, K % 256, more than 2^31 blocks) */
+/* F16 / BF16 / F32 (one value per "block"): the sum is stored through tk_f32_to_f16 / tk_f32_to_bf16 / as it is */
 bool tk_launch_lora_merge(int type, void* blocks, int64_t rows, int64_t K, const float* A, const float* B, int r, float scale, hipStream_t s);
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s);
 
 /* step kernels */
 void tk_launch_embed(const void* embd, int type /* a token_embd type of tk_type_desc_of */, int D, const int32_t* tok, int nrows, float* x, hipStream_t s);
 void tk_launch_synth_f16(uint64_t seed, uint64_t tensor_id, int64_t n, float scale, uint16_t* out, hipStream_t s);
+/* scale * tk_synth_normal stored as `type`: TK_TYPE_BF16 through tk_f32_to_bf16 (uint16 out), TK_TYPE_F32 unconverted (float out) */
+void tk_launch_synth_float(int type, uint64_t seed, uint64_t tensor_id, int64_t n, float scale, void* out, hipStream_t s);
 void tk_launch_rmsnorm_q8(float* x, const float* partial, int ks, int n_total_partial, const float* w, float eps, int D, int nrows,
                           TkActQ8 out, hipStream_t s);
 void tk_launch_residual_fold(float* x, const float* partial, int ks, int n_total, int D, int nrows, hipStream_t s);

@@ -112,6 +112,16 @@ __global__ void k_synth_f16(uint64_t seed, uint64_t tid, int64_t n, float scale,
 void tk_launch_synth_f16(uint64_t seed, uint64_t tensor_id, int64_t n, float scale, uint16_t* out, hipStream_t s) {
     hipLaunchKernelGGL(k_synth_f16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, seed, tensor_id, n, scale, out);
 }
+__global__ void k_synth_float(int type, uint64_t seed, uint64_t tid, int64_t n, float scale, void* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = scale * tk_synth_normal(seed, tid, (uint64_t)i);
+    if (type == TK_TYPE_BF16) ((uint16_t*)out)[i] = tk_f32_to_bf16(v);
+    else ((float*)out)[i] = v;
+}
+void tk_launch_synth_float(int type, uint64_t seed, uint64_t tensor_id, int64_t n, float scale, void* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_synth_float, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, type, seed, tensor_id, n, scale, out);
+}
 
 void tk_launch_synth_blocks(int type, uint64_t seed, uint64_t tensor_id, int64_t nblocks, float scale, void* out, hipStream_t s) {
     int64_t grid = (nblocks + 63) / 64;
@@ -136,6 +146,8 @@ __global__ __launch_bounds__(64) void k_lora_merge(int type, void* blocks, int64
         float w;
         if (type == TK_TYPE_Q4_K) w = tk_q4k_dequant((const tk_block_q4_K*)blocks + b, e);
         else if (type == TK_TYPE_Q6_K) w = tk_q6k_dequant((const tk_block_q6_K*)blocks + b, e);
+        else if (type == TK_TYPE_BF16) w = tk_bf16_to_f32(((const uint16_t*)blocks)[b * 256 + e]);
+        else if (type == TK_TYPE_F32) w = ((const float*)blocks)[b * 256 + e];
         else w = tk_f16_to_f32(((const uint16_t*)blocks)[b * 256 + e]);
         float delta = 0.0f;
         for (int j = 0; j < r; ++j) delta = tk_fmaf(B[n * r + j], A[(int64_t)j * K + k0 + e], delta);
@@ -144,6 +156,10 @@ __global__ __launch_bounds__(64) void k_lora_merge(int type, void* blocks, int64
     __syncthreads();
     if (type == TK_TYPE_F16) {
         for (int e = lane; e < 256; e += 64) ((uint16_t*)blocks)[b * 256 + e] = tk_f32_to_f16(x[e]);
+    } else if (type == TK_TYPE_BF16) {
+        for (int e = lane; e < 256; e += 64) ((uint16_t*)blocks)[b * 256 + e] = tk_f32_to_bf16(x[e]);
+    } else if (type == TK_TYPE_F32) {
+        for (int e = lane; e < 256; e += 64) ((float*)blocks)[b * 256 + e] = x[e];
     } else if (lane == 0) {
         if (type == TK_TYPE_Q4_K) { tk_block_q4_K blk; tk_quantize_q4_K(x, &blk); ((tk_block_q4_K*)blocks)[b] = blk; }
         else { tk_block_q6_K blk; tk_quantize_q6_K(x, &blk); ((tk_block_q6_K*)blocks)[b] = blk; }
@@ -493,6 +509,10 @@ __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, f
     if (i >= D) return;
     if (type == TK_TYPE_F16) {
         x[(int64_t)r * D + i] = tk_f16_to_f32(((const uint16_t*)embd)[(int64_t)tok[r] * D + i]);
+    } else if (type == TK_TYPE_BF16) {
+        x[(int64_t)r * D + i] = tk_bf16_to_f32(((const uint16_t*)embd)[(int64_t)tok[r] * D + i]);
+    } else if (type == TK_TYPE_F32) {
+        x[(int64_t)r * D + i] = ((const float*)embd)[(int64_t)tok[r] * D + i];
     } else if (type == TK_TYPE_Q5_K) {
         const tk_block_q5_K* row = (const tk_block_q5_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q5k_dequant(row + i / 256, i % 256);
@@ -558,12 +578,12 @@ __device__ __forceinline__ float block_sum256(float v, float* red /* >= 4 floats
  * (lane order == chunk order), so the block amax / sub-block sums come from shuffles.
  */
 __device__ __forceinline__ void quantize_chunk8(const float* v, int c, int slot, TkActQ8 out) {
-    if (out.af) { /* the f16-weight matmuls' input: the same values rounded through f16, in the tiled GEMM's operand-image order (csrc/nn/tk_gemm_tiled.h) */
+    if (out.af) { /* the float-weight matmuls' input: the same values rounded through the model's float type (out.af_round), in the tiled GEMM's operand-image order (csrc/nn/tk_gemm_tiled.h) */
         float* dst = out.af + (size_t)(slot >> 4) * out.af_ts + (size_t)(c >> 1) * 256 + (size_t)(slot & 15) * 4;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int k16 = 8 * (c & 1) + i; /* position inside the group of 16: g = k16 % 4, t = k16 / 4 */
-            dst[(k16 & 3) * 64 + (k16 >> 2)] = tk_f16_to_f32(tk_f32_to_f16(v[i]));
+            dst[(k16 & 3) * 64 + (k16 >> 2)] = tk_round_through(v[i], out.af_round);
         }
     }
     /* ggml's quantize_row_q8_K_ref: the signed value of the block's FIRST element of largest magnitude (element index = 8 x chunk-in-block + i),

@@ -2,8 +2,8 @@
  * tk_gemm_tiled.h — C[rows][N] = A[rows][K] x W[N][K]^T on the exact fp32 MFMA (v_mfma_f32_16x16x4_f32: an fma chain over its four k,
  * bitwise) with BOTH operands laid out for the matrix cores ahead of time:
  *   W (a model's weights, constant): tiled once at load time — per 16 output columns and 32 k one contiguous piece, 64 lanes x 8 values;
- *     lane (n = l % 16, g = l / 16) holds k = 32 c + 4 t + g, t = 0 .. 7.  f16 values (16 B per lane: fp16 LLM checkpoints) or f32 values
- *     (32 B per lane: Whisper linears).  Rows beyond N in the last tile are zero.
+ *     lane (n = l % 16, g = l / 16) holds k = 32 c + 4 t + g, t = 0 .. 7.  f16 or bf16 values (16 B per lane: fp16 / bf16 LLM checkpoints) or
+ *     f32 values (32 B per lane: Whisper linears, f32 LLM checkpoints).  Rows beyond N in the last tile are zero.
  *   A (activations): an operand image [M-tile of 16 rows][K / 16][4 g][16 rows][4 t] floats, element (row, k) with k = 16 j + 4 t + g.
  *     Producers either write it directly (the LLM's norm / activation kernels, csrc/llm/tk_llm_kernels.hip: quantize_chunk8) or
  *     tk_launch_pack_a() converts a row-major matrix.
@@ -31,7 +31,7 @@ struct TkTiledGemm {
     const uint8_t* tiles[3]; /* up to three weight matrices side by side in N (q | k | v) */
     int row_tiles[3];
     int nseg;
-    int wbytes;              /* 2: f16 tiles, 4: f32 tiles */
+    int wbytes;              /* 2: f16 or bf16 tiles, 4: f32 tiles */
     int K, ks;
     int ldc;                 /* row pitch of out (and of the K-split slabs) */
     int n_valid;             /* columns actually stored (N; the last tile may be padding) */
@@ -53,18 +53,22 @@ struct TkTiledGemm {
     int seg_ldc[3];
     const float* seg_bias[3];
     int seg_n[3];
+    /* wbytes == 2: the 2-byte values are bfloat16 (value = bits << 16) instead of IEEE f16; any ks.  (Read by the launcher only, and placed
+     * where the structure had four bytes of padding: the kernels' argument layout is what it was.) */
+    int bf16;
     /* c_img: the output is ALSO written as the operand image of the next linear layer (K = n_valid), so no pack launch follows */
     float* c_img;
 };
 
 /* false (nothing launched): K / ks is not a multiple of the ring granularity (128 k; 64 k from 129 rows per block on) or a field is inconsistent */
 bool tk_launch_gemm_tiled(const TkTiledGemm& g, hipStream_t s);
-/* row-major f16 / f32 [N][K] (device) -> tiles; N is padded up to a multiple of 16 with zero rows, K must be a multiple of 32 */
+/* row-major f16 / bf16 / f32 [N][K] (device) -> tiles; N is padded up to a multiple of 16 with zero rows, K must be a multiple of 32 */
 size_t tk_tiled_weight_bytes(int64_t N, int64_t K, int wbytes);
 void tk_launch_tile_weights(const void* src, int wbytes, int64_t N, int64_t K, uint8_t* tiles, hipStream_t s);
-/* row-major A [rows][lda] (device) -> operand image; round_f16: values rounded through f16 on the way (fp16-checkpoint semantics) */
+/* row-major A [rows][lda] (device) -> operand image; round (TkRound, common/tk_exact_math.h): values rounded through f16 or bf16 on the way
+ * (fp16- / bf16-checkpoint semantics), TK_ROUND_NONE = as they are */
 size_t tk_a_image_floats(int64_t rows, int64_t K);
-void tk_launch_pack_a(const float* A, int64_t rows, int K, int lda, int round_f16, float* img, hipStream_t s);
+void tk_launch_pack_a(const float* A, int64_t rows, int K, int lda, int round, float* img, hipStream_t s);
 /* opts the kernels into their dynamic LDS on the calling thread's current device; idempotent, thread-safe */
 bool tk_gemm_tiled_prepare_device();
 

@@ -37,10 +37,11 @@ __device__ __forceinline__ float tw_act(float v, int act) {
     }
 }
 
-/* WB = bytes per weight value (2: f16, 4: f32); MT = M-tiles per workgroup.  (Twelve weight pieces in flight for the Whisper decoder's
+/* WB = bytes per weight value (2: f16 or bf16, 4: f32); BF (WB == 2 only): the 2-byte values are bfloat16 — the fp32 value is the bits
+ * shifted into the upper half, a mask or a shift per value and no convert; MT = M-tiles per workgroup.  (Twelve weight pieces in flight for the Whisper decoder's
  * K = 384 launches — one round trip to the weights instead of three — measured 20 % SLOWER per launch: the whole activation image must
  * then land before the first MFMA, profiles/r04_perception.txt.) */
-template <int MT, int WB, int PF /* weight pieces in flight per wave; a ring slot holds a multiple of PF chunks (the launcher's rk), so piece c sits in register set c % PF */>
+template <int MT, int WB, int PF /* weight pieces in flight per wave; a ring slot holds a multiple of PF chunks (the launcher's rk), so piece c sits in register set c % PF */, bool BF = false>
 __global__ __launch_bounds__(512) void k_gemm_tiled(TkTiledGemm a, int groups, int total_row_tiles, int rk /* k per ring slot */, int slot_bytes /* ring slot pitch */) {
     constexpr int LPC = WB == 4 ? 2 : 1; /* 16-byte requests per piece and lane */
     constexpr int PIECE = 512 * WB;      /* bytes of one (row tile, 32 k) piece */
@@ -107,7 +108,11 @@ __global__ __launch_bounds__(512) void k_gemm_tiled(TkTiledGemm a, int groups, i
             for (int u = 0; u < PF; ++u) {
                 const int c = s * cps + cc + u;
                 float wf[8];
-                if (WB == 2) {
+                if (WB == 2 && BF) {
+                    const uint4 w = wq[u][0];
+                    wf[0] = __uint_as_float(w.x << 16); wf[1] = __uint_as_float(w.x & 0xffff0000u); wf[2] = __uint_as_float(w.y << 16); wf[3] = __uint_as_float(w.y & 0xffff0000u);
+                    wf[4] = __uint_as_float(w.z << 16); wf[5] = __uint_as_float(w.z & 0xffff0000u); wf[6] = __uint_as_float(w.w << 16); wf[7] = __uint_as_float(w.w & 0xffff0000u);
+                } else if (WB == 2) {
                     const uint4 w = wq[u][0];
                     wf[0] = tw_f16(w.x & 0xffffu); wf[1] = tw_f16(w.x >> 16); wf[2] = tw_f16(w.y & 0xffffu); wf[3] = tw_f16(w.y >> 16);
                     wf[4] = tw_f16(w.z & 0xffffu); wf[5] = tw_f16(w.z >> 16); wf[6] = tw_f16(w.w & 0xffffu); wf[7] = tw_f16(w.w >> 16);
@@ -235,7 +240,7 @@ void tk_launch_tile_weights(const void* src, int wbytes, int64_t N, int64_t K, u
 }
 
 /* one thread per image element (coalesced 16-byte stores); rows beyond `rows` read as zero */
-__global__ void k_pack_a(const float* A, int64_t rows, int K, int lda, int round_f16, float* img) {
+__global__ void k_pack_a(const float* A, int64_t rows, int K, int lda, int round, float* img) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; /* index of a float4 of the image */
     const int64_t mtiles = (rows + 15) / 16, per_tile = (int64_t)K * 4; /* float4 per M-tile = 16 K / 4 */
     if (i >= mtiles * per_tile) return;
@@ -248,7 +253,7 @@ __global__ void k_pack_a(const float* A, int64_t rows, int K, int lda, int round
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const float x = A[row * lda + 16 * j + 4 * t + g];
-            v[t] = round_f16 ? tk_f16_to_f32(tk_f32_to_f16(x)) : x;
+            v[t] = tk_round_through(x, round);
         }
     }
     *(v4f*)(img + i * 4) = v;
@@ -256,9 +261,9 @@ __global__ void k_pack_a(const float* A, int64_t rows, int K, int lda, int round
 
 size_t tk_a_image_floats(int64_t rows, int64_t K) { return (size_t)((rows + 15) / 16 * 16) * (size_t)K; }
 
-void tk_launch_pack_a(const float* A, int64_t rows, int K, int lda, int round_f16, float* img, hipStream_t s) {
+void tk_launch_pack_a(const float* A, int64_t rows, int K, int lda, int round, float* img, hipStream_t s) {
     const int64_t n4 = (rows + 15) / 16 * (int64_t)K * 4;
-    hipLaunchKernelGGL(k_pack_a, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, A, rows, K, lda, round_f16, img);
+    hipLaunchKernelGGL(k_pack_a, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, A, rows, K, lda, round, img);
 }
 
 /* ---- launch ---- */
@@ -287,7 +292,7 @@ bool tk_gemm_tiled_prepare_device() {
     if (g_tw_opted[dev].load(std::memory_order_acquire)) return true;
     std::lock_guard<std::mutex> lk(g_tw_mu);
     hipError_t e = hipSuccess;
-#define TK_TW_OPT(MTV, PFV) do { if (e == hipSuccess) e = tw_opt_in(k_gemm_tiled<MTV, 2, PFV>); if (e == hipSuccess) e = tw_opt_in(k_gemm_tiled<MTV, 4, PFV>); } while (0)
+#define TK_TW_OPT(MTV, PFV) do { if (e == hipSuccess) e = tw_opt_in(k_gemm_tiled<MTV, 2, PFV>); if (e == hipSuccess) e = tw_opt_in(k_gemm_tiled<MTV, 2, PFV, true>); if (e == hipSuccess) e = tw_opt_in(k_gemm_tiled<MTV, 4, PFV>); } while (0)
     TK_TW_OPT(1, 4); TK_TW_OPT(2, 4); TK_TW_OPT(4, 4); TK_TW_OPT(8, 4); TK_TW_OPT(16, 2); TK_TW_OPT(8, 2); TK_TW_OPT(6, 2);
 #undef TK_TW_OPT
     if (e != hipSuccess) return false;
@@ -346,8 +351,8 @@ bool tk_launch_gemm_tiled(const TkTiledGemm& a, hipStream_t s) {
     if (Kr % rk) return false;
     const int slot_bytes = twin ? slot_kib * 1024 : TK_TW_SLOT_BYTES;
     const size_t ldsb = (size_t)2 * slot_bytes;
-#define TK_TW_LAUNCH(MTV, WBV, PFV) hipLaunchKernelGGL((k_gemm_tiled<MTV, WBV, PFV>), dim3(groups * a.ks, ny), dim3(64 * waves), ldsb, s, a, groups, row_tiles, rk, slot_bytes)
-#define TK_TW_WB(MTV, PFV) do { if (a.wbytes == 2) TK_TW_LAUNCH(MTV, 2, PFV); else TK_TW_LAUNCH(MTV, 4, PFV); } while (0)
+#define TK_TW_LAUNCH(MTV, WBV, PFV, BFV) hipLaunchKernelGGL((k_gemm_tiled<MTV, WBV, PFV, BFV>), dim3(groups * a.ks, ny), dim3(64 * waves), ldsb, s, a, groups, row_tiles, rk, slot_bytes)
+#define TK_TW_WB(MTV, PFV) do { if (a.wbytes == 2 && a.bf16) TK_TW_LAUNCH(MTV, 2, PFV, true); else if (a.wbytes == 2) TK_TW_LAUNCH(MTV, 2, PFV, false); else TK_TW_LAUNCH(MTV, 4, PFV, false); } while (0)
     switch (mt) {
         case 1: TK_TW_WB(1, 4); break;
         case 2: TK_TW_WB(2, 4); break;

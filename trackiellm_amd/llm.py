@@ -10,6 +10,7 @@ from ._lib import check, lib
 TYPE_F32, TYPE_F16, TYPE_Q4_0, TYPE_Q5_0, TYPE_Q8_0, TYPE_Q2_K, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 0, 1, 2, 6, 8, 10, 11, 12, 13, 14
 TYPE_IQ4_NL, TYPE_IQ4_XS = 20, 23
 TYPE_Q4_1, TYPE_Q5_1 = 3, 7
+TYPE_BF16 = 30  # with TYPE_F32 and TYPE_F16 the float matrix types; a model's matrices hold at most one of the three
 FTYPE_Q4_1, FTYPE_Q5_1 = 3, 9  # GGUF metadata only: fill_synthetic refuses them, fill_synthetic_type(TYPE_Q4_1 / TYPE_Q5_1) makes such models
 FTYPE_IQ4_NL, FTYPE_IQ4_XS = 25, 30
 FTYPE_Q4_0, FTYPE_Q5_0, FTYPE_Q8_0 = 2, 8, 7
@@ -85,6 +86,30 @@ def gemv_probe(ttype, blocks, rows, K, ks, x, device=0):
     return y
 
 
+def convert_bf16(x):
+    """the build's float32 -> bfloat16 rounding on the host, no GPU (tk_mi355x_convert_bf16): uint16 bits, x's shape"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty(x.shape, np.uint16)
+    lib().tk_mi355x_convert_bf16.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    check(lib().tk_mi355x_convert_bf16(_p(x), x.size, _p(out)))
+    return out
+
+
+def matmul_float_probe(ttype, w, K, ks, x, seg_rows=None, device=0):
+    """one production float matmul (tk_mi355x_llm_matmul_float_probe): w [rows][K] as uint16 bits (TYPE_F16, TYPE_BF16) or float32 (TYPE_F32), split into
+    the segments seg_rows (default: one) that ride side by side in one launch, against x [nrows][K] with K split ks ways; returns y [nrows][rows] float32"""
+    w = np.ascontiguousarray(w, dtype=np.float32 if ttype == TYPE_F32 else np.uint16).reshape(-1, K)
+    rows = w.shape[0]
+    seg = np.asarray([rows] if seg_rows is None else list(seg_rows), np.int32)
+    segs = (C.c_int32 * 3)(*([int(v) for v in seg] + [0] * (3 - len(seg))))
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, K)
+    y = np.empty((x.shape[0], rows), np.float32)
+    lib().tk_mi355x_llm_matmul_float_probe.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                       C.c_void_p, C.c_void_p]
+    check(lib().tk_mi355x_llm_matmul_float_probe(device, ttype, _p(w), rows, K, ks, len(seg), segs, x.shape[0], _p(x), _p(y)))
+    return y
+
+
 def attention_plan(nrows, n_head, n_kv_head, head_dim, max_ctx, fused=True, device=0, top_position=None):
     """the attention launch a pass takes on `device`: (kernel, query heads per workgroup, positions per slot / resident chunk, slots);
     kernel 0 = k_attention, 1 = k_attention_narrow, 2 = k_attention_prefill, 3 = the long-context decode form (tk_mi355x_attention_plan;
@@ -142,6 +167,11 @@ class LlmModel:
             return self
         fn = lib().tk_mi355x_llm_model_fill_synthetic_f16 if f16 else lib().tk_mi355x_llm_model_fill_synthetic
         check(fn(self.h, C.c_uint64(seed)))
+        return self
+
+    def fill_synthetic_float(self, seed, ttype):
+        """the float checkpoint recipe in TYPE_BF16 or TYPE_F32 (fill_synthetic(f16=True) is the TYPE_F16 one): every matrix and token_embd `ttype`, norms F32"""
+        check(lib().tk_mi355x_llm_model_fill_synthetic_float(self.h, C.c_uint64(seed), int(ttype)))
         return self
 
     def fill_synthetic_type(self, seed, ttype):
