@@ -62,20 +62,21 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_matmul_float_probe(int device,
  * for layers < n_layer / 8) — this build's definition of the two, files load by each tensor's own type regardless —, 11 Q3_K_S (every matrix and token_embd Q3_K), 12 Q3_K_M (Q3_K;
  * attn_v Q5_K for layers < 2 else Q4_K, attn_output Q4_K, ffn_down Q5_K for layers < n_layer / 16 else Q4_K), 14 Q4_K_S (Q4_K; Q5_K for
  * attn_v of layers < 4 and ffn_down of layers < n_layer / 8), 15 Q4_K_M (= fill_synthetic), 16 Q5_K_S (every matrix and token_embd Q5_K),
- * 17 Q5_K_M (Q4_K_M with Q5_K in place of Q4_K); output is Q6_K in all eight; 7 Q8_0 (every matrix, token_embd and output Q8_0); 2 Q4_0, 8 Q5_0, 25 IQ4_NL and 30 IQ4_XS (every layer matrix and token_embd in the base type, output Q6_K).  Other values: TK_ERROR_INVALID_ARGUMENT — among them 13 Q3_K_L
+ * 17 Q5_K_M (Q4_K_M with Q5_K in place of Q4_K); output is Q6_K in all eight; 7 Q8_0 (every matrix, token_embd and output Q8_0); 2 Q4_0, 8 Q5_0, 25 IQ4_NL and 30 IQ4_XS (every layer matrix and token_embd in the base type, output Q6_K); 36 TQ1_0 and 37 TQ2_0 (llama.cpp's recipe for the ternary types: every layer matrix in the base type, token_embd Q4_K, output Q6_K).  Other values: TK_ERROR_INVALID_ARGUMENT — among them 13 Q3_K_L
  * (Q3_K with Q5_K attn_v, attn_output and ffn_down), which has no synthetic recipe; Q3_K_L FILES load all the same, since loading goes by
- * each tensor's own type and any mix of Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_NL / IQ4_XS tensors beside one of F16 / BF16 / F32 is accepted
+ * each tensor's own type and any mix of Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / IQ4_NL / IQ4_XS / TQ1_0 / TQ2_0 tensors beside one of F16 / BF16 / F32 is accepted
  * (file type 18, all Q6_K with a Q6_K token_embd, among them; it has no synthetic recipe either).
  * Loader names of the Q2_K recipes: synthetic://mistral-7b-q2k, synthetic://mistral-7b-q2ks, synthetic://tiny-q2k, synthetic://tiny-q2ks; of
  * the Q8_0 recipe: synthetic://mistral-7b-q80, synthetic://tiny-q80; of the Q4_0 / Q5_0 recipes: synthetic://mistral-7b-q40, synthetic://tiny-q40,
  * synthetic://mistral-7b-q50, synthetic://tiny-q50; of the IQ4_NL / IQ4_XS recipes: synthetic://mistral-7b-iq4nl, synthetic://tiny-iq4nl,
- * synthetic://mistral-7b-iq4xs, synthetic://tiny-iq4xs.  File types 3 (Q4_1) and 9 (Q5_1) have no recipe here: tk_mi355x_llm_model_fill_synthetic_type */
+ * synthetic://mistral-7b-iq4xs, synthetic://tiny-iq4xs; of the ternary recipes: synthetic://mistral-7b-tq10, synthetic://tiny-tq10,
+ * synthetic://mistral-7b-tq20, synthetic://tiny-tq20.  File types 3 (Q4_1) and 9 (Q5_1) have no recipe here: tk_mi355x_llm_model_fill_synthetic_type */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_fill_synthetic_ftype(tk_mi355x_llm_model_t* m, uint64_t seed, int ftype);
 /* seeded weights by TENSOR type: every layer matrix and token_embd of GGML type `ggml_type`, output Q6_K, norms F32.  Takes 3 (Q4_1) and
  * 7 (Q5_1), the types whose file types fill_synthetic_ftype refuses; any other value: TK_ERROR_INVALID_ARGUMENT.
  * Loader names: synthetic://mistral-7b-q41, synthetic://tiny-q41, synthetic://mistral-7b-q51, synthetic://tiny-q51 */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_fill_synthetic_type(tk_mi355x_llm_model_t* m, uint64_t seed, int ggml_type);
-/* test / measurement entry: one production mat-vec of `rows` x K raw GGUF blocks of `type` (2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS; rows % 64 == 0,
+/* test / measurement entry: one production mat-vec of `rows` x K raw GGUF blocks of `type` (2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS, 34 TQ1_0, 35 TQ2_0; rows % 64 == 0,
  * K % (256 ks) == 0, ks <= 8) against x [nrows][K] (nrows <= 256): the blocks are repacked, x is quantised by the production Q8_K kernel,
  * the production launcher runs at width nrows with K split ks ways, and the ks partial sums are added in ascending order into y [nrows][rows] */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, int ks, int nrows,
@@ -98,13 +99,19 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_q5_1(const float* 
  * is not restated).  Entries of their own for the same reason: types 20 and 23 stay TK_ERROR_INVALID_ARGUMENT in tk_mi355x_quantize_blocks */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_iq4_nl(const float* x, int64_t n_blocks, void* out);
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_iq4_xs(const float* x, int64_t n_blocks, void* out);
+/* TQ1_0 / TQ2_0 (GGML types 34 and 35, the ternary types): x [n_blocks][256] floats -> n_blocks 54- / 66-byte blocks, ggml's
+ * quantize_row_tq1_0_ref / quantize_row_tq2_0_ref value for value (d = max |x| stored as f16, trits lroundf(x / max |x|) + 1, five to a
+ * base-3 byte or four to a 2-bit byte).  Types 34 and 35 stay TK_ERROR_INVALID_ARGUMENT in tk_mi355x_quantize_blocks */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_tq1_0(const float* x, int64_t n_blocks, void* out);
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_tq2_0(const float* x, int64_t n_blocks, void* out);
 /* the same for Q2_K (GGML type 10): x [n_blocks][256] floats -> n_blocks 84-byte blocks.  An entry of its own because the set of types
  * tk_mi355x_quantize_blocks takes is fixed — callers rely on type 10 being TK_ERROR_INVALID_ARGUMENT there */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_quantize_blocks_q2k(const float* x, int64_t n_blocks, void* out);
 /* tensor in GGUF block layout; layer = -1 for {0 token_embd, 1 output_norm, 2 output}, else
- * {0 attn_norm,1 q,2 k,3 v,4 o,5 ffn_norm,6 gate,7 up,8 down}; type = ggml type id (0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS, 30 BF16).
+ * {0 attn_norm,1 q,2 k,3 v,4 o,5 ffn_norm,6 gate,7 up,8 down}; type = ggml type id (0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS, 30 BF16, 34 TQ1_0, 35 TQ2_0).
  * token_embd takes every one of them; a matrix of F32 / F16 / BF16 needs rows % 16 == 0 and columns % 32 == 0, and a model's matrices hold at most
- * one of the three (tk_mi355x_llm_model_fill_synthetic_float); a Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, IQ4_NL, IQ4_XS or k-quant tensor needs columns % 256 == 0 */
+ * one of the three (tk_mi355x_llm_model_fill_synthetic_float); a Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, IQ4_NL, IQ4_XS, TQ1_0, TQ2_0 or k-quant tensor needs columns % 256 == 0.
+ * A TQ1_0 matrix is installed as TQ2_0 tiles (its base-3 bytes decoded once, here): it runs the TQ2_0 kernels and holds 66, not 54, bytes per 256 weights */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_set_tensor(tk_mi355x_llm_model_t* m, int layer, int which, int type, const void* data,
                                                                    size_t nbytes);
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_load_gguf(tk_mi355x_llm_model_t** out, const char* path, int device);
@@ -127,6 +134,7 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_gguf_probe(const char* path, tk_mi
 /* token ids of `text` under the vocabulary of a GGUF file (CPU only); returns the count (may exceed cap) or -1 */
 TK_API int tk_mi355x_gguf_tokenize(const char* path, const char* text, int add_bos, int32_t* ids, int cap);
 TK_API void tk_mi355x_llm_model_get_hparams(const tk_mi355x_llm_model_t* m, tk_mi355x_llm_hparams_t* out);
+/* bytes of the matrices as installed = what a decode step streams (a TQ1_0 matrix counts its TQ2_0 tiles: 66 bytes per 256 weights, not the file's 54) */
 TK_API uint64_t tk_mi355x_llm_model_weight_bytes(const tk_mi355x_llm_model_t* m);
 TK_API void tk_mi355x_llm_model_destroy(tk_mi355x_llm_model_t** m);
 

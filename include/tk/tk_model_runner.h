@@ -10,13 +10,14 @@
  * tk_runner_helpers.c:78-138; sampling is argmax.
  *
  * model_path forms accepted by tk_model_loader_load_model:
- *   "/path/model.gguf"                         GGUF v3, llama arch, F32/F16/BF16/Q4_0/Q4_1/Q5_0/Q5_1/Q8_0/Q2_K/Q3_K/Q4_K/Q5_K/Q6_K/IQ4_NL/IQ4_XS tensors
+ *   "/path/model.gguf"                         GGUF v3, llama arch, F32/F16/BF16/Q4_0/Q4_1/Q5_0/Q5_1/Q8_0/Q2_K/Q3_K/Q4_K/Q5_K/Q6_K/IQ4_NL/IQ4_XS/TQ1_0/TQ2_0 tensors
  *   "synthetic://mistral-7b?seed=4"            Mistral-7B-v0.1-shaped, Q4_K_M recipe, seeded weights
  *   "synthetic://tiny?seed=4"                  2-layer test geometry
  *   "synthetic://mistral-7b-q2k", "...-q2ks"   the same shapes in the Q2_K / Q2_K_S recipes (also tiny-q2k, tiny-q2ks)
  *   "synthetic://mistral-7b-q80"               the same shapes with every matrix, token_embd and output Q8_0 (also tiny-q80)
  *   "synthetic://mistral-7b-q40", "...-q50"    the same shapes with every layer matrix and token_embd Q4_0 / Q5_0, output Q6_K (also tiny-q40, tiny-q50)
  *   "synthetic://mistral-7b-iq4nl", "...-iq4xs" the same with IQ4_NL / IQ4_XS as the base type (also tiny-iq4nl, tiny-iq4xs)
+ *   "synthetic://mistral-7b-tq10", "...-tq20"  the ternary recipes: every layer matrix TQ1_0 / TQ2_0, token_embd Q4_K, output Q6_K (also tiny-tq10, tiny-tq20)
  *   "synthetic://mistral-7b-q41", "...-q51"    the same with Q4_1 / Q5_1 as the base type (also tiny-q41, tiny-q51)
  */
 #ifndef TK_MI355X_MODEL_RUNNER_H

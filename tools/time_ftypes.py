@@ -7,8 +7,8 @@ weight bytes plus activation and slab bytes over kernel time).  Per width and re
 32-token prompt per sequence, 4 warm-up steps, then greedy steps through the captured pass, HIP events around the loop) and its ratio to
 Q4_K_M's median; for Q4_K_M also the spread of its repeats, the yardstick for every ratio beside it.
 The float recipes (F16, BF16, F32: every matrix and token_embd in the type, on the exact fp32 MFMA GEMM) have no W4A8 mat-vec to time alone; with
-F16 among the recipes, BF16 and F32 are also printed as ratios to F16's median.
-    python tools/time_ftypes.py [steps [repeats [recipe ...]]]      recipes: IQ4_NL IQ4_XS Q4_0 Q4_1 Q5_0 Q5_1 Q8_0 Q2_K Q2_K_S Q3_K_S Q3_K_M Q4_K_S Q5_K_S Q5_K_M F16 BF16 F32"""
+F16 among the recipes, BF16 and F32 are also printed as ratios to F16's median; TQ1_0 and TQ2_0 also as ratios to Q2_K's and to each other's.
+    python tools/time_ftypes.py [steps [repeats [recipe ...]]]      recipes: TQ1_0 TQ2_0 IQ4_NL IQ4_XS Q4_0 Q4_1 Q5_0 Q5_1 Q8_0 Q2_K Q2_K_S Q3_K_S Q3_K_M Q4_K_S Q5_K_S Q5_K_M F16 BF16 F32"""
 import ctypes as C
 import os
 import sys
@@ -18,7 +18,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import trackiellm_amd as tk  # noqa: E402
 
-FTYPES = {"IQ4_NL": tk.FTYPE_IQ4_NL, "IQ4_XS": tk.FTYPE_IQ4_XS, "Q4_0": tk.FTYPE_Q4_0, "Q5_0": tk.FTYPE_Q5_0, "Q8_0": tk.FTYPE_Q8_0, "Q2_K": tk.FTYPE_Q2_K, "Q2_K_S": tk.FTYPE_Q2_K_S, "Q3_K_S": tk.FTYPE_Q3_K_S, "Q3_K_M": tk.FTYPE_Q3_K_M, "Q4_K_S": tk.FTYPE_Q4_K_S,
+FTYPES = {"TQ1_0": tk.FTYPE_TQ1_0, "TQ2_0": tk.FTYPE_TQ2_0, "IQ4_NL": tk.FTYPE_IQ4_NL, "IQ4_XS": tk.FTYPE_IQ4_XS, "Q4_0": tk.FTYPE_Q4_0, "Q5_0": tk.FTYPE_Q5_0, "Q8_0": tk.FTYPE_Q8_0, "Q2_K": tk.FTYPE_Q2_K, "Q2_K_S": tk.FTYPE_Q2_K_S, "Q3_K_S": tk.FTYPE_Q3_K_S, "Q3_K_M": tk.FTYPE_Q3_K_M, "Q4_K_S": tk.FTYPE_Q4_K_S,
           "Q4_K_M": tk.FTYPE_Q4_K_M, "Q5_K_S": tk.FTYPE_Q5_K_S, "Q5_K_M": tk.FTYPE_Q5_K_M}
 TTYPES = {"Q4_1": tk.TYPE_Q4_1, "Q5_1": tk.TYPE_Q5_1}  # recipes by tensor type (fill_synthetic_type): no file type of fill_synthetic makes them
 FLOATS = {"F16": tk.TYPE_F16, "BF16": tk.TYPE_BF16, "F32": tk.TYPE_F32}  # the float checkpoint recipes (fill_synthetic(f16=True), fill_synthetic_float)
@@ -71,6 +71,12 @@ for rows in WIDTHS:
             f16 = ms[("F16", rows)]
             fm = float(np.median(f16))
             tail += f"; x{med / fm:.3f} of F16 (F16's repeats span {100 * (max(f16) - min(f16)) / fm:.1f} % of its median)"
+        if name in ("TQ1_0", "TQ2_0"):  # against the nearest 2-bit type of the same run, and TQ1_0 (installed as TQ2_0 tiles) against TQ2_0
+            for other in ("Q2_K", "TQ2_0"):
+                if other in names and other != name:
+                    o = ms[(other, rows)]
+                    om = float(np.median(o))
+                    tail += f"; x{med / om:.3f} of {other} ({other}'s repeats span {100 * (max(o) - min(o)) / om:.1f} % of its median)"
         print(f"{name} {rows:3d} rows: {med:.3f} ms per decode step (median of {repeats}), weights at {nbytes[name] / med / 1e9:.2f} TB/s{tail}", flush=True)
 for m in models.values():
     m.close()

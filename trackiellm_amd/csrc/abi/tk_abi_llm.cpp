@@ -176,8 +176,20 @@ tk_error_code_t tk_mi355x_quantize_blocks_iq4_xs(const float* x, int64_t n_block
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_quantize_blocks_tq1_0(const float* x, int64_t n_blocks, void* out) {
+    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
+    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_tq1_0(x + 256 * b, (tk_block_tq1_0*)out + b);
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_quantize_blocks_tq2_0(const float* x, int64_t n_blocks, void* out) {
+    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
+    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_tq2_0(x + 256 * b, (tk_block_tq2_0*)out + b);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_model_fill_synthetic_ftype(tk_mi355x_llm_model_t* m, uint64_t seed, int ftype) {
-    if (!m || !(ftype == 2 || ftype == 8 || ftype == 7 || ftype == 10 || ftype == 11 || ftype == 12 || (ftype >= 14 && ftype <= 17) || ftype == 21 || ftype == 25 || ftype == 30)) return TK_ERROR_INVALID_ARGUMENT;
+    if (!m || !(ftype == 2 || ftype == 8 || ftype == 7 || ftype == 10 || ftype == 11 || ftype == 12 || (ftype >= 14 && ftype <= 17) || ftype == 21 || ftype == 25 || ftype == 30 || ftype == 36 || ftype == 37)) return TK_ERROR_INVALID_ARGUMENT;
     if (!m->model.fill_synthetic(seed, false, ftype)) return fail(TK_ERROR_GPU_ROCM_ERROR, m->model.error);
     return TK_SUCCESS;
 }
@@ -257,6 +269,9 @@ void tk_mi355x_llm_model_get_hparams(const tk_mi355x_llm_model_t* m, tk_mi355x_l
                                    h.ks_qkv, h.ks_o, h.ks_gateup, h.ks_down, h.ks_out};
 }
 
+/* the bytes a decode step streams: the matrices as they are installed.  A TQ1_0 matrix counts the TQ2_0 tile it is installed as, 66 bytes
+ * per 256 weights where its file holds 54: the price of running the 2-bit kernels (a shift and a mask per four weights) in place of a
+ * base-3 decode of several VALU operations per weight inside the W4A8 loops, which nobody has built or measured */
 uint64_t tk_mi355x_llm_model_weight_bytes(const tk_mi355x_llm_model_t* m) {
     if (!m) return 0;
     uint64_t b = m->model.output.bytes;
@@ -774,6 +789,8 @@ tk_error_code_t tk_model_loader_load_model(tk_model_loader_t* loader, const tk_m
         else if (name.size() > 4 && name.compare(name.size() - 4, 4, "-q51") == 0) { gtype = TK_TYPE_Q5_1; name.resize(name.size() - 4); }
         else if (name.size() > 6 && name.compare(name.size() - 6, 6, "-iq4nl") == 0) { ftype = 25; name.resize(name.size() - 6); }
         else if (name.size() > 6 && name.compare(name.size() - 6, 6, "-iq4xs") == 0) { ftype = 30; name.resize(name.size() - 6); }
+        else if (name.size() > 5 && name.compare(name.size() - 5, 5, "-tq10") == 0) { ftype = 36; name.resize(name.size() - 5); } /* the ternary recipes: synthetic://mistral-7b-tq10, synthetic://tiny-tq20 */
+        else if (name.size() > 5 && name.compare(name.size() - 5, 5, "-tq20") == 0) { ftype = 37; name.resize(name.size() - 5); }
         else if (name.size() > 5 && name.compare(name.size() - 5, 5, "-q2ks") == 0) { ftype = 21; name.resize(name.size() - 5); }
         else if (name.size() > 4 && name.compare(name.size() - 4, 4, "-q2k") == 0) { ftype = 10; name.resize(name.size() - 4); }
         if (name == "mistral-7b") h = tk_mi355x_llm_hparams_t{32, 4096, 32, 8, 128, 14336, 32000, 1e-5f, 10000.0f, 0, 0, 0, 0, 1};

@@ -36,6 +36,12 @@
  *   IQ4_XS: 256 weights / 136 B: f16 d, u16 scales_h (little endian), scales_l[4], 128 B of nibbles (sub-block j of 32 weights =
  *         qs[16 j .. 16 j + 15], ordered as an IQ4_NL block).  ls_j = ((scales_l[j / 2] >> 4 (j % 2)) & 15) | ((scales_h >> 2 j) & 3) << 4,
  *         s_j = ls_j - 32 in -32..31, w = (d*s_j)*kv[q], both products exact in fp32 (11 bits times 6, then 17 times 7)
+ *   TQ2_0: 256 weights / 66 B: 64 B of 2-bit codes (weight 128 h + 32 l + m = (qs[32 h + m] >> 2 l) & 3), f16 d LAST.
+ *         w = (c - 1)*d, c in 0..3: the quantiser writes 0..2, code 3 is a valid byte and decodes to +2 d
+ *   TQ1_0: 256 weights / 54 B: 48 B qs and 4 B qh of base-3 digits (five trits a byte, four in qh), f16 d LAST.  Trit n of byte b is
+ *         ((uint16_t)(uint8_t)(b * 3^n) * 3) >> 8, in 0..2 for every byte value; weights 0..159 = trit n of qs[m] at 32 n + m,
+ *         160..239 = trit n of qs[32 + m] at 160 + 16 n + m, 240..255 = trit n of qh[j] at 240 + 4 n + j.   w = (t - 1)*d
+ *         Both are the Q6_K block with the same d, all sixteen scales 1 and q6 = 32 + (t - 1)
  * Host + device code (the quantisers run inside the synthetic-weight kernel
  * and inside the oracle; they are bit-identical by construction).
  */
@@ -65,6 +71,8 @@ enum tk_ggml_type {
     TK_TYPE_IQ4_NL = 20,
     TK_TYPE_IQ4_XS = 23,
     TK_TYPE_BF16 = 30,
+    TK_TYPE_TQ1_0 = 34,
+    TK_TYPE_TQ2_0 = 35,
 };
 
 typedef struct {
@@ -146,6 +154,17 @@ typedef struct {
     uint8_t qs[128];
 } tk_block_iq4_xs; /* 136 B, 256 weights */
 
+typedef struct {
+    uint8_t qs[64];
+    uint16_t d;
+} tk_block_tq2_0; /* 66 B, 256 weights; d is last */
+
+typedef struct {
+    uint8_t qs[48];
+    uint8_t qh[4];
+    uint16_t d;
+} tk_block_tq1_0; /* 54 B, 256 weights; d is last */
+
 /* the non-linear code book of IQ4_NL / IQ4_XS (ggml's published kvalues_iq4nl), indexed by the stored nibble */
 /* -127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113 as the bytes of two constants: a shift and a sign extension on
  * host and device, no table in memory */
@@ -165,7 +184,7 @@ struct tk_type_desc {
     int mask, kernel_index;        /* its bit in the kernels' TYPES argument; its column in k_gemv_fns / k_gemm_fns / k_gemm32_fns */
     bool shares_launch;            /* may ride in one launch beside another such type (the Q4_K | Q6_K kernels); tk_launch_gemv splits any other mix */
     bool token_embd, lora_merge;   /* k_embed decodes it; k_lora_merge re-quantises it */
-    bool host_quantize;            /* tk_mi355x_quantize_blocks takes it (a pinned set: Q2_K, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL and IQ4_XS have entry points of their own) */
+    bool host_quantize;            /* tk_mi355x_quantize_blocks takes it (a pinned set: Q2_K, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL, IQ4_XS, TQ1_0 and TQ2_0 have entry points of their own) */
 };
 TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
     switch (type) {
@@ -185,14 +204,18 @@ TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
         case TK_TYPE_Q6_K: return {"Q6_K", 256,  210,  TK_Q6K_TILE_BYTES, 2,   1,  true,  true,  true,  true};
         case TK_TYPE_IQ4_NL: return {"IQ4_NL", 32, 18, TK_IQ4_NL_TILE_BYTES, 256, 9, false, true, false, false};
         case TK_TYPE_IQ4_XS: return {"IQ4_XS", 256, 136, TK_IQ4_XS_TILE_BYTES, 512, 10, false, true, false, false};
+        /* TQ1_0 is installed as the TQ2_0 tile (k_repack_tq<tk_block_tq1_0> decodes the base-3 bytes once, at load): the same tile bytes, mask and
+         * kernel column, so a TQ1_0 matrix runs the instantiations a TQ2_0 matrix runs and streams 66, not 54, bytes per 256 weights */
+        case TK_TYPE_TQ2_0: return {"TQ2_0", 256, 66, TK_TQ2_0_TILE_BYTES, 4096, 13, false, true, false, false};
+        case TK_TYPE_TQ1_0: return {"TQ1_0", 256, 54, TK_TQ2_0_TILE_BYTES, 4096, 13, false, true, false, false};
         default:           return {nullptr, 1,   4,    0,                 0,   -1, false, false, false, false};
     }
 }
 /* the lists the messages print: kept beside the table, edited with it */
-#define TK_TYPE_NAMES "F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS"
-#define TK_TYPE_NAMES_OR "F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
-#define TK_KQUANT_NAMES_OR "Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL or IQ4_XS"
-#define TK_TOKEN_EMBD_NAMES_OR "Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS, F16, BF16 or F32"
+#define TK_TYPE_NAMES "F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS, TQ1_0, TQ2_0"
+#define TK_TYPE_NAMES_OR "F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS, TQ1_0 or TQ2_0"
+#define TK_KQUANT_NAMES_OR "Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS, TQ1_0 or TQ2_0"
+#define TK_TOKEN_EMBD_NAMES_OR "Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS, TQ1_0, TQ2_0, F16, BF16 or F32"
 #define TK_LORA_MERGE_NAMES_OR "Q4_K, Q6_K, F16, BF16 or F32"
 /* the float matrix types: tiles of the exact fp32 GEMM (nn/tk_gemm_tiled.h), 2 or 4 bytes a weight.  A model holds at most one of them among
  * its matrices: the sessions' operand image carries one rounding (tk_type_float_round) */
@@ -204,19 +227,20 @@ TK_HD constexpr bool tk_type_is_kquant(int type) { return tk_type_desc_of(type).
 TK_HD constexpr size_t tk_type_block_bytes(int type) { return (size_t)tk_type_desc_of(type).block_bytes; }
 TK_HD constexpr size_t tk_type_block_elems(int type) { return (size_t)tk_type_desc_of(type).block_elems; }
 
-/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make thirteen values: the twelve tiled types alone
- * and the one mix of the two shares_launch types, whose kernels pick the tile type per segment at run time. */
-/* the tiled types (tile_bytes != 0), listed: their enum values are not one range (Q4_0 = 2, Q4_1 = 3, Q5_0 = 6, Q5_1 = 7, Q8_0 = 8, the k-quants 10 .. 14, IQ4_NL = 20, IQ4_XS = 23), and a
+/* TYPES of a W4A8 launch = the masks of its segments' types or-ed together.  The launchers make fourteen values: the thirteen tile layouts
+ * alone (TQ1_0 has TQ2_0's) and the one mix of the two shares_launch types, whose kernels pick the tile type per segment at run time. */
+/* the tiled types (tile_bytes != 0), listed: their enum values are not one range (Q4_0 = 2, Q4_1 = 3, Q5_0 = 6, Q5_1 = 7, Q8_0 = 8, the k-quants 10 .. 14, IQ4_NL = 20, IQ4_XS = 23, TQ1_0 = 34, TQ2_0 = 35), and a
  * loop over [first, last] would lean on the types between having no row */
-#define TK_TILED_TYPES 12
+#define TK_TILED_TYPES 14
 TK_HD constexpr int tk_tiled_type(int i) {
     constexpr int types[TK_TILED_TYPES] = {TK_TYPE_Q4_0, TK_TYPE_Q5_0, TK_TYPE_Q8_0, TK_TYPE_Q2_K, TK_TYPE_Q3_K, TK_TYPE_Q4_K, TK_TYPE_Q5_K, TK_TYPE_Q6_K,
-                                             TK_TYPE_IQ4_NL, TK_TYPE_IQ4_XS, TK_TYPE_Q4_1, TK_TYPE_Q5_1};
+                                             TK_TYPE_IQ4_NL, TK_TYPE_IQ4_XS, TK_TYPE_Q4_1, TK_TYPE_Q5_1, TK_TYPE_TQ2_0, TK_TYPE_TQ1_0};
     return types[i];
 }
+
 #define TK_TYPES_Q4K_Q6K (tk_type_desc_of(TK_TYPE_Q4_K).mask | tk_type_desc_of(TK_TYPE_Q6_K).mask)
 #define TK_KERNEL_INDEX_Q4K_Q6K 2
-#define TK_KERNEL_VARIANTS 13
+#define TK_KERNEL_VARIANTS 14
 TK_HD constexpr bool tk_types_has(int types, int type) { return (types & tk_type_desc_of(type).mask) != 0; }
 TK_HD constexpr bool tk_types_is(int types, int type) { return types == tk_type_desc_of(type).mask; }
 /* tile bytes of a single-type launch: a compile-time pitch (tile addresses become scalar base + immediate); 0 for the mix */
@@ -246,9 +270,13 @@ TK_TYPE_ROW_CHECK(TK_TYPE_IQ4_NL, tk_block_iq4_nl, TK_Q32_PER_RUN * 18);
 TK_TYPE_ROW_CHECK(TK_TYPE_IQ4_XS, tk_block_iq4_xs, 144); /* the tile holds the eight sub-block scales as int8 in a 16-byte row tail: 8 B more than the block */
 static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_IQ4_NL).block_elems == 0, "IQ4_NL: a 256-k run must be whole blocks");
 static_assert(sizeof(tk_block_iq4_nl) == sizeof(tk_block_q4_0) && TK_IQ4_NL_TILE_BYTES == TK_Q4_0_TILE_BYTES, "IQ4_NL rides on the Q4_0 repack, fragment and load");
+TK_TYPE_ROW_CHECK(TK_TYPE_TQ2_0, tk_block_tq2_0, 66);
+TK_TYPE_ROW_CHECK(TK_TYPE_TQ1_0, tk_block_tq1_0, 66); /* the tile is TQ2_0's: 2-bit codes, 12 B more than the block's base-3 bytes */
+static_assert(offsetof(tk_block_tq2_0, d) == 64 && offsetof(tk_block_tq1_0, qh) == 48 && offsetof(tk_block_tq1_0, d) == 52, "TQ1_0 / TQ2_0: d is the block's last field");
 #undef TK_TYPE_ROW_CHECK
-/* every tiled type is listed once and nothing else has a tile; every mask is one bit of its own, and the kernel indices of the thirteen
- * TYPES values are 0 .. 12, each once */
+/* every tiled type is listed once and nothing else has a tile; every tile layout's mask is one bit of its own, and the kernel indices of
+ * the fourteen TYPES values are 0 .. 13, each once.  A type installed as another type's tile (TQ1_0 as TQ2_0's) carries that type's mask and has its tile
+ * bytes, mask and index, and the other type is listed before it */
 TK_HD constexpr bool tk_type_table_consistent() {
     int masks = 0, indices = 1 << TK_KERNEL_INDEX_Q4K_Q6K;
     int listed = 0;
@@ -257,6 +285,11 @@ TK_HD constexpr bool tk_type_table_consistent() {
     for (int i = 0; i < TK_TILED_TYPES; ++i) {
         const tk_type_desc d = tk_type_desc_of(tk_tiled_type(i));
         if (d.tile_bytes == 0) return false;
+        if (tk_tiled_type(i) == TK_TYPE_TQ1_0) { /* the one row that repeats a mask: it must repeat the whole column of the type listed before it */
+            const tk_type_desc as = tk_type_desc_of(TK_TYPE_TQ2_0);
+            if (d.tile_bytes != as.tile_bytes || d.mask != as.mask || d.kernel_index != as.kernel_index || (masks & as.mask) == 0) return false;
+            continue;
+        }
         if (d.mask == 0 || (d.mask & (d.mask - 1)) != 0 || (masks & d.mask) != 0) return false;
         if (d.kernel_index < 0 || d.kernel_index >= TK_KERNEL_VARIANTS || ((indices >> d.kernel_index) & 1) != 0) return false;
         masks |= d.mask;
@@ -264,7 +297,7 @@ TK_HD constexpr bool tk_type_table_consistent() {
     }
     return indices == (1 << TK_KERNEL_VARIANTS) - 1;
 }
-static_assert(tk_type_table_consistent(), "tk_type_desc_of: tk_tiled_type must list the rows with a tile, masks must be distinct bits and kernel indices 0 .. 12, each once");
+static_assert(tk_type_table_consistent(), "tk_type_desc_of: tk_tiled_type must list the rows with a tile, masks must be distinct bits and kernel indices 0 .. 13, each once");
 
 /* 6-bit (scale, min) pair j of a Q4_K block */
 TK_HD void tk_q4k_get_scale_min(int j, const uint8_t* q, uint8_t* sc, uint8_t* m) {
@@ -455,6 +488,25 @@ TK_HD void tk_iq4xs_set_scale(tk_block_iq4_xs* b, int j, int s) {
 TK_HD float tk_iq4xs_dequant(const tk_block_iq4_xs* b, int i) {
     return (tk_f16_to_f32(b->d) * (float)tk_iq4xs_scale(b, i >> 5)) * (float)tk_iq4_kv(tk_iq4_quant(b->qs + 16 * (i >> 5), i & 31));
 }
+
+/* TQ2_0: code c in 0..3 of weight i (0..255); w = (c - 1) * d, exact in fp32.  Code 3 decodes to +2 d */
+TK_HD int tk_tq2_0_quant(const tk_block_tq2_0* b, int i) { return (b->qs[32 * (i >> 7) + (i & 31)] >> (2 * ((i >> 5) & 3))) & 3; }
+TK_HD float tk_tq2_0_dequant(const tk_block_tq2_0* b, int i) { return (float)(tk_tq2_0_quant(b, i) - 1) * tk_f16_to_f32(b->d); }
+
+/* trit n (0..4) of a TQ1_0 byte: the byte times 3^n modulo 256, times 3, its ninth and tenth bit.  In 0..2 for every byte value */
+TK_HD constexpr int tk_tq1_0_trit(uint8_t byte, int n) {
+    return (int)(((uint16_t)(uint8_t)(byte * (uint8_t)(0x511B090301ull >> (8 * n))) * 3) >> 8); /* 3^n = 1, 3, 9, 27, 81 */
+}
+static_assert(tk_tq1_0_trit(255, 0) == 2 && tk_tq1_0_trit(255, 1) == 2 && tk_tq1_0_trit(255, 2) == 2 && tk_tq1_0_trit(255, 3) == 2 && tk_tq1_0_trit(255, 4) == 2 &&
+              tk_tq1_0_trit(243, 0) == 2 && tk_tq1_0_trit(243, 1) == 2 && tk_tq1_0_trit(243, 2) == 1 && tk_tq1_0_trit(243, 3) == 1 && tk_tq1_0_trit(243, 4) == 2,
+              "tk_tq1_0_trit: the non-canonical bytes 255 and 243");
+/* TQ1_0: trit t in 0..2 of weight i (0..255): the three segments of the block */
+TK_HD int tk_tq1_0_quant(const tk_block_tq1_0* b, int i) {
+    if (i < 160) return tk_tq1_0_trit(b->qs[i & 31], i >> 5);
+    if (i < 240) return tk_tq1_0_trit(b->qs[32 + ((i - 160) & 15)], (i - 160) >> 4);
+    return tk_tq1_0_trit(b->qh[(i - 240) & 3], (i - 240) >> 2);
+}
+TK_HD float tk_tq1_0_dequant(const tk_block_tq1_0* b, int i) { return (float)(tk_tq1_0_quant(b, i) - 1) * tk_f16_to_f32(b->d); }
 
 /*
  * Deterministic min/max quantisers ("the build's own Q4_K_M recipe").
@@ -838,6 +890,61 @@ TK_HD void tk_quantize_iq4_xs(const float* x, tk_block_iq4_xs* out) {
         const float idl = dl != 0.0f ? tk_divf(1.0f, dl) : 0.0f;
         tk_iq4_pack(x + 32 * j, idl, out->qs + 16 * j);
     }
+}
+
+/* TQ2_0 / TQ1_0: ggml's published quantize_row_tq2_0_ref / quantize_row_tq1_0_ref, value for value, all in binary32: amax = max |x| over
+ * the 256 values, d = amax stored as f16, id = amax ? 1 / amax : 0 from the f32 amax, xi = lroundf(x * id) + 1 in 0..2 (halves away from
+ * zero; |x * id| <= 1 up to rounding and is clamped to that, so the truncation below is exact and xi stays in 0..2).  The loops stay rolled in device code, as IQ4's do */
+TK_HD float tk_tq_amax(const float* x) {
+    float amax = 0.0f;
+    TK_ROLLED
+    for (int i = 0; i < 256; ++i) {
+        const float a = tk_fabsf(x[i]);
+        amax = a > amax ? a : amax;
+    }
+    return amax;
+}
+TK_HD int tk_tq_xi(float x, float id) {
+    float v = x * id;
+    /* an amax below 2^-128 makes id infinite and v +-inf or NaN (0 * inf), where lroundf is unspecified and the truncation below undefined:
+     * such a v is taken as -1 (NaN) or +-1, so host and device make the same bytes.  d is then +0 and every weight decodes to 0 anyway */
+    if (!(v >= -1.0f)) v = -1.0f;
+    if (!(v <= 1.0f)) v = 1.0f;
+    const float t = (float)(int)v, r = v - t;
+    return (int)t + (r >= 0.5f ? 1 : r <= -0.5f ? -1 : 0) + 1;
+}
+TK_HD void tk_quantize_tq2_0(const float* x, tk_block_tq2_0* out) {
+    const float amax = tk_tq_amax(x);
+    const float id = amax != 0.0f ? tk_divf(1.0f, amax) : 0.0f;
+    out->d = tk_f32_to_f16(amax);
+    TK_ROLLED
+    for (int j = 0; j < 64; ++j) { /* byte 32 h + m holds weights 128 h + 32 l + m, l = 0..3 */
+        const float* p = x + 128 * (j >> 5) + (j & 31);
+        int q = 0;
+        TK_ROLLED
+        for (int l = 0; l < 4; ++l) q |= tk_tq_xi(p[32 * l], id) << (2 * l);
+        out->qs[j] = (uint8_t)q;
+    }
+}
+/* one base-3 byte: NT trits taken at x[0], x[stride], ..., the first the most significant, padded to five digits, then
+ * (q * 256 + 242) / 243: the smallest byte whose decode gives the digits back */
+TK_HD uint8_t tk_tq1_0_byte(const float* x, int stride, int nt, float id) {
+    int q = 0;
+    TK_ROLLED
+    for (int n = 0; n < nt; ++n) q = q * 3 + tk_tq_xi(x[stride * n], id);
+    if (nt == 4) q *= 3;
+    return (uint8_t)((q * 256 + 242) / 243);
+}
+TK_HD void tk_quantize_tq1_0(const float* x, tk_block_tq1_0* out) {
+    const float amax = tk_tq_amax(x);
+    const float id = amax != 0.0f ? tk_divf(1.0f, amax) : 0.0f;
+    out->d = tk_f32_to_f16(amax);
+    TK_ROLLED
+    for (int m = 0; m < 32; ++m) out->qs[m] = tk_tq1_0_byte(x + m, 32, 5, id);
+    TK_ROLLED
+    for (int m = 0; m < 16; ++m) out->qs[32 + m] = tk_tq1_0_byte(x + 160 + m, 16, 5, id);
+    TK_ROLLED
+    for (int j = 0; j < 4; ++j) out->qh[j] = tk_tq1_0_byte(x + 240 + j, 4, 4, id);
 }
 
 /* ---- seeded synthetic tensors (splitmix64, seed stated per item) ---- */

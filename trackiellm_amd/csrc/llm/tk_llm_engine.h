@@ -54,7 +54,7 @@ public:
     /* returns false and sets `error` on failure */
     bool init(const TkLlmHParams& hp, int device);
     /* f16: the fp16 checkpoint recipe (every matrix and the embedding IEEE f16, norms f32) instead of Q4_K_M */
-    /* ftype (k-quant checkpoints): llama.cpp's file type 10 Q2_K, 21 Q2_K_S, 11 Q3_K_S, 12 Q3_K_M, 14 Q4_K_S, 15 Q4_K_M, 16 Q5_K_S, 17 Q5_K_M; 7 Q8_0, 2 Q4_0, 8 Q5_0, 25 IQ4_NL, 30 IQ4_XS (recipe_type) */
+    /* ftype (k-quant checkpoints): llama.cpp's file type 10 Q2_K, 21 Q2_K_S, 11 Q3_K_S, 12 Q3_K_M, 14 Q4_K_S, 15 Q4_K_M, 16 Q5_K_S, 17 Q5_K_M; 7 Q8_0, 2 Q4_0, 8 Q5_0, 25 IQ4_NL, 30 IQ4_XS, 36 TQ1_0, 37 TQ2_0 (recipe_type) */
     bool fill_synthetic(uint64_t seed, bool f16 = false, int ftype = 15);
     /* by tensor type, for the types no file type of fill_synthetic names (Q4_1, Q5_1): every layer matrix and token_embd `type`, output Q6_K, norms F32 */
     bool fill_synthetic_type(uint64_t seed, int type);

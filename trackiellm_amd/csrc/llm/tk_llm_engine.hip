@@ -39,9 +39,14 @@ static int use_more_bits(int i, int n) { return i < n / 8 || i >= 7 * n / 8 || (
  * for layers < n_layer / 16 else Q4_K; 10 Q2_K: Q2_K, v Q4_K when n_head / n_kv_head >= 4 else Q3_K, o and down Q3_K; 21 Q2_K_S: Q2_K,
  * v Q4_K when n_head / n_kv_head >= 4, down Q4_K for layers < n_layer / 8.  output is Q6_K in all eight.  7 Q8_0: every matrix, token_embd
  * and output Q8_0.  2 Q4_0 / 8 Q5_0 / 25 IQ4_NL / 30 IQ4_XS: every layer matrix and token_embd in the base type, output Q6_K.
+ * 36 TQ1_0 / 37 TQ2_0 (llama.cpp's recipe for the ternary types): every layer matrix in the base type, token_embd Q4_K, output Q6_K.
  * ftype < 0 (fill_synthetic_type): the same recipe with the tensor type -ftype as the base type */
 int TkLlmModel::recipe_type(const TkLlmHParams& hp, int layer, int which, int ftype) {
     if (ftype == 7) return (layer < 0 ? which == TK_T_OUT_NORM : which == TK_L_ATTN_NORM || which == TK_L_FFN_NORM) ? TK_TYPE_F32 : TK_TYPE_Q8_0;
+    if (ftype == 36 || ftype == 37) {
+        if (layer < 0) return which == TK_T_OUTPUT ? TK_TYPE_Q6_K : (which == TK_T_TOKEN_EMBD ? TK_TYPE_Q4_K : TK_TYPE_F32);
+        return which == TK_L_ATTN_NORM || which == TK_L_FFN_NORM ? TK_TYPE_F32 : ftype == 36 ? TK_TYPE_TQ1_0 : TK_TYPE_TQ2_0;
+    }
     if (ftype < 0 || ftype == 2 || ftype == 8 || ftype == 25 || ftype == 30) {
         const int base = ftype < 0 ? -ftype : ftype == 2 ? TK_TYPE_Q4_0 : ftype == 8 ? TK_TYPE_Q5_0 : ftype == 25 ? TK_TYPE_IQ4_NL : TK_TYPE_IQ4_XS;
         if (layer < 0) return which == TK_T_OUTPUT ? TK_TYPE_Q6_K : (which == TK_T_TOKEN_EMBD ? base : TK_TYPE_F32);

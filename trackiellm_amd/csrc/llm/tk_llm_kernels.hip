@@ -93,6 +93,14 @@ __global__ void k_synth_blocks(int type, uint64_t seed, uint64_t tid, int64_t nb
         tk_block_iq4_xs blk;
         tk_quantize_iq4_xs(x, &blk);
         ((tk_block_iq4_xs*)out)[b] = blk;
+    } else if (type == TK_TYPE_TQ2_0) {
+        tk_block_tq2_0 blk;
+        tk_quantize_tq2_0(x, &blk);
+        ((tk_block_tq2_0*)out)[b] = blk;
+    } else if (type == TK_TYPE_TQ1_0) {
+        tk_block_tq1_0 blk;
+        tk_quantize_tq1_0(x, &blk);
+        ((tk_block_tq1_0*)out)[b] = blk;
     } else {
         tk_block_q6_K blk;
         tk_quantize_q6_K(x, &blk);
@@ -481,9 +489,32 @@ __global__ void k_repack_iq4_xs(const tk_block_iq4_xs* src, int64_t nblk, uint8_
     }
 }
 
+/* TQ2_0 tile (tk_llm_layout.h): the Q2_K tile's one load of 2-bit selectors, then the sixteen d.  BLOCK = tk_block_tq1_0: the same tile
+ * from a TQ1_0 block, whose base-3 bytes are decoded here, once at load (tk_tq1_0_quant, the decode k_embed uses), into the codes 0..2 */
+__device__ __forceinline__ int tq_code(const tk_block_tq2_0* b, int i) { return tk_tq2_0_quant(b, i); }
+__device__ __forceinline__ int tq_code(const tk_block_tq1_0* b, int i) { return tk_tq1_0_quant(b, i); }
+template <typename BLOCK>
+__global__ void k_repack_tq(const BLOCK* src, int64_t nblk, uint8_t* tiles) {
+    const int lane = threadIdx.x;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t rt = blockIdx.y, blk = blockIdx.x;
+    const BLOCK* b = src + (rt * 16 + n) * nblk + blk;
+    uint8_t* tile = tiles + (rt * nblk + blk) * TK_TQ2_0_TILE_BYTES;
+    uint32_t q[4] = {0, 0, 0, 0};
+    for (int o = 0; o < 16; ++o) {
+        const int k0 = 32 * (o >> 1) + 8 * g + 4 * (o & 1);
+        for (int t = 0; t < 4; ++t) q[o >> 2] |= (uint32_t)tq_code(b, k0 + t) << (8 * t + 2 * (o & 3));
+    }
+    *(uint4*)(tile + lane * 16) = make_uint4(q[0], q[1], q[2], q[3]);
+    if (g == 0) *(uint16_t*)(tile + 1024 + n * 2) = b->d;
+}
+
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s) {
     dim3 grid((unsigned)(K / 256), (unsigned)(rows / 16));
     switch (type) {
+        /* a TQ1_0 matrix is installed as TQ2_0 tiles */
+        case TK_TYPE_TQ2_0: hipLaunchKernelGGL(k_repack_tq<tk_block_tq2_0>, grid, dim3(64), 0, s, (const tk_block_tq2_0*)blocks, K / 256, tiles); break;
+        case TK_TYPE_TQ1_0: hipLaunchKernelGGL(k_repack_tq<tk_block_tq1_0>, grid, dim3(64), 0, s, (const tk_block_tq1_0*)blocks, K / 256, tiles); break;
         /* an IQ4_NL block has the Q4_0 block's bytes and its tile is the Q4_0 tile: the same kernel */
         case TK_TYPE_IQ4_NL: hipLaunchKernelGGL(k_repack_q4_0, grid, dim3(64), 0, s, (const tk_block_q4_0*)blocks, K / 256, tiles); break;
         case TK_TYPE_IQ4_XS: hipLaunchKernelGGL(k_repack_iq4_xs, grid, dim3(64), 0, s, (const tk_block_iq4_xs*)blocks, K / 256, tiles); break;
@@ -543,6 +574,12 @@ __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, f
     } else if (type == TK_TYPE_IQ4_XS) {
         const tk_block_iq4_xs* row = (const tk_block_iq4_xs*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_iq4xs_dequant(row + i / 256, i % 256);
+    } else if (type == TK_TYPE_TQ2_0) {
+        const tk_block_tq2_0* row = (const tk_block_tq2_0*)embd + (int64_t)tok[r] * (D / 256);
+        x[(int64_t)r * D + i] = tk_tq2_0_dequant(row + i / 256, i % 256);
+    } else if (type == TK_TYPE_TQ1_0) { /* token_embd stays in GGUF layout: the base-3 bytes are decoded per weight */
+        const tk_block_tq1_0* row = (const tk_block_tq1_0*)embd + (int64_t)tok[r] * (D / 256);
+        x[(int64_t)r * D + i] = tk_tq1_0_dequant(row + i / 256, i % 256);
     } else if (type == TK_TYPE_Q6_K) {
         const tk_block_q6_K* row = (const tk_block_q6_K*)embd + (int64_t)tok[r] * (D / 256);
         x[(int64_t)r * D + i] = tk_q6k_dequant(row + i / 256, i % 256);
@@ -743,6 +780,7 @@ struct FragQ5 { uint4 q0, q1, h; uint2 qh; };
 struct FragQ3 { uint4 q; uint2 qh, sc; uint32_t d; };
 struct FragQ2 { uint4 q; uint2 sm; uint32_t dd; };
 struct FragQ8 { uint4 q[4], d; };
+struct FragTQ { uint4 q; uint32_t d; }; /* the TQ2_0 tile (a TQ1_0 matrix is installed as one too) */
 /* the Q4_0 tile's fragment; IQ4_NL and IQ4_XS load the same three reads, and the type id in the name picks their unpack_q32 overload.
  * IQ4_XS: d = the row's 16-byte tile tail, s_0 .. s_7 as int8 in d.x, d.y and the f16 d in the low half of d.z */
 template <int QT> struct FragQ4x { uint4 q0, q1, d; };
@@ -798,6 +836,13 @@ __device__ __forceinline__ FragQ2 load_q2(const uint8_t* tile, int lane) {
     const v2u32 sm = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + (lane & 15) * 16 + (lane >> 5) * 8));
     f.sm = make_uint2(sm.x, sm.y);
     f.dd = *(const uint32_t*)(tile + 1280 + (lane & 15) * 4);
+    return f;
+}
+
+__device__ __forceinline__ FragTQ load_tq(const uint8_t* tile, int lane) {
+    FragTQ f;
+    f.q = ldg_nt(tile + lane * 16);
+    f.d = *(const uint16_t*)(tile + 1024 + (lane & 15) * 2);
     return f;
 }
 
@@ -883,6 +928,7 @@ TK_TILE(TileIQ4NL, TK_TYPE_IQ4_NL, FragIQ4NL, load_q4_0<TK_TYPE_IQ4_NL>);
 TK_TILE(TileIQ4XS, TK_TYPE_IQ4_XS, FragIQ4XS, load_q4_0<TK_TYPE_IQ4_XS>);
 TK_TILE(TileQ41, TK_TYPE_Q4_1, FragQ41, load_q4_1);
 TK_TILE(TileQ51, TK_TYPE_Q5_1, FragQ51, load_q5_1);
+TK_TILE(TileTQ, TK_TYPE_TQ2_0, FragTQ, load_tq);
 #undef TK_TILE
 /* the tile pitch of a launch: a compile-time constant in single-type launches (tile addresses become scalar base + immediate); the
  * Q4_K | Q6_K kernels take it from the segment's type */
@@ -1238,6 +1284,53 @@ __device__ __forceinline__ void mma_q2(const OpsQ4& o, const uint8_t* lds_act, c
 }
 
 /*
+ * TQ2_0 (and TQ1_0, installed as the same tile): w = d * (c - 1), c in 0..3, one scale per 256 weights and nothing to fold: the operand
+ * byte is c - 1 itself.  v_perm_b32 picks it from the constant bytes {-1, 0, 1, 2} with the four 2-bit codes of an operand dword as its
+ * selector — Q2_K's look-up with a constant table: a shift, a mask and a permute per operand dword, no byte ever borrows from its
+ * neighbour, and code 3 gives +2.  One MFMA chain per M-tile gives P = sum_k (c - 1)_k a_k, |P| <= 256 * 2 * 127, and
+ * acc = fmaf(d * d8, (float)P, acc) is llama.cpp's ggml_vec_dot_tq2_0_q8_K per run and the Q6_K contract of the block's Q6_K twin
+ * (scales 1, q6 = 32 + (c - 1)) value for value.
+ */
+#define TK_TQ_BYTES 0x020100FFu /* byte c = (int8)(c - 1) */
+/* the sixteen operand dwords of one lane's k slice into b[ST * (o >> 2) + OFF][o & 3] (q3_operands) */
+template <int ST, int OFF>
+__device__ __forceinline__ void tq_operands(const uint32_t (&X)[4], v4i* b) {
+#pragma unroll
+    for (int o = 0; o < 16; ++o) b[ST * (o >> 2) + OFF][o & 3] = (int)__builtin_amdgcn_perm(0u, TK_TQ_BYTES, (X[o >> 2] >> (2 * (o & 3))) & 0x03030303u);
+}
+
+__device__ __forceinline__ void unpack_tq(const FragTQ& f, OpsQ4& o) { /* bl = the operand, dw = d; bh, bm, dmin stay unused */
+    const uint32_t X[4] = {f.q.x, f.q.y, f.q.z, f.q.w};
+    tq_operands<1, 0>(X, o.bl);
+    o.dw = f16bits_to_f32(f.d);
+}
+
+template <int MT>
+__device__ __forceinline__ void mma_tq(const OpsQ4& o, const uint8_t* lds_act, const float* lds_ad, size_t act_ts, int ad_ts, int blk, int lane,
+                                       float (*acc)[4]) {
+    const int g = lane >> 4;
+    const v4i zero = {0, 0, 0, 0};
+    v4i P[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) P[m] = zero;
+    const uint8_t* ap = lds_act + (size_t)blk * 4096 + lane * 16;
+#pragma unroll
+    for (int j2 = 0; j2 < 4; ++j2) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const v4i a = *(const v4i*)(ap + m * act_ts + j2 * 1024);
+            P[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, o.bl[j2], P[m], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const v4f da = *(const v4f*)(lds_ad + m * ad_ts + blk * TK_ROW_SLOTS + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[m][r] = tk_fmaf(o.dw * da[r], (float)P[m][r], acc[m][r]);
+    }
+}
+
+/*
  * Q8_0: w = d * q per block of 32, d an f16 and q any int8, so a 256-k run carries eight scales per weight row and nothing folds into
  * the operand: the tile's bytes ARE the B operand.  Per 32-block j one K = 32 MFMA from a zero accumulator gives the exact integer
  * P_j = sum_k q_k a_k (|P_j| <= 32 * 128 * 127 < 2^23) over the existing Q8_K activation image — its [2 sub-blocks][8] lane layout holds the
@@ -1524,7 +1617,13 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
     typedef typename TileQ32Of<TYPES>::type TileQ32;
     constexpr bool ONLY41 = tk_types_only41(TYPES);
     typedef typename TileQ41Of<TYPES>::type TileQ41x;
+    constexpr bool ONLYT = tk_types_is(TYPES, TK_TYPE_TQ2_0);
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
+    TileTQ::Frag ft[ONLYT ? PF : 1];
+    if constexpr (ONLYT) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) ft[u] = TileTQ::load(tile + (size_t)u * tile_bytes, lane);
+    }
     TileQ4::Frag f4[HAS4 ? PF : 1];
     TileQ6::Frag f6[HAS6 ? PF : 1];
     TileQ5::Frag f5[ONLY5 ? PF : 1];
@@ -1811,6 +1910,29 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
             mma_q2<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
         }
     }
+    if constexpr (ONLYT) { /* TQ2_0 tiles (TQ2_0 and TQ1_0 matrices) */
+        const uint8_t* tp = tile + PF * tile_bytes;
+#pragma unroll 1
+        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
+#pragma unroll
+            for (int u = 0; u < PF; ++u) {
+                OpsQ4 o;
+                __builtin_amdgcn_sched_barrier(0);
+                unpack_tq(ft[u], o);
+                __builtin_amdgcn_sched_barrier(0);
+                ft[u] = TileTQ::load(tp + u * tile_bytes, lane);
+                __builtin_amdgcn_sched_barrier(0);
+                mma_tq<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            OpsQ4 o;
+            __builtin_amdgcn_sched_barrier(0);
+            unpack_tq(ft[u], o);
+            mma_tq<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
+        }
+    }
     if constexpr (ONLY8) {
         const uint8_t* tp = tile + PF * tile_bytes;
 #pragma unroll 1
@@ -1987,7 +2109,9 @@ struct PTile { v4i pl, ph; v4f cm, da; };
 #define TK_MFMA64 __builtin_amdgcn_mfma_i32_16x16x64_i8
 /* QT: the tile type.  P = 8 Ph + Pl for Q4_K's scale digits, 64 Ph + Pl for the Q5_K / Q6_K folds, -Pl for Q3_K's one chain (mma_q3);
  * Q4_K and Q5_K have the min term on the sub-block sums.  Q2_K: P = Pl and its min term M = Ph, the second int8 chain (mma_q2) */
-constexpr bool tk_has_mins(int qt) { return qt != TK_TYPE_Q6_K && qt != TK_TYPE_Q3_K && qt != TK_TYPE_Q2_K; }
+constexpr bool tk_has_mins(int qt) { return qt != TK_TYPE_Q6_K && qt != TK_TYPE_Q3_K && qt != TK_TYPE_Q2_K && qt != TK_TYPE_TQ2_0; }
+/* the types with one int8 chain per M-tile and nothing else: Q3_K (holding -P) and TQ2_0 (holding P) */
+constexpr bool tk_one_chain(int qt) { return qt == TK_TYPE_Q3_K || qt == TK_TYPE_TQ2_0; }
 template <int QT>
 __device__ __forceinline__ void finish_tile(const PTile& R, const OpsQ4& o, float* acc) {
     if constexpr (QT == TK_TYPE_Q3_K) {
@@ -2001,6 +2125,11 @@ __device__ __forceinline__ void finish_tile(const PTile& R, const OpsQ4& o, floa
             acc[r] = tk_fmaf(o.dw * R.da[r], (float)R.pl[r], acc[r]);
             acc[r] = tk_fmaf(-(o.dmin * R.da[r]), (float)R.ph[r], acc[r]);
         }
+        return;
+    }
+    if constexpr (QT == TK_TYPE_TQ2_0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = tk_fmaf(o.dw * R.da[r], (float)R.pl[r], acc[r]);
         return;
     }
 #pragma unroll
@@ -2039,7 +2168,7 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
             c[w].pl = TK_MFMA64(t.a[0], o[w].bl[0], zero, 0, 0, 0);
-            if constexpr (QT != TK_TYPE_Q3_K) c[w].ph = TK_MFMA64(t.a[0], o[w].bh[0], zero, 0, 0, 0);
+            if constexpr (!tk_one_chain(QT)) c[w].ph = TK_MFMA64(t.a[0], o[w].bh[0], zero, 0, 0, 0);
             else c[w].ph = zero;
         }
 #pragma unroll
@@ -2047,7 +2176,7 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
 #pragma unroll
             for (int w = 0; w < NT; ++w) {
                 c[w].pl = TK_MFMA64(t.a[j2], o[w].bl[j2], c[w].pl, 0, 0, 0);
-                if constexpr (QT != TK_TYPE_Q3_K) c[w].ph = TK_MFMA64(t.a[j2], o[w].bh[j2], c[w].ph, 0, 0, 0);
+                if constexpr (!tk_one_chain(QT)) c[w].ph = TK_MFMA64(t.a[j2], o[w].bh[j2], c[w].ph, 0, 0, 0);
             }
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
@@ -2191,6 +2320,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     typedef typename TileQ32Of<TYPES>::type TileQ32;
     constexpr bool ONLY41 = tk_types_only41(TYPES);
     typedef typename TileQ41Of<TYPES>::type TileQ41x;
+    constexpr bool ONLYT = tk_types_is(TYPES, TK_TYPE_TQ2_0);
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     const size_t tile_bytes = types_tile_bytes<TYPES>(is4);
     const size_t tile_pitch = (size_t)nblk_total * tile_bytes; /* to the same block of the next row tile */
@@ -2237,6 +2367,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     TileQ8::Frag f8[ONLY8 ? NT : 1];
     typename TileQ32::Frag f32[ONLY32 ? NT : 1];
     typename TileQ41x::Frag f41[ONLY41 ? NT : 1];
+    TileTQ::Frag ft[ONLYT ? NT : 1];
     if (active) {
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
@@ -2248,6 +2379,7 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             if constexpr (ONLY8) f8[w] = TileQ8::load(tile + w * tile_pitch, lane);
             if constexpr (ONLY32) f32[w] = TileQ32::load(tile + w * tile_pitch, lane);
             if constexpr (ONLY41) f41[w] = TileQ41x::load(tile + w * tile_pitch, lane);
+            if constexpr (ONLYT) ft[w] = TileTQ::load(tile + w * tile_pitch, lane);
         }
     }
     for (int i = 0; i < CB && i < nb; ++i) stage(i, i);
@@ -2308,6 +2440,15 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
             for (int w = 0; w < NT; ++w) f2[w] = TileQ2::load(next + w * tile_pitch, lane);
             __builtin_amdgcn_sched_barrier(0);
             gemm_block<MT, NT, TK_TYPE_Q2_K>(o, chunk, rot, lane, acc);
+        }
+        if constexpr (ONLYT) {
+#pragma unroll
+            for (int w = 0; w < NT; ++w) unpack_tq(ft[w], o[w]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NT; ++w) ft[w] = TileTQ::load(next + w * tile_pitch, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            gemm_block<MT, NT, TK_TYPE_TQ2_0>(o, chunk, rot, lane, acc);
         }
         if constexpr (ONLY8) {
             OpsQ8 o8[NT];
@@ -2531,6 +2672,19 @@ __device__ __forceinline__ void unpack_q2_x32(const FragQ2& f0, const FragQ2& f1
     o.dmin = f16bits_to_f32(dd >> 16);
 }
 
+/* the TQ2_0 operand (unpack_tq) on the 32x32x32 map: the four packed dwords take the lane swap; d is that of the lane's own row */
+__device__ __forceinline__ void unpack_tq_x32(const FragTQ& f0, const FragTQ& f1, int lane, Ops32& o) {
+    const bool up = (lane & 16) != 0;
+    const uint32_t x0[4] = {f0.q.x, f0.q.y, f0.q.z, f0.q.w}, x1[4] = {f1.q.x, f1.q.y, f1.q.z, f1.q.w};
+    uint32_t Xa[4], Xb[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) pair_swap(x0[c], x1[c], &Xa[c], &Xb[c]);
+    tq_operands<2, 0>(Xa, o.bl);
+    tq_operands<2, 1>(Xb, o.bl);
+    o.dw = f16bits_to_f32(up ? f1.d : f0.d);
+    o.dmin = 0.0f;
+}
+
 /* Q8_0 on the 32x32x32 map: one v_mfma_i32_32x32x32_i8 is exactly one 32-block of the wave's 32 weight rows.  After the lane swap dword
  * pair (2 e, 2 e + 1) of load i holds k-slices 2 h and 2 h + 1 of block 2 i + e: b[j] = the lane's sixteen weights of block j.  d: the
  * eight scales of the lane's own weight row (lanes 16..31 of a half: tile 1's) */
@@ -2712,7 +2866,7 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
         /* P = 8 Ph + Pl (64 Ph + Pl for Q6_K) inside ONE accumulator: the high-digit chain first, its result shifted on the VALU, then the
          * low-digit chain on top of it (sixteen live registers fewer than two accumulators, and the finishing below needs no shift-add);
          * the independent min-term MFMA sits where the shift waits for the last high-digit MFMA.  Q5_K: 64 Ph + Pl with the min term */
-        constexpr bool MINS = tk_has_mins(QT); /* Q3_K: the low chain alone, from zero, holding -P.  Q2_K: ph is the min chain M and stays
+        constexpr bool MINS = tk_has_mins(QT); /* Q3_K: the low chain alone, from zero, holding -P (TQ2_0: the same, holding P).  Q2_K: ph is the min chain M and stays
                                                 * beside pl = P, which starts from zero (the registers cm has for the other min types) */
         v4i A[8];
 #pragma unroll
@@ -2725,7 +2879,7 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
         v16i ph = zero;
         v16f cm;
         v16i pl;
-        if constexpr (QT != TK_TYPE_Q3_K) {
+        if constexpr (!tk_one_chain(QT)) {
 #pragma unroll
             for (int u = 0; u < 8; ++u) ph = TK_MFMA32(A[u], o.bh[u], ph, 0, 0, 0);
         }
@@ -2875,6 +3029,11 @@ __device__ __forceinline__ typename TkTile<QT>::Frag g32_load(const uint8_t* til
         f.qh = make_uint2(qh.x, qh.y);
         f.d = ldg_nt(tile + 2560 + ho);
         return f;
+    } else if constexpr (QT == TK_TYPE_TQ2_0) {
+        FragTQ f;
+        f.q = ldg_nt(tile + lo);
+        f.d = *(const uint16_t*)(tile + 1024 + (ho >> 3));
+        return f;
     } else if constexpr (QT == TK_TYPE_Q2_K) {
         FragQ2 f;
         f.q = ldg_nt(tile + lo);
@@ -2924,6 +3083,7 @@ __device__ __forceinline__ void g32_unpack(const typename TkTile<QT>::Frag& f0, 
     else if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q3_K) unpack_q3_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q2_K) unpack_q2_x32(f0, f1, lane, o);
+    else if constexpr (QT == TK_TYPE_TQ2_0) unpack_tq_x32(f0, f1, lane, o);
     else unpack_q6_x32(f0, f1, lane, o);
 }
 
@@ -3088,6 +3248,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     if constexpr (tk_types_is(TYPES, TK_TYPE_IQ4_XS)) g32_k_loop<TK_TYPE_IQ4_XS>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (tk_types_is(TYPES, TK_TYPE_Q4_1)) g32_k_loop<TK_TYPE_Q4_1>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if constexpr (tk_types_is(TYPES, TK_TYPE_Q5_1)) g32_k_loop<TK_TYPE_Q5_1>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (tk_types_is(TYPES, TK_TYPE_TQ2_0)) g32_k_loop<TK_TYPE_TQ2_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -3165,27 +3326,27 @@ typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
 /* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone.  Type index =
  * the type's kernel_index (tk_type_desc_of), TK_KERNEL_INDEX_Q4K_Q6K for the mix; the static_asserts below hold every column to it */
 static const TkGemvKernel k_gemv_fns[3][2][2][TK_KERNEL_VARIANTS] = {
-    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>, k_gemv_w4a8<1, 1, 32, 0>, k_gemv_w4a8<1, 1, 64, 0>, k_gemv_w4a8<1, 1, 128, 0>, k_gemv_w4a8<1, 1, 256, 0>, k_gemv_w4a8<1, 1, 512, 0>, k_gemv_w4a8<1, 1, 1024, 0>, k_gemv_w4a8<1, 1, 2048, 0>},
-      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>, k_gemv_w4a8<2, 1, 32, 0>, k_gemv_w4a8<2, 1, 64, 0>, k_gemv_w4a8<2, 1, 128, 0>, k_gemv_w4a8<2, 1, 256, 0>, k_gemv_w4a8<2, 1, 512, 0>, k_gemv_w4a8<2, 1, 1024, 0>, k_gemv_w4a8<2, 1, 2048, 0>}},
-     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>, k_gemv_w4a8<1, 2, 32, 0>, k_gemv_w4a8<1, 2, 64, 0>, k_gemv_w4a8<1, 2, 128, 0>, k_gemv_w4a8<1, 2, 256, 0>, k_gemv_w4a8<1, 2, 512, 0>, k_gemv_w4a8<1, 2, 1024, 0>, k_gemv_w4a8<1, 2, 2048, 0>},
-      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>, k_gemv_w4a8<2, 2, 32, 0>, k_gemv_w4a8<2, 2, 64, 0>, k_gemv_w4a8<2, 2, 128, 0>, k_gemv_w4a8<2, 2, 256, 0>, k_gemv_w4a8<2, 2, 512, 0>, k_gemv_w4a8<2, 2, 1024, 0>, k_gemv_w4a8<2, 2, 2048, 0>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>, k_gemv_w4a8<2, 1, 32, 1>, k_gemv_w4a8<2, 1, 64, 1>, k_gemv_w4a8<2, 1, 128, 1>, k_gemv_w4a8<2, 1, 256, 1>, k_gemv_w4a8<2, 1, 512, 1>, k_gemv_w4a8<2, 1, 1024, 1>, k_gemv_w4a8<2, 1, 2048, 1>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>, k_gemv_w4a8<2, 1, 32, 2>, k_gemv_w4a8<2, 1, 64, 2>, k_gemv_w4a8<2, 1, 128, 2>, k_gemv_w4a8<2, 1, 256, 2>, k_gemv_w4a8<2, 1, 512, 2>, k_gemv_w4a8<2, 1, 1024, 2>, k_gemv_w4a8<2, 1, 2048, 2>}}},
+    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>, k_gemv_w4a8<1, 1, 32, 0>, k_gemv_w4a8<1, 1, 64, 0>, k_gemv_w4a8<1, 1, 128, 0>, k_gemv_w4a8<1, 1, 256, 0>, k_gemv_w4a8<1, 1, 512, 0>, k_gemv_w4a8<1, 1, 1024, 0>, k_gemv_w4a8<1, 1, 2048, 0>, k_gemv_w4a8<1, 1, 4096, 0>},
+      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>, k_gemv_w4a8<2, 1, 32, 0>, k_gemv_w4a8<2, 1, 64, 0>, k_gemv_w4a8<2, 1, 128, 0>, k_gemv_w4a8<2, 1, 256, 0>, k_gemv_w4a8<2, 1, 512, 0>, k_gemv_w4a8<2, 1, 1024, 0>, k_gemv_w4a8<2, 1, 2048, 0>, k_gemv_w4a8<2, 1, 4096, 0>}},
+     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>, k_gemv_w4a8<1, 2, 32, 0>, k_gemv_w4a8<1, 2, 64, 0>, k_gemv_w4a8<1, 2, 128, 0>, k_gemv_w4a8<1, 2, 256, 0>, k_gemv_w4a8<1, 2, 512, 0>, k_gemv_w4a8<1, 2, 1024, 0>, k_gemv_w4a8<1, 2, 2048, 0>, k_gemv_w4a8<1, 2, 4096, 0>},
+      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>, k_gemv_w4a8<2, 2, 32, 0>, k_gemv_w4a8<2, 2, 64, 0>, k_gemv_w4a8<2, 2, 128, 0>, k_gemv_w4a8<2, 2, 256, 0>, k_gemv_w4a8<2, 2, 512, 0>, k_gemv_w4a8<2, 2, 1024, 0>, k_gemv_w4a8<2, 2, 2048, 0>, k_gemv_w4a8<2, 2, 4096, 0>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>, k_gemv_w4a8<2, 1, 32, 1>, k_gemv_w4a8<2, 1, 64, 1>, k_gemv_w4a8<2, 1, 128, 1>, k_gemv_w4a8<2, 1, 256, 1>, k_gemv_w4a8<2, 1, 512, 1>, k_gemv_w4a8<2, 1, 1024, 1>, k_gemv_w4a8<2, 1, 2048, 1>, k_gemv_w4a8<2, 1, 4096, 1>}}},
+    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>, k_gemv_w4a8<2, 1, 32, 2>, k_gemv_w4a8<2, 1, 64, 2>, k_gemv_w4a8<2, 1, 128, 2>, k_gemv_w4a8<2, 1, 256, 2>, k_gemv_w4a8<2, 1, 512, 2>, k_gemv_w4a8<2, 1, 1024, 2>, k_gemv_w4a8<2, 1, 2048, 2>, k_gemv_w4a8<2, 1, 4096, 2>}}},
 };
 /* [mt / 2 - 2][type index] */
 static const TkGemvKernel k_gemm_fns[5][TK_KERNEL_VARIANTS] = {
-    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>, k_gemm_w4a8<4, 32>, k_gemm_w4a8<4, 64>, k_gemm_w4a8<4, 128>, k_gemm_w4a8<4, 256>, k_gemm_w4a8<4, 512>, k_gemm_w4a8<4, 1024>, k_gemm_w4a8<4, 2048>},
-    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>, k_gemm_w4a8<6, 32>, k_gemm_w4a8<6, 64>, k_gemm_w4a8<6, 128>, k_gemm_w4a8<6, 256>, k_gemm_w4a8<6, 512>, k_gemm_w4a8<6, 1024>, k_gemm_w4a8<6, 2048>},
-    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>, k_gemm_w4a8<8, 32>, k_gemm_w4a8<8, 64>, k_gemm_w4a8<8, 128>, k_gemm_w4a8<8, 256>, k_gemm_w4a8<8, 512>, k_gemm_w4a8<8, 1024>, k_gemm_w4a8<8, 2048>},
-    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>, k_gemm_w4a8<10, 32>, k_gemm_w4a8<10, 64>, k_gemm_w4a8<10, 128>, k_gemm_w4a8<10, 256>, k_gemm_w4a8<10, 512>, k_gemm_w4a8<10, 1024>, k_gemm_w4a8<10, 2048>},
-    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>, k_gemm_w4a8<12, 32>, k_gemm_w4a8<12, 64>, k_gemm_w4a8<12, 128>, k_gemm_w4a8<12, 256>, k_gemm_w4a8<12, 512>, k_gemm_w4a8<12, 1024>, k_gemm_w4a8<12, 2048>},
+    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>, k_gemm_w4a8<4, 32>, k_gemm_w4a8<4, 64>, k_gemm_w4a8<4, 128>, k_gemm_w4a8<4, 256>, k_gemm_w4a8<4, 512>, k_gemm_w4a8<4, 1024>, k_gemm_w4a8<4, 2048>, k_gemm_w4a8<4, 4096>},
+    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>, k_gemm_w4a8<6, 32>, k_gemm_w4a8<6, 64>, k_gemm_w4a8<6, 128>, k_gemm_w4a8<6, 256>, k_gemm_w4a8<6, 512>, k_gemm_w4a8<6, 1024>, k_gemm_w4a8<6, 2048>, k_gemm_w4a8<6, 4096>},
+    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>, k_gemm_w4a8<8, 32>, k_gemm_w4a8<8, 64>, k_gemm_w4a8<8, 128>, k_gemm_w4a8<8, 256>, k_gemm_w4a8<8, 512>, k_gemm_w4a8<8, 1024>, k_gemm_w4a8<8, 2048>, k_gemm_w4a8<8, 4096>},
+    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>, k_gemm_w4a8<10, 32>, k_gemm_w4a8<10, 64>, k_gemm_w4a8<10, 128>, k_gemm_w4a8<10, 256>, k_gemm_w4a8<10, 512>, k_gemm_w4a8<10, 1024>, k_gemm_w4a8<10, 2048>, k_gemm_w4a8<10, 4096>},
+    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>, k_gemm_w4a8<12, 32>, k_gemm_w4a8<12, 64>, k_gemm_w4a8<12, 128>, k_gemm_w4a8<12, 256>, k_gemm_w4a8<12, 512>, k_gemm_w4a8<12, 1024>, k_gemm_w4a8<12, 2048>, k_gemm_w4a8<12, 4096>},
 };
 /* [type index] */
-static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>, k_gemm32_w4a8<32>, k_gemm32_w4a8<64>, k_gemm32_w4a8<128>, k_gemm32_w4a8<256>, k_gemm32_w4a8<512>, k_gemm32_w4a8<1024>, k_gemm32_w4a8<2048>};
+static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>, k_gemm32_w4a8<32>, k_gemm32_w4a8<64>, k_gemm32_w4a8<128>, k_gemm32_w4a8<256>, k_gemm32_w4a8<512>, k_gemm32_w4a8<1024>, k_gemm32_w4a8<2048>, k_gemm32_w4a8<4096>};
 
 /* column c of the three tables holds the kernels of TYPES = tk_column_types[c]: every type's mask at its kernel_index */
 constexpr bool tk_columns_match_the_type_table() {
-    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048};
+    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096};
     for (int i = 0; i < TK_TILED_TYPES; ++i)
         if (tk_column_types[tk_type_desc_of(tk_tiled_type(i)).kernel_index] != tk_type_desc_of(tk_tiled_type(i)).mask) return false;
     return tk_column_types[TK_KERNEL_INDEX_Q4K_Q6K] == TK_TYPES_Q4K_Q6K;

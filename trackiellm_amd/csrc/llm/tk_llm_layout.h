@@ -2,7 +2,7 @@
  * tk_llm_layout.h — HBM layouts of the MI355X LLM path.
  *
  * GGUF k-quant blocks are kept bit-for-bit (the same quantised values, and the file's bytes per 256 weights
- * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked; Q8_0 / Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1: eight 34- / 18- / 22- / 18- / 20- / 24-byte blocks per 256 weights; IQ4_XS: its scales unpacked too) but re-tiled at load time so that one wavefront's 16-byte-per-lane
+ * for every type of tk_type_desc_of but Q3_K, whose scales are stored unpacked; Q8_0 / Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1: eight 34- / 18- / 22- / 18- / 20- / 24-byte blocks per 256 weights; IQ4_XS: its scales unpacked too; TQ1_0: its base-3 digits as 2-bit codes, 66 for 54 bytes) but re-tiled at load time so that one wavefront's 16-byte-per-lane
  * load is a contiguous 1 KiB run that already IS an MFMA operand:
  *
  *  Weight tile = 16 weight rows x 256 k (one super-block column).  Lane l = (n = l & 15, g = l >> 4)
@@ -68,6 +68,13 @@
  *                    (one shift and one mask per part put the four 3-bit u of an operand dword at bits 0..2 of its bytes)
  *      [1536 ,1792)  16 rows x 16 int8 group scales s = sc6 - 32, byte 8 h + j = group 2 j + h: a lane reads the 8 bytes of its k half
  *      [1792 ,1824)  16 x f16 d
+ *  TQ2_0 tile (1056 B = 16 x 66): the 2-bit codes c (0..3, w = (c - 1) d), operand dword o = 2 j + hh of lane l as in the Q3_K tile above
+ *      [0    ,1024)  one load, the Q2_K tile's: lane l -> 4 dwords; bits 8 t + 2 (o & 3) .. + 1 of dword o >> 2 = c of weight t of operand
+ *                    dword o (one shift and one mask give the four byte selectors 0..3 of an operand dword)
+ *      [1024 ,1056)  16 x f16 d
+ *  The kernels turn the selectors into int8 c - 1 with one v_perm_b32 on the constant bytes {-1, 0, 1, 2}: code 3 gives +2, no byte carries.
+ *  TQ1_0 tile: the TQ2_0 tile.  k_repack_tq<tk_block_tq1_0> decodes the block's base-3 bytes once, at load, and writes the trits t (0..2) as codes, so
+ *  a TQ1_0 matrix streams 66 bytes per 256 weights where its file holds 54, and runs the kernels a TQ2_0 matrix runs
  *  Q6_K tile (3360 B = 16 x 210): weights stored as 6-bit two's complement q' = (q - 32) & 63
  *      [0    ,2048)  two loads as above holding the LOW nibbles of q'
  *      [2048 ,3072)  lane l -> 4 dwords; dword u covers sub-blocks 2u, 2u+1: the 2 high bits of
@@ -113,6 +120,7 @@
 #define TK_IQ4_XS_TILE_BYTES 2304
 #define TK_Q4_1_TILE_BYTES 2560
 #define TK_Q5_1_TILE_BYTES 3072
+#define TK_TQ2_0_TILE_BYTES 1056 /* TQ1_0's too: it is installed as this tile */
 #define TK_ROW_SLOTS 16  /* rows of one MFMA M-tile */
 #define TK_MAX_TILES 16   /* M-tiles per pass: a weight tile is unpacked once and multiplied against all of them */
 #define TK_MAX_ROWS (TK_ROW_SLOTS * TK_MAX_TILES)

@@ -10,14 +10,16 @@ from ._lib import check, lib
 TYPE_F32, TYPE_F16, TYPE_Q4_0, TYPE_Q5_0, TYPE_Q8_0, TYPE_Q2_K, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 0, 1, 2, 6, 8, 10, 11, 12, 13, 14
 TYPE_IQ4_NL, TYPE_IQ4_XS = 20, 23
 TYPE_Q4_1, TYPE_Q5_1 = 3, 7
+TYPE_TQ1_0, TYPE_TQ2_0 = 34, 35  # the ternary types; a TQ1_0 matrix is installed as TQ2_0 tiles (66 resident bytes per 256 weights, not the file's 54)
 TYPE_BF16 = 30  # with TYPE_F32 and TYPE_F16 the float matrix types; a model's matrices hold at most one of the three
 FTYPE_Q4_1, FTYPE_Q5_1 = 3, 9  # GGUF metadata only: fill_synthetic refuses them, fill_synthetic_type(TYPE_Q4_1 / TYPE_Q5_1) makes such models
 FTYPE_IQ4_NL, FTYPE_IQ4_XS = 25, 30
+FTYPE_TQ1_0, FTYPE_TQ2_0 = 36, 37  # every layer matrix in the base type, token_embd Q4_K, output Q6_K
 FTYPE_Q4_0, FTYPE_Q5_0, FTYPE_Q8_0 = 2, 8, 7
 TYPES_OF_32 = (TYPE_Q4_0, TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1, TYPE_Q8_0, TYPE_IQ4_NL)  # blocks of 32 weights; every other quantised type has blocks of 256
 FTYPE_Q2_K, FTYPE_Q2_K_S = 10, 21
 FTYPE_Q3_K_S, FTYPE_Q3_K_M, FTYPE_Q4_K_S, FTYPE_Q4_K_M, FTYPE_Q5_K_S, FTYPE_Q5_K_M = 11, 12, 14, 15, 16, 17
-BLOCK_BYTES = {TYPE_Q4_0: 18, TYPE_Q5_0: 22, TYPE_Q8_0: 34, TYPE_Q2_K: 84, TYPE_Q3_K: 110, TYPE_Q4_K: 144, TYPE_Q5_K: 176, TYPE_Q6_K: 210, TYPE_IQ4_NL: 18, TYPE_IQ4_XS: 136, TYPE_Q4_1: 20, TYPE_Q5_1: 24}
+BLOCK_BYTES = {TYPE_Q4_0: 18, TYPE_Q5_0: 22, TYPE_Q8_0: 34, TYPE_Q2_K: 84, TYPE_Q3_K: 110, TYPE_Q4_K: 144, TYPE_Q5_K: 176, TYPE_Q6_K: 210, TYPE_IQ4_NL: 18, TYPE_IQ4_XS: 136, TYPE_Q4_1: 20, TYPE_Q5_1: 24, TYPE_TQ1_0: 54, TYPE_TQ2_0: 66}
 
 
 def prefix_match(toks, records, self_slot=-1, cursor=-1):
@@ -54,15 +56,16 @@ def lora_probe(path):
 
 def quantize_blocks(ttype, x):
     """the build's own block quantiser on the host, no GPU (tk_mi355x_quantize_blocks; tk_mi355x_quantize_blocks_q2k for TYPE_Q2_K,
-    tk_mi355x_quantize_blocks_q4_0 / _q5_0 / _q4_1 / _q5_1 / _iq4_nl / _iq4_xs for TYPE_Q4_0 / TYPE_Q5_0 / TYPE_Q4_1 / TYPE_Q5_1 / TYPE_IQ4_NL / TYPE_IQ4_XS):
+    tk_mi355x_quantize_blocks_q4_0 / _q5_0 / _q4_1 / _q5_1 / _iq4_nl / _iq4_xs / _tq1_0 / _tq2_0 for TYPE_Q4_0 / TYPE_Q5_0 / TYPE_Q4_1 / TYPE_Q5_1 / TYPE_IQ4_NL / TYPE_IQ4_XS / TYPE_TQ1_0 / TYPE_TQ2_0):
     x [..., 256 n] float32 -> uint8 [n_blocks][block bytes] of k-quant `ttype`; TYPE_Q4_0 / TYPE_Q5_0 / TYPE_Q8_0 / TYPE_IQ4_NL: blocks of 32 weights,
     [n / 32][18 / 22 / 34 / 18]"""
     x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 32 if ttype in TYPES_OF_32 else 256)
     out = np.empty((x.shape[0], BLOCK_BYTES[ttype]), np.uint8)
-    if ttype in (TYPE_Q4_0, TYPE_Q5_0, TYPE_Q4_1, TYPE_Q5_1, TYPE_IQ4_NL, TYPE_IQ4_XS):
+    if ttype in (TYPE_Q4_0, TYPE_Q5_0, TYPE_Q4_1, TYPE_Q5_1, TYPE_IQ4_NL, TYPE_IQ4_XS, TYPE_TQ1_0, TYPE_TQ2_0):
         fn = {TYPE_Q4_0: lib().tk_mi355x_quantize_blocks_q4_0, TYPE_Q5_0: lib().tk_mi355x_quantize_blocks_q5_0,
               TYPE_Q4_1: lib().tk_mi355x_quantize_blocks_q4_1, TYPE_Q5_1: lib().tk_mi355x_quantize_blocks_q5_1,
-              TYPE_IQ4_NL: lib().tk_mi355x_quantize_blocks_iq4_nl, TYPE_IQ4_XS: lib().tk_mi355x_quantize_blocks_iq4_xs}[ttype]
+              TYPE_IQ4_NL: lib().tk_mi355x_quantize_blocks_iq4_nl, TYPE_IQ4_XS: lib().tk_mi355x_quantize_blocks_iq4_xs,
+              TYPE_TQ1_0: lib().tk_mi355x_quantize_blocks_tq1_0, TYPE_TQ2_0: lib().tk_mi355x_quantize_blocks_tq2_0}[ttype]
         fn.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         check(fn(_p(x), x.shape[0], _p(out)))
         return out
