@@ -799,137 +799,189 @@ __device__ __forceinline__ uint4 ldg_nt(const uint8_t* p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-__device__ __forceinline__ FragQ4 load_q4(const uint8_t* tile, int lane) {
+/* One lane's loads of a tile, written once per type as a function of the lane's 32-bit byte offsets, which an offsets struct P forms at each
+ * use: lo(b) = lane * b, the lane's b bytes of a 64-lane row of the tile; ho(b) = (lane & 15) * b, its weight row's b bytes of a
+ * per-row field; khalf(b) = (lane >> 5) * b, its k half's b bytes.  TkTile<QT>::load passes the lane (LaneOffsets); g32_load passes
+ * lo(16) and ho(16) as two opaque registers (OpaqueOffsets) and the other offsets are shifts of those.  (As two values formed once ahead
+ * of the loads the offsets changed 96 lane-pointer kernels, and with the lane form's offsets written as shifts of lo(16) and ho(16), 42.) */
+struct LaneOffsets {
+    int lane;
+    __device__ __forceinline__ int lo(int b) const { return lane * b; }
+    __device__ __forceinline__ int ho(int b) const { return (lane & 15) * b; }
+    __device__ __forceinline__ int khalf(int b) const { return (lane >> 5) * b; }
+};
+struct OpaqueOffsets {
+    unsigned l, h; /* lo(16), ho(16) */
+    static __device__ __forceinline__ unsigned scaled(unsigned v, unsigned b) { return b >= 16u ? v * (b / 16u) : v / (16u / b); }
+    __device__ __forceinline__ unsigned lo(unsigned b) const { return scaled(l, b); }
+    __device__ __forceinline__ unsigned ho(unsigned b) const { return scaled(h, b); }
+    __device__ __forceinline__ unsigned khalf(unsigned b) const { return (l / (512u / b)) & b; } /* b a power of two */
+};
+template <typename P>
+__device__ __forceinline__ FragQ4 load_q4(const uint8_t* tile, P p) {
     FragQ4 f;
-    f.q0 = ldg_nt(tile + lane * 16);
-    f.q1 = ldg_nt(tile + 1024 + lane * 16);
-    f.h = ldg_nt(tile + 2048 + (lane & 15) * 16);
+    f.q0 = ldg_nt(tile + p.lo(16));
+    f.q1 = ldg_nt(tile + 1024 + p.lo(16));
+    f.h = ldg_nt(tile + 2048 + p.ho(16));
     return f;
 }
 
-__device__ __forceinline__ FragQ5 load_q5(const uint8_t* tile, int lane) {
+template <typename P>
+__device__ __forceinline__ FragQ5 load_q5(const uint8_t* tile, P p) {
     FragQ5 f;
-    f.q0 = ldg_nt(tile + lane * 16);
-    f.q1 = ldg_nt(tile + 1024 + lane * 16);
-    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + lane * 8));
+    f.q0 = ldg_nt(tile + p.lo(16));
+    f.q1 = ldg_nt(tile + 1024 + p.lo(16));
+    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + p.lo(8)));
     f.qh = make_uint2(qh.x, qh.y);
-    f.h = ldg_nt(tile + 2560 + (lane & 15) * 16);
+    f.h = ldg_nt(tile + 2560 + p.ho(16));
     return f;
 }
 
 /* sc: the eight group scales of this lane's k half (lane groups 2, 3 hold k 16..31 of every sub-block) */
-__device__ __forceinline__ FragQ3 load_q3(const uint8_t* tile, int lane) {
+template <typename P>
+__device__ __forceinline__ FragQ3 load_q3(const uint8_t* tile, P p) {
     FragQ3 f;
-    f.q = ldg_nt(tile + lane * 16);
-    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + lane * 8));
+    f.q = ldg_nt(tile + p.lo(16));
+    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + p.lo(8)));
     f.qh = make_uint2(qh.x, qh.y);
-    const v2u32 sc = __builtin_nontemporal_load((const v2u32*)(tile + 1536 + (lane & 15) * 16 + (lane >> 5) * 8));
+    const v2u32 sc = __builtin_nontemporal_load((const v2u32*)(tile + 1536 + p.ho(16) + p.khalf(8)));
     f.sc = make_uint2(sc.x, sc.y);
-    f.d = *(const uint16_t*)(tile + 1792 + (lane & 15) * 2);
+    f.d = *(const uint16_t*)(tile + 1792 + p.ho(2));
     return f;
 }
 
 /* sm: the eight (scale, min) bytes of this lane's k half; dd = d | dmin << 16 */
-__device__ __forceinline__ FragQ2 load_q2(const uint8_t* tile, int lane) {
+template <typename P>
+__device__ __forceinline__ FragQ2 load_q2(const uint8_t* tile, P p) {
     FragQ2 f;
-    f.q = ldg_nt(tile + lane * 16);
-    const v2u32 sm = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + (lane & 15) * 16 + (lane >> 5) * 8));
+    f.q = ldg_nt(tile + p.lo(16));
+    const v2u32 sm = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + p.ho(16) + p.khalf(8)));
     f.sm = make_uint2(sm.x, sm.y);
-    f.dd = *(const uint32_t*)(tile + 1280 + (lane & 15) * 4);
+    f.dd = *(const uint32_t*)(tile + 1280 + p.ho(4));
     return f;
 }
 
-__device__ __forceinline__ FragTQ load_tq(const uint8_t* tile, int lane) {
+template <typename P>
+__device__ __forceinline__ FragTQ load_tq(const uint8_t* tile, P p) {
     FragTQ f;
-    f.q = ldg_nt(tile + lane * 16);
-    f.d = *(const uint16_t*)(tile + 1024 + (lane & 15) * 2);
+    f.q = ldg_nt(tile + p.lo(16));
+    f.d = *(const uint16_t*)(tile + 1024 + p.ho(2));
     return f;
 }
 
 /* q[i]: the lane's eight weights of blocks 2 i and 2 i + 1, operand bytes as they stand; d: the eight f16 block scales of the lane's row */
-__device__ __forceinline__ FragQ8 load_q8(const uint8_t* tile, int lane) {
+template <typename P>
+__device__ __forceinline__ FragQ8 load_q8(const uint8_t* tile, P p) {
     FragQ8 f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) f.q[i] = ldg_nt(tile + 1024 * i + lane * 16);
-    f.d = ldg_nt(tile + 4096 + (lane & 15) * 16);
+    for (int i = 0; i < 4; ++i) f.q[i] = ldg_nt(tile + 1024 * i + p.lo(16));
+    f.d = ldg_nt(tile + 4096 + p.ho(16));
     return f;
 }
 
 /* q0, q1: the Q4_K tile's nibble loads (dword s of load L = block 4 L + s); d: the eight f16 block scales of the lane's row */
-template <int QT>
-__device__ __forceinline__ FragQ4x<QT> load_q4_0(const uint8_t* tile, int lane) {
+template <int QT, typename P>
+__device__ __forceinline__ FragQ4x<QT> load_q4_0(const uint8_t* tile, P p) {
     FragQ4x<QT> f;
-    f.q0 = ldg_nt(tile + lane * 16);
-    f.q1 = ldg_nt(tile + 1024 + lane * 16);
-    f.d = ldg_nt(tile + 2048 + (lane & 15) * 16);
+    f.q0 = ldg_nt(tile + p.lo(16));
+    f.q1 = ldg_nt(tile + 1024 + p.lo(16));
+    f.d = ldg_nt(tile + 2048 + p.ho(16));
     return f;
 }
 
-__device__ __forceinline__ FragQ50 load_q5_0(const uint8_t* tile, int lane) {
+template <typename P>
+__device__ __forceinline__ FragQ50 load_q5_0(const uint8_t* tile, P p) {
     FragQ50 f;
-    f.q0 = ldg_nt(tile + lane * 16);
-    f.q1 = ldg_nt(tile + 1024 + lane * 16);
-    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + lane * 8));
+    f.q0 = ldg_nt(tile + p.lo(16));
+    f.q1 = ldg_nt(tile + 1024 + p.lo(16));
+    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + p.lo(8)));
     f.qh = make_uint2(qh.x, qh.y);
-    f.d = ldg_nt(tile + 2560 + (lane & 15) * 16);
+    f.d = ldg_nt(tile + 2560 + p.ho(16));
     return f;
 }
 
 /* d, m: the two 16-byte halves of the row's 32-byte tile tail */
-__device__ __forceinline__ FragQ41 load_q4_1(const uint8_t* tile, int lane) {
+template <typename P>
+__device__ __forceinline__ FragQ41 load_q4_1(const uint8_t* tile, P p) {
     FragQ41 f;
-    f.q0 = ldg_nt(tile + lane * 16);
-    f.q1 = ldg_nt(tile + 1024 + lane * 16);
-    f.d = ldg_nt(tile + 2048 + (lane & 15) * 32);
-    f.m = ldg_nt(tile + 2064 + (lane & 15) * 32);
+    f.q0 = ldg_nt(tile + p.lo(16));
+    f.q1 = ldg_nt(tile + 1024 + p.lo(16));
+    f.d = ldg_nt(tile + 2048 + p.ho(32));
+    f.m = ldg_nt(tile + 2064 + p.ho(32));
     return f;
 }
 
-__device__ __forceinline__ FragQ51 load_q5_1(const uint8_t* tile, int lane) {
+template <typename P>
+__device__ __forceinline__ FragQ51 load_q5_1(const uint8_t* tile, P p) {
     FragQ51 f;
-    f.q0 = ldg_nt(tile + lane * 16);
-    f.q1 = ldg_nt(tile + 1024 + lane * 16);
-    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + lane * 8));
+    f.q0 = ldg_nt(tile + p.lo(16));
+    f.q1 = ldg_nt(tile + 1024 + p.lo(16));
+    const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + p.lo(8)));
     f.qh = make_uint2(qh.x, qh.y);
-    f.d = ldg_nt(tile + 2560 + (lane & 15) * 32);
-    f.m = ldg_nt(tile + 2576 + (lane & 15) * 32);
+    f.d = ldg_nt(tile + 2560 + p.ho(32));
+    f.m = ldg_nt(tile + 2576 + p.ho(32));
     return f;
 }
 
-__device__ __forceinline__ FragQ6 load_q6(const uint8_t* tile, int lane) {
+template <typename P>
+__device__ __forceinline__ FragQ6 load_q6(const uint8_t* tile, P p) {
     FragQ6 f;
-    f.q0 = ldg_nt(tile + lane * 16);
-    f.q1 = ldg_nt(tile + 1024 + lane * 16);
-    f.qh = ldg_nt(tile + 2048 + lane * 16);
-    f.sc = ldg_nt(tile + 3072 + (lane & 15) * 16);
-    f.d = *(const uint16_t*)(tile + 3328 + (lane & 15) * 2);
+    f.q0 = ldg_nt(tile + p.lo(16));
+    f.q1 = ldg_nt(tile + 1024 + p.lo(16));
+    f.qh = ldg_nt(tile + 2048 + p.lo(16));
+    f.sc = ldg_nt(tile + 3072 + p.ho(16));
+    f.d = *(const uint16_t*)(tile + 3328 + p.ho(2));
     return f;
 }
 
-/* The weight tile of a type as the three W4A8 families see it: one lane's packed fragment, the tile's bytes and the lane-pointer load
- * (k_gemm32_w4a8 issues the same loads in scalar-base form: g32_load) */
+/* The weight tile of a type as the three W4A8 families see it, and the whole device-side description of the type: one lane's packed
+ * fragment, the tile's bytes and the lane-pointer load (k_gemm32_w4a8 issues the same loads in scalar-base form: g32_load); the operand
+ * struct its unpack fills for the 16x16 MFMAs (Ops; Q6_K's is the mat-vec's, k_gemm_w4a8 folds Q6_K into an OpsQ4) and for the 32x32x32
+ * ones (Ops32); the chain the wide kernels run on those operands; for the fold chain, whether it has the f16 min-term MFMA on the
+ * sub-block sums (has_mins) and whether it is one int8 chain per M-tile and nothing else (one_chain: Q3_K holding -P, TQ2_0 holding P).
+ * The kernels read a type from here, from the two unpack forwarders (unpack16, g32_unpack) and, in k_gemv_w4a8, from the macro that
+ * picks its MFMA chain (TK_GEMV_MMA_SINGLE); a single-type kernel gets its type from its mask (tk_types_single) */
+enum TkChain {
+    TK_CHAIN_FOLD, /* scales folded into the operands: two int8 chains (or one) over the whole 256-k run, finished once per block (gemm_block) */
+    TK_CHAIN_Q8,   /* the Q8_0 chains: one K = 32 MFMA and one scale per 32-block (gemm_block_q8) */
+    TK_CHAIN_Q81   /* the Q8_0 chains with the min term (gemm_block_q81) */
+};
+struct OpsQ4; struct OpsQ6; struct OpsQ8; struct OpsQ81; struct Ops32; struct Ops32Q8; struct Ops32Q81;
 template <int QT> struct TkTile;
-#define TK_TILE(NAME, QT, F, LOAD)                                                                            \
+#define TK_TILE(NAME, QT, F, LOAD, OPS, OPS32, CHAIN, MINS, ONE)                                              \
     template <> struct TkTile<QT> {                                                                           \
         typedef F Frag;                                                                                       \
+        typedef OPS Ops;                                                                                      \
+        typedef OPS32 Ops32;                                                                                  \
         static constexpr size_t bytes = tk_type_desc_of(QT).tile_bytes;                                       \
-        static __device__ __forceinline__ F load(const uint8_t* tile, int lane) { return LOAD(tile, lane); }  \
+        static constexpr TkChain chain = CHAIN;                                                               \
+        static constexpr bool has_mins = MINS, one_chain = ONE;                                               \
+        template <typename P>                                                                                 \
+        static __device__ __forceinline__ F load_at(const uint8_t* tile, P p) { return LOAD(tile, p); }       \
+        static __device__ __forceinline__ F load(const uint8_t* tile, int lane) { return LOAD(tile, LaneOffsets{lane}); } \
     };                                                                                                        \
     typedef TkTile<QT> NAME
-TK_TILE(TileQ2, TK_TYPE_Q2_K, FragQ2, load_q2);
-TK_TILE(TileQ3, TK_TYPE_Q3_K, FragQ3, load_q3);
-TK_TILE(TileQ4, TK_TYPE_Q4_K, FragQ4, load_q4);
-TK_TILE(TileQ5, TK_TYPE_Q5_K, FragQ5, load_q5);
-TK_TILE(TileQ6, TK_TYPE_Q6_K, FragQ6, load_q6);
-TK_TILE(TileQ8, TK_TYPE_Q8_0, FragQ8, load_q8);
-TK_TILE(TileQ40, TK_TYPE_Q4_0, FragQ40, load_q4_0<TK_TYPE_Q4_0>);
-TK_TILE(TileQ50, TK_TYPE_Q5_0, FragQ50, load_q5_0);
-TK_TILE(TileIQ4NL, TK_TYPE_IQ4_NL, FragIQ4NL, load_q4_0<TK_TYPE_IQ4_NL>);
-TK_TILE(TileIQ4XS, TK_TYPE_IQ4_XS, FragIQ4XS, load_q4_0<TK_TYPE_IQ4_XS>);
-TK_TILE(TileQ41, TK_TYPE_Q4_1, FragQ41, load_q4_1);
-TK_TILE(TileQ51, TK_TYPE_Q5_1, FragQ51, load_q5_1);
-TK_TILE(TileTQ, TK_TYPE_TQ2_0, FragTQ, load_tq);
+TK_TILE(TileQ2, TK_TYPE_Q2_K, FragQ2, load_q2, OpsQ4, ::Ops32, TK_CHAIN_FOLD, false, false);
+TK_TILE(TileQ3, TK_TYPE_Q3_K, FragQ3, load_q3, OpsQ4, ::Ops32, TK_CHAIN_FOLD, false, true);
+TK_TILE(TileQ4, TK_TYPE_Q4_K, FragQ4, load_q4, OpsQ4, ::Ops32, TK_CHAIN_FOLD, true, false);
+TK_TILE(TileQ5, TK_TYPE_Q5_K, FragQ5, load_q5, OpsQ4, ::Ops32, TK_CHAIN_FOLD, true, false);
+TK_TILE(TileQ6, TK_TYPE_Q6_K, FragQ6, load_q6, OpsQ6, ::Ops32, TK_CHAIN_FOLD, false, false);
+TK_TILE(TileQ8, TK_TYPE_Q8_0, FragQ8, load_q8, OpsQ8, Ops32Q8, TK_CHAIN_Q8, false, false);
+TK_TILE(TileQ40, TK_TYPE_Q4_0, FragQ40, load_q4_0<TK_TYPE_Q4_0>, OpsQ8, Ops32Q8, TK_CHAIN_Q8, false, false);
+TK_TILE(TileQ50, TK_TYPE_Q5_0, FragQ50, load_q5_0, OpsQ8, Ops32Q8, TK_CHAIN_Q8, false, false);
+TK_TILE(TileIQ4NL, TK_TYPE_IQ4_NL, FragIQ4NL, load_q4_0<TK_TYPE_IQ4_NL>, OpsQ8, Ops32Q8, TK_CHAIN_Q8, false, false);
+TK_TILE(TileIQ4XS, TK_TYPE_IQ4_XS, FragIQ4XS, load_q4_0<TK_TYPE_IQ4_XS>, OpsQ8, Ops32Q8, TK_CHAIN_Q8, false, false);
+TK_TILE(TileQ41, TK_TYPE_Q4_1, FragQ41, load_q4_1, OpsQ81, Ops32Q81, TK_CHAIN_Q81, false, false);
+TK_TILE(TileQ51, TK_TYPE_Q5_1, FragQ51, load_q5_1, OpsQ81, Ops32Q81, TK_CHAIN_Q81, false, false);
+TK_TILE(TileTQ, TK_TYPE_TQ2_0, FragTQ, load_tq, OpsQ4, ::Ops32, TK_CHAIN_FOLD, false, true);
 #undef TK_TILE
+/* the type of a single-type launch: the tiled type whose mask TYPES is (a TQ1_0 matrix is a TQ2_0 tile: the one listed first).  The
+ * Q4_K | Q6_K mix has none: Q4_K's, unused, so that the trait of the result always exists */
+constexpr int tk_types_single(int types) {
+    for (int i = 0; i < TK_TILED_TYPES; ++i)
+        if (tk_types_is(types, tk_tiled_type(i))) return tk_tiled_type(i);
+    return TK_TYPE_Q4_K;
+}
 /* the tile pitch of a launch: a compile-time constant in single-type launches (tile addresses become scalar base + immediate); the
  * Q4_K | Q6_K kernels take it from the segment's type */
 template <int TYPES>
@@ -1425,15 +1477,6 @@ __device__ __forceinline__ void unpack_q32(const FragIQ4XS& f, OpsQ8& o) {
     iq4_operands(f, o);
     iq4xs_scales(f.d, o.d);
 }
-/* the tile of a launch whose TYPES is the mask of Q4_0, Q5_0, IQ4_NL or IQ4_XS alone (any other TYPES: Q4_0's, unused) */
-template <int TYPES> struct TileQ32Of { typedef TileQ40 type; };
-template <> struct TileQ32Of<tk_type_desc_of(TK_TYPE_Q5_0).mask> { typedef TileQ50 type; };
-template <> struct TileQ32Of<tk_type_desc_of(TK_TYPE_IQ4_NL).mask> { typedef TileIQ4NL type; };
-template <> struct TileQ32Of<tk_type_desc_of(TK_TYPE_IQ4_XS).mask> { typedef TileIQ4XS type; };
-/* the launches that run the Q8_0 chains behind an unpack of their own */
-constexpr bool tk_types_only32(int types) {
-    return tk_types_is(types, TK_TYPE_Q4_0) || tk_types_is(types, TK_TYPE_Q5_0) || tk_types_is(types, TK_TYPE_IQ4_NL) || tk_types_is(types, TK_TYPE_IQ4_XS);
-}
 
 /* the 8-byte half e of a 16-byte operand register set: the A or B operand of one 32-block */
 __device__ __forceinline__ long half_of(const v4i& v, int e) { return (long)(((unsigned long)(uint32_t)v[2 * e + 1] << 32) | (uint32_t)v[2 * e]); }
@@ -1496,10 +1539,6 @@ __device__ __forceinline__ void unpack_q41(const FragQ51& f, OpsQ81& o) {
     q32_scales(f.d, o.d);
     q32_scales(f.m, o.m);
 }
-/* the tile of a launch whose TYPES is the mask of Q4_1 or Q5_1 alone (any other TYPES: Q4_1's, unused) */
-template <int TYPES> struct TileQ41Of { typedef TileQ41 type; };
-template <> struct TileQ41Of<tk_type_desc_of(TK_TYPE_Q5_1).mask> { typedef TileQ51 type; };
-constexpr bool tk_types_only41(int types) { return tk_types_is(types, TK_TYPE_Q4_1) || tk_types_is(types, TK_TYPE_Q5_1); }
 
 /* mma_q8 with the min term: per 32-block the product MFMA and, on the same A operand, the sum MFMA against all ones.  Two blocks (one
  * 16-byte A read per M-tile) form a group; the MFMAs of group j2 + 1 are issued before group j2 is finished on the VALU and no further
@@ -1551,6 +1590,18 @@ __device__ __forceinline__ void mma_q81(const OpsQ81& o, const uint8_t* lds_act,
                 }
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+
+/* the 16x16 unpack of a single-type launch's tile (k_gemv_w4a8, k_gemm_w4a8); Q4_K and Q6_K, the types of the mix, are called by name there */
+template <int QT>
+__device__ __forceinline__ void unpack16(const typename TkTile<QT>::Frag& f, int lane, typename TkTile<QT>::Ops& o) {
+    if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_fold(f, lane, o);
+    else if constexpr (QT == TK_TYPE_Q3_K) unpack_q3(f, o);
+    else if constexpr (QT == TK_TYPE_Q2_K) unpack_q2(f, o);
+    else if constexpr (QT == TK_TYPE_TQ2_0) unpack_tq(f, o);
+    else if constexpr (QT == TK_TYPE_Q8_0) unpack_q8(f, o);
+    else if constexpr (TkTile<QT>::chain == TK_CHAIN_Q8) unpack_q32(f, o); /* Q4_0 / Q5_0 / IQ4_NL / IQ4_XS: the type's unpack in front of the Q8_0 chain */
+    else unpack_q41(f, o);                                                 /* Q4_1 / Q5_1 */
 }
 
 size_t tk_gemv_lds_bytes(int K, int ks, int mtiles) {
@@ -1611,59 +1662,19 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
      * fill.  Loop bodies below contain NO conditional loads: hipcc then keeps counted vmcnt waits and the next
      * group's tiles stay in flight under the current group's MFMAs (a branch around a load costs a vmcnt(0)). */
     constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
-    constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
-    constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
-    constexpr bool ONLY32 = tk_types_only32(TYPES);
-    typedef typename TileQ32Of<TYPES>::type TileQ32;
-    constexpr bool ONLY41 = tk_types_only41(TYPES);
-    typedef typename TileQ41Of<TYPES>::type TileQ41x;
-    constexpr bool ONLYT = tk_types_is(TYPES, TK_TYPE_TQ2_0);
+    constexpr bool SINGLE = !HAS4 && !HAS6; /* every other TYPES is one type's mask: the launch's tile is that type's trait */
+    constexpr int ST = tk_types_single(TYPES);
+    typedef TkTile<ST> TileS;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
-    TileTQ::Frag ft[ONLYT ? PF : 1];
-    if constexpr (ONLYT) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) ft[u] = TileTQ::load(tile + (size_t)u * tile_bytes, lane);
-    }
     TileQ4::Frag f4[HAS4 ? PF : 1];
     TileQ6::Frag f6[HAS6 ? PF : 1];
-    TileQ5::Frag f5[ONLY5 ? PF : 1];
-    TileQ3::Frag f3[ONLY3 ? PF : 1];
-    TileQ2::Frag f2[ONLY2 ? PF : 1];
-    TileQ8::Frag f8[ONLY8 ? PF : 1];
-    typename TileQ32::Frag f32[ONLY32 ? PF : 1];
-    typename TileQ41x::Frag f41[ONLY41 ? PF : 1];
-    if constexpr (ONLY8) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) f8[u] = TileQ8::load(tile + (size_t)u * tile_bytes, lane);
-    }
-    if constexpr (ONLY32) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) f32[u] = TileQ32::load(tile + (size_t)u * tile_bytes, lane);
-    }
-    if constexpr (ONLY41) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) f41[u] = TileQ41x::load(tile + (size_t)u * tile_bytes, lane);
-    }
-    if constexpr (ONLY3) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) f3[u] = TileQ3::load(tile + (size_t)u * tile_bytes, lane);
-    }
-    if constexpr (ONLY2) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) f2[u] = TileQ2::load(tile + (size_t)u * tile_bytes, lane);
-    }
-    if (HAS4 && is4) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) f4[HAS4 ? u : 0] = TileQ4::load(tile + (size_t)u * tile_bytes, lane);
-    }
-    if constexpr (ONLY5) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) f5[u] = TileQ5::load(tile + (size_t)u * tile_bytes, lane);
-    }
-    if (HAS6 && !is4) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) f6[HAS6 ? u : 0] = TileQ6::load(tile + (size_t)u * tile_bytes, lane);
-    }
+    typename TileS::Frag fs[SINGLE ? PF : 1];
+#define TK_GEMV_FIRST(TILE, F) \
+    { _Pragma("unroll") for (int u = 0; u < PF; ++u) F = TILE::load(tile + (size_t)u * tile_bytes, lane); }
+    if constexpr (SINGLE) TK_GEMV_FIRST(TileS, fs[u])
+    if (HAS4 && is4) TK_GEMV_FIRST(TileQ4, f4[HAS4 ? u : 0])
+    if (HAS6 && !is4) TK_GEMV_FIRST(TileQ6, f6[HAS6 ? u : 0])
+#undef TK_GEMV_FIRST
     if (FUSE != 0) {
         const int nw = nthr >> 6, hw = tid >> 5, nhw = nthr >> 5;
         TkActQ8 lo{}; /* the LDS image as quantize_chunk8's destination: same layout as the global one, block 0 = this K-range's first */
@@ -1794,213 +1805,49 @@ __global__ __launch_bounds__(512) void k_gemv_w4a8(TkGemvArgs a, int groups, int
 
     /* steady state per tile: unpack (frees the packed fragment) -> request the tile PF blocks ahead into the same registers ->
      * MFMAs; so a tile has PF - 1 blocks of MFMA time plus its own to arrive */
-    /* One copy of the loop per type on purpose: behind a function template or a lambda the compiler schedules every instantiation differently. */
-    if (HAS4 && is4) {
-        const uint8_t* tp = tile + PF * tile_bytes; /* one moving wave-uniform pointer: no per-load 64-bit VGPR address chains */
-#pragma unroll 1
-        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                OpsQ4 o;
-                __builtin_amdgcn_sched_barrier(0);
-                unpack_q4(f4[HAS4 ? u : 0], lane, o);
-                __builtin_amdgcn_sched_barrier(0);
-                f4[HAS4 ? u : 0] = TileQ4::load(tp + u * tile_bytes, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_q4<MT>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, g * PF + u, lane, acc);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            OpsQ4 o;
-            __builtin_amdgcn_sched_barrier(0);
-            unpack_q4(f4[HAS4 ? u : 0], lane, o);
-            mma_q4<MT>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
-        }
+    /* The loop is written once, as a macro that expands to the same tokens at each use: behind a function template or a lambda the compiler
+     * schedules every instantiation differently, and so it does when the block index is named (`const int blk = g * PF + u`, before the
+     * first sched_barrier or in front of the call: 17 instantiations change) instead of staying an argument expression of the MFMA call
+     * (DESIGN.md section 4).  TILE: the tile's trait; F: fragment u; UNPACK: the call that fills `o` from it; MMA: a one-line macro of the block index */
+#define TK_GEMV_STREAM(TILE, F, UNPACK, MMA)                                                                                      \
+    {                                                                                                                            \
+        const uint8_t* tp = tile + PF * tile_bytes; /* one moving wave-uniform pointer: no per-load 64-bit VGPR address chains */ \
+        _Pragma("unroll 1") for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {                                          \
+            _Pragma("unroll") for (int u = 0; u < PF; ++u) {                                                                     \
+                typename TILE::Ops o;                                                                                            \
+                __builtin_amdgcn_sched_barrier(0);                                                                               \
+                UNPACK;                                                                                                          \
+                __builtin_amdgcn_sched_barrier(0);                                                                               \
+                F = TILE::load(tp + u * tile_bytes, lane);                                                                       \
+                __builtin_amdgcn_sched_barrier(0);                                                                               \
+                MMA(g * PF + u);                                                                                                 \
+            }                                                                                                                    \
+        }                                                                                                                        \
+        _Pragma("unroll") for (int u = 0; u < PF; ++u) {                                                                         \
+            typename TILE::Ops o;                                                                                                \
+            __builtin_amdgcn_sched_barrier(0);                                                                                   \
+            UNPACK;                                                                                                              \
+            MMA((ngrp - 1) * PF + u);                                                                                            \
+        }                                                                                                                        \
     }
-    if (HAS6 && !is4) {
-        const uint8_t* tp = tile + PF * tile_bytes;
-#pragma unroll 1
-        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                OpsQ6 o;
-                __builtin_amdgcn_sched_barrier(0);
-                unpack_q6(f6[HAS6 ? u : 0], o);
-                __builtin_amdgcn_sched_barrier(0);
-                f6[HAS6 ? u : 0] = TileQ6::load(tp + u * tile_bytes, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_q6<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            OpsQ6 o;
-            __builtin_amdgcn_sched_barrier(0);
-            unpack_q6(f6[HAS6 ? u : 0], o);
-            mma_q6<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
-        }
-    }
-    if constexpr (ONLY5) {
-        const uint8_t* tp = tile + PF * tile_bytes;
-#pragma unroll 1
-        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                OpsQ4 o;
-                __builtin_amdgcn_sched_barrier(0);
-                unpack_q5_fold(f5[u], lane, o);
-                __builtin_amdgcn_sched_barrier(0);
-                f5[u] = TileQ5::load(tp + u * tile_bytes, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_q4<MT, 6>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, g * PF + u, lane, acc);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            OpsQ4 o;
-            __builtin_amdgcn_sched_barrier(0);
-            unpack_q5_fold(f5[u], lane, o);
-            mma_q4<MT, 6>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
-        }
-    }
-    if constexpr (ONLY3) {
-        const uint8_t* tp = tile + PF * tile_bytes;
-#pragma unroll 1
-        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                OpsQ4 o;
-                __builtin_amdgcn_sched_barrier(0);
-                unpack_q3(f3[u], o);
-                __builtin_amdgcn_sched_barrier(0);
-                f3[u] = TileQ3::load(tp + u * tile_bytes, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_q3<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            OpsQ4 o;
-            __builtin_amdgcn_sched_barrier(0);
-            unpack_q3(f3[u], o);
-            mma_q3<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
-        }
-    }
-    if constexpr (ONLY2) {
-        const uint8_t* tp = tile + PF * tile_bytes;
-#pragma unroll 1
-        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                OpsQ4 o;
-                __builtin_amdgcn_sched_barrier(0);
-                unpack_q2(f2[u], o);
-                __builtin_amdgcn_sched_barrier(0);
-                f2[u] = TileQ2::load(tp + u * tile_bytes, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_q2<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            OpsQ4 o;
-            __builtin_amdgcn_sched_barrier(0);
-            unpack_q2(f2[u], o);
-            mma_q2<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
-        }
-    }
-    if constexpr (ONLYT) { /* TQ2_0 tiles (TQ2_0 and TQ1_0 matrices) */
-        const uint8_t* tp = tile + PF * tile_bytes;
-#pragma unroll 1
-        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                OpsQ4 o;
-                __builtin_amdgcn_sched_barrier(0);
-                unpack_tq(ft[u], o);
-                __builtin_amdgcn_sched_barrier(0);
-                ft[u] = TileTQ::load(tp + u * tile_bytes, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_tq<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            OpsQ4 o;
-            __builtin_amdgcn_sched_barrier(0);
-            unpack_tq(ft[u], o);
-            mma_tq<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
-        }
-    }
-    if constexpr (ONLY8) {
-        const uint8_t* tp = tile + PF * tile_bytes;
-#pragma unroll 1
-        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                OpsQ8 o;
-                __builtin_amdgcn_sched_barrier(0);
-                unpack_q8(f8[u], o);
-                __builtin_amdgcn_sched_barrier(0);
-                f8[u] = TileQ8::load(tp + u * tile_bytes, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            OpsQ8 o;
-            __builtin_amdgcn_sched_barrier(0);
-            unpack_q8(f8[u], o);
-            mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
-        }
-    }
-    if constexpr (ONLY32) { /* Q4_0 / Q5_0 / IQ4_NL / IQ4_XS: the Q8_0 loop with the type's unpack in front of the Q8_0 chain */
-        const uint8_t* tp = tile + PF * tile_bytes;
-#pragma unroll 1
-        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                OpsQ8 o;
-                __builtin_amdgcn_sched_barrier(0);
-                unpack_q32(f32[u], o);
-                __builtin_amdgcn_sched_barrier(0);
-                f32[u] = TileQ32::load(tp + u * tile_bytes, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            OpsQ8 o;
-            __builtin_amdgcn_sched_barrier(0);
-            unpack_q32(f32[u], o);
-            mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
-        }
-    }
-    if constexpr (ONLY41) { /* Q4_1 / Q5_1: the same loop in front of the chain with the min term */
-        const uint8_t* tp = tile + PF * tile_bytes;
-#pragma unroll 1
-        for (int g = 0; g < ngrp - 1; ++g, tp += PF * tile_bytes) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                OpsQ81 o;
-                __builtin_amdgcn_sched_barrier(0);
-                unpack_q41(f41[u], o);
-                __builtin_amdgcn_sched_barrier(0);
-                f41[u] = TileQ41x::load(tp + u * tile_bytes, lane);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_q81<MT>(o, lds_act, lds_ad, act_ts, ad_ts, g * PF + u, lane, acc);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            OpsQ81 o;
-            __builtin_amdgcn_sched_barrier(0);
-            unpack_q41(f41[u], o);
-            mma_q81<MT>(o, lds_act, lds_ad, act_ts, ad_ts, (ngrp - 1) * PF + u, lane, acc);
-        }
+#define TK_GEMV_MMA_Q4(blk) mma_q4<MT>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, blk, lane, acc)
+#define TK_GEMV_MMA_Q6(blk) mma_q6<MT>(o, lds_act, lds_ad, act_ts, ad_ts, blk, lane, acc)
+    /* the chain of a single-type launch: the one per-type list of this kernel besides unpack16 */
+#define TK_GEMV_MMA_SINGLE(blk)                                                                                               \
+    if constexpr (ST == TK_TYPE_Q5_K) mma_q4<MT, 6>(o, lds_act, lds_abs, lds_ad, act_ts, abs_ts, ad_ts, blk, lane, acc);      \
+    else if constexpr (ST == TK_TYPE_Q3_K) mma_q3<MT>(o, lds_act, lds_ad, act_ts, ad_ts, blk, lane, acc);                     \
+    else if constexpr (ST == TK_TYPE_Q2_K) mma_q2<MT>(o, lds_act, lds_ad, act_ts, ad_ts, blk, lane, acc);                     \
+    else if constexpr (ST == TK_TYPE_TQ2_0) mma_tq<MT>(o, lds_act, lds_ad, act_ts, ad_ts, blk, lane, acc);                    \
+    else if constexpr (TileS::chain == TK_CHAIN_Q8) mma_q8<MT>(o, lds_act, lds_ad, act_ts, ad_ts, blk, lane, acc);            \
+    else mma_q81<MT>(o, lds_act, lds_ad, act_ts, ad_ts, blk, lane, acc)
+    if (HAS4 && is4) TK_GEMV_STREAM(TileQ4, f4[HAS4 ? u : 0], unpack_q4(f4[HAS4 ? u : 0], lane, o), TK_GEMV_MMA_Q4)
+    if (HAS6 && !is4) TK_GEMV_STREAM(TileQ6, f6[HAS6 ? u : 0], unpack_q6(f6[HAS6 ? u : 0], o), TK_GEMV_MMA_Q6)
+    if constexpr (SINGLE) TK_GEMV_STREAM(TileS, fs[u], unpack16<ST>(fs[u], lane, o), TK_GEMV_MMA_SINGLE)
+#undef TK_GEMV_STREAM
+#undef TK_GEMV_MMA_Q4
+#undef TK_GEMV_MMA_Q6
+#undef TK_GEMV_MMA_SINGLE
+    if constexpr (SINGLE && TileS::chain == TK_CHAIN_Q81) {
         /* the results are read under `row < nrows` only, and the compiler sinks the last tiles' finishing into that branch, behind all of
          * their MFMAs: with twice the results of a Q8_0 tile alive that spills at PF = MT = 2.  An opaque use keeps it where it is written */
 #pragma unroll
@@ -2109,9 +1956,6 @@ struct PTile { v4i pl, ph; v4f cm, da; };
 #define TK_MFMA64 __builtin_amdgcn_mfma_i32_16x16x64_i8
 /* QT: the tile type.  P = 8 Ph + Pl for Q4_K's scale digits, 64 Ph + Pl for the Q5_K / Q6_K folds, -Pl for Q3_K's one chain (mma_q3);
  * Q4_K and Q5_K have the min term on the sub-block sums.  Q2_K: P = Pl and its min term M = Ph, the second int8 chain (mma_q2) */
-constexpr bool tk_has_mins(int qt) { return qt != TK_TYPE_Q6_K && qt != TK_TYPE_Q3_K && qt != TK_TYPE_Q2_K && qt != TK_TYPE_TQ2_0; }
-/* the types with one int8 chain per M-tile and nothing else: Q3_K (holding -P) and TQ2_0 (holding P) */
-constexpr bool tk_one_chain(int qt) { return qt == TK_TYPE_Q3_K || qt == TK_TYPE_TQ2_0; }
 template <int QT>
 __device__ __forceinline__ void finish_tile(const PTile& R, const OpsQ4& o, float* acc) {
     if constexpr (QT == TK_TYPE_Q3_K) {
@@ -2156,7 +2000,7 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
     const uint8_t* act[2] = {chunk + rot * 4096, chunk - rot * 4096};
     const uint8_t* amn[2] = {chunk + OFF_AMN + rot * 512, chunk + OFF_AMN - rot * 512};
     const uint8_t* adp[2] = {chunk + OFF_AD + rot * 64, chunk + OFF_AD - rot * 64};
-#define TK_LDS_TILE(slot, m) lds_tile<tk_has_mins(QT)>(T[slot], act[(m) >= MT / 2] + (m) * 4096, amn[(m) >= MT / 2] + (m) * 512, adp[(m) >= MT / 2] + (m) * 64, lane)
+#define TK_LDS_TILE(slot, m) lds_tile<TkTile<QT>::has_mins>(T[slot], act[(m) >= MT / 2] + (m) * 4096, amn[(m) >= MT / 2] + (m) * 512, adp[(m) >= MT / 2] + (m) * 64, lane)
 #pragma unroll
     for (int m = 0; m < AD && m < MT; ++m) TK_LDS_TILE(m, m);
 #pragma unroll
@@ -2168,7 +2012,7 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
             c[w].pl = TK_MFMA64(t.a[0], o[w].bl[0], zero, 0, 0, 0);
-            if constexpr (!tk_one_chain(QT)) c[w].ph = TK_MFMA64(t.a[0], o[w].bh[0], zero, 0, 0, 0);
+            if constexpr (!TkTile<QT>::one_chain) c[w].ph = TK_MFMA64(t.a[0], o[w].bh[0], zero, 0, 0, 0);
             else c[w].ph = zero;
         }
 #pragma unroll
@@ -2176,11 +2020,11 @@ __device__ __forceinline__ void gemm_block(const OpsQ4 (&o)[NT], const uint8_t* 
 #pragma unroll
             for (int w = 0; w < NT; ++w) {
                 c[w].pl = TK_MFMA64(t.a[j2], o[w].bl[j2], c[w].pl, 0, 0, 0);
-                if constexpr (!tk_one_chain(QT)) c[w].ph = TK_MFMA64(t.a[j2], o[w].bh[j2], c[w].ph, 0, 0, 0);
+                if constexpr (!TkTile<QT>::one_chain) c[w].ph = TK_MFMA64(t.a[j2], o[w].bh[j2], c[w].ph, 0, 0, 0);
             }
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
-            if (tk_has_mins(QT)) c[w].cm = __builtin_amdgcn_mfma_f32_16x16x32_f16(t.mn, o[w].bm16, (v4f){0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+            if (TkTile<QT>::has_mins) c[w].cm = __builtin_amdgcn_mfma_f32_16x16x32_f16(t.mn, o[w].bm16, (v4f){0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
             c[w].da = t.da;
         }
         if (m > 0) {
@@ -2314,13 +2158,9 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
     }
     const int type = a.seg[seg].type;
     constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
-    constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
-    constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
-    constexpr bool ONLY32 = tk_types_only32(TYPES);
-    typedef typename TileQ32Of<TYPES>::type TileQ32;
-    constexpr bool ONLY41 = tk_types_only41(TYPES);
-    typedef typename TileQ41Of<TYPES>::type TileQ41x;
-    constexpr bool ONLYT = tk_types_is(TYPES, TK_TYPE_TQ2_0);
+    constexpr bool SINGLE = !HAS4 && !HAS6; /* every other TYPES is one type's mask: the launch's tile is that type's trait */
+    constexpr int ST = tk_types_single(TYPES);
+    typedef TkTile<ST> TileS;
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     const size_t tile_bytes = types_tile_bytes<TYPES>(is4);
     const size_t tile_pitch = (size_t)nblk_total * tile_bytes; /* to the same block of the next row tile */
@@ -2361,25 +2201,13 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
 
     TileQ4::Frag f4[HAS4 ? NT : 1];
     TileQ6::Frag f6[HAS6 ? NT : 1];
-    TileQ5::Frag f5[ONLY5 ? NT : 1];
-    TileQ3::Frag f3[ONLY3 ? NT : 1];
-    TileQ2::Frag f2[ONLY2 ? NT : 1];
-    TileQ8::Frag f8[ONLY8 ? NT : 1];
-    typename TileQ32::Frag f32[ONLY32 ? NT : 1];
-    typename TileQ41x::Frag f41[ONLY41 ? NT : 1];
-    TileTQ::Frag ft[ONLYT ? NT : 1];
+    typename TileS::Frag fs[SINGLE ? NT : 1];
     if (active) {
 #pragma unroll
         for (int w = 0; w < NT; ++w) {
             if (HAS4 && is4) f4[HAS4 ? w : 0] = TileQ4::load(tile + w * tile_pitch, lane);
             if (HAS6 && !is4) f6[HAS6 ? w : 0] = TileQ6::load(tile + w * tile_pitch, lane);
-            if constexpr (ONLY5) f5[w] = TileQ5::load(tile + w * tile_pitch, lane);
-            if constexpr (ONLY3) f3[w] = TileQ3::load(tile + w * tile_pitch, lane);
-            if constexpr (ONLY2) f2[w] = TileQ2::load(tile + w * tile_pitch, lane);
-            if constexpr (ONLY8) f8[w] = TileQ8::load(tile + w * tile_pitch, lane);
-            if constexpr (ONLY32) f32[w] = TileQ32::load(tile + w * tile_pitch, lane);
-            if constexpr (ONLY41) f41[w] = TileQ41x::load(tile + w * tile_pitch, lane);
-            if constexpr (ONLYT) ft[w] = TileTQ::load(tile + w * tile_pitch, lane);
+            if constexpr (SINGLE) fs[w] = TileS::load(tile + w * tile_pitch, lane);
         }
     }
     for (int i = 0; i < CB && i < nb; ++i) stage(i, i);
@@ -2394,95 +2222,36 @@ __global__ __launch_bounds__(512) void k_gemm_w4a8(TkGemvArgs a, int groups, int
         if (!active) continue;
         const uint8_t* chunk = lds + (((b / CB) & 1) * CB + b % CB) * CH;
         const uint8_t* next = tile + (size_t)(b + 1 < nb ? b + 1 : b) * tile_bytes; /* the last step re-requests its own tile: no branch around a load */
-        OpsQ4 o[NT];
-        /* One copy of the step per type on purpose: behind a function template the compiler schedules every instantiation differently. */
-        if (HAS4 && is4) {
-#pragma unroll
-            for (int w = 0; w < NT; ++w) unpack_q4(f4[HAS4 ? w : 0], lane, o[w]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) f4[HAS4 ? w : 0] = TileQ4::load(next + w * tile_pitch, lane);
-            __builtin_amdgcn_sched_barrier(0);
-            gemm_block<MT, NT, TK_TYPE_Q4_K>(o, chunk, rot, lane, acc);
-        }
-        if (HAS6 && !is4) {
-#pragma unroll
-            for (int w = 0; w < NT; ++w) unpack_q6_fold(f6[HAS6 ? w : 0], lane, o[w]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) f6[HAS6 ? w : 0] = TileQ6::load(next + w * tile_pitch, lane);
-            __builtin_amdgcn_sched_barrier(0);
-            gemm_block<MT, NT, TK_TYPE_Q6_K>(o, chunk, rot, lane, acc);
-        }
-        if constexpr (ONLY5) {
-#pragma unroll
-            for (int w = 0; w < NT; ++w) unpack_q5_fold(f5[w], lane, o[w]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) f5[w] = TileQ5::load(next + w * tile_pitch, lane);
-            __builtin_amdgcn_sched_barrier(0);
-            gemm_block<MT, NT, TK_TYPE_Q5_K>(o, chunk, rot, lane, acc);
-        }
-        if constexpr (ONLY3) {
-#pragma unroll
-            for (int w = 0; w < NT; ++w) unpack_q3(f3[w], o[w]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) f3[w] = TileQ3::load(next + w * tile_pitch, lane);
-            __builtin_amdgcn_sched_barrier(0);
-            gemm_block<MT, NT, TK_TYPE_Q3_K>(o, chunk, rot, lane, acc);
-        }
-        if constexpr (ONLY2) {
-#pragma unroll
-            for (int w = 0; w < NT; ++w) unpack_q2(f2[w], o[w]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) f2[w] = TileQ2::load(next + w * tile_pitch, lane);
-            __builtin_amdgcn_sched_barrier(0);
-            gemm_block<MT, NT, TK_TYPE_Q2_K>(o, chunk, rot, lane, acc);
-        }
-        if constexpr (ONLYT) {
-#pragma unroll
-            for (int w = 0; w < NT; ++w) unpack_tq(ft[w], o[w]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) ft[w] = TileTQ::load(next + w * tile_pitch, lane);
-            __builtin_amdgcn_sched_barrier(0);
-            gemm_block<MT, NT, TK_TYPE_TQ2_0>(o, chunk, rot, lane, acc);
-        }
-        if constexpr (ONLY8) {
-            OpsQ8 o8[NT];
-#pragma unroll
-            for (int w = 0; w < NT; ++w) unpack_q8(f8[w], o8[w]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) f8[w] = TileQ8::load(next + w * tile_pitch, lane);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) gemm_block_q8<MT>(o8[w], chunk, rot, lane, acc[w]);
-        }
-        if constexpr (ONLY32) {
-            OpsQ8 o8[NT];
-#pragma unroll
-            for (int w = 0; w < NT; ++w) unpack_q32(f32[w], o8[w]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) f32[w] = TileQ32::load(next + w * tile_pitch, lane);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) gemm_block_q8<MT>(o8[w], chunk, rot, lane, acc[w]);
-        }
-        if constexpr (ONLY41) {
-            OpsQ81 o8[NT];
-#pragma unroll
-            for (int w = 0; w < NT; ++w) unpack_q41(f41[w], o8[w]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) f41[w] = TileQ41x::load(next + w * tile_pitch, lane);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < NT; ++w) gemm_block_q81<MT>(o8[w], chunk, rot, lane, acc[w]);
-        }
+        /* The step is written once, as a macro that expands to the same tokens at each use: behind a function template the compiler schedules
+         * every instantiation differently.  TILE: the tile's trait; F: fragment w; UNPACK: the call that fills o[w]
+         * from it; BLOCK: a macro of the block's MFMA phase.  The operands are one array for all uses: with one array per use the Q4_K | Q6_K
+         * kernels of 4 and 8 M-tiles change.  Q6_K is folded into an OpsQ4 here (unpack_q6_fold), not into its mat-vec operands */
+        typename std::conditional<SINGLE, typename TileS::Ops, OpsQ4>::type o[NT];
+#define TK_GEMM_STEP(TILE, F, UNPACK, BLOCK)                                                            \
+    {                                                                                                  \
+        _Pragma("unroll") for (int w = 0; w < NT; ++w) UNPACK;                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                             \
+        _Pragma("unroll") for (int w = 0; w < NT; ++w) F = TILE::load(next + w * tile_pitch, lane);    \
+        __builtin_amdgcn_sched_barrier(0);                                                             \
+        BLOCK;                                                                                         \
+    }
+#define TK_GEMM_BLOCK_Q4 gemm_block<MT, NT, TK_TYPE_Q4_K>(o, chunk, rot, lane, acc)
+#define TK_GEMM_BLOCK_Q6 gemm_block<MT, NT, TK_TYPE_Q6_K>(o, chunk, rot, lane, acc)
+#define TK_GEMM_BLOCK_SINGLE                                                                                  \
+    if constexpr (TileS::chain == TK_CHAIN_FOLD) gemm_block<MT, NT, ST>(o, chunk, rot, lane, acc);            \
+    else {                                                                                                    \
+        _Pragma("unroll") for (int w = 0; w < NT; ++w) {                                                      \
+            if constexpr (TileS::chain == TK_CHAIN_Q8) gemm_block_q8<MT>(o[w], chunk, rot, lane, acc[w]);     \
+            else gemm_block_q81<MT>(o[w], chunk, rot, lane, acc[w]);                                          \
+        }                                                                                                     \
+    }
+        if constexpr (HAS4) if (is4) TK_GEMM_STEP(TileQ4, f4[HAS4 ? w : 0], unpack_q4(f4[HAS4 ? w : 0], lane, o[w]), TK_GEMM_BLOCK_Q4)
+        if constexpr (HAS6) if (!is4) TK_GEMM_STEP(TileQ6, f6[HAS6 ? w : 0], unpack_q6_fold(f6[HAS6 ? w : 0], lane, o[w]), TK_GEMM_BLOCK_Q6)
+        if constexpr (SINGLE) TK_GEMM_STEP(TileS, fs[w], unpack16<ST>(fs[w], lane, o[w]), TK_GEMM_BLOCK_SINGLE)
+#undef TK_GEMM_STEP
+#undef TK_GEMM_BLOCK_Q4
+#undef TK_GEMM_BLOCK_Q6
+#undef TK_GEMM_BLOCK_SINGLE
     }
     if (!active) return;
 
@@ -2788,19 +2557,6 @@ __device__ __forceinline__ void unpack_q41_x32(const FragQ51& f0, const FragQ51&
     q32_scales(up ? f1.d : f0.d, o.d);
     q32_scales(up ? f1.m : f0.m, o.m);
 }
-/* the types that run the chains with the min term (gemm_block32_q81); they read the A operand as the Q8_0 chains do */
-constexpr bool tk_is_q41(int qt) { return qt == TK_TYPE_Q4_1 || qt == TK_TYPE_Q5_1; }
-/* the types that run the Q8_0 chains: one K = 32 MFMA and one scale per 32-block */
-constexpr bool tk_is_q32(int qt) { return qt == TK_TYPE_Q8_0 || qt == TK_TYPE_Q4_0 || qt == TK_TYPE_Q5_0 || qt == TK_TYPE_IQ4_NL || qt == TK_TYPE_IQ4_XS; }
-template <int QT> struct G32Ops { typedef struct Ops32 type; };
-template <> struct G32Ops<TK_TYPE_Q8_0> { typedef Ops32Q8 type; };
-template <> struct G32Ops<TK_TYPE_Q4_0> { typedef Ops32Q8 type; };
-template <> struct G32Ops<TK_TYPE_Q5_0> { typedef Ops32Q8 type; };
-template <> struct G32Ops<TK_TYPE_IQ4_NL> { typedef Ops32Q8 type; };
-template <> struct G32Ops<TK_TYPE_IQ4_XS> { typedef Ops32Q8 type; };
-template <> struct G32Ops<TK_TYPE_Q4_1> { typedef Ops32Q81 type; };
-template <> struct G32Ops<TK_TYPE_Q5_1> { typedef Ops32Q81 type; };
-
 /* s_waitcnt vmcnt(n) alone (expcnt / lgkmcnt untouched): until all but this wave's n youngest vector-memory operations are done.  The
  * LDS-DMA pieces of a chunk are invisible to the compiler's own wait insertion, so the ring is guarded by hand. */
 __device__ __forceinline__ void wait_vmcnt(int n) {
@@ -2843,14 +2599,14 @@ __device__ __forceinline__ v4i q8_a32(const Ptrs32& p, int t, int j) {
 
 template <int QT>
 __device__ __forceinline__ void load_atile32(ATile32& T, const Ptrs32& p, int t) {
-    if constexpr (tk_is_q32(QT) || tk_is_q41(QT)) {
+    if constexpr (TkTile<QT>::chain != TK_CHAIN_FOLD) { /* the Q8_0 chains, with the min term or without, read 8-byte halves */
 #pragma unroll
         for (int j = 0; j < 4; ++j) T.a[j] = q8_a32(p, t, j);
         return;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) T.a[u] = *(const v4i*)(p.ap + t * 8192 + (u >> 1) * 1024 + (u & 1) * 256);
-    if (tk_has_mins(QT)) T.mn = *(const v8h*)(p.mp + t * 1024);
+    if (TkTile<QT>::has_mins) T.mn = *(const v8h*)(p.mp + t * 1024);
 }
 
 /* one 256-k block: this wave's 32 weight rows x its four 32-row M-tiles.  T arrives holding tile 0's operands; the operands of tile
@@ -2866,7 +2622,7 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
         /* P = 8 Ph + Pl (64 Ph + Pl for Q6_K) inside ONE accumulator: the high-digit chain first, its result shifted on the VALU, then the
          * low-digit chain on top of it (sixteen live registers fewer than two accumulators, and the finishing below needs no shift-add);
          * the independent min-term MFMA sits where the shift waits for the last high-digit MFMA.  Q5_K: 64 Ph + Pl with the min term */
-        constexpr bool MINS = tk_has_mins(QT); /* Q3_K: the low chain alone, from zero, holding -P (TQ2_0: the same, holding P).  Q2_K: ph is the min chain M and stays
+        constexpr bool MINS = TkTile<QT>::has_mins; /* Q3_K: the low chain alone, from zero, holding -P (TQ2_0: the same, holding P).  Q2_K: ph is the min chain M and stays
                                                 * beside pl = P, which starts from zero (the registers cm has for the other min types) */
         v4i A[8];
 #pragma unroll
@@ -2879,7 +2635,7 @@ __device__ __forceinline__ void gemm_block32(const Ops32& o, ATile32& T, const P
         v16i ph = zero;
         v16f cm;
         v16i pl;
-        if constexpr (!tk_one_chain(QT)) {
+        if constexpr (!TkTile<QT>::one_chain) {
 #pragma unroll
             for (int u = 0; u < 8; ++u) ph = TK_MFMA32(A[u], o.bh[u], ph, 0, 0, 0);
         }
@@ -2993,92 +2749,13 @@ template <int QT>
 __device__ __forceinline__ typename TkTile<QT>::Frag g32_load(const uint8_t* tile, int lane) {
     unsigned lo = (unsigned)lane * 16u, ho = (unsigned)(lane & 15) * 16u;
     asm volatile("" : "+v"(lo), "+v"(ho));
-    if constexpr (QT == TK_TYPE_Q8_0) {
-        FragQ8 f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f.q[i] = ldg_nt(tile + 1024 * i + lo);
-        f.d = ldg_nt(tile + 4096 + ho);
-        return f;
-    } else if constexpr (QT == TK_TYPE_Q4_0 || QT == TK_TYPE_IQ4_NL || QT == TK_TYPE_IQ4_XS) { /* one tile layout, one set of loads */
-        FragQ4x<QT> f;
-        f.q0 = ldg_nt(tile + lo);
-        f.q1 = ldg_nt(tile + 1024 + lo);
-        f.d = ldg_nt(tile + 2048 + ho);
-        return f;
-    } else if constexpr (QT == TK_TYPE_Q4_1) {
-        FragQ41 f;
-        f.q0 = ldg_nt(tile + lo);
-        f.q1 = ldg_nt(tile + 1024 + lo);
-        f.d = ldg_nt(tile + 2048 + 2 * ho);
-        f.m = ldg_nt(tile + 2064 + 2 * ho);
-        return f;
-    } else if constexpr (QT == TK_TYPE_Q5_1) {
-        FragQ51 f;
-        f.q0 = ldg_nt(tile + lo);
-        f.q1 = ldg_nt(tile + 1024 + lo);
-        const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + (lo >> 1)));
-        f.qh = make_uint2(qh.x, qh.y);
-        f.d = ldg_nt(tile + 2560 + 2 * ho);
-        f.m = ldg_nt(tile + 2576 + 2 * ho);
-        return f;
-    } else if constexpr (QT == TK_TYPE_Q5_0) {
-        FragQ50 f;
-        f.q0 = ldg_nt(tile + lo);
-        f.q1 = ldg_nt(tile + 1024 + lo);
-        const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + (lo >> 1)));
-        f.qh = make_uint2(qh.x, qh.y);
-        f.d = ldg_nt(tile + 2560 + ho);
-        return f;
-    } else if constexpr (QT == TK_TYPE_TQ2_0) {
-        FragTQ f;
-        f.q = ldg_nt(tile + lo);
-        f.d = *(const uint16_t*)(tile + 1024 + (ho >> 3));
-        return f;
-    } else if constexpr (QT == TK_TYPE_Q2_K) {
-        FragQ2 f;
-        f.q = ldg_nt(tile + lo);
-        const v2u32 sm = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + ho + ((lo >> 6) & 8u)));
-        f.sm = make_uint2(sm.x, sm.y);
-        f.dd = *(const uint32_t*)(tile + 1280 + (ho >> 2));
-        return f;
-    } else if constexpr (QT == TK_TYPE_Q3_K) {
-        FragQ3 f;
-        f.q = ldg_nt(tile + lo);
-        const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 1024 + (lo >> 1)));
-        f.qh = make_uint2(qh.x, qh.y);
-        const v2u32 sc = __builtin_nontemporal_load((const v2u32*)(tile + 1536 + ho + ((lo >> 6) & 8u)));
-        f.sc = make_uint2(sc.x, sc.y);
-        f.d = *(const uint16_t*)(tile + 1792 + (ho >> 3));
-        return f;
-    } else if constexpr (QT == TK_TYPE_Q5_K) {
-        FragQ5 f;
-        f.q0 = ldg_nt(tile + lo);
-        f.q1 = ldg_nt(tile + 1024 + lo);
-        const v2u32 qh = __builtin_nontemporal_load((const v2u32*)(tile + 2048 + (lo >> 1)));
-        f.qh = make_uint2(qh.x, qh.y);
-        f.h = ldg_nt(tile + 2560 + ho);
-        return f;
-    } else if constexpr (QT == TK_TYPE_Q4_K) {
-        FragQ4 f;
-        f.q0 = ldg_nt(tile + lo);
-        f.q1 = ldg_nt(tile + 1024 + lo);
-        f.h = ldg_nt(tile + 2048 + ho);
-        return f;
-    } else {
-        FragQ6 f;
-        f.q0 = ldg_nt(tile + lo);
-        f.q1 = ldg_nt(tile + 1024 + lo);
-        f.qh = ldg_nt(tile + 2048 + lo);
-        f.sc = ldg_nt(tile + 3072 + ho);
-        f.d = *(const uint16_t*)(tile + 3328 + (ho >> 3));
-        return f;
-    }
+    return TkTile<QT>::load_at(tile, OpaqueOffsets{lo, ho});
 }
 template <int QT>
-__device__ __forceinline__ void g32_unpack(const typename TkTile<QT>::Frag& f0, const typename TkTile<QT>::Frag& f1, int lane, typename G32Ops<QT>::type& o) {
+__device__ __forceinline__ void g32_unpack(const typename TkTile<QT>::Frag& f0, const typename TkTile<QT>::Frag& f1, int lane, typename TkTile<QT>::Ops32& o) {
     if constexpr (QT == TK_TYPE_Q8_0) unpack_q8_x32(f0, f1, lane, o);
-    else if constexpr (QT == TK_TYPE_Q4_0 || QT == TK_TYPE_Q5_0 || QT == TK_TYPE_IQ4_NL || QT == TK_TYPE_IQ4_XS) unpack_q32_x32(f0, f1, lane, o);
-    else if constexpr (tk_is_q41(QT)) unpack_q41_x32(f0, f1, lane, o);
+    else if constexpr (TkTile<QT>::chain == TK_CHAIN_Q8) unpack_q32_x32(f0, f1, lane, o);
+    else if constexpr (TkTile<QT>::chain == TK_CHAIN_Q81) unpack_q41_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q4_K) unpack_q4_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q5_K) unpack_q5_x32(f0, f1, lane, o);
     else if constexpr (QT == TK_TYPE_Q3_K) unpack_q3_x32(f0, f1, lane, o);
@@ -3116,7 +2793,7 @@ __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_byte
         ATile32 T;
         load_atile32<QT>(T, bp, 0); /* tile 0's operands: their LDS latency hides under the unpack */
         __builtin_amdgcn_sched_barrier(0);
-        typename G32Ops<QT>::type o;
+        typename TkTile<QT>::Ops32 o;
         g32_unpack<QT>(f0, f1, lane, o);
         __builtin_amdgcn_sched_barrier(0);
         f0 = g32_load<QT>(next, lane);
@@ -3124,8 +2801,8 @@ __device__ __forceinline__ void g32_k_loop(const uint8_t* tile, size_t tile_byte
         __builtin_amdgcn_sched_barrier(0);
         /* the last block restages itself into the slot nobody reads any more: no branch around the DMA issue */
         /* the ring's four staging parts ride on the tiles' MFMA phases: one per tile */
-        if constexpr (tk_is_q32(QT)) gemm_block32_q8(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
-        else if constexpr (tk_is_q41(QT)) gemm_block32_q81(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
+        if constexpr (TkTile<QT>::chain == TK_CHAIN_Q8) gemm_block32_q8(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
+        else if constexpr (TkTile<QT>::chain == TK_CHAIN_Q81) gemm_block32_q81(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
         else gemm_block32<QT>(o, T, bp, acc, [&](int t) { stage_part(more ? b + 1 : b, (b + 1) & 1, t); });
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -3178,8 +2855,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     }
     const int type = a.seg[seg].type;
     constexpr bool HAS4 = tk_types_has(TYPES, TK_TYPE_Q4_K), HAS6 = tk_types_has(TYPES, TK_TYPE_Q6_K);
-    constexpr bool ONLY5 = tk_types_is(TYPES, TK_TYPE_Q5_K), ONLY3 = tk_types_is(TYPES, TK_TYPE_Q3_K), ONLY2 = tk_types_is(TYPES, TK_TYPE_Q2_K);
-    constexpr bool ONLY8 = tk_types_is(TYPES, TK_TYPE_Q8_0);
     const bool is4 = HAS4 && (!HAS6 || type == TK_TYPE_Q4_K);
     const size_t tile_bytes = types_tile_bytes<TYPES>(is4);
     const ptrdiff_t tile_pitch = a.swiglu ? a.seg[1].tiles - a.seg[0].tiles : (ptrdiff_t)((size_t)nblk_total * tile_bytes);
@@ -3238,17 +2913,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm32_w4a8(TkGemvArgs a, int groups
     }
     if (HAS4 && is4) g32_k_loop<TK_TYPE_Q4_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
     if (HAS6 && !is4) g32_k_loop<TK_TYPE_Q6_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (ONLY5) g32_k_loop<TK_TYPE_Q5_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (ONLY3) g32_k_loop<TK_TYPE_Q3_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (ONLY2) g32_k_loop<TK_TYPE_Q2_K>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (ONLY8) g32_k_loop<TK_TYPE_Q8_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (tk_types_is(TYPES, TK_TYPE_Q4_0)) g32_k_loop<TK_TYPE_Q4_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (tk_types_is(TYPES, TK_TYPE_Q5_0)) g32_k_loop<TK_TYPE_Q5_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (tk_types_is(TYPES, TK_TYPE_IQ4_NL)) g32_k_loop<TK_TYPE_IQ4_NL>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (tk_types_is(TYPES, TK_TYPE_IQ4_XS)) g32_k_loop<TK_TYPE_IQ4_XS>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (tk_types_is(TYPES, TK_TYPE_Q4_1)) g32_k_loop<TK_TYPE_Q4_1>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (tk_types_is(TYPES, TK_TYPE_Q5_1)) g32_k_loop<TK_TYPE_Q5_1>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
-    if constexpr (tk_types_is(TYPES, TK_TYPE_TQ2_0)) g32_k_loop<TK_TYPE_TQ2_0>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
+    if constexpr (!HAS4 && !HAS6) g32_k_loop<tk_types_single(TYPES)>(tile, tile_bytes, tile_pitch, nb, lds, CH, lane, acc, stage_small, stage_part);
 
     /* Epilogue: 64 accumulator registers per lane.  Stored as they stand, a store instruction writes one dword per lane (two 128-byte row
      * segments): 64 store instructions per wave, and the tail of the launch is store-ISSUE bound (exit - loop end 4 us of gate|up's 76).
@@ -3323,34 +2988,47 @@ static constexpr int TK_GEMM32_FROM_ROWS = 12 * TK_ROW_SLOTS + 1;
  * tk_llm_prepare_device() opts each of them into TK_MAX_DYN_LDS.  nullptr: a combination no launch makes. */
 typedef void (*TkGemvKernel)(TkGemvArgs, int, int);
 typedef void (*TkGemm32Kernel)(TkGemvArgs, int, int, int);
-/* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight; two M-tiles never run Q6_K alone.  Type index =
- * the type's kernel_index (tk_type_desc_of), TK_KERNEL_INDEX_Q4K_Q6K for the mix; the static_asserts below hold every column to it */
+/* The fourteen TYPES values in column order, once: X(TYPES, ...) per column.  Type index = the type's kernel_index (tk_type_desc_of),
+ * TK_KERNEL_INDEX_Q4K_Q6K for the mix; the static_assert below holds every column to it */
+#define TK_TYPES_COLUMNS(X, ...)                                                                                                        \
+    X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(8, __VA_ARGS__) X(16, __VA_ARGS__) X(32, __VA_ARGS__)     \
+    X(64, __VA_ARGS__) X(128, __VA_ARGS__) X(256, __VA_ARGS__) X(512, __VA_ARGS__) X(1024, __VA_ARGS__) X(2048, __VA_ARGS__) X(4096, __VA_ARGS__)
+/* two M-tiles never run Q6_K alone (tk_launch_gemv takes the mix's kernel): those two entries are nullptr and nothing is instantiated for them */
+template <int PF, int MT, int TYPES, int FUSE>
+constexpr TkGemvKernel tk_gemv_fn() {
+    if constexpr (MT == 2 && tk_types_is(TYPES, TK_TYPE_Q6_K)) return nullptr;
+    else return k_gemv_w4a8<PF, MT, TYPES, FUSE>;
+}
+#define TK_GEMV_FN(TYPES, PF, MT, FUSE) tk_gemv_fn<PF, MT, TYPES, FUSE>(),
+#define TK_GEMM_FN(TYPES, MT) k_gemm_w4a8<MT, TYPES>,
+#define TK_GEMM32_FN(TYPES, UNUSED) k_gemm32_w4a8<TYPES>,
+#define TK_COLUMN_TYPES(TYPES, UNUSED) TYPES,
+/* [fuse][mt - 1][pf - 1][type index]: fused launches have one M-tile and two tiles in flight */
 static const TkGemvKernel k_gemv_fns[3][2][2][TK_KERNEL_VARIANTS] = {
-    {{{k_gemv_w4a8<1, 1, 1, 0>, k_gemv_w4a8<1, 1, 2, 0>, k_gemv_w4a8<1, 1, 3, 0>, k_gemv_w4a8<1, 1, 4, 0>, k_gemv_w4a8<1, 1, 8, 0>, k_gemv_w4a8<1, 1, 16, 0>, k_gemv_w4a8<1, 1, 32, 0>, k_gemv_w4a8<1, 1, 64, 0>, k_gemv_w4a8<1, 1, 128, 0>, k_gemv_w4a8<1, 1, 256, 0>, k_gemv_w4a8<1, 1, 512, 0>, k_gemv_w4a8<1, 1, 1024, 0>, k_gemv_w4a8<1, 1, 2048, 0>, k_gemv_w4a8<1, 1, 4096, 0>},
-      {k_gemv_w4a8<2, 1, 1, 0>, k_gemv_w4a8<2, 1, 2, 0>, k_gemv_w4a8<2, 1, 3, 0>, k_gemv_w4a8<2, 1, 4, 0>, k_gemv_w4a8<2, 1, 8, 0>, k_gemv_w4a8<2, 1, 16, 0>, k_gemv_w4a8<2, 1, 32, 0>, k_gemv_w4a8<2, 1, 64, 0>, k_gemv_w4a8<2, 1, 128, 0>, k_gemv_w4a8<2, 1, 256, 0>, k_gemv_w4a8<2, 1, 512, 0>, k_gemv_w4a8<2, 1, 1024, 0>, k_gemv_w4a8<2, 1, 2048, 0>, k_gemv_w4a8<2, 1, 4096, 0>}},
-     {{k_gemv_w4a8<1, 2, 1, 0>, nullptr, k_gemv_w4a8<1, 2, 3, 0>, k_gemv_w4a8<1, 2, 4, 0>, k_gemv_w4a8<1, 2, 8, 0>, k_gemv_w4a8<1, 2, 16, 0>, k_gemv_w4a8<1, 2, 32, 0>, k_gemv_w4a8<1, 2, 64, 0>, k_gemv_w4a8<1, 2, 128, 0>, k_gemv_w4a8<1, 2, 256, 0>, k_gemv_w4a8<1, 2, 512, 0>, k_gemv_w4a8<1, 2, 1024, 0>, k_gemv_w4a8<1, 2, 2048, 0>, k_gemv_w4a8<1, 2, 4096, 0>},
-      {k_gemv_w4a8<2, 2, 1, 0>, nullptr, k_gemv_w4a8<2, 2, 3, 0>, k_gemv_w4a8<2, 2, 4, 0>, k_gemv_w4a8<2, 2, 8, 0>, k_gemv_w4a8<2, 2, 16, 0>, k_gemv_w4a8<2, 2, 32, 0>, k_gemv_w4a8<2, 2, 64, 0>, k_gemv_w4a8<2, 2, 128, 0>, k_gemv_w4a8<2, 2, 256, 0>, k_gemv_w4a8<2, 2, 512, 0>, k_gemv_w4a8<2, 2, 1024, 0>, k_gemv_w4a8<2, 2, 2048, 0>, k_gemv_w4a8<2, 2, 4096, 0>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 1>, k_gemv_w4a8<2, 1, 2, 1>, k_gemv_w4a8<2, 1, 3, 1>, k_gemv_w4a8<2, 1, 4, 1>, k_gemv_w4a8<2, 1, 8, 1>, k_gemv_w4a8<2, 1, 16, 1>, k_gemv_w4a8<2, 1, 32, 1>, k_gemv_w4a8<2, 1, 64, 1>, k_gemv_w4a8<2, 1, 128, 1>, k_gemv_w4a8<2, 1, 256, 1>, k_gemv_w4a8<2, 1, 512, 1>, k_gemv_w4a8<2, 1, 1024, 1>, k_gemv_w4a8<2, 1, 2048, 1>, k_gemv_w4a8<2, 1, 4096, 1>}}},
-    {{{}, {k_gemv_w4a8<2, 1, 1, 2>, k_gemv_w4a8<2, 1, 2, 2>, k_gemv_w4a8<2, 1, 3, 2>, k_gemv_w4a8<2, 1, 4, 2>, k_gemv_w4a8<2, 1, 8, 2>, k_gemv_w4a8<2, 1, 16, 2>, k_gemv_w4a8<2, 1, 32, 2>, k_gemv_w4a8<2, 1, 64, 2>, k_gemv_w4a8<2, 1, 128, 2>, k_gemv_w4a8<2, 1, 256, 2>, k_gemv_w4a8<2, 1, 512, 2>, k_gemv_w4a8<2, 1, 1024, 2>, k_gemv_w4a8<2, 1, 2048, 2>, k_gemv_w4a8<2, 1, 4096, 2>}}},
+    {{{TK_TYPES_COLUMNS(TK_GEMV_FN, 1, 1, 0)}, {TK_TYPES_COLUMNS(TK_GEMV_FN, 2, 1, 0)}},
+     {{TK_TYPES_COLUMNS(TK_GEMV_FN, 1, 2, 0)}, {TK_TYPES_COLUMNS(TK_GEMV_FN, 2, 2, 0)}}},
+    {{{}, {TK_TYPES_COLUMNS(TK_GEMV_FN, 2, 1, 1)}}},
+    {{{}, {TK_TYPES_COLUMNS(TK_GEMV_FN, 2, 1, 2)}}},
 };
 /* [mt / 2 - 2][type index] */
 static const TkGemvKernel k_gemm_fns[5][TK_KERNEL_VARIANTS] = {
-    {k_gemm_w4a8<4, 1>, k_gemm_w4a8<4, 2>, k_gemm_w4a8<4, 3>, k_gemm_w4a8<4, 4>, k_gemm_w4a8<4, 8>, k_gemm_w4a8<4, 16>, k_gemm_w4a8<4, 32>, k_gemm_w4a8<4, 64>, k_gemm_w4a8<4, 128>, k_gemm_w4a8<4, 256>, k_gemm_w4a8<4, 512>, k_gemm_w4a8<4, 1024>, k_gemm_w4a8<4, 2048>, k_gemm_w4a8<4, 4096>},
-    {k_gemm_w4a8<6, 1>, k_gemm_w4a8<6, 2>, k_gemm_w4a8<6, 3>, k_gemm_w4a8<6, 4>, k_gemm_w4a8<6, 8>, k_gemm_w4a8<6, 16>, k_gemm_w4a8<6, 32>, k_gemm_w4a8<6, 64>, k_gemm_w4a8<6, 128>, k_gemm_w4a8<6, 256>, k_gemm_w4a8<6, 512>, k_gemm_w4a8<6, 1024>, k_gemm_w4a8<6, 2048>, k_gemm_w4a8<6, 4096>},
-    {k_gemm_w4a8<8, 1>, k_gemm_w4a8<8, 2>, k_gemm_w4a8<8, 3>, k_gemm_w4a8<8, 4>, k_gemm_w4a8<8, 8>, k_gemm_w4a8<8, 16>, k_gemm_w4a8<8, 32>, k_gemm_w4a8<8, 64>, k_gemm_w4a8<8, 128>, k_gemm_w4a8<8, 256>, k_gemm_w4a8<8, 512>, k_gemm_w4a8<8, 1024>, k_gemm_w4a8<8, 2048>, k_gemm_w4a8<8, 4096>},
-    {k_gemm_w4a8<10, 1>, k_gemm_w4a8<10, 2>, k_gemm_w4a8<10, 3>, k_gemm_w4a8<10, 4>, k_gemm_w4a8<10, 8>, k_gemm_w4a8<10, 16>, k_gemm_w4a8<10, 32>, k_gemm_w4a8<10, 64>, k_gemm_w4a8<10, 128>, k_gemm_w4a8<10, 256>, k_gemm_w4a8<10, 512>, k_gemm_w4a8<10, 1024>, k_gemm_w4a8<10, 2048>, k_gemm_w4a8<10, 4096>},
-    {k_gemm_w4a8<12, 1>, k_gemm_w4a8<12, 2>, k_gemm_w4a8<12, 3>, k_gemm_w4a8<12, 4>, k_gemm_w4a8<12, 8>, k_gemm_w4a8<12, 16>, k_gemm_w4a8<12, 32>, k_gemm_w4a8<12, 64>, k_gemm_w4a8<12, 128>, k_gemm_w4a8<12, 256>, k_gemm_w4a8<12, 512>, k_gemm_w4a8<12, 1024>, k_gemm_w4a8<12, 2048>, k_gemm_w4a8<12, 4096>},
+    {TK_TYPES_COLUMNS(TK_GEMM_FN, 4)}, {TK_TYPES_COLUMNS(TK_GEMM_FN, 6)}, {TK_TYPES_COLUMNS(TK_GEMM_FN, 8)}, {TK_TYPES_COLUMNS(TK_GEMM_FN, 10)}, {TK_TYPES_COLUMNS(TK_GEMM_FN, 12)},
 };
 /* [type index] */
-static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {k_gemm32_w4a8<1>, k_gemm32_w4a8<2>, k_gemm32_w4a8<3>, k_gemm32_w4a8<4>, k_gemm32_w4a8<8>, k_gemm32_w4a8<16>, k_gemm32_w4a8<32>, k_gemm32_w4a8<64>, k_gemm32_w4a8<128>, k_gemm32_w4a8<256>, k_gemm32_w4a8<512>, k_gemm32_w4a8<1024>, k_gemm32_w4a8<2048>, k_gemm32_w4a8<4096>};
+static const TkGemm32Kernel k_gemm32_fns[TK_KERNEL_VARIANTS] = {TK_TYPES_COLUMNS(TK_GEMM32_FN, 0)};
 
 /* column c of the three tables holds the kernels of TYPES = tk_column_types[c]: every type's mask at its kernel_index */
 constexpr bool tk_columns_match_the_type_table() {
-    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {1, 2, 3, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096};
+    constexpr int tk_column_types[TK_KERNEL_VARIANTS] = {TK_TYPES_COLUMNS(TK_COLUMN_TYPES, 0)};
     for (int i = 0; i < TK_TILED_TYPES; ++i)
         if (tk_column_types[tk_type_desc_of(tk_tiled_type(i)).kernel_index] != tk_type_desc_of(tk_tiled_type(i)).mask) return false;
     return tk_column_types[TK_KERNEL_INDEX_Q4K_Q6K] == TK_TYPES_Q4K_Q6K;
 }
+#undef TK_GEMV_FN
+#undef TK_GEMM_FN
+#undef TK_GEMM32_FN
+#undef TK_COLUMN_TYPES
+#undef TK_TYPES_COLUMNS
 static_assert(tk_columns_match_the_type_table(), "k_gemv_fns / k_gemm_fns / k_gemm32_fns: column order against tk_type_desc_of");
 
 void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
