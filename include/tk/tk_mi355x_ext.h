@@ -321,6 +321,46 @@ TK_API const char* tk_mi355x_llm_runner_tool_call_text(struct tk_llm_runner_s* r
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_gemm_pair(int device, int M, int N, int K, const float* a, const float* w, const float* bias,
                                                         const float* residual, int act, int f16, float* c_staged, float* c_tiled);
 
+/* test hook for the perception GEMM launcher (csrc/nn/tk_nn_kernels: tk_launch_gemm): ONE launch described by plain numbers and host arrays,
+ * so that every kernel and instantiation the launcher can take — the element-wise fallbacks, [K][N] weights, the two-level batch, implicit
+ * im2col, pitches wider than the extent, f16 B, the opt-in split-f16 contraction — is reachable at shapes no network sends.
+ * The fields mirror the launcher's descriptor (csrc/common/tk_gemm_desc.h) one to one.  a / b / bias / residual / c are host arrays of
+ * n_a / n_b / n_bias / n_residual / n_c ELEMENTS (b: uint16 f16 bits when b_f16 != 0, float otherwise; bias and residual may be NULL with
+ * count 0); each is copied into a device allocation of exactly that size, A and B a_offset / b_offset elements into theirs (the only way to
+ * a base that is not 16-byte aligned).  c is IN/OUT: its content is uploaded before the launch and the whole array read back after it, so
+ * columns n >= N inside the pitch, rows >= M and the gaps between batch members come back as the caller left them.
+ * Every address the descriptor can reach is checked against those counts first: anything outside, a negative extent, pitch or stride, a C
+ * pitch below N or an unknown act is TK_ERROR_INVALID_ARGUMENT and nothing is launched; so is a descriptor the launcher itself refuses
+ * (kernel = -1: an implicit-im2col form with [K][N] weights (b_kn != 0: its kernels read B as [N][K] only), f16 weights, or without 16-byte
+ * groups — channels, pixel pitch, K or ldb no multiple of 4, a base off 16 bytes, K not whole rows of taps).
+ * kernel (out) is the launcher's own answer, tk_gemm_kernel_of: family * 1000 + IM * 100 + PATH * 10 + NT with family 0 k_gemm_f32,
+ * 1 k_gemm_f32_tall, 2 k_gemm_f32_big, 3 k_gemm_h3_tall, 4 k_gemm_h3_big; IM 1 = implicit im2col; PATH the operand loaders' instantiation
+ * (0 element-wise fallbacks, 1 [N][K] and 2 [K][N] 16-byte groups); NT the 32-column accumulators per wave of the tall kernels (0 elsewhere).
+ * device < 0: validate and report `kernel` only — no device is touched (the answer then assumes 16-byte aligned allocations, which is what
+ * the device allocator returns). */
+typedef struct {
+    int32_t M, N, K, lda, ldb, ldc, ldr, b_kn, act;
+    float alpha;
+    int32_t batch, batch_inner;
+    int64_t sA, sB, sC, sR, sA2, sB2, sC2, sR2;
+    int32_t b_f16;
+    int32_t im_C, im_H, im_W, im_ldx, im_kw, im_stride, im_pad, im_Ho, im_Wo;
+    int32_t fast;
+    int32_t a_offset, b_offset;
+    int32_t kernel; /* out */
+    const float* a; const void* b; const float* bias; const float* residual; float* c;
+    int64_t n_a, n_b, n_bias, n_residual, n_c;
+} tk_mi355x_gemm_probe_t;
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_gemm_probe(int device, tk_mi355x_gemm_probe_t* p);
+
+/* test hook for the fused split-f16 attention (csrc/nn/tk_nn_kernels: tk_launch_attention_h3): ONE launch over host arrays.  q and out
+ * [B] sequences q_bstride floats apart, each [Tq] rows of pitch d; k and v [B] x [Tk] rows of pitch d, kv_bstride apart; head h reads and writes
+ * columns [64 h, 64 h + 64).  n_q counts q's and out's floats, n_kv k's and v's.  out is IN/OUT like the GEMM probe's c: rows >= Tq and the
+ * floats between sequences keep the caller's content.  Arrays too small for the geometry, or a geometry the launcher refuses (d != 64 nh, a
+ * stride that is not a multiple of 4), are TK_ERROR_INVALID_ARGUMENT: nothing is launched and out is not written. */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_attention_h3_probe(int device, int B, int nh, int Tq, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, float scale,
+                                                                 const float* q, const float* k, const float* v, int64_t n_q, int64_t n_kv, float* out);
+
 /* test hook for the node-by-node ONNX executor (csrc/nn/tk_onnx_exec): loads `path`, binds the n_feeds float tensors (name, data on the
  * host, rank and dims), runs the graph once and keeps host copies of the n_outputs named float values WITH THE SHAPES THE EXECUTOR
  * PRODUCED.  A refusal (unsupported op / attribute, bad shapes) comes back as an error code with the executor's text as the error

@@ -28,7 +28,7 @@ struct TkGemm {
     int c_feeds_linear;
     /* implicit im2col (im_C > 0): A is a convolution's NHWC input [B][im_H][im_W] pixels of pitch im_ldx; GEMM row m = (b, oy, ox) over
      * im_Ho x im_Wo outputs and column k = (ky im_kw + kx) im_C + c address it directly (zero outside the image), K = kh kw im_C.
-     * Same values in the same order as the explicit column matrix; lda, batch and b_kn are unused */
+     * Same values in the same order as the explicit column matrix; lda and batch are unused, B is [N][ldb] (b_kn must be 0) */
     int im_C, im_H, im_W, im_ldx, im_kw, im_stride, im_pad, im_Ho, im_Wo;
     /* opt-in (0 = the exact chain above, always what the oracle evaluates): the HIP backend may contract on the f16 matrix pipe with every
      * operand split into two f16 halves (x = hi + lo / 2048 to ~22 bits; hi.hi + (hi.lo + lo.hi) / 2048 with fp32 accumulation): NOT the

@@ -172,6 +172,118 @@ tk_error_code_t tk_mi355x_gemm_pair(int device, int M, int N, int K, const float
     return ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
 }
 
+/* the highest element index each operand of a launch can touch (-1: never read), from the loaders' own predicates: a row m < M, a column
+ * k < K / n < N, every batch member; false: a field outside what a launch may hold.  Extents are capped so that no product leaves int64. */
+struct ProbeReach { int64_t a, b, c, r; };
+static bool probe_reach(const tk_mi355x_gemm_probe_t& p, ProbeReach& o) {
+    const int64_t cap = (int64_t)1 << 28;
+    auto dim = [&](int64_t v) { return v >= 1 && v <= cap; };
+    auto str = [&](int64_t v) { return v >= 0 && v <= cap; };
+    if (!dim(p.M) || !dim(p.N) || !dim(p.K) || !dim(p.ldb) || !dim(p.ldc) || p.ldc < p.N || p.act < 0 || p.act > 3) return false;
+    if (p.batch < 1 || p.batch > 4096 || p.batch_inner < 0 || p.batch_inner > p.batch || (p.batch_inner > 0 && p.batch % p.batch_inner)) return false;
+    if ((p.b_kn != 0 && p.b_kn != 1) || (p.b_f16 != 0 && p.b_f16 != 1) || p.a_offset < 0 || p.a_offset > 64 || p.b_offset < 0 || p.b_offset > 64) return false;
+    const int64_t st[8] = {p.sA, p.sB, p.sC, p.sR, p.sA2, p.sB2, p.sC2, p.sR2};
+    for (int64_t v : st) if (!str(v)) return false;
+    if (p.residual && (!dim(p.ldr) || p.ldr < p.N)) return false;
+    /* offset of the last batch member along one operand's strides */
+    const int64_t zi = p.batch_inner > 0 ? p.batch_inner - 1 : p.batch - 1, zo = p.batch_inner > 0 ? p.batch / p.batch_inner - 1 : 0;
+    auto last = [&](int64_t s1, int64_t s2) { return zi * s1 + (p.batch_inner > 0 ? zo * s2 : 0); };
+    if (p.im_C > 0) {
+        if (!dim(p.im_H) || !dim(p.im_W) || !dim(p.im_ldx) || p.im_ldx < p.im_C || !dim(p.im_kw) || !dim(p.im_stride) || p.im_pad < 0 || p.im_pad > cap ||
+            !dim(p.im_Ho) || !dim(p.im_Wo) || p.batch != 1 || p.K % ((int64_t)p.im_C * p.im_kw))
+            return false;
+        const int64_t images = ((int64_t)p.M - 1) / ((int64_t)p.im_Ho * p.im_Wo) + 1; /* a row addresses image m / (Ho Wo), any pixel inside it */
+        if (images > cap / p.im_H / p.im_W) return false;
+        o.a = (images * p.im_H * p.im_W - 1) * p.im_ldx + p.im_C - 1;
+    } else {
+        if (p.im_C < 0 || !dim(p.lda)) return false;
+        o.a = last(p.sA, p.sA2) + ((int64_t)p.M - 1) * p.lda + p.K - 1;
+    }
+    o.b = last(p.sB, p.sB2) + (p.b_kn ? ((int64_t)p.K - 1) * p.ldb + p.N - 1 : ((int64_t)p.N - 1) * p.ldb + p.K - 1);
+    o.c = last(p.sC, p.sC2) + ((int64_t)p.M - 1) * p.ldc + p.N - 1;
+    o.r = p.residual ? last(p.sR, p.sR2) + ((int64_t)p.M - 1) * p.ldr + p.N - 1 : -1;
+    return true;
+}
+
+tk_error_code_t tk_mi355x_gemm_probe(int device, tk_mi355x_gemm_probe_t* p) {
+    if (!p) return TK_ERROR_INVALID_ARGUMENT;
+    p->kernel = TK_GEMM_REFUSED;
+    ProbeReach reach;
+    if (!p->a || !p->b || !p->c || !probe_reach(*p, reach)) return TK_ERROR_INVALID_ARGUMENT;
+    if (p->n_a < 1 || p->n_b < 1 || p->n_c < 1 || reach.a >= p->n_a || reach.b >= p->n_b || reach.c >= p->n_c) return TK_ERROR_INVALID_ARGUMENT;
+    if (p->bias ? p->n_bias < p->N : p->n_bias != 0) return TK_ERROR_INVALID_ARGUMENT;
+    if (p->residual ? reach.r >= p->n_residual : p->n_residual != 0) return TK_ERROR_INVALID_ARGUMENT;
+    const size_t eb = p->b_f16 ? 2 : 4;
+    TkGemm g{};
+    g.M = p->M; g.N = p->N; g.K = p->K; g.lda = p->lda; g.ldb = p->ldb; g.ldc = p->ldc; g.ldr = p->ldr; g.b_kn = p->b_kn; g.act = p->act; g.alpha = p->alpha;
+    g.batch = p->batch; g.sA = p->sA; g.sB = p->sB; g.sC = p->sC; g.sR = p->sR;
+    g.batch_inner = p->batch_inner; g.sA2 = p->sA2; g.sB2 = p->sB2; g.sC2 = p->sC2; g.sR2 = p->sR2;
+    g.b_f16 = p->b_f16; g.fast = p->fast;
+    g.im_C = p->im_C; g.im_H = p->im_H; g.im_W = p->im_W; g.im_ldx = p->im_ldx; g.im_kw = p->im_kw; g.im_stride = p->im_stride; g.im_pad = p->im_pad;
+    g.im_Ho = p->im_Ho; g.im_Wo = p->im_Wo;
+    if (device < 0) { /* the launcher's answer alone: bases as the device allocator would align them */
+        g.A = (const float*)(uintptr_t)256 + p->a_offset;
+        g.B = (const float*)((uintptr_t)256 + (size_t)p->b_offset * eb);
+        p->kernel = tk_gemm_kernel_of(g);
+        return p->kernel < 0 ? TK_ERROR_INVALID_ARGUMENT : TK_SUCCESS;
+    }
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    if (!tk_nn_prepare_device()) return TK_ERROR_GPU_ROCM_ERROR;
+    float *da = nullptr, *dbias = nullptr, *dr = nullptr, *dc = nullptr;
+    uint8_t* db = nullptr;
+    const size_t ba = ((size_t)p->n_a + p->a_offset) * 4, bb = ((size_t)p->n_b + p->b_offset) * eb;
+    bool ok = hipMalloc((void**)&da, ba) == hipSuccess && hipMalloc((void**)&db, bb) == hipSuccess && hipMalloc((void**)&dc, (size_t)p->n_c * 4) == hipSuccess &&
+              (!p->bias || hipMalloc((void**)&dbias, (size_t)p->n_bias * 4) == hipSuccess) &&
+              (!p->residual || hipMalloc((void**)&dr, (size_t)p->n_residual * 4) == hipSuccess);
+    ok = ok && hipMemcpy(da + p->a_offset, p->a, (size_t)p->n_a * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(db + (size_t)p->b_offset * eb, p->b, (size_t)p->n_b * eb, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(dc, p->c, (size_t)p->n_c * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         (!p->bias || hipMemcpy(dbias, p->bias, (size_t)p->n_bias * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+         (!p->residual || hipMemcpy(dr, p->residual, (size_t)p->n_residual * 4, hipMemcpyHostToDevice) == hipSuccess);
+    tk_error_code_t rc = ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
+    if (ok) {
+        g.A = da + p->a_offset; g.B = (const float*)(db + (size_t)p->b_offset * eb); g.C = dc; g.bias = dbias; g.residual = dr;
+        p->kernel = tk_gemm_kernel_of(g);
+        if (!tk_launch_gemm(g, nullptr)) rc = TK_ERROR_INVALID_ARGUMENT;
+        else if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(p->c, dc, (size_t)p->n_c * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+    }
+    void* ptrs[] = {da, db, dbias, dr, dc};
+    for (void* q : ptrs) if (q) (void)hipFree(q);
+    return rc;
+}
+
+tk_error_code_t tk_mi355x_attention_h3_probe(int device, int B, int nh, int Tq, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, float scale, const float* q,
+                                             const float* k, const float* v, int64_t n_q, int64_t n_kv, float* out) {
+    const int64_t cap = (int64_t)1 << 28;
+    if (!q || !k || !v || !out || B < 1 || B > 4096 || nh < 1 || nh > 4096 || Tq < 1 || Tq > cap || Tk < 1 || Tk > cap || d < 1 || d > cap || q_bstride < 0 ||
+        q_bstride > cap || kv_bstride < 0 || kv_bstride > cap)
+        return TK_ERROR_INVALID_ARGUMENT;
+    /* what the launcher refuses, before any device work (it checks the same and the bases' alignment) */
+    if (d != nh * 64 || (q_bstride & 3) || (kv_bstride & 3)) return TK_ERROR_INVALID_ARGUMENT;
+    if ((B - 1) * q_bstride + (int64_t)Tq * d > n_q || (B - 1) * kv_bstride + (int64_t)Tk * d > n_kv) return TK_ERROR_INVALID_ARGUMENT;
+    if (B > 1 && (q_bstride < (int64_t)Tq * d || kv_bstride < (int64_t)Tk * d)) return TK_ERROR_INVALID_ARGUMENT; /* sequences would overlap */
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device < 0 || device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    float *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr;
+    bool ok = hipMalloc((void**)&dq, (size_t)n_q * 4) == hipSuccess && hipMalloc((void**)&dk, (size_t)n_kv * 4) == hipSuccess &&
+              hipMalloc((void**)&dv, (size_t)n_kv * 4) == hipSuccess && hipMalloc((void**)&dout, (size_t)n_q * 4) == hipSuccess;
+    ok = ok && hipMemcpy(dq, q, (size_t)n_q * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dk, k, (size_t)n_kv * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(dv, v, (size_t)n_kv * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dout, out, (size_t)n_q * 4, hipMemcpyHostToDevice) == hipSuccess;
+    tk_error_code_t rc = ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
+    if (ok) {
+        if (!tk_launch_attention_h3(dq, dk, dv, dout, B, nh, Tq, Tk, q_bstride, kv_bstride, d, scale, nullptr)) rc = TK_ERROR_INVALID_ARGUMENT;
+        else if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, dout, (size_t)n_q * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+    }
+    void* ptrs[] = {dq, dk, dv, dout};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    return rc;
+}
+
 tk_error_code_t tk_kernels_depth_to_point_cloud(const tk_depth_to_points_params_t* p, tk_hip_stream_t stream) {
     if (!p || !p->d_metric_depth_map || !p->d_point_cloud || p->width == 0 || p->height == 0 || p->fx == 0.0f || p->fy == 0.0f)
         return TK_ERROR_INVALID_ARGUMENT;

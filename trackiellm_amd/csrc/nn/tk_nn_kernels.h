@@ -19,7 +19,19 @@
 
 #include "../common/tk_gemm_desc.h"
 
-void tk_launch_gemm(const TkGemm& g, hipStream_t s);
+/* false (nothing launched): a descriptor tk_gemm_kernel_of refuses — one without output cells (M < 1 or N < 1: nothing is left stale), or an
+ * implicit-im2col form outside tk_gemm_im2col_ok().  The engines' callers drop the result because they cannot be refused: im_* is set in one
+ * place only (the detector's conv, csrc/vision/tk_vision_engine.hip), after tk_gemm_im2col_ok() held for its input and [N][K] f32 weights, with
+ * b_kn = 0 and ldb = K = k k C, C % 4 == 0; every other caller leaves im_C = 0, for which only an empty extent is refused.  A caller that builds
+ * descriptors from outside data (the test hook tk_mi355x_gemm_probe) checks the result. */
+bool tk_launch_gemm(const TkGemm& g, hipStream_t s);
+/* which kernel and instantiation tk_launch_gemm takes for g — a pure host function, and the launcher's own switch:
+ * code = family * 1000 + IM * 100 + PATH * 10 + NT (IM: implicit im2col; PATH: the operand loaders' instantiation, 0 element-wise fallbacks,
+ * 1 [N][K] and 2 [K][N] 16-byte groups; NT: 32-column accumulators per wave of the tall kernels, 0 elsewhere), or TK_GEMM_REFUSED */
+enum { TK_GEMM_F32 = 0, TK_GEMM_F32_TALL = 1, TK_GEMM_F32_BIG = 2, TK_GEMM_H3_TALL = 3, TK_GEMM_H3_BIG = 4, TK_GEMM_REFUSED = -1 };
+#define TK_GEMM_CODE(FAMILY, IM, PATH, NT) ((FAMILY) * 1000 + ((IM) ? 100 : 0) + (PATH) * 10 + (NT))
+#define TK_GEMM_FAMILY(CODE) ((CODE) / 1000)
+int tk_gemm_kernel_of(const TkGemm& g);
 /* whether a convolution can be addressed by the GEMM itself (TkGemm::im_*): channels and pitch multiples of 4, input x and the [N][K]
  * f32 weights w 16-byte aligned */
 bool tk_gemm_im2col_ok(const float* x, int C, int ldx, const float* w);

@@ -834,64 +834,75 @@ static bool tk_gemm_fast(const TkGemm& g) {
     return true;
 }
 
-void tk_launch_gemm(const TkGemm& g, hipStream_t s) {
+/* The launcher's choice, as a pure function of the descriptor (no device involved): tk_launch_gemm switches on this answer and tests assert it.
+ * TkGemm::fast: the split-f16 kernels where the operands meet the one-load-per-group conditions ([N][K] f32 weights); every other
+ * shape keeps the exact chain.  Which kernel runs depends on N and the batch layout only, NEVER on M: a row's result must not depend
+ * on how many other rows (frames, utterances) share its launch — the two split kernels evaluate an element identically (the same 16-k
+ * MFMA steps from k = 0), the exact ones differ from them, so a choice by M would make a fast handle's result depend on its batch.
+ * Refused (TK_GEMM_REFUSED, nothing is launched): no output cell (M < 1 or N < 1) or K < 0, and an implicit-im2col descriptor outside what
+ * tk_gemm_im2col_ok() admits — its kernels are the PATH 1 instantiations only: they read B as [N][K] and load A and B in 16-byte groups
+ * without a fallback.  So b_kn must be 0, the weights f32, channels, pixel pitch, K and ldb multiples of 4, both bases 16-byte aligned, and
+ * K whole ROWS of taps (a multiple of im_C * im_kw). */
+int tk_gemm_kernel_of(const TkGemm& g) {
+    if (g.M < 1 || g.N < 1 || g.K < 0) return TK_GEMM_REFUSED;
     const int nz = g.batch > 0 ? g.batch : 1;
-    const bool im = g.im_C > 0; /* validated by tk_gemm_im2col_ok(): aligned [N][K] f32 weights, C % 4 == 0, no batch */
+    const bool im = g.im_C > 0;
     const int path = tk_gemm_fast(g) ? (g.b_kn ? 2 : 1) : 0;
-#define TK_GEMM_PATHS(KERNEL, GRID, LDS)                                                                      \
-    do {                                                                                                      \
-        if (im) hipLaunchKernelGGL((KERNEL<true, 1>), GRID, dim3(256), LDS, s, g);                            \
-        else if (path == 1) hipLaunchKernelGGL((KERNEL<false, 1>), GRID, dim3(256), LDS, s, g);               \
-        else if (path == 2) hipLaunchKernelGGL((KERNEL<false, 2>), GRID, dim3(256), LDS, s, g);               \
-        else hipLaunchKernelGGL((KERNEL<false, 0>), GRID, dim3(256), LDS, s, g);                              \
-    } while (0)
-    /* TkGemm::fast: the split-f16 kernels where the operands meet the one-load-per-group conditions ([N][K] f32 weights); every other
-     * shape keeps the exact chain.  Which kernel runs depends on N and the batch layout only, NEVER on M: a row's result must not depend
-     * on how many other rows (frames, utterances) share its launch — the two split kernels evaluate an element identically (the same 16-k
-     * MFMA steps from k = 0), the exact ones differ from them, so a choice by M would make a fast handle's result depend on its batch. */
+    if (im && (path == 0 || g.b_kn || (g.im_C & 3) || (g.im_ldx & 3) || (((uintptr_t)g.A) & 15) || g.im_kw < 1 || g.K % (g.im_C * g.im_kw) || g.im_stride < 1 || g.im_Ho < 1 ||
+               g.im_Wo < 1))
+        return TK_GEMM_REFUSED;
+    const int lp = im ? 1 : path; /* the loaders' instantiation */
+    const int nt = (g.N + 31) / 32;
     const bool fast = g.fast != 0 && !g.b_kn && (im || path == 1);
-    if (fast && g.N >= 96) {
-        (void)tk_nn_prepare_device();
-        const dim3 grid((g.N + LBN - 1) / LBN, (g.M + LBM - 1) / LBM, nz);
-        if (im) hipLaunchKernelGGL((k_gemm_h3_big<true>), grid, dim3(256), H3_BIG_LDS, s, g);
-        else hipLaunchKernelGGL((k_gemm_h3_big<false>), grid, dim3(256), H3_BIG_LDS, s, g);
-        return;
+    if (fast && g.N >= 96) return TK_GEMM_CODE(TK_GEMM_H3_BIG, im, 1, 0);
+    if (fast && nz == 1 && g.batch_inner == 0) return TK_GEMM_CODE(TK_GEMM_H3_TALL, im, 1, nt); /* N < 96 */
+    if (g.M >= 256 && g.N >= 96) return TK_GEMM_CODE(TK_GEMM_F32_BIG, im, lp, 0);
+    if (g.N < 96 && g.M >= 4 * NBM && !g.b_kn && !g.b_f16 && nz == 1 && g.batch_inner == 0) /* narrow and tall: every column in one workgroup */
+        return TK_GEMM_CODE(TK_GEMM_F32_TALL, im, lp, nt);
+    return TK_GEMM_CODE(TK_GEMM_F32, im, lp, 0);
+}
+
+bool tk_launch_gemm(const TkGemm& g, hipStream_t s) {
+    const int code = tk_gemm_kernel_of(g);
+    if (code < 0) return false;
+    const int nz = g.batch > 0 ? g.batch : 1;
+    dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, nz); /* k_gemm_f32 */
+    size_t lds = 0;
+    switch (TK_GEMM_FAMILY(code)) {
+        case TK_GEMM_F32_TALL: case TK_GEMM_H3_TALL: grid = dim3(1, (g.M + NBM - 1) / NBM, 1); break;
+        case TK_GEMM_F32_BIG: case TK_GEMM_H3_BIG:
+            (void)tk_nn_prepare_device();
+            grid = dim3((g.N + LBN - 1) / LBN, (g.M + LBM - 1) / LBM, nz);
+            lds = TK_GEMM_FAMILY(code) == TK_GEMM_H3_BIG ? H3_BIG_LDS : (size_t)2 * (LBM + LBN) * LDS_LD * sizeof(float);
+            break;
+        default: break;
     }
-    if (fast && nz == 1 && g.batch_inner == 0) { /* N < 96 */
-        const dim3 grid(1, (g.M + NBM - 1) / NBM, 1);
-        const int nt = (g.N + 31) / 32;
-#define TK_TALL_H3(NTV)                                                                                       \
-    do {                                                                                                      \
-        if (im) hipLaunchKernelGGL((k_gemm_h3_tall<true, NTV>), grid, dim3(256), 0, s, g);                    \
-        else hipLaunchKernelGGL((k_gemm_h3_tall<false, NTV>), grid, dim3(256), 0, s, g);                      \
-    } while (0)
-        if (nt == 1) TK_TALL_H3(1); else if (nt == 2) TK_TALL_H3(2); else TK_TALL_H3(3);
-#undef TK_TALL_H3
-        return;
+#define TK_CASE(FAMILY, IM, PATH, NT, ...) \
+    case TK_GEMM_CODE(FAMILY, IM, PATH, NT): hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(256), lds, s, g); return true
+#define TK_CASE_PATHS(FAMILY, KERNEL)                    \
+    TK_CASE(FAMILY, 0, 0, 0, KERNEL<false, 0>);          \
+    TK_CASE(FAMILY, 0, 1, 0, KERNEL<false, 1>);          \
+    TK_CASE(FAMILY, 0, 2, 0, KERNEL<false, 2>);          \
+    TK_CASE(FAMILY, 1, 1, 0, KERNEL<true, 1>)
+#define TK_CASE_TALL(NT)                                                      \
+    TK_CASE(TK_GEMM_F32_TALL, 0, 0, NT, k_gemm_f32_tall<false, 0, NT>);       \
+    TK_CASE(TK_GEMM_F32_TALL, 0, 1, NT, k_gemm_f32_tall<false, 1, NT>);       \
+    TK_CASE(TK_GEMM_F32_TALL, 1, 1, NT, k_gemm_f32_tall<true, 1, NT>);        \
+    TK_CASE(TK_GEMM_H3_TALL, 0, 1, NT, k_gemm_h3_tall<false, NT>);            \
+    TK_CASE(TK_GEMM_H3_TALL, 1, 1, NT, k_gemm_h3_tall<true, NT>)
+    switch (code) {
+        TK_CASE_PATHS(TK_GEMM_F32, k_gemm_f32);
+        TK_CASE_PATHS(TK_GEMM_F32_BIG, k_gemm_f32_big);
+        TK_CASE_TALL(1);
+        TK_CASE_TALL(2);
+        TK_CASE_TALL(3);
+        TK_CASE(TK_GEMM_H3_BIG, 0, 1, 0, k_gemm_h3_big<false>);
+        TK_CASE(TK_GEMM_H3_BIG, 1, 1, 0, k_gemm_h3_big<true>);
+        default: return false; /* not reached: every code tk_gemm_kernel_of returns has its case */
     }
-    if (g.M >= 256 && g.N >= 96) {
-        const size_t lds = (size_t)2 * (LBM + LBN) * LDS_LD * sizeof(float);
-        (void)tk_nn_prepare_device();
-        const dim3 grid((g.N + LBN - 1) / LBN, (g.M + LBM - 1) / LBM, nz);
-        TK_GEMM_PATHS(k_gemm_f32_big, grid, lds);
-        return;
-    }
-    if (g.N < 96 && g.M >= 4 * NBM && !g.b_kn && !g.b_f16 && nz == 1 && g.batch_inner == 0) { /* narrow and tall: every column in one workgroup */
-        const dim3 grid(1, (g.M + NBM - 1) / NBM, 1);
-        const int nt = (g.N + 31) / 32;
-#define TK_TALL(NTV)                                                                                          \
-    do {                                                                                                      \
-        if (im) hipLaunchKernelGGL((k_gemm_f32_tall<true, 1, NTV>), grid, dim3(256), 0, s, g);                \
-        else if (path == 1) hipLaunchKernelGGL((k_gemm_f32_tall<false, 1, NTV>), grid, dim3(256), 0, s, g);   \
-        else hipLaunchKernelGGL((k_gemm_f32_tall<false, 0, NTV>), grid, dim3(256), 0, s, g);                  \
-    } while (0)
-        if (nt == 1) TK_TALL(1); else if (nt == 2) TK_TALL(2); else TK_TALL(3);
-#undef TK_TALL
-        return;
-    }
-    const dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, nz);
-    TK_GEMM_PATHS(k_gemm_f32, grid, 0);
-#undef TK_GEMM_PATHS
+#undef TK_CASE_TALL
+#undef TK_CASE_PATHS
+#undef TK_CASE
 }
 
 bool tk_gemm_im2col_ok(const float* x, int C, int ldx, const float* w) {
