@@ -361,6 +361,45 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_gemm_probe(int device, tk_mi355x_g
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_attention_h3_probe(int device, int B, int nh, int Tq, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, float scale,
                                                                  const float* q, const float* k, const float* v, int64_t n_q, int64_t n_kv, float* out);
 
+/* test hook for the five token-selection kernels: ONE launch of tk_launch_argmax (kind 0: k_argmax — greedy, greedy under per-row masks,
+ * stochastic through the canonical sampler), tk_launch_argmax_rows (1), tk_launch_pick_rows (2) or tk_launch_pick_rows_filtered (3) on host
+ * arrays, so that crafted logit rows (ties, -inf, signed zeros, any vocabulary size) reach each kernel alone.
+ * logits: [rows] rows of `cols` floats, `ld` floats apart (n_logits floats in all; kind 0 reads packed rows: ld == cols).
+ * kind 0: masks (optional) = n_masks bit masks of (cols + 31) / 32 words each (bit i & 31 of word i >> 5 = token i allowed), allow_row (optional)
+ *   [rows] = the row's mask index or -1; samp (optional, IN/OUT) [rows]: temperature > 0 samples the row and adds one to its counter;
+ *   tok / pos / nsteps (optional, IN/OUT) [rows]; hist (optional, IN/OUT) n_hist ints, row r's token goes to hist[nsteps[r] * hist_stride + r]
+ *   (hist needs nsteps).
+ * kinds 1-3: tok [rows] is required; temperature / seed / counter0 are the pick's generator (row r draws with counter0 + r; kind 1 ignores
+ *   them), logprob (optional, IN/OUT) [rows] asks for the log-probabilities (kind 1: must be NULL).
+ * kind 3: suppress [cols] (non-zero = never sampled), state (IN/OUT) [rows][8] as tk_launch_pick_rows_filtered documents it, beg / eot / tid0.
+ * Every IN/OUT array is uploaded before the launch and read back whole after it: what the kernel must not touch comes back as the caller
+ * left it.  Checked before anything is launched (TK_ERROR_INVALID_ARGUMENT): rows outside [1, tk_mi355x_llm_max_rows()] (kind 0) or
+ * [1, 4096]; cols < 1; ld < cols (kind 0: ld != cols); logits too short; a mask index outside [-1, n_masks); cols > 65536 with any sampled
+ * row or with kind 3 (the sampler's ids have 16 bits, the filter's LDS mask 2048 words); a temperature that is negative or not finite; hist
+ * too small for nsteps (or nsteps negative, hist_stride < rows); kind 3: beg / eot / tid0 outside the vocabulary, a live row with no allowed
+ * token or a NaN logit (the kernel would read logits[0x7fffffff]), counters in state outside [0, 2^24].
+ * device < 0: validate only — no device is touched. */
+enum { TK_MI355X_PICK_ARGMAX = 0, TK_MI355X_PICK_ARGMAX_ROWS = 1, TK_MI355X_PICK_ROWS = 2, TK_MI355X_PICK_ROWS_FILTERED = 3 };
+typedef struct {
+    int32_t kind, rows, cols, ld;
+    const float* logits;
+    int64_t n_logits;
+    const uint32_t* masks;
+    const int32_t* allow_row;
+    int32_t n_masks, hist_stride;
+    tk_mi355x_sampling_t* samp;
+    int32_t *tok, *pos, *nsteps, *hist;
+    int64_t n_hist;
+    float temperature;
+    uint32_t counter0;
+    uint64_t seed;
+    float* logprob;
+    const uint8_t* suppress;
+    int32_t* state;
+    int32_t beg, eot, tid0, reserved;
+} tk_mi355x_token_pick_probe_t;
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_token_pick_probe(int device, tk_mi355x_token_pick_probe_t* p);
+
 /* test hook for the node-by-node ONNX executor (csrc/nn/tk_onnx_exec): loads `path`, binds the n_feeds float tensors (name, data on the
  * host, rank and dims), runs the graph once and keeps host copies of the n_outputs named float values WITH THE SHAPES THE EXECUTOR
  * PRODUCED.  A refusal (unsupported op / attribute, bad shapes) comes back as an error code with the executor's text as the error

@@ -137,6 +137,23 @@ extern "C" int32_t orc_whisper_filter_pick(const float* x, int cols, const uint8
     return tok;
 }
 
+/* One unfiltered pick (k_argmax_rows / k_pick_rows of csrc/nn/tk_nn_kernels.hip): the token — first index of the maximum at temperature 0, else one
+ * draw of the canonical sampler over the 64 largest logits — and, when logprob is given, its log-probability under softmax(l / temperature) over
+ * the whole vocabulary, summed in the kernels' order (chain_sum_1024). */
+extern "C" int32_t orc_pick_row(const float* xr, int cols, float temperature, uint64_t seed, uint32_t counter, float* logprob) {
+    int best = 0;
+    for (int i = 1; i < cols; ++i) if (xr[i] > xr[best]) best = i;
+    const float mx = xr[best];
+    const bool hot = temperature > 0.0f;
+    const int tok = hot ? orc_sample_row(xr, cols, nullptr, temperature, 0, 1.0f, 0.0f, seed, counter) : best;
+    if (logprob) {
+        auto z = [&](int i) { return hot ? tk_divf(xr[i] - mx, temperature) : xr[i] - mx; };
+        const float S = chain_sum_1024(cols, [](int) { return true; }, [&](int i) { return tk_expf(z(i)); });
+        *logprob = z(tok) - tk_logf(S);
+    }
+    return tok;
+}
+
 struct CpuAudioOps {
     std::vector<std::vector<float>> bufs;
     float* alloc(size_t n) { bufs.emplace_back(n ? n : 1, 0.0f); return bufs.back().data(); }
@@ -227,34 +244,9 @@ struct CpuAudioOps {
             return;
         }
         for (int r = 0; r < rows; ++r) {
-            const float* xr = x + (int64_t)r * ld;
-            int best = 0;
-            for (int i = 1; i < cols; ++i) if (xr[i] > xr[best]) best = i;
-            out[r] = best;
-            if (!pick_on) continue;
-            const float mx = xr[best];
-            if (pick_temp > 0.0f)
-                out[r] = orc_sample_row(xr, cols, nullptr, pick_temp, 0, 1.0f, 0.0f, pick_seed, (uint32_t)(pick_step * rows + r));
-            if (!pick_lp) continue;
-            /* sum of exponentials: 1024 strided chains, each wave of 64 chains joined by the xor butterfly (32 .. 1), then waves 0 .. 15 in order */
-            float chain[1024];
-            for (int t = 0; t < 1024; ++t) {
-                float s = 0.0f;
-                for (int i = t; i < cols; i += 1024) s = s + tk_expf(pick_temp > 0.0f ? tk_divf(xr[i] - mx, pick_temp) : xr[i] - mx);
-                chain[t] = s;
-            }
-            float S = 0.0f;
-            for (int w = 0; w < 16; ++w) {
-                float a[64], nx[64];
-                for (int j = 0; j < 64; ++j) a[j] = chain[w * 64 + j];
-                for (int sft = 32; sft >= 1; sft >>= 1) {
-                    for (int j = 0; j < 64; ++j) nx[j] = a[j] + a[j ^ sft];
-                    for (int j = 0; j < 64; ++j) a[j] = nx[j];
-                }
-                S = w == 0 ? a[0] : S + a[0];
-            }
-            const float z = pick_temp > 0.0f ? tk_divf(xr[out[r]] - mx, pick_temp) : xr[out[r]] - mx;
-            pick_lp[(int64_t)pick_step * rows + r] = z - tk_logf(S);
+            float lp = 0.0f;
+            out[r] = orc_pick_row(x + (int64_t)r * ld, cols, pick_on ? pick_temp : 0.0f, pick_seed, (uint32_t)(pick_step * rows + r), pick_on && pick_lp ? &lp : nullptr);
+            if (pick_on && pick_lp) pick_lp[(int64_t)pick_step * rows + r] = lp;
         }
         if (pick_on) pick_step++;
     }

@@ -513,3 +513,14 @@ def whisper_filter_pick(logits, suppress, state, beg, eot, tid0=50, temperature=
     L.orc_whisper_filter_pick.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]
     tok = L.orc_whisper_filter_pick(ptr(logits), len(logits), ptr(suppress), ptr(state), beg, eot, tid0, temperature, seed, counter, C.byref(lp))
     return int(tok), float(lp.value)
+
+
+def pick_row(logits, temperature=0.0, seed=0, counter=0, want_logprob=True):
+    """one unfiltered ASR pick (orc_pick_row: k_argmax_rows / k_pick_rows): logits [cols] -> (token, logprob as float32 or None)"""
+    logits = np.ascontiguousarray(logits, np.float32)
+    lp = C.c_float(0)
+    L = lib()
+    L.orc_pick_row.restype = C.c_int32
+    L.orc_pick_row.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]
+    tok = L.orc_pick_row(ptr(logits), logits.size, temperature, seed, counter, C.byref(lp) if want_logprob else None)
+    return int(tok), (np.float32(lp.value) if want_logprob else None)

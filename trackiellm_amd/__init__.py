@@ -14,5 +14,6 @@ from .vision import ObjectDetector, VisionPipeline, classify_attributes, preproc
 from .vision import DepthEstimator, depth_onnx_probe, fuse_data, fusion_reset, fusion_raw_distance  # noqa: F401,E402
 from .vision import onnx_run  # noqa: F401,E402
 from .nn import GemmProbe, gemm_probe, gemm_code, attention_h3_probe, GEMM_F32, GEMM_F32_TALL, GEMM_F32_BIG, GEMM_H3_TALL, GEMM_H3_BIG  # noqa: F401,E402
+from .pick import TokenPickProbe, token_pick_probe, sampling_rows, SAMPLING_DTYPE, PICK_ARGMAX, PICK_ARGMAX_ROWS, PICK_ROWS, PICK_ROWS_FILTERED  # noqa: F401,E402
 from .audio import Asr, Vad, WhisperHP, WHISPER_TINY_EN, AudioPipeline  # noqa: F401,E402
 from .cortex import Cortex, RocmDispatcher, PreprocessParams, DepthPostParams, DepthToPointsParams, Float3  # noqa: F401,E402

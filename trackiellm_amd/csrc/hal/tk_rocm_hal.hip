@@ -3,6 +3,7 @@
  * (src/gpu/rocm/tk_rocm_dispatch.hpp:83-217, src/gpu/rocm/tk_rocm_kernels.hpp:96,133,176).
  */
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdlib.h>
 
 #include <vector>
@@ -14,6 +15,7 @@
 #include "tk/tk_rocm_hal.h"
 #include "../nn/tk_gemm_tiled.h"
 #include "../nn/tk_nn_kernels.h"
+#include "../llm/tk_llm_kernels.h"
 
 struct tk_gpu_buffer_s {
     void* dptr;
@@ -281,6 +283,102 @@ tk_error_code_t tk_mi355x_attention_h3_probe(int device, int B, int nh, int Tq, 
     }
     void* ptrs[] = {dq, dk, dv, dout};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    return rc;
+}
+
+/* what a token-pick launch may be handed (tk_mi355x_ext.h states the rules); false: refuse */
+static bool pick_probe_ok(const tk_mi355x_token_pick_probe_t& p) {
+    static_assert(sizeof(tk_mi355x_sampling_t) == sizeof(TkSampleRow), "the public sampling state is the kernels' TkSampleRow");
+    const bool llm = p.kind == TK_MI355X_PICK_ARGMAX;
+    if (p.kind < TK_MI355X_PICK_ARGMAX || p.kind > TK_MI355X_PICK_ROWS_FILTERED || !p.logits) return false;
+    if (p.rows < 1 || p.rows > (llm ? TK_MAX_ROWS : 4096) || p.cols < 1 || p.cols > (1 << 24) || p.ld < p.cols || p.ld > (1 << 24) || (llm && p.ld != p.cols)) return false;
+    if (p.n_logits < (int64_t)(p.rows - 1) * p.ld + p.cols) return false;
+    const bool wide = p.cols > 65536;
+    if (llm) {
+        if (p.n_masks < 0 || (p.masks == nullptr) != (p.n_masks == 0)) return false;
+        if (p.allow_row)
+            for (int r = 0; r < p.rows; ++r)
+                if (p.allow_row[r] < -1 || p.allow_row[r] >= p.n_masks) return false;
+        if (p.samp)
+            for (int r = 0; r < p.rows; ++r) {
+                const float t = p.samp[r].temperature;
+                if (!isfinite(t) || t < 0.0f || (t > 0.0f && wide)) return false;
+            }
+        if (p.hist) {
+            if (!p.nsteps || p.hist_stride < p.rows || p.n_hist < 1) return false;
+            for (int r = 0; r < p.rows; ++r)
+                if (p.nsteps[r] < 0 || (int64_t)p.nsteps[r] * p.hist_stride + r >= p.n_hist) return false;
+        }
+        return true;
+    }
+    if (!p.tok || !isfinite(p.temperature) || p.temperature < 0.0f) return false;
+    if (p.kind == TK_MI355X_PICK_ARGMAX_ROWS) return p.logprob == nullptr;
+    if (p.kind == TK_MI355X_PICK_ROWS) return !(wide && p.temperature > 0.0f);
+    if (wide || !p.suppress || !p.state || p.beg < 0 || p.beg > p.cols || p.eot < 0 || p.eot >= p.cols || p.tid0 < -1 || p.tid0 > p.cols) return false;
+    for (int r = 0; r < p.rows; ++r) {
+        const int32_t* st = p.state + (int64_t)r * TK_WH_STATE_INTS;
+        const int32_t counts[4] = {st[0], st[4], st[5], st[7]};
+        for (int32_t v : counts) if (v < 0 || v > (1 << 24)) return false;
+        if (st[6] != 0) continue; /* stands still: reads no logit */
+        /* the kernel's allowed set A0: empty, its pick stays 0x7fffffff and logits[pick] is read; so it does when every allowed logit is a NaN */
+        const int n_tok = st[0], last_ts = n_tok > 0 ? st[1] : 0, prev_ts = n_tok < 2 ? 1 : st[2];
+        const int ts_lo = st[3] ? p.beg + st[4] / 2 : p.beg, ts_hi = n_tok == 0 && p.tid0 >= 0 ? p.beg + p.tid0 : 0x7fffffff;
+        bool any = false;
+        for (int i = 0; i < p.cols; ++i) {
+            const float v = p.logits[(int64_t)r * p.ld + i];
+            if (v != v) return false;
+            bool ok = p.suppress[i] == 0;
+            if (i >= p.beg) ok = ok && i >= ts_lo && i <= ts_hi && !(last_ts && prev_ts);
+            if (last_ts && !prev_ts && i < p.eot) ok = false;
+            any = any || ok;
+        }
+        if (!any) return false;
+    }
+    return true;
+}
+
+tk_error_code_t tk_mi355x_token_pick_probe(int device, tk_mi355x_token_pick_probe_t* p) {
+    if (!p || !pick_probe_ok(*p)) return TK_ERROR_INVALID_ARGUMENT;
+    if (device < 0) return TK_SUCCESS;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    const size_t rows = (size_t)p->rows, mask_words = (size_t)p->n_masks * (size_t)((p->cols + 31) / 32);
+    /* host array, bytes, device copy, read back after the launch */
+    struct Buf { const void* host; size_t bytes; void* dev; bool out; };
+    Buf b[] = {{p->logits, (size_t)p->n_logits * 4, nullptr, false}, {p->masks, mask_words * 4, nullptr, false}, {p->allow_row, rows * 4, nullptr, false},
+               {p->samp, rows * sizeof(TkSampleRow), nullptr, true}, {p->tok, rows * 4, nullptr, true}, {p->pos, rows * 4, nullptr, true},
+               {p->nsteps, rows * 4, nullptr, true}, {p->hist, (size_t)p->n_hist * 4, nullptr, true}, {p->logprob, rows * 4, nullptr, true},
+               {p->suppress, (size_t)p->cols, nullptr, false}, {p->state, rows * TK_WH_STATE_INTS * 4, nullptr, true}};
+    enum { LOGITS, MASKS, ALLOW_ROW, SAMP, TOK, POS, NSTEPS, HIST, LOGPROB, SUPPRESS, STATE };
+    const bool llm = p->kind == TK_MI355X_PICK_ARGMAX;
+    bool ok = true;
+    for (Buf& q : b) {
+        const int which = (int)(&q - b);
+        const bool used = q.host && (llm ? which <= HIST : which == LOGITS || which == TOK || which == LOGPROB || (p->kind == TK_MI355X_PICK_ROWS_FILTERED && which >= SUPPRESS));
+        if (!used) { q.host = nullptr; continue; }
+        ok = ok && hipMalloc(&q.dev, q.bytes) == hipSuccess && hipMemcpy(q.dev, q.host, q.bytes, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    tk_error_code_t rc = ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
+    if (ok) {
+        const float* x = (const float*)b[LOGITS].dev;
+        const TkPick pk{p->temperature, p->seed, p->counter0, (float*)b[LOGPROB].dev};
+        if (llm)
+            tk_launch_argmax(x, p->cols, p->rows, (const uint32_t*)b[MASKS].dev, (const int32_t*)b[ALLOW_ROW].dev, (TkSampleRow*)b[SAMP].dev, (int32_t*)b[TOK].dev,
+                             (int32_t*)b[POS].dev, (int32_t*)b[NSTEPS].dev, (int32_t*)b[HIST].dev, p->hist_stride, nullptr);
+        else if (p->kind == TK_MI355X_PICK_ARGMAX_ROWS) tk_launch_argmax_rows(x, p->rows, p->cols, p->ld, (int32_t*)b[TOK].dev, nullptr);
+        else if (p->kind == TK_MI355X_PICK_ROWS) tk_launch_pick_rows(x, p->rows, p->cols, p->ld, (int32_t*)b[TOK].dev, pk, nullptr);
+        else {
+            const TkWhFilter f{(const uint8_t*)b[SUPPRESS].dev, (int32_t*)b[STATE].dev, p->beg, p->eot, p->tid0};
+            tk_launch_pick_rows_filtered(x, p->rows, p->cols, p->ld, (int32_t*)b[TOK].dev, pk, f, nullptr);
+        }
+        if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+        else
+            for (Buf& q : b)
+                if (q.host && q.out && hipMemcpy(const_cast<void*>(q.host), q.dev, q.bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+    }
+    for (Buf& q : b) if (q.dev) (void)hipFree(q.dev);
     return rc;
 }
 

@@ -1241,7 +1241,7 @@ __global__ __launch_bounds__(1024) void k_argmax_rows(const float* x, int cols, 
     int idx = 0x7fffffff;
     for (int i = t; i < cols; i += 1024) {
         const float v = xr[i];
-        if (v > best) { best = v; idx = i; }
+        if (v > best || idx == 0x7fffffff) { best = v; idx = i; } /* k_argmax's rule: a chain's first element stands even at -inf, so a row with nothing above -inf answers index 0 */
     }
     for (int s = 32; s >= 1; s >>= 1) {
         const float ov = __shfl_xor(best, s, 64);
@@ -1274,7 +1274,7 @@ __global__ __launch_bounds__(1024) void k_pick_rows(const float* x, int cols, in
     int idx = 0x7fffffff;
     for (int i = t; i < cols; i += 1024) {
         const float v = xr[i];
-        if (v > best) { best = v; idx = i; }
+        if (v > best || idx == 0x7fffffff) { best = v; idx = i; } /* k_argmax's rule: a chain's first element stands even at -inf, so a row with nothing above -inf answers index 0 */
     }
     for (int s = 32; s >= 1; s >>= 1) {
         const float ov = __shfl_xor(best, s, 64);

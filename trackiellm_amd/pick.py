@@ -1,0 +1,68 @@
+"""The token-selection kernels one launch at a time: the test hook tk_mi355x_token_pick_probe."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, lib
+
+PICK_ARGMAX, PICK_ARGMAX_ROWS, PICK_ROWS, PICK_ROWS_FILTERED = 0, 1, 2, 3
+WH_STATE_INTS = 8
+# tk_mi355x_sampling_t as a NumPy record (the kernels' TkSampleRow)
+SAMPLING_DTYPE = np.dtype([("temperature", "<f4"), ("top_p", "<f4"), ("min_p", "<f4"), ("top_k", "<i4"), ("seed", "<u8"), ("counter", "<u4"),
+                           ("reserved", "<u4")])
+
+
+class TokenPickProbe(C.Structure):  # tk_mi355x_token_pick_probe_t
+    _fields_ = [(n, C.c_int32) for n in ("kind", "rows", "cols", "ld")] + [("logits", C.c_void_p), ("n_logits", C.c_int64), ("masks", C.c_void_p),
+                ("allow_row", C.c_void_p), ("n_masks", C.c_int32), ("hist_stride", C.c_int32), ("samp", C.c_void_p), ("tok", C.c_void_p),
+                ("pos", C.c_void_p), ("nsteps", C.c_void_p), ("hist", C.c_void_p), ("n_hist", C.c_int64), ("temperature", C.c_float),
+                ("counter0", C.c_uint32), ("seed", C.c_uint64), ("logprob", C.c_void_p), ("suppress", C.c_void_p), ("state", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("beg", "eot", "tid0", "reserved")]
+
+
+def sampling_rows(rows):
+    """[(temperature, top_k, top_p, min_p, seed, counter)] -> a SAMPLING_DTYPE array"""
+    a = np.zeros(len(rows), SAMPLING_DTYPE)
+    for r, (temp, top_k, top_p, min_p, seed, counter) in enumerate(rows):
+        a[r] = (temp, top_p, min_p, top_k, seed, counter, 0)
+    return a
+
+
+def token_pick_probe(kind, logits, rows, cols, ld=None, masks=None, allow_row=None, samp=None, tok=None, pos=None, nsteps=None, hist=None, hist_stride=0,
+                     temperature=0.0, seed=0, counter0=0, logprob=None, suppress=None, state=None, beg=0, eot=0, tid0=-1, n_masks=None, device=0):
+    """ONE launch of a token-selection kernel (tk_mi355x_token_pick_probe).  logits: float32, rows `ld` apart.  masks: uint32 [n_masks][(cols + 31) / 32].
+    samp (SAMPLING_DTYPE), tok, pos, nsteps, hist (int32), logprob (float32) and state (int32 [rows][8]) are IN/OUT: COPIES are launched on and returned
+    in a dict under the same names (None stays None: a NULL pointer).  device < 0: validation only."""
+    def own(x, dtype):
+        return None if x is None else np.array(x, dtype=dtype, order="C", copy=True)
+
+    def addr(x):
+        return None if x is None else x.ctypes.data
+
+    logits = np.ascontiguousarray(logits, np.float32).reshape(-1)
+    masks = None if masks is None else np.ascontiguousarray(masks, np.uint32)
+    allow_row = None if allow_row is None else np.ascontiguousarray(allow_row, np.int32)
+    suppress = None if suppress is None else np.ascontiguousarray(suppress, np.uint8)
+    io = dict(samp=own(samp, SAMPLING_DTYPE), tok=own(tok, np.int32), pos=own(pos, np.int32), nsteps=own(nsteps, np.int32), hist=own(hist, np.int32),
+              logprob=own(logprob, np.float32), state=own(state, np.int32))
+    words = (cols + 31) // 32
+    if masks is not None and (n_masks is None) and masks.size % max(words, 1):
+        raise ValueError("token_pick_probe: masks must hold whole masks of (cols + 31) / 32 words")
+    for name, per_row in (("samp", 1), ("tok", 1), ("pos", 1), ("nsteps", 1), ("logprob", 1), ("state", WH_STATE_INTS)):
+        if rows >= 1 and io[name] is not None and io[name].size != rows * per_row:
+            raise ValueError("token_pick_probe: %s must have %d entries" % (name, rows * per_row))
+    if (rows >= 1 and allow_row is not None and allow_row.size != rows) or (suppress is not None and suppress.size != cols):
+        raise ValueError("token_pick_probe: allow_row must have `rows` entries and suppress `cols`")
+    p = TokenPickProbe()
+    p.kind, p.rows, p.cols, p.ld = kind, rows, cols, cols if ld is None else ld
+    p.logits, p.n_logits = logits.ctypes.data, logits.size
+    p.masks, p.allow_row = addr(masks), addr(allow_row)
+    p.n_masks = (0 if masks is None else masks.size // words) if n_masks is None else n_masks
+    p.hist_stride, p.n_hist = hist_stride, 0 if io["hist"] is None else io["hist"].size
+    p.samp, p.tok, p.pos, p.nsteps, p.hist = addr(io["samp"]), addr(io["tok"]), addr(io["pos"]), addr(io["nsteps"]), addr(io["hist"])
+    p.temperature, p.counter0, p.seed = temperature, counter0, seed
+    p.logprob, p.suppress, p.state = addr(io["logprob"]), addr(suppress), addr(io["state"])
+    p.beg, p.eot, p.tid0 = beg, eot, tid0
+    lib().tk_mi355x_token_pick_probe.argtypes = [C.c_int, C.POINTER(TokenPickProbe)]
+    check(lib().tk_mi355x_token_pick_probe(device, C.byref(p)))
+    return io
