@@ -400,6 +400,87 @@ typedef struct {
 } tk_mi355x_token_pick_probe_t;
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_token_pick_probe(int device, tk_mi355x_token_pick_probe_t* p);
 
+/* test hook for the perception streams' row and layout kernels (csrc/nn/tk_nn_kernels): ONE launch of one launcher on host arrays, so that
+ * shapes no network sends (pitches wider than the extent, odd sizes around the kernels' 256 / 2048 thresholds, unaligned bases, rows that are
+ * no multiple of 16) reach each kernel alone.  The contract is the GEMM probe's: a / b / c / idx / pos_idx are inputs of n_a / n_b / n_c /
+ * n_idx / n_idx ELEMENTS; y (n_y floats) and img (n_img floats, optional) are IN/OUT: uploaded before the launch, read back whole after it, so
+ * every float the kernel must not touch comes back as the caller left it.  a is placed a_offset floats and y y_offset floats into their
+ * device allocations (0..64): the only way to a base that is not 16-byte aligned.  Every address the launch can reach is computed from the
+ * geometry and checked against the counts first; anything outside, an extent < 1, a pitch below the extent, a stride < 1, a negative pad, a
+ * window wider than the padded input, or anything the launcher itself refuses is TK_ERROR_INVALID_ARGUMENT with nothing launched.
+ *   op                 geometry                                   arrays
+ *   CONV_STEM          B H W C ldx | N k stride pad ldy act       a = x [B H W][ldx], b = w [N][k k C], c = bias [N] or NULL, y [B Ho Wo][ldy]
+ *   IM2COL             B H W C ldx | k (square) stride pad        a = x, y = col [B Ho Wo][k k C] packed
+ *   IM2COL1D           B H(=T) C ldx | k stride pad               a = x [B T][ldx], y = col [B To][k C] packed
+ *   MAXPOOL5           B H W C ldx ldy                            a = x, y [B H W][ldy]
+ *   UPSAMPLE2X         B H W C ldx ldy                            a = x, y [B 2H 2W][ldy]
+ *   COPY_COLS          rows C ldx ldy                             a = x [rows][ldx], y [rows][ldy]
+ *   LAYERNORM          rows C(=D) eps                             a = x [rows][D], b = w [D], c = bias [D], y [rows][D], img (optional)
+ *                                                                 [ceil(rows / 16) 16][D]: the tiled GEMM's operand image, D % 16 == 0 only
+ *   SOFTMAX_ROWS       rows C(=cols) ldy(=ld)                     y [rows][ld], in place (a unused)
+ *   ADD_ROWS           rows C(=D) add_rows                        y = x [rows][D] in place, a = add [add_rows][D]
+ *   EMBED_ROWS         rows C(=D) table_rows pos_rows             a = table [table_rows][D], b = pos [pos_rows][D], idx / pos_idx [rows], y [rows][D];
+ *                                                                 every index is checked against table_rows / pos_rows
+ *   ATTEND1            B H(=Tk) C(=d) N(=nh) q_bstride kv_bstride a = q [B] rows q_bstride apart, b = k and c = v [B] x [Tk][d], kv_bstride apart, y = out
+ *                                                                 like q, img (optional) [ceil(B / 16) 16][d]; with B > 1 q_bstride >= d
+ * kernel (out) is the launcher's own choice: ATTEND1 0, or -1 when the launcher refuses (d / nh no multiple of 16 or above 256, more than 60 KiB
+ * of LDS: d / nh = 64 admits Tk = 3008 and refuses 3009, 80 is refused; a batch stride that is no multiple of 4); SOFTMAX_ROWS 0 the three-pass kernel, 1 one block per row out of registers, 2 one wave per row;
+ * IM2COL 0 element-wise, 1 16-byte groups; CONV_STEM 0, or -1 when the launcher refuses (N != 16, C != 3, k != 3, ldy % 4, y off 16 bytes);
+ * every other op 0.  device < 0: validate and report `kernel` only, no device is touched (bases then as the device allocator aligns them). */
+enum {
+    TK_MI355X_ROW_CONV_STEM = 0, TK_MI355X_ROW_IM2COL = 1, TK_MI355X_ROW_IM2COL1D = 2, TK_MI355X_ROW_MAXPOOL5 = 3, TK_MI355X_ROW_UPSAMPLE2X = 4,
+    TK_MI355X_ROW_COPY_COLS = 5, TK_MI355X_ROW_LAYERNORM = 6, TK_MI355X_ROW_SOFTMAX_ROWS = 7, TK_MI355X_ROW_ADD_ROWS = 8, TK_MI355X_ROW_EMBED_ROWS = 9,
+    TK_MI355X_ROW_ATTEND1 = 10
+};
+typedef struct {
+    int32_t op;
+    int32_t B, H, W, C, ldx, ldy;   /* images */
+    int32_t rows;                   /* row ops */
+    int32_t N, k, stride, pad, act; /* conv_stem / im2col / im2col1d; act: 0 none, 1 SiLU */
+    int32_t add_rows, table_rows, pos_rows;
+    float eps;
+    int32_t a_offset, y_offset;
+    int32_t kernel;                 /* out */
+    const float *a, *b, *c;
+    const int32_t *idx, *pos_idx;
+    float *y, *img;
+    int64_t n_a, n_b, n_c, n_idx, n_y, n_img;
+    int64_t q_bstride, kv_bstride;  /* attend1 */
+} tk_mi355x_nn_row_probe_t;
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_nn_row_probe(int device, tk_mi355x_nn_row_probe_t* p);
+
+/* test hook for the detector's post-processing kernels (csrc/vision/tk_vision_engine.hip), ONE decode + rank + mask + scan sequence on host arrays:
+ * kind 0: three raw head maps head[i] = [B][H_i W_i][ld[i]] floats (n_head[i] in all) with ld[i] >= 64 + nc and H_i = in_h / s, W_i = in_w / s
+ *         for s = 8, 16, 32 (in_w, in_h multiples of 32; n_anchors must be the three grids' total): k_yolo_decode, then tk_launch_yolo_post;
+ * kind 1: out = [B][4 + nc][n_anchors] decoded boxes and class probabilities (n_out floats), any n_anchors >= 1: k_yolo_decode_out per frame,
+ *         then the same post launches.
+ * IN/OUT, each uploaded before the launches and read back whole after them, so stale content of an earlier call can be planted and whatever the
+ * kernels must not touch comes back as it was: cand [B][n_anchors] records, order [B][2048] anchor ids by (score desc, anchor asc), n_cand [B],
+ * mask [B][2048][32] 64-bit words (optional: NULL leaves the device matrix filled with 0xFF bytes), kept [B][500] records, n_kept [B].  The
+ * counts must be exactly those sizes.  A record is tk_mi355x_box_t (cls = -1 in cand: not a candidate).
+ * TK_ERROR_INVALID_ARGUMENT with nothing launched: B outside [1, 256], nc outside [1, 4096], n_anchors outside [1, 2^20], a pitch below
+ * 64 + nc, an array too small for its geometry or of the wrong count.  device < 0: validate only. */
+typedef struct { float x1, y1, x2, y2, score; int32_t cls, anchor; } tk_mi355x_box_t;
+typedef struct {
+    int32_t kind, B, nc, n_anchors;
+    int32_t in_w, in_h;
+    int32_t ld[3];
+    int32_t reserved;
+    float conf, iou;
+    const float* head[3];
+    int64_t n_head[3];
+    const float* out;
+    int64_t n_out;
+    tk_mi355x_box_t* cand;
+    int32_t* order;
+    int32_t* n_cand;
+    uint64_t* mask;
+    tk_mi355x_box_t* kept;
+    int32_t* n_kept;
+    int64_t cand_count, order_count, n_cand_count, mask_count, kept_count, n_kept_count;
+} tk_mi355x_detector_post_probe_t;
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_detector_post_probe(int device, tk_mi355x_detector_post_probe_t* p);
+
 /* test hook for the node-by-node ONNX executor (csrc/nn/tk_onnx_exec): loads `path`, binds the n_feeds float tensors (name, data on the
  * host, rank and dims), runs the graph once and keeps host copies of the n_outputs named float values WITH THE SHAPES THE EXECUTOR
  * PRODUCED.  A refusal (unsupported op / attribute, bad shapes) comes back as an error code with the executor's text as the error

@@ -276,6 +276,47 @@ struct CpuAudioOps {
     }
 };
 
+/* the row steps of the Whisper graph alone (CpuAudioOps above), on plain arrays */
+extern "C" void orc_layernorm(const float* x, int rows, int D, const float* w, const float* b, float* y) { CpuAudioOps().layernorm(x, rows, D, w, b, y); }
+extern "C" void orc_softmax_rows(float* x, int rows, int cols, int ld) { CpuAudioOps().softmax_rows(x, rows, cols, ld); }
+/* tests only: softmax_rows with the sum taken in the REVERSED order — each of the 256 strided partials from its last element down, the butterfly's
+ * and the waves' operands swapped end for end — to show that the canonical order is pinned by the bits */
+extern "C" void orc_softmax_rows_reversed_sum(float* x, int rows, int cols, int ld) {
+    for (int r = 0; r < rows; ++r) {
+        float* xr = x + (int64_t)r * ld;
+        float m = -INFINITY;
+        for (int i = 0; i < cols; ++i) m = tk_fmaxf(m, xr[i]);
+        for (int i = 0; i < cols; ++i) xr[i] = tk_expf(xr[i] - m);
+        float part[256];
+        for (int t = 0; t < 256; ++t) {
+            float s = 0.0f;
+            const int last = cols - 1 - ((cols - 1 - t) % 256 + 256) % 256; /* the largest i < cols with i % 256 == t (below t: none) */
+            for (int i = last; i >= t; i -= 256) s = s + xr[i];
+            part[255 - t] = s;
+        }
+        const float tot = sum256(part);
+        for (int i = 0; i < cols; ++i) xr[i] = tk_divf(xr[i], tot);
+    }
+}
+extern "C" void orc_im2col1d(const float* x, int B, int T, int C, int ldx, int kw, int stride, int pad, float* col) {
+    CpuAudioOps().im2col1d(x, B, T, C, ldx, kw, stride, pad, col);
+}
+extern "C" void orc_add_rows(float* x, const float* add, int rows, int D, int add_rows) { CpuAudioOps().add_rows(x, add, rows, D, add_rows); }
+extern "C" void orc_embed_rows(const float* table, const float* pos, const int32_t* idx, const int32_t* pos_idx, int rows, int D, float* out) {
+    CpuAudioOps().embed_rows(table, pos, idx, pos_idx, rows, D, out);
+}
+extern "C" float orc_layernorm_eps() { return TK_WH_LN_EPS; }
+/* the attention of tk_whisper_graph.h at ONE query row per sequence, in its three-launch form (scores GEMM, softmax_rows, value GEMM): what the
+ * decoder-step kernel must equal.  q / out [B] rows q_bstride apart, k / v [B] x [Tk] rows of pitch d, kv_bstride apart */
+extern "C" void orc_attend1(const float* q, const float* k, const float* v, float* out, int B, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, int nh) {
+    const TkWhisperHP hp{};
+    const TkWhManifest man{};
+    CpuAudioOps ops;
+    TkWhisperGraph<CpuAudioOps> g{hp, man, nullptr};
+    std::vector<float> scores((size_t)B * nh * g.score_pitch(Tk));
+    g.attention(ops, q, k, v, out, B, 1, Tk, q_bstride, kv_bstride, d, nh, scores.data());
+}
+
 struct orc_whisper {
     TkWhisperHP hp;
     TkWhManifest man;

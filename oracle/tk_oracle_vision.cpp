@@ -172,25 +172,16 @@ void orc_yolo_forward(orc_yolo* m, int B, int H, int W, const float* in, float* 
         }
 }
 
-/* raw: [anchors][64+nc] of ONE frame -> survivors; returns count; boxes5 = x1,y1,x2,y2,score (input-tensor pixels) */
-int orc_yolo_post(const float* raw, int H, int W, int nc, float conf, float iou, float* boxes5, int32_t* cls, int32_t* anchors, int cap) {
-    const int no = 64 + nc;
-    std::vector<tk_yolo_cand_t> cand;
-    int a = 0;
-    const int strides[3] = {8, 16, 32};
-    for (int i = 0; i < 3; ++i) {
-        const int gh = H / strides[i], gw = W / strides[i];
-        for (int l = 0; l < gh * gw; ++l, ++a) {
-            tk_yolo_cand_t c;
-            tk_yolo_decode_anchor(raw + (size_t)a * no, nc, (float)(l % gw) + 0.5f, (float)(l / gw) + 0.5f, (float)strides[i], &c);
-            c.anchor = a;
-            if (c.score > conf) cand.push_back(c);
-        }
-    }
+/* the candidates of one frame -> ranked (score desc, anchor asc), capped, greedy class-aware NMS; order (optional) [TK_YOLO_MAX_CAND] takes the
+ * ranked anchor ids and *n_cand their count */
+static int yolo_rank_and_suppress(std::vector<tk_yolo_cand_t>& cand, float iou, float* boxes5, int32_t* cls, int32_t* anchors, int cap, int32_t* order,
+                                  int32_t* n_cand) {
     std::stable_sort(cand.begin(), cand.end(), [](const tk_yolo_cand_t& p, const tk_yolo_cand_t& q) {
         return p.score > q.score || (p.score == q.score && p.anchor < q.anchor);
     });
     if ((int)cand.size() > TK_YOLO_MAX_CAND) cand.resize(TK_YOLO_MAX_CAND);
+    if (order) for (size_t i = 0; i < cand.size(); ++i) order[i] = cand[i].anchor;
+    if (n_cand) *n_cand = (int32_t)cand.size();
     std::vector<tk_yolo_cand_t> kept;
     for (const auto& c : cand) {
         bool drop = false;
@@ -210,9 +201,35 @@ int orc_yolo_post(const float* raw, int H, int W, int nc, float conf, float iou,
     return (int)kept.size();
 }
 
+/* raw: [anchors][ld] of ONE frame (ld >= 64 + nc) -> survivors; returns count; boxes5 = x1,y1,x2,y2,score (input-tensor pixels).  decoded (optional)
+ * [anchors] takes every anchor's decoded record as the detector keeps it (cls = -1: not a candidate); order / n_cand (optional) the ranked list */
+int orc_yolo_post_ranked(const float* raw, int ld, int H, int W, int nc, float conf, float iou, float* boxes5, int32_t* cls, int32_t* anchors, int cap,
+                         tk_yolo_cand_t* decoded, int32_t* order, int32_t* n_cand) {
+    const int no = ld;
+    std::vector<tk_yolo_cand_t> cand;
+    int a = 0;
+    const int strides[3] = {8, 16, 32};
+    for (int i = 0; i < 3; ++i) {
+        const int gh = H / strides[i], gw = W / strides[i];
+        for (int l = 0; l < gh * gw; ++l, ++a) {
+            tk_yolo_cand_t c;
+            tk_yolo_decode_anchor(raw + (size_t)a * no, nc, (float)(l % gw) + 0.5f, (float)(l / gw) + 0.5f, (float)strides[i], &c);
+            c.anchor = a;
+            if (c.score > conf) cand.push_back(c);
+            if (decoded) { decoded[a] = c; if (!(c.score > conf)) decoded[a].cls = -1; }
+        }
+    }
+    return yolo_rank_and_suppress(cand, iou, boxes5, cls, anchors, cap, order, n_cand);
+}
+
+int orc_yolo_post(const float* raw, int H, int W, int nc, float conf, float iou, float* boxes5, int32_t* cls, int32_t* anchors, int cap) {
+    return orc_yolo_post_ranked(raw, 64 + nc, H, W, nc, conf, iou, boxes5, cls, anchors, cap, nullptr, nullptr, nullptr);
+}
+
 /* out: [4 + nc][anchors] of ONE frame — a YOLO-class graph's own decoded output (Ultralytics export: box centre / size in input pixels, class
  * probabilities) -> survivors of the same threshold / ordering / class-aware NMS as orc_yolo_post; returns count */
-int orc_yolo_post_out(const float* out, int nc, int n_anchors, float conf, float iou, float* boxes5, int32_t* cls, int32_t* anchors, int cap) {
+int orc_yolo_post_out_ranked(const float* out, int nc, int n_anchors, float conf, float iou, float* boxes5, int32_t* cls, int32_t* anchors, int cap,
+                             tk_yolo_cand_t* decoded, int32_t* order, int32_t* n_cand) {
     std::vector<tk_yolo_cand_t> cand;
     for (int a = 0; a < n_anchors; ++a) {
         tk_yolo_cand_t c;
@@ -225,28 +242,29 @@ int orc_yolo_post_out(const float* out, int nc, int n_anchors, float conf, float
         }
         c.anchor = a;
         if (c.score > conf) cand.push_back(c);
+        if (decoded) { decoded[a] = c; if (!(c.score > conf)) decoded[a].cls = -1; }
     }
-    std::stable_sort(cand.begin(), cand.end(), [](const tk_yolo_cand_t& p, const tk_yolo_cand_t& q) {
-        return p.score > q.score || (p.score == q.score && p.anchor < q.anchor);
-    });
-    if ((int)cand.size() > TK_YOLO_MAX_CAND) cand.resize(TK_YOLO_MAX_CAND);
-    std::vector<tk_yolo_cand_t> kept;
-    for (const auto& c : cand) {
-        bool drop = false;
-        for (const auto& k : kept)
-            if (k.cls == c.cls && tk_yolo_iou(&k, &c) > iou) { drop = true; break; }
-        if (!drop) {
-            kept.push_back(c);
-            if ((int)kept.size() >= TK_OBJECT_DETECTOR_MAX_DETECTIONS) break;
-        }
-    }
-    for (int i = 0; i < (int)kept.size() && i < cap; ++i) {
-        boxes5[5 * i] = kept[i].x1; boxes5[5 * i + 1] = kept[i].y1; boxes5[5 * i + 2] = kept[i].x2; boxes5[5 * i + 3] = kept[i].y2;
-        boxes5[5 * i + 4] = kept[i].score;
-        cls[i] = kept[i].cls;
-        anchors[i] = kept[i].anchor;
-    }
-    return (int)kept.size();
+    return yolo_rank_and_suppress(cand, iou, boxes5, cls, anchors, cap, order, n_cand);
+}
+
+int orc_yolo_post_out(const float* out, int nc, int n_anchors, float conf, float iou, float* boxes5, int32_t* cls, int32_t* anchors, int cap) {
+    return orc_yolo_post_out_ranked(out, nc, n_anchors, conf, iou, boxes5, cls, anchors, cap, nullptr, nullptr, nullptr);
+}
+
+/* the layout steps of the detector graph alone (CpuOps above), on plain arrays with pitches */
+void orc_maxpool5(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy) {
+    CpuOps ops{nullptr};
+    TkT tx, ty;
+    tx.p = const_cast<float*>(x); tx.B = B; tx.H = H; tx.W = W; tx.C = C; tx.ld = ldx;
+    ty = tx; ty.p = y; ty.ld = ldy;
+    ops.maxpool5(tx, ty);
+}
+void orc_upsample2x(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy) {
+    CpuOps ops{nullptr};
+    TkT tx, ty;
+    tx.p = const_cast<float*>(x); tx.B = B; tx.H = H; tx.W = W; tx.C = C; tx.ld = ldx;
+    ty = tx; ty.p = y; ty.H = 2 * H; ty.W = 2 * W; ty.ld = ldy;
+    ops.upsample2x(tx, ty);
 }
 
 /* plain fp32 GEMM oracle of tk_gemm_f32: C = act(alpha * sum_k A[m][k] B[n][k] + bias) + residual, k-ordered fma chain */
@@ -266,6 +284,41 @@ void orc_gemm(const float* A, const float* B, float* C, const float* bias, const
             if (residual) v = v + residual[(size_t)m * ldr + n];
             C[(size_t)m * ldc + n] = v;
         }
+}
+
+/* the chain the detector's stem must equal: the NHWC im2col matrix (padding taps as zeros), then orc_gemm with its epilogue.  x [B][H][W] pixels of
+ * pitch ldx, w [N][k k C], y [B Ho Wo] rows of pitch ldy.  mutant (tests only; 0 = the contract): 1 = a padding tap is SKIPPED instead of entering
+ * the chain as a = 0 (the same bits for finite weights; a non-finite weight on a padding tap tells them apart) */
+void orc_conv_chain(const float* x, int B, int H, int W, int C, int ldx, const float* w, const float* bias, int act, int N, int k, int stride, int pad, float* y,
+                    int ldy, int mutant) {
+    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1, K = k * k * C;
+    const int64_t M = (int64_t)B * Ho * Wo;
+    std::vector<float> col((size_t)M * K), out((size_t)M * N);
+    std::vector<uint8_t> inside((size_t)M * K);
+    for (int64_t m = 0; m < M; ++m) {
+        const int ox = (int)(m % Wo), oy = (int)((m / Wo) % Ho), b = (int)(m / ((int64_t)Wo * Ho));
+        for (int ky = 0; ky < k; ++ky)
+            for (int kx = 0; kx < k; ++kx) {
+                const int iy = oy * stride + ky - pad, ix = ox * stride + kx - pad;
+                const bool in = iy >= 0 && iy < H && ix >= 0 && ix < W;
+                for (int c = 0; c < C; ++c) {
+                    col[(size_t)m * K + (ky * k + kx) * C + c] = in ? x[(((int64_t)b * H + iy) * W + ix) * ldx + c] : 0.0f;
+                    inside[(size_t)m * K + (ky * k + kx) * C + c] = in;
+                }
+            }
+    }
+    if (!mutant) orc_gemm(col.data(), w, out.data(), bias, nullptr, (int)M, N, K, K, K, N, 0, 0, act, 1.0f);
+    else
+        for (int64_t m = 0; m < M; ++m)
+            for (int n = 0; n < N; ++n) {
+                float acc = 0.0f;
+                for (int kk = 0; kk < K; ++kk)
+                    if (inside[(size_t)m * K + kk]) acc = tk_fmaf(col[(size_t)m * K + kk], w[(size_t)n * K + kk], acc);
+                float v = acc + (bias ? bias[n] : 0.0f);
+                if (act == 1) v = tk_siluf(v);
+                out[(size_t)m * N + n] = v;
+            }
+    for (int64_t m = 0; m < M; ++m) memcpy(y + m * ldy, out.data() + m * N, (size_t)N * 4);
 }
 
 } /* extern "C" */

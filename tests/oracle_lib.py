@@ -337,6 +337,36 @@ def yolo_post_out(out, nc, conf, iou, cap=500):
     return boxes[:n], cls[:n], anc[:n]
 
 
+YOLO_BOX_DTYPE = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("score", "<f4"), ("cls", "<i4"), ("anchor", "<i4")])  # tk_yolo_cand_t
+
+
+def yolo_post_ranked(conf, iou, nc, raw=None, ld=None, H=0, W=0, out=None):
+    """one frame through orc_yolo_post_ranked (raw [anchors][ld] head values, scales 8 / 16 / 32 concatenated) or orc_yolo_post_out_ranked
+    (out [4 + nc][anchors]) -> dict(cand: every anchor's decoded record, cls = -1 where it is no candidate; order: the ranked anchor ids;
+    kept: the survivors' records)"""
+    L = lib()
+    cap = 500
+    boxes, cls, anc = np.zeros((cap, 5), np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    order, n_cand = np.full(2048, -1, np.int32), C.c_int32(0)
+    if raw is not None:
+        raw = np.ascontiguousarray(raw, np.float32)
+        cand = np.zeros(raw.shape[0], YOLO_BOX_DTYPE)
+        L.orc_yolo_post_ranked.restype = C.c_int
+        L.orc_yolo_post_ranked.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_float] * 2 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3
+        n = L.orc_yolo_post_ranked(ptr(raw), ld, H, W, nc, conf, iou, ptr(boxes), ptr(cls), ptr(anc), cap, ptr(cand), ptr(order), C.byref(n_cand))
+    else:
+        out = np.ascontiguousarray(out, np.float32)
+        cand = np.zeros(out.shape[1], YOLO_BOX_DTYPE)
+        L.orc_yolo_post_out_ranked.restype = C.c_int
+        L.orc_yolo_post_out_ranked.argtypes = [C.c_void_p] + [C.c_int] * 2 + [C.c_float] * 2 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3
+        n = L.orc_yolo_post_out_ranked(ptr(out), nc, out.shape[1], conf, iou, ptr(boxes), ptr(cls), ptr(anc), cap, ptr(cand), ptr(order), C.byref(n_cand))
+    kept = np.zeros(n, YOLO_BOX_DTYPE)
+    for i, k in enumerate(("x1", "y1", "x2", "y2", "score")):
+        kept[k] = boxes[:n, i]
+    kept["cls"], kept["anchor"] = cls[:n], anc[:n]
+    return dict(cand=cand, order=order[:n_cand.value].copy(), n_cand=n_cand.value, kept=kept, n_kept=n)
+
+
 def gemm(A, B, bias=None, residual=None, b_kn=False, act=0, alpha=1.0):
     A = np.ascontiguousarray(A, np.float32)
     B = np.ascontiguousarray(B, np.float32)
@@ -350,6 +380,89 @@ def gemm(A, B, bias=None, residual=None, b_kn=False, act=0, alpha=1.0):
     L.orc_gemm(ptr(A), ptr(B), ptr(Cm), ptr(bias) if bias is not None else None, ptr(residual) if residual is not None else None,
                M, N, K, K, B.shape[1], N, N, int(b_kn), act, alpha)
     return Cm
+
+
+# ---------------------------------------------------------------- row and layout steps of the perception graphs, alone
+def _f32(x):
+    return np.ascontiguousarray(x, np.float32)
+
+
+def layernorm_eps():
+    lib().orc_layernorm_eps.restype = C.c_float
+    return float(lib().orc_layernorm_eps())
+
+
+def layernorm(x, w, b):
+    """x [rows][D] -> y, the Whisper graph's norm (eps = layernorm_eps())"""
+    x, w, b = _f32(x), _f32(w), _f32(b)
+    y = np.empty_like(x)
+    lib().orc_layernorm.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib().orc_layernorm(ptr(x), x.shape[0], x.shape[1], ptr(w), ptr(b), ptr(y))
+    return y
+
+
+def softmax_rows(x, rows, cols, ld, reversed_sum=False):
+    """in place on a copy of the flat array x: rows `ld` apart, the first `cols` entries of each (reversed_sum: the oracle's mutant, tests only)"""
+    x = np.array(x, np.float32).reshape(-1)
+    fn = lib().orc_softmax_rows_reversed_sum if reversed_sum else lib().orc_softmax_rows
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    fn(ptr(x), rows, cols, ld)
+    return x
+
+
+def conv_chain(x, w, bias, y, B, H, W, Cc, ldx, N, k, stride, pad, ldy, act, skip_padding_taps=False):
+    """orc_conv_chain on a copy of the flat array y: im2col + orc_gemm, the chain the detector's stem must equal (skip_padding_taps: the mutant)"""
+    x, w = _f32(x).reshape(-1), _f32(w).reshape(-1)
+    bias = None if bias is None else _f32(bias)
+    y = np.array(y, np.float32).reshape(-1)
+    lib().orc_conv_chain.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_int]
+    lib().orc_conv_chain(ptr(x), B, H, W, Cc, ldx, ptr(w), ptr(bias) if bias is not None else None, act, N, k, stride, pad, ptr(y), ldy, int(skip_padding_taps))
+    return y
+
+
+def im2col1d(x, B, T, Cc, ldx, kw, stride, pad):
+    x = _f32(x).reshape(-1)
+    To = (T + 2 * pad - kw) // stride + 1
+    col = np.empty(B * To * kw * Cc, np.float32)
+    lib().orc_im2col1d.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
+    lib().orc_im2col1d(ptr(x), B, T, Cc, ldx, kw, stride, pad, ptr(col))
+    return col
+
+
+def add_rows(x, add, rows, D, n_add):
+    x = np.array(x, np.float32).reshape(-1)
+    add = _f32(add).reshape(-1)
+    lib().orc_add_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib().orc_add_rows(ptr(x), ptr(add), rows, D, n_add)
+    return x
+
+
+def embed_rows(table, pos, idx, pos_idx, D):
+    table, pos = _f32(table).reshape(-1), _f32(pos).reshape(-1)
+    idx, pos_idx = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(pos_idx, np.int32)
+    out = np.empty(len(idx) * D, np.float32)
+    lib().orc_embed_rows.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]
+    lib().orc_embed_rows(ptr(table), ptr(pos), ptr(idx), ptr(pos_idx), len(idx), D, ptr(out))
+    return out
+
+
+def attend1(q, k, v, out, B, Tk, q_bstride, kv_bstride, d, nh):
+    """orc_attend1 on a copy of the flat array out: the graph's attention at one query row per sequence, three-launch form"""
+    q, k, v = _f32(q).reshape(-1), _f32(k).reshape(-1), _f32(v).reshape(-1)
+    out = np.array(out, np.float32).reshape(-1)
+    lib().orc_attend1.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int]
+    lib().orc_attend1(ptr(q), ptr(k), ptr(v), ptr(out), B, Tk, q_bstride, kv_bstride, d, nh)
+    return out
+
+
+def pool_or_upsample(which, x, y, B, H, W, Cc, ldx, ldy):
+    """orc_maxpool5 / orc_upsample2x on a copy of the flat array y (pitch ldy)"""
+    x = _f32(x).reshape(-1)
+    y = np.array(y, np.float32).reshape(-1)
+    fn = getattr(lib(), "orc_" + which)
+    fn.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int]
+    fn(ptr(x), B, H, W, Cc, ldx, ptr(y), ldy)
+    return y
 
 
 # ---------------------------------------------------------------- audio oracle bindings

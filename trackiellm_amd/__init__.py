@@ -12,8 +12,10 @@ from .llm import LlmHParams, LlmModel, LlmSession, LlmPipe, PipeHandle, ModelLoa
 from .llm import TYPE_F32, TYPE_F16, TYPE_Q4_0, TYPE_Q5_0, TYPE_Q8_0, TYPE_Q2_K, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K, TYPE_IQ4_NL, TYPE_IQ4_XS, TYPE_Q4_1, TYPE_Q5_1, TYPE_BF16, TYPE_TQ1_0, TYPE_TQ2_0, FTYPE_TQ1_0, FTYPE_TQ2_0, FTYPE_Q4_1, FTYPE_Q5_1, FTYPE_IQ4_NL, FTYPE_IQ4_XS, FTYPE_Q4_0, FTYPE_Q5_0, FTYPE_Q8_0, FTYPE_Q2_K, FTYPE_Q2_K_S, FTYPE_Q3_K_S, FTYPE_Q3_K_M, FTYPE_Q4_K_S, FTYPE_Q4_K_M, FTYPE_Q5_K_S, FTYPE_Q5_K_M  # noqa: F401
 from .vision import ObjectDetector, VisionPipeline, classify_attributes, preprocess, COCO80  # noqa: F401,E402
 from .vision import DepthEstimator, depth_onnx_probe, fuse_data, fusion_reset, fusion_raw_distance  # noqa: F401,E402
-from .vision import onnx_run  # noqa: F401,E402
+from .vision import onnx_run, detector_post_probe, DetectorPostProbe, BOX_DTYPE, YOLO_MAX_CAND, YOLO_MAX_DET  # noqa: F401,E402
 from .nn import GemmProbe, gemm_probe, gemm_code, attention_h3_probe, GEMM_F32, GEMM_F32_TALL, GEMM_F32_BIG, GEMM_H3_TALL, GEMM_H3_BIG  # noqa: F401,E402
+from .nn import NnRowProbe, nn_row_probe, ROW_CONV_STEM, ROW_IM2COL, ROW_IM2COL1D, ROW_MAXPOOL5, ROW_UPSAMPLE2X, ROW_COPY_COLS, ROW_LAYERNORM, ROW_SOFTMAX_ROWS, ROW_ADD_ROWS, ROW_EMBED_ROWS, ROW_ATTEND1  # noqa: F401,E402
+from .nn import SOFTMAX_GENERIC, SOFTMAX_REG, SOFTMAX_WAVE, IM2COL_ELEMENT, IM2COL_V4  # noqa: F401,E402
 from .pick import TokenPickProbe, token_pick_probe, sampling_rows, SAMPLING_DTYPE, PICK_ARGMAX, PICK_ARGMAX_ROWS, PICK_ROWS, PICK_ROWS_FILTERED  # noqa: F401,E402
 from .audio import Asr, Vad, WhisperHP, WHISPER_TINY_EN, AudioPipeline  # noqa: F401,E402
 from .cortex import Cortex, RocmDispatcher, PreprocessParams, DepthPostParams, DepthToPointsParams, Float3  # noqa: F401,E402

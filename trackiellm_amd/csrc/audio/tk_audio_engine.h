@@ -14,6 +14,15 @@
 
 #include "../common/tk_whisper_graph.h"
 
+/* the decoder-step attention (k_attend1: one query row per sequence and head, tk_audio_engine.hip) as a free launcher: admission test, LDS size,
+ * launch.  q / out: [B] rows q_bstride floats apart, k / v: [B] x [Tk] rows of pitch d, kv_bstride apart; head h in columns [h hd, h hd + hd),
+ * hd = d / nh.  false, nothing launched: hd no multiple of 16 or above 256, more LDS than 60 KiB (hd = 64: Tk > 3008), a batch stride that is
+ * no multiple of 4, k or v off 16 bytes, an empty extent.  img (optional): out also as the tiled GEMM's operand image [ceil(B / 16) 16][d]. */
+size_t tk_attend1_lds_bytes(int Tk, int d, int nh);
+bool tk_attend1_ok(const float* k, const float* v, int B, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, int nh);
+bool tk_launch_attend1(const float* q, const float* k, const float* v, float* out, int B, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, int nh, float* img,
+                       hipStream_t s);
+
 class TkWhisperModel {
 public:
     TkWhisperHP hp{};

@@ -181,6 +181,36 @@ __global__ __launch_bounds__(256) void k_attend1(const float* q, const float* k,
     }
 }
 
+/* The launcher: admission test, LDS size, launch.  hd = d / nh must be a multiple of 16 (whole 1 KiB DMA pieces, 16-byte key groups) and the value
+ * ring + Tk scores + the query fit 60 KiB of LDS: hd = 64 admits Tk <= 3008, hd = 80 nothing.  The kernel reads 16-byte groups of k and v at
+ * b * kv_bstride + h * hd + 4 i and DMA-copies 16-byte groups of v, so both bases and kv_bstride must keep them aligned (a rule of safety); q and
+ * out are read and written one float at a time: q_bstride is held to the same rule for symmetry only (no caller sends another).  img is the caller's choice (NULL: none; it needs d % 16 == 0, which hd % 16 == 0 gives). */
+size_t tk_attend1_lds_bytes(int Tk, int d, int nh) {
+    if (Tk < 1 || nh < 1 || d < 1 || d % nh) return 0;
+    const int hd = d / nh;
+    return ((size_t)TK_AT1_NS * TK_AT1_CK * hd + (size_t)Tk + (size_t)hd) * 4;
+}
+bool tk_attend1_ok(const float* k, const float* v, int B, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, int nh) {
+    if (B < 1 || B > 65535 || nh < 1 || nh > 65535 || Tk < 1 || d < 1 || d % nh) return false;
+    const int hd = d / nh;
+    if (hd > 256 || (hd & 15) || (d & 3) || tk_attend1_lds_bytes(Tk, d, nh) > 60 * 1024) return false; /* the three-launch form takes what does not fit */
+    if (q_bstride < 0 || kv_bstride < 0 || (q_bstride & 3) || (kv_bstride & 3)) return false;
+    return ((((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0;
+}
+/* the launch alone, for a geometry tk_attend1_ok admitted */
+static void attend1_enqueue(const float* q, const float* k, const float* v, float* out, int B, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, int nh, float* img,
+                            hipStream_t s) {
+    const int hd = d / nh;
+    hipLaunchKernelGGL(k_attend1, dim3(nh, B), dim3(256), tk_attend1_lds_bytes(Tk, d, nh), s, q, k, v, out, Tk, q_bstride, kv_bstride, d, hd,
+                       tk_divf(1.0f, tk_sqrtf((float)hd)), img);
+}
+bool tk_launch_attend1(const float* q, const float* k, const float* v, float* out, int B, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, int nh, float* img,
+                       hipStream_t s) {
+    if (!tk_attend1_ok(k, v, B, Tk, q_bstride, kv_bstride, d, nh)) return false;
+    attend1_enqueue(q, k, v, out, B, Tk, q_bstride, kv_bstride, d, nh, img, s);
+    return true;
+}
+
 /* ---------------------------------------------------------------- GPU ops for the shared graph */
 
 /* shapes the tiled GEMM takes: a plain linear layer C = act(A W^T + b) + R with K a multiple of 128 */
@@ -306,20 +336,19 @@ struct TkAudioGpuOps {
         }
         if (in_place) drop_image(); /* the output overwrote the packed matrix: the image is stale */
     }
-    void im2col1d(const float* x, int B, int T, int C, int ldx, int kw, int stride, int pad, float* col) { drop_image(); tk_launch_im2col1d(x, B, T, C, ldx, kw, stride, pad, col, s); }
+    void refused(const char* what) { if (a->launch_error.empty()) a->launch_error = std::string(what) + ": the launcher refused its geometry"; }
+    void im2col1d(const float* x, int B, int T, int C, int ldx, int kw, int stride, int pad, float* col) { drop_image(); if (!tk_launch_im2col1d(x, B, T, C, ldx, kw, stride, pad, col, s)) refused("im2col1d"); }
     void layernorm(const float* x, int rows, int D, const float* w, const float* b, float* y) {
         drop_image();
         float* img = D % 128 == 0 && !(a->fast && long_ok) ? image_for(y, rows, D, D) : nullptr; /* a norm feeds linear layers: packed on the way out */
-        tk_launch_layernorm(x, rows, D, w, b, TK_WH_LN_EPS, y, s, img);
+        if (!tk_launch_layernorm(x, rows, D, w, b, TK_WH_LN_EPS, y, s, img)) refused("layernorm");
     }
-    void softmax_rows(float* x, int rows, int cols, int ld) { drop_image(); tk_launch_softmax_rows(x, rows, cols, ld, s); }
+    void softmax_rows(float* x, int rows, int cols, int ld) { drop_image(); if (!tk_launch_softmax_rows(x, rows, cols, ld, s)) refused("softmax_rows"); }
     bool attend1(const float* q, const float* k, const float* v, float* out, int B, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, int nh) {
         drop_image();
-        const int hd = d / nh;
-        const size_t ldsb = ((size_t)TK_AT1_NS * TK_AT1_CK * hd + (size_t)Tk + (size_t)hd) * 4;
-        if (hd > 256 || (hd & 15) || (d & 3) || Tk < 1 || ldsb > 60 * 1024) return false; /* the three-launch form takes what does not fit */
+        if (!tk_attend1_ok(k, v, B, Tk, q_bstride, kv_bstride, d, nh)) return false; /* the three-launch form takes what does not fit */
         float* img = (short_pass(B) && d % 128 == 0 && q_bstride == d) ? image_for(out, B, d, d) : nullptr; /* the output projection's input, packed on the way out */
-        hipLaunchKernelGGL(k_attend1, dim3(nh, B), dim3(256), ldsb, s, q, k, v, out, Tk, q_bstride, kv_bstride, d, hd, tk_divf(1.0f, tk_sqrtf((float)hd)), img);
+        attend1_enqueue(q, k, v, out, B, Tk, q_bstride, kv_bstride, d, nh, img, s);
         return true;
     }
     /* the opt-in fast contraction's attention (TkAsr::fast): Q K^T, softmax and P V of a long pass in one kernel, no score matrix in HBM */
@@ -328,10 +357,10 @@ struct TkAudioGpuOps {
         drop_image();
         return tk_launch_attention_h3(q, k, v, out, B, nh, Tq, Tk, q_bstride, kv_bstride, d, tk_divf(1.0f, tk_sqrtf(64.0f)), s);
     }
-    void add_rows(float* x, const float* add, int rows, int D, int add_rows) { drop_image(); tk_launch_add_rows(x, add, rows, D, add_rows, s); }
+    void add_rows(float* x, const float* add, int rows, int D, int add_rows) { drop_image(); if (!tk_launch_add_rows(x, add, rows, D, add_rows, s)) refused("add_rows"); }
     void embed_rows(const float* table, const float* pos, const int32_t* idx, const int32_t* pos_idx, int rows, int D, float* out) {
         drop_image();
-        tk_launch_embed_rows(table, pos, idx, pos_idx, rows, D, out, s);
+        if (!tk_launch_embed_rows(table, pos, idx, pos_idx, rows, D, out, s)) refused("embed_rows");
     }
     void argmax_rows(const float* x, int rows, int cols, int ld, int32_t* out) {
         drop_image();

@@ -12,6 +12,7 @@
 #include "tk/tk_mi355x_ext.h"
 
 #include "../vision/tk_vision_engine.h"
+#include "../audio/tk_audio_engine.h"
 #include "tk/tk_rocm_hal.h"
 #include "../nn/tk_gemm_tiled.h"
 #include "../nn/tk_nn_kernels.h"
@@ -109,12 +110,14 @@ tk_error_code_t tk_kernels_postprocess_depth_map(const tk_postprocess_depth_para
 }
 
 tk_error_code_t tk_kernels_softmax(const tk_softmax_params_t* p, tk_hip_stream_t stream) {
-    if (!p || !p->d_input_tensor || !p->d_output_tensor || p->num_rows == 0 || p->num_cols == 0) return TK_ERROR_INVALID_ARGUMENT;
+    if (!p || !p->d_input_tensor || !p->d_output_tensor || p->num_rows == 0 || p->num_cols == 0 || p->num_rows > 0x7fffffffu || p->num_cols > 0x7fffffffu)
+        return TK_ERROR_INVALID_ARGUMENT;
     if (p->d_output_tensor != p->d_input_tensor &&
         hipMemcpyAsync(p->d_output_tensor, p->d_input_tensor, (size_t)p->num_rows * p->num_cols * sizeof(float), hipMemcpyDeviceToDevice,
                        (hipStream_t)stream) != hipSuccess)
         return TK_ERROR_GPU_ROCM_ERROR;
-    tk_launch_softmax_rows((float*)p->d_output_tensor, (int)p->num_rows, (int)p->num_cols, (int)p->num_cols, (hipStream_t)stream);
+    if (!tk_launch_softmax_rows((float*)p->d_output_tensor, (int)p->num_rows, (int)p->num_cols, (int)p->num_cols, (hipStream_t)stream))
+        return TK_ERROR_INVALID_ARGUMENT;
     return launch_status();
 }
 
@@ -379,6 +382,238 @@ tk_error_code_t tk_mi355x_token_pick_probe(int device, tk_mi355x_token_pick_prob
                 if (q.host && q.out && hipMemcpy(const_cast<void*>(q.host), q.dev, q.bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
     }
     for (Buf& q : b) if (q.dev) (void)hipFree(q.dev);
+    return rc;
+}
+
+/* one host array of a probe: where it comes from, how many bytes, how far into its device allocation it is placed, whether it is read back */
+struct ProbeBuf { const void* host; size_t bytes, offset; bool out; void* dev; };
+static bool probe_upload(ProbeBuf* b, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (!b[i].host) continue;
+        if (hipMalloc(&b[i].dev, b[i].bytes + b[i].offset) != hipSuccess) return false;
+        if (hipMemcpy((uint8_t*)b[i].dev + b[i].offset, b[i].host, b[i].bytes, hipMemcpyHostToDevice) != hipSuccess) return false;
+    }
+    return true;
+}
+static bool probe_download(ProbeBuf* b, int n) {
+    bool ok = true;
+    for (int i = 0; i < n; ++i)
+        if (b[i].host && b[i].out && hipMemcpy(const_cast<void*>(b[i].host), (uint8_t*)b[i].dev + b[i].offset, b[i].bytes, hipMemcpyDeviceToHost) != hipSuccess) ok = false;
+    return ok;
+}
+static void probe_free(ProbeBuf* b, int n) {
+    for (int i = 0; i < n; ++i) if (b[i].dev) (void)hipFree(b[i].dev);
+}
+static tk_error_code_t probe_device(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    return TK_SUCCESS;
+}
+
+/* floats each array of a row-probe launch must hold (0: not read), from the kernels' own index expressions; false: a geometry no launch may have */
+struct RowReach { int64_t a, b, c, idx, y, img; };
+static bool row_probe_reach(const tk_mi355x_nn_row_probe_t& p, RowReach& o) {
+    const int64_t cap = (int64_t)1 << 20, big = (int64_t)1 << 28;
+    auto dim = [&](int64_t v) { return v >= 1 && v <= cap; };
+    o = RowReach{0, 0, 0, 0, 0, 0};
+    if (p.a_offset < 0 || p.a_offset > 64 || p.y_offset < 0 || p.y_offset > 64) return false;
+    if (p.op == TK_MI355X_ROW_ATTEND1) {
+        if (!dim(p.B) || !dim(p.H) || !dim(p.C) || !dim(p.N) || p.q_bstride < 0 || p.q_bstride > big || p.kv_bstride < 0 || p.kv_bstride > big) return false;
+        if (p.B > 1 && p.q_bstride < p.C) return false; /* output rows would overlap */
+        const int64_t q_need = ((int64_t)p.B - 1) * p.q_bstride + p.C, kv_need = ((int64_t)p.B - 1) * p.kv_bstride + (int64_t)p.H * p.C;
+        if (q_need > big || kv_need > big) return false;
+        o.a = q_need; o.b = kv_need; o.c = kv_need; o.y = q_need;
+        if (p.img) o.img = (((int64_t)p.B + 15) / 16) * 16 * p.C;
+        return true;
+    }
+    const bool image = p.op <= TK_MI355X_ROW_UPSAMPLE2X;
+    if (image) {
+        const int W = p.op == TK_MI355X_ROW_IM2COL1D ? 1 : p.W;
+        if (!dim(p.B) || !dim(p.H) || !dim(W) || !dim(p.C) || !dim(p.ldx) || p.ldx < p.C) return false;
+        const int64_t pixels = (int64_t)p.B * p.H * W;
+        if (pixels > big || pixels * p.ldx > big) return false;
+        o.a = (pixels - 1) * p.ldx + p.C;
+        if (p.op <= TK_MI355X_ROW_IM2COL1D) {
+            if (!dim(p.k) || !dim(p.stride) || p.pad < 0 || p.pad > cap || p.H + 2 * (int64_t)p.pad < p.k || (p.op != TK_MI355X_ROW_IM2COL1D && W + 2 * (int64_t)p.pad < p.k)) return false;
+            const int64_t Ho = (p.H + 2 * (int64_t)p.pad - p.k) / p.stride + 1, Wo = p.op == TK_MI355X_ROW_IM2COL1D ? 1 : (W + 2 * (int64_t)p.pad - p.k) / p.stride + 1;
+            const int64_t K = (int64_t)p.k * (p.op == TK_MI355X_ROW_IM2COL1D ? 1 : p.k) * p.C, opix = (int64_t)p.B * Ho * Wo;
+            if (opix > big || K > big || opix * K > big) return false;
+            if (p.op == TK_MI355X_ROW_CONV_STEM) {
+                if (!dim(p.N) || !dim(p.ldy) || p.ldy < p.N || (p.act != TK_ACT_NONE && p.act != TK_ACT_SILU) || opix * p.ldy > big || K * p.N > big) return false;
+                o.b = K * p.N;
+                o.c = p.N;
+                o.y = (opix - 1) * p.ldy + p.N;
+            } else o.y = opix * K;
+        } else {
+            if (!dim(p.ldy) || p.ldy < p.C) return false;
+            const int64_t opix = p.op == TK_MI355X_ROW_UPSAMPLE2X ? 4 * pixels : pixels;
+            if (opix * p.ldy > big) return false;
+            o.y = (opix - 1) * p.ldy + p.C;
+        }
+        return true;
+    }
+    if (!dim(p.rows) || !dim(p.C)) return false;
+    const int64_t packed = (int64_t)p.rows * p.C;
+    if (packed > big) return false;
+    switch (p.op) {
+    case TK_MI355X_ROW_COPY_COLS:
+        if (!dim(p.ldx) || !dim(p.ldy) || p.ldx < p.C || p.ldy < p.C || (int64_t)p.rows * p.ldx > big || (int64_t)p.rows * p.ldy > big) return false;
+        o.a = ((int64_t)p.rows - 1) * p.ldx + p.C;
+        o.y = ((int64_t)p.rows - 1) * p.ldy + p.C;
+        return true;
+    case TK_MI355X_ROW_LAYERNORM:
+        if (!(p.eps >= 0.0f) || !(p.eps < 1.0f)) return false;
+        o.a = packed; o.b = p.C; o.c = p.C; o.y = packed;
+        if (p.img) {
+            if (p.C & 15) return false; /* the launcher refuses it too: 16-row blocks of the image would overlap */
+            o.img = (((int64_t)p.rows + 15) / 16) * 16 * p.C;
+        }
+        return true;
+    case TK_MI355X_ROW_SOFTMAX_ROWS:
+        if (!dim(p.ldy) || p.ldy < p.C || (int64_t)p.rows * p.ldy > big) return false;
+        o.y = ((int64_t)p.rows - 1) * p.ldy + p.C;
+        return true;
+    case TK_MI355X_ROW_ADD_ROWS:
+        if (!dim(p.add_rows) || (int64_t)p.add_rows * p.C > big) return false;
+        o.a = (int64_t)p.add_rows * p.C; o.y = packed;
+        return true;
+    case TK_MI355X_ROW_EMBED_ROWS:
+        if (!dim(p.table_rows) || !dim(p.pos_rows) || (int64_t)p.table_rows * p.C > big || (int64_t)p.pos_rows * p.C > big) return false;
+        o.a = (int64_t)p.table_rows * p.C; o.b = (int64_t)p.pos_rows * p.C; o.idx = p.rows; o.y = packed;
+        return true;
+    default: return false;
+    }
+}
+
+/* the launch itself (or, with s_dry, the launcher's kernel code alone) on the given bases; false: the launcher refuses */
+static bool row_probe_launch(tk_mi355x_nn_row_probe_t& p, const float* a, const float* b, const float* c, const int32_t* idx, const int32_t* pos_idx, float* y, float* img,
+                             bool dry) {
+    p.kernel = 0;
+    switch (p.op) {
+    case TK_MI355X_ROW_CONV_STEM:
+        if (!tk_conv_stem_ok(p.B, p.H, p.W, p.C, p.ldx, p.N, p.k, p.stride, p.pad, y, p.ldy)) { p.kernel = -1; return false; }
+        if (dry) return true;
+        if (!tk_launch_conv_stem(a, p.B, p.H, p.W, p.C, p.ldx, b, c, p.act, p.N, p.k, p.stride, p.pad, y, p.ldy, nullptr)) { p.kernel = -1; return false; }
+        return true;
+    case TK_MI355X_ROW_IM2COL:
+        p.kernel = tk_im2col_kernel_of(a, p.B, p.H, p.W, p.C, p.ldx, p.k, p.k, p.stride, p.pad, y);
+        return p.kernel >= 0 && (dry || tk_launch_im2col(a, p.B, p.H, p.W, p.C, p.ldx, p.k, p.k, p.stride, p.pad, y, nullptr));
+    case TK_MI355X_ROW_IM2COL1D: return dry || tk_launch_im2col1d(a, p.B, p.H, p.C, p.ldx, p.k, p.stride, p.pad, y, nullptr);
+    case TK_MI355X_ROW_MAXPOOL5: return dry || tk_launch_maxpool5(a, p.B, p.H, p.W, p.C, p.ldx, y, p.ldy, nullptr);
+    case TK_MI355X_ROW_UPSAMPLE2X: return dry || tk_launch_upsample2x(a, p.B, p.H, p.W, p.C, p.ldx, y, p.ldy, nullptr);
+    case TK_MI355X_ROW_COPY_COLS: return dry || tk_launch_copy_cols(a, p.rows, p.C, p.ldx, y, p.ldy, nullptr);
+    case TK_MI355X_ROW_LAYERNORM: return dry || tk_launch_layernorm(a, p.rows, p.C, b, c, p.eps, y, nullptr, img);
+    case TK_MI355X_ROW_SOFTMAX_ROWS:
+        p.kernel = tk_softmax_kernel_of(p.rows, p.C, p.ldy, y);
+        return p.kernel >= 0 && (dry || tk_launch_softmax_rows(y, p.rows, p.C, p.ldy, nullptr));
+    case TK_MI355X_ROW_ADD_ROWS: return dry || tk_launch_add_rows(y, a, p.rows, p.C, p.add_rows, nullptr);
+    case TK_MI355X_ROW_EMBED_ROWS: return dry || tk_launch_embed_rows(a, b, idx, pos_idx, p.rows, p.C, y, nullptr);
+    case TK_MI355X_ROW_ATTEND1:
+        if (!tk_attend1_ok(b, c, p.B, p.H, p.q_bstride, p.kv_bstride, p.C, p.N)) { p.kernel = -1; return false; }
+        return dry || tk_launch_attend1(a, b, c, y, p.B, p.H, p.q_bstride, p.kv_bstride, p.C, p.N, img, nullptr);
+    default: return false;
+    }
+}
+
+tk_error_code_t tk_mi355x_nn_row_probe(int device, tk_mi355x_nn_row_probe_t* p) {
+    if (!p) return TK_ERROR_INVALID_ARGUMENT;
+    p->kernel = -1;
+    RowReach need;
+    if (p->op < TK_MI355X_ROW_CONV_STEM || p->op > TK_MI355X_ROW_ATTEND1 || !row_probe_reach(*p, need)) return TK_ERROR_INVALID_ARGUMENT;
+    /* an array the op reads must be there and long enough; one it does not read must be absent (bias of the stem: the caller's choice) */
+    auto fits = [](const void* ptr, int64_t n, int64_t want, bool optional) {
+        if (want == 0) return ptr == nullptr && n == 0;
+        if (!ptr) return optional && n == 0;
+        return n >= want;
+    };
+    if (!fits(p->a, p->n_a, need.a, false) || !fits(p->b, p->n_b, need.b, false) || !fits(p->c, p->n_c, need.c, p->op == TK_MI355X_ROW_CONV_STEM) ||
+        !fits(p->idx, p->n_idx, need.idx, false) || !fits(p->pos_idx, p->pos_idx ? p->n_idx : 0, need.idx, false) || !fits(p->y, p->n_y, need.y, false) ||
+        !fits(p->img, p->n_img, need.img, true))
+        return TK_ERROR_INVALID_ARGUMENT;
+    if (p->op == TK_MI355X_ROW_EMBED_ROWS)
+        for (int r = 0; r < p->rows; ++r)
+            if (p->idx[r] < 0 || p->idx[r] >= p->table_rows || p->pos_idx[r] < 0 || p->pos_idx[r] >= p->pos_rows) return TK_ERROR_INVALID_ARGUMENT;
+    if (device < 0) { /* bases as the device allocator aligns them */
+        const float* a = p->a ? (const float*)(uintptr_t)256 + p->a_offset : nullptr;
+        const float* aligned = (const float*)(uintptr_t)256;
+        return row_probe_launch(*p, a, aligned, aligned, nullptr, nullptr, (float*)(uintptr_t)256 + p->y_offset, nullptr, true) ? TK_SUCCESS : TK_ERROR_INVALID_ARGUMENT;
+    }
+    tk_error_code_t rc = probe_device(device);
+    if (rc != TK_SUCCESS) return rc;
+    enum { A, Bm, Cm, IDX, POS, Y, IMG, NBUF };
+    ProbeBuf b[NBUF] = {{p->a, (size_t)p->n_a * 4, (size_t)p->a_offset * 4, false, nullptr}, {p->b, (size_t)p->n_b * 4, 0, false, nullptr},
+                        {p->c, (size_t)p->n_c * 4, 0, false, nullptr}, {p->idx, (size_t)p->n_idx * 4, 0, false, nullptr},
+                        {p->pos_idx, (size_t)p->n_idx * 4, 0, false, nullptr}, {p->y, (size_t)p->n_y * 4, (size_t)p->y_offset * 4, true, nullptr},
+                        {p->img, (size_t)p->n_img * 4, 0, true, nullptr}};
+    if (!probe_upload(b, NBUF)) rc = TK_ERROR_GPU_ROCM_ERROR;
+    else {
+        auto at = [&](int i) { return b[i].dev ? (float*)((uint8_t*)b[i].dev + b[i].offset) : nullptr; };
+        if (!row_probe_launch(*p, at(A), at(Bm), at(Cm), (const int32_t*)b[IDX].dev, (const int32_t*)b[POS].dev, at(Y), at(IMG), false)) rc = TK_ERROR_INVALID_ARGUMENT;
+        else if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess || !probe_download(b, NBUF)) rc = TK_ERROR_GPU_ROCM_ERROR;
+    }
+    probe_free(b, NBUF);
+    return rc;
+}
+
+tk_error_code_t tk_mi355x_detector_post_probe(int device, tk_mi355x_detector_post_probe_t* p) {
+    static_assert(sizeof(tk_mi355x_box_t) == sizeof(tk_yolo_cand_t) && sizeof(tk_mi355x_box_t) == sizeof(TkDetection), "the public record is the kernels' candidate and detection");
+    if (!p || (p->kind != 0 && p->kind != 1) || p->B < 1 || p->B > 256 || p->nc < 1 || p->nc > 4096 || p->n_anchors < 1 || p->n_anchors > (1 << 20))
+        return TK_ERROR_INVALID_ARGUMENT;
+    const int64_t B = p->B, words = TK_YOLO_MAX_CAND / 64;
+    TkT heads[3];
+    if (p->kind == 0) {
+        if (p->in_w < 32 || p->in_h < 32 || p->in_w > 4096 || p->in_h > 4096 || (p->in_w & 31) || (p->in_h & 31) || p->out || p->n_out != 0) return TK_ERROR_INVALID_ARGUMENT;
+        int64_t total = 0;
+        for (int i = 0; i < 3; ++i) {
+            const int H = p->in_h >> (3 + i), W = p->in_w >> (3 + i);
+            if (!p->head[i] || p->ld[i] < 64 + p->nc || p->ld[i] > (1 << 16) || p->n_head[i] < (B * H * W - 1) * p->ld[i] + 64 + p->nc) return TK_ERROR_INVALID_ARGUMENT;
+            heads[i].B = p->B; heads[i].H = H; heads[i].W = W; heads[i].C = 64 + p->nc; heads[i].ld = p->ld[i];
+            total += (int64_t)H * W;
+        }
+        if (total != p->n_anchors) return TK_ERROR_INVALID_ARGUMENT;
+    } else {
+        if (!p->out || p->n_out < B * (4 + p->nc) * p->n_anchors) return TK_ERROR_INVALID_ARGUMENT;
+        for (int i = 0; i < 3; ++i) if (p->head[i] || p->n_head[i] != 0) return TK_ERROR_INVALID_ARGUMENT;
+    }
+    if (!p->cand || !p->order || !p->n_cand || !p->kept || !p->n_kept || p->cand_count != B * p->n_anchors || p->order_count != B * TK_YOLO_MAX_CAND ||
+        p->n_cand_count != B || p->kept_count != B * TK_OBJECT_DETECTOR_MAX_DETECTIONS || p->n_kept_count != B ||
+        (p->mask ? p->mask_count != B * TK_YOLO_MAX_CAND * words : p->mask_count != 0))
+        return TK_ERROR_INVALID_ARGUMENT;
+    if (device < 0) return TK_SUCCESS;
+    tk_error_code_t rc = probe_device(device);
+    if (rc != TK_SUCCESS) return rc;
+    enum { H0, H1, H2, OUT, CAND, ORDER, NCAND, MASK, KEPT, NKEPT, NBUF };
+    const size_t rec = sizeof(tk_mi355x_box_t);
+    ProbeBuf b[NBUF] = {{p->head[0], (size_t)p->n_head[0] * 4, 0, false, nullptr}, {p->head[1], (size_t)p->n_head[1] * 4, 0, false, nullptr},
+                        {p->head[2], (size_t)p->n_head[2] * 4, 0, false, nullptr}, {p->out, (size_t)p->n_out * 4, 0, false, nullptr},
+                        {p->cand, (size_t)p->cand_count * rec, 0, true, nullptr}, {p->order, (size_t)p->order_count * 4, 0, true, nullptr},
+                        {p->n_cand, (size_t)B * 4, 0, true, nullptr}, {p->mask, (size_t)p->mask_count * 8, 0, true, nullptr},
+                        {p->kept, (size_t)p->kept_count * rec, 0, true, nullptr}, {p->n_kept, (size_t)B * 4, 0, true, nullptr}};
+    void* own_mask = nullptr; /* no host mask: the matrix still exists on the device, stale like the caller's other arrays */
+    const size_t mask_bytes = (size_t)B * TK_YOLO_MAX_CAND * words * 8;
+    bool ok = probe_upload(b, NBUF);
+    if (ok && !p->mask) ok = hipMalloc(&own_mask, mask_bytes) == hipSuccess && hipMemset(own_mask, 0xFF, mask_bytes) == hipSuccess;
+    if (!ok) rc = TK_ERROR_GPU_ROCM_ERROR;
+    else {
+        tk_yolo_cand_t* cand = (tk_yolo_cand_t*)b[CAND].dev;
+        bool launched = true;
+        if (p->kind == 0) {
+            for (int i = 0; i < 3; ++i) heads[i].p = (float*)b[H0 + i].dev;
+            launched = tk_launch_yolo_decode(heads, p->B, p->nc, p->n_anchors, p->conf, cand, nullptr);
+        } else
+            for (int f = 0; f < p->B && launched; ++f)
+                launched = tk_launch_yolo_decode_out((const float*)b[OUT].dev + (size_t)f * (4 + p->nc) * p->n_anchors, p->nc, p->n_anchors, p->conf,
+                                                     cand + (size_t)f * p->n_anchors, nullptr);
+        launched = launched && tk_launch_yolo_post(cand, p->n_anchors, p->B, p->iou, (int32_t*)b[ORDER].dev, (int32_t*)b[NCAND].dev,
+                                                   (uint64_t*)(p->mask ? b[MASK].dev : own_mask), (TkDetection*)b[KEPT].dev, (int32_t*)b[NKEPT].dev, nullptr);
+        if (!launched) rc = TK_ERROR_INVALID_ARGUMENT;
+        else if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess || !probe_download(b, NBUF)) rc = TK_ERROR_GPU_ROCM_ERROR;
+    }
+    probe_free(b, NBUF);
+    if (own_mask) (void)hipFree(own_mask);
     return rc;
 }
 

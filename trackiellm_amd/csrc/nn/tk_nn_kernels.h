@@ -37,6 +37,9 @@ int tk_gemm_kernel_of(const TkGemm& g);
 bool tk_gemm_im2col_ok(const float* x, int C, int ldx, const float* w);
 /* direct 3x3 convolution of a 3-channel image into 16 channels (the detector's stem), the GEMM's chain and epilogue (bias, act) per
  * output; false (nothing launched): another shape — use im2col + tk_launch_gemm */
+/* the stem launcher's admission test, a pure host function: N == 16, C == 3, k == 3, ldy % 4 == 0, y 16-byte aligned, a non-empty output of
+ * fewer than 2^31 pixels, stride >= 1, pad >= 0, pitches not below the extents */
+bool tk_conv_stem_ok(int B, int H, int W, int C, int ldx, int N, int k, int stride, int pad, const float* y, int ldy);
 bool tk_launch_conv_stem(const float* x, int B, int H, int W, int C, int ldx, const float* w, const float* bias, int act, int N, int k, int stride, int pad, float* y,
                          int ldy, hipStream_t s);
 /* opts the large-tile GEMM into its dynamic LDS on the calling thread's current device; idempotent, thread-safe.  tk_launch_gemm does
@@ -48,16 +51,22 @@ bool tk_nn_prepare_device();
 bool tk_launch_attention_h3(const float* q, const float* k, const float* v, float* out, int B, int nh, int Tq, int Tk, int64_t q_bstride, int64_t kv_bstride, int d,
                             float scale, hipStream_t s);
 
+/* The row and layout launchers below return false with nothing launched for what no caller sends: an empty extent (rows, B, H, W, C, D < 1),
+ * a pitch below the extent, a stride < 1, a negative pad, a window wider than the padded input, more 256-element blocks than a grid holds.
+ * Every caller checks the result: the engines report a refusal as their own error, the hooks as TK_ERROR_INVALID_ARGUMENT. */
 /* NHWC im2col: col[b*Ho*Wo + oy*Wo + ox][(ky*kw + kx)*C + c]; input row stride ldx floats per pixel */
-void tk_launch_im2col(const float* x, int B, int H, int W, int C, int ldx, int kh, int kw, int stride, int pad, float* col, hipStream_t s);
-/* 1-D variant for conv1d over [T][C] rows */
-void tk_launch_maxpool5(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy, hipStream_t s);
-void tk_launch_upsample2x(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy, hipStream_t s);
-void tk_launch_copy_cols(const float* x, int rows, int C, int ldx, float* y, int ldy, hipStream_t s);
+[[nodiscard]] bool tk_launch_im2col(const float* x, int B, int H, int W, int C, int ldx, int kh, int kw, int stride, int pad, float* col, hipStream_t s);
+/* which kernel tk_launch_im2col takes — a pure host function and the launcher's own switch: the 16-byte kernel needs C % 4 == 0, ldx % 4 == 0,
+ * x and col 16-byte aligned and fewer than 2^31 groups */
+enum { TK_IM2COL_ELEMENT = 0, TK_IM2COL_V4 = 1, TK_IM2COL_REFUSED = -1 };
+int tk_im2col_kernel_of(const float* x, int B, int H, int W, int C, int ldx, int kh, int kw, int stride, int pad, const float* col);
+[[nodiscard]] bool tk_launch_maxpool5(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy, hipStream_t s);
+[[nodiscard]] bool tk_launch_upsample2x(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy, hipStream_t s);
+[[nodiscard]] bool tk_launch_copy_cols(const float* x, int rows, int C, int ldx, float* y, int ldy, hipStream_t s);
 /* rows of [T][C] (row pitch ldx) -> col[b*To + t][(kx*C + c)], kernel width kw, zero padding `pad` on both ends */
-void tk_launch_im2col1d(const float* x, int B, int T, int C, int ldx, int kw, int stride, int pad, float* col, hipStream_t s);
+[[nodiscard]] bool tk_launch_im2col1d(const float* x, int B, int T, int C, int ldx, int kw, int stride, int pad, float* col, hipStream_t s);
 /* out[r][:] = table[idx[r]][:] + pos[(pos0[r])][:] */
-void tk_launch_embed_rows(const float* table, const float* pos, const int32_t* idx, const int32_t* pos_idx, int rows, int D, float* out, hipStream_t s);
+[[nodiscard]] bool tk_launch_embed_rows(const float* table, const float* pos, const int32_t* idx, const int32_t* pos_idx, int rows, int D, float* out, hipStream_t s);
 void tk_launch_argmax_rows(const float* x, int rows, int cols, int ld, int32_t* out, hipStream_t s);
 /* token pick under whisper.cpp's decoding policy: arg max (temp 0) or one draw from softmax(l / temp), + the pick's log-probability under
  * that distribution per row (logprob may be null); the generator is keyed by (seed, counter0 + row) */
@@ -72,8 +81,14 @@ void tk_launch_pick_rows(const float* x, int rows, int cols, int ld, int32_t* ou
 #define TK_WH_STATE_INTS 8
 struct TkWhFilter { const uint8_t* suppress; int32_t* state; int32_t beg, eot, tid0; };
 void tk_launch_pick_rows_filtered(const float* x, int rows, int cols, int ld, int32_t* out, const TkPick& pk, const TkWhFilter& f, hipStream_t s);
-void tk_launch_layernorm(const float* x, int rows, int D, const float* w, const float* b, float eps, float* y, hipStream_t s, float* img = nullptr /* optional: also the tiled GEMM's operand image of y */);
-void tk_launch_softmax_rows(float* x, int rows, int cols, int ld, hipStream_t s);
-void tk_launch_add_rows(float* x, const float* add, int rows, int D, int add_rows, hipStream_t s);
+/* also refused: an image with D % 16 != 0 (its 16-row blocks would overlap) */
+[[nodiscard]] bool tk_launch_layernorm(const float* x, int rows, int D, const float* w, const float* b, float eps, float* y, hipStream_t s, float* img = nullptr /* optional: also the tiled GEMM's operand image of y */);
+[[nodiscard]] bool tk_launch_softmax_rows(float* x, int rows, int cols, int ld, hipStream_t s);
+/* which of the three bit-identical kernels tk_launch_softmax_rows takes — a pure host function and the launcher's own switch: one wave per row
+ * (cols <= 2048, cols and ld multiples of 4, base 16-byte aligned, rows >= 1024), one block per row out of registers (cols <= 2048), or the
+ * three-pass kernel */
+enum { TK_SOFTMAX_GENERIC = 0, TK_SOFTMAX_REG = 1, TK_SOFTMAX_WAVE = 2, TK_SOFTMAX_REFUSED = -1 };
+int tk_softmax_kernel_of(int rows, int cols, int ld, const float* base);
+[[nodiscard]] bool tk_launch_add_rows(float* x, const float* add, int rows, int D, int add_rows, hipStream_t s);
 
 #endif

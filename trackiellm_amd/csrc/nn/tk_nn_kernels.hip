@@ -956,12 +956,18 @@ __global__ __launch_bounds__(256) void k_conv_stem(const float* x, int H, int W,
     }
 }
 
+bool tk_conv_stem_ok(int B, int H, int W, int C, int ldx, int N, int k, int stride, int pad, const float* y, int ldy) {
+    if (!(N == 16 && C == 3 && k == 3) || (ldy & 3) || (((uintptr_t)y) & 15)) return false;
+    if (B < 1 || H < 1 || W < 1 || stride < 1 || pad < 0 || ldx < C || ldy < N || H + 2 * (int64_t)pad < k || W + 2 * (int64_t)pad < k) return false;
+    const int64_t total = (int64_t)B * ((H + 2 * pad - k) / stride + 1) * ((W + 2 * pad - k) / stride + 1);
+    return total > 0 && total < ((int64_t)1 << 31);
+}
+
 bool tk_launch_conv_stem(const float* x, int B, int H, int W, int C, int ldx, const float* w, const float* bias, int act, int N, int k, int stride, int pad, float* y,
                          int ldy, hipStream_t s) {
-    if (!(N == 16 && C == 3 && k == 3) || (ldy & 3) || (((uintptr_t)y) & 15)) return false;
+    if (!tk_conv_stem_ok(B, H, W, C, ldx, N, k, stride, pad, y, ldy)) return false;
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     const int64_t total = (int64_t)B * Ho * Wo;
-    if (total <= 0 || total >= ((int64_t)1 << 31)) return false;
     hipLaunchKernelGGL((k_conv_stem<16, 3, 3>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, H, W, ldx, w, bias, act, stride, pad, Ho, Wo, (uint32_t)total, y, ldy);
     return true;
 }
@@ -998,17 +1004,29 @@ __global__ void k_im2col_v4(const float* x, int H, int W, int C4, int ldx, int k
     *(float4*)(col + (int64_t)t * 4) = v;
 }
 
-void tk_launch_im2col(const float* x, int B, int H, int W, int C, int ldx, int kh, int kw, int stride, int pad, float* col, hipStream_t s) {
+int tk_im2col_kernel_of(const float* x, int B, int H, int W, int C, int ldx, int kh, int kw, int stride, int pad, const float* col) {
+    if (B < 1 || H < 1 || W < 1 || C < 1 || ldx < C || kh < 1 || kw < 1 || stride < 1 || pad < 0 || H + 2 * (int64_t)pad < kh || W + 2 * (int64_t)pad < kw)
+        return TK_IM2COL_REFUSED;
     const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
     const int64_t total = (int64_t)B * Ho * Wo * kh * kw * C;
-    if ((C & 3) == 0 && (ldx & 3) == 0 && total / 4 < ((int64_t)1 << 31) && (((uintptr_t)x | (uintptr_t)col) & 15) == 0) {
+    if ((C & 3) == 0 && (ldx & 3) == 0 && total / 4 < ((int64_t)1 << 31) && (((uintptr_t)x | (uintptr_t)col) & 15) == 0) return TK_IM2COL_V4;
+    return TK_IM2COL_ELEMENT;
+}
+
+bool tk_launch_im2col(const float* x, int B, int H, int W, int C, int ldx, int kh, int kw, int stride, int pad, float* col, hipStream_t s) {
+    const int kernel = tk_im2col_kernel_of(x, B, H, W, C, ldx, kh, kw, stride, pad, col);
+    if (kernel == TK_IM2COL_REFUSED) return false;
+    const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
+    const int64_t total = (int64_t)B * Ho * Wo * kh * kw * C;
+    if (kernel == TK_IM2COL_V4) {
         const uint32_t total4 = (uint32_t)(total / 4);
         hipLaunchKernelGGL(k_im2col_v4, dim3((total4 + 255u) / 256u), dim3(256), 0, s, x, H, W, C / 4, ldx, kh, kw, stride, pad, Ho, Wo, total4, col);
-        return;
+        return true;
     }
     int64_t blocks = (total + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(k_im2col, dim3((unsigned)blocks), dim3(256), 0, s, x, B, H, W, C, ldx, kh, kw, stride, pad, Ho, Wo, col);
+    return true;
 }
 
 /* 5x5 max pool, stride 1, pad 2 (SPPF); padding never wins (-inf) */
@@ -1027,9 +1045,15 @@ __global__ void k_maxpool5(const float* x, int B, int H, int W, int C, int ldx, 
         y[pix * ldy + c] = m;
     }
 }
-void tk_launch_maxpool5(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy, hipStream_t s) {
+/* the element-wise launchers below start one 256-thread block per 256 elements: an empty extent or more blocks than a grid holds is refused */
+static bool nn_extent_ok(int64_t total) { return total >= 1 && (total + 255) / 256 < ((int64_t)1 << 31); }
+
+bool tk_launch_maxpool5(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy, hipStream_t s) {
+    if (B < 1 || H < 1 || W < 1 || C < 1 || ldx < C || ldy < C) return false;
     const int64_t total = (int64_t)B * H * W * C;
+    if (!nn_extent_ok(total)) return false;
     hipLaunchKernelGGL(k_maxpool5, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, B, H, W, C, ldx, y, ldy);
+    return true;
 }
 
 __global__ void k_upsample2x(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy) {
@@ -1041,9 +1065,12 @@ __global__ void k_upsample2x(const float* x, int B, int H, int W, int C, int ldx
         y[pix * ldy + c] = x[(((int64_t)b * H + oy / 2) * W + ox / 2) * ldx + c];
     }
 }
-void tk_launch_upsample2x(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy, hipStream_t s) {
+bool tk_launch_upsample2x(const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy, hipStream_t s) {
+    if (B < 1 || H < 1 || W < 1 || C < 1 || ldx < C || ldy < C) return false;
     const int64_t total = (int64_t)B * 4 * H * W * C;
+    if (!nn_extent_ok(total)) return false;
     hipLaunchKernelGGL(k_upsample2x, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, B, H, W, C, ldx, y, ldy);
+    return true;
 }
 
 __global__ void k_copy_cols(const float* x, int64_t rows, int C, int ldx, float* y, int ldy) {
@@ -1051,9 +1078,12 @@ __global__ void k_copy_cols(const float* x, int64_t rows, int C, int ldx, float*
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
         y[(i / C) * ldy + (i % C)] = x[(i / C) * ldx + (i % C)];
 }
-void tk_launch_copy_cols(const float* x, int rows, int C, int ldx, float* y, int ldy, hipStream_t s) {
+bool tk_launch_copy_cols(const float* x, int rows, int C, int ldx, float* y, int ldy, hipStream_t s) {
+    if (rows < 1 || C < 1 || ldx < C || ldy < C) return false;
     const int64_t total = (int64_t)rows * C;
+    if (!nn_extent_ok(total)) return false;
     hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, (int64_t)rows, C, ldx, y, ldy);
+    return true;
 }
 
 __device__ __forceinline__ float nn_block_sum256(float v, float* red) {
@@ -1086,8 +1116,12 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* x, int D, const 
         if (ir) ir[(int64_t)(i >> 4) * 256 + (i & 3) * 64 + ((i & 15) >> 2)] = v;
     }
 }
-void tk_launch_layernorm(const float* x, int rows, int D, const float* w, const float* b, float eps, float* y, hipStream_t s, float* img) {
+/* false (nothing launched): no rows or columns, or an image asked for rows that are not whole 16-column blocks (the image's [j] index is k / 16:
+ * with D % 16 != 0 consecutive 16-row blocks would overlap) */
+bool tk_launch_layernorm(const float* x, int rows, int D, const float* w, const float* b, float eps, float* y, hipStream_t s, float* img) {
+    if (rows < 1 || D < 1 || (img && (D & 15))) return false;
     hipLaunchKernelGGL(k_layernorm, dim3(rows), dim3(256), 0, s, x, D, w, b, eps, y, img);
+    return true;
 }
 
 /* in-place row softmax over the first `cols` entries of every row (row pitch ld) */
@@ -1182,11 +1216,19 @@ __global__ __launch_bounds__(256) void k_softmax_rows_wave(float* x, int64_t row
     }
 }
 
-void tk_launch_softmax_rows(float* x, int rows, int cols, int ld, hipStream_t s) {
-    if (cols <= 2048 && (cols & 3) == 0 && (ld & 3) == 0 && (((uintptr_t)x) & 15) == 0 && rows >= 1024)
-        hipLaunchKernelGGL(k_softmax_rows_wave, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, (int64_t)rows, cols, ld);
-    else if (cols <= 2048) hipLaunchKernelGGL(k_softmax_rows_reg, dim3(rows), dim3(256), 0, s, x, cols, ld);
-    else hipLaunchKernelGGL(k_softmax_rows, dim3(rows), dim3(256), 0, s, x, cols, ld);
+int tk_softmax_kernel_of(int rows, int cols, int ld, const float* base) {
+    if (rows < 1 || cols < 1 || ld < cols) return TK_SOFTMAX_REFUSED;
+    if (cols <= 2048 && (cols & 3) == 0 && (ld & 3) == 0 && (((uintptr_t)base) & 15) == 0 && rows >= 1024) return TK_SOFTMAX_WAVE;
+    return cols <= 2048 ? TK_SOFTMAX_REG : TK_SOFTMAX_GENERIC;
+}
+
+bool tk_launch_softmax_rows(float* x, int rows, int cols, int ld, hipStream_t s) {
+    switch (tk_softmax_kernel_of(rows, cols, ld, x)) {
+    case TK_SOFTMAX_WAVE: hipLaunchKernelGGL(k_softmax_rows_wave, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, (int64_t)rows, cols, ld); return true;
+    case TK_SOFTMAX_REG: hipLaunchKernelGGL(k_softmax_rows_reg, dim3(rows), dim3(256), 0, s, x, cols, ld); return true;
+    case TK_SOFTMAX_GENERIC: hipLaunchKernelGGL(k_softmax_rows, dim3(rows), dim3(256), 0, s, x, cols, ld); return true;
+    default: return false;
+    }
 }
 
 __global__ void k_add_rows(float* x, const float* add, int64_t rows, int D, int add_rows) {
@@ -1196,9 +1238,12 @@ __global__ void k_add_rows(float* x, const float* add, int64_t rows, int D, int 
         x[i] = x[i] + add[(r % add_rows) * D + (i % D)];
     }
 }
-void tk_launch_add_rows(float* x, const float* add, int rows, int D, int add_rows, hipStream_t s) {
+bool tk_launch_add_rows(float* x, const float* add, int rows, int D, int add_rows, hipStream_t s) {
+    if (rows < 1 || D < 1 || add_rows < 1) return false;
     const int64_t total = (int64_t)rows * D;
+    if (!nn_extent_ok(total)) return false;
     hipLaunchKernelGGL(k_add_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, add, (int64_t)rows, D, add_rows);
+    return true;
 }
 
 __global__ void k_im2col1d(const float* x, int B, int T, int C, int ldx, int kw, int stride, int pad, int To, float* col) {
@@ -1213,12 +1258,14 @@ __global__ void k_im2col1d(const float* x, int B, int T, int C, int ldx, int kw,
         col[i] = (it >= 0 && it < T) ? x[((int64_t)b * T + it) * ldx + c] : 0.0f;
     }
 }
-void tk_launch_im2col1d(const float* x, int B, int T, int C, int ldx, int kw, int stride, int pad, float* col, hipStream_t s) {
+bool tk_launch_im2col1d(const float* x, int B, int T, int C, int ldx, int kw, int stride, int pad, float* col, hipStream_t s) {
+    if (B < 1 || T < 1 || C < 1 || ldx < C || kw < 1 || stride < 1 || pad < 0 || T + 2 * (int64_t)pad < kw) return false;
     const int To = (T + 2 * pad - kw) / stride + 1;
     const int64_t total = (int64_t)B * To * kw * C;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(k_im2col1d, dim3((unsigned)blocks), dim3(256), 0, s, x, B, T, C, ldx, kw, stride, pad, To, col);
+    return true;
 }
 
 __global__ void k_embed_rows(const float* table, const float* pos, const int32_t* idx, const int32_t* pos_idx, int D, float* out) {
@@ -1227,8 +1274,10 @@ __global__ void k_embed_rows(const float* table, const float* pos, const int32_t
     const float* p = pos + (int64_t)pos_idx[r] * D;
     for (int i = threadIdx.x; i < D; i += blockDim.x) out[(int64_t)r * D + i] = t[i] + p[i];
 }
-void tk_launch_embed_rows(const float* table, const float* pos, const int32_t* idx, const int32_t* pos_idx, int rows, int D, float* out, hipStream_t s) {
+bool tk_launch_embed_rows(const float* table, const float* pos, const int32_t* idx, const int32_t* pos_idx, int rows, int D, float* out, hipStream_t s) {
+    if (rows < 1 || D < 1) return false;
     hipLaunchKernelGGL(k_embed_rows, dim3(rows), dim3(128), 0, s, table, pos, idx, pos_idx, D, out);
+    return true;
 }
 
 /* first index of the row maximum */

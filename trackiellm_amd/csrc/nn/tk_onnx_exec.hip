@@ -1166,7 +1166,7 @@ bool TkOnnxExec::exec_image_op(const TkOnnxNode& nd, std::map<std::string, Val>&
             if (!y) return false;
             if (xc.count() == 0) return true;
             hipLaunchKernelGGL(k_oe_copy, grid_for(xc.count()), dim3(128), 0, stream_, xc.d, y->d, xc.count());
-            tk_launch_softmax_rows(y->d, (int)(xc.count() / cols), (int)cols, (int)cols, stream_);
+            if (!tk_launch_softmax_rows(y->d, (int)(xc.count() / cols), (int)cols, (int)cols, stream_)) { error = "Softmax: row geometry outside what the row kernels take"; return false; }
             return true;
         }
         if (ax != r - 1) { /* an inner axis (the DFL of a YOLO head: [1, 16, 4, anchors] over axis 1): one thread per (outer, inner) pair walks the axis in index order */
@@ -1182,7 +1182,7 @@ bool TkOnnxExec::exec_image_op(const TkOnnxNode& nd, std::map<std::string, Val>&
         if (!y) return false;
         const int cols = (int)xc.shape.back();
         hipLaunchKernelGGL(k_oe_copy, grid_for(xc.count()), dim3(128), 0, stream_, xc.d, y->d, xc.count());
-        tk_launch_softmax_rows(y->d, (int)(xc.count() / cols), cols, cols, stream_);
+        if (xc.count() > 0 && !tk_launch_softmax_rows(y->d, (int)(xc.count() / cols), cols, cols, stream_)) { error = "Softmax: row geometry outside what the row kernels take"; return false; }
         return true;
     }
     *handled = false;

@@ -531,7 +531,10 @@ bool TkOnnxExec::exec_seq_op(const TkOnnxNode& nd, std::map<std::string, Val>& v
         }
         Val* y = out_f(0, xc.shape);
         if (!y) return false;
-        if (xc.count() > 0) tk_launch_layernorm(xc.d, (int)(xc.count() / D), D, scc.d, bias, nd.af("epsilon", 1e-5f), y->d, stream_);
+        if (xc.count() > 0 && !tk_launch_layernorm(xc.d, (int)(xc.count() / D), D, scc.d, bias, nd.af("epsilon", 1e-5f), y->d, stream_)) {
+            error = "LayerNormalization: row geometry outside what the row kernel takes";
+            return false;
+        }
         return true;
     }
     if (op == "ReduceSum" || op == "ReduceL2" || op == "ReduceMax" || op == "ReduceMin") {

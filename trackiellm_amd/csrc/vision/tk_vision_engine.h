@@ -34,6 +34,14 @@ struct TkDetection {
     int32_t cls, anchor;
 };
 
+/* detector post-processing, one launcher per step (tk_vision_engine.hip); false: nothing launched (an empty extent, a batch above 65535,
+ * heads that do not add up to n_anchors or are narrower than 64 + nc).  cand [B][n_anchors]; order [B][TK_YOLO_MAX_CAND]; n_cand [B];
+ * mask [B][TK_YOLO_MAX_CAND][TK_YOLO_MAX_CAND / 64]; kept [B][TK_OBJECT_DETECTOR_MAX_DETECTIONS]; n_kept [B] */
+bool tk_launch_yolo_decode(const TkT heads[3], int B, int nc, int n_anchors, float conf, tk_yolo_cand_t* cand, hipStream_t s);
+bool tk_launch_yolo_decode_out(const float* out, int nc, int n_anchors, float conf, tk_yolo_cand_t* cand, hipStream_t s); /* one frame */
+bool tk_launch_yolo_post(const tk_yolo_cand_t* cand, int n_anchors, int B, float iou, int32_t* order, int32_t* n_cand, uint64_t* mask, TkDetection* kept,
+                         int32_t* n_kept, hipStream_t s);
+
 class TkYoloModel {
 public:
     int device = 0, nc = TK_YOLO_NC;

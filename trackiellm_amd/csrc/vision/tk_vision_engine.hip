@@ -202,6 +202,7 @@ bool TkYoloModel::load_onnx(const char* path) {
 struct TkGpuOps {
     TkDetector* d;
     hipStream_t s;
+    bool refused = false; /* a launcher turned its geometry down (nothing launched): enqueue reports it */
     TkT alloc(int B, int H, int W, int C) {
         TkT t;
         t.B = B; t.H = H; t.W = W; t.C = C; t.ld = C;
@@ -223,7 +224,7 @@ struct TkGpuOps {
                                                sp.s, sp.k / 2, y.p, y.ld, s)) {
             return; /* the 3-channel stem: a direct kernel, the GEMM's chain */
         } else {
-            tk_launch_im2col(x.p, x.B, x.H, x.W, x.C, x.ld, sp.k, sp.k, sp.s, sp.k / 2, d->col, s);
+            if (!tk_launch_im2col(x.p, x.B, x.H, x.W, x.C, x.ld, sp.k, sp.k, sp.s, sp.k / 2, d->col, s)) refused = true;
             g.A = d->col; g.lda = g.K;
         }
         g.B = d->model->w[idx]; g.ldb = g.K; g.b_kn = 0;
@@ -233,11 +234,11 @@ struct TkGpuOps {
         g.act = sp.act ? TK_ACT_SILU : TK_ACT_NONE;
         g.alpha = 1.0f; g.batch = 1;
         g.fast = d->fast ? 1 : 0;
-        tk_launch_gemm(g, s);
+        if (!tk_launch_gemm(g, s)) refused = true;
     }
-    void maxpool5(const TkT& x, const TkT& y) { tk_launch_maxpool5(x.p, x.B, x.H, x.W, x.C, x.ld, y.p, y.ld, s); }
-    void upsample2x(const TkT& x, const TkT& y) { tk_launch_upsample2x(x.p, x.B, x.H, x.W, x.C, x.ld, y.p, y.ld, s); }
-    void copy(const TkT& x, const TkT& y) { tk_launch_copy_cols(x.p, x.B * x.H * x.W, x.C, x.ld, y.p, y.ld, s); }
+    void maxpool5(const TkT& x, const TkT& y) { if (!tk_launch_maxpool5(x.p, x.B, x.H, x.W, x.C, x.ld, y.p, y.ld, s)) refused = true; }
+    void upsample2x(const TkT& x, const TkT& y) { if (!tk_launch_upsample2x(x.p, x.B, x.H, x.W, x.C, x.ld, y.p, y.ld, s)) refused = true; }
+    void copy(const TkT& x, const TkT& y) { if (!tk_launch_copy_cols(x.p, x.B * x.H * x.W, x.C, x.ld, y.p, y.ld, s)) refused = true; }
 };
 
 /* sizing pass: same graph, counts arena floats and the largest im2col matrix */
@@ -378,6 +379,37 @@ __global__ void k_yolo_scan(const tk_yolo_cand_t* cand, int n_anchors, const int
     if (lane == 0) n_kept[b] = nk;
 }
 
+/* the launchers every caller goes through (TkDetector::enqueue, forward_graph, the test hook tk_mi355x_detector_post_probe).  false: nothing
+ * launched — an empty extent, a batch the grid cannot hold, or (decode) heads that do not add up to n_anchors / are narrower than 64 + nc */
+bool tk_launch_yolo_decode(const TkT heads[3], int B, int nc, int n_anchors, float conf, tk_yolo_cand_t* cand, hipStream_t s) {
+    if (B < 1 || B > 65535 || nc < 1 || n_anchors < 1) return false;
+    int64_t total = 0;
+    for (int i = 0; i < 3; ++i) {
+        if (heads[i].H < 1 || heads[i].W < 1 || heads[i].ld < 64 + nc) return false;
+        total += (int64_t)heads[i].H * heads[i].W;
+    }
+    if (total != n_anchors) return false;
+    hipLaunchKernelGGL(k_yolo_decode, dim3((n_anchors + 255) / 256, B), dim3(256), 0, s, heads[0], heads[1], heads[2], nc, n_anchors, conf, cand);
+    return true;
+}
+
+bool tk_launch_yolo_decode_out(const float* out, int nc, int n_anchors, float conf, tk_yolo_cand_t* cand, hipStream_t s) {
+    if (nc < 1 || n_anchors < 1) return false;
+    hipLaunchKernelGGL(k_yolo_decode_out, dim3((n_anchors + 255) / 256), dim3(256), 0, s, out, nc, n_anchors, conf, cand);
+    return true;
+}
+
+/* rank, suppression matrix, greedy scan of B frames' decoded candidates.  order, mask and kept are written up to n_cand / n_kept of THIS call only
+ * and every read of them is bounded by the same counts, so whatever an earlier call left beyond is never looked at. */
+bool tk_launch_yolo_post(const tk_yolo_cand_t* cand, int n_anchors, int B, float iou, int32_t* order, int32_t* n_cand, uint64_t* mask, TkDetection* kept,
+                         int32_t* n_kept, hipStream_t s) {
+    if (B < 1 || B > 65535 || n_anchors < 1) return false;
+    hipLaunchKernelGGL(k_yolo_rank, dim3((n_anchors + 255) / 256, B), dim3(256), 0, s, cand, n_anchors, order, n_cand);
+    hipLaunchKernelGGL(k_yolo_mask, dim3(TK_YOLO_MAX_CAND / 64 / 8, TK_YOLO_MAX_CAND / 8, B), dim3(8, 8), 0, s, cand, n_anchors, order, n_cand, iou, mask);
+    hipLaunchKernelGGL(k_yolo_scan, dim3(B), dim3(64), 0, s, cand, n_anchors, order, n_cand, mask, kept, n_kept);
+    return true;
+}
+
 /* ------------------------------------------------------------------------------------------ detector */
 
 TkDetector::~TkDetector() {
@@ -443,7 +475,7 @@ bool TkDetector::run_graph(int B, float* host_out) {
                     std::to_string(in_w) + " x " + std::to_string(in_h) + " at strides 8 / 16 / 32)";
             return false;
         }
-        hipLaunchKernelGGL(k_yolo_decode_out, dim3((n_anchors + 255) / 256), dim3(256), 0, stream, o->d, model->nc, n_anchors, conf, cand + (size_t)b * n_anchors);
+        if (!tk_launch_yolo_decode_out(o->d, model->nc, n_anchors, conf, cand + (size_t)b * n_anchors, stream)) { error = "detector decode refused its geometry"; return false; }
         if (host_out) HIPQ(hipMemcpyAsync(host_out + (size_t)b * o->count(), o->d, (size_t)o->count() * 4, hipMemcpyDeviceToHost, stream)); /* before the next run reuses the arena */
     }
     return true;
@@ -457,9 +489,7 @@ bool TkDetector::forward_graph(int B, const float* nchw_host, std::vector<float>
     out->assign((size_t)B * (4 + model->nc) * n_anchors, 0.0f);
     last_B = 0;
     if (!run_graph(B, out->data())) return false;
-    hipLaunchKernelGGL(k_yolo_rank, dim3((n_anchors + 255) / 256, B), dim3(256), 0, stream, cand, n_anchors, order, n_cand);
-    hipLaunchKernelGGL(k_yolo_mask, dim3(TK_YOLO_MAX_CAND / 64 / 8, TK_YOLO_MAX_CAND / 8, B), dim3(8, 8), 0, stream, cand, n_anchors, order, n_cand, iou, mask);
-    hipLaunchKernelGGL(k_yolo_scan, dim3(B), dim3(64), 0, stream, cand, n_anchors, order, n_cand, mask, kept, n_kept);
+    if (!tk_launch_yolo_post(cand, n_anchors, B, iou, order, n_cand, mask, kept, n_kept, stream)) { error = "detector post-processing refused its geometry"; return false; }
     HIPQ(hipGetLastError());
     HIPQ(hipStreamSynchronize(stream));
     return true;
@@ -468,9 +498,7 @@ bool TkDetector::forward_graph(int B, const float* nchw_host, std::vector<float>
 bool TkDetector::enqueue(int B) {
     if (model->generic) {
         if (!run_graph(B, nullptr)) return false;
-        hipLaunchKernelGGL(k_yolo_rank, dim3((n_anchors + 255) / 256, B), dim3(256), 0, stream, cand, n_anchors, order, n_cand);
-        hipLaunchKernelGGL(k_yolo_mask, dim3(TK_YOLO_MAX_CAND / 64 / 8, TK_YOLO_MAX_CAND / 8, B), dim3(8, 8), 0, stream, cand, n_anchors, order, n_cand, iou, mask);
-        hipLaunchKernelGGL(k_yolo_scan, dim3(B), dim3(64), 0, stream, cand, n_anchors, order, n_cand, mask, kept, n_kept);
+        if (!tk_launch_yolo_post(cand, n_anchors, B, iou, order, n_cand, mask, kept, n_kept, stream)) { error = "detector post-processing refused its geometry"; return false; }
         HIPQ(hipGetLastError());
         return true;
     }
@@ -479,10 +507,9 @@ bool TkDetector::enqueue(int B) {
     TkT x;
     x.p = input; x.B = B; x.H = in_h; x.W = in_w; x.C = 3; x.ld = 3;
     TkYoloV8n<TkGpuOps>::forward(ops, x, heads, model->nc);
-    hipLaunchKernelGGL(k_yolo_decode, dim3((n_anchors + 255) / 256, B), dim3(256), 0, stream, heads[0], heads[1], heads[2], model->nc, n_anchors, conf, cand);
-    hipLaunchKernelGGL(k_yolo_rank, dim3((n_anchors + 255) / 256, B), dim3(256), 0, stream, cand, n_anchors, order, n_cand);
-    hipLaunchKernelGGL(k_yolo_mask, dim3(TK_YOLO_MAX_CAND / 64 / 8, TK_YOLO_MAX_CAND / 8, B), dim3(8, 8), 0, stream, cand, n_anchors, order, n_cand, iou, mask);
-    hipLaunchKernelGGL(k_yolo_scan, dim3(B), dim3(64), 0, stream, cand, n_anchors, order, n_cand, mask, kept, n_kept);
+    if (ops.refused) { error = "detector network: a launcher refused its geometry"; return false; }
+    if (!tk_launch_yolo_decode(heads, B, model->nc, n_anchors, conf, cand, stream)) { error = "detector decode refused its geometry"; return false; }
+    if (!tk_launch_yolo_post(cand, n_anchors, B, iou, order, n_cand, mask, kept, n_kept, stream)) { error = "detector post-processing refused its geometry"; return false; }
     HIPQ(hipGetLastError());
     return true;
 }

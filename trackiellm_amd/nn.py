@@ -1,4 +1,4 @@
-"""Perception kernels one launch at a time: the test hooks tk_mi355x_gemm_probe and tk_mi355x_attention_h3_probe."""
+"""Perception kernels one launch at a time: the test hooks tk_mi355x_gemm_probe, tk_mi355x_attention_h3_probe and tk_mi355x_nn_row_probe."""
 import ctypes as C
 
 import numpy as np
@@ -74,3 +74,46 @@ def attention_h3_probe(q, k, v, out, B, nh, Tq, Tk, d, scale, q_bstride=None, kv
     check(lib().tk_mi355x_attention_h3_probe(device, B, nh, Tq, Tk, qb, kb, d, scale, q.ctypes.data, k.ctypes.data, v.ctypes.data, q.size, k.size,
                                              res.ctypes.data))
     return res
+
+
+# tk_mi355x_nn_row_probe's ops, and the launchers' kernel codes it reports
+ROW_CONV_STEM, ROW_IM2COL, ROW_IM2COL1D, ROW_MAXPOOL5, ROW_UPSAMPLE2X, ROW_COPY_COLS, ROW_LAYERNORM, ROW_SOFTMAX_ROWS, ROW_ADD_ROWS, ROW_EMBED_ROWS, ROW_ATTEND1 = range(11)
+SOFTMAX_GENERIC, SOFTMAX_REG, SOFTMAX_WAVE = 0, 1, 2
+IM2COL_ELEMENT, IM2COL_V4 = 0, 1
+
+
+class NnRowProbe(C.Structure):  # tk_mi355x_nn_row_probe_t
+    _fields_ = [(n, C.c_int32) for n in ("op", "B", "H", "W", "C", "ldx", "ldy", "rows", "N", "k", "stride", "pad", "act", "add_rows", "table_rows",
+                                         "pos_rows")] + [("eps", C.c_float)] + [(n, C.c_int32) for n in ("a_offset", "y_offset", "kernel")] + \
+               [(n, C.c_void_p) for n in ("a", "b", "c", "idx", "pos_idx", "y", "img")] + \
+               [(n, C.c_int64) for n in ("n_a", "n_b", "n_c", "n_idx", "n_y", "n_img", "q_bstride", "kv_bstride")]
+
+
+def nn_row_probe(op, y, a=None, b=None, c=None, idx=None, pos_idx=None, img=None, a_offset=0, y_offset=0, device=0, **geometry):
+    """ONE launch of a row / layout launcher (tk_mi355x_nn_row_probe).  y (and img): float32 arrays with the caller's initial content; COPIES are
+    launched on and returned.  a / b / c: float32 inputs, idx / pos_idx: int32, as the header's table assigns them per op; geometry: the
+    struct's integer fields (B, H, W, C, ldx, ldy, rows, N, k, stride, pad, act, add_rows, table_rows, pos_rows, q_bstride, kv_bstride) and eps.
+    device < 0: validation and the launcher's kernel code only.  Returns (y, img or None, kernel code)."""
+    a, b, c = _flat(a, np.float32), _flat(b, np.float32), _flat(c, np.float32)
+    idx, pos_idx = _flat(idx, np.int32), _flat(pos_idx, np.int32)
+    out = np.array(y, dtype=np.float32, order="C", copy=True)
+    image = None if img is None else np.array(img, dtype=np.float32, order="C", copy=True)
+    p = NnRowProbe()
+    p.op, p.a_offset, p.y_offset = op, a_offset, y_offset
+    for name, value in geometry.items():
+        if name not in dict(NnRowProbe._fields_) or name in ("op", "kernel", "a_offset", "y_offset") or name.startswith("n_"):
+            raise TypeError("nn_row_probe: no geometry field %r" % name)
+        setattr(p, name, value)
+    if idx is not None and pos_idx is not None and idx.size != pos_idx.size:
+        raise ValueError("nn_row_probe: idx and pos_idx must have the same length")
+    for name, arr in (("a", a), ("b", b), ("c", c), ("y", out), ("img", image)):
+        if arr is not None:
+            setattr(p, name, arr.ctypes.data)
+            setattr(p, "n_" + name, arr.size)
+    if idx is not None:
+        p.idx, p.n_idx = idx.ctypes.data, idx.size
+    if pos_idx is not None:
+        p.pos_idx = pos_idx.ctypes.data
+    lib().tk_mi355x_nn_row_probe.argtypes = [C.c_int, C.POINTER(NnRowProbe)]
+    check(lib().tk_mi355x_nn_row_probe(device, C.byref(p)))
+    return out, image, int(p.kernel)

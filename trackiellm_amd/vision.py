@@ -387,3 +387,53 @@ def onnx_run(path, feeds, outputs, device=0):
         return got
     finally:
         L.tk_mi355x_onnx_result_free(C.byref(res))
+
+
+# ---- detector post-processing one sequence at a time: the test hook tk_mi355x_detector_post_probe ----
+
+YOLO_MAX_CAND, YOLO_MAX_DET = 2048, 500
+BOX_DTYPE = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("score", "<f4"), ("cls", "<i4"), ("anchor", "<i4")])  # tk_mi355x_box_t
+
+
+class DetectorPostProbe(C.Structure):  # tk_mi355x_detector_post_probe_t
+    _fields_ = [(n, C.c_int32) for n in ("kind", "B", "nc", "n_anchors", "in_w", "in_h")] + [("ld", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("conf", C.c_float), ("iou", C.c_float), ("head", C.c_void_p * 3), ("n_head", C.c_int64 * 3), ("out", C.c_void_p), ("n_out", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("cand", "order", "n_cand", "mask", "kept", "n_kept")] + \
+               [(n, C.c_int64) for n in ("cand_count", "order_count", "n_cand_count", "mask_count", "kept_count", "n_kept_count")]
+
+
+def detector_post_probe(B, nc, n_anchors, conf, iou, heads=None, ld=None, in_w=0, in_h=0, out=None, with_mask=True, stale=0xFF, device=0, sizes=None):
+    """ONE decode + rank + mask + scan sequence (tk_mi355x_detector_post_probe).  heads: three float32 arrays [B][H_i W_i][ld[i]] (kind 0, with in_w /
+    in_h) or out: [B][4 + nc][n_anchors] (kind 1).  The six in/out arrays start filled with `stale` bytes — the buffers of an earlier call — and come
+    back whole in a dict: cand [B][n_anchors] and kept [B][500] (BOX_DTYPE), order [B][2048], n_cand [B], mask [B][2048][32] uint64 (None without
+    with_mask), n_kept [B].  sizes: overrides of the arrays' element counts by name (to ask for a refusal).  device < 0: validation only."""
+    sizes = dict(sizes or {})
+    want = dict(cand=B * n_anchors, order=B * YOLO_MAX_CAND, n_cand=B, mask=B * YOLO_MAX_CAND * (YOLO_MAX_CAND // 64), kept=B * YOLO_MAX_DET, n_kept=B)
+    dtypes = dict(cand=BOX_DTYPE, order=np.int32, n_cand=np.int32, mask=np.uint64, kept=BOX_DTYPE, n_kept=np.int32)
+    io = {}
+    for name in want:
+        if name == "mask" and not with_mask:
+            io[name] = None
+            continue
+        n = max(int(sizes.get(name, want[name])), 0)
+        io[name] = np.frombuffer(bytes([stale]) * (n * np.dtype(dtypes[name]).itemsize), dtype=dtypes[name]).copy()
+    p = DetectorPostProbe()
+    p.kind, p.B, p.nc, p.n_anchors, p.in_w, p.in_h, p.conf, p.iou = (0 if heads is not None else 1), B, nc, n_anchors, in_w, in_h, conf, iou
+    keep = []
+    if heads is not None:
+        for i in range(3):
+            h = np.ascontiguousarray(heads[i], np.float32).reshape(-1)
+            keep.append(h)
+            p.head[i], p.n_head[i], p.ld[i] = h.ctypes.data, h.size, ld[i]
+    if out is not None:
+        o = np.ascontiguousarray(out, np.float32).reshape(-1)
+        keep.append(o)
+        p.out, p.n_out = o.ctypes.data, o.size
+    for name, arr in io.items():
+        if arr is not None:
+            setattr(p, name, arr.ctypes.data)
+            setattr(p, name + "_count", arr.size)
+    lib().tk_mi355x_detector_post_probe.argtypes = [C.c_int, C.POINTER(DetectorPostProbe)]
+    check(lib().tk_mi355x_detector_post_probe(device, C.byref(p)))
+    shapes = dict(cand=(B, n_anchors), order=(B, YOLO_MAX_CAND), n_cand=(B,), mask=(B, YOLO_MAX_CAND, YOLO_MAX_CAND // 64), kept=(B, YOLO_MAX_DET), n_kept=(B,))
+    return {k: (None if v is None else v.reshape(shapes[k]) if v.size == want[k] else v) for k, v in io.items()}
