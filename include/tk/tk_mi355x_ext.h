@@ -81,6 +81,12 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_fill_synthetic_type(tk_m
  * the production launcher runs at width nrows with K split ks ways, and the ks partial sums are added in ascending order into y [nrows][rows] */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, int ks, int nrows,
                                                              const float* x, float* y);
+/* test entry: the repack alone.  `rows` x K raw GGUF blocks of `type` (the types of tk_mi355x_llm_gemv_probe; rows % 16 == 0, K % 256 == 0,
+ * K <= 65536, rows x K <= 2^26) -> tiles [rows / 16][K / 256][the type's tile bytes], the resident layout the W4A8 kernels read (an IQ4_NL
+ * matrix gives the Q4_0 tiles of the same bytes, a TQ1_0 matrix TQ2_0 tiles).  device >= 0: the load-time repack kernel on that device;
+ * device < 0: the same per-lane function in a host loop, no GPU touched.  The arguments are checked before any device is: a null pointer, another type
+ * or another shape is TK_ERROR_INVALID_ARGUMENT */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_repack_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, void* tiles);
 /* no GPU: the build's own one-pass block quantisers (csrc/common/tk_ggml_blocks.h) on the host.  x [n_blocks][256] floats -> n_blocks GGUF
  * blocks of `type` (11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K) in out; the same code the synthetic-weight kernel runs on the device.  Type 8
  * (Q8_0): n_blocks counts 32-weight blocks, x [n_blocks][32] -> n_blocks 34-byte blocks, ggml's quantize_row_q8_0_ref value for value */

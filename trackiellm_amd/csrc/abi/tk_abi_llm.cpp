@@ -89,6 +89,15 @@ static void default_plan(tk_mi355x_llm_hparams_t* h) {
     h->ks_out = 1;
 }
 
+/* the host quantiser entries' one loop: x [n_blocks][the type's weights per block] -> n_blocks blocks (n_blocks counts the type's own blocks: 32 weights
+ * for Q8_0, 256 for the k-quants) */
+template <int T> static tk_error_code_t quantize_blocks_of(const float* x, int64_t n_blocks, void* out) {
+    typedef TkBlock<T> B;
+    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
+    for (int64_t b = 0; b < n_blocks; ++b) B::quantize(x + B::elems * b, (typename B::block*)out + b);
+    return TK_SUCCESS;
+}
+
 extern "C" {
 
 tk_error_code_t tk_mi355x_llm_model_create(tk_mi355x_llm_model_t** out, const tk_mi355x_llm_hparams_t* hp, int device) {
@@ -119,74 +128,30 @@ tk_error_code_t tk_mi355x_llm_gemv_probe(int device, int type, const void* block
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_llm_repack_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, void* tiles) {
+    if (!blocks || !tiles) return TK_ERROR_INVALID_ARGUMENT;
+    std::string err;
+    if (!tk_llm_repack_probe(device, type, blocks, rows, K, tiles, err))
+        return fail(err.find("device") != std::string::npos ? TK_ERROR_GPU_ROCM_ERROR : TK_ERROR_INVALID_ARGUMENT, err);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_quantize_blocks(int type, const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0 || !tk_type_desc_of(type).host_quantize) return TK_ERROR_INVALID_ARGUMENT;
-    for (int64_t b = 0; b < n_blocks; ++b) {
-        const float* xb = x + tk_type_block_elems(type) * b; /* n_blocks counts the type's own blocks: 32 weights for Q8_0, 256 for the k-quants */
-        switch (type) {
-            case TK_TYPE_Q8_0: tk_quantize_q8_0(xb, (tk_block_q8_0*)out + b); break;
-            case TK_TYPE_Q3_K: tk_quantize_q3_K(xb, (tk_block_q3_K*)out + b); break;
-            case TK_TYPE_Q4_K: tk_quantize_q4_K(xb, (tk_block_q4_K*)out + b); break;
-            case TK_TYPE_Q5_K: tk_quantize_q5_K(xb, (tk_block_q5_K*)out + b); break;
-            default: tk_quantize_q6_K(xb, (tk_block_q6_K*)out + b); break;
-        }
-    }
-    return TK_SUCCESS;
+    if (!tk_type_desc_of(type).host_quantize) return TK_ERROR_INVALID_ARGUMENT; /* a pinned set: every other type has an entry of its own below */
+    tk_error_code_t rc = TK_ERROR_INVALID_ARGUMENT;
+    tk_type_dispatch(type, [&](auto trait) { rc = quantize_blocks_of<decltype(trait)::type>(x, n_blocks, out); });
+    return rc;
 }
 
-tk_error_code_t tk_mi355x_quantize_blocks_q2k(const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
-    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_q2_K(x + 256 * b, (tk_block_q2_K*)out + b);
-    return TK_SUCCESS;
-}
-
-tk_error_code_t tk_mi355x_quantize_blocks_q4_0(const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
-    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_q4_0(x + 32 * b, (tk_block_q4_0*)out + b);
-    return TK_SUCCESS;
-}
-
-tk_error_code_t tk_mi355x_quantize_blocks_q5_0(const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
-    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_q5_0(x + 32 * b, (tk_block_q5_0*)out + b);
-    return TK_SUCCESS;
-}
-
-tk_error_code_t tk_mi355x_quantize_blocks_q4_1(const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
-    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_q4_1(x + 32 * b, (tk_block_q4_1*)out + b);
-    return TK_SUCCESS;
-}
-
-tk_error_code_t tk_mi355x_quantize_blocks_q5_1(const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
-    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_q5_1(x + 32 * b, (tk_block_q5_1*)out + b);
-    return TK_SUCCESS;
-}
-
-tk_error_code_t tk_mi355x_quantize_blocks_iq4_nl(const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
-    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_iq4_nl(x + 32 * b, (tk_block_iq4_nl*)out + b);
-    return TK_SUCCESS;
-}
-
-tk_error_code_t tk_mi355x_quantize_blocks_iq4_xs(const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
-    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_iq4_xs(x + 256 * b, (tk_block_iq4_xs*)out + b);
-    return TK_SUCCESS;
-}
-
-tk_error_code_t tk_mi355x_quantize_blocks_tq1_0(const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
-    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_tq1_0(x + 256 * b, (tk_block_tq1_0*)out + b);
-    return TK_SUCCESS;
-}
-
-tk_error_code_t tk_mi355x_quantize_blocks_tq2_0(const float* x, int64_t n_blocks, void* out) {
-    if (!x || !out || n_blocks < 0) return TK_ERROR_INVALID_ARGUMENT;
-    for (int64_t b = 0; b < n_blocks; ++b) tk_quantize_tq2_0(x + 256 * b, (tk_block_tq2_0*)out + b);
-    return TK_SUCCESS;
-}
+tk_error_code_t tk_mi355x_quantize_blocks_q2k(const float* x, int64_t n_blocks, void* out) { return quantize_blocks_of<TK_TYPE_Q2_K>(x, n_blocks, out); }
+tk_error_code_t tk_mi355x_quantize_blocks_q4_0(const float* x, int64_t n_blocks, void* out) { return quantize_blocks_of<TK_TYPE_Q4_0>(x, n_blocks, out); }
+tk_error_code_t tk_mi355x_quantize_blocks_q5_0(const float* x, int64_t n_blocks, void* out) { return quantize_blocks_of<TK_TYPE_Q5_0>(x, n_blocks, out); }
+tk_error_code_t tk_mi355x_quantize_blocks_q4_1(const float* x, int64_t n_blocks, void* out) { return quantize_blocks_of<TK_TYPE_Q4_1>(x, n_blocks, out); }
+tk_error_code_t tk_mi355x_quantize_blocks_q5_1(const float* x, int64_t n_blocks, void* out) { return quantize_blocks_of<TK_TYPE_Q5_1>(x, n_blocks, out); }
+tk_error_code_t tk_mi355x_quantize_blocks_iq4_nl(const float* x, int64_t n_blocks, void* out) { return quantize_blocks_of<TK_TYPE_IQ4_NL>(x, n_blocks, out); }
+tk_error_code_t tk_mi355x_quantize_blocks_iq4_xs(const float* x, int64_t n_blocks, void* out) { return quantize_blocks_of<TK_TYPE_IQ4_XS>(x, n_blocks, out); }
+tk_error_code_t tk_mi355x_quantize_blocks_tq1_0(const float* x, int64_t n_blocks, void* out) { return quantize_blocks_of<TK_TYPE_TQ1_0>(x, n_blocks, out); }
+tk_error_code_t tk_mi355x_quantize_blocks_tq2_0(const float* x, int64_t n_blocks, void* out) { return quantize_blocks_of<TK_TYPE_TQ2_0>(x, n_blocks, out); }
 
 tk_error_code_t tk_mi355x_llm_model_fill_synthetic_ftype(tk_mi355x_llm_model_t* m, uint64_t seed, int ftype) {
     if (!m || !(ftype == 2 || ftype == 8 || ftype == 7 || ftype == 10 || ftype == 11 || ftype == 12 || (ftype >= 14 && ftype <= 17) || ftype == 21 || ftype == 25 || ftype == 30 || ftype == 36 || ftype == 37)) return TK_ERROR_INVALID_ARGUMENT;

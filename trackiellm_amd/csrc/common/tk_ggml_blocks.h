@@ -115,7 +115,6 @@ typedef struct {
     uint16_t d;
     int8_t qs[32];
 } tk_block_q8_0; /* 34 B, 32 weights */
-#define TK_Q8_0_PER_RUN (TK_QK_K / 32) /* Q8_0 blocks of one 256-k run = one W4A8 tile column */
 
 typedef struct {
     uint16_t d;
@@ -127,7 +126,6 @@ typedef struct {
     uint8_t qh[4]; /* one little-endian u32 */
     uint8_t qs[16];
 } tk_block_q5_0; /* 22 B, 32 weights */
-#define TK_Q32_PER_RUN (TK_QK_K / 32) /* 32-weight blocks (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, IQ4_NL) of one 256-k run */
 
 typedef struct {
     uint16_t d;
@@ -204,7 +202,7 @@ TK_HD constexpr tk_type_desc tk_type_desc_of(int type) {
         case TK_TYPE_Q6_K: return {"Q6_K", 256,  210,  TK_Q6K_TILE_BYTES, 2,   1,  true,  true,  true,  true};
         case TK_TYPE_IQ4_NL: return {"IQ4_NL", 32, 18, TK_IQ4_NL_TILE_BYTES, 256, 9, false, true, false, false};
         case TK_TYPE_IQ4_XS: return {"IQ4_XS", 256, 136, TK_IQ4_XS_TILE_BYTES, 512, 10, false, true, false, false};
-        /* TQ1_0 is installed as the TQ2_0 tile (k_repack_tq<tk_block_tq1_0> decodes the base-3 bytes once, at load): the same tile bytes, mask and
+        /* TQ1_0 is installed as the TQ2_0 tile (TkBlock<TK_TYPE_TQ1_0>::code is the decoded trit: the repack decodes the base-3 bytes once, at load): the same tile bytes, mask and
          * kernel column, so a TQ1_0 matrix runs the instantiations a TQ2_0 matrix runs and streams 66, not 54, bytes per 256 weights */
         case TK_TYPE_TQ2_0: return {"TQ2_0", 256, 66, TK_TQ2_0_TILE_BYTES, 4096, 13, false, true, false, false};
         case TK_TYPE_TQ1_0: return {"TQ1_0", 256, 54, TK_TQ2_0_TILE_BYTES, 4096, 13, false, true, false, false};
@@ -250,30 +248,6 @@ TK_HD constexpr size_t tk_types_tile_bytes(int types) {
     return 0;
 }
 
-#define TK_TYPE_ROW_CHECK(T, block, tile_per_block)                                                                                   \
-    static_assert(sizeof(block) == tk_type_desc_of(T).block_bytes, #T ": block_bytes is not the size of its block struct");         \
-    static_assert(tk_type_desc_of(T).tile_bytes == TK_TILE_ROWS * (tile_per_block), #T ": tile_bytes is not 16 x the tile's bytes per block (tk_llm_layout.h)")
-TK_TYPE_ROW_CHECK(TK_TYPE_Q8_0, tk_block_q8_0, TK_Q8_0_PER_RUN * 34); /* a tile column is one 256-k run: eight blocks per row */
-TK_TYPE_ROW_CHECK(TK_TYPE_Q4_0, tk_block_q4_0, TK_Q32_PER_RUN * 18);
-TK_TYPE_ROW_CHECK(TK_TYPE_Q5_0, tk_block_q5_0, TK_Q32_PER_RUN * 22);
-TK_TYPE_ROW_CHECK(TK_TYPE_Q4_1, tk_block_q4_1, TK_Q32_PER_RUN * 20);
-TK_TYPE_ROW_CHECK(TK_TYPE_Q5_1, tk_block_q5_1, TK_Q32_PER_RUN * 24);
-static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_Q4_1).block_elems == 0 && TK_QK_K % tk_type_desc_of(TK_TYPE_Q5_1).block_elems == 0, "Q4_1 / Q5_1: a 256-k run must be whole blocks");
-static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_Q4_0).block_elems == 0 && TK_QK_K % tk_type_desc_of(TK_TYPE_Q5_0).block_elems == 0, "Q4_0 / Q5_0: a 256-k run must be whole blocks");
-static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_Q8_0).block_elems == 0, "Q8_0: a 256-k run must be whole blocks");
-TK_TYPE_ROW_CHECK(TK_TYPE_Q2_K, tk_block_q2_K, 84);
-TK_TYPE_ROW_CHECK(TK_TYPE_Q3_K, tk_block_q3_K, 114); /* the tile holds the sixteen group scales as int8: 4 B more than the block's packed 6-bit ones */
-TK_TYPE_ROW_CHECK(TK_TYPE_Q4_K, tk_block_q4_K, 144);
-TK_TYPE_ROW_CHECK(TK_TYPE_Q5_K, tk_block_q5_K, 176);
-TK_TYPE_ROW_CHECK(TK_TYPE_Q6_K, tk_block_q6_K, 210);
-TK_TYPE_ROW_CHECK(TK_TYPE_IQ4_NL, tk_block_iq4_nl, TK_Q32_PER_RUN * 18);
-TK_TYPE_ROW_CHECK(TK_TYPE_IQ4_XS, tk_block_iq4_xs, 144); /* the tile holds the eight sub-block scales as int8 in a 16-byte row tail: 8 B more than the block */
-static_assert(TK_QK_K % tk_type_desc_of(TK_TYPE_IQ4_NL).block_elems == 0, "IQ4_NL: a 256-k run must be whole blocks");
-static_assert(sizeof(tk_block_iq4_nl) == sizeof(tk_block_q4_0) && TK_IQ4_NL_TILE_BYTES == TK_Q4_0_TILE_BYTES, "IQ4_NL rides on the Q4_0 repack, fragment and load");
-TK_TYPE_ROW_CHECK(TK_TYPE_TQ2_0, tk_block_tq2_0, 66);
-TK_TYPE_ROW_CHECK(TK_TYPE_TQ1_0, tk_block_tq1_0, 66); /* the tile is TQ2_0's: 2-bit codes, 12 B more than the block's base-3 bytes */
-static_assert(offsetof(tk_block_tq2_0, d) == 64 && offsetof(tk_block_tq1_0, qh) == 48 && offsetof(tk_block_tq1_0, d) == 52, "TQ1_0 / TQ2_0: d is the block's last field");
-#undef TK_TYPE_ROW_CHECK
 /* every tiled type is listed once and nothing else has a tile; every tile layout's mask is one bit of its own, and the kernel indices of
  * the fourteen TYPES values are 0 .. 13, each once.  A type installed as another type's tile (TQ1_0 as TQ2_0's) carries that type's mask and has its tile
  * bytes, mask and index, and the other type is listed before it */
@@ -946,6 +920,96 @@ TK_HD void tk_quantize_tq1_0(const float* x, tk_block_tq1_0* out) {
     TK_ROLLED
     for (int j = 0; j < 4; ++j) out->qh[j] = tk_tq1_0_byte(x + 240 + j, 4, 4, id);
 }
+
+/* The GGUF side of a type, described once: TkBlock<T> for every row of tk_type_desc_of.  What k_synth_blocks, k_embed, k_lora_merge, the
+ * repack (tk_repack_lane) and the host quantiser entries do per type is a member of this trait, reached from a run-time type through
+ * tk_type_dispatch, the one per-type list:
+ *   block, per_run, elems   the block struct, its count in a 256-k run and its weights.  The float types are "blocks" of one element
+ *   dequant(b, i)           weight i (0 .. elems - 1) of block b
+ *   quantize(x, out)        elems floats -> one block
+ *   code(run, k)            the tiled types: the integer the W4A8 tile stores for weight k (0 .. 255) of a run (tk_llm_layout.h).  Q6_K's is
+ *                           q ^ 32 (the 6-bit two's complement of q - 32), Q3_K's q + 4, Q8_0's the raw byte, TQ1_0's the decoded trit; an
+ *                           IQ4_NL block has the Q4_0 block's bytes, and so its codes */
+#if defined(__HIPCC__)
+#define TK_HD_MEMBER static TK_HD
+#else
+#define TK_HD_MEMBER TK_HD /* static inline already */
+#endif
+template <int T> struct TkBlock;
+#define TK_BLOCK(T, BLOCK, PER_RUN, DEQUANT, QUANTIZE, CODE)                                   \
+    template <> struct TkBlock<T> {                                                            \
+        typedef BLOCK block;                                                                   \
+        static constexpr int type = T, per_run = PER_RUN, elems = TK_QK_K / (PER_RUN);         \
+        TK_HD_MEMBER float dequant(const block* b, int i) { return DEQUANT; }                  \
+        TK_HD_MEMBER void quantize(const float* x, block* out) { QUANTIZE; }                   \
+        TK_HD_MEMBER int code(const block* run, int k) { return CODE; }                        \
+    }
+TK_BLOCK(TK_TYPE_F32, float, 256, b[i], *out = *x, 0);
+TK_BLOCK(TK_TYPE_F16, uint16_t, 256, tk_f16_to_f32(b[i]), *out = tk_f32_to_f16(*x), 0);
+TK_BLOCK(TK_TYPE_BF16, uint16_t, 256, tk_bf16_to_f32(b[i]), *out = tk_f32_to_bf16(*x), 0);
+TK_BLOCK(TK_TYPE_Q4_0, tk_block_q4_0, 8, tk_q4_0_dequant(b, i), tk_quantize_q4_0(x, out), tk_q4_0_quant(run + (k >> 5), k & 31));
+TK_BLOCK(TK_TYPE_Q4_1, tk_block_q4_1, 8, tk_q4_1_dequant(b, i), tk_quantize_q4_1(x, out), tk_q4_1_quant(run + (k >> 5), k & 31));
+TK_BLOCK(TK_TYPE_Q5_0, tk_block_q5_0, 8, tk_q5_0_dequant(b, i), tk_quantize_q5_0(x, out), tk_q5_0_quant(run + (k >> 5), k & 31));
+TK_BLOCK(TK_TYPE_Q5_1, tk_block_q5_1, 8, tk_q5_1_dequant(b, i), tk_quantize_q5_1(x, out), tk_q5_1_quant(run + (k >> 5), k & 31));
+TK_BLOCK(TK_TYPE_Q8_0, tk_block_q8_0, 8, tk_q8_0_dequant(b, i), tk_quantize_q8_0(x, out), (uint8_t)run[k >> 5].qs[k & 31]);
+TK_BLOCK(TK_TYPE_Q2_K, tk_block_q2_K, 1, tk_q2k_dequant(b, i), tk_quantize_q2_K(x, out), tk_q2k_quant(run, k));
+TK_BLOCK(TK_TYPE_Q3_K, tk_block_q3_K, 1, tk_q3k_dequant(b, i), tk_quantize_q3_K(x, out), tk_q3k_quant(run, k) + 4);
+TK_BLOCK(TK_TYPE_Q4_K, tk_block_q4_K, 1, tk_q4k_dequant(b, i), tk_quantize_q4_K(x, out), tk_q4k_quant(run, k));
+TK_BLOCK(TK_TYPE_Q5_K, tk_block_q5_K, 1, tk_q5k_dequant(b, i), tk_quantize_q5_K(x, out), tk_q5k_quant(run, k));
+TK_BLOCK(TK_TYPE_Q6_K, tk_block_q6_K, 1, tk_q6k_dequant(b, i), tk_quantize_q6_K(x, out), tk_q6k_quant(run, k) ^ 32);
+TK_BLOCK(TK_TYPE_IQ4_NL, tk_block_iq4_nl, 8, tk_iq4nl_dequant(b, i), tk_quantize_iq4_nl(x, out), tk_iq4_quant(run[k >> 5].qs, k & 31));
+TK_BLOCK(TK_TYPE_IQ4_XS, tk_block_iq4_xs, 1, tk_iq4xs_dequant(b, i), tk_quantize_iq4_xs(x, out), tk_iq4_quant(run->qs + 16 * (k >> 5), k & 31));
+TK_BLOCK(TK_TYPE_TQ1_0, tk_block_tq1_0, 1, tk_tq1_0_dequant(b, i), tk_quantize_tq1_0(x, out), tk_tq1_0_quant(run, k));
+TK_BLOCK(TK_TYPE_TQ2_0, tk_block_tq2_0, 1, tk_tq2_0_dequant(b, i), tk_quantize_tq2_0(x, out), tk_tq2_0_quant(run, k));
+#undef TK_BLOCK
+
+/* run-time type -> trait: f(TkBlock<type>{}) for a type of this build (true), nothing for any other value (false) */
+template <typename F> TK_HD constexpr bool tk_type_dispatch(int type, F&& f) {
+    switch (type) {
+#define TK_CASE(T) case T: f(TkBlock<T>{}); return true
+        TK_CASE(TK_TYPE_F32); TK_CASE(TK_TYPE_F16); TK_CASE(TK_TYPE_BF16);
+        TK_CASE(TK_TYPE_Q4_0); TK_CASE(TK_TYPE_Q4_1); TK_CASE(TK_TYPE_Q5_0); TK_CASE(TK_TYPE_Q5_1); TK_CASE(TK_TYPE_Q8_0);
+        TK_CASE(TK_TYPE_Q2_K); TK_CASE(TK_TYPE_Q3_K); TK_CASE(TK_TYPE_Q4_K); TK_CASE(TK_TYPE_Q5_K); TK_CASE(TK_TYPE_Q6_K);
+        TK_CASE(TK_TYPE_IQ4_NL); TK_CASE(TK_TYPE_IQ4_XS); TK_CASE(TK_TYPE_TQ1_0); TK_CASE(TK_TYPE_TQ2_0);
+#undef TK_CASE
+        default: return false;
+    }
+}
+/* a case for every row of tk_type_desc_of and for nothing else, and each trait agrees with its row: the block's size and its weights */
+TK_HD constexpr bool tk_type_dispatch_complete() {
+    for (int t = 0; t < 64; ++t) {
+        bool agrees = false;
+        const bool has = tk_type_dispatch(t, [&](auto b) {
+            typedef decltype(b) B;
+            agrees = B::type == t && (int)sizeof(typename B::block) == tk_type_desc_of(t).block_bytes && B::elems == tk_type_desc_of(t).block_elems &&
+                     B::elems * B::per_run == TK_QK_K; /* a 256-k run is whole blocks */
+        });
+        if (has != tk_type_known(t) || (has && !agrees)) return false;
+    }
+    return true;
+}
+static_assert(tk_type_dispatch_complete(), "tk_type_dispatch: one case per row of tk_type_desc_of, whose block_bytes and block_elems are the trait's");
+
+/* tile_bytes = 16 rows x the tile's bytes for one row's 256-k run (tk_llm_layout.h); the block sizes are held to the trait above */
+#define TK_TYPE_ROW_CHECK(T, tile_per_run) \
+    static_assert(tk_type_desc_of(T).tile_bytes == TK_TILE_ROWS * (tile_per_run), #T ": tile_bytes is not 16 x the tile's bytes per row and run (tk_llm_layout.h)")
+TK_TYPE_ROW_CHECK(TK_TYPE_Q8_0, 8 * 34); /* a tile column is one 256-k run: eight blocks per row */
+TK_TYPE_ROW_CHECK(TK_TYPE_Q4_0, 8 * 18);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q5_0, 8 * 22);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q4_1, 8 * 20);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q5_1, 8 * 24);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q2_K, 84);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q3_K, 114); /* the tile holds the sixteen group scales as int8: 4 B more than the block's packed 6-bit ones */
+TK_TYPE_ROW_CHECK(TK_TYPE_Q4_K, 144);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q5_K, 176);
+TK_TYPE_ROW_CHECK(TK_TYPE_Q6_K, 210);
+TK_TYPE_ROW_CHECK(TK_TYPE_IQ4_NL, 8 * 18);
+TK_TYPE_ROW_CHECK(TK_TYPE_IQ4_XS, 144); /* the tile holds the eight sub-block scales as int8 in a 16-byte row tail: 8 B more than the block */
+static_assert(sizeof(tk_block_iq4_nl) == sizeof(tk_block_q4_0) && TK_IQ4_NL_TILE_BYTES == TK_Q4_0_TILE_BYTES, "IQ4_NL rides on the Q4_0 repack, fragment and load");
+TK_TYPE_ROW_CHECK(TK_TYPE_TQ2_0, 66);
+TK_TYPE_ROW_CHECK(TK_TYPE_TQ1_0, 66); /* the tile is TQ2_0's: 2-bit codes, 12 B more than the block's base-3 bytes */
+static_assert(offsetof(tk_block_tq2_0, d) == 64 && offsetof(tk_block_tq1_0, qh) == 48 && offsetof(tk_block_tq1_0, d) == 52, "TQ1_0 / TQ2_0: d is the block's last field");
+#undef TK_TYPE_ROW_CHECK
 
 /* ---- seeded synthetic tensors (splitmix64, seed stated per item) ---- */
 

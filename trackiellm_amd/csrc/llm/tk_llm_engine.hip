@@ -555,6 +555,40 @@ bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, i
     return ok;
 }
 
+bool tk_llm_repack_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, void* tiles, std::string& error) {
+    if (!tk_type_is_kquant(type)) {
+        error = "repack probe: type must be " TK_KQUANT_NAMES_OR;
+        return false;
+    }
+    if (rows < 16 || rows % 16 || rows > (1 << 20) || K < 256 || K % 256 || K > 65536 || rows * K > (1LL << 26)) {
+        error = "repack probe: needs rows % 16 == 0, K % 256 == 0, K <= 65536 and rows x K <= 2^26";
+        return false;
+    }
+    if (device < 0) {
+        tk_repack_host(type, blocks, rows, K, (uint8_t*)tiles);
+        return true;
+    }
+    const size_t nrun = (size_t)rows * (size_t)(K / 256);
+    const size_t nb = nrun * (256 / tk_type_block_elems(type) * tk_type_block_bytes(type));
+    const size_t nt = nrun / TK_TILE_ROWS * (size_t)tk_type_desc_of(type).tile_bytes;
+    HIPQ(hipSetDevice(device));
+    void* db = nullptr;
+    uint8_t* dt = nullptr;
+    bool ok = hipMalloc(&db, nb) == hipSuccess && hipMalloc((void**)&dt, nt) == hipSuccess;
+    if (!ok) error = "repack probe: out of device memory";
+    if (ok) {
+        ok = hipMemcpy(db, blocks, nb, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) {
+            tk_launch_repack(type, db, rows, K, dt, nullptr);
+            ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(tiles, dt, nt, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+        if (!ok) error = "repack probe: device error";
+    }
+    if (db) (void)hipFree(db);
+    if (dt) (void)hipFree(dt);
+    return ok;
+}
+
 bool tk_llm_matmul_float_probe(int device, int type, const void* w, int64_t rows, int64_t K, int ks, int nseg, const int32_t* seg_rows, int nrows,
                                const float* x, float* y, std::string& error) {
     if (type != TK_TYPE_F16 && type != TK_TYPE_BF16 && type != TK_TYPE_F32) { error = "float matmul probe: type must be F16, BF16 or F32"; return false; }

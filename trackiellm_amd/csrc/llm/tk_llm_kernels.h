@@ -70,6 +70,7 @@ void tk_launch_synth_f32(uint64_t seed, uint64_t tensor_id, int64_t n, float* ou
 /* F16 / BF16 / F32 (one value per "block"): the sum is stored through tk_f32_to_f16 / tk_f32_to_bf16 / as it is */
 bool tk_launch_lora_merge(int type, void* blocks, int64_t rows, int64_t K, const float* A, const float* B, int r, float scale, hipStream_t s);
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s);
+void tk_repack_host(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles); /* the same tiles without a device */
 
 /* step kernels */
 void tk_launch_embed(const void* embd, int type /* a token_embd type of tk_type_desc_of */, int D, const int32_t* tok, int nrows, float* x, hipStream_t s);

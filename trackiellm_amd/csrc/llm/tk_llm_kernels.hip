@@ -33,79 +33,19 @@ typedef float v2f __attribute__((ext_vector_type(2)));
  * synthetic checkpoints (no real weights offline) — generated directly in HBM
  * ------------------------------------------------------------------------------------------ */
 __global__ void k_synth_blocks(int type, uint64_t seed, uint64_t tid, int64_t nblocks, float scale, uint8_t* out) {
-    int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; /* b counts 256-weight runs: a 32-weight type's eight blocks */
     if (b >= nblocks) return;
     float x[256];
     for (int i = 0; i < 256; ++i) x[i] = scale * tk_synth_normal(seed, tid, (uint64_t)(256 * b + i));
-    if (type == TK_TYPE_Q4_K) {
-        tk_block_q4_K blk;
-        tk_quantize_q4_K(x, &blk);
-        ((tk_block_q4_K*)out)[b] = blk;
-    } else if (type == TK_TYPE_Q5_K) {
-        tk_block_q5_K blk;
-        tk_quantize_q5_K(x, &blk);
-        ((tk_block_q5_K*)out)[b] = blk;
-    } else if (type == TK_TYPE_Q3_K) {
-        tk_block_q3_K blk;
-        tk_quantize_q3_K(x, &blk);
-        ((tk_block_q3_K*)out)[b] = blk;
-    } else if (type == TK_TYPE_Q2_K) {
-        tk_block_q2_K blk;
-        tk_quantize_q2_K(x, &blk);
-        ((tk_block_q2_K*)out)[b] = blk;
-    } else if (type == TK_TYPE_Q8_0) { /* b counts 256-weight runs here too: the run's eight 32-weight blocks */
-        for (int j = 0; j < TK_Q8_0_PER_RUN; ++j) {
-            tk_block_q8_0 blk;
-            tk_quantize_q8_0(x + 32 * j, &blk);
-            ((tk_block_q8_0*)out)[TK_Q8_0_PER_RUN * b + j] = blk;
-        }
-    } else if (type == TK_TYPE_Q4_0) {
-        for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
-            tk_block_q4_0 blk;
-            tk_quantize_q4_0(x + 32 * j, &blk);
-            ((tk_block_q4_0*)out)[TK_Q32_PER_RUN * b + j] = blk;
-        }
-    } else if (type == TK_TYPE_Q5_0) {
-        for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
-            tk_block_q5_0 blk;
-            tk_quantize_q5_0(x + 32 * j, &blk);
-            ((tk_block_q5_0*)out)[TK_Q32_PER_RUN * b + j] = blk;
-        }
-    } else if (type == TK_TYPE_Q4_1) {
-        for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
-            tk_block_q4_1 blk;
-            tk_quantize_q4_1(x + 32 * j, &blk);
-            ((tk_block_q4_1*)out)[TK_Q32_PER_RUN * b + j] = blk;
-        }
-    } else if (type == TK_TYPE_Q5_1) {
-        for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
-            tk_block_q5_1 blk;
-            tk_quantize_q5_1(x + 32 * j, &blk);
-            ((tk_block_q5_1*)out)[TK_Q32_PER_RUN * b + j] = blk;
-        }
-    } else if (type == TK_TYPE_IQ4_NL) {
-        for (int j = 0; j < TK_Q32_PER_RUN; ++j) {
-            tk_block_iq4_nl blk;
-            tk_quantize_iq4_nl(x + 32 * j, &blk);
-            ((tk_block_iq4_nl*)out)[TK_Q32_PER_RUN * b + j] = blk;
-        }
-    } else if (type == TK_TYPE_IQ4_XS) {
-        tk_block_iq4_xs blk;
-        tk_quantize_iq4_xs(x, &blk);
-        ((tk_block_iq4_xs*)out)[b] = blk;
-    } else if (type == TK_TYPE_TQ2_0) {
-        tk_block_tq2_0 blk;
-        tk_quantize_tq2_0(x, &blk);
-        ((tk_block_tq2_0*)out)[b] = blk;
-    } else if (type == TK_TYPE_TQ1_0) {
-        tk_block_tq1_0 blk;
-        tk_quantize_tq1_0(x, &blk);
-        ((tk_block_tq1_0*)out)[b] = blk;
-    } else {
-        tk_block_q6_K blk;
-        tk_quantize_q6_K(x, &blk);
-        ((tk_block_q6_K*)out)[b] = blk;
-    }
+    tk_type_dispatch(type, [&](auto trait) {
+        typedef decltype(trait) B;
+        if constexpr (tk_type_is_kquant(B::type))
+            for (int j = 0; j < B::per_run; ++j) {
+                typename B::block blk;
+                B::quantize(x + B::elems * j, &blk);
+                ((typename B::block*)out)[B::per_run * b + j] = blk;
+            }
+    });
 }
 
 __global__ void k_synth_f32(uint64_t seed, uint64_t tid, int64_t n, float* out) {
@@ -150,28 +90,24 @@ __global__ __launch_bounds__(64) void k_lora_merge(int type, void* blocks, int64
     __shared__ float x[256];
     const int64_t nblk = K / 256, b = blockIdx.x, n = b / nblk, k0 = (b % nblk) * 256;
     const int lane = threadIdx.x;
-    for (int e = lane; e < 256; e += 64) {
-        float w;
-        if (type == TK_TYPE_Q4_K) w = tk_q4k_dequant((const tk_block_q4_K*)blocks + b, e);
-        else if (type == TK_TYPE_Q6_K) w = tk_q6k_dequant((const tk_block_q6_K*)blocks + b, e);
-        else if (type == TK_TYPE_BF16) w = tk_bf16_to_f32(((const uint16_t*)blocks)[b * 256 + e]);
-        else if (type == TK_TYPE_F32) w = ((const float*)blocks)[b * 256 + e];
-        else w = tk_f16_to_f32(((const uint16_t*)blocks)[b * 256 + e]);
-        float delta = 0.0f;
-        for (int j = 0; j < r; ++j) delta = tk_fmaf(B[n * r + j], A[(int64_t)j * K + k0 + e], delta);
-        x[e] = w + scale * delta;
-    }
-    __syncthreads();
-    if (type == TK_TYPE_F16) {
-        for (int e = lane; e < 256; e += 64) ((uint16_t*)blocks)[b * 256 + e] = tk_f32_to_f16(x[e]);
-    } else if (type == TK_TYPE_BF16) {
-        for (int e = lane; e < 256; e += 64) ((uint16_t*)blocks)[b * 256 + e] = tk_f32_to_bf16(x[e]);
-    } else if (type == TK_TYPE_F32) {
-        for (int e = lane; e < 256; e += 64) ((float*)blocks)[b * 256 + e] = x[e];
-    } else if (lane == 0) {
-        if (type == TK_TYPE_Q4_K) { tk_block_q4_K blk; tk_quantize_q4_K(x, &blk); ((tk_block_q4_K*)blocks)[b] = blk; }
-        else { tk_block_q6_K blk; tk_quantize_q6_K(x, &blk); ((tk_block_q6_K*)blocks)[b] = blk; }
-    }
+    tk_type_dispatch(type, [&](auto trait) {
+        typedef decltype(trait) T;
+        if constexpr (tk_type_desc_of(T::type).lora_merge) {
+            typename T::block* run = (typename T::block*)blocks + b * T::per_run;
+            for (int e = lane; e < 256; e += 64) {
+                const float w = T::dequant(run + e / T::elems, e % T::elems);
+                float delta = 0.0f;
+                for (int j = 0; j < r; ++j) delta = tk_fmaf(B[n * r + j], A[(int64_t)j * K + k0 + e], delta);
+                x[e] = w + scale * delta;
+            }
+            __syncthreads();
+            for (int j = lane; j < T::per_run; j += 64) { /* a quantised run is one block: lane 0.  A float run is 256 elements, four a lane */
+                typename T::block blk;
+                T::quantize(x + T::elems * j, &blk);
+                run[j] = blk;
+            }
+        }
+    });
 }
 bool tk_launch_lora_merge(int type, void* blocks, int64_t rows, int64_t K, const float* A, const float* B, int r, float scale, hipStream_t s) {
     if (!tk_type_desc_of(type).lora_merge || K % 256 || rows < 1 || r < 1 || rows * (K / 256) > 0x7fffffffLL) return false;
@@ -182,353 +118,112 @@ bool tk_launch_lora_merge(int type, void* blocks, int64_t rows, int64_t K, const
 /* ------------------------------------------------------------------------------------------
  * GGUF blocks -> MFMA-fragment tiles (tk_llm_layout.h).  One wave per tile.
  * ------------------------------------------------------------------------------------------ */
-__global__ void k_repack_q4k(const tk_block_q4_K* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_q4_K* b = src + (rt * 16 + n) * nblk + blk;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q4K_TILE_BYTES;
-    for (int i = 0; i < 2; ++i) {
-        uint32_t dw[4];
-        for (int s = 0; s < 4; ++s) {
-            int k0 = 32 * (4 * i + s) + 8 * g;
-            uint32_t v = 0;
-            for (int t = 0; t < 4; ++t) v |= (uint32_t)(tk_q4k_quant(b, k0 + t) | (tk_q4k_quant(b, k0 + 4 + t) << 4)) << (8 * t);
-            dw[s] = v;
-        }
-        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
-    }
-    if (g == 0) {
-        uint32_t h[4];
-        h[0] = (uint32_t)b->d | ((uint32_t)b->dmin << 16);
-        for (int k = 0; k < 3; ++k)
-            h[1 + k] = (uint32_t)b->scales[4 * k] | ((uint32_t)b->scales[4 * k + 1] << 8) | ((uint32_t)b->scales[4 * k + 2] << 16) |
-                       ((uint32_t)b->scales[4 * k + 3] << 24);
-        *(uint4*)(tile + 2048 + n * 16) = make_uint4(h[0], h[1], h[2], h[3]);
-    }
+/* a store of the tile: one vector store on the device; the host loop (tk_repack_host) makes no claim on the caller's alignment */
+template <typename V> TK_HD void tk_tile_put(uint8_t* p, V v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *(V*)p = v;
+#else
+    __builtin_memcpy(p, &v, sizeof v);
+#endif
 }
 
-__global__ void k_repack_q6k(const tk_block_q6_K* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
+/* One lane's share of the tile of row tile rt, run blk (nblk runs a row): row n = lane & 15, k group g = lane >> 4.  Every tile is made of
+ * the same few planes over c = TkBlock<T>::code.  Operand dword o = 2 j + hh of a lane holds weights 32 j + 8 g + 4 hh .. + 3 of the run, one a
+ * byte; a plane keeps some bits of each:
+ *   nibble planes (two 1 KiB loads)  c & 15 as nibble hh of the bytes of dword j
+ *   2-bit plane (1 KiB)              c & 3 (Q6_K, after its nibbles: c >> 4) as slot o & 3 of the bytes of dword o >> 2
+ *   1-bit plane (512 B)              the bit above (Q5_K, Q5_0, Q5_1: bit 4 hh + (j & 3); Q3_K: bit o & 7) of the bytes of dword o >> 3
+ *   byte planes (four 1 KiB loads)   Q8_0: c itself, dword o
+ * then the tail: a 16-byte record per row written by lane group 0 (32 bytes by groups 0 and 1 where the blocks have an m), then, for the
+ * types whose record is all scales, the row's d.  The offsets advance past what is written and must end at the type's tile_bytes */
+template <int T>
+TK_HD void tk_repack_lane(const typename TkBlock<T>::block* src, int64_t nblk, uint8_t* tiles, int64_t rt, int64_t blk, int lane) {
+    typedef TkBlock<T> B;
+    constexpr bool q5 = T == TK_TYPE_Q5_K || T == TK_TYPE_Q5_0 || T == TK_TYPE_Q5_1, dm = T == TK_TYPE_Q4_1 || T == TK_TYPE_Q5_1;
+    constexpr bool tq = T == TK_TYPE_TQ2_0 || T == TK_TYPE_TQ1_0, byt = T == TK_TYPE_Q8_0;
+    constexpr bool two = tq || T == TK_TYPE_Q6_K || T == TK_TYPE_Q3_K || T == TK_TYPE_Q2_K, one = q5 || T == TK_TYPE_Q3_K;
+    constexpr bool nib = !byt && (!two || T == TK_TYPE_Q6_K);
+    constexpr int at_two = nib ? 2048 : 0, at_one = at_two + (two ? 1024 : 0), at_byt = at_one + (one ? 512 : 0), at_rec = at_byt + (byt ? 4096 : 0);
     const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_q6_K* b = src + (rt * 16 + n) * nblk + blk;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q6K_TILE_BYTES;
-    uint32_t hi[4] = {0, 0, 0, 0};
-    for (int i = 0; i < 2; ++i) {
-        uint32_t dw[4];
-        for (int s = 0; s < 4; ++s) {
-            int j = 4 * i + s;
-            int k0 = 32 * j + 8 * g;
-            uint32_t v = 0;
-            for (int t = 0; t < 4; ++t) {
-                int qa = (tk_q6k_quant(b, k0 + t) ^ 32);     /* 6-bit two's complement of q-32 */
-                int qb = (tk_q6k_quant(b, k0 + 4 + t) ^ 32);
-                v |= (uint32_t)((qa & 15) | ((qb & 15) << 4)) << (8 * t);
-                int u = j >> 1, e = j & 1;
-                hi[u] |= (uint32_t)(qa >> 4) << (8 * t + 2 * (2 * e));
-                hi[u] |= (uint32_t)(qb >> 4) << (8 * t + 2 * (2 * e + 1));
-            }
-            dw[s] = v;
-        }
-        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
-    }
-    *(uint4*)(tile + 2048 + lane * 16) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-    if (g == 0) {
-        uint32_t sc[4];
-        for (int k = 0; k < 4; ++k)
-            sc[k] = (uint32_t)(uint8_t)b->scales[4 * k] | ((uint32_t)(uint8_t)b->scales[4 * k + 1] << 8) |
-                    ((uint32_t)(uint8_t)b->scales[4 * k + 2] << 16) | ((uint32_t)(uint8_t)b->scales[4 * k + 3] << 24);
-        *(uint4*)(tile + 3072 + n * 16) = make_uint4(sc[0], sc[1], sc[2], sc[3]);
-        *(uint16_t*)(tile + 3328 + n * 2) = b->d;
-    }
-}
+    const typename B::block* run = src + ((rt * 16 + n) * nblk + blk) * B::per_run;
+    uint8_t* tile = tiles + (rt * nblk + blk) * tk_type_desc_of(T).tile_bytes;
 
-__global__ void k_repack_q5k(const tk_block_q5_K* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_q5_K* b = src + (rt * 16 + n) * nblk + blk;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q5K_TILE_BYTES;
-    uint32_t hb[2] = {0, 0};
-    for (int i = 0; i < 2; ++i) {
-        uint32_t dw[4];
-        for (int s = 0; s < 4; ++s) {
-            int k0 = 32 * (4 * i + s) + 8 * g;
-            uint32_t v = 0;
-            for (int t = 0; t < 4; ++t) {
-                const int qa = tk_q5k_quant(b, k0 + t), qb = tk_q5k_quant(b, k0 + 4 + t);
-                v |= (uint32_t)((qa & 15) | ((qb & 15) << 4)) << (8 * t);
-                hb[i] |= (uint32_t)(qa >> 4) << (8 * t + s);
-                hb[i] |= (uint32_t)(qb >> 4) << (8 * t + 4 + s);
-            }
-            dw[s] = v;
-        }
-        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
-    }
-    *(uint2*)(tile + 2048 + lane * 8) = make_uint2(hb[0], hb[1]);
-    if (g == 0) {
-        uint32_t h[4];
-        h[0] = (uint32_t)b->d | ((uint32_t)b->dmin << 16);
-        for (int k = 0; k < 3; ++k)
-            h[1 + k] = (uint32_t)b->scales[4 * k] | ((uint32_t)b->scales[4 * k + 1] << 8) | ((uint32_t)b->scales[4 * k + 2] << 16) |
-                       ((uint32_t)b->scales[4 * k + 3] << 24);
-        *(uint4*)(tile + 2560 + n * 16) = make_uint4(h[0], h[1], h[2], h[3]);
-    }
-}
-
-/* Q3_K tile (tk_llm_layout.h): operand dword o = 2 j + hh (sub-block j, k0 + 4 hh .. + 3) keeps its four 3-bit quants u = q + 4 as
- * 2-bit slot o & 3 of the bytes of low dword o >> 2 and bit o & 7 of the bytes of high dword o >> 3 */
-__global__ void k_repack_q3k(const tk_block_q3_K* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_q3_K* b = src + (rt * 16 + n) * nblk + blk;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q3K_TILE_BYTES;
-    uint32_t lo[4] = {0, 0, 0, 0}, hi[2] = {0, 0};
-    for (int o = 0; o < 16; ++o) {
-        const int k0 = 32 * (o >> 1) + 8 * g + 4 * (o & 1);
+    uint32_t pn[8] = {}, p2[4] = {}, p1[2] = {}, pb[16] = {};
+#pragma unroll
+    for (int o = 0; o < 16; ++o)
+#pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const int u = tk_q3k_quant(b, k0 + t) + 4;
-            lo[o >> 2] |= (uint32_t)(u & 3) << (8 * t + 2 * (o & 3));
-            hi[o >> 3] |= (uint32_t)(u >> 2) << (8 * t + (o & 7));
+            const int c = B::code(run, 32 * (o >> 1) + 8 * g + 4 * (o & 1) + t);
+            if (nib) pn[o >> 1] |= (uint32_t)(c & 15) << (8 * t + 4 * (o & 1));
+            if (two) p2[o >> 2] |= (uint32_t)(T == TK_TYPE_Q6_K ? c >> 4 : c & 3) << (8 * t + 2 * (o & 3));
+            if (one) p1[o >> 3] |= (uint32_t)(q5 ? c >> 4 : c >> 2) << (8 * t + (q5 ? 4 * (o & 1) + ((o >> 1) & 3) : o & 7));
+            if (byt) pb[o] = pb[o] | (uint32_t)c << (8 * t);
         }
+    if (nib)
+        for (int i = 0; i < 2; ++i) tk_tile_put(tile + 1024 * i + lane * 16, make_uint4(pn[4 * i], pn[4 * i + 1], pn[4 * i + 2], pn[4 * i + 3]));
+    if (two) tk_tile_put(tile + at_two + lane * 16, make_uint4(p2[0], p2[1], p2[2], p2[3]));
+    if (one) tk_tile_put(tile + at_one + lane * 8, make_uint2(p1[0], p1[1]));
+    if (byt)
+        for (int i = 0; i < 4; ++i) tk_tile_put(tile + at_byt + 1024 * i + lane * 16, make_uint4(pb[4 * i], pb[4 * i + 1], pb[4 * i + 2], pb[4 * i + 3]));
+
+    uint32_t rec[4] = {}; /* the row's record */
+    auto byte = [&](int i, int v) { rec[i >> 2] |= (uint32_t)(v & 255) << (8 * (i & 3)); };
+    auto half = [&](int i, uint16_t v) { rec[i >> 1] |= (uint32_t)v << (16 * (i & 1)); };
+    (void)byte, (void)half; /* TQ2_0 and TQ1_0 have no record */
+    if constexpr (T == TK_TYPE_Q4_K || T == TK_TYPE_Q5_K) { /* d, dmin and the 12 packed (scale, min) bytes: the block's head as it is */
+        half(0, run->d);
+        half(1, run->dmin);
+        for (int i = 0; i < 12; ++i) byte(4 + i, run->scales[i]);
+    } else if constexpr (T == TK_TYPE_Q6_K) {
+        for (int i = 0; i < 16; ++i) byte(i, run->scales[i]);
+    } else if constexpr (T == TK_TYPE_Q3_K) { /* byte 8 h + j = the scale of group 2 j + h: the eight scales of one k half are one 8-byte read */
+        for (int i = 0; i < 16; ++i) byte(8 * (i & 1) + (i >> 1), tk_q3k_scale(run, i));
+    } else if constexpr (T == TK_TYPE_Q2_K) { /* the (scale, min) bytes in the same order */
+        for (int i = 0; i < 16; ++i) byte(8 * (i & 1) + (i >> 1), run->scales[i]);
+    } else if constexpr (T == TK_TYPE_IQ4_XS) { /* the eight scales s_j as int8, the f16 d and six zero bytes */
+        for (int j = 0; j < 8; ++j) byte(j, tk_iq4xs_scale(run, j));
+        half(4, run->d);
+    } else if constexpr (dm) { /* lane group 0 writes the row's eight d, group 1 its eight m */
+        for (int j = 0; j < 8; ++j) half(j, g == 0 ? run[j].d : run[j].m);
+    } else if constexpr (B::per_run == 8) {
+        for (int j = 0; j < 8; ++j) half(j, run[j].d);
     }
-    *(uint4*)(tile + lane * 16) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-    *(uint2*)(tile + 1024 + lane * 8) = make_uint2(hi[0], hi[1]);
-    if (g == 0) {
-        uint32_t sc[4] = {0, 0, 0, 0}; /* byte 8 h + j = the scale of group 2 j + h: the eight scales of one k half are one 8-byte read */
-        for (int h = 0; h < 2; ++h)
-            for (int j = 0; j < 8; ++j) sc[2 * h + (j >> 2)] |= (uint32_t)(uint8_t)tk_q3k_scale(b, 2 * j + h) << (8 * (j & 3));
-        *(uint4*)(tile + 1536 + n * 16) = make_uint4(sc[0], sc[1], sc[2], sc[3]);
-        *(uint16_t*)(tile + 1792 + n * 2) = b->d;
+    constexpr int rec_bytes = tq ? 0 : dm ? 32 : 16, at_d = at_rec + TK_TILE_ROWS * rec_bytes;
+    if (g < rec_bytes / 16) tk_tile_put(tile + at_rec + n * rec_bytes + g * 16, make_uint4(rec[0], rec[1], rec[2], rec[3]));
+    if constexpr (T == TK_TYPE_Q2_K) {
+        if (g == 0) tk_tile_put(tile + at_d + n * 4, (uint32_t)run->d | ((uint32_t)run->dmin << 16));
+        static_assert(at_d + TK_TILE_ROWS * 4 == tk_type_desc_of(T).tile_bytes, "Q2_K tile: planes, record and (d, dmin) are not its tile_bytes");
+    } else if constexpr (tq || T == TK_TYPE_Q6_K || T == TK_TYPE_Q3_K) {
+        if (g == 0) tk_tile_put(tile + at_d + n * 2, (uint16_t)run->d);
+        static_assert(at_d + TK_TILE_ROWS * 2 == tk_type_desc_of(T).tile_bytes, "tile: planes, record and d are not the type's tile_bytes");
+    } else {
+        static_assert(at_d == tk_type_desc_of(T).tile_bytes, "tile: planes and record are not the type's tile_bytes");
     }
 }
 
-/* Q2_K tile (tk_llm_layout.h): the Q3_K tile's low part alone, the (scale, min) bytes ordered by k half, then (d, dmin) */
-__global__ void k_repack_q2k(const tk_block_q2_K* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_q2_K* b = src + (rt * 16 + n) * nblk + blk;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q2K_TILE_BYTES;
-    uint32_t q[4] = {0, 0, 0, 0};
-    for (int o = 0; o < 16; ++o) {
-        const int k0 = 32 * (o >> 1) + 8 * g + 4 * (o & 1);
-        for (int t = 0; t < 4; ++t) q[o >> 2] |= (uint32_t)tk_q2k_quant(b, k0 + t) << (8 * t + 2 * (o & 3));
-    }
-    *(uint4*)(tile + lane * 16) = make_uint4(q[0], q[1], q[2], q[3]);
-    if (g == 0) {
-        uint32_t sm[4] = {0, 0, 0, 0};
-        for (int h = 0; h < 2; ++h)
-            for (int j = 0; j < 8; ++j) sm[2 * h + (j >> 2)] |= (uint32_t)b->scales[2 * j + h] << (8 * (j & 3));
-        *(uint4*)(tile + 1024 + n * 16) = make_uint4(sm[0], sm[1], sm[2], sm[3]);
-        *(uint32_t*)(tile + 1280 + n * 4) = (uint32_t)b->d | ((uint32_t)b->dmin << 16);
-    }
+template <int T>
+__global__ void k_repack(const typename TkBlock<T>::block* src, int64_t nblk, uint8_t* tiles) {
+    tk_repack_lane<T>(src, nblk, tiles, blockIdx.y, blockIdx.x, threadIdx.x);
 }
 
-/* Q8_0 tile (tk_llm_layout.h): a 256-k run of 16 rows = eight blocks per row.  nblk counts 256-k runs, as for the other tiles */
-__global__ void k_repack_q8_0(const tk_block_q8_0* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_q8_0* b = src + ((rt * 16 + n) * nblk + blk) * TK_Q8_0_PER_RUN;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q8_0_TILE_BYTES;
-    for (int i = 0; i < 4; ++i) {
-        uint32_t dw[4];
-        for (int c = 0; c < 4; ++c) { /* dword 2 e + hh: weights 8 g + 4 hh .. + 3 of block 2 i + e */
-            const int8_t* q = b[2 * i + (c >> 1)].qs + 8 * g + 4 * (c & 1);
-            dw[c] = (uint32_t)(uint8_t)q[0] | ((uint32_t)(uint8_t)q[1] << 8) | ((uint32_t)(uint8_t)q[2] << 16) | ((uint32_t)(uint8_t)q[3] << 24);
-        }
-        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
-    }
-    if (g == 0) {
-        uint32_t d[4];
-        for (int k = 0; k < 4; ++k) d[k] = (uint32_t)b[2 * k].d | ((uint32_t)b[2 * k + 1].d << 16);
-        *(uint4*)(tile + 4096 + n * 16) = make_uint4(d[0], d[1], d[2], d[3]);
-    }
-}
-
-/* Q4_0 tile (tk_llm_layout.h): the Q4_K tile's two nibble loads with the run's 32-blocks in place of sub-blocks, then the eight d per row */
-__global__ void k_repack_q4_0(const tk_block_q4_0* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_q4_0* b = src + ((rt * 16 + n) * nblk + blk) * TK_Q32_PER_RUN;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q4_0_TILE_BYTES;
-    for (int i = 0; i < 2; ++i) {
-        uint32_t dw[4];
-        for (int s = 0; s < 4; ++s) {
-            const tk_block_q4_0* bj = b + 4 * i + s;
-            const int k0 = 8 * g;
-            uint32_t v = 0;
-            for (int t = 0; t < 4; ++t) v |= (uint32_t)(tk_q4_0_quant(bj, k0 + t) | (tk_q4_0_quant(bj, k0 + 4 + t) << 4)) << (8 * t);
-            dw[s] = v;
-        }
-        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
-    }
-    if (g == 0) {
-        uint32_t d[4];
-        for (int k = 0; k < 4; ++k) d[k] = (uint32_t)b[2 * k].d | ((uint32_t)b[2 * k + 1].d << 16);
-        *(uint4*)(tile + 2048 + n * 16) = make_uint4(d[0], d[1], d[2], d[3]);
-    }
-}
-
-/* Q5_0 tile: the Q4_0 tile's nibble loads, the high bits where the Q5_K tile keeps them, then the eight d per row */
-__global__ void k_repack_q5_0(const tk_block_q5_0* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_q5_0* b = src + ((rt * 16 + n) * nblk + blk) * TK_Q32_PER_RUN;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q5_0_TILE_BYTES;
-    uint32_t hb[2] = {0, 0};
-    for (int i = 0; i < 2; ++i) {
-        uint32_t dw[4];
-        for (int s = 0; s < 4; ++s) {
-            const tk_block_q5_0* bj = b + 4 * i + s;
-            const int k0 = 8 * g;
-            uint32_t v = 0;
-            for (int t = 0; t < 4; ++t) {
-                const int qa = tk_q5_0_quant(bj, k0 + t), qb = tk_q5_0_quant(bj, k0 + 4 + t);
-                v |= (uint32_t)((qa & 15) | ((qb & 15) << 4)) << (8 * t);
-                hb[i] |= (uint32_t)(qa >> 4) << (8 * t + s);
-                hb[i] |= (uint32_t)(qb >> 4) << (8 * t + 4 + s);
-            }
-            dw[s] = v;
-        }
-        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
-    }
-    *(uint2*)(tile + 2048 + lane * 8) = make_uint2(hb[0], hb[1]);
-    if (g == 0) {
-        uint32_t d[4];
-        for (int k = 0; k < 4; ++k) d[k] = (uint32_t)b[2 * k].d | ((uint32_t)b[2 * k + 1].d << 16);
-        *(uint4*)(tile + 2560 + n * 16) = make_uint4(d[0], d[1], d[2], d[3]);
-    }
-}
-
-/* Q4_1 tile (tk_llm_layout.h): the Q4_0 tile's two nibble loads, then per row the eight d and the eight m */
-__global__ void k_repack_q4_1(const tk_block_q4_1* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_q4_1* b = src + ((rt * 16 + n) * nblk + blk) * TK_Q32_PER_RUN;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q4_1_TILE_BYTES;
-    for (int i = 0; i < 2; ++i) {
-        uint32_t dw[4];
-        for (int s = 0; s < 4; ++s) {
-            const tk_block_q4_1* bj = b + 4 * i + s;
-            const int k0 = 8 * g;
-            uint32_t v = 0;
-            for (int t = 0; t < 4; ++t) v |= (uint32_t)(tk_q4_1_quant(bj, k0 + t) | (tk_q4_1_quant(bj, k0 + 4 + t) << 4)) << (8 * t);
-            dw[s] = v;
-        }
-        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
-    }
-    if (g < 2) { /* lane group 0 writes the row's d, group 1 its m */
-        uint32_t d[4];
-        for (int k = 0; k < 4; ++k) d[k] = g == 0 ? (uint32_t)b[2 * k].d | ((uint32_t)b[2 * k + 1].d << 16) : (uint32_t)b[2 * k].m | ((uint32_t)b[2 * k + 1].m << 16);
-        *(uint4*)(tile + 2048 + n * 32 + g * 16) = make_uint4(d[0], d[1], d[2], d[3]);
-    }
-}
-
-/* Q5_1 tile: the Q5_0 tile's nibble loads and high bits, then the Q4_1 tile's (d, m) tail */
-__global__ void k_repack_q5_1(const tk_block_q5_1* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_q5_1* b = src + ((rt * 16 + n) * nblk + blk) * TK_Q32_PER_RUN;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_Q5_1_TILE_BYTES;
-    uint32_t hb[2] = {0, 0};
-    for (int i = 0; i < 2; ++i) {
-        uint32_t dw[4];
-        for (int s = 0; s < 4; ++s) {
-            const tk_block_q5_1* bj = b + 4 * i + s;
-            const int k0 = 8 * g;
-            uint32_t v = 0;
-            for (int t = 0; t < 4; ++t) {
-                const int qa = tk_q5_1_quant(bj, k0 + t), qb = tk_q5_1_quant(bj, k0 + 4 + t);
-                v |= (uint32_t)((qa & 15) | ((qb & 15) << 4)) << (8 * t);
-                hb[i] |= (uint32_t)(qa >> 4) << (8 * t + s);
-                hb[i] |= (uint32_t)(qb >> 4) << (8 * t + 4 + s);
-            }
-            dw[s] = v;
-        }
-        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
-    }
-    *(uint2*)(tile + 2048 + lane * 8) = make_uint2(hb[0], hb[1]);
-    if (g < 2) {
-        uint32_t d[4];
-        for (int k = 0; k < 4; ++k) d[k] = g == 0 ? (uint32_t)b[2 * k].d | ((uint32_t)b[2 * k + 1].d << 16) : (uint32_t)b[2 * k].m | ((uint32_t)b[2 * k + 1].m << 16);
-        *(uint4*)(tile + 2560 + n * 32 + g * 16) = make_uint4(d[0], d[1], d[2], d[3]);
-    }
-}
-
-/* IQ4_XS tile (tk_llm_layout.h): the Q4_0 tile's two nibble loads with the block's sub-blocks in place of 32-blocks, then per row the
- * eight scales s_j as int8, the f16 d and six zero bytes */
-__global__ void k_repack_iq4_xs(const tk_block_iq4_xs* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const tk_block_iq4_xs* b = src + (rt * 16 + n) * nblk + blk;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_IQ4_XS_TILE_BYTES;
-    for (int i = 0; i < 2; ++i) {
-        uint32_t dw[4];
-        for (int s = 0; s < 4; ++s) {
-            const uint8_t* qs = b->qs + 16 * (4 * i + s);
-            const int k0 = 8 * g;
-            uint32_t v = 0;
-            for (int t = 0; t < 4; ++t) v |= (uint32_t)(tk_iq4_quant(qs, k0 + t) | (tk_iq4_quant(qs, k0 + 4 + t) << 4)) << (8 * t);
-            dw[s] = v;
-        }
-        *(uint4*)(tile + 1024 * i + lane * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
-    }
-    if (g == 0) {
-        uint32_t sc[2] = {0, 0};
-        for (int j = 0; j < 8; ++j) sc[j >> 2] |= (uint32_t)(uint8_t)(int8_t)tk_iq4xs_scale(b, j) << (8 * (j & 3));
-        *(uint4*)(tile + 2048 + n * 16) = make_uint4(sc[0], sc[1], (uint32_t)b->d, 0u);
-    }
-}
-
-/* TQ2_0 tile (tk_llm_layout.h): the Q2_K tile's one load of 2-bit selectors, then the sixteen d.  BLOCK = tk_block_tq1_0: the same tile
- * from a TQ1_0 block, whose base-3 bytes are decoded here, once at load (tk_tq1_0_quant, the decode k_embed uses), into the codes 0..2 */
-__device__ __forceinline__ int tq_code(const tk_block_tq2_0* b, int i) { return tk_tq2_0_quant(b, i); }
-__device__ __forceinline__ int tq_code(const tk_block_tq1_0* b, int i) { return tk_tq1_0_quant(b, i); }
-template <typename BLOCK>
-__global__ void k_repack_tq(const BLOCK* src, int64_t nblk, uint8_t* tiles) {
-    const int lane = threadIdx.x;
-    const int n = lane & 15, g = lane >> 4;
-    const int64_t rt = blockIdx.y, blk = blockIdx.x;
-    const BLOCK* b = src + (rt * 16 + n) * nblk + blk;
-    uint8_t* tile = tiles + (rt * nblk + blk) * TK_TQ2_0_TILE_BYTES;
-    uint32_t q[4] = {0, 0, 0, 0};
-    for (int o = 0; o < 16; ++o) {
-        const int k0 = 32 * (o >> 1) + 8 * g + 4 * (o & 1);
-        for (int t = 0; t < 4; ++t) q[o >> 2] |= (uint32_t)tq_code(b, k0 + t) << (8 * t + 2 * (o & 3));
-    }
-    *(uint4*)(tile + lane * 16) = make_uint4(q[0], q[1], q[2], q[3]);
-    if (g == 0) *(uint16_t*)(tile + 1024 + n * 2) = b->d;
-}
-
+/* GGUF blocks -> tiles, one wave per tile.  A TQ1_0 matrix becomes TQ2_0 tiles and an IQ4_NL matrix Q4_0 tiles: their codes say so */
 void tk_launch_repack(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles, hipStream_t s) {
-    dim3 grid((unsigned)(K / 256), (unsigned)(rows / 16));
-    switch (type) {
-        /* a TQ1_0 matrix is installed as TQ2_0 tiles */
-        case TK_TYPE_TQ2_0: hipLaunchKernelGGL(k_repack_tq<tk_block_tq2_0>, grid, dim3(64), 0, s, (const tk_block_tq2_0*)blocks, K / 256, tiles); break;
-        case TK_TYPE_TQ1_0: hipLaunchKernelGGL(k_repack_tq<tk_block_tq1_0>, grid, dim3(64), 0, s, (const tk_block_tq1_0*)blocks, K / 256, tiles); break;
-        /* an IQ4_NL block has the Q4_0 block's bytes and its tile is the Q4_0 tile: the same kernel */
-        case TK_TYPE_IQ4_NL: hipLaunchKernelGGL(k_repack_q4_0, grid, dim3(64), 0, s, (const tk_block_q4_0*)blocks, K / 256, tiles); break;
-        case TK_TYPE_IQ4_XS: hipLaunchKernelGGL(k_repack_iq4_xs, grid, dim3(64), 0, s, (const tk_block_iq4_xs*)blocks, K / 256, tiles); break;
-        case TK_TYPE_Q4_0: hipLaunchKernelGGL(k_repack_q4_0, grid, dim3(64), 0, s, (const tk_block_q4_0*)blocks, K / 256, tiles); break;
-        case TK_TYPE_Q5_0: hipLaunchKernelGGL(k_repack_q5_0, grid, dim3(64), 0, s, (const tk_block_q5_0*)blocks, K / 256, tiles); break;
-        case TK_TYPE_Q4_1: hipLaunchKernelGGL(k_repack_q4_1, grid, dim3(64), 0, s, (const tk_block_q4_1*)blocks, K / 256, tiles); break;
-        case TK_TYPE_Q5_1: hipLaunchKernelGGL(k_repack_q5_1, grid, dim3(64), 0, s, (const tk_block_q5_1*)blocks, K / 256, tiles); break;
-        case TK_TYPE_Q8_0: hipLaunchKernelGGL(k_repack_q8_0, grid, dim3(64), 0, s, (const tk_block_q8_0*)blocks, K / 256, tiles); break;
-        case TK_TYPE_Q2_K: hipLaunchKernelGGL(k_repack_q2k, grid, dim3(64), 0, s, (const tk_block_q2_K*)blocks, K / 256, tiles); break;
-        case TK_TYPE_Q3_K: hipLaunchKernelGGL(k_repack_q3k, grid, dim3(64), 0, s, (const tk_block_q3_K*)blocks, K / 256, tiles); break;
-        case TK_TYPE_Q4_K: hipLaunchKernelGGL(k_repack_q4k, grid, dim3(64), 0, s, (const tk_block_q4_K*)blocks, K / 256, tiles); break;
-        case TK_TYPE_Q5_K: hipLaunchKernelGGL(k_repack_q5k, grid, dim3(64), 0, s, (const tk_block_q5_K*)blocks, K / 256, tiles); break;
-        default: hipLaunchKernelGGL(k_repack_q6k, grid, dim3(64), 0, s, (const tk_block_q6_K*)blocks, K / 256, tiles); break;
-    }
+    const dim3 grid((unsigned)(K / 256), (unsigned)(rows / 16));
+    tk_type_dispatch(type, [&](auto trait) {
+        constexpr int T = decltype(trait)::type;
+        if constexpr (tk_type_is_kquant(T)) hipLaunchKernelGGL(k_repack<T>, grid, dim3(64), 0, s, (const typename TkBlock<T>::block*)blocks, K / 256, tiles);
+    });
+}
+
+/* the same tiles from the same lane function in a host loop: what pins the tile bytes without a GPU (tk_mi355x_llm_repack_probe) */
+void tk_repack_host(int type, const void* blocks, int64_t rows, int64_t K, uint8_t* tiles) {
+    tk_type_dispatch(type, [&](auto trait) {
+        constexpr int T = decltype(trait)::type;
+        if constexpr (tk_type_is_kquant(T))
+            for (int64_t rt = 0; rt < rows / 16; ++rt)
+                for (int64_t blk = 0; blk < K / 256; ++blk)
+                    for (int lane = 0; lane < 64; ++lane) tk_repack_lane<T>((const typename TkBlock<T>::block*)blocks, K / 256, tiles, rt, blk, lane);
+    });
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -538,55 +233,13 @@ __global__ void k_embed(const void* embd, int type, int D, const int32_t* tok, f
     const int r = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= D) return;
-    if (type == TK_TYPE_F16) {
-        x[(int64_t)r * D + i] = tk_f16_to_f32(((const uint16_t*)embd)[(int64_t)tok[r] * D + i]);
-    } else if (type == TK_TYPE_BF16) {
-        x[(int64_t)r * D + i] = tk_bf16_to_f32(((const uint16_t*)embd)[(int64_t)tok[r] * D + i]);
-    } else if (type == TK_TYPE_F32) {
-        x[(int64_t)r * D + i] = ((const float*)embd)[(int64_t)tok[r] * D + i];
-    } else if (type == TK_TYPE_Q5_K) {
-        const tk_block_q5_K* row = (const tk_block_q5_K*)embd + (int64_t)tok[r] * (D / 256);
-        x[(int64_t)r * D + i] = tk_q5k_dequant(row + i / 256, i % 256);
-    } else if (type == TK_TYPE_Q3_K) {
-        const tk_block_q3_K* row = (const tk_block_q3_K*)embd + (int64_t)tok[r] * (D / 256);
-        x[(int64_t)r * D + i] = tk_q3k_dequant(row + i / 256, i % 256);
-    } else if (type == TK_TYPE_Q2_K) {
-        const tk_block_q2_K* row = (const tk_block_q2_K*)embd + (int64_t)tok[r] * (D / 256);
-        x[(int64_t)r * D + i] = tk_q2k_dequant(row + i / 256, i % 256);
-    } else if (type == TK_TYPE_Q8_0) {
-        const tk_block_q8_0* row = (const tk_block_q8_0*)embd + (int64_t)tok[r] * (D / 32);
-        x[(int64_t)r * D + i] = tk_q8_0_dequant(row + i / 32, i % 32);
-    } else if (type == TK_TYPE_Q4_0) {
-        const tk_block_q4_0* row = (const tk_block_q4_0*)embd + (int64_t)tok[r] * (D / 32);
-        x[(int64_t)r * D + i] = tk_q4_0_dequant(row + i / 32, i % 32);
-    } else if (type == TK_TYPE_Q5_0) {
-        const tk_block_q5_0* row = (const tk_block_q5_0*)embd + (int64_t)tok[r] * (D / 32);
-        x[(int64_t)r * D + i] = tk_q5_0_dequant(row + i / 32, i % 32);
-    } else if (type == TK_TYPE_Q4_1) {
-        const tk_block_q4_1* row = (const tk_block_q4_1*)embd + (int64_t)tok[r] * (D / 32);
-        x[(int64_t)r * D + i] = tk_q4_1_dequant(row + i / 32, i % 32);
-    } else if (type == TK_TYPE_Q5_1) {
-        const tk_block_q5_1* row = (const tk_block_q5_1*)embd + (int64_t)tok[r] * (D / 32);
-        x[(int64_t)r * D + i] = tk_q5_1_dequant(row + i / 32, i % 32);
-    } else if (type == TK_TYPE_IQ4_NL) {
-        const tk_block_iq4_nl* row = (const tk_block_iq4_nl*)embd + (int64_t)tok[r] * (D / 32);
-        x[(int64_t)r * D + i] = tk_iq4nl_dequant(row + i / 32, i % 32);
-    } else if (type == TK_TYPE_IQ4_XS) {
-        const tk_block_iq4_xs* row = (const tk_block_iq4_xs*)embd + (int64_t)tok[r] * (D / 256);
-        x[(int64_t)r * D + i] = tk_iq4xs_dequant(row + i / 256, i % 256);
-    } else if (type == TK_TYPE_TQ2_0) {
-        const tk_block_tq2_0* row = (const tk_block_tq2_0*)embd + (int64_t)tok[r] * (D / 256);
-        x[(int64_t)r * D + i] = tk_tq2_0_dequant(row + i / 256, i % 256);
-    } else if (type == TK_TYPE_TQ1_0) { /* token_embd stays in GGUF layout: the base-3 bytes are decoded per weight */
-        const tk_block_tq1_0* row = (const tk_block_tq1_0*)embd + (int64_t)tok[r] * (D / 256);
-        x[(int64_t)r * D + i] = tk_tq1_0_dequant(row + i / 256, i % 256);
-    } else if (type == TK_TYPE_Q6_K) {
-        const tk_block_q6_K* row = (const tk_block_q6_K*)embd + (int64_t)tok[r] * (D / 256);
-        x[(int64_t)r * D + i] = tk_q6k_dequant(row + i / 256, i % 256);
-    } else {
-        const tk_block_q4_K* row = (const tk_block_q4_K*)embd + (int64_t)tok[r] * (D / 256);
-        x[(int64_t)r * D + i] = tk_q4k_dequant(row + i / 256, i % 256);
-    }
+    tk_type_dispatch(type, [&](auto trait) { /* token_embd stays in GGUF layout: every weight is decoded from its block */
+        typedef decltype(trait) B;
+        if constexpr (tk_type_desc_of(B::type).token_embd) {
+            const typename B::block* row = (const typename B::block*)embd + (int64_t)tok[r] * (D / B::elems);
+            x[(int64_t)r * D + i] = B::dequant(row + i / B::elems, i % B::elems);
+        }
+    });
 }
 
 void tk_launch_embed(const void* embd, int type, int D, const int32_t* tok, int nrows, float* x, hipStream_t s) {

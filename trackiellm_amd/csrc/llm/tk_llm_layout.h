@@ -73,7 +73,7 @@
  *                    dword o (one shift and one mask give the four byte selectors 0..3 of an operand dword)
  *      [1024 ,1056)  16 x f16 d
  *  The kernels turn the selectors into int8 c - 1 with one v_perm_b32 on the constant bytes {-1, 0, 1, 2}: code 3 gives +2, no byte carries.
- *  TQ1_0 tile: the TQ2_0 tile.  k_repack_tq<tk_block_tq1_0> decodes the block's base-3 bytes once, at load, and writes the trits t (0..2) as codes, so
+ *  TQ1_0 tile: the TQ2_0 tile.  The repack (TkBlock<TK_TYPE_TQ1_0>::code, tk_ggml_blocks.h) decodes the block's base-3 bytes once, at load, and writes the trits t (0..2) as codes, so
  *  a TQ1_0 matrix streams 66 bytes per 256 weights where its file holds 54, and runs the kernels a TQ2_0 matrix runs
  *  Q6_K tile (3360 B = 16 x 210): weights stored as 6-bit two's complement q' = (q - 32) & 63
  *      [0    ,2048)  two loads as above holding the LOW nibbles of q'

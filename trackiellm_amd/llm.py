@@ -54,6 +54,11 @@ def lora_probe(path):
     return r.value, a.value, n.value
 
 
+# the types with a host quantiser entry of their own, tk_mi355x_quantize_blocks_<name>; tk_mi355x_quantize_blocks(type, ...) takes the others
+QUANTIZE_ENTRY = {TYPE_Q2_K: "q2k", TYPE_Q4_0: "q4_0", TYPE_Q5_0: "q5_0", TYPE_Q4_1: "q4_1", TYPE_Q5_1: "q5_1", TYPE_IQ4_NL: "iq4_nl", TYPE_IQ4_XS: "iq4_xs",
+                  TYPE_TQ1_0: "tq1_0", TYPE_TQ2_0: "tq2_0"}
+
+
 def quantize_blocks(ttype, x):
     """the build's own block quantiser on the host, no GPU (tk_mi355x_quantize_blocks; tk_mi355x_quantize_blocks_q2k for TYPE_Q2_K,
     tk_mi355x_quantize_blocks_q4_0 / _q5_0 / _q4_1 / _q5_1 / _iq4_nl / _iq4_xs / _tq1_0 / _tq2_0 for TYPE_Q4_0 / TYPE_Q5_0 / TYPE_Q4_1 / TYPE_Q5_1 / TYPE_IQ4_NL / TYPE_IQ4_XS / TYPE_TQ1_0 / TYPE_TQ2_0):
@@ -61,17 +66,10 @@ def quantize_blocks(ttype, x):
     [n / 32][18 / 22 / 34 / 18]"""
     x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 32 if ttype in TYPES_OF_32 else 256)
     out = np.empty((x.shape[0], BLOCK_BYTES[ttype]), np.uint8)
-    if ttype in (TYPE_Q4_0, TYPE_Q5_0, TYPE_Q4_1, TYPE_Q5_1, TYPE_IQ4_NL, TYPE_IQ4_XS, TYPE_TQ1_0, TYPE_TQ2_0):
-        fn = {TYPE_Q4_0: lib().tk_mi355x_quantize_blocks_q4_0, TYPE_Q5_0: lib().tk_mi355x_quantize_blocks_q5_0,
-              TYPE_Q4_1: lib().tk_mi355x_quantize_blocks_q4_1, TYPE_Q5_1: lib().tk_mi355x_quantize_blocks_q5_1,
-              TYPE_IQ4_NL: lib().tk_mi355x_quantize_blocks_iq4_nl, TYPE_IQ4_XS: lib().tk_mi355x_quantize_blocks_iq4_xs,
-              TYPE_TQ1_0: lib().tk_mi355x_quantize_blocks_tq1_0, TYPE_TQ2_0: lib().tk_mi355x_quantize_blocks_tq2_0}[ttype]
+    if ttype in QUANTIZE_ENTRY:
+        fn = getattr(lib(), "tk_mi355x_quantize_blocks_" + QUANTIZE_ENTRY[ttype])
         fn.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         check(fn(_p(x), x.shape[0], _p(out)))
-        return out
-    if ttype == TYPE_Q2_K:
-        lib().tk_mi355x_quantize_blocks_q2k.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-        check(lib().tk_mi355x_quantize_blocks_q2k(_p(x), x.shape[0], _p(out)))
         return out
     lib().tk_mi355x_quantize_blocks.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     check(lib().tk_mi355x_quantize_blocks(ttype, _p(x), x.shape[0], _p(out)))
@@ -87,6 +85,24 @@ def gemv_probe(ttype, blocks, rows, K, ks, x, device=0):
     lib().tk_mi355x_llm_gemv_probe.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     check(lib().tk_mi355x_llm_gemv_probe(device, ttype, _p(blocks), rows, K, ks, x.shape[0], _p(x), _p(y)))
     return y
+
+
+# bytes of one W4A8 tile, 16 rows x 256 k (csrc/llm/tk_llm_layout.h): 16 x the bytes of a row's run, but for Q3_K and IQ4_XS, whose tiles hold
+# their scales unpacked, and TQ1_0, which is installed as TQ2_0 tiles
+TILE_BYTES = {t: 16 * (256 // (32 if t in TYPES_OF_32 else 256)) * b for t, b in BLOCK_BYTES.items()}
+TILE_BYTES.update({TYPE_Q3_K: 16 * 114, TYPE_IQ4_XS: 16 * 144, TYPE_TQ1_0: 16 * 66})
+
+
+def repack_probe(ttype, blocks, rows, K, device=0):
+    """the load-time repack alone (tk_mi355x_llm_repack_probe): raw GGUF blocks [rows][K / 256] of `ttype` ([rows][K / 32] for the TYPES_OF_32) ->
+    uint8 tiles [rows / 16][K / 256][TILE_BYTES[ttype]]; device < 0 runs the same lane function on the host, no GPU touched"""
+    blocks = np.ascontiguousarray(blocks).view(np.uint8).reshape(-1)
+    if ttype in BLOCK_BYTES and blocks.size != rows * K // (32 if ttype in TYPES_OF_32 else 256) * BLOCK_BYTES[ttype]:
+        raise ValueError("repack_probe: blocks is not rows x K weights of this type")
+    tiles = np.empty((max(rows // 16, 0), max(K // 256, 0), TILE_BYTES.get(ttype, 0)), np.uint8)
+    lib().tk_mi355x_llm_repack_probe.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    check(lib().tk_mi355x_llm_repack_probe(device, ttype, _p(blocks), rows, K, _p(tiles)))
+    return tiles
 
 
 def convert_bf16(x):
