@@ -208,7 +208,25 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_forward_stage(tk_mi355x_llm_se
  * runs); tk_mi355x_llm_runner_set_sampling switches a runner to that chain, on the device, with a counter-based generator keyed by
  * (random_seed, tokens sampled so far by this runner): the same seed gives the same ids whatever else shares the runner's passes, and the
  * oracle restates the arithmetic (orc_sample_row) so tests compare ids for fixed seeds.  temperature 0 = back to greedy.  top_k 0 = 64 (the
- * most candidates kept); top_p 1 and min_p 0 switch those filters off.  llama.cpp itself is absent (parity unpinned vs its generator). ---- */
+ * most candidates kept); top_p 1 and min_p 0 switch those filters off.  llama.cpp itself is absent (parity unpinned vs its generator).
+ *
+ * The whole chain, in llama.cpp's order (llama_sampling_prepare, then grammar, then the sampler), every stage on the device:
+ *   1. logit bias:  logit[id] += bias                                                     (tk_mi355x_llm_runner_set_logit_bias; bias -inf bans a token)
+ *   2. repetition penalties over the window = the last last_n ids the runner has accepted: for every distinct token t in it, c occurrences,
+ *      l = logit[t];  l = l <= 0 ? l * repeat : l / repeat;  l = l - (float(c) * freq + present)   (tk_mi355x_llm_runner_set_penalties)
+ *   3. the tool-call grammar's token mask   4. greedy arg max, or top-k, top-p, min-p, temperature and one draw.
+ * Stages 1 and 2 are OFF by default (llama.cpp: penalty_last_n 64, penalty_repeat 1.10 or 1.00 depending on its generation, freq = present = 0;
+ * the reference pins no generation).  Each is one correctly rounded fp32 operation after the other, the same on host and device
+ * (csrc/common/tk_logit_adjust.h), so adjusted logits are reproducible bit for bit.  They apply to greedy rows too.
+ * The window: an id enters it when tk_llm_runner_generate_next_token takes it (llama_sampling_accept, the id that turns out to be EOS included);
+ * it empties in tk_llm_runner_prepare_generation, the only call in which the reference resets its sampler; add_tool_response and reset_context
+ * leave it alone.  The first token after a prompt is sampled over an empty window: only the bias applies.
+ * Not restated from llama.cpp: its `prev` ring starts as last_n zeros, so it penalises token 0 until last_n tokens have been accepted — here the
+ * window holds accepted ids only; and last_n = -1 ("the context size") is refused (a window holds at most 256 ids).  The newline token is
+ * penalised like any other (penalize_nl = true).
+ * Run-ahead: a runner whose next row is adjusted, or whose penalties are on, does not run ahead (csrc/llm/tk_llm_batcher.h) — its next window
+ * depends on the id it accepts — and pays one host round trip per token, like a runner under a grammar mask or a temperature.  A runner
+ * with neither bias nor penalties (or with repeat 1, freq 0, present 0) runs exactly the passes it ran before. ---- */
 typedef struct {
     float temperature, top_p, min_p;
     int32_t top_k;
@@ -221,6 +239,30 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_sampling(struct tk_
 /* tk_mi355x_llm_forward with a sampling state per row (temperature <= 0: that row takes the arg max); ids [nrows] */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_forward_sampled(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos,
                                                                   const int32_t* tok, const tk_mi355x_sampling_t* sampling, float* logits, int32_t* ids);
+/* one row's logit adjustment.  Limits (checked wherever one is taken): 0 <= n_recent <= 256, 0 <= n_bias <= 256, repeat finite and > 0, freq and
+ * present finite, every bias finite or -inf, every id in [0, vocab), bias ids unique, no NULL array with a non-zero count.  A row with n_bias == 0
+ * and (n_recent == 0 or repeat == 1, freq == 0, present == 0) is NEUTRAL: it is not adjusted at all */
+typedef struct {
+    float repeat, freq, present; /* 1, 0, 0 = off */
+    int32_t n_recent;
+    const int32_t* recent;
+    int32_t n_bias;
+    const int32_t* bias_ids;
+    const float* bias;
+} tk_mi355x_logit_adjust_t;
+/* the runner's repetition penalties: last_n in [0, 256] (0 = off); takes effect from the next sampled token */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_penalties(struct tk_llm_runner_s* runner, int32_t last_n, float repeat, float freq, float present);
+/* replaces the runner's bias list (copied); n = 0 clears it; takes effect from the next sampled token */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_logit_bias(struct tk_llm_runner_s* runner, int32_t n, const int32_t* ids, const float* bias);
+/* the ids the runner has accepted since the last prepare_generation, oldest first — the most recent 256 of them, whatever last_n is; the
+ * penalties read the last last_n.  Writes at most cap ids and returns the count held (may exceed cap); -1: no runner */
+TK_API int32_t tk_mi355x_llm_runner_recent_tokens(struct tk_llm_runner_s* runner, int32_t* out, int32_t cap);
+/* tk_mi355x_llm_forward_sampled with an adjustment per row: adjust [nrows] (neutral rows are plain rows); sampling may be NULL (every row
+ * greedy).  Masks and sampling see the adjusted logits, and `logits` receives the ADJUSTED rows.  A pass with no non-neutral row is the pass
+ * tk_mi355x_llm_forward_sampled runs.  tk_mi355x_llm_decode after it is unadjusted */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_forward_adjusted(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos,
+                                                                   const int32_t* tok, const tk_mi355x_sampling_t* sampling,
+                                                                   const tk_mi355x_logit_adjust_t* adjust, float* logits, int32_t* ids);
 /* KV cache import / export: positions [pos0, pos0 + n_pos) of one (layer, sequence) as IEEE f16 bits, host arrays laid out
  * [position][kv head][head_dim] (what llama.cpp's llama_state_seq_* moves for one sequence; the reference clears the cache per prompt,
  * src/ai_models/tk_runner_streaming.c:31, so it has no counterpart there).  Restores a saved prompt prefix; the parity tests use it to put
@@ -405,6 +447,13 @@ typedef struct {
     int32_t beg, eot, tid0, reserved;
 } tk_mi355x_token_pick_probe_t;
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_token_pick_probe(int device, tk_mi355x_token_pick_probe_t* p);
+
+/* test hook for the logit adjustment, the contract of tk_mi355x_token_pick_probe: ONE launch of k_logit_adjust (tk_launch_logit_adjust) on logits
+ * [rows][cols] (IN/OUT, packed, n_logits floats in all, read back whole), adjust [rows].  Everything is validated before anything is launched
+ * (TK_ERROR_INVALID_ARGUMENT, logits untouched): rows outside [1, tk_mi355x_llm_max_rows()], cols outside [1, 2^24], n_logits < rows * cols, and
+ * every limit of tk_mi355x_logit_adjust_t for every row.  device < 0: the same per-row function in a host loop, no GPU touched */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_logit_adjust_probe(int device, int32_t rows, int32_t cols, float* logits, int64_t n_logits,
+                                                                 const tk_mi355x_logit_adjust_t* adjust);
 
 /* test hook for the perception streams' row and layout kernels (csrc/nn/tk_nn_kernels): ONE launch of one launcher on host arrays, so that
  * shapes no network sends (pitches wider than the extent, odd sizes around the kernels' 256 / 2048 thresholds, unaligned bases, rows that are

@@ -4,7 +4,9 @@ tk_llm_runner_prepare_generation -> N x tk_llm_runner_generate_next_token on the
 TK_MI355X_NO_FUSE=1 keeps the norm / SwiGLU producers as launches of their own (A/B); under rocprofv3 --kernel-trace --stats the per-kernel
 durations of the decode step come out (ROC_AQL_QUEUE_SIZE=524288 for the graph path, DESIGN.md "Profiling").
 --prefix-cache (default off) switches the model's prompt prefix cache on; either way a second turn (the same preamble, another ending) is prepared
-after the decode loop and its prepare_generation latency and the model's prefix_cache_stats are printed."""
+after the decode loop and its prepare_generation latency and the model's prefix_cache_stats are printed.
+--penalties LAST_N,REPEAT (default none) gives the runner repetition penalties: an adjusted runner does not run ahead, so this measures the
+extra launch, the table upload and above all one host round trip per token (profiles/sampler_adjust.txt)."""
 import os
 import sys
 import time
@@ -18,6 +20,11 @@ h = loader.load("synthetic://mistral-7b?seed=4")
 prefix_cache = "--prefix-cache" in sys.argv
 tk.ModelLoader.set_prefix_cache(h, prefix_cache)
 runner = tk.LlmRunner(h, context_size=512)
+penalties = "none"
+if "--penalties" in sys.argv:
+    penalties = sys.argv[sys.argv.index("--penalties") + 1]
+    last_n, repeat = penalties.split(",")
+    runner.set_penalties(int(last_n), float(repeat))
 t = time.time()
 runner.prepare("The user is in a room. " * 8)
 t_first = time.time() - t
@@ -30,7 +37,7 @@ for _ in range(N):
         break
     n += 1
 dt = time.time() - t
-print(f"one runner: {n} tokens, {1000 * dt / max(n, 1):.3f} ms per token, {n / dt:.1f} tok/s (TK_MI355X_NO_FUSE={os.environ.get('TK_MI355X_NO_FUSE', '0')})", flush=True)
+print(f"one runner: {n} tokens, {1000 * dt / max(n, 1):.3f} ms per token, {n / dt:.1f} tok/s (TK_MI355X_NO_FUSE={os.environ.get('TK_MI355X_NO_FUSE', '0')}, penalties {penalties})", flush=True)
 t = time.time()
 runner.prepare("The user is in a room. " * 7 + "The user is in a hall. ")
 t_second = time.time() - t

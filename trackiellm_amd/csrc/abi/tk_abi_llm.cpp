@@ -16,6 +16,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -375,19 +376,36 @@ tk_error_code_t tk_mi355x_llm_forward(tk_mi355x_llm_session_t* s, int nrows, con
     return TK_SUCCESS;
 }
 
-tk_error_code_t tk_mi355x_llm_forward_sampled(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok,
-                                              const tk_mi355x_sampling_t* sampling, float* logits, int32_t* ids) {
-    if (!s || !seq || !pos || !tok || !sampling || nrows < 1 || nrows > TK_MAX_ROWS) return TK_ERROR_INVALID_ARGUMENT;
+/* a sampling pass with optional per-row sampling states and logit adjustments: both checked per row before anything runs */
+static tk_error_code_t forward_rows(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok,
+                                    const tk_mi355x_sampling_t* sampling, const tk_mi355x_logit_adjust_t* adjust, float* logits, int32_t* ids) {
+    static_assert(sizeof(tk_mi355x_logit_adjust_t) == sizeof(TkLogitAdjust), "the public logit adjustment is the library's TkLogitAdjust (tk_rocm_hal.hip checks the fields)");
+    if (!s || !seq || !pos || !tok || nrows < 1 || nrows > TK_MAX_ROWS) return TK_ERROR_INVALID_ARGUMENT;
+    const TkLogitAdjust* adj = (const TkLogitAdjust*)adjust;
+    for (int r = 0; r < nrows && adj; ++r)
+        if (const char* why = adj[r].check(s->session.model->hp.vocab)) return fail(TK_ERROR_INVALID_ARGUMENT, "logit adjustment of row " + std::to_string(r) + ": " + why);
     TkSampleRow rows[TK_MAX_ROWS] = {};
-    for (int r = 0; r < nrows; ++r) {
+    for (int r = 0; r < nrows && sampling; ++r) {
         const tk_mi355x_sampling_t& p = sampling[r];
         /* the checks tk_mi355x_llm_runner_set_sampling makes, per row */
         if (!(p.temperature >= 0.0f) || p.top_k < 0 || p.top_k > TK_SAMPLE_MAX_K || !(p.top_p > 0.0f) || p.top_p > 1.0f || !(p.min_p >= 0.0f) || p.min_p > 1.0f)
             return fail(TK_ERROR_INVALID_ARGUMENT, "sampling parameters of row " + std::to_string(r) + " are out of range (temperature >= 0, 0 <= top_k <= 64, 0 < top_p <= 1, 0 <= min_p <= 1)");
         rows[r].temp = p.temperature; rows[r].top_p = p.top_p; rows[r].min_p = p.min_p; rows[r].top_k = p.top_k; rows[r].seed = p.seed; rows[r].counter = p.counter;
     }
-    if (!s->session.forward(nrows, seq, pos, tok, logits, ids, true, nullptr, rows)) return fail(TK_ERROR_INFERENCE_FAILED, s->session.error);
+    if (!s->session.forward(nrows, seq, pos, tok, logits, ids, true, nullptr, sampling ? rows : nullptr, adj)) return fail(TK_ERROR_INFERENCE_FAILED, s->session.error);
     return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_forward_sampled(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok,
+                                              const tk_mi355x_sampling_t* sampling, float* logits, int32_t* ids) {
+    if (!sampling) return TK_ERROR_INVALID_ARGUMENT;
+    return forward_rows(s, nrows, seq, pos, tok, sampling, nullptr, logits, ids);
+}
+
+tk_error_code_t tk_mi355x_llm_forward_adjusted(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok,
+                                               const tk_mi355x_sampling_t* sampling, const tk_mi355x_logit_adjust_t* adjust, float* logits, int32_t* ids) {
+    if (!adjust) return TK_ERROR_INVALID_ARGUMENT;
+    return forward_rows(s, nrows, seq, pos, tok, sampling, adjust, logits, ids);
 }
 
 tk_error_code_t tk_mi355x_llm_session_kv_write(tk_mi355x_llm_session_t* s, int layer, int seq, int pos0, int n_pos, const uint16_t* k, const uint16_t* v) {
@@ -808,6 +826,28 @@ struct tk_llm_runner_s {
      * tokens this runner has sampled since its creation), so a runner's ids do not depend on which other runners share its passes */
     TkSampleRow samp{};
     const TkSampleRow* next_samp() { return samp.temp > 0.0f ? &samp : nullptr; }
+    /* logit bias and repetition penalties (tk_mi355x_ext.h "sampling"), off by default.  accepted: the ids generate_next_token has taken from
+     * `pending` since the last prepare_generation (llama_sampling_accept), the most recent TK_ADJUST_MAX_RECENT of them, oldest first */
+    std::vector<int32_t> accepted;
+    int32_t pen_last_n = 0;
+    float pen_repeat = 1.0f, pen_freq = 0.0f, pen_present = 0.0f;
+    std::vector<int32_t> bias_ids;
+    std::vector<float> bias;
+    TkLogitAdjust adj;
+    void accept(int32_t id) {
+        if (accepted.size() == TK_ADJUST_MAX_RECENT) accepted.erase(accepted.begin());
+        accepted.push_back(id);
+    }
+    /* the adjustment of the next sampled row, or nullptr when the runner has neither penalties nor a bias list (it then submits what it always did) */
+    const TkLogitAdjust* next_adjust() {
+        if (pen_last_n == 0 && bias_ids.empty()) return nullptr;
+        const size_t n = std::min(accepted.size(), (size_t)pen_last_n);
+        adj = TkLogitAdjust{};
+        adj.repeat = pen_repeat; adj.freq = pen_freq; adj.present = pen_present;
+        adj.n_recent = (int32_t)n; adj.recent = accepted.data() + (accepted.size() - n);
+        adj.n_bias = (int32_t)bias_ids.size(); adj.bias_ids = bias_ids.data(); adj.bias = bias.data();
+        return &adj;
+    }
     bool is_processing = false;
     std::string piece;
     std::string system_prompt;
@@ -872,6 +912,30 @@ tk_error_code_t tk_mi355x_llm_runner_set_sampling(tk_llm_runner_t* runner, float
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_llm_runner_set_penalties(tk_llm_runner_t* runner, int32_t last_n, float repeat, float freq, float present) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    if (last_n < 0 || last_n > TK_ADJUST_MAX_RECENT) return fail(TK_ERROR_INVALID_ARGUMENT, "penalties: last_n must be in [0, 256] (-1, the context size, is not supported)");
+    const TkAdjustRow d{repeat, freq, present, 0, 0}; /* the values; the window is the runner's own */
+    if (const char* why = tk_adjust_check(d, nullptr, nullptr, nullptr, runner->model->model.hp.vocab)) return fail(TK_ERROR_INVALID_ARGUMENT, std::string("penalties: ") + why);
+    runner->pen_last_n = last_n; runner->pen_repeat = repeat; runner->pen_freq = freq; runner->pen_present = present;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_runner_set_logit_bias(tk_llm_runner_t* runner, int32_t n, const int32_t* ids, const float* bias) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    const TkAdjustRow d{1.0f, 0.0f, 0.0f, 0, n};
+    if (const char* why = tk_adjust_check(d, nullptr, ids, bias, runner->model->model.hp.vocab)) return fail(TK_ERROR_INVALID_ARGUMENT, std::string("logit bias: ") + why);
+    runner->bias_ids.assign(ids, ids + n);
+    runner->bias.assign(bias, bias + n);
+    return TK_SUCCESS;
+}
+
+int32_t tk_mi355x_llm_runner_recent_tokens(tk_llm_runner_t* runner, int32_t* out, int32_t cap) {
+    if (!runner) return -1;
+    for (int32_t i = 0; out && i < cap && i < (int32_t)runner->accepted.size(); ++i) out[i] = runner->accepted[(size_t)i];
+    return (int32_t)runner->accepted.size();
+}
+
 tk_error_code_t tk_llm_runner_create(tk_llm_runner_t** out_runner, void* model_handle, const tk_llm_config_t* config) {
     if (!out_runner || !model_handle || !config) return TK_ERROR_INVALID_ARGUMENT;
     std::unique_ptr<tk_llm_runner_s> r(new tk_llm_runner_s());
@@ -925,7 +989,7 @@ static tk_error_code_t feed(tk_llm_runner_s* r, const std::vector<int32_t>& toks
     int32_t am = -1;
     std::string err;
     /* whole_context (prepare_generation): the tokens start at position 0, so the scheduler may keep or copy rows the cache already holds for them */
-    if (!r->batcher->submit(r->slot, r->n_past, toks.data(), (int)toks.size(), r->next_mask(), &am, &err, r->next_samp(), whole_context ? &r->last_prompt : nullptr))
+    if (!r->batcher->submit(r->slot, r->n_past, toks.data(), (int)toks.size(), r->next_mask(), &am, &err, r->next_samp(), whole_context ? &r->last_prompt : nullptr, r->next_adjust()))
         return fail(TK_ERROR_INFERENCE_FAILED, err);
     if (r->samp.temp > 0.0f) r->samp.counter++;
     r->n_past += (int)toks.size();
@@ -943,6 +1007,7 @@ tk_error_code_t tk_llm_runner_prepare_generation(tk_llm_runner_t* runner, const 
     std::vector<int32_t> toks = runner->model->tok.encode(prompt, true);
     runner->n_past = 0; /* llama_kv_cache_clear: positions restart, stale cache rows are never attended */
     runner->pending = -1;
+    runner->accepted.clear(); /* llama_sampling_reset (tk_runner_streaming.c:42): the only call that empties the window */
     runner->last_prompt = TkLlmBatcher::PrefixRows{(int32_t)toks.size(), 0, 0};
     tk_error_code_t rc = feed(runner, toks, true);
     if (rc != TK_SUCCESS) return rc;
@@ -953,6 +1018,7 @@ tk_error_code_t tk_llm_runner_prepare_generation(tk_llm_runner_t* runner, const 
 const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
     if (!runner || !runner->is_processing) return NULL;
     const int32_t id = runner->pending;
+    if (id >= 0) runner->accept(id); /* llama_sampling_accept (tk_runner_streaming.c:61) comes before the EOS test: that id is in the window too */
     if (id < 0 || id == runner->model->tok.eos) { runner->is_processing = false; return NULL; }
     if (runner->grammar_on) {
         /* llama_sampling_accept: advance the grammar by the sampled token; then the reference's "grammar rule completed" test
@@ -973,7 +1039,7 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
     if (runner->n_past + 1 >= runner->n_ctx) { runner->is_processing = false; return NULL; }
     int32_t t = id, am = -1;
     std::string err;
-    if (!runner->batcher->submit(runner->slot, runner->n_past, &t, 1, runner->next_mask(), &am, &err, runner->next_samp())) {
+    if (!runner->batcher->submit(runner->slot, runner->n_past, &t, 1, runner->next_mask(), &am, &err, runner->next_samp(), nullptr, runner->next_adjust())) {
         tk_error_set_detail("%s", err.c_str());
         runner->is_processing = false;
         return NULL;

@@ -385,6 +385,46 @@ tk_error_code_t tk_mi355x_token_pick_probe(int device, tk_mi355x_token_pick_prob
     return rc;
 }
 
+static_assert(sizeof(tk_mi355x_logit_adjust_t) == sizeof(TkLogitAdjust) && offsetof(tk_mi355x_logit_adjust_t, recent) == offsetof(TkLogitAdjust, recent) &&
+                  offsetof(tk_mi355x_logit_adjust_t, n_bias) == offsetof(TkLogitAdjust, n_bias) && offsetof(tk_mi355x_logit_adjust_t, bias) == offsetof(TkLogitAdjust, bias),
+              "the public logit adjustment is the library's TkLogitAdjust");
+
+tk_error_code_t tk_mi355x_logit_adjust_probe(int device, int32_t rows, int32_t cols, float* logits, int64_t n_logits, const tk_mi355x_logit_adjust_t* adjust) {
+    if (!logits || !adjust || rows < 1 || rows > TK_MAX_ROWS || cols < 1 || cols > (1 << 24) || n_logits < (int64_t)rows * cols) return TK_ERROR_INVALID_ARGUMENT;
+    const TkLogitAdjust* adj = (const TkLogitAdjust*)adjust;
+    for (int r = 0; r < rows; ++r)
+        if (adj[r].check(cols)) return TK_ERROR_INVALID_ARGUMENT;
+    if (device < 0) {
+        for (int r = 0; r < rows; ++r) tk_logit_adjust_row(logits + (int64_t)r * cols, adj[r].row(), adj[r].recent, adj[r].bias_ids, adj[r].bias);
+        return TK_SUCCESS;
+    }
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    /* the session's tables (TkLlmSession::forward): descriptors, then windows, bias ids and bias values of TK_ADJUST_MAX_* entries per row */
+    std::vector<TkAdjustRow> desc((size_t)rows);
+    std::vector<int32_t> ids((size_t)rows * TK_ADJUST_MAX_RECENT, 0), bids((size_t)rows * TK_ADJUST_MAX_BIAS, 0);
+    std::vector<float> bias((size_t)rows * TK_ADJUST_MAX_BIAS, 0.0f);
+    for (int r = 0; r < rows; ++r) {
+        desc[(size_t)r] = adj[r].row();
+        for (int j = 0; j < adj[r].n_recent; ++j) ids[(size_t)r * TK_ADJUST_MAX_RECENT + j] = adj[r].recent[j];
+        for (int j = 0; j < adj[r].n_bias; ++j) { bids[(size_t)r * TK_ADJUST_MAX_BIAS + j] = adj[r].bias_ids[j]; bias[(size_t)r * TK_ADJUST_MAX_BIAS + j] = adj[r].bias[j]; }
+    }
+    struct Buf { const void* host; size_t bytes; void* dev; };
+    Buf b[] = {{logits, (size_t)n_logits * 4, nullptr}, {desc.data(), desc.size() * sizeof(TkAdjustRow), nullptr}, {ids.data(), ids.size() * 4, nullptr},
+               {bids.data(), bids.size() * 4, nullptr}, {bias.data(), bias.size() * 4, nullptr}};
+    bool ok = true;
+    for (Buf& q : b) ok = ok && hipMalloc(&q.dev, q.bytes) == hipSuccess && hipMemcpy(q.dev, q.host, q.bytes, hipMemcpyHostToDevice) == hipSuccess;
+    tk_error_code_t rc = ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
+    if (ok) {
+        tk_launch_logit_adjust((float*)b[0].dev, cols, rows, (const TkAdjustRow*)b[1].dev, (const int32_t*)b[2].dev, (const int32_t*)b[3].dev, (const float*)b[4].dev, nullptr);
+        if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(logits, b[0].dev, b[0].bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+    }
+    for (Buf& q : b) if (q.dev) (void)hipFree(q.dev);
+    return rc;
+}
+
 /* one host array of a probe: where it comes from, how many bytes, how far into its device allocation it is placed, whether it is read back */
 struct ProbeBuf { const void* host; size_t bytes, offset; bool out; void* dev; };
 static bool probe_upload(ProbeBuf* b, int n) {

@@ -102,12 +102,16 @@ void TkLlmBatcher::drop_ahead(int slot) {
 }
 
 bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp,
-                          PrefixRows* prefix) {
+                          PrefixRows* prefix, const TkLogitAdjust* adjust) {
     if (n <= 0) { *err = "nothing to feed"; return false; }
+    if (adjust)
+        if (const char* why = adjust->check(session_.model->hp.vocab)) { *err = std::string("logit adjustment: ") + why; return false; }
     if (slot < 0 || slot >= (int)slot_used_.size() || pos0 < 0 || pos0 + n > n_ctx_) { *err = "rows do not fit the context window"; return false; }
     Request r;
     r.slot = slot; r.pos0 = pos0; r.n = n; r.toks = toks; r.mask = mask;
     if (samp) r.samp = *samp;
+    if (adjust && !adjust->neutral()) { r.adj = *adjust; r.adjusted = true; }
+    r.hold = r.adjusted || (adjust && (adjust->repeat != 1.0f || adjust->freq != 0.0f || adjust->present != 0.0f));
     r.whole = prefix != nullptr && pos0 == 0;
     if (prefix) *prefix = PrefixRows{n, 0, 0};
     const bool stochastic = r.samp.temp > 0.0f;
@@ -115,7 +119,7 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
     if (stop_) { *err = "scheduler stopped"; return false; }
     Ahead& a = ahead_[(size_t)slot];
     if (a.st != Ahead::NONE && !a.discard) {
-        if (n == 1 && !mask && !stochastic && pos0 == a.pos && toks[0] == a.tok) { /* the row this call asks for is the one that ran (or runs) ahead */
+        if (n == 1 && !mask && !stochastic && !r.adjusted && pos0 == a.pos && toks[0] == a.tok) { /* the row this call asks for is the one that ran (or runs) ahead */
             if (a.st == Ahead::DONE) {
                 const bool ok = a.ok;
                 const int32_t got = a.sampled;
@@ -149,6 +153,7 @@ void TkLlmBatcher::loop() {
     std::vector<int32_t> sq, ps, tk, am;
     std::vector<const uint32_t*> masks;
     std::vector<TkSampleRow> samps;
+    std::vector<TkLogitAdjust> adjs;
     struct Taken { Request* r; int take, last_row; };   /* `take` rows of a request end at row `last_row` of the pass */
     struct AheadRow { int slot, row; };                  /* a sequence's run-ahead row and where it sits in the pass */
     std::vector<Taken> in_pass;
@@ -171,8 +176,8 @@ void TkLlmBatcher::loop() {
     for (;;) {
         double t_woke = 0.0;
         in_pass.clear(); completing.clear(); ahead_rows.clear(); copies.clear(); copy_for.clear();
-        sq.clear(); ps.clear(); tk.clear(); masks.clear(); samps.clear();
-        bool any_mask = false, any_samp = false;
+        sq.clear(); ps.clear(); tk.clear(); masks.clear(); samps.clear(); adjs.clear();
+        bool any_mask = false, any_samp = false, any_adj = false;
         {
             std::unique_lock<std::mutex> lk(mu_);
             cv_.wait(lk, [&] { return stop_ || !queue_.empty() || any_planned(); });
@@ -207,6 +212,7 @@ void TkLlmBatcher::loop() {
                     tk.push_back(r->toks[r->done_rows + i]);
                     masks.push_back(nullptr);
                     samps.push_back(TkSampleRow{});
+                    adjs.push_back(TkLogitAdjust{});
                 }
                 in_pass.push_back(Taken{r, take, (int)sq.size() - 1});
                 if (r->done_rows + take == r->n) {
@@ -215,6 +221,8 @@ void TkLlmBatcher::loop() {
                     samps.back() = r->samp;
                     any_mask = any_mask || r->mask != nullptr;
                     any_samp = any_samp || r->samp.temp > 0.0f;
+                    adjs.back() = r->adj;
+                    any_adj = any_adj || r->adjusted;
                 }
             };
             /* prefix cache (tk_llm_batcher.h): a whole-context request that is about to enter the pass first moves its cursor over the rows its
@@ -262,6 +270,7 @@ void TkLlmBatcher::loop() {
                     tk.push_back(a.tok);
                     masks.push_back(nullptr);
                     samps.push_back(TkSampleRow{});
+                    adjs.push_back(TkLogitAdjust{});
                     ahead_rows.push_back(AheadRow{(int)s, (int)sq.size() - 1});
                 }
             };
@@ -283,7 +292,7 @@ void TkLlmBatcher::loop() {
         bool copied_ok = true;
         if (!copies.empty()) copied_ok = session_.enqueue_kv_copy(copies.data(), (int)copies.size());
         const bool ok = copied_ok && session_.forward(nrows, sq.data(), ps.data(), tk.data(), nullptr, head ? am.data() : nullptr, head, head && any_mask ? masks.data() : nullptr,
-                                        head && any_samp ? samps.data() : nullptr);
+                                        head && any_samp ? samps.data() : nullptr, head && any_adj ? adjs.data() : nullptr);
         {
             std::lock_guard<std::mutex> lk(mu_);
             passes_++;
@@ -310,7 +319,7 @@ void TkLlmBatcher::loop() {
                     r->sampled = ok ? am[(size_t)row - 1] : -1;
                     for (auto it = queue_.begin(); it != queue_.end(); ++it)
                         if (*it == r) { queue_.erase(it); break; }
-                    if (ok) plan_ahead(r->slot, r->pos0 + r->n - 1, r->sampled, r->mask != nullptr || r->samp.temp > 0.0f);
+                    if (ok) plan_ahead(r->slot, r->pos0 + r->n - 1, r->sampled, r->mask != nullptr || r->samp.temp > 0.0f || r->hold);
                     if (!ok || ahead_[(size_t)r->slot].st != Ahead::PLANNED) held++;
                     r->finished = true;
                     r->cv.notify_all();

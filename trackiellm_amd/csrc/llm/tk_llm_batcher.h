@@ -14,7 +14,8 @@
  * comes back with the id it was just given — while the GPU waits.  So when a sequence's sampled id has been handed to its owner, the
  * scheduler feeds that id at the next position in its very next pass WITHOUT waiting for the owner (one position ahead, never more); the
  * owner's next call then finds its row in flight or already done.  Not for rows sampled under a grammar mask (the next mask depends on
- * the accepted token), not after EOS, not at the end of the context.  An owner that comes back with something else (a tool response, a
+ * the accepted token), not for rows sampled under a non-neutral logit adjustment (the next window of the repetition penalties depends on the
+ * accepted token, and the owner may change its bias list; this holds from the first sampled token on, whose window is still empty), not after EOS, not at the end of the context.  An owner that comes back with something else (a tool response, a
  * new prompt) or not at all costs one wasted row: the cache row it wrote is overwritten before anything attends to it, because positions
  * are fed in order.  Tokens are unchanged — a row's result does not depend on when or with whom it runs.
  *
@@ -68,9 +69,11 @@ public:
      * (seed, counter) instead of the arg max; such rows never run ahead (the next counter is the owner's) */
     /* prefix (optional; prepare_generation only): the tokens are the WHOLE context from position 0 (pos0 == 0), so rows the cache already holds
      * for them may be kept or copied when the prefix cache is on; receives what became of the n rows */
+    /* adjust (optional): logit bias and repetition penalties of the sampled row (common/tk_logit_adjust.h); its arrays belong to the caller until
+     * the call returns, like `mask`; checked here against the limits.  A non-neutral one keeps the row from running ahead (header comment) */
     struct PrefixRows { int32_t prompt_rows = 0, kept = 0, copied = 0; };
     bool submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp = nullptr,
-                PrefixRows* prefix = nullptr);
+                PrefixRows* prefix = nullptr, const TkLogitAdjust* adjust = nullptr);
     /* the prompt prefix cache, off by default; may change at any time, read when the scheduler first takes a prompt.  false: the model's rows are
      * not whole 16-byte words (head_dim % 8 != 0) */
     bool set_prefix_cache(bool on);
@@ -88,6 +91,9 @@ private:
         const int32_t* toks;
         const uint32_t* mask;
         TkSampleRow samp{};
+        TkLogitAdjust adj{};
+        bool adjusted = false; /* adj is not neutral */
+        bool hold = false;     /* no run-ahead from this row: adjusted, or penalties that are on over a still empty window (the next one is not) */
         int32_t sampled = -1;
         bool finished = false, ok = true;
         std::string error;

@@ -96,9 +96,14 @@ public:
     /* one pass over nrows <= TK_MAX_ROWS rows (16-row M-tiles); host arrays.  row_masks (optional): row_masks[r] = nullptr or the
      * (vocab + 31) / 32 words whose bit t says token t may be sampled for row r: grammar-constrained greedy sampling, per row, so
      * constrained and unconstrained rows share passes (and the captured graphs).  row_samp (optional): [nrows] sampling state, temp > 0
-     * = the reference's default stochastic chain for that row (tk_llm_kernels.h), else greedy */
+     * = the reference's default stochastic chain for that row (tk_llm_kernels.h), else greedy.  row_adjust (optional): [nrows] logit bias and
+     * repetition penalties per row (common/tk_logit_adjust.h), applied to the row's logits before masks and sampling see them; every row is checked
+     * before anything is enqueued.  A pass with at least one non-neutral row uploads the tables and replays graphs of its own (the ones with the
+     * k_logit_adjust launch); any other pass replays the graphs it always did and uploads nothing.  logits_host of an adjusted row are the ADJUSTED
+     * logits */
     bool forward(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, float* logits_host, int32_t* argmax_host,
-                 bool lm_head = true, const uint32_t* const* row_masks = nullptr, const TkSampleRow* row_samp = nullptr);
+                 bool lm_head = true, const uint32_t* const* row_masks = nullptr, const TkSampleRow* row_samp = nullptr,
+                 const TkLogitAdjust* row_adjust = nullptr);
     /* one pipeline stage of a pass: layers [l0, l1) on this GPU.  The first stage starts from `tok` (x_in == nullptr), later stages
      * from the residual stream x_in [nrows][d_model] fp32; every stage but the last writes the stream to x_out; the last one
      * (head == true, l1 == n_layer) samples.  x_on_host: x_in / x_out are host pointers (gloo transport), otherwise device
@@ -109,7 +114,8 @@ public:
      * holding the first sampled token so decode() can follow; first_tokens_host[nseq] optional */
     bool prefill(int nseq, int n_prompt, const int32_t* tokens, int32_t* first_tokens_host);
     /* greedy decode loop, on-device feedback, hipGraph replay.  Starts from the rows' current
-     * (tok, pos) state left by the previous forward()/decode(); out_tokens[n_steps][nrows]. */
+     * (tok, pos) state left by the previous forward()/decode(); out_tokens[n_steps][nrows].  The loop is unadjusted: it replays the plain
+     * graphs, and it clears the adjustment descriptors a previous forward() left as it clears the masks. */
     bool decode(int nrows, int n_steps, int32_t* out_tokens_host);
     bool reset();
     /* KV cache import / export: rows [pos0, pos0 + n_pos) of one (layer, sequence) as f16 bits, host arrays in [position][kv head][dim]
@@ -153,6 +159,15 @@ private:
     TkSampleRow* d_samp = nullptr;  /* [TK_MAX_ROWS] sampling state of the rows of the current pass (temp 0 = greedy); decode() continues from it */
     bool samp_dirty = false;        /* d_samp holds a stochastic row */
     TkKvCopyDesc *d_kvcopy = nullptr, *h_kvcopy = nullptr; /* [TK_MAX_ROWS] descriptors of one k_kv_copy_rows launch: device array, pinned staging */
+    /* logit adjustment of the rows of the current pass, at fixed addresses (the adjusted graphs hold them): [TK_MAX_ROWS] descriptors, the rows'
+     * windows [TK_MAX_ROWS][TK_ADJUST_MAX_RECENT], bias ids and values [TK_MAX_ROWS][TK_ADJUST_MAX_BIAS]; h_adj: one pinned staging block of
+     * the four in that order (free again when forward() has waited for the stream) */
+    TkAdjustRow* d_adj = nullptr;
+    int32_t *d_adj_ids = nullptr, *d_adj_bias_ids = nullptr;
+    float* d_adj_bias = nullptr;
+    uint8_t* h_adj = nullptr;
+    bool adj_dirty = false;   /* d_adj holds a non-neutral descriptor */
+    bool adjust_pass = false; /* set by forward(), read by enqueue_range: the pass being enqueued launches k_logit_adjust before the pick */
     std::string launch_error; /* set by enqueue_* when a launcher refuses its arguments (no HIP error is raised for that) */
     int hist_cap = 0;
     hipGraphExec_t graph_exec[2][TK_MAX_ROWS + 1] = {}; /* [long_pass][row count]: decode pass (head + sampling, every sequence once) */
@@ -160,6 +175,9 @@ private:
      * (a prompt's last chunk) */
     hipGraphExec_t graph_prefill[2][TK_MAX_ROWS + 1] = {};
     hipGraphExec_t graph_head_nf[2][TK_MAX_ROWS + 1] = {};
+    /* their siblings for passes with an adjusted row: the same launches plus k_logit_adjust in front of the pick */
+    hipGraphExec_t graph_exec_adj[2][TK_MAX_ROWS + 1] = {};
+    hipGraphExec_t graph_head_nf_adj[2][TK_MAX_ROWS + 1] = {};
     /* set by whoever describes a pass, read by enqueue_range: a multi-position pass that reaches position 128 (TK_TILED_ATT_FROM_POS) or beyond takes
      * k_attention_prefill (16 rows of a sequence per workgroup), shorter contexts k_attention's per-row form (3 us per launch quicker below ~128
      * positions, profiles/r05_prefill_attention.txt); the two are bit-identical, so the choice never shows in a result */

@@ -387,6 +387,13 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     HIPQ(hipMalloc((void**)&d_kvcopy, TK_MAX_ROWS * sizeof(TkKvCopyDesc)));
     HIPQ(hipMemset(d_kvcopy, 0, TK_MAX_ROWS * sizeof(TkKvCopyDesc)));
     HIPQ(hipHostMalloc((void**)&h_kvcopy, TK_MAX_ROWS * sizeof(TkKvCopyDesc), hipHostMallocDefault));
+    HIPQ(hipMalloc((void**)&d_adj, TK_MAX_ROWS * sizeof(TkAdjustRow)));
+    HIPQ(hipMemset(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow))); /* no window, no bias: every row is neutral */
+    HIPQ(hipMalloc((void**)&d_adj_ids, (size_t)TK_MAX_ROWS * TK_ADJUST_MAX_RECENT * 4));
+    HIPQ(hipMalloc((void**)&d_adj_bias_ids, (size_t)TK_MAX_ROWS * TK_ADJUST_MAX_BIAS * 4));
+    HIPQ(hipMalloc((void**)&d_adj_bias, (size_t)TK_MAX_ROWS * TK_ADJUST_MAX_BIAS * 4));
+    HIPQ(hipHostMalloc((void**)&h_adj, TK_MAX_ROWS * (sizeof(TkAdjustRow) + (size_t)TK_ADJUST_MAX_RECENT * 4 + (size_t)TK_ADJUST_MAX_BIAS * 8), hipHostMallocDefault));
+    adj_dirty = false;
     /* RoPE table, double precision on the host (same formula as the oracle) */
     std::vector<float> cs((size_t)mctx * half), sn((size_t)mctx * half);
     for (int p = 0; p < mctx; ++p)
@@ -417,10 +424,15 @@ TkLlmSession::~TkLlmSession() {
     for (auto& v : graph_exec) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     for (auto& v : graph_prefill) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     for (auto& v : graph_head_nf) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
+    for (auto& v : graph_exec_adj) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
+    for (auto& v : graph_head_nf_adj) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     void* ptrs[] = {kcache, vcache, x, x2, qbuf, partial, partial2, logits, rope_cos, rope_sin, d_seq, d_pos, d_tok, d_nsteps, d_hist, d_mask, d_mask_row, d_samp, d_tab, d_tiles, d_scores};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (d_kvcopy) (void)hipFree(d_kvcopy);
     if (h_kvcopy) (void)hipHostFree(h_kvcopy);
+    void* adj[] = {d_adj, d_adj_ids, d_adj_bias_ids, d_adj_bias};
+    for (void* p : adj) if (p) (void)hipFree(p);
+    if (h_adj) (void)hipHostFree(h_adj);
     free_act(&act_d); free_act(&act_qd); free_act(&act_ff);
     if (stream) (void)hipStreamDestroy(stream);
 }
@@ -781,6 +793,8 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
         tk_launch_rmsnorm_q8(x, l1 > l0 ? partial : nullptr, ks_res, D, (const float*)model->out_norm.data, h.rms_eps, D, nrows, act_d, s);
         (void)enqueue_matmul(lm, 1, D, 1, h.vocab, act_d, logits, nrows);
     }
+    /* llama.cpp's order: bias, penalties, grammar, chain — masks and sampling see the adjusted logits */
+    if (adjust_pass) tk_launch_logit_adjust(logits, h.vocab, nrows, d_adj, d_adj_ids, d_adj_bias_ids, d_adj_bias, s);
     tk_launch_argmax(logits, h.vocab, nrows, d_mask, d_mask_row, d_samp, d_tok, d_pos, d_nsteps, d_hist, TK_MAX_ROWS, s);
 }
 
@@ -831,8 +845,13 @@ bool TkLlmSession::capture_pass(hipGraphExec_t* slot, int nrows, bool lm_head, b
 }
 
 bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, float* logits_host, int32_t* argmax_host,
-                           bool lm_head, const uint32_t* const* row_masks, const TkSampleRow* row_samp) {
+                           bool lm_head, const uint32_t* const* row_masks, const TkSampleRow* row_samp, const TkLogitAdjust* row_adjust) {
     if (nrows <= 0 || nrows > TK_MAX_ROWS) { error = "nrows must be in [1,256]"; return false; }
+    bool any_adj = false;
+    for (int r = 0; r < nrows && lm_head && row_adjust; ++r) {
+        if (const char* why = row_adjust[r].check(model->hp.vocab)) { error = "logit adjustment of row " + std::to_string(r) + ": " + why; return false; }
+        any_adj = any_adj || !row_adjust[r].neutral();
+    }
     for (int r = 0; r < nrows; ++r) {
         if (seq[r] < 0 || seq[r] >= max_seq || pos[r] < 0 || pos[r] >= max_ctx || tok[r] < 0 || tok[r] >= model->hp.vocab) {
             error = "row out of range (sequence id, position or token id)";
@@ -877,17 +896,49 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
             HIPQ(hipMemsetAsync(d_samp, 0, TK_MAX_ROWS * sizeof(TkSampleRow), stream));
             samp_dirty = false;
         }
+        /* logit adjustment: the tables of the pass's rows through the pinned block (free: the last forward() waited for the stream); a neutral row
+         * gets the all-zero descriptor its workgroup returns on */
+        if (any_adj) {
+            TkAdjustRow* hd = (TkAdjustRow*)h_adj;
+            int32_t* hids = (int32_t*)(hd + TK_MAX_ROWS);
+            int32_t* hbids = hids + (size_t)TK_MAX_ROWS * TK_ADJUST_MAX_RECENT;
+            float* hbias = (float*)(hbids + (size_t)TK_MAX_ROWS * TK_ADJUST_MAX_BIAS);
+            memset(hd, 0, TK_MAX_ROWS * sizeof(TkAdjustRow));
+            for (int r = 0; r < nrows; ++r) {
+                const TkLogitAdjust& a = row_adjust[r];
+                if (a.neutral()) continue;
+                hd[r] = a.row();
+                if (a.n_recent > 0) memcpy(hids + (size_t)r * TK_ADJUST_MAX_RECENT, a.recent, (size_t)a.n_recent * 4);
+                if (a.n_bias > 0) {
+                    memcpy(hbids + (size_t)r * TK_ADJUST_MAX_BIAS, a.bias_ids, (size_t)a.n_bias * 4);
+                    memcpy(hbias + (size_t)r * TK_ADJUST_MAX_BIAS, a.bias, (size_t)a.n_bias * 4);
+                }
+            }
+            HIPQ(hipMemcpyAsync(d_adj, hd, TK_MAX_ROWS * sizeof(TkAdjustRow), hipMemcpyHostToDevice, stream));
+            HIPQ(hipMemcpyAsync(d_adj_ids, hids, (size_t)nrows * TK_ADJUST_MAX_RECENT * 4, hipMemcpyHostToDevice, stream));
+            HIPQ(hipMemcpyAsync(d_adj_bias_ids, hbids, (size_t)nrows * TK_ADJUST_MAX_BIAS * 4, hipMemcpyHostToDevice, stream));
+            HIPQ(hipMemcpyAsync(d_adj_bias, hbias, (size_t)nrows * TK_ADJUST_MAX_BIAS * 4, hipMemcpyHostToDevice, stream));
+            adj_dirty = true;
+        } else if (adj_dirty) {
+            HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream));
+            adj_dirty = false;
+        }
     }
+    adjust_pass = any_adj;
     /* a pass replays a captured graph (one per (row count, form)): a host that asks for one token at a time — the reference's runner
      * API — pays one graph launch, not ~260 kernel launches, per token; masked rows ride the same graphs (the table above is data) */
     hipGraphExec_t* slot = !graphs_enabled() ? nullptr
                            : !lm_head ? &graph_prefill[tiled_pass][nrows] : distinct ? &graph_exec[long_pass][nrows] : &graph_head_nf[tiled_pass][nrows];
+    if (slot && any_adj) slot = distinct ? &graph_exec_adj[long_pass][nrows] : &graph_head_nf_adj[tiled_pass][nrows];
     if (slot) {
-        if (!capture_pass(slot, nrows, lm_head, lm_head && distinct)) return false;
+        const bool captured = capture_pass(slot, nrows, lm_head, lm_head && distinct);
+        adjust_pass = false; /* whoever enqueues or captures next (decode(), prefill(), a pipeline stage) describes a plain pass */
+        if (!captured) return false;
         HIPQ(hipGraphLaunch(*slot, stream));
     } else {
         launch_error.clear();
         enqueue_pass(nrows, lm_head, distinct);
+        adjust_pass = false;
     }
     if (!launch_error.empty()) { error = launch_error; (void)hipStreamSynchronize(stream); return false; }
     HIPQ(hipGetLastError());
@@ -917,6 +968,7 @@ bool TkLlmSession::forward_stage(int nrows, const int32_t* seq, const int32_t* p
     if (tok) HIPQ(hipMemcpyAsync(d_tok, tok, nrows * 4, hipMemcpyHostToDevice, stream));
     HIPQ(hipMemsetAsync(d_nsteps, 0, TK_MAX_ROWS * 4, stream));
     if (mask_rows_dirty) { HIPQ(hipMemsetAsync(d_mask_row, 0xFF, TK_MAX_ROWS * 4, stream)); mask_rows_dirty = false; }
+    if (adj_dirty) { HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream)); adj_dirty = false; }
     const size_t xb = (size_t)nrows * h.d_model * 4;
     if (x_in) HIPQ(hipMemcpyAsync(x, x_in, xb, x_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
     bool distinct = true;
@@ -998,6 +1050,7 @@ bool TkLlmSession::decode(int nrows, int n_steps, int32_t* out_tokens_host) {
     for (int r = 0; r < nrows; ++r) top0 = hpos[r] > top0 ? hpos[r] : top0;
     HIPQ(hipMemsetAsync(d_nsteps, 0, TK_MAX_ROWS * 4, stream));
     if (mask_rows_dirty) { HIPQ(hipMemsetAsync(d_mask_row, 0xFF, TK_MAX_ROWS * 4, stream)); mask_rows_dirty = false; } /* the loop samples unconstrained */
+    if (adj_dirty) { HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream)); adj_dirty = false; } /* and unadjusted: it replays the plain graphs */
     hipEvent_t e0, e1;
     HIPQ(hipEventCreate(&e0));
     HIPQ(hipEventCreate(&e1));

@@ -98,6 +98,10 @@ void tk_launch_quant_q8(const float* hbuf, int FF, int nrows, TkActQ8 out, hipSt
 /* allow_base / allow_row (both optional): per-row allowed-token bit masks, allow_row[r] = mask index or -1; samp (optional): [nrows] */
 void tk_launch_argmax(const float* logits, int vocab, int nrows, const uint32_t* allow_base, const int32_t* allow_row, TkSampleRow* samp, int32_t* tok,
                       int32_t* pos, int32_t* nsteps, int32_t* hist, int hist_stride, hipStream_t s);
+#include "../common/tk_logit_adjust.h"
+/* logit bias + repetition penalties on logits [nrows][vocab], in place, before tk_launch_argmax: desc [nrows]; ids [nrows][TK_ADJUST_MAX_RECENT] the
+ * rows' windows; bias_ids / bias [nrows][TK_ADJUST_MAX_BIAS].  The caller has checked every row with tk_adjust_check: the kernel trusts the ids */
+void tk_launch_logit_adjust(float* logits, int vocab, int nrows, const TkAdjustRow* desc, const int32_t* ids, const int32_t* bias_ids, const float* bias, hipStream_t s);
 
 /* the attention launch a pass takes: kernel 0 = k_attention<gq, fused, head_dim, chunk> (chunk = positions per ring slot, slots = ring depth 2), kernel 1 =
  * k_attention_narrow (gq 2, chunk = positions resident per chunk, the whole context when it fits) */

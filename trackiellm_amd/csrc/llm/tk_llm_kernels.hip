@@ -4168,6 +4168,29 @@ void tk_launch_argmax(const float* logits, int vocab, int nrows, const uint32_t*
 }
 
 /* ------------------------------------------------------------------------------------------
+ * logit bias + repetition penalties (common/tk_logit_adjust.h), in front of k_argmax on the passes that carry an adjusted row: one workgroup
+ * per row, lane j holds bias entry j, then window id j.  The window sits in LDS: each lane compares its id with all of them (256 x 256
+ * compares at most) to count it and to learn whether it holds the first occurrence — the one lane that writes the token's logit.  A neutral
+ * row's workgroup returns before it reads anything but its descriptor.
+ * ------------------------------------------------------------------------------------------ */
+__global__ __launch_bounds__(TK_ADJUST_LANES) void k_logit_adjust(float* logits, int vocab, const TkAdjustRow* __restrict__ desc, const int32_t* __restrict__ ids,
+                                                                  const int32_t* __restrict__ bias_ids, const float* __restrict__ bias) {
+    __shared__ int32_t win[TK_ADJUST_MAX_RECENT];
+    const int r = blockIdx.x, j = threadIdx.x;
+    const TkAdjustRow d = desc[r];
+    if (tk_adjust_neutral(d)) return; /* uniform per workgroup */
+    float* lg = logits + (int64_t)r * vocab;
+    if (j < d.n_recent) win[j] = ids[(size_t)r * TK_ADJUST_MAX_RECENT + j];
+    if (j < d.n_bias) tk_adjust_bias_lane(lg, bias_ids + (size_t)r * TK_ADJUST_MAX_BIAS, bias + (size_t)r * TK_ADJUST_MAX_BIAS, j);
+    __syncthreads(); /* the window is in LDS, and every bias is in global memory before a penalty lane of this workgroup reads its logit */
+    if (j < d.n_recent) tk_adjust_penalty_lane(lg, d, win, j);
+}
+
+void tk_launch_logit_adjust(float* logits, int vocab, int nrows, const TkAdjustRow* desc, const int32_t* ids, const int32_t* bias_ids, const float* bias, hipStream_t s) {
+    hipLaunchKernelGGL(k_logit_adjust, dim3(nrows), dim3(TK_ADJUST_LANES), 0, s, logits, vocab, desc, ids, bias_ids, bias);
+}
+
+/* ------------------------------------------------------------------------------------------
  * per-device opt-in to > 64 KiB of dynamic LDS for every kernel above (see the comment at TK_MAX_DYN_LDS)
  * ------------------------------------------------------------------------------------------ */
 const char* tk_llm_prepare_device(int device) {

@@ -255,6 +255,26 @@ class LlmSession:
         check(lib().tk_mi355x_llm_forward_sampled(self.h, n, _p(seq), _p(pos), _p(tok), tab, _p(logits), _p(ids)))
         return logits, ids
 
+    def forward_adjusted(self, seq, pos, tok, adjust, sampling=None, want_logits=True):
+        """forward_sampled() with a logit adjustment per row (tk_mi355x_llm_forward_adjusted): adjust = the specs of pick.logit_adjust_rows, one per
+        row (None = a neutral row); sampling as forward_sampled's, or None = every row greedy.  The logits returned are the ADJUSTED ones"""
+        from .pick import logit_adjust_rows
+        seq = np.ascontiguousarray(seq, dtype=np.int32)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        tok = np.ascontiguousarray(tok, dtype=np.int32)
+        n = len(seq)
+        tab = None
+        if sampling is not None:
+            tab = (Sampling * n)()
+            for r, (temp, top_k, top_p, min_p, seed, counter) in enumerate(sampling):
+                tab[r] = Sampling(temp, top_p, min_p, top_k, seed, counter, 0)
+        adj, keep = logit_adjust_rows(adjust)
+        logits = np.empty((n, self.vocab), dtype=np.float32) if want_logits else None
+        ids = np.empty(n, dtype=np.int32)
+        check(lib().tk_mi355x_llm_forward_adjusted(self.h, n, _p(seq), _p(pos), _p(tok), tab, adj, _p(logits), _p(ids)))
+        del keep
+        return logits, ids
+
     def forward_stage(self, seq, pos, layer0, layer1, tok=None, x_in=None, x_out=None, head=False, on_host=True):
         """layers [layer0, layer1) of one pass (pipeline stage).  x_in / x_out: float32 [n][d_model] numpy arrays (on_host) or raw
         device addresses (ints, e.g. torch_tensor.data_ptr()) on this session's GPU.  Returns arg max ids when head."""
@@ -492,6 +512,29 @@ class LlmRunner:
     def set_sampling(self, temperature, top_k=40, top_p=0.95, min_p=0.05):
         """the reference's default stochastic chain (llama_sampling_default_params) instead of greedy; temperature 0 = greedy again"""
         check(lib().tk_mi355x_llm_runner_set_sampling(self.h, C.c_float(temperature), top_k, C.c_float(top_p), C.c_float(min_p)))
+
+    def set_penalties(self, last_n, repeat=1.0, freq=0.0, present=0.0):
+        """repetition penalties over the last last_n accepted ids (llama_sample_repetition_penalties); last_n 0 = off; from the next sampled token"""
+        check(lib().tk_mi355x_llm_runner_set_penalties(self.h, int(last_n), C.c_float(repeat), C.c_float(freq), C.c_float(present)))
+
+    def set_logit_bias(self, ids, bias):
+        """replaces the runner's bias list: logit[ids[j]] += bias[j] before everything else (-inf bans a token); empty lists clear it"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        bias = np.ascontiguousarray(bias, dtype=np.float32).reshape(-1)
+        if ids.size != bias.size:
+            raise ValueError("set_logit_bias: ids and bias must have one length")
+        check(lib().tk_mi355x_llm_runner_set_logit_bias(self.h, int(ids.size), _p(ids) if ids.size else None, _p(bias) if bias.size else None))
+
+    def recent_tokens(self):
+        """the ids accepted since the last prepare(), oldest first (the most recent 256)"""
+        f = lib().tk_mi355x_llm_runner_recent_tokens
+        f.restype = C.c_int32
+        out = np.zeros(256, np.int32)
+        n = f(self.h, _p(out), 256)
+        return out[:max(n, 0)].tolist()
+
+    def add_tool_response(self, tool_name, tool_output):
+        check(lib().tk_llm_runner_add_tool_response(self.h, tool_name.encode(), tool_output.encode()))
 
     def last_prompt_rows(self):
         """(rows, of them kept in place, of them copied from another runner's slot) of the last prepare()"""

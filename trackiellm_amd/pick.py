@@ -1,4 +1,4 @@
-"""The token-selection kernels one launch at a time: the test hook tk_mi355x_token_pick_probe."""
+"""The token-selection kernels one launch at a time: the test hooks tk_mi355x_token_pick_probe and tk_mi355x_logit_adjust_probe."""
 import ctypes as C
 
 import numpy as np
@@ -66,3 +66,49 @@ def token_pick_probe(kind, logits, rows, cols, ld=None, masks=None, allow_row=No
     lib().tk_mi355x_token_pick_probe.argtypes = [C.c_int, C.POINTER(TokenPickProbe)]
     check(lib().tk_mi355x_token_pick_probe(device, C.byref(p)))
     return io
+
+
+class LogitAdjust(C.Structure):  # tk_mi355x_logit_adjust_t
+    _fields_ = [("repeat", C.c_float), ("freq", C.c_float), ("present", C.c_float), ("n_recent", C.c_int32), ("recent", C.c_void_p),
+                ("n_bias", C.c_int32), ("bias_ids", C.c_void_p), ("bias", C.c_void_p)]
+
+
+def logit_adjust_rows(specs):
+    """[None | dict(repeat=1, freq=0, present=0, recent=None, bias_ids=None, bias=None, n_recent=None, n_bias=None)] -> (a LogitAdjust array, the
+    NumPy arrays it points into: keep them alive as long as the array is used).  None = a neutral row.  n_recent / n_bias default to the arrays'
+    lengths; given, they are passed as they are (a count without an array is a NULL pointer with that count)."""
+    tab, keep = (LogitAdjust * len(specs))(), []
+    for r, sp in enumerate(specs):
+        sp = sp or {}
+        arrs = []
+        for name, dtype in (("recent", np.int32), ("bias_ids", np.int32), ("bias", np.float32)):
+            a = sp.get(name)
+            a = None if a is None else np.ascontiguousarray(a, dtype).reshape(-1)
+            arrs.append(a)
+            keep.append(a)
+        recent, bias_ids, bias = arrs
+        n_recent = sp.get("n_recent", 0 if recent is None else recent.size)
+        n_bias = sp.get("n_bias", 0 if bias_ids is None else bias_ids.size)
+        tab[r] = LogitAdjust(sp.get("repeat", 1.0), sp.get("freq", 0.0), sp.get("present", 0.0), n_recent, None if recent is None else recent.ctypes.data,
+                             n_bias, None if bias_ids is None else bias_ids.ctypes.data, None if bias is None else bias.ctypes.data)
+    return tab, keep
+
+
+def logit_adjust_probe(logits, rows, cols, adjust, device=0, n_logits=None):
+    """ONE launch of k_logit_adjust (tk_mi355x_logit_adjust_probe) on a COPY of logits (float32, [rows][cols] packed), which is returned; adjust:
+    the specs of logit_adjust_rows, one per row.  device < 0: the same per-row function in a host loop, no GPU touched.  A refusal raises TkError
+    with the copy untouched: pass a float32 array as `out` through logit_adjust_probe_into to see that"""
+    out = np.array(logits, dtype=np.float32, order="C", copy=True).reshape(-1)
+    logit_adjust_probe_into(out, rows, cols, adjust, device=device, n_logits=n_logits)
+    return out.reshape(rows, cols) if out.size == rows * cols else out
+
+
+def logit_adjust_probe_into(out, rows, cols, adjust, device=0, n_logits=None):
+    """logit_adjust_probe in place on the C-contiguous float32 array `out`"""
+    if out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("logit_adjust_probe_into: out must be a C-contiguous float32 array")
+    tab, keep = logit_adjust_rows(adjust)
+    f = lib().tk_mi355x_logit_adjust_probe
+    f.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    check(f(device, rows, cols, out.ctypes.data, out.size if n_logits is None else n_logits, C.cast(tab, C.c_void_p) if len(adjust) else None))
+    del keep
