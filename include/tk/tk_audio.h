@@ -137,6 +137,28 @@ TK_API void tk_mi355x_asr_last_decode(const tk_asr_whisper_context_t* ctx, float
 /* the decoder prompt the next transcription starts from (English-only: <|sot|><|notimestamps|>; multilingual: + language and task
  * tokens, whisper.cpp's whisper_full order); returns the count, -1 when the configured language has no token */
 TK_API int tk_mi355x_asr_prompt_tokens(tk_asr_whisper_context_t* ctx, int32_t* out, int cap);
+/* Language detection: language = "auto" (tk_asr_whisper_config_t.language, tk_asr_whisper_set_language) on a multilingual vocabulary (>= 51865
+ * tokens) is whisper.cpp's: every utterance decodes <|startoftranscript|>, the most probable language token (soft-max over the language tokens'
+ * logits, csrc/common/tk_lang_pick.h: first index of the maximum) becomes the prompt's language token, then the decode goes on in that language —
+ * on the device, between the first and the second decoder step of the same transcription, with no extra encoder or decoder pass.  The prompt
+ * tk_mi355x_asr_prompt_tokens reports then holds -1 in the language position.  English-only vocabularies ignore the string as before.
+ *   detect_language: whisper_lang_auto_detect for `batch` utterances — lang_ids [batch] (index into Whisper's language table), probs (optional)
+ *     [batch][n_lang], n_lang = n_vocab - 51865 + 99, the probability of every language; TK_ERROR_INVALID_ARGUMENT on an English-only model;
+ *   last_languages: per row of the context's last transcription or detection the language its prompt named and its probability — detected, or the
+ *     configured one with probability 1 (English-only: 0 = "en"); returns the number of rows, at most `cap` are written; either array may be NULL;
+ *   transcribe_tokens_langs: transcribe_tokens with one language per utterance, lang_ids [batch] = a language id or -1 = detect it: a batch may mix
+ *     detected and configured rows (the context's own language is not used; its task is);
+ *   last_language_logits: the language tokens' logits the last detect_language decided on, [batch][n_lang] (a parity hook: they are the slice
+ *     [sot + 1, sot + 1 + n_lang) of the <|startoftranscript|> step's logits); returns the number of floats, at most `cap` are written;
+ *   whisper_lang_code / whisper_lang_id: Whisper's language table ("en" = 0 ... "yue" = 99); NULL / -1 for what it does not hold. */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_asr_detect_language(tk_asr_whisper_context_t* ctx, int batch, const int16_t* pcm, int n_samples, int32_t* lang_ids,
+                                                                  float* probs);
+TK_API int tk_mi355x_asr_last_languages(const tk_asr_whisper_context_t* ctx, int32_t* ids, float* probs, int cap);
+TK_API int tk_mi355x_asr_last_language_logits(const tk_asr_whisper_context_t* ctx, float* out, int cap);
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_asr_transcribe_tokens_langs(tk_asr_whisper_context_t* ctx, int batch, const int16_t* pcm, int n_samples, int n_steps,
+                                                                          const int32_t* lang_ids, int32_t* tokens_out, float* logits_out);
+TK_API const char* tk_mi355x_whisper_lang_code(int id);
+TK_API int tk_mi355x_whisper_lang_id(const char* code);
 /* geometry of a created context (a whisper.cpp ggml checkpoint brings its own) */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_asr_get_hparams(tk_asr_whisper_context_t* ctx, tk_mi355x_whisper_hparams_t* out);
 /* whisper.cpp "ggml" checkpoint (the file tk_asr_whisper_config_t.model_path names, src/audio/tk_asr_whisper.c:238): parse header,

@@ -455,6 +455,15 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_token_pick_probe(int device, tk_mi
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_logit_adjust_probe(int device, int32_t rows, int32_t cols, float* logits, int64_t n_logits,
                                                                  const tk_mi355x_logit_adjust_t* adjust);
 
+/* test hook for Whisper's language detection (csrc/common/tk_lang_pick.h), the contract of tk_mi355x_token_pick_probe: ONE launch of k_lang_pick
+ * (tk_launch_lang_pick) on logits [rows] rows `ld` floats apart (n_logits floats in all), language tokens tok0 .. tok0 + n_lang - 1.  auto_row [rows]:
+ * != 0 = the row stores its language token tok0 + id into slot[row]; slot [rows] IN/OUT (read back whole: other rows come back as they went in);
+ * ids [rows] OUT; probs [rows][n_lang] OUT.  Everything is validated before anything is launched (TK_ERROR_INVALID_ARGUMENT, nothing written): a
+ * NULL array, rows outside [1, 4096], n_lang outside [1, 128], tok0 < 0 or tok0 + n_lang > cols, ld < cols, n_logits < (rows - 1) ld + cols, a
+ * +inf logit in a language slice.  device < 0: the same per-row function in a host loop, no GPU touched */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_lang_pick_probe(int device, int32_t rows, int32_t cols, int32_t ld, const float* logits, int64_t n_logits, int32_t tok0,
+                                                              int32_t n_lang, const int32_t* auto_row, int32_t* slot, int32_t* ids, float* probs);
+
 /* test hook for the perception streams' row and layout kernels (csrc/nn/tk_nn_kernels): ONE launch of one launcher on host arrays, so that
  * shapes no network sends (pitches wider than the extent, odd sizes around the kernels' 256 / 2048 thresholds, unaligned bases, rows that are
  * no multiple of 16) reach each kernel alone.  The contract is the GEMM probe's: a / b / c / idx / pos_idx are inputs of n_a / n_b / n_c /

@@ -16,7 +16,7 @@ from .vision import onnx_run, detector_post_probe, DetectorPostProbe, BOX_DTYPE,
 from .nn import GemmProbe, gemm_probe, gemm_code, attention_h3_probe, GEMM_F32, GEMM_F32_TALL, GEMM_F32_BIG, GEMM_H3_TALL, GEMM_H3_BIG  # noqa: F401,E402
 from .nn import NnRowProbe, nn_row_probe, ROW_CONV_STEM, ROW_IM2COL, ROW_IM2COL1D, ROW_MAXPOOL5, ROW_UPSAMPLE2X, ROW_COPY_COLS, ROW_LAYERNORM, ROW_SOFTMAX_ROWS, ROW_ADD_ROWS, ROW_EMBED_ROWS, ROW_ATTEND1  # noqa: F401,E402
 from .nn import SOFTMAX_GENERIC, SOFTMAX_REG, SOFTMAX_WAVE, IM2COL_ELEMENT, IM2COL_V4  # noqa: F401,E402
-from .pick import LogitAdjust, logit_adjust_rows, logit_adjust_probe, logit_adjust_probe_into  # noqa: F401,E402
+from .pick import LogitAdjust, logit_adjust_rows, logit_adjust_probe, logit_adjust_probe_into, lang_pick_probe  # noqa: F401,E402
 from .pick import TokenPickProbe, token_pick_probe, sampling_rows, SAMPLING_DTYPE, PICK_ARGMAX, PICK_ARGMAX_ROWS, PICK_ROWS, PICK_ROWS_FILTERED  # noqa: F401,E402
-from .audio import Asr, Vad, WhisperHP, WHISPER_TINY_EN, AudioPipeline  # noqa: F401,E402
+from .audio import Asr, Vad, WhisperHP, WHISPER_TINY_EN, AudioPipeline, whisper_lang_code, whisper_lang_id  # noqa: F401,E402
 from .cortex import Cortex, RocmDispatcher, PreprocessParams, DepthPostParams, DepthToPointsParams, Float3  # noqa: F401,E402

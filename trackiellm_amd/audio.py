@@ -26,7 +26,7 @@ class AsrResult(C.Structure):
 
 
 class Asr:
-    def __init__(self, model="synthetic://whisper-tiny.en?seed=6", hp=None, seed=6, device=0, max_batch=1, sample_rate=16000):
+    def __init__(self, model="synthetic://whisper-tiny.en?seed=6", hp=None, seed=6, device=0, max_batch=1, sample_rate=16000, language="en", translate=False):
         self.h = C.c_void_p()
         if hp is not None:
             self.hp = hp
@@ -35,7 +35,7 @@ class Asr:
             self.hp = WHISPER_TINY_EN()
             lib().tk_path_create.restype = C.POINTER(_Path)
             p = lib().tk_path_create(model.encode())
-            cfg = _AsrConfig(p, b"en", False, sample_rate, None, 4, 16384, 0.01)
+            cfg = _AsrConfig(p, language.encode() if language is not None else None, bool(translate), sample_rate, None, 4, 16384, 0.01)
             try:
                 check(lib().tk_asr_whisper_create(C.byref(self.h), C.byref(cfg)))
             finally:
@@ -121,6 +121,48 @@ class Asr:
     def set_language(self, lang):
         return lib().tk_asr_whisper_set_language(self.h, lang.encode() if lang is not None else None)
 
+    def n_lang(self):
+        """language tokens of this vocabulary (0: English-only)"""
+        return self.hp.n_vocab - 51865 + 99 if self.hp.n_vocab >= 51865 else 0
+
+    def detect_language(self, pcm):
+        """whisper.cpp's whisper_lang_auto_detect for pcm [B][n] -> (ids [B], probs [B][n_lang]); raises TkError on an English-only model"""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        B, n = pcm.shape
+        ids = np.zeros(B, np.int32)
+        probs = np.zeros((B, max(self.n_lang(), 1)), np.float32)
+        check(lib().tk_mi355x_asr_detect_language(self.h, B, pcm.ctypes.data_as(C.c_void_p), n, ids.ctypes.data_as(C.c_void_p), probs.ctypes.data_as(C.c_void_p)))
+        return ids, probs
+
+    def last_language_logits(self):
+        """[B][n_lang]: the language tokens' logits the last detect_language decided on"""
+        n = lib().tk_mi355x_asr_last_language_logits(self.h, None, 0)
+        out = np.zeros(max(n, 0), np.float32)
+        if n > 0:
+            lib().tk_mi355x_asr_last_language_logits(self.h, out.ctypes.data_as(C.c_void_p), n)
+        return out.reshape(-1, self.n_lang()) if n > 0 else out
+
+    def last_languages(self):
+        """(ids, probabilities) per row of the last transcription or detection: detected, or the configured language with probability 1"""
+        n = lib().tk_mi355x_asr_last_languages(self.h, None, None, 0)
+        ids, probs = np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.float32)
+        if n > 0:
+            lib().tk_mi355x_asr_last_languages(self.h, ids.ctypes.data_as(C.c_void_p), probs.ctypes.data_as(C.c_void_p), n)
+        return ids, probs
+
+    def transcribe_tokens_langs(self, pcm, n_steps, lang_ids):
+        """transcribe_tokens with one language per utterance: lang_ids [B] = a language id or -1 = detect it -> (tokens [B][n_steps], first logits)"""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        B, n = pcm.shape
+        lang_ids = np.ascontiguousarray(lang_ids, np.int32)
+        if lang_ids.shape != (B,):
+            raise ValueError("transcribe_tokens_langs: one language id per utterance")
+        toks = np.zeros((B, n_steps), np.int32)
+        lg = np.empty((B, self.hp.n_vocab), np.float32)
+        check(lib().tk_mi355x_asr_transcribe_tokens_langs(self.h, B, pcm.ctypes.data_as(C.c_void_p), n, n_steps, lang_ids.ctypes.data_as(C.c_void_p),
+                                                          toks.ctypes.data_as(C.c_void_p), lg.ctypes.data_as(C.c_void_p)))
+        return toks, lg
+
     def prompt_tokens(self):
         buf = (C.c_int32 * 8)()
         n = lib().tk_mi355x_asr_prompt_tokens(self.h, buf, 8)
@@ -142,6 +184,18 @@ class Asr:
             self.close()
         except Exception:
             pass
+
+
+def whisper_lang_code(i):
+    """Whisper's language table: id -> code ("en" = 0 ... "yue" = 99), None outside it"""
+    lib().tk_mi355x_whisper_lang_code.restype = C.c_char_p
+    c = lib().tk_mi355x_whisper_lang_code(int(i))
+    return None if c is None else c.decode()
+
+
+def whisper_lang_id(code):
+    """code -> id, -1 for a code the table does not hold"""
+    return lib().tk_mi355x_whisper_lang_id(code.encode() if code is not None else None)
 
 
 class _VadConfig(C.Structure):

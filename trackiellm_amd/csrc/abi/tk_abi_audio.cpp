@@ -15,6 +15,7 @@
 #include "../audio/tk_audio_engine.h"
 #include "../audio/tk_vad_graph.h"
 #include "../audio/tk_whisper_ggml.h"
+#include "../common/tk_lang_pick.h"
 #include "tk/tk_audio.h"
 #include "tk/tk_mi355x_ext.h"
 
@@ -65,6 +66,8 @@ struct AsrReq {
     int32_t* tokens = nullptr;   /* [n_steps] */
     float* logprobs = nullptr;   /* [n_steps], policy / ref only */
     int32_t result_len = 0, status = 0; /* ref only */
+    int32_t lang_id = -1;        /* the language the decoder's prompt named: detected (prompt[1] == -1) or configured */
+    float lang_prob = 1.0f;
     bool ok = false, done = false;
     std::string err;
 };
@@ -169,6 +172,7 @@ struct SharedAsr {
                         for (int b = 0; b < B; ++b) memcpy(job[b]->tokens, &toks[(size_t)b * first->n_steps], (size_t)first->n_steps * sizeof(int32_t));
                 }
                 if (!ok) err = eng->error;
+                for (int b = 0; ok && b < B && b < (int)eng->last_lang_id.size(); ++b) { job[b]->lang_id = eng->last_lang_id[(size_t)b]; job[b]->lang_prob = eng->last_lang_prob[(size_t)b]; }
             }
             el.unlock();
             lk.lock();
@@ -211,6 +215,14 @@ struct tk_asr_whisper_context_s {
     uint64_t policy_seed = 0;
     float last_temperature = 0.0f, last_avg_logprob = 0.0f;
     int last_attempts = 0;
+    std::vector<int32_t> last_lang_ids; /* per row of the last decode / detection: tk_mi355x_asr_last_languages */
+    std::vector<float> last_lang_probs;
+    std::vector<float> last_lang_logits; /* [rows][n_lang] the last tk_mi355x_asr_detect_language decided on */
+    void note_languages(const int32_t* ids, const float* probs, int n) {
+        last_lang_ids.assign(ids, ids + n);
+        last_lang_probs.assign(probs, probs + n);
+        if (!multilingual) { last_lang_ids.assign((size_t)n, 0); last_lang_probs.assign((size_t)n, 1.0f); } /* an English-only vocabulary: "en", whatever the string */
+    }
     ~tk_asr_whisper_context_s() {
         if (sh) { std::lock_guard<std::mutex> lk(sh->mu); sh->handles--; }
     }
@@ -224,23 +236,27 @@ static const char* const k_whisper_langs[] = {
     "br", "eu", "is", "hy", "ne", "mn", "bs", "kk", "sq", "sw", "gl", "mr", "pa", "si", "km", "sn", "yo", "so", "af", "oc", "ka", "be", "tg", "sd", "gu",
     "am", "yi", "lo", "uz", "fo", "ht", "ps", "tk", "nn", "mt", "sa", "lb", "my", "bo", "tl", "mg", "as", "tt", "haw", "ln", "ha", "ba", "jw", "su", "yue"};
 
+#define TK_WHISPER_LANGS ((int)(sizeof k_whisper_langs / sizeof k_whisper_langs[0]))
+
 static int whisper_lang_id(const std::string& code) {
-    for (int i = 0; i < (int)(sizeof k_whisper_langs / sizeof k_whisper_langs[0]); ++i)
+    for (int i = 0; i < TK_WHISPER_LANGS; ++i)
         if (code == k_whisper_langs[i]) return i;
     return -1;
 }
 
 /* decoder prompt, as whisper.cpp's whisper_full builds it: English-only vocabularies start from <|startoftranscript|> alone;
  * multilingual ones add the language and task tokens; <|notimestamps|> closes both (the reference's wrapper concatenates segment
- * texts only, tk_asr_whisper.c:160-181).  Returns false for a language the vocabulary has no token for. */
+ * texts only, tk_asr_whisper.c:160-181).  Returns false for a language the vocabulary has no token for.  "auto" on a multilingual
+ * vocabulary puts -1 into the language position: every utterance detects its own language on the device (TkAsr::transcribe). */
 static bool asr_prompt(const tk_asr_whisper_context_s* c, std::vector<int32_t>* out, std::string* why, bool timestamps = false) {
     out->clear();
     out->push_back(c->sot);
     if (c->multilingual) {
         const int n_lang = c->sh->model.hp.n_vocab - 51865 + 99; /* 99 languages at 51865 tokens, 100 (+ yue) at 51866 */
-        int id = whisper_lang_id(c->language.empty() || c->language == "auto" ? std::string("en") : c->language); /* no language detection pass: "auto" decodes as English */
+        const bool detect = c->language == "auto";
+        const int id = detect ? 0 : whisper_lang_id(c->language.empty() ? std::string("en") : c->language);
         if (id < 0 || id >= n_lang) { *why = "unknown language \"" + c->language + "\""; return false; }
-        out->push_back(c->sot + 1 + id);
+        out->push_back(detect ? -1 : c->sot + 1 + id);
         out->push_back(c->sot + 1 + n_lang + (c->translate ? 0 : 1)); /* <|translate|>, <|transcribe|> follow the language block */
     }
     if (!timestamps) out->push_back(c->nots); /* the reference leaves no_timestamps at its default (off): its decodes start without this token */
@@ -378,6 +394,7 @@ static tk_error_code_t asr_run_ref(tk_asr_whisper_context_s* c, const int16_t* p
         if (!r.ok) return afail(TK_ERROR_INFERENCE_FAILED, r.err);
         if (result_len) *result_len = r.result_len;
         if (status) *status = r.status;
+        c->note_languages(&r.lang_id, &r.lang_prob, 1);
         return TK_SUCCESS;
     }
     std::lock_guard<std::mutex> lk(sh->eng_mu);
@@ -389,15 +406,16 @@ static tk_error_code_t asr_run_ref(tk_asr_whisper_context_s* c, const int16_t* p
         return afail(TK_ERROR_INFERENCE_FAILED, sh->eng->error);
     if (result_len) *result_len = rl;
     if (status) *status = stt;
+    c->note_languages(sh->eng->last_lang_id.data(), sh->eng->last_lang_prob.data(), 1);
     return TK_SUCCESS;
 }
 
 /* one decode of `batch` utterances for this context: through the scheduler (shared contexts, one utterance per call) or straight on the engine */
 static tk_error_code_t asr_run(tk_asr_whisper_context_s* c, int batch, const int16_t* pcm, int n_samples, const std::vector<int32_t>& prompt, int n_steps, bool policy,
                                float temperature, uint64_t seed, int32_t* tokens_out, float* logprobs_out, std::vector<float>* mel, std::vector<float>* enc,
-                               std::vector<float>* lg) {
+                               std::vector<float>* lg, const int32_t* lang_slot = nullptr) {
     SharedAsr* sh = c->sh.get();
-    if (sh->scheduled && batch == 1 && !mel && !enc && !lg) {
+    if (sh->scheduled && batch == 1 && !mel && !enc && !lg && !lang_slot) {
         AsrReq r;
         r.pcm = pcm; r.n_samples = n_samples; r.n_steps = n_steps; r.prompt = prompt; r.fast = c->fast; r.policy = policy; r.temperature = temperature; r.seed = seed;
         r.tokens = tokens_out; r.logprobs = logprobs_out;
@@ -405,16 +423,20 @@ static tk_error_code_t asr_run(tk_asr_whisper_context_s* c, int batch, const int
         if (n_samples < 0 || n_samples > h.n_samples()) return afail(TK_ERROR_INFERENCE_FAILED, "audio longer than the model window");
         if (prompt.empty() || (int)prompt.size() + n_steps > h.n_text_ctx) return afail(TK_ERROR_INFERENCE_FAILED, "prompt + steps exceed the text context");
         sh->submit(&r);
-        return r.ok ? TK_SUCCESS : afail(TK_ERROR_INFERENCE_FAILED, r.err);
+        if (!r.ok) return afail(TK_ERROR_INFERENCE_FAILED, r.err);
+        c->note_languages(&r.lang_id, &r.lang_prob, 1);
+        return TK_SUCCESS;
     }
     /* the test / bench entry points on a shared context (copies of the mel, batches): the engine itself, one caller at a time */
     std::lock_guard<std::mutex> lk(sh->eng_mu);
     std::string err;
     if (!sh->ensure_engine(batch, &err)) return afail(TK_ERROR_GPU_MEMORY, err);
     sh->eng->fast = c->fast;
-    const bool ok = policy ? sh->eng->transcribe_policy(batch, pcm, n_samples, prompt.data(), (int)prompt.size(), n_steps, temperature, seed, tokens_out, logprobs_out)
-                           : sh->eng->transcribe(batch, pcm, n_samples, prompt.data(), (int)prompt.size(), n_steps, tokens_out, mel, enc, lg);
-    return ok ? TK_SUCCESS : afail(TK_ERROR_INFERENCE_FAILED, sh->eng->error);
+    const bool ok = policy ? sh->eng->transcribe_policy(batch, pcm, n_samples, prompt.data(), (int)prompt.size(), n_steps, temperature, seed, tokens_out, logprobs_out, lang_slot)
+                           : sh->eng->transcribe(batch, pcm, n_samples, prompt.data(), (int)prompt.size(), n_steps, tokens_out, mel, enc, lg, lang_slot);
+    if (!ok) return afail(TK_ERROR_INFERENCE_FAILED, sh->eng->error);
+    c->note_languages(sh->eng->last_lang_id.data(), sh->eng->last_lang_prob.data(), batch);
+    return TK_SUCCESS;
 }
 
 extern "C" {
@@ -534,6 +556,58 @@ tk_error_code_t tk_mi355x_asr_transcribe_tokens(tk_asr_whisper_context_t* c, int
     if (logits_out) memcpy(logits_out, lg.data(), lg.size() * 4);
     return TK_SUCCESS;
 }
+
+tk_error_code_t tk_mi355x_asr_transcribe_tokens_langs(tk_asr_whisper_context_t* c, int batch, const int16_t* pcm, int n_samples, int n_steps, const int32_t* lang_ids,
+                                                      int32_t* tokens_out, float* logits_out) {
+    if (!c || (!pcm && n_samples > 0) || !tokens_out || !lang_ids || n_steps <= 0 || batch < 1) return TK_ERROR_INVALID_ARGUMENT;
+    if (!c->multilingual) return afail(TK_ERROR_INVALID_ARGUMENT, "an English-only vocabulary has no language position");
+    const int n_lang = tk_whisper_n_lang(c->sh->model.hp.n_vocab);
+    std::vector<int32_t> slot((size_t)batch);
+    for (int b = 0; b < batch; ++b) {
+        if (lang_ids[b] < -1 || lang_ids[b] >= n_lang) return afail(TK_ERROR_INVALID_ARGUMENT, "a language id is outside Whisper's table");
+        slot[(size_t)b] = lang_ids[b] < 0 ? -1 : c->sot + 1 + lang_ids[b];
+    }
+    const std::vector<int32_t> prompt = {c->sot, -1, c->sot + 1 + n_lang + (c->translate ? 0 : 1), c->nots};
+    std::vector<float> lg;
+    tk_error_code_t rc = asr_run(c, batch, pcm, n_samples, prompt, n_steps, false, 0.0f, 0, tokens_out, nullptr, nullptr, nullptr, logits_out ? &lg : nullptr, slot.data());
+    if (rc == TK_SUCCESS && logits_out) memcpy(logits_out, lg.data(), lg.size() * 4);
+    return rc;
+}
+
+tk_error_code_t tk_mi355x_asr_detect_language(tk_asr_whisper_context_t* c, int batch, const int16_t* pcm, int n_samples, int32_t* lang_ids, float* probs) {
+    if (!c || (!pcm && n_samples > 0) || !lang_ids || batch < 1) return TK_ERROR_INVALID_ARGUMENT;
+    if (!c->multilingual) return afail(TK_ERROR_INVALID_ARGUMENT, "an English-only vocabulary has no language tokens to detect");
+    SharedAsr* sh = c->sh.get();
+    std::lock_guard<std::mutex> lk(sh->eng_mu); /* the engine itself, one caller at a time (as the batched test / bench entry points) */
+    std::string err;
+    if (!sh->ensure_engine(batch, &err)) return afail(TK_ERROR_GPU_MEMORY, err);
+    sh->eng->fast = c->fast;
+    if (!sh->eng->detect_language(batch, pcm, n_samples, lang_ids, probs)) return afail(TK_ERROR_INFERENCE_FAILED, sh->eng->error);
+    c->note_languages(sh->eng->last_lang_id.data(), sh->eng->last_lang_prob.data(), batch);
+    c->last_lang_logits = sh->eng->detect_logits;
+    return TK_SUCCESS;
+}
+
+int tk_mi355x_asr_last_language_logits(const tk_asr_whisper_context_t* c, float* out, int cap) {
+    if (!c || cap < 0) return -1;
+    const int n = (int)c->last_lang_logits.size();
+    for (int i = 0; out && i < n && i < cap; ++i) out[i] = c->last_lang_logits[(size_t)i];
+    return n;
+}
+
+int tk_mi355x_asr_last_languages(const tk_asr_whisper_context_t* c, int32_t* ids, float* probs, int cap) {
+    if (!c || cap < 0) return -1;
+    const int n = (int)c->last_lang_ids.size();
+    for (int i = 0; i < n && i < cap; ++i) {
+        if (ids) ids[i] = c->last_lang_ids[(size_t)i];
+        if (probs) probs[i] = c->last_lang_probs[(size_t)i];
+    }
+    return n;
+}
+
+const char* tk_mi355x_whisper_lang_code(int id) { return id >= 0 && id < TK_WHISPER_LANGS ? k_whisper_langs[id] : nullptr; }
+
+int tk_mi355x_whisper_lang_id(const char* code) { return code ? whisper_lang_id(code) : -1; }
 
 tk_error_code_t tk_mi355x_asr_transcribe_policy(tk_asr_whisper_context_t* c, int batch, const int16_t* pcm, int n_samples, int n_steps, float temperature,
                                                 uint64_t seed, int32_t* tokens_out, float* logprobs_out) {

@@ -56,14 +56,26 @@ public:
     ~TkAsr();
     bool init(TkWhisperModel* m, int max_batch);
     /* pcm[B][n_samples] (host), greedy decode of exactly n_steps tokens after the start-of-transcript prompt;
-     * tokens_out[B][n_steps]; optional copies of the mel / encoder output for parity tests */
+     * tokens_out[B][n_steps]; optional copies of the mel / encoder output for parity tests.
+     * The language position of the prompt (prompt[1]) may be decided on the device, per row: lang_slot (optional) [B] = the row's token there, or
+     * -1 = the language Whisper detects for that utterance (common/tk_lang_pick.h on the logits of the <|startoftranscript|> step, multilingual
+     * vocabularies only); without the array prompt[1] itself stands for every row, -1 included.  A batch may mix both kinds; a batch without a -1
+     * enqueues what it enqueued before there was detection.  last_lang_id / last_lang_prob report every row of the call. */
     bool transcribe(int B, const int16_t* pcm, int n_samples, const int32_t* prompt, int n_prompt, int n_steps, int32_t* tokens_out,
-                    std::vector<float>* mel_out, std::vector<float>* enc_out, std::vector<float>* first_logits);
+                    std::vector<float>* mel_out, std::vector<float>* enc_out, std::vector<float>* first_logits, const int32_t* lang_slot = nullptr);
+    /* whisper.cpp's whisper_lang_auto_detect: encode, decode <|startoftranscript|> once, stop.  ids_out [B] = each utterance's language (index into
+     * Whisper's language table), probs_out (optional) [B][n_lang] = the probability of every language, n_lang = tk_whisper_n_lang(n_vocab) */
+    bool detect_language(int B, const int16_t* pcm, int n_samples, int32_t* ids_out, float* probs_out);
+    /* per row of the last transcribe* call: the language the decoder's prompt named — detected (with its probability) or configured (probability
+     * 1); -1 where the prompt has no language position or names no language token */
+    std::vector<int32_t> last_lang_id;
+    std::vector<float> last_lang_prob;
+    std::vector<float> detect_logits; /* [B][n_lang] of the last detect_language: the language tokens' logits it decided on (parity tests) */
     /* the same with whisper.cpp's per-step bookkeeping: temperature 0 = arg max, > 0 = one draw per step from softmax(l / temperature) by the
      * canonical sampler keyed by (seed, step x B + b); logprobs_out [B][n_steps] = log-probability of every produced token under that
      * distribution (what the policy's logprob / entropy thresholds are taken on) */
     bool transcribe_policy(int B, const int16_t* pcm, int n_samples, const int32_t* prompt, int n_prompt, int n_steps, float temperature, uint64_t seed,
-                           int32_t* tokens_out, float* logprobs_out);
+                           int32_t* tokens_out, float* logprobs_out, const int32_t* lang_slot = nullptr);
     /* the decode as whisper.cpp runs it under the reference's parameters (src/audio/tk_asr_whisper.c:89-110; csrc/nn/tk_nn_kernels.h: TkWhFilter):
      * logit filters, timestamp rules and the per-token bookkeeping on the device, at most n_steps tokens per utterance.  n_samples_row [B] = each
      * utterance's own length (rows are padded to `n_samples` with zeros): it sets the row's seek_end.  suppress [n_vocab] = 1 where a token is
@@ -71,7 +83,7 @@ public:
      * up the row's text, status [B] = 0 (n_steps reached), 1 (completed), 2 (failed: whisper.cpp would fall back to the next temperature) */
     bool transcribe_ref(int B, const int16_t* pcm, int n_samples, const int32_t* n_samples_row, const int32_t* prompt, int n_prompt, int n_steps, float temperature,
                         uint64_t seed, const uint8_t* suppress, int32_t token_beg, int32_t token_eot, int32_t* tokens_out, float* logprobs_out, int32_t* result_len,
-                        int32_t* status);
+                        int32_t* status, const int32_t* lang_slot = nullptr);
 
 private:
     friend struct TkAudioGpuOps;
@@ -86,6 +98,11 @@ private:
     std::vector<uint8_t> suppress_host;
     int32_t* wh_state = nullptr;     /* [max_batch][TK_WH_STATE_INTS] */
     float* lp_dev = nullptr;         /* [n_text_ctx][max_batch] log-probabilities of a policy / reference-parameter decode */
+    /* language detection: [max_batch] ids, [max_batch] probabilities of them, [max_batch][TK_LANG_MAX] all probabilities (detect_language) */
+    int32_t* lang_id_dev = nullptr;
+    float *lang_prob_dev = nullptr, *lang_probs_dev = nullptr;
+    bool detect_only = false; /* detect_language: the transcribe in flight stops behind the <|startoftranscript|> step */
+    std::vector<float> detect_probs; /* [B][n_lang] of that call */
     bool ensure_decode_buffers();
     std::vector<float> pick_logprobs; /* [total steps][B], read back by transcribe_policy */
 };

@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "../common/tk_lang_pick.h"
 #include "../nn/tk_gemm_tiled.h"
 #include "../nn/tk_nn_kernels.h"
 
@@ -532,6 +533,7 @@ TkAsr::~TkAsr() {
     if (suppress_dev) (void)hipFree(suppress_dev);
     if (lp_dev) (void)hipFree(lp_dev);
     if (wh_state) (void)hipFree(wh_state);
+    if (lang_id_dev) (void)hipFree(lang_id_dev);
     if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -555,7 +557,7 @@ bool TkAsr::init(TkWhisperModel* m, int mb) {
 }
 
 bool TkAsr::transcribe_policy(int B, const int16_t* pcm, int n_samples, const int32_t* prompt, int n_prompt, int n_steps, float temperature, uint64_t seed,
-                              int32_t* tokens_out, float* logprobs_out) {
+                              int32_t* tokens_out, float* logprobs_out, const int32_t* lang_slot) {
     if (!(temperature >= 0.0f) || model->hp.n_vocab > 65536) { error = "temperature must be >= 0 and the vocabulary at most 65536 tokens"; return false; }
     const int total = n_prompt + n_steps - 1;
     if (B < 1 || total < 1) { error = "nothing to decode"; return false; }
@@ -564,7 +566,7 @@ bool TkAsr::transcribe_policy(int B, const int16_t* pcm, int n_samples, const in
     if (total > model->hp.n_text_ctx || B > max_batch) { error = "prompt + steps exceed the text context"; return false; }
     float* d_lp = lp_dev;
     pick.on = true; pick.temp = temperature; pick.seed = seed; pick.logprob = d_lp; pick.step = 0;
-    const bool ok = transcribe(B, pcm, n_samples, prompt, n_prompt, n_steps, tokens_out, nullptr, nullptr, nullptr); /* synchronises the stream */
+    const bool ok = transcribe(B, pcm, n_samples, prompt, n_prompt, n_steps, tokens_out, nullptr, nullptr, nullptr, lang_slot); /* synchronises the stream */
     pick.on = false;
     bool copied = true;
     if (ok && logprobs_out) {
@@ -587,12 +589,17 @@ bool TkAsr::ensure_decode_buffers() {
     if (!lp_dev) HIPQ(hipMalloc((void**)&lp_dev, (size_t)max_batch * h.n_text_ctx * sizeof(float)));
     if (!suppress_dev) HIPQ(hipMalloc((void**)&suppress_dev, (size_t)h.n_vocab));
     if (!wh_state) HIPQ(hipMalloc((void**)&wh_state, (size_t)max_batch * TK_WH_STATE_INTS * sizeof(int32_t)));
+    if (!lang_id_dev) { /* one allocation: ids | their probabilities | every language's probability */
+        HIPQ(hipMalloc((void**)&lang_id_dev, (size_t)max_batch * (2 + TK_LANG_MAX) * 4));
+        lang_prob_dev = (float*)lang_id_dev + max_batch;
+        lang_probs_dev = lang_prob_dev + max_batch;
+    }
     return true;
 }
 
 bool TkAsr::transcribe_ref(int B, const int16_t* pcm, int n_samples, const int32_t* n_samples_row, const int32_t* prompt, int n_prompt, int n_steps, float temperature,
                            uint64_t seed, const uint8_t* suppress, int32_t token_beg, int32_t token_eot, int32_t* tokens_out, float* logprobs_out, int32_t* result_len,
-                           int32_t* status) {
+                           int32_t* status, const int32_t* lang_slot) {
     const TkWhisperHP& h = model->hp;
     if (!(temperature >= 0.0f) || h.n_vocab > 65536) { error = "temperature must be >= 0 and the vocabulary at most 65536 tokens"; return false; }
     if (B < 1 || B > max_batch || !suppress || !n_samples_row || token_beg <= token_eot || token_beg >= h.n_vocab) { error = "bad arguments to the reference-parameter decode"; return false; }
@@ -614,7 +621,7 @@ bool TkAsr::transcribe_ref(int B, const int16_t* pcm, int n_samples, const int32
     pick.on = true; pick.temp = temperature; pick.seed = seed; pick.logprob = d_lp; pick.step = 0;
     pick.filtered = true; pick.first_step = n_prompt - 1; pick.suppress = suppress_dev; pick.state = wh_state; pick.beg = token_beg; pick.eot = token_eot;
     pick.tid0 = 50; /* max_initial_ts 1.0 s / (30 s / 1500 positions) */
-    const bool ok = transcribe(B, pcm, n_samples, prompt, n_prompt, n_steps, tokens_out, nullptr, nullptr, nullptr); /* synchronises the stream */
+    const bool ok = transcribe(B, pcm, n_samples, prompt, n_prompt, n_steps, tokens_out, nullptr, nullptr, nullptr, lang_slot); /* synchronises the stream */
     pick.on = false; pick.filtered = false;
     bool copied = true;
     std::vector<int32_t> st1((size_t)B * TK_WH_STATE_INTS);
@@ -636,13 +643,47 @@ bool TkAsr::transcribe_ref(int B, const int16_t* pcm, int n_samples, const int32
     return ok && copied;
 }
 
+bool TkAsr::detect_language(int B, const int16_t* pcm, int n_samples, int32_t* ids_out, float* probs_out) {
+    const int n_lang = tk_whisper_n_lang(model->hp.n_vocab);
+    if (n_lang < 1) { error = "language detection needs a multilingual vocabulary"; return false; }
+    if (!ids_out) { error = "no array for the language ids"; return false; }
+    const int32_t prompt[2] = {TK_WH_SOT_MULTILINGUAL, -1};
+    detect_only = true;
+    const bool ok = transcribe(B, pcm, n_samples, prompt, 2, 1, nullptr, nullptr, nullptr, nullptr); /* synchronises the stream */
+    detect_only = false;
+    if (!ok) return false;
+    for (int b = 0; b < B; ++b) ids_out[b] = last_lang_id[(size_t)b];
+    if (probs_out) memcpy(probs_out, detect_probs.data(), (size_t)B * n_lang * sizeof(float));
+    return true;
+}
+
 bool TkAsr::transcribe(int B, const int16_t* pcm, int n_samples, const int32_t* prompt, int n_prompt, int n_steps, int32_t* tokens_out,
-                       std::vector<float>* mel_out, std::vector<float>* enc_out, std::vector<float>* first_logits) {
+                       std::vector<float>* mel_out, std::vector<float>* enc_out, std::vector<float>* first_logits, const int32_t* lang_slot) {
     const TkWhisperHP& h = model->hp;
     if (B < 1 || B > max_batch) { error = "batch larger than the ASR context was created for"; return false; }
     if (n_samples < 0 || n_samples > h.n_samples()) { error = "audio longer than the model window"; return false; }
     if (n_prompt < 1 || n_prompt + n_steps > h.n_text_ctx) { error = "prompt + steps exceed the text context"; return false; }
+    /* the language position: one token per row, -1 = decided on the device behind the <|startoftranscript|> step */
+    const int n_lang = tk_whisper_n_lang(h.n_vocab);
+    const int32_t tok0 = prompt[0] + 1;
+    std::vector<int32_t> row_lang;
+    bool any_auto = false;
+    if (lang_slot && n_prompt < 2) { error = "a per-row language needs a prompt with a language position"; return false; }
+    if (n_prompt >= 2) {
+        row_lang.resize((size_t)B);
+        for (int b = 0; b < B; ++b) {
+            const int32_t t = lang_slot ? lang_slot[b] : prompt[1];
+            if (lang_slot && (t < -1 || t >= h.n_vocab)) { error = "a per-row language token is outside the vocabulary"; return false; }
+            row_lang[(size_t)b] = t;
+            any_auto = any_auto || t == -1;
+        }
+    }
+    if (any_auto && (n_lang > TK_LANG_MAX || tk_lang_pick_check(B, h.n_vocab, h.n_vocab, tok0, n_lang))) {
+        error = "language detection needs a multilingual vocabulary (99 to 128 language tokens behind <|startoftranscript|>)";
+        return false;
+    }
     HIPQ(hipSetDevice(model->device));
+    if (any_auto && !ensure_decode_buffers()) return false;
     size_t need = (size_t)B * (n_samples > 0 ? n_samples : 1);
     if (need > pcm_cap) need = (size_t)max_batch * (size_t)h.n_samples(); /* once: the engine's whole batch of full windows (0.96 MB each) */
     if (need > pcm_cap) {
@@ -669,18 +710,22 @@ bool TkAsr::transcribe(int B, const int16_t* pcm, int n_samples, const int32_t* 
      * table; one copy and one synchronisation at the end.  (A synchronisation and three small copies per step made the 16 steps of 32
      * utterances 1.2 ms each on a 0.3 ms GPU workload.) */
     const int total = n_prompt + n_steps - 1; /* the last generated token is not fed back */
-    const size_t tab_ints = ((size_t)n_prompt + 2 * (size_t)total) * B;
+    const size_t tab_ints = ((size_t)n_prompt + 2 * (size_t)total + (any_auto ? 1 : 0)) * B;
     ops.drop_image();
     if (arena_used + tab_ints + 64 > arena_floats) { error = "ASR arena too small for the decode tables"; return false; }
-    int32_t* tab = ops.alloc_i32(tab_ints); /* [n_prompt][B] prompt tokens, [total][B] positions, [total][B] arg-max slots */
+    int32_t* tab = ops.alloc_i32(tab_ints); /* [n_prompt][B] prompt tokens, [total][B] positions, ([B] rows that detect their language,) [total][B] arg-max slots */
     int32_t* tok_tab = tab;
     int32_t* pos_tab = tab + (size_t)n_prompt * B;
-    int32_t* out_tab = pos_tab + (size_t)total * B;
-    std::vector<int32_t> host_tab(((size_t)n_prompt + total) * B);
+    int32_t* auto_tab = pos_tab + (size_t)total * B;
+    int32_t* out_tab = auto_tab + (any_auto ? B : 0);
+    std::vector<int32_t> host_tab(((size_t)n_prompt + total + (any_auto ? 1 : 0)) * B);
     for (int p = 0; p < n_prompt; ++p)
         for (int b = 0; b < B; ++b) host_tab[(size_t)p * B + b] = prompt[p];
+    /* a detecting row's slot holds a valid placeholder (<|en|>) until k_lang_pick stores the row's own language there, before step 1 reads it */
+    for (int b = 0; b < B && n_prompt >= 2; ++b) host_tab[(size_t)B + b] = row_lang[(size_t)b] == -1 ? tok0 : row_lang[(size_t)b];
     for (int p = 0; p < total; ++p)
         for (int b = 0; b < B; ++b) host_tab[((size_t)n_prompt + p) * B + b] = p;
+    for (int b = 0; b < B && any_auto; ++b) host_tab[((size_t)n_prompt + total) * B + b] = row_lang[(size_t)b] == -1 ? 1 : 0;
     HIPQ(hipMemcpyAsync(tok_tab, host_tab.data(), host_tab.size() * 4, hipMemcpyHostToDevice, stream));
     int steps_run = n_steps; /* sampled positions really enqueued */
     std::vector<int32_t> st_host;
@@ -689,6 +734,13 @@ bool TkAsr::transcribe(int B, const int16_t* pcm, int n_samples, const int32_t* 
         st.pos = pos_tab + (size_t)p * B;
         st.next = out_tab + (size_t)p * B;
         g.decode_step(ops, st, p);
+        if (p == 0 && any_auto) { /* the <|startoftranscript|> step's logits hold the utterance's language: into the rows' slots of prompt position 1 */
+            ops.flush();
+            if (!tk_launch_lang_pick(st.logits, B, h.n_vocab, h.n_vocab, tok0, n_lang, auto_tab, tok_tab + (size_t)B, lang_id_dev, lang_prob_dev,
+                                     detect_only ? lang_probs_dev : nullptr, stream))
+                ops.refused("lang_pick");
+            if (detect_only) { steps_run = 0; break; }
+        }
         if (p == n_prompt - 1 && first_logits) {
             first_logits->resize((size_t)B * h.n_vocab);
             HIPQ(hipMemcpyAsync(first_logits->data(), st.logits, first_logits->size() * 4, hipMemcpyDeviceToHost, stream));
@@ -709,9 +761,27 @@ bool TkAsr::transcribe(int B, const int16_t* pcm, int n_samples, const int32_t* 
     }
     ops.flush();
     std::vector<int32_t> outs((size_t)steps_run * B);
-    HIPQ(hipMemcpyAsync(outs.data(), out_tab + (size_t)(n_prompt - 1) * B, outs.size() * 4, hipMemcpyDeviceToHost, stream));
+    if (!outs.empty()) HIPQ(hipMemcpyAsync(outs.data(), out_tab + (size_t)(n_prompt - 1) * B, outs.size() * 4, hipMemcpyDeviceToHost, stream));
+    last_lang_id.assign((size_t)B, -1);
+    last_lang_prob.assign((size_t)B, 1.0f);
+    if (any_auto) { /* the detected languages come back with the tokens */
+        HIPQ(hipMemcpyAsync(last_lang_id.data(), lang_id_dev, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
+        HIPQ(hipMemcpyAsync(last_lang_prob.data(), lang_prob_dev, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
+        if (detect_only) {
+            detect_probs.resize((size_t)B * n_lang);
+            HIPQ(hipMemcpyAsync(detect_probs.data(), lang_probs_dev, detect_probs.size() * 4, hipMemcpyDeviceToHost, stream));
+            detect_logits.resize((size_t)B * n_lang); /* the slices the kernel read, row by row out of the [B][n_vocab] logits */
+            HIPQ(hipMemcpy2DAsync(detect_logits.data(), (size_t)n_lang * 4, st.logits + tok0, (size_t)h.n_vocab * 4, (size_t)n_lang * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
+        }
+    }
     HIPQ(hipStreamSynchronize(stream)); /* host_tab and outs live until here */
-    for (int step = 0; step < n_steps; ++step)
+    for (int b = 0; b < B && n_prompt >= 2; ++b) {
+        const int32_t t = row_lang[(size_t)b];
+        if (t == -1) continue;
+        last_lang_id[(size_t)b] = n_lang > 0 && t >= tok0 && t < tok0 + n_lang ? t - tok0 : -1;
+        last_lang_prob[(size_t)b] = 1.0f;
+    }
+    for (int step = 0; step < n_steps && tokens_out; ++step)
         for (int b = 0; b < B; ++b) tokens_out[(size_t)b * n_steps + step] = step < steps_run ? outs[(size_t)step * B + b] : pick.eot;
     HIPQ(hipGetLastError());
     if (!launch_error.empty()) { error = launch_error; return false; }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../common/tk_exact_math.h"
+#include "../common/tk_lang_pick.h"
 #include "tk/tk_mi355x_ext.h"
 
 #include "../vision/tk_vision_engine.h"
@@ -420,6 +421,47 @@ tk_error_code_t tk_mi355x_logit_adjust_probe(int device, int32_t rows, int32_t c
         tk_launch_logit_adjust((float*)b[0].dev, cols, rows, (const TkAdjustRow*)b[1].dev, (const int32_t*)b[2].dev, (const int32_t*)b[3].dev, (const float*)b[4].dev, nullptr);
         if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
         else if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(logits, b[0].dev, b[0].bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+    }
+    for (Buf& q : b) if (q.dev) (void)hipFree(q.dev);
+    return rc;
+}
+
+tk_error_code_t tk_mi355x_lang_pick_probe(int device, int32_t rows, int32_t cols, int32_t ld, const float* logits, int64_t n_logits, int32_t tok0, int32_t n_lang,
+                                          const int32_t* auto_row, int32_t* slot, int32_t* ids, float* probs) {
+    if (!logits || !auto_row || !slot || !ids || !probs || tk_lang_pick_check(rows, cols, ld, tok0, n_lang)) return TK_ERROR_INVALID_ARGUMENT;
+    if (n_logits < (int64_t)(rows - 1) * ld + cols) return TK_ERROR_INVALID_ARGUMENT;
+    for (int r = 0; r < rows; ++r)
+        for (int i = 0; i < n_lang; ++i)
+            if (logits[(int64_t)r * ld + tok0 + i] > 3.402823466e38f) return TK_ERROR_INVALID_ARGUMENT; /* +inf: inf - inf has no probability */
+    if (device < 0) {
+        for (int r = 0; r < rows; ++r) {
+            ids[r] = tk_lang_pick_row(logits + (int64_t)r * ld + tok0, n_lang, nullptr, probs + (int64_t)r * n_lang);
+            if (auto_row[r] != 0) slot[r] = tok0 + ids[r];
+        }
+        return TK_SUCCESS;
+    }
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    std::vector<float> pid((size_t)rows);
+    /* host array, bytes, device copy, read back after the launch */
+    struct Buf { const void* host; size_t bytes; void* dev; bool out; };
+    Buf b[] = {{logits, (size_t)n_logits * 4, nullptr, false}, {auto_row, (size_t)rows * 4, nullptr, false}, {slot, (size_t)rows * 4, nullptr, true},
+               {ids, (size_t)rows * 4, nullptr, true}, {pid.data(), (size_t)rows * 4, nullptr, true}, {probs, (size_t)rows * n_lang * 4, nullptr, true}};
+    bool ok = true;
+    for (Buf& q : b) ok = ok && hipMalloc(&q.dev, q.bytes) == hipSuccess && hipMemcpy(q.dev, q.host, q.bytes, hipMemcpyHostToDevice) == hipSuccess;
+    tk_error_code_t rc = ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
+    if (ok) {
+        if (!tk_launch_lang_pick((const float*)b[0].dev, rows, cols, ld, tok0, n_lang, (const int32_t*)b[1].dev, (int32_t*)b[2].dev, (int32_t*)b[3].dev, (float*)b[4].dev,
+                                 (float*)b[5].dev, nullptr)) rc = TK_ERROR_INVALID_ARGUMENT;
+        else if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+        else
+            for (Buf& q : b)
+                if (q.out && hipMemcpy(const_cast<void*>(q.host), q.dev, q.bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+        /* the kernel's own prob[id] is the engine's per-row answer: it must be the row's entry of probs */
+        for (int r = 0; rc == TK_SUCCESS && r < rows; ++r)
+            if (tk_f32_bits(pid[(size_t)r]) != tk_f32_bits(probs[(int64_t)r * n_lang + ids[r]])) rc = TK_ERROR_GPU_ROCM_ERROR;
     }
     for (Buf& q : b) if (q.dev) (void)hipFree(q.dev);
     return rc;

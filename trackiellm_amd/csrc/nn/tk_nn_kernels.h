@@ -68,6 +68,11 @@ int tk_im2col_kernel_of(const float* x, int B, int H, int W, int C, int ldx, int
 /* out[r][:] = table[idx[r]][:] + pos[(pos0[r])][:] */
 [[nodiscard]] bool tk_launch_embed_rows(const float* table, const float* pos, const int32_t* idx, const int32_t* pos_idx, int rows, int D, float* out, hipStream_t s);
 void tk_launch_argmax_rows(const float* x, int rows, int cols, int ld, int32_t* out, hipStream_t s);
+/* Whisper's language detection (common/tk_lang_pick.h) over the n_lang logits from column tok0 on of every row: lang_id [rows], prob_id [rows] =
+ * the probability of the row's language, probs (optional) [rows][n_lang]; where auto_row[row] != 0 the token tok0 + id is stored into slot[row]
+ * (both optional; other rows' slots stay untouched).  false, nothing launched: a geometry tk_lang_pick_check refuses */
+[[nodiscard]] bool tk_launch_lang_pick(const float* x, int rows, int cols, int ld, int tok0, int n_lang, const int32_t* auto_row, int32_t* slot, int32_t* lang_id,
+                                       float* prob_id, float* probs, hipStream_t s);
 /* token pick under whisper.cpp's decoding policy: arg max (temp 0) or one draw from softmax(l / temp), + the pick's log-probability under
  * that distribution per row (logprob may be null); the generator is keyed by (seed, counter0 + row) */
 struct TkPick { float temp; uint64_t seed; uint32_t counter0; float* logprob; };

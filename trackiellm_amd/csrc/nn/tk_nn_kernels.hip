@@ -4,6 +4,7 @@
 #include <mutex>
 
 #include "../common/tk_exact_math.h"
+#include "../common/tk_lang_pick.h"
 #include "../common/tk_sample_device.h"
 
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -1370,6 +1371,59 @@ void tk_launch_pick_rows(const float* x, int rows, int cols, int ld, int32_t* ou
 
 void tk_launch_argmax_rows(const float* x, int rows, int cols, int ld, int32_t* out, hipStream_t s) {
     hipLaunchKernelGGL(k_argmax_rows, dim3(rows), dim3(1024), 0, s, x, cols, ld, out);
+}
+
+/* Whisper's language detection (common/tk_lang_pick.h) on the logits of the <|startoftranscript|> step: one 64-lane wave per row, lane t holds the
+ * language logits t and t + 64.  The first-index maximum is a wave butterfly (value descending, index ascending: a total order, so every lane ends
+ * on the same pair), the weights go to LDS, lane 0 adds them in index order, every lane divides its own.  Where auto_row[row] != 0 the row's
+ * language token tok0 + id is stored into slot[row] — the decoder's prompt table, read by the next step; other rows leave their slot alone. */
+__global__ __launch_bounds__(64) void k_lang_pick(const float* x, int ld, int tok0, int n_lang, const int32_t* auto_row, int32_t* slot, int32_t* lang_id,
+                                                  float* prob_id, float* probs) {
+    __shared__ float sp[TK_LANG_MAX];
+    __shared__ float ssum;
+    const int r = blockIdx.x, t = threadIdx.x;
+    const float* l = x + (int64_t)r * ld + tok0;
+    const bool in0 = t < n_lang, in1 = t + 64 < n_lang;
+    const float l0 = in0 ? l[t] : 0.0f, l1 = in1 ? l[t + 64] : 0.0f;
+    float best = -INFINITY;
+    int idx = 0x7fffffff; /* nothing above -inf yet */
+    if (in0 && l0 > best) { best = l0; idx = t; }
+    if (in1 && l1 > best) { best = l1; idx = t + 64; }
+    for (int s = 32; s >= 1; s >>= 1) {
+        const float ov = __shfl_xor(best, s, 64);
+        const int oi = __shfl_xor(idx, s, 64);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    }
+    const bool any = idx != 0x7fffffff;
+    const int id = any ? idx : 0;
+    const float m = best; /* l[id] whenever a weight is taken (any) */
+    const float p0 = in0 ? tk_lang_weight(l0, m, any) : 0.0f, p1 = in1 ? tk_lang_weight(l1, m, any) : 0.0f;
+    if (in0) sp[t] = p0;
+    if (in1) sp[t + 64] = p1;
+    __syncthreads();
+    if (t == 0) {
+        float S = 0.0f;
+        for (int i = 0; i < n_lang; ++i) S = tk_lang_add(S, sp[i]);
+        ssum = S;
+    }
+    __syncthreads();
+    const float S = ssum;
+    const float q0 = tk_lang_prob(p0, S, any), q1 = tk_lang_prob(p1, S, any);
+    if (probs) {
+        if (in0) probs[(int64_t)r * n_lang + t] = q0;
+        if (in1) probs[(int64_t)r * n_lang + t + 64] = q1;
+    }
+    if (t == (id & 63)) {
+        lang_id[r] = id;
+        prob_id[r] = id < 64 ? q0 : q1;
+        if (slot && auto_row && auto_row[r] != 0) slot[r] = tok0 + id;
+    }
+}
+bool tk_launch_lang_pick(const float* x, int rows, int cols, int ld, int tok0, int n_lang, const int32_t* auto_row, int32_t* slot, int32_t* lang_id, float* prob_id,
+                         float* probs, hipStream_t s) {
+    if (tk_lang_pick_check(rows, cols, ld, tok0, n_lang) || !x || !lang_id || !prob_id) return false;
+    hipLaunchKernelGGL(k_lang_pick, dim3(rows), dim3(64), 0, s, x, ld, tok0, n_lang, auto_row, slot, lang_id, prob_id, probs);
+    return true;
 }
 
 /* ---- whisper.cpp's logit filters and decode bookkeeping on the device (one workgroup per row; restated sequentially in

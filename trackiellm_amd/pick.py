@@ -1,4 +1,5 @@
-"""The token-selection kernels one launch at a time: the test hooks tk_mi355x_token_pick_probe and tk_mi355x_logit_adjust_probe."""
+"""The token-selection kernels one launch at a time: the test hooks tk_mi355x_token_pick_probe, tk_mi355x_logit_adjust_probe and
+tk_mi355x_lang_pick_probe."""
 import ctypes as C
 
 import numpy as np
@@ -112,3 +113,21 @@ def logit_adjust_probe_into(out, rows, cols, adjust, device=0, n_logits=None):
     f.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
     check(f(device, rows, cols, out.ctypes.data, out.size if n_logits is None else n_logits, C.cast(tab, C.c_void_p) if len(adjust) else None))
     del keep
+
+
+def lang_pick_probe(logits, rows, cols, tok0, n_lang, auto_row, slot, ld=None, device=0, n_logits=None):
+    """ONE launch of k_lang_pick (tk_mi355x_lang_pick_probe): Whisper's language detection over the n_lang logits from column tok0 on of every row.
+    logits: float32, rows `ld` apart.  auto_row [rows]: != 0 = the row stores its token tok0 + id into its slot.  slot [rows] is IN/OUT: a COPY is
+    launched on and returned.  -> (ids [rows], probs [rows][n_lang], slot).  device < 0: the same per-row function in a host loop, no GPU touched"""
+    logits = np.ascontiguousarray(logits, np.float32).reshape(-1)
+    auto_row = np.ascontiguousarray(auto_row, np.int32).reshape(-1)
+    slot = np.array(slot, dtype=np.int32, order="C", copy=True).reshape(-1)
+    if rows >= 1 and (auto_row.size != rows or slot.size != rows):
+        raise ValueError("lang_pick_probe: auto_row and slot must have `rows` entries")
+    ids = np.full(max(rows, 1), -1, np.int32)
+    probs = np.full((max(rows, 1), max(min(n_lang, 128), 1)), -1.0, np.float32)
+    f = lib().tk_mi355x_lang_pick_probe
+    f.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    check(f(device, rows, cols, cols if ld is None else ld, logits.ctypes.data, logits.size if n_logits is None else n_logits, tok0, n_lang, auto_row.ctypes.data,
+            slot.ctypes.data, ids.ctypes.data, probs.ctypes.data))
+    return ids, probs, slot
