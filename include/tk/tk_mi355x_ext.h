@@ -464,6 +464,75 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_logit_adjust_probe(int device, int
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_lang_pick_probe(int device, int32_t rows, int32_t cols, int32_t ld, const float* logits, int64_t n_logits, int32_t tok0,
                                                               int32_t n_lang, const int32_t* auto_row, int32_t* slot, int32_t* ids, float* probs);
 
+/* test hook for the LLM stream's step kernels (csrc/llm/tk_llm_kernels.hip), the contract of tk_mi355x_token_pick_probe: ONE launch of one production
+ * launcher on host arrays.  M = tk_mi355x_llm_max_rows().  Every array is given with its count in ELEMENTS; IN/OUT arrays are uploaded before the
+ * launch and read back whole after it, so every byte the kernel must not touch comes back as the caller left it.
+ *   op             launcher                      arrays
+ *   EMBED          tk_launch_embed               embd = vocab rows of K weights as GGUF blocks of `type` (n_embd BYTES), tok [nrows] in [0, vocab),
+ *                                                x [nrows][K] IN/OUT
+ *   RMSNORM        tk_launch_rmsnorm_q8          x [M][K] IN/OUT, partial [ks][M][n_total] or NULL (ks, n_total then unused), w [K], eps, af_round -> image
+ *   RESIDUAL_FOLD  tk_launch_residual_fold       x [M][K] IN/OUT, partial [ks][M][n_total], n_total >= K
+ *   SWIGLU         tk_launch_swiglu_q8           partial [ks][M][2 K] (gate | up) -> image; K = d_ff
+ *   QUANT          tk_launch_quant_q8            x [nrows][K] (read only), af_round -> image
+ *   ROPE_APPEND    tk_launch_qkv_rope_append     partial [ks][M][n_total], n_total >= (n_head + 2 n_kv_head) head_dim, rope_cos / rope_sin
+ *                                                [max_ctx][head_dim / 2] (n_rope each) as the caller gives them, seq / pos [nrows], layer -> qbuf
+ *                                                [M][n_head head_dim] IN/OUT, kcache / vcache [n_layer][max_seq][n_kv_head][max_ctx][head_dim] f16 bits
+ *                                                IN/OUT (n_cache each)
+ *   PV_JOIN        tk_launch_att_pv_join         pv_part [nrows][n_head][4][head_dim], l_part [nrows][n_head][4] -> image; K = n_head head_dim
+ *   ATT_TILES      tk_launch_att_tiles           seq [nrows] -> tiles [1 + M] IN/OUT
+ * The image (RMSNORM, SWIGLU, QUANT, PV_JOIN) comes back RAW, in the layout csrc/llm/tk_llm_layout.h documents, all M rows' worth, IN/OUT: aq
+ * [M / 16][K 16] int8, ad [M / 16][K / 256][16] floats, abs [M / 16][K / 256][2][16][8] int8, abs16 the same shape in f16 bits, and af
+ * [M / 16][K / 16][4][16][4] floats when af_round is 1 (F16) or 2 (BF16) or af is given (af_round 0: unrounded); af NULL: no float image.
+ * Everything is validated before anything is launched; a refusal is TK_ERROR_INVALID_ARGUMENT with nothing written: a NULL array the op needs, a
+ * count too small for its geometry, nrows outside [1, M], ks outside [1, 8], K < 256 or no multiple of 256 (EMBED: of `type`'s block too), K or
+ * n_total above 65536, n_total % 4, a (n_head, n_kv_head, head_dim) that a model refuses (PV_JOIN: head_dim 64 or 128 with n_head a multiple of
+ * 256 / head_dim), seq / pos / layer / tok outside their arrays, a `type` that is no token_embd type, af_round outside [0, 2], and a launch whose
+ * dynamic LDS exceeds what its kernel is opted into (RMSNORM: K > 40704).  device < 0: validate only, no device is touched.
+ * The twins run one operation in its two production forms on the same inputs, in one call, and return both results.  wblocks: raw GGUF blocks of
+ * wtype (Q4_K or Q6_K), wrows x K weights (n_wblocks BYTES); y_a / y_b [ks][M][wrows] IN/OUT: the mat-vec's K-split slabs of form a / form b.
+ *   FUSED_NORM     a: tk_launch_rmsnorm_q8 (x [M][K] IN/OUT, partial [fks][M][n_total] or NULL, w, eps) then a plain tk_launch_gemv;
+ *                  b: tk_launch_gemv with fuse = 1 on the caller's x, its updated rows into x_b [M][K] IN/OUT
+ *   FUSED_SWIGLU   a: tk_launch_swiglu_q8 (partial [fks][M][2 K]) then a plain tk_launch_gemv; b: tk_launch_gemv with fuse = 2
+ *                  both: nrows <= 2, wrows a multiple of 64, and what tk_gemv_fuses_producer asks (K % (512 ks) == 0, the image inside the LDS opt-in)
+ *   WIDE_SWIGLU    x [nrows][K] quantised by tk_launch_quant_q8; wblocks = gate [wrows][K] then up [wrows][K]; a: tk_launch_gemv with swiglu = 1 then
+ *                  tk_launch_quant_q8 -> the image (aq, ad, abs, abs16 of wrows columns); b: the plain gate | up launch then tk_launch_swiglu_q8 -> the
+ *                  image aq_b, ad_b, abs_b, abs16_b (the counts of the first); nrows >= 193 (where a pass takes form a), wrows a multiple of 256 */
+enum {
+    TK_MI355X_STEP_EMBED = 0, TK_MI355X_STEP_RMSNORM = 1, TK_MI355X_STEP_RESIDUAL_FOLD = 2, TK_MI355X_STEP_SWIGLU = 3, TK_MI355X_STEP_QUANT = 4,
+    TK_MI355X_STEP_ROPE_APPEND = 5, TK_MI355X_STEP_PV_JOIN = 6, TK_MI355X_STEP_ATT_TILES = 7,
+    TK_MI355X_STEP_FUSED_NORM = 8, TK_MI355X_STEP_FUSED_SWIGLU = 9, TK_MI355X_STEP_WIDE_SWIGLU = 10
+};
+typedef struct tk_mi355x_llm_step_probe_s {
+    int32_t op, nrows, K, ks, n_total, af_round, type, vocab;
+    int32_t n_head, n_kv_head, head_dim, n_layer, max_seq, max_ctx, layer;
+    float eps;
+    float* x;
+    const float *partial, *w;
+    const void* embd;
+    const int32_t *tok, *seq, *pos;
+    const float *rope_cos, *rope_sin;
+    float* qbuf;
+    uint16_t *kcache, *vcache;
+    const float *pv_part, *l_part;
+    int32_t* tiles;
+    int8_t* aq;
+    float* ad;
+    int8_t* abs;
+    uint16_t* abs16;
+    float* af;
+    int64_t n_x, n_partial, n_w, n_embd, n_rows /* tok, seq, pos */, n_rope, n_qbuf, n_cache, n_pv, n_l, n_tiles, n_aq, n_ad, n_abs, n_abs16, n_af;
+    /* the twins */
+    const void* wblocks;
+    float *y_a, *y_b, *x_b;
+    int8_t* aq_b;
+    float* ad_b;
+    int8_t* abs_b;
+    uint16_t* abs16_b;
+    int64_t n_wblocks, n_y, n_xb;
+    int32_t wtype, wrows, fks, reserved;
+} tk_mi355x_llm_step_probe_t;
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_step_probe(int device, tk_mi355x_llm_step_probe_t* p);
+
 /* test hook for the perception streams' row and layout kernels (csrc/nn/tk_nn_kernels): ONE launch of one launcher on host arrays, so that
  * shapes no network sends (pitches wider than the extent, odd sizes around the kernels' 256 / 2048 thresholds, unaligned bases, rows that are
  * no multiple of 16) reach each kernel alone.  The contract is the GEMM probe's: a / b / c / idx / pos_idx are inputs of n_a / n_b / n_c /

@@ -177,6 +177,32 @@ static float dot_q6k_range(const tk_block_q6_K* w, const int8_t* q, const float*
     return acc;
 }
 
+/* The steps orc_llm_forward takes between its matmuls, one statement each: the forward pass calls them, and the kernel-level tests call the same
+ * functions (tests/test_llm_step_gpu.py), so the two cannot drift apart.
+ * K-split slabs p[0], p[stride], ..: added in ascending order, starting FROM the first (no 0.0f + p[0]: it would turn -0.0f into +0.0f) */
+float orc_slab_sum(const float* p, int ks, int64_t stride) {
+    float acc = p[0];
+    for (int s = 1; s < ks; ++s) acc = acc + p[(int64_t)s * stride];
+    return acc;
+}
+/* RoPE of the adjacent pair (a, b) = dims (2 i, 2 i + 1) by the table entries (cs, sn) of (position, i) */
+void orc_rope_pair(float a, float b, float cs, float sn, float* out2) {
+    out2[0] = tk_fmaf(-b, sn, a * cs);
+    out2[1] = tk_fmaf(a, sn, b * cs);
+}
+float orc_swiglu(float gate, float up) { return tk_siluf(gate) * up; }
+float orc_divf(float a, float b) { return tk_divf(a, b); }
+/* the float-weight matmuls' input rounding (TkRound: 0 none, 1 through f16, 2 through bf16) */
+float orc_round_through(float v, int mode) { return tk_round_through(v, mode); }
+
+/* the same functions over arrays, for the tests: element i of n */
+void orc_slab_sum_n(const float* p, int ks, int64_t stride, int64_t n, float* out) { for (int64_t i = 0; i < n; ++i) out[i] = orc_slab_sum(p + i, ks, stride); }
+void orc_rope_pairs_n(const float* ab, const float* cs, const float* sn, int64_t n_pairs, float* out) { for (int64_t i = 0; i < n_pairs; ++i) orc_rope_pair(ab[2 * i], ab[2 * i + 1], cs[i], sn[i], out + 2 * i); }
+void orc_swiglu_n(const float* gate, const float* up, int64_t n, float* out) { for (int64_t i = 0; i < n; ++i) out[i] = orc_swiglu(gate[i], up[i]); }
+void orc_divf_n(const float* a, const float* b, int64_t n, float* out) { for (int64_t i = 0; i < n; ++i) out[i] = orc_divf(a[i], b[i]); }
+void orc_round_through_n(const float* v, int mode, int64_t n, float* out) { for (int64_t i = 0; i < n; ++i) out[i] = orc_round_through(v[i], mode); }
+void orc_f32_to_f16_n(const float* v, int64_t n, uint16_t* out) { for (int64_t i = 0; i < n; ++i) out[i] = tk_f32_to_f16(v[i]); }
+
 /* y[rows] = W[rows x K] . x, K split into `ks` ranges whose partials are added in order */
 void orc_gemv_q8(int type, const void* w, int64_t rows, int64_t K, int ks, const int8_t* q, const float* d,
                  const int32_t* bsum, float* y) {
@@ -184,14 +210,12 @@ void orc_gemv_q8(int type, const void* w, int64_t rows, int64_t K, int ks, const
     int per = nb / ks;
 #pragma omp parallel for schedule(static)
     for (int64_t r = 0; r < rows; ++r) {
-        float acc = 0.0f;
+        std::vector<float> p(ks);
         for (int s = 0; s < ks; ++s) {
-            float p;
-            if (type == TK_TYPE_Q4_K) p = dot_q4k_range((const tk_block_q4_K*)w + r * nb, q, d, bsum, s * per, (s + 1) * per);
-            else p = dot_q6k_range((const tk_block_q6_K*)w + r * nb, q, d, s * per, (s + 1) * per);
-            acc = (s == 0) ? p : acc + p;
+            if (type == TK_TYPE_Q4_K) p[s] = dot_q4k_range((const tk_block_q4_K*)w + r * nb, q, d, bsum, s * per, (s + 1) * per);
+            else p[s] = dot_q6k_range((const tk_block_q6_K*)w + r * nb, q, d, s * per, (s + 1) * per);
         }
-        y[r] = acc;
+        y[r] = orc_slab_sum(p.data(), ks, 1);
     }
 }
 
@@ -409,13 +433,13 @@ static void gemv_f16(const orc_tensor& t, int ks, const float* h, float* y) {
     const uint16_t* w = (const uint16_t*)t.data.data();
 #pragma omp parallel for schedule(static)
     for (int64_t r = 0; r < t.rows; ++r) {
-        float total = 0.0f;
+        std::vector<float> p(ks);
         for (int s = 0; s < ks; ++s) {
             float acc = 0.0f;
             for (int i = s * Kr; i < (s + 1) * Kr; ++i) acc = tk_fmaf(a[i], tk_f16_to_f32(w[r * K + i]), acc);
-            total = s == 0 ? acc : total + acc;
+            p[s] = acc;
         }
-        y[r] = total;
+        y[r] = orc_slab_sum(p.data(), ks, 1);
     }
 }
 
@@ -468,17 +492,14 @@ void orc_llm_forward(orc_llm* m, int n_rows, const int32_t* seq, const int32_t* 
             const float* cs = &m->rope_cos[(size_t)pos[r] * half];
             const float* sn = &m->rope_sin[(size_t)pos[r] * half];
             for (int hh = 0; hh < NH; ++hh)
-                for (int i = 0; i < half; ++i) {
-                    float a = qr[hh * HD + 2 * i], b = qr[hh * HD + 2 * i + 1];
-                    qr[hh * HD + 2 * i] = tk_fmaf(-b, sn[i], a * cs[i]);
-                    qr[hh * HD + 2 * i + 1] = tk_fmaf(a, sn[i], b * cs[i]);
-                }
+                for (int i = 0; i < half; ++i) orc_rope_pair(qr[hh * HD + 2 * i], qr[hh * HD + 2 * i + 1], cs[i], sn[i], &qr[hh * HD + 2 * i]);
             size_t base = ((((size_t)l * c.max_seq + seq[r]) * c.max_ctx + pos[r]) * NKV) * HD;
             for (int hh = 0; hh < NKV; ++hh)
                 for (int i = 0; i < half; ++i) {
-                    float a = kv[hh * HD + 2 * i], b = kv[hh * HD + 2 * i + 1];
-                    m->kcache[base + hh * HD + 2 * i] = tk_f32_to_f16(tk_fmaf(-b, sn[i], a * cs[i]));
-                    m->kcache[base + hh * HD + 2 * i + 1] = tk_f32_to_f16(tk_fmaf(a, sn[i], b * cs[i]));
+                    float k2[2];
+                    orc_rope_pair(kv[hh * HD + 2 * i], kv[hh * HD + 2 * i + 1], cs[i], sn[i], k2);
+                    m->kcache[base + hh * HD + 2 * i] = tk_f32_to_f16(k2[0]);
+                    m->kcache[base + hh * HD + 2 * i + 1] = tk_f32_to_f16(k2[1]);
                 }
             for (int i = 0; i < KVD; ++i) m->vcache[base + i] = tk_f32_to_f16(vv[i]);
         }
@@ -517,7 +538,7 @@ void orc_llm_forward(orc_llm* m, int n_rows, const int32_t* seq, const int32_t* 
             orc_q8k_quantize(h.data(), D, q8.data(), qd.data(), qb.data());
             mat(L[ORC_L_GATE], c.ks_gateup, h.data(), q8.data(), qd.data(), qb.data(), gate.data());
             mat(L[ORC_L_UP], c.ks_gateup, h.data(), q8.data(), qd.data(), qb.data(), up.data());
-            for (int i = 0; i < FF; ++i) act[i] = tk_siluf(gate[i]) * up[i];
+            for (int i = 0; i < FF; ++i) act[i] = orc_swiglu(gate[i], up[i]);
             matvec(L[ORC_L_DOWN], c.ks_down, act.data(), o.data(), q8, qd, qb);
             for (int i = 0; i < D; ++i) xr[i] = xr[i] + o[i];
         }

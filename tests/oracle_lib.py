@@ -201,6 +201,62 @@ def rmsnorm(x, w, eps):
     return out
 
 
+# ---------------------------------------------------------------- the LLM pass's steps between its matmuls, alone (orc_llm_forward calls the same functions)
+def slab_sum(p, ks, stride, n):
+    """out[i] = p[i] + p[i + stride] + ... (ks terms, ascending), i < n, on the flat float32 array p"""
+    p = _f32(p).reshape(-1)
+    assert ks >= 1 and (ks - 1) * stride + n <= p.size
+    out = np.empty(n, np.float32)
+    lib().orc_slab_sum_n.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+    lib().orc_slab_sum_n(ptr(p), ks, stride, n, ptr(out))
+    return out
+
+
+def rope_pairs(ab, cs, sn):
+    """ab [n][2] adjacent pairs, cs / sn [n] -> rotated [n][2]"""
+    ab, cs, sn = _f32(ab).reshape(-1, 2), _f32(cs).reshape(-1), _f32(sn).reshape(-1)
+    assert len(ab) == len(cs) == len(sn)
+    out = np.empty_like(ab)
+    lib().orc_rope_pairs_n.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]
+    lib().orc_rope_pairs_n(ptr(ab), ptr(cs), ptr(sn), len(ab), ptr(out))
+    return out
+
+
+def _binary_n(name, a, b):
+    a, b = _f32(a), _f32(b)
+    assert a.shape == b.shape
+    out = np.empty_like(a)
+    fn = getattr(lib(), name)
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    fn(ptr(a), ptr(b), a.size, ptr(out))
+    return out
+
+
+def swiglu(gate, up):
+    return _binary_n("orc_swiglu_n", gate, up)
+
+
+def divf(a, b):
+    return _binary_n("orc_divf_n", a, b)
+
+
+def round_through(v, mode):
+    """0: as it is, 1: through f16, 2: through bf16"""
+    v = _f32(v)
+    out = np.empty_like(v)
+    lib().orc_round_through_n.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+    lib().orc_round_through_n(ptr(v), mode, v.size, ptr(out))
+    return out
+
+
+def f32_to_f16(v):
+    v = _f32(v)
+    out = np.empty(v.shape, np.uint16)
+    lib().orc_f32_to_f16_n.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    lib().orc_f32_to_f16_n(ptr(v), v.size, ptr(out))
+    return out
+
+
 # ---------------------------------------------------------------- vision oracle bindings
 class _Frame(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("stride", C.c_uint32), ("format", C.c_int), ("data", C.c_void_p)]

@@ -129,6 +129,13 @@ tk_error_code_t tk_mi355x_llm_gemv_probe(int device, int type, const void* block
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_llm_step_probe(int device, tk_mi355x_llm_step_probe_t* p) {
+    if (!p) return TK_ERROR_INVALID_ARGUMENT;
+    std::string err;
+    if (!tk_llm_step_probe(device, p, err)) return fail(err.find("device error") != std::string::npos || err.find("memory") != std::string::npos ? TK_ERROR_GPU_ROCM_ERROR : TK_ERROR_INVALID_ARGUMENT, err);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_repack_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, void* tiles) {
     if (!blocks || !tiles) return TK_ERROR_INVALID_ARGUMENT;
     std::string err;

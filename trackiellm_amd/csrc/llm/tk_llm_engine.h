@@ -211,6 +211,10 @@ bool tk_llm_matmul_float_probe(int device, int type, const void* w, int64_t rows
 bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, int ks, int nrows, const float* x, float* y,
                        std::string& error);
 
+/* one step launcher on host arrays (tk_mi355x_llm_step_probe, include/tk/tk_mi355x_ext.h): everything validated first, device < 0 validates only */
+struct tk_mi355x_llm_step_probe_s;
+bool tk_llm_step_probe(int device, tk_mi355x_llm_step_probe_s* p, std::string& error);
+
 /* the repack alone (tk_mi355x_llm_repack_probe): raw GGUF blocks [rows][K / 256 runs] -> the type's tiles (tk_llm_layout.h) on the host.
  * device >= 0: tk_launch_repack there; device < 0: tk_repack_host, the same lane function in a host loop, no GPU touched */
 bool tk_llm_repack_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, void* tiles, std::string& error);

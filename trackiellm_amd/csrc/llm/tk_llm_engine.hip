@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "../common/tk_ggml_blocks.h"
+#include "tk/tk_mi355x_ext.h"
 #include "../nn/tk_gemm_tiled.h"
 #include "../nn/tk_nn_kernels.h"
 
@@ -98,15 +99,24 @@ TkDevTensor* TkLlmModel::slot(int layer, int which) {
     return t[which];
 }
 
+/* the head geometry the step and attention kernels take; nullptr or why not (TkLlmModel::init, tk_llm_step_probe) */
+static const char* head_geometry_error(int n_head, int n_kv_head, int head_dim) {
+    const int grp = n_kv_head > 0 ? n_head / n_kv_head : 0;
+    if (n_head <= 0 || head_dim <= 0 || ((int64_t)n_head * head_dim) % 256) return "d_model, d_ff and n_head*head_dim must be multiples of 256";
+    if (n_kv_head <= 0 || n_head % n_kv_head || (grp != 1 && grp != 2 && grp != 4)) return "n_head / n_kv_head must be 1, 2 or 4";
+    if ((grp * head_dim) % 256 || head_dim % 64) return "head_dim must be a multiple of 64 and (n_head/n_kv_head)*head_dim a multiple of 256";
+    return nullptr;
+}
+
 bool TkLlmModel::init(const TkLlmHParams& h, int dev) {
     hp = h;
     device = dev;
-    const int grp = h.n_kv_head > 0 ? h.n_head / h.n_kv_head : 0;
     const int64_t qd = (int64_t)h.n_head * h.head_dim, kvd = (int64_t)h.n_kv_head * h.head_dim;
     auto bad = [&](const char* why) { error = std::string("unsupported model geometry: ") + why; return false; };
-    if (h.n_layer <= 0 || h.d_model % 256 || h.d_ff % 256 || qd % 256) return bad("d_model, d_ff and n_head*head_dim must be multiples of 256");
-    if (h.n_kv_head <= 0 || h.n_head % h.n_kv_head || (grp != 1 && grp != 2 && grp != 4)) return bad("n_head / n_kv_head must be 1, 2 or 4");
-    if ((grp * h.head_dim) % 256 || h.head_dim % 64) return bad("head_dim must be a multiple of 64 and (n_head/n_kv_head)*head_dim a multiple of 256");
+    if (h.n_layer <= 0 || h.d_model <= 0 || h.d_ff <= 0 || h.d_model % 256 || h.d_ff % 256) return bad("d_model, d_ff and n_head*head_dim must be multiples of 256");
+    if (const char* why = head_geometry_error(h.n_head, h.n_kv_head, h.head_dim)) return bad(why);
+    /* the norm keeps a whole row of the residual stream in LDS: (d_model + 4) floats of the 160 KiB a kernel can be opted into */
+    if (h.d_model > tk_llm_max_d_model()) return bad("d_model above 40704: the RMS norm keeps one row of d_model floats in 160 KiB of LDS");
     if (qd % 64 || kvd % 64 || h.d_ff % 64 || h.vocab % 64 || h.d_model % 64) return bad("row counts must be multiples of 64");
     if (h.ks_out != 1) return bad("ks_out must be 1");
     const int ksv[4] = {h.ks_qkv, h.ks_o, h.ks_gateup, h.ks_down};
@@ -564,6 +574,275 @@ bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, i
     if (tiles) (void)hipFree(tiles);
     if (dx) (void)hipFree(dx);
     if (out) (void)hipFree(out);
+    return ok;
+}
+
+/* ---- tk_mi355x_llm_step_probe: one step launcher on host arrays ---- */
+namespace {
+struct StepNeed { /* what an op reads and writes, in elements; 0 = unused */
+    int64_t x = 0, partial = 0, w = 0, embd = 0, rows = 0, rope = 0, qbuf = 0, cache = 0, pv = 0, l = 0, tiles = 0, wblocks = 0, y = 0, xb = 0;
+    int64_t image_k = 0; /* columns of the returned image(s); 0 = none */
+    bool image = false, x_out = false, image_b = false;
+};
+}
+
+static bool step_probe_check(const tk_mi355x_llm_step_probe_t& p, StepNeed& n, std::string& error) {
+    auto bad = [&](const char* why) { error = std::string("step probe: ") + why; return false; };
+    const int64_t M = TK_MAX_ROWS;
+    if (p.nrows < 1 || p.nrows > TK_MAX_ROWS) return bad("nrows outside [1, 256]");
+    const bool has_k = p.op != TK_MI355X_STEP_ROPE_APPEND && p.op != TK_MI355X_STEP_ATT_TILES;
+    if (has_k && (p.K < 256 || p.K % 256 || p.K > 65536)) return bad("K must be a multiple of 256 in [256, 65536]");
+    const bool has_slabs = p.op == TK_MI355X_STEP_RESIDUAL_FOLD || p.op == TK_MI355X_STEP_SWIGLU || p.op == TK_MI355X_STEP_ROPE_APPEND ||
+                           (p.op == TK_MI355X_STEP_RMSNORM && p.partial);
+    if (has_slabs && (p.ks < 1 || p.ks > 8)) return bad("ks outside [1, 8]");
+    if (has_slabs && p.op != TK_MI355X_STEP_SWIGLU && (p.n_total < 4 || p.n_total % 4 || p.n_total > 65536)) return bad("n_total must be a multiple of 4 up to 65536");
+    switch (p.op) {
+    case TK_MI355X_STEP_EMBED: {
+        if (!tk_type_desc_of(p.type).token_embd) return bad("type is no token_embd type");
+        const int64_t be = tk_type_block_elems(p.type);
+        if (p.K % be || p.vocab < 1 || p.vocab > (1 << 20)) return bad("K must hold whole blocks of the type and vocab lie in [1, 2^20]");
+        n.embd = (int64_t)p.vocab * (p.K / be) * tk_type_block_bytes(p.type);
+        n.rows = p.nrows; n.x = (int64_t)p.nrows * p.K; n.x_out = true;
+        if (!p.tok || p.n_rows < n.rows) return bad("tok missing or too short");
+        for (int r = 0; r < p.nrows; ++r)
+            if (p.tok[r] < 0 || p.tok[r] >= p.vocab) return bad("a token outside the table");
+        break;
+    }
+    case TK_MI355X_STEP_RMSNORM:
+        if (tk_rmsnorm_lds_bytes(p.K) > tk_rmsnorm_lds_bytes(tk_llm_max_d_model())) return bad("K above 40704: the norm's row does not fit the 160 KiB of LDS the kernel is opted into");
+        if (p.partial && p.n_total < p.K) return bad("n_total below K");
+        n.x = M * p.K; n.x_out = true; n.w = p.K; n.image = true;
+        n.partial = p.partial ? (int64_t)p.ks * M * p.n_total : 0;
+        if (!(p.eps >= 0.0f) || !(p.eps < 1.0f)) return bad("eps outside [0, 1)");
+        break;
+    case TK_MI355X_STEP_RESIDUAL_FOLD:
+        if (p.n_total < p.K) return bad("n_total below K");
+        n.x = M * p.K; n.x_out = true; n.partial = (int64_t)p.ks * M * p.n_total;
+        break;
+    case TK_MI355X_STEP_SWIGLU:
+        n.partial = (int64_t)p.ks * M * 2 * p.K; n.image = true;
+        break;
+    case TK_MI355X_STEP_QUANT:
+        n.x = (int64_t)p.nrows * p.K; n.image = true;
+        break;
+    case TK_MI355X_STEP_ROPE_APPEND: {
+        if (const char* why = head_geometry_error(p.n_head, p.n_kv_head, p.head_dim)) return bad(why);
+        const int64_t qd = (int64_t)p.n_head * p.head_dim, kvd = (int64_t)p.n_kv_head * p.head_dim;
+        if (qd + 2 * kvd > p.n_total) return bad("n_total below (n_head + 2 n_kv_head) head_dim");
+        if (p.n_layer < 1 || p.max_seq < 1 || p.max_ctx < 1 || p.layer < 0 || p.layer >= p.n_layer) return bad("layer outside [0, n_layer), or an empty cache");
+        n.cache = (int64_t)p.n_layer * p.max_seq * kvd * p.max_ctx;
+        if (n.cache > (1LL << 28)) return bad("cache above 2^28 halves");
+        n.partial = (int64_t)p.ks * M * p.n_total; n.rope = (int64_t)p.max_ctx * (p.head_dim / 2); n.qbuf = M * qd; n.rows = p.nrows;
+        if (!p.seq || !p.pos || p.n_rows < n.rows) return bad("seq / pos missing or too short");
+        for (int r = 0; r < p.nrows; ++r)
+            if (p.seq[r] < 0 || p.seq[r] >= p.max_seq || p.pos[r] < 0 || p.pos[r] >= p.max_ctx) return bad("a (sequence, position) outside the cache");
+        break;
+    }
+    case TK_MI355X_STEP_PV_JOIN:
+        if ((p.head_dim != 64 && p.head_dim != 128) || p.n_head < 1 || p.n_head % (256 / p.head_dim) || (int64_t)p.n_head * p.head_dim != p.K)
+            return bad("head_dim must be 64 or 128, n_head a multiple of 256 / head_dim, K = n_head head_dim");
+        n.pv = (int64_t)p.nrows * p.n_head * 4 * p.head_dim; n.l = (int64_t)p.nrows * p.n_head * 4; n.image = true;
+        break;
+    case TK_MI355X_STEP_ATT_TILES:
+        n.rows = p.nrows; n.tiles = 1 + M;
+        if (!p.seq || p.n_rows < n.rows) return bad("seq missing or too short");
+        break;
+    case TK_MI355X_STEP_FUSED_NORM:
+    case TK_MI355X_STEP_FUSED_SWIGLU: {
+        const bool norm = p.op == TK_MI355X_STEP_FUSED_NORM;
+        if (p.wtype != TK_TYPE_Q4_K && p.wtype != TK_TYPE_Q6_K) return bad("wtype must be Q4_K or Q6_K");
+        if (p.wrows < 64 || p.wrows % 64 || p.wrows > 4096) return bad("wrows must be a multiple of 64 up to 4096");
+        if (p.ks < 1 || p.ks > 8 || p.K % (256 * p.ks)) return bad("ks outside [1, 8] or K % (256 ks) != 0");
+        const int fks = norm && !p.partial ? 0 : p.fks;
+        if ((norm ? fks < 0 : fks < 1) || fks > 8) return bad("fks outside [1, 8]");
+        if (!tk_gemv_fuses_producer(p.nrows, p.K, p.ks, fks)) return bad("no fused launch at this shape: nrows <= 2, K % (512 ks) == 0 and the image inside the LDS opt-in");
+        if (norm) {
+            if (fks && (p.n_total < p.K || p.n_total % 4 || p.n_total > 65536)) return bad("n_total must be a multiple of 4 in [K, 65536]");
+            if (!(p.eps >= 0.0f) || !(p.eps < 1.0f)) return bad("eps outside [0, 1)");
+            n.x = M * p.K; n.x_out = true; n.xb = M * p.K; n.w = p.K; n.partial = (int64_t)fks * M * p.n_total;
+        } else n.partial = (int64_t)fks * M * 2 * p.K;
+        n.wblocks = (int64_t)p.wrows * (p.K / 256) * (int64_t)tk_type_block_bytes(p.wtype);
+        n.y = (int64_t)p.ks * M * p.wrows;
+        break;
+    }
+    case TK_MI355X_STEP_WIDE_SWIGLU:
+        if (p.wrows < 256 || p.wrows % 256 || p.wrows > 4096 || p.K > 4096) return bad("wrows must be a multiple of 256 up to 4096, K at most 4096");
+        if (!tk_gemv_fuses_swiglu(p.nrows, 1, p.wtype, p.wtype) || (p.wtype != TK_TYPE_Q4_K && p.wtype != TK_TYPE_Q6_K)) return bad("no wide SwiGLU launch at this shape: nrows >= 193, wtype Q4_K or Q6_K");
+        n.x = (int64_t)p.nrows * p.K; n.wblocks = 2 * (int64_t)p.wrows * (p.K / 256) * (int64_t)tk_type_block_bytes(p.wtype);
+        n.image = n.image_b = true; n.image_k = p.wrows;
+        break;
+    default: return bad("unknown op");
+    }
+    if (n.image && !n.image_k) n.image_k = p.K;
+    if (p.af_round < 0 || p.af_round > 2) return bad("af_round outside [0, 2]");
+    if (n.image && p.af_round != 0 && !p.af) return bad("a float rounding needs the af image");
+    auto need = [&](const void* a, int64_t have, int64_t want) { return want == 0 || (a && have >= want); };
+    const int64_t K = n.image_k;
+    if (!need(p.wblocks, p.n_wblocks, n.wblocks) || !need(p.y_a, p.n_y, n.y) || !need(p.y_b, p.n_y, n.y) || !need(p.x_b, p.n_xb, n.xb))
+        return bad("a NULL array of the twins, or a count too small for the geometry");
+    if (n.image_b && (!p.aq_b || !p.ad_b || !p.abs_b || !p.abs16_b || p.af)) return bad("the second image is NULL (or af given: the wide form has no float image)");
+    if (!need(p.x, p.n_x, n.x) || !need(p.partial, p.n_partial, n.partial) || !need(p.w, p.n_w, n.w) || !need(p.embd, p.n_embd, n.embd) ||
+        !need(p.rope_cos, p.n_rope, n.rope) || !need(p.rope_sin, p.n_rope, n.rope) || !need(p.qbuf, p.n_qbuf, n.qbuf) || !need(p.kcache, p.n_cache, n.cache) ||
+        !need(p.vcache, p.n_cache, n.cache) || !need(p.pv_part, p.n_pv, n.pv) || !need(p.l_part, p.n_l, n.l) || !need(p.tiles, p.n_tiles, n.tiles))
+        return bad("a NULL array, or a count too small for the geometry");
+    if (n.image && (!need(p.aq, p.n_aq, M * K) || !need(p.ad, p.n_ad, K) || !need(p.abs, p.n_abs, TK_MAX_TILES * K) || !need(p.abs16, p.n_abs16, TK_MAX_TILES * K) ||
+                    (p.af && p.n_af < M * K)))
+        return bad("an image array is NULL or too small");
+    return true;
+}
+
+bool tk_llm_step_probe(int device, tk_mi355x_llm_step_probe_s* pp, std::string& error) {
+    tk_mi355x_llm_step_probe_t& p = *pp;
+    StepNeed n;
+    if (!step_probe_check(p, n, error)) return false;
+    if (device < 0) return true;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) { error = "step probe: device ordinal out of range"; return false; }
+    HIPQ(hipSetDevice(device));
+    if (const char* e = tk_llm_prepare_device(device)) { error = e; return false; }
+    std::vector<void*> owned;
+    bool ok = true;
+    auto up = [&](const void* src, int64_t elems, size_t esz) -> void* { /* a device copy of a host array; nullptr for an absent one */
+        if (!ok || !src || elems <= 0) return nullptr;
+        void* d = nullptr;
+        if (hipMalloc(&d, (size_t)elems * esz) != hipSuccess) { ok = false; error = "step probe: out of device memory"; return nullptr; }
+        owned.push_back(d);
+        if (hipMemcpy(d, src, (size_t)elems * esz, hipMemcpyHostToDevice) != hipSuccess) { ok = false; error = "step probe: device error (upload)"; }
+        return d;
+    };
+    const int64_t M = TK_MAX_ROWS, K = n.image_k ? n.image_k : p.K;
+    float* dx = (float*)up(p.x, n.x, 4);
+    const float* dpart = (const float*)up(p.partial, n.partial, 4);
+    const float* dw = (const float*)up(p.w, n.w, 4);
+    const void* dembd = up(p.embd, n.embd, 1);
+    const int32_t* dtok = (const int32_t*)up(p.tok, p.op == TK_MI355X_STEP_EMBED ? n.rows : 0, 4);
+    const int32_t* dseq = (const int32_t*)up(p.seq, p.op != TK_MI355X_STEP_EMBED ? n.rows : 0, 4);
+    const int32_t* dpos = (const int32_t*)up(p.pos, p.op == TK_MI355X_STEP_ROPE_APPEND ? n.rows : 0, 4);
+    const float* dcos = (const float*)up(p.rope_cos, n.rope, 4);
+    const float* dsin = (const float*)up(p.rope_sin, n.rope, 4);
+    float* dq = (float*)up(p.qbuf, n.qbuf, 4);
+    uint16_t* dk = (uint16_t*)up(p.kcache, n.cache, 2);
+    uint16_t* dv = (uint16_t*)up(p.vcache, n.cache, 2);
+    const float* dpv = (const float*)up(p.pv_part, n.pv, 4);
+    const float* dl = (const float*)up(p.l_part, n.l, 4);
+    int32_t* dtiles = (int32_t*)up(p.tiles, n.tiles, 4);
+    TkActQ8 act{};
+    if (n.image) { /* alloc_act's strides over the caller's bytes: the image arrives as it was given, sentinels included */
+        act.aq_ts = TK_AQ_BYTES(K); act.ad_ts = TK_AD_FLOATS(K); act.abs_ts = TK_ABS_BYTES(K);
+        act.af_ts = (uint32_t)((size_t)K * TK_ROW_SLOTS); act.af_round = p.af_round;
+        act.aq = (int8_t*)up(p.aq, M * K, 1);
+        act.ad = (float*)up(p.ad, K, 4);
+        act.abs = (int8_t*)up(p.abs, TK_MAX_TILES * K, 1);
+        act.abs16 = (uint16_t*)up(p.abs16, TK_MAX_TILES * K, 2);
+        act.af = (float*)up(p.af, M * K, 4);
+    }
+    const bool twin = p.op >= TK_MI355X_STEP_FUSED_NORM;
+    auto make_act = [&](TkActQ8& a, int64_t k, const void* aq, const void* ad, const void* ab, const void* ab16) { /* an image over the caller's bytes, or (null) zeroed */
+        a.aq_ts = TK_AQ_BYTES(k); a.ad_ts = TK_AD_FLOATS(k); a.abs_ts = TK_ABS_BYTES(k); a.af = nullptr; a.af_ts = (uint32_t)((size_t)k * TK_ROW_SLOTS); a.af_round = TK_ROUND_NONE;
+        std::vector<uint8_t> zero;
+        if (!aq) { try { zero.assign((size_t)M * k, 0); } catch (const std::bad_alloc&) { ok = false; error = "step probe: out of host memory"; return; } }
+        a.aq = (int8_t*)up(aq ? aq : zero.data(), M * k, 1);
+        a.ad = (float*)up(ad ? ad : zero.data(), k, 4);
+        a.abs = (int8_t*)up(ab ? ab : zero.data(), TK_MAX_TILES * k, 1);
+        a.abs16 = (uint16_t*)up(ab16 ? ab16 : zero.data(), TK_MAX_TILES * k, 2);
+    };
+    const void* dwb = up(p.wblocks, n.wblocks, 1);
+    float *dya = (float*)up(p.y_a, n.y, 4), *dyb = (float*)up(p.y_b, n.y, 4), *dxb = (float*)up(p.x_b, n.xb, 4);
+    TkActQ8 act_b{}, act_in{};
+    if (n.image_b) make_act(act_b, K, p.aq_b, p.ad_b, p.abs_b, p.abs16_b);
+    if (ok && twin) {
+        hipStream_t s = nullptr;
+        const int nseg = p.op == TK_MI355X_STEP_WIDE_SWIGLU ? 2 : 1;
+        const size_t tb = (size_t)tk_type_desc_of(p.wtype).tile_bytes, nblk = (size_t)p.K / 256;
+        void* dt = nullptr;
+        if (hipMalloc(&dt, (size_t)nseg * p.wrows / TK_TILE_ROWS * nblk * tb) != hipSuccess) { ok = false; error = "step probe: out of device memory"; }
+        else owned.push_back(dt);
+        if (ok) {
+            tk_launch_repack(p.wtype, dwb, (int64_t)nseg * p.wrows, p.K, (uint8_t*)dt, s);
+            TkGemvArgs g{};
+            g.seg[0] = TkGemvSeg{(const uint8_t*)dt, p.wtype, p.wrows / TK_TILE_ROWS};
+            g.seg[1] = TkGemvSeg{(const uint8_t*)dt + (size_t)p.wrows / TK_TILE_ROWS * nblk * tb, p.wtype, p.wrows / TK_TILE_ROWS};
+            g.nseg = nseg; g.K = p.K; g.nrows = p.nrows;
+            if (p.op == TK_MI355X_STEP_WIDE_SWIGLU) {
+                make_act(act_in, p.K, nullptr, nullptr, nullptr, nullptr);
+                float* h = nullptr; /* form a's h [nrows][FF], then form b's gate | up slab [M][2 FF] */
+                if (ok && hipMalloc((void**)&h, (size_t)M * 2 * p.wrows * 4) != hipSuccess) { ok = false; error = "step probe: out of device memory"; }
+                if (ok) {
+                    owned.push_back(h);
+                    tk_launch_quant_q8(dx, p.K, p.nrows, act_in, s);
+                    set_act(g, act_in);
+                    g.ks = 1; g.out = h;
+                    TkGemvArgs a = g;
+                    a.swiglu = 1; a.n_total = p.wrows;
+                    tk_launch_gemv(a, s);
+                    tk_launch_quant_q8(h, p.wrows, p.nrows, act, s);
+                    g.n_total = 2 * p.wrows; /* the launch order keeps h's two uses apart: one stream */
+                    tk_launch_gemv(g, s);
+                    tk_launch_swiglu_q8(h, 1, p.wrows, p.nrows, act_b, s);
+                }
+            } else {
+                const bool norm = p.op == TK_MI355X_STEP_FUSED_NORM;
+                const int fks = norm && !p.partial ? 0 : p.fks;
+                make_act(act_in, p.K, nullptr, nullptr, nullptr, nullptr);
+                if (ok) {
+                    g.ks = p.ks; g.n_total = p.wrows;
+                    TkGemvArgs b = g; /* form b first: it reads the caller's x, which form a's norm updates in place */
+                    b.out = dyb; b.fuse = norm ? 1 : 2; b.fx_in = dx; b.fx_out = dxb; b.fslab = dpart; b.fks = fks; b.fn_total = norm ? p.n_total : 2 * p.K; b.fw = dw; b.feps = p.eps;
+                    tk_launch_gemv(b, s);
+                    if (norm) tk_launch_rmsnorm_q8(dx, dpart, fks, p.n_total, dw, p.eps, p.K, p.nrows, act_in, s);
+                    else tk_launch_swiglu_q8(dpart, fks, p.K, p.nrows, act_in, s);
+                    set_act(g, act_in);
+                    g.out = dya;
+                    tk_launch_gemv(g, s);
+                }
+            }
+        }
+        ok = ok && hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+        auto down = [&](void* dst, const void* src, int64_t elems, size_t esz) {
+            if (ok && dst && src && elems > 0) ok = hipMemcpy(dst, src, (size_t)elems * esz, hipMemcpyDeviceToHost) == hipSuccess;
+        };
+        if (n.x_out) down(p.x, dx, n.x, 4);
+        down(p.x_b, dxb, n.xb, 4);
+        down(p.y_a, dya, n.y, 4);
+        down(p.y_b, dyb, n.y, 4);
+        if (n.image) {
+            down(p.aq, act.aq, M * K, 1); down(p.ad, act.ad, K, 4); down(p.abs, act.abs, TK_MAX_TILES * K, 1); down(p.abs16, act.abs16, TK_MAX_TILES * K, 2);
+            down(p.aq_b, act_b.aq, M * K, 1); down(p.ad_b, act_b.ad, K, 4); down(p.abs_b, act_b.abs, TK_MAX_TILES * K, 1); down(p.abs16_b, act_b.abs16, TK_MAX_TILES * K, 2);
+        }
+        if (!ok && error.empty()) error = "step probe: device error";
+    } else if (ok) {
+        hipStream_t s = nullptr;
+        switch (p.op) {
+        case TK_MI355X_STEP_EMBED: tk_launch_embed(dembd, p.type, p.K, dtok, p.nrows, dx, s); break;
+        case TK_MI355X_STEP_RMSNORM: tk_launch_rmsnorm_q8(dx, dpart, p.ks, p.n_total, dw, p.eps, p.K, p.nrows, act, s); break;
+        case TK_MI355X_STEP_RESIDUAL_FOLD: tk_launch_residual_fold(dx, dpart, p.ks, p.n_total, p.K, p.nrows, s); break;
+        case TK_MI355X_STEP_SWIGLU: tk_launch_swiglu_q8(dpart, p.ks, p.K, p.nrows, act, s); break;
+        case TK_MI355X_STEP_QUANT: tk_launch_quant_q8(dx, p.K, p.nrows, act, s); break;
+        case TK_MI355X_STEP_ROPE_APPEND:
+            tk_launch_qkv_rope_append(dpart, p.ks, p.n_total, p.n_head, p.n_kv_head, p.head_dim, dcos, dsin, dseq, dpos, p.nrows, dq, dk, dv, p.layer, p.max_seq, p.max_ctx, s);
+            break;
+        case TK_MI355X_STEP_PV_JOIN: tk_launch_att_pv_join(dpv, dl, p.nrows, p.n_head, p.head_dim, act, s); break;
+        default: tk_launch_att_tiles(dseq, p.nrows, dtiles, s); break;
+        }
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+        auto down = [&](void* dst, const void* src, int64_t elems, size_t esz) {
+            if (ok && dst && src && elems > 0) ok = hipMemcpy(dst, src, (size_t)elems * esz, hipMemcpyDeviceToHost) == hipSuccess;
+        };
+        if (n.x_out) down(p.x, dx, n.x, 4);
+        down(p.qbuf, dq, n.qbuf, 4);
+        down(p.kcache, dk, n.cache, 2);
+        down(p.vcache, dv, n.cache, 2);
+        down(p.tiles, dtiles, n.tiles, 4);
+        if (n.image) {
+            down(p.aq, act.aq, M * K, 1);
+            down(p.ad, act.ad, K, 4);
+            down(p.abs, act.abs, TK_MAX_TILES * K, 1);
+            down(p.abs16, act.abs16, TK_MAX_TILES * K, 2);
+            down(p.af, act.af, M * K, 4);
+        }
+        if (!ok && error.empty()) error = "step probe: device error";
+    }
+    for (void* d : owned) (void)hipFree(d);
     return ok;
 }
 

@@ -79,6 +79,8 @@ void tk_launch_synth_f16(uint64_t seed, uint64_t tensor_id, int64_t n, float sca
 void tk_launch_synth_float(int type, uint64_t seed, uint64_t tensor_id, int64_t n, float scale, void* out, hipStream_t s);
 void tk_launch_rmsnorm_q8(float* x, const float* partial, int ks, int n_total_partial, const float* w, float eps, int D, int nrows,
                           TkActQ8 out, hipStream_t s);
+size_t tk_rmsnorm_lds_bytes(int D); /* dynamic LDS of one k_rmsnorm_q8 workgroup */
+int tk_llm_max_d_model();           /* the widest d_model whose norm fits the LDS opt-in (a multiple of 256) */
 void tk_launch_residual_fold(float* x, const float* partial, int ks, int n_total, int D, int nrows, hipStream_t s);
 void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s);
 void tk_launch_qkv_rope_append(const float* partial, int ks, int n_total, int n_head, int n_kv_head, int head_dim, const float* rope_cos,
@@ -91,6 +93,7 @@ void tk_launch_swiglu_q8(const float* partial, int ks, int FF, int nrows, TkActQ
 /* wide passes: the gate | up launch forms h = silu(gate) * up in its epilogue (half the slab bytes written and read back); then only the quantisation is left */
 /* rows up to which the norm / SwiGLU producer of a mat-vec launch runs inside it (TkGemvArgs::fuse) */
 #define TK_GEMV_FUSE_MAX_ROWS 2
+size_t tk_gemv_fused_lds_bytes(int K, int ks, int fuse /* 1 or 2 */); /* dynamic LDS of a mat-vec launch that carries its producer */
 bool tk_gemv_fuses_producer(int nrows, int K, int ks, int fks);
 bool tk_gemv_fuses_swiglu(int nrows, int ks, int type_gate, int type_up);
 void tk_launch_quant_q8(const float* hbuf, int FF, int nrows, TkActQ8 out, hipStream_t s);
@@ -138,6 +141,8 @@ void tk_launch_attention_long(const float* partial, int ks, int n_total, const f
 struct TkKvCopyDesc { int32_t src_seq, dst_seq, p0, n; };
 bool tk_launch_kv_copy_rows(const TkKvCopyDesc* desc, int ndesc, int max_n, uint16_t* kcache, uint16_t* vcache, int n_layer, int n_kv_head, int head_dim, int max_seq,
                             int max_ctx, hipStream_t s);
+/* the long-context form's last launch alone: the four classes of every head joined, divided, quantised (head_dim 64 or 128, n_head a multiple of 256 / head_dim) */
+void tk_launch_att_pv_join(const float* pv_part, const float* l_part, int nrows, int n_head, int head_dim, TkActQ8 out, hipStream_t s);
 size_t tk_gemv_lds_bytes(int K, int ks, int mtiles);
 /* dynamic LDS of one k_attention workgroup; must stay below 160 KiB (the session checks it against its max_ctx) */
 size_t tk_attention_lds_bytes(int gq, int head_dim, int max_ctx, int chunk /* positions per ring slot: 32, 64 or 128 */);

@@ -408,13 +408,17 @@ void tk_launch_residual_fold(float* x, const float* partial, int ks, int n_total
     hipLaunchKernelGGL(k_residual_fold, dim3((D / 4 + 255) / 256, nrows), dim3(256), 0, s, x, partial, ks, n_total, D);
 }
 
+/* the finished row and the canonical sum's four partials: above the 64 KiB default from d_model 16384 on, so tk_llm_prepare_device() opts the
+ * kernel in like the others, and tk_llm_max_d_model() is where TK_MAX_DYN_LDS ends (TkLlmModel::init refuses a wider model) */
+size_t tk_rmsnorm_lds_bytes(int D) { return ((size_t)D + 4) * sizeof(float); }
+
 void tk_launch_rmsnorm_q8(float* x, const float* partial, int ks, int n_total_partial, const float* w, float eps, int D, int nrows,
                           TkActQ8 out, hipStream_t s) {
     int nthr = D / 4; /* one thread per 16-byte group of the row, 256 .. 1024 */
     nthr = nthr < 256 ? 256 : nthr > 1024 ? 1024 : (nthr + 255) / 256 * 256;
     /* (round 6: four-wave workgroups while several decode streams share the device — so that the norm fits beside other streams' resident mat-vec
      * workgroups instead of waiting for one to retire — measured SLOWER: 3.99 against 3.90 ms per step and group at 3 x 16 rows, profiles/r06_northstar_explore.txt) */
-    hipLaunchKernelGGL(k_rmsnorm_q8, dim3(nrows), dim3(nthr), (D + 4) * sizeof(float), s, x, partial, ks, n_total_partial, w, eps, D, out);
+    hipLaunchKernelGGL(k_rmsnorm_q8, dim3(nrows), dim3(nthr), tk_rmsnorm_lds_bytes(D), s, x, partial, ks, n_total_partial, w, eps, D, out);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -2750,14 +2754,24 @@ void tk_launch_gemv(const TkGemvArgs& a, hipStream_t s) {
      * depth; the two-type kernel does not. */
     const int gti = mt == 2 && tk_types_is(types, TK_TYPE_Q6_K) ? TK_KERNEL_INDEX_Q4K_Q6K : ti;
     const int pf = nb % 2 == 0 ? 2 : 1;
-    const size_t fuse_lds = a.fuse == 1 ? ((size_t)a.K + 4) * sizeof(float) : 0; /* the finished row and the canonical sum's four partials */
+    const size_t fuse_lds = a.fuse == 1 ? tk_rmsnorm_lds_bytes(a.K) : 0; /* the finished row and the canonical sum's four partials */
     /* tk_gemv_fuses_producer() admits only launches of one M-tile and two tiles in flight */
     const int fuse = a.fuse && mt == 1 && pf == 2 ? (a.fuse == 1 ? 1 : 2) : 0;
     hipLaunchKernelGGL(k_gemv_fns[fuse][mt - 1][pf - 1][gti], dim3(groups * a.ks), dim3(64 * waves), lds + fuse_lds, s, a, groups, row_tiles);
 }
 
+size_t tk_gemv_fused_lds_bytes(int K, int ks, int fuse) {
+    return tk_gemv_lds_bytes(K, ks, 1) + (fuse == 1 ? tk_rmsnorm_lds_bytes(K) : 0); /* fuse 1: the finished row and the canonical sum's four partials */
+}
+
+int tk_llm_max_d_model() { return (int)((TK_MAX_DYN_LDS / sizeof(float) - 4) / 256 * 256); }
+
+/* a fused launch keeps the whole K-range's image in LDS whatever its length (tk_launch_gemv: image_fits), and the norm's row beside it: a
+ * geometry whose image does not fit (d_model 7936 and up at ks = 1, the logits matrix's split) takes the stand-alone producer.  The norm's
+ * size is asked of both forms: the caller does not say which one the launch carries */
 bool tk_gemv_fuses_producer(int nrows, int K, int ks, int fks) {
-    return nrows >= 1 && nrows <= TK_GEMV_FUSE_MAX_ROWS && ks >= 1 && K % (512 * ks) == 0 && fks >= 0 && fks <= TK_RMS_MAX_KS;
+    return nrows >= 1 && nrows <= TK_GEMV_FUSE_MAX_ROWS && ks >= 1 && K % (512 * ks) == 0 && fks >= 0 && fks <= TK_RMS_MAX_KS &&
+           tk_gemv_fused_lds_bytes(K, ks, 1) <= (size_t)TK_MAX_DYN_LDS;
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -3784,6 +3798,11 @@ __global__ __launch_bounds__(256) void k_att_pv_join(const float* __restrict__ p
     }
 }
 
+void tk_launch_att_pv_join(const float* pv_part, const float* l_part, int nrows, int n_head, int head_dim, TkActQ8 out, hipStream_t s) {
+    if (head_dim == 128) hipLaunchKernelGGL((k_att_pv_join<128>), dim3(n_head / 2, nrows), dim3(256), 0, s, pv_part, l_part, n_head, out);
+    else hipLaunchKernelGGL((k_att_pv_join<64>), dim3(n_head / 4, nrows), dim3(256), 0, s, pv_part, l_part, n_head, out);
+}
+
 void tk_launch_attention_long(const float* partial, int ks, int n_total, const float* rope_cos, const float* rope_sin, uint16_t* kcache, uint16_t* vcache,
                               const int32_t* seq, const int32_t* pos, int nrows, int n_head, int n_kv_head, int head_dim, int layer, int max_seq, int max_ctx,
                               float* scores, TkActQ8 out, hipStream_t s) {
@@ -3796,13 +3815,12 @@ void tk_launch_attention_long(const float* partial, int ks, int n_total, const f
         hipLaunchKernelGGL((k_att_scores_long<128>), gs, dim3(256), 0, s, partial, ks, n_total, rope_cos, rope_sin, kcache, vcache, seq, pos, n_head, n_kv_head, layer,
                            max_seq, max_ctx, scores);
         hipLaunchKernelGGL((k_att_pv_chain<128>), gc, dim3(64), 0, s, scores, vcache, seq, pos, n_head, n_kv_head, layer, max_seq, max_ctx, pv_part, l_part);
-        hipLaunchKernelGGL((k_att_pv_join<128>), dim3(n_head / 2, nrows), dim3(256), 0, s, pv_part, l_part, n_head, out);
     } else {
         hipLaunchKernelGGL((k_att_scores_long<64>), gs, dim3(256), 0, s, partial, ks, n_total, rope_cos, rope_sin, kcache, vcache, seq, pos, n_head, n_kv_head, layer,
                            max_seq, max_ctx, scores);
         hipLaunchKernelGGL((k_att_pv_chain<64>), gc, dim3(64), 0, s, scores, vcache, seq, pos, n_head, n_kv_head, layer, max_seq, max_ctx, pv_part, l_part);
-        hipLaunchKernelGGL((k_att_pv_join<64>), dim3(n_head / 4, nrows), dim3(256), 0, s, pv_part, l_part, n_head, out);
     }
+    tk_launch_att_pv_join(pv_part, l_part, nrows, n_head, head_dim, out, s);
 }
 
 size_t tk_attention_long_scratch_floats(int n_head, int head_dim, int max_ctx) {
@@ -4210,6 +4228,7 @@ const char* tk_llm_prepare_device(int device) {
     opt(k_attention_narrow);
     opt(k_attention_prefill<128>);
     opt(k_attention_prefill<64>);
+    opt(k_rmsnorm_q8);
     if (e != hipSuccess) return hipGetErrorString(e);
     done[device] = true;
     return nullptr;

@@ -87,6 +87,76 @@ def gemv_probe(ttype, blocks, rows, K, ks, x, device=0):
     return y
 
 
+# tk_mi355x_llm_step_probe's ops
+STEP_EMBED, STEP_RMSNORM, STEP_RESIDUAL_FOLD, STEP_SWIGLU, STEP_QUANT, STEP_ROPE_APPEND, STEP_PV_JOIN, STEP_ATT_TILES, STEP_FUSED_NORM, STEP_FUSED_SWIGLU, STEP_WIDE_SWIGLU = range(11)
+STEP_IMAGE_OPS = (STEP_RMSNORM, STEP_SWIGLU, STEP_QUANT, STEP_PV_JOIN, STEP_WIDE_SWIGLU)
+ROUND_NONE, ROUND_F16, ROUND_BF16 = 0, 1, 2
+
+
+class LlmStepProbe(C.Structure):  # tk_mi355x_llm_step_probe_t
+    _fields_ = [(n, C.c_int32) for n in ("op", "nrows", "K", "ks", "n_total", "af_round", "type", "vocab", "n_head", "n_kv_head", "head_dim", "n_layer", "max_seq",
+                                          "max_ctx", "layer")] + [("eps", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("x", "partial", "w", "embd", "tok", "seq", "pos", "rope_cos", "rope_sin", "qbuf", "kcache", "vcache", "pv_part", "l_part",
+                                           "tiles", "aq", "ad", "abs", "abs16", "af")] + \
+               [(n, C.c_int64) for n in ("n_x", "n_partial", "n_w", "n_embd", "n_rows", "n_rope", "n_qbuf", "n_cache", "n_pv", "n_l", "n_tiles", "n_aq", "n_ad", "n_abs",
+                                          "n_abs16", "n_af")] + \
+               [(n, C.c_void_p) for n in ("wblocks", "y_a", "y_b", "x_b", "aq_b", "ad_b", "abs_b", "abs16_b")] + \
+               [(n, C.c_int64) for n in ("n_wblocks", "n_y", "n_xb")] + [(n, C.c_int32) for n in ("wtype", "wrows", "fks", "reserved")]
+
+
+_STEP_ARRAYS = {"x": (np.float32, "n_x"), "partial": (np.float32, "n_partial"), "w": (np.float32, "n_w"), "embd": (np.uint8, "n_embd"), "tok": (np.int32, "n_rows"),
+                "seq": (np.int32, "n_rows"), "pos": (np.int32, "n_rows"), "rope_cos": (np.float32, "n_rope"), "rope_sin": (np.float32, "n_rope"),
+                "qbuf": (np.float32, "n_qbuf"), "kcache": (np.uint16, "n_cache"), "vcache": (np.uint16, "n_cache"), "pv_part": (np.float32, "n_pv"),
+                "l_part": (np.float32, "n_l"), "tiles": (np.int32, "n_tiles"), "aq": (np.int8, "n_aq"), "ad": (np.float32, "n_ad"), "abs": (np.int8, "n_abs"),
+                "abs16": (np.uint16, "n_abs16"), "af": (np.float32, "n_af"), "wblocks": (np.uint8, "n_wblocks"), "y_a": (np.float32, "n_y"), "y_b": (np.float32, "n_y"),
+                "x_b": (np.float32, "n_xb"), "aq_b": (np.int8, None), "ad_b": (np.float32, None), "abs_b": (np.int8, None), "abs16_b": (np.uint16, None)}
+_STEP_OUT = ("x", "qbuf", "kcache", "vcache", "tiles", "aq", "ad", "abs", "abs16", "af", "y_a", "y_b", "x_b", "aq_b", "ad_b", "abs_b", "abs16_b")
+_STEP_SCALARS = ("nrows", "K", "ks", "n_total", "af_round", "type", "vocab", "n_head", "n_kv_head", "head_dim", "n_layer", "max_seq", "max_ctx", "layer", "wtype", "wrows", "fks")
+
+
+def llm_step_probe(op, device=0, image_fill=None, **kw):
+    """ONE launch of a step launcher of the LLM stream (tk_mi355x_llm_step_probe).  Keywords: the struct's scalars (nrows, K, ks, n_total, af_round, type, vocab,
+    n_head, n_kv_head, head_dim, n_layer, max_seq, max_ctx, layer, wtype, wrows, fks, eps) and its arrays by name; COPIES of the in/out arrays (x, qbuf, kcache, vcache, tiles
+    the raw image aq / ad / abs / abs16 / af, and the twins' y_a, y_b, x_b and second image) come back in a dict, None where not given.  image_fill: a byte (0..255) — the image arrays not given are
+    made here, every byte of them that value: aq, ad, abs, abs16, and with want_af the float image af.  device < 0 validates only"""
+    p = LlmStepProbe()
+    p.op = op
+    keep = {}
+    if image_fill is not None and op in STEP_IMAGE_OPS:
+        K, M = int(kw.get("wrows" if op == STEP_WIDE_SWIGLU else "K", 0)), lib().tk_mi355x_llm_max_rows()
+        if 0 < K <= 65536:
+            for suffix in ("", "_b") if op == STEP_WIDE_SWIGLU else ("",):
+                for name, n in (("aq", M * K), ("ad", K), ("abs", M // 16 * K), ("abs16", M // 16 * K)):
+                    kw.setdefault(name + suffix, np.frombuffer(bytes([image_fill]) * (n * np.dtype(_STEP_ARRAYS[name][0]).itemsize), _STEP_ARRAYS[name][0]))
+            if kw.get("want_af", False):
+                kw.setdefault("af", np.frombuffer(bytes([image_fill]) * (M * K * 4), np.float32))
+    kw.pop("want_af", None)
+    for name, v in kw.items():
+        if name in _STEP_ARRAYS:
+            if v is None:
+                continue
+            dt, cnt = _STEP_ARRAYS[name]
+            a = np.array(v, dtype=dt).reshape(-1) if name in _STEP_OUT else np.ascontiguousarray(v, dtype=dt).reshape(-1)
+            keep[name] = a
+            setattr(p, name, a.ctypes.data)
+            if cnt is None:                                               # the second image: the counts of the first
+                continue
+            if cnt in ("n_rows", "n_rope", "n_cache", "n_y"):              # shared counts: the shortest array given
+                have = getattr(p, cnt)
+                setattr(p, cnt, a.size if have == 0 else min(have, a.size))
+            else:
+                setattr(p, cnt, a.size)
+        elif name == "eps":
+            p.eps = float(v)
+        elif name in _STEP_SCALARS:
+            setattr(p, name, int(v))
+        else:
+            raise TypeError("llm_step_probe: no field %r" % name)
+    lib().tk_mi355x_llm_step_probe.argtypes = [C.c_int, C.POINTER(LlmStepProbe)]
+    check(lib().tk_mi355x_llm_step_probe(device, C.byref(p)))
+    return {k: keep.get(k) for k in _STEP_OUT}
+
+
 # bytes of one W4A8 tile, 16 rows x 256 k (csrc/llm/tk_llm_layout.h): 16 x the bytes of a row's run, but for Q3_K and IQ4_XS, whose tiles hold
 # their scales unpacked, and TQ1_0, which is installed as TQ2_0 tiles
 TILE_BYTES = {t: 16 * (256 // (32 if t in TYPES_OF_32 else 256)) * b for t, b in BLOCK_BYTES.items()}
