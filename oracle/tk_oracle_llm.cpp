@@ -460,6 +460,16 @@ static void matvec(const orc_tensor& t, int ks, const float* h, float* y, std::v
     orc_gemv_q8(t.type, t.data.data(), t.rows, K, ks, q.data(), d.data(), bs.data(), y);
 }
 
+/* Deliberately wrong attention, for the tests that prove a bit-exact comparison can see a subtly wrong kernel (tests/test_attention_geometry_cpu.py);
+ * 0 = the canonical arithmetic, and nothing but those tests ever sets anything else:
+ *   1  the four PV / denominator partial sums are combined as (a0 + a2) + (a1 + a3) instead of ((a0 + a1) + a2) + a3;
+ *   2  the score of position T - 2 is left out (of the maximum, the denominator and the PV sums). */
+static int g_attention_mutant = 0;
+void orc_set_attention_mutant(int which) { g_attention_mutant = which; }
+static float att_join4(const float* a) {
+    return g_attention_mutant == 1 ? (a[0] + a[2]) + (a[1] + a[3]) : ((a[0] + a[1]) + a[2]) + a[3];
+}
+
 /*
  * One pass over n_rows (seq, pos, token) rows.  All rows' K/V are appended before any row
  * attends, so several rows of one sequence (prefill) see each other causally.
@@ -513,7 +523,9 @@ void orc_llm_forward(orc_llm* m, int n_rows, const int32_t* seq, const int32_t* 
             for (int hh = 0; hh < NH; ++hh) {
                 int kvh = hh / grp;
                 float mx = -INFINITY;
+                const int skip = g_attention_mutant == 2 ? T - 2 : -1; /* mutant 2: this position does not exist */
                 for (int t = 0; t < T; ++t) {
+                    if (t == skip) continue;
                     const uint16_t* kr = &m->kcache[sbase + ((size_t)t * NKV + kvh) * HD];
                     float a = 0.0f;
                     for (int i = 0; i < HD; ++i) a = tk_fmaf(qr[hh * HD + i], tk_f16_to_f32(kr[i]), a);
@@ -522,13 +534,17 @@ void orc_llm_forward(orc_llm* m, int n_rows, const int32_t* seq, const int32_t* 
                 }
                 /* canonical order: 4 interleaved partial sums over positions (t mod 4), combined in order */
                 float lp[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                for (int t = 0; t < T; ++t) { sc[t] = tk_expf(sc[t] - mx); lp[t & 3] = lp[t & 3] + sc[t]; }
-                const float lsum = ((lp[0] + lp[1]) + lp[2]) + lp[3];
+                for (int t = 0; t < T; ++t) {
+                    if (t == skip) continue;
+                    sc[t] = tk_expf(sc[t] - mx);
+                    lp[t & 3] = lp[t & 3] + sc[t];
+                }
+                const float lsum = att_join4(lp);
                 for (int i = 0; i < HD; ++i) {
                     float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                     for (int t = 0; t < T; ++t)
-                        a[t & 3] = tk_fmaf(sc[t], tk_f16_to_f32(m->vcache[sbase + ((size_t)t * NKV + kvh) * HD + i]), a[t & 3]);
-                    ar[hh * HD + i] = tk_divf(((a[0] + a[1]) + a[2]) + a[3], lsum);
+                        if (t != skip) a[t & 3] = tk_fmaf(sc[t], tk_f16_to_f32(m->vcache[sbase + ((size_t)t * NKV + kvh) * HD + i]), a[t & 3]);
+                    ar[hh * HD + i] = tk_divf(att_join4(a), lsum);
                 }
             }
             matvec(L[ORC_L_O], c.ks_o, ar, o.data(), q8, qd, qb);

@@ -57,6 +57,7 @@ def lib():
         L.orc_llm_forward.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.orc_sample_row.restype = C.c_int32
         L.orc_sample_row.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_uint32]
+        L.orc_set_attention_mutant.argtypes = [C.c_int]
         L.orc_llm_kv_write.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2
         L.orc_llm_kv_read.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2
         L.orc_rmsnorm.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
@@ -150,6 +151,24 @@ class OracleLlm:
         am = np.empty(n, dtype=np.int32)
         lib().orc_llm_forward(self.h, n, ptr(seq), ptr(pos), ptr(tok), ptr(logits) if want_logits else None, ptr(am))
         return logits, am
+
+
+ATT_CANONICAL, ATT_MUTANT_JOIN_ORDER, ATT_MUTANT_SKIP_T2 = 0, 1, 2
+
+
+class attention_mutant:
+    """`with attention_mutant(ATT_MUTANT_..)`: every OracleLlm.forward inside computes deliberately wrong attention (orc_set_attention_mutant);
+    the canonical arithmetic is back on the way out, whatever happens inside"""
+
+    def __init__(self, which):
+        self.which = which
+
+    def __enter__(self):
+        lib().orc_set_attention_mutant(self.which)
+
+    def __exit__(self, *exc):
+        lib().orc_set_attention_mutant(ATT_CANONICAL)
+        return False
 
 
 def sample_row(logits, temp, top_k, top_p, min_p, seed, counter, allow=None):

@@ -105,6 +105,8 @@ static const char* head_geometry_error(int n_head, int n_kv_head, int head_dim) 
     if (n_head <= 0 || head_dim <= 0 || ((int64_t)n_head * head_dim) % 256) return "d_model, d_ff and n_head*head_dim must be multiples of 256";
     if (n_kv_head <= 0 || n_head % n_kv_head || (grp != 1 && grp != 2 && grp != 4)) return "n_head / n_kv_head must be 1, 2 or 4";
     if ((grp * head_dim) % 256 || head_dim % 64) return "head_dim must be a multiple of 64 and (n_head/n_kv_head)*head_dim a multiple of 256";
+    /* k_attention's value phase gives a lane the dims (2 lane, 2 lane + 1) of two blocks of 128: 256 dims of a head and no more */
+    if (head_dim > 256) return "head_dim must be at most 256: the attention kernels form 256 output dims per head";
     return nullptr;
 }
 

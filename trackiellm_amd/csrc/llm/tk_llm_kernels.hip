@@ -2874,6 +2874,12 @@ __device__ __forceinline__ v2f sum_partials_pair(const float* partial, int ks, i
     return o;
 }
 
+/* The XOR swizzle of a key row's 16-byte pieces: piece i of row r lies in piece slot i ^ (r & mask).  That is a permutation of the row's
+ * ppr = head_dim / 8 slots only if the XOR never carries a slot index past ppr, i.e. if mask + 1 divides ppr: the mask is the largest power
+ * of two that divides ppr, less one (ppr - 1 for head_dim 64, 128, 256; 7 for head_dim 192, whose 24 pieces swizzle inside groups of 8).
+ * att_stage (writer), the own-row patch and the key reader of k_attention all take it from here. */
+__device__ __forceinline__ int att_swizzle_mask(int ppr) { return (ppr & -ppr) - 1; }
+
 /* stage rows [row0, row0 + 32) of one (sequence, kv head) cache run into an LDS slot; rows past `last_row` are clamped (their
  * content is never used).  swz: XOR-swizzle the 16-byte pieces of a row by the row number (K); plain copy otherwise (V).
  * Every wave issues exactly chunk_bytes / 4096 one-KiB pieces: the counted waits rely on it. */
@@ -2882,13 +2888,14 @@ __device__ __forceinline__ v2f sum_partials_pair(const float* partial, int ks, i
 __device__ __forceinline__ void att_stage(const uint16_t* run, int row0, int last_row, int rb /* row bytes */, uint8_t* slot, bool swz, int wave, int lane, int chunk,
                                           int row_end = -1) {
     const int pieces = chunk * rb / 1024, ppr = rb / 16; /* 1 KiB pieces per chunk; 16-byte pieces per row */
+    const int swm = att_swizzle_mask(ppr);
     for (int pc = wave; pc < pieces; pc += 4) {
         if (row_end >= 0 && row0 + pc * 64 / ppr >= row_end) continue; /* wave-uniform: a piece's first row (no early exit: the loop stays unrolled) */
         const int idx = pc * 64 + lane;           /* 16-byte piece index inside the chunk */
         const int r = idx / ppr, cs = idx % ppr;  /* row inside the chunk, piece slot inside the row */
         int gr = row0 + r;
         gr = gr < last_row ? gr : last_row;
-        const int src = swz ? (cs ^ (r & (ppr - 1))) : cs;
+        const int src = swz ? (cs ^ (r & swm)) : cs;
         const auto gs = (const __attribute__((address_space(1))) void*)((const uint8_t*)run + (int64_t)gr * rb + src * 16);
         const auto ls = (__attribute__((address_space(3))) void*)(slot + pc * 1024);
         __builtin_amdgcn_global_load_lds(gs, ls, 16, 0, 0);
@@ -2941,7 +2948,7 @@ __global__ __launch_bounds__(256, CH == 32 ? 8 : 4) void k_attention(const float
     const int nchunk = (T + CH - 1) / CH;
     const int total = 2 * nchunk;              /* the stream: K chunks nchunk - 1 .. 0, then V chunks 0 .. nchunk - 1 */
     const int last_row = max_ctx - 1;
-    const int ppr = rb / 16;
+    const int ppr = rb / 16, swm = att_swizzle_mask(ppr);
     auto issue = [&](int j) { /* chunk j of the stream into slot j % 2; always issued (a chunk with nothing cached yet re-reads clamped rows) */
         const bool is_k = j < nchunk;
         const int c = is_k ? nchunk - 1 - j : j - nchunk;
@@ -2998,7 +3005,7 @@ __global__ __launch_bounds__(256, CH == 32 ? 8 : 4) void k_attention(const float
         uint8_t* slot = ring + (j % 2) * slot_bytes;
         if (FUSED && j == 0) { /* the row's own key (position p, always in the last chunk) comes from LDS, swizzled like the rest */
             const int rr = p - c * CH;
-            if (t < ppr) *(uint4*)(slot + rr * rb + ((t ^ (rr & (ppr - 1))) * 16)) = *(const uint4*)((const uint8_t*)own + t * 16);
+            if (t < ppr) *(uint4*)(slot + rr * rb + ((t ^ (rr & swm)) * 16)) = *(const uint4*)((const uint8_t*)own + t * 16);
             __syncthreads();
         }
         const int tt = c * CH + srr;
@@ -3010,7 +3017,7 @@ __global__ __launch_bounds__(256, CH == 32 ? 8 : 4) void k_attention(const float
             for (int i0 = 0; i0 < ppr; i0 += KB) {
                 uint4 kv[KB];
 #pragma unroll
-                for (int u = 0; u < KB; ++u) kv[u] = *(const uint4*)(kr + (((i0 + u) ^ (srr & (ppr - 1))) * 16));
+                for (int u = 0; u < KB; ++u) kv[u] = *(const uint4*)(kr + (((i0 + u) ^ (srr & swm)) * 16));
 #pragma unroll
                 for (int u = 0; u < KB; ++u) {
                     const v4f q0 = *(const v4f*)(qh + 8 * (i0 + u)), q1 = *(const v4f*)(qh + 8 * (i0 + u) + 4);
