@@ -279,6 +279,40 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_kv_copy(tk_mi355x_llm_
  * of `iters` rounds after a warm-up; bytes = read + written by one round of either form */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_time_kv_copy(tk_mi355x_llm_session_t* s, int n_pos, int n_dst, int iters, float* kernel_ms,
                                                                float* memcpy_ms, double* bytes);
+/* ---- context shift (csrc/common/tk_kv_shift.h; opt-in; include/tk/ABI_NOTES.md): what llama.cpp's hosts do when a context fills — keep the first
+ * n_keep tokens, drop half of the rest, move the surviving cache rows down and re-rotate their keys to the new positions. ---- */
+/* rows [p0, p1) of sequence seq become rows [p0 + delta, p1 + delta) in every layer, KV head and both caches: values are copied bit for bit, every key
+ * pair (a, b) becomes f16(fma(b, s, a c)), f16(fma(-a, s, b c)) with c, s = the session's RoPE table at row -delta (a second f16 rounding of the key,
+ * as llama.cpp's K-shift on an f16 cache).  One launch, synchronous.  Valid: 0 <= p0 < p1 <= max_ctx, delta < 0, p0 + delta >= 0, seq a sequence of the
+ * session; anything else is TK_ERROR_INVALID_ARGUMENT and nothing is launched.  Source and destination may overlap.  Rows outside the destination
+ * range keep their bits — the stale tail [p1 + delta, p1) included — and so does every other sequence.  TK_ERROR_NOT_IMPLEMENTED: head_dim % 8 != 0 */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_kv_shift(tk_mi355x_llm_session_t* s, int seq, int p0, int p1, int delta);
+/* stand-alone timing of that launch (tools/time_kv_shift.py): `iters` launches after a warm-up, device events around them; average ms of one, bytes
+ * read + written by one */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_time_kv_shift(tk_mi355x_llm_session_t* s, int seq, int p0, int p1, int delta, int iters, float* avg_ms,
+                                                                double* bytes);
+/* the same move on host arrays (tests), tk_mi355x_logit_adjust_probe's contract: kcache / vcache are IN/OUT, in the cache layout
+ * [n_layer][max_seq][n_kv_head][max_ctx][head_dim] f16 bits for the geometry given; rope_cos / rope_sin are [max_ctx][head_dim / 2] as the caller
+ * gives them.  device >= 0: ONE production launch on that device, the arrays read back whole.  device < 0: the same per-row function in a host loop,
+ * no GPU touched.  Everything is validated before any device is touched: a NULL array, head_dim not a multiple of 8 (or above 256), a move the
+ * session entry refuses, or more than 2^31 cache elements are TK_ERROR_INVALID_ARGUMENT with the arrays untouched */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_kv_shift_probe(int device, int32_t n_layer, int32_t max_seq, int32_t n_kv_head, int32_t max_ctx, int32_t head_dim,
+                                                             uint16_t* kcache, uint16_t* vcache, const float* rope_cos, const float* rope_sin, int32_t seq,
+                                                             int32_t p0, int32_t p1, int32_t delta);
+/* the runner's policy, OFF by default (off: generate_next_token ends at the end of the context and a tool response that does not fit fails, as the
+ * reference does).  on = 1: when generate_next_token would stop because n_past + 1 >= n_ctx, or add_tool_response's tokens would not fit, the runner
+ * applies llama.cpp's rule ONCE — n_left = n_past - n_keep, n_discard = n_left / 2, rows [n_keep + n_discard, n_past) move by -n_discard,
+ * n_past -= n_discard — and goes on.  n_keep >= 0, or -1 = the token count of the last prepare_generation (llama.cpp's --keep -1), resolved when the
+ * shift happens.  If n_discard == 0, or a tool response still does not fit after one shift, the call ends exactly as with the policy off and
+ * nothing has moved.  prepare_generation with a prompt longer than the context fails as before.  The penalty window, the grammar state, the
+ * sampling counter and tool_call_text are untouched by a shift.  Takes effect from the next call.  n_keep < -1: TK_ERROR_INVALID_ARGUMENT.
+ * Two failures a host may want to tell apart.  A device error in the move itself: generate_next_token returns NULL, as at the end of a generation,
+ * with the error detail set (tk_error_get_detail; it is empty after a normal end) and context_shifts unchanged; add_tool_response returns
+ * TK_ERROR_INFERENCE_FAILED with that detail.  A shift that succeeded followed by a pass that failed: the rows HAVE moved, n_past is the reduced
+ * one and context_shifts counts the shift — the runner's state is that of a shifted context whose next token was not computed. */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_context_shift(struct tk_llm_runner_s* runner, int on, int32_t n_keep);
+/* shifts made, and rows dropped by them in total, since the last prepare_generation */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_context_shifts(struct tk_llm_runner_s* runner, int32_t* shifts, int64_t* discarded);
 /* equal-length prompts for sequences 0..nseq-1; first_tokens[nseq] optional */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_prefill(tk_mi355x_llm_session_t* s, int nseq, int n_prompt, const int32_t* tokens,
                                                           int32_t* first_tokens);

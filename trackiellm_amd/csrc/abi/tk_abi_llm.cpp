@@ -437,6 +437,20 @@ tk_error_code_t tk_mi355x_llm_session_kv_copy(tk_mi355x_llm_session_t* s, int sr
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_llm_session_kv_shift(tk_mi355x_llm_session_t* s, int seq, int p0, int p1, int delta) {
+    if (!s) return TK_ERROR_INVALID_ARGUMENT;
+    if (!s->session.kv_copy_applies()) return fail(TK_ERROR_NOT_IMPLEMENTED, "kv_shift needs head_dim to be a multiple of 8");
+    bool bad_args = false;
+    if (!s->session.kv_shift(seq, p0, p1, delta, &bad_args)) return fail(bad_args ? TK_ERROR_INVALID_ARGUMENT : TK_ERROR_GPU_ROCM_ERROR, s->session.error);
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_time_kv_shift(tk_mi355x_llm_session_t* s, int seq, int p0, int p1, int delta, int iters, float* avg_ms, double* bytes) {
+    if (!s || !avg_ms || !bytes) return TK_ERROR_INVALID_ARGUMENT;
+    if (!s->session.time_kv_shift(seq, p0, p1, delta, iters, avg_ms, bytes)) return fail(TK_ERROR_GPU_ROCM_ERROR, s->session.error);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_prefill(tk_mi355x_llm_session_t* s, int nseq, int n_prompt, const int32_t* tokens, int32_t* first_tokens) {
     if (!s || !tokens) return TK_ERROR_INVALID_ARGUMENT;
     if (!s->session.prefill(nseq, n_prompt, tokens, first_tokens)) return fail(TK_ERROR_INFERENCE_FAILED, s->session.error);
@@ -855,6 +869,12 @@ struct tk_llm_runner_s {
         adj.n_bias = (int32_t)bias_ids.size(); adj.bias_ids = bias_ids.data(); adj.bias = bias.data();
         return &adj;
     }
+    /* context shift (tk_mi355x_llm_runner_set_context_shift), off by default: llama.cpp's answer to a full context */
+    bool shift_on = false;
+    int32_t shift_keep = 0;      /* n_keep; -1 = prompt_tokens, resolved when a shift happens */
+    int32_t prompt_tokens = 0;   /* token count of the last prepare_generation */
+    int32_t n_shifts = 0;        /* since the last prepare_generation */
+    int64_t n_discarded = 0;
     bool is_processing = false;
     std::string piece;
     std::string system_prompt;
@@ -989,10 +1009,52 @@ void tk_llm_runner_destroy(tk_llm_runner_t** runner) {
     *runner = nullptr;
 }
 
+tk_error_code_t tk_mi355x_llm_runner_set_context_shift(tk_llm_runner_t* runner, int on, int32_t n_keep) {
+    if (!runner || (on != 0 && on != 1)) return TK_ERROR_INVALID_ARGUMENT;
+    if (n_keep < -1) return fail(TK_ERROR_INVALID_ARGUMENT, "context shift: n_keep must be >= 0, or -1 for the last prompt's token count");
+    if (on && runner->model->model.hp.head_dim % 8 != 0) return fail(TK_ERROR_NOT_IMPLEMENTED, "context shift moves rows in 16-byte words: head_dim must be a multiple of 8");
+    runner->shift_on = on != 0;
+    runner->shift_keep = n_keep;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_runner_context_shifts(tk_llm_runner_t* runner, int32_t* shifts, int64_t* discarded) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    if (shifts) *shifts = runner->n_shifts;
+    if (discarded) *discarded = runner->n_discarded;
+    return TK_SUCCESS;
+}
+
+/* llama.cpp's context shift (examples/main): n_left = n_past - n_keep, n_discard = n_left / 2, rows [n_keep + n_discard, n_past) move down by
+ * n_discard, n_past -= n_discard.  Applied once, when `need` more rows do not fit (n_past + need >= n_ctx) but fit after the shift; false (nothing
+ * changed, *failed false) when the policy is off, nothing can be dropped or the rows still would not fit; false with *failed when the move failed */
+static bool context_shift(tk_llm_runner_s* r, int need, bool* failed) {
+    *failed = false;
+    if (!r->shift_on) return false;
+    const int n_keep = r->shift_keep < 0 ? r->prompt_tokens : r->shift_keep;
+    const int n_discard = (r->n_past - n_keep) / 2;
+    if (n_discard <= 0 || r->n_past - n_discard + need >= r->n_ctx) return false;
+    std::string err;
+    if (!r->batcher->shift(r->slot, n_keep, n_discard, r->n_past, &err)) {
+        tk_error_set_detail("%s", err.c_str());
+        *failed = true;
+        return false;
+    }
+    r->n_past -= n_discard;
+    r->n_shifts++;
+    r->n_discarded += n_discard;
+    return true;
+}
+
 /* feed `toks` at positions n_past.. ; the last one is sampled.  The rows join whatever passes the model's scheduler is forming. */
 static tk_error_code_t feed(tk_llm_runner_s* r, const std::vector<int32_t>& toks, bool whole_context = false) {
     if (toks.empty()) return TK_SUCCESS;
-    if (r->n_past + (int)toks.size() >= r->n_ctx) return fail(TK_ERROR_INFERENCE_FAILED, "prompt exceeds the context window");
+    if (r->n_past + (int)toks.size() >= r->n_ctx) {
+        bool failed = false;
+        /* a prompt (whole_context) that is longer than the context is refused whatever the policy: there is nothing behind it to drop */
+        if (whole_context || !context_shift(r, (int)toks.size(), &failed))
+            return failed ? TK_ERROR_INFERENCE_FAILED : fail(TK_ERROR_INFERENCE_FAILED, "prompt exceeds the context window");
+    }
     int32_t am = -1;
     std::string err;
     /* whole_context (prepare_generation): the tokens start at position 0, so the scheduler may keep or copy rows the cache already holds for them */
@@ -1016,6 +1078,9 @@ tk_error_code_t tk_llm_runner_prepare_generation(tk_llm_runner_t* runner, const 
     runner->pending = -1;
     runner->accepted.clear(); /* llama_sampling_reset (tk_runner_streaming.c:42): the only call that empties the window */
     runner->last_prompt = TkLlmBatcher::PrefixRows{(int32_t)toks.size(), 0, 0};
+    runner->prompt_tokens = (int32_t)toks.size();
+    runner->n_shifts = 0;
+    runner->n_discarded = 0;
     tk_error_code_t rc = feed(runner, toks, true);
     if (rc != TK_SUCCESS) return rc;
     runner->is_processing = true;
@@ -1043,7 +1108,10 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
             return (const char*)1;
         }
     }
-    if (runner->n_past + 1 >= runner->n_ctx) { runner->is_processing = false; return NULL; }
+    if (runner->n_past + 1 >= runner->n_ctx) {
+        bool failed = false;
+        if (!context_shift(runner, 1, &failed)) { runner->is_processing = false; return NULL; }
+    }
     int32_t t = id, am = -1;
     std::string err;
     if (!runner->batcher->submit(runner->slot, runner->n_past, &t, 1, runner->next_mask(), &am, &err, runner->next_samp(), nullptr, runner->next_adjust())) {

@@ -426,6 +426,46 @@ tk_error_code_t tk_mi355x_logit_adjust_probe(int device, int32_t rows, int32_t c
     return rc;
 }
 
+tk_error_code_t tk_mi355x_kv_shift_probe(int device, int32_t n_layer, int32_t max_seq, int32_t n_kv_head, int32_t max_ctx, int32_t head_dim, uint16_t* kcache,
+                                         uint16_t* vcache, const float* rope_cos, const float* rope_sin, int32_t seq, int32_t p0, int32_t p1, int32_t delta) {
+    const int32_t cap = 1 << 16;
+    if (!kcache || !vcache || !rope_cos || !rope_sin || n_layer < 1 || n_layer > cap || max_seq < 1 || max_seq > cap || n_kv_head < 1 || n_kv_head > cap || max_ctx < 1 ||
+        max_ctx > cap || head_dim < 8 || head_dim > 256 || head_dim % 8 != 0)
+        return TK_ERROR_INVALID_ARGUMENT;
+    const TkKvShiftDesc m{seq, p0, p1, delta};
+    if (!tk_kv_shift_ok(m, max_seq, max_ctx)) return TK_ERROR_INVALID_ARGUMENT;
+    const int64_t elems = (int64_t)n_layer * max_seq * n_kv_head * max_ctx * head_dim;
+    if (elems > ((int64_t)1 << 31)) return TK_ERROR_INVALID_ARGUMENT;
+    if (device < 0) {
+        for (int layer = 0; layer < n_layer; ++layer)
+            for (int kvh = 0; kvh < n_kv_head; ++kvh) {
+                const size_t run = (((size_t)layer * max_seq + seq) * n_kv_head + kvh) * max_ctx * head_dim;
+                tk_kv_shift_run(kcache + run, true, m, head_dim, rope_cos, rope_sin);
+                tk_kv_shift_run(vcache + run, false, m, head_dim, rope_cos, rope_sin);
+            }
+        return TK_SUCCESS;
+    }
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    const size_t table = (size_t)max_ctx * (head_dim / 2) * 4;
+    struct Buf { const void* host; size_t bytes; void* dev; bool out; };
+    Buf b[] = {{kcache, (size_t)elems * 2, nullptr, true}, {vcache, (size_t)elems * 2, nullptr, true}, {rope_cos, table, nullptr, false}, {rope_sin, table, nullptr, false}};
+    bool ok = true;
+    for (Buf& q : b) ok = ok && hipMalloc(&q.dev, q.bytes) == hipSuccess && hipMemcpy(q.dev, q.host, q.bytes, hipMemcpyHostToDevice) == hipSuccess;
+    tk_error_code_t rc = ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
+    if (ok) {
+        if (!tk_launch_kv_shift_rows(m, (uint16_t*)b[0].dev, (uint16_t*)b[1].dev, (const float*)b[2].dev, (const float*)b[3].dev, n_layer, n_kv_head, head_dim, max_seq,
+                                     max_ctx, nullptr)) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+        else
+            for (Buf& q : b)
+                if (q.out && hipMemcpy(const_cast<void*>(q.host), q.dev, q.bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+    }
+    for (Buf& q : b) if (q.dev) (void)hipFree(q.dev);
+    return rc;
+}
+
 tk_error_code_t tk_mi355x_lang_pick_probe(int device, int32_t rows, int32_t cols, int32_t ld, const float* logits, int64_t n_logits, int32_t tok0, int32_t n_lang,
                                           const int32_t* auto_row, int32_t* slot, int32_t* ids, float* probs) {
     if (!logits || !auto_row || !slot || !ids || !probs || tk_lang_pick_check(rows, cols, ld, tok0, n_lang)) return TK_ERROR_INVALID_ARGUMENT;

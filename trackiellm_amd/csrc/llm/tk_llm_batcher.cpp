@@ -149,6 +149,19 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
     return true;
 }
 
+bool TkLlmBatcher::shift(int slot, int n_keep, int n_discard, int n_past, std::string* err) {
+    if (slot < 0 || slot >= (int)slot_used_.size() || n_keep < 0 || n_discard < 1 || n_keep + n_discard >= n_past || n_past > n_ctx_) { *err = "context shift: rows outside the context window"; return false; }
+    ShiftReq r;
+    r.slot = slot; r.n_keep = n_keep; r.n_discard = n_discard; r.n_past = n_past;
+    std::unique_lock<std::mutex> lk(mu_);
+    if (stop_) { *err = "scheduler stopped"; return false; }
+    shifts_.push_back(&r);
+    cv_.notify_all();
+    r.cv.wait(lk, [&] { return r.finished; });
+    if (!r.ok) { *err = r.error; return false; }
+    return true;
+}
+
 void TkLlmBatcher::loop() {
     std::vector<int32_t> sq, ps, tk, am;
     std::vector<const uint32_t*> masks;
@@ -159,6 +172,7 @@ void TkLlmBatcher::loop() {
     std::vector<Taken> in_pass;
     std::vector<Request*> completing;
     std::vector<AheadRow> ahead_rows;
+    std::vector<ShiftReq*> shifting;
     /* prefix cache: the copies of the pass being formed (at most one per request of the pass), the request each serves, and the slots that are
      * a source / a destination of this launch */
     std::vector<TkKvCopyDesc> copies;
@@ -180,14 +194,39 @@ void TkLlmBatcher::loop() {
         bool any_mask = false, any_samp = false, any_adj = false;
         {
             std::unique_lock<std::mutex> lk(mu_);
-            cv_.wait(lk, [&] { return stop_ || !queue_.empty() || any_planned(); });
+            cv_.wait(lk, [&] { return stop_ || !queue_.empty() || !shifts_.empty() || any_planned(); });
             t_woke = trace_path_.empty() ? 0.0 : now_ms();
             if (stop_) {
                 for (Request* r : queue_) { r->ok = false; r->error = "scheduler stopped"; r->finished = true; r->cv.notify_all(); }
                 queue_.clear();
+                for (ShiftReq* r : shifts_) { r->ok = false; r->error = "scheduler stopped"; r->finished = true; r->cv.notify_all(); }
+                shifts_.clear();
                 for (Ahead& a : ahead_)
                     if (a.waiter) { a.waiter->ok = false; a.waiter->error = "scheduler stopped"; a.waiter->finished = true; a.waiter->cv.notify_all(); a.waiter = nullptr; }
                 return;
+            }
+            /* context shifts (tk_llm_batcher.h): no pass is in flight here.  What ran ahead of the owner is retired and the record cut to the rows that
+             * stay valid BEFORE the rows move; the moves run without the lock, and this iteration forms no pass */
+            if (!shifts_.empty()) {
+                shifting.assign(shifts_.begin(), shifts_.end());
+                shifts_.clear();
+                for (ShiftReq* r : shifting) {
+                    drop_ahead(r->slot);
+                    std::vector<int32_t>& rec = rec_[(size_t)r->slot];
+                    if (rec.size() > (size_t)r->n_keep) rec.resize((size_t)r->n_keep);
+                }
+                lk.unlock();
+                for (ShiftReq* r : shifting) {
+                    r->ok = session_.kv_shift(r->slot, r->n_keep + r->n_discard, r->n_past, -r->n_discard);
+                    if (!r->ok) r->error = session_.error;
+                }
+                lk.lock();
+                for (ShiftReq* r : shifting) { /* the owner wakes under the lock and takes its request with it */
+                    if (!r->ok) rec_[(size_t)r->slot].clear();
+                    r->finished = true;
+                    r->cv.notify_all();
+                }
+                continue;
             }
             /* the owners of the requests the last pass finished WITHOUT a run-ahead row (masked steps) are about to ask for their next
              * token: give them a moment so that K runners decoding in lock step share every pass (a late one simply rides the next pass) */
@@ -195,7 +234,9 @@ void TkLlmBatcher::loop() {
                 /* the window grows with the number of owners expected back (waking K host threads takes time) and stays well under the cost
                  * of the pass it fills: 200 us + 8 us per expected request, at most 2.5 ms (a 256-row pass is ~8 ms, a 16-row pass ~2.3 ms) */
                 const int64_t us = std::min<int64_t>(2500, 200 + 8 * (int64_t)expect_);
-                cv_.wait_for(lk, std::chrono::microseconds(us), [&] { return stop_ || queue_.size() >= expect_; });
+                cv_.wait_for(lk, std::chrono::microseconds(us), [&] { return stop_ || queue_.size() >= expect_ || !shifts_.empty(); });
+                /* an expected owner shifts before it asks: serve the shift first (top of the loop); its request then joins the others' pass */
+                if (!shifts_.empty()) continue;
             }
             /* FIFO: a request contributes as many of its remaining rows as the pass still holds, then the run-ahead rows.  A grammar-masked
              * request samples under its own token mask, which the arg max kernel takes per ROW: masked and unmasked requests share passes.

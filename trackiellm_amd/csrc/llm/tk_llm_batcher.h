@@ -41,6 +41,15 @@
  *     one is in the record already; an INFLIGHT one belongs to a pass that completes — and enters the record, at its position, for its token —
  *     before the scheduler forms the next pass, which is the first moment the new prompt is matched.  The record says the truth either way: if
  *     the new prompt continues with that very token the row is kept, otherwise the match ends before it.
+ *
+ * Context shift (shift()).  A runner whose context is full may drop rows behind its first n_keep and move the rest down (k_kv_shift_rows).  The
+ * scheduler thread takes queued shifts at the top of an iteration, before it forms a pass: no pass is in flight then (the same thread runs them), so
+ * an INFLIGHT run-ahead row of the slot has completed; drop_ahead(slot) retires what is left (a PLANNED row never runs), and the slot's record is
+ * truncated to n_keep BEFORE the launch.  The moved rows were computed in a context that no longer exists — they are not "the rows a recomputation
+ * would write" — so they are never kept or copied: the record ends at n_keep, and record_row does not extend a record that does not reach the row's
+ * position, so it stays there until a prompt is fed from within [0, n_keep].  Rows [0, n_keep) are untouched and stay valid.  The iteration that
+ * runs shifts forms no pass and launches no copy, so a slot that is being shifted is neither source nor destination of a copy of that iteration;
+ * against the copies of other iterations the session stream orders it.
  */
 #ifndef TK_LLM_BATCHER_H
 #define TK_LLM_BATCHER_H
@@ -74,6 +83,10 @@ public:
     struct PrefixRows { int32_t prompt_rows = 0, kept = 0, copied = 0; };
     bool submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp = nullptr,
                 PrefixRows* prefix = nullptr, const TkLogitAdjust* adjust = nullptr);
+    /* Blocking: context shift of sequence `slot` (common/tk_kv_shift.h, llama.cpp's rule): the first n_keep rows stay, the n_discard rows after them are
+     * dropped, rows [n_keep + n_discard, n_past) move down by n_discard.  Queued like a request: the scheduler thread runs it between passes on the
+     * session stream (header comment, "Context shift").  Thread-safe; the slot's owner has no other call outstanding */
+    bool shift(int slot, int n_keep, int n_discard, int n_past, std::string* err);
     /* the prompt prefix cache, off by default; may change at any time, read when the scheduler first takes a prompt.  false: the model's rows are
      * not whole 16-byte words (head_dim % 8 != 0) */
     bool set_prefix_cache(bool on);
@@ -120,6 +133,13 @@ private:
     std::mutex mu_;
     std::condition_variable cv_;
     std::deque<Request*> queue_;
+    struct ShiftReq {
+        int slot, n_keep, n_discard, n_past;
+        bool finished = false, ok = true;
+        std::string error;
+        std::condition_variable cv;
+    };
+    std::deque<ShiftReq*> shifts_;
     bool stop_ = false;
     bool decode_first_ = false; /* TK_MI355X_BATCHER_DECODE_FIRST=1: sampled rows before prompt rows when a pass is formed (A/B; tk_llm_batcher.cpp) */
     size_t expect_ = 0; /* requests finished by the last pass: their owners are about to submit the next token */

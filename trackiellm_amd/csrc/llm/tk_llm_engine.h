@@ -131,6 +131,14 @@ public:
      * copied rows, and a source row that forward() overwrites is read first.  Descriptors are checked like kv_copy's arguments; no two share a
      * destination and no destination is another one's source (the caller's rule: the kernel copies them in no particular order). */
     bool enqueue_kv_copy(const TkKvCopyDesc* descs, int n);
+    /* context shift (common/tk_kv_shift.h): rows [p0, p1) of sequence seq become rows [p0 + delta, p1 + delta), delta < 0, in every layer: values copied,
+     * keys re-rotated to their new positions; one launch of k_kv_shift_rows on `stream`, synchronous.  Needs 0 <= p0 < p1 <= max_ctx and
+     * p0 + delta >= 0; source and destination may overlap.  Rows outside the destination range keep their bits, the stale tail [p1 + delta, p1)
+     * included.  *bad_args (optional) tells a refused argument from a device error */
+    bool kv_shift(int seq, int p0, int p1, int delta, bool* bad_args = nullptr);
+    /* stand-alone timing of that launch (tools/time_kv_shift.py): the move `iters` times after one untimed launch, device events around them; average
+     * ms of one launch, bytes = read + written by one (the two table rows aside) */
+    bool time_kv_shift(int seq, int p0, int p1, int delta, int iters, float* avg_ms, double* bytes);
     bool kv_copy_applies() const { return model && model->hp.head_dim % 8 == 0; } /* 16-byte accesses need rows of whole 16-byte words */
     /* per-launch timing of the last decode(): average ms of one step measured with HIP events */
     float last_step_ms = 0.0f;

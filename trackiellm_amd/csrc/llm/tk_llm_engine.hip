@@ -425,6 +425,11 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     /* the prefix cache's copy kernel runs between passes, outside any capture: launched once here, with nothing to copy, so that its code object
      * is loaded before the first pass is recorded into a graph */
     if (kv_copy_applies() && !enqueue_kv_copy(nullptr, 0)) return false;
+    /* so does the context shift's kernel: once with an empty move */
+    if (kv_copy_applies() && !tk_launch_kv_shift_rows(TkKvShiftDesc{0, 0, 0, 0}, kcache, vcache, rope_cos, rope_sin, h.n_layer, h.n_kv_head, h.head_dim, max_seq, max_ctx, stream)) {
+        error = "kv_shift: launch failed";
+        return false;
+    }
     HIPQ(hipDeviceSynchronize());
     return true;
 }
@@ -510,6 +515,42 @@ bool TkLlmSession::kv_copy(int src_seq, int dst_seq, int pos0, int n_pos) {
     const TkKvCopyDesc d{src_seq, dst_seq, pos0, n_pos};
     if (!enqueue_kv_copy(&d, 1)) return false;
     HIPQ(hipStreamSynchronize(stream));
+    return true;
+}
+
+bool TkLlmSession::kv_shift(int seq, int p0, int p1, int delta, bool* bad_args) {
+    const TkLlmHParams& h = model->hp;
+    const TkKvShiftDesc m{seq, p0, p1, delta};
+    if (bad_args) *bad_args = true;
+    if (!kv_copy_applies()) { error = "kv_shift: head_dim must be a multiple of 8"; return false; }
+    if (!tk_kv_shift_ok(m, max_seq, max_ctx)) { error = "kv_shift: needs a sequence of the session, 0 <= p0 < p1 <= max_ctx, delta < 0 and p0 + delta >= 0"; return false; }
+    if (bad_args) *bad_args = false;
+    HIPQ(hipSetDevice(model->device));
+    if (!tk_launch_kv_shift_rows(m, kcache, vcache, rope_cos, rope_sin, h.n_layer, h.n_kv_head, h.head_dim, max_seq, max_ctx, stream)) { error = "kv_shift: launch failed"; return false; }
+    HIPQ(hipStreamSynchronize(stream));
+    return true;
+}
+
+bool TkLlmSession::time_kv_shift(int seq, int p0, int p1, int delta, int iters, float* avg_ms, double* bytes) {
+    const TkLlmHParams& h = model->hp;
+    const TkKvShiftDesc m{seq, p0, p1, delta};
+    if (!kv_copy_applies() || !tk_kv_shift_ok(m, max_seq, max_ctx) || iters < 1) { error = "time_kv_shift: a move kv_shift refuses, or no iterations"; return false; }
+    HIPQ(hipSetDevice(model->device));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPQ(hipEventCreate(&e0));
+    HIPQ(hipEventCreate(&e1));
+    bool ok = true;
+    for (int i = 0; i <= iters && ok; ++i) { /* launch 0 is the warm-up */
+        if (i == 1) ok = hipEventRecord(e0, stream) == hipSuccess;
+        ok = ok && tk_launch_kv_shift_rows(m, kcache, vcache, rope_cos, rope_sin, h.n_layer, h.n_kv_head, h.head_dim, max_seq, max_ctx, stream);
+    }
+    float ms = 0.0f;
+    ok = ok && hipEventRecord(e1, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (!ok) { error = "time_kv_shift: device error"; return false; }
+    *avg_ms = ms / (float)iters;
+    *bytes = 2.0 * 2.0 * (double)h.n_layer * h.n_kv_head * (double)(p1 - p0) * h.head_dim * 2.0; /* read + written, K and V, f16 */
     return true;
 }
 

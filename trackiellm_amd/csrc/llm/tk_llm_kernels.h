@@ -141,6 +141,13 @@ void tk_launch_attention_long(const float* partial, int ks, int n_total, const f
 struct TkKvCopyDesc { int32_t src_seq, dst_seq, p0, n; };
 bool tk_launch_kv_copy_rows(const TkKvCopyDesc* desc, int ndesc, int max_n, uint16_t* kcache, uint16_t* vcache, int n_layer, int n_kv_head, int head_dim, int max_seq,
                             int max_ctx, hipStream_t s);
+#include "../common/tk_kv_shift.h"
+/* context shift (common/tk_kv_shift.h): rows [p0, p1) of sequence m.seq moved to [p0 + delta, p1 + delta), delta < 0, in every layer, KV head and both
+ * caches in one launch; V copied, K re-rotated by delta positions with rows -delta of rope_cos / rope_sin ([max_ctx][head_dim / 2]).  Source and
+ * destination may overlap.  A move with p1 <= p0 launches one idle workgroup.  false: a move or geometry the kernel does not take (nothing is
+ * launched) or a failed launch */
+bool tk_launch_kv_shift_rows(const TkKvShiftDesc& m, uint16_t* kcache, uint16_t* vcache, const float* rope_cos, const float* rope_sin, int n_layer, int n_kv_head,
+                             int head_dim, int max_seq, int max_ctx, hipStream_t s);
 /* the long-context form's last launch alone: the four classes of every head joined, divided, quantised (head_dim 64 or 128, n_head a multiple of 256 / head_dim) */
 void tk_launch_att_pv_join(const float* pv_part, const float* l_part, int nrows, int n_head, int head_dim, TkActQ8 out, hipStream_t s);
 size_t tk_gemv_lds_bytes(int K, int ks, int mtiles);

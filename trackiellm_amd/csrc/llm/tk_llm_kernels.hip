@@ -4240,3 +4240,113 @@ const char* tk_llm_prepare_device(int device) {
     done[device] = true;
     return nullptr;
 }
+
+/* ------------------------------------------------------------------------------------------
+ * context shift
+ * ------------------------------------------------------------------------------------------ */
+/* Context shift (common/tk_kv_shift.h): cache rows [p0, p1) of one sequence become rows [p0 - d, p1 - d), d = -delta > 0, in every layer, KV head
+ * and both caches, in one launch — V as a bit copy, K re-rotated by -d positions on the way.  One workgroup owns one (layer, KV head, K | V) run,
+ * because source and destination overlap whenever p1 - p0 > d and nothing orders two workgroups.  It walks the run in ascending blocks of
+ * TK_KV_SHIFT_BLOCK_ROWS rows: every lane loads its 16-byte words of the block into registers, the workgroup meets at a barrier, every lane stores.
+ *   Why the walk is safe.  With B = TK_KV_SHIFT_BLOCK_ROWS = 128, block i reads rows [p0 + B i, p0 + B i + B) and writes rows [p0 + B i - d,
+ *   p0 + B i + B - d).  Its highest store is row p0 + B i + B - 1 - d < p0 + B (i + 1), the lowest row block i + 1 (or any later one) still has to
+ *   read, because d >= 1: the destination lies BELOW the source, so a block's stores reach only rows that this block, or an earlier one, has
+ *   already read.  The rows block i itself reads are all in registers when the barrier opens, whichever lane stores on them.  Between block i's
+ *   stores and block i + 1's loads no barrier is needed: they never touch the same row.  The argument holds for any B >= 1.
+ * A workgroup is 1024 lanes and a block 128 x head_dim / 8 words, NU = ceil(head_dim / 64) <= 4 per lane (template parameter), consecutive lanes
+ * on consecutive words.  At every head_dim the model loader accepts a block is exactly NU x 1024 words, so a full block loads and stores WITHOUT a
+ * lane predicate: the NU 16-byte loads of a lane are issued back to back and are in flight together (one at head_dim 64, two at 128, three at
+ * 192, four at 256, k_kv_copy_rows' count), and its stores follow behind counted waits, not one round trip each.  Only the run's last, partial
+ * block — or a head_dim that is no multiple of 64, which only the probe can ask for — takes the guarded form, as k_kv_copy_rows' tail does.
+ * Why 128 rows and 1024 lanes: a run is walked by ONE workgroup, block after block, so what a CU has in flight is what its workgroups' blocks
+ * hold.  With 32-row blocks and 256 lanes (8 KiB per block at head_dim 128) the 7B move of profiles/context_shift.txt ran at a quarter of the
+ * roofline whether or not the loads were predicated; 128-row blocks (32 KiB) halve its time.
+ * A lane's column within the row — and with it its cosines and sines of table row d — is the same in every block (a block is a whole number of
+ * rows), so they are loaded once, before the walk. */
+#define TK_KV_SHIFT_THREADS 1024
+#define TK_KV_SHIFT_MAX_UNROLL 4
+template <int NU>
+__global__ __launch_bounds__(TK_KV_SHIFT_THREADS) void k_kv_shift_rows(TkKvShiftDesc m, uint16_t* kcache, uint16_t* vcache, const float* __restrict__ rope_cos,
+                                                                       const float* __restrict__ rope_sin, int n_layer, int n_kv_head, int max_seq, int max_ctx,
+                                                                       int head_dim) {
+    /* the host checks the move before it is sent; a bad one moves nothing rather than touching memory outside the cache */
+    if (!tk_kv_shift_ok(m, max_seq, max_ctx)) return;
+    const int wpr = head_dim / 8; /* 16-byte words per row */
+    if (wpr < 1 || wpr * 8 != head_dim || TK_KV_SHIFT_BLOCK_ROWS * wpr > TK_KV_SHIFT_THREADS * NU) return;
+    int run = (int)blockIdx.x;
+    const int kvh = run % n_kv_head; run /= n_kv_head;
+    const int layer = run % n_layer; run /= n_layer;
+    if (run > 1) return;
+    const bool is_k = run == 0;
+    const int d = -m.delta, half = head_dim / 2;
+    uint16_t* base = (is_k ? kcache : vcache) + (((size_t)layer * max_seq + m.seq) * n_kv_head + kvh) * max_ctx * head_dim;
+    const v4i* sp = (const v4i*)(base + (size_t)m.p0 * head_dim);
+    v4i* dp = (v4i*)(base + (size_t)(m.p0 - d) * head_dim);
+    const int block = TK_KV_SHIFT_BLOCK_ROWS * wpr, words = (m.p1 - m.p0) * wpr;
+    float c4[NU][4], s4[NU][4];
+    if (is_k) {
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int col = ((int)threadIdx.x + u * TK_KV_SHIFT_THREADS) % wpr; /* this lane's word of the row */
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                c4[u][j] = rope_cos[(size_t)d * half + 4 * col + j];
+                s4[u][j] = rope_sin[(size_t)d * half + 4 * col + j];
+            }
+        }
+    }
+    auto rotate = [&](v4i (&t)[NU]) {
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            uint32_t q[4] = {(uint32_t)t[u].x, (uint32_t)t[u].y, (uint32_t)t[u].z, (uint32_t)t[u].w};
+            tk_kv_shift_word(q, c4[u], s4[u]);
+            t[u].x = (int)q[0]; t[u].y = (int)q[1]; t[u].z = (int)q[2]; t[u].w = (int)q[3];
+        }
+    };
+    int w0 = 0;
+    /* full blocks of exactly NU x 1024 words: no lane predicate on the loads or on the stores */
+    if (block == NU * TK_KV_SHIFT_THREADS) {
+        for (; w0 + block <= words; w0 += block) {
+            const v4i* s0 = sp + w0 + (int)threadIdx.x;
+            v4i* d0 = dp + w0 + (int)threadIdx.x;
+            v4i t[NU];
+#pragma unroll
+            for (int u = 0; u < NU; ++u) t[u] = s0[u * TK_KV_SHIFT_THREADS];
+            if (is_k) rotate(t);
+            __syncthreads(); /* every row of the block is in registers: stores may now land on them */
+#pragma unroll
+            for (int u = 0; u < NU; ++u) d0[u * TK_KV_SHIFT_THREADS] = t[u];
+        }
+    }
+    /* the run's last, partial block (and every block of a head_dim that is no multiple of 64) */
+    for (; w0 < words; w0 += block) {
+        const int nw = min(block, words - w0);
+        const v4i* s0 = sp + w0 + (int)threadIdx.x;
+        v4i* d0 = dp + w0 + (int)threadIdx.x;
+        v4i t[NU];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) t[u] = (int)threadIdx.x + u * TK_KV_SHIFT_THREADS < nw ? s0[u * TK_KV_SHIFT_THREADS] : v4i{0, 0, 0, 0};
+        if (is_k) rotate(t); /* a word past the block's end is zeros here and is not stored */
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+            if ((int)threadIdx.x + u * TK_KV_SHIFT_THREADS < nw) d0[u * TK_KV_SHIFT_THREADS] = t[u];
+    }
+}
+
+bool tk_launch_kv_shift_rows(const TkKvShiftDesc& m, uint16_t* kcache, uint16_t* vcache, const float* rope_cos, const float* rope_sin, int n_layer, int n_kv_head,
+                             int head_dim, int max_seq, int max_ctx, hipStream_t s) {
+    if (head_dim < 8 || head_dim % 8 != 0 || TK_KV_SHIFT_BLOCK_ROWS * (head_dim / 8) > TK_KV_SHIFT_THREADS * TK_KV_SHIFT_MAX_UNROLL || n_layer < 1 || n_kv_head < 1 ||
+        max_seq < 1 || max_ctx < 1)
+        return false;
+    /* an empty move (p1 <= p0): one workgroup that returns at once (sessions launch it at creation so that the code object is resident before any
+     * stream capture begins); any other move is checked here as the kernel checks it */
+    const bool empty = m.p1 <= m.p0;
+    if (!empty && !tk_kv_shift_ok(m, max_seq, max_ctx)) return false;
+    const long runs = empty ? 1 : 2L * n_layer * n_kv_head;
+    /* words a lane holds of one block: the kernel's unroll count */
+    const int nu = (TK_KV_SHIFT_BLOCK_ROWS * (head_dim / 8) + TK_KV_SHIFT_THREADS - 1) / TK_KV_SHIFT_THREADS;
+    auto* fn = nu == 1 ? k_kv_shift_rows<1> : nu == 2 ? k_kv_shift_rows<2> : nu == 3 ? k_kv_shift_rows<3> : k_kv_shift_rows<4>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)runs), dim3(TK_KV_SHIFT_THREADS), 0, s, m, kcache, vcache, rope_cos, rope_sin, n_layer, n_kv_head, max_seq, max_ctx, head_dim);
+    return hipGetLastError() == hipSuccess;
+}

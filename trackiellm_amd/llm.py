@@ -377,6 +377,17 @@ class LlmSession:
         """rows [pos0, pos0 + n_pos) of src_seq onto the same rows of dst_seq, every layer, on the device (tk_mi355x_llm_session_kv_copy)"""
         check(lib().tk_mi355x_llm_session_kv_copy(self.h, int(src_seq), int(dst_seq), int(pos0), int(n_pos)))
 
+    def kv_shift(self, seq, p0, p1, delta):
+        """rows [p0, p1) of seq become rows [p0 + delta, p1 + delta) (delta < 0) in every layer: values copied, keys re-rotated to the new positions
+        (tk_mi355x_llm_session_kv_shift)"""
+        check(lib().tk_mi355x_llm_session_kv_shift(self.h, int(seq), int(p0), int(p1), int(delta)))
+
+    def time_kv_shift(self, seq, p0, p1, delta, iters):
+        """(ms of one launch, bytes read + written) of that move, `iters` launches after a warm-up"""
+        ms, nbytes = C.c_float(0), C.c_double(0)
+        check(lib().tk_mi355x_llm_time_kv_shift(self.h, int(seq), int(p0), int(p1), int(delta), int(iters), C.byref(ms), C.byref(nbytes)))
+        return ms.value, nbytes.value
+
     def prefill(self, tokens):
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
         nseq, n_prompt = tokens.shape
@@ -418,6 +429,31 @@ class LlmSession:
             self.close()
         except Exception:
             pass
+
+
+def kv_shift_probe(kcache, vcache, rope_cos, rope_sin, seq, p0, p1, delta, device=0):
+    """ONE launch of k_kv_shift_rows (tk_mi355x_kv_shift_probe) on COPIES of kcache / vcache (uint16 f16 bits, [n_layer][max_seq][n_kv_head][max_ctx]
+    [head_dim]), which are returned; rope_cos / rope_sin float32 [max_ctx][head_dim / 2]; device < 0: the same per-row function in a host loop.  A
+    refusal raises with the copies untouched: pass arrays through kv_shift_probe_into to see that"""
+    k = np.array(kcache, dtype=np.uint16, order="C", copy=True)
+    v = np.array(vcache, dtype=np.uint16, order="C", copy=True)
+    kv_shift_probe_into(k, v, rope_cos, rope_sin, seq, p0, p1, delta, device=device)
+    return k, v
+
+
+def kv_shift_probe_into(kcache, vcache, rope_cos, rope_sin, seq, p0, p1, delta, device=0, head_dim=None):
+    """kv_shift_probe in place on C-contiguous uint16 arrays of 5 dimensions; None for an array passes NULL; head_dim overrides the arrays' last
+    dimension (refusal tests)"""
+    shape = next((a.shape for a in (kcache, vcache) if a is not None), (1, 1, 1, 1, 8))
+    for a in (kcache, vcache):
+        if a is not None and (a.dtype != np.uint16 or not a.flags["C_CONTIGUOUS"] or a.ndim != 5 or a.shape != shape):
+            raise ValueError("kv_shift_probe_into: caches must be C-contiguous uint16 arrays of one 5-dimensional shape")
+    n_layer, max_seq, n_kv_head, max_ctx, hd = shape
+    for a in (rope_cos, rope_sin):
+        if a is not None and (a.dtype != np.float32 or not a.flags["C_CONTIGUOUS"] or a.size < max_ctx * (hd // 2)):
+            raise ValueError("kv_shift_probe_into: tables must be C-contiguous float32 arrays of [max_ctx][head_dim / 2]")
+    check(lib().tk_mi355x_kv_shift_probe(int(device), n_layer, max_seq, n_kv_head, max_ctx, hd if head_dim is None else int(head_dim), _p(kcache), _p(vcache),
+                                         _p(rope_cos), _p(rope_sin), int(seq), int(p0), int(p1), int(delta)))
 
 
 class PipeHandle(C.Structure):
@@ -605,6 +641,17 @@ class LlmRunner:
 
     def add_tool_response(self, tool_name, tool_output):
         check(lib().tk_llm_runner_add_tool_response(self.h, tool_name.encode(), tool_output.encode()))
+
+    def set_context_shift(self, on, n_keep=0):
+        """llama.cpp's context shift instead of stopping at the end of the context (off by default): keep the first n_keep rows (-1 = the last prompt's
+        token count), drop half of the rest, move the others down (tk_mi355x_llm_runner_set_context_shift)"""
+        check(lib().tk_mi355x_llm_runner_set_context_shift(self.h, 1 if on else 0, int(n_keep)))
+
+    def context_shifts(self):
+        """(shifts, rows dropped by them) since the last prepare()"""
+        n, d = C.c_int32(0), C.c_int64(0)
+        check(lib().tk_mi355x_llm_runner_context_shifts(self.h, C.byref(n), C.byref(d)))
+        return n.value, d.value
 
     def last_prompt_rows(self):
         """(rows, of them kept in place, of them copied from another runner's slot) of the last prepare()"""
