@@ -313,6 +313,38 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_kv_shift_probe(int device, int32_t
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_context_shift(struct tk_llm_runner_s* runner, int on, int32_t n_keep);
 /* shifts made, and rows dropped by them in total, since the last prepare_generation */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_context_shifts(struct tk_llm_runner_s* runner, int32_t* shifts, int64_t* discarded);
+/* ---- lookup decoding (csrc/llm/tk_lookup.h; opt-in; include/tk/ABI_NOTES.md): llama.cpp's lookup / n-gram speculation and the hosted APIs'
+ * "predicted outputs" for a GREEDY runner.  The runner drafts the ids that follow its pending one from a prediction its host gave it, then from its
+ * own context, feeds the pending id and the drafts as consecutive positions of one pass and keeps the drafts the model's own arg max confirms: one
+ * stream of the weights yields several tokens, and the tokens are exactly the ones the runner emits with lookup off. ---- */
+/* the draft rule alone (no GPU).  ctx [n_ctx]: the prompt and every id sampled so far, the pending one last; pred [n_pred]: the prediction (may be
+ * empty).  For n = ngram_max down to ngram_min (n <= n_ctx), s = the last n ids of ctx: first the prediction — the smallest j with
+ * pred[j .. j + n) == s and j + n < n_pred, drafts pred[j + n ..) — then the context — the largest j with j + n <= n_ctx - 1 and ctx[j .. j + n) == s,
+ * drafts ctx[j + n ..) — at most n_draft ids, cut at the end of the source; the first hit wins.  Returns the draft count (out: room for n_draft),
+ * 0 when nothing matches; -1: n_draft outside [0, 15], not 1 <= ngram_min <= ngram_max <= 8, a negative count or a missing array */
+TK_API int tk_mi355x_lookup_draft(const int32_t* ctx, int n_ctx, const int32_t* pred, int n_pred, int ngram_min, int ngram_max, int n_draft, int32_t* out);
+/* the accept rule alone (no GPU).  toks [n]: what a verify pass fed (toks[0] the pending id, the drafts behind it); picks [n]: the arg max of every
+ * row.  m = the number of leading drafts the picks confirm (picks[i] == toks[i + 1] for all i < m), cut so that picks[m] is the first pick equal to
+ * eos.  out_ids (room for n) = picks[0 .. m]; returns m + 1; -1: n < 1 or a missing array */
+TK_API int tk_mi355x_lookup_accept(const int32_t* toks, const int32_t* picks, int n, int32_t eos, int32_t* out_ids);
+/* the verify pass on a session: nrows <= tk_mi355x_llm_max_rows() greedy, unmasked, unadjusted rows; the rows of each sequence stand at consecutive
+ * ascending positions and are contiguous in the pass; the head runs on ALL rows: picks [nrows] = the arg max of every row, logits [nrows][vocab]
+ * optional.  form: the attention of the pass — 0 k_attention per row, 2 k_attention_prefill's tiles, 4 the run form of the long-context attention
+ * (k_qkv_rope_append, then k_att_scores_long's run variant, k_att_pv_chain, k_att_pv_join; at most 8 rows, head_dim 64 or 128, a session whose
+ * max_ctx exceeds 512), -1 the session's choice (tk_mi355x_attention_plan_verify).  The three forms are bit-identical.  Rows that break the rule
+ * above or a form that does not apply: TK_ERROR_INVALID_ARGUMENT, nothing enqueued */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_forward_verify(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos,
+                                                                 const int32_t* tok, int form, float* logits, int32_t* picks);
+/* n_draft = 0 (off, the default) .. 15 drafts per pass; 1 <= ngram_min <= ngram_max <= 8.  Anything else: TK_ERROR_INVALID_ARGUMENT, the previous
+ * setting kept.  Lookup does nothing — the runner submits exactly what it does with lookup off — while the runner has a temperature, a grammar mask,
+ * penalties or a logit bias.  Takes effect from the next pass */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_lookup(struct tk_llm_runner_s* runner, int32_t n_draft, int32_t ngram_min, int32_t ngram_max);
+/* the host's prediction of the reply (copied): at most 4096 ids, each inside the vocabulary; n = 0 clears it.  It survives prepare_generation.
+ * Anything else: TK_ERROR_INVALID_ARGUMENT, the previous prediction kept */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_prediction(struct tk_llm_runner_s* runner, const int32_t* ids, int32_t n);
+/* since the last prepare_generation: passes that carried at least one draft, drafts fed, drafts accepted */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_lookup_stats(struct tk_llm_runner_s* runner, uint64_t* verify_passes, uint64_t* drafted,
+                                                                      uint64_t* accepted);
 /* equal-length prompts for sequences 0..nseq-1; first_tokens[nseq] optional */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_prefill(tk_mi355x_llm_session_t* s, int nseq, int n_prompt, const int32_t* tokens,
                                                           int32_t* first_tokens);
@@ -383,6 +415,11 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_attention_plan(int device, int nro
  * are bit-identical. */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_attention_plan_at(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, int fused,
                                                                 int top_position, int32_t out[4]);
+/* the same for a verify pass (tk_mi355x_llm_forward_verify, form -1) of nrows rows whose highest position is top_position: kernel 4 = the run form of
+ * the long-context attention where it is chosen (profiles/lookup_decoding.txt), else kernel 2 from position 128, else kernel 0; the other three
+ * numbers as tk_mi355x_attention_plan(fused = 0) gives them */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_attention_plan_verify(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx,
+                                                                    int top_position, int32_t out[4]);
 
 /* ---- tool-call grammar (GBNF) — the sampling constraint of tk_llm_runner_prepare_generation(..., use_tool_grammar = true)
  * (reference: src/ai_models/grammars/tool_call.gbnf via llama.cpp's grammar sampler, tk_runner_lifecycle.c:59,

@@ -27,6 +27,7 @@
 #include "../llm/tk_grammar.h"
 #include "../llm/tk_llm_batcher.h"
 #include "../llm/tk_llm_engine.h"
+#include "../llm/tk_lookup.h"
 #include "../llm/tk_lora.h"
 #include "../llm/tk_prefix_match.h"
 #include "../llm/tk_llm_pipe.h"
@@ -571,6 +572,31 @@ tk_error_code_t tk_mi355x_attention_plan_at(int device, int nrows, int n_head, i
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_attention_plan_verify(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, int top_position, int32_t out[4]) {
+    const tk_error_code_t rc = tk_mi355x_attention_plan_at(device, nrows, n_head, n_kv_head, head_dim, max_ctx, 0, top_position, out);
+    if (rc != TK_SUCCESS) return rc;
+    /* TkLlmSession::verify_form on top of a multi-position pass's plan */
+    if (max_ctx > TK_LONG_ATT_MIN_POS && tk_attention_long_applies(nrows, n_head, n_kv_head, head_dim) && top_position >= tk_verify_run_min_pos(nrows)) {
+        out[0] = 4; out[1] = n_head / n_kv_head; out[2] = 64; out[3] = 1;
+    }
+    return TK_SUCCESS;
+}
+
+int tk_mi355x_lookup_draft(const int32_t* ctx, int n_ctx, const int32_t* pred, int n_pred, int ngram_min, int ngram_max, int n_draft, int32_t* out) {
+    return tk_lookup_draft(ctx, n_ctx, pred, n_pred, ngram_min, ngram_max, n_draft, out);
+}
+
+int tk_mi355x_lookup_accept(const int32_t* toks, const int32_t* picks, int n, int32_t eos, int32_t* out_ids) { return tk_lookup_accept(toks, picks, n, eos, out_ids); }
+
+tk_error_code_t tk_mi355x_llm_forward_verify(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, int form,
+                                             float* logits, int32_t* picks) {
+    if (!s || !seq || !pos || !tok) return TK_ERROR_INVALID_ARGUMENT;
+    bool bad_args = false;
+    if (!s->session.forward_verify(nrows, seq, pos, tok, form, logits, picks, &bad_args))
+        return fail(bad_args ? TK_ERROR_INVALID_ARGUMENT : TK_ERROR_INFERENCE_FAILED, s->session.error);
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_time_attention(tk_mi355x_llm_session_t* s, int nrows, int ctx, int iters, float* avg_ms, double* kv_bytes) {
     if (!s || !avg_ms || !kv_bytes) return TK_ERROR_INVALID_ARGUMENT;
     if (!s->session.time_attention(nrows, ctx, iters, avg_ms, kv_bytes)) return fail(TK_ERROR_GPU_ROCM_ERROR, s->session.error);
@@ -875,6 +901,24 @@ struct tk_llm_runner_s {
     int32_t prompt_tokens = 0;   /* token count of the last prepare_generation */
     int32_t n_shifts = 0;        /* since the last prepare_generation */
     int64_t n_discarded = 0;
+    /* lookup decoding (tk_mi355x_llm_runner_set_lookup, csrc/llm/tk_lookup.h), off by default.  ctx_ids: the ids of the context — one per cache row
+     * below n_past, then the ids sampled but not handed out yet (`pending`, then `queued`); a context shift drops the ids whose rows it drops.
+     * queued: the ids a verify pass accepted behind `pending`, handed out one per generate_next_token; while it is not empty `pending` and all of
+     * them but the last have been fed already (n_past counts their rows), and no pass is submitted */
+    int32_t lookup_draft = 0, lookup_min = 1, lookup_max = 1;
+    std::vector<int32_t> prediction;
+    std::vector<int32_t> ctx_ids;
+    std::vector<int32_t> queued;
+    uint64_t lookup_passes = 0, lookup_drafted = 0, lookup_accepted = 0; /* since the last prepare_generation */
+    /* lookup does nothing while the runner samples stochastically, under a grammar mask, or with penalties or a bias: it then submits what it always did */
+    bool lookup_active() const { return lookup_draft > 0 && !(samp.temp > 0.0f) && !grammar_on && pen_last_n == 0 && bias_ids.empty(); }
+    /* the owner abandons the ids it was handed but has not given out (a tool response, a reset): back to the state of a runner that holds `pending`
+     * alone — the rows fed ahead are stale rows beyond n_past, overwritten before anything attends to them */
+    void drop_queued() {
+        n_past -= (int)queued.size();
+        queued.clear();
+        if ((int)ctx_ids.size() > n_past) ctx_ids.resize((size_t)n_past);
+    }
     bool is_processing = false;
     std::string piece;
     std::string system_prompt;
@@ -963,6 +1007,31 @@ int32_t tk_mi355x_llm_runner_recent_tokens(tk_llm_runner_t* runner, int32_t* out
     return (int32_t)runner->accepted.size();
 }
 
+tk_error_code_t tk_mi355x_llm_runner_set_lookup(tk_llm_runner_t* runner, int32_t n_draft, int32_t ngram_min, int32_t ngram_max) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    if (n_draft < 0 || n_draft > TK_LOOKUP_MAX_DRAFT) return fail(TK_ERROR_INVALID_ARGUMENT, "lookup: n_draft must be in [0, 15]");
+    if (ngram_min < 1 || ngram_min > ngram_max || ngram_max > TK_LOOKUP_MAX_NGRAM) return fail(TK_ERROR_INVALID_ARGUMENT, "lookup: 1 <= ngram_min <= ngram_max <= 8");
+    runner->lookup_draft = n_draft; runner->lookup_min = ngram_min; runner->lookup_max = ngram_max;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_runner_set_prediction(tk_llm_runner_t* runner, const int32_t* ids, int32_t n) {
+    if (!runner || n < 0 || (n > 0 && !ids)) return TK_ERROR_INVALID_ARGUMENT;
+    if (n > TK_LOOKUP_MAX_PRED) return fail(TK_ERROR_INVALID_ARGUMENT, "prediction: at most 4096 ids");
+    for (int32_t i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= runner->model->model.hp.vocab) return fail(TK_ERROR_INVALID_ARGUMENT, "prediction: id " + std::to_string(i) + " is outside the vocabulary");
+    runner->prediction.assign(ids, ids + n);
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_runner_lookup_stats(tk_llm_runner_t* runner, uint64_t* verify_passes, uint64_t* drafted, uint64_t* accepted) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    if (verify_passes) *verify_passes = runner->lookup_passes;
+    if (drafted) *drafted = runner->lookup_drafted;
+    if (accepted) *accepted = runner->lookup_accepted;
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_llm_runner_create(tk_llm_runner_t** out_runner, void* model_handle, const tk_llm_config_t* config) {
     if (!out_runner || !model_handle || !config) return TK_ERROR_INVALID_ARGUMENT;
     std::unique_ptr<tk_llm_runner_s> r(new tk_llm_runner_s());
@@ -1040,6 +1109,8 @@ static bool context_shift(tk_llm_runner_s* r, int need, bool* failed) {
         *failed = true;
         return false;
     }
+    /* the context's ids lose what the cache lost */
+    if ((int)r->ctx_ids.size() >= n_keep + n_discard) r->ctx_ids.erase(r->ctx_ids.begin() + n_keep, r->ctx_ids.begin() + n_keep + n_discard);
     r->n_past -= n_discard;
     r->n_shifts++;
     r->n_discarded += n_discard;
@@ -1049,6 +1120,7 @@ static bool context_shift(tk_llm_runner_s* r, int need, bool* failed) {
 /* feed `toks` at positions n_past.. ; the last one is sampled.  The rows join whatever passes the model's scheduler is forming. */
 static tk_error_code_t feed(tk_llm_runner_s* r, const std::vector<int32_t>& toks, bool whole_context = false) {
     if (toks.empty()) return TK_SUCCESS;
+    r->drop_queued(); /* ids handed to the runner but not to its caller (lookup decoding): the tokens go where they go with lookup off */
     if (r->n_past + (int)toks.size() >= r->n_ctx) {
         bool failed = false;
         /* a prompt (whole_context) that is longer than the context is refused whatever the policy: there is nothing behind it to drop */
@@ -1058,11 +1130,14 @@ static tk_error_code_t feed(tk_llm_runner_s* r, const std::vector<int32_t>& toks
     int32_t am = -1;
     std::string err;
     /* whole_context (prepare_generation): the tokens start at position 0, so the scheduler may keep or copy rows the cache already holds for them */
-    if (!r->batcher->submit(r->slot, r->n_past, toks.data(), (int)toks.size(), r->next_mask(), &am, &err, r->next_samp(), whole_context ? &r->last_prompt : nullptr, r->next_adjust()))
+    if (!r->batcher->submit(r->slot, r->n_past, toks.data(), (int)toks.size(), r->next_mask(), &am, &err, r->next_samp(), whole_context ? &r->last_prompt : nullptr, r->next_adjust(),
+                            r->lookup_active()))
         return fail(TK_ERROR_INFERENCE_FAILED, err);
     if (r->samp.temp > 0.0f) r->samp.counter++;
     r->n_past += (int)toks.size();
     r->pending = am;
+    r->ctx_ids.insert(r->ctx_ids.end(), toks.begin(), toks.end());
+    r->ctx_ids.push_back(am);
     return TK_SUCCESS;
 }
 
@@ -1081,6 +1156,9 @@ tk_error_code_t tk_llm_runner_prepare_generation(tk_llm_runner_t* runner, const 
     runner->prompt_tokens = (int32_t)toks.size();
     runner->n_shifts = 0;
     runner->n_discarded = 0;
+    runner->queued.clear();
+    runner->ctx_ids.clear();
+    runner->lookup_passes = runner->lookup_drafted = runner->lookup_accepted = 0;
     tk_error_code_t rc = feed(runner, toks, true);
     if (rc != TK_SUCCESS) return rc;
     runner->is_processing = true;
@@ -1092,6 +1170,12 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
     const int32_t id = runner->pending;
     if (id >= 0) runner->accept(id); /* llama_sampling_accept (tk_runner_streaming.c:61) comes before the EOS test: that id is in the window too */
     if (id < 0 || id == runner->model->tok.eos) { runner->is_processing = false; return NULL; }
+    if (!runner->queued.empty()) { /* lookup decoding: this id's row is in the cache already, and the id behind it has been sampled */
+        runner->pending = runner->queued.front();
+        runner->queued.erase(runner->queued.begin());
+        runner->piece = runner->model->tok.piece(id);
+        return runner->piece.c_str();
+    }
     if (runner->grammar_on) {
         /* llama_sampling_accept: advance the grammar by the sampled token; then the reference's "grammar rule completed" test
          * (tk_runner_streaming.c:69-75): the token is NOT decoded, generation pauses, the sentinel address is returned */
@@ -1114,7 +1198,34 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
     }
     int32_t t = id, am = -1;
     std::string err;
-    if (!runner->batcher->submit(runner->slot, runner->n_past, &t, 1, runner->next_mask(), &am, &err, runner->next_samp(), nullptr, runner->next_adjust())) {
+    const bool lookup = runner->lookup_active();
+    if (lookup) {
+        /* the pending id and what the draft rule guesses behind it in ONE pass; the drafts are clipped so that every fed position q has q + 1 < n_ctx:
+         * the generation ends, or shifts, at exactly the token it does with lookup off */
+        int32_t fed[1 + TK_LOOKUP_MAX_DRAFT], ids[1 + TK_LOOKUP_MAX_DRAFT];
+        fed[0] = id;
+        int nd = tk_lookup_draft(runner->ctx_ids.data(), (int)runner->ctx_ids.size(), runner->prediction.data(), (int)runner->prediction.size(), runner->lookup_min,
+                                 runner->lookup_max, runner->lookup_draft, fed + 1);
+        nd = std::max(0, std::min(nd, runner->n_ctx - runner->n_past - 2));
+        if (nd > 0) {
+            int n_ids = 0;
+            if (!runner->batcher->submit_verify(runner->slot, runner->n_past, fed, 1 + nd, ids, &n_ids, &err) || n_ids < 1) {
+                tk_error_set_detail("%s", err.c_str());
+                runner->is_processing = false;
+                return NULL;
+            }
+            runner->lookup_passes++;
+            runner->lookup_drafted += (uint64_t)nd;
+            runner->lookup_accepted += (uint64_t)(n_ids - 1);
+            runner->n_past += n_ids; /* rows 0 .. m of the pass are valid cache rows */
+            runner->pending = ids[0];
+            runner->queued.assign(ids + 1, ids + n_ids);
+            runner->ctx_ids.insert(runner->ctx_ids.end(), ids, ids + n_ids);
+            runner->piece = runner->model->tok.piece(id);
+            return runner->piece.c_str();
+        }
+    }
+    if (!runner->batcher->submit(runner->slot, runner->n_past, &t, 1, runner->next_mask(), &am, &err, runner->next_samp(), nullptr, runner->next_adjust(), lookup)) {
         tk_error_set_detail("%s", err.c_str());
         runner->is_processing = false;
         return NULL;
@@ -1122,6 +1233,7 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
     if (runner->samp.temp > 0.0f) runner->samp.counter++;
     runner->n_past++;
     runner->pending = am;
+    runner->ctx_ids.push_back(am);
     runner->piece = runner->model->tok.piece(id);
     return runner->piece.c_str();
 }
@@ -1140,6 +1252,8 @@ tk_error_code_t tk_llm_runner_reset_context(tk_llm_runner_t* runner) {
     if (!runner) return TK_ERROR_INVALID_ARGUMENT;
     runner->n_past = 0;
     runner->pending = -1;
+    runner->queued.clear();
+    runner->ctx_ids.clear();
     runner->is_processing = false;
     return TK_SUCCESS;
 }

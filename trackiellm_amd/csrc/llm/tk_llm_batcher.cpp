@@ -1,4 +1,5 @@
 #include "tk_llm_batcher.h"
+#include "tk_lookup.h"
 #include "tk_prefix_match.h"
 
 #include <algorithm>
@@ -102,7 +103,7 @@ void TkLlmBatcher::drop_ahead(int slot) {
 }
 
 bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp,
-                          PrefixRows* prefix, const TkLogitAdjust* adjust) {
+                          PrefixRows* prefix, const TkLogitAdjust* adjust, bool hold) {
     if (n <= 0) { *err = "nothing to feed"; return false; }
     if (adjust)
         if (const char* why = adjust->check(session_.model->hp.vocab)) { *err = std::string("logit adjustment: ") + why; return false; }
@@ -111,7 +112,8 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
     r.slot = slot; r.pos0 = pos0; r.n = n; r.toks = toks; r.mask = mask;
     if (samp) r.samp = *samp;
     if (adjust && !adjust->neutral()) { r.adj = *adjust; r.adjusted = true; }
-    r.hold = r.adjusted || (adjust && (adjust->repeat != 1.0f || adjust->freq != 0.0f || adjust->present != 0.0f));
+    r.owner_hold = hold;
+    r.hold = hold || r.adjusted || (adjust && (adjust->repeat != 1.0f || adjust->freq != 0.0f || adjust->present != 0.0f));
     r.whole = prefix != nullptr && pos0 == 0;
     if (prefix) *prefix = PrefixRows{n, 0, 0};
     const bool stochastic = r.samp.temp > 0.0f;
@@ -127,7 +129,7 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
                 if (!ok) { *err = last_error_; return false; }
                 rows_++;
                 *sampled = got;
-                plan_ahead(slot, pos0, got, false);
+                plan_ahead(slot, pos0, got, hold); /* hold: lookup was switched on while a row ran ahead; it is the last one */
                 cv_.notify_all();
                 return true;
             }
@@ -146,6 +148,25 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
     if (prefix) { prefix->kept = r.kept; prefix->copied = r.copied; }
     if (!r.ok) { *err = r.error; return false; }
     *sampled = r.sampled;
+    return true;
+}
+
+bool TkLlmBatcher::submit_verify(int slot, int pos0, const int32_t* toks, int n, int32_t* ids_out, int* n_out, std::string* err) {
+    if (n < 1 || n > TK_LOOKUP_MAX_DRAFT + 1 || !toks || !ids_out || !n_out) { *err = "verify request: between 1 and 16 rows"; return false; }
+    if (slot < 0 || slot >= (int)slot_used_.size() || pos0 < 0 || pos0 + n > n_ctx_) { *err = "rows do not fit the context window"; return false; }
+    Request r;
+    r.slot = slot; r.pos0 = pos0; r.n = n; r.toks = toks; r.mask = nullptr;
+    r.verify = true;
+    r.hold = true;
+    std::unique_lock<std::mutex> lk(mu_);
+    if (stop_) { *err = "scheduler stopped"; return false; }
+    drop_ahead(slot); /* a slot with lookup on plans no row ahead; one left from before lookup was switched on is retired like any other */
+    queue_.push_back(&r);
+    cv_.notify_all();
+    r.cv.wait(lk, [&] { return r.finished; });
+    if (!r.ok) { *err = r.error; return false; }
+    *n_out = (int)r.ids.size();
+    for (size_t i = 0; i < r.ids.size(); ++i) ids_out[i] = r.ids[i];
     return true;
 }
 
@@ -173,6 +194,7 @@ void TkLlmBatcher::loop() {
     std::vector<Request*> completing;
     std::vector<AheadRow> ahead_rows;
     std::vector<ShiftReq*> shifting;
+    std::vector<char> rejected; /* [row of the pass]: a verify request's row behind its last accepted one */
     /* prefix cache: the copies of the pass being formed (at most one per request of the pass), the request each serves, and the slots that are
      * a source / a destination of this launch */
     std::vector<TkKvCopyDesc> copies;
@@ -192,6 +214,7 @@ void TkLlmBatcher::loop() {
         in_pass.clear(); completing.clear(); ahead_rows.clear(); copies.clear(); copy_for.clear();
         sq.clear(); ps.clear(); tk.clear(); masks.clear(); samps.clear(); adjs.clear();
         bool any_mask = false, any_samp = false, any_adj = false;
+        bool any_verify = false, all_qualify = true; /* verify requests (tk_llm_batcher.h): the pass may take forward_verify */
         {
             std::unique_lock<std::mutex> lk(mu_);
             cv_.wait(lk, [&] { return stop_ || !queue_.empty() || !shifts_.empty() || any_planned(); });
@@ -256,6 +279,8 @@ void TkLlmBatcher::loop() {
                     adjs.push_back(TkLogitAdjust{});
                 }
                 in_pass.push_back(Taken{r, take, (int)sq.size() - 1});
+                any_verify = any_verify || r->verify;
+                all_qualify = all_qualify && (r->verify || (r->done_rows + take == r->n && !r->mask && !(r->samp.temp > 0.0f) && !r->adjusted));
                 if (r->done_rows + take == r->n) {
                     completing.push_back(r);
                     masks.back() = r->mask; /* the row that is sampled */
@@ -299,7 +324,7 @@ void TkLlmBatcher::loop() {
                 for (Request* r : queue_) {
                     if ((int)sq.size() >= TK_MAX_ROWS) break;
                     use_cache(r);
-                    if (r->n - r->done_rows == 1) add_rows(r, 1);
+                    if (r->n - r->done_rows == 1) add_rows(r, 1); /* a verify request of one row among them */
                 }
             auto add_ahead = [&] {
                 for (size_t s = 0; s < ahead_.size() && (int)sq.size() < TK_MAX_ROWS; ++s) {
@@ -320,6 +345,7 @@ void TkLlmBatcher::loop() {
                 if ((int)sq.size() >= TK_MAX_ROWS) break;
                 use_cache(r);
                 if (decode_first && r->n - r->done_rows == 1) continue; /* taken above */
+                if (r->verify && r->n > TK_MAX_ROWS - (int)sq.size()) continue; /* its rows enter one pass together: the next one */
                 add_rows(r, std::min(r->n - r->done_rows, TK_MAX_ROWS - (int)sq.size()));
             }
             if (!decode_first) add_ahead();
@@ -332,7 +358,9 @@ void TkLlmBatcher::loop() {
         /* the copies go first on the session's stream: forward() then reads the copied rows, and a source row it overwrites was read before */
         bool copied_ok = true;
         if (!copies.empty()) copied_ok = session_.enqueue_kv_copy(copies.data(), (int)copies.size());
-        const bool ok = copied_ok && session_.forward(nrows, sq.data(), ps.data(), tk.data(), nullptr, head ? am.data() : nullptr, head, head && any_mask ? masks.data() : nullptr,
+        /* a pass with a verify request in which every request qualifies: every row is sampled, greedy, and a long context may take the run form */
+        const bool ok = any_verify && all_qualify ? copied_ok && session_.forward_verify(nrows, sq.data(), ps.data(), tk.data(), -1, nullptr, am.data())
+                        : copied_ok && session_.forward(nrows, sq.data(), ps.data(), tk.data(), nullptr, head ? am.data() : nullptr, head, head && any_mask ? masks.data() : nullptr,
                                         head && any_samp ? samps.data() : nullptr, head && any_adj ? adjs.data() : nullptr);
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -340,11 +368,22 @@ void TkLlmBatcher::loop() {
             if (nrows > max_rows_) max_rows_ = nrows;
             if (!ok) last_error_ = session_.error;
             if (!copies.empty()) copy_launches_++;
+            /* verify requests: the accept rule on the picks of their rows; the rows behind the last accepted one are not recorded */
+            rejected.assign((size_t)nrows, 0);
+            for (const Taken& t : in_pass) {
+                if (!t.r->verify || !ok) continue;
+                const int row0 = t.last_row - t.take + 1;
+                t.r->ids.resize((size_t)t.take);
+                const int kept = tk_lookup_accept(tk.data() + row0, am.data() + row0, t.take, eos_, t.r->ids.data());
+                t.r->ids.resize((size_t)kept);
+                for (int i = kept; i < t.take; ++i) rejected[(size_t)(row0 + i)] = 1;
+            }
             /* records: what the cache holds now that the pass is complete — copied rows, then the pass's rows in feeding order */
             if (ok) {
                 for (size_t c = 0; c < copies.size(); ++c)
                     for (int i = 0; i < copies[c].n; ++i) record_row(copies[c].dst_seq, copies[c].p0 + i, copy_for[c]->toks[copies[c].p0 + i]);
-                for (int i = 0; i < nrows; ++i) record_row(sq[(size_t)i], ps[(size_t)i], tk[(size_t)i]);
+                for (int i = 0; i < nrows; ++i)
+                    if (!rejected[(size_t)i]) record_row(sq[(size_t)i], ps[(size_t)i], tk[(size_t)i]);
             } else {
                 for (const TkKvCopyDesc& c : copies) rec_[(size_t)c.dst_seq].clear();
                 for (int i = 0; i < nrows; ++i) rec_[(size_t)sq[(size_t)i]].clear();
@@ -361,7 +400,8 @@ void TkLlmBatcher::loop() {
                     for (auto it = queue_.begin(); it != queue_.end(); ++it)
                         if (*it == r) { queue_.erase(it); break; }
                     if (ok) plan_ahead(r->slot, r->pos0 + r->n - 1, r->sampled, r->mask != nullptr || r->samp.temp > 0.0f || r->hold);
-                    if (!ok || ahead_[(size_t)r->slot].st != Ahead::PLANNED) held++;
+                    /* an owner that was handed several ids comes back only when it has given all but the last to its caller: nobody waits for it */
+                    if (!ok || (ahead_[(size_t)r->slot].st != Ahead::PLANNED && r->ids.size() <= 1)) held++;
                     r->finished = true;
                     r->cv.notify_all();
                 }
@@ -379,7 +419,7 @@ void TkLlmBatcher::loop() {
                     if (!ok) w->error = session_.error;
                     w->sampled = got;
                     rows_++;
-                    if (ok) plan_ahead(s, pos, got, false);
+                    if (ok) plan_ahead(s, pos, got, w->owner_hold);
                     w->finished = true;
                     w->cv.notify_all();
                 } else {

@@ -15,7 +15,9 @@
  * scheduler feeds that id at the next position in its very next pass WITHOUT waiting for the owner (one position ahead, never more); the
  * owner's next call then finds its row in flight or already done.  Not for rows sampled under a grammar mask (the next mask depends on
  * the accepted token), not for rows sampled under a non-neutral logit adjustment (the next window of the repetition penalties depends on the
- * accepted token, and the owner may change its bias list; this holds from the first sampled token on, whose window is still empty), not after EOS, not at the end of the context.  An owner that comes back with something else (a tool response, a
+ * accepted token, and the owner may change its bias list; this holds from the first sampled token on, whose window is still empty), not for a slot
+ * whose runner has lookup decoding on (the row after a sampled id is the first row of the owner's next verify pass, which carries drafts that only the
+ * owner can make: such a slot submits with `hold`, and a verify request never plans a row ahead), not after EOS, not at the end of the context.  An owner that comes back with something else (a tool response, a
  * new prompt) or not at all costs one wasted row: the cache row it wrote is overwritten before anything attends to it, because positions
  * are fed in order.  Tokens are unchanged — a row's result does not depend on when or with whom it runs.
  *
@@ -50,6 +52,19 @@
  * position, so it stays there until a prompt is fed from within [0, n_keep].  Rows [0, n_keep) are untouched and stay valid.  The iteration that
  * runs shifts forms no pass and launches no copy, so a slot that is being shifted is neither source nor destination of a copy of that iteration;
  * against the copies of other iterations the session stream orders it.
+ *
+ * Verify requests (submit_verify; lookup decoding, tk_lookup.h).  A greedy runner feeds its pending id and n - 1 drafted ids at positions pos0,
+ * pos0 + 1, ... of its slot; EVERY row is sampled, and the accept rule keeps the ids picks[0 .. m] that one-row passes would have produced.  The n rows
+ * enter one pass together (a request that finds fewer rows left waits for the next pass).  A pass that holds at least one verify request and in
+ * which every other request is a plain greedy, unmasked, unadjusted one that ends in this pass (its last row is the sampled one; run-ahead rows are
+ * such rows too) goes through TkLlmSession::forward_verify, where a long context may take the run form of the long attention; any other pass goes
+ * through forward() as before — forward() returns the arg max of every row of a multi-position pass too, and both paths give a row the same bits.
+ * A pass without a verify request is untouched: it replays the graphs it always did.
+ *   Records.  record_row runs for rows 0 .. m of a verify request only, so the slot's record ends at pos0 + m + 1: the prefix cache never keeps or
+ *     copies a rejected row.
+ *   Rejected rows stay in the cache beyond the owner's n_past and are overwritten before anything attends to them, because positions are fed in
+ *     ascending order: the argument made above for wasted run-ahead rows.
+ *   stats()' rows count all n rows of a verify request.
  */
 #ifndef TK_LLM_BATCHER_H
 #define TK_LLM_BATCHER_H
@@ -82,7 +97,12 @@ public:
      * the call returns, like `mask`; checked here against the limits.  A non-neutral one keeps the row from running ahead (header comment) */
     struct PrefixRows { int32_t prompt_rows = 0, kept = 0, copied = 0; };
     bool submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp = nullptr,
-                PrefixRows* prefix = nullptr, const TkLogitAdjust* adjust = nullptr);
+                PrefixRows* prefix = nullptr, const TkLogitAdjust* adjust = nullptr, bool hold = false);
+    /* hold: no row runs ahead of this request's sampled id (the owner has lookup decoding on: its next call is a verify request or comes with `hold` again) */
+    /* Blocking: the verify pass of lookup decoding (header comment, "Verify requests"): toks[0] is the slot's pending id, toks[1 .. n) are drafts, fed at
+     * positions pos0 .. pos0 + n - 1 in ONE pass, 1 <= n <= TK_LOOKUP_MAX_DRAFT + 1; every row is sampled greedily.  ids_out (room for n) receives the
+     * ids the accept rule keeps, *n_out = m + 1 of them; rows pos0 .. pos0 + m are the slot's valid cache rows afterwards */
+    bool submit_verify(int slot, int pos0, const int32_t* toks, int n, int32_t* ids_out, int* n_out, std::string* err);
     /* Blocking: context shift of sequence `slot` (common/tk_kv_shift.h, llama.cpp's rule): the first n_keep rows stay, the n_discard rows after them are
      * dropped, rows [n_keep + n_discard, n_past) move down by n_discard.  Queued like a request: the scheduler thread runs it between passes on the
      * session stream (header comment, "Context shift").  Thread-safe; the slot's owner has no other call outstanding */
@@ -108,6 +128,9 @@ private:
         bool adjusted = false; /* adj is not neutral */
         bool hold = false;     /* no run-ahead from this row: adjusted, or penalties that are on over a still empty window (the next one is not) */
         int32_t sampled = -1;
+        bool owner_hold = false;      /* submit's `hold` argument: the owner has lookup decoding on */
+        bool verify = false;         /* a verify request: all n rows in one pass, every row sampled */
+        std::vector<int32_t> ids;     /* what the accept rule kept of its picks (m + 1 ids) */
         bool finished = false, ok = true;
         std::string error;
         std::condition_variable cv;

@@ -104,6 +104,18 @@ public:
     bool forward(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, float* logits_host, int32_t* argmax_host,
                  bool lm_head = true, const uint32_t* const* row_masks = nullptr, const TkSampleRow* row_samp = nullptr,
                  const TkLogitAdjust* row_adjust = nullptr);
+    /* the verify pass of lookup decoding (tk_lookup.h): up to TK_MAX_ROWS greedy, unmasked, unadjusted rows; the rows of each sequence stand at
+     * consecutive ascending positions and are contiguous in the pass; the head runs on ALL rows (picks_host[r] = arg max of row r, logits_host
+     * optional).  form: the attention of the pass — 0 k_attention per row, 2 k_attention_prefill's 16-row tiles, 4 the run form of the long-context
+     * attention (tk_llm_kernels.h; at most TK_LONG_ATT_MAX_ROWS rows, head_dim 64 or 128, a session whose window can reach TK_LONG_ATT_MIN_POS), all
+     * three bit-identical; -1 = the session's choice (verify_form).  A form that does not apply is refused before anything is enqueued
+     * (*bad_args, optional, tells that from a device error).  The pass replays graphs of its own ([form][row count]): forward()'s graphs and
+     * choose_attention are untouched, and the run form is chosen through this entry only. */
+    bool forward_verify(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, int form, float* logits_host, int32_t* picks_host,
+                        bool* bad_args = nullptr);
+    /* the form forward_verify(form = -1) takes for nrows rows whose highest position is `top`: 4 from tk_verify_run_min_pos(nrows) where the run form
+     * applies, else 2 from position 128 where k_attention_prefill applies, else 0 */
+    int verify_form(int nrows, int top) const;
     /* one pipeline stage of a pass: layers [l0, l1) on this GPU.  The first stage starts from `tok` (x_in == nullptr), later stages
      * from the residual stream x_in [nrows][d_model] fp32; every stage but the last writes the stream to x_out; the last one
      * (head == true, l1 == n_layer) samples.  x_on_host: x_in / x_out are host pointers (gloo transport), otherwise device
@@ -193,6 +205,10 @@ private:
     /* a decode pass (every sequence once) of at most TK_LONG_ATT_MAX_ROWS rows that reaches position TK_LONG_ATT_MIN_POS runs its attention as
      * append + scores + PV launches spread over the chip (tk_launch_attention_long) instead of one latency chain per pair of heads; bit-identical */
     bool long_pass = false;
+    /* set by forward_verify only: the multi-position pass being enqueued takes the run form of the long-context attention (rope/append launch,
+     * then tk_launch_attention_long(run)); verify passes replay graph_verify[form / 2][row count] */
+    bool run_pass = false;
+    hipGraphExec_t graph_verify[3][TK_MAX_ROWS + 1] = {};
     bool counted_ = false; /* this session is in the device's count of live decode sessions (tk_attention_note_session) */
     float* d_scores = nullptr; /* [TK_LONG_ATT_MAX_ROWS][n_head][max_ctx], allocated when the window can reach TK_LONG_ATT_MIN_POS */
     void choose_attention(const int32_t* pos, int nrows);

@@ -443,6 +443,7 @@ TkLlmSession::~TkLlmSession() {
     for (auto& v : graph_head_nf) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     for (auto& v : graph_exec_adj) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     for (auto& v : graph_head_nf_adj) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
+    for (auto& v : graph_verify) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     void* ptrs[] = {kcache, vcache, x, x2, qbuf, partial, partial2, logits, rope_cos, rope_sin, d_seq, d_pos, d_tok, d_nsteps, d_hist, d_mask, d_mask_row, d_samp, d_tab, d_tiles, d_scores};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (d_kvcopy) (void)hipFree(d_kvcopy);
@@ -1055,7 +1056,9 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
     };
     /* passes that hold several positions of a sequence (prompt chunks): 16 rows of a sequence per attention workgroup on the fp32 matrix pipe
      * (k_attention_prefill, bit-identical to k_attention); the row -> tile table is built once per pass from the sequence ids on the device */
-    const bool tiled_attn = !fused_attn && l1 > l0 && tiled_pass && tk_attention_prefill_applies(h.n_head, h.n_kv_head, h.head_dim);
+    /* the verify pass of lookup decoding over a long context (forward_verify only): rope/append as its own launch, then the long form's run variant */
+    const bool run_attn = !fused_attn && l1 > l0 && run_pass && d_scores && tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim);
+    const bool tiled_attn = !fused_attn && !run_attn && l1 > l0 && tiled_pass && tk_attention_prefill_applies(h.n_head, h.n_kv_head, h.head_dim);
     /* few rows over a long context: the fused kernels would walk it as one latency chain per pair of heads */
     const bool long_attn = fused_attn && l1 > l0 && long_pass && d_scores && tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim);
     if (tiled_attn) tk_launch_att_tiles(d_seq, nrows, d_tiles, s);
@@ -1071,7 +1074,7 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
             if (!fused_attn)
                 tk_launch_qkv_rope_append(partial2, ks_qkv, QD + 2 * KVD, h.n_head, h.n_kv_head, h.head_dim, rope_cos, rope_sin, d_seq, d_pos, nrows,
                                           qbuf, kcache, vcache, l, max_seq, max_ctx, s);
-            if (long_attn) tk_launch_attention_long(partial2, ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, d_scores, act_qd, s);
+            if (long_attn || run_attn) tk_launch_attention_long(partial2, ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, d_scores, act_qd, s, run_attn);
             else if (tiled_attn) tk_launch_attention_prefill(qbuf, kcache, vcache, d_seq, d_pos, d_tiles, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, act_qd, s);
             else tk_launch_attention(qbuf, partial2, ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head,
                                      h.head_dim, l, max_seq, max_ctx, act_qd, fused_attn, s);
@@ -1085,7 +1088,7 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
         if (!fused_attn)
             tk_launch_qkv_rope_append(partial, ks_qkv, QD + 2 * KVD, h.n_head, h.n_kv_head, h.head_dim, rope_cos, rope_sin, d_seq, d_pos, nrows,
                                       qbuf, kcache, vcache, l, max_seq, max_ctx, s);
-        if (long_attn) tk_launch_attention_long(partial, ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, d_scores, act_qd, s);
+        if (long_attn || run_attn) tk_launch_attention_long(partial, ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, d_scores, act_qd, s, run_attn);
         else if (tiled_attn) tk_launch_attention_prefill(qbuf, kcache, vcache, d_seq, d_pos, d_tiles, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, act_qd, s);
         else tk_launch_attention(qbuf, partial, ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head,
                                  h.head_dim, l, max_seq, max_ctx, act_qd, fused_attn, s);
@@ -1267,6 +1270,70 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
     if (!lm_head) { HIPQ(hipStreamSynchronize(stream)); return true; }
     if (logits_host) HIPQ(hipMemcpyAsync(logits_host, logits, (size_t)nrows * model->hp.vocab * 4, hipMemcpyDeviceToHost, stream));
     if (argmax_host) HIPQ(hipMemcpyAsync(argmax_host, d_tok, nrows * 4, hipMemcpyDeviceToHost, stream));
+    HIPQ(hipStreamSynchronize(stream));
+    return true;
+}
+
+int TkLlmSession::verify_form(int nrows, int top) const {
+    const TkLlmHParams& h = model->hp;
+    if (d_scores && tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim) && top >= tk_verify_run_min_pos(nrows)) return 4;
+    if (top >= TK_TILED_ATT_FROM_POS && tk_attention_prefill_applies(h.n_head, h.n_kv_head, h.head_dim)) return 2;
+    return 0;
+}
+
+bool TkLlmSession::forward_verify(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, int form, float* logits_host, int32_t* picks_host,
+                                  bool* bad_args) {
+    const TkLlmHParams& h = model->hp;
+    if (bad_args) *bad_args = true;
+    if (nrows <= 0 || nrows > TK_MAX_ROWS) { error = "nrows must be in [1,256]"; return false; }
+    if (!seq || !pos || !tok) { error = "verify pass: missing row arrays"; return false; }
+    int top = 0;
+    for (int r = 0; r < nrows; ++r) {
+        if (seq[r] < 0 || seq[r] >= max_seq || pos[r] < 0 || pos[r] >= max_ctx || tok[r] < 0 || tok[r] >= h.vocab) {
+            error = "row out of range (sequence id, position or token id)";
+            return false;
+        }
+        top = pos[r] > top ? pos[r] : top;
+        if (r > 0 && seq[r] == seq[r - 1] && pos[r] != pos[r - 1] + 1) { error = "verify pass: the rows of a sequence stand at consecutive ascending positions"; return false; }
+        for (int b = 0; b + 1 < r; ++b)
+            if (seq[b] == seq[r] && seq[r - 1] != seq[r]) { error = "verify pass: the rows of a sequence are contiguous in the pass"; return false; }
+    }
+    if (form == -1) form = verify_form(nrows, top);
+    if (form != 0 && form != 2 && form != 4) { error = "verify pass: form must be -1, 0, 2 or 4"; return false; }
+    if (form == 2 && !tk_attention_prefill_applies(h.n_head, h.n_kv_head, h.head_dim)) { error = "verify pass: the tiled attention form does not take this head geometry"; return false; }
+    if (form == 4 && !(d_scores && tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim))) {
+        error = "verify pass: the run form takes at most " + std::to_string(TK_LONG_ATT_MAX_ROWS) + " rows, head_dim 64 or 128, and a context window beyond " + std::to_string(TK_LONG_ATT_MIN_POS) + " positions";
+        return false;
+    }
+    if (bad_args) *bad_args = false;
+    HIPQ(hipSetDevice(model->device));
+    HIPQ(hipMemcpyAsync(d_seq, seq, nrows * 4, hipMemcpyHostToDevice, stream));
+    HIPQ(hipMemcpyAsync(d_pos, pos, nrows * 4, hipMemcpyHostToDevice, stream));
+    HIPQ(hipMemcpyAsync(d_tok, tok, nrows * 4, hipMemcpyHostToDevice, stream));
+    HIPQ(hipMemsetAsync(d_nsteps, 0, TK_MAX_ROWS * 4, stream));
+    /* greedy, unmasked, unadjusted rows: whatever an earlier pass left in the tables goes */
+    if (mask_rows_dirty) { HIPQ(hipMemsetAsync(d_mask_row, 0xFF, TK_MAX_ROWS * 4, stream)); mask_rows_dirty = false; }
+    if (samp_dirty) { HIPQ(hipMemsetAsync(d_samp, 0, TK_MAX_ROWS * sizeof(TkSampleRow), stream)); samp_dirty = false; }
+    if (adj_dirty) { HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream)); adj_dirty = false; }
+    adjust_pass = false;
+    /* the pass is described here, not by choose_attention: rope/append always runs as a launch of its own (fused_attn = false) */
+    const bool tiled_was = tiled_pass, long_was = long_pass;
+    tiled_pass = form == 2; long_pass = false; run_pass = form == 4;
+    bool ok = true;
+    if (graphs_enabled()) {
+        hipGraphExec_t* slot = &graph_verify[form / 2][nrows];
+        ok = capture_pass(slot, nrows, true, false);
+        if (ok && hipGraphLaunch(*slot, stream) != hipSuccess) { error = "verify pass: graph launch failed"; ok = false; }
+    } else {
+        launch_error.clear();
+        enqueue_pass(nrows, true, false);
+    }
+    tiled_pass = tiled_was; long_pass = long_was; run_pass = false;
+    if (!ok) return false;
+    if (!launch_error.empty()) { error = launch_error; (void)hipStreamSynchronize(stream); return false; }
+    HIPQ(hipGetLastError());
+    if (logits_host) HIPQ(hipMemcpyAsync(logits_host, logits, (size_t)nrows * h.vocab * 4, hipMemcpyDeviceToHost, stream));
+    if (picks_host) HIPQ(hipMemcpyAsync(picks_host, d_tok, nrows * 4, hipMemcpyDeviceToHost, stream));
     HIPQ(hipStreamSynchronize(stream));
     return true;
 }

@@ -133,7 +133,14 @@ bool tk_attention_long_applies(int nrows, int n_head, int n_kv_head, int head_di
 size_t tk_attention_long_scratch_floats(int n_head, int head_dim, int max_ctx); /* floats of the `scores` scratch buffer */
 void tk_launch_attention_long(const float* partial, int ks, int n_total, const float* rope_cos, const float* rope_sin, uint16_t* kcache, uint16_t* vcache,
                               const int32_t* seq, const int32_t* pos, int nrows, int n_head, int n_kv_head, int head_dim, int layer, int max_seq, int max_ctx,
-                              float* scores, TkActQ8 out, hipStream_t s);
+                              float* scores, TkActQ8 out, hipStream_t s, bool run = false);
+/* run = the verify pass of lookup decoding (TkLlmSession::forward_verify): several consecutive positions of a sequence in one pass of at most
+ * TK_LONG_ATT_MAX_ROWS rows.  tk_launch_qkv_rope_append has already put the pass's rows into the cache; the scores launch finishes only the queries,
+ * stores nothing to the caches and reads key rows <= p from them.  Bit-identical to k_attention's per-row form and to k_attention_prefill.
+ * tk_verify_run_min_pos: the top position from which the session prefers the run form to k_attention_prefill for a pass of `nrows` rows.  By
+ * measurement on full 7B (profiles/lookup_decoding.txt): at 2, 5 and 8 rows the run form wins every round at every context timed, 256 .. 4 000
+ * (2.6 against 3.3 ms per pass at 256, 3.5 against 13.9 ms at 4 000); 256 is the lowest context that was timed, so the choice starts there */
+static inline int tk_verify_run_min_pos(int nrows) { (void)nrows; return 256; }
 /* prompt prefix cache (tk_llm_batcher.h): rows [p0, p0 + n) of sequence src_seq copied onto the same rows of dst_seq in every layer, KV head and
  * both caches, all `ndesc` <= TK_MAX_ROWS descriptors (a device array) in one launch.  src_seq != dst_seq; no two descriptors of a launch share a
  * destination, and no destination of a launch is another descriptor's source.  max_n = the largest n among them (sizes the grid together with the

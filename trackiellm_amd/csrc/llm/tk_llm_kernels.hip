@@ -3617,8 +3617,14 @@ __global__ __launch_bounds__((256 / HD) * 256) void k_attention_prefill(const fl
  *   k_att_pv_join       the four classes joined in order, division, Q8 quantisation.
  * Bit-identical to k_attention / k_attention_narrow (tests/test_llm_attention_gpu.py: the decode cases past 2 048 positions run both).
  * The session takes this form for passes of at most TK_LONG_ATT_MAX_ROWS rows that reach tk_long_att_min_pos(rows) (tk_llm_kernels.h).
+ *
+ * RUN (the verify pass of lookup decoding, TkLlmSession::forward_verify): the pass holds several consecutive positions of one sequence, so row
+ * i + 1 attends to the key row i appends — a key that the append inside row i's last-block workgroup may not have stored yet.  Such a pass
+ * therefore runs k_qkv_rope_append as a launch of its own first (stream order makes every row of the pass visible), and this variant finishes
+ * only the queries: it stores nothing to the caches, stages key rows <= p from the cache (no clamp to p - 1) and patches nothing in from LDS.
+ * A score is the same canonical fma chain over the same f16 key bits, so the run form is bit-identical to the two other forms of such a pass.
  * ------------------------------------------------------------------------------------------ */
-template <int HD>
+template <int HD, bool RUN>
 __global__ __launch_bounds__(256) void k_att_scores_long(const float* __restrict__ partial, int ks, int n_total, const float* __restrict__ rope_cos,
                                                          const float* __restrict__ rope_sin, uint16_t* __restrict__ kcache, uint16_t* __restrict__ vcache,
                                                          const int32_t* __restrict__ seq, const int32_t* __restrict__ pos, int n_head, int n_kv_head, int layer,
@@ -3633,7 +3639,7 @@ __global__ __launch_bounds__(256) void k_att_scores_long(const float* __restrict
     const int t = threadIdx.x, lane = t & 63, n16 = lane & 15, G = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int GQ = n_head / n_kv_head, QD = n_head * HD, KVD = n_kv_head * HD;
-    const bool last = 64 * b + 64 >= T; /* this block holds position p */
+    const bool last = !RUN && 64 * b + 64 >= T; /* this block holds position p and its workgroup appends the row (never in a run: the rows are in the cache) */
     uint16_t* krun = kcache + (((int64_t)layer * max_seq + seq[r]) * n_kv_head + kvh) * (int64_t)max_ctx * HD;
     {   /* q (every block) and k, v of this row (the last block): K-split sums, RoPE on adjacent pairs, f16 rounding — k_qkv_rope_append's
          * arithmetic, inside this launch (a launch of its own cost 4.8 us per layer) */
@@ -3662,7 +3668,8 @@ __global__ __launch_bounds__(256) void k_att_scores_long(const float* __restrict
         if (PIECES % 256 == 0 || pid < PIECES) {
             const int pn = pid / PPR, q8 = pid % PPR;
             int pr = 64 * b + pn;
-            pr = pr < p ? pr : (p > 0 ? p - 1 : 0); /* cached rows only: position p itself is patched in from LDS below (its store may still be on its way) */
+            if (RUN) pr = pr < p ? pr : p; /* rows <= p are in the cache; rows beyond p may belong to later rows of the run and are never read */
+            else pr = pr < p ? pr : (p > 0 ? p - 1 : 0); /* cached rows only: position p itself is patched in from LDS below (its store may still be on its way) */
             const uint4 kk = *(const uint4*)(krun + (int64_t)pr * HD + 8 * q8);
             const uint32_t wv[4] = {kk.x, kk.y, kk.z, kk.w};
 #pragma unroll
@@ -3812,21 +3819,25 @@ void tk_launch_att_pv_join(const float* pv_part, const float* l_part, int nrows,
 
 void tk_launch_attention_long(const float* partial, int ks, int n_total, const float* rope_cos, const float* rope_sin, uint16_t* kcache, uint16_t* vcache,
                               const int32_t* seq, const int32_t* pos, int nrows, int n_head, int n_kv_head, int head_dim, int layer, int max_seq, int max_ctx,
-                              float* scores, TkActQ8 out, hipStream_t s) {
+                              float* scores, TkActQ8 out, hipStream_t s, bool run) {
     const dim3 gs(n_kv_head, (max_ctx + 63) / 64, nrows);
     /* the scratch buffer: scores, then the classes' partial outputs and denominators (tk_attention_long_scratch_floats) */
     float* pv_part = scores + (size_t)TK_LONG_ATT_MAX_ROWS * n_head * max_ctx;
     float* l_part = pv_part + (size_t)TK_LONG_ATT_MAX_ROWS * n_head * TK_ATT_TSPLIT * head_dim;
     const dim3 gc(TK_ATT_TSPLIT, n_head, nrows);
+#define TK_SCORES_LONG(HD_, RUN_)                                                                                                                              \
+    hipLaunchKernelGGL((k_att_scores_long<HD_, RUN_>), gs, dim3(256), 0, s, partial, ks, n_total, rope_cos, rope_sin, kcache, vcache, seq, pos, n_head, n_kv_head, \
+                       layer, max_seq, max_ctx, scores)
     if (head_dim == 128) {
-        hipLaunchKernelGGL((k_att_scores_long<128>), gs, dim3(256), 0, s, partial, ks, n_total, rope_cos, rope_sin, kcache, vcache, seq, pos, n_head, n_kv_head, layer,
-                           max_seq, max_ctx, scores);
+        if (run) TK_SCORES_LONG(128, true);
+        else TK_SCORES_LONG(128, false);
         hipLaunchKernelGGL((k_att_pv_chain<128>), gc, dim3(64), 0, s, scores, vcache, seq, pos, n_head, n_kv_head, layer, max_seq, max_ctx, pv_part, l_part);
     } else {
-        hipLaunchKernelGGL((k_att_scores_long<64>), gs, dim3(256), 0, s, partial, ks, n_total, rope_cos, rope_sin, kcache, vcache, seq, pos, n_head, n_kv_head, layer,
-                           max_seq, max_ctx, scores);
+        if (run) TK_SCORES_LONG(64, true);
+        else TK_SCORES_LONG(64, false);
         hipLaunchKernelGGL((k_att_pv_chain<64>), gc, dim3(64), 0, s, scores, vcache, seq, pos, n_head, n_kv_head, layer, max_seq, max_ctx, pv_part, l_part);
     }
+#undef TK_SCORES_LONG
     tk_launch_att_pv_join(pv_part, l_part, nrows, n_head, head_dim, out, s);
 }
 

@@ -38,6 +38,32 @@ def prefix_match(toks, records, self_slot=-1, cursor=-1):
     return out[0], out[1], out[2]
 
 
+def lookup_draft(ctx, pred, ngram_min, ngram_max, n_draft):
+    """lookup decoding's draft rule, no GPU involved (tk_mi355x_lookup_draft): the ids drafted behind the last id of `ctx` from the prediction `pred`
+    (may be empty), then from `ctx` itself"""
+    ctx = np.ascontiguousarray(ctx, dtype=np.int32).reshape(-1)
+    pred = np.ascontiguousarray(pred, dtype=np.int32).reshape(-1)
+    out = np.zeros(max(int(n_draft), 1), np.int32)
+    n = lib().tk_mi355x_lookup_draft(_p(ctx) if ctx.size else None, int(ctx.size), _p(pred) if pred.size else None, int(pred.size), int(ngram_min), int(ngram_max),
+                                     int(n_draft), _p(out))
+    if n < 0:
+        raise ValueError("lookup_draft: bad arguments")
+    return out[:n].tolist()
+
+
+def lookup_accept(toks, picks, eos):
+    """lookup decoding's accept rule, no GPU involved (tk_mi355x_lookup_accept): the ids a verify pass that fed `toks` and picked `picks` hands out"""
+    toks = np.ascontiguousarray(toks, dtype=np.int32).reshape(-1)
+    picks = np.ascontiguousarray(picks, dtype=np.int32).reshape(-1)
+    if toks.size != picks.size:
+        raise ValueError("lookup_accept: toks and picks must have one length")
+    out = np.zeros(max(int(toks.size), 1), np.int32)
+    n = lib().tk_mi355x_lookup_accept(_p(toks) if toks.size else None, _p(picks) if picks.size else None, int(toks.size), int(eos), _p(out))
+    if n < 0:
+        raise ValueError("lookup_accept: bad arguments")
+    return out[:n].tolist()
+
+
 class LlmHParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_layer", "d_model", "n_head", "n_kv_head", "head_dim", "d_ff", "vocab")] + \
                [("rms_eps", C.c_float), ("rope_theta", C.c_float)] + \
@@ -211,6 +237,14 @@ def attention_plan(nrows, n_head, n_kv_head, head_dim, max_ctx, fused=True, devi
     return tuple(out)
 
 
+def attention_plan_verify(nrows, n_head, n_kv_head, head_dim, max_ctx, top_position, device=0):
+    """attention_plan for a verify pass of lookup decoding (LlmSession.forward_verify, form -1): kernel 4 = the run form of the long-context
+    attention, else 2 or 0 (tk_mi355x_attention_plan_verify)"""
+    out = (C.c_int32 * 4)()
+    check(lib().tk_mi355x_attention_plan_verify(device, nrows, n_head, n_kv_head, head_dim, max_ctx, int(top_position), out))
+    return tuple(out)
+
+
 class Sampling(C.Structure):  # tk_mi355x_sampling_t
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("min_p", C.c_float), ("top_k", C.c_int32), ("seed", C.c_uint64),
                 ("counter", C.c_uint32), ("reserved", C.c_uint32)]
@@ -344,6 +378,19 @@ class LlmSession:
         check(lib().tk_mi355x_llm_forward_adjusted(self.h, n, _p(seq), _p(pos), _p(tok), tab, adj, _p(logits), _p(ids)))
         del keep
         return logits, ids
+
+    def forward_verify(self, seq, pos, tok, form=-1, want_logits=True):
+        """the verify pass of lookup decoding (tk_mi355x_llm_forward_verify): greedy rows, the rows of a sequence at consecutive ascending positions
+        and contiguous; every row is sampled.  form: 0 k_attention per row, 2 k_attention_prefill, 4 the run form of the long-context attention,
+        -1 the session's choice.  Returns (logits or None, picks)"""
+        seq = np.ascontiguousarray(seq, dtype=np.int32)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        tok = np.ascontiguousarray(tok, dtype=np.int32)
+        n = len(seq)
+        logits = np.empty((n, self.vocab), dtype=np.float32) if want_logits else None
+        picks = np.empty(n, dtype=np.int32)
+        check(lib().tk_mi355x_llm_forward_verify(self.h, n, _p(seq), _p(pos), _p(tok), int(form), _p(logits), _p(picks)))
+        return logits, picks
 
     def forward_stage(self, seq, pos, layer0, layer1, tok=None, x_in=None, x_out=None, head=False, on_host=True):
         """layers [layer0, layer1) of one pass (pipeline stage).  x_in / x_out: float32 [n][d_model] numpy arrays (on_host) or raw
@@ -652,6 +699,22 @@ class LlmRunner:
         n, d = C.c_int32(0), C.c_int64(0)
         check(lib().tk_mi355x_llm_runner_context_shifts(self.h, C.byref(n), C.byref(d)))
         return n.value, d.value
+
+    def set_lookup(self, n_draft, ngram_min=1, ngram_max=3):
+        """lookup decoding for a greedy runner (off by default; n_draft 0 = off): up to n_draft ids drafted per pass from the prediction, then from
+        the context, by the longest n-gram of ngram_max .. ngram_min ids that ends the context (tk_mi355x_llm_runner_set_lookup)"""
+        check(lib().tk_mi355x_llm_runner_set_lookup(self.h, int(n_draft), int(ngram_min), int(ngram_max)))
+
+    def set_prediction(self, ids):
+        """the host's prediction of the reply, as token ids (copied; an empty list clears it; it survives prepare())"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        check(lib().tk_mi355x_llm_runner_set_prediction(self.h, _p(ids) if ids.size else None, int(ids.size)))
+
+    def lookup_stats(self):
+        """(passes that carried drafts, drafts fed, drafts accepted) since the last prepare()"""
+        v, d, a = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib().tk_mi355x_llm_runner_lookup_stats(self.h, C.byref(v), C.byref(d), C.byref(a)))
+        return v.value, d.value, a.value
 
     def last_prompt_rows(self):
         """(rows, of them kept in place, of them copied from another runner's slot) of the last prepare()"""
