@@ -653,6 +653,56 @@ typedef struct {
 } tk_mi355x_nn_row_probe_t;
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_nn_row_probe(int device, tk_mi355x_nn_row_probe_t* p);
 
+/* test hook for the kernels at the two ends of the perception streams — sensor bytes to the networks' first tensor, the networks' last tensor to
+ * what the cortex reads: ONE launch of one production launcher on host arrays (DEPTH_METRIC: the min / max launch and then the metric launch,
+ * as the depth engine issues them).  The contract is tk_mi355x_nn_row_probe's: a / b / c are inputs of n_a / n_b / n_c ELEMENTS of the type
+ * the table names; y (n_y elements) and y2 (n_y2) are IN/OUT: uploaded before the launch, read back whole after it, so every element the kernel
+ * must not touch comes back as the caller left it.  Every address the launch can reach is computed from the geometry and checked against the
+ * counts first; anything outside, an extent < 1, a pitch below the row, an array the op does not use that is not NULL with a count of 0, or
+ * anything the launcher itself refuses is TK_ERROR_INVALID_ARGUMENT with nothing launched.
+ *   op                 geometry                                   arrays
+ *   FRAMES             B n_samples pcm_stride n_total T           a = pcm int16 [B] rows pcm_stride apart (n_samples read of each), b = window [400],
+ *                                                                 y [B][T][400]; 1 <= n_samples <= n_total, pcm_stride >= n_samples, n_total > 200 and
+ *                                                                 160 (T - 1) + 199 <= 2 (n_total - 1): one reflection at either end stays inside
+ *   POWER              rows nb                                    a = ri [rows][2 nb] (re | im), y [rows][nb]
+ *   LOGMEL_FINISH      B per_b                                    y = mel [B][per_b], in place
+ *   VAD_HEAD           rows(=n) hidden                            a = hid [n][hidden], b = w2 [hidden], c = b2 [1], y = prob [n]
+ *   PREPROCESS         in_w in_h in_stride bpp out_w out_h nhwc   a = frame uint8, rows in_stride BYTES apart (the last row may end at its last pixel's third
+ *                      mean std_dev scale                         byte), y [3][out_h][out_w] or, nhwc = 1, [out_h][out_w][3]; in_w, in_h >= 2, bpp 3 or 4,
+ *                                                                 in_stride >= in_w bpp.  scale == 1/255 or 0 selects k_preprocess, any other finite value
+ *                                                                 k_preprocess_scaled, exactly as tk_kernels_preprocess_image chooses
+ *   DEPTH_MINMAX       n                                          a = x [n], y = {min, max}
+ *   DEPTH_METRIC       n min_depth max_depth                      a = x [n], y = metric [n], y2 = {min, max} as the first launch left them
+ *   POSTPROCESS_DEPTH  width height scale shift                   a = raw [height][width], y [height][width] (tk_kernels_postprocess_depth_map)
+ *   DEPTH_TO_POINTS    width height fx fy cx cy                   a = depth [height][width], y [height][width][3] (tk_kernels_depth_to_point_cloud);
+ *                                                                 fx or fy == 0 is the launcher's refusal
+ *   BOX_ATTRIBUTES     in_w in_h (the frame) rows(=boxes)         a = frame uint8 [in_h][in_w][3] packed, b = rects int32 [boxes][4] = {x, y, w, h},
+ *                                                                 y int32 [boxes][2] = {colour bin, door closed}; the hook (not the kernel) asks |x|, |y| <= 2^30,
+ *                                                                 |w|, |h| <= 2^20 and an area of at most 2^24 pixels, so that no launch runs long
+ * kernel (out): PREPROCESS 0 k_preprocess, 1 k_preprocess_scaled; POSTPROCESS_DEPTH and DEPTH_TO_POINTS the number of 256-thread blocks of the
+ * launch (capped by the launcher: a map of more elements takes further trips of the grid-stride loop); -1 a refusal; every other op 0.
+ * device < 0: validate and report `kernel` only, no device is touched. */
+enum {
+    TK_MI355X_EDGE_FRAMES = 0, TK_MI355X_EDGE_POWER = 1, TK_MI355X_EDGE_LOGMEL_FINISH = 2, TK_MI355X_EDGE_VAD_HEAD = 3, TK_MI355X_EDGE_PREPROCESS = 4,
+    TK_MI355X_EDGE_DEPTH_MINMAX = 5, TK_MI355X_EDGE_DEPTH_METRIC = 6, TK_MI355X_EDGE_POSTPROCESS_DEPTH = 7, TK_MI355X_EDGE_DEPTH_TO_POINTS = 8,
+    TK_MI355X_EDGE_BOX_ATTRIBUTES = 9
+};
+typedef struct {
+    int32_t op;
+    int32_t B, n_samples, pcm_stride, n_total, T;           /* FRAMES; B also LOGMEL_FINISH */
+    int32_t rows, nb, per_b, hidden;
+    int32_t in_w, in_h, in_stride, bpp, out_w, out_h, nhwc; /* PREPROCESS; in_w, in_h also BOX_ATTRIBUTES */
+    int32_t width, height;                                  /* POSTPROCESS_DEPTH, DEPTH_TO_POINTS */
+    int32_t kernel;                                         /* out */
+    int64_t n;                                              /* DEPTH_MINMAX, DEPTH_METRIC */
+    float mean[3], std_dev[3], scale, shift;
+    float min_depth, max_depth, fx, fy, cx, cy;
+    const void *a, *b, *c;
+    void *y, *y2;
+    int64_t n_a, n_b, n_c, n_y, n_y2;
+} tk_mi355x_edge_probe_t;
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_edge_probe(int device, tk_mi355x_edge_probe_t* p);
+
 /* test hook for the detector's post-processing kernels (csrc/vision/tk_vision_engine.hip), ONE decode + rank + mask + scan sequence on host arrays:
  * kind 0: three raw head maps head[i] = [B][H_i W_i][ld[i]] floats (n_head[i] in all) with ld[i] >= 64 + nc and H_i = in_h / s, W_i = in_w / s
  *         for s = 8, 16, 32 (in_w, in_h multiples of 32; n_anchors must be the three grids' total): k_yolo_decode, then tk_launch_yolo_post;

@@ -305,6 +305,13 @@ extern "C" void orc_add_rows(float* x, const float* add, int rows, int D, int ad
 extern "C" void orc_embed_rows(const float* table, const float* pos, const int32_t* idx, const int32_t* pos_idx, int rows, int D, float* out) {
     CpuAudioOps().embed_rows(table, pos, idx, pos_idx, rows, D, out);
 }
+/* the log-mel front end's three steps alone, and tk_log10f on one argument (tests measure it against float64) */
+extern "C" void orc_frames(const int16_t* pcm, int B, int n_samples, int pcm_stride, int n_total, int T, const float* window, float* out) {
+    CpuAudioOps().frames(pcm, B, n_samples, pcm_stride, n_total, T, window, out);
+}
+extern "C" void orc_power(const float* ri, int rows, int nb, float* out) { CpuAudioOps().power(ri, rows, nb, out); }
+extern "C" void orc_logmel_finish(float* mel, int B, int per_b) { CpuAudioOps().logmel_finish(mel, B, per_b); }
+extern "C" void orc_log10f_n(const float* x, int64_t n, float* y) { for (int64_t i = 0; i < n; ++i) y[i] = tk_log10f(x[i]); }
 extern "C" float orc_layernorm_eps() { return TK_WH_LN_EPS; }
 /* the attention of tk_whisper_graph.h at ONE query row per sequence, in its three-launch form (scores GEMM, softmax_rows, value GEMM): what the
  * decoder-step kernel must equal.  q / out [B] rows q_bstride apart, k / v [B] x [Tk] rows of pitch d, kv_bstride apart */
@@ -465,15 +472,20 @@ int orc_whisper_decode_failed(const int32_t* toks, const float* lp, int n_steps,
 }
 
 /* ---- VAD ---- */
-void orc_vad_probabilities(uint64_t seed, int window, int hidden, const float* windows, int n, float* prob) {
-    std::vector<float> w1((size_t)window * hidden), b1(hidden), w2(hidden), b2(1), hid((size_t)n * hidden);
-    tk_vad_synth(seed, window, hidden, w1.data(), b1.data(), w2.data(), b2.data());
-    orc_gemm(windows, w1.data(), hid.data(), b1.data(), nullptr, n, hidden, window, window, window, hidden, 0, 0, 0, 1.0f);
+/* the second layer on given hidden rows: relu, one fma chain over the hidden units, + b2, sigmoid */
+void orc_vad_head(const float* hid, int n, int hidden, const float* w2, const float* b2, float* prob) {
     for (int i = 0; i < n; ++i) {
         float acc = 0.0f;
         for (int k = 0; k < hidden; ++k) acc = tk_fmaf(tk_fmaxf(hid[(size_t)i * hidden + k], 0.0f), w2[k], acc);
         prob[i] = tk_sigmoidf(acc + b2[0]);
     }
+}
+
+void orc_vad_probabilities(uint64_t seed, int window, int hidden, const float* windows, int n, float* prob) {
+    std::vector<float> w1((size_t)window * hidden), b1(hidden), w2(hidden), b2(1), hid((size_t)n * hidden);
+    tk_vad_synth(seed, window, hidden, w1.data(), b1.data(), w2.data(), b2.data());
+    orc_gemm(windows, w1.data(), hid.data(), b1.data(), nullptr, n, hidden, window, window, window, hidden, 0, 0, 0, 1.0f);
+    orc_vad_head(hid.data(), n, hidden, w2.data(), b2.data(), prob);
 }
 
 typedef struct {

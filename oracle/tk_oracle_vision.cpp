@@ -19,14 +19,17 @@
 #include <algorithm>
 #include <vector>
 
+#include "../trackiellm_amd/csrc/common/tk_box_attr.h"
 #include "../trackiellm_amd/csrc/common/tk_ggml_blocks.h"
 #include "../trackiellm_amd/csrc/common/tk_yolo_post.h"
 #include "../trackiellm_amd/csrc/common/tk_yolov8n_graph.h"
 
 extern "C" {
 
-int orc_preprocess(const uint8_t* data, uint32_t w, uint32_t h, uint32_t stride, uint32_t bpp, float* out, uint32_t tw, uint32_t th,
-                   const float* mean, const float* std_dev, int nhwc) {
+/* scale 1/255 (or 0, "unset"): the reference's own v / 255; any other value: v * scale, the HAL's multiply-by-scale variant */
+int orc_preprocess_scaled(const uint8_t* data, uint32_t w, uint32_t h, uint32_t stride, uint32_t bpp, float* out, uint32_t tw, uint32_t th,
+                          const float* mean, const float* std_dev, int nhwc, float scale) {
+    const bool canonical = scale == 1.0f / 255.0f || scale == 0.0f;
     if (!data || !out || tw == 0 || th == 0) return 1001;
     const float x_ratio = ((float)w - 1.0f) / (float)tw;
     const float y_ratio = ((float)h - 1.0f) / (float)th;
@@ -44,13 +47,71 @@ int orc_preprocess(const uint8_t* data, uint32_t w, uint32_t h, uint32_t stride,
                 v = v + (p2 * xd) * (1.0f - yd);
                 v = v + (p3 * (1.0f - xd)) * yd;
                 v = v + (p4 * xd) * yd;
-                const float o = (v / 255.0f - mean[c]) / std_dev[c];
+                const float o = ((canonical ? v / 255.0f : v * scale) - mean[c]) / std_dev[c];
                 if (nhwc) out[((size_t)oy * tw + ox) * 3 + c] = o;
                 else out[c * np + (size_t)oy * tw + ox] = o;
             }
         }
     return 0;
 }
+
+int orc_preprocess(const uint8_t* data, uint32_t w, uint32_t h, uint32_t stride, uint32_t bpp, float* out, uint32_t tw, uint32_t th,
+                   const float* mean, const float* std_dev, int nhwc) {
+    return orc_preprocess_scaled(data, w, h, stride, bpp, out, tw, th, mean, std_dev, nhwc, 1.0f / 255.0f);
+}
+
+/* ---- the depth stream's element-wise steps (src/vision/tk_depth_midas.c:471-499, src/gpu/rocm/tk_rocm_kernels.cpp:148-202) ---- */
+void orc_depth_minmax(const float* x, int64_t n, float* mm) {
+    float lo = x[0], hi = x[0];
+    for (int64_t i = 1; i < n; ++i) { if (x[i] < lo) lo = x[i]; if (x[i] > hi) hi = x[i]; }
+    mm[0] = lo; mm[1] = hi;
+}
+void orc_depth_metric(const float* x, int64_t n, float min_depth, float max_depth, float* y, float* mm) {
+    orc_depth_minmax(x, n, mm);
+    const float lo = mm[0], range = mm[1] - mm[0];
+    for (int64_t i = 0; i < n; ++i) {
+        if (range < 1e-6f) { y[i] = max_depth; continue; }
+        const float normalized = tk_divf(x[i] - lo, range);
+        y[i] = max_depth - normalized * (max_depth - min_depth);
+    }
+}
+void orc_postprocess_depth(const float* raw, int64_t n, float scale, float shift, float* out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = raw[i] * scale + shift;
+}
+void orc_depth_to_points(const float* depth, uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, float* xyz) {
+    for (uint32_t v = 0; v < height; ++v)
+        for (uint32_t u = 0; u < width; ++u) {
+            const size_t i = (size_t)v * width + u;
+            const float d = depth[i];
+            float x = 0.0f, y = 0.0f, z = 0.0f;
+            if (d > 0.0f) { x = tk_divf(((float)u - cx) * d, fx); y = tk_divf(((float)v - cy) * d, fy); z = d; }
+            xyz[3 * i] = x; xyz[3 * i + 1] = y; xyz[3 * i + 2] = z;
+        }
+}
+
+/* ---- the per-box attribute classifiers (src/vision/tk_attribute_classifier.c) on the shared per-pixel arithmetic; out [n][2] = {bin, closed}.
+ * Row by row over the box as the reference walks it; out-of-frame pixels are skipped in both loops ---- */
+void orc_box_attributes(const uint8_t* frame, int W, int H, int n, const int32_t* rects, int32_t* out) {
+    for (int k = 0; k < n; ++k) {
+        const int bx = rects[4 * k], by = rects[4 * k + 1], bw = rects[4 * k + 2], bh = rects[4 * k + 3];
+        long bins[9] = {0};
+        int edges = 0;
+        for (int64_t y = by; y < (int64_t)by + bh; ++y)
+            for (int64_t x = bx; x < (int64_t)bx + bw; ++x) {
+                if (x < 0 || x >= W || y < 0 || y >= H) continue;
+                const uint8_t* p = frame + (y * W + x) * 3;
+                const int c = tk_color_bin(p[0], p[1], p[2]);
+                if (c >= 0) bins[c]++;
+                if (x > bx && x < (int64_t)bx + bw - 1 && y > by && y < (int64_t)by + bh - 1 && y >= 1 && y < H - 1 && tk_edge_between(p - (int64_t)W * 3, p + (int64_t)W * 3))
+                    edges++;
+            }
+        int best = 0;
+        for (int i = 1; i < 9; ++i) if (bins[i] > bins[best]) best = i;
+        out[2 * k] = best;
+        out[2 * k + 1] = tk_door_closed(edges, bw, bh);
+    }
+}
+int orc_color_bin(uint8_t r, uint8_t g, uint8_t b) { return tk_color_bin(r, g, b); }
 
 struct orc_yolo {
     int nc;

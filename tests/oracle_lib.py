@@ -712,3 +712,89 @@ def pick_row(logits, temperature=0.0, seed=0, counter=0, want_logprob=True):
     L.orc_pick_row.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]
     tok = L.orc_pick_row(ptr(logits), logits.size, temperature, seed, counter, C.byref(lp) if want_logprob else None)
     return int(tok), (np.float32(lp.value) if want_logprob else None)
+
+
+# ---- the perception front- and back-end steps alone (tests/edge_cases.py: reference A) ----
+def frames(pcm, B, n_samples, pcm_stride, n_total, T, window, out):
+    """CpuAudioOps::frames on pcm int16 [B] rows pcm_stride apart; out: float32 [B T 400] with the caller's content, a copy is written and returned"""
+    pcm, window = np.ascontiguousarray(pcm, np.int16).reshape(-1), _f32(window)
+    y = np.array(out, np.float32, order="C", copy=True)
+    lib().orc_frames.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 2
+    lib().orc_frames(ptr(pcm), B, n_samples, pcm_stride, n_total, T, ptr(window), ptr(y))
+    return y
+
+
+def power(ri, rows, nb, out):
+    ri, y = _f32(ri), np.array(out, np.float32, order="C", copy=True)
+    lib().orc_power.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib().orc_power(ptr(ri), rows, nb, ptr(y))
+    return y
+
+
+def logmel_finish(mel, B, per_b):
+    y = np.array(mel, np.float32, order="C", copy=True)
+    lib().orc_logmel_finish.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib().orc_logmel_finish(ptr(y), B, per_b)
+    return y
+
+
+def log10f(x):
+    """tk_log10f element by element"""
+    x = _f32(x)
+    y = np.empty_like(x)
+    lib().orc_log10f_n.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    lib().orc_log10f_n(ptr(x), x.size, ptr(y))
+    return y
+
+
+def vad_head(hid, n, hidden, w2, b2, out):
+    hid, w2, b2 = _f32(hid), _f32(w2), _f32(b2)
+    y = np.array(out, np.float32, order="C", copy=True)
+    lib().orc_vad_head.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib().orc_vad_head(ptr(hid), n, hidden, ptr(w2), ptr(b2), ptr(y))
+    return y
+
+
+def preprocess_scaled(src, in_w, in_h, stride, bpp, out, out_w, out_h, mean, std, nhwc, scale):
+    """orc_preprocess_scaled on a flat uint8 buffer; out: float32 with the caller's content, a copy is written and returned"""
+    src, mean, std = np.ascontiguousarray(src, np.uint8).reshape(-1), _f32(mean), _f32(std)
+    y = np.array(out, np.float32, order="C", copy=True)
+    lib().orc_preprocess_scaled.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_float]
+    assert lib().orc_preprocess_scaled(ptr(src), in_w, in_h, stride, bpp, ptr(y), out_w, out_h, ptr(mean), ptr(std), int(nhwc), scale) == 0
+    return y
+
+
+def depth_minmax(x):
+    x, mm = _f32(x), np.zeros(2, np.float32)
+    lib().orc_depth_minmax.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    lib().orc_depth_minmax(ptr(x), x.size, ptr(mm))
+    return mm
+
+
+def depth_metric(x, min_depth, max_depth, out):
+    x, y, mm = _f32(x), np.array(out, np.float32, order="C", copy=True), np.zeros(2, np.float32)
+    lib().orc_depth_metric.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    lib().orc_depth_metric(ptr(x), x.size, min_depth, max_depth, ptr(y), ptr(mm))
+    return y, mm
+
+
+def postprocess_depth(raw, scale, shift, out):
+    raw, y = _f32(raw), np.array(out, np.float32, order="C", copy=True)
+    lib().orc_postprocess_depth.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]
+    lib().orc_postprocess_depth(ptr(raw), raw.size, scale, shift, ptr(y))
+    return y
+
+
+def depth_to_points(depth, width, height, fx, fy, cx, cy, out):
+    depth, y = _f32(depth), np.array(out, np.float32, order="C", copy=True)
+    lib().orc_depth_to_points.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_float] * 4 + [C.c_void_p]
+    lib().orc_depth_to_points(ptr(depth), width, height, fx, fy, cx, cy, ptr(y))
+    return y
+
+
+def box_attributes(frame, W, H, rects, out):
+    frame, rects = np.ascontiguousarray(frame, np.uint8).reshape(-1), np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+    y = np.array(out, np.int32, order="C", copy=True)
+    lib().orc_box_attributes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib().orc_box_attributes(ptr(frame), W, H, len(rects), ptr(rects), ptr(y))
+    return y

@@ -15,6 +15,7 @@ from .vision import ObjectDetector, VisionPipeline, classify_attributes, preproc
 from .vision import DepthEstimator, depth_onnx_probe, fuse_data, fusion_reset, fusion_raw_distance  # noqa: F401,E402
 from .vision import onnx_run, detector_post_probe, DetectorPostProbe, BOX_DTYPE, YOLO_MAX_CAND, YOLO_MAX_DET  # noqa: F401,E402
 from .nn import GemmProbe, gemm_probe, gemm_code, attention_h3_probe, GEMM_F32, GEMM_F32_TALL, GEMM_F32_BIG, GEMM_H3_TALL, GEMM_H3_BIG  # noqa: F401,E402
+from .nn import EdgeProbe, edge_probe, EDGE_FRAMES, EDGE_POWER, EDGE_LOGMEL_FINISH, EDGE_VAD_HEAD, EDGE_PREPROCESS, EDGE_DEPTH_MINMAX, EDGE_DEPTH_METRIC, EDGE_POSTPROCESS_DEPTH, EDGE_DEPTH_TO_POINTS, EDGE_BOX_ATTRIBUTES, PREPROCESS_CANONICAL, PREPROCESS_SCALED  # noqa: F401,E402
 from .nn import NnRowProbe, nn_row_probe, ROW_CONV_STEM, ROW_IM2COL, ROW_IM2COL1D, ROW_MAXPOOL5, ROW_UPSAMPLE2X, ROW_COPY_COLS, ROW_LAYERNORM, ROW_SOFTMAX_ROWS, ROW_ADD_ROWS, ROW_EMBED_ROWS, ROW_ATTEND1  # noqa: F401,E402
 from .nn import SOFTMAX_GENERIC, SOFTMAX_REG, SOFTMAX_WAVE, IM2COL_ELEMENT, IM2COL_V4  # noqa: F401,E402
 from .pick import LogitAdjust, logit_adjust_rows, logit_adjust_probe, logit_adjust_probe_into, lang_pick_probe  # noqa: F401,E402

@@ -23,6 +23,14 @@ bool tk_attend1_ok(const float* k, const float* v, int B, int Tk, int64_t q_bstr
 bool tk_launch_attend1(const float* q, const float* k, const float* v, float* out, int B, int Tk, int64_t q_bstride, int64_t kv_bstride, int d, int nh, float* img,
                        hipStream_t s);
 
+/* the log-mel front end's three kernels and the VAD's second layer as free launchers (grid arithmetic in one place; the engines and the edge
+ * probe call these).  frames: pcm [B] rows pcm_stride samples apart -> out [B][T][TK_WH_NFFT], window [TK_WH_NFFT]; power: ri [rows][2 nb]
+ * (re | im) -> out [rows][nb]; logmel_finish: mel [B][per_b] in place, one workgroup per utterance; vad_head: hid [n][hidden] -> prob [n]. */
+void tk_launch_frames(const int16_t* pcm, int B, int n_samples, int pcm_stride, int n_total, int T, const float* window, float* out, hipStream_t s);
+void tk_launch_power(const float* ri, int rows, int nb, float* out, hipStream_t s);
+void tk_launch_logmel_finish(float* mel, int B, int per_b, hipStream_t s);
+void tk_launch_vad_head(const float* hid, int n, int hidden, const float* w2, const float* b2, float* prob, hipStream_t s);
+
 class TkWhisperModel {
 public:
     TkWhisperHP hp{};

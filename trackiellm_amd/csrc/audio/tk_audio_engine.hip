@@ -71,6 +71,16 @@ __global__ __launch_bounds__(1024) void k_logmel_finish(float* mel, int per_b) {
     for (int i = threadIdx.x; i < per_b; i += 1024) m[i] = (tk_fmaxf(m[i], floor_v) + 4.0f) * 0.25f;
 }
 
+void tk_launch_frames(const int16_t* pcm, int B, int n_samples, int pcm_stride, int n_total, int T, const float* window, float* out, hipStream_t s) {
+    const int64_t per = (int64_t)T * TK_WH_NFFT;
+    hipLaunchKernelGGL(k_frames, dim3((unsigned)((per + 255) / 256), 1, B), dim3(256), 0, s, pcm, n_samples, pcm_stride, n_total, T, window, out);
+}
+void tk_launch_power(const float* ri, int rows, int nb, float* out, hipStream_t s) {
+    const int64_t n = (int64_t)rows * nb;
+    hipLaunchKernelGGL(k_power, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ri, (int64_t)rows, nb, out);
+}
+void tk_launch_logmel_finish(float* mel, int B, int per_b, hipStream_t s) { hipLaunchKernelGGL(k_logmel_finish, dim3(B), dim3(1024), 0, s, mel, per_b); }
+
 
 /* ---------------------------------------------------------------- decoder-step attention, fused
 
@@ -381,15 +391,10 @@ struct TkAudioGpuOps {
     }
     void frames(const int16_t* pcm, int B, int n_samples, int pcm_stride, int n_total, int T, const float* window, float* out) {
         drop_image();
-        const int64_t per = (int64_t)T * TK_WH_NFFT;
-        hipLaunchKernelGGL(k_frames, dim3((unsigned)((per + 255) / 256), 1, B), dim3(256), 0, s, pcm, n_samples, pcm_stride, n_total, T, window, out);
+        tk_launch_frames(pcm, B, n_samples, pcm_stride, n_total, T, window, out, s);
     }
-    void power(const float* ri, int rows, int nb, float* out) {
-        drop_image();
-        const int64_t n = (int64_t)rows * nb;
-        hipLaunchKernelGGL(k_power, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ri, (int64_t)rows, nb, out);
-    }
-    void logmel_finish(float* mel, int B, int per_b) { drop_image(); hipLaunchKernelGGL(k_logmel_finish, dim3(B), dim3(1024), 0, s, mel, per_b); }
+    void power(const float* ri, int rows, int nb, float* out) { drop_image(); tk_launch_power(ri, rows, nb, out, s); }
+    void logmel_finish(float* mel, int B, int per_b) { drop_image(); tk_launch_logmel_finish(mel, B, per_b, s); }
 };
 
 /* sizing twin of the ops (counts arena floats for a given batch) */
@@ -827,6 +832,9 @@ __global__ void k_vad_head(const float* hid, int n, int hidden, const float* w2,
     for (int k = 0; k < hidden; ++k) acc = tk_fmaf(tk_fmaxf(hid[(int64_t)i * hidden + k], 0.0f), w2[k], acc);
     prob[i] = tk_sigmoidf(acc + b2[0]);
 }
+void tk_launch_vad_head(const float* hid, int n, int hidden, const float* w2, const float* b2, float* prob, hipStream_t s) {
+    hipLaunchKernelGGL(k_vad_head, dim3((n + 63) / 64), dim3(64), 0, s, hid, n, hidden, w2, b2, prob);
+}
 
 bool TkVadModel::infer(const float* windows_host, int n, float* prob_host) {
     if (n <= 0) return true;
@@ -849,7 +857,7 @@ bool TkVadModel::infer(const float* windows_host, int n, float* prob_host) {
     g.A = x; g.B = w1; g.C = hbuf; g.bias = b1; g.M = n; g.N = hidden; g.K = window; g.lda = window; g.ldb = window; g.ldc = hidden;
     g.alpha = 1.0f; g.batch = 1;
     tk_launch_gemm(g, stream);
-    hipLaunchKernelGGL(k_vad_head, dim3((n + 63) / 64), dim3(64), 0, stream, hbuf, n, hidden, w2, b2, p);
+    tk_launch_vad_head(hbuf, n, hidden, w2, b2, p, stream);
     HIPQ(hipGetLastError());
     HIPQ(hipMemcpyAsync(prob_host, p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
     HIPQ(hipStreamSynchronize(stream));

@@ -13,6 +13,7 @@
 #include "tk/tk_mi355x_ext.h"
 
 #include "../vision/tk_vision_engine.h"
+#include "../vision/tk_depth_engine.h"
 #include "../audio/tk_audio_engine.h"
 #include "tk/tk_rocm_hal.h"
 #include "../nn/tk_gemm_tiled.h"
@@ -70,8 +71,28 @@ __global__ void k_preprocess_scaled(TkPreprocessArgs a, float scale) {
         v = v + ((float)r0[x1 * a.bpp + c] * xd) * (1.0f - yd);
         v = v + ((float)r1[x * a.bpp + c] * (1.0f - xd)) * yd;
         v = v + ((float)r1[x1 * a.bpp + c] * xd) * yd;
-        a.dst[c * np + pix] = tk_divf(v * scale - a.mean[c], a.std_dev[c]);
+        const float o = tk_divf(v * scale - a.mean[c], a.std_dev[c]);
+        if (a.nhwc) a.dst[pix * 3 + c] = o;
+        else a.dst[c * np + pix] = o;
     }
+}
+
+/* the pre-processor for a given scale: 1/255 (or 0, "unset") is the canonical kernel's own division by 255, any other value the multiply-by-scale
+ * variant.  Returns the choice: 0 k_preprocess, 1 k_preprocess_scaled; with dry, the choice alone */
+static int launch_preprocess_for_scale(const TkPreprocessArgs& a, float scale, hipStream_t s, bool dry) {
+    if (scale == 1.0f / 255.0f || scale == 0.0f) {
+        if (!dry) tk_launch_preprocess(a, s);
+        return 0;
+    }
+    if (!dry) hipLaunchKernelGGL(k_preprocess_scaled, dim3((a.out_w + 63) / 64, (a.out_h + 3) / 4), dim3(64, 4), 0, s, a, scale);
+    return 1;
+}
+
+/* the two element-wise depth kernels' grid: one thread per element up to TK_DEPTH_GRID_CAP blocks of 256, a grid-stride loop beyond */
+#define TK_DEPTH_GRID_CAP 2048
+static unsigned depth_grid_blocks(size_t n) {
+    const size_t blocks = (n + 255) / 256;
+    return (unsigned)(blocks > TK_DEPTH_GRID_CAP ? TK_DEPTH_GRID_CAP : blocks);
 }
 
 static tk_error_code_t launch_status() { return hipGetLastError() == hipSuccess ? TK_SUCCESS : TK_ERROR_GPU_KERNEL_LAUNCH; }
@@ -86,8 +107,7 @@ tk_error_code_t tk_kernels_preprocess_image(const tk_preprocess_params_t* p, tk_
     a.dst = p->d_output_tensor; a.out_w = p->output_width; a.out_h = p->output_height; a.nhwc = 0;
     a.mean[0] = p->mean.x; a.mean[1] = p->mean.y; a.mean[2] = p->mean.z;
     a.std_dev[0] = p->std_dev.x; a.std_dev[1] = p->std_dev.y; a.std_dev[2] = p->std_dev.z;
-    if (p->scale == 1.0f / 255.0f || p->scale == 0.0f) tk_launch_preprocess(a, (hipStream_t)stream);
-    else hipLaunchKernelGGL(k_preprocess_scaled, dim3((a.out_w + 63) / 64, (a.out_h + 3) / 4), dim3(64, 4), 0, (hipStream_t)stream, a, p->scale);
+    (void)launch_preprocess_for_scale(a, p->scale, (hipStream_t)stream, false);
     return launch_status();
 }
 
@@ -103,10 +123,7 @@ tk_error_code_t tk_kernels_preprocess_image_generic(const tk_preprocess_params_g
 
 tk_error_code_t tk_kernels_postprocess_depth_map(const tk_postprocess_depth_params_t* p, tk_hip_stream_t stream) {
     if (!p || !p->d_raw_depth_map || !p->d_metric_depth_map || p->width == 0 || p->height == 0) return TK_ERROR_INVALID_ARGUMENT;
-    const size_t n = (size_t)p->width * p->height;
-    size_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_postprocess_depth, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *p);
+    hipLaunchKernelGGL(k_postprocess_depth, dim3(depth_grid_blocks((size_t)p->width * p->height)), dim3(256), 0, (hipStream_t)stream, *p);
     return launch_status();
 }
 
@@ -679,6 +696,165 @@ tk_error_code_t tk_mi355x_nn_row_probe(int device, tk_mi355x_nn_row_probe_t* p) 
     return rc;
 }
 
+/* elements each array of an edge-probe launch must hold (0: not used) and the bytes of one element, from the kernels' own index expressions;
+ * false: a geometry no launch may have */
+struct EdgeReach { int64_t a, b, c, y, y2; int sa, sb, sy; };
+static bool edge_probe_reach(const tk_mi355x_edge_probe_t& p, EdgeReach& o) {
+    const int64_t cap = (int64_t)1 << 20, big = (int64_t)1 << 28;
+    auto dim = [&](int64_t v) { return v >= 1 && v <= cap; };
+    auto finite = [](float v) { return v - v == 0.0f; };
+    o = EdgeReach{0, 0, 0, 0, 0, 4, 4, 4};
+    switch (p.op) {
+    case TK_MI355X_EDGE_FRAMES: {
+        /* taps run from -NFFT/2 to (T - 1) HOP + NFFT/2 - 1: one reflection at either end must land inside [0, n_total) */
+        if (p.B < 1 || p.B > 65535 || !dim(p.T) || p.n_total <= TK_WH_NFFT / 2 || p.n_total > (1 << 24) || p.n_samples < 1 || p.n_samples > p.n_total || p.pcm_stride < p.n_samples ||
+            p.pcm_stride > (1 << 24))
+            return false;
+        const int64_t last = ((int64_t)p.T - 1) * TK_WH_HOP + TK_WH_NFFT - 1 - TK_WH_NFFT / 2;
+        if (last > 2 * ((int64_t)p.n_total - 1)) return false;
+        o.a = ((int64_t)p.B - 1) * p.pcm_stride + p.n_samples; o.sa = 2;
+        o.b = TK_WH_NFFT;
+        o.y = (int64_t)p.B * p.T * TK_WH_NFFT;
+        return o.a <= big && o.y <= big;
+    }
+    case TK_MI355X_EDGE_POWER:
+        if (!dim(p.rows) || !dim(p.nb) || (int64_t)p.rows * p.nb * 2 > big) return false;
+        o.a = (int64_t)p.rows * p.nb * 2; o.y = (int64_t)p.rows * p.nb;
+        return true;
+    case TK_MI355X_EDGE_LOGMEL_FINISH:
+        if (p.B < 1 || p.B > 65535 || !dim(p.per_b) || (int64_t)p.B * p.per_b > big) return false;
+        o.y = (int64_t)p.B * p.per_b;
+        return true;
+    case TK_MI355X_EDGE_VAD_HEAD:
+        if (!dim(p.rows) || !dim(p.hidden) || (int64_t)p.rows * p.hidden > big) return false;
+        o.a = (int64_t)p.rows * p.hidden; o.b = p.hidden; o.c = 1; o.y = p.rows;
+        return true;
+    case TK_MI355X_EDGE_PREPROCESS: {
+        if (p.in_w < 2 || p.in_w > cap || p.in_h < 2 || p.in_h > cap || !dim(p.out_w) || p.out_h < 1 || p.out_h > (1 << 18) || (p.bpp != 3 && p.bpp != 4) || (p.nhwc != 0 && p.nhwc != 1) ||
+            p.in_stride < (int64_t)p.in_w * p.bpp || p.in_stride > (1 << 24) || !finite(p.scale))
+            return false;
+        /* the last tap: row in_h - 1, pixel in_w - 1, channel 2 */
+        o.a = ((int64_t)p.in_h - 1) * p.in_stride + ((int64_t)p.in_w - 1) * p.bpp + 3; o.sa = 1;
+        o.y = 3 * (int64_t)p.out_w * p.out_h;
+        return o.a <= big && o.y <= big;
+    }
+    case TK_MI355X_EDGE_DEPTH_MINMAX:
+    case TK_MI355X_EDGE_DEPTH_METRIC:
+        if (p.n < 1 || p.n > big) return false;
+        o.a = p.n;
+        if (p.op == TK_MI355X_EDGE_DEPTH_MINMAX) o.y = 2;
+        else { o.y = p.n; o.y2 = 2; }
+        return true;
+    case TK_MI355X_EDGE_POSTPROCESS_DEPTH:
+    case TK_MI355X_EDGE_DEPTH_TO_POINTS: {
+        if (!dim(p.width) || !dim(p.height) || (int64_t)p.width * p.height * 3 > big) return false;
+        const int64_t n = (int64_t)p.width * p.height;
+        o.a = n;
+        o.y = p.op == TK_MI355X_EDGE_DEPTH_TO_POINTS ? 3 * n : n;
+        return true;
+    }
+    case TK_MI355X_EDGE_BOX_ATTRIBUTES:
+        if (!dim(p.in_w) || !dim(p.in_h) || !dim(p.rows) || (int64_t)p.in_w * p.in_h * 3 > big) return false;
+        o.a = (int64_t)p.in_w * p.in_h * 3; o.sa = 1;
+        o.b = 4 * (int64_t)p.rows;
+        o.y = 2 * (int64_t)p.rows;
+        return true;
+    default: return false;
+    }
+}
+
+/* the launch itself (or, with dry, the launcher's answer alone) on the given bases; false: the launcher refuses */
+static bool edge_probe_launch(tk_mi355x_edge_probe_t& p, const void* a, const void* b, const void* c, void* y, void* y2, bool dry) {
+    p.kernel = 0;
+    switch (p.op) {
+    case TK_MI355X_EDGE_FRAMES:
+        if (!dry) tk_launch_frames((const int16_t*)a, p.B, p.n_samples, p.pcm_stride, p.n_total, p.T, (const float*)b, (float*)y, nullptr);
+        return true;
+    case TK_MI355X_EDGE_POWER:
+        if (!dry) tk_launch_power((const float*)a, p.rows, p.nb, (float*)y, nullptr);
+        return true;
+    case TK_MI355X_EDGE_LOGMEL_FINISH:
+        if (!dry) tk_launch_logmel_finish((float*)y, p.B, p.per_b, nullptr);
+        return true;
+    case TK_MI355X_EDGE_VAD_HEAD:
+        if (!dry) tk_launch_vad_head((const float*)a, p.rows, p.hidden, (const float*)b, (const float*)c, (float*)y, nullptr);
+        return true;
+    case TK_MI355X_EDGE_PREPROCESS: {
+        TkPreprocessArgs g{};
+        g.src = (const uint8_t*)a; g.in_w = (uint32_t)p.in_w; g.in_h = (uint32_t)p.in_h; g.in_stride = (uint32_t)p.in_stride; g.bpp = (uint32_t)p.bpp;
+        g.dst = (float*)y; g.out_w = (uint32_t)p.out_w; g.out_h = (uint32_t)p.out_h; g.nhwc = p.nhwc;
+        for (int i = 0; i < 3; ++i) { g.mean[i] = p.mean[i]; g.std_dev[i] = p.std_dev[i]; }
+        p.kernel = launch_preprocess_for_scale(g, p.scale, nullptr, dry);
+        return true;
+    }
+    case TK_MI355X_EDGE_DEPTH_MINMAX:
+        if (!dry) tk_launch_depth_minmax((const float*)a, p.n, (float*)y, nullptr);
+        return true;
+    case TK_MI355X_EDGE_DEPTH_METRIC: /* as TkDepthEngine::to_metric: the two launches in stream order */
+        if (!dry) {
+            tk_launch_depth_minmax((const float*)a, p.n, (float*)y2, nullptr);
+            tk_launch_depth_metric((const float*)a, (const float*)y2, p.min_depth, p.max_depth, (float*)y, p.n, nullptr);
+        }
+        return true;
+    case TK_MI355X_EDGE_POSTPROCESS_DEPTH: {
+        const tk_postprocess_depth_params_t q{(const float*)a, (uint32_t)p.width, (uint32_t)p.height, (float*)y, p.scale, p.shift};
+        p.kernel = (int32_t)depth_grid_blocks((size_t)p.width * p.height);
+        return dry || tk_kernels_postprocess_depth_map(&q, nullptr) == TK_SUCCESS;
+    }
+    case TK_MI355X_EDGE_DEPTH_TO_POINTS: {
+        const tk_depth_to_points_params_t q{(const float*)a, (uint32_t)p.width, (uint32_t)p.height, (tk_float3*)y, p.fx, p.fy, p.cx, p.cy};
+        p.kernel = (int32_t)depth_grid_blocks((size_t)p.width * p.height);
+        if (p.fx == 0.0f || p.fy == 0.0f) { p.kernel = -1; return false; } /* the launcher's own refusal */
+        return dry || tk_kernels_depth_to_point_cloud(&q, nullptr) == TK_SUCCESS;
+    }
+    case TK_MI355X_EDGE_BOX_ATTRIBUTES:
+        if (!dry) tk_launch_box_attributes((const uint8_t*)a, p.in_w, p.in_h, p.rows, (const int32_t*)b, (int32_t*)y, nullptr);
+        return true;
+    default: return false;
+    }
+}
+
+tk_error_code_t tk_mi355x_edge_probe(int device, tk_mi355x_edge_probe_t* p) {
+    static_assert(sizeof(tk_float3) == 12, "a point is three packed floats");
+    if (!p) return TK_ERROR_INVALID_ARGUMENT;
+    p->kernel = -1;
+    EdgeReach need;
+    if (!edge_probe_reach(*p, need)) return TK_ERROR_INVALID_ARGUMENT;
+    /* an array the op uses must be there and long enough; one it does not use must be absent */
+    auto fits = [](const void* ptr, int64_t n, int64_t want) { return want == 0 ? (ptr == nullptr && n == 0) : (ptr != nullptr && n >= want); };
+    if (!fits(p->a, p->n_a, need.a) || !fits(p->b, p->n_b, need.b) || !fits(p->c, p->n_c, need.c) || !fits(p->y, p->n_y, need.y) || !fits(p->y2, p->n_y2, need.y2))
+        return TK_ERROR_INVALID_ARGUMENT;
+    if (p->op == TK_MI355X_EDGE_BOX_ATTRIBUTES) { /* a test hook: boxes a launch walks in no time (the public entry points take any rectangle, ABI_NOTES.md) */
+        const int32_t* r = (const int32_t*)p->b;
+        const int32_t far = 1 << 30, wide = 1 << 20;
+        for (int i = 0; i < p->rows; ++i) {
+            const int32_t bx = r[4 * i], by = r[4 * i + 1], bw = r[4 * i + 2], bh = r[4 * i + 3];
+            if (bx < -far || bx > far || by < -far || by > far || bw < -wide || bw > wide || bh < -wide || bh > wide) return TK_ERROR_INVALID_ARGUMENT;
+            if (bw > 0 && bh > 0 && (int64_t)bw * bh > ((int64_t)1 << 24)) return TK_ERROR_INVALID_ARGUMENT;
+        }
+    }
+    if (device < 0) {
+        const void* aligned = (const void*)(uintptr_t)256;
+        return edge_probe_launch(*p, aligned, aligned, aligned, (void*)(uintptr_t)256, (void*)(uintptr_t)256, true) ? TK_SUCCESS : TK_ERROR_INVALID_ARGUMENT;
+    }
+    { tk_mi355x_edge_probe_t dry = *p; /* what the launcher refuses is refused before the device is touched */
+      if (!edge_probe_launch(dry, p->a, p->b, p->c, p->y, p->y2, true)) { p->kernel = dry.kernel; return TK_ERROR_INVALID_ARGUMENT; } }
+    tk_error_code_t rc = probe_device(device);
+    if (rc != TK_SUCCESS) return rc;
+    enum { A, Bm, Cm, Y, Y2, NBUF };
+    ProbeBuf b[NBUF] = {{p->a, (size_t)p->n_a * need.sa, 0, false, nullptr}, {p->b, (size_t)p->n_b * need.sb, 0, false, nullptr},
+                        {p->c, (size_t)p->n_c * 4, 0, false, nullptr}, {p->y, (size_t)p->n_y * need.sy, 0, true, nullptr},
+                        {p->y2, (size_t)p->n_y2 * 4, 0, true, nullptr}};
+    if (!probe_upload(b, NBUF)) rc = TK_ERROR_GPU_ROCM_ERROR;
+    else {
+        if (!edge_probe_launch(*p, b[A].dev, b[Bm].dev, b[Cm].dev, b[Y].dev, b[Y2].dev, false)) rc = TK_ERROR_INVALID_ARGUMENT;
+        else if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess || !probe_download(b, NBUF)) rc = TK_ERROR_GPU_ROCM_ERROR;
+    }
+    probe_free(b, NBUF);
+    return rc;
+}
+
 tk_error_code_t tk_mi355x_detector_post_probe(int device, tk_mi355x_detector_post_probe_t* p) {
     static_assert(sizeof(tk_mi355x_box_t) == sizeof(tk_yolo_cand_t) && sizeof(tk_mi355x_box_t) == sizeof(TkDetection), "the public record is the kernels' candidate and detection");
     if (!p || (p->kind != 0 && p->kind != 1) || p->B < 1 || p->B > 256 || p->nc < 1 || p->nc > 4096 || p->n_anchors < 1 || p->n_anchors > (1 << 20))
@@ -742,10 +918,7 @@ tk_error_code_t tk_mi355x_detector_post_probe(int device, tk_mi355x_detector_pos
 tk_error_code_t tk_kernels_depth_to_point_cloud(const tk_depth_to_points_params_t* p, tk_hip_stream_t stream) {
     if (!p || !p->d_metric_depth_map || !p->d_point_cloud || p->width == 0 || p->height == 0 || p->fx == 0.0f || p->fy == 0.0f)
         return TK_ERROR_INVALID_ARGUMENT;
-    const size_t n = (size_t)p->width * p->height;
-    size_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_depth_to_points, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *p);
+    hipLaunchKernelGGL(k_depth_to_points, dim3(depth_grid_blocks((size_t)p->width * p->height)), dim3(256), 0, (hipStream_t)stream, *p);
     return launch_status();
 }
 

@@ -19,6 +19,11 @@
 #define TK_DEPTH_MIN_M 0.1f  /* src/vision/tk_depth_midas.c:46-47 */
 #define TK_DEPTH_MAX_M 10.0f
 
+/* the metric conversion's two kernels as free launchers (the engine and the edge probe call these): mm [2] = {min, max} of x [n], n >= 1, by one
+ * 1024-thread workgroup; y [n] = max_depth - (x - min) / (max - min) * (max_depth - min_depth), max_depth everywhere when max - min < 1e-6 */
+void tk_launch_depth_minmax(const float* x, int64_t n, float* mm, hipStream_t s);
+void tk_launch_depth_metric(const float* x, const float* mm, float min_depth, float max_depth, float* y, int64_t n, hipStream_t s);
+
 class TkDepthEngine {
 public:
     std::string error;

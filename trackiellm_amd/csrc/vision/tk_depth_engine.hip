@@ -43,6 +43,11 @@ __global__ void k_depth_metric(const float* x, const float* mm, float min_depth,
     y[i] = max_depth - normalized * (max_depth - min_depth);
 }
 
+void tk_launch_depth_minmax(const float* x, int64_t n, float* mm, hipStream_t s) { hipLaunchKernelGGL(k_depth_minmax, dim3(1), dim3(1024), 0, s, x, n, mm); }
+void tk_launch_depth_metric(const float* x, const float* mm, float min_depth, float max_depth, float* y, int64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(k_depth_metric, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, mm, min_depth, max_depth, y, n);
+}
+
 TkDepthEngine::~TkDepthEngine() {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
@@ -104,8 +109,8 @@ bool TkDepthEngine::run_network(const float** raw_dev) {
 }
 
 bool TkDepthEngine::to_metric(const float* raw_dev, float* metric_dev, int64_t n) {
-    hipLaunchKernelGGL(k_depth_minmax, dim3(1), dim3(1024), 0, stream_, raw_dev, n, mm_dev_);
-    hipLaunchKernelGGL(k_depth_metric, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, raw_dev, mm_dev_, TK_DEPTH_MIN_M, TK_DEPTH_MAX_M, metric_dev, n);
+    tk_launch_depth_minmax(raw_dev, n, mm_dev_, stream_);
+    tk_launch_depth_metric(raw_dev, mm_dev_, TK_DEPTH_MIN_M, TK_DEPTH_MAX_M, metric_dev, n, stream_);
     DQ(hipGetLastError());
     return true;
 }

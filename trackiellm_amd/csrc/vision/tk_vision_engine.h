@@ -42,6 +42,10 @@ bool tk_launch_yolo_decode_out(const float* out, int nc, int n_anchors, float co
 bool tk_launch_yolo_post(const tk_yolo_cand_t* cand, int n_anchors, int B, float iou, int32_t* order, int32_t* n_cand, uint64_t* mask, TkDetection* kept,
                          int32_t* n_kept, hipStream_t s);
 
+/* k_box_attributes as a free launcher (the detector, the host entry point and the edge probe call it): one workgroup per box; frame tightly packed
+ * RGB8 [H][W][3], rects [n][4] = {x, y, w, h}, out [n][2] = {colour bin, door closed}; n >= 1 */
+void tk_launch_box_attributes(const uint8_t* frame, int W, int H, int n, const int32_t* rects, int32_t* out, hipStream_t s);
+
 class TkYoloModel {
 public:
     int device = 0, nc = TK_YOLO_NC;

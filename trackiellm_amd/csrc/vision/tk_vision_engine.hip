@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "../common/tk_box_attr.h"
 #include "../nn/tk_nn_kernels.h"
 
 /* Perception streams run at the highest stream priority: their kernels are small and many, and behind the LLM's large GEMM
@@ -541,42 +542,13 @@ bool TkDetector::detect(int B, const uint8_t* const* frames, uint32_t w, uint32_
 /* ------------------------------------------------------------------------------------------
  * Per-box attributes (reference: src/vision/tk_attribute_classifier.c, run per detection by tk_vision_pipeline.c:462-485).
  * One workgroup per box; both classifiers are byte / integer histograms over the box's pixels, so the counts are exact whatever
- * the order the threads visit them in, and the fp32 / fp64 arithmetic of the HSV test is the reference's, operation for operation:
- *   r,g,b = u8 / 255.0f;  v = max, delta = max - min, s = delta / max  (s = 0 when max = 0)
- *   h = 60 * ((g - b) / delta | 2 + (b - r) / delta | 4 + (r - g) / delta), + 360 when negative   (the constants are doubles in the
- *   reference: a float op double op rounds once more on the store to float, reproduced with explicit double arithmetic)
- *   s < 0.1 (double compare): black (v < 0.1) / white (v > 0.9) / gray, else six 60-degree hue bins starting at 330.
+ * the order the threads visit them in; the per-pixel arithmetic is common/tk_box_attr.h, the reference's operation for operation.
  * Dominant colour = first bin with the maximum count.  Like the reference the frame is read as tightly packed RGB8
  * (row pitch = 3 * width, :56); pixels outside the frame are skipped (:54).
  * Door state: count interior pixels whose luminance (integer 299/587/114 per mille) differs by more than 100 between the rows above
  * and below; closed when count / (w * h) > 0.1.  The reference does not bounds-check this loop (:113-117); out-of-frame pixels are
  * skipped here.
  * ------------------------------------------------------------------------------------------ */
-__device__ __forceinline__ int tk_color_bin(uint8_t R, uint8_t G, uint8_t B) {
-    const float r = tk_divf((float)R, 255.0f), g = tk_divf((float)G, 255.0f), b = tk_divf((float)B, 255.0f);
-    const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
-    const float delta = mx - mn, v = mx;
-    float s = 0.0f, h = 0.0f;
-    if ((double)mx > 0.0) {
-        s = tk_divf(delta, mx);
-        if (r >= mx) h = tk_divf(g - b, delta);
-        else if (g >= mx) h = (float)(2.0 + (double)tk_divf(b - r, delta));
-        else h = (float)(4.0 + (double)tk_divf(r - g, delta));
-        h = (float)((double)h * 60.0);
-        if ((double)h < 0.0) h = (float)((double)h + 360.0);
-    }
-    if ((double)s < 0.1) return (double)v < 0.1 ? 6 : ((double)v > 0.9 ? 7 : 8);
-    if (h < 30.0f || h >= 330.0f) return 0;
-    if (h < 90.0f) return 1;
-    if (h < 150.0f) return 2;
-    if (h < 210.0f) return 3;
-    if (h < 270.0f) return 4;
-    if (h < 330.0f) return 5;
-    return -1; /* NaN hue: the reference counts the pixel in no bin */
-}
-
-__device__ __forceinline__ int tk_luma(const uint8_t* p) { return (int)(uint8_t)((p[0] * 299 + p[1] * 587 + p[2] * 114) / 1000); }
-
 __global__ __launch_bounds__(256) void k_box_attributes(const uint8_t* frame, int W, int H, const int32_t* rects, int32_t* out) {
     __shared__ int bins[9];
     __shared__ int edges;
@@ -594,8 +566,7 @@ __global__ __launch_bounds__(256) void k_box_attributes(const uint8_t* frame, in
         if (c >= 0) atomicAdd(&bins[c], 1);
         const int lx = x - bx, ly = y - by; /* door-state loop: interior of the box, rows above / below inside the frame */
         if (lx >= 1 && lx < bw - 1 && ly >= 1 && ly < bh - 1 && y >= 1 && y < H - 1) {
-            const int d = tk_luma(p - (int64_t)W * 3) - tk_luma(p + (int64_t)W * 3);
-            if ((d < 0 ? -d : d) > 100) atomicAdd(&edges, 1);
+            if (tk_edge_between(p - (int64_t)W * 3, p + (int64_t)W * 3)) atomicAdd(&edges, 1);
         }
     }
     __syncthreads();
@@ -604,9 +575,12 @@ __global__ __launch_bounds__(256) void k_box_attributes(const uint8_t* frame, in
         for (int i = 1; i < 9; ++i)
             if (bins[i] > bins[best]) best = i;
         out[2 * box] = best;
-        const float density = tk_divf((float)edges, (float)(bw * bh));
-        out[2 * box + 1] = (double)density > 0.1 ? 1 : 0;
+        out[2 * box + 1] = tk_door_closed(edges, bw, bh);
     }
+}
+
+void tk_launch_box_attributes(const uint8_t* frame, int W, int H, int n, const int32_t* rects, int32_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_box_attributes, dim3(n), dim3(256), 0, s, frame, W, H, rects, out);
 }
 
 bool TkDetector::run_attributes(const uint8_t* frame, uint32_t w, uint32_t h, int n, const int32_t* rects, int32_t* color, int32_t* door_closed) {
@@ -621,7 +595,7 @@ bool TkDetector::run_attributes(const uint8_t* frame, uint32_t w, uint32_t h, in
     }
     int32_t* res = attr_dev + (size_t)attr_cap * 4;
     HIPQ(hipMemcpyAsync(attr_dev, rects, (size_t)n * 16, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_box_attributes, dim3(n), dim3(256), 0, stream, frame, (int)w, (int)h, attr_dev, res);
+    tk_launch_box_attributes(frame, (int)w, (int)h, n, attr_dev, res, stream);
     std::vector<int32_t> hr((size_t)n * 2);
     HIPQ(hipMemcpyAsync(hr.data(), res, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
     HIPQ(hipStreamSynchronize(stream));
@@ -649,7 +623,7 @@ bool tk_classify_boxes_host(int device, const uint8_t* frame, uint32_t w, uint32
     std::vector<int32_t> hr((size_t)n * 2);
     if (ok) ok = hipMemcpy(df, frame, fb, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dr, rects, (size_t)n * 16, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
-        hipLaunchKernelGGL(k_box_attributes, dim3(n), dim3(256), 0, nullptr, df, (int)w, (int)h, dr, dr + (size_t)n * 4);
+        tk_launch_box_attributes(df, (int)w, (int)h, n, dr, dr + (size_t)n * 4, nullptr);
         ok = hipGetLastError() == hipSuccess && hipMemcpy(hr.data(), dr + (size_t)n * 4, (size_t)n * 8, hipMemcpyDeviceToHost) == hipSuccess;
     }
     if (df) (void)hipFree(df);

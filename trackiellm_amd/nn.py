@@ -1,4 +1,4 @@
-"""Perception kernels one launch at a time: the test hooks tk_mi355x_gemm_probe, tk_mi355x_attention_h3_probe and tk_mi355x_nn_row_probe."""
+"""Perception kernels one launch at a time: the test hooks tk_mi355x_gemm_probe, tk_mi355x_attention_h3_probe, tk_mi355x_nn_row_probe and tk_mi355x_edge_probe."""
 import ctypes as C
 
 import numpy as np
@@ -117,3 +117,41 @@ def nn_row_probe(op, y, a=None, b=None, c=None, idx=None, pos_idx=None, img=None
     lib().tk_mi355x_nn_row_probe.argtypes = [C.c_int, C.POINTER(NnRowProbe)]
     check(lib().tk_mi355x_nn_row_probe(device, C.byref(p)))
     return out, image, int(p.kernel)
+
+
+# tk_mi355x_edge_probe's ops, and the element type of each op's arrays (a, b, y); c and y2 are float32
+EDGE_FRAMES, EDGE_POWER, EDGE_LOGMEL_FINISH, EDGE_VAD_HEAD, EDGE_PREPROCESS, EDGE_DEPTH_MINMAX, EDGE_DEPTH_METRIC, EDGE_POSTPROCESS_DEPTH, EDGE_DEPTH_TO_POINTS, \
+    EDGE_BOX_ATTRIBUTES = range(10)
+PREPROCESS_CANONICAL, PREPROCESS_SCALED = 0, 1
+_EDGE_TYPES = {EDGE_FRAMES: (np.int16, np.float32, np.float32), EDGE_PREPROCESS: (np.uint8, np.float32, np.float32),
+               EDGE_BOX_ATTRIBUTES: (np.uint8, np.int32, np.int32)}
+
+
+class EdgeProbe(C.Structure):  # tk_mi355x_edge_probe_t
+    _fields_ = [(n, C.c_int32) for n in ("op", "B", "n_samples", "pcm_stride", "n_total", "T", "rows", "nb", "per_b", "hidden", "in_w", "in_h", "in_stride", "bpp",
+                                         "out_w", "out_h", "nhwc", "width", "height", "kernel")] + [("n", C.c_int64), ("mean", C.c_float * 3), ("std_dev", C.c_float * 3)] + \
+               [(n, C.c_float) for n in ("scale", "shift", "min_depth", "max_depth", "fx", "fy", "cx", "cy")] + \
+               [(n, C.c_void_p) for n in ("a", "b", "c", "y", "y2")] + [(n, C.c_int64) for n in ("n_a", "n_b", "n_c", "n_y", "n_y2")]
+
+
+def edge_probe(op, y, a=None, b=None, c=None, y2=None, device=0, **geometry):
+    """ONE launch of a front- or back-end launcher (tk_mi355x_edge_probe).  y (and y2): arrays with the caller's initial content; COPIES are launched
+    on and returned.  a / b / c: inputs, of the element types the header's table names per op; geometry: the struct's integer and float fields,
+    mean / std_dev as three floats.  device < 0: validation and the launcher's answer only.  Returns (y, y2 or None, kernel)."""
+    ta, tb, ty = _EDGE_TYPES.get(op, (np.float32, np.float32, np.float32))
+    a, b, c = _flat(a, ta), _flat(b, tb), _flat(c, np.float32)
+    out = None if y is None else np.array(y, dtype=ty, order="C", copy=True)
+    out2 = None if y2 is None else np.array(y2, dtype=np.float32, order="C", copy=True)
+    p = EdgeProbe()
+    p.op = op
+    for name, value in geometry.items():
+        if name not in dict(EdgeProbe._fields_) or name in ("op", "kernel", "a", "b", "c", "y", "y2") or name.startswith("n_") and name not in ("n_samples", "n_total"):
+            raise TypeError("edge_probe: no geometry field %r" % name)
+        setattr(p, name, (C.c_float * 3)(*value) if name in ("mean", "std_dev") else value)
+    for name, arr in (("a", a), ("b", b), ("c", c), ("y", out), ("y2", out2)):
+        if arr is not None:
+            setattr(p, name, arr.ctypes.data)
+            setattr(p, "n_" + name, arr.size)
+    lib().tk_mi355x_edge_probe.argtypes = [C.c_int, C.POINTER(EdgeProbe)]
+    check(lib().tk_mi355x_edge_probe(device, C.byref(p)))
+    return out, out2, int(p.kernel)
