@@ -263,6 +263,56 @@ TK_API int32_t tk_mi355x_llm_runner_recent_tokens(struct tk_llm_runner_s* runner
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_forward_adjusted(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos,
                                                                    const int32_t* tok, const tk_mi355x_sampling_t* sampling,
                                                                    const tk_mi355x_logit_adjust_t* adjust, float* logits, int32_t* ids);
+/* ---- log-probabilities (csrc/common/tk_token_logprob.h; opt-in; include/tk/ABI_NOTES.md): llama.cpp's server `n_probs`, the hosted APIs' `logprobs` /
+ * `top_logprobs` — how sure the model was of the id it produced, and what it would have said instead.  One device kernel behind the token pick, on
+ * the logits the pick read, for the rows that ask; a runner, session or pass that does not ask runs exactly the launches and graphs it ran before.
+ *   Distribution: softmax over the WHOLE vocabulary of the row's logits after stages 1 and 2 of the chain above (logit bias, repetition penalties) and
+ *   BEFORE stage 3 and 4: no grammar mask, no temperature, no top-k / top-p / min-p — the model's own distribution.  A token banned with a -inf bias has
+ *   log-probability -inf; a token the grammar forbids keeps its model log-probability and may appear among the alternatives.
+ *   Arithmetic (the same bits on host and device): m = the maximum logit; S = the sum of tk_expf(l_i - m) in one fixed order — 1024 lanes each adding
+ *   their terms i = t, t + 1024, ... ascending from +0, a six-level xor butterfly inside each wave of 64, the sixteen wave sums in ascending order —;
+ *   logprob_i = (l_i - m) - tk_logf(S).  The order depends neither on the pass width nor on the pass: a row's record is the same in any pass.
+ *   Alternatives: the min(n_top, vocab) most probable tokens in the sampler's order — descending logit (+0 above -0), ties to the lower id —: the prefix of
+ *   the candidate list the stochastic chain draws from on an unmasked row.  The first one is the greedy pick, except on a row whose maximum is a zero
+ *   of both signs (the arg max compares floats and takes the lower id).
+ *   Limits: n_top -1 = off, 0 = the produced id only, 1 .. 20 = that many alternatives; vocabularies of at most 65536 tokens.
+ * Out of scope: the prompt's tokens ("echo"), the rows of a lookup verify pass, the pipeline (tk_mi355x_pipe_*) path. ---- */
+#define TK_MI355X_LOGPROB_MAX_TOP 20
+/* one produced token's record.  n_top = the count of alternatives actually filled (min(asked, vocab)); entries past it are not written */
+typedef struct {
+    float logprob; /* of the produced id */
+    int32_t n_top;
+    int32_t top_ids[TK_MI355X_LOGPROB_MAX_TOP];
+    float top_logprobs[TK_MI355X_LOGPROB_MAX_TOP];
+} tk_mi355x_token_logprob_t;
+/* the runner's setting: -1 off (the default), 0 .. 20 on.  Anything else: TK_ERROR_INVALID_ARGUMENT, the previous setting kept.  Takes effect from the
+ * next sampled token.  A runner with log-probabilities on keeps running ahead (csrc/llm/tk_llm_batcher.h: the record rides with the id); lookup
+ * decoding does nothing while they are on.  Prefix cache, context shift and grammar are unaffected; the token stream is the one the runner emits with
+ * the setting off */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_logprobs(struct tk_llm_runner_s* runner, int32_t n_top);
+/* the record of the id the last prepare_generation / generate_next_token (or add_tool_response) sampled — the id the NEXT generate_next_token hands out
+ * as a piece, or finds to be EOS or the end of a tool call.  TK_ERROR_INVALID_STATE, `out` untouched: the setting is off, or nothing has been sampled
+ * since it was switched on */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_last_logprobs(struct tk_llm_runner_s* runner, tk_mi355x_token_logprob_t* out);
+/* tk_mi355x_llm_forward_adjusted plus the records: n_top [nrows] per row, records [nrows]; sampling and adjust may be NULL.  Records of rows with
+ * n_top = -1 come back as the caller left them, and so do the entries of a record past its filled count.  A pass with every n_top = -1 is the pass
+ * tk_mi355x_llm_forward_adjusted runs.  An n_top outside [-1, 20], or a vocabulary above 65536 with a row that asks: TK_ERROR_INVALID_ARGUMENT, nothing
+ * enqueued */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_forward_logprobs(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos,
+                                                                   const int32_t* tok, const tk_mi355x_sampling_t* sampling,
+                                                                   const tk_mi355x_logit_adjust_t* adjust, const int32_t* n_top, float* logits, int32_t* ids,
+                                                                   tk_mi355x_token_logprob_t* records);
+/* the kernel alone on host arrays (tests), tk_mi355x_logit_adjust_probe's contract: logits = `rows` rows of `cols` floats `ld` apart (n_logits floats in
+ * all), ids [rows] the chosen id of every row, n_top [rows], records [rows] IN/OUT.  device >= 0: ONE production launch (k_token_logprobs) on that
+ * device, the records read back whole — what the kernel did not write is what the caller put there.  device < 0: the same row function in a host loop,
+ * no GPU touched.  Everything is validated before anything is launched; TK_ERROR_INVALID_ARGUMENT with nothing written: rows outside
+ * [1, tk_mi355x_llm_max_rows()], cols outside [1, 65536], ld < cols, logits too short (n_logits < (rows - 1) * ld + cols), an id outside [0, cols), an
+ * n_top outside [-1, 20], a live row (n_top >= 0) that holds a NaN or +inf logit or no finite logit at all */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_token_logprobs_probe(int device, int32_t rows, int32_t cols, int32_t ld, const float* logits, int64_t n_logits,
+                                                                   const int32_t* ids, const int32_t* n_top, tk_mi355x_token_logprob_t* records);
+/* stand-alone timing of that launch (tools/time_token_logprobs.py): rows x cols generated logits, every row with the same n_top (0 .. 20); `iters`
+ * launches after a warm-up, device events around them; average ms of one */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_time_token_logprobs(int device, int32_t rows, int32_t cols, int32_t n_top, int32_t iters, float* avg_ms);
 /* KV cache import / export: positions [pos0, pos0 + n_pos) of one (layer, sequence) as IEEE f16 bits, host arrays laid out
  * [position][kv head][head_dim] (what llama.cpp's llama_state_seq_* moves for one sequence; the reference clears the cache per prompt,
  * src/ai_models/tk_runner_streaming.c:31, so it has no counterpart there).  Restores a saved prompt prefix; the parity tests use it to put
@@ -337,7 +387,7 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_forward_verify(tk_mi355x_llm_s
                                                                  const int32_t* tok, int form, float* logits, int32_t* picks);
 /* n_draft = 0 (off, the default) .. 15 drafts per pass; 1 <= ngram_min <= ngram_max <= 8.  Anything else: TK_ERROR_INVALID_ARGUMENT, the previous
  * setting kept.  Lookup does nothing — the runner submits exactly what it does with lookup off — while the runner has a temperature, a grammar mask,
- * penalties or a logit bias.  Takes effect from the next pass */
+ * penalties, a logit bias, or log-probabilities on (tk_mi355x_llm_runner_set_logprobs: a verify pass reports none).  Takes effect from the next pass */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_lookup(struct tk_llm_runner_s* runner, int32_t n_draft, int32_t ngram_min, int32_t ngram_max);
 /* the host's prediction of the reply (copied): at most 4096 ids, each inside the vocabulary; n = 0 clears it.  It survives prepare_generation.
  * Anything else: TK_ERROR_INVALID_ARGUMENT, the previous prediction kept */

@@ -386,12 +386,18 @@ tk_error_code_t tk_mi355x_llm_forward(tk_mi355x_llm_session_t* s, int nrows, con
 
 /* a sampling pass with optional per-row sampling states and logit adjustments: both checked per row before anything runs */
 static tk_error_code_t forward_rows(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok,
-                                    const tk_mi355x_sampling_t* sampling, const tk_mi355x_logit_adjust_t* adjust, float* logits, int32_t* ids) {
+                                    const tk_mi355x_sampling_t* sampling, const tk_mi355x_logit_adjust_t* adjust, float* logits, int32_t* ids,
+                                    const int32_t* n_top = nullptr, tk_mi355x_token_logprob_t* records = nullptr) {
+    static_assert(sizeof(tk_mi355x_token_logprob_t) == sizeof(TkTokenLogprob) && offsetof(tk_mi355x_token_logprob_t, top_ids) == offsetof(TkTokenLogprob, top_ids) &&
+                      offsetof(tk_mi355x_token_logprob_t, top_logprobs) == offsetof(TkTokenLogprob, top_logprobs),
+                  "the public log-probability record is the library's TkTokenLogprob");
     static_assert(sizeof(tk_mi355x_logit_adjust_t) == sizeof(TkLogitAdjust), "the public logit adjustment is the library's TkLogitAdjust (tk_rocm_hal.hip checks the fields)");
     if (!s || !seq || !pos || !tok || nrows < 1 || nrows > TK_MAX_ROWS) return TK_ERROR_INVALID_ARGUMENT;
     const TkLogitAdjust* adj = (const TkLogitAdjust*)adjust;
     for (int r = 0; r < nrows && adj; ++r)
         if (const char* why = adj[r].check(s->session.model->hp.vocab)) return fail(TK_ERROR_INVALID_ARGUMENT, "logit adjustment of row " + std::to_string(r) + ": " + why);
+    for (int r = 0; r < nrows && n_top; ++r)
+        if (const char* why = tk_logprob_check(n_top[r], s->session.model->hp.vocab)) return fail(TK_ERROR_INVALID_ARGUMENT, "log-probabilities of row " + std::to_string(r) + ": " + why);
     TkSampleRow rows[TK_MAX_ROWS] = {};
     for (int r = 0; r < nrows && sampling; ++r) {
         const tk_mi355x_sampling_t& p = sampling[r];
@@ -400,8 +406,16 @@ static tk_error_code_t forward_rows(tk_mi355x_llm_session_t* s, int nrows, const
             return fail(TK_ERROR_INVALID_ARGUMENT, "sampling parameters of row " + std::to_string(r) + " are out of range (temperature >= 0, 0 <= top_k <= 64, 0 < top_p <= 1, 0 <= min_p <= 1)");
         rows[r].temp = p.temperature; rows[r].top_p = p.top_p; rows[r].min_p = p.min_p; rows[r].top_k = p.top_k; rows[r].seed = p.seed; rows[r].counter = p.counter;
     }
-    if (!s->session.forward(nrows, seq, pos, tok, logits, ids, true, nullptr, sampling ? rows : nullptr, adj)) return fail(TK_ERROR_INFERENCE_FAILED, s->session.error);
+    if (!s->session.forward(nrows, seq, pos, tok, logits, ids, true, nullptr, sampling ? rows : nullptr, adj, n_top, (TkTokenLogprob*)records))
+        return fail(TK_ERROR_INFERENCE_FAILED, s->session.error);
     return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_forward_logprobs(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok,
+                                               const tk_mi355x_sampling_t* sampling, const tk_mi355x_logit_adjust_t* adjust, const int32_t* n_top,
+                                               float* logits, int32_t* ids, tk_mi355x_token_logprob_t* records) {
+    if (!n_top || !records) return TK_ERROR_INVALID_ARGUMENT;
+    return forward_rows(s, nrows, seq, pos, tok, sampling, adjust, logits, ids, n_top, records);
 }
 
 tk_error_code_t tk_mi355x_llm_forward_sampled(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok,
@@ -895,6 +909,11 @@ struct tk_llm_runner_s {
         adj.n_bias = (int32_t)bias_ids.size(); adj.bias_ids = bias_ids.data(); adj.bias = bias.data();
         return &adj;
     }
+    /* log-probabilities (tk_mi355x_llm_runner_set_logprobs, csrc/common/tk_token_logprob.h), off by default.  last_lp: the record of the id in `pending`,
+     * valid once something has been sampled since the feature was switched on */
+    int32_t lp_ntop = -1;
+    TkTokenLogprob last_lp{};
+    bool lp_valid = false;
     /* context shift (tk_mi355x_llm_runner_set_context_shift), off by default: llama.cpp's answer to a full context */
     bool shift_on = false;
     int32_t shift_keep = 0;      /* n_keep; -1 = prompt_tokens, resolved when a shift happens */
@@ -910,8 +929,9 @@ struct tk_llm_runner_s {
     std::vector<int32_t> ctx_ids;
     std::vector<int32_t> queued;
     uint64_t lookup_passes = 0, lookup_drafted = 0, lookup_accepted = 0; /* since the last prepare_generation */
-    /* lookup does nothing while the runner samples stochastically, under a grammar mask, or with penalties or a bias: it then submits what it always did */
-    bool lookup_active() const { return lookup_draft > 0 && !(samp.temp > 0.0f) && !grammar_on && pen_last_n == 0 && bias_ids.empty(); }
+    /* lookup does nothing while the runner samples stochastically, under a grammar mask, with penalties or a bias, or with log-probabilities on (a verify
+     * pass reports none): it then submits what it always did */
+    bool lookup_active() const { return lookup_draft > 0 && !(samp.temp > 0.0f) && !grammar_on && pen_last_n == 0 && bias_ids.empty() && lp_ntop < 0; }
     /* the owner abandons the ids it was handed but has not given out (a tool response, a reset): back to the state of a runner that holds `pending`
      * alone — the rows fed ahead are stale rows beyond n_past, overwritten before anything attends to them */
     void drop_queued() {
@@ -1005,6 +1025,25 @@ int32_t tk_mi355x_llm_runner_recent_tokens(tk_llm_runner_t* runner, int32_t* out
     if (!runner) return -1;
     for (int32_t i = 0; out && i < cap && i < (int32_t)runner->accepted.size(); ++i) out[i] = runner->accepted[(size_t)i];
     return (int32_t)runner->accepted.size();
+}
+
+tk_error_code_t tk_mi355x_llm_runner_set_logprobs(tk_llm_runner_t* runner, int32_t n_top) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    if (const char* why = tk_logprob_check(n_top, runner->model->model.hp.vocab)) return fail(TK_ERROR_INVALID_ARGUMENT, std::string("log-probabilities: ") + why);
+    if ((n_top < 0) != (runner->lp_ntop < 0)) runner->lp_valid = false; /* switched on or off: the next sampled token brings the first record */
+    runner->lp_ntop = n_top;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_runner_last_logprobs(tk_llm_runner_t* runner, tk_mi355x_token_logprob_t* out) {
+    if (!runner || !out) return TK_ERROR_INVALID_ARGUMENT;
+    if (runner->lp_ntop < 0) return fail(TK_ERROR_INVALID_STATE, "log-probabilities are off for this runner");
+    if (!runner->lp_valid) return fail(TK_ERROR_INVALID_STATE, "no token has been sampled since log-probabilities were switched on");
+    const TkTokenLogprob& g = runner->last_lp;
+    out->logprob = g.logprob;
+    out->n_top = g.n_top;
+    for (int j = 0; j < g.n_top; ++j) { out->top_ids[j] = g.top_ids[j]; out->top_logprobs[j] = g.top_logprobs[j]; }
+    return TK_SUCCESS;
 }
 
 tk_error_code_t tk_mi355x_llm_runner_set_lookup(tk_llm_runner_t* runner, int32_t n_draft, int32_t ngram_min, int32_t ngram_max) {
@@ -1131,8 +1170,9 @@ static tk_error_code_t feed(tk_llm_runner_s* r, const std::vector<int32_t>& toks
     std::string err;
     /* whole_context (prepare_generation): the tokens start at position 0, so the scheduler may keep or copy rows the cache already holds for them */
     if (!r->batcher->submit(r->slot, r->n_past, toks.data(), (int)toks.size(), r->next_mask(), &am, &err, r->next_samp(), whole_context ? &r->last_prompt : nullptr, r->next_adjust(),
-                            r->lookup_active()))
+                            r->lookup_active(), r->lp_ntop, r->lp_ntop >= 0 ? &r->last_lp : nullptr))
         return fail(TK_ERROR_INFERENCE_FAILED, err);
+    r->lp_valid = r->lp_ntop >= 0;
     if (r->samp.temp > 0.0f) r->samp.counter++;
     r->n_past += (int)toks.size();
     r->pending = am;
@@ -1173,6 +1213,7 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
     if (!runner->queued.empty()) { /* lookup decoding: this id's row is in the cache already, and the id behind it has been sampled */
         runner->pending = runner->queued.front();
         runner->queued.erase(runner->queued.begin());
+        runner->lp_valid = false; /* an id a verify pass sampled: it has no record (log-probabilities were switched on behind it) */
         runner->piece = runner->model->tok.piece(id);
         return runner->piece.c_str();
     }
@@ -1225,11 +1266,13 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
             return runner->piece.c_str();
         }
     }
-    if (!runner->batcher->submit(runner->slot, runner->n_past, &t, 1, runner->next_mask(), &am, &err, runner->next_samp(), nullptr, runner->next_adjust(), lookup)) {
+    if (!runner->batcher->submit(runner->slot, runner->n_past, &t, 1, runner->next_mask(), &am, &err, runner->next_samp(), nullptr, runner->next_adjust(), lookup,
+                                 runner->lp_ntop, runner->lp_ntop >= 0 ? &runner->last_lp : nullptr)) {
         tk_error_set_detail("%s", err.c_str());
         runner->is_processing = false;
         return NULL;
     }
+    runner->lp_valid = runner->lp_ntop >= 0;
     if (runner->samp.temp > 0.0f) runner->samp.counter++;
     runner->n_past++;
     runner->pending = am;

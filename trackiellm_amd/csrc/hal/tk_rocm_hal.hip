@@ -443,6 +443,81 @@ tk_error_code_t tk_mi355x_logit_adjust_probe(int device, int32_t rows, int32_t c
     return rc;
 }
 
+static_assert(sizeof(tk_mi355x_token_logprob_t) == sizeof(TkTokenLogprob) && offsetof(tk_mi355x_token_logprob_t, n_top) == offsetof(TkTokenLogprob, n_top) &&
+                  offsetof(tk_mi355x_token_logprob_t, top_ids) == offsetof(TkTokenLogprob, top_ids) &&
+                  offsetof(tk_mi355x_token_logprob_t, top_logprobs) == offsetof(TkTokenLogprob, top_logprobs) && TK_MI355X_LOGPROB_MAX_TOP == TK_LOGPROB_MAX_TOP,
+              "the public log-probability record is the library's TkTokenLogprob");
+
+tk_error_code_t tk_mi355x_token_logprobs_probe(int device, int32_t rows, int32_t cols, int32_t ld, const float* logits, int64_t n_logits, const int32_t* ids,
+                                               const int32_t* n_top, tk_mi355x_token_logprob_t* records) {
+    if (!logits || !ids || !n_top || !records || rows < 1 || rows > TK_MAX_ROWS || cols < 1 || cols > TK_LOGPROB_MAX_VOCAB || ld < cols || ld > (1 << 24) ||
+        n_logits < (int64_t)(rows - 1) * ld + cols)
+        return TK_ERROR_INVALID_ARGUMENT;
+    for (int r = 0; r < rows; ++r) {
+        if (tk_logprob_check(n_top[r], cols) || ids[r] < 0 || ids[r] >= cols) return TK_ERROR_INVALID_ARGUMENT;
+        if (n_top[r] >= 0 && tk_logprob_check_row(logits + (int64_t)r * ld, cols)) return TK_ERROR_INVALID_ARGUMENT;
+    }
+    TkTokenLogprob* rec = (TkTokenLogprob*)records;
+    if (device < 0) {
+        for (int r = 0; r < rows; ++r) tk_token_logprob_row(logits + (int64_t)r * ld, cols, ids[r], n_top[r], rec + r);
+        return TK_SUCCESS;
+    }
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    struct Buf { const void* host; size_t bytes; void* dev; };
+    Buf b[] = {{logits, (size_t)n_logits * 4, nullptr}, {ids, (size_t)rows * 4, nullptr}, {n_top, (size_t)rows * 4, nullptr}, {rec, (size_t)rows * sizeof(TkTokenLogprob), nullptr}};
+    bool ok = true;
+    for (Buf& q : b) ok = ok && hipMalloc(&q.dev, q.bytes) == hipSuccess && hipMemcpy(q.dev, q.host, q.bytes, hipMemcpyHostToDevice) == hipSuccess;
+    tk_error_code_t rc = ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
+    if (ok) {
+        tk_launch_token_logprobs((const float*)b[0].dev, cols, ld, rows, (const int32_t*)b[2].dev, (const int32_t*)b[1].dev, (TkTokenLogprob*)b[3].dev, nullptr);
+        if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(rec, b[3].dev, b[3].bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+    }
+    for (Buf& q : b) if (q.dev) (void)hipFree(q.dev);
+    return rc;
+}
+
+/* stand-alone timing of that launch (tools/time_token_logprobs.py): rows x cols logits from a fixed generator, every row with the same n_top and chosen
+ * id 0; `iters` launches after one untimed launch, device events around them; average ms of one */
+tk_error_code_t tk_mi355x_time_token_logprobs(int device, int32_t rows, int32_t cols, int32_t n_top, int32_t iters, float* avg_ms) {
+    if (!avg_ms || rows < 1 || rows > TK_MAX_ROWS || cols < 1 || cols > TK_LOGPROB_MAX_VOCAB || n_top < 0 || n_top > TK_LOGPROB_MAX_TOP || iters < 1 || iters > 100000)
+        return TK_ERROR_INVALID_ARGUMENT;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device < 0 || device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    std::vector<float> lg((size_t)rows * cols);
+    uint64_t z = 0x9E3779B97F4A7C15ull;
+    for (float& v : lg) { /* logits spread over [-8, 8) */
+        z = z * 6364136223846793005ull + 1442695040888963407ull;
+        v = (float)(uint32_t)(z >> 40) * (16.0f / 16777216.0f) - 8.0f;
+    }
+    std::vector<int32_t> ids((size_t)rows, 0), nt((size_t)rows, n_top);
+    void *d_lg = nullptr, *d_ids = nullptr, *d_nt = nullptr, *d_rec = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok = hipMalloc(&d_lg, lg.size() * 4) == hipSuccess && hipMalloc(&d_ids, ids.size() * 4) == hipSuccess && hipMalloc(&d_nt, nt.size() * 4) == hipSuccess &&
+              hipMalloc(&d_rec, (size_t)rows * sizeof(TkTokenLogprob)) == hipSuccess && hipMemcpy(d_lg, lg.data(), lg.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_nt, nt.data(), nt.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    tk_error_code_t rc = ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
+    if (ok) {
+        tk_launch_token_logprobs((const float*)d_lg, cols, cols, rows, (const int32_t*)d_nt, (const int32_t*)d_ids, (TkTokenLogprob*)d_rec, nullptr);
+        (void)hipEventRecord(e0, nullptr);
+        for (int i = 0; i < iters; ++i) tk_launch_token_logprobs((const float*)d_lg, cols, cols, rows, (const int32_t*)d_nt, (const int32_t*)d_ids, (TkTokenLogprob*)d_rec, nullptr);
+        (void)hipEventRecord(e1, nullptr);
+        float ms = 0.0f;
+        if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+        else *avg_ms = ms / (float)iters;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    void* ptrs[] = {d_lg, d_ids, d_nt, d_rec};
+    for (void* q : ptrs) if (q) (void)hipFree(q);
+    return rc;
+}
+
 tk_error_code_t tk_mi355x_kv_shift_probe(int device, int32_t n_layer, int32_t max_seq, int32_t n_kv_head, int32_t max_ctx, int32_t head_dim, uint16_t* kcache,
                                          uint16_t* vcache, const float* rope_cos, const float* rope_sin, int32_t seq, int32_t p0, int32_t p1, int32_t delta) {
     const int32_t cap = 1 << 16;

@@ -85,13 +85,14 @@ void TkLlmBatcher::record_row(int slot, int pos, int32_t tok) {
 }
 
 /* the owner of `slot` has just been handed `sampled` for position pos_done: feed it at pos_done + 1 in the next pass */
-void TkLlmBatcher::plan_ahead(int slot, int pos_done, int32_t sampled, bool masked) {
+void TkLlmBatcher::plan_ahead(int slot, int pos_done, int32_t sampled, bool masked, int32_t n_top) {
     Ahead& a = ahead_[(size_t)slot];
     if (masked || sampled < 0 || sampled == eos_ || pos_done + 2 >= n_ctx_ || a.st != Ahead::NONE) return; /* the runner stops at n_past + 1 >= n_ctx */
     a = Ahead();
     a.st = Ahead::PLANNED;
     a.pos = pos_done + 1;
     a.tok = sampled;
+    a.n_top = n_top; /* the owner's log-probability setting rides along: the record depends on nothing the owner decides */
 }
 
 void TkLlmBatcher::drop_ahead(int slot) {
@@ -103,8 +104,10 @@ void TkLlmBatcher::drop_ahead(int slot) {
 }
 
 bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp,
-                          PrefixRows* prefix, const TkLogitAdjust* adjust, bool hold) {
+                          PrefixRows* prefix, const TkLogitAdjust* adjust, bool hold, int32_t n_top, TkTokenLogprob* record) {
     if (n <= 0) { *err = "nothing to feed"; return false; }
+    if (const char* why = tk_logprob_check(n_top, session_.model->hp.vocab)) { *err = std::string("log-probabilities: ") + why; return false; }
+    if (n_top >= 0 && !record) { *err = "log-probabilities asked for without a record to fill"; return false; }
     if (adjust)
         if (const char* why = adjust->check(session_.model->hp.vocab)) { *err = std::string("logit adjustment: ") + why; return false; }
     if (slot < 0 || slot >= (int)slot_used_.size() || pos0 < 0 || pos0 + n > n_ctx_) { *err = "rows do not fit the context window"; return false; }
@@ -113,6 +116,7 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
     if (samp) r.samp = *samp;
     if (adjust && !adjust->neutral()) { r.adj = *adjust; r.adjusted = true; }
     r.owner_hold = hold;
+    r.n_top = n_top; r.rec = record;
     r.hold = hold || r.adjusted || (adjust && (adjust->repeat != 1.0f || adjust->freq != 0.0f || adjust->present != 0.0f));
     r.whole = prefix != nullptr && pos0 == 0;
     if (prefix) *prefix = PrefixRows{n, 0, 0};
@@ -121,15 +125,16 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
     if (stop_) { *err = "scheduler stopped"; return false; }
     Ahead& a = ahead_[(size_t)slot];
     if (a.st != Ahead::NONE && !a.discard) {
-        if (n == 1 && !mask && !stochastic && !r.adjusted && pos0 == a.pos && toks[0] == a.tok) { /* the row this call asks for is the one that ran (or runs) ahead */
+        if (n == 1 && !mask && !stochastic && !r.adjusted && pos0 == a.pos && toks[0] == a.tok && n_top == a.n_top) { /* the row this call asks for is the one that ran (or runs) ahead */
             if (a.st == Ahead::DONE) {
                 const bool ok = a.ok;
                 const int32_t got = a.sampled;
+                if (ok && n_top >= 0) *record = a.rec; /* handed over with the id */
                 a = Ahead();
                 if (!ok) { *err = last_error_; return false; }
                 rows_++;
                 *sampled = got;
-                plan_ahead(slot, pos0, got, hold); /* hold: lookup was switched on while a row ran ahead; it is the last one */
+                plan_ahead(slot, pos0, got, hold, n_top); /* hold: lookup was switched on while a row ran ahead; it is the last one */
                 cv_.notify_all();
                 return true;
             }
@@ -188,6 +193,8 @@ void TkLlmBatcher::loop() {
     std::vector<const uint32_t*> masks;
     std::vector<TkSampleRow> samps;
     std::vector<TkLogitAdjust> adjs;
+    std::vector<int32_t> ntops;        /* [row of the pass]: -1, or the n_top of the request / run-ahead row that is sampled there */
+    std::vector<TkTokenLogprob> recs;  /* [row of the pass]: what forward() filled for the rows that ask */
     struct Taken { Request* r; int take, last_row; };   /* `take` rows of a request end at row `last_row` of the pass */
     struct AheadRow { int slot, row; };                  /* a sequence's run-ahead row and where it sits in the pass */
     std::vector<Taken> in_pass;
@@ -212,8 +219,8 @@ void TkLlmBatcher::loop() {
     for (;;) {
         double t_woke = 0.0;
         in_pass.clear(); completing.clear(); ahead_rows.clear(); copies.clear(); copy_for.clear();
-        sq.clear(); ps.clear(); tk.clear(); masks.clear(); samps.clear(); adjs.clear();
-        bool any_mask = false, any_samp = false, any_adj = false;
+        sq.clear(); ps.clear(); tk.clear(); masks.clear(); samps.clear(); adjs.clear(); ntops.clear();
+        bool any_mask = false, any_samp = false, any_adj = false, any_lp = false;
         bool any_verify = false, all_qualify = true; /* verify requests (tk_llm_batcher.h): the pass may take forward_verify */
         {
             std::unique_lock<std::mutex> lk(mu_);
@@ -277,10 +284,11 @@ void TkLlmBatcher::loop() {
                     masks.push_back(nullptr);
                     samps.push_back(TkSampleRow{});
                     adjs.push_back(TkLogitAdjust{});
+                    ntops.push_back(-1);
                 }
                 in_pass.push_back(Taken{r, take, (int)sq.size() - 1});
                 any_verify = any_verify || r->verify;
-                all_qualify = all_qualify && (r->verify || (r->done_rows + take == r->n && !r->mask && !(r->samp.temp > 0.0f) && !r->adjusted));
+                all_qualify = all_qualify && (r->verify || (r->done_rows + take == r->n && !r->mask && !(r->samp.temp > 0.0f) && !r->adjusted && r->n_top < 0));
                 if (r->done_rows + take == r->n) {
                     completing.push_back(r);
                     masks.back() = r->mask; /* the row that is sampled */
@@ -289,6 +297,8 @@ void TkLlmBatcher::loop() {
                     any_samp = any_samp || r->samp.temp > 0.0f;
                     adjs.back() = r->adj;
                     any_adj = any_adj || r->adjusted;
+                    ntops.back() = r->n_top;
+                    any_lp = any_lp || r->n_top >= 0;
                 }
             };
             /* prefix cache (tk_llm_batcher.h): a whole-context request that is about to enter the pass first moves its cursor over the rows its
@@ -337,6 +347,9 @@ void TkLlmBatcher::loop() {
                     masks.push_back(nullptr);
                     samps.push_back(TkSampleRow{});
                     adjs.push_back(TkLogitAdjust{});
+                    ntops.push_back(a.n_top);
+                    any_lp = any_lp || a.n_top >= 0;
+                    all_qualify = all_qualify && a.n_top < 0; /* forward_verify reports no log-probabilities */
                     ahead_rows.push_back(AheadRow{(int)s, (int)sq.size() - 1});
                 }
             };
@@ -353,6 +366,7 @@ void TkLlmBatcher::loop() {
         const int nrows = (int)sq.size();
         if (nrows == 0) continue;
         am.assign((size_t)nrows, -1);
+        if (any_lp) recs.assign((size_t)nrows, TkTokenLogprob{});
         const double t_formed = trace_path_.empty() ? 0.0 : now_ms();
         const bool head = !completing.empty() || !ahead_rows.empty();
         /* the copies go first on the session's stream: forward() then reads the copied rows, and a source row it overwrites was read before */
@@ -361,7 +375,8 @@ void TkLlmBatcher::loop() {
         /* a pass with a verify request in which every request qualifies: every row is sampled, greedy, and a long context may take the run form */
         const bool ok = any_verify && all_qualify ? copied_ok && session_.forward_verify(nrows, sq.data(), ps.data(), tk.data(), -1, nullptr, am.data())
                         : copied_ok && session_.forward(nrows, sq.data(), ps.data(), tk.data(), nullptr, head ? am.data() : nullptr, head, head && any_mask ? masks.data() : nullptr,
-                                        head && any_samp ? samps.data() : nullptr, head && any_adj ? adjs.data() : nullptr);
+                                        head && any_samp ? samps.data() : nullptr, head && any_adj ? adjs.data() : nullptr,
+                                        head && any_lp ? ntops.data() : nullptr, head && any_lp ? recs.data() : nullptr);
         {
             std::lock_guard<std::mutex> lk(mu_);
             passes_++;
@@ -397,9 +412,10 @@ void TkLlmBatcher::loop() {
                 if (!ok) { r->ok = false; r->error = session_.error; r->done_rows = r->n; }
                 if (r->done_rows == r->n) {
                     r->sampled = ok ? am[(size_t)row - 1] : -1;
+                    if (ok && r->n_top >= 0) *r->rec = recs[(size_t)row - 1]; /* the owner is blocked in submit(): its record is ours to write */
                     for (auto it = queue_.begin(); it != queue_.end(); ++it)
                         if (*it == r) { queue_.erase(it); break; }
-                    if (ok) plan_ahead(r->slot, r->pos0 + r->n - 1, r->sampled, r->mask != nullptr || r->samp.temp > 0.0f || r->hold);
+                    if (ok) plan_ahead(r->slot, r->pos0 + r->n - 1, r->sampled, r->mask != nullptr || r->samp.temp > 0.0f || r->hold, r->n_top);
                     /* an owner that was handed several ids comes back only when it has given all but the last to its caller: nobody waits for it */
                     if (!ok || (ahead_[(size_t)r->slot].st != Ahead::PLANNED && r->ids.size() <= 1)) held++;
                     r->finished = true;
@@ -414,17 +430,19 @@ void TkLlmBatcher::loop() {
                 if (a.waiter) { /* the owner is already waiting for exactly this row */
                     Request* w = a.waiter;
                     const int pos = a.pos;
+                    if (ok && a.n_top >= 0) *w->rec = recs[(size_t)ar.row]; /* submit() matched the waiter's n_top with the row's */
                     a = Ahead();
                     w->ok = ok;
                     if (!ok) w->error = session_.error;
                     w->sampled = got;
                     rows_++;
-                    if (ok) plan_ahead(s, pos, got, w->owner_hold);
+                    if (ok) plan_ahead(s, pos, got, w->owner_hold, w->n_top);
                     w->finished = true;
                     w->cv.notify_all();
                 } else {
                     a.st = Ahead::DONE;
                     a.sampled = got;
+                    if (ok && a.n_top >= 0) a.rec = recs[(size_t)ar.row]; /* held until the owner takes the id */
                     a.ok = ok;
                 }
             }

@@ -17,7 +17,10 @@
  * the accepted token), not for rows sampled under a non-neutral logit adjustment (the next window of the repetition penalties depends on the
  * accepted token, and the owner may change its bias list; this holds from the first sampled token on, whose window is still empty), not for a slot
  * whose runner has lookup decoding on (the row after a sampled id is the first row of the owner's next verify pass, which carries drafts that only the
- * owner can make: such a slot submits with `hold`, and a verify request never plans a row ahead), not after EOS, not at the end of the context.  An owner that comes back with something else (a tool response, a
+ * owner can make: such a slot submits with `hold`, and a verify request never plans a row ahead), not after EOS, not at the end of the context.
+ * A runner with log-probabilities on (submit's n_top >= 0, common/tk_token_logprob.h) KEEPS running ahead: the record of a row depends on nothing its
+ * owner decides, so the run-ahead row of such a slot is planned with the slot's n_top, its record is held in the Ahead entry and handed over with the
+ * id; an owner that comes back with another n_top than the row was planned with has gone another way, like one that comes back with another token.  An owner that comes back with something else (a tool response, a
  * new prompt) or not at all costs one wasted row: the cache row it wrote is overwritten before anything attends to it, because positions
  * are fed in order.  Tokens are unchanged — a row's result does not depend on when or with whom it runs.
  *
@@ -56,7 +59,7 @@
  * Verify requests (submit_verify; lookup decoding, tk_lookup.h).  A greedy runner feeds its pending id and n - 1 drafted ids at positions pos0,
  * pos0 + 1, ... of its slot; EVERY row is sampled, and the accept rule keeps the ids picks[0 .. m] that one-row passes would have produced.  The n rows
  * enter one pass together (a request that finds fewer rows left waits for the next pass).  A pass that holds at least one verify request and in
- * which every other request is a plain greedy, unmasked, unadjusted one that ends in this pass (its last row is the sampled one; run-ahead rows are
+ * which every other request is a plain greedy, unmasked, unadjusted one without log-probabilities that ends in this pass (its last row is the sampled one; run-ahead rows are
  * such rows too) goes through TkLlmSession::forward_verify, where a long context may take the run form of the long attention; any other pass goes
  * through forward() as before — forward() returns the arg max of every row of a multi-position pass too, and both paths give a row the same bits.
  * A pass without a verify request is untouched: it replays the graphs it always did.
@@ -96,8 +99,10 @@ public:
     /* adjust (optional): logit bias and repetition penalties of the sampled row (common/tk_logit_adjust.h); its arrays belong to the caller until
      * the call returns, like `mask`; checked here against the limits.  A non-neutral one keeps the row from running ahead (header comment) */
     struct PrefixRows { int32_t prompt_rows = 0, kept = 0, copied = 0; };
+    /* n_top (optional): -1 = off, 0 .. TK_LOGPROB_MAX_TOP = the log-probability of the sampled id and that many alternatives into *record
+     * (common/tk_token_logprob.h), filled when the call returns true; such a row still runs ahead (header comment) */
     bool submit(int slot, int pos0, const int32_t* toks, int n, const uint32_t* mask, int32_t* sampled, std::string* err, const TkSampleRow* samp = nullptr,
-                PrefixRows* prefix = nullptr, const TkLogitAdjust* adjust = nullptr, bool hold = false);
+                PrefixRows* prefix = nullptr, const TkLogitAdjust* adjust = nullptr, bool hold = false, int32_t n_top = -1, TkTokenLogprob* record = nullptr);
     /* hold: no row runs ahead of this request's sampled id (the owner has lookup decoding on: its next call is a verify request or comes with `hold` again) */
     /* Blocking: the verify pass of lookup decoding (header comment, "Verify requests"): toks[0] is the slot's pending id, toks[1 .. n) are drafts, fed at
      * positions pos0 .. pos0 + n - 1 in ONE pass, 1 <= n <= TK_LOOKUP_MAX_DRAFT + 1; every row is sampled greedily.  ids_out (room for n) receives the
@@ -128,6 +133,8 @@ private:
         bool adjusted = false; /* adj is not neutral */
         bool hold = false;     /* no run-ahead from this row: adjusted, or penalties that are on over a still empty window (the next one is not) */
         int32_t sampled = -1;
+        int32_t n_top = -1;           /* log-probabilities of the sampled row: -1 off */
+        TkTokenLogprob* rec = nullptr; /* the owner's record, written before `finished` */
         bool owner_hold = false;      /* submit's `hold` argument: the owner has lookup decoding on */
         bool verify = false;         /* a verify request: all n rows in one pass, every row sampled */
         std::vector<int32_t> ids;     /* what the accept rule kept of its picks (m + 1 ids) */
@@ -140,11 +147,13 @@ private:
         enum State { NONE, PLANNED, INFLIGHT, DONE } st = NONE;
         int pos = 0;
         int32_t tok = 0, sampled = -1;
+        int32_t n_top = -1;   /* the slot's log-probability setting when the row was planned */
+        TkTokenLogprob rec{}; /* DONE: the row's record, handed over with `sampled` */
         bool ok = true, discard = false;
         Request* waiter = nullptr;
     };
     void loop();
-    void plan_ahead(int slot, int pos_done, int32_t sampled, bool masked); /* mu_ held */
+    void plan_ahead(int slot, int pos_done, int32_t sampled, bool masked, int32_t n_top = -1); /* mu_ held */
     void drop_ahead(int slot);                                              /* mu_ held */
     std::vector<Ahead> ahead_;
     int32_t eos_ = -1;

@@ -100,10 +100,14 @@ public:
      * repetition penalties per row (common/tk_logit_adjust.h), applied to the row's logits before masks and sampling see them; every row is checked
      * before anything is enqueued.  A pass with at least one non-neutral row uploads the tables and replays graphs of its own (the ones with the
      * k_logit_adjust launch); any other pass replays the graphs it always did and uploads nothing.  logits_host of an adjusted row are the ADJUSTED
-     * logits */
+     * logits.  row_ntop (optional): [nrows] per row -1 = off, 0 .. TK_LOGPROB_MAX_TOP = the log-probability of the row's picked id and that many
+     * alternatives (common/tk_token_logprob.h) into records_host[r]; checked before anything is enqueued.  A pass with a row that asks uploads the
+     * table, replays graphs of its own (the ones with the k_token_logprobs launch behind the pick; adjusted or not: four families in all) and copies
+     * the pass's records back; a record is written as far as it was filled, a row that is off leaves records_host[r] alone; any other pass runs
+     * what it always did */
     bool forward(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, float* logits_host, int32_t* argmax_host,
                  bool lm_head = true, const uint32_t* const* row_masks = nullptr, const TkSampleRow* row_samp = nullptr,
-                 const TkLogitAdjust* row_adjust = nullptr);
+                 const TkLogitAdjust* row_adjust = nullptr, const int32_t* row_ntop = nullptr, TkTokenLogprob* records_host = nullptr);
     /* the verify pass of lookup decoding (tk_lookup.h): up to TK_MAX_ROWS greedy, unmasked, unadjusted rows; the rows of each sequence stand at
      * consecutive ascending positions and are contiguous in the pass; the head runs on ALL rows (picks_host[r] = arg max of row r, logits_host
      * optional).  form: the attention of the pass — 0 k_attention per row, 2 k_attention_prefill's 16-row tiles, 4 the run form of the long-context
@@ -127,7 +131,7 @@ public:
     bool prefill(int nseq, int n_prompt, const int32_t* tokens, int32_t* first_tokens_host);
     /* greedy decode loop, on-device feedback, hipGraph replay.  Starts from the rows' current
      * (tok, pos) state left by the previous forward()/decode(); out_tokens[n_steps][nrows].  The loop is unadjusted: it replays the plain
-     * graphs, and it clears the adjustment descriptors a previous forward() left as it clears the masks. */
+     * graphs, and it clears the adjustment descriptors and the log-probability table a previous forward() left as it clears the masks. */
     bool decode(int nrows, int n_steps, int32_t* out_tokens_host);
     bool reset();
     /* KV cache import / export: rows [pos0, pos0 + n_pos) of one (layer, sequence) as f16 bits, host arrays in [position][kv head][dim]
@@ -188,6 +192,12 @@ private:
     uint8_t* h_adj = nullptr;
     bool adj_dirty = false;   /* d_adj holds a non-neutral descriptor */
     bool adjust_pass = false; /* set by forward(), read by enqueue_range: the pass being enqueued launches k_logit_adjust before the pick */
+    /* log-probabilities of the rows of the current pass, at fixed addresses (the graphs below hold them): [TK_MAX_ROWS] n_top per row (-1 = off) and
+     * [TK_MAX_ROWS] records; h_lp_rec: pinned, the records of a pass on their way back */
+    int32_t* d_lp_ntop = nullptr;
+    TkTokenLogprob *d_lp_rec = nullptr, *h_lp_rec = nullptr;
+    bool lp_dirty = false;     /* d_lp_ntop holds something other than all -1 */
+    bool logprob_pass = false; /* set by forward(), read by enqueue_range: the pass being enqueued launches k_token_logprobs behind the pick */
     std::string launch_error; /* set by enqueue_* when a launcher refuses its arguments (no HIP error is raised for that) */
     int hist_cap = 0;
     hipGraphExec_t graph_exec[2][TK_MAX_ROWS + 1] = {}; /* [long_pass][row count]: decode pass (head + sampling, every sequence once) */
@@ -198,6 +208,9 @@ private:
     /* their siblings for passes with an adjusted row: the same launches plus k_logit_adjust in front of the pick */
     hipGraphExec_t graph_exec_adj[2][TK_MAX_ROWS + 1] = {};
     hipGraphExec_t graph_head_nf_adj[2][TK_MAX_ROWS + 1] = {};
+    /* and for passes with a row that asks for log-probabilities, [adjusted][...]: the same launches plus k_token_logprobs behind the pick */
+    hipGraphExec_t graph_exec_lp[2][2][TK_MAX_ROWS + 1] = {};
+    hipGraphExec_t graph_head_nf_lp[2][2][TK_MAX_ROWS + 1] = {};
     /* set by whoever describes a pass, read by enqueue_range: a multi-position pass that reaches position 128 (TK_TILED_ATT_FROM_POS) or beyond takes
      * k_attention_prefill (16 rows of a sequence per workgroup), shorter contexts k_attention's per-row form (3 us per launch quicker below ~128
      * positions, profiles/r05_prefill_attention.txt); the two are bit-identical, so the choice never shows in a result */

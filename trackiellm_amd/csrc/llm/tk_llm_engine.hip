@@ -406,6 +406,12 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     HIPQ(hipMalloc((void**)&d_adj_bias, (size_t)TK_MAX_ROWS * TK_ADJUST_MAX_BIAS * 4));
     HIPQ(hipHostMalloc((void**)&h_adj, TK_MAX_ROWS * (sizeof(TkAdjustRow) + (size_t)TK_ADJUST_MAX_RECENT * 4 + (size_t)TK_ADJUST_MAX_BIAS * 8), hipHostMallocDefault));
     adj_dirty = false;
+    HIPQ(hipMalloc((void**)&d_lp_ntop, TK_MAX_ROWS * 4));
+    HIPQ(hipMemset(d_lp_ntop, 0xFF, TK_MAX_ROWS * 4)); /* -1: no row asks */
+    HIPQ(hipMalloc((void**)&d_lp_rec, TK_MAX_ROWS * sizeof(TkTokenLogprob)));
+    HIPQ(hipMemset(d_lp_rec, 0, TK_MAX_ROWS * sizeof(TkTokenLogprob)));
+    HIPQ(hipHostMalloc((void**)&h_lp_rec, TK_MAX_ROWS * sizeof(TkTokenLogprob), hipHostMallocDefault));
+    lp_dirty = false;
     /* RoPE table, double precision on the host (same formula as the oracle) */
     std::vector<float> cs((size_t)mctx * half), sn((size_t)mctx * half);
     for (int p = 0; p < mctx; ++p)
@@ -444,6 +450,8 @@ TkLlmSession::~TkLlmSession() {
     for (auto& v : graph_exec_adj) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     for (auto& v : graph_head_nf_adj) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     for (auto& v : graph_verify) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
+    for (auto& f : graph_exec_lp) for (auto& v : f) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
+    for (auto& f : graph_head_nf_lp) for (auto& v : f) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     void* ptrs[] = {kcache, vcache, x, x2, qbuf, partial, partial2, logits, rope_cos, rope_sin, d_seq, d_pos, d_tok, d_nsteps, d_hist, d_mask, d_mask_row, d_samp, d_tab, d_tiles, d_scores};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (d_kvcopy) (void)hipFree(d_kvcopy);
@@ -451,6 +459,9 @@ TkLlmSession::~TkLlmSession() {
     void* adj[] = {d_adj, d_adj_ids, d_adj_bias_ids, d_adj_bias};
     for (void* p : adj) if (p) (void)hipFree(p);
     if (h_adj) (void)hipHostFree(h_adj);
+    if (d_lp_ntop) (void)hipFree(d_lp_ntop);
+    if (d_lp_rec) (void)hipFree(d_lp_rec);
+    if (h_lp_rec) (void)hipHostFree(h_lp_rec);
     free_act(&act_d); free_act(&act_qd); free_act(&act_ff);
     if (stream) (void)hipStreamDestroy(stream);
 }
@@ -1121,6 +1132,8 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
     /* llama.cpp's order: bias, penalties, grammar, chain — masks and sampling see the adjusted logits */
     if (adjust_pass) tk_launch_logit_adjust(logits, h.vocab, nrows, d_adj, d_adj_ids, d_adj_bias_ids, d_adj_bias, s);
     tk_launch_argmax(logits, h.vocab, nrows, d_mask, d_mask_row, d_samp, d_tok, d_pos, d_nsteps, d_hist, TK_MAX_ROWS, s);
+    /* the rows that ask: the log-probability of the id just picked, on the logits the pick read (adjusted, unmasked) */
+    if (logprob_pass) tk_launch_token_logprobs(logits, h.vocab, h.vocab, nrows, d_lp_ntop, d_tok, d_lp_rec, s);
 }
 
 static bool graphs_enabled() {
@@ -1170,9 +1183,15 @@ bool TkLlmSession::capture_pass(hipGraphExec_t* slot, int nrows, bool lm_head, b
 }
 
 bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, float* logits_host, int32_t* argmax_host,
-                           bool lm_head, const uint32_t* const* row_masks, const TkSampleRow* row_samp, const TkLogitAdjust* row_adjust) {
+                           bool lm_head, const uint32_t* const* row_masks, const TkSampleRow* row_samp, const TkLogitAdjust* row_adjust,
+                           const int32_t* row_ntop, TkTokenLogprob* records_host) {
     if (nrows <= 0 || nrows > TK_MAX_ROWS) { error = "nrows must be in [1,256]"; return false; }
-    bool any_adj = false;
+    bool any_adj = false, any_lp = false;
+    for (int r = 0; r < nrows && lm_head && row_ntop; ++r) {
+        if (const char* why = tk_logprob_check(row_ntop[r], model->hp.vocab)) { error = "log-probabilities of row " + std::to_string(r) + ": " + why; return false; }
+        any_lp = any_lp || row_ntop[r] >= 0;
+    }
+    if (any_lp && !records_host) { error = "log-probabilities asked for without records to fill"; return false; }
     for (int r = 0; r < nrows && lm_head && row_adjust; ++r) {
         if (const char* why = row_adjust[r].check(model->hp.vocab)) { error = "logit adjustment of row " + std::to_string(r) + ": " + why; return false; }
         any_adj = any_adj || !row_adjust[r].neutral();
@@ -1248,29 +1267,51 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
             HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream));
             adj_dirty = false;
         }
+        /* log-probabilities: the per-row n_top table, uploaded only when a row asks (pageable source: staged before the call returns) */
+        if (any_lp) {
+            int32_t ntab[TK_MAX_ROWS];
+            for (int r = 0; r < TK_MAX_ROWS; ++r) ntab[r] = r < nrows ? row_ntop[r] : -1;
+            HIPQ(hipMemcpyAsync(d_lp_ntop, ntab, TK_MAX_ROWS * 4, hipMemcpyHostToDevice, stream));
+            lp_dirty = true;
+        } else if (lp_dirty) {
+            HIPQ(hipMemsetAsync(d_lp_ntop, 0xFF, TK_MAX_ROWS * 4, stream));
+            lp_dirty = false;
+        }
     }
     adjust_pass = any_adj;
+    logprob_pass = any_lp;
     /* a pass replays a captured graph (one per (row count, form)): a host that asks for one token at a time — the reference's runner
      * API — pays one graph launch, not ~260 kernel launches, per token; masked rows ride the same graphs (the table above is data) */
     hipGraphExec_t* slot = !graphs_enabled() ? nullptr
                            : !lm_head ? &graph_prefill[tiled_pass][nrows] : distinct ? &graph_exec[long_pass][nrows] : &graph_head_nf[tiled_pass][nrows];
     if (slot && any_adj) slot = distinct ? &graph_exec_adj[long_pass][nrows] : &graph_head_nf_adj[tiled_pass][nrows];
+    if (slot && any_lp) slot = distinct ? &graph_exec_lp[any_adj][long_pass][nrows] : &graph_head_nf_lp[any_adj][tiled_pass][nrows];
     if (slot) {
         const bool captured = capture_pass(slot, nrows, lm_head, lm_head && distinct);
-        adjust_pass = false; /* whoever enqueues or captures next (decode(), prefill(), a pipeline stage) describes a plain pass */
+        adjust_pass = logprob_pass = false; /* whoever enqueues or captures next (decode(), prefill(), a pipeline stage) describes a plain pass */
         if (!captured) return false;
         HIPQ(hipGraphLaunch(*slot, stream));
     } else {
         launch_error.clear();
         enqueue_pass(nrows, lm_head, distinct);
-        adjust_pass = false;
+        adjust_pass = logprob_pass = false;
     }
     if (!launch_error.empty()) { error = launch_error; (void)hipStreamSynchronize(stream); return false; }
     HIPQ(hipGetLastError());
     if (!lm_head) { HIPQ(hipStreamSynchronize(stream)); return true; }
     if (logits_host) HIPQ(hipMemcpyAsync(logits_host, logits, (size_t)nrows * model->hp.vocab * 4, hipMemcpyDeviceToHost, stream));
     if (argmax_host) HIPQ(hipMemcpyAsync(argmax_host, d_tok, nrows * 4, hipMemcpyDeviceToHost, stream));
+    if (any_lp) HIPQ(hipMemcpyAsync(h_lp_rec, d_lp_rec, (size_t)nrows * sizeof(TkTokenLogprob), hipMemcpyDeviceToHost, stream));
     HIPQ(hipStreamSynchronize(stream));
+    /* the records of the rows that asked, as far as they were filled: everything else of records_host stays as the caller left it */
+    for (int r = 0; r < nrows && any_lp; ++r) {
+        if (row_ntop[r] < 0) continue;
+        const TkTokenLogprob& g = h_lp_rec[r];
+        TkTokenLogprob& o = records_host[r];
+        o.logprob = g.logprob;
+        o.n_top = g.n_top < 0 ? 0 : g.n_top > TK_LOGPROB_MAX_TOP ? TK_LOGPROB_MAX_TOP : g.n_top;
+        for (int j = 0; j < o.n_top; ++j) { o.top_ids[j] = g.top_ids[j]; o.top_logprobs[j] = g.top_logprobs[j]; }
+    }
     return true;
 }
 
@@ -1315,7 +1356,8 @@ bool TkLlmSession::forward_verify(int nrows, const int32_t* seq, const int32_t* 
     if (mask_rows_dirty) { HIPQ(hipMemsetAsync(d_mask_row, 0xFF, TK_MAX_ROWS * 4, stream)); mask_rows_dirty = false; }
     if (samp_dirty) { HIPQ(hipMemsetAsync(d_samp, 0, TK_MAX_ROWS * sizeof(TkSampleRow), stream)); samp_dirty = false; }
     if (adj_dirty) { HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream)); adj_dirty = false; }
-    adjust_pass = false;
+    if (lp_dirty) { HIPQ(hipMemsetAsync(d_lp_ntop, 0xFF, TK_MAX_ROWS * 4, stream)); lp_dirty = false; }
+    adjust_pass = logprob_pass = false;
     /* the pass is described here, not by choose_attention: rope/append always runs as a launch of its own (fused_attn = false) */
     const bool tiled_was = tiled_pass, long_was = long_pass;
     tiled_pass = form == 2; long_pass = false; run_pass = form == 4;
@@ -1358,6 +1400,7 @@ bool TkLlmSession::forward_stage(int nrows, const int32_t* seq, const int32_t* p
     HIPQ(hipMemsetAsync(d_nsteps, 0, TK_MAX_ROWS * 4, stream));
     if (mask_rows_dirty) { HIPQ(hipMemsetAsync(d_mask_row, 0xFF, TK_MAX_ROWS * 4, stream)); mask_rows_dirty = false; }
     if (adj_dirty) { HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream)); adj_dirty = false; }
+    if (lp_dirty) { HIPQ(hipMemsetAsync(d_lp_ntop, 0xFF, TK_MAX_ROWS * 4, stream)); lp_dirty = false; }
     const size_t xb = (size_t)nrows * h.d_model * 4;
     if (x_in) HIPQ(hipMemcpyAsync(x, x_in, xb, x_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
     bool distinct = true;
@@ -1440,6 +1483,7 @@ bool TkLlmSession::decode(int nrows, int n_steps, int32_t* out_tokens_host) {
     HIPQ(hipMemsetAsync(d_nsteps, 0, TK_MAX_ROWS * 4, stream));
     if (mask_rows_dirty) { HIPQ(hipMemsetAsync(d_mask_row, 0xFF, TK_MAX_ROWS * 4, stream)); mask_rows_dirty = false; } /* the loop samples unconstrained */
     if (adj_dirty) { HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream)); adj_dirty = false; } /* and unadjusted: it replays the plain graphs */
+    if (lp_dirty) { HIPQ(hipMemsetAsync(d_lp_ntop, 0xFF, TK_MAX_ROWS * 4, stream)); lp_dirty = false; } /* and reports no log-probabilities */
     hipEvent_t e0, e1;
     HIPQ(hipEventCreate(&e0));
     HIPQ(hipEventCreate(&e1));

@@ -105,6 +105,11 @@ void tk_launch_argmax(const float* logits, int vocab, int nrows, const uint32_t*
 /* logit bias + repetition penalties on logits [nrows][vocab], in place, before tk_launch_argmax: desc [nrows]; ids [nrows][TK_ADJUST_MAX_RECENT] the
  * rows' windows; bias_ids / bias [nrows][TK_ADJUST_MAX_BIAS].  The caller has checked every row with tk_adjust_check: the kernel trusts the ids */
 void tk_launch_logit_adjust(float* logits, int vocab, int nrows, const TkAdjustRow* desc, const int32_t* ids, const int32_t* bias_ids, const float* bias, hipStream_t s);
+#include "../common/tk_token_logprob.h"
+/* log-probability of the picked token and the n_top[r] most probable alternatives of every row with n_top[r] >= 0 (common/tk_token_logprob.h), after
+ * tk_launch_argmax on the logits it read: logits [nrows] rows of `vocab` floats `ld` apart; tok [nrows] the picked ids; rec [nrows].  The caller has
+ * checked n_top with tk_logprob_check (vocab <= 65536) and tok[r] is a token of the row */
+void tk_launch_token_logprobs(const float* logits, int vocab, int ld, int nrows, const int32_t* n_top, const int32_t* tok, TkTokenLogprob* rec, hipStream_t s);
 
 /* the attention launch a pass takes: kernel 0 = k_attention<gq, fused, head_dim, chunk> (chunk = positions per ring slot, slots = ring depth 2), kernel 1 =
  * k_attention_narrow (gq 2, chunk = positions resident per chunk, the whole context when it fits) */

@@ -4227,6 +4227,126 @@ void tk_launch_logit_adjust(float* logits, int vocab, int nrows, const TkAdjustR
 }
 
 /* ------------------------------------------------------------------------------------------
+ * log-probability of the picked token + the most probable alternatives (common/tk_token_logprob.h), behind k_argmax on the passes that carry a
+ * row that asks: one workgroup of 1024 lanes per row, on the logits the pick has just read (the head launch wrote them: they sit in L2 / MALL).
+ * A row with n_top = -1 returns after reading its descriptor.
+ * The row is read ONCE: lane t keeps the keys (tk_lp_key) of its tokens t, t + 1024, ... in NE registers (NE = 32 up to 32768 tokens, else 64;
+ * slots past the row hold key 0, below every real key).  From the registers: the maximum key (m is its logit), the sum of the terms in the
+ * header's fixed order, and the selection — the K-th largest key T found bit by bit from the top (32 rounds of "how many keys are >= P | bit",
+ * each a count over the registers, a wave sum and one barrier), then, only when more tokens tie at T than the list has room for, the highest
+ * id that still gets in, the same way over 16 id bits.  The at most 20 selected tokens go to LDS and are ranked by comparison; lane t < K
+ * writes entry t of the record; entries past the count are not written.  No histogram, no LDS atomics in the rounds.
+ * ------------------------------------------------------------------------------------------ */
+template <int NE>
+__global__ __launch_bounds__(TK_LOGPROB_LANES) void k_token_logprobs(const float* __restrict__ logits, int vocab, int ld, const int32_t* __restrict__ n_top,
+                                                                     const int32_t* __restrict__ tok, TkTokenLogprob* rec) {
+    __shared__ uint32_t red[2][16]; /* a round's wave counts, two buffers: one barrier per round */
+    __shared__ float wsum[16];
+    __shared__ float bc[2]; /* m, log S */
+    __shared__ uint32_t lkey[32], lid[32], nsel;
+    const int r = blockIdx.x, t = threadIdx.x;
+    const int nt = n_top[r];
+    if (nt < 0) return; /* uniform per workgroup */
+    const float* lg = logits + (int64_t)r * ld;
+    uint32_t key[NE];
+#pragma unroll
+    for (int j = 0; j < NE; ++j) { /* NE loads in flight; an index past the row loads a clamped element and keeps key 0 */
+        const int i = t + TK_LOGPROB_LANES * j;
+        const float v = lg[i < vocab ? i : vocab - 1];
+        key[j] = i < vocab ? tk_lp_key(v) : 0u;
+    }
+    if (t == 0) nsel = 0;
+    int buf = 0;
+    /* a value of every lane -> the workgroup's sum (counts) or maximum (keys), the same in every lane */
+    auto block_sum = [&](uint32_t c) {
+        for (int s = 32; s >= 1; s >>= 1) c += __shfl_xor(c, s, TK_WAVE);
+        if ((t & 63) == 0) red[buf][t >> 6] = c;
+        __syncthreads();
+        uint32_t tot = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) tot += red[buf][w];
+        buf ^= 1;
+        return tot;
+    };
+    uint32_t kmax = 0;
+#pragma unroll
+    for (int j = 0; j < NE; ++j) kmax = key[j] > kmax ? key[j] : kmax;
+    for (int s = 32; s >= 1; s >>= 1) { const uint32_t o = __shfl_xor(kmax, s, TK_WAVE); kmax = o > kmax ? o : kmax; }
+    if ((t & 63) == 0) red[buf][t >> 6] = kmax;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 16; ++w) kmax = red[buf][w] > kmax ? red[buf][w] : kmax;
+    buf ^= 1;
+    const float m = tk_lp_unkey(kmax); /* the logit of the first token: every token with that key holds the same bits */
+    float ssum = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NE; ++j) /* tk_lp_lane_sum's terms in its order, from the registers; key 0 = an empty slot (no logit but a NaN has it) */
+        if (key[j] != 0u) ssum = tk_lp_add(ssum, tk_lp_term(tk_lp_unkey(key[j]), m));
+    for (int s = 32; s >= 1; s >>= 1) ssum = tk_lp_add(ssum, __shfl_xor(ssum, s, TK_WAVE));
+    if ((t & 63) == 0) wsum[t >> 6] = ssum;
+    __syncthreads();
+    if (t == 0) {
+        const float logS = tk_logf(tk_lp_join_waves(wsum));
+        bc[1] = logS;
+        const int32_t id = tok[r];
+        /* the pick is a token of the row; one that is not (a mask that allows nothing) gets a NaN rather than a read outside the row */
+        rec[r].logprob = (uint32_t)id < (uint32_t)vocab ? tk_lp_logprob(lg[id], m, logS) : tk_bits_f32(0x7fc00000u);
+    }
+    const int K = nt < vocab ? nt : vocab; /* <= TK_LOGPROB_MAX_TOP */
+    if (K == 0) { if (t == 0) rec[r].n_top = 0; return; }
+    /* T = the K-th largest key: the largest P with at least K keys >= P */
+    uint32_t T = 0;
+    for (int b = 31; b >= 0; --b) {
+        const uint32_t cand = T | (1u << b);
+        uint32_t c = 0;
+#pragma unroll
+        for (int j = 0; j < NE; ++j) c += key[j] >= cand ? 1u : 0u;
+        if (block_sum(c) >= (uint32_t)K) T = cand;
+    }
+    uint32_t c_ge = 0, c_gt = 0;
+#pragma unroll
+    for (int j = 0; j < NE; ++j) { c_ge += key[j] >= T ? 1u : 0u; c_gt += key[j] > T ? 1u : 0u; }
+    c_ge = block_sum(c_ge);
+    c_gt = block_sum(c_gt);
+    /* the tokens above T all get in; of those at T the `room` lowest ids: X = the room-th lowest of them = the largest x with fewer than `room` ids below it */
+    uint32_t X = 0xFFFFFFFFu;
+    if (c_ge > (uint32_t)K) { /* uniform */
+        const uint32_t room = (uint32_t)K - c_gt;
+        X = 0;
+        for (int b = 15; b >= 0; --b) {
+            const uint32_t cand = X | (1u << b);
+            uint32_t c = 0;
+#pragma unroll
+            for (int j = 0; j < NE; ++j) c += (key[j] == T && (uint32_t)(t + TK_LOGPROB_LANES * j) < cand) ? 1u : 0u;
+            if (block_sum(c) < room) X = cand;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NE; ++j) {
+        const uint32_t id = (uint32_t)(t + TK_LOGPROB_LANES * j);
+        if (key[j] > T || (key[j] == T && id <= X)) { /* exactly K tokens in the whole workgroup (T >= 1: no empty slot) */
+            const uint32_t slot = atomicAdd(&nsel, 1u);
+            if (slot < 32u) { lkey[slot] = key[j]; lid[slot] = id; }
+        }
+    }
+    __syncthreads();
+    const float logS = bc[1];
+    if (t < K) { /* rank by comparison: descending key, ascending id */
+        const uint32_t k = lkey[t], id = lid[t];
+        int rank = 0;
+        for (int j = 0; j < K; ++j) rank += (lkey[j] > k || (lkey[j] == k && lid[j] < id)) ? 1 : 0;
+        rec[r].top_ids[rank] = (int32_t)id;
+        rec[r].top_logprobs[rank] = tk_lp_logprob(tk_lp_unkey(k), m, logS);
+    }
+    if (t == 0) rec[r].n_top = K;
+}
+
+void tk_launch_token_logprobs(const float* logits, int vocab, int ld, int nrows, const int32_t* n_top, const int32_t* tok, TkTokenLogprob* rec, hipStream_t s) {
+    if (vocab <= 32 * TK_LOGPROB_LANES) hipLaunchKernelGGL((k_token_logprobs<32>), dim3(nrows), dim3(TK_LOGPROB_LANES), 0, s, logits, vocab, ld, n_top, tok, rec);
+    else hipLaunchKernelGGL((k_token_logprobs<64>), dim3(nrows), dim3(TK_LOGPROB_LANES), 0, s, logits, vocab, ld, n_top, tok, rec);
+}
+
+/* ------------------------------------------------------------------------------------------
  * per-device opt-in to > 64 KiB of dynamic LDS for every kernel above (see the comment at TK_MAX_DYN_LDS)
  * ------------------------------------------------------------------------------------------ */
 const char* tk_llm_prepare_device(int device) {

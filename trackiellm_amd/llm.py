@@ -250,6 +250,48 @@ class Sampling(C.Structure):  # tk_mi355x_sampling_t
                 ("counter", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+LOGPROB_MAX_TOP = 20
+
+
+class TokenLogprob(C.Structure):  # tk_mi355x_token_logprob_t
+    _fields_ = [("logprob", C.c_float), ("n_top", C.c_int32), ("top_ids", C.c_int32 * LOGPROB_MAX_TOP), ("top_logprobs", C.c_float * LOGPROB_MAX_TOP)]
+
+
+# the same record as a NumPy dtype: arrays of records go to the library as they are, sentinels included
+TOKEN_LOGPROB_DTYPE = np.dtype([("logprob", np.float32), ("n_top", np.int32), ("top_ids", np.int32, (LOGPROB_MAX_TOP,)), ("top_logprobs", np.float32, (LOGPROB_MAX_TOP,))])
+assert TOKEN_LOGPROB_DTYPE.itemsize == C.sizeof(TokenLogprob)
+
+
+def token_logprobs_probe(logits, rows, cols, ids, n_top, records=None, ld=None, device=0, n_logits=None):
+    """ONE launch of k_token_logprobs (tk_mi355x_token_logprobs_probe): logits float32, `rows` rows of `cols` floats `ld` (default cols) apart; ids [rows]
+    the chosen id of every row; n_top [rows] (-1 = the row is off).  records: a C-contiguous TOKEN_LOGPROB_DTYPE array of `rows` entries that is
+    filled IN PLACE (whatever the launch does not write keeps the caller's bytes), or None for a zeroed one.  device < 0: the same row function in a
+    host loop, no GPU touched.  Returns the records; a refusal raises TkError with nothing written"""
+    logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1)
+    ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    n_top = np.ascontiguousarray(n_top, dtype=np.int32).reshape(-1)
+    if records is None:
+        records = np.zeros(max(int(rows), 1), TOKEN_LOGPROB_DTYPE)
+    if records.dtype != TOKEN_LOGPROB_DTYPE or not records.flags.c_contiguous:
+        raise ValueError("token_logprobs_probe: records must be a C-contiguous TOKEN_LOGPROB_DTYPE array")
+    if ids.size < rows or n_top.size < rows or records.size < rows:
+        raise ValueError("token_logprobs_probe: ids, n_top and records need one entry per row")
+    f = lib().tk_mi355x_token_logprobs_probe
+    f.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    check(f(int(device), int(rows), int(cols), int(cols if ld is None else ld), _p(logits), int(logits.size if n_logits is None else n_logits), _p(ids), _p(n_top),
+            _p(records)))
+    return records
+
+
+def time_token_logprobs(rows, cols, n_top, iters=200, device=0):
+    """average ms of one k_token_logprobs launch at rows x cols with every row asking for n_top alternatives (tk_mi355x_time_token_logprobs)"""
+    ms = C.c_float(0)
+    f = lib().tk_mi355x_time_token_logprobs
+    f.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]
+    check(f(int(device), int(rows), int(cols), int(n_top), int(iters), C.byref(ms)))
+    return ms.value
+
+
 def MISTRAL_7B():
     return LlmHParams(32, 4096, 32, 8, 128, 14336, 32000, 1e-5, 10000.0, 0, 0, 0, 0, 1)
 
@@ -378,6 +420,37 @@ class LlmSession:
         check(lib().tk_mi355x_llm_forward_adjusted(self.h, n, _p(seq), _p(pos), _p(tok), tab, adj, _p(logits), _p(ids)))
         del keep
         return logits, ids
+
+    def forward_logprobs(self, seq, pos, tok, n_top, adjust=None, sampling=None, want_logits=True, records=None):
+        """forward_adjusted() plus log-probability records (tk_mi355x_llm_forward_logprobs): n_top [rows], -1 = that row is off; adjust and sampling as
+        forward_adjusted's, or None.  records: a TOKEN_LOGPROB_DTYPE array filled in place (rows that are off and entries past a record's count keep
+        the caller's bytes), or None for a zeroed one.  Returns (logits or None, ids, records)"""
+        from .pick import logit_adjust_rows
+        seq = np.ascontiguousarray(seq, dtype=np.int32)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        tok = np.ascontiguousarray(tok, dtype=np.int32)
+        n = len(seq)
+        n_top = np.ascontiguousarray(n_top, dtype=np.int32).reshape(-1)
+        if n_top.size != n:
+            raise ValueError("forward_logprobs: one n_top per row")
+        tab = None
+        if sampling is not None:
+            tab = (Sampling * n)()
+            for r, (temp, top_k, top_p, min_p, seed, counter) in enumerate(sampling):
+                tab[r] = Sampling(temp, top_p, min_p, top_k, seed, counter, 0)
+        adj, keep = logit_adjust_rows(adjust) if adjust is not None else (None, None)
+        if records is None:
+            records = np.zeros(n, TOKEN_LOGPROB_DTYPE)
+        if records.dtype != TOKEN_LOGPROB_DTYPE or not records.flags.c_contiguous or records.size < n:
+            raise ValueError("forward_logprobs: records must be a C-contiguous TOKEN_LOGPROB_DTYPE array with one entry per row")
+        logits = np.empty((n, self.vocab), dtype=np.float32) if want_logits else None
+        ids = np.empty(n, dtype=np.int32)
+        f = lib().tk_mi355x_llm_forward_logprobs
+        f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
+        check(f(self.h, n, _p(seq), _p(pos), _p(tok), C.cast(tab, C.c_void_p) if tab is not None else None, C.cast(adj, C.c_void_p) if adj is not None else None,
+                _p(n_top), _p(logits), _p(ids), _p(records)))
+        del keep
+        return logits, ids, records
 
     def forward_verify(self, seq, pos, tok, form=-1, want_logits=True):
         """the verify pass of lookup decoding (tk_mi355x_llm_forward_verify): greedy rows, the rows of a sequence at consecutive ascending positions
@@ -704,6 +777,18 @@ class LlmRunner:
         """lookup decoding for a greedy runner (off by default; n_draft 0 = off): up to n_draft ids drafted per pass from the prediction, then from
         the context, by the longest n-gram of ngram_max .. ngram_min ids that ends the context (tk_mi355x_llm_runner_set_lookup)"""
         check(lib().tk_mi355x_llm_runner_set_lookup(self.h, int(n_draft), int(ngram_min), int(ngram_max)))
+
+    def set_logprobs(self, n_top):
+        """log-probabilities of every sampled token (off by default): -1 = off, 0 = the produced id only, 1 .. 20 = that many alternatives
+        (tk_mi355x_llm_runner_set_logprobs); from the next sampled token"""
+        check(lib().tk_mi355x_llm_runner_set_logprobs(self.h, int(n_top)))
+
+    def last_logprobs(self):
+        """the record of the id the last prepare() / next_token() sampled, as (logprob, [(id, logprob), ...]); raises TkError while the setting is off or
+        nothing has been sampled since it was switched on"""
+        rec = TokenLogprob()
+        check(lib().tk_mi355x_llm_runner_last_logprobs(self.h, C.byref(rec)))
+        return rec.logprob, [(rec.top_ids[j], rec.top_logprobs[j]) for j in range(rec.n_top)]
 
     def set_prediction(self, ids):
         """the host's prediction of the reply, as token ids (copied; an empty list clears it; it survives prepare())"""
