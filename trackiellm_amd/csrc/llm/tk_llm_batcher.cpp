@@ -115,7 +115,6 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
     r.slot = slot; r.pos0 = pos0; r.n = n; r.toks = toks; r.mask = mask;
     if (samp) r.samp = *samp;
     if (adjust && !adjust->neutral()) { r.adj = *adjust; r.adjusted = true; }
-    r.owner_hold = hold;
     r.n_top = n_top; r.rec = record;
     r.hold = hold || r.adjusted || (adjust && (adjust->repeat != 1.0f || adjust->freq != 0.0f || adjust->present != 0.0f));
     r.whole = prefix != nullptr && pos0 == 0;
@@ -129,12 +128,13 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
             if (a.st == Ahead::DONE) {
                 const bool ok = a.ok;
                 const int32_t got = a.sampled;
+                const std::string failed = a.error; /* of the pass that carried the row, not of whichever pass failed last */
                 if (ok && n_top >= 0) *record = a.rec; /* handed over with the id */
                 a = Ahead();
-                if (!ok) { *err = last_error_; return false; }
+                if (!ok) { *err = failed; return false; }
                 rows_++;
                 *sampled = got;
-                plan_ahead(slot, pos0, got, hold, n_top); /* hold: lookup was switched on while a row ran ahead; it is the last one */
+                plan_ahead(slot, pos0, got, r.hold, n_top); /* hold: lookup or the penalties were switched on while a row ran ahead; it is the last one */
                 cv_.notify_all();
                 return true;
             }
@@ -381,7 +381,6 @@ void TkLlmBatcher::loop() {
             std::lock_guard<std::mutex> lk(mu_);
             passes_++;
             if (nrows > max_rows_) max_rows_ = nrows;
-            if (!ok) last_error_ = session_.error;
             if (!copies.empty()) copy_launches_++;
             /* verify requests: the accept rule on the picks of their rows; the rows behind the last accepted one are not recorded */
             rejected.assign((size_t)nrows, 0);
@@ -436,7 +435,7 @@ void TkLlmBatcher::loop() {
                     if (!ok) w->error = session_.error;
                     w->sampled = got;
                     rows_++;
-                    if (ok) plan_ahead(s, pos, got, w->owner_hold, w->n_top);
+                    if (ok) plan_ahead(s, pos, got, w->hold, w->n_top);
                     w->finished = true;
                     w->cv.notify_all();
                 } else {
@@ -444,6 +443,7 @@ void TkLlmBatcher::loop() {
                     a.sampled = got;
                     if (ok && a.n_top >= 0) a.rec = recs[(size_t)ar.row]; /* held until the owner takes the id */
                     a.ok = ok;
+                    if (!ok) a.error = session_.error;
                 }
             }
             expect_ = held;

@@ -131,11 +131,10 @@ private:
         TkSampleRow samp{};
         TkLogitAdjust adj{};
         bool adjusted = false; /* adj is not neutral */
-        bool hold = false;     /* no run-ahead from this row: adjusted, or penalties that are on over a still empty window (the next one is not) */
+        bool hold = false;     /* no run-ahead from this row: submit's `hold`, adjusted, or penalties that are on over a still empty window (the next one is not) */
         int32_t sampled = -1;
         int32_t n_top = -1;           /* log-probabilities of the sampled row: -1 off */
         TkTokenLogprob* rec = nullptr; /* the owner's record, written before `finished` */
-        bool owner_hold = false;      /* submit's `hold` argument: the owner has lookup decoding on */
         bool verify = false;         /* a verify request: all n rows in one pass, every row sampled */
         std::vector<int32_t> ids;     /* what the accept rule kept of its picks (m + 1 ids) */
         bool finished = false, ok = true;
@@ -150,6 +149,7 @@ private:
         int32_t n_top = -1;   /* the slot's log-probability setting when the row was planned */
         TkTokenLogprob rec{}; /* DONE: the row's record, handed over with `sampled` */
         bool ok = true, discard = false;
+        std::string error;    /* DONE and not ok: the session's error of the pass that carried the row */
         Request* waiter = nullptr;
     };
     void loop();
@@ -158,7 +158,6 @@ private:
     std::vector<Ahead> ahead_;
     int32_t eos_ = -1;
     uint64_t wasted_ = 0;
-    std::string last_error_;
     TkLlmSession session_;
     int n_ctx_ = 0;
     std::vector<char> slot_used_;
