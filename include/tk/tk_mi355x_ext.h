@@ -470,6 +470,9 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_attention_plan_at(int device, int 
  * numbers as tk_mi355x_attention_plan(fused = 0) gives them */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_attention_plan_verify(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx,
                                                                     int top_position, int32_t out[4]);
+/* read-only: how many passes (and timing loops) the session has recorded into a hipGraph so far.  A session records one graph per (form of a pass,
+ * row count) at first use and replays it from then on; $TK_MI355X_NO_GRAPH=1 records none */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_graph_captures(tk_mi355x_llm_session_t* session, uint64_t* n);
 
 /* ---- tool-call grammar (GBNF) — the sampling constraint of tk_llm_runner_prepare_generation(..., use_tool_grammar = true)
  * (reference: src/ai_models/grammars/tool_call.gbnf via llama.cpp's grammar sampler, tk_runner_lifecycle.c:59,

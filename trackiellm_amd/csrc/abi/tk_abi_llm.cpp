@@ -571,28 +571,35 @@ tk_error_code_t tk_mi355x_attention_plan(int device, int nrows, int n_head, int 
     return TK_SUCCESS;
 }
 
+/* what a session of this geometry and window would know when it describes a pass of nrows rows (TkLlmSession::pass_caps) */
+static TkPassCaps plan_caps(int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx) {
+    return TkPassCaps{max_ctx > TK_LONG_ATT_MIN_POS, tk_attention_prefill_applies(n_head, n_kv_head, head_dim), tk_attention_long_applies(nrows, n_head, n_kv_head, head_dim)};
+}
+/* the launcher's plan in out[] with the session's per-pass choice (tk_pass_form.h) on top */
+static void plan_set_kernel(int32_t out[4], int kernel, int n_head, int n_kv_head) {
+    if (kernel >= 3) { out[1] = n_head / n_kv_head; out[2] = 64; out[3] = 1; }
+    out[0] = kernel;
+}
+
 tk_error_code_t tk_mi355x_attention_plan_at(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, int fused, int top_position, int32_t out[4]) {
     const tk_error_code_t rc = tk_mi355x_attention_plan(device, nrows, n_head, n_kv_head, head_dim, max_ctx, fused, out);
     if (rc != TK_SUCCESS) return rc;
     if (top_position < 0 || top_position >= max_ctx) return TK_ERROR_INVALID_ARGUMENT;
-    /* the session's per-pass choices (TkLlmSession::choose_attention_top) on top of the launcher's */
-    if (fused) {
-        if (max_ctx > TK_LONG_ATT_MIN_POS && tk_attention_long_applies(nrows, n_head, n_kv_head, head_dim) && top_position >= tk_long_att_min_pos(nrows)) {
-            out[0] = 3; out[1] = n_head / n_kv_head; out[2] = 64; out[3] = 1;
-        }
-    } else if (out[0] == 2 && top_position < 128) {
-        out[0] = 0;
-    }
+    plan_set_kernel(out, tk_plan_kernel_at(out[0], fused != 0, nrows, top_position, plan_caps(nrows, n_head, n_kv_head, head_dim, max_ctx)), n_head, n_kv_head);
     return TK_SUCCESS;
 }
 
 tk_error_code_t tk_mi355x_attention_plan_verify(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, int top_position, int32_t out[4]) {
-    const tk_error_code_t rc = tk_mi355x_attention_plan_at(device, nrows, n_head, n_kv_head, head_dim, max_ctx, 0, top_position, out);
+    const tk_error_code_t rc = tk_mi355x_attention_plan(device, nrows, n_head, n_kv_head, head_dim, max_ctx, 0, out);
     if (rc != TK_SUCCESS) return rc;
-    /* TkLlmSession::verify_form on top of a multi-position pass's plan */
-    if (max_ctx > TK_LONG_ATT_MIN_POS && tk_attention_long_applies(nrows, n_head, n_kv_head, head_dim) && top_position >= tk_verify_run_min_pos(nrows)) {
-        out[0] = 4; out[1] = n_head / n_kv_head; out[2] = 64; out[3] = 1;
-    }
+    if (top_position < 0 || top_position >= max_ctx) return TK_ERROR_INVALID_ARGUMENT;
+    plan_set_kernel(out, tk_plan_kernel_verify(out[0], nrows, top_position, plan_caps(nrows, n_head, n_kv_head, head_dim, max_ctx)), n_head, n_kv_head);
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_session_graph_captures(tk_mi355x_llm_session_t* s, uint64_t* n) {
+    if (!s || !n) return TK_ERROR_INVALID_ARGUMENT;
+    *n = s->session.n_captures;
     return TK_SUCCESS;
 }
 

@@ -15,10 +15,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "tk_llm_kernels.h"
+#include "tk_pass_form.h"
 
 struct TkLlmHParams {
     int32_t n_layer, d_model, n_head, n_kv_head, head_dim, d_ff, vocab;
@@ -98,11 +100,11 @@ public:
      * constrained and unconstrained rows share passes (and the captured graphs).  row_samp (optional): [nrows] sampling state, temp > 0
      * = the reference's default stochastic chain for that row (tk_llm_kernels.h), else greedy.  row_adjust (optional): [nrows] logit bias and
      * repetition penalties per row (common/tk_logit_adjust.h), applied to the row's logits before masks and sampling see them; every row is checked
-     * before anything is enqueued.  A pass with at least one non-neutral row uploads the tables and replays graphs of its own (the ones with the
+     * before anything is enqueued.  A pass with at least one non-neutral row uploads the tables and is a form of its own (TkPassForm::adjust: the
      * k_logit_adjust launch); any other pass replays the graphs it always did and uploads nothing.  logits_host of an adjusted row are the ADJUSTED
      * logits.  row_ntop (optional): [nrows] per row -1 = off, 0 .. TK_LOGPROB_MAX_TOP = the log-probability of the row's picked id and that many
      * alternatives (common/tk_token_logprob.h) into records_host[r]; checked before anything is enqueued.  A pass with a row that asks uploads the
-     * table, replays graphs of its own (the ones with the k_token_logprobs launch behind the pick; adjusted or not: four families in all) and copies
+     * table, is a form of its own (TkPassForm::logprobs: the k_token_logprobs launch behind the pick) and copies
      * the pass's records back; a record is written as far as it was filled, a row that is off leaves records_host[r] alone; any other pass runs
      * what it always did */
     bool forward(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, float* logits_host, int32_t* argmax_host,
@@ -112,14 +114,11 @@ public:
      * consecutive ascending positions and are contiguous in the pass; the head runs on ALL rows (picks_host[r] = arg max of row r, logits_host
      * optional).  form: the attention of the pass — 0 k_attention per row, 2 k_attention_prefill's 16-row tiles, 4 the run form of the long-context
      * attention (tk_llm_kernels.h; at most TK_LONG_ATT_MAX_ROWS rows, head_dim 64 or 128, a session whose window can reach TK_LONG_ATT_MIN_POS), all
-     * three bit-identical; -1 = the session's choice (verify_form).  A form that does not apply is refused before anything is enqueued
-     * (*bad_args, optional, tells that from a device error).  The pass replays graphs of its own ([form][row count]): forward()'s graphs and
-     * choose_attention are untouched, and the run form is chosen through this entry only. */
+     * three bit-identical; -1 = the session's choice (tk_verify_form).  A form that does not apply is refused before anything is enqueued
+     * (*bad_args, optional, tells that from a device error).  Forms 0 and 2 are the forms of a sampling pass that holds several positions of a
+     * sequence and share its graphs; the run form is chosen through this entry only. */
     bool forward_verify(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, int form, float* logits_host, int32_t* picks_host,
                         bool* bad_args = nullptr);
-    /* the form forward_verify(form = -1) takes for nrows rows whose highest position is `top`: 4 from tk_verify_run_min_pos(nrows) where the run form
-     * applies, else 2 from position 128 where k_attention_prefill applies, else 0 */
-    int verify_form(int nrows, int top) const;
     /* one pipeline stage of a pass: layers [l0, l1) on this GPU.  The first stage starts from `tok` (x_in == nullptr), later stages
      * from the residual stream x_in [nrows][d_model] fp32; every stage but the last writes the stream to x_out; the last one
      * (head == true, l1 == n_layer) samples.  x_on_host: x_in / x_out are host pointers (gloo transport), otherwise device
@@ -130,8 +129,8 @@ public:
      * holding the first sampled token so decode() can follow; first_tokens_host[nseq] optional */
     bool prefill(int nseq, int n_prompt, const int32_t* tokens, int32_t* first_tokens_host);
     /* greedy decode loop, on-device feedback, hipGraph replay.  Starts from the rows' current
-     * (tok, pos) state left by the previous forward()/decode(); out_tokens[n_steps][nrows].  The loop is unadjusted: it replays the plain
-     * graphs, and it clears the adjustment descriptors and the log-probability table a previous forward() left as it clears the masks. */
+     * (tok, pos) state left by the previous forward()/decode(); out_tokens[n_steps][nrows].  The loop is unadjusted: its passes are plain
+     * forms, and it clears the adjustment descriptors and the log-probability table a previous forward() left as it clears the masks. */
     bool decode(int nrows, int n_steps, int32_t* out_tokens_host);
     bool reset();
     /* KV cache import / export: rows [pos0, pos0 + n_pos) of one (layer, sequence) as f16 bits, host arrays in [position][kv head][dim]
@@ -170,9 +169,39 @@ public:
 private:
     friend class TkLlmPipe; /* tk_llm_pipe.h: a pipeline stage enqueues layer ranges of this session between its hand-off kernels */
     int last_ks_res = 1;    /* slabs of the residual update the last enqueue_range left pending in `partial` */
-    void enqueue_pass(int nrows, bool lm_head, bool fused_attn);
-    void enqueue_range(int nrows, int l0, int l1, bool embed, bool fold_out, bool lm_head, bool fused_attn);
+    /* A pass is described once, as a TkPassForm (tk_pass_form.h; DESIGN.md "The forms of a pass"), by the entry that runs it; these launch what
+     * the form says and hold no state of their own about it */
+    TkPassCaps pass_caps(int nrows) const;
+    void enqueue_pass(int nrows, const TkPassForm& f);
+    void enqueue_range(int nrows, int l0, int l1, bool embed, bool fold_out, const TkPassForm& f);
+    void enqueue_attention(const TkPassForm& f, const float* qkv_slab, int ks_qkv, int layer, int nrows);
     int enqueue_matmul(const TkDevTensor* const* t, int nseg, int K, int ks, int n_total, const TkActQ8& act, float* out, int nrows);
+    /* the pass on the stream: a replay of its graph, recorded at first use (one per (form, row count)) — a host that asks for one token at a time,
+     * the reference's runner API, pays one graph launch, not ~260 kernel launches, per token —, or eager launches (TK_MI355X_NO_GRAPH=1) */
+    bool launch_pass(const TkPassForm& f, int nrows, bool use_graph);
+    hipGraphExec_t capture_pass(const TkPassForm& f, int nrows); /* nullptr: failed, `error` says why */
+    hipGraphExec_t graphs[TK_PASS_FORM_KEYS][TK_MAX_ROWS + 1] = {}; /* [tk_pass_form_key][row count] */
+    /* THE capture path of the process: `enqueue` recorded from `stream` into *slot (untouched when it holds a graph already), one capture at a time
+     * per process.  The stream always leaves capture mode and the graph is always freed; a launcher's refusal (launch_error) or a HIP error
+     * leaves *slot null and `error` set ("graph capture of <what> failed: ...").  Counts into n_captures / capture_ms */
+    bool capture(hipGraphExec_t* slot, const char* what, const std::function<void()>& enqueue);
+    /* the timing entries' loop: warm(), then launch(0 .. iters - 1) recorded into one graph, replayed once untimed and once between two events
+     * (TK_MI355X_NO_GRAPH=1: the launches themselves between the events); *avg_ms = one launch */
+    bool time_launches(int iters, const std::function<void()>& warm, const std::function<void(int)>& launch, float* avg_ms);
+    /* Row plumbing of the host-described entries.  check_pass_rows: 1 <= nrows <= TK_MAX_ROWS and every (sequence, position, token) inside the session
+     * (tok may be null: a later pipeline stage); *top = the highest position, *distinct (optional) = no sequence twice.  upload_rows: the rows'
+     * tables to the device (d_tok only when given) and the decode history's step counts cleared.  clear_row_tables: the per-row tables an earlier
+     * forward() may have left and this pass does not want, each only when it is dirty.  Who clears what:
+     *   forward() with the head      uploads or clears all four itself, table by table, as its rows ask
+     *   forward() without the head   nothing: no launch of the pass reads a table
+     *   forward_verify()             masks, sampling, adjust, logprobs: greedy, unmasked, unadjusted rows, whatever an earlier pass left
+     *   forward_stage()              masks, adjust, logprobs; d_samp stays (a stale stochastic row would sample: see DESIGN.md)
+     *   decode()                     masks, adjust, logprobs; d_samp stays ON PURPOSE: the loop continues the rows' sampling state
+     *   TkLlmPipe::pass / ::decode   masks only: a pipe's session is fed by the pipe alone, which never sets the other three */
+    enum { TK_ROWS_MASKS = 1, TK_ROWS_SAMPLING = 2, TK_ROWS_ADJUST = 4, TK_ROWS_LOGPROBS = 8 };
+    bool check_pass_rows(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, int* top, bool* distinct);
+    bool upload_rows(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok);
+    bool clear_row_tables(unsigned which);
     uint16_t *kcache = nullptr, *vcache = nullptr;
     float *x = nullptr, *x2 = nullptr, *qbuf = nullptr, *partial = nullptr, *partial2 = nullptr, *logits = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
     TkActQ8 act_d{}, act_qd{}, act_ff{};
@@ -183,7 +212,7 @@ private:
     TkSampleRow* d_samp = nullptr;  /* [TK_MAX_ROWS] sampling state of the rows of the current pass (temp 0 = greedy); decode() continues from it */
     bool samp_dirty = false;        /* d_samp holds a stochastic row */
     TkKvCopyDesc *d_kvcopy = nullptr, *h_kvcopy = nullptr; /* [TK_MAX_ROWS] descriptors of one k_kv_copy_rows launch: device array, pinned staging */
-    /* logit adjustment of the rows of the current pass, at fixed addresses (the adjusted graphs hold them): [TK_MAX_ROWS] descriptors, the rows'
+    /* logit adjustment of the rows of the current pass, at fixed addresses (the graphs hold them): [TK_MAX_ROWS] descriptors, the rows'
      * windows [TK_MAX_ROWS][TK_ADJUST_MAX_RECENT], bias ids and values [TK_MAX_ROWS][TK_ADJUST_MAX_BIAS]; h_adj: one pinned staging block of
      * the four in that order (free again when forward() has waited for the stream) */
     TkAdjustRow* d_adj = nullptr;
@@ -191,49 +220,21 @@ private:
     float* d_adj_bias = nullptr;
     uint8_t* h_adj = nullptr;
     bool adj_dirty = false;   /* d_adj holds a non-neutral descriptor */
-    bool adjust_pass = false; /* set by forward(), read by enqueue_range: the pass being enqueued launches k_logit_adjust before the pick */
-    /* log-probabilities of the rows of the current pass, at fixed addresses (the graphs below hold them): [TK_MAX_ROWS] n_top per row (-1 = off) and
+    /* log-probabilities of the rows of the current pass, at fixed addresses (the graphs hold them): [TK_MAX_ROWS] n_top per row (-1 = off) and
      * [TK_MAX_ROWS] records; h_lp_rec: pinned, the records of a pass on their way back */
     int32_t* d_lp_ntop = nullptr;
     TkTokenLogprob *d_lp_rec = nullptr, *h_lp_rec = nullptr;
     bool lp_dirty = false;     /* d_lp_ntop holds something other than all -1 */
-    bool logprob_pass = false; /* set by forward(), read by enqueue_range: the pass being enqueued launches k_token_logprobs behind the pick */
     std::string launch_error; /* set by enqueue_* when a launcher refuses its arguments (no HIP error is raised for that) */
     int hist_cap = 0;
-    hipGraphExec_t graph_exec[2][TK_MAX_ROWS + 1] = {}; /* [long_pass][row count]: decode pass (head + sampling, every sequence once) */
-    /* [tiled_pass][row count]: prompt pass (no head, rope/append as its own kernel); sampling pass that holds several positions of one sequence
-     * (a prompt's last chunk) */
-    hipGraphExec_t graph_prefill[2][TK_MAX_ROWS + 1] = {};
-    hipGraphExec_t graph_head_nf[2][TK_MAX_ROWS + 1] = {};
-    /* their siblings for passes with an adjusted row: the same launches plus k_logit_adjust in front of the pick */
-    hipGraphExec_t graph_exec_adj[2][TK_MAX_ROWS + 1] = {};
-    hipGraphExec_t graph_head_nf_adj[2][TK_MAX_ROWS + 1] = {};
-    /* and for passes with a row that asks for log-probabilities, [adjusted][...]: the same launches plus k_token_logprobs behind the pick */
-    hipGraphExec_t graph_exec_lp[2][2][TK_MAX_ROWS + 1] = {};
-    hipGraphExec_t graph_head_nf_lp[2][2][TK_MAX_ROWS + 1] = {};
-    /* set by whoever describes a pass, read by enqueue_range: a multi-position pass that reaches position 128 (TK_TILED_ATT_FROM_POS) or beyond takes
-     * k_attention_prefill (16 rows of a sequence per workgroup), shorter contexts k_attention's per-row form (3 us per launch quicker below ~128
-     * positions, profiles/r05_prefill_attention.txt); the two are bit-identical, so the choice never shows in a result */
-    bool tiled_pass = false;
-    /* a decode pass (every sequence once) of at most TK_LONG_ATT_MAX_ROWS rows that reaches position TK_LONG_ATT_MIN_POS runs its attention as
-     * append + scores + PV launches spread over the chip (tk_launch_attention_long) instead of one latency chain per pair of heads; bit-identical */
-    bool long_pass = false;
-    /* set by forward_verify only: the multi-position pass being enqueued takes the run form of the long-context attention (rope/append launch,
-     * then tk_launch_attention_long(run)); verify passes replay graph_verify[form / 2][row count] */
-    bool run_pass = false;
-    hipGraphExec_t graph_verify[3][TK_MAX_ROWS + 1] = {};
     bool counted_ = false; /* this session is in the device's count of live decode sessions (tk_attention_note_session) */
     float* d_scores = nullptr; /* [TK_LONG_ATT_MAX_ROWS][n_head][max_ctx], allocated when the window can reach TK_LONG_ATT_MIN_POS */
-    void choose_attention(const int32_t* pos, int nrows);
-    void choose_attention_top(int top, int nrows);
     int32_t* d_tab = nullptr;                           /* prefill schedule: [3][total rows] = seq, pos, tok */
     int32_t* d_tiles = nullptr;                         /* [1 + TK_MAX_ROWS] 16-row tiles of a multi-position pass (k_att_tiles) */
     size_t tab_cap = 0;
-    bool capture_pass(hipGraphExec_t* slot, int nrows, bool lm_head, bool fused_attn);
 public:
     uint64_t n_captures = 0; /* passes recorded into a graph so far, and the host time that took (diagnostics: TK_MI355X_BATCHER_TRACE) */
     double capture_ms = 0.0;
-private:
 };
 
 /* one production float matmul (tk_mi355x_llm_matmul_float_probe): w [rows][K] row-major values of `type` (1 F16, 30 BF16, 0 F32), rows = the sum of

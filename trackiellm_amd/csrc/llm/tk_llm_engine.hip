@@ -444,14 +444,7 @@ TkLlmSession::~TkLlmSession() {
     if (model && counted_) tk_attention_note_session(model->device, -1);
     if (model) (void)hipSetDevice(model->device);
     if (stream) (void)hipStreamSynchronize(stream);
-    for (auto& v : graph_exec) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
-    for (auto& v : graph_prefill) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
-    for (auto& v : graph_head_nf) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
-    for (auto& v : graph_exec_adj) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
-    for (auto& v : graph_head_nf_adj) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
-    for (auto& v : graph_verify) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
-    for (auto& f : graph_exec_lp) for (auto& v : f) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
-    for (auto& f : graph_head_nf_lp) for (auto& v : f) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
+    for (auto& v : graphs) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
     void* ptrs[] = {kcache, vcache, x, x2, qbuf, partial, partial2, logits, rope_cos, rope_sin, d_seq, d_pos, d_tok, d_nsteps, d_hist, d_mask, d_mask_row, d_samp, d_tab, d_tiles, d_scores};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (d_kvcopy) (void)hipFree(d_kvcopy);
@@ -1001,11 +994,11 @@ bool tk_llm_matmul_float_probe(int device, int type, const void* w, int64_t rows
     return ok;
 }
 
-void TkLlmSession::enqueue_pass(int nrows, bool lm_head, bool fused_attn) { enqueue_range(nrows, 0, model->hp.n_layer, true, false, lm_head, fused_attn); }
+void TkLlmSession::enqueue_pass(int nrows, const TkPassForm& f) { enqueue_range(nrows, 0, model->hp.n_layer, true, false, f); }
 
 /* layers [l0, l1) of one pass.  embed: the residual stream starts from the token embeddings (first pipeline stage), otherwise x
  * already holds it.  fold_out: finish the last layer's residual update so x is the complete stream (it leaves this GPU).
- * head: final norm + lm_head + arg max (last stage). */
+ * f: the form of the pass (tk_pass_form.h); f.head: final norm + lm_head + arg max (last stage). */
 /* one matmul group of a pass: the K-quant tensors of a launch go to the W4A8 kernels (K-split partial slabs, canonical plan `ks`); a float
  * group (F16 / BF16 / F32) goes through the exact fp32 GEMM on the activations rounded through that type (per slab one chain over its k).  Returns
  * the number of partial slabs the consumers must add. */
@@ -1035,7 +1028,22 @@ static bool producer_fusion_enabled() {
     return !(nf && nf[0] == '1');
 }
 
-void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fold_out, bool lm_head, bool fused_attn) {
+/* rope/append and attention of one layer on the q|k|v slabs in `qkv_slab`, as the form says */
+void TkLlmSession::enqueue_attention(const TkPassForm& f, const float* qkv_slab, int ks_qkv, int l, int nrows) {
+    const TkLlmHParams& h = model->hp;
+    const int n_qkv = (h.n_head + 2 * h.n_kv_head) * h.head_dim;
+    hipStream_t s = stream;
+    if (!f.rope_in_attention)
+        tk_launch_qkv_rope_append(qkv_slab, ks_qkv, n_qkv, h.n_head, h.n_kv_head, h.head_dim, rope_cos, rope_sin, d_seq, d_pos, nrows, qbuf, kcache, vcache, l, max_seq, max_ctx, s);
+    if (f.attn == TK_ATT_LONG || f.attn == TK_ATT_RUN)
+        tk_launch_attention_long(qkv_slab, ks_qkv, n_qkv, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, d_scores, act_qd, s, f.attn == TK_ATT_RUN);
+    else if (f.attn == TK_ATT_TILED)
+        tk_launch_attention_prefill(qbuf, kcache, vcache, d_seq, d_pos, d_tiles, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, act_qd, s);
+    else
+        tk_launch_attention(qbuf, qkv_slab, ks_qkv, n_qkv, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, act_qd, f.rope_in_attention, s);
+}
+
+void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fold_out, const TkPassForm& f) {
     const TkLlmHParams& h = model->hp;
     const int D = h.d_model, QD = h.n_head * h.head_dim, KVD = h.n_kv_head * h.head_dim, FF = h.d_ff;
     hipStream_t s = stream;
@@ -1065,14 +1073,14 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
         tk_launch_gemv(a, s);
         return ks;
     };
-    /* passes that hold several positions of a sequence (prompt chunks): 16 rows of a sequence per attention workgroup on the fp32 matrix pipe
-     * (k_attention_prefill, bit-identical to k_attention); the row -> tile table is built once per pass from the sequence ids on the device */
-    /* the verify pass of lookup decoding over a long context (forward_verify only): rope/append as its own launch, then the long form's run variant */
-    const bool run_attn = !fused_attn && l1 > l0 && run_pass && d_scores && tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim);
-    const bool tiled_attn = !fused_attn && !run_attn && l1 > l0 && tiled_pass && tk_attention_prefill_applies(h.n_head, h.n_kv_head, h.head_dim);
-    /* few rows over a long context: the fused kernels would walk it as one latency chain per pair of heads */
-    const bool long_attn = fused_attn && l1 > l0 && long_pass && d_scores && tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim);
-    if (tiled_attn) tk_launch_att_tiles(d_seq, nrows, d_tiles, s);
+    /* a form is only ever built by tk_pass_form.h's resolvers; one that names a launch its other fields rule out would read what nobody wrote */
+    const bool scored = f.attn == TK_ATT_LONG || f.attn == TK_ATT_RUN;
+    if ((f.rope_in_attention ? f.attn == TK_ATT_TILED || f.attn == TK_ATT_RUN : f.attn == TK_ATT_LONG) || (scored && !d_scores)) {
+        if (launch_error.empty()) launch_error = "a pass was described in a form that does not exist";
+        return;
+    }
+    /* k_attention_prefill's row -> tile table: built once per pass from the sequence ids on the device */
+    if (f.attn == TK_ATT_TILED && l1 > l0) tk_launch_att_tiles(d_seq, nrows, d_tiles, s);
     int ks_res = 1; /* slabs of the pending residual update (the previous layer's down projection) */
     for (int l = l0; l < l1; ++l) {
         const TkLlmLayer& L = model->layers[l];
@@ -1082,13 +1090,7 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
         const TkDevTensor* dn[1] = {&L.down};
         if (fuse) {
             const int ks_qkv = fused_gemv(qkv, 3, D, h.ks_qkv, QD + 2 * KVD, partial2, 1, x, x2, l == l0 ? nullptr : partial, ks_res, D, (const float*)L.attn_norm.data);
-            if (!fused_attn)
-                tk_launch_qkv_rope_append(partial2, ks_qkv, QD + 2 * KVD, h.n_head, h.n_kv_head, h.head_dim, rope_cos, rope_sin, d_seq, d_pos, nrows,
-                                          qbuf, kcache, vcache, l, max_seq, max_ctx, s);
-            if (long_attn || run_attn) tk_launch_attention_long(partial2, ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, d_scores, act_qd, s, run_attn);
-            else if (tiled_attn) tk_launch_attention_prefill(qbuf, kcache, vcache, d_seq, d_pos, d_tiles, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, act_qd, s);
-            else tk_launch_attention(qbuf, partial2, ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head,
-                                     h.head_dim, l, max_seq, max_ctx, act_qd, fused_attn, s);
+            enqueue_attention(f, partial2, ks_qkv, l, nrows);
             const int ks_o = enqueue_matmul(ot, 1, QD, h.ks_o, D, act_qd, partial, nrows);
             const int ks_gu = fused_gemv(gu, 2, D, h.ks_gateup, 2 * FF, partial2, 1, x2, x, partial, ks_o, D, (const float*)L.ffn_norm.data);
             ks_res = fused_gemv(dn, 1, FF, h.ks_down, D, partial, 2, nullptr, nullptr, partial2, ks_gu, 2 * FF, nullptr);
@@ -1096,13 +1098,7 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
         }
         tk_launch_rmsnorm_q8(x, l == l0 ? nullptr : partial, ks_res, D, (const float*)L.attn_norm.data, h.rms_eps, D, nrows, act_d, s);
         const int ks_qkv = enqueue_matmul(qkv, 3, D, h.ks_qkv, QD + 2 * KVD, act_d, partial, nrows);
-        if (!fused_attn)
-            tk_launch_qkv_rope_append(partial, ks_qkv, QD + 2 * KVD, h.n_head, h.n_kv_head, h.head_dim, rope_cos, rope_sin, d_seq, d_pos, nrows,
-                                      qbuf, kcache, vcache, l, max_seq, max_ctx, s);
-        if (long_attn || run_attn) tk_launch_attention_long(partial, ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, d_scores, act_qd, s, run_attn);
-        else if (tiled_attn) tk_launch_attention_prefill(qbuf, kcache, vcache, d_seq, d_pos, d_tiles, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, act_qd, s);
-        else tk_launch_attention(qbuf, partial, ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head,
-                                 h.head_dim, l, max_seq, max_ctx, act_qd, fused_attn, s);
+        enqueue_attention(f, partial, ks_qkv, l, nrows);
         const int ks_o = enqueue_matmul(ot, 1, QD, h.ks_o, D, act_qd, partial, nrows);
         tk_launch_rmsnorm_q8(x, partial, ks_o, D, (const float*)L.ffn_norm.data, h.rms_eps, D, nrows, act_d, s);
         if (tk_gemv_fuses_swiglu(nrows, h.ks_gateup, L.gate.type, L.up.type)) { /* wide pass: SwiGLU in the launch's epilogue, `partial` holds h [rows][FF] */
@@ -1119,7 +1115,7 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
         ks_res = enqueue_matmul(dn, 1, FF, h.ks_down, D, act_ff, partial, nrows);
     }
     last_ks_res = ks_res;
-    if (!lm_head) { /* prompt rows whose logits nobody reads (K/V are already appended), or a pipeline stage that hands x on */
+    if (!f.head) { /* prompt rows whose logits nobody reads (K/V are already appended), or a pipeline stage that hands x on */
         if (fold_out && l1 > l0) tk_launch_residual_fold(x, partial, ks_res, D, D, nrows, s);
         return;
     }
@@ -1130,10 +1126,10 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
         (void)enqueue_matmul(lm, 1, D, 1, h.vocab, act_d, logits, nrows);
     }
     /* llama.cpp's order: bias, penalties, grammar, chain — masks and sampling see the adjusted logits */
-    if (adjust_pass) tk_launch_logit_adjust(logits, h.vocab, nrows, d_adj, d_adj_ids, d_adj_bias_ids, d_adj_bias, s);
+    if (f.adjust) tk_launch_logit_adjust(logits, h.vocab, nrows, d_adj, d_adj_ids, d_adj_bias_ids, d_adj_bias, s);
     tk_launch_argmax(logits, h.vocab, nrows, d_mask, d_mask_row, d_samp, d_tok, d_pos, d_nsteps, d_hist, TK_MAX_ROWS, s);
     /* the rows that ask: the log-probability of the id just picked, on the logits the pick read (adjusted, unmasked) */
-    if (logprob_pass) tk_launch_token_logprobs(logits, h.vocab, h.vocab, nrows, d_lp_ntop, d_tok, d_lp_rec, s);
+    if (f.logprobs) tk_launch_token_logprobs(logits, h.vocab, h.vocab, nrows, d_lp_ntop, d_tok, d_lp_rec, s);
 }
 
 static bool graphs_enabled() {
@@ -1142,22 +1138,18 @@ static bool graphs_enabled() {
     return !(ng && ng[0] == '1');
 }
 
+/* two events that are released on every path */
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t create() { const hipError_t e = hipEventCreate(&e0); return e != hipSuccess ? e : hipEventCreate(&e1); }
+    ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
 /* one capture at a time per process; relaxed mode: other host threads (detector / ASR / VAD streams) keep calling allocation and copy
  * APIs while this stream records */
 static std::mutex g_capture_mu;
 
-static constexpr int TK_TILED_ATT_FROM_POS = 128; /* see TkLlmSession::tiled_pass */
-void TkLlmSession::choose_attention(const int32_t* pos, int nrows) {
-    int top = 0;
-    for (int r = 0; r < nrows; ++r) top = pos[r] > top ? pos[r] : top;
-    choose_attention_top(top, nrows);
-}
-void TkLlmSession::choose_attention_top(int top, int nrows) {
-    tiled_pass = top >= TK_TILED_ATT_FROM_POS;
-    long_pass = d_scores != nullptr && nrows <= TK_LONG_ATT_MAX_ROWS && top >= tk_long_att_min_pos(nrows);
-}
-
-bool TkLlmSession::capture_pass(hipGraphExec_t* slot, int nrows, bool lm_head, bool fused_attn) {
+bool TkLlmSession::capture(hipGraphExec_t* slot, const char* what, const std::function<void()>& enqueue) {
     if (*slot) return true;
     const auto t_cap = std::chrono::steady_clock::now();
     struct Tally { TkLlmSession* s; std::chrono::steady_clock::time_point t0; ~Tally() { s->n_captures++; s->capture_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } tally{this, t_cap};
@@ -1165,7 +1157,7 @@ bool TkLlmSession::capture_pass(hipGraphExec_t* slot, int nrows, bool lm_head, b
     hipGraph_t g = nullptr;
     HIPQ(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed));
     launch_error.clear();
-    enqueue_pass(nrows, lm_head, fused_attn);
+    enqueue();
     /* from here on the stream must leave capture mode and the graph must be freed whatever fails */
     const hipError_t e_end = hipStreamEndCapture(stream, &g);
     hipError_t e_inst = hipSuccess;
@@ -1176,17 +1168,76 @@ bool TkLlmSession::capture_pass(hipGraphExec_t* slot, int nrows, bool lm_head, b
         *slot = nullptr;
         (void)hipGetLastError();
         error = !launch_error.empty() ? launch_error
-                : std::string("graph capture of a pass failed: ") + hipGetErrorString(e_end != hipSuccess ? e_end : e_inst);
+                : std::string("graph capture of ") + what + " failed: " + hipGetErrorString(e_end != hipSuccess ? e_end : e_inst);
         return false;
     }
+    return true;
+}
+
+hipGraphExec_t TkLlmSession::capture_pass(const TkPassForm& f, int nrows) {
+    hipGraphExec_t* slot = &graphs[tk_pass_form_key(f)][nrows];
+    if (*slot) return *slot; /* the replay path: an index, nothing built */
+    return capture(slot, "a pass", [&] { enqueue_pass(nrows, f); }) ? *slot : nullptr;
+}
+
+bool TkLlmSession::launch_pass(const TkPassForm& f, int nrows, bool use_graph) {
+    if (use_graph) {
+        const hipGraphExec_t g = capture_pass(f, nrows);
+        if (!g) return false;
+        HIPQ(hipGraphLaunch(g, stream));
+        return true;
+    }
+    launch_error.clear();
+    enqueue_pass(nrows, f);
+    if (!launch_error.empty()) { error = launch_error; (void)hipStreamSynchronize(stream); return false; }
+    return true;
+}
+
+TkPassCaps TkLlmSession::pass_caps(int nrows) const {
+    const TkLlmHParams& h = model->hp;
+    return TkPassCaps{d_scores != nullptr, tk_attention_prefill_applies(h.n_head, h.n_kv_head, h.head_dim), tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim)};
+}
+
+bool TkLlmSession::check_pass_rows(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, int* top, bool* distinct) {
+    if (nrows <= 0 || nrows > TK_MAX_ROWS) { error = "nrows must be in [1,256]"; return false; }
+    *top = 0;
+    for (int r = 0; r < nrows; ++r) {
+        if (seq[r] < 0 || seq[r] >= max_seq || pos[r] < 0 || pos[r] >= max_ctx || (tok && (tok[r] < 0 || tok[r] >= model->hp.vocab))) {
+            error = "row out of range (sequence id, position or token id)";
+            return false;
+        }
+        *top = pos[r] > *top ? pos[r] : *top;
+    }
+    if (!distinct) return true;
+    *distinct = true; /* every sequence at most once in the pass -> rope/append can be fused into attention */
+    for (int a = 0; a < nrows && *distinct; ++a)
+        for (int b = a + 1; b < nrows; ++b)
+            if (seq[a] == seq[b]) { *distinct = false; break; }
+    return true;
+}
+
+bool TkLlmSession::upload_rows(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok) {
+    HIPQ(hipMemcpyAsync(d_seq, seq, nrows * 4, hipMemcpyHostToDevice, stream));
+    HIPQ(hipMemcpyAsync(d_pos, pos, nrows * 4, hipMemcpyHostToDevice, stream));
+    if (tok) HIPQ(hipMemcpyAsync(d_tok, tok, nrows * 4, hipMemcpyHostToDevice, stream));
+    HIPQ(hipMemsetAsync(d_nsteps, 0, TK_MAX_ROWS * 4, stream));
+    return true;
+}
+
+bool TkLlmSession::clear_row_tables(unsigned which) {
+    if ((which & TK_ROWS_MASKS) && mask_rows_dirty) { HIPQ(hipMemsetAsync(d_mask_row, 0xFF, TK_MAX_ROWS * 4, stream)); mask_rows_dirty = false; }
+    if ((which & TK_ROWS_SAMPLING) && samp_dirty) { HIPQ(hipMemsetAsync(d_samp, 0, TK_MAX_ROWS * sizeof(TkSampleRow), stream)); samp_dirty = false; }
+    if ((which & TK_ROWS_ADJUST) && adj_dirty) { HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream)); adj_dirty = false; }
+    if ((which & TK_ROWS_LOGPROBS) && lp_dirty) { HIPQ(hipMemsetAsync(d_lp_ntop, 0xFF, TK_MAX_ROWS * 4, stream)); lp_dirty = false; }
     return true;
 }
 
 bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, float* logits_host, int32_t* argmax_host,
                            bool lm_head, const uint32_t* const* row_masks, const TkSampleRow* row_samp, const TkLogitAdjust* row_adjust,
                            const int32_t* row_ntop, TkTokenLogprob* records_host) {
-    if (nrows <= 0 || nrows > TK_MAX_ROWS) { error = "nrows must be in [1,256]"; return false; }
-    bool any_adj = false, any_lp = false;
+    int top = 0;
+    bool distinct = true, any_adj = false, any_lp = false;
+    if (!check_pass_rows(nrows, seq, pos, tok, &top, &distinct)) return false;
     for (int r = 0; r < nrows && lm_head && row_ntop; ++r) {
         if (const char* why = tk_logprob_check(row_ntop[r], model->hp.vocab)) { error = "log-probabilities of row " + std::to_string(r) + ": " + why; return false; }
         any_lp = any_lp || row_ntop[r] >= 0;
@@ -1196,22 +1247,8 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
         if (const char* why = row_adjust[r].check(model->hp.vocab)) { error = "logit adjustment of row " + std::to_string(r) + ": " + why; return false; }
         any_adj = any_adj || !row_adjust[r].neutral();
     }
-    for (int r = 0; r < nrows; ++r) {
-        if (seq[r] < 0 || seq[r] >= max_seq || pos[r] < 0 || pos[r] >= max_ctx || tok[r] < 0 || tok[r] >= model->hp.vocab) {
-            error = "row out of range (sequence id, position or token id)";
-            return false;
-        }
-    }
     HIPQ(hipSetDevice(model->device));
-    HIPQ(hipMemcpyAsync(d_seq, seq, nrows * 4, hipMemcpyHostToDevice, stream));
-    HIPQ(hipMemcpyAsync(d_pos, pos, nrows * 4, hipMemcpyHostToDevice, stream));
-    HIPQ(hipMemcpyAsync(d_tok, tok, nrows * 4, hipMemcpyHostToDevice, stream));
-    HIPQ(hipMemsetAsync(d_nsteps, 0, TK_MAX_ROWS * 4, stream));
-    choose_attention(pos, nrows);
-    bool distinct = true; /* every sequence at most once in the pass -> rope/append can be fused into attention */
-    for (int a = 0; a < nrows && distinct; ++a)
-        for (int b = a + 1; b < nrows; ++b)
-            if (seq[a] == seq[b]) { distinct = false; break; }
+    if (!upload_rows(nrows, seq, pos, tok)) return false;
     if (lm_head) { /* per-row sampling masks: the masks of the constrained rows, compacted, + the row -> mask table the arg max kernel reads */
         int32_t rowtab[TK_MAX_ROWS];
         int nmask = 0;
@@ -1236,9 +1273,6 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
             for (int r = 0; r < nrows; ++r) tab[r] = row_samp[r];
             HIPQ(hipMemcpyAsync(d_samp, tab, sizeof tab, hipMemcpyHostToDevice, stream));
             samp_dirty = true;
-        } else if (samp_dirty) {
-            HIPQ(hipMemsetAsync(d_samp, 0, TK_MAX_ROWS * sizeof(TkSampleRow), stream));
-            samp_dirty = false;
         }
         /* logit adjustment: the tables of the pass's rows through the pinned block (free: the last forward() waited for the stream); a neutral row
          * gets the all-zero descriptor its workgroup returns on */
@@ -1263,9 +1297,6 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
             HIPQ(hipMemcpyAsync(d_adj_bias_ids, hbids, (size_t)nrows * TK_ADJUST_MAX_BIAS * 4, hipMemcpyHostToDevice, stream));
             HIPQ(hipMemcpyAsync(d_adj_bias, hbias, (size_t)nrows * TK_ADJUST_MAX_BIAS * 4, hipMemcpyHostToDevice, stream));
             adj_dirty = true;
-        } else if (adj_dirty) {
-            HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream));
-            adj_dirty = false;
         }
         /* log-probabilities: the per-row n_top table, uploaded only when a row asks (pageable source: staged before the call returns) */
         if (any_lp) {
@@ -1273,30 +1304,13 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
             for (int r = 0; r < TK_MAX_ROWS; ++r) ntab[r] = r < nrows ? row_ntop[r] : -1;
             HIPQ(hipMemcpyAsync(d_lp_ntop, ntab, TK_MAX_ROWS * 4, hipMemcpyHostToDevice, stream));
             lp_dirty = true;
-        } else if (lp_dirty) {
-            HIPQ(hipMemsetAsync(d_lp_ntop, 0xFF, TK_MAX_ROWS * 4, stream));
-            lp_dirty = false;
         }
+        /* the tables no row of this pass filled go back to neutral (masks: the upload above is the whole table) */
+        if (!clear_row_tables((any_samp ? 0 : TK_ROWS_SAMPLING) | (any_adj ? 0 : TK_ROWS_ADJUST) | (any_lp ? 0 : TK_ROWS_LOGPROBS))) return false;
     }
-    adjust_pass = any_adj;
-    logprob_pass = any_lp;
-    /* a pass replays a captured graph (one per (row count, form)): a host that asks for one token at a time — the reference's runner
-     * API — pays one graph launch, not ~260 kernel launches, per token; masked rows ride the same graphs (the table above is data) */
-    hipGraphExec_t* slot = !graphs_enabled() ? nullptr
-                           : !lm_head ? &graph_prefill[tiled_pass][nrows] : distinct ? &graph_exec[long_pass][nrows] : &graph_head_nf[tiled_pass][nrows];
-    if (slot && any_adj) slot = distinct ? &graph_exec_adj[long_pass][nrows] : &graph_head_nf_adj[tiled_pass][nrows];
-    if (slot && any_lp) slot = distinct ? &graph_exec_lp[any_adj][long_pass][nrows] : &graph_head_nf_lp[any_adj][tiled_pass][nrows];
-    if (slot) {
-        const bool captured = capture_pass(slot, nrows, lm_head, lm_head && distinct);
-        adjust_pass = logprob_pass = false; /* whoever enqueues or captures next (decode(), prefill(), a pipeline stage) describes a plain pass */
-        if (!captured) return false;
-        HIPQ(hipGraphLaunch(*slot, stream));
-    } else {
-        launch_error.clear();
-        enqueue_pass(nrows, lm_head, distinct);
-        adjust_pass = logprob_pass = false;
-    }
-    if (!launch_error.empty()) { error = launch_error; (void)hipStreamSynchronize(stream); return false; }
+    /* masked, sampled and greedy rows ride the same graphs (their tables are data); without the head the pass ropes apart whatever its rows, so
+     * that it is the form of a prompt chunk */
+    if (!launch_pass(tk_pass_form(lm_head, lm_head && distinct, nrows, top, pass_caps(nrows), any_adj, any_lp), nrows, graphs_enabled())) return false;
     HIPQ(hipGetLastError());
     if (!lm_head) { HIPQ(hipStreamSynchronize(stream)); return true; }
     if (logits_host) HIPQ(hipMemcpyAsync(logits_host, logits, (size_t)nrows * model->hp.vocab * 4, hipMemcpyDeviceToHost, stream));
@@ -1315,64 +1329,25 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
     return true;
 }
 
-int TkLlmSession::verify_form(int nrows, int top) const {
-    const TkLlmHParams& h = model->hp;
-    if (d_scores && tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim) && top >= tk_verify_run_min_pos(nrows)) return 4;
-    if (top >= TK_TILED_ATT_FROM_POS && tk_attention_prefill_applies(h.n_head, h.n_kv_head, h.head_dim)) return 2;
-    return 0;
-}
-
 bool TkLlmSession::forward_verify(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, int form, float* logits_host, int32_t* picks_host,
                                   bool* bad_args) {
     const TkLlmHParams& h = model->hp;
     if (bad_args) *bad_args = true;
-    if (nrows <= 0 || nrows > TK_MAX_ROWS) { error = "nrows must be in [1,256]"; return false; }
     if (!seq || !pos || !tok) { error = "verify pass: missing row arrays"; return false; }
     int top = 0;
-    for (int r = 0; r < nrows; ++r) {
-        if (seq[r] < 0 || seq[r] >= max_seq || pos[r] < 0 || pos[r] >= max_ctx || tok[r] < 0 || tok[r] >= h.vocab) {
-            error = "row out of range (sequence id, position or token id)";
-            return false;
-        }
-        top = pos[r] > top ? pos[r] : top;
-        if (r > 0 && seq[r] == seq[r - 1] && pos[r] != pos[r - 1] + 1) { error = "verify pass: the rows of a sequence stand at consecutive ascending positions"; return false; }
+    if (!check_pass_rows(nrows, seq, pos, tok, &top, nullptr)) return false;
+    for (int r = 1; r < nrows; ++r) {
+        if (seq[r] == seq[r - 1] && pos[r] != pos[r - 1] + 1) { error = "verify pass: the rows of a sequence stand at consecutive ascending positions"; return false; }
         for (int b = 0; b + 1 < r; ++b)
             if (seq[b] == seq[r] && seq[r - 1] != seq[r]) { error = "verify pass: the rows of a sequence are contiguous in the pass"; return false; }
     }
-    if (form == -1) form = verify_form(nrows, top);
-    if (form != 0 && form != 2 && form != 4) { error = "verify pass: form must be -1, 0, 2 or 4"; return false; }
-    if (form == 2 && !tk_attention_prefill_applies(h.n_head, h.n_kv_head, h.head_dim)) { error = "verify pass: the tiled attention form does not take this head geometry"; return false; }
-    if (form == 4 && !(d_scores && tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim))) {
-        error = "verify pass: the run form takes at most " + std::to_string(TK_LONG_ATT_MAX_ROWS) + " rows, head_dim 64 or 128, and a context window beyond " + std::to_string(TK_LONG_ATT_MIN_POS) + " positions";
-        return false;
-    }
+    const TkPassCaps caps = pass_caps(nrows);
+    if (form == -1) form = tk_verify_form(nrows, top, caps);
+    if (const char* why = tk_verify_form_error(form, caps)) { error = why; return false; }
     if (bad_args) *bad_args = false;
     HIPQ(hipSetDevice(model->device));
-    HIPQ(hipMemcpyAsync(d_seq, seq, nrows * 4, hipMemcpyHostToDevice, stream));
-    HIPQ(hipMemcpyAsync(d_pos, pos, nrows * 4, hipMemcpyHostToDevice, stream));
-    HIPQ(hipMemcpyAsync(d_tok, tok, nrows * 4, hipMemcpyHostToDevice, stream));
-    HIPQ(hipMemsetAsync(d_nsteps, 0, TK_MAX_ROWS * 4, stream));
-    /* greedy, unmasked, unadjusted rows: whatever an earlier pass left in the tables goes */
-    if (mask_rows_dirty) { HIPQ(hipMemsetAsync(d_mask_row, 0xFF, TK_MAX_ROWS * 4, stream)); mask_rows_dirty = false; }
-    if (samp_dirty) { HIPQ(hipMemsetAsync(d_samp, 0, TK_MAX_ROWS * sizeof(TkSampleRow), stream)); samp_dirty = false; }
-    if (adj_dirty) { HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream)); adj_dirty = false; }
-    if (lp_dirty) { HIPQ(hipMemsetAsync(d_lp_ntop, 0xFF, TK_MAX_ROWS * 4, stream)); lp_dirty = false; }
-    adjust_pass = logprob_pass = false;
-    /* the pass is described here, not by choose_attention: rope/append always runs as a launch of its own (fused_attn = false) */
-    const bool tiled_was = tiled_pass, long_was = long_pass;
-    tiled_pass = form == 2; long_pass = false; run_pass = form == 4;
-    bool ok = true;
-    if (graphs_enabled()) {
-        hipGraphExec_t* slot = &graph_verify[form / 2][nrows];
-        ok = capture_pass(slot, nrows, true, false);
-        if (ok && hipGraphLaunch(*slot, stream) != hipSuccess) { error = "verify pass: graph launch failed"; ok = false; }
-    } else {
-        launch_error.clear();
-        enqueue_pass(nrows, true, false);
-    }
-    tiled_pass = tiled_was; long_pass = long_was; run_pass = false;
-    if (!ok) return false;
-    if (!launch_error.empty()) { error = launch_error; (void)hipStreamSynchronize(stream); return false; }
+    if (!upload_rows(nrows, seq, pos, tok) || !clear_row_tables(TK_ROWS_MASKS | TK_ROWS_SAMPLING | TK_ROWS_ADJUST | TK_ROWS_LOGPROBS)) return false;
+    if (!launch_pass(tk_pass_form_verify(form), nrows, graphs_enabled())) return false;
     HIPQ(hipGetLastError());
     if (logits_host) HIPQ(hipMemcpyAsync(logits_host, logits, (size_t)nrows * h.vocab * 4, hipMemcpyDeviceToHost, stream));
     if (picks_host) HIPQ(hipMemcpyAsync(picks_host, d_tok, nrows * 4, hipMemcpyDeviceToHost, stream));
@@ -1383,33 +1358,19 @@ bool TkLlmSession::forward_verify(int nrows, const int32_t* seq, const int32_t* 
 bool TkLlmSession::forward_stage(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, const float* x_in, float* x_out, bool x_on_host,
                                  int l0, int l1, bool head, int32_t* argmax_host) {
     const TkLlmHParams& h = model->hp;
-    if (nrows <= 0 || nrows > TK_MAX_ROWS) { error = "nrows must be in [1,256]"; return false; }
     if (l0 < 0 || l1 < l0 || l1 > h.n_layer) { error = "bad layer range"; return false; }
     if ((tok == nullptr) == (x_in == nullptr)) { error = "a stage starts from tokens (first stage) or from a residual stream, not both"; return false; }
     if (head && l1 != h.n_layer) { error = "the head belongs to the stage that ends at the last layer"; return false; }
     if (!head && !x_out) { error = "a stage without the head must hand its residual stream on"; return false; }
-    for (int r = 0; r < nrows; ++r)
-        if (seq[r] < 0 || seq[r] >= max_seq || pos[r] < 0 || pos[r] >= max_ctx || (tok && (tok[r] < 0 || tok[r] >= h.vocab))) {
-            error = "row out of range (sequence id, position or token id)";
-            return false;
-        }
+    int top = 0;
+    bool distinct = true;
+    if (!check_pass_rows(nrows, seq, pos, tok, &top, &distinct)) return false;
     HIPQ(hipSetDevice(model->device));
-    HIPQ(hipMemcpyAsync(d_seq, seq, nrows * 4, hipMemcpyHostToDevice, stream));
-    HIPQ(hipMemcpyAsync(d_pos, pos, nrows * 4, hipMemcpyHostToDevice, stream));
-    if (tok) HIPQ(hipMemcpyAsync(d_tok, tok, nrows * 4, hipMemcpyHostToDevice, stream));
-    HIPQ(hipMemsetAsync(d_nsteps, 0, TK_MAX_ROWS * 4, stream));
-    if (mask_rows_dirty) { HIPQ(hipMemsetAsync(d_mask_row, 0xFF, TK_MAX_ROWS * 4, stream)); mask_rows_dirty = false; }
-    if (adj_dirty) { HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream)); adj_dirty = false; }
-    if (lp_dirty) { HIPQ(hipMemsetAsync(d_lp_ntop, 0xFF, TK_MAX_ROWS * 4, stream)); lp_dirty = false; }
+    if (!upload_rows(nrows, seq, pos, tok) || !clear_row_tables(TK_ROWS_MASKS | TK_ROWS_ADJUST | TK_ROWS_LOGPROBS)) return false;
     const size_t xb = (size_t)nrows * h.d_model * 4;
     if (x_in) HIPQ(hipMemcpyAsync(x, x_in, xb, x_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
-    bool distinct = true;
-    for (int a = 0; a < nrows && distinct; ++a)
-        for (int b = a + 1; b < nrows; ++b)
-            if (seq[a] == seq[b]) { distinct = false; break; }
     launch_error.clear();
-    choose_attention(pos, nrows);
-    enqueue_range(nrows, l0, l1, tok != nullptr, !head, head, distinct);
+    enqueue_range(nrows, l0, l1, tok != nullptr, !head, tk_pass_form(head, distinct, nrows, top, pass_caps(nrows)));
     if (!launch_error.empty()) { error = launch_error; (void)hipStreamSynchronize(stream); return false; }
     HIPQ(hipGetLastError());
     if (!head) HIPQ(hipMemcpyAsync(x_out, x, xb, x_on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
@@ -1453,11 +1414,9 @@ bool TkLlmSession::prefill(int nseq, int n_prompt, const int32_t* tokens, int32_
         const bool use_graph = graphs_enabled();
         for (int64_t off = 0; off < total; off += TK_MAX_ROWS) {
             const int n = (int)std::min<int64_t>(TK_MAX_ROWS, total - off);
-            choose_attention(tab.data() + total + off, n);
-            if (use_graph && !capture_pass(&graph_prefill[tiled_pass][n], n, false, false)) return false;
+            const int top = *std::max_element(tab.data() + total + off, tab.data() + total + off + n);
             hipLaunchKernelGGL(k_stage_rows, dim3((n + 255) / 256), dim3(256), 0, stream, d_tab + off, n, (int)total, d_seq, d_pos, d_tok);
-            if (use_graph) HIPQ(hipGraphLaunch(graph_prefill[tiled_pass][n], stream));
-            else { launch_error.clear(); enqueue_pass(n, false, false); if (!launch_error.empty()) { error = launch_error; return false; } }
+            if (!launch_pass(tk_pass_form(false, false, n, top, pass_caps(n)), n, use_graph)) return false;
         }
         HIPQ(hipGetLastError());
     }
@@ -1481,30 +1440,43 @@ bool TkLlmSession::decode(int nrows, int n_steps, int32_t* out_tokens_host) {
     int top0 = 0;
     for (int r = 0; r < nrows; ++r) top0 = hpos[r] > top0 ? hpos[r] : top0;
     HIPQ(hipMemsetAsync(d_nsteps, 0, TK_MAX_ROWS * 4, stream));
-    if (mask_rows_dirty) { HIPQ(hipMemsetAsync(d_mask_row, 0xFF, TK_MAX_ROWS * 4, stream)); mask_rows_dirty = false; } /* the loop samples unconstrained */
-    if (adj_dirty) { HIPQ(hipMemsetAsync(d_adj, 0, TK_MAX_ROWS * sizeof(TkAdjustRow), stream)); adj_dirty = false; } /* and unadjusted: it replays the plain graphs */
-    if (lp_dirty) { HIPQ(hipMemsetAsync(d_lp_ntop, 0xFF, TK_MAX_ROWS * 4, stream)); lp_dirty = false; } /* and reports no log-probabilities */
-    hipEvent_t e0, e1;
-    HIPQ(hipEventCreate(&e0));
-    HIPQ(hipEventCreate(&e1));
-    HIPQ(hipEventRecord(e0, stream));
-    for (int i = 0; i < n_steps; ++i) {
-        choose_attention_top(top0 + i, nrows); /* positions advance on the device; the host knows where the loop stands */
-        if (use_graph) {
-            if (!capture_pass(&graph_exec[long_pass][nrows], nrows, true, true)) { (void)hipStreamSynchronize(stream); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return false; }
-            HIPQ(hipGraphLaunch(graph_exec[long_pass][nrows], stream));
-        } else { launch_error.clear(); enqueue_pass(nrows, true, true); if (!launch_error.empty()) { error = launch_error; break; } }
-    }
-    if (!launch_error.empty()) { (void)hipStreamSynchronize(stream); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); launch_error.clear(); return false; }
+    /* the loop samples unconstrained, unadjusted and reports no log-probabilities: its steps are plain forms */
+    if (!clear_row_tables(TK_ROWS_MASKS | TK_ROWS_ADJUST | TK_ROWS_LOGPROBS)) return false;
+    const TkPassCaps caps = pass_caps(nrows);
+    EventPair ev;
+    HIPQ(ev.create());
+    HIPQ(hipEventRecord(ev.e0, stream));
+    for (int i = 0; i < n_steps; ++i) /* positions advance on the device; the host knows where the loop stands */
+        if (!launch_pass(tk_pass_form(true, true, nrows, top0 + i, caps), nrows, use_graph)) { (void)hipStreamSynchronize(stream); return false; }
     HIPQ(hipGetLastError());
-    HIPQ(hipEventRecord(e1, stream));
+    HIPQ(hipEventRecord(ev.e1, stream));
     if (out_tokens_host) HIPQ(hipMemcpyAsync(out_tokens_host, d_hist, (size_t)n_steps * TK_MAX_ROWS * 4, hipMemcpyDeviceToHost, stream));
     HIPQ(hipStreamSynchronize(stream));
     float ms = 0.0f;
-    HIPQ(hipEventElapsedTime(&ms, e0, e1));
+    HIPQ(hipEventElapsedTime(&ms, ev.e0, ev.e1));
     last_step_ms = ms / n_steps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    return true;
+}
+
+bool TkLlmSession::time_launches(int iters, const std::function<void()>& warm, const std::function<void(int)>& launch, float* avg_ms) {
+    EventPair ev;
+    struct Exec { hipGraphExec_t g = nullptr; ~Exec() { if (g) (void)hipGraphExecDestroy(g); } } ge;
+    HIPQ(ev.create());
+    warm();
+    /* launched the way decode() launches them: as nodes of a hipGraph (unless TK_MI355X_NO_GRAPH=1, see decode()) */
+    const bool use_graph = graphs_enabled();
+    if (use_graph) {
+        if (!capture(&ge.g, "a timing loop", [&] { for (int i = 0; i < iters; ++i) launch(i); })) return false;
+        HIPQ(hipGraphLaunch(ge.g, stream)); /* warm */
+    }
+    HIPQ(hipEventRecord(ev.e0, stream));
+    if (use_graph) HIPQ(hipGraphLaunch(ge.g, stream));
+    else for (int i = 0; i < iters; ++i) launch(i);
+    HIPQ(hipEventRecord(ev.e1, stream));
+    HIPQ(hipStreamSynchronize(stream));
+    float ms = 0.0f;
+    HIPQ(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *avg_ms = ms / iters;
     return true;
 }
 
@@ -1557,35 +1529,8 @@ bool TkLlmSession::time_gemv(int layer, int which, int nrows, int iters, float* 
         bytes = b;
     }
     *algo_bytes = bytes;
-    hipEvent_t e0, e1;
-    HIPQ(hipEventCreate(&e0));
-    HIPQ(hipEventCreate(&e1));
-    for (size_t i = 0; i < set.size(); ++i) tk_launch_gemv(set[i], stream);
-    /* launched the way decode() launches them: as nodes of a hipGraph (unless TK_MI355X_NO_GRAPH=1, see decode()) */
-    const bool use_graph = graphs_enabled();
-    hipGraphExec_t ge = nullptr;
-    if (use_graph) {
-        std::lock_guard<std::mutex> lk(g_capture_mu);
-        hipGraph_t g = nullptr;
-        HIPQ(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed));
-        for (int i = 0; i < iters; ++i) tk_launch_gemv(set[(size_t)i % set.size()], stream);
-        HIPQ(hipStreamEndCapture(stream, &g));
-        HIPQ(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        HIPQ(hipGraphDestroy(g));
-        HIPQ(hipGraphLaunch(ge, stream)); /* warm */
-    }
-    HIPQ(hipEventRecord(e0, stream));
-    if (use_graph) HIPQ(hipGraphLaunch(ge, stream));
-    else for (int i = 0; i < iters; ++i) tk_launch_gemv(set[(size_t)i % set.size()], stream);
-    HIPQ(hipEventRecord(e1, stream));
-    HIPQ(hipStreamSynchronize(stream));
-    if (ge) (void)hipGraphExecDestroy(ge);
-    float ms = 0.0f;
-    HIPQ(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return true;
+    return time_launches(iters, [&] { for (size_t i = 0; i < set.size(); ++i) tk_launch_gemv(set[i], stream); },
+                         [&](int i) { tk_launch_gemv(set[(size_t)i % set.size()], stream); }, avg_ms);
 }
 
 /* stand-alone timing of the decode attention launch (k_attention, fused rope/append form) at `nrows` rows whose sequences all sit at
@@ -1660,32 +1605,5 @@ bool TkLlmSession::time_attention(int nrows, int ctx, int iters, float* avg_ms, 
                             h.head_dim, l % h.n_layer, max_seq, max_ctx, act_qd, !unfused, stream);
     };
     *kv_bytes = (double)nrows * ctx * KVD * 2.0 * 2.0;
-    const bool use_graph = graphs_enabled();
-    hipGraphExec_t ge = nullptr;
-    launch(0);
-    if (use_graph) {
-        std::lock_guard<std::mutex> lk(g_capture_mu);
-        hipGraph_t g = nullptr;
-        HIPQ(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed));
-        for (int i = 0; i < iters; ++i) launch(i);
-        HIPQ(hipStreamEndCapture(stream, &g));
-        HIPQ(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        HIPQ(hipGraphDestroy(g));
-        HIPQ(hipGraphLaunch(ge, stream)); /* warm */
-    }
-    hipEvent_t e0, e1;
-    HIPQ(hipEventCreate(&e0));
-    HIPQ(hipEventCreate(&e1));
-    HIPQ(hipEventRecord(e0, stream));
-    if (use_graph) HIPQ(hipGraphLaunch(ge, stream));
-    else for (int i = 0; i < iters; ++i) launch(i);
-    HIPQ(hipEventRecord(e1, stream));
-    HIPQ(hipStreamSynchronize(stream));
-    if (ge) (void)hipGraphExecDestroy(ge);
-    float ms = 0.0f;
-    HIPQ(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return true;
+    return time_launches(iters, [&] { launch(0); }, launch, avg_ms);
 }

@@ -289,7 +289,6 @@ bool TkLlmPipe::connect_rccl(const unsigned char unique_id[128]) {
 
 /* ---- host side ------------------------------------------------------------------------------------------------------------------ */
 
-static std::mutex g_pipe_capture_mu;
 static const char* const kFailedMsg =
     "a pipeline wait timed out: a neighbouring stage never published (peer process gone, or the stages walk different pass orders); the pipe "
     "is out of step with its neighbours and must be re-created";
@@ -388,14 +387,14 @@ bool TkLlmPipe::connect_local(TkLlmPipe* next, TkLlmPipe* prev) {
 }
 
 /* one pass of this stage on the session's stream: [take the ids (stage 0) | wait for + take the stream] -> layers [l0, l1) -> [hand the
- * stream on | sample and return the ids].  take_ids: stage 0 feeds the ids of the id mailbox instead of what d_tok holds;
- * advance_pos: the rows' device-side positions move on by one afterwards (a sampling pass: k_argmax does it on the last stage, the
+ * stream on | sample and return the ids].  f: the form of the pass, f.head only on the last stage; take_ids: stage 0 feeds the ids of the id
+ * mailbox instead of what d_tok holds; advance_pos: the rows' device-side positions move on by one afterwards (a sampling pass: k_argmax does it on the last stage, the
  * other stages follow suit here, so every stage's positions agree when a decode loop starts) */
-void TkLlmPipe::enqueue_stage(int nrows, bool take_ids, bool head, bool advance_pos, bool fused_attn) {
+void TkLlmPipe::enqueue_stage(int nrows, bool take_ids, bool advance_pos, const TkPassForm& f) {
     const TkLlmHParams& h = s_->model->hp;
     hipStream_t st = s_->stream;
     const int D = h.d_model, slot_floats = TK_MAX_ROWS * D;
-    const bool first = stage == 0, last = stage == n_stages - 1;
+    const bool first = stage == 0, last = stage == n_stages - 1, sample = f.head;
     if (rccl_comm_) { /* the collective transport: one ncclRecv / ncclSend per boundary on this stage's stream, matched by the neighbour's */
         RcclApi& r = rccl();
         auto chk = [&](int rc, const char* what) { if (rc != 0 && s_->launch_error.empty()) s_->launch_error = std::string(what) + ": " + r.GetErrorString(rc); };
@@ -407,8 +406,7 @@ void TkLlmPipe::enqueue_stage(int nrows, bool take_ids, bool head, bool advance_
         } else {
             chk(r.Recv(s_->x, (size_t)nrows * D, TK_NCCL_FLOAT32, stage - 1, rccl_comm_, st), "ncclRecv (stream)");
         }
-        const bool sample = head && last;
-        s_->enqueue_range(nrows, l0, l1, first, !last, sample, fused_attn); /* fold_out: the stream that leaves is complete */
+        s_->enqueue_range(nrows, l0, l1, first, !last, f); /* fold_out: the stream that leaves is complete */
         if (!last) chk(r.Send(s_->x, (size_t)nrows * D, TK_NCCL_FLOAT32, stage + 1, rccl_comm_, st), "ncclSend (stream)");
         else if (sample) chk(r.Send(s_->d_tok, (size_t)nrows, TK_NCCL_INT32, 0, rccl_comm_, st), "ncclSend (ids)");
         if (advance_pos && !sample) hipLaunchKernelGGL(k_pipe_advance, dim3((nrows + 63) / 64), dim3(64), 0, st, s_->d_pos, nrows);
@@ -422,8 +420,7 @@ void TkLlmPipe::enqueue_stage(int nrows, bool take_ids, bool head, bool advance_
         const int n4 = nrows * D / 4;
         hipLaunchKernelGGL(k_pipe_take_x, dim3((n4 + 255) / 256), dim3(256), 0, st, mine_, prev_, st_, s_->x, n4, slot_floats, f16_ ? 1 : 0);
     }
-    const bool sample = head && last;
-    s_->enqueue_range(nrows, l0, l1, first, false, sample, fused_attn);
+    s_->enqueue_range(nrows, l0, l1, first, false, f);
     if (!last) {
         const float* partial = l1 > l0 ? s_->partial : nullptr;
         hipLaunchKernelGGL(k_pipe_send_x, dim3((D / 4 + 255) / 256, nrows), dim3(256), 0, st, s_->x, partial, s_->last_ks_res, D, D, next_, mine_, st_, slot_floats,
@@ -435,15 +432,12 @@ void TkLlmPipe::enqueue_stage(int nrows, bool take_ids, bool head, bool advance_
 }
 
 bool TkLlmPipe::pass(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, bool head) {
-    const TkLlmHParams& h = s_->model->hp;
     if (nrows <= 0 || nrows > TK_MAX_ROWS || !seq || !pos) { error = "nrows must be in [1, 256] and (seq, pos) given"; return false; }
     if (n_stages > 1 && !rccl_comm_ && (!next_ || !prev_)) { error = "the pipe is not connected"; return false; }
     if (failed_) { error = kFailedMsg; return false; }
+    int top = 0;
     bool distinct = true;
-    for (int r = 0; r < nrows; ++r) {
-        if (seq[r] < 0 || seq[r] >= s_->max_seq || pos[r] < 0 || pos[r] >= s_->max_ctx || (stage == 0 && tok && (tok[r] < 0 || tok[r] >= h.vocab))) { error = "row out of range (sequence id, position or token id)"; return false; }
-        for (int q = 0; q < r && distinct; ++q) distinct = seq[q] != seq[r];
-    }
+    if (!s_->check_pass_rows(nrows, seq, pos, stage == 0 ? tok : nullptr, &top, &distinct)) { error = s_->error; return false; }
     PQ(hipSetDevice(s_->model->device));
     int32_t* hb = h_rows_ + (size_t)(h_next_ % 64) * 3 * TK_MAX_ROWS; /* pinned: the copies below run when the stream gets there */
     if (h_next_ >= 64) PQ(hipStreamSynchronize(s_->stream)); /* ring wrapped: rare (prompts of more than 64 passes) */
@@ -457,7 +451,7 @@ bool TkLlmPipe::pass(int nrows, const int32_t* seq, const int32_t* pos, const in
         memcpy(hb + 2 * TK_MAX_ROWS, tok, nrows * 4);
         PQ(hipMemcpyAsync(s_->d_tok, hb + 2 * TK_MAX_ROWS, nrows * 4, hipMemcpyHostToDevice, s_->stream));
     }
-    if (s_->mask_rows_dirty) { PQ(hipMemsetAsync(s_->d_mask_row, 0xFF, TK_MAX_ROWS * 4, s_->stream)); s_->mask_rows_dirty = false; }
+    if (!s_->clear_row_tables(TkLlmSession::TK_ROWS_MASKS)) { error = s_->error; return false; }
     s_->launch_error.clear();
     /* id FIFO bookkeeping (every stage enqueues the same schedule, so stage 0 can count the last stage's sends): host-given tokens make
      * whatever the FIFO still holds stale — the previous generation's last sample — so it is drained before this pass */
@@ -486,11 +480,9 @@ bool TkLlmPipe::pass(int nrows, const int32_t* seq, const int32_t* pos, const in
     if (take) { --ids_outstanding_; if (rccl_comm_ && !id_msg_rows_.empty()) id_msg_rows_.pop_front(); }
     if (stage == 0 && head && n_stages > 1) { ++ids_outstanding_; if (rccl_comm_) id_msg_rows_.push_back(nrows); }
     /* host-described passes go eagerly (their row tables differ); distinct rows take the fused-attention form, as forward() does */
-    s_->choose_attention(pos, nrows);
-    host_top_ = 0; /* where decode() continues from: the rows' positions advance on the device after a sampling pass */
-    for (int r = 0; r < nrows; ++r) host_top_ = pos[r] > host_top_ ? pos[r] : host_top_;
-    if (head) ++host_top_;
-    enqueue_stage(nrows, take, head, head, distinct);
+    const TkPassForm form = tk_pass_form(head && stage == n_stages - 1, distinct, nrows, top, s_->pass_caps(nrows));
+    host_top_ = head ? top + 1 : top; /* where decode() continues from: the rows' positions advance on the device after a sampling pass */
+    enqueue_stage(nrows, take, head, form);
     if (!s_->launch_error.empty()) { error = s_->launch_error; return false; }
     PQ(hipGetLastError());
     return true;
@@ -502,40 +494,22 @@ bool TkLlmPipe::decode(int nrows, int n_steps) {
     if (failed_) { error = kFailedMsg; return false; }
     if (stage == 0 && n_stages > 1 && ids_outstanding_ < 1) { error = "decode() without a sampling pass before it: the id mailbox would be empty"; return false; }
     PQ(hipSetDevice(s_->model->device));
-    if (s_->mask_rows_dirty) { PQ(hipMemsetAsync(s_->d_mask_row, 0xFF, TK_MAX_ROWS * 4, s_->stream)); s_->mask_rows_dirty = false; }
+    if (!s_->clear_row_tables(TkLlmSession::TK_ROWS_MASKS)) { error = s_->error; return false; }
     PQ(hipMemsetAsync(s_->d_nsteps, 0, TK_MAX_ROWS * 4, s_->stream));
     const char* ng = getenv("TK_MI355X_NO_GRAPH");
     const bool use_graph = !(ng && ng[0] == '1') && !rccl_comm_; /* collective calls are launched eagerly */
-    /* the attention form (fused / long-context three-launch form) follows the position the loop stands at, as TkLlmSession::decode does: the
-     * host knows it from the last pass() and counts the steps; one graph per (form, row count) */
-    auto capture = [&](hipGraphExec_t* slot) -> bool {
-        if (*slot) return true;
-        std::lock_guard<std::mutex> lk(g_pipe_capture_mu);
-        hipGraph_t g = nullptr;
-        PQ(hipStreamBeginCapture(s_->stream, hipStreamCaptureModeRelaxed));
-        s_->launch_error.clear();
-        enqueue_stage(nrows, true, true, true, true);
-        const hipError_t e_end = hipStreamEndCapture(s_->stream, &g);
-        hipError_t e_inst = hipSuccess;
-        if (e_end == hipSuccess && s_->launch_error.empty()) e_inst = hipGraphInstantiate(slot, g, nullptr, nullptr, 0);
-        if (g) (void)hipGraphDestroy(g);
-        if (e_end != hipSuccess || e_inst != hipSuccess || !s_->launch_error.empty()) {
-            *slot = nullptr;
-            (void)hipGetLastError();
-            error = !s_->launch_error.empty() ? s_->launch_error : std::string("graph capture of a pipeline pass failed: ") + hipGetErrorString(e_end != hipSuccess ? e_end : e_inst);
-            return false;
-        }
-        return true;
-    };
     /* a step takes one id message and (the last stage) sends one: the FIFO's length is unchanged, its row counts all become nrows */
     if (rccl_comm_ && stage == 0 && n_stages > 1) { id_msg_rows_.assign(id_msg_rows_.size(), nrows); }
+    /* the form follows the position the loop stands at, as TkLlmSession::decode's does: the host knows it from the last pass() and counts the
+     * steps; one graph per (resolved attention, row count) */
+    const TkPassCaps caps = s_->pass_caps(nrows);
     for (int i = 0; i < n_steps; ++i) {
-        s_->choose_attention_top(host_top_ + i, nrows);
+        const TkPassForm form = tk_pass_form(stage == n_stages - 1, true, nrows, host_top_ + i, caps);
         if (use_graph) {
-            hipGraphExec_t* slot = &graph_[s_->long_pass ? 1 : 0][nrows];
-            if (!capture(slot)) return false;
+            hipGraphExec_t* slot = &graph_[form.attn == TK_ATT_LONG ? 1 : 0][nrows];
+            if (!*slot && !s_->capture(slot, "a pipeline pass", [&] { enqueue_stage(nrows, true, true, form); })) { error = s_->error; return false; }
             PQ(hipGraphLaunch(*slot, s_->stream));
-        } else { s_->launch_error.clear(); enqueue_stage(nrows, true, true, true, true); if (!s_->launch_error.empty()) { error = s_->launch_error; return false; } }
+        } else { s_->launch_error.clear(); enqueue_stage(nrows, true, true, form); if (!s_->launch_error.empty()) { error = s_->launch_error; return false; } }
     }
     host_top_ += n_steps;
     PQ(hipGetLastError());

@@ -539,6 +539,13 @@ class LlmSession:
         check(lib().tk_mi355x_llm_time_kv_copy(self.h, n_pos, n_dst, iters, C.byref(k), C.byref(m), C.byref(nbytes)))
         return k.value, m.value, nbytes.value
 
+    @property
+    def graph_captures(self):
+        """passes (and timing loops) this session has recorded into a graph so far (tk_mi355x_llm_session_graph_captures)"""
+        n = C.c_uint64(0)
+        check(lib().tk_mi355x_llm_session_graph_captures(self.h, C.byref(n)))
+        return n.value
+
     def close(self):
         if self.h:
             lib().tk_mi355x_llm_session_destroy(C.byref(self.h))
