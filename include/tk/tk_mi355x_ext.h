@@ -186,6 +186,8 @@ TK_API int tk_mi355x_prefix_match(const int32_t* toks, int n, const int32_t* rec
                                   int cursor, int32_t out[3]);
 
 /* sessions --------------------------------------------------------------------------------- */
+/* max_seq sequences of max_ctx positions each, 1 <= max_ctx <= 32768 (RoPE is unscaled; a wider window is refused with a message that says so).
+ * The KV cache is 2 x n_layer x max_seq x max_ctx x n_kv_head x head_dim f16 in one allocation each; a failure to allocate names the bytes. */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_create(tk_mi355x_llm_session_t** out, tk_mi355x_llm_model_t* m, int max_seq,
                                                                  int max_ctx);
 TK_API void tk_mi355x_llm_session_destroy(tk_mi355x_llm_session_t** s);
@@ -455,9 +457,16 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_time_attention(tk_mi355x_llm_s
  * matrix pipe, taken by passes that reach position 128 or beyond; the other three numbers describe the k_attention form that shorter contexts
  * take and that TK_MI355X_NO_PREFILL_ATT=1 puts back everywhere — the two forms are bit-identical).  fused != 0: a decode
  * pass (every sequence once), else a pass that holds several positions of a sequence (prompt chunks).  The parity
- * tests assert the instantiation they exercise from this answer (csrc/llm/tk_llm_kernels.hip: tk_attention_plan). */
+ * tests assert the instantiation they exercise from this answer (csrc/llm/tk_llm_kernels.hip: tk_attention_plan).
+ * kernel 5 = k_attention_far: what stands in for kernels 0 and 1 in a session whose max_ctx is beyond tk_mi355x_attention_resident_limit (or beyond
+ * $TK_MI355X_ATT_RESIDENT_MAX=<positions>, for tests and A/B timing): the same (row, block of query heads) workgroups and ring, no score row
+ * in LDS — keys streamed twice, values once; a fused pass gets a k_qkv_rope_append launch in front.  Bit-identical to the others.
+ * device < 0 selects none: the answer is for the thread's current device, and for a 256-CU one on a host without a GPU. */
 TK_API int tk_mi355x_device_cu_count(int device); /* compute units of a HIP device (256 on an MI355X), -1 when there is no such device */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_attention_plan(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, int fused, int32_t out[4]);
+/* host only, no device: the largest max_ctx at which a session of this head geometry still keeps its score rows in LDS (kernels 0 and 1) — 8192
+ * for 32 / 8 / 128, 9216 for 32 / 8 / 64; 0 for a geometry that is none.  Sessions above it run kernel 5 in their place. */
+TK_API int tk_mi355x_attention_resident_limit(int n_head, int n_kv_head, int head_dim);
 /* the same for a pass whose highest position is `top_position` (a session picks per pass from the positions it is handed): kernel 3 = the
  * long-context decode form (fused != 0; 1 .. 4 rows from position 512, 5 .. 8 rows from 768: k_att_scores_long +
  * k_att_pv_chain + k_att_pv_join — scores over (row, KV head, 64-position block) workgroups, one PV chain per (row, head, class) wave — instead

@@ -19,7 +19,7 @@ loader = tk.ModelLoader()
 h = loader.load("synthetic://mistral-7b?seed=4")
 prefix_cache = "--prefix-cache" in sys.argv
 tk.ModelLoader.set_prefix_cache(h, prefix_cache)
-runner = tk.LlmRunner(h, context_size=512)
+runner = tk.LlmRunner(h, context_size=int(os.environ.get("TK_B1_CTX", "512")))  # TK_B1_CTX=4096: the window of the reference's default runner
 penalties = "none"
 if "--penalties" in sys.argv:
     penalties = sys.argv[sys.argv.index("--penalties") + 1]

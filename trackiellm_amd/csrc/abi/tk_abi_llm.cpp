@@ -565,7 +565,8 @@ int tk_mi355x_device_cu_count(int device) {
 
 tk_error_code_t tk_mi355x_attention_plan(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, int fused, int32_t out[4]) {
     if (!out || nrows < 1 || nrows > TK_MAX_ROWS || n_head < 1 || n_kv_head < 1 || n_head % n_kv_head || head_dim < 1 || max_ctx < 1) return TK_ERROR_INVALID_ARGUMENT;
-    if (hipSetDevice(device) != hipSuccess) return fail(TK_ERROR_GPU_DEVICE_NOT_FOUND, "no such HIP device");
+    /* device < 0: none is selected — the answer is for the thread's current device, and for a 256-CU one on a host that has none */
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(TK_ERROR_GPU_DEVICE_NOT_FOUND, "no such HIP device");
     const TkAttentionPlan pl = tk_attention_plan(nrows, n_head, n_kv_head, head_dim, max_ctx, fused != 0);
     out[0] = pl.kernel; out[1] = pl.gq; out[2] = pl.chunk; out[3] = pl.slots;
     return TK_SUCCESS;
@@ -575,17 +576,22 @@ tk_error_code_t tk_mi355x_attention_plan(int device, int nrows, int n_head, int 
 static TkPassCaps plan_caps(int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx) {
     return TkPassCaps{max_ctx > TK_LONG_ATT_MIN_POS, tk_attention_prefill_applies(n_head, n_kv_head, head_dim), tk_attention_long_applies(nrows, n_head, n_kv_head, head_dim)};
 }
-/* the launcher's plan in out[] with the session's per-pass choice (tk_pass_form.h) on top */
-static void plan_set_kernel(int32_t out[4], int kernel, int n_head, int n_kv_head) {
-    if (kernel >= 3) { out[1] = n_head / n_kv_head; out[2] = 64; out[3] = 1; }
-    out[0] = kernel;
+/* the launcher's plan in out[] with the session's per-pass choice (tk_pass_form.h) on top; far: the per-row form of this window is
+ * k_attention_far (kernel 5), which is what a pass runs where the choice says 0 */
+static void plan_set_kernel(int32_t out[4], int kernel, int n_head, int n_kv_head, bool far) {
+    if (kernel == 3 || kernel == 4) { out[1] = n_head / n_kv_head; out[2] = 64; out[3] = 1; }
+    out[0] = kernel == 0 && far ? 5 : kernel;
 }
+static bool plan_is_far(int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx) { return tk_attention_plan(nrows, n_head, n_kv_head, head_dim, max_ctx, true).far; }
+
+int tk_mi355x_attention_resident_limit(int n_head, int n_kv_head, int head_dim) { return tk_attention_resident_limit(n_head, n_kv_head, head_dim); }
 
 tk_error_code_t tk_mi355x_attention_plan_at(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, int fused, int top_position, int32_t out[4]) {
     const tk_error_code_t rc = tk_mi355x_attention_plan(device, nrows, n_head, n_kv_head, head_dim, max_ctx, fused, out);
     if (rc != TK_SUCCESS) return rc;
     if (top_position < 0 || top_position >= max_ctx) return TK_ERROR_INVALID_ARGUMENT;
-    plan_set_kernel(out, tk_plan_kernel_at(out[0], fused != 0, nrows, top_position, plan_caps(nrows, n_head, n_kv_head, head_dim, max_ctx)), n_head, n_kv_head);
+    plan_set_kernel(out, tk_plan_kernel_at(out[0], fused != 0, nrows, top_position, plan_caps(nrows, n_head, n_kv_head, head_dim, max_ctx)), n_head, n_kv_head,
+                    plan_is_far(nrows, n_head, n_kv_head, head_dim, max_ctx));
     return TK_SUCCESS;
 }
 
@@ -593,7 +599,8 @@ tk_error_code_t tk_mi355x_attention_plan_verify(int device, int nrows, int n_hea
     const tk_error_code_t rc = tk_mi355x_attention_plan(device, nrows, n_head, n_kv_head, head_dim, max_ctx, 0, out);
     if (rc != TK_SUCCESS) return rc;
     if (top_position < 0 || top_position >= max_ctx) return TK_ERROR_INVALID_ARGUMENT;
-    plan_set_kernel(out, tk_plan_kernel_verify(out[0], nrows, top_position, plan_caps(nrows, n_head, n_kv_head, head_dim, max_ctx)), n_head, n_kv_head);
+    plan_set_kernel(out, tk_plan_kernel_verify(out[0], nrows, top_position, plan_caps(nrows, n_head, n_kv_head, head_dim, max_ctx)), n_head, n_kv_head,
+                    plan_is_far(nrows, n_head, n_kv_head, head_dim, max_ctx));
     return TK_SUCCESS;
 }
 

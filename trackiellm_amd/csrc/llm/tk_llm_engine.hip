@@ -350,8 +350,9 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     if (!m || !m->ready()) { error = "model has missing tensors"; return false; }
     if (mseq <= 0 || mctx <= 0) { error = "max_seq and max_ctx must be positive"; return false; }
     const TkLlmHParams& h = m->hp;
-    if (tk_attention_lds_bytes(h.n_head / h.n_kv_head, h.head_dim, mctx, 64) > 160 * 1024) {
-        error = "max_ctx too large: the attention kernel keeps one score row per query head of a KV group in LDS (about 9000 positions for 4 x 128)";
+    /* a window beyond tk_attention_resident_limit takes k_attention_far, whose LDS does not depend on it (tk_attention_plan) */
+    if (mctx > TK_MAX_CONTEXT) {
+        error = "max_ctx too large: a session's context window is at most " + std::to_string(TK_MAX_CONTEXT) + " positions (RoPE is unscaled), asked for " + std::to_string(mctx);
         return false;
     }
     HIPQ(hipSetDevice(m->device));
@@ -360,8 +361,14 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     counted_ = true;
     const int QD = h.n_head * h.head_dim, KVD = h.n_kv_head * h.head_dim, half = h.head_dim / 2;
     size_t kv = (size_t)h.n_layer * mseq * mctx * KVD;
-    HIPQ(hipMalloc((void**)&kcache, kv * 2));
-    HIPQ(hipMalloc((void**)&vcache, kv * 2));
+    /* the one allocation that grows with sequences x window: a failure names what was asked for (16 sequences of 32 768 positions of a 7B model
+     * are 69 GB) */
+    if (hipMalloc((void**)&kcache, kv * 2) != hipSuccess || hipMalloc((void**)&vcache, kv * 2) != hipSuccess) {
+        (void)hipGetLastError();
+        error = "KV cache: could not allocate 2 x " + std::to_string(kv * 2) + " bytes on the device (" + std::to_string(h.n_layer) + " layers x " + std::to_string(mseq) +
+                " sequences x " + std::to_string(mctx) + " positions x " + std::to_string(KVD) + " f16, keys and values)";
+        return false;
+    }
     HIPQ(hipMemset(kcache, 0, kv * 2));
     HIPQ(hipMemset(vcache, 0, kv * 2));
     HIPQ(hipMalloc((void**)&x, (size_t)TK_MAX_ROWS * h.d_model * 4));

@@ -112,8 +112,18 @@ void tk_launch_logit_adjust(float* logits, int vocab, int nrows, const TkAdjustR
 void tk_launch_token_logprobs(const float* logits, int vocab, int ld, int nrows, const int32_t* n_top, const int32_t* tok, TkTokenLogprob* rec, hipStream_t s);
 
 /* the attention launch a pass takes: kernel 0 = k_attention<gq, fused, head_dim, chunk> (chunk = positions per ring slot, slots = ring depth 2), kernel 1 =
- * k_attention_narrow (gq 2, chunk = positions resident per chunk, the whole context when it fits) */
-struct TkAttentionPlan { int kernel, gq, chunk, slots; size_t lds_bytes; };
+ * k_attention_narrow (gq 2, chunk = positions resident per chunk, the whole context when it fits), kernel 5 = k_attention_far<gq, head_dim, chunk>
+ * (the per-row form of a window beyond tk_attention_resident_limit: no score row in LDS; a fused pass gets k_qkv_rope_append in front).
+ * far: the window takes the far form wherever a pass takes the per-row one (kernel 2 names the tiled form the session prefers from
+ * TK_TILED_ATT_FROM_POS; below it the pass runs kernel 5 when `far`, else 0) */
+struct TkAttentionPlan { int kernel, gq, chunk, slots; size_t lds_bytes; bool far; };
+/* the widest context window a session may have: RoPE is unscaled, and the 32 k checkpoints this library loads need none up to here */
+#define TK_MAX_CONTEXT 32768
+/* host only: the largest window whose score rows — one per query head of a KV group — fit a k_attention workgroup's LDS beside a 64-position
+ * ring (what TkLlmSession::init refused beyond, before the far form); sessions above it, or above TK_MI355X_ATT_RESIDENT_MAX=<positions>
+ * (read where the plan is made; tests and A/B timing), take k_attention_far instead of k_attention and k_attention_narrow */
+int tk_attention_resident_limit(int n_head, int n_kv_head, int head_dim);
+size_t tk_attention_far_lds_bytes(int gq, int head_dim, int chunk);
 /* a decode session on `device` came (+1) or went (-1): with more than one alive the plan prefers forms that share a CU with other streams' launches */
 void tk_attention_note_session(int device, int delta);
 TkAttentionPlan tk_attention_plan(int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, bool fused);

@@ -3154,6 +3154,181 @@ __global__ __launch_bounds__(256, CH == 32 ? 8 : 4) void k_attention(const float
 }
 
 /* ------------------------------------------------------------------------------------------
+ * The far form of k_attention: the same attention for a session whose window has no room in LDS for a score row (tk_attention_plan: kernel 5).
+ * One workgroup per (row, block of GQ query heads), the same two-slot LDS-DMA ring and key swizzle; the LDS it takes is the ring, q and ONE
+ * chunk of probabilities, whatever the context (tk_attention_far_lds_bytes).  The cache run is streamed twice:
+ *   pass A  key chunks 0 .. n - 1: every score — one fma chain over head_dim, times att_scale — of which only the per-head maximum is kept;
+ *   pass B  for c = 0 .. n - 1: key chunk c again, its scores formed once more and stored as exp(s - max), [CH][GQ] floats; then value chunk c
+ *           into the PV and denominator sums.
+ * Keys are read twice and values once: 1.5 x the bytes of the resident form.
+ *
+ * Bit-identical to k_attention, hence to every other form and to the oracle:
+ *   - a score depends only on (q, key row): both passes run the one chain of far_score() on the same LDS layout, so pass B's score of a
+ *     position has the bits pass A took the maximum over, and they are the bits k_attention forms (-ffp-contract=off: no fusion either side);
+ *   - a maximum does not depend on the order or the grouping it is taken in;
+ *   - the partial sums are the same chains: wave j takes positions = j (mod 4) (CH is a multiple of 4: a chunk's first position is 0 mod 4)
+ *     in ascending order — chunk after chunk, ascending inside a chunk — into accumulators that persist across the chunks, with the
+ *     same batches of four whose dead slots enter as fma(0, v, acc) and l + 0; the join is ((p0 + p1) + p2) + p3, tk_divf, quantize_chunk8.
+ * The rows were roped and appended by k_qkv_rope_append before (the launcher enqueues it in front for a pass that asks for a fused launch:
+ * its sums and rope are k_attention's FUSED prologue, term for term), so this kernel only reads the cache.
+ * ------------------------------------------------------------------------------------------ */
+template <int HD>
+__device__ __forceinline__ float far_score(const uint8_t* kr /* the key row in its ring slot */, const float* qh, int srr, int ppr, int swm, float att_scale) {
+    float a = 0.0f;
+    constexpr int KB = HD ? HD / 8 : 1; /* key pieces read per batch: the whole row when head_dim is known */
+    for (int i0 = 0; i0 < ppr; i0 += KB) {
+        uint4 kv[KB];
+#pragma unroll
+        for (int u = 0; u < KB; ++u) kv[u] = *(const uint4*)(kr + (((i0 + u) ^ (srr & swm)) * 16));
+#pragma unroll
+        for (int u = 0; u < KB; ++u) {
+            const v4f q0 = *(const v4f*)(qh + 8 * (i0 + u)), q1 = *(const v4f*)(qh + 8 * (i0 + u) + 4);
+            const uint32_t kw[4] = {kv[u].x, kv[u].y, kv[u].z, kv[u].w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float kf = f16bits_to_f32((kw[e >> 1] >> (16 * (e & 1))) & 0xffffu);
+                a = tk_fmaf(e < 4 ? q0[e] : q1[e - 4], kf, a);
+            }
+        }
+    }
+    return a * att_scale;
+}
+
+template <int GQ, int HD /* head_dim when it is 64 or 128, 0 = any */, int CH /* positions per ring slot: 32 or 64 */>
+__global__ __launch_bounds__(256) void k_attention_far(const float* __restrict__ qbuf, const uint16_t* __restrict__ kcache, const uint16_t* __restrict__ vcache,
+                                                       const int32_t* __restrict__ seq, const int32_t* __restrict__ pos, int n_head, int n_kv_head, int head_dim_rt,
+                                                       int layer, int max_seq, int max_ctx, TkActQ8 out) {
+    static_assert(CH == 32 || CH == 64, "a head's CH scoring threads lie inside one wave; CH % 4 == 0 keeps the position classes aligned");
+    extern __shared__ __attribute__((aligned(16))) uint8_t att_lds[];
+    const int head_dim = HD ? HD : head_dim_rt;
+    const int hb = blockIdx.x, r = blockIdx.y, t = threadIdx.x, lane = t & 63;
+    const int kvh = hb * GQ / (n_head / n_kv_head);
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int p = pos[r], T = p + 1, sq = seq[r];
+    const int W = GQ * head_dim, rb = head_dim * 2, QD = n_head * head_dim;
+    const int slot_bytes = CH * rb;
+    /* LDS: the ring (whose slots the epilogue's arrays take over), q, one chunk of probabilities (tk_attention_far_lds_bytes mirrors this) */
+    uint8_t* ring = att_lds;
+    const int ring_bytes = 2 * slot_bytes, epi_bytes = (TK_ATT_TSPLIT * W + TK_ATT_TSPLIT * TK_ATT_MAX_GRP + W) * (int)sizeof(float);
+    float* qs = (float*)(att_lds + (ring_bytes > epi_bytes ? ring_bytes : epi_bytes)); /* [GQ][head_dim] */
+    float* pr = qs + W;                                                                /* [CH][GQ] */
+    float* part = (float*)ring;
+    float* lpart = part + TK_ATT_TSPLIT * W;
+    float* obuf = lpart + TK_ATT_TSPLIT * TK_ATT_MAX_GRP;
+    const int64_t run0 = (((int64_t)layer * max_seq + sq) * n_kv_head + kvh) * (int64_t)max_ctx * head_dim;
+    const uint16_t* krun = kcache + run0;
+    const uint16_t* vrun = vcache + run0;
+    const int nchunk = (T + CH - 1) / CH;
+    const int total = 3 * nchunk; /* the stream: K chunks 0 .. n - 1 (pass A), then K chunk c, V chunk c for c = 0 .. n - 1 (pass B) */
+    const int last_row = max_ctx - 1;
+    const int ppr = rb / 16, swm = att_swizzle_mask(ppr);
+    auto issue = [&](int j) {
+        const bool is_k = j < nchunk || ((j - nchunk) & 1) == 0;
+        const int c = j < nchunk ? j : (j - nchunk) >> 1;
+        att_stage(is_k ? krun : vrun, c * CH, last_row, rb, ring + (j % 2) * slot_bytes, is_k, wave, lane, CH);
+    };
+    /* before touching chunk j: it has landed; everybody is done with chunk j - 1, whose slot takes chunk j + 1 */
+    auto acquire = [&](int j) {
+        wait_vmcnt(0);
+        __syncthreads();
+        if (j + 1 < total) issue(j + 1);
+    };
+
+    issue(0);
+    for (int i = t; i < W; i += 256) qs[i] = qbuf[(int64_t)r * QD + hb * W + i];
+    const float att_scale = tk_divf(1.0f, tk_sqrtf((float)head_dim));
+    const bool scorer = t < GQ * CH;
+    const int sh = t / CH, srr = t % CH; /* this thread's head and row of every chunk */
+    const float* qh = qs + (scorer ? sh : 0) * head_dim;
+
+    /* ---- pass A: the per-head maximum ---- */
+    float m = -INFINITY;
+    for (int j = 0; j < nchunk; ++j) {
+        acquire(j); /* the first barrier also publishes qs */
+        if (scorer && j * CH + srr < T) m = tk_fmaxf(m, far_score<HD>(ring + (j % 2) * slot_bytes + srr * rb, qh, srr, ppr, swm, att_scale));
+    }
+    for (int s = CH / 2; s >= 1; s >>= 1) m = tk_fmaxf(m, wave_xor_f(m, s)); /* over the CH lanes of one head: every one of them ends with it */
+
+    /* ---- pass B: probabilities of one chunk, then its values; wave j takes positions = j (mod 4), lane owns dims (2 lane, 2 lane + 1) [+ 128] ---- */
+    float acc[GQ][2][2], l[GQ];
+#pragma unroll
+    for (int h = 0; h < GQ; ++h) { l[h] = 0.0f; acc[h][0][0] = acc[h][0][1] = acc[h][1][0] = acc[h][1][1] = 0.0f; }
+    for (int c = 0; c < nchunk; ++c) {
+        const int jk = nchunk + 2 * c;
+        acquire(jk); /* every wave is past the PV of chunk c - 1: pr may be overwritten */
+        if (scorer && c * CH + srr < T) pr[srr * GQ + sh] = tk_expf(far_score<HD>(ring + (jk % 2) * slot_bytes + srr * rb, qh, srr, ppr, swm, att_scale) - m);
+        acquire(jk + 1); /* publishes pr */
+        const uint8_t* slot = ring + ((jk + 1) % 2) * slot_bytes;
+        const int t_end = T - c * CH < CH ? T - c * CH : CH;
+        constexpr int PB = 4; /* k_attention's batches: dead slots of the last one read a clamped row and enter with probability 0 */
+        for (int rr0 = wave; rr0 < t_end; rr0 += PB * TK_ATT_TSPLIT) {
+            float pb[PB][GQ];
+            uint32_t vv[PB][2];
+#pragma unroll
+            for (int u = 0; u < PB; ++u) {
+                const int rr = rr0 + u * TK_ATT_TSPLIT;
+                const bool live = rr < t_end;
+                const int rc = live ? rr : t_end - 1;
+                const float* pp = pr + rc * GQ;
+                if (GQ == 4) { const v4f x = *(const v4f*)pp; pb[u][0] = x[0]; pb[u][1 % GQ] = x[1]; pb[u][2 % GQ] = x[2]; pb[u][3 % GQ] = x[3]; }
+                else if (GQ == 2) { const v2f x = *(const v2f*)pp; pb[u][0] = x[0]; pb[u][1 % GQ] = x[1]; }
+                else pb[u][0] = pp[0];
+#pragma unroll
+                for (int h = 0; h < GQ; ++h) pb[u][h] = live ? pb[u][h] : 0.0f;
+#pragma unroll
+                for (int db = 0; db < 2; ++db) {
+                    const int d0 = 2 * lane + 128 * db;
+                    vv[u][db] = d0 < head_dim ? *(const uint32_t*)(slot + rc * rb + d0 * 2) : 0u;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < PB; ++u) {
+#pragma unroll
+                for (int db = 0; db < 2; ++db) {
+                    if (2 * lane + 128 * db < head_dim) {
+                        const float v0 = f16bits_to_f32(vv[u][db] & 0xffffu), v1 = f16bits_to_f32(vv[u][db] >> 16);
+#pragma unroll
+                        for (int h = 0; h < GQ; ++h) {
+                            acc[h][db][0] = tk_fmaf(pb[u][h], v0, acc[h][db][0]);
+                            acc[h][db][1] = tk_fmaf(pb[u][h], v1, acc[h][db][1]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int h = 0; h < GQ; ++h) l[h] = l[h] + pb[u][h];
+            }
+        }
+    }
+    __syncthreads(); /* every wave is done with the ring: it now holds the epilogue's arrays */
+#pragma unroll
+    for (int h = 0; h < GQ; ++h) {
+#pragma unroll
+        for (int db = 0; db < 2; ++db) {
+            const int d0 = 2 * lane + 128 * db;
+            if (d0 < head_dim) {
+                part[wave * W + h * head_dim + d0] = acc[h][db][0];
+                part[wave * W + h * head_dim + d0 + 1] = acc[h][db][1];
+            }
+        }
+        if (lane == 0) lpart[wave * TK_ATT_MAX_GRP + h] = l[h];
+    }
+    __syncthreads();
+    for (int i = t; i < W; i += 256) {
+        const int h = i / head_dim;
+        const float a = ((part[i] + part[W + i]) + part[2 * W + i]) + part[3 * W + i];
+        const float ll = ((lpart[h] + lpart[TK_ATT_MAX_GRP + h]) + lpart[2 * TK_ATT_MAX_GRP + h]) + lpart[3 * TK_ATT_MAX_GRP + h];
+        obuf[i] = tk_divf(a, ll);
+    }
+    __syncthreads();
+    for (int c = t; c < W / 8; c += 256) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = obuf[8 * c + i];
+        quantize_chunk8(v, hb * (W / 8) + c, r, out);
+    }
+}
+
+/* ------------------------------------------------------------------------------------------
  * Narrow decode passes (at most one workgroup per CU: 1 .. 16 rows of Mistral-7B): the same attention, arithmetic for arithmetic, as
  * k_attention<2, true, 128, ...>, laid out for LATENCY.  There the launch is a chain of ~11 barrier-separated phases of four waves (two
  * K chunks, two V chunks, their own-row patches, max, exp, three epilogue steps: 15 us per layer of a one-runner decode step, a quarter of
@@ -3980,8 +4155,46 @@ size_t tk_attention_lds_bytes(int gq, int head_dim, int max_ctx, int chunk) {
 
 /* Which attention launch a pass takes on the calling thread's device (the choice depends on its CU count): the one place that decides,
  * used by the launcher and exported (tk_mi355x_attention_plan) so tests assert what they run from the launcher's own answer. */
+size_t tk_attention_far_lds_bytes(int gq, int head_dim, int chunk) {
+    const size_t W = (size_t)gq * head_dim;
+    const size_t ring = (size_t)2 * chunk * head_dim * 2;
+    const size_t epilogue = ((size_t)TK_ATT_TSPLIT * W + TK_ATT_TSPLIT * TK_ATT_MAX_GRP + W) * sizeof(float); /* aliases the ring */
+    return (ring > epilogue ? ring : epilogue) + (W + (size_t)chunk * gq) * sizeof(float); /* q, one chunk of probabilities */
+}
+
+int tk_attention_resident_limit(int n_head, int n_kv_head, int head_dim) {
+    if (n_head < 1 || n_kv_head < 1 || n_head % n_kv_head || head_dim < 1) return 0;
+    const int grp = n_head / n_kv_head;
+    int lo = 0, hi = TK_MAX_CONTEXT; /* the bytes grow with the window: the largest one that fits, by bisection */
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        if (tk_attention_lds_bytes(grp, head_dim, mid, 64) <= (size_t)TK_MAX_DYN_LDS) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+/* a session constant: this window takes the far form wherever a pass would take k_attention or k_attention_narrow */
+static bool tk_attention_far_window(int n_head, int n_kv_head, int head_dim, int max_ctx) {
+    if (max_ctx > tk_attention_resident_limit(n_head, n_kv_head, head_dim)) return true;
+    /* TK_MI355X_ATT_RESIDENT_MAX=<positions>: a window above it takes the far form even where the resident one fits (parity tests of both in
+     * small windows, A/B timing) */
+    const char* rm = getenv("TK_MI355X_ATT_RESIDENT_MAX");
+    return rm && rm[0] >= '0' && rm[0] <= '9' && max_ctx > atoi(rm);
+}
+
 TkAttentionPlan tk_attention_plan(int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, bool fused) {
     TkAttentionPlan pl{};
+    if (tk_attention_far_window(n_head, n_kv_head, head_dim, max_ctx)) {
+        /* the same two choices as below, by the same measurements: half a group of 4 per workgroup while the launch is latency-bound, 32-position
+         * slots once several workgroups per CU are resident; no 128-position slots (a head's scoring threads stay inside one wave) */
+        int gq = n_head / n_kv_head;
+        if (gq == 4 && (2 * head_dim) % 256 == 0 && nrows * n_kv_head < 2 * TK_NUM_CU) gq = 2;
+        pl.kernel = 5; pl.gq = gq; pl.chunk = (n_head / gq) * nrows > 4 * TK_NUM_CU ? 32 : 64; pl.slots = 2; pl.far = true;
+        pl.lds_bytes = tk_attention_far_lds_bytes(gq, head_dim, pl.chunk);
+        if (!fused && tk_attention_prefill_applies(n_head, n_kv_head, head_dim)) pl.kernel = 2;
+        return pl;
+    }
     if (const int cap = tk_attention_narrow_cap(nrows, n_head, n_kv_head, head_dim, max_ctx, fused)) {
         pl.kernel = 1; pl.gq = 2; pl.chunk = cap; pl.slots = 1;
         pl.lds_bytes = tk_attention_narrow_fixed_lds(max_ctx) + (size_t)cap * 512;
@@ -4036,10 +4249,26 @@ static const TkAttentionKernel k_attention_fns[3][2][3][3] = {
       {k_attention<4, true, 128, 32>, k_attention<4, true, 128, 64>}}},
 };
 
+/* [gq 1, 2, 4][head_dim any, 64, 128][chunk 32, 64]: a group of one head exists only at head_dim 256, half a group of 4 only where 2 x head_dim
+ * fills 256s; the run-time head_dim instantiation stands in for a pair no geometry of TkLlmModel::init reaches */
+typedef void (*TkAttentionFarKernel)(const float*, const uint16_t*, const uint16_t*, const int32_t*, const int32_t*, int, int, int, int, int, int, TkActQ8);
+static const TkAttentionFarKernel k_attention_far_fns[3][3][2] = {
+    {{k_attention_far<1, 0, 32>, k_attention_far<1, 0, 64>}, {k_attention_far<1, 0, 32>, k_attention_far<1, 0, 64>}, {k_attention_far<1, 0, 32>, k_attention_far<1, 0, 64>}},
+    {{k_attention_far<2, 0, 32>, k_attention_far<2, 0, 64>}, {k_attention_far<2, 0, 32>, k_attention_far<2, 0, 64>}, {k_attention_far<2, 128, 32>, k_attention_far<2, 128, 64>}},
+    {{k_attention_far<4, 0, 32>, k_attention_far<4, 0, 64>}, {k_attention_far<4, 64, 32>, k_attention_far<4, 64, 64>}, {k_attention_far<4, 128, 32>, k_attention_far<4, 128, 64>}},
+};
+
 void tk_launch_attention(const float* qbuf, const float* partial, int ks, int n_total, const float* rope_cos, const float* rope_sin,
                          uint16_t* kcache, uint16_t* vcache, const int32_t* seq, const int32_t* pos, int nrows, int n_head, int n_kv_head,
                          int head_dim, int layer, int max_seq, int max_ctx, TkActQ8 out, bool fused, hipStream_t s) {
     const TkAttentionPlan pl = tk_attention_plan(nrows, n_head, n_kv_head, head_dim, max_ctx, fused);
+    if (pl.far) {
+        /* the far kernel only reads the cache: a pass that asks for the fused launch gets its rows roped and appended in front, the same bits */
+        if (fused) tk_launch_qkv_rope_append(partial, ks, n_total, n_head, n_kv_head, head_dim, rope_cos, rope_sin, seq, pos, nrows, const_cast<float*>(qbuf), kcache, vcache, layer, max_seq, max_ctx, s);
+        const TkAttentionFarKernel k = k_attention_far_fns[pl.gq == 4 ? 2 : pl.gq - 1][head_dim == 128 ? 2 : head_dim == 64 ? 1 : 0][pl.chunk == 64];
+        hipLaunchKernelGGL(k, dim3(n_head / pl.gq, nrows), dim3(256), pl.lds_bytes, s, qbuf, kcache, vcache, seq, pos, n_head, n_kv_head, head_dim, layer, max_seq, max_ctx, out);
+        return;
+    }
     if (pl.kernel == 1) {
         hipLaunchKernelGGL(k_attention_narrow, dim3(n_head / 2, nrows), dim3(1024), pl.lds_bytes, s, partial, ks, n_total, rope_cos, rope_sin, kcache,
                            vcache, seq, pos, n_head, n_kv_head, layer, max_seq, max_ctx, pl.chunk, out);
@@ -4363,6 +4592,7 @@ const char* tk_llm_prepare_device(int device) {
     for (const auto& f1 : k_gemm_fns) for (TkGemvKernel fn : f1) opt(fn);
     for (TkGemm32Kernel fn : k_gemm32_fns) opt(fn);
     for (const auto& f3 : k_attention_fns) for (const auto& f2 : f3) for (const auto& f1 : f2) for (TkAttentionKernel fn : f1) opt(fn);
+    for (const auto& f2 : k_attention_far_fns) for (const auto& f1 : f2) for (TkAttentionFarKernel fn : f1) opt(fn);
     opt(k_attention_narrow);
     opt(k_attention_prefill<128>);
     opt(k_attention_prefill<64>);

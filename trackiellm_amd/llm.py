@@ -227,7 +227,7 @@ def matmul_float_probe(ttype, w, K, ks, x, seg_rows=None, device=0):
 
 def attention_plan(nrows, n_head, n_kv_head, head_dim, max_ctx, fused=True, device=0, top_position=None):
     """the attention launch a pass takes on `device`: (kernel, query heads per workgroup, positions per slot / resident chunk, slots);
-    kernel 0 = k_attention, 1 = k_attention_narrow, 2 = k_attention_prefill, 3 = the long-context decode form (tk_mi355x_attention_plan;
+    kernel 0 = k_attention, 1 = k_attention_narrow, 2 = k_attention_prefill, 3 = the long-context decode form, 5 = k_attention_far (tk_mi355x_attention_plan;
     with top_position — the pass's highest position — tk_mi355x_attention_plan_at: the session's per-pass choice)"""
     out = (C.c_int32 * 4)()
     if top_position is None:
@@ -235,6 +235,14 @@ def attention_plan(nrows, n_head, n_kv_head, head_dim, max_ctx, fused=True, devi
     else:
         check(lib().tk_mi355x_attention_plan_at(device, nrows, n_head, n_kv_head, head_dim, max_ctx, 1 if fused else 0, int(top_position), out))
     return tuple(out)
+
+
+def attention_resident_limit(n_head, n_kv_head, head_dim):
+    """the largest session window whose attention keeps its score rows in LDS (kernels 0 and 1); a wider window, up to 32768 positions, runs
+    kernel 5 = k_attention_far in their place (tk_mi355x_attention_resident_limit; host only, needs no device)"""
+    fn = lib().tk_mi355x_attention_resident_limit
+    fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_int, C.c_int]
+    return int(fn(n_head, n_kv_head, head_dim))
 
 
 def attention_plan_verify(nrows, n_head, n_kv_head, head_dim, max_ctx, top_position, device=0):
