@@ -278,7 +278,7 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_forward_adjusted(tk_mi355x_llm
  *   the candidate list the stochastic chain draws from on an unmasked row.  The first one is the greedy pick, except on a row whose maximum is a zero
  *   of both signs (the arg max compares floats and takes the lower id).
  *   Limits: n_top -1 = off, 0 = the produced id only, 1 .. 20 = that many alternatives; vocabularies of at most 65536 tokens.
- * Out of scope: the prompt's tokens ("echo"), the rows of a lookup verify pass, the pipeline (tk_mi355x_pipe_*) path. ---- */
+ * Out of scope: the prompt's tokens ("echo"), the rows of tk_mi355x_llm_forward_verify, the pipeline (tk_mi355x_pipe_*) path. ---- */
 #define TK_MI355X_LOGPROB_MAX_TOP 20
 /* one produced token's record.  n_top = the count of alternatives actually filled (min(asked, vocab)); entries past it are not written */
 typedef struct {
@@ -289,7 +289,7 @@ typedef struct {
 } tk_mi355x_token_logprob_t;
 /* the runner's setting: -1 off (the default), 0 .. 20 on.  Anything else: TK_ERROR_INVALID_ARGUMENT, the previous setting kept.  Takes effect from the
  * next sampled token.  A runner with log-probabilities on keeps running ahead (csrc/llm/tk_llm_batcher.h: the record rides with the id); lookup
- * decoding does nothing while they are on.  Prefix cache, context shift and grammar are unaffected; the token stream is the one the runner emits with
+ * decoding does nothing while they are on unless its scope has TK_MI355X_LOOKUP_LOGPROBS.  Prefix cache, context shift and grammar are unaffected; the token stream is the one the runner emits with
  * the setting off */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_logprobs(struct tk_llm_runner_s* runner, int32_t n_top);
 /* the record of the id the last prepare_generation / generate_next_token (or add_tool_response) sampled — the id the NEXT generate_next_token hands out
@@ -389,7 +389,8 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_forward_verify(tk_mi355x_llm_s
                                                                  const int32_t* tok, int form, float* logits, int32_t* picks);
 /* n_draft = 0 (off, the default) .. 15 drafts per pass; 1 <= ngram_min <= ngram_max <= 8.  Anything else: TK_ERROR_INVALID_ARGUMENT, the previous
  * setting kept.  Lookup does nothing — the runner submits exactly what it does with lookup off — while the runner has a temperature, a grammar mask,
- * penalties, a logit bias, or log-probabilities on (tk_mi355x_llm_runner_set_logprobs: a verify pass reports none).  Takes effect from the next pass */
+ * penalties, a logit bias, or log-probabilities on, unless tk_mi355x_llm_runner_set_lookup_scope covers every such condition.  Takes effect from the
+ * next pass */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_lookup(struct tk_llm_runner_s* runner, int32_t n_draft, int32_t ngram_min, int32_t ngram_max);
 /* the host's prediction of the reply (copied): at most 4096 ids, each inside the vocabulary; n = 0 clears it.  It survives prepare_generation.
  * Anything else: TK_ERROR_INVALID_ARGUMENT, the previous prediction kept */
@@ -397,6 +398,37 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_prediction(struct t
 /* since the last prepare_generation: passes that carried at least one draft, drafts fed, drafts accepted */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_lookup_stats(struct tk_llm_runner_s* runner, uint64_t* verify_passes, uint64_t* drafted,
                                                                       uint64_t* accepted);
+/* the scope of lookup decoding (csrc/llm/tk_lookup_scope.h; opt-in): under which of the four conditions above a runner with lookup on still drafts.
+ * The default, 0, is the behaviour described at tk_mi355x_llm_runner_set_lookup.  A runner drafts while it has a temperature, a grammar mask, penalties
+ * or a bias, or log-probabilities on iff the bit of EVERY condition that currently holds is set; one missing bit makes it inactive.  Row i of its verify
+ * pass then samples under the tables a one-row pass at that position would have had — the chain with counter c + i, the mask of a copy of the grammar
+ * state after the pending id and drafts 0 .. i - 1 (the drafts are cut in front of the first one the state refuses and of the first one that would
+ * complete the grammar), the penalty window after them, the runner's n_top — so the ids, the records (tk_mi355x_llm_runner_last_logprobs is valid for
+ * every id), the tool-call text, the counter and the token at which the runner ends or shifts are those of the runner with lookup off.  Unknown bits:
+ * TK_ERROR_INVALID_ARGUMENT, the previous scope kept.  Takes effect from the next pass */
+#define TK_MI355X_LOOKUP_SAMPLED 1u
+#define TK_MI355X_LOOKUP_GRAMMAR 2u
+#define TK_MI355X_LOOKUP_ADJUSTED 4u
+#define TK_MI355X_LOOKUP_LOGPROBS 8u
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_lookup_scope(struct tk_llm_runner_s* runner, uint32_t flags);
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_get_lookup_scope(struct tk_llm_runner_s* runner, uint32_t* flags);
+/* diagnostic (tools/time_lookup.py): host milliseconds since the last prepare_generation spent cutting the drafts under the grammar and building
+ * the per-row masks of the runner's verify requests, and spent in the verify requests themselves (queueing, the pass, the wake-up) */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_lookup_host_ms(struct tk_llm_runner_s* runner, double* masks_ms, double* requests_ms);
+/* one sampling pass with all four optional per-row tables: masks [nrows] pointers, NULL = that row is unmasked, else (vocab + 31) / 32 words whose bit t
+ * says token t may be picked; sampling, adjust, n_top / records as tk_mi355x_llm_forward_logprobs takes them; each table may be NULL.  The rows may be
+ * several positions of one sequence: when the rows of each sequence stand at consecutive ascending positions and are contiguous in the pass, and some
+ * sequence appears more than once, the pass takes the attention tk_mi355x_llm_forward_verify(form -1) takes for them — the run form of the long-context
+ * attention where tk_mi355x_attention_plan_verify names kernel 4 — and every form gives the same bits.  This is the verify pass of a runner whose
+ * lookup scope is not 0.  A row outside the session, an adjustment or n_top outside its limits, sampling parameters out of range, a row that asks for a
+ * record without `records`: TK_ERROR_INVALID_ARGUMENT, nothing enqueued */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_forward_rows(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos,
+                                                               const int32_t* tok, const uint32_t* const* masks, const tk_mi355x_sampling_t* sampling,
+                                                               const tk_mi355x_logit_adjust_t* adjust, const int32_t* n_top, float* logits, int32_t* picks,
+                                                               tk_mi355x_token_logprob_t* records);
+/* diagnostic: the form key (csrc/llm/tk_pass_form.h, tk_pass_form_key) of the last pass the session ran through tk_mi355x_llm_forward* /
+ * _forward_verify, -1 before the first.  With the head the key is 5 + 4 * attention + 2 * adjusted + with records; attention 4 is the run form */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_last_pass_key(tk_mi355x_llm_session_t* session, int* key);
 /* equal-length prompts for sequences 0..nseq-1; first_tokens[nseq] optional */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_prefill(tk_mi355x_llm_session_t* s, int nseq, int n_prompt, const int32_t* tokens,
                                                           int32_t* first_tokens);

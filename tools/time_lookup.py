@@ -3,6 +3,12 @@
 positions — developer tool, needs an MI355X.
 
     python tools/time_lookup.py [--rounds 4] [--parent-lib /path/to/the/parent/commit's/libtrackie_mi355x.so]
+                                [--temperature 0.7] [--grammar] [--brace-bias B]
+
+--temperature T (> 0) runs the reference's runner: temperature T with the default chain, seed 11; --grammar arms the tool-call grammar; both put the
+lookup configurations inside the runner's scope (tk_mi355x_llm_runner_set_lookup_scope), "off" being lookup on with scope 0.  --brace-bias adds a
+logit bias on the closing brace (a synthetic model under the grammar either closes its call at once or never).  With a scope the tool also prints the
+host time spent building the per-row masks beside the time spent in the verify requests (tk_mi355x_llm_runner_lookup_host_ms).
 
 Configurations, interleaved round by round in one call, their order rotated every round:
     parent    the parent commit's library (only with --parent-lib), the runner as it was
@@ -39,24 +45,36 @@ def child():
     import trackiellm_amd as tk
     loader = tk.ModelLoader()
     handle = loader.load(PATH, force_reload=True)
-    runner = tk.LlmRunner(handle, context_size=4096)
     print(json.dumps({"ready": True}), flush=True)
     for line in sys.stdin:
         cmd = json.loads(line)
         if cmd.get("quit"):
             break
+        # a runner per generation: the sampling counter counts from the runner's creation, so every generation draws the same stream; the session,
+        # its cache and its graphs belong to the model and stay
+        runner = tk.LlmRunner(handle, context_size=4096, random_seed=11)
+        if cmd.get("temperature", 0.0) > 0.0:
+            runner.set_sampling(cmd["temperature"])
+        if cmd.get("brace_bias") is not None:
+            runner.set_logit_bias([3 + ord("}")], [cmd["brace_bias"]])
         if "lookup" in cmd:
             runner.set_lookup(*cmd["lookup"])
             runner.set_prediction(cmd["prediction"])
-        runner.prepare(prompt_of(cmd["prompt_bytes"]))
+            if "scope" in cmd:  # the parent library has no scope: it is never sent one
+                runner.set_lookup_scope_bits(cmd["scope"])
+        runner.prepare(prompt_of(cmd["prompt_bytes"]), use_tool_grammar=bool(cmd.get("grammar")))
         n = 0
         t0 = time.perf_counter()
-        while n < TOKENS and runner.next_token() is not None:
+        while n < TOKENS:
+            p = runner.next_token()
+            if p is None or p == "<tool_call>":
+                break
             n += 1
         dt = time.perf_counter() - t0
         stats = runner.lookup_stats() if "lookup" in cmd else (0, 0, 0)
-        print(json.dumps({"tokens": n, "seconds": dt, "ids": runner.recent_tokens(), "stats": stats}), flush=True)
-    runner.close()
+        host = runner.lookup_host_ms() if "scope" in cmd else (0.0, 0.0)
+        print(json.dumps({"tokens": n, "seconds": dt, "ids": runner.recent_tokens(), "stats": stats, "host_ms": host}), flush=True)
+        runner.close()
     loader.unload(handle)
     loader.close()
 
@@ -89,6 +107,9 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--parent-first", action="store_true", help="create the parent library's process before this library's")
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--temperature", type=float, default=0.0)
+    ap.add_argument("--grammar", action="store_true")
+    ap.add_argument("--brace-bias", type=float, default=None)
     args = ap.parse_args()
     if args.child:
         return child()
@@ -99,30 +120,38 @@ def main():
     if args.parent_lib and not parent:
         parent = Child(args.parent_lib)
     try:
+        base = dict(temperature=args.temperature, grammar=args.grammar, brace_bias=args.brace_bias)
+        scoped = args.temperature > 0.0 or args.grammar or args.brace_bias is not None
+        scope = dict(scope=15) if scoped else {}
         for name, nbytes in CONTEXTS.items():
-            plain = new.run(prompt_bytes=nbytes)  # warm-up of the plain passes, and the prediction
+            plain = new.run(prompt_bytes=nbytes, **base)  # warm-up of the plain passes, and the prediction
             ids = plain["ids"][:plain["tokens"]]
             seen = set(plain["ids"]) | set(3 + b for b in prompt_of(nbytes).encode()) | {1, 2}
             never = [t for t in range(300, 2000) if t not in seen][:64]
-            configs = {"off": dict(lookup=(0, 1, 3), prediction=[]), "cost": dict(lookup=(4, 1, 3), prediction=never), "ceiling": dict(lookup=(4, 1, 3), prediction=ids)}
+            configs = {"off": dict(lookup=(0, 1, 3), prediction=[]), "cost": dict(lookup=(4, 1, 3), prediction=never, **scope), "ceiling": dict(lookup=(4, 1, 3), prediction=ids, **scope)}
+            if scoped:  # scope off: lookup on, the scope 0 — the runner is inactive, as it was before the scope existed
+                configs["off"] = dict(lookup=(4, 1, 3), prediction=ids, scope=0)
             for cfg in configs.values():
+                cfg.update(base)
                 new.run(prompt_bytes=nbytes, **cfg)  # warm-up: the verify passes' graphs
             if parent:
-                parent.run(prompt_bytes=nbytes)
+                parent.run(prompt_bytes=nbytes, **base)
             rates = {k: [] for k in (["parent"] if parent else []) + list(configs)}
             last = {}
             order = list(rates)
             for rnd in range(args.rounds):
                 for k in order[rnd % len(order):] + order[:rnd % len(order)]:  # the order rotates: no configuration always follows the same one
-                    r = parent.run(prompt_bytes=nbytes) if k == "parent" else new.run(prompt_bytes=nbytes, **configs[k])
+                    r = parent.run(prompt_bytes=nbytes, **base) if k == "parent" else new.run(prompt_bytes=nbytes, **configs[k])
                     assert r["ids"] == plain["ids"], "%s: ids differ from the plain run" % k
                     rates[k].append(r["tokens"] / r["seconds"])
                     last[k] = r
             print("%s context (%d prompt tokens, %d tokens generated):" % (name, nbytes + 1, plain["tokens"]))
             for k, v in rates.items():
                 s = last.get(k, {}).get("stats", (0, 0, 0))
-                print("  %-8s %s tok/s   range %.0f - %.0f   verify passes %d, drafted %d, accepted %d" %
-                      (k, " ".join("%.0f" % x for x in v), min(v), max(v), s[0], s[1], s[2]), flush=True)
+                h = last.get(k, {}).get("host_ms", (0.0, 0.0))
+                print("  %-8s %s tok/s   range %.0f - %.0f   verify passes %d, drafted %d, accepted %d%s" %
+                      (k, " ".join("%.0f" % x for x in v), min(v), max(v), s[0], s[1], s[2],
+                       "   masks %.2f ms beside %.2f ms in the requests (%.3f / %.3f per pass)" % (h[0], h[1], h[0] / max(s[0], 1), h[1] / max(s[0], 1)) if scoped and s[0] else ""), flush=True)
     finally:
         new.close()
         if parent:

@@ -17,6 +17,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <chrono>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -28,6 +29,7 @@
 #include "../llm/tk_llm_batcher.h"
 #include "../llm/tk_llm_engine.h"
 #include "../llm/tk_lookup.h"
+#include "../llm/tk_lookup_scope.h"
 #include "../llm/tk_lora.h"
 #include "../llm/tk_prefix_match.h"
 #include "../llm/tk_llm_pipe.h"
@@ -387,7 +389,7 @@ tk_error_code_t tk_mi355x_llm_forward(tk_mi355x_llm_session_t* s, int nrows, con
 /* a sampling pass with optional per-row sampling states and logit adjustments: both checked per row before anything runs */
 static tk_error_code_t forward_rows(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok,
                                     const tk_mi355x_sampling_t* sampling, const tk_mi355x_logit_adjust_t* adjust, float* logits, int32_t* ids,
-                                    const int32_t* n_top = nullptr, tk_mi355x_token_logprob_t* records = nullptr) {
+                                    const int32_t* n_top = nullptr, tk_mi355x_token_logprob_t* records = nullptr, const uint32_t* const* masks = nullptr) {
     static_assert(sizeof(tk_mi355x_token_logprob_t) == sizeof(TkTokenLogprob) && offsetof(tk_mi355x_token_logprob_t, top_ids) == offsetof(TkTokenLogprob, top_ids) &&
                       offsetof(tk_mi355x_token_logprob_t, top_logprobs) == offsetof(TkTokenLogprob, top_logprobs),
                   "the public log-probability record is the library's TkTokenLogprob");
@@ -406,8 +408,32 @@ static tk_error_code_t forward_rows(tk_mi355x_llm_session_t* s, int nrows, const
             return fail(TK_ERROR_INVALID_ARGUMENT, "sampling parameters of row " + std::to_string(r) + " are out of range (temperature >= 0, 0 <= top_k <= 64, 0 < top_p <= 1, 0 <= min_p <= 1)");
         rows[r].temp = p.temperature; rows[r].top_p = p.top_p; rows[r].min_p = p.min_p; rows[r].top_k = p.top_k; rows[r].seed = p.seed; rows[r].counter = p.counter;
     }
-    if (!s->session.forward(nrows, seq, pos, tok, logits, ids, true, nullptr, sampling ? rows : nullptr, adj, n_top, (TkTokenLogprob*)records))
+    if (!s->session.forward(nrows, seq, pos, tok, logits, ids, true, masks, sampling ? rows : nullptr, adj, n_top, (TkTokenLogprob*)records))
         return fail(TK_ERROR_INFERENCE_FAILED, s->session.error);
+    return TK_SUCCESS;
+}
+
+/* the head pass with all four per-row tables; the rows themselves are checked here too, so that a refusal is an argument error with nothing enqueued */
+tk_error_code_t tk_mi355x_llm_forward_rows(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok,
+                                           const uint32_t* const* masks, const tk_mi355x_sampling_t* sampling, const tk_mi355x_logit_adjust_t* adjust,
+                                           const int32_t* n_top, float* logits, int32_t* picks, tk_mi355x_token_logprob_t* records) {
+    if (!s || !seq || !pos || !tok || nrows < 1 || nrows > TK_MAX_ROWS) return TK_ERROR_INVALID_ARGUMENT;
+    const TkLlmSession& ses = s->session;
+    bool any_lp = false, any_drawn = false;
+    for (int r = 0; r < nrows; ++r) {
+        if (seq[r] < 0 || seq[r] >= ses.max_seq || pos[r] < 0 || pos[r] >= ses.max_ctx || tok[r] < 0 || tok[r] >= ses.model->hp.vocab)
+            return fail(TK_ERROR_INVALID_ARGUMENT, "row " + std::to_string(r) + " is out of range (sequence id, position or token id)");
+        any_lp = any_lp || (n_top && n_top[r] >= 0);
+        any_drawn = any_drawn || (sampling && sampling[r].temperature > 0.0f);
+    }
+    if (any_lp && !records) return fail(TK_ERROR_INVALID_ARGUMENT, "log-probabilities asked for without records to fill");
+    if (any_drawn && ses.model->hp.vocab > 65536) return fail(TK_ERROR_INVALID_ARGUMENT, "stochastic sampling supports vocabularies of at most 65536 tokens");
+    return forward_rows(s, nrows, seq, pos, tok, sampling, adjust, logits, picks, n_top, records, masks);
+}
+
+tk_error_code_t tk_mi355x_llm_session_last_pass_key(tk_mi355x_llm_session_t* s, int* key) {
+    if (!s || !key) return TK_ERROR_INVALID_ARGUMENT;
+    *key = s->session.last_pass_key;
     return TK_SUCCESS;
 }
 
@@ -943,14 +969,32 @@ struct tk_llm_runner_s {
     std::vector<int32_t> ctx_ids;
     std::vector<int32_t> queued;
     uint64_t lookup_passes = 0, lookup_drafted = 0, lookup_accepted = 0; /* since the last prepare_generation */
-    /* lookup does nothing while the runner samples stochastically, under a grammar mask, with penalties or a bias, or with log-probabilities on (a verify
-     * pass reports none): it then submits what it always did */
-    bool lookup_active() const { return lookup_draft > 0 && !(samp.temp > 0.0f) && !grammar_on && pen_last_n == 0 && bias_ids.empty() && lp_ntop < 0; }
-    /* the owner abandons the ids it was handed but has not given out (a tool response, a reset): back to the state of a runner that holds `pending`
+    /* the scope (tk_mi355x_llm_runner_set_lookup_scope, csrc/llm/tk_lookup_scope.h), 0 by default: lookup does nothing while the runner samples
+     * stochastically, under a grammar mask, with penalties or a bias, or with log-probabilities on, unless the scope has the bit of every such
+     * condition that holds; an inactive runner submits what it always did */
+    uint32_t lookup_scope = 0;
+    bool adjusted() const { return pen_last_n != 0 || !bias_ids.empty(); }
+    bool lookup_active() const { return lookup_draft > 0 && tk_lookup_scope_allows(lookup_scope, samp.temp > 0.0f, grammar_on, adjusted(), lp_ntop >= 0); }
+    /* what a verify pass with tables left with the queued ids: their records (one per queued id when the pass asked for them, else empty), and whether
+     * the pass drew them from the stochastic chain — samp.counter then counts them already */
+    std::vector<TkTokenLogprob> queued_lp;
+    bool queued_drawn = false;
+    /* host time since the last prepare_generation (tk_mi355x_llm_runner_lookup_host_ms): cutting the drafts under the grammar and building the
+     * per-row masks of the verify requests, and the verify requests themselves (submit_verify: queueing, the pass, the wake-up) */
+    double lookup_masks_ms = 0.0, lookup_requests_ms = 0.0;
+    /* the queued ids are forgotten (a new prompt, a reset): the sampling counter goes back to the number of tokens the runner has sampled and kept,
+     * and their records go with them */
+    void forget_queued() {
+        if (queued_drawn) samp.counter -= (uint32_t)queued.size();
+        queued.clear();
+        queued_lp.clear();
+        queued_drawn = false;
+    }
+    /* the owner abandons the ids it was handed but has not given out (a tool response): back to the state of a runner that holds `pending`
      * alone — the rows fed ahead are stale rows beyond n_past, overwritten before anything attends to them */
     void drop_queued() {
         n_past -= (int)queued.size();
-        queued.clear();
+        forget_queued();
         if ((int)ctx_ids.size() > n_past) ctx_ids.resize((size_t)n_past);
     }
     bool is_processing = false;
@@ -1065,6 +1109,29 @@ tk_error_code_t tk_mi355x_llm_runner_set_lookup(tk_llm_runner_t* runner, int32_t
     if (n_draft < 0 || n_draft > TK_LOOKUP_MAX_DRAFT) return fail(TK_ERROR_INVALID_ARGUMENT, "lookup: n_draft must be in [0, 15]");
     if (ngram_min < 1 || ngram_min > ngram_max || ngram_max > TK_LOOKUP_MAX_NGRAM) return fail(TK_ERROR_INVALID_ARGUMENT, "lookup: 1 <= ngram_min <= ngram_max <= 8");
     runner->lookup_draft = n_draft; runner->lookup_min = ngram_min; runner->lookup_max = ngram_max;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_runner_set_lookup_scope(tk_llm_runner_t* runner, uint32_t flags) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    if (flags & ~TK_LOOKUP_SCOPE_ALL) return fail(TK_ERROR_INVALID_ARGUMENT, "lookup scope: unknown flag bits");
+    static_assert(TK_MI355X_LOOKUP_SAMPLED == TK_LOOKUP_SCOPE_SAMPLED && TK_MI355X_LOOKUP_GRAMMAR == TK_LOOKUP_SCOPE_GRAMMAR &&
+                      TK_MI355X_LOOKUP_ADJUSTED == TK_LOOKUP_SCOPE_ADJUSTED && TK_MI355X_LOOKUP_LOGPROBS == TK_LOOKUP_SCOPE_LOGPROBS,
+                  "the public scope flags are tk_lookup_scope.h's");
+    runner->lookup_scope = flags;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_runner_lookup_host_ms(tk_llm_runner_t* runner, double* masks_ms, double* requests_ms) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    if (masks_ms) *masks_ms = runner->lookup_masks_ms;
+    if (requests_ms) *requests_ms = runner->lookup_requests_ms;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_runner_get_lookup_scope(tk_llm_runner_t* runner, uint32_t* flags) {
+    if (!runner || !flags) return TK_ERROR_INVALID_ARGUMENT;
+    *flags = runner->lookup_scope;
     return TK_SUCCESS;
 }
 
@@ -1210,9 +1277,10 @@ tk_error_code_t tk_llm_runner_prepare_generation(tk_llm_runner_t* runner, const 
     runner->prompt_tokens = (int32_t)toks.size();
     runner->n_shifts = 0;
     runner->n_discarded = 0;
-    runner->queued.clear();
+    runner->forget_queued();
     runner->ctx_ids.clear();
     runner->lookup_passes = runner->lookup_drafted = runner->lookup_accepted = 0;
+    runner->lookup_masks_ms = runner->lookup_requests_ms = 0.0;
     tk_error_code_t rc = feed(runner, toks, true);
     if (rc != TK_SUCCESS) return rc;
     runner->is_processing = true;
@@ -1224,13 +1292,7 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
     const int32_t id = runner->pending;
     if (id >= 0) runner->accept(id); /* llama_sampling_accept (tk_runner_streaming.c:61) comes before the EOS test: that id is in the window too */
     if (id < 0 || id == runner->model->tok.eos) { runner->is_processing = false; return NULL; }
-    if (!runner->queued.empty()) { /* lookup decoding: this id's row is in the cache already, and the id behind it has been sampled */
-        runner->pending = runner->queued.front();
-        runner->queued.erase(runner->queued.begin());
-        runner->lp_valid = false; /* an id a verify pass sampled: it has no record (log-probabilities were switched on behind it) */
-        runner->piece = runner->model->tok.piece(id);
-        return runner->piece.c_str();
-    }
+    /* the per-id logic is the same for an id that a verify pass queued: the window above, the grammar here */
     if (runner->grammar_on) {
         /* llama_sampling_accept: advance the grammar by the sampled token; then the reference's "grammar rule completed" test
          * (tk_runner_streaming.c:69-75): the token is NOT decoded, generation pauses, the sentinel address is returned */
@@ -1247,6 +1309,18 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
             return (const char*)1;
         }
     }
+    if (!runner->queued.empty()) { /* lookup decoding: this id's row is in the cache already, and the id behind it has been sampled */
+        runner->pending = runner->queued.front();
+        runner->queued.erase(runner->queued.begin());
+        /* its record came with it when the verify pass asked for records; an id sampled before log-probabilities were switched on has none */
+        runner->lp_valid = runner->lp_ntop >= 0 && !runner->queued_lp.empty();
+        if (!runner->queued_lp.empty()) {
+            runner->last_lp = runner->queued_lp.front();
+            runner->queued_lp.erase(runner->queued_lp.begin());
+        }
+        runner->piece = runner->model->tok.piece(id);
+        return runner->piece.c_str();
+    }
     if (runner->n_past + 1 >= runner->n_ctx) {
         bool failed = false;
         if (!context_shift(runner, 1, &failed)) { runner->is_processing = false; return NULL; }
@@ -1262,13 +1336,60 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
         int nd = tk_lookup_draft(runner->ctx_ids.data(), (int)runner->ctx_ids.size(), runner->prediction.data(), (int)runner->prediction.size(), runner->lookup_min,
                                  runner->lookup_max, runner->lookup_draft, fed + 1);
         nd = std::max(0, std::min(nd, runner->n_ctx - runner->n_past - 2));
+        /* the tables of the rows (csrc/llm/tk_lookup_scope.h): row i gets what a one-row pass behind pending, d0 .. d(i-1) would have had.  The
+         * grammar states are copies — the runner's own advances only when an id is handed out — and cut the drafts */
+        std::vector<TkGrammarState> gstates;
+        const auto t_masks = std::chrono::steady_clock::now();
+        auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+        if (runner->grammar_on && nd > 0) {
+            (void)runner->next_mask(); /* builds the trie at first use; runner->mask is row 0's mask: the state has accepted the pending id */
+            const auto& tok = runner->model->tok;
+            nd = tk_lookup_grammar_cut(
+                runner->gstate, fed + 1, nd,
+                [&](TkGrammarState* s, int32_t d) { const std::string pc = d == tok.eos ? std::string() : tok.piece(d); return !pc.empty() && s->accept(pc); },
+                [](const TkGrammarState& s) { return s.complete(); }, &gstates);
+        }
         if (nd > 0) {
+            const int n = 1 + nd;
             int n_ids = 0;
-            if (!runner->batcher->submit_verify(runner->slot, runner->n_past, fed, 1 + nd, ids, &n_ids, &err) || n_ids < 1) {
+            const bool drawn = runner->samp.temp > 0.0f, masked = runner->grammar_on, adjusted = runner->adjusted(), records = runner->lp_ntop >= 0;
+            std::vector<std::vector<uint32_t>> mask_bits(masked ? (size_t)n : 0);
+            const uint32_t* mask_ptr[1 + TK_LOOKUP_MAX_DRAFT] = {};
+            if (masked) mask_ptr[0] = runner->mask.data();
+            for (int i = 1; i < n && masked; ++i) {
+                gstates[(size_t)i].mask(runner->trie, runner->model->tok.eos, &mask_bits[(size_t)i]);
+                mask_ptr[i] = mask_bits[(size_t)i].data();
+            }
+            if (masked) runner->lookup_masks_ms += ms_since(t_masks);
+            std::vector<int32_t> windows(adjusted ? (size_t)n * (size_t)std::max(runner->pen_last_n, 1) : 0);
+            TkLogitAdjust adj[1 + TK_LOOKUP_MAX_DRAFT];
+            for (int i = 0; i < n && adjusted; ++i) {
+                int32_t* w = windows.data() + (size_t)i * (size_t)std::max(runner->pen_last_n, 1);
+                adj[i] = TkLogitAdjust{};
+                adj[i].repeat = runner->pen_repeat; adj[i].freq = runner->pen_freq; adj[i].present = runner->pen_present;
+                adj[i].n_recent = tk_lookup_row_window(runner->accepted.data(), (int)runner->accepted.size(), fed + 1, i, runner->pen_last_n, w);
+                adj[i].recent = w;
+                adj[i].n_bias = (int32_t)runner->bias_ids.size(); adj[i].bias_ids = runner->bias_ids.data(); adj[i].bias = runner->bias.data();
+            }
+            TkTokenLogprob recs[1 + TK_LOOKUP_MAX_DRAFT];
+            const auto t_request = std::chrono::steady_clock::now();
+            if (!runner->batcher->submit_verify(runner->slot, runner->n_past, fed, n, ids, &n_ids, &err, masked ? mask_ptr : nullptr, runner->next_samp(), adjusted ? adj : nullptr,
+                                                runner->lp_ntop, records ? recs : nullptr, masked || adjusted || records ? n : 0) ||
+                n_ids < 1) {
                 tk_error_set_detail("%s", err.c_str());
                 runner->is_processing = false;
                 return NULL;
             }
+            runner->lookup_requests_ms += ms_since(t_request);
+            /* the chain has drawn the ids that were kept: the counter is the one n_ids one-row passes would have left */
+            if (drawn) runner->samp.counter += (uint32_t)n_ids;
+            runner->queued_drawn = drawn;
+            runner->queued_lp.clear();
+            if (records) {
+                runner->last_lp = recs[0];
+                runner->queued_lp.assign(recs + 1, recs + n_ids);
+            }
+            runner->lp_valid = records;
             runner->lookup_passes++;
             runner->lookup_drafted += (uint64_t)nd;
             runner->lookup_accepted += (uint64_t)(n_ids - 1);
@@ -1309,7 +1430,7 @@ tk_error_code_t tk_llm_runner_reset_context(tk_llm_runner_t* runner) {
     if (!runner) return TK_ERROR_INVALID_ARGUMENT;
     runner->n_past = 0;
     runner->pending = -1;
-    runner->queued.clear();
+    runner->forget_queued();
     runner->ctx_ids.clear();
     runner->is_processing = false;
     return TK_SUCCESS;

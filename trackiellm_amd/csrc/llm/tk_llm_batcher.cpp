@@ -1,5 +1,6 @@
 #include "tk_llm_batcher.h"
 #include "tk_lookup.h"
+#include "tk_lookup_scope.h"
 #include "tk_prefix_match.h"
 
 #include <algorithm>
@@ -156,13 +157,30 @@ bool TkLlmBatcher::submit(int slot, int pos0, const int32_t* toks, int n, const 
     return true;
 }
 
-bool TkLlmBatcher::submit_verify(int slot, int pos0, const int32_t* toks, int n, int32_t* ids_out, int* n_out, std::string* err) {
+bool TkLlmBatcher::submit_verify(int slot, int pos0, const int32_t* toks, int n, int32_t* ids_out, int* n_out, std::string* err, const uint32_t* const* row_masks,
+                                 const TkSampleRow* samp, const TkLogitAdjust* row_adjust, int32_t n_top, TkTokenLogprob* records, int n_tables) {
     if (n < 1 || n > TK_LOOKUP_MAX_DRAFT + 1 || !toks || !ids_out || !n_out) { *err = "verify request: between 1 and 16 rows"; return false; }
     if (slot < 0 || slot >= (int)slot_used_.size() || pos0 < 0 || pos0 + n > n_ctx_) { *err = "rows do not fit the context window"; return false; }
+    if (const char* why = tk_logprob_check(n_top, session_.model->hp.vocab)) { *err = std::string("log-probabilities: ") + why; return false; }
+    if (n_top >= 0 && !records) { *err = "log-probabilities asked for without records to fill"; return false; }
+    if (n_top < 0 && records) { *err = "verify request: records given without an n_top"; return false; }
+    if ((row_masks || row_adjust || records) && n_tables != n) { *err = "verify request: a per-row table holds one entry per row"; return false; }
+    for (int i = 0; i < n && row_adjust; ++i)
+        if (const char* why = row_adjust[i].check(session_.model->hp.vocab)) { *err = "logit adjustment of row " + std::to_string(i) + ": " + why; return false; }
     Request r;
     r.slot = slot; r.pos0 = pos0; r.n = n; r.toks = toks; r.mask = nullptr;
     r.verify = true;
     r.hold = true;
+    bool any_mask = false, any_adj = false;
+    for (int i = 0; i < n; ++i) {
+        any_mask = any_mask || (row_masks && row_masks[i]);
+        any_adj = any_adj || (row_adjust && !row_adjust[i].neutral());
+    }
+    if (any_mask) r.row_masks = row_masks;
+    if (any_adj) { r.row_adjust = row_adjust; r.adjusted = true; }
+    if (samp && samp->temp > 0.0f) r.samp = *samp;
+    r.n_top = n_top; r.rec = records;
+    r.tabled = any_mask || any_adj || r.samp.temp > 0.0f || n_top >= 0;
     std::unique_lock<std::mutex> lk(mu_);
     if (stop_) { *err = "scheduler stopped"; return false; }
     drop_ahead(slot); /* a slot with lookup on plans no row ahead; one left from before lookup was switched on is retired like any other */
@@ -288,8 +306,21 @@ void TkLlmBatcher::loop() {
                 }
                 in_pass.push_back(Taken{r, take, (int)sq.size() - 1});
                 any_verify = any_verify || r->verify;
-                all_qualify = all_qualify && (r->verify || (r->done_rows + take == r->n && !r->mask && !(r->samp.temp > 0.0f) && !r->adjusted && r->n_top < 0));
-                if (r->done_rows + take == r->n) {
+                all_qualify = all_qualify && (r->verify ? !r->tabled : (r->done_rows + take == r->n && !r->mask && !(r->samp.temp > 0.0f) && !r->adjusted && r->n_top < 0));
+                if (r->tabled) { /* a verify request with tables (tk_lookup_scope.h): every row is sampled under its own; take == n */
+                    const size_t row0 = sq.size() - (size_t)take;
+                    for (int i = 0; i < take; ++i) {
+                        if (r->row_masks) masks[row0 + (size_t)i] = r->row_masks[i];
+                        if (r->samp.temp > 0.0f) { samps[row0 + (size_t)i] = r->samp; samps[row0 + (size_t)i].counter = tk_lookup_row_counter(r->samp.counter, i); }
+                        if (r->row_adjust && !r->row_adjust[i].neutral()) adjs[row0 + (size_t)i] = r->row_adjust[i];
+                        ntops[row0 + (size_t)i] = r->n_top;
+                        any_mask = any_mask || masks[row0 + (size_t)i] != nullptr;
+                    }
+                    completing.push_back(r);
+                    any_samp = any_samp || r->samp.temp > 0.0f;
+                    any_adj = any_adj || r->row_adjust != nullptr;
+                    any_lp = any_lp || r->n_top >= 0;
+                } else if (r->done_rows + take == r->n) {
                     completing.push_back(r);
                     masks.back() = r->mask; /* the row that is sampled */
                     samps.back() = r->samp;
@@ -411,7 +442,9 @@ void TkLlmBatcher::loop() {
                 if (!ok) { r->ok = false; r->error = session_.error; r->done_rows = r->n; }
                 if (r->done_rows == r->n) {
                     r->sampled = ok ? am[(size_t)row - 1] : -1;
-                    if (ok && r->n_top >= 0) *r->rec = recs[(size_t)row - 1]; /* the owner is blocked in submit(): its record is ours to write */
+                    if (ok && r->n_top >= 0 && r->verify) /* the records of the ids the accept rule kept, record i with id i */
+                        for (size_t i = 0; i < r->ids.size(); ++i) r->rec[i] = recs[(size_t)(row - take) + i];
+                    else if (ok && r->n_top >= 0) *r->rec = recs[(size_t)row - 1]; /* the owner is blocked in submit(): its record is ours to write */
                     for (auto it = queue_.begin(); it != queue_.end(); ++it)
                         if (*it == r) { queue_.erase(it); break; }
                     if (ok) plan_ahead(r->slot, r->pos0 + r->n - 1, r->sampled, r->mask != nullptr || r->samp.temp > 0.0f || r->hold, r->n_top);

@@ -68,6 +68,15 @@
  *   Rejected rows stay in the cache beyond the owner's n_past and are overwritten before anything attends to them, because positions are fed in
  *     ascending order: the argument made above for wasted run-ahead rows.
  *   stats()' rows count all n rows of a verify request.
+ *
+ * Verify requests with tables (submit_verify's trailing arguments; tk_lookup_scope.h).  A runner whose lookup scope covers its temperature, grammar,
+ * penalties / bias or log-probabilities gives every row of its request the tables a one-row pass at that position would have had: a mask per row, the
+ * sampling state of row 0 (row i draws with counter + i), an adjustment per row, n_top for every row and a record per row.  Such a request makes its
+ * pass go through forward() — the only entry that takes tables — with the tables on ALL its rows; forward() gives rows that are runs of consecutive
+ * positions the attention forward_verify would (tk_pass_form_rows), so a long context still takes the run form.  A pass whose verify requests carry
+ * no table and whose other requests qualify takes forward_verify as before.  Accept rule, records of the cache, rejected rows and stats are those of
+ * any verify request; the log-probability records of ids 0 .. m are handed over with them.  Everything travels through forward()'s existing
+ * parameters: the scheduler calls the six session members it always called.
  */
 #ifndef TK_LLM_BATCHER_H
 #define TK_LLM_BATCHER_H
@@ -107,7 +116,14 @@ public:
     /* Blocking: the verify pass of lookup decoding (header comment, "Verify requests"): toks[0] is the slot's pending id, toks[1 .. n) are drafts, fed at
      * positions pos0 .. pos0 + n - 1 in ONE pass, 1 <= n <= TK_LOOKUP_MAX_DRAFT + 1; every row is sampled greedily.  ids_out (room for n) receives the
      * ids the accept rule keeps, *n_out = m + 1 of them; rows pos0 .. pos0 + m are the slot's valid cache rows afterwards */
-    bool submit_verify(int slot, int pos0, const int32_t* toks, int n, int32_t* ids_out, int* n_out, std::string* err);
+    /* Tables (optional; tk_lookup_scope.h, header comment "Verify requests with tables"): the request of a runner that samples, is masked, adjusted or
+     * asks for records.  row_masks: n_tables pointers, nullptr = that row is unmasked; samp: the sampling state of row 0, row i draws with
+     * counter + i (temp <= 0: greedy); row_adjust: n_tables adjustments, checked here against the limits; n_top >= 0 with records: n_tables records,
+     * records[0 .. *n_out) filled, record i for id i.  The arrays belong to the caller until the call returns.  n_tables must be n when a per-row table
+     * is given; n_top >= 0 without records, or records without n_top, is refused.  Without any table the request is the one it always was */
+    bool submit_verify(int slot, int pos0, const int32_t* toks, int n, int32_t* ids_out, int* n_out, std::string* err, const uint32_t* const* row_masks = nullptr,
+                       const TkSampleRow* samp = nullptr, const TkLogitAdjust* row_adjust = nullptr, int32_t n_top = -1, TkTokenLogprob* records = nullptr,
+                       int n_tables = 0);
     /* Blocking: context shift of sequence `slot` (common/tk_kv_shift.h, llama.cpp's rule): the first n_keep rows stay, the n_discard rows after them are
      * dropped, rows [n_keep + n_discard, n_past) move down by n_discard.  Queued like a request: the scheduler thread runs it between passes on the
      * session stream (header comment, "Context shift").  Thread-safe; the slot's owner has no other call outstanding */
@@ -136,6 +152,11 @@ private:
         int32_t n_top = -1;           /* log-probabilities of the sampled row: -1 off */
         TkTokenLogprob* rec = nullptr; /* the owner's record, written before `finished` */
         bool verify = false;         /* a verify request: all n rows in one pass, every row sampled */
+        /* a verify request with tables (tk_lookup_scope.h): per-row masks and adjustments of the owner, `samp` the state of row 0, n_top for every row,
+         * rec an array of n records; tabled: the pass goes through forward() with these on all n rows */
+        const uint32_t* const* row_masks = nullptr;
+        const TkLogitAdjust* row_adjust = nullptr;
+        bool tabled = false;
         std::vector<int32_t> ids;     /* what the accept rule kept of its picks (m + 1 ids) */
         bool finished = false, ok = true;
         std::string error;

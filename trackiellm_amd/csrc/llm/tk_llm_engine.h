@@ -106,7 +106,9 @@ public:
      * alternatives (common/tk_token_logprob.h) into records_host[r]; checked before anything is enqueued.  A pass with a row that asks uploads the
      * table, is a form of its own (TkPassForm::logprobs: the k_token_logprobs launch behind the pick) and copies
      * the pass's records back; a record is written as far as it was filled, a row that is off leaves records_host[r] alone; any other pass runs
-     * what it always did */
+     * what it always did.  A pass with the head in which some sequence stands at several positions and whose rows keep forward_verify's layout
+     * rule takes the attention forward_verify would choose for them (tk_pass_form_rows: the run form of the long attention from
+     * tk_verify_run_min_pos on), whatever tables its rows carry: the verify pass of a runner that samples, is masked, adjusted or asks for records */
     bool forward(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, float* logits_host, int32_t* argmax_host,
                  bool lm_head = true, const uint32_t* const* row_masks = nullptr, const TkSampleRow* row_samp = nullptr,
                  const TkLogitAdjust* row_adjust = nullptr, const int32_t* row_ntop = nullptr, TkTokenLogprob* records_host = nullptr);
@@ -233,6 +235,7 @@ private:
     int32_t* d_tiles = nullptr;                         /* [1 + TK_MAX_ROWS] 16-row tiles of a multi-position pass (k_att_tiles) */
     size_t tab_cap = 0;
 public:
+    int last_pass_key = -1;  /* tk_pass_form_key of the last pass forward / forward_verify launched (a diagnostic: which attention a pass took) */
     uint64_t n_captures = 0; /* passes recorded into a graph so far, and the host time that took (diagnostics: TK_MI355X_BATCHER_TRACE) */
     double capture_ms = 0.0;
 };

@@ -1188,6 +1188,7 @@ hipGraphExec_t TkLlmSession::capture_pass(const TkPassForm& f, int nrows) {
 }
 
 bool TkLlmSession::launch_pass(const TkPassForm& f, int nrows, bool use_graph) {
+    last_pass_key = tk_pass_form_key(f);
     if (use_graph) {
         const hipGraphExec_t g = capture_pass(f, nrows);
         if (!g) return false;
@@ -1317,7 +1318,14 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
     }
     /* masked, sampled and greedy rows ride the same graphs (their tables are data); without the head the pass ropes apart whatever its rows, so
      * that it is the form of a prompt chunk */
-    if (!launch_pass(tk_pass_form(lm_head, lm_head && distinct, nrows, top, pass_caps(nrows), any_adj, any_lp), nrows, graphs_enabled())) return false;
+    /* with the head, rows that are runs of consecutive positions — a verify pass with tables — take the attention a verify pass of them takes */
+    bool runs = lm_head && !distinct && nrows <= TK_LONG_ATT_MAX_ROWS;
+    for (int r = 1; r < nrows && runs; ++r) {
+        if (seq[r] == seq[r - 1]) { runs = pos[r] == pos[r - 1] + 1; continue; }
+        for (int b = 0; b + 1 < r && runs; ++b) runs = seq[b] != seq[r];
+    }
+    const TkPassForm form = lm_head ? tk_pass_form_rows(distinct, runs, nrows, top, pass_caps(nrows), any_adj, any_lp) : tk_pass_form(false, false, nrows, top, pass_caps(nrows));
+    if (!launch_pass(form, nrows, graphs_enabled())) return false;
     HIPQ(hipGetLastError());
     if (!lm_head) { HIPQ(hipStreamSynchronize(stream)); return true; }
     if (logits_host) HIPQ(hipMemcpyAsync(logits_host, logits, (size_t)nrows * model->hp.vocab * 4, hipMemcpyDeviceToHost, stream));

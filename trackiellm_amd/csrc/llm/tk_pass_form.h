@@ -20,7 +20,8 @@ enum TkPassAttn {
     TK_ATT_ROW = 0, /* k_attention, one workgroup per (row, KV group) */
     TK_ATT_TILED,   /* k_att_tiles once per pass, then k_attention_prefill */
     TK_ATT_LONG,    /* the long-context form of a pass that holds every sequence once: append + scores + PV launches spread over the chip */
-    TK_ATT_RUN      /* the run variant of the long-context form: several consecutive positions of a sequence (verify passes only) */
+    TK_ATT_RUN      /* the run variant of the long-context form: several consecutive positions of a sequence (verify passes, and forward() with the head
+                     * over rows that are such runs: tk_pass_form_rows) */
 };
 
 struct TkPassForm {
@@ -73,6 +74,14 @@ static inline TkPassForm tk_pass_form(bool head, bool once, int nrows, int top, 
 }
 /* a verify pass of form 0 / 2 / 4 is a sampling pass that holds several positions of a sequence, with the attention given */
 static inline TkPassForm tk_pass_form_verify(int form) { return TkPassForm{true, false, tk_verify_attn(form), false, false}; }
+/* forward() with the head, described row by row.  once: every sequence at most once — tk_pass_form's form.  Otherwise some sequence stands at several
+ * positions; runs: the rows also keep forward_verify's layout rule (each sequence's rows consecutive, ascending, contiguous).  Such a pass is a verify
+ * pass whose rows may carry masks, sampling states, adjustments and log-probabilities (tk_lookup_scope.h), so it takes the attention a verify pass of
+ * these rows takes: the run form where tk_verify_form says 4, else the tiles or the per-row form as before */
+static inline TkPassForm tk_pass_form_rows(bool once, bool runs, int nrows, int top, const TkPassCaps& c, bool adjust = false, bool logprobs = false) {
+    if (once || !runs || tk_verify_form(nrows, top, c) != 4) return tk_pass_form(true, once, nrows, top, c, adjust, logprobs);
+    return TkPassForm{true, false, TK_ATT_RUN, adjust, logprobs};
+}
 
 /* the kernel number tk_mi355x_attention_plan_at / _plan_verify report: the launcher's own plan (0 k_attention, 1 its narrow form, 2
  * k_attention_prefill) with the pass's choice on top — 3 the long-context form, 4 its run variant, 0 for a tiled plan below TK_TILED_ATT_FROM_POS */

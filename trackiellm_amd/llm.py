@@ -473,6 +473,66 @@ class LlmSession:
         check(lib().tk_mi355x_llm_forward_verify(self.h, n, _p(seq), _p(pos), _p(tok), int(form), _p(logits), _p(picks)))
         return logits, picks
 
+    def forward_rows(self, seq, pos, tok, masks=None, sampling=None, adjust=None, n_top=None, want_logits=True, records=None):
+        """one sampling pass with every optional per-row table (tk_mi355x_llm_forward_rows): masks = [None | uint32 array of (vocab + 31) // 32 words]
+        per row; sampling, adjust, n_top and records as forward_logprobs takes them, each None = not given.  The rows may be several consecutive
+        positions of a sequence (the verify pass of a runner whose lookup scope is not 0).  Returns (logits or None, picks, records or None)"""
+        from .pick import logit_adjust_rows
+        seq = np.ascontiguousarray(seq, dtype=np.int32)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        tok = np.ascontiguousarray(tok, dtype=np.int32)
+        n = len(seq)
+        if len(pos) != n or len(tok) != n:
+            raise ValueError("forward_rows: seq, pos and tok need one entry per row")
+        words = (self.vocab + 31) // 32
+        mtab, mkeep = None, []
+        if masks is not None:
+            if len(masks) != n:
+                raise ValueError("forward_rows: one mask (or None) per row")
+            mtab = (C.c_void_p * n)()
+            for r, m in enumerate(masks):
+                if m is None:
+                    continue
+                m = np.ascontiguousarray(m, dtype=np.uint32).reshape(-1)
+                if m.size != words:
+                    raise ValueError("forward_rows: a mask holds (vocab + 31) // 32 words")
+                mkeep.append(m)
+                mtab[r] = m.ctypes.data
+        tab = None
+        if sampling is not None:
+            if len(sampling) != n:
+                raise ValueError("forward_rows: one sampling state per row")
+            tab = (Sampling * n)()
+            for r, (temp, top_k, top_p, min_p, seed, counter) in enumerate(sampling):
+                tab[r] = Sampling(temp, top_p, min_p, top_k, seed, counter, 0)
+        if adjust is not None and len(adjust) != n:
+            raise ValueError("forward_rows: one adjustment (or None) per row")
+        adj, keep = logit_adjust_rows(adjust) if adjust is not None else (None, None)
+        if n_top is not None:
+            n_top = np.ascontiguousarray(n_top, dtype=np.int32).reshape(-1)
+            if n_top.size != n:
+                raise ValueError("forward_rows: one n_top per row")
+            if records is None:
+                records = np.zeros(n, TOKEN_LOGPROB_DTYPE)
+        if records is not None and (records.dtype != TOKEN_LOGPROB_DTYPE or not records.flags.c_contiguous or records.size < n):
+            raise ValueError("forward_rows: records must be a C-contiguous TOKEN_LOGPROB_DTYPE array with one entry per row")
+        logits = np.empty((n, self.vocab), dtype=np.float32) if want_logits else None
+        picks = np.empty(n, dtype=np.int32)
+        f = lib().tk_mi355x_llm_forward_rows
+        f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10
+        check(f(self.h, n, _p(seq), _p(pos), _p(tok), C.cast(mtab, C.c_void_p) if mtab is not None else None, C.cast(tab, C.c_void_p) if tab is not None else None,
+                C.cast(adj, C.c_void_p) if adj is not None else None, _p(n_top), _p(logits), _p(picks), _p(records)))
+        del keep, mkeep
+        return logits, picks, records
+
+    @property
+    def last_pass_key(self):
+        """the form key (csrc/llm/tk_pass_form.h) of the last pass this session ran, -1 before the first: with the head,
+        5 + 4 * attention + 2 * adjusted + with records, attention 4 = the run form (tk_mi355x_llm_session_last_pass_key)"""
+        k = C.c_int(-1)
+        check(lib().tk_mi355x_llm_session_last_pass_key(self.h, C.byref(k)))
+        return k.value
+
     def forward_stage(self, seq, pos, layer0, layer1, tok=None, x_in=None, x_out=None, head=False, on_host=True):
         """layers [layer0, layer1) of one pass (pipeline stage).  x_in / x_out: float32 [n][d_model] numpy arrays (on_host) or raw
         device addresses (ints, e.g. torch_tensor.data_ptr()) on this session's GPU.  Returns arg max ids when head."""
@@ -777,6 +837,12 @@ class LlmRunner:
     def add_tool_response(self, tool_name, tool_output):
         check(lib().tk_llm_runner_add_tool_response(self.h, tool_name.encode(), tool_output.encode()))
 
+    def tool_call_text(self):
+        """what the tool-call grammar has accepted since the last prepare(), as bytes (tk_mi355x_llm_runner_tool_call_text)"""
+        f = lib().tk_mi355x_llm_runner_tool_call_text
+        f.restype, f.argtypes = C.c_char_p, [C.c_void_p]
+        return f(self.h) or b""
+
     def set_context_shift(self, on, n_keep=0):
         """llama.cpp's context shift instead of stopping at the end of the context (off by default): keep the first n_keep rows (-1 = the last prompt's
         token count), drop half of the rest, move the others down (tk_mi355x_llm_runner_set_context_shift)"""
@@ -792,6 +858,31 @@ class LlmRunner:
         """lookup decoding for a greedy runner (off by default; n_draft 0 = off): up to n_draft ids drafted per pass from the prediction, then from
         the context, by the longest n-gram of ngram_max .. ngram_min ids that ends the context (tk_mi355x_llm_runner_set_lookup)"""
         check(lib().tk_mi355x_llm_runner_set_lookup(self.h, int(n_draft), int(ngram_min), int(ngram_max)))
+
+    def set_lookup_scope(self, sampled=False, grammar=False, adjusted=False, logprobs=False):
+        """under which conditions a runner with lookup on still drafts (tk_mi355x_llm_runner_set_lookup_scope): with a temperature, under a grammar
+        mask, with penalties or a logit bias, with log-probabilities on.  All False (the default): a greedy, unmasked, unadjusted runner only"""
+        f = lib().tk_mi355x_llm_runner_set_lookup_scope
+        f.argtypes = [C.c_void_p, C.c_uint32]
+        check(f(self.h, (1 if sampled else 0) | (2 if grammar else 0) | (4 if adjusted else 0) | (8 if logprobs else 0)))
+
+    def lookup_scope(self):
+        """the scope's flag bits: 1 sampled, 2 grammar, 4 adjusted, 8 logprobs"""
+        v = C.c_uint32(0)
+        check(lib().tk_mi355x_llm_runner_get_lookup_scope(self.h, C.byref(v)))
+        return v.value
+
+    def lookup_host_ms(self):
+        """(ms building the per-row masks of the verify requests, ms inside the verify requests) since the last prepare()"""
+        a, b = C.c_double(0), C.c_double(0)
+        check(lib().tk_mi355x_llm_runner_lookup_host_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def set_lookup_scope_bits(self, flags):
+        """set_lookup_scope by flag bits; unknown bits raise TkError"""
+        f = lib().tk_mi355x_llm_runner_set_lookup_scope
+        f.argtypes = [C.c_void_p, C.c_uint32]
+        check(f(self.h, int(flags)))
 
     def set_logprobs(self, n_top):
         """log-probabilities of every sampled token (off by default): -1 = off, 0 = the produced id only, 1 .. 20 = that many alternatives
