@@ -522,6 +522,35 @@ TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_graph_captures(tk_mi35
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_grammar_check(const char* gbnf, const char* text, int32_t* n_accepted, int32_t* complete);
 /* allowed[b] = 1 when byte b may follow `prefix` (which must itself be accepted) */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_grammar_next_bytes(const char* gbnf, const char* prefix, uint8_t allowed[256], int32_t* complete);
+/* ---- grammar masks built on the device; a grammar per runner (csrc/common/tk_grammar_walk.h) ---- */
+/* The allowed-token mask of a grammar state, built by k_grammar_mask inside the runner's pass instead of by the host's trie walk: off (0, the default) or
+ * on (1).  Off: the runner submits exactly what it always did.  On: every masked row of the runner — the sampled row of a prompt or a token, and each row
+ * of a scoped lookup verify request — carries its grammar state; the bits are exact (bit for bit the host's).  A state that does not fit the image's
+ * caps, a grammar without an image, and a runner whose session holds 8 other grammars already, take the host mask, row by row.  A token whose walk
+ * exceeds a cap is written as forbidden and counted: the runner then discards that request's result and submits it once more with host masks, so the
+ * ids it emits are the ids of the setting off in every case */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_device_mask(struct tk_llm_runner_s* runner, int on);
+/* since the last prepare_generation: mask rows built on the device, built on the host, and requests submitted again because of an undecided token */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_mask_stats(struct tk_llm_runner_s* runner, uint64_t* device_rows, uint64_t* host_rows, uint64_t* redone_requests);
+/* The runner's grammar becomes `gbnf` (llama.cpp server's `grammar` field); NULL restores the tool-call grammar loaded at create.  It is armed by
+ * prepare_generation(use_tool_grammar = true) as before; the completion sentinel and tool_call_text behave as before.  A text that does not parse:
+ * TK_ERROR_INVALID_ARGUMENT, the parser's message in the error detail, the grammar unchanged.  While a generation is in progress:
+ * TK_ERROR_INVALID_STATE.  Works with the device mask on and off */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_runner_set_grammar(struct tk_llm_runner_s* runner, const char* gbnf);
+/* k_grammar_mask alone on host arrays (tests), tk_mi355x_token_logprobs_probe's contract.  n_rows mask rows; row r is the state after the grammar
+ * accepted prefixes[r], or is off when prefixes[r] is NULL (its bits and its count stay as given).  The vocabulary: offsets [vocab + 1] ascending from 0
+ * into `pieces`; an empty piece is never allowed; eos (-1: none) is allowed iff the state is complete, whatever its piece.  bits [n_rows][(vocab + 31) /
+ * 32] IN/OUT; undecided [n_rows] receives, for every live row, the number of tokens whose walk exceeded a cap (written 0).  device >= 0: ONE production
+ * launch over the live rows, bits read back whole.  device < 0: the same walk in a host loop, no GPU touched.  Everything is validated before a device is
+ * touched; TK_ERROR_INVALID_ARGUMENT with nothing written: n_rows outside [1, tk_mi355x_llm_max_rows()], vocab outside [1, 2^20], eos outside
+ * [-1, vocab), offsets that do not start at 0, descend or pass 2^26, a prefix the grammar does not accept, a state or grammar without an image;
+ * TK_ERROR_CONFIG_PARSE_FAILED: the grammar does not parse */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_grammar_mask_probe(int device, const char* gbnf, int32_t n_rows, const char* const* prefixes, const uint8_t* pieces,
+                                                                 const uint32_t* offsets, int32_t vocab, int32_t eos, uint32_t* bits, int32_t* undecided);
+/* timing (tools/time_grammar_mask.py): n_rows equal states after `prefix`; device_ms = state upload + launch, the average of `iters` rounds between two
+ * events; host_ms = the trie walk it replaces for ONE row, in the same process */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_time_grammar_mask(int device, const char* gbnf, const char* prefix, int32_t n_rows, const uint8_t* pieces,
+                                                                const uint32_t* offsets, int32_t vocab, int32_t eos, int32_t iters, float* device_ms, float* host_ms);
 /* text accepted by the grammar in the current generation: the tool call to read after tk_llm_runner_generate_next_token
  * returned the sentinel (const char*)1; valid until the next prepare_generation */
 struct tk_llm_runner_s;

@@ -780,6 +780,146 @@ tk_error_code_t tk_mi355x_grammar_next_bytes(const char* gbnf, const char* prefi
     return TK_SUCCESS;
 }
 
+/* k_grammar_mask alone on host arrays (include/tk/tk_mi355x_ext.h): everything is validated, and every state exported, before a device is touched */
+tk_error_code_t tk_mi355x_grammar_mask_probe(int device, const char* gbnf, int32_t n_rows, const char* const* prefixes, const uint8_t* pieces, const uint32_t* offsets,
+                                             int32_t vocab, int32_t eos, uint32_t* bits, int32_t* undecided) {
+    if (!prefixes || !pieces || !offsets || !bits || !undecided || n_rows < 1 || n_rows > TK_MAX_ROWS || vocab < 1 || vocab > (1 << 20) || eos < -1 || eos >= vocab)
+        return TK_ERROR_INVALID_ARGUMENT;
+    if (offsets[0] != 0) return fail(TK_ERROR_INVALID_ARGUMENT, "grammar mask: offsets start at 0");
+    for (int32_t t = 0; t < vocab; ++t)
+        if (offsets[t + 1] < offsets[t] || offsets[t + 1] > (1u << 26)) return fail(TK_ERROR_INVALID_ARGUMENT, "grammar mask: offsets ascend and stay below 2^26");
+    TkGrammar g;
+    std::string err;
+    if (!g.parse(gbnf ? gbnf : TK_DEFAULT_TOOL_CALL_GBNF, &err)) return fail(TK_ERROR_CONFIG_PARSE_FAILED, "GBNF: " + err);
+    TkGrammarImage gi;
+    if (!g.flatten(&gi)) return fail(TK_ERROR_INVALID_ARGUMENT, "grammar mask: the grammar has too many elements for an image");
+    std::vector<TkGrammarStateImage> states;
+    std::vector<int32_t> live;
+    for (int32_t r = 0; r < n_rows; ++r) {
+        if (!prefixes[r]) continue; /* the row is off: its bits and its count stay as the caller left them */
+        TkGrammarState st;
+        st.init(&g);
+        TkGrammarStateImage img;
+        if (!st.accept(std::string(prefixes[r]))) return fail(TK_ERROR_INVALID_ARGUMENT, "grammar mask: prefix " + std::to_string(r) + " is not in the grammar");
+        if (!st.export_image(&img)) return fail(TK_ERROR_INVALID_ARGUMENT, "grammar mask: the state after prefix " + std::to_string(r) + " does not fit the image's caps");
+        img.mask_row = r;
+        img.grammar = 0;
+        states.push_back(img);
+        live.push_back(r);
+    }
+    const size_t words = ((size_t)vocab + 31) / 32;
+    if (states.empty()) return TK_SUCCESS;
+    if (device < 0) {
+        for (size_t i = 0; i < states.size(); ++i) undecided[live[i]] = tk_grammar_mask_row(gi, states[i], offsets, pieces, vocab, eos, bits + (size_t)live[i] * words);
+        return TK_SUCCESS;
+    }
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    const std::vector<uint32_t>& gw = g.flat_words();
+    std::vector<int32_t> und(states.size(), 0);
+    const uint8_t none = 0;
+    struct Buf { const void* host; size_t bytes; void* dev; };
+    enum { WORDS, STATES, OFFSETS, PIECES, BITS, UND, ARENA };
+    Buf b[] = {{gw.data(), gw.size() * 4, nullptr}, {states.data(), states.size() * sizeof(TkGrammarStateImage), nullptr}, {offsets, ((size_t)vocab + 1) * 4, nullptr},
+               {offsets[vocab] ? pieces : &none, offsets[vocab] ? (size_t)offsets[vocab] : 1, nullptr}, {bits, (size_t)n_rows * words * 4, nullptr}, {und.data(), und.size() * 4, nullptr},
+               {nullptr, sizeof(TkGrammarImage), nullptr}};
+    bool ok = true;
+    for (Buf& q : b) ok = ok && hipMalloc(&q.dev, q.bytes) == hipSuccess && (!q.host || hipMemcpy(q.dev, q.host, q.bytes, hipMemcpyHostToDevice) == hipSuccess);
+    TkGrammarImage di;
+    TkGrammar::image_over((const uint32_t*)b[WORDS].dev, gi.n_rules, gi.n_elems, gi.n_sets, gi.root, &di);
+    ok = ok && hipMemcpy(b[ARENA].dev, &di, sizeof di, hipMemcpyHostToDevice) == hipSuccess;
+    tk_error_code_t rc = ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
+    if (ok) {
+        tk_launch_grammar_mask((const TkGrammarImage*)b[ARENA].dev, (const TkGrammarStateImage*)b[STATES].dev, (int)states.size(), (const uint32_t*)b[OFFSETS].dev,
+                               (const uint8_t*)b[PIECES].dev, vocab, eos, (uint32_t*)b[BITS].dev, (int32_t*)b[UND].dev, nullptr);
+        if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(bits, b[BITS].dev, b[BITS].bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+                 hipMemcpy(und.data(), b[UND].dev, b[UND].bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = TK_ERROR_GPU_ROCM_ERROR;
+        else
+            for (size_t i = 0; i < states.size(); ++i) undecided[live[i]] = und[i];
+    }
+    for (Buf& q : b) if (q.dev) (void)hipFree(q.dev);
+    return rc;
+}
+
+/* the launch and the host call it replaces, timed side by side (tools/time_grammar_mask.py): the tool-call grammar (gbnf NULL) after `prefix`, n_rows
+ * equal rows over the given vocabulary.  device_ms: the state upload plus the launch, `iters` times between two events after one untimed round, the
+ * average of one; host_ms: TkGrammarState::mask over a trie of the same pieces, the average of min(iters, 20) calls for ONE row */
+tk_error_code_t tk_mi355x_time_grammar_mask(int device, const char* gbnf, const char* prefix, int32_t n_rows, const uint8_t* pieces, const uint32_t* offsets, int32_t vocab,
+                                            int32_t eos, int32_t iters, float* device_ms, float* host_ms) {
+    if (!prefix || !pieces || !offsets || !device_ms || !host_ms || n_rows < 1 || n_rows > TK_MAX_ROWS || vocab < 1 || vocab > (1 << 20) || eos < -1 || eos >= vocab || iters < 1 ||
+        iters > 100000 || offsets[0] != 0)
+        return TK_ERROR_INVALID_ARGUMENT;
+    for (int32_t t = 0; t < vocab; ++t)
+        if (offsets[t + 1] < offsets[t] || offsets[t + 1] > (1u << 26)) return TK_ERROR_INVALID_ARGUMENT;
+    TkGrammar g;
+    std::string err;
+    if (!g.parse(gbnf ? gbnf : TK_DEFAULT_TOOL_CALL_GBNF, &err)) return fail(TK_ERROR_CONFIG_PARSE_FAILED, "GBNF: " + err);
+    TkGrammarImage gi;
+    TkGrammarState st;
+    st.init(&g);
+    TkGrammarStateImage img;
+    if (!g.flatten(&gi) || !st.accept(std::string(prefix)) || !st.export_image(&img)) return fail(TK_ERROR_INVALID_ARGUMENT, "grammar mask timing: no image for this grammar and prefix");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TK_ERROR_GPU_DEVICE_NOT_FOUND;
+    if (device < 0 || device >= n || hipSetDevice(device) != hipSuccess) return TK_ERROR_INVALID_ARGUMENT;
+    {   /* the host call */
+        std::vector<std::string> pcs((size_t)vocab);
+        for (int32_t t = 0; t < vocab; ++t) if (t != eos) pcs[(size_t)t].assign((const char*)pieces + offsets[t], offsets[t + 1] - offsets[t]);
+        TkTokenTrie trie;
+        trie.build(pcs);
+        std::vector<uint32_t> hb;
+        st.mask(trie, eos, &hb);
+        const int reps = iters < 20 ? iters : 20;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int i = 0; i < reps; ++i) st.mask(trie, eos, &hb);
+        *host_ms = (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / reps);
+    }
+    const size_t words = ((size_t)vocab + 31) / 32;
+    const std::vector<uint32_t>& gw = g.flat_words();
+    void *d_words = nullptr, *d_states = nullptr, *d_off = nullptr, *d_pieces = nullptr, *d_bits = nullptr, *d_und = nullptr, *d_arena = nullptr;
+    TkGrammarStateImage* h_states = nullptr;
+    hipStream_t s = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok = hipMalloc(&d_words, gw.size() * 4) == hipSuccess && hipMalloc(&d_states, (size_t)n_rows * sizeof img) == hipSuccess && hipMalloc(&d_off, ((size_t)vocab + 1) * 4) == hipSuccess &&
+              hipMalloc(&d_pieces, (size_t)offsets[vocab] + 1) == hipSuccess && hipMalloc(&d_bits, (size_t)n_rows * words * 4) == hipSuccess && hipMalloc(&d_und, (size_t)n_rows * 4) == hipSuccess &&
+              hipMalloc(&d_arena, sizeof(TkGrammarImage)) == hipSuccess && hipHostMalloc((void**)&h_states, (size_t)n_rows * sizeof img, hipHostMallocDefault) == hipSuccess &&
+              hipMemcpy(d_words, gw.data(), gw.size() * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_off, offsets, ((size_t)vocab + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d_pieces, pieces, offsets[vocab], hipMemcpyHostToDevice) == hipSuccess && hipStreamCreate(&s) == hipSuccess && hipEventCreate(&e0) == hipSuccess &&
+              hipEventCreate(&e1) == hipSuccess;
+    TkGrammarImage di;
+    TkGrammar::image_over((const uint32_t*)d_words, gi.n_rules, gi.n_elems, gi.n_sets, gi.root, &di);
+    ok = ok && hipMemcpy(d_arena, &di, sizeof di, hipMemcpyHostToDevice) == hipSuccess;
+    tk_error_code_t rc = ok ? TK_SUCCESS : TK_ERROR_GPU_ROCM_ERROR;
+    if (ok) {
+        img.grammar = 0;
+        for (int r = 0; r < n_rows; ++r) { h_states[r] = img; h_states[r].mask_row = r; }
+        auto round = [&] { /* what TkLlmSession::forward enqueues for its device rows */
+            (void)hipMemcpyAsync(d_states, h_states, (size_t)n_rows * sizeof img, hipMemcpyHostToDevice, s);
+            (void)hipMemsetAsync(d_und, 0, (size_t)n_rows * 4, s);
+            tk_launch_grammar_mask((const TkGrammarImage*)d_arena, (const TkGrammarStateImage*)d_states, n_rows, (const uint32_t*)d_off, (const uint8_t*)d_pieces, vocab, eos,
+                                   (uint32_t*)d_bits, (int32_t*)d_und, s);
+        };
+        round();
+        (void)hipEventRecord(e0, s);
+        for (int i = 0; i < iters; ++i) round();
+        (void)hipEventRecord(e1, s);
+        float ms = 0.0f;
+        if (hipGetLastError() != hipSuccess) rc = TK_ERROR_GPU_KERNEL_LAUNCH;
+        else if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = TK_ERROR_GPU_ROCM_ERROR;
+        else *device_ms = ms / (float)iters;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (s) (void)hipStreamDestroy(s);
+    if (h_states) (void)hipHostFree(h_states);
+    void* ptrs[] = {d_words, d_states, d_off, d_pieces, d_bits, d_und, d_arena};
+    for (void* q : ptrs) if (q) (void)hipFree(q);
+    return rc;
+}
+
 /* ------------------------------------------------------------------ reference surface ------ */
 
 struct tk_model_loader_s {
@@ -1009,18 +1149,77 @@ struct tk_llm_runner_s {
     bool trie_built = false;
     std::vector<uint32_t> mask;
     std::string tool_call_text; /* what the grammar has accepted so far: the tool call the host reads after the sentinel */
-    /* allowed-token bits for the next sample, or nullptr when sampling is unconstrained */
-    const uint32_t* next_mask() {
-        if (!grammar_on) return nullptr;
+    std::string tool_grammar_text; /* what was loaded at create: tk_mi355x_llm_runner_set_grammar(NULL) goes back to it */
+    /* masks built on the device (tk_mi355x_llm_runner_set_device_mask, csrc/common/tk_grammar_walk.h), off by default.  gslot: the grammar's image in
+     * the session's arena, -2 = not asked for yet, -1 = none (no image, or the arena is full: host masks).  attached: the mask pointers of the
+     * request being submitted that stand for a state on the device.  The three counters run since the last prepare_generation */
+    bool device_mask = false;
+    bool vocab_sent = false;
+    int gslot = -2;
+    std::vector<const uint32_t*> attached;
+    uint64_t mask_device_rows = 0, mask_host_rows = 0, mask_redone = 0;
+    bool device_ready() {
+        if (gslot != -2) return gslot >= 0;
+        gslot = -1;
+        TkGrammarImage gi;
+        if (!grammar.flatten(&gi)) return false;
+        TkLlmSession* ses = batcher->session();
+        if (!vocab_sent) { /* the vocabulary image: the pieces the trie indexes, back to back */
+            const int vocab = model->model.hp.vocab;
+            std::vector<uint32_t> off((size_t)vocab + 1, 0u);
+            std::string bytes;
+            for (int i = 0; i < vocab; ++i) {
+                if (i != model->tok.eos) bytes += model->tok.piece(i);
+                off[(size_t)i + 1] = (uint32_t)bytes.size();
+            }
+            if (!ses->install_vocab_image(off.data(), (const uint8_t*)bytes.data(), model->tok.eos)) return false;
+            vocab_sent = true;
+        }
+        const std::vector<uint32_t>& w = grammar.flat_words();
+        gslot = ses->grammar_slot(w.data(), w.size(), gi.n_rules, gi.n_elems, gi.n_sets, gi.root);
+        return gslot >= 0;
+    }
+    /* the mask of one sampled row whose grammar state is `s`: the pointer the scheduler is given.  With the device mask on the state is attached to
+     * that pointer and the bits are built by the pass itself (the words behind the pointer are not read); a state without an image, and every row
+     * when host_only, takes TkGrammarState::mask */
+    const uint32_t* row_mask(const TkGrammarState& s, std::vector<uint32_t>* bits, bool host_only) {
+        if (device_mask && !host_only && device_ready()) {
+            TkGrammarStateImage img;
+            if (s.export_image(&img)) {
+                img.grammar = gslot;
+                bits->resize(((size_t)model->model.hp.vocab + 31) / 32);
+                if (batcher->session()->attach_grammar_state(bits->data(), img)) {
+                    attached.push_back(bits->data());
+                    mask_device_rows++;
+                    return bits->data();
+                }
+            }
+        }
         if (!trie_built) {
             std::vector<std::string> pieces((size_t)model->model.hp.vocab);
             for (int i = 0; i < (int)pieces.size(); ++i) pieces[i] = (i == model->tok.eos) ? std::string() : model->tok.piece(i);
             trie.build(pieces);
             trie_built = true;
         }
-        gstate.mask(trie, model->tok.eos, &mask);
-        return mask.data();
+        s.mask(trie, model->tok.eos, bits);
+        mask_host_rows++;
+        return bits->data();
     }
+    /* after the request: the attached states are forgotten.  true (ok: the request succeeded): a row's mask was not built, or the walk left one of
+     * its tokens undecided — the row may have picked from too small a set, and the request is submitted again with host masks */
+    bool finish_masks(bool ok) {
+        bool redo = false;
+        for (const uint32_t* p : attached) {
+            bool ran = false;
+            int32_t undecided = 0;
+            batcher->session()->detach_grammar_state(p, &ran, &undecided);
+            redo = redo || !ran || undecided > 0;
+        }
+        attached.clear();
+        return ok && redo;
+    }
+    /* allowed-token bits for the next sample, or nullptr when sampling is unconstrained */
+    const uint32_t* next_mask(bool host_only = false) { return grammar_on ? row_mask(gstate, &mask, host_only) : nullptr; }
 };
 
 /* the reference reads the grammar from a cwd-relative path; fall back to the built-in text of the same language */
@@ -1122,6 +1321,35 @@ tk_error_code_t tk_mi355x_llm_runner_set_lookup_scope(tk_llm_runner_t* runner, u
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_llm_runner_set_device_mask(tk_llm_runner_t* runner, int on) {
+    if (!runner || (on != 0 && on != 1)) return TK_ERROR_INVALID_ARGUMENT;
+    runner->device_mask = on != 0;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_runner_mask_stats(tk_llm_runner_t* runner, uint64_t* device_rows, uint64_t* host_rows, uint64_t* redone_requests) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    if (device_rows) *device_rows = runner->mask_device_rows;
+    if (host_rows) *host_rows = runner->mask_host_rows;
+    if (redone_requests) *redone_requests = runner->mask_redone;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_runner_set_grammar(tk_llm_runner_t* runner, const char* gbnf) {
+    if (!runner) return TK_ERROR_INVALID_ARGUMENT;
+    if (runner->is_processing) return fail(TK_ERROR_INVALID_STATE, "set_grammar: a generation is in progress");
+    TkGrammar g;
+    std::string err;
+    const bool parsed = g.parse(gbnf ? std::string(gbnf) : runner->tool_grammar_text, &err);
+    if (gbnf && !parsed) return fail(TK_ERROR_INVALID_ARGUMENT, "GBNF: " + err); /* the runner's grammar is unchanged */
+    /* NULL: the state tk_llm_runner_create left, a tool grammar that was rejected there included */
+    runner->grammar = std::move(g); /* the same object: the grammar state keeps pointing at it */
+    runner->has_grammar = parsed;
+    runner->grammar_on = false; /* armed by the next prepare_generation(use_tool_grammar = true) */
+    runner->gslot = -2;
+    return TK_SUCCESS;
+}
+
 tk_error_code_t tk_mi355x_llm_runner_lookup_host_ms(tk_llm_runner_t* runner, double* masks_ms, double* requests_ms) {
     if (!runner) return TK_ERROR_INVALID_ARGUMENT;
     if (masks_ms) *masks_ms = runner->lookup_masks_ms;
@@ -1177,7 +1405,8 @@ tk_error_code_t tk_llm_runner_create(tk_llm_runner_t** out_runner, void* model_h
         }
     }
     std::string gerr;
-    r->has_grammar = r->grammar.parse(load_tool_grammar_text(), &gerr);
+    r->tool_grammar_text = load_tool_grammar_text();
+    r->has_grammar = r->grammar.parse(r->tool_grammar_text, &gerr);
     if (!r->has_grammar) tk_error_set_detail("tool-call grammar rejected (%s): tool grammar disabled", gerr.c_str()); /* the reference logs and goes on */
     {
         std::lock_guard<std::mutex> gl(g_models_mu);
@@ -1250,9 +1479,14 @@ static tk_error_code_t feed(tk_llm_runner_s* r, const std::vector<int32_t>& toks
     int32_t am = -1;
     std::string err;
     /* whole_context (prepare_generation): the tokens start at position 0, so the scheduler may keep or copy rows the cache already holds for them */
-    if (!r->batcher->submit(r->slot, r->n_past, toks.data(), (int)toks.size(), r->next_mask(), &am, &err, r->next_samp(), whole_context ? &r->last_prompt : nullptr, r->next_adjust(),
-                            r->lookup_active(), r->lp_ntop, r->lp_ntop >= 0 ? &r->last_lp : nullptr))
-        return fail(TK_ERROR_INFERENCE_FAILED, err);
+    bool ok = r->batcher->submit(r->slot, r->n_past, toks.data(), (int)toks.size(), r->next_mask(), &am, &err, r->next_samp(), whole_context ? &r->last_prompt : nullptr,
+                                 r->next_adjust(), r->lookup_active(), r->lp_ntop, r->lp_ntop >= 0 ? &r->last_lp : nullptr);
+    if (r->finish_masks(ok)) { /* an undecided token: the sampled row again, at its position, under a host mask; nothing of the runner has advanced */
+        r->mask_redone++;
+        ok = r->batcher->submit(r->slot, r->n_past + (int)toks.size() - 1, &toks.back(), 1, r->next_mask(true), &am, &err, r->next_samp(), nullptr, r->next_adjust(),
+                                r->lookup_active(), r->lp_ntop, r->lp_ntop >= 0 ? &r->last_lp : nullptr);
+    }
+    if (!ok) return fail(TK_ERROR_INFERENCE_FAILED, err);
     r->lp_valid = r->lp_ntop >= 0;
     if (r->samp.temp > 0.0f) r->samp.counter++;
     r->n_past += (int)toks.size();
@@ -1281,6 +1515,7 @@ tk_error_code_t tk_llm_runner_prepare_generation(tk_llm_runner_t* runner, const 
     runner->ctx_ids.clear();
     runner->lookup_passes = runner->lookup_drafted = runner->lookup_accepted = 0;
     runner->lookup_masks_ms = runner->lookup_requests_ms = 0.0;
+    runner->mask_device_rows = runner->mask_host_rows = runner->mask_redone = 0;
     tk_error_code_t rc = feed(runner, toks, true);
     if (rc != TK_SUCCESS) return rc;
     runner->is_processing = true;
@@ -1342,7 +1577,6 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
         const auto t_masks = std::chrono::steady_clock::now();
         auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
         if (runner->grammar_on && nd > 0) {
-            (void)runner->next_mask(); /* builds the trie at first use; runner->mask is row 0's mask: the state has accepted the pending id */
             const auto& tok = runner->model->tok;
             nd = tk_lookup_grammar_cut(
                 runner->gstate, fed + 1, nd,
@@ -1355,12 +1589,6 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
             const bool drawn = runner->samp.temp > 0.0f, masked = runner->grammar_on, adjusted = runner->adjusted(), records = runner->lp_ntop >= 0;
             std::vector<std::vector<uint32_t>> mask_bits(masked ? (size_t)n : 0);
             const uint32_t* mask_ptr[1 + TK_LOOKUP_MAX_DRAFT] = {};
-            if (masked) mask_ptr[0] = runner->mask.data();
-            for (int i = 1; i < n && masked; ++i) {
-                gstates[(size_t)i].mask(runner->trie, runner->model->tok.eos, &mask_bits[(size_t)i]);
-                mask_ptr[i] = mask_bits[(size_t)i].data();
-            }
-            if (masked) runner->lookup_masks_ms += ms_since(t_masks);
             std::vector<int32_t> windows(adjusted ? (size_t)n * (size_t)std::max(runner->pen_last_n, 1) : 0);
             TkLogitAdjust adj[1 + TK_LOOKUP_MAX_DRAFT];
             for (int i = 0; i < n && adjusted; ++i) {
@@ -1372,15 +1600,29 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
                 adj[i].n_bias = (int32_t)runner->bias_ids.size(); adj[i].bias_ids = runner->bias_ids.data(); adj[i].bias = runner->bias.data();
             }
             TkTokenLogprob recs[1 + TK_LOOKUP_MAX_DRAFT];
-            const auto t_request = std::chrono::steady_clock::now();
-            if (!runner->batcher->submit_verify(runner->slot, runner->n_past, fed, n, ids, &n_ids, &err, masked ? mask_ptr : nullptr, runner->next_samp(), adjusted ? adj : nullptr,
-                                                runner->lp_ntop, records ? recs : nullptr, masked || adjusted || records ? n : 0) ||
-                n_ids < 1) {
+            bool ok = false;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                /* row 0's state is the runner's own (it has accepted the pending id), row i's the copy behind draft i - 1.  A second attempt
+                 * follows a request in which a mask row held an undecided token: the WHOLE request again, at the same positions and with the same
+                 * sampling counter, under host masks — nothing of the runner has advanced */
+                const auto t_attempt = attempt ? std::chrono::steady_clock::now() : t_masks;
+                for (int i = 0; i < n && masked; ++i)
+                    mask_ptr[i] = runner->row_mask(i == 0 ? runner->gstate : gstates[(size_t)i], i == 0 ? &runner->mask : &mask_bits[(size_t)i], attempt > 0);
+                if (masked) runner->lookup_masks_ms += ms_since(t_attempt);
+                const auto t_request = std::chrono::steady_clock::now();
+                ok = runner->batcher->submit_verify(runner->slot, runner->n_past, fed, n, ids, &n_ids, &err, masked ? mask_ptr : nullptr, runner->next_samp(),
+                                                    adjusted ? adj : nullptr, runner->lp_ntop, records ? recs : nullptr, masked || adjusted || records ? n : 0) &&
+                     n_ids >= 1;
+                runner->lookup_requests_ms += ms_since(t_request);
+                if (!runner->finish_masks(ok)) break;
+                runner->mask_redone++;
+                ok = false;
+            }
+            if (!ok) {
                 tk_error_set_detail("%s", err.c_str());
                 runner->is_processing = false;
                 return NULL;
             }
-            runner->lookup_requests_ms += ms_since(t_request);
             /* the chain has drawn the ids that were kept: the counter is the one n_ids one-row passes would have left */
             if (drawn) runner->samp.counter += (uint32_t)n_ids;
             runner->queued_drawn = drawn;
@@ -1401,8 +1643,14 @@ const char* tk_llm_runner_generate_next_token(tk_llm_runner_t* runner) {
             return runner->piece.c_str();
         }
     }
-    if (!runner->batcher->submit(runner->slot, runner->n_past, &t, 1, runner->next_mask(), &am, &err, runner->next_samp(), nullptr, runner->next_adjust(), lookup,
-                                 runner->lp_ntop, runner->lp_ntop >= 0 ? &runner->last_lp : nullptr)) {
+    bool ok = runner->batcher->submit(runner->slot, runner->n_past, &t, 1, runner->next_mask(), &am, &err, runner->next_samp(), nullptr, runner->next_adjust(), lookup,
+                                      runner->lp_ntop, runner->lp_ntop >= 0 ? &runner->last_lp : nullptr);
+    if (runner->finish_masks(ok)) { /* an undecided token: the row again under a host mask; nothing of the runner has advanced */
+        runner->mask_redone++;
+        ok = runner->batcher->submit(runner->slot, runner->n_past, &t, 1, runner->next_mask(true), &am, &err, runner->next_samp(), nullptr, runner->next_adjust(), lookup,
+                                     runner->lp_ntop, runner->lp_ntop >= 0 ? &runner->last_lp : nullptr);
+    }
+    if (!ok) {
         tk_error_set_detail("%s", err.c_str());
         runner->is_processing = false;
         return NULL;

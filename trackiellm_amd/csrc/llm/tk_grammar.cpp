@@ -271,6 +271,28 @@ bool TkGrammar::parse(const std::string& text, std::string* err) {
     auto it = names_.find("root");
     if (it == names_.end()) { if (err) *err = "grammar has no root rule"; return false; }
     root_ = (int)it->second;
+    /* the flat image: rule offsets, elements, sets */
+    flat_.clear();
+    uint32_t off = 0;
+    for (const auto& r : rules_) { flat_.push_back(off); off += (uint32_t)r.size(); }
+    flat_.push_back(off);
+    n_elems_ = off;
+    for (const auto& r : rules_)
+        for (const Elem& e : r) flat_.push_back((uint32_t)e.type | (e.value << 2));
+    for (const ByteSet& s : sets_) flat_.insert(flat_.end(), s.begin(), s.end());
+    return true;
+}
+
+void TkGrammar::image_over(const uint32_t* words, int32_t n_rules, int32_t n_elems, int32_t n_sets, int32_t root, TkGrammarImage* img) {
+    img->rule_off = words;
+    img->elems = words + n_rules + 1;
+    img->sets = img->elems + n_elems;
+    img->n_rules = n_rules; img->n_elems = n_elems; img->n_sets = n_sets; img->root = root;
+}
+
+bool TkGrammar::flatten(TkGrammarImage* img) const {
+    if (root_ < 0 || flat_.empty() || n_elems_ > TK_GW_MAX_ELEMS) return false;
+    image_over(flat_.data(), (int32_t)rules_.size(), (int32_t)n_elems_, (int32_t)sets_.size(), root_, img);
     return true;
 }
 
@@ -380,6 +402,36 @@ bool TkGrammarState::complete() const {
     for (const Stack& s : stacks_)
         if (s.empty()) return true;
     return false;
+}
+
+bool TkGrammarState::export_image(TkGrammarStateImage* img) const {
+    TkGrammarImage gi;
+    if (!g_ || !g_->flatten(&gi) || stacks_.size() > TK_GW_MAX_STACKS) return false;
+    const Stack* first = nullptr;
+    size_t cp = 0;
+    for (const Stack& st : stacks_) {
+        if (st.empty()) continue;
+        if (!first) { first = &st; cp = st.size(); continue; }
+        size_t k = 0;
+        while (k < cp && k < st.size() && st[k] == (*first)[k]) ++k;
+        cp = k;
+    }
+    if (cp > TK_GW_MAX_BOTTOM) cp = TK_GW_MAX_BOTTOM;
+    memset(img, 0, sizeof *img);
+    img->complete = complete() ? 1 : 0;
+    img->n_bottom = (int32_t)cp;
+    img->n_stacks = (int32_t)stacks_.size();
+    for (size_t k = 0; k < cp; ++k) img->bottom[k] = (uint16_t)(gi.rule_off[(*first)[k].first] + (*first)[k].second);
+    for (size_t i = 0; i < stacks_.size(); ++i) {
+        const Stack& st = stacks_[i];
+        TkGwStack& o = img->stacks[i];
+        if (st.empty()) continue; /* base 0, n 0 */
+        if (st.size() - cp > TK_GW_MAX_PRIV) return false;
+        o.base = (uint8_t)cp;
+        o.n = (uint8_t)(st.size() - cp);
+        for (size_t k = cp; k < st.size(); ++k) o.priv[k - cp] = (uint16_t)(gi.rule_off[st[k].first] + st[k].second);
+    }
+    return true;
 }
 
 void TkGrammarState::walk(const TkTokenTrie& trie, int node, const std::vector<Stack>& stacks, std::vector<uint32_t>* bits) const {

@@ -26,6 +26,8 @@
 #include <string>
 #include <vector>
 
+#include "../common/tk_grammar_walk.h"
+
 class TkGrammar {
 public:
     enum { END = 0, ALT = 1, RULE = 2, SET = 3 };
@@ -37,8 +39,16 @@ public:
     const std::vector<Elem>& rule(uint32_t id) const { return rules_[id]; }
     bool in_set(uint32_t set, uint8_t b) const { return (sets_[set][b >> 5] >> (b & 31)) & 1u; }
     size_t n_rules() const { return rules_.size(); }
+    /* the grammar as plain arrays (common/tk_grammar_walk.h), built by parse(): [n_rules + 1 rule offsets][n_elems elements][n_sets * 8 set words] in
+     * flat_words(); flatten() points an image at them.  false: the grammar has more than TK_GW_MAX_ELEMS elements and no image */
+    bool flatten(TkGrammarImage* img) const;
+    const std::vector<uint32_t>& flat_words() const { return flat_; }
+    /* the same image over another copy of flat_words() (a device buffer) */
+    static void image_over(const uint32_t* words, int32_t n_rules, int32_t n_elems, int32_t n_sets, int32_t root, TkGrammarImage* img);
 
 private:
+    std::vector<uint32_t> flat_;
+    uint32_t n_elems_ = 0;
     std::vector<std::vector<Elem>> rules_;
     std::vector<ByteSet> sets_;
     std::map<std::string, uint32_t> names_;
@@ -74,6 +84,11 @@ public:
     bool dead() const { return stacks_.empty(); }
     /* bit i of bits[] = token i may be sampled next; eos_id (>= 0) is allowed iff complete() */
     void mask(const TkTokenTrie& trie, int eos_id, std::vector<uint32_t>* bits) const;
+    /* the state as the per-token walk reads it (common/tk_grammar_walk.h): the common bottom of the stacks, each stack's top beyond it, the completion
+     * flag; mask_row and grammar are left to the caller.  false: the grammar has no image or the state does not fit the caps (more than
+     * TK_GW_MAX_STACKS stacks, a bottom above TK_GW_MAX_BOTTOM, a top above TK_GW_MAX_PRIV) — such a state takes mask() */
+    bool export_image(TkGrammarStateImage* img) const;
+    const TkGrammar* grammar() const { return g_; }
 
 private:
     const TkGrammar* g_ = nullptr;

@@ -99,6 +99,9 @@ public:
     void release_slot(int slot);
     int n_ctx() const { return n_ctx_; }
     int slots() const { return (int)slot_used_.size(); }
+    /* the shared session, for its thread-safe grammar-mask registry alone (TkLlmSession::attach_grammar_state): a runner attaches a state to the mask
+     * pointer it submits; the scheduler itself knows nothing of it */
+    TkLlmSession* session() { return &session_; }
     /* Blocking: feed `n` tokens of sequence `slot` at positions pos0, pos0 + 1, ...; *sampled = arg max after the last one (over the
      * tokens `mask` allows, when given: (vocab + 31) / 32 words, bit t = token t).  Thread-safe; one outstanding call per slot. */
     /* samp (optional): sampling state of the sampled row — temp > 0 draws from the reference's default stochastic chain with the given

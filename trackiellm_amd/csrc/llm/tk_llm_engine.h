@@ -16,6 +16,8 @@
 #include <stdint.h>
 
 #include <functional>
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -167,8 +169,36 @@ public:
      * form it replaces — a hipMemcpy2DAsync per (destination, layer, K | V) on the same stream — alternating, `iters` times after one untimed round
      * of each, device events around each form; bytes = read + written by one round of either */
     bool time_kv_copy(int n_pos, int n_dst, int iters, float* kernel_ms, float* memcpy_ms, double* bytes);
+    /* Grammar masks built on the device (common/tk_grammar_walk.h, k_grammar_mask).  All four are thread-safe and called by the runners
+     * (abi/tk_abi_llm.cpp), never by the scheduler: the scheduler hands forward() the host mask pointers it always did, and forward() looks each one up.
+     *   install_vocab_image   once per session, at first use: offsets [vocab + 1] and the bytes of the pieces (an empty piece is never allowed)
+     *   grammar_slot          the image of a grammar in the session's arena, keyed by its words: the slot of an equal image when there is one, else a
+     *                         new one (a slot stays taken while the session lives); -1 = the arena's TK_GRAMMAR_ARENA_SLOTS are taken (such a
+     *                         runner keeps building its masks on the host)
+     *   attach_grammar_state  the masked row whose host mask pointer is `mask_ptr` gets its mask from `image` (image.grammar = a slot): forward()
+     *                         uploads the state images of such rows, runs ONE k_grammar_mask launch for all of them into the compacted rows of d_mask, in
+     *                         front of the pass where the host masks are copied, and copies nothing from mask_ptr.  After the pass it reads the
+     *                         undecided counts back with the ids
+     *   detach_grammar_state  forgets the pointer; *ran = a pass built the mask, *undecided = tokens of it that the walk could not decide (written as
+     *                         forbidden: the row may have picked from too small a set) */
+    enum { TK_GRAMMAR_ARENA_SLOTS = 8 };
+    bool install_vocab_image(const uint32_t* offsets, const uint8_t* pieces, int32_t eos);
+    int grammar_slot(const uint32_t* words, size_t n_words, int32_t n_rules, int32_t n_elems, int32_t n_sets, int32_t root);
+    bool attach_grammar_state(const uint32_t* mask_ptr, const TkGrammarStateImage& image);
+    void detach_grammar_state(const uint32_t* mask_ptr, bool* ran, int32_t* undecided);
 
 private:
+    struct GrammarRow { TkGrammarStateImage image; bool ran = false; int32_t undecided = 0; };
+    std::mutex gm_mu;                                   /* guards the registry, the arena's keys and the installation */
+    std::map<const uint32_t*, GrammarRow> gm_rows;      /* attached states by host mask pointer */
+    std::vector<uint32_t> gm_keys[TK_GRAMMAR_ARENA_SLOTS];
+    uint32_t* gm_words[TK_GRAMMAR_ARENA_SLOTS] = {};    /* device copies of the grammars' words */
+    TkGrammarImage* d_gm_arena = nullptr;               /* [TK_GRAMMAR_ARENA_SLOTS] images with device pointers */
+    uint32_t* d_gm_offsets = nullptr;                   /* the vocabulary image */
+    uint8_t* d_gm_pieces = nullptr;
+    int32_t gm_eos = -1;
+    TkGrammarStateImage *d_gm_states = nullptr, *h_gm_states = nullptr; /* [TK_MAX_ROWS] state images of a pass: device array, pinned staging */
+    int32_t *d_mask_undecided = nullptr, *h_mask_undecided = nullptr;   /* [TK_MAX_ROWS] per launch row */
     friend class TkLlmPipe; /* tk_llm_pipe.h: a pipeline stage enqueues layer ranges of this session between its hand-off kernels */
     int last_ks_res = 1;    /* slabs of the residual update the last enqueue_range left pending in `partial` */
     /* A pass is described once, as a TkPassForm (tk_pass_form.h; DESIGN.md "The forms of a pass"), by the entry that runs it; these launch what

@@ -462,8 +462,76 @@ TkLlmSession::~TkLlmSession() {
     if (d_lp_ntop) (void)hipFree(d_lp_ntop);
     if (d_lp_rec) (void)hipFree(d_lp_rec);
     if (h_lp_rec) (void)hipHostFree(h_lp_rec);
+    void* gm[] = {d_gm_arena, d_gm_offsets, d_gm_pieces, d_gm_states, d_mask_undecided};
+    for (void* p : gm) if (p) (void)hipFree(p);
+    for (uint32_t* p : gm_words) if (p) (void)hipFree(p);
+    if (h_gm_states) (void)hipHostFree(h_gm_states);
+    if (h_mask_undecided) (void)hipHostFree(h_mask_undecided);
     free_act(&act_d); free_act(&act_qd); free_act(&act_ff);
     if (stream) (void)hipStreamDestroy(stream);
+}
+
+/* ---- grammar masks on the device: the runners' side (the header comment has the contract) ---- */
+
+bool TkLlmSession::install_vocab_image(const uint32_t* offsets, const uint8_t* pieces, int32_t eos) {
+    std::lock_guard<std::mutex> lk(gm_mu);
+    if (d_gm_offsets) return true;
+    const size_t vocab = (size_t)model->hp.vocab, nbytes = offsets[vocab];
+    if (hipSetDevice(model->device) != hipSuccess) return false;
+    bool ok = hipMalloc((void**)&d_gm_pieces, nbytes ? nbytes : 1) == hipSuccess && hipMalloc((void**)&d_gm_arena, TK_GRAMMAR_ARENA_SLOTS * sizeof(TkGrammarImage)) == hipSuccess &&
+              hipMalloc((void**)&d_gm_states, TK_MAX_ROWS * sizeof(TkGrammarStateImage)) == hipSuccess &&
+              hipHostMalloc((void**)&h_gm_states, TK_MAX_ROWS * sizeof(TkGrammarStateImage), hipHostMallocDefault) == hipSuccess &&
+              hipMalloc((void**)&d_mask_undecided, TK_MAX_ROWS * 4) == hipSuccess && hipHostMalloc((void**)&h_mask_undecided, TK_MAX_ROWS * 4, hipHostMallocDefault) == hipSuccess &&
+              hipMemcpy(d_gm_pieces, pieces, nbytes, hipMemcpyHostToDevice) == hipSuccess;
+    uint32_t* off = nullptr;
+    ok = ok && hipMalloc((void**)&off, (vocab + 1) * 4) == hipSuccess && hipMemcpy(off, offsets, (vocab + 1) * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) { if (off) (void)hipFree(off); (void)hipGetLastError(); return false; } /* what was allocated is freed with the session */
+    gm_eos = eos;
+    d_gm_offsets = off; /* last: forward() takes it as "installed" */
+    return true;
+}
+
+int TkLlmSession::grammar_slot(const uint32_t* words, size_t n_words, int32_t n_rules, int32_t n_elems, int32_t n_sets, int32_t root) {
+    std::lock_guard<std::mutex> lk(gm_mu);
+    if (!d_gm_offsets || n_words == 0 || n_words != (size_t)n_rules + 1 + (size_t)n_elems + (size_t)n_sets * 8) return -1;
+    int free_slot = -1;
+    for (int i = 0; i < TK_GRAMMAR_ARENA_SLOTS; ++i) {
+        if (gm_keys[i].empty()) { if (free_slot < 0) free_slot = i; continue; }
+        if (gm_keys[i].size() == n_words && memcmp(gm_keys[i].data(), words, n_words * 4) == 0) return i;
+    }
+    if (free_slot < 0 || hipSetDevice(model->device) != hipSuccess) return -1;
+    uint32_t* d = nullptr;
+    TkGrammarImage img;
+    if (hipMalloc((void**)&d, n_words * 4) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    img.rule_off = d; img.elems = d + n_rules + 1; img.sets = img.elems + n_elems;
+    img.n_rules = n_rules; img.n_elems = n_elems; img.n_sets = n_sets; img.root = root;
+    /* no pass reads this entry yet: a state that names it is attached after this returns */
+    if (hipMemcpy(d, words, n_words * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_gm_arena + free_slot, &img, sizeof img, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        (void)hipGetLastError();
+        return -1;
+    }
+    gm_words[free_slot] = d;
+    gm_keys[free_slot].assign(words, words + n_words);
+    return free_slot;
+}
+
+bool TkLlmSession::attach_grammar_state(const uint32_t* mask_ptr, const TkGrammarStateImage& image) {
+    std::lock_guard<std::mutex> lk(gm_mu);
+    if (!mask_ptr || !d_gm_offsets || image.grammar < 0 || image.grammar >= TK_GRAMMAR_ARENA_SLOTS || gm_keys[image.grammar].empty()) return false;
+    GrammarRow& g = gm_rows[mask_ptr];
+    g.image = image;
+    g.ran = false;
+    g.undecided = 0;
+    return true;
+}
+
+void TkLlmSession::detach_grammar_state(const uint32_t* mask_ptr, bool* ran, int32_t* undecided) {
+    std::lock_guard<std::mutex> lk(gm_mu);
+    auto it = gm_rows.find(mask_ptr);
+    *ran = it != gm_rows.end() && it->second.ran;
+    *undecided = it != gm_rows.end() ? it->second.undecided : 0;
+    if (it != gm_rows.end()) gm_rows.erase(it);
 }
 
 bool TkLlmSession::reset() {
@@ -1243,7 +1311,8 @@ bool TkLlmSession::clear_row_tables(unsigned which) {
 bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok, float* logits_host, int32_t* argmax_host,
                            bool lm_head, const uint32_t* const* row_masks, const TkSampleRow* row_samp, const TkLogitAdjust* row_adjust,
                            const int32_t* row_ntop, TkTokenLogprob* records_host) {
-    int top = 0;
+    int top = 0, ngm = 0;
+    const uint32_t* gm_ptr[TK_MAX_ROWS]; /* the host mask pointers of the rows whose masks the device builds */
     bool distinct = true, any_adj = false, any_lp = false;
     if (!check_pass_rows(nrows, seq, pos, tok, &top, &distinct)) return false;
     for (int r = 0; r < nrows && lm_head && row_ntop; ++r) {
@@ -1264,9 +1333,26 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
         for (int r = 0; r < TK_MAX_ROWS; ++r) rowtab[r] = -1;
         for (int r = 0; r < nrows; ++r) {
             if (row_masks && row_masks[r]) {
-                HIPQ(hipMemcpyAsync(d_mask + (size_t)nmask * words, row_masks[r], words * 4, hipMemcpyHostToDevice, stream));
+                /* a row with a grammar state attached (attach_grammar_state) gets its bits from k_grammar_mask below, not from the host */
+                bool on_device = false;
+                {
+                    std::lock_guard<std::mutex> lk(gm_mu);
+                    auto it = gm_rows.find(row_masks[r]);
+                    if (it != gm_rows.end()) { /* only a session with the vocabulary image installed has entries */
+                        h_gm_states[ngm] = it->second.image;
+                        h_gm_states[ngm].mask_row = nmask;
+                        gm_ptr[ngm++] = row_masks[r];
+                        on_device = true;
+                    }
+                }
+                if (!on_device) HIPQ(hipMemcpyAsync(d_mask + (size_t)nmask * words, row_masks[r], words * 4, hipMemcpyHostToDevice, stream));
                 rowtab[r] = nmask++;
             }
+        }
+        if (ngm > 0) { /* ONE launch for every such row of the pass, on the stream in front of the pass's graph (pinned staging: free again when forward() has waited) */
+            HIPQ(hipMemcpyAsync(d_gm_states, h_gm_states, (size_t)ngm * sizeof(TkGrammarStateImage), hipMemcpyHostToDevice, stream));
+            HIPQ(hipMemsetAsync(d_mask_undecided, 0, (size_t)ngm * 4, stream));
+            tk_launch_grammar_mask(d_gm_arena, d_gm_states, ngm, d_gm_offsets, d_gm_pieces, model->hp.vocab, gm_eos, d_mask, d_mask_undecided, stream);
         }
         if (nmask > 0 || mask_rows_dirty) {
             HIPQ(hipMemcpyAsync(d_mask_row, rowtab, TK_MAX_ROWS * 4, hipMemcpyHostToDevice, stream)); /* whole table (a wider pass may have left entries); pageable source: staged before the call returns */
@@ -1331,7 +1417,15 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
     if (logits_host) HIPQ(hipMemcpyAsync(logits_host, logits, (size_t)nrows * model->hp.vocab * 4, hipMemcpyDeviceToHost, stream));
     if (argmax_host) HIPQ(hipMemcpyAsync(argmax_host, d_tok, nrows * 4, hipMemcpyDeviceToHost, stream));
     if (any_lp) HIPQ(hipMemcpyAsync(h_lp_rec, d_lp_rec, (size_t)nrows * sizeof(TkTokenLogprob), hipMemcpyDeviceToHost, stream));
+    if (ngm > 0) HIPQ(hipMemcpyAsync(h_mask_undecided, d_mask_undecided, (size_t)ngm * 4, hipMemcpyDeviceToHost, stream));
     HIPQ(hipStreamSynchronize(stream));
+    if (ngm > 0) { /* the undecided counts came back with the ids: into the registry, where the rows' owners read them */
+        std::lock_guard<std::mutex> lk(gm_mu);
+        for (int i = 0; i < ngm; ++i) {
+            auto it = gm_rows.find(gm_ptr[i]);
+            if (it != gm_rows.end()) { it->second.ran = true; it->second.undecided = h_mask_undecided[i]; }
+        }
+    }
     /* the records of the rows that asked, as far as they were filled: everything else of records_host stays as the caller left it */
     for (int r = 0; r < nrows && any_lp; ++r) {
         if (row_ntop[r] < 0) continue;

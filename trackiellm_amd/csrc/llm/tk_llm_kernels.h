@@ -110,6 +110,13 @@ void tk_launch_logit_adjust(float* logits, int vocab, int nrows, const TkAdjustR
  * tk_launch_argmax on the logits it read: logits [nrows] rows of `vocab` floats `ld` apart; tok [nrows] the picked ids; rec [nrows].  The caller has
  * checked n_top with tk_logprob_check (vocab <= 65536) and tok[r] is a token of the row */
 void tk_launch_token_logprobs(const float* logits, int vocab, int ld, int nrows, const int32_t* n_top, const int32_t* tok, TkTokenLogprob* rec, hipStream_t s);
+#include "../common/tk_grammar_walk.h"
+/* grammar token masks on the device (common/tk_grammar_walk.h): ONE launch for n_rows states.  states [n_rows], each naming its grammar image in
+ * grammars[] (device pointers inside) and its row of `mask` ([.][(vocab + 31) / 32] words, every word of such a row written whole); offsets [vocab + 1]
+ * and pieces: the vocabulary image; eos (< 0: none) is allowed iff the state is complete; undecided [n_rows], zeroed by the caller, counts the tokens
+ * of each state whose walk exceeded a cap (written 0).  The caller vouches for the images: the kernel trusts positions and offsets */
+void tk_launch_grammar_mask(const TkGrammarImage* grammars, const TkGrammarStateImage* states, int n_rows, const uint32_t* offsets, const uint8_t* pieces, int vocab,
+                            int eos, uint32_t* mask, int32_t* undecided, hipStream_t s);
 
 /* the attention launch a pass takes: kernel 0 = k_attention<gq, fused, head_dim, chunk> (chunk = positions per ring slot, slots = ring depth 2), kernel 1 =
  * k_attention_narrow (gq 2, chunk = positions resident per chunk, the whole context when it fits), kernel 5 = k_attention_far<gq, head_dim, chunk>

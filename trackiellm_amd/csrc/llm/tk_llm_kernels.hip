@@ -4576,6 +4576,54 @@ void tk_launch_token_logprobs(const float* logits, int vocab, int ld, int nrows,
 }
 
 /* ------------------------------------------------------------------------------------------
+ * grammar token masks (common/tk_grammar_walk.h): one lane per token, blockIdx.y = the state (mask row) of the launch.
+ *   Every lane walks its token's bytes from the row's state (tk_grammar_mask_token: the host's function); a wave forms the two mask words of its 64
+ *   tokens by ballot and lane 0 stores them, so every word of the row is written whole, without atomics, and the bits above `vocab` are 0.
+ *   Undecided tokens are written 0 and counted into undecided[blockIdx.y] (zeroed by the caller).
+ *   The state image (its shared bottom) is staged in LDS; the grammar image too when it has at most TK_GW_LDS_WORDS words, else it is read from
+ *   global memory.  The lanes' two stack sets (1 KiB a lane) live in scratch: 256 lanes of LDS copies would be 256 KiB a workgroup.
+ * ------------------------------------------------------------------------------------------ */
+#define TK_GMASK_LANES 256
+__global__ __launch_bounds__(TK_GMASK_LANES) void k_grammar_mask(const TkGrammarImage* __restrict__ grammars, const TkGrammarStateImage* __restrict__ states,
+                                                                 const uint32_t* __restrict__ offsets, const uint8_t* __restrict__ pieces, int vocab, int eos,
+                                                                 int words, uint32_t* __restrict__ mask, int32_t* __restrict__ undecided) {
+    __shared__ TkGrammarStateImage st;
+    __shared__ uint32_t gw[TK_GW_LDS_WORDS];
+    const int t = threadIdx.x, row = blockIdx.y;
+    {
+        const uint32_t* src = (const uint32_t*)(states + row);
+        uint32_t* dst = (uint32_t*)&st;
+        for (int i = t; i < (int)(sizeof(TkGrammarStateImage) / 4); i += TK_GMASK_LANES) dst[i] = src[i];
+    }
+    __syncthreads();
+    TkGrammarImage g = grammars[st.grammar];
+    const int total = g.n_rules + 1 + g.n_elems + g.n_sets * 8;
+    if (total <= TK_GW_LDS_WORDS) { /* uniform over the workgroup */
+        for (int i = t; i < total; i += TK_GMASK_LANES) gw[i] = g.rule_off[i];
+        __syncthreads();
+        g.rule_off = gw;
+        g.elems = gw + g.n_rules + 1;
+        g.sets = g.elems + g.n_elems;
+    }
+    const int tok = blockIdx.x * TK_GMASK_LANES + t;
+    const int r = tok < vocab ? tk_grammar_mask_token(g, st, st.bottom, offsets, pieces, tok, eos) : TK_GW_FORBIDDEN;
+    const unsigned long long allowed = __ballot(r == TK_GW_ALLOWED), und = __ballot(r == TK_GW_UNDECIDED);
+    if ((t & 63) == 0) {
+        const int w0 = tok >> 5; /* tok is a multiple of 64 here */
+        uint32_t* out = mask + (size_t)st.mask_row * words;
+        if (w0 < words) out[w0] = (uint32_t)allowed;
+        if (w0 + 1 < words) out[w0 + 1] = (uint32_t)(allowed >> 32);
+        if (und) atomicAdd(undecided + row, (int32_t)__popcll(und));
+    }
+}
+
+void tk_launch_grammar_mask(const TkGrammarImage* grammars, const TkGrammarStateImage* states, int n_rows, const uint32_t* offsets, const uint8_t* pieces, int vocab,
+                            int eos, uint32_t* mask, int32_t* undecided, hipStream_t s) {
+    hipLaunchKernelGGL(k_grammar_mask, dim3((vocab + TK_GMASK_LANES - 1) / TK_GMASK_LANES, n_rows), dim3(TK_GMASK_LANES), 0, s, grammars, states, offsets, pieces, vocab,
+                       eos, (vocab + 31) / 32, mask, undecided);
+}
+
+/* ------------------------------------------------------------------------------------------
  * per-device opt-in to > 64 KiB of dynamic LDS for every kernel above (see the comment at TK_MAX_DYN_LDS)
  * ------------------------------------------------------------------------------------------ */
 const char* tk_llm_prepare_device(int device) {

@@ -291,6 +291,56 @@ def token_logprobs_probe(logits, rows, cols, ids, n_top, records=None, ld=None, 
     return records
 
 
+def _vocab_image(pieces):
+    """pieces (bytes each) -> (offsets uint32 [n + 1], the bytes back to back as uint8)"""
+    pieces = [bytes(p) for p in pieces]
+    offsets = np.zeros(len(pieces) + 1, np.uint32)
+    offsets[1:] = np.cumsum([len(p) for p in pieces], dtype=np.int64)
+    data = np.frombuffer(b"".join(pieces) or b"\0", dtype=np.uint8).copy()
+    return offsets, data
+
+
+def grammar_mask_probe(gbnf, prefixes, pieces, eos=-1, bits=None, undecided=None, device=0, vocab=None, offsets=None):
+    """ONE launch of k_grammar_mask (tk_mi355x_grammar_mask_probe).  gbnf: GBNF text or None for the tool-call grammar; prefixes: one per mask row,
+    bytes / str, or None for a row that is off; pieces: the vocabulary's pieces as bytes (an empty piece is never allowed); eos: the token allowed iff the
+    state is complete (-1: none).  bits: uint32 [rows][(vocab + 31) // 32] filled IN PLACE (None: zeros); undecided: int32 [rows] IN PLACE (None: zeros).
+    device < 0: the same walk in a host loop, no GPU touched.  vocab / offsets override what the pieces give (the refusal tests).  Returns
+    (bits, undecided); a refusal raises TkError with nothing written"""
+    offs, data = _vocab_image(pieces)
+    if offsets is not None:
+        offs = np.ascontiguousarray(offsets, dtype=np.uint32)
+    n = len(pieces) if vocab is None else int(vocab)
+    rows = len(prefixes)
+    words = (max(n, 1) + 31) // 32
+    if bits is None:
+        bits = np.zeros((max(rows, 1), words), np.uint32)
+    if undecided is None:
+        undecided = np.zeros(max(rows, 1), np.int32)
+    if bits.dtype != np.uint32 or not bits.flags.c_contiguous or undecided.dtype != np.int32 or not undecided.flags.c_contiguous:
+        raise ValueError("grammar_mask_probe: bits must be C-contiguous uint32 and undecided C-contiguous int32")
+    if bits.size < rows * words or undecided.size < rows or offs.size < n + 1:
+        raise ValueError("grammar_mask_probe: bits, undecided or offsets are too short")
+    pre = (C.c_char_p * max(rows, 1))(*[None if p is None else (p.encode() if isinstance(p, str) else bytes(p)) for p in prefixes])
+    f = lib().tk_mi355x_grammar_mask_probe
+    f.argtypes = [C.c_int, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    g = None if gbnf is None else (gbnf.encode() if isinstance(gbnf, str) else bytes(gbnf))
+    check(f(int(device), g, rows, C.cast(pre, C.c_void_p), _p(data), _p(offs), n, int(eos), _p(bits), _p(undecided)))
+    return bits, undecided
+
+
+def time_grammar_mask(prefix, pieces, rows=1, eos=-1, iters=200, gbnf=None, device=0):
+    """(ms of the state upload plus one k_grammar_mask launch over `rows` equal states, ms of the host trie walk for one row) after `prefix`
+    (tk_mi355x_time_grammar_mask)"""
+    offs, data = _vocab_image(pieces)
+    d, h = C.c_float(0), C.c_float(0)
+    f = lib().tk_mi355x_time_grammar_mask
+    f.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    g = None if gbnf is None else (gbnf.encode() if isinstance(gbnf, str) else bytes(gbnf))
+    check(f(int(device), g, prefix.encode() if isinstance(prefix, str) else bytes(prefix), int(rows), _p(data), _p(offs), len(pieces), int(eos), int(iters), C.byref(d),
+            C.byref(h)))
+    return d.value, h.value
+
+
 def time_token_logprobs(rows, cols, n_top, iters=200, device=0):
     """average ms of one k_token_logprobs launch at rows x cols with every row asking for n_top alternatives (tk_mi355x_time_token_logprobs)"""
     ms = C.c_float(0)
@@ -877,6 +927,28 @@ class LlmRunner:
         a, b = C.c_double(0), C.c_double(0)
         check(lib().tk_mi355x_llm_runner_lookup_host_ms(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def set_device_mask(self, on):
+        """grammar masks built by k_grammar_mask inside the runner's passes instead of by the host's trie walk (off by default; same ids either way:
+        tk_mi355x_llm_runner_set_device_mask)"""
+        f = lib().tk_mi355x_llm_runner_set_device_mask
+        f.argtypes = [C.c_void_p, C.c_int]
+        check(f(self.h, 1 if on else 0))
+
+    def mask_stats(self):
+        """(mask rows built on the device, built on the host, requests submitted again after an undecided token) since the last prepare()"""
+        d, h, r = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        f = lib().tk_mi355x_llm_runner_mask_stats
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(f(self.h, C.byref(d), C.byref(h), C.byref(r)))
+        return d.value, h.value, r.value
+
+    def set_grammar(self, gbnf):
+        """the runner's grammar becomes this GBNF text (str or bytes), armed by prepare(..., use_tool_grammar=True); None restores the tool-call grammar
+        (tk_mi355x_llm_runner_set_grammar).  A text that does not parse, or a call during a generation, raises TkError"""
+        f = lib().tk_mi355x_llm_runner_set_grammar
+        f.argtypes = [C.c_void_p, C.c_char_p]
+        check(f(self.h, None if gbnf is None else (gbnf.encode() if isinstance(gbnf, str) else bytes(gbnf))))
 
     def set_lookup_scope_bits(self, flags):
         """set_lookup_scope by flag bits; unknown bits raise TkError"""
