@@ -190,6 +190,57 @@ TK_API int tk_mi355x_prefix_match(const int32_t* toks, int n, const int32_t* rec
  * The KV cache is 2 x n_layer x max_seq x max_ctx x n_kv_head x head_dim f16 in one allocation each; a failure to allocate names the bytes. */
 TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_create(tk_mi355x_llm_session_t** out, tk_mi355x_llm_model_t* m, int max_seq,
                                                                  int max_ctx);
+/* ---- Q8_0 KV cache (csrc/common/tk_kv_q8.h; opt-in; include/tk/ABI_NOTES.md): llama.cpp's --cache-type-k q8_0 --cache-type-v q8_0.  A key or value
+ * row is stored as ggml's Q8_0 blocks (32 int8 and one f16 scale) of the row the f16 cache would hold: 17/32 of the cache's bytes. ---- */
+#define TK_MI355X_KV_F16 0
+#define TK_MI355X_KV_Q8_0 1
+/* tk_mi355x_llm_session_create with the cache type; kv_type 0 is that call.  Any other value than 0 or 1: TK_ERROR_INVALID_ARGUMENT.  A Q8_0
+ * session runs every pass as k_qkv_rope_append's Q8_0 form + kernel 6 (tk_mi355x_attention_plan_kv); kv_write quantises the f16 rows it is given;
+ * kv_copy works; kv_read is refused with TK_ERROR_INVALID_ARGUMENT (kv_read_q8 returns the raw rows); kv_shift, forward_stage, the pipeline and the
+ * kv_copy / kv_shift timing entries are refused with TK_ERROR_NOT_IMPLEMENTED and a message that says "Q8_0 KV cache"; forward_verify takes form 0
+ * (-1 resolves to it; 2 and 4 are refused by their messages) */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_create_kv(tk_mi355x_llm_session_t** out, tk_mi355x_llm_model_t* m, int max_seq, int max_ctx,
+                                                                    int kv_type);
+TK_API int tk_mi355x_llm_session_kv_type(const tk_mi355x_llm_session_t* s);       /* 0 or 1; -1 for NULL */
+TK_API uint64_t tk_mi355x_llm_session_kv_bytes(const tk_mi355x_llm_session_t* s); /* bytes of the cache arrays, keys and values */
+/* the raw rows of a Q8_0 session: positions [pos0, pos0 + n_pos) of one (layer, sequence), int8 values [position][kv head][head_dim] and f16 scale
+ * bits [position][kv head][head_dim / 32].  TK_ERROR_INVALID_ARGUMENT on an F16 session.  Synchronous. */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_session_kv_read_q8(tk_mi355x_llm_session_t* s, int layer, int seq, int pos0, int n_pos, int8_t* kq,
+                                                                     uint16_t* kd, int8_t* vq, uint16_t* vd);
+/* the cache type of the sessions the runners of a model handle share (what tk_model_loader_load_model returns); set before the first
+ * tk_llm_runner_create on the handle, like tk_mi355x_llm_model_set_runner_slots: afterwards TK_ERROR_INVALID_ARGUMENT with a message.  Default F16.
+ * Runners of a Q8_0 model work as before — sampling, grammars, penalties, log-probabilities, prefix cache, lookup decoding —, except that
+ * tk_mi355x_llm_runner_set_context_shift(on = 1) returns TK_ERROR_NOT_IMPLEMENTED.  _by_name takes llama.cpp's names "f16" and "q8_0"; any other
+ * name is refused by name */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_set_kv_cache_type(void* model_handle, int kv_type);
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_llm_model_set_kv_cache_type_by_name(void* model_handle, const char* name);
+/* tk_mi355x_attention_plan with the cache type: kv_type 1 = {6, query heads per workgroup, positions per ring slot, 2} — kernel 6 = k_attention_far over
+ * a Q8_0 cache, at every window and pass; kv_type 0 = tk_mi355x_attention_plan's answer */
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_attention_plan_kv(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, int fused, int kv_type,
+                                                                int32_t out[4]);
+/* The Q8_0 cache's quantiser and attention on host arrays (tests), tk_mi355x_kv_shift_probe's contract.  The cache arrays are in the cache layout for
+ * the geometry given: kq / vq [n_layer][max_seq][n_kv_head][max_ctx][head_dim] int8, kd / vd [...][max_ctx][head_dim / 32] f16 bits; seq / pos [nrows]
+ * name each row's sequence and position; `layer` the layer.
+ *   mode 0 (quantise): k16 / v16 [nrows][n_kv_head][head_dim] f16 bits become the cache rows (seq[r], pos[r]); the cache arrays are IN/OUT, every
+ *     other row keeps its bits.  device >= 0: ONE launch of the production append kernel (zero query columns, an identity RoPE table).
+ *   mode 1 (attention): q [nrows][n_head][head_dim] fp32 over positions 0 .. pos[r] of sequence seq[r]; out [nrows][n_head][head_dim] = the quotients
+ *     the kernel hands to its Q8 activation quantiser.  device >= 0: ONE launch of kernel 6; needs a head geometry a model may have.
+ * device < 0: the host loops of csrc/common/tk_kv_q8.h, no GPU touched.  Everything is validated before a device is touched: a NULL array, head_dim not a
+ * multiple of 32 (or above 256), n_head no multiple of n_kv_head or a group above 4, a row outside the cache, nrows outside [1, tk_mi355x_llm_max_rows()],
+ * an array shorter than the geometry needs (n_values = elements of kq and of vq, n_scales of kd and of vd, n_rows_elems of k16 / v16 or of q / out)
+ * or more than 2^31 cache elements are TK_ERROR_INVALID_ARGUMENT with nothing written */
+typedef struct tk_mi355x_kv_q8_probe_s {
+    int32_t mode, n_layer, max_seq, n_kv_head, max_ctx, head_dim, layer, nrows, n_head;
+    const int32_t *seq, *pos;
+    int8_t *kq, *vq;
+    uint16_t *kd, *vd;
+    int64_t n_values, n_scales;
+    const uint16_t *k16, *v16; /* mode 0 */
+    const float* q;            /* mode 1 */
+    float* out;                /* mode 1 */
+    int64_t n_rows_elems;
+} tk_mi355x_kv_q8_probe_t;
+TK_API TK_NODISCARD tk_error_code_t tk_mi355x_kv_q8_probe(int device, const tk_mi355x_kv_q8_probe_t* p);
 TK_API void tk_mi355x_llm_session_destroy(tk_mi355x_llm_session_t** s);
 /* rows one pass can hold (16-row MFMA M-tiles x 8): the row capacity of forward(), the column count of decode()'s out_tokens */
 TK_API int tk_mi355x_llm_max_rows(void);

@@ -9,7 +9,7 @@ calling a compute entry without a gfx950 device returns a TK_ERROR_GPU_* code, a
 """
 from ._lib import lib, TkError, check, LIB_PATH  # noqa: F401
 from .llm import llm_step_probe, LlmStepProbe, STEP_EMBED, STEP_RMSNORM, STEP_RESIDUAL_FOLD, STEP_SWIGLU, STEP_QUANT, STEP_ROPE_APPEND, STEP_PV_JOIN, STEP_ATT_TILES, STEP_FUSED_NORM, STEP_FUSED_SWIGLU, STEP_WIDE_SWIGLU, ROUND_NONE, ROUND_F16, ROUND_BF16  # noqa: F401
-from .llm import LlmHParams, LlmModel, LlmSession, LlmPipe, PipeHandle, ModelLoader, LlmRunner, MISTRAL_7B, TINY, attention_plan, lora_probe, gemv_probe, repack_probe, prefix_match, quantize_blocks, convert_bf16, matmul_float_probe, kv_shift_probe, kv_shift_probe_into, lookup_draft, lookup_accept, attention_plan_verify, attention_resident_limit  # noqa: F401
+from .llm import LlmHParams, LlmModel, LlmSession, LlmPipe, PipeHandle, ModelLoader, LlmRunner, MISTRAL_7B, TINY, attention_plan, lora_probe, gemv_probe, repack_probe, prefix_match, quantize_blocks, convert_bf16, matmul_float_probe, kv_shift_probe, kv_shift_probe_into, lookup_draft, lookup_accept, attention_plan_verify, attention_resident_limit, KV_F16, KV_Q8_0, kv_q8_probe_into, kv_q8_quantize_probe, kv_q8_attention_probe  # noqa: F401
 from .llm import TokenLogprob, TOKEN_LOGPROB_DTYPE, LOGPROB_MAX_TOP, token_logprobs_probe, time_token_logprobs  # noqa: F401
 from .llm import grammar_mask_probe, time_grammar_mask  # noqa: F401
 from .llm import TYPE_F32, TYPE_F16, TYPE_Q4_0, TYPE_Q5_0, TYPE_Q8_0, TYPE_Q2_K, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K, TYPE_IQ4_NL, TYPE_IQ4_XS, TYPE_Q4_1, TYPE_Q5_1, TYPE_BF16, TYPE_TQ1_0, TYPE_TQ2_0, FTYPE_TQ1_0, FTYPE_TQ2_0, FTYPE_Q4_1, FTYPE_Q5_1, FTYPE_IQ4_NL, FTYPE_IQ4_XS, FTYPE_Q4_0, FTYPE_Q5_0, FTYPE_Q8_0, FTYPE_Q2_K, FTYPE_Q2_K_S, FTYPE_Q3_K_S, FTYPE_Q3_K_M, FTYPE_Q4_K_S, FTYPE_Q4_K_M, FTYPE_Q5_K_S, FTYPE_Q5_K_M  # noqa: F401

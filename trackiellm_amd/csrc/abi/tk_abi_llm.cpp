@@ -50,6 +50,7 @@ struct tk_mi355x_llm_model_s {
     std::mutex batch_mu;
     std::vector<std::unique_ptr<TkLlmBatcher>> batchers;
     int runner_slots = 0; /* sequences per shared session; 0 = $TK_MI355X_RUNNER_SLOTS or 16 */
+    int kv_cache_type = TK_KV_F16; /* tk_mi355x_llm_model_set_kv_cache_type: the cache type of the runners' shared sessions */
     bool prefix_cache = false; /* tk_mi355x_llm_model_set_prefix_cache: handed to every scheduler of the model, present and future */
 };
 
@@ -373,6 +374,99 @@ tk_error_code_t tk_mi355x_llm_session_create(tk_mi355x_llm_session_t** out, tk_m
     return TK_SUCCESS;
 }
 
+tk_error_code_t tk_mi355x_llm_session_create_kv(tk_mi355x_llm_session_t** out, tk_mi355x_llm_model_t* m, int max_seq, int max_ctx, int kv_type) {
+    if (!out || !m) return TK_ERROR_INVALID_ARGUMENT;
+    if (kv_type != TK_KV_F16 && kv_type != TK_KV_Q8_0) return fail(TK_ERROR_INVALID_ARGUMENT, "kv_type must be 0 (F16) or 1 (Q8_0)");
+    std::unique_ptr<tk_mi355x_llm_session_s> s(new tk_mi355x_llm_session_s());
+    if (!s->session.init(&m->model, max_seq, max_ctx, kv_type)) return fail(TK_ERROR_GPU_MEMORY, s->session.error);
+    *out = s.release();
+    return TK_SUCCESS;
+}
+
+int tk_mi355x_llm_session_kv_type(const tk_mi355x_llm_session_t* s) { return s ? s->session.kv_type : -1; }
+uint64_t tk_mi355x_llm_session_kv_bytes(const tk_mi355x_llm_session_t* s) { return s ? (uint64_t)s->session.kv_bytes() : 0; }
+
+tk_error_code_t tk_mi355x_llm_session_kv_read_q8(tk_mi355x_llm_session_t* s, int layer, int seq, int pos0, int n_pos, int8_t* kq, uint16_t* kd, int8_t* vq, uint16_t* vd) {
+    if (!s || !kq || !kd || !vq || !vd) return TK_ERROR_INVALID_ARGUMENT;
+    if (!s->session.kv_read_q8(layer, seq, pos0, n_pos, kq, kd, vq, vd)) return fail(TK_ERROR_INVALID_ARGUMENT, s->session.error);
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_model_set_kv_cache_type(void* model_handle, int kv_type) {
+    if (!model_handle) return TK_ERROR_INVALID_ARGUMENT;
+    if (kv_type != TK_KV_F16 && kv_type != TK_KV_Q8_0) return fail(TK_ERROR_INVALID_ARGUMENT, "kv_type must be 0 (F16) or 1 (Q8_0)");
+    tk_mi355x_llm_model_t* m = (tk_mi355x_llm_model_t*)model_handle;
+    std::lock_guard<std::mutex> lk(m->batch_mu);
+    if (!m->batchers.empty()) return fail(TK_ERROR_INVALID_ARGUMENT, "the KV cache type is set before the first tk_llm_runner_create on the model: its sessions exist already");
+    m->kv_cache_type = kv_type;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_llm_model_set_kv_cache_type_by_name(void* model_handle, const char* name) {
+    if (!model_handle || !name) return TK_ERROR_INVALID_ARGUMENT;
+    if (strcmp(name, "f16") == 0) return tk_mi355x_llm_model_set_kv_cache_type(model_handle, TK_KV_F16);
+    if (strcmp(name, "q8_0") == 0) return tk_mi355x_llm_model_set_kv_cache_type(model_handle, TK_KV_Q8_0);
+    return fail(TK_ERROR_INVALID_ARGUMENT, std::string("KV cache type \"") + name + "\" is not built: f16 or q8_0");
+}
+
+tk_error_code_t tk_mi355x_attention_plan_kv(int device, int nrows, int n_head, int n_kv_head, int head_dim, int max_ctx, int fused, int kv_type, int32_t out[4]) {
+    if (kv_type == TK_KV_F16) return tk_mi355x_attention_plan(device, nrows, n_head, n_kv_head, head_dim, max_ctx, fused, out);
+    if (kv_type != TK_KV_Q8_0 || !out || nrows < 1 || nrows > TK_MAX_ROWS || n_head < 1 || n_kv_head < 1 || n_head % n_kv_head || head_dim < 1 || max_ctx < 1)
+        return TK_ERROR_INVALID_ARGUMENT;
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(TK_ERROR_GPU_DEVICE_NOT_FOUND, "no such HIP device");
+    const TkAttentionPlan pl = tk_attention_plan_q8(nrows, n_head, n_kv_head, head_dim);
+    out[0] = pl.kernel; out[1] = pl.gq; out[2] = pl.chunk; out[3] = pl.slots;
+    return TK_SUCCESS;
+}
+
+tk_error_code_t tk_mi355x_kv_q8_probe(int device, const tk_mi355x_kv_q8_probe_t* p) {
+    const int32_t cap = 1 << 16;
+    if (!p || (p->mode != 0 && p->mode != 1) || !p->seq || !p->pos || !p->kq || !p->vq || !p->kd || !p->vd) return TK_ERROR_INVALID_ARGUMENT;
+    if (p->n_layer < 1 || p->n_layer > cap || p->max_seq < 1 || p->max_seq > cap || p->n_kv_head < 1 || p->n_kv_head > cap || p->max_ctx < 1 || p->max_ctx > cap ||
+        p->head_dim < 32 || p->head_dim > 256 || p->head_dim % 32 != 0 || p->layer < 0 || p->layer >= p->n_layer || p->nrows < 1 || p->nrows > TK_MAX_ROWS)
+        return TK_ERROR_INVALID_ARGUMENT;
+    const int64_t elems = (int64_t)p->n_layer * p->max_seq * p->n_kv_head * p->max_ctx * p->head_dim;
+    if (elems > ((int64_t)1 << 31) || p->n_values < elems || p->n_scales < elems / TK_KV_Q8_BLOCK) return TK_ERROR_INVALID_ARGUMENT;
+    for (int r = 0; r < p->nrows; ++r)
+        if (p->seq[r] < 0 || p->seq[r] >= p->max_seq || p->pos[r] < 0 || p->pos[r] >= p->max_ctx) return TK_ERROR_INVALID_ARGUMENT;
+    const int hd = p->head_dim, nb = hd / TK_KV_Q8_BLOCK;
+    if (p->mode == 0) {
+        if (!p->k16 || !p->v16 || p->n_rows_elems < (int64_t)p->nrows * p->n_kv_head * hd) return TK_ERROR_INVALID_ARGUMENT;
+        for (int a = 0; a < p->nrows; ++a) /* two rows on one cache row: the launch would write it in no particular order */
+            for (int b = a + 1; b < p->nrows; ++b)
+                if (p->seq[a] == p->seq[b] && p->pos[a] == p->pos[b]) return TK_ERROR_INVALID_ARGUMENT;
+    } else {
+        if (!p->q || !p->out || p->n_head < 1 || p->n_head % p->n_kv_head) return TK_ERROR_INVALID_ARGUMENT;
+        const int grp = p->n_head / p->n_kv_head;
+        if ((grp != 1 && grp != 2 && grp != 4) || p->n_rows_elems < (int64_t)p->nrows * p->n_head * hd) return TK_ERROR_INVALID_ARGUMENT;
+        /* the production launch takes a model's geometries only (TkLlmModel::init): whole 256-blocks of its Q8 activation image */
+        if (device >= 0 && (hd % 64 != 0 || (grp * hd) % 256 != 0)) return TK_ERROR_INVALID_ARGUMENT;
+    }
+    if (device >= 0) {
+        std::string err;
+        if (!tk_llm_kv_q8_probe(device, p, err)) return fail(TK_ERROR_GPU_ROCM_ERROR, err);
+        return TK_SUCCESS;
+    }
+    auto row_of = [&](int r, int kvh) { return (((size_t)p->layer * p->max_seq + p->seq[r]) * p->n_kv_head + kvh) * p->max_ctx; };
+    if (p->mode == 0) {
+        for (int r = 0; r < p->nrows; ++r)
+            for (int kvh = 0; kvh < p->n_kv_head; ++kvh) {
+                const size_t row = row_of(r, kvh) + p->pos[r], src = ((size_t)r * p->n_kv_head + kvh) * hd;
+                tk_kv_q8_row(p->k16 + src, hd, p->kq + row * hd, p->kd + row * nb);
+                tk_kv_q8_row(p->v16 + src, hd, p->vq + row * hd, p->vd + row * nb);
+            }
+        return TK_SUCCESS;
+    }
+    const int grp = p->n_head / p->n_kv_head;
+    std::vector<float> scratch((size_t)p->max_ctx * grp);
+    for (int r = 0; r < p->nrows; ++r)
+        for (int kvh = 0; kvh < p->n_kv_head; ++kvh) {
+            const size_t run = row_of(r, kvh), qo = ((size_t)r * p->n_head + (size_t)kvh * grp) * hd;
+            tk_kv_q8_attention_row(p->q + qo, grp, hd, p->pos[r] + 1, p->kq + run * hd, p->kd + run * nb, p->vq + run * hd, p->vd + run * nb, scratch.data(), p->out + qo);
+        }
+    return TK_SUCCESS;
+}
+
 void tk_mi355x_llm_session_destroy(tk_mi355x_llm_session_t** s) {
     if (!s || !*s) return;
     delete *s;
@@ -481,6 +575,7 @@ tk_error_code_t tk_mi355x_llm_session_kv_copy(tk_mi355x_llm_session_t* s, int sr
 tk_error_code_t tk_mi355x_llm_session_kv_shift(tk_mi355x_llm_session_t* s, int seq, int p0, int p1, int delta) {
     if (!s) return TK_ERROR_INVALID_ARGUMENT;
     if (!s->session.kv_copy_applies()) return fail(TK_ERROR_NOT_IMPLEMENTED, "kv_shift needs head_dim to be a multiple of 8");
+    if (s->session.kv_type == TK_KV_Q8_0) return fail(TK_ERROR_NOT_IMPLEMENTED, "kv_shift: re-rotating quantised keys is not built for a Q8_0 KV cache");
     bool bad_args = false;
     if (!s->session.kv_shift(seq, p0, p1, delta, &bad_args)) return fail(bad_args ? TK_ERROR_INVALID_ARGUMENT : TK_ERROR_GPU_ROCM_ERROR, s->session.error);
     return TK_SUCCESS;
@@ -488,6 +583,7 @@ tk_error_code_t tk_mi355x_llm_session_kv_shift(tk_mi355x_llm_session_t* s, int s
 
 tk_error_code_t tk_mi355x_llm_time_kv_shift(tk_mi355x_llm_session_t* s, int seq, int p0, int p1, int delta, int iters, float* avg_ms, double* bytes) {
     if (!s || !avg_ms || !bytes) return TK_ERROR_INVALID_ARGUMENT;
+    if (s->session.kv_type == TK_KV_Q8_0) return fail(TK_ERROR_NOT_IMPLEMENTED, "time_kv_shift: not built for a Q8_0 KV cache");
     if (!s->session.time_kv_shift(seq, p0, p1, delta, iters, avg_ms, bytes)) return fail(TK_ERROR_GPU_ROCM_ERROR, s->session.error);
     return TK_SUCCESS;
 }
@@ -503,6 +599,7 @@ int tk_mi355x_llm_max_rows(void) { return TK_MAX_ROWS; }
 tk_error_code_t tk_mi355x_llm_forward_stage(tk_mi355x_llm_session_t* s, int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok,
                                             const float* x_in, float* x_out, int x_on_host, int layer0, int layer1, int head, int32_t* argmax) {
     if (!s || !seq || !pos) return TK_ERROR_INVALID_ARGUMENT;
+    if (s->session.kv_type == TK_KV_Q8_0) return fail(TK_ERROR_NOT_IMPLEMENTED, "forward_stage: pipeline stages are not built for a Q8_0 KV cache");
     if (!s->session.forward_stage(nrows, seq, pos, tok, x_in, x_out, x_on_host != 0, layer0, layer1, head != 0, argmax))
         return fail(TK_ERROR_INFERENCE_FAILED, s->session.error);
     return TK_SUCCESS;
@@ -515,6 +612,7 @@ static_assert(sizeof(tk_mi355x_pipe_handle_t) == sizeof(TkPipeHandle), "public a
 tk_error_code_t tk_mi355x_pipe_create(tk_mi355x_pipe_t** out, tk_mi355x_llm_session_t* s, int stage, int n_stages, int layer0, int layer1, int payload_f16,
                                       tk_mi355x_pipe_handle_t* my_handle) {
     if (!out || !s) return TK_ERROR_INVALID_ARGUMENT;
+    if (s->session.kv_type == TK_KV_Q8_0) return fail(TK_ERROR_NOT_IMPLEMENTED, "the layer-sharded pipeline is not built for a Q8_0 KV cache");
     std::unique_ptr<tk_mi355x_pipe_s> p(new tk_mi355x_pipe_s());
     if (!p->pipe.init(&s->session, stage, n_stages, layer0, layer1, payload_f16 != 0, (TkPipeHandle*)my_handle)) return fail(TK_ERROR_INVALID_ARGUMENT, p->pipe.error);
     *out = p.release();
@@ -659,6 +757,7 @@ tk_error_code_t tk_mi355x_llm_time_attention(tk_mi355x_llm_session_t* s, int nro
 
 tk_error_code_t tk_mi355x_llm_time_kv_copy(tk_mi355x_llm_session_t* s, int n_pos, int n_dst, int iters, float* kernel_ms, float* memcpy_ms, double* bytes) {
     if (!s || !kernel_ms || !memcpy_ms || !bytes) return TK_ERROR_INVALID_ARGUMENT;
+    if (s->session.kv_type == TK_KV_Q8_0) return fail(TK_ERROR_NOT_IMPLEMENTED, "time_kv_copy: not built for a Q8_0 KV cache");
     if (!s->session.time_kv_copy(n_pos, n_dst, iters, kernel_ms, memcpy_ms, bytes)) return fail(TK_ERROR_GPU_ROCM_ERROR, s->session.error);
     return TK_SUCCESS;
 }
@@ -1390,14 +1489,14 @@ tk_error_code_t tk_llm_runner_create(tk_llm_runner_t** out_runner, void* model_h
     {   /* a sequence slot in a shared session of this context size; a new session when every slot is taken */
         std::lock_guard<std::mutex> lk(r->model->batch_mu);
         for (auto& b : r->model->batchers)
-            if (b->n_ctx() == r->n_ctx && (r->slot = b->acquire_slot()) >= 0) { r->batcher = b.get(); break; }
+            if (b->n_ctx() == r->n_ctx && (r->slot = b->acquire_slot()) >= 0) /* every session of a model has its one cache type: the setter refuses once one exists */ { r->batcher = b.get(); break; }
         if (!r->batcher) {
             int slots = r->model->runner_slots;
             if (slots <= 0) { const char* e = getenv("TK_MI355X_RUNNER_SLOTS"); slots = e ? atoi(e) : 0; }
             if (slots <= 0) slots = 16;
             std::unique_ptr<TkLlmBatcher> b(new TkLlmBatcher());
             std::string err;
-            if (!b->init(&r->model->model, slots, r->n_ctx, r->model->tok.eos, &err)) return fail(TK_ERROR_GPU_MEMORY, err);
+            if (!b->init(&r->model->model, slots, r->n_ctx, r->model->tok.eos, &err, r->model->kv_cache_type)) return fail(TK_ERROR_GPU_MEMORY, err);
             if (r->model->prefix_cache) (void)b->set_prefix_cache(true);
             r->slot = b->acquire_slot();
             r->batcher = b.get();
@@ -1431,6 +1530,7 @@ tk_error_code_t tk_mi355x_llm_runner_set_context_shift(tk_llm_runner_t* runner, 
     if (!runner || (on != 0 && on != 1)) return TK_ERROR_INVALID_ARGUMENT;
     if (n_keep < -1) return fail(TK_ERROR_INVALID_ARGUMENT, "context shift: n_keep must be >= 0, or -1 for the last prompt's token count");
     if (on && runner->model->model.hp.head_dim % 8 != 0) return fail(TK_ERROR_NOT_IMPLEMENTED, "context shift moves rows in 16-byte words: head_dim must be a multiple of 8");
+    if (on && runner->model->kv_cache_type == TK_KV_Q8_0) return fail(TK_ERROR_NOT_IMPLEMENTED, "context shift re-rotates keys: not built for a Q8_0 KV cache");
     runner->shift_on = on != 0;
     runner->shift_keep = n_keep;
     return TK_SUCCESS;

@@ -25,9 +25,10 @@ TkLlmBatcher::~TkLlmBatcher() {
     }
 }
 
-bool TkLlmBatcher::init(TkLlmModel* model, int slots, int n_ctx, int32_t eos, std::string* err) {
+bool TkLlmBatcher::init(TkLlmModel* model, int slots, int n_ctx, int32_t eos, std::string* err, int kv_type) {
     if (slots < 1) slots = 1;
     if (slots > TK_MAX_ROWS) slots = TK_MAX_ROWS; /* one decode row per runner must fit one pass */
+    session_.kv_type = kv_type;
     if (!session_.init(model, slots, n_ctx)) { *err = session_.error; return false; }
     n_ctx_ = n_ctx;
     slot_used_.assign((size_t)slots, 0);

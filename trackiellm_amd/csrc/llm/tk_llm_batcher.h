@@ -94,7 +94,8 @@ class TkLlmBatcher {
 public:
     ~TkLlmBatcher();
     /* one session with `slots` sequences of `n_ctx` positions on the model's device; starts the scheduler thread */
-    bool init(TkLlmModel* model, int slots, int n_ctx, int32_t eos, std::string* err);
+    /* kv_type: the session's cache type (TkLlmSession::kv_type) */
+    bool init(TkLlmModel* model, int slots, int n_ctx, int32_t eos, std::string* err, int kv_type = 0);
     int acquire_slot();            /* -1 when every slot is taken */
     void release_slot(int slot);
     int n_ctx() const { return n_ctx_; }

@@ -96,7 +96,15 @@ public:
     hipStream_t stream = nullptr;
 
     ~TkLlmSession();
+    /* kv_type: TK_KV_F16, or TK_KV_Q8_0 (common/tk_kv_q8.h) — the cache holds ggml Q8_0 blocks of the rows the f16 cache would hold, 17/32 of its
+     * bytes.  A Q8_0 session describes every pass as "rope apart + per-row attention" (its TkPassCaps are all false, rope_in_attention is never
+     * set): tk_launch_qkv_rope_append_q8, then kernel 6 (k_attention_far over the Q8_0 cache).  kv_read, kv_shift, forward_stage and the kv_copy /
+     * kv_shift timing entries are refused on it.  The type is a member that init reads, so that init keeps its three arguments (the scheduler's
+     * CPU harness defines it); the four-argument form sets the member first */
+    int kv_type = TK_KV_F16;
     bool init(TkLlmModel* m, int max_seq, int max_ctx);
+    bool init(TkLlmModel* m, int max_seq, int max_ctx, int kv_type_) { kv_type = kv_type_; return init(m, max_seq, max_ctx); }
+    size_t kv_bytes() const; /* bytes of the cache arrays, keys and values */
     /* one pass over nrows <= TK_MAX_ROWS rows (16-row M-tiles); host arrays.  row_masks (optional): row_masks[r] = nullptr or the
      * (vocab + 31) / 32 words whose bit t says token t may be sampled for row r: grammar-constrained greedy sampling, per row, so
      * constrained and unconstrained rows share passes (and the captured graphs).  row_samp (optional): [nrows] sampling state, temp > 0
@@ -142,6 +150,9 @@ public:
      * parity tests use it to put an attention launch at any context length in one decode step. */
     bool kv_write(int layer, int seq, int pos0, int n_pos, const uint16_t* k, const uint16_t* v);
     bool kv_read(int layer, int seq, int pos0, int n_pos, uint16_t* k, uint16_t* v);
+    /* Q8_0 sessions.  kv_write quantises the f16 rows it is given on the host (tk_kv_q8_row) and uploads; kv_read is refused (the cache's values
+     * are not f16 numbers); kv_read_q8 returns the raw rows: int8 values [position][kv head][dim] and scale bits [position][kv head][dim / 32] */
+    bool kv_read_q8(int layer, int seq, int pos0, int n_pos, int8_t* kq, uint16_t* kd, int8_t* vq, uint16_t* vd);
     /* rows [pos0, pos0 + n_pos) of sequence src_seq copied onto the same rows of dst_seq (src_seq != dst_seq) in every layer: one launch of
      * k_kv_copy_rows, synchronous.  A cache row at position p depends only on tokens 0 .. p, so a sequence that is to hold the same leading
      * tokens as another can take its rows instead of recomputing them (the prompt prefix cache, tk_llm_batcher.h). */
@@ -235,6 +246,8 @@ private:
     bool upload_rows(int nrows, const int32_t* seq, const int32_t* pos, const int32_t* tok);
     bool clear_row_tables(unsigned which);
     uint16_t *kcache = nullptr, *vcache = nullptr;
+    TkKvQ8 kvq{}; /* the Q8_0 cache (kcache / vcache stay null) */
+    bool refuse_q8(const char* what); /* true (and `error` set) on a Q8_0 session */
     float *x = nullptr, *x2 = nullptr, *qbuf = nullptr, *partial = nullptr, *partial2 = nullptr, *logits = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
     TkActQ8 act_d{}, act_qd{}, act_ff{};
     int32_t *d_seq = nullptr, *d_pos = nullptr, *d_tok = nullptr, *d_nsteps = nullptr, *d_hist = nullptr;
@@ -281,6 +294,10 @@ bool tk_llm_matmul_float_probe(int device, int type, const void* w, int64_t rows
  * width nrows, the ks slabs summed in ascending order; y [nrows][rows] on the host */
 bool tk_llm_gemv_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, int ks, int nrows, const float* x, float* y,
                        std::string& error);
+
+/* the Q8_0 cache's two production launches on host arrays (tk_mi355x_kv_q8_probe, include/tk/tk_mi355x_ext.h); the caller has validated everything */
+struct tk_mi355x_kv_q8_probe_s;
+bool tk_llm_kv_q8_probe(int device, const tk_mi355x_kv_q8_probe_s* p, std::string& error);
 
 /* one step launcher on host arrays (tk_mi355x_llm_step_probe, include/tk/tk_mi355x_ext.h): everything validated first, device < 0 validates only */
 struct tk_mi355x_llm_step_probe_s;

@@ -338,10 +338,24 @@ static void free_act(TkActQ8* a) {
     *a = TkActQ8{};
 }
 
+bool TkLlmSession::refuse_q8(const char* what) {
+    if (kv_type != TK_KV_Q8_0) return false;
+    error = std::string(what) + ": not built for a Q8_0 KV cache";
+    return true;
+}
+
+size_t TkLlmSession::kv_bytes() const {
+    if (!model) return 0;
+    const TkLlmHParams& h = model->hp;
+    const size_t kv = (size_t)h.n_layer * max_seq * max_ctx * h.n_kv_head * h.head_dim;
+    return kv_type == TK_KV_Q8_0 ? 2 * (kv + kv / TK_KV_Q8_BLOCK * 2) : 2 * kv * 2;
+}
+
 bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     model = m;
     max_seq = mseq;
     max_ctx = mctx;
+    if (kv_type != TK_KV_F16 && kv_type != TK_KV_Q8_0) { error = "kv_type must be 0 (F16) or 1 (Q8_0), asked for " + std::to_string(kv_type); return false; }
     if (m && !m->ready()) {
         int other = -1;
         const int ft = m->float_type(&other);
@@ -363,14 +377,31 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     size_t kv = (size_t)h.n_layer * mseq * mctx * KVD;
     /* the one allocation that grows with sequences x window: a failure names what was asked for (16 sequences of 32 768 positions of a 7B model
      * are 69 GB) */
-    if (hipMalloc((void**)&kcache, kv * 2) != hipSuccess || hipMalloc((void**)&vcache, kv * 2) != hipSuccess) {
-        (void)hipGetLastError();
-        error = "KV cache: could not allocate 2 x " + std::to_string(kv * 2) + " bytes on the device (" + std::to_string(h.n_layer) + " layers x " + std::to_string(mseq) +
-                " sequences x " + std::to_string(mctx) + " positions x " + std::to_string(KVD) + " f16, keys and values)";
-        return false;
+    if (kv_type == TK_KV_Q8_0) {
+        /* head_dim % 64 == 0 (TkLlmModel::init): rows are whole blocks, value rows whole 16-byte words, scale rows whole 4-byte words */
+        const size_t sc = kv / TK_KV_Q8_BLOCK * 2;
+        if (hipMalloc((void**)&kvq.kq, kv) != hipSuccess || hipMalloc((void**)&kvq.vq, kv) != hipSuccess || hipMalloc((void**)&kvq.kd, sc) != hipSuccess ||
+            hipMalloc((void**)&kvq.vd, sc) != hipSuccess) {
+            (void)hipGetLastError();
+            error = "Q8_0 KV cache: could not allocate 2 x " + std::to_string(kv) + " bytes of int8 values and 2 x " + std::to_string(sc) + " bytes of f16 scales on the device (" +
+                    std::to_string(h.n_layer) + " layers x " + std::to_string(mseq) + " sequences x " + std::to_string(mctx) + " positions x " + std::to_string(KVD) +
+                    " elements, keys and values)";
+            return false;
+        }
+        HIPQ(hipMemset(kvq.kq, 0, kv));
+        HIPQ(hipMemset(kvq.vq, 0, kv));
+        HIPQ(hipMemset(kvq.kd, 0, sc));
+        HIPQ(hipMemset(kvq.vd, 0, sc));
+    } else {
+        if (hipMalloc((void**)&kcache, kv * 2) != hipSuccess || hipMalloc((void**)&vcache, kv * 2) != hipSuccess) {
+            (void)hipGetLastError();
+            error = "KV cache: could not allocate 2 x " + std::to_string(kv * 2) + " bytes on the device (" + std::to_string(h.n_layer) + " layers x " + std::to_string(mseq) +
+                    " sequences x " + std::to_string(mctx) + " positions x " + std::to_string(KVD) + " f16, keys and values)";
+            return false;
+        }
+        HIPQ(hipMemset(kcache, 0, kv * 2));
+        HIPQ(hipMemset(vcache, 0, kv * 2));
     }
-    HIPQ(hipMemset(kcache, 0, kv * 2));
-    HIPQ(hipMemset(vcache, 0, kv * 2));
     HIPQ(hipMalloc((void**)&x, (size_t)TK_MAX_ROWS * h.d_model * 4));
     HIPQ(hipMalloc((void**)&qbuf, (size_t)TK_MAX_ROWS * QD * 4));
     size_t pmax = (size_t)h.ks_qkv * (QD + 2 * KVD);
@@ -394,7 +425,7 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
     HIPQ(hipMalloc((void**)&d_hist, (size_t)hist_cap * TK_MAX_ROWS * 4));
     HIPQ(hipMalloc((void**)&d_tiles, (size_t)(1 + TK_MAX_ROWS) * 4));
     HIPQ(hipMemset(d_tiles, 0, (size_t)(1 + TK_MAX_ROWS) * 4));
-    if (mctx > TK_LONG_ATT_MIN_POS && tk_attention_long_applies(1, h.n_head, h.n_kv_head, h.head_dim))
+    if (kv_type == TK_KV_F16 && mctx > TK_LONG_ATT_MIN_POS && tk_attention_long_applies(1, h.n_head, h.n_kv_head, h.head_dim))
         HIPQ(hipMalloc((void**)&d_scores, tk_attention_long_scratch_floats(h.n_head, h.head_dim, mctx) * sizeof(float)));
     HIPQ(hipMalloc((void**)&d_mask, (size_t)TK_MAX_ROWS * (((size_t)h.vocab + 31) / 32) * 4));
     HIPQ(hipMalloc((void**)&d_mask_row, TK_MAX_ROWS * 4));
@@ -439,9 +470,23 @@ bool TkLlmSession::init(TkLlmModel* m, int mseq, int mctx) {
      * is loaded before the first pass is recorded into a graph */
     if (kv_copy_applies() && !enqueue_kv_copy(nullptr, 0)) return false;
     /* so does the context shift's kernel: once with an empty move */
-    if (kv_copy_applies() && !tk_launch_kv_shift_rows(TkKvShiftDesc{0, 0, 0, 0}, kcache, vcache, rope_cos, rope_sin, h.n_layer, h.n_kv_head, h.head_dim, max_seq, max_ctx, stream)) {
+    if (kv_type == TK_KV_F16 && kv_copy_applies() &&
+        !tk_launch_kv_shift_rows(TkKvShiftDesc{0, 0, 0, 0}, kcache, vcache, rope_cos, rope_sin, h.n_layer, h.n_kv_head, h.head_dim, max_seq, max_ctx, stream)) {
         error = "kv_shift: launch failed";
         return false;
+    }
+    /* and the Q8_0 cache's append and attention kernels: one row of sequence 0 at position 0, whose q | k | v slab is zero (the row quantises to the
+     * zeros the cache already holds) */
+    if (kv_type == TK_KV_Q8_0) {
+        HIPQ(hipMemsetAsync(partial, 0, pmax * TK_MAX_ROWS * 4, stream));
+        HIPQ(hipMemsetAsync(d_seq, 0, 4, stream));
+        HIPQ(hipMemsetAsync(d_pos, 0, 4, stream));
+        tk_launch_qkv_rope_append_q8(partial, 1, QD + 2 * KVD, h.n_head, h.n_kv_head, h.head_dim, rope_cos, rope_sin, d_seq, d_pos, 1, qbuf, kvq, 0, max_seq, max_ctx, stream);
+        if (!tk_launch_attention_q8(qbuf, kvq, d_seq, d_pos, 1, h.n_head, h.n_kv_head, h.head_dim, 0, max_seq, max_ctx, act_qd, nullptr, stream)) {
+            error = "Q8_0 KV cache: the attention kernel does not take this head geometry";
+            return false;
+        }
+        HIPQ(hipGetLastError());
     }
     HIPQ(hipDeviceSynchronize());
     return true;
@@ -452,7 +497,7 @@ TkLlmSession::~TkLlmSession() {
     if (model) (void)hipSetDevice(model->device);
     if (stream) (void)hipStreamSynchronize(stream);
     for (auto& v : graphs) for (auto& g : v) if (g) (void)hipGraphExecDestroy(g);
-    void* ptrs[] = {kcache, vcache, x, x2, qbuf, partial, partial2, logits, rope_cos, rope_sin, d_seq, d_pos, d_tok, d_nsteps, d_hist, d_mask, d_mask_row, d_samp, d_tab, d_tiles, d_scores};
+    void* ptrs[] = {kcache, vcache, kvq.kq, kvq.vq, kvq.kd, kvq.vd, x, x2, qbuf, partial, partial2, logits, rope_cos, rope_sin, d_seq, d_pos, d_tok, d_nsteps, d_hist, d_mask, d_mask_row, d_samp, d_tab, d_tiles, d_scores};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (d_kvcopy) (void)hipFree(d_kvcopy);
     if (h_kvcopy) (void)hipHostFree(h_kvcopy);
@@ -545,6 +590,27 @@ bool TkLlmSession::kv_write(int layer, int seq, int pos0, int n_pos, const uint1
     const TkLlmHParams& h = model->hp;
     if (layer < 0 || layer >= h.n_layer || seq < 0 || seq >= max_seq || pos0 < 0 || n_pos <= 0 || pos0 + n_pos > max_ctx || !k || !v) { error = "kv_write: (layer, sequence, positions) outside the cache"; return false; }
     HIPQ(hipSetDevice(model->device));
+    if (kv_type == TK_KV_Q8_0) { /* the rows quantised here by the one definition the append kernel runs, laid out [kv head][position] as the cache has them */
+        const int nb = h.head_dim / TK_KV_Q8_BLOCK;
+        const size_t rows = (size_t)h.n_kv_head * n_pos;
+        std::vector<int8_t> q[2] = {std::vector<int8_t>(rows * h.head_dim), std::vector<int8_t>(rows * h.head_dim)};
+        std::vector<uint16_t> d[2] = {std::vector<uint16_t>(rows * nb), std::vector<uint16_t>(rows * nb)};
+        for (int kvh = 0; kvh < h.n_kv_head; ++kvh)
+            for (int p = 0; p < n_pos; ++p) {
+                const size_t src = ((size_t)p * h.n_kv_head + kvh) * h.head_dim, row = (size_t)kvh * n_pos + p;
+                tk_kv_q8_row(k + src, h.head_dim, q[0].data() + row * h.head_dim, d[0].data() + row * nb);
+                tk_kv_q8_row(v + src, h.head_dim, q[1].data() + row * h.head_dim, d[1].data() + row * nb);
+            }
+        for (int kvh = 0; kvh < h.n_kv_head; ++kvh) {
+            const size_t dst = (((size_t)layer * max_seq + seq) * h.n_kv_head + kvh) * max_ctx + pos0, src = (size_t)kvh * n_pos;
+            HIPQ(hipMemcpyAsync(kvq.kq + dst * h.head_dim, q[0].data() + src * h.head_dim, (size_t)n_pos * h.head_dim, hipMemcpyHostToDevice, stream));
+            HIPQ(hipMemcpyAsync(kvq.vq + dst * h.head_dim, q[1].data() + src * h.head_dim, (size_t)n_pos * h.head_dim, hipMemcpyHostToDevice, stream));
+            HIPQ(hipMemcpyAsync(kvq.kd + dst * nb, d[0].data() + src * nb, (size_t)n_pos * nb * 2, hipMemcpyHostToDevice, stream));
+            HIPQ(hipMemcpyAsync(kvq.vd + dst * nb, d[1].data() + src * nb, (size_t)n_pos * nb * 2, hipMemcpyHostToDevice, stream));
+        }
+        HIPQ(hipStreamSynchronize(stream)); /* the staging vectors die with this scope */
+        return true;
+    }
     const size_t hd = (size_t)h.head_dim * 2; /* bytes of one cache row */
     for (int kvh = 0; kvh < h.n_kv_head; ++kvh) { /* host pitch = one position of all heads; device run of one head = consecutive positions */
         const size_t dst = ((((size_t)layer * max_seq + seq) * h.n_kv_head + kvh) * max_ctx + pos0) * h.head_dim;
@@ -557,6 +623,7 @@ bool TkLlmSession::kv_write(int layer, int seq, int pos0, int n_pos, const uint1
 
 bool TkLlmSession::kv_read(int layer, int seq, int pos0, int n_pos, uint16_t* k, uint16_t* v) {
     const TkLlmHParams& h = model->hp;
+    if (kv_type == TK_KV_Q8_0) { error = "kv_read: the rows of a Q8_0 KV cache are not f16 numbers (kv_read_q8 returns them)"; return false; }
     if (layer < 0 || layer >= h.n_layer || seq < 0 || seq >= max_seq || pos0 < 0 || n_pos <= 0 || pos0 + n_pos > max_ctx || !k || !v) { error = "kv_read: (layer, sequence, positions) outside the cache"; return false; }
     HIPQ(hipSetDevice(model->device));
     const size_t hd = (size_t)h.head_dim * 2;
@@ -564,6 +631,26 @@ bool TkLlmSession::kv_read(int layer, int seq, int pos0, int n_pos, uint16_t* k,
         const size_t src = ((((size_t)layer * max_seq + seq) * h.n_kv_head + kvh) * max_ctx + pos0) * h.head_dim;
         HIPQ(hipMemcpy2DAsync(k + (size_t)kvh * h.head_dim, hd * h.n_kv_head, kcache + src, hd, hd, (size_t)n_pos, hipMemcpyDeviceToHost, stream));
         HIPQ(hipMemcpy2DAsync(v + (size_t)kvh * h.head_dim, hd * h.n_kv_head, vcache + src, hd, hd, (size_t)n_pos, hipMemcpyDeviceToHost, stream));
+    }
+    HIPQ(hipStreamSynchronize(stream));
+    return true;
+}
+
+bool TkLlmSession::kv_read_q8(int layer, int seq, int pos0, int n_pos, int8_t* kq, uint16_t* kd, int8_t* vq, uint16_t* vd) {
+    const TkLlmHParams& h = model->hp;
+    if (kv_type != TK_KV_Q8_0) { error = "kv_read_q8: the session's KV cache is f16 (kv_read returns its rows)"; return false; }
+    if (layer < 0 || layer >= h.n_layer || seq < 0 || seq >= max_seq || pos0 < 0 || n_pos <= 0 || pos0 + n_pos > max_ctx || !kq || !kd || !vq || !vd) {
+        error = "kv_read_q8: (layer, sequence, positions) outside the cache";
+        return false;
+    }
+    HIPQ(hipSetDevice(model->device));
+    const size_t hd = (size_t)h.head_dim, sb = (size_t)h.head_dim / TK_KV_Q8_BLOCK * 2; /* bytes of one row's values and scales */
+    for (int kvh = 0; kvh < h.n_kv_head; ++kvh) {
+        const size_t src = (((size_t)layer * max_seq + seq) * h.n_kv_head + kvh) * max_ctx + pos0;
+        HIPQ(hipMemcpy2DAsync(kq + (size_t)kvh * hd, hd * h.n_kv_head, kvq.kq + src * hd, hd, hd, (size_t)n_pos, hipMemcpyDeviceToHost, stream));
+        HIPQ(hipMemcpy2DAsync(vq + (size_t)kvh * hd, hd * h.n_kv_head, kvq.vq + src * hd, hd, hd, (size_t)n_pos, hipMemcpyDeviceToHost, stream));
+        HIPQ(hipMemcpy2DAsync((uint8_t*)kd + (size_t)kvh * sb, sb * h.n_kv_head, (const uint8_t*)kvq.kd + src * sb, sb, sb, (size_t)n_pos, hipMemcpyDeviceToHost, stream));
+        HIPQ(hipMemcpy2DAsync((uint8_t*)vd + (size_t)kvh * sb, sb * h.n_kv_head, (const uint8_t*)kvq.vd + src * sb, sb, sb, (size_t)n_pos, hipMemcpyDeviceToHost, stream));
     }
     HIPQ(hipStreamSynchronize(stream));
     return true;
@@ -587,7 +674,9 @@ bool TkLlmSession::enqueue_kv_copy(const TkKvCopyDesc* descs, int n) {
         memcpy(h_kvcopy, descs, (size_t)n * sizeof(TkKvCopyDesc));
         HIPQ(hipMemcpyAsync(d_kvcopy, h_kvcopy, (size_t)n * sizeof(TkKvCopyDesc), hipMemcpyHostToDevice, stream));
     }
-    if (!tk_launch_kv_copy_rows(d_kvcopy, n, max_n, kcache, vcache, h.n_layer, h.n_kv_head, h.head_dim, max_seq, max_ctx, stream)) { error = "kv_copy: launch failed"; return false; }
+    const bool launched = kv_type == TK_KV_Q8_0 ? tk_launch_kv_copy_rows_q8(d_kvcopy, n, max_n, kvq, h.n_layer, h.n_kv_head, h.head_dim, max_seq, max_ctx, stream)
+                                                : tk_launch_kv_copy_rows(d_kvcopy, n, max_n, kcache, vcache, h.n_layer, h.n_kv_head, h.head_dim, max_seq, max_ctx, stream);
+    if (!launched) { error = "kv_copy: launch failed"; return false; }
     return true;
 }
 
@@ -602,6 +691,7 @@ bool TkLlmSession::kv_shift(int seq, int p0, int p1, int delta, bool* bad_args) 
     const TkLlmHParams& h = model->hp;
     const TkKvShiftDesc m{seq, p0, p1, delta};
     if (bad_args) *bad_args = true;
+    if (refuse_q8("kv_shift")) return false;
     if (!kv_copy_applies()) { error = "kv_shift: head_dim must be a multiple of 8"; return false; }
     if (!tk_kv_shift_ok(m, max_seq, max_ctx)) { error = "kv_shift: needs a sequence of the session, 0 <= p0 < p1 <= max_ctx, delta < 0 and p0 + delta >= 0"; return false; }
     if (bad_args) *bad_args = false;
@@ -614,6 +704,7 @@ bool TkLlmSession::kv_shift(int seq, int p0, int p1, int delta, bool* bad_args) 
 bool TkLlmSession::time_kv_shift(int seq, int p0, int p1, int delta, int iters, float* avg_ms, double* bytes) {
     const TkLlmHParams& h = model->hp;
     const TkKvShiftDesc m{seq, p0, p1, delta};
+    if (refuse_q8("time_kv_shift")) return false;
     if (!kv_copy_applies() || !tk_kv_shift_ok(m, max_seq, max_ctx) || iters < 1) { error = "time_kv_shift: a move kv_shift refuses, or no iterations"; return false; }
     HIPQ(hipSetDevice(model->device));
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -969,6 +1060,63 @@ bool tk_llm_step_probe(int device, tk_mi355x_llm_step_probe_s* pp, std::string& 
     return ok;
 }
 
+bool tk_llm_kv_q8_probe(int device, const tk_mi355x_kv_q8_probe_s* pp, std::string& error) {
+    const tk_mi355x_kv_q8_probe_s& p = *pp;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) { error = "kv_q8 probe: no such HIP device"; return false; }
+    HIPQ(hipSetDevice(device));
+    if (const char* e = tk_llm_prepare_device(device)) { error = std::string("LDS opt-in failed: ") + e; return false; }
+    const int hd = p.head_dim;
+    const size_t elems = (size_t)p.n_layer * p.max_seq * p.n_kv_head * p.max_ctx * hd, scales = elems / TK_KV_Q8_BLOCK;
+    const int n_head = p.mode == 0 ? p.n_kv_head : p.n_head; /* mode 0: one zero query head per KV head */
+    const int QD = n_head * hd, KVD = p.n_kv_head * hd, n_total = QD + 2 * KVD;
+    std::vector<void*> owned;
+    bool ok = true;
+    auto dev = [&](const void* host, size_t bytes) -> void* { /* a device array, a copy of `host` or zeros */
+        void* d = nullptr;
+        if (!ok || hipMalloc(&d, bytes ? bytes : 1) != hipSuccess) { ok = false; return nullptr; }
+        owned.push_back(d);
+        ok = (host ? hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) : hipMemset(d, 0, bytes)) == hipSuccess;
+        return d;
+    };
+    TkKvQ8 c{(int8_t*)dev(p.kq, elems), (uint16_t*)dev(p.kd, scales * 2), (int8_t*)dev(p.vq, elems), (uint16_t*)dev(p.vd, scales * 2)};
+    int32_t* d_seq = (int32_t*)dev(p.seq, (size_t)p.nrows * 4);
+    int32_t* d_pos = (int32_t*)dev(p.pos, (size_t)p.nrows * 4);
+    TkActQ8 act{};
+    if (p.mode == 0) {
+        /* the production append launch on a slab that holds the rows: ks = 1, q columns zero, k | v columns the f16 values widened; RoPE by an identity
+         * table (cos 1, sin 0) gives fma(-b, 0, a * 1) = a (a zero may change its sign, which the quantiser does not see), f16 rounding gives it back */
+        std::vector<float> slab((size_t)p.nrows * n_total, 0.0f), cs((size_t)p.max_ctx * (hd / 2), 1.0f);
+        for (int r = 0; r < p.nrows; ++r)
+            for (int i = 0; i < KVD; ++i) {
+                slab[(size_t)r * n_total + QD + i] = tk_f16_to_f32(p.k16[(size_t)r * KVD + i]);
+                slab[(size_t)r * n_total + QD + KVD + i] = tk_f16_to_f32(p.v16[(size_t)r * KVD + i]);
+            }
+        float* d_slab = (float*)dev(slab.data(), slab.size() * 4);
+        float* d_cos = (float*)dev(cs.data(), cs.size() * 4);
+        float* d_sin = (float*)dev(nullptr, cs.size() * 4);
+        float* d_q = (float*)dev(nullptr, (size_t)p.nrows * QD * 4);
+        if (ok) {
+            tk_launch_qkv_rope_append_q8(d_slab, 1, n_total, n_head, p.n_kv_head, hd, d_cos, d_sin, d_seq, d_pos, p.nrows, d_q, c, p.layer, p.max_seq, p.max_ctx, nullptr);
+            ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(p.kq, c.kq, elems, hipMemcpyDeviceToHost) == hipSuccess &&
+                 hipMemcpy(p.vq, c.vq, elems, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(p.kd, c.kd, scales * 2, hipMemcpyDeviceToHost) == hipSuccess &&
+                 hipMemcpy(p.vd, c.vd, scales * 2, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+    } else {
+        float* d_q = (float*)dev(p.q, (size_t)p.nrows * QD * 4);
+        float* d_o = (float*)dev(p.out, (size_t)p.nrows * QD * 4);
+        ok = ok && alloc_act(&act, QD, -1, error);
+        if (ok) {
+            ok = tk_launch_attention_q8(d_q, c, d_seq, d_pos, p.nrows, n_head, p.n_kv_head, hd, p.layer, p.max_seq, p.max_ctx, act, d_o, nullptr) &&
+                 hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(p.out, d_o, (size_t)p.nrows * QD * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+        free_act(&act);
+    }
+    for (void* d : owned) (void)hipFree(d);
+    if (!ok) { (void)hipGetLastError(); if (error.empty()) error = "kv_q8 probe: device error"; }
+    return ok;
+}
+
 bool tk_llm_repack_probe(int device, int type, const void* blocks, int64_t rows, int64_t K, void* tiles, std::string& error) {
     if (!tk_type_is_kquant(type)) {
         error = "repack probe: type must be " TK_KQUANT_NAMES_OR;
@@ -1108,6 +1256,12 @@ void TkLlmSession::enqueue_attention(const TkPassForm& f, const float* qkv_slab,
     const TkLlmHParams& h = model->hp;
     const int n_qkv = (h.n_head + 2 * h.n_kv_head) * h.head_dim;
     hipStream_t s = stream;
+    if (kv_type == TK_KV_Q8_0) { /* one form: rope apart, then kernel 6 (enqueue_range has refused every other description) */
+        tk_launch_qkv_rope_append_q8(qkv_slab, ks_qkv, n_qkv, h.n_head, h.n_kv_head, h.head_dim, rope_cos, rope_sin, d_seq, d_pos, nrows, qbuf, kvq, l, max_seq, max_ctx, s);
+        if (!tk_launch_attention_q8(qbuf, kvq, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l, max_seq, max_ctx, act_qd, nullptr, s) && launch_error.empty())
+            launch_error = "Q8_0 KV cache: the attention kernel does not take this pass";
+        return;
+    }
     if (!f.rope_in_attention)
         tk_launch_qkv_rope_append(qkv_slab, ks_qkv, n_qkv, h.n_head, h.n_kv_head, h.head_dim, rope_cos, rope_sin, d_seq, d_pos, nrows, qbuf, kcache, vcache, l, max_seq, max_ctx, s);
     if (f.attn == TK_ATT_LONG || f.attn == TK_ATT_RUN)
@@ -1150,7 +1304,8 @@ void TkLlmSession::enqueue_range(int nrows, int l0, int l1, bool embed, bool fol
     };
     /* a form is only ever built by tk_pass_form.h's resolvers; one that names a launch its other fields rule out would read what nobody wrote */
     const bool scored = f.attn == TK_ATT_LONG || f.attn == TK_ATT_RUN;
-    if ((f.rope_in_attention ? f.attn == TK_ATT_TILED || f.attn == TK_ATT_RUN : f.attn == TK_ATT_LONG) || (scored && !d_scores)) {
+    if ((f.rope_in_attention ? f.attn == TK_ATT_TILED || f.attn == TK_ATT_RUN : f.attn == TK_ATT_LONG) || (scored && !d_scores) ||
+        (kv_type == TK_KV_Q8_0 && (f.rope_in_attention || f.attn != TK_ATT_ROW))) {
         if (launch_error.empty()) launch_error = "a pass was described in a form that does not exist";
         return;
     }
@@ -1271,6 +1426,7 @@ bool TkLlmSession::launch_pass(const TkPassForm& f, int nrows, bool use_graph) {
 
 TkPassCaps TkLlmSession::pass_caps(int nrows) const {
     const TkLlmHParams& h = model->hp;
+    if (kv_type == TK_KV_Q8_0) return TkPassCaps{false, false, false}; /* one attention, the per-row one */
     return TkPassCaps{d_scores != nullptr, tk_attention_prefill_applies(h.n_head, h.n_kv_head, h.head_dim), tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim)};
 }
 
@@ -1410,7 +1566,8 @@ bool TkLlmSession::forward(int nrows, const int32_t* seq, const int32_t* pos, co
         if (seq[r] == seq[r - 1]) { runs = pos[r] == pos[r - 1] + 1; continue; }
         for (int b = 0; b + 1 < r && runs; ++b) runs = seq[b] != seq[r];
     }
-    const TkPassForm form = lm_head ? tk_pass_form_rows(distinct, runs, nrows, top, pass_caps(nrows), any_adj, any_lp) : tk_pass_form(false, false, nrows, top, pass_caps(nrows));
+    const bool once = distinct && kv_type == TK_KV_F16; /* a Q8_0 session always ropes apart */
+    const TkPassForm form = lm_head ? tk_pass_form_rows(once, runs, nrows, top, pass_caps(nrows), any_adj, any_lp) : tk_pass_form(false, false, nrows, top, pass_caps(nrows));
     if (!launch_pass(form, nrows, graphs_enabled())) return false;
     HIPQ(hipGetLastError());
     if (!lm_head) { HIPQ(hipStreamSynchronize(stream)); return true; }
@@ -1471,6 +1628,7 @@ bool TkLlmSession::forward_stage(int nrows, const int32_t* seq, const int32_t* p
     if ((tok == nullptr) == (x_in == nullptr)) { error = "a stage starts from tokens (first stage) or from a residual stream, not both"; return false; }
     if (head && l1 != h.n_layer) { error = "the head belongs to the stage that ends at the last layer"; return false; }
     if (!head && !x_out) { error = "a stage without the head must hand its residual stream on"; return false; }
+    if (refuse_q8("forward_stage")) return false;
     int top = 0;
     bool distinct = true;
     if (!check_pass_rows(nrows, seq, pos, tok, &top, &distinct)) return false;
@@ -1556,7 +1714,7 @@ bool TkLlmSession::decode(int nrows, int n_steps, int32_t* out_tokens_host) {
     HIPQ(ev.create());
     HIPQ(hipEventRecord(ev.e0, stream));
     for (int i = 0; i < n_steps; ++i) /* positions advance on the device; the host knows where the loop stands */
-        if (!launch_pass(tk_pass_form(true, true, nrows, top0 + i, caps), nrows, use_graph)) { (void)hipStreamSynchronize(stream); return false; }
+        if (!launch_pass(tk_pass_form(true, kv_type == TK_KV_F16, nrows, top0 + i, caps), nrows, use_graph)) { (void)hipStreamSynchronize(stream); return false; }
     HIPQ(hipGetLastError());
     HIPQ(hipEventRecord(ev.e1, stream));
     if (out_tokens_host) HIPQ(hipMemcpyAsync(out_tokens_host, d_hist, (size_t)n_steps * TK_MAX_ROWS * 4, hipMemcpyDeviceToHost, stream));
@@ -1648,6 +1806,7 @@ bool TkLlmSession::time_gemv(int layer, int which, int nrows, int iters, float* 
 bool TkLlmSession::time_kv_copy(int n_pos, int n_dst, int iters, float* kernel_ms, float* memcpy_ms, double* bytes) {
     const TkLlmHParams& h = model->hp;
     if (n_pos < 1 || n_pos > max_ctx || n_dst < 1 || n_dst >= max_seq || n_dst > TK_MAX_ROWS || iters < 1) { error = "bad n_pos / n_dst / iters"; return false; }
+    if (refuse_q8("time_kv_copy")) return false;
     HIPQ(hipSetDevice(model->device));
     std::vector<TkKvCopyDesc> ds((size_t)n_dst);
     for (int d = 0; d < n_dst; ++d) ds[(size_t)d] = TkKvCopyDesc{0, d + 1, 0, n_pos};
@@ -1702,6 +1861,12 @@ bool TkLlmSession::time_attention(int nrows, int ctx, int iters, float* avg_ms, 
     const bool longf = lf && lf[0] == '1' && d_scores && tk_attention_long_applies(nrows, h.n_head, h.n_kv_head, h.head_dim);
     const bool unfused = (uf && uf[0] == '1') || longf;
     auto launch = [&](int l) {
+        if (kv_type == TK_KV_Q8_0) { /* the Q8_0 session's decode launch set: append + kernel 6 */
+            tk_launch_qkv_rope_append_q8(partial, h.ks_qkv, QD + 2 * KVD, h.n_head, h.n_kv_head, h.head_dim, rope_cos, rope_sin, d_seq, d_pos, nrows, qbuf, kvq, l % h.n_layer,
+                                         max_seq, max_ctx, stream);
+            (void)tk_launch_attention_q8(qbuf, kvq, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l % h.n_layer, max_seq, max_ctx, act_qd, nullptr, stream);
+            return;
+        }
         if (longf) {
             tk_launch_attention_long(partial, h.ks_qkv, QD + 2 * KVD, rope_cos, rope_sin, kcache, vcache, d_seq, d_pos, nrows, h.n_head, h.n_kv_head, h.head_dim, l % h.n_layer,
                                      max_seq, max_ctx, d_scores, act_qd, stream);
@@ -1714,5 +1879,6 @@ bool TkLlmSession::time_attention(int nrows, int ctx, int iters, float* avg_ms, 
                             h.head_dim, l % h.n_layer, max_seq, max_ctx, act_qd, !unfused, stream);
     };
     *kv_bytes = (double)nrows * ctx * KVD * 2.0 * 2.0;
+    if (kv_type == TK_KV_Q8_0) *kv_bytes = (double)nrows * ctx * KVD * (34.0 / 32.0) * 3.0; /* keys twice, values once, 34 bytes per 32 elements */
     return time_launches(iters, [&] { launch(0); }, launch, avg_ms);
 }

@@ -170,6 +170,22 @@ static inline int tk_verify_run_min_pos(int nrows) { (void)nrows; return 256; }
 struct TkKvCopyDesc { int32_t src_seq, dst_seq, p0, n; };
 bool tk_launch_kv_copy_rows(const TkKvCopyDesc* desc, int ndesc, int max_n, uint16_t* kcache, uint16_t* vcache, int n_layer, int n_kv_head, int head_dim, int max_seq,
                             int max_ctx, hipStream_t s);
+#include "../common/tk_kv_q8.h"
+/* The Q8_0 KV cache (common/tk_kv_q8.h): int8 values [layer][seq][kv_head][max_ctx][head_dim] and f16 scales [layer][seq][kv_head][max_ctx][head_dim / 32],
+ * for K and for V.  head_dim % 64 == 0 (every geometry TkLlmModel::init accepts), so value rows are whole 16-byte words and scale rows 4-byte ones */
+struct TkKvQ8 { int8_t* kq; uint16_t* kd; int8_t* vq; uint16_t* vd; };
+/* k_qkv_rope_append's Q8_0 form: the same K-split sums, RoPE and f16 rounding, then the block quantiser; q goes to qbuf unchanged */
+void tk_launch_qkv_rope_append_q8(const float* partial, int ks, int n_total, int n_head, int n_kv_head, int head_dim, const float* rope_cos, const float* rope_sin,
+                                  const int32_t* seq, const int32_t* pos, int nrows, float* qbuf, TkKvQ8 cache, int layer, int max_seq, int max_ctx, hipStream_t s);
+/* kernel 6 of the attention plan: k_attention_far over a Q8_0 cache (the rows appended by tk_launch_qkv_rope_append_q8 before), every pass of a
+ * Q8_0 session.  o32 (optional, the probe's): the quotients [nrows][n_head * head_dim] before quantize_chunk8 as well.  false: a geometry the
+ * kernel does not take (nothing is launched) */
+TkAttentionPlan tk_attention_plan_q8(int nrows, int n_head, int n_kv_head, int head_dim);
+bool tk_launch_attention_q8(const float* qbuf, TkKvQ8 cache, const int32_t* seq, const int32_t* pos, int nrows, int n_head, int n_kv_head, int head_dim, int layer,
+                            int max_seq, int max_ctx, TkActQ8 out, float* o32, hipStream_t s);
+/* tk_launch_kv_copy_rows on a Q8_0 cache: values and scales of both caches, bit for bit, in one launch */
+bool tk_launch_kv_copy_rows_q8(const TkKvCopyDesc* desc, int ndesc, int max_n, TkKvQ8 cache, int n_layer, int n_kv_head, int head_dim, int max_seq, int max_ctx,
+                               hipStream_t s);
 #include "../common/tk_kv_shift.h"
 /* context shift (common/tk_kv_shift.h): rows [p0, p1) of sequence m.seq moved to [p0 + delta, p1 + delta), delta < 0, in every layer, KV head and both
  * caches in one launch; V copied, K re-rotated by delta positions with rows -delta of rope_cos / rope_sin ([max_ctx][head_dim / 2]).  Source and

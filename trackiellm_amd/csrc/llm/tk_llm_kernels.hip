@@ -2822,6 +2822,61 @@ void tk_launch_qkv_rope_append(const float* partial, int ks, int n_total, int n_
                        rope_sin, seq, pos, qbuf, kcache, vcache, layer, max_seq, max_ctx);
 }
 
+/* The Q8_0 cache's form (common/tk_kv_q8.h): the same sums, rope and f16 rounding, term for term; the row the f16 cache would hold then waits in
+ * LDS, widened to fp32, and one thread per block of 32 runs tk_kv_q8_block on it.  LDS: 2 * head_dim floats (K row, V row). */
+__global__ void k_qkv_rope_append_q8(const float* partial, int ks, int n_total, int n_head, int n_kv_head, int head_dim, const float* rope_cos,
+                                     const float* rope_sin, const int32_t* seq, const int32_t* pos, float* qbuf, TkKvQ8 cache, int layer, int max_seq, int max_ctx) {
+    extern __shared__ __attribute__((aligned(16))) float kvrow[];
+    const int kvh = blockIdx.x, r = blockIdx.y;
+    const int half = head_dim / 2, grp = n_head / n_kv_head;
+    const int QD = n_head * head_dim, KVD = n_kv_head * head_dim;
+    const int p = pos[r], sq = seq[r];
+    const float* cs = rope_cos + (int64_t)p * half;
+    const float* sn = rope_sin + (int64_t)p * half;
+    for (int idx = threadIdx.x; idx < (grp + 1) * half; idx += blockDim.x) {
+        const int hsel = idx / half, i = idx % half;
+        if (hsel < grp) {
+            const int col = (kvh * grp + hsel) * head_dim + 2 * i;
+            const float a = sum_partials(partial, ks, n_total, r, col);
+            const float b = sum_partials(partial, ks, n_total, r, col + 1);
+            qbuf[(int64_t)r * QD + col] = tk_fmaf(-b, sn[i], a * cs[i]);
+            qbuf[(int64_t)r * QD + col + 1] = tk_fmaf(a, sn[i], b * cs[i]);
+        } else {
+            const int col = QD + kvh * head_dim + 2 * i;
+            const float a = sum_partials(partial, ks, n_total, r, col);
+            const float b = sum_partials(partial, ks, n_total, r, col + 1);
+            kvrow[2 * i] = tk_f16_to_f32(tk_f32_to_f16(tk_fmaf(-b, sn[i], a * cs[i])));
+            kvrow[2 * i + 1] = tk_f16_to_f32(tk_f32_to_f16(tk_fmaf(a, sn[i], b * cs[i])));
+            const int vcol = QD + KVD + kvh * head_dim + 2 * i;
+            kvrow[head_dim + 2 * i] = tk_f16_to_f32(tk_f32_to_f16(sum_partials(partial, ks, n_total, r, vcol)));
+            kvrow[head_dim + 2 * i + 1] = tk_f16_to_f32(tk_f32_to_f16(sum_partials(partial, ks, n_total, r, vcol + 1)));
+        }
+    }
+    __syncthreads();
+    const int nb = head_dim / TK_KV_Q8_BLOCK;
+    const int64_t row = (((int64_t)layer * max_seq + sq) * n_kv_head + kvh) * max_ctx + p; /* [layer][seq][kv head][ctx] */
+    for (int b = threadIdx.x; b < 2 * nb; b += blockDim.x) {
+        const bool is_v = b >= nb;
+        const int bb = is_v ? b - nb : b;
+        int8_t q[TK_KV_Q8_BLOCK];
+        const uint16_t d = tk_kv_q8_block(kvrow + (is_v ? head_dim : 0) + bb * TK_KV_Q8_BLOCK, q);
+        uint32_t w[TK_KV_Q8_BLOCK / 4];
+#pragma unroll
+        for (int i = 0; i < TK_KV_Q8_BLOCK / 4; ++i)
+            w[i] = (uint32_t)(uint8_t)q[4 * i] | ((uint32_t)(uint8_t)q[4 * i + 1] << 8) | ((uint32_t)(uint8_t)q[4 * i + 2] << 16) | ((uint32_t)(uint8_t)q[4 * i + 3] << 24);
+        uint4* dst = (uint4*)((is_v ? cache.vq : cache.kq) + row * head_dim + bb * TK_KV_Q8_BLOCK); /* 32-byte aligned: head_dim % 32 == 0 */
+        dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+        dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+        (is_v ? cache.vd : cache.kd)[row * nb + bb] = d;
+    }
+}
+
+void tk_launch_qkv_rope_append_q8(const float* partial, int ks, int n_total, int n_head, int n_kv_head, int head_dim, const float* rope_cos, const float* rope_sin,
+                                  const int32_t* seq, const int32_t* pos, int nrows, float* qbuf, TkKvQ8 cache, int layer, int max_seq, int max_ctx, hipStream_t s) {
+    hipLaunchKernelGGL(k_qkv_rope_append_q8, dim3(n_kv_head, nrows), dim3(256), (size_t)2 * head_dim * sizeof(float), s, partial, ks, n_total, n_head, n_kv_head, head_dim,
+                       rope_cos, rope_sin, seq, pos, qbuf, cache, layer, max_seq, max_ctx);
+}
+
 /* ------------------------------------------------------------------------------------------
  * causal GQA attention.  One workgroup per (row, KV head): it serves all GQ = n_head / n_kv_head query heads that share the KV head, so
  * the head's K and V rows are read ONCE per row, and they are read as what they are in the cache layout
@@ -3194,8 +3249,39 @@ __device__ __forceinline__ float far_score(const uint8_t* kr /* the key row in i
     return a * att_scale;
 }
 
-template <int GQ, int HD /* head_dim when it is 64 or 128, 0 = any */, int CH /* positions per ring slot: 32 or 64 */>
-__global__ __launch_bounds__(256) void k_attention_far(const float* __restrict__ qbuf, const uint16_t* __restrict__ kcache, const uint16_t* __restrict__ vcache,
+/* The same chain over a Q8_0 key row (common/tk_kv_q8.h): 16 int8 values per 16-byte piece, the value of an element = its block's scale (sc: the
+ * row's head_dim / 32 scales, widened) times the int8 — exact in fp32 —, where the f16 row widens a half */
+template <int HD>
+__device__ __forceinline__ float far_score_q8(const uint8_t* kr, const float* sc, const float* qh, int srr, int ppr, int swm, float att_scale) {
+    float a = 0.0f;
+    constexpr int KB = HD ? HD / 16 : 1;
+    for (int i0 = 0; i0 < ppr; i0 += KB) {
+        uint4 kv[KB];
+#pragma unroll
+        for (int u = 0; u < KB; ++u) kv[u] = *(const uint4*)(kr + (((i0 + u) ^ (srr & swm)) * 16));
+#pragma unroll
+        for (int u = 0; u < KB; ++u) {
+            const float d = sc[(i0 + u) >> 1];
+            const uint32_t kw[4] = {kv[u].x, kv[u].y, kv[u].z, kv[u].w};
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const float kf = d * (float)(int8_t)((kw[e >> 2] >> (8 * (e & 3))) & 0xffu);
+                a = tk_fmaf(qh[16 * (i0 + u) + e], kf, a);
+            }
+        }
+    }
+    return a * att_scale;
+}
+
+/* what k_attention_far reads: the f16 caches, or (Q8: kernel 6 of the attention plan) the Q8_0 cache's int8 values and f16 scales.  o32
+ * (optional, the probe's): the quotients before quantize_chunk8, [row][n_head * head_dim] */
+template <bool Q8> struct TkFarCache { const uint16_t* k; const uint16_t* v; };
+template <> struct TkFarCache<true> { const int8_t* k; const int8_t* v; const uint16_t* kd; const uint16_t* vd; float* o32; };
+#define TK_KV_Q8_MAX_NB 8 /* scales of a row: head_dim <= 256 */
+
+template <int GQ, int HD /* head_dim when it is 64 or 128, 0 = any */, int CH /* positions per ring slot: 32 or 64 */,
+          bool Q8 = false /* a Q8_0 cache: rows of head_dim bytes in the ring, the chunk's scales loaded plainly */>
+__global__ __launch_bounds__(256) void k_attention_far(const float* __restrict__ qbuf, const TkFarCache<Q8> cache,
                                                        const int32_t* __restrict__ seq, const int32_t* __restrict__ pos, int n_head, int n_kv_head, int head_dim_rt,
                                                        int layer, int max_seq, int max_ctx, TkActQ8 out) {
     static_assert(CH == 32 || CH == 64, "a head's CH scoring threads lie inside one wave; CH % 4 == 0 keeps the position classes aligned");
@@ -3205,19 +3291,23 @@ __global__ __launch_bounds__(256) void k_attention_far(const float* __restrict__
     const int kvh = hb * GQ / (n_head / n_kv_head);
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int p = pos[r], T = p + 1, sq = seq[r];
-    const int W = GQ * head_dim, rb = head_dim * 2, QD = n_head * head_dim;
+    const int W = GQ * head_dim, rb = Q8 ? head_dim : head_dim * 2, QD = n_head * head_dim;
     const int slot_bytes = CH * rb;
-    /* LDS: the ring (whose slots the epilogue's arrays take over), q, one chunk of probabilities (tk_attention_far_lds_bytes mirrors this) */
+    /* LDS: the ring (whose slots the epilogue's arrays take over), q, one chunk of probabilities, Q8: one chunk of value scales
+     * (tk_attention_far_lds_bytes mirrors this) */
     uint8_t* ring = att_lds;
     const int ring_bytes = 2 * slot_bytes, epi_bytes = (TK_ATT_TSPLIT * W + TK_ATT_TSPLIT * TK_ATT_MAX_GRP + W) * (int)sizeof(float);
     float* qs = (float*)(att_lds + (ring_bytes > epi_bytes ? ring_bytes : epi_bytes)); /* [GQ][head_dim] */
     float* pr = qs + W;                                                                /* [CH][GQ] */
+    uint16_t* vsc = (uint16_t*)(pr + CH * GQ);                                         /* Q8: [CH][head_dim / 32] */
     float* part = (float*)ring;
     float* lpart = part + TK_ATT_TSPLIT * W;
     float* obuf = lpart + TK_ATT_TSPLIT * TK_ATT_MAX_GRP;
     const int64_t run0 = (((int64_t)layer * max_seq + sq) * n_kv_head + kvh) * (int64_t)max_ctx * head_dim;
-    const uint16_t* krun = kcache + run0;
-    const uint16_t* vrun = vcache + run0;
+    const auto* krun = cache.k + run0;
+    const auto* vrun = cache.v + run0;
+    const int nb = head_dim / TK_KV_Q8_BLOCK; /* Q8: scales per row */
+    const int64_t srun0 = (((int64_t)layer * max_seq + sq) * n_kv_head + kvh) * (int64_t)max_ctx * nb;
     const int nchunk = (T + CH - 1) / CH;
     const int total = 3 * nchunk; /* the stream: K chunks 0 .. n - 1 (pass A), then K chunk c, V chunk c for c = 0 .. n - 1 (pass B) */
     const int last_row = max_ctx - 1;
@@ -3225,13 +3315,47 @@ __global__ __launch_bounds__(256) void k_attention_far(const float* __restrict__
     auto issue = [&](int j) {
         const bool is_k = j < nchunk || ((j - nchunk) & 1) == 0;
         const int c = j < nchunk ? j : (j - nchunk) >> 1;
-        att_stage(is_k ? krun : vrun, c * CH, last_row, rb, ring + (j % 2) * slot_bytes, is_k, wave, lane, CH);
+        att_stage((const uint16_t*)(is_k ? krun : vrun), c * CH, last_row, rb, ring + (j % 2) * slot_bytes, is_k, wave, lane, CH);
     };
     /* before touching chunk j: it has landed; everybody is done with chunk j - 1, whose slot takes chunk j + 1 */
     auto acquire = [&](int j) {
         wait_vmcnt(0);
         __syncthreads();
         if (j + 1 < total) issue(j + 1);
+    };
+    /* Q8: the same for key chunk c, whose scales the scoring thread of a row loads itself — requested BEFORE the next chunk's DMA, so that
+     * waiting for them does not wait for that; rows past the window are clamped (never used) */
+    float ksc[TK_KV_Q8_MAX_NB];
+    auto acquire_k = [&](int j, int c, bool with_v) {
+        if constexpr (Q8) {
+            wait_vmcnt(0);
+            __syncthreads();
+            int gr = c * CH + (t % CH);
+            gr = gr < last_row ? gr : last_row;
+            const uint16_t* sp = cache.kd + srun0 + (int64_t)gr * nb;
+            uint16_t hs[TK_KV_Q8_MAX_NB];
+#pragma unroll
+            for (int b = 0; b < TK_KV_Q8_MAX_NB; ++b) hs[b] = b < nb ? sp[b] : (uint16_t)0;
+            /* pass B: value chunk c's scales as well, [CH][nb] halves (at most two per thread), into LDS beside the probabilities */
+            uint16_t vs[2] = {0, 0};
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int i = t + 256 * u;
+                if (with_v && i < CH * nb) {
+                    int vr = c * CH + i / nb;
+                    vr = vr < last_row ? vr : last_row;
+                    vs[u] = cache.vd[srun0 + (int64_t)vr * nb + i % nb];
+                }
+            }
+            if (j + 1 < total) issue(j + 1);
+#pragma unroll
+            for (int b = 0; b < TK_KV_Q8_MAX_NB; ++b) ksc[b] = f16bits_to_f32(hs[b]);
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                if (with_v && t + 256 * u < CH * nb) vsc[t + 256 * u] = vs[u];
+        } else {
+            acquire(j);
+        }
     };
 
     issue(0);
@@ -3244,8 +3368,12 @@ __global__ __launch_bounds__(256) void k_attention_far(const float* __restrict__
     /* ---- pass A: the per-head maximum ---- */
     float m = -INFINITY;
     for (int j = 0; j < nchunk; ++j) {
-        acquire(j); /* the first barrier also publishes qs */
-        if (scorer && j * CH + srr < T) m = tk_fmaxf(m, far_score<HD>(ring + (j % 2) * slot_bytes + srr * rb, qh, srr, ppr, swm, att_scale));
+        acquire_k(j, j, false); /* the first barrier also publishes qs */
+        if constexpr (Q8) {
+            if (scorer && j * CH + srr < T) m = tk_fmaxf(m, far_score_q8<HD>(ring + (j % 2) * slot_bytes + srr * rb, ksc, qh, srr, ppr, swm, att_scale));
+        } else {
+            if (scorer && j * CH + srr < T) m = tk_fmaxf(m, far_score<HD>(ring + (j % 2) * slot_bytes + srr * rb, qh, srr, ppr, swm, att_scale));
+        }
     }
     for (int s = CH / 2; s >= 1; s >>= 1) m = tk_fmaxf(m, wave_xor_f(m, s)); /* over the CH lanes of one head: every one of them ends with it */
 
@@ -3255,15 +3383,20 @@ __global__ __launch_bounds__(256) void k_attention_far(const float* __restrict__
     for (int h = 0; h < GQ; ++h) { l[h] = 0.0f; acc[h][0][0] = acc[h][0][1] = acc[h][1][0] = acc[h][1][1] = 0.0f; }
     for (int c = 0; c < nchunk; ++c) {
         const int jk = nchunk + 2 * c;
-        acquire(jk); /* every wave is past the PV of chunk c - 1: pr may be overwritten */
-        if (scorer && c * CH + srr < T) pr[srr * GQ + sh] = tk_expf(far_score<HD>(ring + (jk % 2) * slot_bytes + srr * rb, qh, srr, ppr, swm, att_scale) - m);
-        acquire(jk + 1); /* publishes pr */
+        acquire_k(jk, c, true); /* every wave is past the PV of chunk c - 1: pr (and vsc) may be overwritten */
+        if constexpr (Q8) {
+            if (scorer && c * CH + srr < T) pr[srr * GQ + sh] = tk_expf(far_score_q8<HD>(ring + (jk % 2) * slot_bytes + srr * rb, ksc, qh, srr, ppr, swm, att_scale) - m);
+        } else {
+            if (scorer && c * CH + srr < T) pr[srr * GQ + sh] = tk_expf(far_score<HD>(ring + (jk % 2) * slot_bytes + srr * rb, qh, srr, ppr, swm, att_scale) - m);
+        }
+        acquire(jk + 1); /* publishes pr (and vsc) */
         const uint8_t* slot = ring + ((jk + 1) % 2) * slot_bytes;
         const int t_end = T - c * CH < CH ? T - c * CH : CH;
         constexpr int PB = 4; /* k_attention's batches: dead slots of the last one read a clamped row and enter with probability 0 */
         for (int rr0 = wave; rr0 < t_end; rr0 += PB * TK_ATT_TSPLIT) {
             float pb[PB][GQ];
             uint32_t vv[PB][2];
+            float vd[PB][2]; /* Q8: the scale of this lane's two dims (2 lane and 2 lane + 1 share a block) */
 #pragma unroll
             for (int u = 0; u < PB; ++u) {
                 const int rr = rr0 + u * TK_ATT_TSPLIT;
@@ -3278,7 +3411,12 @@ __global__ __launch_bounds__(256) void k_attention_far(const float* __restrict__
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
                     const int d0 = 2 * lane + 128 * db;
-                    vv[u][db] = d0 < head_dim ? *(const uint32_t*)(slot + rc * rb + d0 * 2) : 0u;
+                    if constexpr (Q8) {
+                        vv[u][db] = d0 < head_dim ? (uint32_t)*(const uint16_t*)(slot + rc * rb + d0) : 0u;
+                        vd[u][db] = d0 < head_dim ? f16bits_to_f32(vsc[rc * nb + d0 / TK_KV_Q8_BLOCK]) : 0.0f;
+                    } else {
+                        vv[u][db] = d0 < head_dim ? *(const uint32_t*)(slot + rc * rb + d0 * 2) : 0u;
+                    }
                 }
             }
 #pragma unroll
@@ -3286,7 +3424,14 @@ __global__ __launch_bounds__(256) void k_attention_far(const float* __restrict__
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
                     if (2 * lane + 128 * db < head_dim) {
-                        const float v0 = f16bits_to_f32(vv[u][db] & 0xffffu), v1 = f16bits_to_f32(vv[u][db] >> 16);
+                        float v0, v1;
+                        if constexpr (Q8) {
+                            v0 = vd[u][db] * (float)(int8_t)(vv[u][db] & 0xffu);
+                            v1 = vd[u][db] * (float)(int8_t)((vv[u][db] >> 8) & 0xffu);
+                        } else {
+                            v0 = f16bits_to_f32(vv[u][db] & 0xffffu);
+                            v1 = f16bits_to_f32(vv[u][db] >> 16);
+                        }
 #pragma unroll
                         for (int h = 0; h < GQ; ++h) {
                             acc[h][db][0] = tk_fmaf(pb[u][h], v0, acc[h][db][0]);
@@ -3318,6 +3463,7 @@ __global__ __launch_bounds__(256) void k_attention_far(const float* __restrict__
         const float a = ((part[i] + part[W + i]) + part[2 * W + i]) + part[3 * W + i];
         const float ll = ((lpart[h] + lpart[TK_ATT_MAX_GRP + h]) + lpart[2 * TK_ATT_MAX_GRP + h]) + lpart[3 * TK_ATT_MAX_GRP + h];
         obuf[i] = tk_divf(a, ll);
+        if constexpr (Q8) { if (cache.o32) cache.o32[(int64_t)r * QD + hb * W + i] = obuf[i]; }
     }
     __syncthreads();
     for (int c = t; c < W / 8; c += 256) {
@@ -4078,6 +4224,60 @@ __global__ __launch_bounds__(TK_KV_COPY_THREADS) void k_kv_copy_rows(const TkKvC
     for (; w < words; w += stride) dp[w] = sp[w];
 }
 
+/* The same copy on a Q8_0 cache (common/tk_kv_q8.h): a (descriptor, layer, kv_head) has FOUR contiguous runs — K values, V values, n * head_dim
+ * bytes each, 16-byte aligned (head_dim % 16 == 0), and K scales, V scales, n * head_dim / 16 bytes each, 4-byte aligned (head_dim % 64 == 0: an
+ * even number of halves per row).  blockIdx.x names the run; a value run strides over 16-byte words as above, a scale run over 4-byte ones. */
+__global__ __launch_bounds__(TK_KV_COPY_THREADS) void k_kv_copy_rows_q8(const TkKvCopyDesc* __restrict__ desc, int ndesc, TkKvQ8 cache, int n_layer, int n_kv_head, int max_seq,
+                                                                        int max_ctx, int head_dim) {
+    int run = (int)blockIdx.x;
+    const int kvh = run % n_kv_head; run /= n_kv_head;
+    const int layer = run % n_layer; run /= n_layer;
+    const int d = run >> 2, which = run & 3; /* 0 K values, 1 V values, 2 K scales, 3 V scales */
+    if (d >= ndesc) return;
+    const TkKvCopyDesc ds = desc[d];
+    if (ds.src_seq < 0 || ds.src_seq >= max_seq || ds.dst_seq < 0 || ds.dst_seq >= max_seq || ds.src_seq == ds.dst_seq || ds.p0 < 0 || ds.n <= 0 ||
+        ds.n > max_ctx - ds.p0)
+        return;
+    const size_t srow = (((size_t)layer * max_seq + ds.src_seq) * n_kv_head + kvh) * max_ctx + ds.p0;
+    const size_t drow = (((size_t)layer * max_seq + ds.dst_seq) * n_kv_head + kvh) * max_ctx + ds.p0;
+    const int stride = (int)gridDim.y * TK_KV_COPY_THREADS;
+    int w = (int)blockIdx.y * TK_KV_COPY_THREADS + (int)threadIdx.x;
+    if (which < 2) {
+        int8_t* base = which ? cache.vq : cache.kq;
+        const v4i* __restrict__ sp = (const v4i*)(base + srow * head_dim);
+        v4i* __restrict__ dp = (v4i*)(base + drow * head_dim);
+        const int words = ds.n * (head_dim / 16);
+        for (; w + (TK_KV_COPY_UNROLL - 1) * stride < words; w += TK_KV_COPY_UNROLL * stride) {
+            v4i t[TK_KV_COPY_UNROLL];
+#pragma unroll
+            for (int u = 0; u < TK_KV_COPY_UNROLL; ++u) t[u] = sp[w + u * stride];
+#pragma unroll
+            for (int u = 0; u < TK_KV_COPY_UNROLL; ++u) dp[w + u * stride] = t[u];
+        }
+        for (; w < words; w += stride) dp[w] = sp[w];
+    } else {
+        uint16_t* base = which == 3 ? cache.vd : cache.kd;
+        const int nb = head_dim / TK_KV_Q8_BLOCK;
+        const uint32_t* __restrict__ sp = (const uint32_t*)(base + srow * nb);
+        uint32_t* __restrict__ dp = (uint32_t*)(base + drow * nb);
+        const int words = ds.n * (nb / 2);
+        for (; w < words; w += stride) dp[w] = sp[w];
+    }
+}
+
+bool tk_launch_kv_copy_rows_q8(const TkKvCopyDesc* desc, int ndesc, int max_n, TkKvQ8 cache, int n_layer, int n_kv_head, int head_dim, int max_seq, int max_ctx,
+                               hipStream_t s) {
+    if (ndesc < 0 || ndesc > TK_MAX_ROWS || max_n < 0 || max_n > max_ctx || head_dim % 64 != 0 || n_layer < 1 || n_kv_head < 1) return false;
+    const long runs = ndesc > 0 ? 4L * ndesc * n_layer * n_kv_head : 1;
+    const long sweep = (long)TK_KV_COPY_THREADS * TK_KV_COPY_UNROLL;
+    const long need = std::max(1L, ((long)max_n * (head_dim / 16) + sweep - 1) / sweep);
+    const long want = (8L * TK_NUM_CU + runs - 1) / runs;
+    const long gy = std::min(std::min(need, want), 65535L);
+    hipLaunchKernelGGL(k_kv_copy_rows_q8, dim3((unsigned)runs, (unsigned)std::max(1L, gy)), dim3(TK_KV_COPY_THREADS), 0, s, desc, ndesc, cache, n_layer, n_kv_head, max_seq, max_ctx,
+                       head_dim);
+    return hipGetLastError() == hipSuccess;
+}
+
 bool tk_launch_kv_copy_rows(const TkKvCopyDesc* desc, int ndesc, int max_n, uint16_t* kcache, uint16_t* vcache, int n_layer, int n_kv_head, int head_dim, int max_seq,
                             int max_ctx, hipStream_t s) {
     if (ndesc < 0 || ndesc > TK_MAX_ROWS || max_n < 0 || max_n > max_ctx || head_dim % 8 != 0 || n_layer < 1 || n_kv_head < 1) return false;
@@ -4251,7 +4451,7 @@ static const TkAttentionKernel k_attention_fns[3][2][3][3] = {
 
 /* [gq 1, 2, 4][head_dim any, 64, 128][chunk 32, 64]: a group of one head exists only at head_dim 256, half a group of 4 only where 2 x head_dim
  * fills 256s; the run-time head_dim instantiation stands in for a pair no geometry of TkLlmModel::init reaches */
-typedef void (*TkAttentionFarKernel)(const float*, const uint16_t*, const uint16_t*, const int32_t*, const int32_t*, int, int, int, int, int, int, TkActQ8);
+typedef void (*TkAttentionFarKernel)(const float*, const TkFarCache<false>, const int32_t*, const int32_t*, int, int, int, int, int, int, TkActQ8);
 static const TkAttentionFarKernel k_attention_far_fns[3][3][2] = {
     {{k_attention_far<1, 0, 32>, k_attention_far<1, 0, 64>}, {k_attention_far<1, 0, 32>, k_attention_far<1, 0, 64>}, {k_attention_far<1, 0, 32>, k_attention_far<1, 0, 64>}},
     {{k_attention_far<2, 0, 32>, k_attention_far<2, 0, 64>}, {k_attention_far<2, 0, 32>, k_attention_far<2, 0, 64>}, {k_attention_far<2, 128, 32>, k_attention_far<2, 128, 64>}},
@@ -4266,7 +4466,8 @@ void tk_launch_attention(const float* qbuf, const float* partial, int ks, int n_
         /* the far kernel only reads the cache: a pass that asks for the fused launch gets its rows roped and appended in front, the same bits */
         if (fused) tk_launch_qkv_rope_append(partial, ks, n_total, n_head, n_kv_head, head_dim, rope_cos, rope_sin, seq, pos, nrows, const_cast<float*>(qbuf), kcache, vcache, layer, max_seq, max_ctx, s);
         const TkAttentionFarKernel k = k_attention_far_fns[pl.gq == 4 ? 2 : pl.gq - 1][head_dim == 128 ? 2 : head_dim == 64 ? 1 : 0][pl.chunk == 64];
-        hipLaunchKernelGGL(k, dim3(n_head / pl.gq, nrows), dim3(256), pl.lds_bytes, s, qbuf, kcache, vcache, seq, pos, n_head, n_kv_head, head_dim, layer, max_seq, max_ctx, out);
+        hipLaunchKernelGGL(k, dim3(n_head / pl.gq, nrows), dim3(256), pl.lds_bytes, s, qbuf, TkFarCache<false>{kcache, vcache}, seq, pos, n_head, n_kv_head, head_dim, layer, max_seq,
+                           max_ctx, out);
         return;
     }
     if (pl.kernel == 1) {
@@ -4278,6 +4479,45 @@ void tk_launch_attention(const float* qbuf, const float* partial, int ks, int n_
     const TkAttentionKernel k = k_attention_fns[gq == 4 ? 2 : gq - 1][fused][head_dim == 128 ? 2 : head_dim == 64 ? 1 : 0][chunk == 128 ? 2 : chunk == 64 ? 1 : 0];
     hipLaunchKernelGGL(k, dim3(n_head / gq, nrows), dim3(256), pl.lds_bytes, s, qbuf, partial, ks, n_total, rope_cos, rope_sin, kcache, vcache, seq, pos,
                        n_head, n_kv_head, head_dim, layer, max_seq, max_ctx, out);
+}
+
+/* Kernel 6 of the attention plan: k_attention_far<.., Q8> — the far form's workgroups, ring and passes over a Q8_0 cache (common/tk_kv_q8.h), for
+ * every pass of a Q8_0 session, whatever its window.  Same table as the f16 far form; gq and the slot size follow the same two rules.  A ring
+ * slot holds CH rows of head_dim BYTES: CH * head_dim / 1024 one-KiB pieces, 2 at head_dim 64 and 32-position slots — att_stage hands piece pc to
+ * wave pc % 4, so waves 2 and 3 then issue none, which the kernel's waits (all vmcnt(0)) allow. */
+typedef void (*TkAttentionFarQ8Kernel)(const float*, const TkFarCache<true>, const int32_t*, const int32_t*, int, int, int, int, int, int, TkActQ8);
+static const TkAttentionFarQ8Kernel k_attention_far_q8_fns[3][3][2] = {
+    {{k_attention_far<1, 0, 32, true>, k_attention_far<1, 0, 64, true>}, {k_attention_far<1, 0, 32, true>, k_attention_far<1, 0, 64, true>}, {k_attention_far<1, 0, 32, true>, k_attention_far<1, 0, 64, true>}},
+    {{k_attention_far<2, 0, 32, true>, k_attention_far<2, 0, 64, true>}, {k_attention_far<2, 0, 32, true>, k_attention_far<2, 0, 64, true>}, {k_attention_far<2, 128, 32, true>, k_attention_far<2, 128, 64, true>}},
+    {{k_attention_far<4, 0, 32, true>, k_attention_far<4, 0, 64, true>}, {k_attention_far<4, 64, 32, true>, k_attention_far<4, 64, 64, true>}, {k_attention_far<4, 128, 32, true>, k_attention_far<4, 128, 64, true>}},
+};
+
+static size_t tk_attention_far_q8_lds_bytes(int gq, int head_dim, int chunk) {
+    const size_t W = (size_t)gq * head_dim;
+    const size_t ring = (size_t)2 * chunk * head_dim;
+    const size_t epilogue = ((size_t)TK_ATT_TSPLIT * W + TK_ATT_TSPLIT * TK_ATT_MAX_GRP + W) * sizeof(float); /* aliases the ring */
+    return (ring > epilogue ? ring : epilogue) + (W + (size_t)chunk * gq) * sizeof(float) + (size_t)chunk * (head_dim / TK_KV_Q8_BLOCK) * 2; /* q, probabilities, value scales */
+}
+
+TkAttentionPlan tk_attention_plan_q8(int nrows, int n_head, int n_kv_head, int head_dim) {
+    TkAttentionPlan pl{};
+    int gq = n_head / n_kv_head;
+    if (gq == 4 && (2 * head_dim) % 256 == 0 && nrows * n_kv_head < 2 * TK_NUM_CU) gq = 2;
+    pl.kernel = 6; pl.gq = gq; pl.chunk = (n_head / gq) * nrows > 4 * TK_NUM_CU ? 32 : 64; pl.slots = 2; pl.far = true;
+    pl.lds_bytes = tk_attention_far_q8_lds_bytes(gq, head_dim, pl.chunk);
+    return pl;
+}
+
+bool tk_launch_attention_q8(const float* qbuf, TkKvQ8 cache, const int32_t* seq, const int32_t* pos, int nrows, int n_head, int n_kv_head, int head_dim, int layer,
+                            int max_seq, int max_ctx, TkActQ8 out, float* o32, hipStream_t s) {
+    if (nrows < 1 || nrows > TK_MAX_ROWS || n_kv_head < 1 || n_head % n_kv_head || head_dim < 64 || head_dim > 256 || head_dim % 64) return false;
+    const int grp = n_head / n_kv_head;
+    if ((grp != 1 && grp != 2 && grp != 4) || (grp * head_dim) % 256) return false;
+    const TkAttentionPlan pl = tk_attention_plan_q8(nrows, n_head, n_kv_head, head_dim);
+    const TkAttentionFarQ8Kernel k = k_attention_far_q8_fns[pl.gq == 4 ? 2 : pl.gq - 1][head_dim == 128 ? 2 : head_dim == 64 ? 1 : 0][pl.chunk == 64];
+    hipLaunchKernelGGL(k, dim3(n_head / pl.gq, nrows), dim3(256), pl.lds_bytes, s, qbuf, TkFarCache<true>{cache.kq, cache.vq, cache.kd, cache.vd, o32}, seq, pos, n_head, n_kv_head,
+                       head_dim, layer, max_seq, max_ctx, out);
+    return true;
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -4641,6 +4881,7 @@ const char* tk_llm_prepare_device(int device) {
     for (TkGemm32Kernel fn : k_gemm32_fns) opt(fn);
     for (const auto& f3 : k_attention_fns) for (const auto& f2 : f3) for (const auto& f1 : f2) for (TkAttentionKernel fn : f1) opt(fn);
     for (const auto& f2 : k_attention_far_fns) for (const auto& f1 : f2) for (TkAttentionFarKernel fn : f1) opt(fn);
+    for (const auto& f2 : k_attention_far_q8_fns) for (const auto& f1 : f2) for (TkAttentionFarQ8Kernel fn : f1) opt(fn);
     opt(k_attention_narrow);
     opt(k_attention_prefill<128>);
     opt(k_attention_prefill<64>);

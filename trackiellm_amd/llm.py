@@ -225,12 +225,18 @@ def matmul_float_probe(ttype, w, K, ks, x, seg_rows=None, device=0):
     return y
 
 
-def attention_plan(nrows, n_head, n_kv_head, head_dim, max_ctx, fused=True, device=0, top_position=None):
+KV_F16, KV_Q8_0 = 0, 1
+
+
+def attention_plan(nrows, n_head, n_kv_head, head_dim, max_ctx, fused=True, device=0, top_position=None, kv_type=0):
     """the attention launch a pass takes on `device`: (kernel, query heads per workgroup, positions per slot / resident chunk, slots);
     kernel 0 = k_attention, 1 = k_attention_narrow, 2 = k_attention_prefill, 3 = the long-context decode form, 5 = k_attention_far (tk_mi355x_attention_plan;
-    with top_position — the pass's highest position — tk_mi355x_attention_plan_at: the session's per-pass choice)"""
+    with top_position — the pass's highest position — tk_mi355x_attention_plan_at: the session's per-pass choice); kv_type = KV_Q8_0: kernel 6, the far
+    form over a Q8_0 cache, for every pass of such a session (tk_mi355x_attention_plan_kv)"""
     out = (C.c_int32 * 4)()
-    if top_position is None:
+    if kv_type != 0:
+        check(lib().tk_mi355x_attention_plan_kv(device, nrows, n_head, n_kv_head, head_dim, max_ctx, 1 if fused else 0, int(kv_type), out))
+    elif top_position is None:
         check(lib().tk_mi355x_attention_plan(device, nrows, n_head, n_kv_head, head_dim, max_ctx, 1 if fused else 0, out))
     else:
         check(lib().tk_mi355x_attention_plan_at(device, nrows, n_head, n_kv_head, head_dim, max_ctx, 1 if fused else 0, int(top_position), out))
@@ -428,11 +434,31 @@ class LlmModel:
 
 
 class LlmSession:
-    def __init__(self, model, max_seq, max_ctx):
+    def __init__(self, model, max_seq, max_ctx, kv_type=0):
+        """kv_type: KV_F16, or KV_Q8_0 = the KV cache as ggml Q8_0 blocks, 17/32 of the bytes (tk_mi355x_llm_session_create_kv)"""
         self.model = model
         self.vocab = model.hparams.vocab
+        self.kv_type = int(kv_type)
         self.h = C.c_void_p()
-        check(lib().tk_mi355x_llm_session_create(C.byref(self.h), model.h, max_seq, max_ctx))
+        if self.kv_type == 0:
+            check(lib().tk_mi355x_llm_session_create(C.byref(self.h), model.h, max_seq, max_ctx))
+        else:
+            check(lib().tk_mi355x_llm_session_create_kv(C.byref(self.h), model.h, max_seq, max_ctx, self.kv_type))
+
+    def kv_bytes(self):
+        """bytes of the session's cache arrays, keys and values"""
+        f = lib().tk_mi355x_llm_session_kv_bytes
+        f.restype, f.argtypes = C.c_uint64, [C.c_void_p]
+        return int(f(self.h))
+
+    def kv_read_q8(self, layer, seq, pos0, n_pos):
+        """the raw rows of a Q8_0 session: (k int8 [n_pos][n_kv_head][head_dim], k scale bits uint16 [n_pos][n_kv_head][head_dim / 32], v, v scales)"""
+        hp = self.model.hparams
+        kq = np.empty((n_pos, hp.n_kv_head, hp.head_dim), np.int8)
+        kd = np.empty((n_pos, hp.n_kv_head, hp.head_dim // 32), np.uint16)
+        vq, vd = np.empty_like(kq), np.empty_like(kd)
+        check(lib().tk_mi355x_llm_session_kv_read_q8(self.h, layer, seq, pos0, n_pos, _p(kq), _p(kd), _p(vq), _p(vd)))
+        return kq, kd, vq, vd
 
     def forward(self, seq, pos, tok, want_logits=True):
         seq = np.ascontiguousarray(seq, dtype=np.int32)
@@ -676,6 +702,61 @@ class LlmSession:
             pass
 
 
+class KvQ8Probe(C.Structure):
+    """tk_mi355x_kv_q8_probe_t (include/tk/tk_mi355x_ext.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("mode", "n_layer", "max_seq", "n_kv_head", "max_ctx", "head_dim", "layer", "nrows", "n_head")] + \
+               [(n, C.c_void_p) for n in ("seq", "pos", "kq", "vq", "kd", "vd")] + [("n_values", C.c_int64), ("n_scales", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("k16", "v16", "q", "out")] + [("n_rows_elems", C.c_int64)]
+
+
+def kv_q8_probe_into(mode, kq, kd, vq, vd, seq, pos, layer=0, k16=None, v16=None, q=None, out=None, device=0, head_dim=None, n_values=None, n_scales=None,
+                     n_rows_elems=None):
+    """tk_mi355x_kv_q8_probe in place.  kq / vq: int8 [n_layer][max_seq][n_kv_head][max_ctx][head_dim], kd / vd: uint16 [...][max_ctx][head_dim / 32]
+    (None passes NULL; the geometry then comes from the first array given).  mode 0: k16 / v16 uint16 [nrows][n_kv_head][head_dim] are quantised
+    into the rows (seq[r], pos[r]) of `layer`.  mode 1: q float32 [nrows][n_head][head_dim] -> out, the attention over positions 0 .. pos[r].
+    device >= 0: one production launch; device < 0: the host loops.  head_dim / n_values / n_scales / n_rows_elems override what the arrays say"""
+    shape = next(a.shape for a in (kq, vq) if a is not None) if (kq is not None or vq is not None) else None
+    if shape is None:
+        sd = next(a.shape for a in (kd, vd) if a is not None)
+        shape = sd[:4] + (sd[4] * 32,)
+    for a, dt in ((kq, np.int8), (vq, np.int8), (kd, np.uint16), (vd, np.uint16), (k16, np.uint16), (v16, np.uint16), (q, np.float32), (out, np.float32)):
+        if a is not None and (a.dtype != dt or not a.flags.c_contiguous):
+            raise ValueError("kv_q8_probe_into: arrays must be C-contiguous and of their type")
+    seq = np.ascontiguousarray(seq, dtype=np.int32)
+    pos = np.ascontiguousarray(pos, dtype=np.int32)
+    rows = k16 if mode == 0 else q
+    p = KvQ8Probe()
+    p.mode, p.layer, p.nrows = int(mode), int(layer), int(seq.size)
+    p.n_layer, p.max_seq, p.n_kv_head, p.max_ctx = (int(x) for x in shape[:4])
+    p.head_dim = int(shape[4] if head_dim is None else head_dim)
+    p.n_head = int(q.shape[1]) if q is not None and q.ndim == 3 else int(shape[2])
+    p.seq, p.pos = _p(seq), _p(pos)
+    p.kq, p.vq, p.kd, p.vd = _p(kq), _p(vq), _p(kd), _p(vd)
+    p.n_values = int(n_values if n_values is not None else min(a.size for a in (kq, vq) if a is not None) if (kq is not None or vq is not None) else 0)
+    p.n_scales = int(n_scales if n_scales is not None else min(a.size for a in (kd, vd) if a is not None) if (kd is not None or vd is not None) else 0)
+    p.k16, p.v16, p.q, p.out = _p(k16), _p(v16), _p(q), _p(out)
+    p.n_rows_elems = int(n_rows_elems if n_rows_elems is not None else 0 if rows is None else rows.size)
+    f = lib().tk_mi355x_kv_q8_probe
+    f.argtypes = [C.c_int, C.POINTER(KvQ8Probe)]
+    check(f(int(device), C.byref(p)))
+
+
+def kv_q8_quantize_probe(kq, kd, vq, vd, seq, pos, k16, v16, layer=0, device=0):
+    """mode 0 on COPIES of the cache arrays: returns (kq, kd, vq, vd) with the rows written"""
+    c = [np.array(a, copy=True) for a in (kq, kd, vq, vd)]
+    kv_q8_probe_into(0, c[0], c[1], c[2], c[3], seq, pos, layer=layer, k16=np.ascontiguousarray(k16, dtype=np.uint16), v16=np.ascontiguousarray(v16, dtype=np.uint16),
+                     device=device)
+    return tuple(c)
+
+
+def kv_q8_attention_probe(kq, kd, vq, vd, seq, pos, q, layer=0, device=0, fill=np.nan):
+    """mode 1: the attention of q [nrows][n_head][head_dim] over the cache arrays; returns out, pre-filled with `fill`"""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    out = np.full(q.shape, fill, np.float32)
+    kv_q8_probe_into(1, kq, kd, vq, vd, seq, pos, layer=layer, q=q, out=out, device=device)
+    return out
+
+
 def kv_shift_probe(kcache, vcache, rope_cos, rope_sin, seq, p0, p1, delta, device=0):
     """ONE launch of k_kv_shift_rows (tk_mi355x_kv_shift_probe) on COPIES of kcache / vcache (uint16 f16 bits, [n_layer][max_seq][n_kv_head][max_ctx]
     [head_dim]), which are returned; rope_cos / rope_sin float32 [max_ctx][head_dim / 2]; device < 0: the same per-row function in a host loop.  A
@@ -811,6 +892,19 @@ class ModelLoader:
     def set_runner_slots(handle, slots):
         """sequences per shared decode session of the runners created on this model handle (before the first tk_llm_runner_create)"""
         check(lib().tk_mi355x_llm_model_set_runner_slots(handle, slots))
+
+    @staticmethod
+    def set_kv_cache_type(handle, kv_type):
+        """the KV cache type of the sessions the runners of this model handle share: KV_F16 / KV_Q8_0, or llama.cpp's names "f16" / "q8_0"; before
+        the first tk_llm_runner_create on the handle"""
+        if isinstance(kv_type, str):
+            f = lib().tk_mi355x_llm_model_set_kv_cache_type_by_name
+            f.argtypes = [C.c_void_p, C.c_char_p]
+            check(f(handle, kv_type.encode()))
+        else:
+            f = lib().tk_mi355x_llm_model_set_kv_cache_type
+            f.argtypes = [C.c_void_p, C.c_int]
+            check(f(handle, int(kv_type)))
 
     @staticmethod
     def batch_stats(handle):
