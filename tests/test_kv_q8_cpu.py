@@ -156,6 +156,25 @@ def test_lossless_rows_quantise_without_loss():
     assert np.array_equal(e, np.round(e)) and e.min() >= -10 and e.max() <= -4
 
 
+DEEP_KEY_EXPONENTS = (-14, -10)  # the key rows of the deep session tests (tests/test_kv_q8_deep_gpu.py)
+
+
+def test_lossless_rows_of_another_exponent_range_quantise_without_loss():
+    """the range the deep session tests take for their key rows, and the widest one lossless_rows accepts: quantise, dequantise, identical; the
+    default range draws what it drew before the argument existed"""
+    for lo, hi in (DEEP_KEY_EXPONENTS, (-14, 8)):
+        rows = R.lossless_rows((7, 3, 2, 256), 5, exponents=(lo, hi))
+        q, d = R.quantize(rows)
+        assert not R.inverse_overflows(rows).any()
+        assert np.array_equal(R.value(q, d), rows.view(np.float16).astype(np.float32))
+        assert (np.abs(q.reshape(7, 3, 2, 8, 32)).max(axis=-1) == 127).all()
+        e = np.log2(d.view(np.float16).astype(np.float64))
+        assert np.array_equal(e, np.round(e)) and e.min() == lo and e.max() == hi
+    assert np.array_equal(R.lossless_rows((5, 2, 64), 3), R.lossless_rows((5, 2, 64), 3, exponents=(-10, -4)))
+    same_draws = R.lossless_rows((5, 2, 64), 3, exponents=(-11, -5)).view(np.float16).astype(np.float64) * 2.0
+    assert np.array_equal(same_draws, R.lossless_rows((5, 2, 64), 3).view(np.float16).astype(np.float64))
+
+
 @pytest.mark.parametrize("head_dim", HEAD_DIMS)
 def test_quantiser_equals_the_restatement_on_seeded_rows(tk, head_dim):
     seq, pos = np.array([0, 2, 2, 1], np.int32), np.array([0, 39, 7, 20], np.int32)
@@ -241,6 +260,105 @@ def test_host_attention_reads_only_the_rows_positions_and_heads_it_is_given(tk):
             one = [np.ascontiguousarray(a[1:2, seq[r]:seq[r] + 1, kvh:kvh + 1]) for a in (kq, kd, vq, vd)]
             alone = tk.kv_q8_attention_probe(*one, [0], [pos[r]], q[r:r + 1, kvh * gq:(kvh + 1) * gq], device=-1)
             assert np.array_equal(got[r, kvh * gq:(kvh + 1) * gq].view(np.uint32), alone[0].view(np.uint32)), (r, kvh)
+
+
+# ---- the host loop at depth ---------------------------------------------------------------------------------------------------------------------
+
+DEEP_FROM = 3000  # a row of a deep probe pass at or above this position is a deep row
+
+
+def one_run(run, kvh, T):
+    """positions [0, T) of one KV head of general_run()'s arrays as a cache of one layer, one sequence and one KV head"""
+    return [np.ascontiguousarray(a[kvh, :T][None, None, None]) for a in run]
+
+
+@pytest.mark.parametrize("name", list(R.DEEP_PROBE))
+def test_deep_probe_rows_depend_on_their_deep_positions(tk, name):
+    """the condition under which the bit-for-bit comparison of tests/test_kv_q8_deep_gpu.py says something about deep positions, on the host loop
+    alone: for every deep row of every pass of the case (one KV head of it, row r takes head r % n_kv_head; the heads of a row share nothing) the
+    output bits of EVERY query head of the group change when the int8 values of the V row at T - 1 change, again when those of the V row at T / 2
+    do, and again when one K scale at T / 2 + 1 doubles.  Holds at DEEP_K_SCALE = 0.6, the key scale of the other attention tests: the scores'
+    standard deviation is 0.6 whatever the head_dim (|q| = sqrt(head_dim), times 0.6 / sqrt(head_dim)), a softmax close to flat over thousands of
+    positions.  Host cost: 4 runs x group x T x head_dim x 2 fmas per deep row, 0.6 G fmas for the largest case"""
+    (nh, nkv, hd), W = R.DEEP_PROBE[name]
+    grp = nh // nkv
+    runs = {s: R.general_run((nh, nkv, hd), W, s) for s in (0, 1)}
+    seen = set()
+    for i, (seq, pos) in enumerate(R.probe_passes(name)):
+        q = R.probe_q(name, i, seq.size, nh, hd)
+        for r in np.flatnonzero(pos >= DEEP_FROM):
+            T, kvh = int(pos[r]) + 1, int(r) % nkv
+            if (int(seq[r]), T, kvh) in seen:   # the same run under another q: shown once
+                continue
+            seen.add((int(seq[r]), T, kvh))
+            cache = one_run(runs[int(seq[r])], kvh, T)
+            qr = np.ascontiguousarray(q[r:r + 1, kvh * grp:(kvh + 1) * grp])
+            last = tk.kv_q8_attention_probe(*cache, [0], [T - 1], qr, device=-1, fill=np.float32(-77.0))
+            assert np.isfinite(last).all() and (last != -77.0).all()
+            for what in ("V row at T - 1", "V row at T / 2", "K scale at T / 2 + 1"):
+                if what == "K scale at T / 2 + 1":
+                    assert 0 < cache[1][0, 0, 0, T // 2 + 1, 0] < 0x7800
+                    cache[1][0, 0, 0, T // 2 + 1, 0] += 0x0400   # the next power of two
+                else:
+                    t = T - 1 if what == "V row at T - 1" else T // 2
+                    cache[2][0, 0, 0, t] = ~cache[2][0, 0, 0, t]
+                    cache[2][0, 0, 0, t][cache[2][0, 0, 0, t] == -128] = 127   # values a quantised row can hold
+                out = tk.kv_q8_attention_probe(*cache, [0], [T - 1], qr, device=-1, fill=np.float32(-77.0))
+                moved = (out.view(np.uint32) != last.view(np.uint32)).reshape(grp, hd).any(axis=1)
+                assert moved.all(), (name, i, int(r), T, what, moved.tolist())
+                last = out
+    assert len(seen) >= (1 if W == 32768 else 5)
+
+
+def float64_attention(q, k, v):
+    """-> (out, bound, scale), [gq][head_dim] float64: the attention of q [gq][hd] over the dequantised k, v [T][hd], the forward bound of
+    tk_kv_q8_attention_row's fp32 arithmetic on it, and the size of what an output sums, sum_t p_t |v_t| (see the test below)"""
+    from nn_row_ref import EXPF_REL, SQRT_REL, U
+    T, hd = k.shape
+    scale = 1.0 / np.sqrt(np.float64(hd))
+    s = (k @ q.T) * scale                                                                       # [T][gq]
+    s_err = hd * U * (np.abs(k) @ np.abs(q).T) * scale + np.abs(s) * (SQRT_REL + 2 * U)
+    top = s.argmax(axis=0)
+    dlt = s - s.max(axis=0)
+    assert dlt.min() > -80.0                                                                    # tk_expf flushes nothing
+    e = np.exp(dlt)
+    p = e / e.sum(axis=0)
+    out = p.T @ v
+    terms = p.T @ np.abs(v)                                                                     # sum_t p_t |v_t|
+    eta = np.abs(dlt) * U + s_err + s_err[top, np.arange(q.shape[0])]                           # relative error of a probability from its exponent
+    from_scores = (p * eta).T @ np.abs(v) + (p * eta).sum(axis=0)[:, None] * terms              # numerator and denominator, first order
+    return out, (T / 4 + 5) * U * terms + EXPF_REL * terms + from_scores, terms
+
+
+@pytest.mark.parametrize("T", (8448, 32768))
+def test_host_attention_loop_at_depth_lies_within_a_derived_bound_of_float64(tk, T):
+    """one (row, KV head) of g2_d128 — two query heads, head_dim 128 — over T positions of general rows, against a float64 NumPy attention over
+    R.value(q, scale): scores, max, exp, PV, division.  The bound per output element, first order in U = 2^-24, has three parts:
+
+      PV     an output is N / l; N is four interleaved fma chains of T / 4 terms by position mod 4, joined by three adds, then one division: a term
+             passes through at most T / 4 + 5 roundings, so |error| <= (T / 4 + 5) U sum_t |p_t v_t| (p_t = e_t / l; the element values d * q are exact)
+      exp    tk_expf's documented relative error 2^-22 on every e_t: 2^-22 sum_t |p_t v_t|
+      score  a score is a chain of head_dim fmas times att_scale = tk_divf(1, tk_sqrtf(head_dim)): |error| <= head_dim U sum_i |q_i k_ti| att_scale
+             + |s_t| (2^-23 + 2 U), as nn_row_ref.attend1_64 has it; with the rounding of s_t - m and the same error of the maximum it is the
+             relative error eta_t of e_t, which enters the numerator as sum_t p_t eta_t |v_t| and the denominator as (sum_t p_t eta_t) sum_t p_t |v_t|
+
+    The bound must itself stay below 1e-3 of the output's scale sum_t p_t |v_t| — the size of what the output sums; the output is smaller, its terms
+    cancel — so that a loose bound cannot hide an error: at T = 32 768 the PV part alone is 4.9e-4 of it.  Measured (printed):
+    T = 8448: max error 3.3e-08, bound 1.95e-04 .. 2.17e-04, at most 2.7e-04 of the scale; T = 32 768: max error 5.4e-08, bound 4.87e-04 ..
+    5.13e-04, at most 6.4e-04 of the scale (outputs up to 0.033 and 0.018).  The errors of the chains average out; the bound is the worst case.
+    tests/test_kv_q8_deep_gpu.py ties the launch to this loop bit for bit."""
+    gq, head_dim = 2, 128
+    q, cache, k, v = attention_case(T, gq, head_dim, 23)
+    got = tk.kv_q8_attention_probe(*cache, [0], [T - 1], q[None], device=-1, fill=np.float32(-77.0))[0].astype(np.float64)
+    want, bnd, scale = float64_attention(q.astype(np.float64), k, v)
+    err = np.abs(got - want)
+    print("T %d: max error %.3g, bound %.3g .. %.3g, bound / scale at most %.3g, max |out| %.3g" % (T, err.max(), bnd.min(), bnd.max(), (bnd / scale).max(), np.abs(want).max()))
+    assert np.isfinite(got).all() and (got != -77.0).all()
+    assert (bnd < 1e-3 * scale).all()
+    assert (err < bnd).all(), (T, float((err / bnd).max()))
+    # what the bound does see at this depth: the upper half of the window left out
+    half, _, _ = float64_attention(q.astype(np.float64), k[:T // 2], v[:T // 2])
+    assert (np.abs(got - half) > bnd).any()
 
 
 REFUSALS = ["null_kq", "null_kd", "null_vq", "null_vd", "null_rows", "head_dim_48", "values_short", "scales_short", "rows_short", "row_outside", "bad_mode", "null_q", "null_out",

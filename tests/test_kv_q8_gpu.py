@@ -80,7 +80,7 @@ class Rig:
 
     def __init__(self, gpu, geometry, zero_kv):
         self.gpu, self.geometry = gpu, geometry
-        nh, nkv, hd = G.GEOMETRIES[geometry]
+        nh, nkv, hd = G.GEOMETRIES[geometry] if isinstance(geometry, str) else geometry   # a name of the table, or (n_head, n_kv_head, head_dim)
         m = G.MODEL
         self.model = gpu.LlmModel(gpu.LlmHParams(m["n_layer"], m["d_model"], nh, nkv, hd, m["d_ff"], m["vocab"], 1e-5, 10000.0, 0, 0, 0, 0, 1)).fill_synthetic(4)
         self.hp = self.model.hparams
